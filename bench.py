@@ -2,7 +2,7 @@
 """bench.py -- the reference's headline metric on MI355X:
 "Mpaths/s + ms/frame, conference 1024^2, 4096 VPLs, 1/2/4/8 GPU" (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W [--workload ir|evplp|ppm|vsl] [--scene hard|easy] [--front-end ranks|group]
+    python bench.py --gpus N --steps K --warmup W [--workload ir|evplp|ppm|vsl] [--scene hard|easy] [--front-end ranks|group] [--dump-outputs DIR]
 
 A step = one iteration of the technique loop (rt/rtcomphoton/rtcomphoton.h:936-1068):
   ir    BASELINE config #2 (default, the headline): Instant Radiosity, 1024 light paths x 4 vertices = 4096 VPL record
@@ -105,13 +105,39 @@ def parse():
     ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements (configs #3-#5, other scene, 16384-slot variant, GPU path tracer, render_json)")
     ap.add_argument("--cpu-iters", type=int, default=0, help="path-tracer iterations of the CPU baseline sample (0 = auto, ~12 s)")
     ap.add_argument("--dump-frame", default="", help="rank 0 writes the assembled VPL + photon accumulators of the last frame to this .npy file (tests)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the last timed step computed -- the composite image and the accumulators, assembled over the ranks -- "
+                         "as DIR/<name>.npy in float32, at most 64 MB in all (a fixed, seeded sample of pixels when the frame is larger)")
     a = ap.parse_args()
     heavy = a.workload == "vsl"
     if a.steps is None:
         a.steps = 2 if heavy else 60       # default timed region: several seconds
     if a.warmup is None:
         a.warmup = 1 if heavy else 3
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     return a
+
+
+DUMP_BYTES = 64 * 10 ** 6               # --dump-outputs: all files together
+DUMP_SEED = 20261015                    # ... and the seed of the pixel sample of a larger frame
+
+
+def write_outputs(np, d, arrays):
+    """arrays: name -> (H, W, C) float32 frame.  Whole frames when they fit DUMP_BYTES, else the same seeded sample of pixels of
+    each, (K, C) in image-row order.  Returns the description the result line carries."""
+    os.makedirs(d, exist_ok=True)
+    H, W = next(iter(arrays.values())).shape[:2]
+    per_pixel = sum(v.shape[-1] * 4 for v in arrays.values())
+    room = DUMP_BYTES - 256 * len(arrays)              # (.npy headers)
+    sample = None
+    if H * W * per_pixel > room:
+        sample = np.sort(np.random.default_rng(DUMP_SEED).choice(H * W, room // per_pixel, replace=False))
+        arrays = {k: v.reshape(H * W, -1)[sample] for k, v in arrays.items()}
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
+    return {"dir": d, "arrays": {k: list(v.shape) for k, v in arrays.items()}, "dtype": "float32",
+            "pixels": "all" if sample is None else f"{sample.size} of {H * W}, numpy default_rng({DUMP_SEED}).choice without replacement, sorted"}
 
 
 def spawn_ranks(a):
@@ -489,6 +515,51 @@ def run_workload(env, wl, steps, warmup, scene, primary=True):
     if wl == "ppm":
         profile_passes(True)
     splat_pairs = (sum(c.pass_stats(ev.PASS_SPLAT)["shaded"] for c in ranks) - pairs_before) if wl != "ir" else 0
+
+    def assemble(t, ch=4):
+        # this rank's strip (or every rank's, all-gathered) -> the (H, W, ch) image: a rank's local rows are its blocks' rows
+        t = t.cpu().numpy().reshape(n_ranks if use_dist else 1, ctx.local_rows, W, ch)
+        img = np.zeros((H, W, ch), np.float32)
+        from evplp_amd import strips as _strips
+        for r in range(t.shape[0]):
+            blocks = _strips.blocks_of_rank(owner[0], r, block_cost[0]) if owner[0] is not None else np.arange(r, nblocks, t.shape[0])
+            gr = _strips.rows_of_blocks(H, blocks, SR, ctx.local_rows) if t.shape[0] > 1 else np.arange(ctx.local_rows)
+            ok = gr < H
+            img[gr[ok]] = t[r][ok]
+        return img
+
+    dumped = None
+    if a.dump_outputs and primary:
+        # what the last timed step computed, before anything else runs on these contexts: the composite as resolve() returns it
+        # (the scales of that step's present(); resolve and download settle the splat first) and the accumulators it was made from
+        scale = 1.0 / (warmup + steps)
+        outputs = {}
+        if group is not None:
+            outputs["image"] = group.resolve(scale, scale, 1.0, mask_emitter=True, gamma=True)
+            rows = [c.global_rows() for c in ranks]
+            for key, buf in (("vpl_accum", ev.BUF_VPL_ACCUM), ("photon_accum", ev.BUF_PHOTON_ACCUM)):
+                img = np.zeros((H, W, 4), np.float32)
+                for c, gr in zip(ranks, rows):
+                    ok = gr < H
+                    img[gr[ok]] = c.download(buf)[ok]
+                outputs[key] = img
+        else:
+            rgb = torch.from_numpy(ctx.resolve(scale, scale, 1.0, mask_emitter=True, gamma=True)).to(dev).reshape(-1)
+            rgb_full = torch.zeros(world * rgb.numel(), dtype=torch.float32, device=dev) if use_dist else rgb
+            if use_dist:
+                env.all_gather(rgb_full, rgb)
+                env.all_gather(full, strip)
+                if wl != "ir":
+                    env.all_gather(pfull, pstrip)
+            torch.cuda.synchronize(dev)
+            outputs["image"] = assemble(rgb_full, 3)
+            outputs["vpl_accum"], outputs["photon_accum"] = assemble(full), (assemble(pfull) if wl != "ir" else None)
+        if wl == "ir":
+            outputs.pop("photon_accum")            # (photon splat off)
+        if wl == "ppm":
+            outputs.pop("vpl_accum")               # (no VPLs)
+        if rank == 0:
+            dumped = write_outputs(np, a.dump_outputs, outputs)
     extra = min(10, len(jitters) - (warmup + steps))
     if wl == "ppm":
         for i in range(extra - 3):
@@ -540,16 +611,6 @@ def run_workload(env, wl, steps, warmup, scene, primary=True):
                 ok = gr < H
                 vp[gr[ok]] = c.download(ev.BUF_VPL_ACCUM)[ok]; pp[gr[ok]] = c.download(ev.BUF_PHOTON_ACCUM)[ok]
         else:
-            def assemble(t):
-                t = t.cpu().numpy().reshape(n_ranks if use_dist else 1, ctx.local_rows, W, 4)
-                img = np.zeros((H, W, 4), np.float32)
-                from evplp_amd import strips as _strips
-                for r in range(t.shape[0]):
-                    blocks = _strips.blocks_of_rank(owner[0], r, block_cost[0]) if owner[0] is not None else np.arange(r, nblocks, t.shape[0])
-                    gr = _strips.rows_of_blocks(H, blocks, SR, ctx.local_rows) if t.shape[0] > 1 else np.arange(ctx.local_rows)
-                    ok = gr < H
-                    img[gr[ok]] = t[r][ok]
-                return img
             if use_dist and (wl == "ppm" or a.exchange_every != 1):
                 env.all_gather(full, strip)
                 if wl != "ir":
@@ -585,6 +646,8 @@ def run_workload(env, wl, steps, warmup, scene, primary=True):
                        "shadow_rays_per_frame": rays / steps, "unoccluded_pairs_per_frame": shaded / steps,
                        "mrays_per_s": rays / dt / 1e6, "bvh_builder": acc.get("builder", a.bvh), "bvh": acc},
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if physical < n_ranks:
             out["config"]["note"] = f"{n_ranks} ranks share {physical} physical GPU(s): the N > 1 logic with the real kernels, not a scaling measurement"
         feeders = {k: (sum(v) / len(v) if v else None) for k, v in feeder_ms.items()}

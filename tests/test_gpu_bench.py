@@ -114,6 +114,33 @@ def test_bench_group_front_end(tmp_path):
     assert a[0].tobytes() == b[0].tobytes()
 
 
+def _outputs(d):
+    return {f[:-len(".npy")]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: what the last timed step computed, assembled over the ranks, as float32 .npy files -- the composite
+    resolve() returns and the accumulators it was made from (for config #2 the VPL frame --dump-frame writes); the same arguments
+    write the same bytes again; two ranks, under either front end, write the frame of one rank; the photon workloads add their
+    photon frame."""
+    one = run_bench(SMALL + ["--dump-outputs", str(tmp_path / "one"), "--dump-frame", str(tmp_path / "one.npy")])
+    assert one["dump_outputs"]["pixels"] == "all" and one["steps"] == 2
+    o = _outputs(tmp_path / "one")
+    run_bench(SMALL + ["--dump-outputs", str(tmp_path / "again")])
+    again = _outputs(tmp_path / "again")
+    assert sorted(again) == sorted(o) and all(again[k].tobytes() == o[k].tobytes() for k in o)
+    assert sorted(o) == ["image", "vpl_accum"] and o["image"].shape == (256, 256, 3) and o["vpl_accum"].shape == (256, 256, 4)
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in o.values()) and o["image"].max() > 0
+    assert o["vpl_accum"].tobytes() == np.load(tmp_path / "one.npy")[0].tobytes()
+    for name, extra, env in (("group", ["--front-end", "group"], None), ("gloo", [], {"EVPLP_BENCH_BACKEND": "gloo"})):
+        run_bench(SMALL + ["--gpus", "2", "--dump-outputs", str(tmp_path / name)] + extra, env)
+        t = _outputs(tmp_path / name)
+        assert t["vpl_accum"].tobytes() == o["vpl_accum"].tobytes() and t["image"].tobytes() == o["image"].tobytes(), name
+    ev = run_bench(["--workload", "evplp", "--steps", "3"] + SMALL[2:] + ["--dump-outputs", str(tmp_path / "evplp")])
+    e = _outputs(tmp_path / "evplp")
+    assert ev["steps"] == 3 and sorted(e) == ["image", "photon_accum", "vpl_accum"] and e["photon_accum"][..., :3].max() > 0
+
+
 def test_bench_default_extras_small():
     """The default line's extra objects (here at a small size): the path through evplp_render_json agrees with the timed loop, and
     configs #3 / #4 / #5 ride along with their rooflines."""

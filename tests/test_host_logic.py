@@ -202,12 +202,19 @@ def test_shipped_scene_files_carry_every_key_the_techniques_require():
     assert seen == len(files) == 30
 
 
-def test_lfs_pointer_meshes_are_reported_as_such(evplp):
-    f = "/root/reference/scene/conference/conference_ours.json"
-    if not os.path.exists(f):
-        pytest.skip("reference scenes not present here")
-    rc, msg = _render(evplp, f)
-    assert rc == evplp.ERR_IO and "Git-LFS pointer" in msg
+def test_lfs_pointer_meshes_are_reported_as_such(evplp, tmp_path):
+    """The reference's scene files name meshes that its repository holds as Git-LFS pointer stubs: a scene whose scene and
+    light meshes are such stubs is refused as an I/O error that says so."""
+    import hashlib
+    jp = evplp.synth_scene(str(tmp_path), "room", 600, 1, 32, 32)
+    root = json.load(open(jp))
+    meshes = list(root["scene"]) + [root["arealight"]["obj"]]
+    for m in meshes:
+        p = tmp_path / m
+        data = p.read_bytes()
+        p.write_text(f"version https://git-lfs.github.com/spec/v1\noid sha256:{hashlib.sha256(data).hexdigest()}\nsize {len(data)}\n")
+    rc, msg = _render(evplp, jp)
+    assert rc == evplp.ERR_IO and "Git-LFS pointer" in msg and meshes[0] in msg
 
 
 def test_deal_blocks_balances_and_is_deterministic(evplp):
