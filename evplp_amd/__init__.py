@@ -81,7 +81,8 @@ class GroupConfig(C.Structure):
                 ("partition", C.c_int32), ("strip_capacity_pct", C.c_int32), ("split_light_paths", C.c_int32), ("reserved", C.c_int32)]
 
 
-PARTITION_STRIPS, PARTITION_BANDS = 0, 1
+PARTITION_STRIPS, PARTITION_BANDS, PARTITION_ITERATIONS = 0, 1, 2
+PARTITIONS = {"strips": PARTITION_STRIPS, "bands": PARTITION_BANDS, "iterations": PARTITION_ITERATIONS}
 
 
 class PassStats(C.Structure):
@@ -156,6 +157,8 @@ _SIGNATURES = {
     "evplp_group_splat_photons": (C.c_int, [_P, C.POINTER(FrameParams), C.c_int32]),
     "evplp_group_path_trace": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_int32]),
     "evplp_group_synchronize": (C.c_int, [_P]),
+    "evplp_group_select_rank": (C.c_int, [_P, C.c_int32]),
+    "evplp_group_synchronize_rank": (C.c_int, [_P, C.c_int32]),
     "evplp_group_host_stats": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double * 3)]),
     "evplp_group_rebalance": (C.c_int, [_P, _P]),
     "evplp_group_calibrate": (C.c_int, [_P, C.c_int32]),
@@ -544,7 +547,9 @@ def rank_blocks(costs, owner, rank: int) -> np.ndarray:
 
 
 class Group:
-    """evplp_group: n row-strip ranks driven by one thread (RCCL across distinct GPUs, device copies for virtual ranks)."""
+    """evplp_group: n ranks driven by one thread (RCCL across distinct GPUs, device copies for virtual ranks) that share out the image
+    (partition "strips" / "bands") or the iterations of a progressive run ("iterations": select_rank() picks the rank the passes go to,
+    present() / resolve() sum the ranks' accumulators on the GPUs)."""
 
     def __init__(self, res_x, res_y, num_light_paths, num_vpl_light_paths, photons_per_path, n_ranks, devices=None, strip_rows=0,
                  use_rccl=False, deterministic=False, bvh_builder=BVH_SAH, overlap_light_tracing=False, partition="strips", strip_capacity_pct=0, split_light_paths=0, cut_scratch_bytes=0, vsl_mask_bytes=0):
@@ -556,8 +561,10 @@ class Group:
         cfg.bvh_builder = bvh_builder; cfg.deterministic = int(deterministic); cfg.overlap_light_tracing = int(overlap_light_tracing)
         cfg.cut_scratch_bytes = int(cut_scratch_bytes); cfg.vsl_mask_bytes = int(vsl_mask_bytes)
         gc = GroupConfig(); gc.n_ranks = n_ranks; gc.strip_rows = strip_rows; gc.use_rccl = int(use_rccl)
-        gc.partition = PARTITION_BANDS if partition == "bands" else PARTITION_STRIPS; gc.strip_capacity_pct = int(strip_capacity_pct); gc.split_light_paths = int(split_light_paths)
-        self.partition = partition if n_ranks > 1 else "strips"
+        if partition not in PARTITIONS:
+            raise ValueError(f"partition: one of {sorted(PARTITIONS)}, got {partition!r}")
+        gc.partition = PARTITIONS[partition]; gc.strip_capacity_pct = int(strip_capacity_pct); gc.split_light_paths = int(split_light_paths)
+        self.partition = partition if n_ranks > 1 or partition == "iterations" else "strips"
         self._devs = (C.c_int32 * n_ranks)(*devices) if devices is not None else None
         gc.devices = C.cast(self._devs, C.POINTER(C.c_int32)) if self._devs is not None else None
         h = C.c_void_p()
@@ -611,6 +618,14 @@ class Group:
     def synchronize(self):
         self._check(self._lib.evplp_group_synchronize(self._h))
 
+    def select_rank(self, r: int):
+        """iterations partition: the rank the pass calls go to from now on"""
+        self._check(self._lib.evplp_group_select_rank(self._h, r))
+
+    def synchronize_rank(self, r: int):
+        """wait for rank r's worker and its context's streams only"""
+        self._check(self._lib.evplp_group_synchronize_rank(self._h, r))
+
     def rebalance(self) -> np.ndarray:
         """bands partition: move the band boundaries to equal measured cost (clears the accumulators); returns the n + 1 boundaries.
         strips partition: deal the blocks by the cost clocked since calibrate() (block_owners() has the result)"""
@@ -639,7 +654,8 @@ class Group:
         return {"calls_ms": out[0], "exchange_ms": out[1], "commands": int(out[2])}
 
     def present(self, vpl_scale=1.0, photon_scale=1.0, light_scale=1.0, mask_emitter=False, gamma=False, exchange=True):
-        """composite + all-gather of the strips on the devices (the per-frame exchange); nothing comes to the host.  exchange=False: the composite alone"""
+        """composite + all-gather of the strips on the devices (the per-frame exchange; iterations partition: the reduction); nothing comes to the host.
+        exchange=False: the composite alone (iterations partition: of the selected rank's own accumulators)"""
         self._check(self._lib.evplp_group_present_ex(self._h, vpl_scale, photon_scale, light_scale, int(mask_emitter), int(gamma), int(exchange)))
 
     def rank(self, r: int) -> "Context":
@@ -648,7 +664,8 @@ class Group:
         h = self._lib.evplp_group_context(self._h, r)
         if not h:
             raise EvplpError(ERR_INVALID, "evplp_group_context: bad rank")
-        c = Context.borrowed(h, self.W, self.H, strip_rank=r, strip_count=self.n, strip_rows=self.strip_rows,
+        whole = self.partition == "iterations"       # (every rank holds the whole image)
+        c = Context.borrowed(h, self.W, self.H, strip_rank=0 if whole else r, strip_count=1 if whole else self.n, strip_rows=self.strip_rows,
                              num_light_paths=self._paths[0], num_vpl_light_paths=self._paths[1], photons_per_path=self._paths[2])
         if self.partition == "bands":
             b = getattr(self, "_bands", None)
@@ -658,6 +675,8 @@ class Group:
             c.cfg.strip_rank, c.cfg.strip_count = 0, 1
             c.cfg.band_first_row = int(b[r]); c.cfg.band_rows = int((b[r + 1] if r + 1 < self.n else (self.H + 15) // 16 * 16) - b[r])
         return c
+
+    context = rank
 
     def resolve(self, vpl_scale=1.0, photon_scale=1.0, light_scale=1.0, mask_emitter=False, gamma=False):
         out = np.empty((self.H, self.W, 3), dtype=np.float32)

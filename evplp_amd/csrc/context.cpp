@@ -995,6 +995,12 @@ int resolve_to_device(evplp_context *c, float vs, float ps, float ls, int32_t ma
                    (const float4 *)c->buf[EVPLP_BUF_LIGHT], vs, ps, ls, mask_emitter, gamma, c->d_rgb, c->stream);
     return pass_end(c, EVPLP_PASS_RESOLVE);
 }
+// every pending photon splat has its verdict (and its re-run, if its bins overflowed, is enqueued): the accumulators are final in
+// stream order (the reduction of an EVPLP_PARTITION_ITERATIONS group reads them)
+int settle(evplp_context *c) {
+    CTX_CHECK(c);
+    return settle_splat(c);
+}
 } // namespace evplp
 
 extern "C" int evplp_resolve(evplp_context *c, float vs, float ps, float ls, int32_t mask_emitter, int32_t gamma, float *out_rgb) {

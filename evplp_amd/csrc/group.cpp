@@ -5,6 +5,11 @@
 // xGMI, one communicator per GPU; the library is opened at run time so that hosts without it can still use single contexts).  Ranks that
 // share one device ("virtual ranks": tests, single-GPU boxes) exchange by device-to-device copies instead.
 //
+// EVPLP_PARTITION_ITERATIONS shares out the ITERATIONS of a progressive run instead of the image: every rank is a whole-image context,
+// the single-rank pass calls go to the rank evplp_group_select_rank chose, and a written frame is the rank-order sum of the ranks'
+// accumulators, formed on every GPU by reduce_shards_kernel (kernels_splat.hip) -- from an all-gather into a staging buffer (RCCL) or
+// straight from the peers' planes (virtual ranks).
+//
 // (round 5) ONE WORKER THREAD PER RANK.  Until round 4 the caller's thread issued every rank's launches in turn: at eight ranks that is
 // ~50 enqueue calls per iteration against config #4's 0.15-0.6 ms iteration -- the host, not the GPUs, would have set that
 // configuration's pace.  Now a group call only POSTS a small command record to each rank's single-producer ring (no lock taken by a
@@ -36,6 +41,7 @@
 
 namespace evplp {
 int resolve_to_device(evplp_context *c, float vs, float ps, float ls, int32_t mask_emitter, int32_t gamma, bool settle);   // context.cpp
+int settle(evplp_context *c);                                                                                                  // context.cpp
 }
 
 namespace {
@@ -55,7 +61,7 @@ struct Rccl {
     }
 };
 
-enum Op { OP_QUIT = 0, OP_CLEAR, OP_SYNC, OP_PRIMARY, OP_TRACE, OP_GATHER, OP_SPLAT, OP_PATH_TRACE, OP_PRESENT, OP_LOAD_SCENE, OP_SET_PROXY, OP_ASSEMBLE };
+enum Op { OP_QUIT = 0, OP_CLEAR, OP_SYNC, OP_PRIMARY, OP_TRACE, OP_GATHER, OP_SPLAT, OP_PATH_TRACE, OP_PRESENT, OP_LOAD_SCENE, OP_SET_PROXY, OP_ASSEMBLE, OP_REDUCE };
 // One posted call: plain data, copied into the ring (pointers must stay valid until the caller has drained: load_scene, set_proxy, resolve do)
 struct Cmd {
     int op = OP_QUIT;
@@ -116,6 +122,13 @@ struct evplp_group {
     uint32_t *d_owner = nullptr;            // rank 0's device: [image blocks] rank << 16 | local block (assemble_strips_kernel)
     int strip_rows = 16, image_blocks = 0, cap_blocks = 0;
     size_t strip_floats_cap = 0;            // d_frame's chunk size (the capacity); strip_floats <= it is what an exchange moves
+    // EVPLP_PARTITION_ITERATIONS: every rank renders whole frames; the pass calls go to `selected`; a present with exchange / a resolve sums
+    // the ranks' planes (OP_REDUCE).  sums_fresh (caller's thread): no pass was posted since the last reduction -- the cached sums still hold
+    bool iterations = false; int selected = 0; bool sums_fresh = false;
+    size_t plane_px = 0;                    // W * local_rows: the pixels of one accumulator plane
+    std::vector<float4 *> d_sum;            // per rank: [3][plane_px] VPL, photon and light planes reduced over the ranks (the first reduction)
+    std::vector<float4 *> d_stage;          // per rank, RCCL only: [n][plane_px] one plane of every rank (all-gathered)
+    std::vector<int> num_cus;               // per rank: the reduction's grid
     std::vector<Worker *> workers;
     SpinBarrier barrier;
     std::atomic<int> failed{ 0 };           // some rank has failed: collectives are skipped by everybody
@@ -163,7 +176,76 @@ static void worker_all_gather(Worker *w, float *recv, size_t count, const std::v
     if (e != hipSuccess) worker_fail(w, EVPLP_ERR_HIP, hipGetErrorString(e));
 }
 
+// EVPLP_PARTITION_ITERATIONS: the three accumulator planes of every rank summed -- VPL and photon in rank order in fp32, light as the first
+// non-zero pixel in rank order -- into this rank's d_sum, then composited from there.  cmd.i[3] = 0: no pass since the last reduction, the
+// cached sums are composited again and nothing is exchanged.  The planes are read through the contexts' CURRENT buffer pointers.
+static const int kSumPlanes[3] = { EVPLP_BUF_VPL_ACCUM, EVPLP_BUF_PHOTON_ACCUM, EVPLP_BUF_LIGHT };
+static void worker_reduce(Worker *w, const Cmd &cmd) {
+    evplp_group *g = w->g; const int r = w->rank; evplp_context *c = g->ctx[(size_t)r];
+    const size_t px = g->plane_px;
+    const bool exchange = cmd.i[3] != 0;
+    auto ok = [&] { return w->status.load(std::memory_order_relaxed) == 0; };
+    auto hip_fail = [&](hipError_t e) { (void)hipGetLastError(); worker_fail(w, e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP, hipGetErrorString(e)); };
+    const double t0 = now_ms();
+    if (exchange && ok()) {
+        const int rc = evplp::settle(c);                   // (the sums must be exact: every splat has its verdict, a re-run is enqueued)
+        if (rc < 0) worker_fail(w, rc, evplp_last_error(c));
+        hipError_t e = hipSuccess;
+        if (ok() && !g->d_sum[(size_t)r]) e = hipMalloc((void **)&g->d_sum[(size_t)r], sizeof(float4) * 3 * px);
+        if (e == hipSuccess && ok() && !g->virtual_ranks && !g->d_stage[(size_t)r]) e = hipMalloc((void **)&g->d_stage[(size_t)r], sizeof(float4) * (size_t)g->n * px);
+        if (e != hipSuccess) hip_fail(e);
+    }
+    if (!exchange && ok() && !g->d_sum[(size_t)r]) worker_fail(w, EVPLP_ERR_INVALID, "evplp_group_resolve: no reduction to composite");
+    const double t1 = now_ms();
+    if (exchange) {            // (reached by every rank, failed or not: the barrier decides for all)
+        float4 *sum = g->d_sum[(size_t)r];
+        evplp::ShardPlanes src; std::memset(&src, 0, sizeof(src));
+        if (g->n == 1 && g->virtual_ranks) {               // one rank: its planes, copied in stream order
+            if (ok()) for (int k = 0; k < 3; k++) {
+                src.p[0] = (const float4 *)c->buf[kSumPlanes[k]];
+                evplp::launch_reduce_shards(src, 1, k == 2, px, sum + (size_t)k * px, g->num_cus[(size_t)r], c->stream);
+            }
+        } else if (g->virtual_ranks) {
+            // every rank's planes are final when its stream is idle; nobody writes them again before every reader has finished (second barrier)
+            hipError_t e = ok() ? hipStreamSynchronize(c->stream) : hipSuccess;
+            if (e != hipSuccess) hip_fail(e);
+            if (g->barrier.wait(&g->failed) == 0) {
+                for (int k = 0; k < 3; k++) {
+                    for (int q = 0; q < g->n; q++) src.p[q] = (const float4 *)g->ctx[(size_t)q]->buf[kSumPlanes[k]];
+                    evplp::launch_reduce_shards(src, g->n, k == 2, px, sum + (size_t)k * px, g->num_cus[(size_t)r], c->stream);
+                }
+                e = hipGetLastError();
+                if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+                g->barrier.wait();
+                if (e != hipSuccess) hip_fail(e);
+            }
+        } else if (g->barrier.wait(&g->failed) == 0) {
+            // distinct devices: one plane at a time all-gathered into the staging buffer, then reduced from there (stream order; no
+            // ncclAllReduce: its association is not fixed)
+            float4 *stage = g->d_stage[(size_t)r];
+            for (int q = 0; q < g->n; q++) src.p[q] = stage + (size_t)q * px;
+            for (int k = 0; k < 3; k++) {
+                ncclResult_t nr = g->rccl.AllGather(c->buf[kSumPlanes[k]], stage, px * 4, ncclFloat, g->comms[(size_t)r], c->stream);
+                if (nr != ncclSuccess) worker_fail(w, EVPLP_ERR_HIP, g->rccl.GetErrorString(nr));
+                evplp::launch_reduce_shards(src, g->n, k == 2, px, sum + (size_t)k * px, g->num_cus[(size_t)r], c->stream);
+            }
+            hipError_t e = hipGetLastError();
+            if (e != hipSuccess) hip_fail(e);
+        }
+        w->t_exchange += now_ms() - t1;
+    }
+    const double t2 = now_ms();
+    if (ok()) {
+        const float4 *sum = g->d_sum[(size_t)r];
+        evplp::launch_resolve(c->st, sum, sum + px, sum + 2 * px, cmd.f[0], cmd.f[1], cmd.f[2], cmd.i[0], cmd.i[1], c->d_rgb, c->stream);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) hip_fail(e);
+    }
+    w->t_calls += (t1 - t0) + (now_ms() - t2); w->n_cmds++;
+}
+
 static void worker_run(Worker *w, const Cmd &cmd) {
+    if (cmd.op == OP_REDUCE) { worker_reduce(w, cmd); return; }
     evplp_group *g = w->g; const int r = w->rank; evplp_context *c = g->ctx[(size_t)r];
     const bool collective = (cmd.op == OP_PRESENT && cmd.i[3] != 0) || (cmd.op == OP_TRACE && g->split_paths);
     int rc = EVPLP_OK;
@@ -196,8 +278,9 @@ static void worker_run(Worker *w, const Cmd &cmd) {
             hipSetDevice(g->device[0]);
             const size_t frame_floats = (size_t)c->st.W * c->st.H * 3;
             hipError_t e = hipSuccess;
-            if (!g->d_assembled) e = hipMalloc((void **)&g->d_assembled, sizeof(float) * frame_floats);
-            if (e == hipSuccess) {
+            if (g->iterations) e = hipMemcpyAsync(cmd.out, c->d_rgb, frame_floats * sizeof(float), hipMemcpyDeviceToHost, c->stream);   // (whole-image ranks: rows in image order)
+            else if (!g->d_assembled) e = hipMalloc((void **)&g->d_assembled, sizeof(float) * frame_floats);
+            if (e == hipSuccess && !g->iterations) {
                 evplp::launch_assemble_strips(c->st, g->n, g->bands ? &g->band_table : nullptr, g->owner.empty() ? nullptr : g->d_owner, (int)(g->strip_floats / ((size_t)c->st.W * 3)), g->d_frame[0], g->d_assembled, c->stream);
                 e = hipMemcpyAsync(cmd.out, g->d_assembled, frame_floats * sizeof(float), hipMemcpyDeviceToHost, c->stream);
             }
@@ -265,6 +348,14 @@ static int post_all(evplp_group *g, const Cmd &cmd) {
     for (Worker *w : g->workers) post(w, cmd);
     return EVPLP_OK;
 }
+// a pass call: every rank (strips, bands), or the selected rank alone (EVPLP_PARTITION_ITERATIONS; the cached sums are stale from here on)
+static int post_pass(evplp_group *g, const Cmd &cmd) {
+    if (!g->iterations) return post_all(g, cmd);
+    g->sums_fresh = false;
+    if (g->failed.load(std::memory_order_acquire)) { drain(g); return group_status(g); }
+    post(g->workers[(size_t)g->selected], cmd);
+    return EVPLP_OK;
+}
 // calls whose arguments must outlive them, or whose result the caller needs: post, wait until every worker is idle, report
 static int post_and_wait(evplp_group *g, const Cmd &cmd) {
     int rc = post_all(g, cmd);
@@ -290,7 +381,27 @@ static int check_frame_params(evplp_group *g, const evplp_frame_params *fp, cons
 
 extern "C" const char *evplp_group_last_error(const evplp_group *g) { return g ? g->error : g_group_create_error; }
 extern "C" int evplp_group_size(const evplp_group *g) { return g ? g->n : EVPLP_ERR_INVALID; }
-extern "C" evplp_context *evplp_group_context(evplp_group *g, int32_t rank) { return (g && rank >= 0 && rank < g->n) ? g->ctx[(size_t)rank] : nullptr; }
+extern "C" evplp_context *evplp_group_context(evplp_group *g, int32_t rank) {
+    if (!g || rank < 0 || rank >= g->n) return nullptr;
+    g->sums_fresh = false;                 // (the caller may write the accumulators through it)
+    return g->ctx[(size_t)rank];
+}
+extern "C" int evplp_group_select_rank(evplp_group *g, int32_t rank) {
+    GRP_CHECK(g);
+    if (!g->iterations) { g->set_error("evplp_group_select_rank: the group shares out the image (strips / bands): every pass runs on every rank"); return EVPLP_ERR_INVALID; }
+    if (rank < 0 || rank >= g->n) { g->set_error("evplp_group_select_rank: rank %d out of range (%d ranks)", rank, g->n); return EVPLP_ERR_INVALID; }
+    g->selected = rank;
+    return EVPLP_OK;
+}
+extern "C" int evplp_group_synchronize_rank(evplp_group *g, int32_t rank) {
+    GRP_CHECK(g);
+    if (rank < 0 || rank >= g->n) { g->set_error("evplp_group_synchronize_rank: rank %d out of range (%d ranks)", rank, g->n); return EVPLP_ERR_INVALID; }
+    if (g->failed.load(std::memory_order_acquire)) { drain(g); return group_status(g); }
+    Cmd c; c.op = OP_SYNC;
+    post(g->workers[(size_t)rank], c);
+    drain_one(g->workers[(size_t)rank]);
+    return group_status(g);
+}
 extern "C" int evplp_group_host_stats(evplp_group *g, int32_t rank, double out[3]) {
     GRP_CHECK(g);
     if (rank < 0 || rank >= g->n || !out) { g->set_error("evplp_group_host_stats: bad arguments"); return EVPLP_ERR_INVALID; }
@@ -312,6 +423,7 @@ extern "C" void evplp_group_destroy(evplp_group *g) {
     for (Worker *w : g->workers) { if (w->th.joinable()) w->th.join(); delete w; }
     g->workers.clear();
     for (int r = 0; r < (int)g->d_frame.size(); r++) if (g->d_frame[(size_t)r]) { hipSetDevice(g->device[(size_t)r]); hipFree(g->d_frame[(size_t)r]); }
+    for (int r = 0; r < (int)g->d_sum.size(); r++) if (g->d_sum[(size_t)r] || g->d_stage[(size_t)r]) { hipSetDevice(g->device[(size_t)r]); hipFree(g->d_sum[(size_t)r]); hipFree(g->d_stage[(size_t)r]); }
     if (g->d_assembled || g->d_owner) { hipSetDevice(g->device[0]); hipFree(g->d_assembled); hipFree(g->d_owner); }
     for (ncclComm_t c : g->comms) if (c && g->rccl.CommDestroy) g->rccl.CommDestroy(c);
     for (evplp_context *c : g->ctx) { c->quiesce = nullptr; evplp_destroy(c); }
@@ -337,6 +449,9 @@ extern "C" int evplp_group_create(const evplp_config *cfg, const evplp_group_con
     // nothing any more and the cheaper cuts win at every rank count (single-GPU projection of config #2, profiles/r06_strip_projection.json:
     // n = 8, 8- / 16-row blocks: slowest rank 8.49 / 8.06 ms; n = 4: 14.97 / 14.60).
     const int strip_rows = gc->strip_rows > 0 ? gc->strip_rows : 16;
+    if (gc->partition < EVPLP_PARTITION_STRIPS || gc->partition > EVPLP_PARTITION_ITERATIONS) { delete g; return fail(EVPLP_ERR_INVALID, "evplp_group_create: partition %d unknown", gc->partition); }
+    g->iterations = gc->partition == EVPLP_PARTITION_ITERATIONS;
+    if (g->iterations && gc->split_light_paths > 0) { delete g; return fail(EVPLP_ERR_INVALID, "evplp_group_create: split_light_paths = 1 with EVPLP_PARTITION_ITERATIONS (every rank traces its own iteration's paths)"); }
     // EVPLP_PARTITION_BANDS: contiguous bands of equal height to begin with (multiples of 16 rows), each with room for twice its share
     g->bands = gc->partition == EVPLP_PARTITION_BANDS && g->n > 1;
     const int rows16 = ((cfg->res_y + 15) / 16) * 16, share = std::max(16, ((rows16 / g->n + 15) / 16) * 16), band_cap = std::min(rows16, 2 * share);
@@ -350,6 +465,7 @@ extern "C" int evplp_group_create(const evplp_config *cfg, const evplp_group_con
             const int nb = (cfg->res_y + strip_rows - 1) / strip_rows, share = (nb + g->n - 1) / g->n, pct = gc->strip_capacity_pct > 0 ? std::max(gc->strip_capacity_pct, 100) : 150;
             c.strip_capacity_rows = g->n > 1 ? std::min(nb, (share * pct + 99) / 100) * strip_rows : 0;
         }
+        if (g->iterations) { c.strip_rank = 0; c.strip_count = 1; c.strip_capacity_rows = 0; }     // a whole-image context, as on one GPU
         if (g->bands) {
             c.strip_rank = 0; c.strip_count = 1; c.strip_rows = 0;
             c.band_first_row = g->band_table.first[r]; c.band_rows = (r + 1 < g->n ? g->band_table.first[r + 1] : rows16) - g->band_table.first[r]; c.band_capacity_rows = band_cap;
@@ -366,8 +482,13 @@ extern "C" int evplp_group_create(const evplp_config *cfg, const evplp_group_con
     g->strip_floats = g->bands || g->n == 1 ? g->strip_floats_cap
                                             : (size_t)((g->image_blocks + g->n - 1) / g->n) * (size_t)g->strip_rows * g->ctx[0]->st.W * 3;
     g->d_frame.assign((size_t)g->n, nullptr);
+    g->plane_px = (size_t)g->ctx[0]->st.W * g->ctx[0]->st.local_rows;
+    g->d_sum.assign((size_t)g->n, nullptr); g->d_stage.assign((size_t)g->n, nullptr); g->num_cus.assign((size_t)g->n, 256);
     for (int r = 0; r < g->n; r++) {
         hipSetDevice(g->device[(size_t)r]);
+        int cus = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, g->device[(size_t)r]) == hipSuccess && cus > 0) g->num_cus[(size_t)r] = cus;
+        if (g->iterations) continue;      // (no strips to all-gather; the reduction's buffers come with the first reduction)
         hipError_t e = hipMalloc((void **)&g->d_frame[(size_t)r], sizeof(float) * g->strip_floats_cap * (size_t)g->n);
         if (e != hipSuccess) { int code = fail(EVPLP_ERR_OOM, "rank %d: hipMalloc(frame): %s", r, hipGetErrorString(e)); evplp_group_destroy(g); return code; }
     }
@@ -382,7 +503,7 @@ extern "C" int evplp_group_create(const evplp_config *cfg, const evplp_group_con
     // every rank (identical records, no exchange); large ones are split by path range and shared by one all-gather
     // (round 6: until round 5 the rule was "sets of >= 16 384 paths are split".  Config #4 at four ranks: 75 000 paths take 0.24 ms where 300 000
     // take 0.46, and the exchange moves 28.8 MB over every link -- more than the 0.22 ms the split saves at any plausible xGMI rate.)
-    g->split_paths = g->n > 1 && cfg->num_light_paths % (uint32_t)g->n == 0 &&
+    g->split_paths = !g->iterations && g->n > 1 && cfg->num_light_paths % (uint32_t)g->n == 0 &&
                      (gc->split_light_paths > 0 || (gc->split_light_paths == 0 && evplp_group_split_model(cfg->num_light_paths, cfg->photons_per_path, g->n, nullptr) == 1));
     g->per_rank_paths = g->split_paths ? cfg->num_light_paths / (uint32_t)g->n : cfg->num_light_paths;
     g->barrier.n = g->n;
@@ -401,6 +522,7 @@ extern "C" int evplp_group_create(const evplp_config *cfg, const evplp_group_con
 // frame + rebalance converge: a band that was expensive gets shorter, and the next round measures its cost at the new height.
 extern "C" int evplp_group_rebalance(evplp_group *g, int32_t *band_first_rows) {
     GRP_CHECK(g);
+    if (g->iterations && g->n > 1) { g->set_error("evplp_group_rebalance: the group shares out iterations, not the image: nothing to deal"); return EVPLP_ERR_INVALID; }
     drain(g);
     int rc = group_status(g); if (rc < 0) return rc;
     const int H = g->ctx[0]->st.H, n = g->n;
@@ -507,6 +629,7 @@ extern "C" int evplp_group_split_model(uint32_t num_light_paths, uint32_t photon
 }
 extern "C" int evplp_group_calibrate(evplp_group *g, int32_t on) {
     GRP_CHECK(g);
+    if (g->iterations) { g->set_error("evplp_group_calibrate: the group shares out iterations, not the image: no blocks to clock"); return EVPLP_ERR_INVALID; }
     drain(g);
     int rc = group_status(g); if (rc < 0) return rc;
     for (int r = 0; r < g->n; r++) {
@@ -518,33 +641,34 @@ extern "C" int evplp_group_calibrate(evplp_group *g, int32_t on) {
 extern "C" int evplp_group_block_owners(evplp_group *g, int32_t *owner_rank, int32_t capacity) {
     GRP_CHECK(g);
     if (g->bands) { g->set_error("evplp_group_block_owners: the group deals bands, not blocks"); return EVPLP_ERR_INVALID; }
+    if (g->iterations) { g->set_error("evplp_group_block_owners: the group shares out iterations, not blocks"); return EVPLP_ERR_INVALID; }
     for (int b = 0; b < g->image_blocks && owner_rank && b < capacity; b++) owner_rank[b] = g->owner.empty() ? b % g->n : g->owner[(size_t)b];
     return g->image_blocks;
 }
 
-extern "C" int evplp_group_load_scene_json(evplp_group *g, const char *json_path) { GRP_CHECK(g); Cmd c; c.op = OP_LOAD_SCENE; c.p0 = json_path; return post_and_wait(g, c); }
-extern "C" int evplp_group_clear_accumulators(evplp_group *g) { GRP_CHECK(g); Cmd c; c.op = OP_CLEAR; return post_all(g, c); }
+extern "C" int evplp_group_load_scene_json(evplp_group *g, const char *json_path) { GRP_CHECK(g); g->sums_fresh = false; Cmd c; c.op = OP_LOAD_SCENE; c.p0 = json_path; return post_and_wait(g, c); }
+extern "C" int evplp_group_clear_accumulators(evplp_group *g) { GRP_CHECK(g); g->sums_fresh = false; Cmd c; c.op = OP_CLEAR; return post_all(g, c); }
 extern "C" int evplp_group_synchronize(evplp_group *g) { GRP_CHECK(g); Cmd c; c.op = OP_SYNC; return post_and_wait(g, c); }
 extern "C" int evplp_group_primary(evplp_group *g, const float jitter[2], int32_t light_flags) {
     GRP_CHECK(g);
     Cmd c; c.op = OP_PRIMARY; c.f[0] = jitter ? jitter[0] : 0.f; c.f[1] = jitter ? jitter[1] : 0.f; c.i[0] = light_flags;
-    return post_all(g, c);
+    return post_pass(g, c);
 }
-extern "C" int evplp_group_trace_light_paths(evplp_group *g, uint32_t rng_seed) { GRP_CHECK(g); Cmd c; c.op = OP_TRACE; c.u[0] = rng_seed; return post_all(g, c); }
+extern "C" int evplp_group_trace_light_paths(evplp_group *g, uint32_t rng_seed) { GRP_CHECK(g); Cmd c; c.op = OP_TRACE; c.u[0] = rng_seed; return post_pass(g, c); }
 extern "C" int evplp_group_gather(evplp_group *g, const evplp_frame_params *fp, int32_t kind) {
     GRP_CHECK(g);
     if (kind < 0 || kind > 2) { g->set_error("evplp_group_gather: kind must be 0 (VPL), 1 (VSL) or 2 (light-path windows)"); return EVPLP_ERR_INVALID; }
     if (!fp) { g->set_error("evplp_group_gather: null frame params"); return EVPLP_ERR_INVALID; }
     { int rc = check_frame_params(g, fp, "evplp_group_gather", false); if (rc < 0) return rc; }
     Cmd c; c.op = OP_GATHER; c.fp = *fp; c.i[0] = kind;
-    return post_all(g, c);
+    return post_pass(g, c);
 }
 extern "C" int evplp_group_splat_photons(evplp_group *g, const evplp_frame_params *fp, int32_t clear) {
     GRP_CHECK(g);
     if (!fp) { g->set_error("evplp_group_splat_photons: null frame params"); return EVPLP_ERR_INVALID; }
     { int rc = check_frame_params(g, fp, "evplp_group_splat_photons", true); if (rc < 0) return rc; }
     Cmd c; c.op = OP_SPLAT; c.fp = *fp; c.i[0] = clear;
-    return post_all(g, c);
+    return post_pass(g, c);
 }
 extern "C" int evplp_group_set_splat_proxy(evplp_group *g, const float *vertices, int32_t nverts, const int32_t *indices, int32_t ntris) {
     GRP_CHECK(g);
@@ -555,7 +679,7 @@ extern "C" int evplp_group_path_trace(evplp_group *g, const float camera_pos[3],
     GRP_CHECK(g);
     if (!camera_pos) { g->set_error("evplp_group_path_trace: null camera position"); return EVPLP_ERR_INVALID; }
     Cmd c; c.op = OP_PATH_TRACE; c.f[0] = camera_pos[0]; c.f[1] = camera_pos[1]; c.f[2] = camera_pos[2]; c.u[0] = rng_seed; c.u[1] = max_bounces; c.i[0] = do_accumulate;
-    return post_all(g, c);
+    return post_pass(g, c);
 }
 
 // Composite every strip on its GPU and all-gather the strips: every GPU then holds the frame, strip by strip.  This is
@@ -564,14 +688,30 @@ static Cmd present_cmd(float vs, float ps, float ls, int32_t mask_emitter, int32
     Cmd c; c.op = OP_PRESENT; c.f[0] = vs; c.f[1] = ps; c.f[2] = ls; c.i[0] = mask_emitter; c.i[1] = gamma; c.i[2] = settle ? 1 : 0; c.i[3] = exchange ? 1 : 0;
     return c;
 }
+// EVPLP_PARTITION_ITERATIONS: every rank sums the ranks' planes and composites the sums -- or, with no pass since the last reduction, the
+// cached sums again (nothing is exchanged)
+static int post_reduce(evplp_group *g, float vs, float ps, float ls, int32_t mask_emitter, int32_t gamma) {
+    Cmd c = present_cmd(vs, ps, ls, mask_emitter, gamma, true, !g->sums_fresh);
+    c.op = OP_REDUCE;
+    const int rc = post_all(g, c);
+    if (rc >= 0) g->sums_fresh = true;
+    return rc;
+}
 extern "C" int evplp_group_present(evplp_group *g, float vs, float ps, float ls, int32_t mask_emitter, int32_t gamma) {
     GRP_CHECK(g);
+    if (g->iterations) return post_reduce(g, vs, ps, ls, mask_emitter, gamma);
     return post_all(g, present_cmd(vs, ps, ls, mask_emitter, gamma, false, true));       // (the per-iteration composite: no wait for the splat's verdict)
 }
 // exchange = 0: every rank composites its strip where it is and nobody waits for anybody -- no host barrier, no collective: the iteration of
 // a loop whose frame is looked at only now and then (a sub-millisecond iteration pays for the exchange otherwise: DESIGN section 5)
 extern "C" int evplp_group_present_ex(evplp_group *g, float vs, float ps, float ls, int32_t mask_emitter, int32_t gamma, int32_t exchange) {
     GRP_CHECK(g);
+    if (g->iterations) {        // exchange = 0: the selected rank composites its own accumulators
+        if (exchange != 0) return post_reduce(g, vs, ps, ls, mask_emitter, gamma);
+        if (g->failed.load(std::memory_order_acquire)) { drain(g); return group_status(g); }
+        post(g->workers[(size_t)g->selected], present_cmd(vs, ps, ls, mask_emitter, gamma, false, false));
+        return EVPLP_OK;
+    }
     return post_all(g, present_cmd(vs, ps, ls, mask_emitter, gamma, false, exchange != 0));
 }
 
@@ -579,7 +719,7 @@ extern "C" int evplp_group_present_ex(evplp_group *g, float vs, float ps, float 
 extern "C" int evplp_group_resolve(evplp_group *g, float vs, float ps, float ls, int32_t mask_emitter, int32_t gamma, float *out_rgb) {
     GRP_CHECK(g);
     if (!out_rgb) { g->set_error("evplp_group_resolve: null output"); return EVPLP_ERR_INVALID; }
-    int rc = post_all(g, present_cmd(vs, ps, ls, mask_emitter, gamma, true, true));
+    int rc = g->iterations ? post_reduce(g, vs, ps, ls, mask_emitter, gamma) : post_all(g, present_cmd(vs, ps, ls, mask_emitter, gamma, true, true));
     if (rc < 0) return rc;
     Cmd c; c.op = OP_ASSEMBLE; c.out = out_rgb;      // (rank 0's stream: behind its side of the exchange)
     post(g->workers[0], c);

@@ -857,6 +857,40 @@ void launch_resolve(const StripDev &st, const float4 *vpl, const float4 *pm, con
     size_t n = (size_t)st.W * st.local_rows;
     hipLaunchKernelGGL(resolve_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, st, vpl, pm, light, vs, ps, ls, mask_emitter, gamma, out_rgb);
 }
+// The accumulators of the ranks of an EVPLP_PARTITION_ITERATIONS group (evplp_group_resolve): out[i] = src[0][i] + src[1][i] + ... +
+// src[n-1][i] in that order, every add rounded on its own (__fadd_rn: no contraction, no reassociation -- the sharded run reproduces
+// itself bit for bit), or (FirstNonzero) the first src[r][i] in rank order with a non-zero component: every iteration writes the same
+// emitter colour, so that is one GPU's union over the iterations.  The n pointers are kernel arguments (512 B of kernarg, scalar loads);
+// a plane is read in groups of four -- four 16-byte loads in flight per lane before the adds, in the same order.  HBM-bound.
+template <bool FirstNonzero>
+__global__ __launch_bounds__(256) void reduce_shards_kernel(ShardPlanes src, int n, size_t count, float4 *out) {
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) {
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        bool have = false;
+        for (int r0 = 0; r0 < n; r0 += 4) {
+            float4 v[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) v[k] = r0 + k < n ? src.p[r0 + k][i] : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                if (r0 + k >= n) break;
+                if (FirstNonzero) {
+                    const bool nz = v[k].x != 0.f || v[k].y != 0.f || v[k].z != 0.f || v[k].w != 0.f;
+                    if (!have && nz) { acc = v[k]; have = true; }
+                } else if (r0 + k == 0) acc = v[k];
+                else { acc.x = __fadd_rn(acc.x, v[k].x); acc.y = __fadd_rn(acc.y, v[k].y); acc.z = __fadd_rn(acc.z, v[k].z); acc.w = __fadd_rn(acc.w, v[k].w); }
+            }
+        }
+        out[i] = acc;
+    }
+}
+void launch_reduce_shards(const ShardPlanes &src, int n, int first_nonzero, size_t count, float4 *out, int num_cus, hipStream_t s) {
+    const size_t blocks = std::min<size_t>((count + 255) / 256, (size_t)std::max(num_cus, 1) * 8);      // grid-stride beyond 8 blocks per CU
+    if (blocks == 0) return;
+    if (first_nonzero) hipLaunchKernelGGL(reduce_shards_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, src, n, count, out);
+    else hipLaunchKernelGGL(reduce_shards_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, src, n, count, out);
+}
 // De-interleave of the all-gathered row strips (evplp_group_resolve): gathered = [n ranks][chunk_rows][W][3] (the rows an exchange moves: <= local_rows), rank r's local row l
 // is image row StripDev{rank r}.global_row(l); frame = [H][W][3].  One thread per float of the frame.
 // bands: rank r owns the rows [bands.first[r], bands.first[r + 1]) (evplp_group with contiguous bands); null = interleaved strips

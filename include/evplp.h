@@ -401,7 +401,23 @@ int evplp_group_split_model(uint32_t num_light_paths, uint32_t photons_per_path,
  * walking the whole tree for a fraction of the rays).  EVPLP_PARTITION_BANDS: one contiguous band of rows per rank (evplp_config band mode;
  * strip_rows is ignored) -- equal heights at first, then dealt by measured cost: evplp_group_rebalance moves the band boundaries so that
  * every rank's last frame would have taken the same time.  Per-pixel results do not depend on either. */
-typedef enum evplp_group_partition { EVPLP_PARTITION_STRIPS = 0, EVPLP_PARTITION_BANDS = 1 } evplp_group_partition;
+/* EVPLP_PARTITION_ITERATIONS: the ranks share out the ITERATIONS of a progressive run instead of the image.  Every rank is a whole-image
+ * context (strip_count 1, no strip capacity) on the single-GPU kernel paths; ranks are distinct devices (RCCL) or virtual ranks on one device,
+ * as above.  evplp_group_select_rank picks the rank that evplp_group_primary, _trace_light_paths, _gather, _splat_photons, _path_trace and
+ * evplp_group_present_ex(.., exchange = 0) -- a composite of that rank's OWN accumulators -- go to (rank 0 by default); clear, load scene,
+ * splat proxy and profile passes still go to every rank.  evplp_group_present (and present_ex with exchange != 0) and evplp_group_resolve
+ * REDUCE: every rank settles its photon splats, the planes EVPLP_BUF_VPL_ACCUM, _PHOTON_ACCUM and _LIGHT of all ranks are exchanged (an
+ * ncclAllGather per plane into a staging buffer, or read in place on a shared device), and every rank forms, on its GPU, the VPL and photon
+ * sums in rank order 0, 1, .., n-1 in fp32 (every add rounded: the run reproduces itself bit for bit) and the light plane as the first
+ * non-zero pixel in rank order -- every iteration writes the same emitter colour, so that is exactly one GPU's union over the iterations --
+ * and composites them (every GPU holds the frame); evplp_group_resolve copies rank 0's composite to the caller.  A present / resolve with
+ * no pass call since the last reduction composites the cached sums again and exchanges nothing; any pass call, a clear or an
+ * evplp_group_context call (the caller may write through it) makes them stale.  Refused with EVPLP_ERR_INVALID (the group stays usable):
+ * evplp_group_calibrate, evplp_group_rebalance (a single rank: EVPLP_OK), evplp_group_block_owners, split_light_paths = 1 at create
+ * (0 does not consult the cost model: every rank traces its own iteration's paths).  Memory per rank beyond a single context: the sums,
+ * 3 x W x local_rows x 16 B (1080p: 100 MB), allocated at the first reduction (a failed allocation is a sticky EVPLP_ERR_OOM), and with
+ * RCCL a staging buffer of n x W x local_rows x 16 B (1080p, n = 8: 267 MB). */
+typedef enum evplp_group_partition { EVPLP_PARTITION_STRIPS = 0, EVPLP_PARTITION_BANDS = 1, EVPLP_PARTITION_ITERATIONS = 2 } evplp_group_partition;
 /* cfg: as for evplp_create; device / strip_* are set per rank by the group */
 int evplp_group_create(const evplp_config *cfg, const evplp_group_config *gcfg, evplp_group **out);
 void evplp_group_destroy(evplp_group *g);
@@ -417,6 +433,11 @@ int evplp_group_splat_photons(evplp_group *g, const evplp_frame_params *fp, int3
 int evplp_group_set_splat_proxy(evplp_group *g, const float *vertices, int32_t nverts, const int32_t *indices, int32_t ntris);
 int evplp_group_path_trace(evplp_group *g, const float camera_pos[3], uint32_t rng_seed, uint32_t max_bounces, int32_t do_accumulate);
 int evplp_group_synchronize(evplp_group *g);
+/* EVPLP_PARTITION_ITERATIONS: the rank the single-rank pass calls go to from now on (see the partition enum).  Other partitions, or a rank out
+ * of range: EVPLP_ERR_INVALID. */
+int evplp_group_select_rank(evplp_group *g, int32_t rank);
+/* Waits for rank `rank`'s worker and its context's streams only (any partition); returns the group's sticky status. */
+int evplp_group_synchronize_rank(evplp_group *g, int32_t rank);
 /* Calibration for evplp_group_rebalance under EVPLP_PARTITION_STRIPS: evplp_calibrate_blocks on every rank (waits for the workers). */
 int evplp_group_calibrate(evplp_group *g, int32_t on);
 /* The owner of every image block (nblocks = ceil(res_y / strip_rows) ints, rank numbers); returns nblocks. */
@@ -510,9 +531,11 @@ int evplp_synth_scene_ex(const char *out_dir, const char *name, int32_t target_t
  * the frames that are written -- the default: the loop is headless; 1 = the reference's per-iteration draw; "splitLightPaths": evplp_group_config.split_light_paths, absent = the cost model; "cutScratchGB" /
  * "vslMaskGB": evplp_config.cut_scratch_bytes / vsl_mask_bytes).
  * "device": {"gpus": N, "partition": "iterations"} (photonfam / lvcphotonfam, frameMode accumulate): the N GPUs share out the ITERATIONS of the
- * progressive run instead of the image -- GPU g renders iterations g, g + N, ... of the whole frame on a context of its own, nothing is
- * exchanged inside the loop, the accumulators are summed (rank order, on the host) when a frame is written.  N times the iterations per second
- * with no replicated work; images agree with one GPU's to fp32 round-off (the sums are associated differently), not bit for bit. */
+ * progressive run instead of the image -- one evplp_group of N EVPLP_PARTITION_ITERATIONS ranks, GPU g renders iterations g, g + N, ... of the
+ * whole frame, nothing is exchanged inside the loop ("exchangeEvery": k > 0 reduces in every k-th iteration), and the accumulators are summed
+ * on the GPUs (rank order, reduce_shards_kernel) when a frame is written.  Under a time limit the loop waits only for the rank the next
+ * iteration reuses.  N times the iterations per second with no replicated work; VPL and photon images agree with one GPU's to fp32
+ * round-off (the sums are associated differently), not bit for bit; the emitter image is one GPU's exactly. */
 int evplp_render_json(const char *json_path, const char *json_overrides, int32_t device, char *err, size_t err_cap);
 
 #ifdef __cplusplus
