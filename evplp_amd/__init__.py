@@ -19,7 +19,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EVPLP_LIB") or os.path.join(_HERE, "lib", "libevplp_hip.so")
 INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 # evplp_status
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_IO, ERR_PARSE, ERR_OOM = 0, -1, -2, -3, -4, -5, -6
@@ -49,8 +49,7 @@ class Config(C.Structure):
                 ("strip_rank", C.c_int32), ("strip_count", C.c_int32), ("strip_rows", C.c_int32),
                 ("num_light_paths", C.c_uint32), ("num_vpl_light_paths", C.c_uint32), ("photons_per_path", C.c_uint32),
                 ("bvh_builder", C.c_int32), ("deterministic", C.c_int32), ("gather_splits_per_wave", C.c_int32),
-                ("overlap_light_tracing", C.c_int32), ("cut_scratch_bytes", C.c_uint64), ("vsl_mask_bytes", C.c_uint64),
-                ("band_first_row", C.c_int32), ("band_rows", C.c_int32), ("band_capacity_rows", C.c_int32), ("strip_capacity_rows", C.c_int32)]
+                ("overlap_light_tracing", C.c_int32), ("cut_scratch_bytes", C.c_uint64), ("vsl_mask_bytes", C.c_uint64), ("strip_capacity_rows", C.c_int32)]
 
 
 class Material(C.Structure):
@@ -81,8 +80,8 @@ class GroupConfig(C.Structure):
                 ("partition", C.c_int32), ("strip_capacity_pct", C.c_int32), ("split_light_paths", C.c_int32), ("reserved", C.c_int32)]
 
 
-PARTITION_STRIPS, PARTITION_BANDS, PARTITION_ITERATIONS = 0, 1, 2
-PARTITIONS = {"strips": PARTITION_STRIPS, "bands": PARTITION_BANDS, "iterations": PARTITION_ITERATIONS}
+PARTITION_STRIPS, PARTITION_ITERATIONS = 0, 2
+PARTITIONS = {"strips": PARTITION_STRIPS, "iterations": PARTITION_ITERATIONS}
 
 
 class PassStats(C.Structure):
@@ -122,7 +121,6 @@ _SIGNATURES = {
     "evplp_resolve": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, _P]),
     "evplp_present": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32]),
     "evplp_clear_accumulators": (C.c_int, [_P]),
-    "evplp_set_band": (C.c_int, [_P, C.c_int32, C.c_int32]),
     "evplp_set_blocks": (C.c_int, [_P, _P, C.c_int32]),
     "evplp_get_blocks": (C.c_int, [_P, _P, C.c_int32]),
     "evplp_calibrate_blocks": (C.c_int, [_P, C.c_int32]),
@@ -160,7 +158,7 @@ _SIGNATURES = {
     "evplp_group_select_rank": (C.c_int, [_P, C.c_int32]),
     "evplp_group_synchronize_rank": (C.c_int, [_P, C.c_int32]),
     "evplp_group_host_stats": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double * 3)]),
-    "evplp_group_rebalance": (C.c_int, [_P, _P]),
+    "evplp_group_rebalance": (C.c_int, [_P]),
     "evplp_group_calibrate": (C.c_int, [_P, C.c_int32]),
     "evplp_group_split_model": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int32, C.POINTER(C.c_double * 2)]),
     "evplp_group_block_owners": (C.c_int, [_P, _P, C.c_int32]),
@@ -248,13 +246,9 @@ class Context:
     def __init__(self, res_x: int, res_y: int, num_light_paths: int, num_vpl_light_paths: int, photons_per_path: int,
                  device: int = 0, strip_rank: int = 0, strip_count: int = 1, strip_rows: int = 16,
                  bvh_builder: int = BVH_SAH, deterministic: bool = False, gather_splits_per_wave: int = 0, overlap_light_tracing: bool = False,
-                 band=None, band_capacity_rows: int = 0, strip_capacity_rows: int = 0, cut_scratch_bytes: int = 0, vsl_mask_bytes: int = 0):
-        """band = (first_row, rows): the context owns those contiguous image rows instead of interleaved strips."""
+                 strip_capacity_rows: int = 0, cut_scratch_bytes: int = 0, vsl_mask_bytes: int = 0):
         self._lib = lib()
         cfg = Config()
-        if band is not None:
-            cfg.band_first_row, cfg.band_rows = int(band[0]), int(band[1]); cfg.band_capacity_rows = int(band_capacity_rows)
-            strip_rank, strip_count = 0, 1
         cfg.abi_version = ABI_VERSION; cfg.device = device; cfg.res_x = res_x; cfg.res_y = res_y
         cfg.strip_rank = strip_rank; cfg.strip_count = strip_count; cfg.strip_rows = strip_rows
         cfg.num_light_paths = num_light_paths; cfg.num_vpl_light_paths = num_vpl_light_paths
@@ -452,10 +446,6 @@ class Context:
         self._check(self._lib.evplp_block_costs(self._h, _ptr(out), out.size))
         return out
 
-    def set_band(self, first_row: int, rows: int):
-        self._check(self._lib.evplp_set_band(self._h, first_row, rows))
-        self.cfg.band_first_row, self.cfg.band_rows = first_row, rows
-
     # -- buffers
     def buffer_info(self, which: int):
         p, n = C.c_void_p(), C.c_size_t()
@@ -509,10 +499,6 @@ class Context:
     def global_rows(self) -> np.ndarray:
         """Global image row of every local row (>= H for padding rows)."""
         from . import strips
-        if self.cfg.band_rows > 0:
-            l = np.arange(self.local_rows)
-            rows = min(self.cfg.band_rows, self.H - self.cfg.band_first_row)
-            return np.where(l < rows, self.cfg.band_first_row + l, self.H + l)
         if self.cfg.strip_count <= 1:
             return strips.global_rows(self.H, self.cfg.strip_rank, self.cfg.strip_count, self.cfg.strip_rows)
         return strips.rows_of_blocks(self.H, self.blocks(), self.cfg.strip_rows, self.local_rows)      # (the library's table: dealt or round-robin)
@@ -548,7 +534,7 @@ def rank_blocks(costs, owner, rank: int) -> np.ndarray:
 
 class Group:
     """evplp_group: n ranks driven by one thread (RCCL across distinct GPUs, device copies for virtual ranks) that share out the image
-    (partition "strips" / "bands") or the iterations of a progressive run ("iterations": select_rank() picks the rank the passes go to,
+    (partition "strips") or the iterations of a progressive run ("iterations": select_rank() picks the rank the passes go to,
     present() / resolve() sum the ranks' accumulators on the GPUs)."""
 
     def __init__(self, res_x, res_y, num_light_paths, num_vpl_light_paths, photons_per_path, n_ranks, devices=None, strip_rows=0,
@@ -564,7 +550,7 @@ class Group:
         if partition not in PARTITIONS:
             raise ValueError(f"partition: one of {sorted(PARTITIONS)}, got {partition!r}")
         gc.partition = PARTITIONS[partition]; gc.strip_capacity_pct = int(strip_capacity_pct); gc.split_light_paths = int(split_light_paths)
-        self.partition = partition if n_ranks > 1 or partition == "iterations" else "strips"
+        self.partition = partition
         self._devs = (C.c_int32 * n_ranks)(*devices) if devices is not None else None
         gc.devices = C.cast(self._devs, C.POINTER(C.c_int32)) if self._devs is not None else None
         h = C.c_void_p()
@@ -626,13 +612,9 @@ class Group:
         """wait for rank r's worker and its context's streams only"""
         self._check(self._lib.evplp_group_synchronize_rank(self._h, r))
 
-    def rebalance(self) -> np.ndarray:
-        """bands partition: move the band boundaries to equal measured cost (clears the accumulators); returns the n + 1 boundaries.
-        strips partition: deal the blocks by the cost clocked since calibrate() (block_owners() has the result)"""
-        out = np.zeros(self.n + 1, dtype=np.int32)
-        self._check(self._lib.evplp_group_rebalance(self._h, _ptr(out)))
-        self._bands = out.copy()
-        return out
+    def rebalance(self) -> None:
+        """strips partition: deal the blocks by the cost clocked since calibrate() (clears the accumulators; block_owners() has the result)"""
+        self._check(self._lib.evplp_group_rebalance(self._h))
 
     def calibrate(self, on: bool = True):
         """strips partition: the gathers clock their blocks until rebalance() deals them by cost"""
@@ -667,13 +649,6 @@ class Group:
         whole = self.partition == "iterations"       # (every rank holds the whole image)
         c = Context.borrowed(h, self.W, self.H, strip_rank=0 if whole else r, strip_count=1 if whole else self.n, strip_rows=self.strip_rows,
                              num_light_paths=self._paths[0], num_vpl_light_paths=self._paths[1], photons_per_path=self._paths[2])
-        if self.partition == "bands":
-            b = getattr(self, "_bands", None)
-            if b is None:
-                rows16 = (self.H + 15) // 16 * 16; share = max(16, (rows16 // self.n + 15) // 16 * 16)
-                b = np.minimum(np.arange(self.n + 1) * share, self.H); b[self.n] = self.H
-            c.cfg.strip_rank, c.cfg.strip_count = 0, 1
-            c.cfg.band_first_row = int(b[r]); c.cfg.band_rows = int((b[r + 1] if r + 1 < self.n else (self.H + 15) // 16 * 16) - b[r])
         return c
 
     context = rank

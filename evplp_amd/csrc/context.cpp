@@ -58,15 +58,6 @@ extern "C" int evplp_create(const evplp_config *cfg, evplp_context **out) {
     if (strip_rows <= 0 || (strip_rows % 8) != 0 || cfg->strip_rank < 0 || cfg->strip_rank >= strip_count) {
         snprintf(g_create_error, sizeof(g_create_error), "evplp_create: strip_rows must be a positive multiple of 8 and 0 <= strip_rank < strip_count"); return EVPLP_ERR_INVALID;
     }
-    const bool band_mode = cfg->band_rows > 0;
-    if (band_mode) {
-        const int cap = cfg->band_capacity_rows > 0 ? cfg->band_capacity_rows : cfg->band_rows;
-        if (strip_count != 1 || cfg->band_first_row < 0 || (cfg->band_first_row % 16) != 0 || cfg->band_first_row >= cfg->res_y || cap < cfg->band_rows ||
-            ((cfg->band_rows % 16) != 0 && cfg->band_first_row + cfg->band_rows < cfg->res_y) || cfg->band_first_row + cfg->band_rows > ((cfg->res_y + 15) / 16) * 16) {
-            snprintf(g_create_error, sizeof(g_create_error), "evplp_create: a band starts on a multiple of 16 rows inside the image, is a multiple of 16 rows high unless it ends the image, fits its capacity, and excludes strip_count > 1");
-            return EVPLP_ERR_INVALID;
-        }
-    }
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= 0) {
@@ -95,12 +86,6 @@ extern "C" int evplp_create(const evplp_config *cfg, evplp_context **out) {
     if (strip_count > 1 && cfg->strip_capacity_rows > owned * strip_rows) owned = std::min((cfg->strip_capacity_rows + strip_rows - 1) / strip_rows, nblocks);
     c->st.local_rows = owned * strip_rows;
     c->st.cap_blocks = owned; c->image_blocks = nblocks;
-    if (band_mode) {
-        const int cap = cfg->band_capacity_rows > 0 ? cfg->band_capacity_rows : cfg->band_rows;
-        c->st.strip_rows = ((cap + 7) / 8) * 8; c->cfg.strip_rows = c->st.strip_rows;
-        c->st.local_rows = c->st.strip_rows;
-        c->st.band_first = cfg->band_first_row; c->st.band_rows = std::min(cfg->band_rows, cfg->res_y - cfg->band_first_row);
-    }
     // rows of this strip that fall inside the image
     c->rows_in_image = 0;
     for (int l = 0; l < c->st.local_rows; l++) if (c->st.global_row(l) < c->st.H) c->rows_in_image++;
@@ -745,9 +730,8 @@ static int run_gather(evplp_context *c, const evplp_frame_params *fp, bool vsl) 
         // (a row strip of an n-way partition is a SMALL launch, and small launches want short items: one rank's gather of an eight-way
         // partition of config #2 takes 9.3 / 12.1 / 17.5 ms for k = 1 / 2 / 4 where an eighth of the one-GPU kernel is 6.2 ms --
         // profiles/r05_strip_projection.json: projected 5.2x instead of 4.1x at eight ranks.  The result does not depend on k.)
-        // (round 6: keyed on the size of the launch -- at most 8 192 owned tiles, the threshold of item_deal -- instead of on strip_count > 1, which
-        // missed the bands of EVPLP_PARTITION_BANDS; at eight dealt ranks k = 2 projects x5.1 where k = 1 projects x6.5: an item twice as long
-        // is a tail twice as long)
+        // (round 6: keyed on the size of the launch -- at most 8 192 owned tiles, the threshold of item_deal -- instead of on strip_count > 1; at
+        // eight dealt ranks k = 2 projects x5.1 where k = 1 projects x6.5: an item twice as long is a tail twice as long)
         const bool small_launch = small_gather_launch(c);
         k = c->cfg.gather_splits_per_wave > 0 ? c->cfg.gather_splits_per_wave : (small_launch ? 1 : kDefaultSplitsPerWave);
         if (c->env_gather_k > 0) k = c->env_gather_k;
@@ -1022,28 +1006,12 @@ static void count_rows_in_image(evplp_context *c) {
     c->rows_in_image = 0;
     for (int l = 0; l < c->st.local_rows; l++) if (c->st.global_row(l) < c->st.H) c->rows_in_image++;
 }
-extern "C" int evplp_set_band(evplp_context *c, int32_t first_row, int32_t rows) {
-    CTX_CHECK(c);
-    { int rc_ = settle_splat(c); if (rc_) return rc_; }
-    if (c->st.band_rows <= 0) { c->set_error("evplp_set_band: the context was not created in band mode"); return EVPLP_ERR_INVALID; }
-    if (first_row < 0 || (first_row % 16) != 0 || first_row >= c->st.H || rows <= 0 || rows > c->st.local_rows ||
-        ((rows % 16) != 0 && first_row + rows < c->st.H) || first_row + rows > ((c->st.H + 15) / 16) * 16) {
-        c->set_error("evplp_set_band: rows [%d, %d) are not a band this context can hold (capacity %d rows, multiples of 16)", first_row, first_row + rows, c->st.local_rows); return EVPLP_ERR_INVALID;
-    }
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream)); if (c->aux_stream) HIP_TRY(c, hipStreamSynchronize(c->aux_stream));
-    c->st.band_first = first_row; c->st.band_rows = std::min(rows, c->st.H - first_row);
-    c->cfg.band_first_row = first_row; c->cfg.band_rows = rows;
-    count_rows_in_image(c);
-    c->primary_cuts_valid = false; c->tile_box_valid = false;
-    return evplp_clear_accumulators(c);
-}
 
 // ---- dealt blocks (include/evplp.h): the owned-block table of a row-strip context, and the per-block cost the deal is made from
 extern "C" int evplp_set_blocks(evplp_context *c, const int32_t *image_blocks, int32_t count) {
     CTX_CHECK(c);
     { int rc_ = settle_splat(c); if (rc_) return rc_; }
-    if (c->st.strip_count <= 1 || c->st.band_rows > 0) { c->set_error("evplp_set_blocks: the context is not a row-strip context (strip_count > 1)"); return EVPLP_ERR_INVALID; }
+    if (c->st.strip_count <= 1) { c->set_error("evplp_set_blocks: the context is not a row-strip context (strip_count > 1)"); return EVPLP_ERR_INVALID; }
     const int cap = c->st.cap_blocks, nb = c->image_blocks;
     if (image_blocks && (count < 0 || count > cap)) { c->set_error("evplp_set_blocks: %d blocks do not fit the context's %d (strip_capacity_rows)", count, cap); return EVPLP_ERR_INVALID; }
     std::vector<int32_t> table;
@@ -1071,7 +1039,7 @@ extern "C" int evplp_set_blocks(evplp_context *c, const int32_t *image_blocks, i
 extern "C" int evplp_get_blocks(evplp_context *c, int32_t *image_blocks, int32_t capacity) {
     CTX_CHECK(c);
     int n = 0;
-    const int cap = c->st.band_rows > 0 ? 0 : c->st.local_rows / c->st.strip_rows;
+    const int cap = c->st.local_rows / c->st.strip_rows;
     for (int l = 0; l < cap; l++) {
         const int b = c->st.global_block(l);
         if (b >= c->image_blocks) continue;
@@ -1103,7 +1071,7 @@ extern "C" int evplp_block_costs(evplp_context *c, uint64_t *cost_per_image_bloc
     for (int b = 0; b < c->image_blocks; b++) cost_per_image_block[b] = 0;
     int n = 0;
     for (int l = 0; l < cap; l++) {
-        const int b = c->st.band_rows > 0 ? 0 : c->st.global_block(l);
+        const int b = c->st.global_block(l);
         if (b < c->image_blocks) { cost_per_image_block[b] += local[(size_t)l]; n++; }
     }
     return n;

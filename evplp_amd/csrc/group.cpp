@@ -116,7 +116,6 @@ struct evplp_group {
     float *d_assembled = nullptr;           // rank 0's device: [H][W][3] the frame in image order (evplp_group_resolve)
     size_t strip_floats = 0;                // local_rows * W * 3
     bool split_paths = false; uint32_t per_rank_paths = 0;
-    bool bands = false; evplp::BandTable band_table{};    // EVPLP_PARTITION_BANDS: first image row of every rank's band (+ H)
     // EVPLP_PARTITION_STRIPS: the blocks as dealt (evplp_group_rebalance); empty = block b belongs to rank b % n
     std::vector<int32_t> owner;             // [image blocks] rank
     uint32_t *d_owner = nullptr;            // rank 0's device: [image blocks] rank << 16 | local block (assemble_strips_kernel)
@@ -281,7 +280,7 @@ static void worker_run(Worker *w, const Cmd &cmd) {
             if (g->iterations) e = hipMemcpyAsync(cmd.out, c->d_rgb, frame_floats * sizeof(float), hipMemcpyDeviceToHost, c->stream);   // (whole-image ranks: rows in image order)
             else if (!g->d_assembled) e = hipMalloc((void **)&g->d_assembled, sizeof(float) * frame_floats);
             if (e == hipSuccess && !g->iterations) {
-                evplp::launch_assemble_strips(c->st, g->n, g->bands ? &g->band_table : nullptr, g->owner.empty() ? nullptr : g->d_owner, (int)(g->strip_floats / ((size_t)c->st.W * 3)), g->d_frame[0], g->d_assembled, c->stream);
+                evplp::launch_assemble_strips(c->st, g->n, g->owner.empty() ? nullptr : g->d_owner, (int)(g->strip_floats / ((size_t)c->st.W * 3)), g->d_frame[0], g->d_assembled, c->stream);
                 e = hipMemcpyAsync(cmd.out, g->d_assembled, frame_floats * sizeof(float), hipMemcpyDeviceToHost, c->stream);
             }
             if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -348,7 +347,7 @@ static int post_all(evplp_group *g, const Cmd &cmd) {
     for (Worker *w : g->workers) post(w, cmd);
     return EVPLP_OK;
 }
-// a pass call: every rank (strips, bands), or the selected rank alone (EVPLP_PARTITION_ITERATIONS; the cached sums are stale from here on)
+// a pass call: every rank (strips), or the selected rank alone (EVPLP_PARTITION_ITERATIONS; the cached sums are stale from here on)
 static int post_pass(evplp_group *g, const Cmd &cmd) {
     if (!g->iterations) return post_all(g, cmd);
     g->sums_fresh = false;
@@ -388,7 +387,7 @@ extern "C" evplp_context *evplp_group_context(evplp_group *g, int32_t rank) {
 }
 extern "C" int evplp_group_select_rank(evplp_group *g, int32_t rank) {
     GRP_CHECK(g);
-    if (!g->iterations) { g->set_error("evplp_group_select_rank: the group shares out the image (strips / bands): every pass runs on every rank"); return EVPLP_ERR_INVALID; }
+    if (!g->iterations) { g->set_error("evplp_group_select_rank: the group shares out the image (strips): every pass runs on every rank"); return EVPLP_ERR_INVALID; }
     if (rank < 0 || rank >= g->n) { g->set_error("evplp_group_select_rank: rank %d out of range (%d ranks)", rank, g->n); return EVPLP_ERR_INVALID; }
     g->selected = rank;
     return EVPLP_OK;
@@ -430,6 +429,9 @@ extern "C" void evplp_group_destroy(evplp_group *g) {
     delete g;
 }
 
+// the floats an exchange moves under the round-robin deal (n > 1)
+static size_t round_robin_floats(const evplp_group *g) { return (size_t)((g->image_blocks + g->n - 1) / g->n) * (size_t)g->strip_rows * g->ctx[0]->st.W * 3; }
+
 extern "C" int evplp_group_create(const evplp_config *cfg, const evplp_group_config *gc, evplp_group **out) {
     auto fail = [&](int code, const char *fmt, ...) { va_list ap; va_start(ap, fmt); vsnprintf(g_group_create_error, sizeof(g_group_create_error), fmt, ap); va_end(ap); return code; };
     if (!cfg || !gc || !out) return fail(EVPLP_ERR_INVALID, "evplp_group_create: null argument");
@@ -449,15 +451,9 @@ extern "C" int evplp_group_create(const evplp_config *cfg, const evplp_group_con
     // nothing any more and the cheaper cuts win at every rank count (single-GPU projection of config #2, profiles/r06_strip_projection.json:
     // n = 8, 8- / 16-row blocks: slowest rank 8.49 / 8.06 ms; n = 4: 14.97 / 14.60).
     const int strip_rows = gc->strip_rows > 0 ? gc->strip_rows : 16;
-    if (gc->partition < EVPLP_PARTITION_STRIPS || gc->partition > EVPLP_PARTITION_ITERATIONS) { delete g; return fail(EVPLP_ERR_INVALID, "evplp_group_create: partition %d unknown", gc->partition); }
+    if (gc->partition != EVPLP_PARTITION_STRIPS && gc->partition != EVPLP_PARTITION_ITERATIONS) { delete g; return fail(EVPLP_ERR_INVALID, "evplp_group_create: partition %d unknown", gc->partition); }
     g->iterations = gc->partition == EVPLP_PARTITION_ITERATIONS;
     if (g->iterations && gc->split_light_paths > 0) { delete g; return fail(EVPLP_ERR_INVALID, "evplp_group_create: split_light_paths = 1 with EVPLP_PARTITION_ITERATIONS (every rank traces its own iteration's paths)"); }
-    // EVPLP_PARTITION_BANDS: contiguous bands of equal height to begin with (multiples of 16 rows), each with room for twice its share
-    g->bands = gc->partition == EVPLP_PARTITION_BANDS && g->n > 1;
-    const int rows16 = ((cfg->res_y + 15) / 16) * 16, share = std::max(16, ((rows16 / g->n + 15) / 16) * 16), band_cap = std::min(rows16, 2 * share);
-    for (int r = 0; r <= g->n; r++) g->band_table.first[r] = std::min(r * share, cfg->res_y);
-    g->band_table.first[g->n] = cfg->res_y;
-    if (g->bands && g->band_table.first[g->n - 1] >= cfg->res_y) { delete g; return fail(EVPLP_ERR_INVALID, "evplp_group_create: %d bands of at least 16 rows do not fit %d image rows", gc->n_ranks, cfg->res_y); }
     for (int r = 0; r < g->n; r++) {
         evplp_config c = *cfg;
         c.device = g->device[(size_t)r]; c.strip_rank = r; c.strip_count = g->n; c.strip_rows = strip_rows;
@@ -466,10 +462,6 @@ extern "C" int evplp_group_create(const evplp_config *cfg, const evplp_group_con
             c.strip_capacity_rows = g->n > 1 ? std::min(nb, (share * pct + 99) / 100) * strip_rows : 0;
         }
         if (g->iterations) { c.strip_rank = 0; c.strip_count = 1; c.strip_capacity_rows = 0; }     // a whole-image context, as on one GPU
-        if (g->bands) {
-            c.strip_rank = 0; c.strip_count = 1; c.strip_rows = 0;
-            c.band_first_row = g->band_table.first[r]; c.band_rows = (r + 1 < g->n ? g->band_table.first[r + 1] : rows16) - g->band_table.first[r]; c.band_capacity_rows = band_cap;
-        }
         evplp_context *h = nullptr;
         int rc = evplp_create(&c, &h);
         if (rc < 0) { int code = fail(rc, "rank %d: %s", r, evplp_last_error(nullptr)); evplp_group_destroy(g); return code; }
@@ -479,8 +471,7 @@ extern "C" int evplp_group_create(const evplp_config *cfg, const evplp_group_con
     g->strip_floats_cap = (size_t)g->ctx[0]->st.local_rows * g->ctx[0]->st.W * 3;
     // an exchange moves the rows in use: the equal share under the round-robin deal (the capacity beyond it holds nothing), the fullest rank's
     // blocks after a deal by cost
-    g->strip_floats = g->bands || g->n == 1 ? g->strip_floats_cap
-                                            : (size_t)((g->image_blocks + g->n - 1) / g->n) * (size_t)g->strip_rows * g->ctx[0]->st.W * 3;
+    g->strip_floats = g->n == 1 ? g->strip_floats_cap : round_robin_floats(g);
     g->d_frame.assign((size_t)g->n, nullptr);
     g->plane_px = (size_t)g->ctx[0]->st.W * g->ctx[0]->st.local_rows;
     g->d_sum.assign((size_t)g->n, nullptr); g->d_stage.assign((size_t)g->n, nullptr); g->num_cus.assign((size_t)g->n, 256);
@@ -517,104 +508,57 @@ extern "C" int evplp_group_create(const evplp_config *cfg, const evplp_group_con
     return EVPLP_OK;
 }
 
-// Bands dealt by cost: every rank's device time since the last rebalance, spread evenly over its rows, is a piecewise-constant cost profile of
-// the image; the new boundaries cut it into n parts of equal cost (multiples of 16 rows, at least 16, at most the capacity).  A few rounds of
-// frame + rebalance converge: a band that was expensive gets shorter, and the next round measures its cost at the new height.
-extern "C" int evplp_group_rebalance(evplp_group *g, int32_t *band_first_rows) {
+// The blocks dealt by the cost the gathers clocked (evplp_group_calibrate).  The ranks take their tables first and the owner table of the
+// assembly follows only once all of them have: whatever fails, everybody returns to the round-robin deal, so d_owner, g->owner and the
+// contexts never disagree.
+extern "C" int evplp_group_rebalance(evplp_group *g) {
     GRP_CHECK(g);
     if (g->iterations && g->n > 1) { g->set_error("evplp_group_rebalance: the group shares out iterations, not the image: nothing to deal"); return EVPLP_ERR_INVALID; }
     drain(g);
     int rc = group_status(g); if (rc < 0) return rc;
-    const int H = g->ctx[0]->st.H, n = g->n;
-    if (!g->bands && n > 1) {
-        // ---- EVPLP_PARTITION_STRIPS: deal the blocks by the cost the gathers clocked (evplp_group_calibrate)
-        const int nb = g->image_blocks;
-        std::vector<uint64_t> cost((size_t)nb, 0), mine((size_t)nb);
-        uint64_t total = 0;
-        for (int r = 0; r < n; r++) {
-            int rb = evplp_block_costs(g->ctx[(size_t)r], mine.data(), nb);
-            if (rb < 0) { g->set_error("rank %d: %s", r, evplp_last_error(g->ctx[(size_t)r])); return rb; }
-            for (int b = 0; b < nb; b++) { cost[(size_t)b] += mine[(size_t)b]; total += mine[(size_t)b]; }
-        }
-        if (total == 0) { g->set_error("evplp_group_rebalance: no block cost was clocked (evplp_group_calibrate, then a frame with a gather)"); return EVPLP_ERR_INVALID; }
-        std::vector<int32_t> owner((size_t)nb);
-        rc = evplp_deal_blocks(cost.data(), nb, n, g->cap_blocks, owner.data());
-        if (rc < 0) { g->set_error("evplp_group_rebalance: %d blocks do not fit %d ranks of %d", nb, n, g->cap_blocks); return rc; }
-        // every rank's blocks, the most expensive first (evplp_rank_blocks: the launch order); all tables are built before any is set
-        std::vector<std::vector<int32_t>> lists((size_t)n);
-        std::vector<uint32_t> packed((size_t)nb);
-        size_t most = 0;
-        for (int r = 0; r < n; r++) {
-            auto &l = lists[(size_t)r];
-            l.resize((size_t)nb);
-            l.resize((size_t)evplp_rank_blocks(cost.data(), owner.data(), nb, r, l.data(), nb));
-            for (size_t i = 0; i < l.size(); i++) packed[(size_t)l[i]] = ((uint32_t)r << 16) | (uint32_t)i;
-            most = std::max(most, l.size());
-        }
+    const int n = g->n, nb = g->image_blocks;
+    if (n == 1) return EVPLP_OK;
+    std::vector<uint64_t> cost((size_t)nb, 0), mine((size_t)nb);
+    uint64_t total = 0;
+    for (int r = 0; r < n; r++) {
+        rc = evplp_block_costs(g->ctx[(size_t)r], mine.data(), nb);
+        if (rc < 0) { g->set_error("rank %d: %s", r, evplp_last_error(g->ctx[(size_t)r])); return rc; }
+        for (int b = 0; b < nb; b++) { cost[(size_t)b] += mine[(size_t)b]; total += mine[(size_t)b]; }
+    }
+    if (total == 0) { g->set_error("evplp_group_rebalance: no block cost was clocked (evplp_group_calibrate, then a frame with a gather)"); return EVPLP_ERR_INVALID; }
+    std::vector<int32_t> owner((size_t)nb);
+    rc = evplp_deal_blocks(cost.data(), nb, n, g->cap_blocks, owner.data());
+    if (rc < 0) { g->set_error("evplp_group_rebalance: %d blocks do not fit %d ranks of %d", nb, n, g->cap_blocks); return rc; }
+    // every rank's blocks, the most expensive first (evplp_rank_blocks: the launch order); all tables are built before any is set
+    std::vector<std::vector<int32_t>> lists((size_t)n);
+    std::vector<uint32_t> packed((size_t)nb);
+    size_t most = 0;
+    for (int r = 0; r < n; r++) {
+        auto &l = lists[(size_t)r];
+        l.resize((size_t)nb);
+        l.resize((size_t)evplp_rank_blocks(cost.data(), owner.data(), nb, r, l.data(), nb));
+        for (size_t i = 0; i < l.size(); i++) packed[(size_t)l[i]] = ((uint32_t)r << 16) | (uint32_t)i;
+        most = std::max(most, l.size());
+    }
+    // (a table evplp_deal_blocks made for this capacity is not refused; if one is, the fallback below still holds)
+    for (int r = 0; r < n && rc >= 0; r++) {
+        rc = evplp_set_blocks(g->ctx[(size_t)r], lists[(size_t)r].data(), (int32_t)lists[(size_t)r].size());
+        if (rc >= 0) rc = evplp_calibrate_blocks(g->ctx[(size_t)r], 0);
+        if (rc < 0) g->set_error("rank %d: %s", r, evplp_last_error(g->ctx[(size_t)r]));
+    }
+    if (rc >= 0) {
         hipSetDevice(g->device[0]);
-        if (!g->d_owner && hipMalloc((void **)&g->d_owner, sizeof(uint32_t) * (size_t)nb) != hipSuccess) { (void)hipGetLastError(); g->set_error("evplp_group_rebalance: hipMalloc(owner table)"); return EVPLP_ERR_OOM; }
-        if (hipMemcpy(g->d_owner, packed.data(), sizeof(uint32_t) * packed.size(), hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); g->set_error("evplp_group_rebalance: hipMemcpy(owner table)"); return EVPLP_ERR_HIP; }
-        for (int r = 0; r < n; r++) {
-            int rb = evplp_set_blocks(g->ctx[(size_t)r], lists[(size_t)r].data(), (int32_t)lists[(size_t)r].size());
-            if (rb >= 0) rb = evplp_calibrate_blocks(g->ctx[(size_t)r], 0);
-            if (rb < 0) {      // (cannot happen with a table evplp_deal_blocks made for this capacity; if it does, everybody returns to the default deal)
-                g->set_error("rank %d: %s", r, evplp_last_error(g->ctx[(size_t)r]));
-                for (int q = 0; q < n; q++) evplp_set_blocks(g->ctx[(size_t)q], nullptr, 0);
-                g->owner.clear(); g->strip_floats = (size_t)((nb + n - 1) / n) * (size_t)g->strip_rows * g->ctx[0]->st.W * 3;
-                return rb;
-            }
-        }
-        g->owner.swap(owner);
-        g->strip_floats = most * (size_t)g->strip_rows * g->ctx[0]->st.W * 3;
+        if (!g->d_owner && hipMalloc((void **)&g->d_owner, sizeof(uint32_t) * (size_t)nb) != hipSuccess) { g->set_error("evplp_group_rebalance: hipMalloc(owner table)"); rc = EVPLP_ERR_OOM; }
+        else if (hipMemcpy(g->d_owner, packed.data(), sizeof(uint32_t) * packed.size(), hipMemcpyHostToDevice) != hipSuccess) { g->set_error("evplp_group_rebalance: hipMemcpy(owner table)"); rc = EVPLP_ERR_HIP; }
+        if (rc < 0) (void)hipGetLastError();
     }
-    if (g->bands) {
-        static const int kPasses[] = { EVPLP_PASS_PRIMARY, EVPLP_PASS_GATHER_VPL, EVPLP_PASS_GATHER_VSL, EVPLP_PASS_GATHER_LVC, EVPLP_PASS_SPLAT, EVPLP_PASS_PATH_TRACE };
-        std::vector<double> cost((size_t)n, 0.0);
-        double total = 0.0;
-        for (int r = 0; r < n; r++) {
-            for (int p : kPasses) {
-                evplp_pass_stats ps;
-                if (g->ctx[(size_t)r]->pass_ran[p] && evplp_pass_stats_get(g->ctx[(size_t)r], p, &ps) == EVPLP_OK) cost[(size_t)r] += ps.ms;
-                g->ctx[(size_t)r]->pass_ran[p] = false;          // (counted once: the next rebalance sees the passes that ran after this one)
-            }
-            total += cost[(size_t)r];
-        }
-        if (!(total > 0.0)) { g->set_error("evplp_group_rebalance: no pass was timed since the last rebalance (evplp_group_profile_passes is off, or no frame ran)"); return EVPLP_ERR_INVALID; }
-        {
-            const int cap = g->ctx[0]->st.local_rows;
-            int first[65]; first[0] = 0; first[n] = H;
-            // cumulative cost at row y: bands in order, constant density within a band
-            auto row_at_cost = [&](double target) {
-                double acc = 0.0;
-                for (int r = 0; r < n; r++) {
-                    const int b0 = g->band_table.first[r], b1 = g->band_table.first[r + 1];
-                    if (acc + cost[(size_t)r] >= target || r == n - 1) return b0 + (cost[(size_t)r] > 0.0 ? (target - acc) / cost[(size_t)r] : 0.0) * (double)(b1 - b0);
-                    acc += cost[(size_t)r];
-                }
-                return (double)H;
-            };
-            for (int r = 1; r < n; r++) {
-                int y = (int)(row_at_cost(total * (double)r / (double)n) / 16.0 + 0.5) * 16;
-                y = std::max(y, first[r - 1] + 16);                               // at least 16 rows
-                y = std::min(y, first[r - 1] + (cap / 16) * 16);                  // at most the capacity
-                y = std::min(y, ((H - 1) / 16) * 16 - (n - 1 - r) * 16);          // room for the bands behind it
-                first[r] = y;
-            }
-            // the bands behind a capped one may be pushed beyond THEIR capacity: walk back from the end
-            for (int r = n - 1; r >= 1; r--) first[r] = std::max(first[r], ((first[r + 1] + 15) / 16) * 16 - (cap / 16) * 16);
-            for (int r = 0; r < n; r++) {
-                const int rows = (r + 1 < n ? first[r + 1] : ((H + 15) / 16) * 16) - first[r];
-                int rb = evplp_set_band(g->ctx[(size_t)r], first[r], rows);
-                if (rb < 0) {      // the group's table follows the contexts: the ranks already moved go back to where the table says they are
-                    g->set_error("rank %d: %s", r, evplp_last_error(g->ctx[(size_t)r]));
-                    for (int q = 0; q < r; q++) evplp_set_band(g->ctx[(size_t)q], g->band_table.first[q], (q + 1 < n ? g->band_table.first[q + 1] : ((H + 15) / 16) * 16) - g->band_table.first[q]);
-                    return rb;
-                }
-            }
-            for (int r = 0; r <= n; r++) g->band_table.first[r] = first[r];
-        }
+    if (rc < 0) {
+        for (int r = 0; r < n; r++) evplp_set_blocks(g->ctx[(size_t)r], nullptr, 0);
+        g->owner.clear(); g->strip_floats = round_robin_floats(g);
+        return rc;
     }
-    if (band_first_rows) for (int r = 0; r <= n; r++) band_first_rows[r] = g->bands ? g->band_table.first[r] : 0;
+    g->owner.swap(owner);
+    g->strip_floats = most * (size_t)g->strip_rows * g->ctx[0]->st.W * 3;
     return EVPLP_OK;
 }
 
@@ -640,7 +584,6 @@ extern "C" int evplp_group_calibrate(evplp_group *g, int32_t on) {
 }
 extern "C" int evplp_group_block_owners(evplp_group *g, int32_t *owner_rank, int32_t capacity) {
     GRP_CHECK(g);
-    if (g->bands) { g->set_error("evplp_group_block_owners: the group deals bands, not blocks"); return EVPLP_ERR_INVALID; }
     if (g->iterations) { g->set_error("evplp_group_block_owners: the group shares out iterations, not blocks"); return EVPLP_ERR_INVALID; }
     for (int b = 0; b < g->image_blocks && owner_rank && b < capacity; b++) owner_rank[b] = g->owner.empty() ? b % g->n : g->owner[(size_t)b];
     return g->image_blocks;

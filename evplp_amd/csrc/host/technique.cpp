@@ -410,7 +410,7 @@ private:
             check(h, evplp_group_primary(h, j0, EVPLP_LIGHT_SKIP), "primary (calibration)");
             check(h, evplp_group_trace_light_paths(h, rng_offset), "light tracing (calibration)");
             check(h, evplp_group_gather(h, &fp, force_vsl ? 1 : 0), "gather (calibration)");
-            check(h, evplp_group_rebalance(h, nullptr), "rebalance");
+            check(h, evplp_group_rebalance(h), "rebalance");
         }
         auto elapsed_ms = [&]() { return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
         // The wait in front of a look at the clock.  Strips: every rank (a frame is all of them).  Iterations: only the rank the NEXT iteration

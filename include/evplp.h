@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define EVPLP_ABI_VERSION 4
+#define EVPLP_ABI_VERSION 5
 
 typedef enum evplp_status {
     EVPLP_OK = 0,
@@ -121,11 +121,6 @@ typedef struct evplp_config {
      * A caller that has the device to itself sets cut_scratch_bytes = 72 GB, vsl_mask_bytes = 14 GB for config #5 (one band, one launch). */
     uint64_t cut_scratch_bytes;
     uint64_t vsl_mask_bytes;
-    /* Band mode, the other way to give a context a share of the image: with band_rows > 0 (and strip_count <= 1) it owns the CONTIGUOUS image
-     * rows [band_first_row, band_first_row + band_rows), stored from local row 0; band_first_row and band_rows are multiples of 16 (the last
-     * band may end at res_y).  band_capacity_rows >= band_rows sizes its buffers (0 = band_rows): evplp_set_band may later move the band
-     * anywhere within that capacity.  evplp_group's "bands" partition deals such bands by measured cost (evplp_group_rebalance). */
-    int32_t band_first_row, band_rows, band_capacity_rows;
     /* Row strips (strip_count > 1): rows of strip storage, a multiple of strip_rows; 0 = the equal share, ceil(blocks / strip_count) blocks.
      * More than that leaves room for a deal by cost (evplp_set_blocks), which gives a rank of cheap blocks more of them. */
     int32_t strip_capacity_rows;
@@ -295,15 +290,12 @@ int evplp_resolve(evplp_context *ctx, float vpl_scale, float photon_scale, float
  * settle first and are exact. */
 int evplp_present(evplp_context *ctx, float vpl_scale, float photon_scale, float light_scale, int32_t mask_emitter, int32_t gamma);
 int evplp_clear_accumulators(evplp_context *ctx);
-/* Band mode only: move the context's band to the rows [first_row, first_row + rows) (multiples of 16; rows <= band_capacity_rows).  The
- * accumulators are cleared and the G-buffer is stale: call between runs, not between the iterations of an accumulating run. */
-int evplp_set_band(evplp_context *ctx, int32_t first_row, int32_t rows);
 
 /* Row-strip contexts (strip_count > 1): which blocks of strip_rows image rows this context owns.  By default block b belongs to rank
  * b % strip_count.  evplp_set_blocks replaces that by a table: local block l holds image block image_blocks[l], l < count <= the context's
  * capacity (evplp_config.strip_capacity_rows / strip_rows); image_blocks = NULL restores the default.  Every kernel, statistic and buffer
- * layout follows the table; per-pixel results do not depend on it.  As with evplp_set_band the accumulators are cleared and the G-buffer is
- * stale afterwards: call between runs.  evplp_get_blocks returns the number of blocks owned (and up to `capacity` of them, in local order). */
+ * layout follows the table; per-pixel results do not depend on it.  The accumulators are cleared and the G-buffer is stale afterwards: call
+ * between runs, not between the iterations of an accumulating run.  evplp_get_blocks returns the number of blocks owned (and up to `capacity` of them, in local order). */
 int evplp_set_blocks(evplp_context *ctx, const int32_t *image_blocks, int32_t count);
 int evplp_get_blocks(evplp_context *ctx, int32_t *image_blocks, int32_t capacity);
 /* What a deal by cost is made from.  While calibration is on, the VPL / VSL gathers run self-clocking variants of their kernels (same
@@ -398,9 +390,8 @@ typedef struct evplp_group_config {
  * splitting is expected to save time, 0 when not; out_ms (optional): [0] all paths on every rank, [1] a share + the exchange. */
 int evplp_group_split_model(uint32_t num_light_paths, uint32_t photons_per_path, int32_t n_ranks, double out_ms[2]);
 /* EVPLP_PARTITION_STRIPS: interleaved blocks of strip_rows rows, block b to rank b % n (balanced by interleaving, at the price of every rank
- * walking the whole tree for a fraction of the rays).  EVPLP_PARTITION_BANDS: one contiguous band of rows per rank (evplp_config band mode;
- * strip_rows is ignored) -- equal heights at first, then dealt by measured cost: evplp_group_rebalance moves the band boundaries so that
- * every rank's last frame would have taken the same time.  Per-pixel results do not depend on either. */
+ * walking the whole tree for a fraction of the rays), or dealt by measured cost (evplp_group_rebalance).  Per-pixel results do not depend on
+ * the deal.  (1 was a partition into contiguous bands of rows, removed in ABI version 5: it is refused as unknown.) */
 /* EVPLP_PARTITION_ITERATIONS: the ranks share out the ITERATIONS of a progressive run instead of the image.  Every rank is a whole-image
  * context (strip_count 1, no strip capacity) on the single-GPU kernel paths; ranks are distinct devices (RCCL) or virtual ranks on one device,
  * as above.  evplp_group_select_rank picks the rank that evplp_group_primary, _trace_light_paths, _gather, _splat_photons, _path_trace and
@@ -417,7 +408,7 @@ int evplp_group_split_model(uint32_t num_light_paths, uint32_t photons_per_path,
  * (0 does not consult the cost model: every rank traces its own iteration's paths).  Memory per rank beyond a single context: the sums,
  * 3 x W x local_rows x 16 B (1080p: 100 MB), allocated at the first reduction (a failed allocation is a sticky EVPLP_ERR_OOM), and with
  * RCCL a staging buffer of n x W x local_rows x 16 B (1080p, n = 8: 267 MB). */
-typedef enum evplp_group_partition { EVPLP_PARTITION_STRIPS = 0, EVPLP_PARTITION_BANDS = 1, EVPLP_PARTITION_ITERATIONS = 2 } evplp_group_partition;
+typedef enum evplp_group_partition { EVPLP_PARTITION_STRIPS = 0, EVPLP_PARTITION_ITERATIONS = 2 } evplp_group_partition;
 /* cfg: as for evplp_create; device / strip_* are set per rank by the group */
 int evplp_group_create(const evplp_config *cfg, const evplp_group_config *gcfg, evplp_group **out);
 void evplp_group_destroy(evplp_group *g);
@@ -443,17 +434,14 @@ int evplp_group_calibrate(evplp_group *g, int32_t on);
 /* The owner of every image block (nblocks = ceil(res_y / strip_rows) ints, rank numbers); returns nblocks. */
 int evplp_group_block_owners(evplp_group *g, int32_t *owner_rank, int32_t capacity);
 /* EVPLP_PARTITION_STRIPS: waits for the ranks, collects the per-block costs their gathers clocked since evplp_group_calibrate(g, 1), deals
- * the blocks by cost (evplp_deal_blocks, capacity = strip_capacity_pct of the equal share), gives every rank its table (evplp_set_blocks)
- * and switches the calibration off.  The all-gather of the strips then moves max-blocks-per-rank x strip_rows rows per rank.  Returns
- * EVPLP_ERR_INVALID when no cost was clocked (no calibration, or no gather ran).  As below, accumulators are cleared: calibrate on a frame
+ * the blocks by cost (evplp_deal_blocks, capacity = strip_capacity_pct of the equal share), gives every rank its table (evplp_set_blocks),
+ * switches the calibration off and uploads the table evplp_group_resolve assembles the frame by.  The all-gather of the strips then moves
+ * max-blocks-per-rank x strip_rows rows per rank.  The accumulators are cleared and the G-buffers are stale afterwards: calibrate on a frame
  * in front of an accumulating run (the technique loop does: "device": {"deal": "cost"}, or by default when the run is long enough).
- * EVPLP_PARTITION_BANDS: waits for the ranks, takes every rank's device time of the passes it ran since the last rebalance (HIP events of
- * primary rays, gathers, photon splat, path tracer), treats it as spread evenly over the rank's rows, and moves the band boundaries (multiples
- * of 16 rows, within the bands' capacity of twice the equal share) to where every rank would have had the same cost.  The accumulators are
- * cleared and the G-buffers are stale afterwards: call it after one or two calibration frames, before an accumulating run (the technique
- * loops always run on strips: the bands are an option of this API, not of evplp_render_json).  band_first_rows: optional, n_ranks + 1 ints, the boundaries it chose (zeros for strips).  A single rank: nothing to do,
- * EVPLP_OK.  Bands without a timed pass since the last rebalance (evplp_profile_passes off): EVPLP_ERR_INVALID, nothing changes. */
-int evplp_group_rebalance(evplp_group *g, int32_t *band_first_rows);
+ * A single rank: nothing to do, EVPLP_OK.  No cost clocked (no calibration, or no gather ran): EVPLP_ERR_INVALID, nothing changes.  A rank
+ * that refuses its table or a failed upload: every rank returns to the round-robin deal and the error is returned.
+ * EVPLP_PARTITION_ITERATIONS with n > 1: EVPLP_ERR_INVALID (see the partition enum). */
+int evplp_group_rebalance(evplp_group *g);
 /* Host time of rank `rank`'s worker so far, in ms: out[0] inside its rank's pass calls (enqueueing; waits for a splat's verdict included),
  * out[1] inside exchanges (host barrier + collective / copies), out[2] commands run.  Waits until that worker is idle. */
 int evplp_group_host_stats(evplp_group *g, int32_t rank, double out[3]);

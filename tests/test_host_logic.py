@@ -14,7 +14,7 @@ import scenes
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_library_exports_every_declared_symbol(evplp):
+def test_library_exports_every_declared_symbol_at_abi_5(evplp):
     hdr = open(os.path.join(ROOT, "include", "evplp.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     declared = set(re.findall(r"\b(evplp_[a-z_0-9]+)\s*\(", hdr))
@@ -23,12 +23,12 @@ def test_library_exports_every_declared_symbol(evplp):
     missing = [n for n in sorted(declared) if not hasattr(lib, n)]
     assert not missing, f"declared in include/evplp.h but not exported: {missing}"
     assert declared == set(evplp._SIGNATURES), declared ^ set(evplp._SIGNATURES)
-    assert lib.evplp_abi_version() == 4 == evplp.ABI_VERSION
+    assert lib.evplp_abi_version() == 5 == evplp.ABI_VERSION
 
 
-def test_struct_layouts_match_the_header(evplp, tmp_path):
+def test_struct_layouts_match_the_abi_5_header(evplp, tmp_path):
     """The ctypes mirrors against the header itself: a C program prints sizeof / offsetof of what include/evplp.h declares."""
-    assert C.sizeof(evplp.FrameParams) == 72 and C.sizeof(evplp.Config) == 88
+    assert C.sizeof(evplp.FrameParams) == 72 and C.sizeof(evplp.Config) == 80
     assert C.sizeof(evplp.Material) == 40 and C.sizeof(evplp.Camera) == 44 and C.sizeof(evplp.PassStats) == 64
     assert evplp.RECORD_DTYPE.itemsize == 96
     src = tmp_path / "layout.c"
@@ -39,7 +39,7 @@ int main(void) {
     printf("%zu %zu %zu %zu %zu %zu %zu\\n", sizeof(evplp_config), sizeof(evplp_frame_params), sizeof(evplp_material), sizeof(evplp_camera), sizeof(evplp_pass_stats),
            sizeof(evplp_record), sizeof(evplp_group_config));
     printf("%zu %zu %zu %zu %zu %zu\\n", offsetof(evplp_config, cut_scratch_bytes), offsetof(evplp_config, vsl_mask_bytes), offsetof(evplp_frame_params, jitter),
-           offsetof(evplp_frame_params, splat_footprint), offsetof(evplp_pass_stats, shaded), offsetof(evplp_config, band_first_row));
+           offsetof(evplp_frame_params, splat_footprint), offsetof(evplp_pass_stats, shaded), offsetof(evplp_config, strip_capacity_rows));
     printf("%d %d\\n", EVPLP_ABI_VERSION, EVPLP_MAX_PROXY_PLANES);
     return 0;
 }
@@ -51,7 +51,7 @@ int main(void) {
     assert sizes == [C.sizeof(evplp.Config), C.sizeof(evplp.FrameParams), C.sizeof(evplp.Material), C.sizeof(evplp.Camera), C.sizeof(evplp.PassStats), 96, C.sizeof(evplp.GroupConfig)]
     offs = [int(x) for x in lines[1].split()]
     assert offs == [evplp.Config.cut_scratch_bytes.offset, evplp.Config.vsl_mask_bytes.offset, evplp.FrameParams.jitter.offset,
-                    evplp.FrameParams.splat_footprint.offset, evplp.PassStats.shaded.offset, evplp.Config.band_first_row.offset]
+                    evplp.FrameParams.splat_footprint.offset, evplp.PassStats.shaded.offset, evplp.Config.strip_capacity_rows.offset]
     assert [int(x) for x in lines[2].split()] == [evplp.ABI_VERSION, 128]
 
 

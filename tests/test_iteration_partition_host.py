@@ -11,20 +11,20 @@ from test_kernel_resources import HIPCC, kernel_table
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_partition_value_in_header_and_binding(evplp, tmp_path):
+def test_partition_values_without_bands_in_header_and_binding(evplp, tmp_path):
     src = tmp_path / "partition.c"
     src.write_text('''#include <stdio.h>
 #include "evplp.h"
 int main(void) {
     evplp_group_partition p = EVPLP_PARTITION_ITERATIONS;
-    printf("%d %d %d\\n", (int)EVPLP_PARTITION_STRIPS, (int)EVPLP_PARTITION_BANDS, (int)p);
+    printf("%d %d\\n", (int)EVPLP_PARTITION_STRIPS, (int)p);
     return 0;
 }
 ''')
     exe = tmp_path / "partition"
     subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
     out = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()
-    assert [int(x) for x in out] == [evplp.PARTITION_STRIPS, evplp.PARTITION_BANDS, evplp.PARTITION_ITERATIONS] == [0, 1, 2]
+    assert [int(x) for x in out] == [evplp.PARTITION_STRIPS, evplp.PARTITION_ITERATIONS] == [0, 2]
     assert evplp.PARTITIONS["iterations"] == 2
 
 
@@ -40,6 +40,13 @@ def test_new_entry_points_are_exported_and_refuse_a_null_group(evplp):
 def test_unknown_partition_name_is_refused_before_any_device_call(evplp):
     with pytest.raises(ValueError):
         evplp.Group(16, 16, 4, 4, 2, 2, devices=[0, 0], partition="rows")
+    with pytest.raises(ValueError):
+        evplp.Group(16, 16, 4, 4, 2, 2, devices=[0, 0], partition="bands")      # (removed in ABI version 5)
+    cfg, gc, h = evplp.Config(), evplp.GroupConfig(), C.c_void_p()
+    cfg.abi_version = evplp.ABI_VERSION; cfg.res_x = cfg.res_y = 16; cfg.num_light_paths = cfg.num_vpl_light_paths = 4; cfg.photons_per_path = 2
+    gc.n_ranks = 2; gc.partition = 1
+    assert evplp.lib().evplp_group_create(C.byref(cfg), C.cast(C.byref(gc), C.c_void_p), C.byref(h)) == evplp.ERR_INVALID and not h.value
+    assert b"partition 1 unknown" in evplp.lib().evplp_group_last_error(None)
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
