@@ -2,7 +2,7 @@
 """bench.py -- the reference's headline metric on MI355X:
 "Mpaths/s + ms/frame, conference 1024^2, 4096 VPLs, 1/2/4/8 GPU" (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W [--workload ir|evplp|ppm|vsl] [--scene hard|easy] [--front-end ranks|group] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--workload ir|evplp|ppm|vsl] [--scene hard|easy] [--front-end ranks|group] [--dump-outputs DIR] [--full]
 
 A step = one iteration of the technique loop (rt/rtcomphoton/rtcomphoton.h:936-1068):
   ir    BASELINE config #2 (default, the headline): Instant Radiosity, 1024 light paths x 4 vertices = 4096 VPL record
@@ -15,11 +15,19 @@ A step = one iteration of the technique loop (rt/rtcomphoton/rtcomphoton.h:936-1
 The scene is a procedural conference stand-in (the reference's meshes are Git-LFS stubs): "data": "synthetic";
 --scene hard (default) is furnished with curved and thin parts, --scene easy is the room of tessellated boxes.
 
-The default run (no flags: config #2 on one GPU) also carries, as extra objects of the same JSON line, short runs of the other
-configurations -- `evplp` (config #3, roofline of the photon splat), `ppm` (config #4: iteration time, splat roofline, the
-light-tracing and G-buffer kernels), `vsl` (config #5) -- the other scene style, the 16 384-slot reading of "4096 VPLs", the GPU
-path tracer, and `render_json`: the same configuration run through evplp_render_json, the entry a maintainer of the reference
-binds (its per-iteration time must agree with ms_per_step).
+A plain run does only what the headline needs: set up, warm up, time the steps, write --dump-outputs, print the line (its
+`roofline` and `feeders` come from the timed steps themselves, except config #4's, which has no read-back in its timed steps and
+carries them with --full only).  Everything that takes runs of its own is behind --full:
+  - after the timed steps of a photon workload: extra steps with the events around the splat's dominant kernel
+    (`tiles_kernel_ms`), the splat pass under both coverage rules (`footprints`) and, for config #4, the iterations its pass
+    times and splat roofline are read from;
+  - `render_json`: the same configuration run through evplp_render_json, the entry a maintainer of the reference binds (its
+    per-iteration time must agree with ms_per_step);
+  - with config #2 on one GPU, short runs of the other configurations -- `evplp` (config #3, roofline of the photon splat), `ppm`
+    (config #4: iteration time, splat roofline, the light-tracing and G-buffer kernels), `vsl` (config #5) -- the other scene
+    style, the 16 384-slot reading of "4096 VPLs" and the GPU path tracer;
+  - `cpu_baseline` and `cpu_baseline_like_for_like` on the host cores.
+--no-extras (items 2 and 3) and --no-cpu-baseline (item 4) narrow --full; without --full they change nothing.
 
 N GPUs, two front ends (--front-end auto picks `group` whenever the process sees N devices, `ranks` otherwise):
   group  one process, `evplp_group` -- the native multi-GPU entry of the C ABI, what a maintainer of the reference binds (one host
@@ -101,8 +109,11 @@ def parse():
     ap.add_argument("--exchange-every", type=int, default=1, help="N > 1: the composited strips are all-gathered every k-th frame (0 = never inside the timed loop)")
     ap.add_argument("--scratch-gb", type=float, default=0.0, help="evplp_config.cut_scratch_bytes in GB (0 = the library's default of 8 GB; config #5 needs 68 GB for one band)")
     ap.add_argument("--mask-gb", type=float, default=0.0, help="evplp_config.vsl_mask_bytes in GB (0 = the library's default of 2 GB; config #5 needs 8.6 GB for one launch)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements (configs #3-#5, other scene, 16384-slot variant, GPU path tracer, render_json)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes runs of its own: the profiled splat steps after the timed region, render_json, configs #3-#5, other scene, "
+                         "16384-slot variant, GPU path tracer, CPU baselines (a plain run times the steps and prints the line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary measurements (configs #3-#5, other scene, 16384-slot variant, GPU path tracer, render_json)")
     ap.add_argument("--cpu-iters", type=int, default=0, help="path-tracer iterations of the CPU baseline sample (0 = auto, ~12 s)")
     ap.add_argument("--dump-frame", default="", help="rank 0 writes the assembled VPL + photon accumulators of the last frame to this .npy file (tests)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
@@ -453,7 +464,7 @@ def run_workload(env, wl, steps, warmup, scene, primary=True):
     def profile_passes(on):
         # the two HIP events per pass behind pass_stats()["ms"]: config #4's sub-millisecond iterations run their timed region without them
         # (as the technique loop of evplp_render_json does for all iterations but its last); the pass times of the line come from the
-        # extra iterations after the timed region, recorded with them
+        # extra iterations after the timed region (--full), recorded with them
         if group is not None:
             group.profile_passes(on)
         else:
@@ -484,12 +495,12 @@ def run_workload(env, wl, steps, warmup, scene, primary=True):
     # Pass statistics synchronise the stream.  The gather workloads (>= 80 ms per step) read them every step.  Config #4's 0.7 ms
     # iterations run their timed region without a single read-back (the host stays an iteration ahead of the GPU, as in the
     # technique loop of evplp_render_json); photon-pixel pairs come from the library's device-side running total, read before and
-    # after, and the HIP-event times of the passes from ten more iterations after the timed region.
+    # after, and (--full) the HIP-event times of the passes from ten more iterations after the timed region.
     pairs_before = sum(c.pass_stats(ev.PASS_SPLAT)["shaded"] for c in ranks) if wl != "ir" else 0
 
     def read_pass_times(profiled=False):
         # the splat's pass time comes from steps WITHOUT the events around its dominant kernel (they sit between its launches:
-        # evplp_profile_kernels), the dominant kernel's own time from a few extra steps with them
+        # evplp_profile_kernels), the dominant kernel's own time from a few extra steps with them (--full)
         if wl != "ir":
             ss = ctx.pass_stats(ev.PASS_SPLAT)
             if profiled:
@@ -560,12 +571,13 @@ def run_workload(env, wl, steps, warmup, scene, primary=True):
             outputs.pop("vpl_accum")               # (no VPLs)
         if rank == 0:
             dumped = write_outputs(np, a.dump_outputs, outputs)
+    # --full: per-kernel figures from steps of their own after the timed region (a plain run stops here)
     extra = min(10, len(jitters) - (warmup + steps))
-    if wl == "ppm":
+    if wl == "ppm" and a.full:
         for i in range(extra - 3):
             frame(warmup + steps + i); read_pass_times()
         sync_all()
-    if wl != "ir":                     # three more steps with the events around the splat's dominant kernel
+    if wl != "ir" and a.full:          # three more steps with the events around the splat's dominant kernel
         for c in ranks:
             c.profile_kernels(True)
         for i in range(max(extra - (1 if wl == "vsl" else 3), 0), extra):
@@ -902,15 +914,15 @@ def main():
     rank0 = env.rank == 0 or not env.use_dist
     single = rank0 and not env.use_dist and not env.group_front_end
 
-    # ---- secondary measurements (one GPU): the path a maintainer binds, configs #3 / #4 / #5, the other scene style, the
+    # ---- secondary measurements (--full, one GPU): the path a maintainer binds, configs #3 / #4 / #5, the other scene style, the
     # 16 384-slot reading of "4096 VPLs", the GPU path tracer
-    if single and not a.no_extras and not env.force_dist:
+    if single and a.full and not a.no_extras and not env.force_dist:
         ev, torch = env.ev, env.torch
         it = {"ir": 20, "evplp": 10, "ppm": 400, "vsl": 2}[wl]
         rj = render_json_time(env, wl, json_path, shape, it)
         rj["ratio_to_ms_per_step"] = rj["ms_per_iteration"] / out["ms_per_step"]
         out["render_json"] = rj
-    if single and wl == "ir" and not a.no_extras and not env.force_dist:
+    if single and wl == "ir" and a.full and not a.no_extras and not env.force_dist:
         def brief(o, keys=("ms_per_step", "value", "steps", "roofline", "roofline_splat", "feeders")):
             r = {k: o[k] for k in keys if k in o}
             r["config"] = {k: o["config"][k] for k in ("workload", "resolution", "num_light_paths", "num_vpl_light_paths", "mis_mode", "usable_vpl_records")}
@@ -963,7 +975,7 @@ def main():
                 pt_ms.append(s["ms"]); pt_paths += s["pairs"]
         out["gpu_path_tracer_mpaths_s"] = pt_paths / (sum(pt_ms) * 1e-3) / 1e6
         c3.close()
-    if single and not a.no_cpu_baseline:
+    if single and a.full and not a.no_cpu_baseline:
         base, like = cpu_baseline(json_path, min(shape[0], shape[1]), a.cpu_iters)
         out["cpu_baseline"] = base
         out["cpu_baseline_like_for_like"] = like

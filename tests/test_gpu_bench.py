@@ -44,8 +44,9 @@ def test_bench_collective_path_on_one_rank():
 @pytest.mark.parametrize("wl", ["evplp", "ppm"])
 def test_bench_photon_workloads_through_the_collective_path(wl):
     """The photon workloads with EVPLP_BENCH_FORCE_DIST=1: light paths traced by path range + in-place record all-gather, both
-    framebuffers all-gathered -- the same photon-pixel pairs as without collectives."""
-    args = ["--workload", wl, "--steps", "2", "--warmup", "1", "--tris", "20000", "--no-cpu-baseline", "--no-extras"] + (["--res", "256"] if wl == "evplp" else [])
+    framebuffers all-gathered -- the same photon-pixel pairs as without collectives (--full: config #4's splat roofline comes from
+    iterations after the timed region)."""
+    args = ["--workload", wl, "--steps", "2", "--warmup", "1", "--tris", "20000", "--full", "--no-cpu-baseline", "--no-extras"] + (["--res", "256"] if wl == "evplp" else [])
     a = run_bench(args, {"EVPLP_BENCH_FORCE_DIST": "1"})
     b = run_bench(args)
     ra, rb = (a.get("roofline_splat") or a["roofline"]), (b.get("roofline_splat") or b["roofline"])
@@ -142,9 +143,9 @@ def test_bench_dump_outputs(tmp_path):
 
 
 def test_bench_default_extras_small():
-    """The default line's extra objects (here at a small size): the path through evplp_render_json agrees with the timed loop, and
+    """The --full line's extra objects (here at a small size): the path through evplp_render_json agrees with the timed loop, and
     configs #3 / #4 / #5 ride along with their rooflines."""
-    d = run_bench(["--steps", "3", "--warmup", "1", "--tris", "20000", "--no-cpu-baseline"])
+    d = run_bench(["--steps", "3", "--warmup", "1", "--tris", "20000", "--full", "--no-cpu-baseline"])
     rj = d["render_json"]
     assert rj["iterations"] == 20 and rj["ms_per_iteration"] > 0
     assert 0.8 <= rj["ratio_to_ms_per_step"] <= 1.25, rj
@@ -154,3 +155,19 @@ def test_bench_default_extras_small():
     assert 0.7 <= p["render_json"]["ratio_to_ms_per_step"] <= 1.4, p["render_json"]
     v = d["vsl"]["roofline"]
     assert v["kernel"].startswith("gather_vsl_walk_kernel") and v["sample_iterations_per_frame"] > v["lit_pairs_per_frame"] > 0
+
+
+def test_bench_plain_run_leaves_the_full_measurements_out():
+    """A plain run times its steps and prints the line; what takes runs of its own (the profiled splat steps after the timed
+    region, render_json, the other configurations, the CPU baselines) comes with --full only."""
+    args = ["--workload", "evplp"] + SMALL[:-2]
+    plain = run_bench(args)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline", "roofline_splat"):
+        assert k in plain, k
+    for k in ("render_json", "cpu_baseline", "cpu_baseline_like_for_like"):
+        assert k not in plain, k
+    assert plain["value"] > 0 and plain["roofline_splat"]["pairs_per_frame"] > 0
+    assert plain["roofline_splat"]["tiles_kernel_ms"] is None and "footprints" not in plain["roofline_splat"]
+    full = run_bench(args + ["--full", "--no-cpu-baseline", "--no-extras"])
+    assert full["roofline_splat"]["tiles_kernel_ms"] > 0 and "proxy_over_ideal" in full["roofline_splat"]["footprints"]
+    assert full["roofline_splat"]["pairs_per_frame"] == plain["roofline_splat"]["pairs_per_frame"]

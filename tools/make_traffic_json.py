@@ -12,7 +12,7 @@ if cut:      # the entry cuts are part of the gather: their scratch is written b
     f += cut["FETCH_SIZE"] * 1024; w += cut["WRITE_SIZE"] * 1024
 json.dump({
     "config": "hard:1024x1024:1024:1",
-    "source": f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, tools/prof_all.sh {tag}) over `python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras`, last launch; summary profiles/{tag}_bench_ir_pmc.txt",
+    "source": f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, tools/prof_all.sh {tag}) over `python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-extras`, last launch; summary profiles/{tag}_bench_ir_pmc.txt",
     "kernel": gk + (" + evplp::gather_cut_kernel" if cut else ""), "round": tag, "FETCH_SIZE_KB": g["FETCH_SIZE"], "WRITE_SIZE_KB": g["WRITE_SIZE"],
     "cut_kernel": ({"FETCH_SIZE_KB": cut["FETCH_SIZE"], "WRITE_SIZE_KB": cut["WRITE_SIZE"]} if cut else None),
     "hbm_bytes_per_launch": f + w, "hbm_bytes_per_launch_if_fetch_x2": 2 * f + w,

@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 ROOT=${GRAFT_REPO_ROOT:-$PWD}
 O=$ROOT/gpurun_out/ppm_timeline; rm -rf $O; mkdir -p $O
 cd /tmp
-rocprofv3 --kernel-trace --output-format csv -d $O/kt -- python3 $ROOT/bench.py --workload ppm --steps 30 --warmup 3 --no-cpu-baseline --no-extras > $O/run.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $O/kt -- python3 $ROOT/bench.py --workload ppm --steps 30 --warmup 3 --full --no-cpu-baseline --no-extras > $O/run.log 2>&1
 f=$(find $O/kt -name "*kernel_trace.csv" | head -1)
 cd $ROOT
 python3 - "$f" <<'PY' > $O/timeline.txt

@@ -7,11 +7,11 @@ ROOT=${GRAFT_REPO_ROOT:-$PWD}
 O=$ROOT/gpurun_out/prof_$tag; mkdir -p $O
 cd /tmp
 for wl in ir evplp ppm; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$wl -- python3 $ROOT/bench.py --workload $wl --steps 10 --warmup 2 --no-cpu-baseline --no-extras > $O/kt_$wl.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$wl -- python3 $ROOT/bench.py --workload $wl --steps 10 --warmup 2 --full --no-cpu-baseline --no-extras > $O/kt_$wl.log 2>&1
   f=$(find $O/kt_$wl -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/${tag}_bench_${wl}_kernel_stats.csv
   find $O/kt_$wl -name "*kernel_trace.csv" -delete; find $O/kt_$wl -name "*_agent_info.csv" -delete
 done
-pmc() { wl=$1; name=$2; shift 2; rocprofv3 --pmc "$@" --output-format csv -d $O/pmc_${wl}_$name -- python3 $ROOT/bench.py --workload $wl --steps 2 --warmup 1 --no-cpu-baseline --no-extras > $O/pmc_${wl}_$name.log 2>&1; }
+pmc() { wl=$1; name=$2; shift 2; rocprofv3 --pmc "$@" --output-format csv -d $O/pmc_${wl}_$name -- python3 $ROOT/bench.py --workload $wl --steps 2 --warmup 1 --full --no-cpu-baseline --no-extras > $O/pmc_${wl}_$name.log 2>&1; }
 for wl in ir evplp ppm; do
   pmc $wl a SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_SMEM SQ_INSTS_SALU SQ_INSTS_VALU SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_VALU
   pmc $wl b SQC_DCACHE_HITS SQC_DCACHE_MISSES SQC_DCACHE_REQ SQ_INST_LEVEL_SMEM SQ_INSTS_LDS SQ_INSTS_BRANCH SQ_WAIT_ANY SQ_WAIT_INST_ANY
