@@ -120,6 +120,8 @@ _SIGNATURES = {
     "evplp_default_splat_proxy": (C.c_int, [_P, _P]),
     "evplp_resolve": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, _P]),
     "evplp_present": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32]),
+    "evplp_set_error_reference": (C.c_int, [_P, _P, _P]),
+    "evplp_frame_error": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_double * 3)]),
     "evplp_clear_accumulators": (C.c_int, [_P]),
     "evplp_set_blocks": (C.c_int, [_P, _P, C.c_int32]),
     "evplp_get_blocks": (C.c_int, [_P, _P, C.c_int32]),
@@ -165,6 +167,8 @@ _SIGNATURES = {
     "evplp_group_resolve": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, _P]),
     "evplp_group_present": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32]),
     "evplp_group_present_ex": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_int32]),
+    "evplp_group_set_error_reference": (C.c_int, [_P, _P, _P]),
+    "evplp_group_frame_error": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_double * 3)]),
     "evplp_jitter_sequence": (C.c_int, [C.c_uint32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "evplp_json_query": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int32, C.POINTER(C.c_double), C.c_char_p, C.c_int32]),
     "evplp_progressive_step": (None, [C.c_int32, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.POINTER(C.c_float),
@@ -215,6 +219,21 @@ def _ptr(a: Optional[np.ndarray]):
 
 def _f32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _error_reference(rgb, mask, W: int, H: int):
+    """The arguments of set_error_reference, checked before any C call: rgb float32 (H, W, 3) top-down (None releases), mask uint8 (H, W, 3)."""
+    if rgb is None:
+        if mask is not None:
+            raise ValueError("set_error_reference: a mask without a reference image")
+        return None, None
+    if not isinstance(rgb, np.ndarray) or rgb.dtype != np.float32 or rgb.shape != (H, W, 3):
+        raise ValueError(f"set_error_reference: the reference must be float32 of shape {(H, W, 3)}, got "
+                         f"{getattr(rgb, 'dtype', type(rgb).__name__)} {getattr(rgb, 'shape', None)}")
+    if mask is not None and (not isinstance(mask, np.ndarray) or mask.dtype != np.uint8 or mask.shape != (H, W, 3)):
+        raise ValueError(f"set_error_reference: the mask must be uint8 of shape {(H, W, 3)}, got "
+                         f"{getattr(mask, 'dtype', type(mask).__name__)} {getattr(mask, 'shape', None)}")
+    return np.ascontiguousarray(rgb), None if mask is None else np.ascontiguousarray(mask)
 
 
 def frame_params(camera_pos, mis_mode=0, pdf_mc=0.0, clamping_value=0.0, photon_radius=0.0, vsl_radius=0.0,
@@ -421,6 +440,17 @@ class Context:
 
     def clear_accumulators(self):
         self._check(self._lib.evplp_clear_accumulators(self._h))
+
+    def set_error_reference(self, rgb: Optional[np.ndarray], mask: Optional[np.ndarray] = None):
+        """The reference of frame_error(): float32 (H, W, 3) rows top to bottom, an optional uint8 (H, W, 3) mask; rgb=None releases it."""
+        rgb, mask = _error_reference(rgb, mask, self.W, self.H)
+        self._check(self._lib.evplp_set_error_reference(self._h, _ptr(rgb), _ptr(mask)))
+
+    def frame_error(self, vpl_scale=1.0, photon_scale=1.0, light_scale=1.0, mask_emitter=False, gamma=False):
+        """(mse, rel_mse, rel_mse_masked) of the composite against the reference, reduced on the device over the rows this context holds"""
+        out = (C.c_double * 3)()
+        self._check(self._lib.evplp_frame_error(self._h, vpl_scale, photon_scale, light_scale, int(mask_emitter), int(gamma), C.byref(out)))
+        return out[0], out[1], out[2]
 
     def set_blocks(self, image_blocks=None):
         """row-strip context: own these image blocks (in this local order) instead of the blocks b % strip_count == strip_rank; None = back to that"""
@@ -657,6 +687,17 @@ class Group:
         out = np.empty((self.H, self.W, 3), dtype=np.float32)
         self._check(self._lib.evplp_group_resolve(self._h, vpl_scale, photon_scale, light_scale, int(mask_emitter), int(gamma), _ptr(out)))
         return out
+
+    def set_error_reference(self, rgb: Optional[np.ndarray], mask: Optional[np.ndarray] = None):
+        """Context.set_error_reference on every rank"""
+        rgb, mask = _error_reference(rgb, mask, self.W, self.H)
+        self._check(self._lib.evplp_group_set_error_reference(self._h, _ptr(rgb), _ptr(mask)))
+
+    def frame_error(self, vpl_scale=1.0, photon_scale=1.0, light_scale=1.0, mask_emitter=False, gamma=False):
+        """(mse, rel_mse, rel_mse_masked) of the whole frame against the reference (strips: no all-gather; equal to one context's, bit for bit)"""
+        out = (C.c_double * 3)()
+        self._check(self._lib.evplp_group_frame_error(self._h, vpl_scale, photon_scale, light_scale, int(mask_emitter), int(gamma), C.byref(out)))
+        return out[0], out[1], out[2]
 
 
 def jitter_sequence(rng_offset: int, count: int, res_x: int, res_y: int) -> np.ndarray:

@@ -201,6 +201,7 @@ extern "C" void evplp_destroy(evplp_context *c) {
     hipFree(c->d_tile_cursor); hipFree(c->d_bin_items); hipFree(c->d_bin_items_tmp); hipFree(c->d_seg); hipFree(c->d_seg_off); hipFree(c->d_big_list); hipFree(c->d_big_count);
     hipFree(c->d_compact); hipFree(c->d_tile_box); hipFree(c->d_tile_pairs); hipFree(c->d_summary); hipFree(c->d_heavy_list); hipFree(c->d_tile_flags);
     hipFree(c->d_proxy_slabs); hipFree(c->d_proxy_hm); hipFree(c->d_tile_frags); hipFree(c->d_blocks); hipFree(c->d_block_cost);
+    hipFree(c->d_err_ref); hipFree(c->d_err_keep); hipFree(c->d_err_rows);
     for (int i = 0; i < EVPLP_PASS_COUNT; i++) {
         if (c->ev_begin[i]) hipEventDestroy(c->ev_begin[i]);
         if (c->ev_end[i]) hipEventDestroy(c->ev_end[i]);
@@ -969,14 +970,16 @@ namespace evplp {
 // settle = false (the per-iteration composite of a running loop): the composite is enqueued behind the last splat without waiting for
 // the verdict on its bins -- the host does not stall; in the rare iteration whose bins overflowed the presented frame lacks that one
 // pass (it is run again and lands in the accumulator before the next composite).  Results that leave the device always settle.
-int resolve_to_device(evplp_context *c, float vs, float ps, float ls, int32_t mask_emitter, int32_t gamma, bool settle) {
+// as_pass = false (the composite evplp_frame_error measures): the pass statistics of EVPLP_PASS_RESOLVE stay as they were
+int resolve_to_device(evplp_context *c, float vs, float ps, float ls, int32_t mask_emitter, int32_t gamma, bool settle, bool as_pass) {
     CTX_CHECK(c);
     if (settle) { int rc_ = settle_splat(c); if (rc_) return rc_; }
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     int rc;
-    if ((rc = pass_begin(c, EVPLP_PASS_RESOLVE))) return rc;
+    if (as_pass && (rc = pass_begin(c, EVPLP_PASS_RESOLVE))) return rc;
     launch_resolve(c->st, (const float4 *)c->buf[EVPLP_BUF_VPL_ACCUM], (const float4 *)c->buf[EVPLP_BUF_PHOTON_ACCUM],
                    (const float4 *)c->buf[EVPLP_BUF_LIGHT], vs, ps, ls, mask_emitter, gamma, c->d_rgb, c->stream);
+    if (!as_pass) { HIP_TRY(c, hipGetLastError()); return EVPLP_OK; }
     return pass_end(c, EVPLP_PASS_RESOLVE);
 }
 // every pending photon splat has its verdict (and its re-run, if its bins overflowed, is enqueued): the accumulators are final in
@@ -990,7 +993,7 @@ int settle(evplp_context *c) {
 extern "C" int evplp_resolve(evplp_context *c, float vs, float ps, float ls, int32_t mask_emitter, int32_t gamma, float *out_rgb) {
     CTX_CHECK(c);
     if (!out_rgb) { c->set_error("evplp_resolve: null output"); return EVPLP_ERR_INVALID; }
-    int rc = evplp::resolve_to_device(c, vs, ps, ls, mask_emitter, gamma, true);
+    int rc = evplp::resolve_to_device(c, vs, ps, ls, mask_emitter, gamma, true, true);
     if (rc) return rc;
     HIP_TRY(c, hipMemcpyAsync(out_rgb, c->d_rgb, sizeof(float) * 3 * (size_t)c->st.W * c->st.local_rows, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -999,7 +1002,81 @@ extern "C" int evplp_resolve(evplp_context *c, float vs, float ps, float ls, int
 
 extern "C" int evplp_present(evplp_context *c, float vs, float ps, float ls, int32_t mask_emitter, int32_t gamma) {
     CTX_CHECK(c);
-    return evplp::resolve_to_device(c, vs, ps, ls, mask_emitter, gamma, !c->aux_stream);      // (overlapped contexts keep the host an iteration ahead)
+    return evplp::resolve_to_device(c, vs, ps, ls, mask_emitter, gamma, !c->aux_stream, true);      // (overlapped contexts keep the host an iteration ahead)
+}
+
+// ---- error against a reference image (include/evplp.h evplp_frame_error): reduced on the device, 32 bytes per row come to the host
+static void release_error_reference(evplp_context *c) {
+    hipFree(c->d_err_ref); hipFree(c->d_err_keep); hipFree(c->d_err_rows);
+    c->d_err_ref = nullptr; c->d_err_keep = nullptr; c->d_err_rows = nullptr; c->err_rows.clear();
+}
+extern "C" int evplp_set_error_reference(evplp_context *c, const float *rgb, const uint8_t *mask) {
+    CTX_CHECK(c);
+    if (!rgb && mask) { c->set_error("evplp_set_error_reference: a mask without a reference image"); return EVPLP_ERR_INVALID; }
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));      // (no composite or reduction of an earlier call still reads the old image)
+    if (!rgb) { release_error_reference(c); return EVPLP_OK; }
+    const size_t px = (size_t)c->st.W * c->st.H;
+    std::vector<uint8_t> keep;
+    if (mask) { keep.resize(px); for (size_t i = 0; i < px; i++) keep[i] = (mask[3 * i] | mask[3 * i + 1] | mask[3 * i + 2]) != 0 ? 1 : 0; }
+    hipError_t e = hipSuccess;
+    if (!c->d_err_ref) e = hipMalloc((void **)&c->d_err_ref, sizeof(float) * 3 * px);
+    if (e == hipSuccess && !c->d_err_rows) e = hipMalloc((void **)&c->d_err_rows, sizeof(RowError) * (size_t)std::max(c->st.local_rows, 1));
+    if (e == hipSuccess && mask && !c->d_err_keep) e = hipMalloc((void **)&c->d_err_keep, px);
+    if (e != hipSuccess) {
+        (void)hipGetLastError(); release_error_reference(c);
+        c->set_error("evplp_set_error_reference: cannot allocate %zu bytes: %s", px * 13, hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP;
+    }
+    if (!mask) { hipFree(c->d_err_keep); c->d_err_keep = nullptr; }
+    e = hipMemcpy(c->d_err_ref, rgb, sizeof(float) * 3 * px, hipMemcpyHostToDevice);
+    if (e == hipSuccess && mask) e = hipMemcpy(c->d_err_keep, keep.data(), px, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { release_error_reference(c); c->set_error("evplp_set_error_reference: upload: %s", hipGetErrorString(e)); return EVPLP_ERR_HIP; }
+    c->err_rows.assign((size_t)std::max(c->st.local_rows, 1), RowError{});
+    return EVPLP_OK;
+}
+namespace evplp {
+// the partials of every local row of the composite in d_rgb, to c->err_rows (waits for them)
+int frame_error_rows(evplp_context *c) {
+    CTX_CHECK(c);
+    if (!c->d_err_ref) { c->set_error("evplp_frame_error: no reference image (evplp_set_error_reference)"); return EVPLP_ERR_INVALID; }
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    launch_frame_error(c->st, c->d_rgb, c->d_err_ref, c->d_err_keep, c->d_err_rows, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(c->err_rows.data(), c->d_err_rows, sizeof(RowError) * (size_t)c->st.local_rows, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return EVPLP_OK;
+}
+// c->err_rows put at their image rows
+void place_row_errors(const evplp_context *c, std::vector<RowError> &rows, std::vector<char> &held) {
+    for (int l = 0; l < c->st.local_rows; l++) {
+        const int y = c->st.global_row(l);
+        if (y < 0 || y >= c->st.H) continue;
+        rows[(size_t)y] = c->err_rows[(size_t)l]; held[(size_t)y] = 1;
+    }
+}
+void sum_row_errors(const std::vector<RowError> &rows, const std::vector<char> &held, double npix, double out[3]) {
+    RowError t{ 0.0, 0.0, 0.0, 0.0 };
+    for (size_t y = 0; y < rows.size(); y++) {
+        if (!held[y]) continue;
+        t.num += rows[y].num; t.rel += rows[y].rel; t.rel_kept += rows[y].rel_kept; t.kept += rows[y].kept;
+    }
+    out[0] = npix > 0 ? t.num / npix : 0.0;
+    out[1] = npix > 0 ? t.rel / npix : 0.0;
+    out[2] = t.kept > 0 ? t.rel_kept / t.kept : 0.0;
+}
+} // namespace evplp
+extern "C" int evplp_frame_error(evplp_context *c, float vs, float ps, float ls, int32_t mask_emitter, int32_t gamma, double out[3]) {
+    CTX_CHECK(c);
+    if (!out) { c->set_error("evplp_frame_error: null output"); return EVPLP_ERR_INVALID; }
+    if (!c->d_err_ref) { c->set_error("evplp_frame_error: no reference image (evplp_set_error_reference)"); return EVPLP_ERR_INVALID; }
+    int rc = evplp::resolve_to_device(c, vs, ps, ls, mask_emitter, gamma, true, false);
+    if (rc) return rc;
+    if ((rc = evplp::frame_error_rows(c))) return rc;
+    std::vector<RowError> rows((size_t)c->st.H); std::vector<char> held((size_t)c->st.H, 0);
+    evplp::place_row_errors(c, rows, held);
+    evplp::sum_row_errors(rows, held, (double)c->st.W * c->rows_in_image, out);
+    return EVPLP_OK;
 }
 
 static void count_rows_in_image(evplp_context *c) {

@@ -18,6 +18,10 @@ struct HostStats { uint64_t rays = 0; };
 struct ProxyHost { std::vector<float4> slabs; std::vector<float> hm; int32_t planes = 0; float rin = 0.f, rout = 0.f; };
 void default_splat_proxy(std::vector<float> &verts, std::vector<int32_t> &tris);
 bool build_proxy_slabs(const float *verts, int32_t nverts, const int32_t *tris, int32_t ntris, ProxyHost *out, std::string *why);
+// evplp_frame_error (context.cpp): the error figures from per-IMAGE-row partials, added in image row order (rows with held[y] = 0 are
+// skipped): out = { sum num / npix, sum rel / npix, sum rel over kept pixels / kept pixels (0 when none) }.  The one place the rows are
+// added, for a context and for a group alike: the figure is then a function of the frame alone, whatever holds which rows.
+void sum_row_errors(const std::vector<RowError> &rows, const std::vector<char> &held, double npix, double out[3]);
 }
 
 struct evplp_context {
@@ -112,6 +116,11 @@ struct evplp_context {
     // A context that belongs to an evplp_group is driven by that rank's worker thread (group.cpp).  A call from any other thread -- the
     // caller reading statistics or buffers through evplp_group_context -- first waits until the worker has nothing queued for it.
     void (*quiesce)(void *) = nullptr; void *quiesce_arg = nullptr; std::thread::id worker_tid{};
+
+    // evplp_set_error_reference: the WHOLE reference image (rows top to bottom, 3 floats per pixel) and the mask as one keep byte per pixel
+    // (null: every pixel is kept), so that a new block table needs no new upload; evplp_frame_error's per-row partials, [local_rows]
+    float *d_err_ref = nullptr; uint8_t *d_err_keep = nullptr;
+    evplp::RowError *d_err_rows = nullptr; std::vector<evplp::RowError> err_rows;
 
     char error[512] = "";
     void set_error(const char *fmt, ...);

@@ -40,8 +40,10 @@
 #include <vector>
 
 namespace evplp {
-int resolve_to_device(evplp_context *c, float vs, float ps, float ls, int32_t mask_emitter, int32_t gamma, bool settle);   // context.cpp
+int resolve_to_device(evplp_context *c, float vs, float ps, float ls, int32_t mask_emitter, int32_t gamma, bool settle, bool as_pass);   // context.cpp
 int settle(evplp_context *c);                                                                                                  // context.cpp
+int frame_error_rows(evplp_context *c);                                                                                        // context.cpp
+void place_row_errors(const evplp_context *c, std::vector<RowError> &rows, std::vector<char> &held);                          // context.cpp
 }
 
 namespace {
@@ -61,7 +63,7 @@ struct Rccl {
     }
 };
 
-enum Op { OP_QUIT = 0, OP_CLEAR, OP_SYNC, OP_PRIMARY, OP_TRACE, OP_GATHER, OP_SPLAT, OP_PATH_TRACE, OP_PRESENT, OP_LOAD_SCENE, OP_SET_PROXY, OP_ASSEMBLE, OP_REDUCE };
+enum Op { OP_QUIT = 0, OP_CLEAR, OP_SYNC, OP_PRIMARY, OP_TRACE, OP_GATHER, OP_SPLAT, OP_PATH_TRACE, OP_PRESENT, OP_LOAD_SCENE, OP_SET_PROXY, OP_ASSEMBLE, OP_REDUCE, OP_SET_REFERENCE, OP_FRAME_ERROR };
 // One posted call: plain data, copied into the ring (pointers must stay valid until the caller has drained: load_scene, set_proxy, resolve do)
 struct Cmd {
     int op = OP_QUIT;
@@ -124,6 +126,7 @@ struct evplp_group {
     // EVPLP_PARTITION_ITERATIONS: every rank renders whole frames; the pass calls go to `selected`; a present with exchange / a resolve sums
     // the ranks' planes (OP_REDUCE).  sums_fresh (caller's thread): no pass was posted since the last reduction -- the cached sums still hold
     bool iterations = false; int selected = 0; bool sums_fresh = false;
+    bool have_reference = false;            // evplp_group_set_error_reference has given every rank an image (caller's thread)
     size_t plane_px = 0;                    // W * local_rows: the pixels of one accumulator plane
     std::vector<float4 *> d_sum;            // per rank: [3][plane_px] VPL, photon and light planes reduced over the ranks (the first reduction)
     std::vector<float4 *> d_stage;          // per rank, RCCL only: [n][plane_px] one plane of every rank (all-gathered)
@@ -268,9 +271,11 @@ static void worker_run(Worker *w, const Cmd &cmd) {
         case OP_GATHER: rc = cmd.i[0] == 0 ? evplp_gather_vpl(c, &cmd.fp) : cmd.i[0] == 1 ? evplp_gather_vsl(c, &cmd.fp) : evplp_gather_lvc(c, &cmd.fp); break;
         case OP_SPLAT: rc = evplp_splat_photons(c, &cmd.fp, cmd.i[0]); break;
         case OP_PATH_TRACE: rc = evplp_path_trace(c, cmd.f, cmd.u[0], cmd.u[1], cmd.i[0]); break;
-        case OP_PRESENT: rc = evplp::resolve_to_device(c, cmd.f[0], cmd.f[1], cmd.f[2], cmd.i[0], cmd.i[1], cmd.i[2] != 0 || !c->aux_stream); break;
+        case OP_PRESENT: rc = evplp::resolve_to_device(c, cmd.f[0], cmd.f[1], cmd.f[2], cmd.i[0], cmd.i[1], cmd.i[2] != 0 || !c->aux_stream, cmd.u[0] == 0); break;   // (u[0]: the composite evplp_group_frame_error measures)
         case OP_LOAD_SCENE: rc = evplp_load_scene_json(c, (const char *)cmd.p0); break;
         case OP_SET_PROXY: rc = evplp_set_splat_proxy(c, (const float *)cmd.p0, cmd.i[0], (const int32_t *)cmd.p1, cmd.i[1]); break;
+        case OP_SET_REFERENCE: rc = evplp_set_error_reference(c, (const float *)cmd.p0, (const uint8_t *)cmd.p1); break;
+        case OP_FRAME_ERROR: rc = evplp::frame_error_rows(c); break;          // (behind this rank's composite, on its stream)
         case OP_ASSEMBLE: {
             // rank 0 puts the strips into image order on the device; one copy lands the frame in the caller's buffer (no host-side assembly:
             // a run that writes every frame resolves every iteration)
@@ -668,4 +673,40 @@ extern "C" int evplp_group_resolve(evplp_group *g, float vs, float ps, float ls,
     post(g->workers[0], c);
     drain(g);
     return group_status(g);
+}
+
+// The error of the frame against a reference image (include/evplp.h).  Strips: every rank composites its rows and reduces them on its GPU,
+// and 32 bytes per row come to the host -- no all-gather.  Iterations: the reduction evplp_group_resolve runs (or its cached sums), then
+// rank 0 reduces the summed composite.  The rows are added on the caller's thread in image row order, by the helper a single context uses.
+extern "C" int evplp_group_set_error_reference(evplp_group *g, const float *rgb, const uint8_t *mask) {
+    GRP_CHECK(g);
+    if (!rgb && mask) { g->set_error("evplp_group_set_error_reference: a mask without a reference image"); return EVPLP_ERR_INVALID; }
+    Cmd c; c.op = OP_SET_REFERENCE; c.p0 = rgb; c.p1 = mask;
+    const int rc = post_and_wait(g, c);             // (the caller's images are read before the call returns)
+    g->have_reference = rc >= 0 && rgb != nullptr;
+    return rc;
+}
+extern "C" int evplp_group_frame_error(evplp_group *g, float vs, float ps, float ls, int32_t mask_emitter, int32_t gamma, double out[3]) {
+    GRP_CHECK(g);
+    if (!out) { g->set_error("evplp_group_frame_error: null output"); return EVPLP_ERR_INVALID; }
+    if (!g->have_reference) { g->set_error("evplp_group_frame_error: no reference image (evplp_group_set_error_reference)"); return EVPLP_ERR_INVALID; }
+    Cmd c; c.op = OP_FRAME_ERROR;
+    int rc;
+    if (g->iterations) {
+        rc = post_reduce(g, vs, ps, ls, mask_emitter, gamma);
+        if (rc >= 0) post(g->workers[0], c);
+    } else {
+        Cmd p = present_cmd(vs, ps, ls, mask_emitter, gamma, true, false);      // (every rank's own rows: nothing is exchanged; not a pass)
+        p.u[0] = 1;
+        rc = post_all(g, p);
+        if (rc >= 0) rc = post_all(g, c);
+    }
+    if (rc < 0) return rc;
+    drain(g);
+    if ((rc = group_status(g)) < 0) return rc;
+    const evplp_context *c0 = g->ctx[0];
+    std::vector<evplp::RowError> rows((size_t)c0->st.H); std::vector<char> held((size_t)c0->st.H, 0);
+    for (int r = 0; r < (g->iterations ? 1 : g->n); r++) evplp::place_row_errors(g->ctx[(size_t)r], rows, held);
+    evplp::sum_row_errors(rows, held, (double)c0->st.W * c0->st.H, out);
+    return EVPLP_OK;
 }

@@ -189,6 +189,112 @@ struct JitterSampler {
         jitter[0] = (2.0f * ux - 1.0f) * (1.0f / (float)W); jitter[1] = (2.0f * uy - 1.0f) * (1.0f / (float)H);
     }
 };
+// a file named in the technique block that cannot be read (evplp_render_json: EVPLP_ERR_IO)
+struct IoError : std::runtime_error { using std::runtime_error::runtime_error; };
+
+// Build-only key "convergence" (not a reference key; the reference leaves error curves to external scripts): the error of the image the
+// run saves as its result against a reference image, measured on the device at checkpoints of the running loop (evplp_group_frame_error:
+// 32 bytes per image row come to the host, nothing else) and written as one JSON file.
+//   {"reference": "ref.pfm", "mask": "mask.png", "everyIterations": 10, "everyMs": 250, "stopRelMse": 0.01, "filename": "curve.json"}
+// reference (PFM / HDR, evplp_load_image) and filename are required; mask (evplp_decode_image) is optional; paths resolve as splatProxy's.
+// Checkpoints: after iteration i (counted from 1) when everyIterations divides i; when the wall clock has passed the next multiple of
+// everyMs (missed multiples are skipped); always one after the loop's last synchronise, unless the last one already saw that iteration.  A
+// checkpoint waits as the loop does before it looks at the clock, takes timeMs (wall clock since the loop's start, earlier checkpoints'
+// overhead included) and then measures; the time inside the error call is summed as overheadMs.  A time limit stays wall clock, overhead
+// included.  stopRelMse ends the run at the first checkpoint whose relMSE (the masked one with a mask) is <= it.  Everything is validated
+// before the group exists: a bad block costs no GPU time.
+class Convergence {
+public:
+    bool on = false;
+    void parse(const Json &tech, const std::string &json_dir, const std::string &out_dir, int W, int H) {
+        if (!tech.has("convergence")) return;
+        const Json &c = tech.at("convergence");
+        if (!c.is_object()) throw JsonError("convergence: expected an object");
+        for (const char *k : { "reference", "filename" }) if (!c.has(k)) throw JsonError(std::string("convergence.") + k + ": missing required key");
+        reference = c.at("reference").as_string("convergence.reference");
+        filename = output_path(out_dir, c.at("filename").as_string("convergence.filename"));
+        if (c.has("everyIterations")) {
+            every_iterations = c.at("everyIterations").as_int("convergence.everyIterations");
+            if (every_iterations <= 0) throw JsonError("convergence.everyIterations: must be > 0");
+        }
+        if (c.has("everyMs")) {
+            every_ms = c.at("everyMs").as_number("convergence.everyMs");
+            if (!(every_ms > 0.0)) throw JsonError("convergence.everyMs: must be > 0");
+            next_ms = every_ms;
+        }
+        if (c.has("stopRelMse")) {
+            stop_rel_mse = c.at("stopRelMse").as_number("convergence.stopRelMse");
+            if (!(stop_rel_mse >= 0.0)) throw JsonError("convergence.stopRelMse: must be >= 0");
+        }
+        const std::string ref_path = join_path(json_dir, reference);
+        int32_t w = 0, h = 0;
+        if (evplp_load_image(ref_path.c_str(), &w, &h, nullptr, 0) != EVPLP_OK) throw IoError("convergence.reference: cannot read " + ref_path);
+        if (w != W || h != H)
+            throw JsonError("convergence.reference: " + ref_path + " is " + std::to_string(w) + " x " + std::to_string(h) + ", the scene renders " + std::to_string(W) + " x " + std::to_string(H));
+        ref.resize((size_t)W * H * 3);
+        if (evplp_load_image(ref_path.c_str(), &w, &h, ref.data(), ref.size()) != EVPLP_OK) throw IoError("convergence.reference: cannot read " + ref_path);
+        if (c.has("mask")) {
+            const std::string mask_path = join_path(json_dir, c.at("mask").as_string("convergence.mask"));
+            int32_t ch = 0;
+            if (evplp_decode_image(mask_path.c_str(), &w, &h, &ch, nullptr, 0) != EVPLP_OK) throw IoError("convergence.mask: cannot read " + mask_path);
+            if (w != W || h != H)
+                throw JsonError("convergence.mask: " + mask_path + " is " + std::to_string(w) + " x " + std::to_string(h) + ", the scene renders " + std::to_string(W) + " x " + std::to_string(H));
+            mask.resize((size_t)W * H * 3);
+            if (evplp_decode_image(mask_path.c_str(), &w, &h, &ch, mask.data(), mask.size()) != EVPLP_OK) throw IoError("convergence.mask: cannot read " + mask_path);
+            for (size_t i = 0; i < (size_t)W * H; i++) kept += (mask[3 * i] | mask[3 * i + 1] | mask[3 * i + 2]) != 0 ? 1 : 0;
+        }
+        pixels = (int64_t)W * H;
+        on = true;
+    }
+    void upload(evplp_group *g) const {
+        if (on) check(g, evplp_group_set_error_reference(g, ref.data(), mask.empty() ? nullptr : mask.data()), "convergence reference");
+    }
+    // after iteration i of the loop, the host clock at hand (no wait yet)
+    bool due(int i, double now_ms) const {
+        return on && ((every_iterations > 0 && i % every_iterations == 0) || (every_ms > 0.0 && now_ms >= next_ms));
+    }
+    // wait_and_clock: the loop's wait, then the wall clock.  Returns true when stopRelMse is reached.
+    template <class WaitAndClock>
+    bool checkpoint(evplp_group *g, int i, WaitAndClock wait_and_clock, float vs, float ps, float ls, int32_t mask_emitter) {
+        const double t = wait_and_clock();
+        const auto t0 = std::chrono::steady_clock::now();
+        Point p; p.iteration = i; p.time_ms = t;
+        check(g, evplp_group_frame_error(g, vs, ps, ls, mask_emitter, 0, p.e), "convergence");
+        overhead_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        points.push_back(p);
+        if (every_ms > 0.0) next_ms = (std::floor(t / every_ms) + 1.0) * every_ms;
+        return stop_rel_mse >= 0.0 && (mask.empty() ? p.e[1] : p.e[2]) <= stop_rel_mse;
+    }
+    // the final checkpoint (after the loop's last synchronise): none when the last one saw this iteration already
+    void finish(evplp_group *g, int i, double now_ms, float vs, float ps, float ls, int32_t mask_emitter) {
+        if (!on) return;
+        if (points.empty() || points.back().iteration != i) checkpoint(g, i, [&] { return now_ms; }, vs, ps, ls, mask_emitter);
+        std::string s = "{\n    \"reference\": " + quoted(reference) + ",\n    \"pixels\": " + std::to_string(pixels) + ",\n";
+        if (!mask.empty()) s += "    \"keptPixels\": " + std::to_string(kept) + ",\n";
+        s += "    \"overheadMs\": " + num(overhead_ms) + ",\n    \"checkpoints\": [";
+        for (size_t k = 0; k < points.size(); k++) {
+            const Point &p = points[k];
+            s += std::string(k ? ",\n" : "\n") + "        {\"iteration\": " + std::to_string(p.iteration) + ", \"timeMs\": " + num(p.time_ms) +
+                 ", \"mse\": " + num(p.e[0]) + ", \"relMse\": " + num(p.e[1]);
+            if (!mask.empty()) s += ", \"relMseMasked\": " + num(p.e[2]);
+            s += "}";
+        }
+        s += "\n    ]\n}\n";
+        std::ofstream of(filename);
+        if (!of || !(of << s)) throw std::runtime_error("cannot write " + filename);
+    }
+
+private:
+    struct Point { int iteration = 0; double time_ms = 0.0; double e[3] = { 0.0, 0.0, 0.0 }; };
+    static std::string num(double v) { if (!std::isfinite(v)) return "null"; char b[40]; std::snprintf(b, sizeof b, "%.17g", v); return b; }     // (every bit of the double)
+    static std::string quoted(const std::string &v) { Json j = Json::string(v); return j.dump(); }
+    std::string reference, filename;
+    std::vector<float> ref; std::vector<uint8_t> mask;
+    int64_t pixels = 0, kept = 0;
+    long long every_iterations = 0;
+    double every_ms = 0.0, next_ms = 0.0, stop_rel_mse = -1.0, overhead_ms = 0.0;
+    std::vector<Point> points;
+};
 } // namespace
 
 // The reference's ground-truth technique: unidirectional path tracing with next-event estimation, one sample per
@@ -215,6 +321,7 @@ public:
         write_every_frame = json.has("writeEveryFrame") ? json.at("writeEveryFrame").as_bool("writeEveryFrame") : false;
         int bvh_builder = EVPLP_BVH_SAH;
         if (json.has("bvhBuilder")) bvh_builder = parse_bvh_builder(json.at("bvhBuilder").as_string("bvhBuilder"));
+        conv.parse(json, out_dir, out_dir, res_x, res_y);
 
         evplp_config cfg; std::memset(&cfg, 0, sizeof(cfg));
         cfg.abi_version = EVPLP_ABI_VERSION; cfg.device = device; cfg.res_x = res_x; cfg.res_y = res_y;
@@ -223,6 +330,7 @@ public:
         cfg.bvh_builder = bvh_builder;
         Grp grp; create_group(grp, cfg, json, device);
         upload_scene_group(grp.g, scene);
+        conv.upload(grp.g);
         run(grp.g, scene, res_x, res_y);
     }
 
@@ -249,10 +357,15 @@ private:
                 save(h, W, H, num_iterations, output_filename.substr(0, i) + "_" + std::to_string(num_iterations) + output_filename.substr(i), rgb);
             }
             if (time_limit_ms < 1e8f) check(h, evplp_group_synchronize(h), "sync");
+            if (conv.due(num_iterations, elapsed_ms())) {
+                const Composite k = composite(num_iterations);
+                if (conv.checkpoint(h, num_iterations, [&] { check(h, evplp_group_synchronize(h), "sync"); return (double)elapsed_ms(); }, k.vs, k.ps, k.ls, k.mask_emitter)) break;
+            }
             if (elapsed_ms() >= time_limit_ms) break;                                         // :667
         }
         check(h, evplp_group_synchronize(h), "sync");
         float time = elapsed_ms();
+        { const Composite k = composite(num_iterations); conv.finish(h, num_iterations, elapsed_ms(), k.vs, k.ps, k.ls, k.mask_emitter); }
         if (use_stat) {                                                                       // :694-704
             Json st = Json::object();
             st.set("time", Json::number(time)); st.set("numIterations", Json::number(num_iterations));
@@ -264,9 +377,11 @@ private:
         save(h, W, H, num_iterations, output_filename, rgb);                                  // :706-719
     }
     // clear-every-frame: the composite as shown (masked emitter); accumulate: light image + path-traced image / n
+    struct Composite { float vs, ps, ls; int32_t mask_emitter; };
+    Composite composite(int n) const { return frame_mode == 2 ? Composite{ 1.0f, 0.0f, 1.0f, 1 } : Composite{ 1.0f / (float)std::max(n, 1), 0.0f, 1.0f, 0 }; }
     void save(evplp_group *h, int W, int H, int n, const std::string &path, std::vector<float> &rgb) {
-        if (frame_mode == 2) check(h, evplp_group_resolve(h, 1.0f, 0.0f, 1.0f, 1, 0, rgb.data()), "resolve");
-        else check(h, evplp_group_resolve(h, 1.0f / (float)std::max(n, 1), 0.0f, 1.0f, 0, 0, rgb.data()), "resolve");
+        const Composite k = composite(n);
+        check(h, evplp_group_resolve(h, k.vs, k.ps, k.ls, k.mask_emitter, 0, rgb.data()), "resolve");
         std::vector<float> top = flip_y(rgb, W, H);
         if (save_image(path.c_str(), W, H, top.data()) != EVPLP_OK) throw std::runtime_error("cannot write " + path);
     }
@@ -275,6 +390,7 @@ private:
     float time_limit_ms = 0.f;
     bool use_jitter = false, use_stat = false, write_every_frame = false;
     std::string output_filename, stat_filename;
+    Convergence conv;
 };
 
 class ComPhotonTechnique {
@@ -330,6 +446,7 @@ public:
         if (num_vpl_light_paths == 0) { std::printf("WARN: 0 VPL light paths. Disable mDoVplSplat\n"); do_vpl_splat = false; }   // :200-203
         if (!lvc && json.has("forceVsl")) force_vsl = json.at("forceVsl").as_bool("forceVsl");
         if (json.has("bvhBuilder")) bvh_builder = parse_bvh_builder(json.at("bvhBuilder").as_string("bvhBuilder"));   // build-only key
+        conv.parse(json, out_dir, out_dir, res_x, res_y);                                                          // build-only key
 
         // ---- setup(): context + scene upload (replaces GL/OptiX setup :646-708)
         evplp_config cfg; std::memset(&cfg, 0, sizeof(cfg));
@@ -355,6 +472,7 @@ public:
         create_group(grp, cfg, json, device, run_opts.shard_iterations);
         upload_scene_group(grp.g, scene);
         splat_footprint = setup_splat_footprint(grp.g, json, out_dir);                                           // :677
+        conv.upload(grp.g);
         float bsr = 0.f, total_area = 0.f, light_area = 0.f;
         { evplp_context *h0 = evplp_group_context(grp.g, 0);
           if (evplp_scene_metrics(h0, &bsr, &total_area, &light_area) < 0) throw std::runtime_error(std::string("scene metrics: ") + evplp_last_error(h0)); }
@@ -469,10 +587,14 @@ private:
                                        &photon_radius, &clamping_value, &pdf_mc, force_vsl ? 1 : 0, &vsl_radius, &vsl_inv_pi_radius2);
             if (write_every_frame) dump_frame(h, W, H, num_iterations, rgb);                  // :1079-1102
             if (time_limit_ms < 1e8f) wait_for_next();                                        // a wall-clock limit needs finished frames
+            // the combinedFilename composite over ALL iterations so far (:1122; an iteration partition reduces the ranks' sums first)
+            if (conv.due(num_iterations, elapsed_ms()) &&
+                conv.checkpoint(h, num_iterations, [&] { wait_for_next(); return (double)elapsed_ms(); }, saved_param(num_iterations), saved_param(num_iterations), 1.0f, 0)) break;
             if (elapsed_ms() >= time_limit_ms) break;                                         // :1065
         }
         check(h, evplp_group_synchronize(h), "sync");                                         // (every iteration posted has finished)
         float time = elapsed_ms();
+        conv.finish(h, num_iterations, elapsed_ms(), saved_param(num_iterations), saved_param(num_iterations), 1.0f, 0);
         check(h, evplp_group_profile_passes(h, 1), "profile");
         if (use_stat) {                                                                       // :1109-1119
             Json st = Json::object();
@@ -483,7 +605,7 @@ private:
             if (!of) throw std::runtime_error("cannot write " + stat_filename);
             of << st.dump() << "\n";
         }
-        float param = frame_mode == 2 ? 1.0f : 1.0f / (float)std::max(num_iterations, 1);     // :1122
+        float param = saved_param(num_iterations);                                            // :1122
         // :1124-1132: three composites, un-masked sums, FlipY, Save (iterations: the first reduces, the other two composite the cached sums)
         auto compose = [&](float vs, float ps, float ls) {
             check(h, evplp_group_resolve(h, vs, ps, ls, 0, 0, rgb.data()), "resolve");
@@ -496,6 +618,8 @@ private:
         if (save_image(weighted_vpl_filename.c_str(), W, H, vpl.data()) != EVPLP_OK) throw std::runtime_error("cannot write " + weighted_vpl_filename);
         if (save_image(weighted_photon_filename.c_str(), W, H, pm.data()) != EVPLP_OK) throw std::runtime_error("cannot write " + weighted_photon_filename);
     }
+
+    float saved_param(int n) const { return frame_mode == 2 ? 1.0f : 1.0f / (float)std::max(n, 1); }     // :1122
 
     void dump_frame(evplp_group *h, int W, int H, int iter, std::vector<float> &rgb) {
         float param = frame_mode == 2 ? 1.0f : 1.0f / (float)iter;                            // :1088
@@ -519,6 +643,7 @@ private:
     bool lvc = false;
     uint32_t splat_footprint = EVPLP_FOOTPRINT_PROXY;
     RunOptions run_opts;
+    Convergence conv;
     int bvh_builder = EVPLP_BVH_SAH;   // measured 9% faster frames than the Morton LBVH on the conference stand-in; "bvhBuilder": "lbvh" selects the LBVH
 };
 
@@ -613,6 +738,7 @@ extern "C" int evplp_render_json(const char *json_path, const char *json_overrid
         }
         if (!ran) return fail(EVPLP_ERR_PARSE, "no technique block (\"pt\", \"photonfam\", \"lvcphotonfam\") in the scene JSON");
     } catch (const JsonError &e) { return fail(EVPLP_ERR_PARSE, e.what()); }
+    catch (const IoError &e) { return fail(EVPLP_ERR_IO, e.what()); }
     catch (const std::exception &e) { return fail(EVPLP_ERR_HIP, e.what()); }
     return EVPLP_OK;
 }

@@ -234,5 +234,11 @@ void launch_assemble_strips(const StripDev &st, int nranks, const uint32_t *owne
 struct ShardPlanes { const float4 *p[64]; };
 void launch_reduce_shards(const ShardPlanes &src, int n, int first_nonzero, size_t count, float4 *out, int num_cus, hipStream_t s);
 void launch_fill_zero(void *p, size_t bytes, hipStream_t s);
+// evplp_frame_error: one image row's figures against the reference (frame_error_kernel, kernels_trace.hip); kept = pixels the mask keeps
+struct RowError { double num, rel, rel_kept, kept; };
+static_assert(sizeof(RowError) == 32, "RowError must be 32 bytes");
+// rgb: the composite (local rows, y = 0 at the bottom); ref: [H][W][3] and keep: [H][W] (null = every pixel), both rows top to bottom;
+// rows: [local_rows], zeros for a local row outside the image
+void launch_frame_error(const StripDev &st, const float *rgb, const float *ref, const uint8_t *keep, RowError *rows, hipStream_t s);
 
 } // namespace evplp

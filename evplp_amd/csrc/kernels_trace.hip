@@ -274,6 +274,51 @@ __global__ __launch_bounds__(1024) void compact_vpl_kernel(const evplp_record *r
     if (tid == 0) *count_out = base;
 }
 
+// evplp_frame_error: the composite against a reference image, one workgroup per local row.  The per-pixel terms are fp32 in the order of
+// floatimage.cpp:64-112 -- d = img - ref, num = d.x^2 + d.y^2 + d.z^2, den = |ref|^2 + 0.001, rel = num / den -- every operation rounded
+// on its own (no contraction, a correctly rounded division), so that numpy's float32 reproduces every term.  They are summed in fp64 in a
+// fixed shape: thread t takes the pixels t, t + 256, .. of the row in increasing x, each wave folds its lanes by a fixed shuffle tree, and
+// thread 0 adds the four waves in order.  A row's figures are a function of the row alone -- not of the rank that holds it, nor of its
+// local row -- and nothing is atomic; the host adds the rows in image order (evplp::sum_row_errors).
+constexpr int kFrameErrorThreads = 256;
+__global__ __launch_bounds__(kFrameErrorThreads) void frame_error_kernel(StripDev st, const float *rgb, const float *ref, const uint8_t *keep, RowError *rows) {
+    __shared__ double wave_sums[kFrameErrorThreads / 64][4];
+    const int l = (int)blockIdx.x, tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int y = st.global_row(l);
+    double s[4] = { 0.0, 0.0, 0.0, 0.0 };
+    if (y < st.H) {
+        const size_t own = (size_t)l * st.W, top = (size_t)(st.H - 1 - y) * st.W;     // (the reference's rows run top to bottom)
+        for (int x = tid; x < st.W; x += kFrameErrorThreads) {
+            const float *a = rgb + 3 * (own + x), *r = ref + 3 * (top + x);
+            const float rx = r[0], ry = r[1], rz = r[2];
+            const float dx = __fsub_rn(a[0], rx), dy = __fsub_rn(a[1], ry), dz = __fsub_rn(a[2], rz);
+            const float num = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+            const float den = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(rx, rx), __fmul_rn(ry, ry)), __fmul_rn(rz, rz)), 0.001f);
+            const float rel = __fdiv_rn(num, den);
+            s[0] += (double)num; s[1] += (double)rel;
+            if (!keep || keep[top + x]) { s[2] += (double)rel; s[3] += 1.0; }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        for (int off = 32; off > 0; off >>= 1) s[k] += __shfl_down(s[k], off, 64);
+    if (lane == 0) for (int k = 0; k < 4; k++) wave_sums[wave][k] = s[k];
+    __syncthreads();
+    if (tid == 0) {
+        double t[4];
+        for (int k = 0; k < 4; k++) {
+            t[k] = wave_sums[0][k];
+            for (int w = 1; w < kFrameErrorThreads / 64; w++) t[k] += wave_sums[w][k];
+        }
+        rows[l] = RowError{ t[0], t[1], t[2], t[3] };
+    }
+}
+
+void launch_frame_error(const StripDev &st, const float *rgb, const float *ref, const uint8_t *keep, RowError *rows, hipStream_t s) {
+    if (st.local_rows <= 0) return;
+    hipLaunchKernelGGL(frame_error_kernel, dim3((unsigned)st.local_rows), dim3(kFrameErrorThreads), 0, s, st, rgb, ref, keep, rows);
+}
+
 void launch_primary(const PrimaryArgs &a, hipStream_t s) {
     int tiles_x = (a.st.W + 7) / 8, tiles_y = (a.st.local_rows + 7) / 8;
 #if EVPLP_PRIMARY_BLOCKS

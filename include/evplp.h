@@ -118,6 +118,7 @@ typedef struct evplp_config {
      *   VSL masks (bounded, above)      -                -                 -               2 GB of 8.6  (in five launches)
      *   photon bins + compact photons   -                0.5 GB            0.4 GB          0.5 GB
      *   scene (331 k triangles)         0.1 GB everywhere (nodes, leaf blocks in two layouts, attributes; textures on top)
+     *   error reference (if set)        12 B + 1 B (mask) per pixel of the WHOLE image on every context (evplp_set_error_reference)
      * A caller that has the device to itself sets cut_scratch_bytes = 72 GB, vsl_mask_bytes = 14 GB for config #5 (one band, one launch). */
     uint64_t cut_scratch_bytes;
     uint64_t vsl_mask_bytes;
@@ -290,6 +291,20 @@ int evplp_resolve(evplp_context *ctx, float vpl_scale, float photon_scale, float
  * settle first and are exact. */
 int evplp_present(evplp_context *ctx, float vpl_scale, float photon_scale, float light_scale, int32_t mask_emitter, int32_t gamma);
 int evplp_clear_accumulators(evplp_context *ctx);
+/* Error against a reference image, reduced on the device (the regime of an equal-time comparison: error over time without reading frames back).
+ * Reference image for evplp_frame_error: W x H RGB float, rows top to bottom (as evplp_load_image returns them).
+ * The mask is optional: 3 bytes per pixel, top to bottom, as evplp_decode_image returns them; a pixel is kept when any of its bytes is
+ * non-zero (as evplp_image_rel_mse_masked).  rgb = NULL releases the reference.  Every context keeps the whole image, so set_blocks /
+ * rebalance need no re-upload.  The images are copied before the call returns.  Device memory: 12 B + 1 B (mask) per image pixel. */
+int evplp_set_error_reference(evplp_context *ctx, const float *rgb_top_down, const uint8_t *mask_rgb8_top_down);
+/* The composite (same arguments as evplp_present) against the reference, on the device, settled like evplp_resolve.
+ * out = { mse, relMse, relMse over kept pixels (0 when none are kept) } over the pixels this context holds.  The per-pixel terms are fp32 in
+ * the order of floatimage.cpp:64-112 (num = |img - ref|^2, rel = num / (|ref|^2 + 0.001), no contraction, a correctly rounded division); they
+ * are summed in fp64, one image row at a time in a fixed order, and the rows in image row order on the host: the figures are a function of the
+ * frame alone (one context and a group of any block table give the same doubles), not of a float accumulator as in the host evplp_image_*
+ * functions.  No reference: EVPLP_ERR_INVALID. */
+int evplp_frame_error(evplp_context *ctx, float vpl_scale, float photon_scale, float light_scale,
+                      int32_t mask_emitter, int32_t gamma, double out[3]);
 
 /* Row-strip contexts (strip_count > 1): which blocks of strip_rows image rows this context owns.  By default block b belongs to rank
  * b % strip_count.  evplp_set_blocks replaces that by a table: local block l holds image block image_blocks[l], l < count <= the context's
@@ -459,6 +474,14 @@ int evplp_group_present(evplp_group *g, float vpl_scale, float photon_scale, flo
 int evplp_group_present_ex(evplp_group *g, float vpl_scale, float photon_scale, float light_scale, int32_t mask_emitter, int32_t gamma, int32_t exchange);
 int evplp_group_resolve(evplp_group *g, float vpl_scale, float photon_scale, float light_scale,
                         int32_t mask_emitter, int32_t gamma, float *out_rgb);
+/* evplp_set_error_reference on every rank (through the workers; the caller's images are read before the call returns). */
+int evplp_group_set_error_reference(evplp_group *g, const float *rgb_top_down, const uint8_t *mask_rgb8_top_down);
+/* evplp_frame_error for the whole image.  EVPLP_PARTITION_STRIPS: every rank composites and reduces its own rows; about 32 bytes per row
+ * come to the host and nothing is all-gathered.  EVPLP_PARTITION_ITERATIONS: the reduction of evplp_group_resolve first (or its cached
+ * sums: a later resolve at the same scales does not reduce again), then rank 0 reduces the summed composite.  The result equals, bit for
+ * bit, one context's over the same frame.  No reference, or a null out: EVPLP_ERR_INVALID on the caller's thread (the group stays usable). */
+int evplp_group_frame_error(evplp_group *g, float vpl_scale, float photon_scale, float light_scale,
+                            int32_t mask_emitter, int32_t gamma, double out[3]);
 
 /* ---- host side of the reference interface (no GPU needed for these) ---- */
 /* The anti-aliasing jitters of the first `count` iterations of a technique run with this rngOffset: NDC translations (x, y) =
