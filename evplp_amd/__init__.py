@@ -122,6 +122,10 @@ _SIGNATURES = {
     "evplp_present": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32]),
     "evplp_set_error_reference": (C.c_int, [_P, _P, _P]),
     "evplp_frame_error": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_double * 3)]),
+    "evplp_noise_track": (C.c_int, [_P, C.c_int32, _P]),
+    "evplp_noise_fold": (C.c_int, [_P, C.c_int32]),
+    "evplp_noise_estimate": (C.c_int, [_P, C.c_float, C.c_float, C.c_int32, C.POINTER(C.c_double * 3)]),
+    "evplp_noise_variance": (C.c_int, [_P, C.c_float, _P]),
     "evplp_clear_accumulators": (C.c_int, [_P]),
     "evplp_set_blocks": (C.c_int, [_P, _P, C.c_int32]),
     "evplp_get_blocks": (C.c_int, [_P, _P, C.c_int32]),
@@ -169,6 +173,10 @@ _SIGNATURES = {
     "evplp_group_present_ex": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_int32]),
     "evplp_group_set_error_reference": (C.c_int, [_P, _P, _P]),
     "evplp_group_frame_error": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_double * 3)]),
+    "evplp_group_noise_track": (C.c_int, [_P, C.c_int32, _P]),
+    "evplp_group_noise_fold": (C.c_int, [_P, C.c_int32]),
+    "evplp_group_noise_estimate": (C.c_int, [_P, C.c_float, C.c_float, C.c_int32, C.POINTER(C.c_double * 3)]),
+    "evplp_group_noise_variance": (C.c_int, [_P, C.c_float, _P]),
     "evplp_jitter_sequence": (C.c_int, [C.c_uint32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "evplp_json_query": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int32, C.POINTER(C.c_double), C.c_char_p, C.c_int32]),
     "evplp_progressive_step": (None, [C.c_int32, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.POINTER(C.c_float),
@@ -234,6 +242,26 @@ def _error_reference(rgb, mask, W: int, H: int):
         raise ValueError(f"set_error_reference: the mask must be uint8 of shape {(H, W, 3)}, got "
                          f"{getattr(mask, 'dtype', type(mask).__name__)} {getattr(mask, 'shape', None)}")
     return np.ascontiguousarray(rgb), None if mask is None else np.ascontiguousarray(mask)
+
+
+def _noise_track_args(on, mask, W: int, H: int):
+    """The arguments of noise_track, checked before any C call: on a bool, mask uint8 (H, W, 3) top-down or None (only with on)."""
+    if not isinstance(on, (bool, int, np.bool_)):
+        raise ValueError(f"noise_track: on must be a bool, got {type(on).__name__}")
+    if mask is not None:
+        if not on:
+            raise ValueError("noise_track: a mask without tracking")
+        if not isinstance(mask, np.ndarray) or mask.dtype != np.uint8 or mask.shape != (H, W, 3):
+            raise ValueError(f"noise_track: the mask must be uint8 of shape {(H, W, 3)}, got "
+                             f"{getattr(mask, 'dtype', type(mask).__name__)} {getattr(mask, 'shape', None)}")
+        mask = np.ascontiguousarray(mask)
+    return int(bool(on)), mask
+
+
+def _fold_iterations(iterations) -> int:
+    if isinstance(iterations, (bool, np.bool_)) or not isinstance(iterations, (int, np.integer)) or iterations < 1:
+        raise ValueError(f"noise_fold: iterations must be an int >= 1, got {iterations!r}")
+    return int(iterations)
 
 
 def frame_params(camera_pos, mis_mode=0, pdf_mc=0.0, clamping_value=0.0, photon_radius=0.0, vsl_radius=0.0,
@@ -451,6 +479,28 @@ class Context:
         out = (C.c_double * 3)()
         self._check(self._lib.evplp_frame_error(self._h, vpl_scale, photon_scale, light_scale, int(mask_emitter), int(gamma), C.byref(out)))
         return out[0], out[1], out[2]
+
+    def noise_track(self, on=True, mask: Optional[np.ndarray] = None):
+        """Start (again) or stop tracking per-pixel noise from the running sums; mask: optional uint8 (H, W, 3) top-down (include/evplp.h)"""
+        on, mask = _noise_track_args(on, mask, self.W, self.H)
+        self._check(self._lib.evplp_noise_track(self._h, on, _ptr(mask)))
+
+    def noise_fold(self, iterations=1):
+        """close a batch of `iterations` accumulating iterations"""
+        k = _fold_iterations(iterations)
+        self._check(self._lib.evplp_noise_fold(self._h, k))
+
+    def noise_estimate(self, scale, light_scale=1.0, mask_emitter=False):
+        """(mse, rel_mse, rel_mse_masked) estimated from the spread of the folded batches for the composite scale * sums + light_scale * light"""
+        out = (C.c_double * 3)()
+        self._check(self._lib.evplp_noise_estimate(self._h, float(scale), float(light_scale), int(mask_emitter), C.byref(out)))
+        return out[0], out[1], out[2]
+
+    def noise_variance(self, scale):
+        """per-pixel variance of scale * sums, float32 (local_rows, W, 3), y = 0 at the bottom"""
+        out = np.empty((self.local_rows, self.W, 3), dtype=np.float32)
+        self._check(self._lib.evplp_noise_variance(self._h, float(scale), _ptr(out)))
+        return out
 
     def set_blocks(self, image_blocks=None):
         """row-strip context: own these image blocks (in this local order) instead of the blocks b % strip_count == strip_rank; None = back to that"""
@@ -698,6 +748,28 @@ class Group:
         out = (C.c_double * 3)()
         self._check(self._lib.evplp_group_frame_error(self._h, vpl_scale, photon_scale, light_scale, int(mask_emitter), int(gamma), C.byref(out)))
         return out[0], out[1], out[2]
+
+    def noise_track(self, on=True, mask: Optional[np.ndarray] = None):
+        """Start (again) or stop tracking per-pixel noise from the running sums; mask: optional uint8 (H, W, 3) top-down (include/evplp.h)"""
+        on, mask = _noise_track_args(on, mask, self.W, self.H)
+        self._check(self._lib.evplp_group_noise_track(self._h, on, _ptr(mask)))
+
+    def noise_fold(self, iterations=1):
+        """close a batch of `iterations` accumulating iterations"""
+        k = _fold_iterations(iterations)
+        self._check(self._lib.evplp_group_noise_fold(self._h, k))
+
+    def noise_estimate(self, scale, light_scale=1.0, mask_emitter=False):
+        """(mse, rel_mse, rel_mse_masked) estimated from the spread of the folded batches for the composite scale * sums + light_scale * light"""
+        out = (C.c_double * 3)()
+        self._check(self._lib.evplp_group_noise_estimate(self._h, float(scale), float(light_scale), int(mask_emitter), C.byref(out)))
+        return out[0], out[1], out[2]
+
+    def noise_variance(self, scale):
+        """per-pixel variance of scale * sums, float32 (H, W, 3), y = 0 at the bottom"""
+        out = np.empty((self.H, self.W, 3), dtype=np.float32)
+        self._check(self._lib.evplp_group_noise_variance(self._h, float(scale), _ptr(out)))
+        return out
 
 
 def jitter_sequence(rng_offset: int, count: int, res_x: int, res_y: int) -> np.ndarray:

@@ -202,6 +202,7 @@ extern "C" void evplp_destroy(evplp_context *c) {
     hipFree(c->d_compact); hipFree(c->d_tile_box); hipFree(c->d_tile_pairs); hipFree(c->d_summary); hipFree(c->d_heavy_list); hipFree(c->d_tile_flags);
     hipFree(c->d_proxy_slabs); hipFree(c->d_proxy_hm); hipFree(c->d_tile_frags); hipFree(c->d_blocks); hipFree(c->d_block_cost);
     hipFree(c->d_err_ref); hipFree(c->d_err_keep); hipFree(c->d_err_rows);
+    hipFree(c->d_noise); hipFree(c->d_noise_keep); hipFree(c->d_noise_rows);
     for (int i = 0; i < EVPLP_PASS_COUNT; i++) {
         if (c->ev_begin[i]) hipEventDestroy(c->ev_begin[i]);
         if (c->ev_end[i]) hipEventDestroy(c->ev_end[i]);
@@ -1047,12 +1048,12 @@ int frame_error_rows(evplp_context *c) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return EVPLP_OK;
 }
-// c->err_rows put at their image rows
-void place_row_errors(const evplp_context *c, std::vector<RowError> &rows, std::vector<char> &held) {
+// a context's per-local-row partials (c->err_rows, c->noise_rows) put at their image rows
+void place_row_errors(const evplp_context *c, const std::vector<RowError> &local, std::vector<RowError> &rows, std::vector<char> &held) {
     for (int l = 0; l < c->st.local_rows; l++) {
         const int y = c->st.global_row(l);
         if (y < 0 || y >= c->st.H) continue;
-        rows[(size_t)y] = c->err_rows[(size_t)l]; held[(size_t)y] = 1;
+        rows[(size_t)y] = local[(size_t)l]; held[(size_t)y] = 1;
     }
 }
 void sum_row_errors(const std::vector<RowError> &rows, const std::vector<char> &held, double npix, double out[3]) {
@@ -1074,8 +1075,116 @@ extern "C" int evplp_frame_error(evplp_context *c, float vs, float ps, float ls,
     if (rc) return rc;
     if ((rc = evplp::frame_error_rows(c))) return rc;
     std::vector<RowError> rows((size_t)c->st.H); std::vector<char> held((size_t)c->st.H, 0);
-    evplp::place_row_errors(c, rows, held);
+    evplp::place_row_errors(c, c->err_rows, rows, held);
     evplp::sum_row_errors(rows, held, (double)c->st.W * c->rows_in_image, out);
+    return EVPLP_OK;
+}
+
+// ---- per-pixel noise from the running sums, without a reference (include/evplp.h evplp_noise_*)
+static void release_noise(evplp_context *c) {
+    hipFree(c->d_noise); hipFree(c->d_noise_keep); hipFree(c->d_noise_rows);
+    c->d_noise = nullptr; c->d_noise_keep = nullptr; c->d_noise_rows = nullptr; c->noise_rows.clear(); c->noise_k = c->noise_b = 0;
+}
+namespace evplp {
+NoisePlanes noise_planes(const evplp_context *c) {
+    const size_t px = (size_t)c->st.W * c->st.local_rows;
+    double *q = (double *)c->d_noise;
+    float4 *prev = (float4 *)(q + 3 * c->noise_stride);
+    return NoisePlanes{ q, prev, prev + px, c->noise_stride };
+}
+NoiseMoments noise_moments_of(const evplp_context *c) {
+    const NoisePlanes m = noise_planes(c);
+    return NoiseMoments{ m.q, nullptr, m.prev, m.start, m.stride };
+}
+size_t noise_bytes(const evplp_context *c) { return sizeof(double) * 3 * c->noise_stride + sizeof(float4) * 2 * (size_t)c->st.W * c->st.local_rows; }
+int noise_rows(evplp_context *c, const NoiseMoments &m, const float4 *light, double K, double B, float scale, float ls, int32_t mask_emitter) {
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    const double s2K = (double)scale * (double)scale * K;
+    launch_noise_rows(c->st, m, K, B, s2K, light, ls, mask_emitter, c->d_rgb, c->d_noise_keep, c->d_noise_rows, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(c->noise_rows.data(), c->d_noise_rows, sizeof(RowError) * (size_t)c->st.local_rows, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return EVPLP_OK;
+}
+int noise_variance_to_device(evplp_context *c, const NoiseMoments &m, double K, double B, float scale) {
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    launch_noise_variance(m, K, B, (double)scale * (double)scale * K, (size_t)c->st.W * c->st.local_rows, c->d_rgb, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return EVPLP_OK;
+}
+} // namespace evplp
+// tracking (re)starts from the accumulators as they are: c_prev = c_start = c, Q = 0, K = B = 0 (stream order)
+static int noise_restart(evplp_context *c) {
+    c->noise_k = c->noise_b = 0;
+    launch_noise_fold(evplp::noise_planes(c), (const float4 *)c->buf[EVPLP_BUF_VPL_ACCUM], (const float4 *)c->buf[EVPLP_BUF_PHOTON_ACCUM],
+                      (size_t)c->st.W * c->st.local_rows, 0, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return EVPLP_OK;
+}
+extern "C" int evplp_noise_track(evplp_context *c, int32_t on, const uint8_t *mask) {
+    CTX_CHECK(c);
+    if (!on && mask) { c->set_error("evplp_noise_track: a mask without tracking"); return EVPLP_ERR_INVALID; }
+    { int rc_ = settle_splat(c); if (rc_) return rc_; }            // (the snapshot sees every splat enqueued so far)
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));                   // (no fold or estimate of an earlier call still reads the old planes)
+    if (!on) { release_noise(c); return EVPLP_OK; }
+    const size_t px = (size_t)c->st.W * c->st.local_rows, image_px = (size_t)c->st.W * c->st.H;
+    c->noise_stride = (px + 1) & ~(size_t)1;
+    std::vector<uint8_t> keep;
+    if (mask) { keep.resize(image_px); for (size_t i = 0; i < image_px; i++) keep[i] = (mask[3 * i] | mask[3 * i + 1] | mask[3 * i + 2]) != 0 ? 1 : 0; }
+    hipError_t e = hipSuccess;
+    if (!c->d_noise) e = hipMalloc((void **)&c->d_noise, evplp::noise_bytes(c));
+    if (e == hipSuccess && !c->d_noise_rows) e = hipMalloc((void **)&c->d_noise_rows, sizeof(RowError) * (size_t)std::max(c->st.local_rows, 1));
+    if (e == hipSuccess && mask && !c->d_noise_keep) e = hipMalloc((void **)&c->d_noise_keep, image_px);
+    if (e != hipSuccess) {
+        (void)hipGetLastError(); release_noise(c);
+        c->set_error("evplp_noise_track: cannot allocate %zu bytes: %s", evplp::noise_bytes(c), hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP;
+    }
+    if (!mask) { hipFree(c->d_noise_keep); c->d_noise_keep = nullptr; }
+    else if ((e = hipMemcpy(c->d_noise_keep, keep.data(), image_px, hipMemcpyHostToDevice)) != hipSuccess) {
+        release_noise(c); c->set_error("evplp_noise_track: upload: %s", hipGetErrorString(e)); return EVPLP_ERR_HIP;
+    }
+    c->noise_rows.assign((size_t)std::max(c->st.local_rows, 1), RowError{});
+    return noise_restart(c);
+}
+extern "C" int evplp_noise_fold(evplp_context *c, int32_t iterations) {
+    CTX_CHECK(c);
+    if (!c->d_noise) { c->set_error("evplp_noise_fold: tracking is off (evplp_noise_track)"); return EVPLP_ERR_INVALID; }
+    if (iterations < 1) { c->set_error("evplp_noise_fold: a batch holds >= 1 iterations, not %d", iterations); return EVPLP_ERR_INVALID; }
+    { int rc_ = settle_splat(c); if (rc_) return rc_; }            // (every splat of the batch has its verdict; a re-run is enqueued before the fold)
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    launch_noise_fold(evplp::noise_planes(c), (const float4 *)c->buf[EVPLP_BUF_VPL_ACCUM], (const float4 *)c->buf[EVPLP_BUF_PHOTON_ACCUM],
+                      (size_t)c->st.W * c->st.local_rows, iterations, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    c->noise_k += iterations; c->noise_b += 1;
+    return EVPLP_OK;
+}
+static int noise_ready(evplp_context *c, const char *name) {
+    if (!c->d_noise) { c->set_error("%s: tracking is off (evplp_noise_track)", name); return EVPLP_ERR_INVALID; }
+    if (c->noise_b < 2) { c->set_error("%s: %lld fold(s): the estimate needs >= 2", name, (long long)c->noise_b); return EVPLP_ERR_INVALID; }
+    return EVPLP_OK;
+}
+extern "C" int evplp_noise_estimate(evplp_context *c, float scale, float ls, int32_t mask_emitter, double out[3]) {
+    CTX_CHECK(c);
+    if (!out) { c->set_error("evplp_noise_estimate: null output"); return EVPLP_ERR_INVALID; }
+    int rc = noise_ready(c, "evplp_noise_estimate");
+    if (rc) return rc;
+    if ((rc = evplp::resolve_to_device(c, scale, scale, ls, mask_emitter, 0, true, false))) return rc;
+    if ((rc = evplp::noise_rows(c, evplp::noise_moments_of(c), (const float4 *)c->buf[EVPLP_BUF_LIGHT], (double)c->noise_k, (double)c->noise_b, scale, ls, mask_emitter))) return rc;
+    std::vector<RowError> rows((size_t)c->st.H); std::vector<char> held((size_t)c->st.H, 0);
+    evplp::place_row_errors(c, c->noise_rows, rows, held);
+    evplp::sum_row_errors(rows, held, (double)c->st.W * c->rows_in_image, out);
+    return EVPLP_OK;
+}
+extern "C" int evplp_noise_variance(evplp_context *c, float scale, float *out_rgb) {
+    CTX_CHECK(c);
+    if (!out_rgb) { c->set_error("evplp_noise_variance: null output"); return EVPLP_ERR_INVALID; }
+    int rc = noise_ready(c, "evplp_noise_variance");
+    if (rc) return rc;
+    if ((rc = evplp::noise_variance_to_device(c, evplp::noise_moments_of(c), (double)c->noise_k, (double)c->noise_b, scale))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(out_rgb, c->d_rgb, sizeof(float) * 3 * (size_t)c->st.W * c->st.local_rows, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return EVPLP_OK;
 }
 
@@ -1161,6 +1270,7 @@ extern "C" int evplp_clear_accumulators(evplp_context *c) {
     HIP_TRY(c, hipMemsetAsync(c->buf[EVPLP_BUF_VPL_ACCUM], 0, buffer_bytes(c, EVPLP_BUF_VPL_ACCUM), c->stream));
     HIP_TRY(c, hipMemsetAsync(c->buf[EVPLP_BUF_PHOTON_ACCUM], 0, buffer_bytes(c, EVPLP_BUF_PHOTON_ACCUM), c->stream));
     HIP_TRY(c, hipMemsetAsync(c->buf[EVPLP_BUF_LIGHT], 0, buffer_bytes(c, EVPLP_BUF_LIGHT), c->stream));
+    if (c->d_noise) return noise_restart(c);                                  // (noise tracking starts again from the empty sums)
     return EVPLP_OK;
 }
 

@@ -24,6 +24,18 @@ bool build_proxy_slabs(const float *verts, int32_t nverts, const int32_t *tris, 
 void sum_row_errors(const std::vector<RowError> &rows, const std::vector<char> &held, double npix, double out[3]);
 }
 
+struct evplp_context;
+namespace evplp {
+// evplp_noise_* (context.cpp), for the group's workers as well
+NoisePlanes noise_planes(const evplp_context *c);
+NoiseMoments noise_moments_of(const evplp_context *c);           // a context's own moments (S = c_prev - c_start)
+size_t noise_bytes(const evplp_context *c);                      // the NoisePlanes allocation
+// the per-row figures of the moments m (K iterations in B folds) against the composite in d_rgb, to c->noise_rows (waits for them)
+int noise_rows(evplp_context *c, const NoiseMoments &m, const float4 *light, double K, double B, float scale, float ls, int32_t mask_emitter);
+// the variance image of the moments m into d_rgb (stream order)
+int noise_variance_to_device(evplp_context *c, const NoiseMoments &m, double K, double B, float scale);
+}
+
 struct evplp_context {
     evplp_config cfg{};
     evplp::StripDev st{};
@@ -121,6 +133,11 @@ struct evplp_context {
     // (null: every pixel is kept), so that a new block table needs no new upload; evplp_frame_error's per-row partials, [local_rows]
     float *d_err_ref = nullptr; uint8_t *d_err_keep = nullptr;
     evplp::RowError *d_err_rows = nullptr; std::vector<evplp::RowError> err_rows;
+    // evplp_noise_track: the moments (kernels.h NoisePlanes, null: tracking is off), the keep byte of every IMAGE pixel (null: every pixel
+    // is kept), evplp_noise_estimate's per-row partials [local_rows]; noise_k = K (iterations folded), noise_b = B (folds)
+    char *d_noise = nullptr; size_t noise_stride = 0; uint8_t *d_noise_keep = nullptr;
+    evplp::RowError *d_noise_rows = nullptr; std::vector<evplp::RowError> noise_rows;
+    int64_t noise_k = 0, noise_b = 0;
 
     char error[512] = "";
     void set_error(const char *fmt, ...);

@@ -43,7 +43,7 @@ namespace evplp {
 int resolve_to_device(evplp_context *c, float vs, float ps, float ls, int32_t mask_emitter, int32_t gamma, bool settle, bool as_pass);   // context.cpp
 int settle(evplp_context *c);                                                                                                  // context.cpp
 int frame_error_rows(evplp_context *c);                                                                                        // context.cpp
-void place_row_errors(const evplp_context *c, std::vector<RowError> &rows, std::vector<char> &held);                          // context.cpp
+void place_row_errors(const evplp_context *c, const std::vector<RowError> &local, std::vector<RowError> &rows, std::vector<char> &held);   // context.cpp
 }
 
 namespace {
@@ -63,7 +63,8 @@ struct Rccl {
     }
 };
 
-enum Op { OP_QUIT = 0, OP_CLEAR, OP_SYNC, OP_PRIMARY, OP_TRACE, OP_GATHER, OP_SPLAT, OP_PATH_TRACE, OP_PRESENT, OP_LOAD_SCENE, OP_SET_PROXY, OP_ASSEMBLE, OP_REDUCE, OP_SET_REFERENCE, OP_FRAME_ERROR };
+enum Op { OP_QUIT = 0, OP_CLEAR, OP_SYNC, OP_PRIMARY, OP_TRACE, OP_GATHER, OP_SPLAT, OP_PATH_TRACE, OP_PRESENT, OP_LOAD_SCENE, OP_SET_PROXY, OP_ASSEMBLE, OP_REDUCE, OP_SET_REFERENCE, OP_FRAME_ERROR,
+          OP_NOISE_TRACK, OP_NOISE_FOLD, OP_NOISE_POOL, OP_NOISE_ROWS, OP_NOISE_VARIANCE };
 // One posted call: plain data, copied into the ring (pointers must stay valid until the caller has drained: load_scene, set_proxy, resolve do)
 struct Cmd {
     int op = OP_QUIT;
@@ -127,6 +128,11 @@ struct evplp_group {
     // the ranks' planes (OP_REDUCE).  sums_fresh (caller's thread): no pass was posted since the last reduction -- the cached sums still hold
     bool iterations = false; int selected = 0; bool sums_fresh = false;
     bool have_reference = false;            // evplp_group_set_error_reference has given every rank an image (caller's thread)
+    bool noise_on = false;                  // evplp_group_noise_track is on on every rank (caller's thread)
+    // EVPLP_PARTITION_ITERATIONS, evplp_group_noise_*: rank 0's pooled moments (Q then S, [3][stride] fp64 each) and K / B summed over the
+    // ranks (written by rank 0's worker); RCCL only: per rank [n][noise_bytes] every rank's NoisePlanes (all-gathered)
+    double *d_noise_pool = nullptr; double pool_k = 0.0, pool_b = 0.0;
+    std::vector<char *> d_noise_stage;
     size_t plane_px = 0;                    // W * local_rows: the pixels of one accumulator plane
     std::vector<float4 *> d_sum;            // per rank: [3][plane_px] VPL, photon and light planes reduced over the ranks (the first reduction)
     std::vector<float4 *> d_stage;          // per rank, RCCL only: [n][plane_px] one plane of every rank (all-gathered)
@@ -246,10 +252,65 @@ static void worker_reduce(Worker *w, const Cmd &cmd) {
     w->t_calls += (t1 - t0) + (now_ms() - t2); w->n_cmds++;
 }
 
+// EVPLP_PARTITION_ITERATIONS, evplp_group_noise_estimate / _variance: every rank's moments pooled on rank 0 -- Q and S summed in rank order
+// (noise_pool_kernel, once per rank), K and B summed -- the way worker_reduce moves the accumulators: virtual ranks are read where they are,
+// distinct devices all-gather their NoisePlanes into a staging buffer first.
+static void worker_noise_pool(Worker *w) {
+    evplp_group *g = w->g; const int r = w->rank; evplp_context *c = g->ctx[(size_t)r];
+    auto ok = [&] { return w->status.load(std::memory_order_relaxed) == 0; };
+    auto hip_fail = [&](hipError_t e) { (void)hipGetLastError(); worker_fail(w, e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP, hipGetErrorString(e)); };
+    const double t0 = now_ms();
+    const size_t px = g->plane_px, stride = c->noise_stride, bytes = evplp::noise_bytes(c);
+    hipError_t e = hipSuccess;
+    if (ok() && r == 0 && !g->d_noise_pool) e = hipMalloc((void **)&g->d_noise_pool, sizeof(double) * 6 * stride);
+    if (e == hipSuccess && ok() && !g->virtual_ranks && !g->d_noise_stage[(size_t)r]) e = hipMalloc((void **)&g->d_noise_stage[(size_t)r], bytes * (size_t)g->n);
+    if (e != hipSuccess) hip_fail(e);
+    // rank 0, behind every rank's last command: K, B and the n launches, src(q) = rank q's moments
+    auto pool = [&](auto src) {
+        double k = 0.0, b = 0.0;
+        for (int q = 0; q < g->n; q++) {
+            k += (double)g->ctx[(size_t)q]->noise_k; b += (double)g->ctx[(size_t)q]->noise_b;
+            evplp::launch_noise_pool(src(q), q == 0, g->d_noise_pool, g->d_noise_pool + 3 * stride, px, c->stream);
+        }
+        g->pool_k = k; g->pool_b = b;
+        hipError_t le = hipGetLastError();
+        if (le != hipSuccess) hip_fail(le);
+    };
+    if (g->n == 1 && g->virtual_ranks) { if (ok()) pool([&](int) { return evplp::noise_moments_of(c); }); }
+    else if (g->virtual_ranks) {
+        // every rank's planes are final when its stream is idle; nobody folds again before rank 0 has read them (second barrier)
+        e = ok() ? hipStreamSynchronize(c->stream) : hipSuccess;
+        if (e != hipSuccess) hip_fail(e);
+        if (g->barrier.wait(&g->failed) == 0) {
+            if (r == 0) {
+                pool([&](int q) { return evplp::noise_moments_of(g->ctx[(size_t)q]); });
+                e = hipStreamSynchronize(c->stream);
+                if (e != hipSuccess) hip_fail(e);
+            }
+            g->barrier.wait();
+        }
+    } else if (g->barrier.wait(&g->failed) == 0) {
+        // distinct devices: the whole NoisePlanes allocation of every rank, all-gathered (stream order), then rank 0 pools from the stage
+        char *stage = g->d_noise_stage[(size_t)r];
+        ncclResult_t nr = g->rccl.AllGather(c->d_noise, stage, bytes / sizeof(float), ncclFloat, g->comms[(size_t)r], c->stream);
+        if (nr != ncclSuccess) worker_fail(w, EVPLP_ERR_HIP, g->rccl.GetErrorString(nr));
+        else if (r == 0) pool([&](int q) {
+            const double *sq = (const double *)(stage + (size_t)q * bytes);
+            const float4 *prev = (const float4 *)(sq + 3 * stride);
+            return evplp::NoiseMoments{ sq, nullptr, prev, prev + px, stride };
+        });
+    }
+    w->t_exchange += now_ms() - t0; w->n_cmds++;
+}
+
+static evplp::NoiseMoments noise_pooled(const evplp_group *g, const evplp_context *c0) {
+    return evplp::NoiseMoments{ g->d_noise_pool, g->d_noise_pool + 3 * c0->noise_stride, nullptr, nullptr, c0->noise_stride };
+}
 static void worker_run(Worker *w, const Cmd &cmd) {
     if (cmd.op == OP_REDUCE) { worker_reduce(w, cmd); return; }
+    if (cmd.op == OP_NOISE_POOL) { worker_noise_pool(w); return; }
     evplp_group *g = w->g; const int r = w->rank; evplp_context *c = g->ctx[(size_t)r];
-    const bool collective = (cmd.op == OP_PRESENT && cmd.i[3] != 0) || (cmd.op == OP_TRACE && g->split_paths);
+    const bool collective = ((cmd.op == OP_PRESENT || cmd.op == OP_NOISE_VARIANCE) && cmd.i[3] != 0) || (cmd.op == OP_TRACE && g->split_paths);
     int rc = EVPLP_OK;
     const double t0 = now_ms();
     if (w->status.load(std::memory_order_relaxed) == 0) {
@@ -276,6 +337,17 @@ static void worker_run(Worker *w, const Cmd &cmd) {
         case OP_SET_PROXY: rc = evplp_set_splat_proxy(c, (const float *)cmd.p0, cmd.i[0], (const int32_t *)cmd.p1, cmd.i[1]); break;
         case OP_SET_REFERENCE: rc = evplp_set_error_reference(c, (const float *)cmd.p0, (const uint8_t *)cmd.p1); break;
         case OP_FRAME_ERROR: rc = evplp::frame_error_rows(c); break;          // (behind this rank's composite, on its stream)
+        case OP_NOISE_TRACK: rc = evplp_noise_track(c, cmd.i[0], (const uint8_t *)cmd.p0); break;
+        case OP_NOISE_FOLD: rc = evplp_noise_fold(c, cmd.i[0]); break;
+        // i[1] = 1: rank 0's moments pooled over the ranks (OP_NOISE_POOL before), with the summed light plane of the reduction
+        case OP_NOISE_ROWS:
+            if (cmd.i[1]) rc = evplp::noise_rows(c, noise_pooled(g, c), g->d_sum[0] + 2 * g->plane_px, g->pool_k, g->pool_b, cmd.f[0], cmd.f[1], cmd.i[0]);
+            else rc = evplp::noise_rows(c, evplp::noise_moments_of(c), (const float4 *)c->buf[EVPLP_BUF_LIGHT], (double)c->noise_k, (double)c->noise_b, cmd.f[0], cmd.f[1], cmd.i[0]);
+            break;
+        case OP_NOISE_VARIANCE:
+            if (cmd.i[1]) rc = evplp::noise_variance_to_device(c, noise_pooled(g, c), g->pool_k, g->pool_b, cmd.f[0]);
+            else rc = evplp::noise_variance_to_device(c, evplp::noise_moments_of(c), (double)c->noise_k, (double)c->noise_b, cmd.f[0]);
+            break;
         case OP_ASSEMBLE: {
             // rank 0 puts the strips into image order on the device; one copy lands the frame in the caller's buffer (no host-side assembly:
             // a run that writes every frame resolves every iteration)
@@ -428,7 +500,8 @@ extern "C" void evplp_group_destroy(evplp_group *g) {
     g->workers.clear();
     for (int r = 0; r < (int)g->d_frame.size(); r++) if (g->d_frame[(size_t)r]) { hipSetDevice(g->device[(size_t)r]); hipFree(g->d_frame[(size_t)r]); }
     for (int r = 0; r < (int)g->d_sum.size(); r++) if (g->d_sum[(size_t)r] || g->d_stage[(size_t)r]) { hipSetDevice(g->device[(size_t)r]); hipFree(g->d_sum[(size_t)r]); hipFree(g->d_stage[(size_t)r]); }
-    if (g->d_assembled || g->d_owner) { hipSetDevice(g->device[0]); hipFree(g->d_assembled); hipFree(g->d_owner); }
+    for (int r = 0; r < (int)g->d_noise_stage.size(); r++) if (g->d_noise_stage[(size_t)r]) { hipSetDevice(g->device[(size_t)r]); hipFree(g->d_noise_stage[(size_t)r]); }
+    if (g->d_assembled || g->d_owner || g->d_noise_pool) { hipSetDevice(g->device[0]); hipFree(g->d_assembled); hipFree(g->d_owner); hipFree(g->d_noise_pool); }
     for (ncclComm_t c : g->comms) if (c && g->rccl.CommDestroy) g->rccl.CommDestroy(c);
     for (evplp_context *c : g->ctx) { c->quiesce = nullptr; evplp_destroy(c); }
     delete g;
@@ -479,7 +552,7 @@ extern "C" int evplp_group_create(const evplp_config *cfg, const evplp_group_con
     g->strip_floats = g->n == 1 ? g->strip_floats_cap : round_robin_floats(g);
     g->d_frame.assign((size_t)g->n, nullptr);
     g->plane_px = (size_t)g->ctx[0]->st.W * g->ctx[0]->st.local_rows;
-    g->d_sum.assign((size_t)g->n, nullptr); g->d_stage.assign((size_t)g->n, nullptr); g->num_cus.assign((size_t)g->n, 256);
+    g->d_sum.assign((size_t)g->n, nullptr); g->d_stage.assign((size_t)g->n, nullptr); g->d_noise_stage.assign((size_t)g->n, nullptr); g->num_cus.assign((size_t)g->n, 256);
     for (int r = 0; r < g->n; r++) {
         hipSetDevice(g->device[(size_t)r]);
         int cus = 0;
@@ -706,7 +779,88 @@ extern "C" int evplp_group_frame_error(evplp_group *g, float vs, float ps, float
     if ((rc = group_status(g)) < 0) return rc;
     const evplp_context *c0 = g->ctx[0];
     std::vector<evplp::RowError> rows((size_t)c0->st.H); std::vector<char> held((size_t)c0->st.H, 0);
-    for (int r = 0; r < (g->iterations ? 1 : g->n); r++) evplp::place_row_errors(g->ctx[(size_t)r], rows, held);
+    for (int r = 0; r < (g->iterations ? 1 : g->n); r++) evplp::place_row_errors(g->ctx[(size_t)r], g->ctx[(size_t)r]->err_rows, rows, held);
     evplp::sum_row_errors(rows, held, (double)c0->st.W * c0->st.H, out);
     return EVPLP_OK;
+}
+
+// Per-pixel noise from the running sums (include/evplp.h).  Strips: every rank tracks, folds and reduces its own rows, and 32 bytes per row
+// come to the host.  Iterations: a fold closes a batch of the selected rank's iterations; an estimate pools the ranks' moments on rank 0.
+// What can be refused without a device is refused here, on the caller's thread, and leaves the group usable.
+extern "C" int evplp_group_noise_track(evplp_group *g, int32_t on, const uint8_t *mask) {
+    GRP_CHECK(g);
+    if (!on && mask) { g->set_error("evplp_group_noise_track: a mask without tracking"); return EVPLP_ERR_INVALID; }
+    Cmd c; c.op = OP_NOISE_TRACK; c.i[0] = on; c.p0 = mask;
+    const int rc = post_and_wait(g, c);             // (the caller's mask is read before the call returns)
+    g->noise_on = rc >= 0 && on != 0;
+    return rc;
+}
+extern "C" int evplp_group_noise_fold(evplp_group *g, int32_t iterations) {
+    GRP_CHECK(g);
+    if (!g->noise_on) { g->set_error("evplp_group_noise_fold: tracking is off (evplp_group_noise_track)"); return EVPLP_ERR_INVALID; }
+    if (iterations < 1) { g->set_error("evplp_group_noise_fold: a batch holds >= 1 iterations, not %d", iterations); return EVPLP_ERR_INVALID; }
+    Cmd c; c.op = OP_NOISE_FOLD; c.i[0] = iterations;
+    if (!g->iterations) return post_all(g, c);
+    if (g->failed.load(std::memory_order_acquire)) { drain(g); return group_status(g); }
+    post(g->workers[(size_t)g->selected], c);
+    return EVPLP_OK;
+}
+// tracking on and B >= 2 (the ranks' folds summed under the iteration partition); drains the workers to read their counts
+static int noise_group_ready(evplp_group *g, const char *name) {
+    if (!g->noise_on) { g->set_error("%s: tracking is off (evplp_group_noise_track)", name); return EVPLP_ERR_INVALID; }
+    drain(g);
+    int rc = group_status(g);
+    if (rc < 0) return rc;
+    int64_t b = 0;
+    for (int r = 0; r < (g->iterations ? g->n : 1); r++) b += g->ctx[(size_t)r]->noise_b;
+    if (b < 2) { g->set_error("%s: %lld fold(s): the estimate needs >= 2", name, (long long)b); return EVPLP_ERR_INVALID; }
+    return EVPLP_OK;
+}
+extern "C" int evplp_group_noise_estimate(evplp_group *g, float scale, float ls, int32_t mask_emitter, double out[3]) {
+    GRP_CHECK(g);
+    if (!out) { g->set_error("evplp_group_noise_estimate: null output"); return EVPLP_ERR_INVALID; }
+    int rc = noise_group_ready(g, "evplp_group_noise_estimate");
+    if (rc < 0) return rc;
+    Cmd rows; rows.op = OP_NOISE_ROWS; rows.f[0] = scale; rows.f[1] = ls; rows.i[0] = mask_emitter; rows.i[1] = g->iterations ? 1 : 0;
+    if (g->iterations) {
+        rc = post_reduce(g, scale, scale, ls, mask_emitter, 0);
+        Cmd pool; pool.op = OP_NOISE_POOL;
+        if (rc >= 0) rc = post_all(g, pool);
+        if (rc >= 0) post(g->workers[0], rows);
+    } else {
+        Cmd p = present_cmd(scale, scale, ls, mask_emitter, 0, true, false);      // (every rank's own rows: nothing is exchanged; not a pass)
+        p.u[0] = 1;
+        rc = post_all(g, p);
+        if (rc >= 0) rc = post_all(g, rows);
+    }
+    if (rc < 0) return rc;
+    drain(g);
+    if ((rc = group_status(g)) < 0) return rc;
+    const evplp_context *c0 = g->ctx[0];
+    std::vector<evplp::RowError> all((size_t)c0->st.H); std::vector<char> held((size_t)c0->st.H, 0);
+    for (int r = 0; r < (g->iterations ? 1 : g->n); r++) evplp::place_row_errors(g->ctx[(size_t)r], g->ctx[(size_t)r]->noise_rows, all, held);
+    evplp::sum_row_errors(all, held, (double)c0->st.W * c0->st.H, out);
+    return EVPLP_OK;
+}
+extern "C" int evplp_group_noise_variance(evplp_group *g, float scale, float *out_rgb) {
+    GRP_CHECK(g);
+    if (!out_rgb) { g->set_error("evplp_group_noise_variance: null output"); return EVPLP_ERR_INVALID; }
+    int rc = noise_group_ready(g, "evplp_group_noise_variance");
+    if (rc < 0) return rc;
+    // every rank's variance into its d_rgb, all-gathered as a present's composite (strips), or rank 0's pooled one; then OP_ASSEMBLE
+    Cmd v; v.op = OP_NOISE_VARIANCE; v.f[0] = scale;
+    if (g->iterations) {
+        Cmd pool; pool.op = OP_NOISE_POOL;
+        rc = post_all(g, pool);
+        v.i[1] = 1;
+        if (rc >= 0) post(g->workers[0], v);
+    } else {
+        v.i[3] = 1;
+        rc = post_all(g, v);
+    }
+    if (rc < 0) return rc;
+    Cmd a; a.op = OP_ASSEMBLE; a.out = out_rgb;
+    post(g->workers[0], a);
+    drain(g);
+    return group_status(g);
 }

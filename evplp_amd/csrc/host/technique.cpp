@@ -295,6 +295,136 @@ private:
     double every_ms = 0.0, next_ms = 0.0, stop_rel_mse = -1.0, overhead_ms = 0.0;
     std::vector<Point> points;
 };
+
+// Build-only key "noise" (not a reference key): the error of the image the run saves, estimated from the spread between its own iterations
+// -- no reference image -- on the device (evplp_group_noise_*: 32 bytes per image row come to the host) and written as one JSON file.
+//   {"batchIterations": 1, "everyIterations": 10, "everyMs": 250, "stopRelMse": 0.01, "mask": "m.png", "filename": "noise.json",
+//    "varianceFilename": "var.pfm"}
+// filename is required.  Every batchIterations iterations of a shard (the whole group on row strips; each rank of an iteration partition, of
+// its own iterations) close one batch (evplp_group_noise_fold).  Checkpoints fall at a fold: when everyIterations (a multiple of
+// batchIterations) divides the iteration count, or at the first fold after the wall clock has passed the next multiple of everyMs; they need
+// two folds, and time themselves as "convergence" does.  After the loop every shard folds the iterations it holds unfolded and one last
+// checkpoint is taken.  stopRelMse ends the run at the first checkpoint whose relMSE (the masked one with a mask) is <= it.
+// varianceFilename: the per-pixel variance of the saved combined image, rows top to bottom.  frameMode "cleareveryframe" keeps no running
+// sum to fold: refused.  Everything is validated before the group exists.
+class Noise {
+public:
+    bool on = false;
+    void parse(const Json &tech, const std::string &json_dir, const std::string &out_dir, int W, int H, int frame_mode) {
+        if (!tech.has("noise")) return;
+        const Json &c = tech.at("noise");
+        if (!c.is_object()) throw JsonError("noise: expected an object");
+        if (!c.has("filename")) throw JsonError("noise.filename: missing required key");
+        if (frame_mode == 2) throw JsonError("noise: frameMode \"cleareveryframe\" keeps no running sum to fold");
+        filename = output_path(out_dir, c.at("filename").as_string("noise.filename"));
+        if (c.has("batchIterations")) {
+            batch = c.at("batchIterations").as_int("noise.batchIterations");
+            if (batch <= 0 || batch > INT32_MAX) throw JsonError("noise.batchIterations: must be > 0");
+        }
+        if (c.has("everyIterations")) {
+            every_iterations = c.at("everyIterations").as_int("noise.everyIterations");
+            if (every_iterations <= 0) throw JsonError("noise.everyIterations: must be > 0");
+            if (every_iterations % batch != 0) throw JsonError("noise.everyIterations: must be a multiple of noise.batchIterations");
+        }
+        if (c.has("everyMs")) {
+            every_ms = c.at("everyMs").as_number("noise.everyMs");
+            if (!(every_ms > 0.0)) throw JsonError("noise.everyMs: must be > 0");
+            next_ms = every_ms;
+        }
+        if (c.has("stopRelMse")) {
+            stop_rel_mse = c.at("stopRelMse").as_number("noise.stopRelMse");
+            if (!(stop_rel_mse >= 0.0)) throw JsonError("noise.stopRelMse: must be >= 0");
+        }
+        if (c.has("varianceFilename")) variance_filename = output_path(out_dir, c.at("varianceFilename").as_string("noise.varianceFilename"));
+        if (c.has("mask")) {
+            const std::string mask_path = join_path(json_dir, c.at("mask").as_string("noise.mask"));
+            int32_t w = 0, h = 0, ch = 0;
+            if (evplp_decode_image(mask_path.c_str(), &w, &h, &ch, nullptr, 0) != EVPLP_OK) throw IoError("noise.mask: cannot read " + mask_path);
+            if (w != W || h != H)
+                throw JsonError("noise.mask: " + mask_path + " is " + std::to_string(w) + " x " + std::to_string(h) + ", the scene renders " + std::to_string(W) + " x " + std::to_string(H));
+            mask.resize((size_t)W * H * 3);
+            if (evplp_decode_image(mask_path.c_str(), &w, &h, &ch, mask.data(), mask.size()) != EVPLP_OK) throw IoError("noise.mask: cannot read " + mask_path);
+            for (size_t i = 0; i < (size_t)W * H; i++) kept += (mask[3 * i] | mask[3 * i + 1] | mask[3 * i + 2]) != 0 ? 1 : 0;
+        }
+        pixels = (int64_t)W * H;
+        on = true;
+    }
+    // tracking starts from the sums as they are (after the loop's clear); shards: 1, or the ranks of an iteration partition
+    void start(evplp_group *g, int shards) {
+        if (!on) return;
+        check(g, evplp_group_noise_track(g, 1, mask.empty() ? nullptr : mask.data()), "noise tracking");
+        own.assign((size_t)shards, 0); folded.assign((size_t)shards, 0);
+    }
+    // after an iteration of `shard` (the selected rank of an iteration partition): folds when its batch is full; true when it folded
+    bool after_iteration(evplp_group *g, int shard) {
+        if (!on) return false;
+        const size_t r = (size_t)shard;
+        if (++own[r] - folded[r] < batch) return false;
+        fold(g, r, batch);
+        return true;
+    }
+    bool due(int i, double now_ms, bool folded_now) const {
+        return on && folded_now && batches >= 2 && ((every_iterations > 0 && i % every_iterations == 0) || (every_ms > 0.0 && now_ms >= next_ms));
+    }
+    // as Convergence::checkpoint; the figure of the image scale * sums + ls * light
+    template <class WaitAndClock>
+    bool checkpoint(evplp_group *g, int i, WaitAndClock wait_and_clock, float scale, float ls, int32_t mask_emitter) {
+        const double t = wait_and_clock();
+        const auto t0 = std::chrono::steady_clock::now();
+        Point p; p.iteration = i; p.time_ms = t; p.batches = batches;
+        check(g, evplp_group_noise_estimate(g, scale, ls, mask_emitter, p.e), "noise");
+        overhead_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        points.push_back(p);
+        if (every_ms > 0.0) next_ms = (std::floor(t / every_ms) + 1.0) * every_ms;
+        return stop_rel_mse >= 0.0 && (mask.empty() ? p.e[1] : p.e[2]) <= stop_rel_mse;
+    }
+    // after the loop's last synchronise: every shard's unfolded iterations as one more batch, the last checkpoint, the files
+    void finish(evplp_group *g, int i, double now_ms, float scale, float ls, int32_t mask_emitter, int W, int H) {
+        if (!on) return;
+        bool more = false;
+        for (size_t r = 0; r < own.size(); r++) {
+            if (own[r] == folded[r]) continue;
+            if (own.size() > 1) check(g, evplp_group_select_rank(g, (int32_t)r), "select rank");
+            fold(g, r, own[r] - folded[r]);
+            more = true;
+        }
+        if (batches >= 2 && (more || points.empty() || points.back().iteration != i)) checkpoint(g, i, [&] { return now_ms; }, scale, ls, mask_emitter);
+        std::string s = "{\n    \"pixels\": " + std::to_string(pixels) + ",\n";
+        if (!mask.empty()) s += "    \"keptPixels\": " + std::to_string(kept) + ",\n";
+        s += "    \"batchIterations\": " + std::to_string(batch) + ",\n    \"overheadMs\": " + num(overhead_ms) + ",\n    \"checkpoints\": [";
+        for (size_t k = 0; k < points.size(); k++) {
+            const Point &p = points[k];
+            s += std::string(k ? ",\n" : "\n") + "        {\"iteration\": " + std::to_string(p.iteration) + ", \"timeMs\": " + num(p.time_ms) +
+                 ", \"batches\": " + std::to_string(p.batches) + ", \"mse\": " + num(p.e[0]) + ", \"relMse\": " + num(p.e[1]);
+            if (!mask.empty()) s += ", \"relMseMasked\": " + num(p.e[2]);
+            s += "}";
+        }
+        s += "\n    ]\n}\n";
+        std::ofstream of(filename);
+        if (!of || !(of << s)) throw std::runtime_error("cannot write " + filename);
+        if (variance_filename.empty()) return;
+        if (batches < 2) { std::printf("note: noise: %lld fold(s), no variance image (%s) without two\n", batches, variance_filename.c_str()); return; }
+        std::vector<float> var((size_t)W * H * 3);
+        check(g, evplp_group_noise_variance(g, scale, var.data()), "noise variance");
+        std::vector<float> top = flip_y(var, W, H);
+        if (save_image(variance_filename.c_str(), W, H, top.data()) != EVPLP_OK) throw std::runtime_error("cannot write " + variance_filename);
+    }
+
+private:
+    struct Point { int iteration = 0; double time_ms = 0.0; long long batches = 0; double e[3] = { 0.0, 0.0, 0.0 }; };
+    static std::string num(double v) { if (!std::isfinite(v)) return "null"; char b[40]; std::snprintf(b, sizeof b, "%.17g", v); return b; }     // (every bit of the double)
+    void fold(evplp_group *g, size_t r, long long k) {
+        check(g, evplp_group_noise_fold(g, (int32_t)k), "noise fold");
+        folded[r] += k; batches++;
+    }
+    std::string filename, variance_filename;
+    std::vector<uint8_t> mask;
+    int64_t pixels = 0, kept = 0;
+    long long batch = 1, every_iterations = 0, batches = 0;
+    double every_ms = 0.0, next_ms = 0.0, stop_rel_mse = -1.0, overhead_ms = 0.0;
+    std::vector<long long> own, folded;      // per shard: iterations run, iterations folded
+    std::vector<Point> points;
+};
 } // namespace
 
 // The reference's ground-truth technique: unidirectional path tracing with next-event estimation, one sample per
@@ -322,6 +452,7 @@ public:
         int bvh_builder = EVPLP_BVH_SAH;
         if (json.has("bvhBuilder")) bvh_builder = parse_bvh_builder(json.at("bvhBuilder").as_string("bvhBuilder"));
         conv.parse(json, out_dir, out_dir, res_x, res_y);
+        noise.parse(json, out_dir, out_dir, res_x, res_y, frame_mode);
 
         evplp_config cfg; std::memset(&cfg, 0, sizeof(cfg));
         cfg.abi_version = EVPLP_ABI_VERSION; cfg.device = device; cfg.res_x = res_x; cfg.res_y = res_y;
@@ -339,6 +470,7 @@ private:
     void run(evplp_group *h, const HostScene &scene, int W, int H) {
         JitterSampler sampler(rng_offset);
         check(h, evplp_group_clear_accumulators(h), "clear");
+        noise.start(h, 1);
         int num_iterations = 0;
         auto t0 = std::chrono::steady_clock::now();
         auto elapsed_ms = [&]() { return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
@@ -361,11 +493,18 @@ private:
                 const Composite k = composite(num_iterations);
                 if (conv.checkpoint(h, num_iterations, [&] { check(h, evplp_group_synchronize(h), "sync"); return (double)elapsed_ms(); }, k.vs, k.ps, k.ls, k.mask_emitter)) break;
             }
+            if (noise.on) {
+                const bool folded = noise.after_iteration(h, 0);
+                const Composite k = composite(num_iterations);
+                if (noise.due(num_iterations, elapsed_ms(), folded) &&
+                    noise.checkpoint(h, num_iterations, [&] { check(h, evplp_group_synchronize(h), "sync"); return (double)elapsed_ms(); }, k.vs, k.ls, k.mask_emitter)) break;
+            }
             if (elapsed_ms() >= time_limit_ms) break;                                         // :667
         }
         check(h, evplp_group_synchronize(h), "sync");
         float time = elapsed_ms();
-        { const Composite k = composite(num_iterations); conv.finish(h, num_iterations, elapsed_ms(), k.vs, k.ps, k.ls, k.mask_emitter); }
+        { const Composite k = composite(num_iterations); conv.finish(h, num_iterations, elapsed_ms(), k.vs, k.ps, k.ls, k.mask_emitter);
+          noise.finish(h, num_iterations, elapsed_ms(), k.vs, k.ls, k.mask_emitter, W, H); }
         if (use_stat) {                                                                       // :694-704
             Json st = Json::object();
             st.set("time", Json::number(time)); st.set("numIterations", Json::number(num_iterations));
@@ -391,6 +530,7 @@ private:
     bool use_jitter = false, use_stat = false, write_every_frame = false;
     std::string output_filename, stat_filename;
     Convergence conv;
+    Noise noise;
 };
 
 class ComPhotonTechnique {
@@ -447,6 +587,7 @@ public:
         if (!lvc && json.has("forceVsl")) force_vsl = json.at("forceVsl").as_bool("forceVsl");
         if (json.has("bvhBuilder")) bvh_builder = parse_bvh_builder(json.at("bvhBuilder").as_string("bvhBuilder"));   // build-only key
         conv.parse(json, out_dir, out_dir, res_x, res_y);                                                          // build-only key
+        noise.parse(json, out_dir, out_dir, res_x, res_y, frame_mode);                                             // build-only key
 
         // ---- setup(): context + scene upload (replaces GL/OptiX setup :646-708)
         evplp_config cfg; std::memset(&cfg, 0, sizeof(cfg));
@@ -512,6 +653,7 @@ private:
         JitterSampler sampler(rng_offset);
         const int S = run_opts.shard_iterations ? evplp_group_size(h) : 1;
         check(h, evplp_group_clear_accumulators(h), "clear");
+        noise.start(h, 1);
         int num_iterations = 0;
         auto t0 = std::chrono::steady_clock::now();
         // Row blocks dealt by cost (RunOptions above): one frame of the first iteration's light paths and gather with the self-clocking
@@ -544,6 +686,7 @@ private:
         const bool always_profile = time_limit_ms < 1e8f;
         check(h, evplp_group_profile_passes(h, always_profile ? 1 : 0), "profile");
         bool profiling = always_profile;
+        noise.start(h, S);
         for (;;) {
             if (num_iterations == num_max_iteration) break;                                   // :938-941
             if (run_opts.shard_iterations) check(h, evplp_group_select_rank(h, num_iterations % S), "select rank");   // (this iteration's rank)
@@ -590,11 +733,18 @@ private:
             // the combinedFilename composite over ALL iterations so far (:1122; an iteration partition reduces the ranks' sums first)
             if (conv.due(num_iterations, elapsed_ms()) &&
                 conv.checkpoint(h, num_iterations, [&] { wait_for_next(); return (double)elapsed_ms(); }, saved_param(num_iterations), saved_param(num_iterations), 1.0f, 0)) break;
+            // (the fold of the rank this iteration ran on; the checkpoint, like conv's, measures the combinedFilename composite)
+            if (noise.on) {
+                const bool folded = noise.after_iteration(h, (num_iterations - 1) % S);
+                if (noise.due(num_iterations, elapsed_ms(), folded) &&
+                    noise.checkpoint(h, num_iterations, [&] { wait_for_next(); return (double)elapsed_ms(); }, saved_param(num_iterations), 1.0f, 0)) break;
+            }
             if (elapsed_ms() >= time_limit_ms) break;                                         // :1065
         }
         check(h, evplp_group_synchronize(h), "sync");                                         // (every iteration posted has finished)
         float time = elapsed_ms();
         conv.finish(h, num_iterations, elapsed_ms(), saved_param(num_iterations), saved_param(num_iterations), 1.0f, 0);
+        noise.finish(h, num_iterations, elapsed_ms(), saved_param(num_iterations), 1.0f, 0, W, H);
         check(h, evplp_group_profile_passes(h, 1), "profile");
         if (use_stat) {                                                                       // :1109-1119
             Json st = Json::object();
@@ -644,6 +794,7 @@ private:
     uint32_t splat_footprint = EVPLP_FOOTPRINT_PROXY;
     RunOptions run_opts;
     Convergence conv;
+    Noise noise;
     int bvh_builder = EVPLP_BVH_SAH;   // measured 9% faster frames than the Morton LBVH on the conference stand-in; "bvhBuilder": "lbvh" selects the LBVH
 };
 

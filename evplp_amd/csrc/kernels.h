@@ -240,5 +240,20 @@ static_assert(sizeof(RowError) == 32, "RowError must be 32 bytes");
 // rgb: the composite (local rows, y = 0 at the bottom); ref: [H][W][3] and keep: [H][W] (null = every pixel), both rows top to bottom;
 // rows: [local_rows], zeros for a local row outside the image
 void launch_frame_error(const StripDev &st, const float *rgb, const float *ref, const uint8_t *keep, RowError *rows, hipStream_t s);
+// evplp_noise_track's planes of one context, one allocation: Q [3][stride] fp64 (one plane per channel; stride = the accumulator plane's
+// pixels rounded up to even), then c_prev and c_start [plane pixels] float4 (w = 0).  56 B per pixel.
+struct NoisePlanes { double *q; float4 *prev, *start; size_t stride; };
+// the moments an estimate reads: one context's (s = null: S = c_prev - c_start, per channel in fp32) or the shards' pooled ones (q and s
+// [3][stride] fp64, summed in rank order)
+struct NoiseMoments { const double *q, *s; const float4 *prev, *start; size_t stride; };
+// k = 0: c_prev = c_start = c, Q = 0 (tracking starts); k >= 1: a batch of k iterations closes (noise_fold_kernel, kernels_trace.hip)
+void launch_noise_fold(const NoisePlanes &m, const float4 *vpl, const float4 *pm, size_t n, int32_t k, hipStream_t s);
+// out q / s [3][stride]: first ? src : out + src (one shard of the pooling, every add rounded)
+void launch_noise_pool(const NoiseMoments &src, bool first, double *q, double *s_out, size_t n, hipStream_t s);
+// per local row: { sum num, sum rel, sum rel over kept pixels, kept pixels } of the variance against the composite rgb (layout as frame_error)
+void launch_noise_rows(const StripDev &st, const NoiseMoments &m, double K, double B, double s2K, const float4 *light, float ls, int mask_emitter,
+                       const float *rgb, const uint8_t *keep, RowError *rows, hipStream_t s);
+// the variance of every plane pixel, 3 floats each (resolve's layout)
+void launch_noise_variance(const NoiseMoments &m, double K, double B, double s2K, size_t n, float *out_rgb, hipStream_t s);
 
 } // namespace evplp

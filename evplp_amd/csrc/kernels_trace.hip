@@ -319,6 +319,141 @@ void launch_frame_error(const StripDev &st, const float *rgb, const float *ref, 
     hipLaunchKernelGGL(frame_error_kernel, dim3((unsigned)st.local_rows), dim3(kFrameErrorThreads), 0, s, st, rgb, ref, keep, rows);
 }
 
+// ---- per-pixel noise from the running sums (include/evplp.h evplp_noise_*).  Every operation is rounded on its own (this file is built
+// without contraction; the _rn intrinsics say so where it matters), so numpy reproduces every per-pixel value.
+// Fold: thread t takes the pixels 2t and 2t + 1 -- the accumulator and c_prev planes as float4, Q as one double2 per channel plane (its
+// planes are padded to an even pixel count, so the pair's load never leaves them).  Per channel, fp32: c = vpl + photon, d = c - c_prev;
+// fp64: Q += d * d / k.  Init (k = 0): c_prev = c_start = c, Q = 0.  One pass, no atomics: 112 B per pixel.
+template <bool Init>
+__global__ __launch_bounds__(256) void noise_fold_kernel(NoisePlanes m, const float4 *vpl, const float4 *pm, size_t n, double k) {
+    const size_t i = 2 * ((size_t)blockIdx.x * 256 + threadIdx.x);
+    if (i >= n) return;
+    const bool two = i + 1 < n;
+    float4 c[2];
+    for (int j = 0; j < 2; j++) {
+        if (j == 1 && !two) { c[1] = make_float4(0.f, 0.f, 0.f, 0.f); break; }
+        const float4 v = vpl[i + j], p = pm[i + j];
+        c[j] = make_float4(__fadd_rn(v.x, p.x), __fadd_rn(v.y, p.y), __fadd_rn(v.z, p.z), 0.f);
+    }
+    if (Init) {
+        for (int j = 0; j < (two ? 2 : 1); j++) { m.prev[i + j] = c[j]; m.start[i + j] = c[j]; }
+        for (int ch = 0; ch < 3; ch++) *(double2 *)(m.q + ch * m.stride + i) = make_double2(0.0, 0.0);
+        return;
+    }
+    float4 prev[2];
+    prev[0] = m.prev[i]; prev[1] = two ? m.prev[i + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
+    double2 q[3];
+    for (int ch = 0; ch < 3; ch++) q[ch] = *(const double2 *)(m.q + ch * m.stride + i);
+    double d[2][3];
+    for (int j = 0; j < 2; j++) {
+        d[j][0] = (double)__fsub_rn(c[j].x, prev[j].x); d[j][1] = (double)__fsub_rn(c[j].y, prev[j].y); d[j][2] = (double)__fsub_rn(c[j].z, prev[j].z);
+    }
+    for (int ch = 0; ch < 3; ch++) {
+        q[ch].x = __dadd_rn(q[ch].x, __ddiv_rn(__dmul_rn(d[0][ch], d[0][ch]), k));
+        q[ch].y = __dadd_rn(q[ch].y, __ddiv_rn(__dmul_rn(d[1][ch], d[1][ch]), k));      // (a lone last pixel: the pad gains 0)
+        *(double2 *)(m.q + ch * m.stride + i) = q[ch];
+    }
+    m.prev[i] = c[0];
+    if (two) m.prev[i + 1] = c[1];
+}
+void launch_noise_fold(const NoisePlanes &m, const float4 *vpl, const float4 *pm, size_t n, int32_t k, hipStream_t s) {
+    const size_t threads = (n + 1) / 2;
+    if (threads == 0) return;
+    const dim3 grid((unsigned)((threads + 255) / 256));
+    if (k == 0) hipLaunchKernelGGL(noise_fold_kernel<true>, grid, dim3(256), 0, s, m, vpl, pm, n, 1.0);
+    else hipLaunchKernelGGL(noise_fold_kernel<false>, grid, dim3(256), 0, s, m, vpl, pm, n, (double)k);
+}
+
+// Q and S of pixel i, per channel
+__device__ inline void noise_moments(const NoiseMoments &m, size_t i, double q[3], double s[3]) {
+    for (int ch = 0; ch < 3; ch++) q[ch] = m.q[ch * m.stride + i];
+    if (m.s) { for (int ch = 0; ch < 3; ch++) s[ch] = m.s[ch * m.stride + i]; return; }
+    const float4 a = m.prev[i], b = m.start[i];
+    s[0] = (double)__fsub_rn(a.x, b.x); s[1] = (double)__fsub_rn(a.y, b.y); s[2] = (double)__fsub_rn(a.z, b.z);
+}
+// the variance of one channel of the image scale * c: s2K * max(0, (Q - S * S / K) / (B - 1)), s2K = scale^2 * K
+__device__ inline double noise_var(double q, double s, double K, double B1, double s2K) {
+    const double v = __ddiv_rn(__dsub_rn(q, __ddiv_rn(__dmul_rn(s, s), K)), B1);
+    return __dmul_rn(s2K, v > 0.0 ? v : 0.0);
+}
+
+// Shard pooling (EVPLP_PARTITION_ITERATIONS): launched once per shard in rank order; q / s_out = first ? the shard's : + the shard's
+__global__ __launch_bounds__(256) void noise_pool_kernel(NoiseMoments src, int first, double *q, double *s_out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double qs[3], ss[3];
+    noise_moments(src, i, qs, ss);
+    for (int ch = 0; ch < 3; ch++) {
+        const size_t o = ch * src.stride + i;
+        q[o] = first ? qs[ch] : __dadd_rn(q[o], qs[ch]);
+        s_out[o] = first ? ss[ch] : __dadd_rn(s_out[o], ss[ch]);
+    }
+}
+void launch_noise_pool(const NoiseMoments &src, bool first, double *q, double *s_out, size_t n, hipStream_t s) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(noise_pool_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, first ? 1 : 0, q, s_out, n);
+}
+
+// evplp_noise_estimate: one workgroup per local row, the reduction of frame_error_kernel (the same fixed shape and fp64 sums).  Per pixel,
+// fp64: var_ch = noise_var(..) (0 on an emitter pixel under mask_emitter: 0 < light.x * ls), num = (var_r + var_g) + var_b,
+// den = ((r * r + g * g) + b * b) + 0.001 of the composite, rel = num / den.
+constexpr int kNoiseRowThreads = 256;
+__global__ __launch_bounds__(kNoiseRowThreads) void noise_rows_kernel(StripDev st, NoiseMoments m, double K, double B1, double s2K, const float4 *light,
+                                                                       float ls, int mask_emitter, const float *rgb, const uint8_t *keep, RowError *rows) {
+    __shared__ double wave_sums[kNoiseRowThreads / 64][4];
+    const int l = (int)blockIdx.x, tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int y = st.global_row(l);
+    double s[4] = { 0.0, 0.0, 0.0, 0.0 };
+    if (y < st.H) {
+        const size_t own = (size_t)l * st.W, top = (size_t)(st.H - 1 - y) * st.W;     // (the mask's rows run top to bottom)
+        for (int x = tid; x < st.W; x += kNoiseRowThreads) {
+            const size_t i = own + x;
+            double num = 0.0;
+            if (!(mask_emitter && 0.0f < __fmul_rn(light[i].x, ls))) {
+                double q[3], sm[3];
+                noise_moments(m, i, q, sm);
+                num = __dadd_rn(__dadd_rn(noise_var(q[0], sm[0], K, B1, s2K), noise_var(q[1], sm[1], K, B1, s2K)), noise_var(q[2], sm[2], K, B1, s2K));
+            }
+            const double r = rgb[3 * i], g = rgb[3 * i + 1], b = rgb[3 * i + 2];
+            const double den = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(r, r), __dmul_rn(g, g)), __dmul_rn(b, b)), 0.001);
+            const double rel = __ddiv_rn(num, den);
+            s[0] += num; s[1] += rel;
+            if (!keep || keep[top + x]) { s[2] += rel; s[3] += 1.0; }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        for (int off = 32; off > 0; off >>= 1) s[k] += __shfl_down(s[k], off, 64);
+    if (lane == 0) for (int k = 0; k < 4; k++) wave_sums[wave][k] = s[k];
+    __syncthreads();
+    if (tid == 0) {
+        double t[4];
+        for (int k = 0; k < 4; k++) {
+            t[k] = wave_sums[0][k];
+            for (int w = 1; w < kNoiseRowThreads / 64; w++) t[k] += wave_sums[w][k];
+        }
+        rows[l] = RowError{ t[0], t[1], t[2], t[3] };
+    }
+}
+void launch_noise_rows(const StripDev &st, const NoiseMoments &m, double K, double B, double s2K, const float4 *light, float ls, int mask_emitter,
+                       const float *rgb, const uint8_t *keep, RowError *rows, hipStream_t s) {
+    if (st.local_rows <= 0) return;
+    hipLaunchKernelGGL(noise_rows_kernel, dim3((unsigned)st.local_rows), dim3(kNoiseRowThreads), 0, s, st, m, K, B - 1.0, s2K, light, ls, mask_emitter, rgb, keep, rows);
+}
+
+// evplp_noise_variance: (float) noise_var per channel of every plane pixel
+__global__ __launch_bounds__(256) void noise_variance_kernel(NoiseMoments m, double K, double B1, double s2K, size_t n, float *out) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double q[3], s[3];
+    noise_moments(m, i, q, s);
+    for (int ch = 0; ch < 3; ch++) out[3 * i + ch] = (float)noise_var(q[ch], s[ch], K, B1, s2K);
+}
+void launch_noise_variance(const NoiseMoments &m, double K, double B, double s2K, size_t n, float *out_rgb, hipStream_t s) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(noise_variance_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, m, K, B - 1.0, s2K, n, out_rgb);
+}
+
 void launch_primary(const PrimaryArgs &a, hipStream_t s) {
     int tiles_x = (a.st.W + 7) / 8, tiles_y = (a.st.local_rows + 7) / 8;
 #if EVPLP_PRIMARY_BLOCKS

@@ -119,6 +119,7 @@ typedef struct evplp_config {
      *   photon bins + compact photons   -                0.5 GB            0.4 GB          0.5 GB
      *   scene (331 k triangles)         0.1 GB everywhere (nodes, leaf blocks in two layouts, attributes; textures on top)
      *   error reference (if set)        12 B + 1 B (mask) per pixel of the WHOLE image on every context (evplp_set_error_reference)
+     *   noise tracking (if on)          56 B per pixel of the context's planes (+ 1 B per image pixel with a mask; evplp_noise_track)
      * A caller that has the device to itself sets cut_scratch_bytes = 72 GB, vsl_mask_bytes = 14 GB for config #5 (one band, one launch). */
     uint64_t cut_scratch_bytes;
     uint64_t vsl_mask_bytes;
@@ -306,6 +307,36 @@ int evplp_set_error_reference(evplp_context *ctx, const float *rgb_top_down, con
 int evplp_frame_error(evplp_context *ctx, float vpl_scale, float photon_scale, float light_scale,
                       int32_t mask_emitter, int32_t gamma, double out[3]);
 
+/* Per-pixel noise without a reference image: the spread between the iterations of an accumulating run, tracked on the device.
+ * Tracking follows the running sum c = rgb(EVPLP_BUF_VPL_ACCUM) + rgb(EVPLP_BUF_PHOTON_ACCUM) (fp32 per channel; the image a technique
+ * saves is scale * c + light).  A fold closes batch j of k_j >= 1 iterations; its sample is D_j = c - c_prev, per channel in fp32.  Per pixel
+ * and channel the library keeps, in fp64, Q = sum_j D_j^2 / k_j (a device plane); S = c_prev - c_start is taken in fp32 when it is needed
+ * (c_prev: c at the last fold, c_start: c when tracking started or the accumulators were last cleared); K = sum_j k_j and B = the number of
+ * folds are host counts.  The per-iteration variance is the batch-means estimator for batches of unequal size,
+ *     s2 = max(0, (Q - S^2 / K) / (B - 1))      (exact in expectation for independent, identically distributed iterations),
+ * and the variance of the image scale * c + light is scale^2 * K * s2 (the light plane is constant and adds nothing).
+ * Not covered: bias -- VPL clamping, the photon radius: for those techniques the figure is a lower bound on the error, for path tracing it is
+ * the error -- and DoProgressive runs, whose iterations are not identically distributed: there the figure is an approximation.
+ * on = 1: allocates and zeroes the moments, settles the pending photon splat and snapshots c_prev = c_start = c (tracking may start in the
+ * middle of a run; a second on = 1 starts again).  mask: optional, in evplp_set_error_reference's format (kept pixels of evplp_noise_estimate's
+ * third figure).  on = 0 releases everything.  Device memory: 56 B per pixel of the context's planes (W x local_rows: Q 3 x 8 B, c_prev and
+ * c_start 16 B each; 8 B more when that pixel count is odd), 1 B per IMAGE pixel with a mask, 32 B per local row.
+ * evplp_clear_accumulators and evplp_set_blocks (so also a group's rebalance) start tracking again from the cleared sums: K = B = 0. */
+int evplp_noise_track(evplp_context *ctx, int32_t on, const uint8_t *mask_rgb8_top_down);
+/* Closes a batch of `iterations` >= 1 accumulating iterations.  It settles the pending photon splat first, as evplp_resolve does, so it sees
+ * every splat of its iterations exactly once (a pass re-run after a bins overflow included); then one element-wise pass, in stream order.
+ * Tracking off, or iterations < 1: EVPLP_ERR_INVALID. */
+int evplp_noise_fold(evplp_context *ctx, int32_t iterations);
+/* The estimated error of the composite evplp_frame_error would measure at vpl_scale = photon_scale = scale (gamma off), reduced on the
+ * device: per pixel num = sum over channels of the variance (0 on an emitter pixel where mask_emitter hides the sums), rel = num /
+ * (|composite|^2 + 0.001), all in fp64; out = { mean num, mean rel, mean rel over kept pixels (0 when none) }.  The rows are reduced in a fixed
+ * order and added on the host in image row order: one context and a row-strip group of any block table give the same doubles.
+ * Tracking off or fewer than two folds: EVPLP_ERR_INVALID. */
+int evplp_noise_estimate(evplp_context *ctx, float scale, float light_scale, int32_t mask_emitter, double out[3]);
+/* The per-pixel variance scale^2 * K * s2 (fp32 per channel) in evplp_resolve's layout: local_rows x W x 3, y = 0 at the bottom.
+ * Tracking off or fewer than two folds: EVPLP_ERR_INVALID. */
+int evplp_noise_variance(evplp_context *ctx, float scale, float *out_rgb);
+
 /* Row-strip contexts (strip_count > 1): which blocks of strip_rows image rows this context owns.  By default block b belongs to rank
  * b % strip_count.  evplp_set_blocks replaces that by a table: local block l holds image block image_blocks[l], l < count <= the context's
  * capacity (evplp_config.strip_capacity_rows / strip_rows); image_blocks = NULL restores the default.  Every kernel, statistic and buffer
@@ -482,6 +513,17 @@ int evplp_group_set_error_reference(evplp_group *g, const float *rgb_top_down, c
  * bit, one context's over the same frame.  No reference, or a null out: EVPLP_ERR_INVALID on the caller's thread (the group stays usable). */
 int evplp_group_frame_error(evplp_group *g, float vpl_scale, float photon_scale, float light_scale,
                             int32_t mask_emitter, int32_t gamma, double out[3]);
+/* evplp_noise_* for a group.  EVPLP_PARTITION_STRIPS: every rank tracks and folds its own rows; an estimate posts about 32 bytes per row to
+ * the host and all-gathers nothing, and equals one context's over the same frame bit for bit.  EVPLP_PARTITION_ITERATIONS: a fold closes a
+ * batch of the SELECTED rank's iterations (evplp_group_select_rank); an estimate pools the ranks on the GPUs -- Q, S, K and B summed over the
+ * ranks, Q and S in rank order on rank 0's device, read in place from virtual ranks and all-gathered from distinct devices (every rank then
+ * holds n x the per-rank bytes of evplp_noise_track in a staging buffer; rank 0 holds 48 B per pixel of pooled moments) -- and composites
+ * the ranks' summed accumulators as evplp_group_resolve does.  Tracking off, fewer than two folds in all, bad arguments: EVPLP_ERR_INVALID
+ * on the caller's thread (the group stays usable).  evplp_group_noise_variance returns the whole image in evplp_group_resolve's layout. */
+int evplp_group_noise_track(evplp_group *g, int32_t on, const uint8_t *mask_rgb8_top_down);
+int evplp_group_noise_fold(evplp_group *g, int32_t iterations);
+int evplp_group_noise_estimate(evplp_group *g, float scale, float light_scale, int32_t mask_emitter, double out[3]);
+int evplp_group_noise_variance(evplp_group *g, float scale, float *out_rgb);
 
 /* ---- host side of the reference interface (no GPU needed for these) ---- */
 /* The anti-aliasing jitters of the first `count` iterations of a technique run with this rngOffset: NDC translations (x, y) =
