@@ -126,6 +126,9 @@ _SIGNATURES = {
     "evplp_noise_fold": (C.c_int, [_P, C.c_int32]),
     "evplp_noise_estimate": (C.c_int, [_P, C.c_float, C.c_float, C.c_int32, C.POINTER(C.c_double * 3)]),
     "evplp_noise_variance": (C.c_int, [_P, C.c_float, _P]),
+    "evplp_adaptive_enable": (C.c_int, [_P, C.c_int32]),
+    "evplp_adaptive_retire": (C.c_int, [_P, C.c_float, C.c_float, C.c_int32, C.c_double, C.c_int32]),
+    "evplp_adaptive_tiles": (C.c_int, [_P, _P, C.c_int32]),
     "evplp_clear_accumulators": (C.c_int, [_P]),
     "evplp_set_blocks": (C.c_int, [_P, _P, C.c_int32]),
     "evplp_get_blocks": (C.c_int, [_P, _P, C.c_int32]),
@@ -177,6 +180,9 @@ _SIGNATURES = {
     "evplp_group_noise_fold": (C.c_int, [_P, C.c_int32]),
     "evplp_group_noise_estimate": (C.c_int, [_P, C.c_float, C.c_float, C.c_int32, C.POINTER(C.c_double * 3)]),
     "evplp_group_noise_variance": (C.c_int, [_P, C.c_float, _P]),
+    "evplp_group_adaptive_enable": (C.c_int, [_P, C.c_int32]),
+    "evplp_group_adaptive_retire": (C.c_int, [_P, C.c_float, C.c_float, C.c_int32, C.c_double, C.c_int32]),
+    "evplp_group_adaptive_tiles": (C.c_int, [_P, _P, C.c_int32]),
     "evplp_jitter_sequence": (C.c_int, [C.c_uint32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "evplp_json_query": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int32, C.POINTER(C.c_double), C.c_char_p, C.c_int32]),
     "evplp_progressive_step": (None, [C.c_int32, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.POINTER(C.c_float),
@@ -262,6 +268,15 @@ def _fold_iterations(iterations) -> int:
     if isinstance(iterations, (bool, np.bool_)) or not isinstance(iterations, (int, np.integer)) or iterations < 1:
         raise ValueError(f"noise_fold: iterations must be an int >= 1, got {iterations!r}")
     return int(iterations)
+
+
+def _adaptive_retire_args(tile_rel_mse, min_batches):
+    """adaptive_retire's thresholds, checked before any C call: tile_rel_mse a number >= 0, min_batches an int >= 2"""
+    if isinstance(tile_rel_mse, (bool, np.bool_)) or not isinstance(tile_rel_mse, (int, float, np.integer, np.floating)) or not tile_rel_mse >= 0.0:
+        raise ValueError(f"adaptive_retire: tile_rel_mse must be a number >= 0, got {tile_rel_mse!r}")
+    if isinstance(min_batches, (bool, np.bool_)) or not isinstance(min_batches, (int, np.integer)) or min_batches < 2:
+        raise ValueError(f"adaptive_retire: min_batches must be an int >= 2, got {min_batches!r}")
+    return float(tile_rel_mse), int(min_batches)
 
 
 def frame_params(camera_pos, mis_mode=0, pdf_mc=0.0, clamping_value=0.0, photon_radius=0.0, vsl_radius=0.0,
@@ -500,6 +515,21 @@ class Context:
         """per-pixel variance of scale * sums, float32 (local_rows, W, 3), y = 0 at the bottom"""
         out = np.empty((self.local_rows, self.W, 3), dtype=np.float32)
         self._check(self._lib.evplp_noise_variance(self._h, float(scale), _ptr(out)))
+        return out
+
+    def adaptive_enable(self, on=True):
+        """Switch the adaptive gather on or off (before the first accumulating gather since the last clear; needs noise tracking; include/evplp.h)"""
+        self._check(self._lib.evplp_adaptive_enable(self._h, int(bool(on))))
+
+    def adaptive_retire(self, scale, tile_rel_mse, min_batches=2, light_scale=1.0, mask_emitter=False) -> int:
+        """retire the active tiles whose mean relative variance of scale * sums + light_scale * light is <= tile_rel_mse; returns how many"""
+        tau, mb = _adaptive_retire_args(tile_rel_mse, min_batches)
+        return self._check(self._lib.evplp_adaptive_retire(self._h, float(scale), float(light_scale), int(mask_emitter), tau, mb))
+
+    def adaptive_tiles(self) -> np.ndarray:
+        """int32 (ceil(H / 8), ceil(W / 8)), tile rows from the bottom: n_t of a retired tile, N of an active one (0: another rank's)"""
+        out = np.zeros(((self.H + 7) // 8, (self.W + 7) // 8), dtype=np.int32)
+        self._check(self._lib.evplp_adaptive_tiles(self._h, _ptr(out), out.size))
         return out
 
     def set_blocks(self, image_blocks=None):
@@ -769,6 +799,21 @@ class Group:
         """per-pixel variance of scale * sums, float32 (H, W, 3), y = 0 at the bottom"""
         out = np.empty((self.H, self.W, 3), dtype=np.float32)
         self._check(self._lib.evplp_group_noise_variance(self._h, float(scale), _ptr(out)))
+        return out
+
+    def adaptive_enable(self, on=True):
+        """Switch the adaptive gather on or off (before the first accumulating gather since the last clear; needs noise tracking; include/evplp.h)"""
+        self._check(self._lib.evplp_group_adaptive_enable(self._h, int(bool(on))))
+
+    def adaptive_retire(self, scale, tile_rel_mse, min_batches=2, light_scale=1.0, mask_emitter=False) -> int:
+        """retire the active tiles whose mean relative variance of scale * sums + light_scale * light is <= tile_rel_mse; returns how many"""
+        tau, mb = _adaptive_retire_args(tile_rel_mse, min_batches)
+        return self._check(self._lib.evplp_group_adaptive_retire(self._h, float(scale), float(light_scale), int(mask_emitter), tau, mb))
+
+    def adaptive_tiles(self) -> np.ndarray:
+        """int32 (ceil(H / 8), ceil(W / 8)), tile rows from the bottom: n_t of a retired tile, N of an active one (0: another rank's)"""
+        out = np.zeros(((self.H + 7) // 8, (self.W + 7) // 8), dtype=np.int32)
+        self._check(self._lib.evplp_group_adaptive_tiles(self._h, _ptr(out), out.size))
         return out
 
 

@@ -32,6 +32,8 @@ static size_t buffer_bytes(const evplp_context *c, int which) {
 }
 
 static int settle_splat(evplp_context *c);
+static int adapt_reset(evplp_context *c);
+namespace evplp { AdaptTiles adapt_view(const evplp_context *c, float scale); }
 
 namespace evplp { void set_context_error(evplp_context *ctx, const char *text) { if (ctx) ctx->set_error("%s", text ? text : ""); } }
 
@@ -203,6 +205,7 @@ extern "C" void evplp_destroy(evplp_context *c) {
     hipFree(c->d_proxy_slabs); hipFree(c->d_proxy_hm); hipFree(c->d_tile_frags); hipFree(c->d_blocks); hipFree(c->d_block_cost);
     hipFree(c->d_err_ref); hipFree(c->d_err_keep); hipFree(c->d_err_rows);
     hipFree(c->d_noise); hipFree(c->d_noise_keep); hipFree(c->d_noise_rows);
+    hipFree(c->d_adapt_tiles); hipFree(c->d_adapt_snap);
     for (int i = 0; i < EVPLP_PASS_COUNT; i++) {
         if (c->ev_begin[i]) hipEventDestroy(c->ev_begin[i]);
         if (c->ev_end[i]) hipEventDestroy(c->ev_end[i]);
@@ -724,7 +727,12 @@ static int run_gather(evplp_context *c, const evplp_frame_params *fp, bool vsl) 
     int rc = pass_ready(c, name, false); if (rc) return rc;
     if ((rc = check_fp(c, fp, name))) return rc;
     if (fp->num_vpl_light_paths == 0) { c->set_error("%s: num_vpl_light_paths is 0 (the reference disables the pass, rtcomphoton.h:200-203)", name); return EVPLP_ERR_INVALID; }
+    if (c->d_adapt_tiles && fp->do_accumulate == 0) { c->set_error("%s: adaptivity is on (evplp_adaptive_enable): a gather must accumulate", name); return EVPLP_ERR_INVALID; }
     GatherArgs a; fill_gather_args(c, fp, a, pass);
+    // adaptivity (evplp_adaptive_enable): retired tiles' items end at once and the reduce writes their pixels from the snapshot.  A calibration
+    // launch gathers every tile (its clocks price whole blocks) and so needs every cut slot: the cut kernel skips nothing then.
+    AdaptArgs ad{};
+    if (c->d_adapt_tiles) { ad.tiles = c->d_adapt_tiles; ad.snap = c->d_adapt_snap; ad.n1 = (int32_t)(c->adapt_n + 1); }
     // work-item size: k consecutive splits per wavefront (fixed summation tree: the result does not depend on k).  The per-item
     // statistics need (VPLs per split) * k < 65536.
     int k = 1;
@@ -777,6 +785,7 @@ static int run_gather(evplp_context *c, const evplp_frame_params *fp, bool vsl) 
             else { (void)hipGetLastError(); use_cuts = false; band_rows = nby; }     // (no memory for the scratch: the walks start at the root)
         }
         ca.cuts = c->d_cuts;
+        ca.adapt_tiles = c->calibrate ? nullptr : ad.tiles;
     } else use_cuts = false;
     if ((rc = pass_begin(c, pass))) return rc;
     const uint32_t nrec = fp->photons_per_path * fp->num_vpl_light_paths;   // lighttracing.cu:368
@@ -829,16 +838,18 @@ static int run_gather(evplp_context *c, const evplp_frame_params *fp, bool vsl) 
         if (vsl) {
             for (int g0 = 0; g0 < vsl_groups; g0 += vsl_per_launch) {
                 a.group_first = g0; a.group_count = std::min(vsl_per_launch, vsl_groups - g0);
-                launch_gather_vsl(a, c->stream);
+                launch_gather_vsl(a, c->stream, ad);
             }
             a.group_first = 0; a.group_count = 0;
-        } else launch_gather_vpl_items(a, c->stream);
+        } else launch_gather_vpl_items(a, c->stream, ad);
     }
     a.band_first = 0; a.band_rows = 0;
     HIP_TRY(c, hipEventRecord(c->ev_dom_end[pass], c->stream));
-    launch_gather_reduce(a, vsl ? 0 : 1, c->stream);
+    launch_gather_reduce(a, vsl ? 0 : 1, c->stream, ad);
     c->pass_has_dom[pass] = true;
-    return pass_end(c, pass);
+    if ((rc = pass_end(c, pass))) return rc;
+    if (fp->do_accumulate) c->adapt_n++;
+    return EVPLP_OK;
 }
 extern "C" int evplp_gather_vpl(evplp_context *c, const evplp_frame_params *fp) { CTX_CHECK(c); return run_gather(c, fp, false); }
 extern "C" int evplp_gather_vsl(evplp_context *c, const evplp_frame_params *fp) { CTX_CHECK(c); return run_gather(c, fp, true); }
@@ -847,6 +858,7 @@ extern "C" int evplp_gather_vsl(evplp_context *c, const evplp_frame_params *fp) 
 extern "C" int evplp_gather_lvc(evplp_context *c, const evplp_frame_params *fp) {
     CTX_CHECK(c);
     const int pass = EVPLP_PASS_GATHER_LVC;
+    if (c->d_adapt_tiles) { c->set_error("evplp_gather_lvc: adaptivity is on (evplp_adaptive_enable): VPL and VSL gathers only"); return EVPLP_ERR_INVALID; }
     int rc = pass_ready(c, "evplp_gather_lvc", false); if (rc) return rc;
     if ((rc = check_fp(c, fp, "evplp_gather_lvc"))) return rc;
     if (fp->num_vpl_light_paths == 0) { c->set_error("evplp_gather_lvc: num_vpl_light_paths is 0"); return EVPLP_ERR_INVALID; }
@@ -858,6 +870,7 @@ extern "C" int evplp_gather_lvc(evplp_context *c, const evplp_frame_params *fp) 
 
 extern "C" int evplp_path_trace(evplp_context *c, const float camera_pos[3], uint32_t rng_seed, uint32_t max_bounces, int32_t do_accumulate) {
     CTX_CHECK(c);
+    if (c->d_adapt_tiles) { c->set_error("evplp_path_trace: adaptivity is on (evplp_adaptive_enable): VPL and VSL gathers only"); return EVPLP_ERR_INVALID; }
     int rc = pass_ready(c, "evplp_path_trace", false); if (rc) return rc;
     if (!camera_pos) { c->set_error("evplp_path_trace: null camera position"); return EVPLP_ERR_INVALID; }
     PathTraceArgs a; std::memset(&a, 0, sizeof(a));
@@ -1086,6 +1099,10 @@ static void release_noise(evplp_context *c) {
     c->d_noise = nullptr; c->d_noise_keep = nullptr; c->d_noise_rows = nullptr; c->noise_rows.clear(); c->noise_k = c->noise_b = 0;
 }
 namespace evplp {
+// the tile records as the noise kernels read them (tiles = null: adaptivity is off)
+AdaptTiles adapt_view(const evplp_context *c, float scale) {
+    return AdaptTiles{ c->d_adapt_tiles, c->tiles_x, 0, (double)c->adapt_n, (double)scale };
+}
 NoisePlanes noise_planes(const evplp_context *c) {
     const size_t px = (size_t)c->st.W * c->st.local_rows;
     double *q = (double *)c->d_noise;
@@ -1100,7 +1117,9 @@ size_t noise_bytes(const evplp_context *c) { return sizeof(double) * 3 * c->nois
 int noise_rows(evplp_context *c, const NoiseMoments &m, const float4 *light, double K, double B, float scale, float ls, int32_t mask_emitter) {
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     const double s2K = (double)scale * (double)scale * K;
-    launch_noise_rows(c->st, m, K, B, s2K, light, ls, mask_emitter, c->d_rgb, c->d_noise_keep, c->d_noise_rows, c->stream);
+    if (c->d_adapt_tiles && !m.s)      // (a context's own moments with retired tiles; pooled shards never have any)
+        launch_noise_rows_adaptive(c->st, m, K, B, s2K, light, ls, mask_emitter, c->d_rgb, c->d_noise_keep, c->d_noise_rows, adapt_view(c, scale), c->stream);
+    else launch_noise_rows(c->st, m, K, B, s2K, light, ls, mask_emitter, c->d_rgb, c->d_noise_keep, c->d_noise_rows, c->stream);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(c->noise_rows.data(), c->d_noise_rows, sizeof(RowError) * (size_t)c->st.local_rows, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1108,7 +1127,8 @@ int noise_rows(evplp_context *c, const NoiseMoments &m, const float4 *light, dou
 }
 int noise_variance_to_device(evplp_context *c, const NoiseMoments &m, double K, double B, float scale) {
     HIP_TRY(c, hipSetDevice(c->cfg.device));
-    launch_noise_variance(m, K, B, (double)scale * (double)scale * K, (size_t)c->st.W * c->st.local_rows, c->d_rgb, c->stream);
+    if (c->d_adapt_tiles && !m.s) launch_noise_variance_adaptive(c->st, m, K, B, (double)scale * (double)scale * K, c->d_rgb, adapt_view(c, scale), c->stream);
+    else launch_noise_variance(m, K, B, (double)scale * (double)scale * K, (size_t)c->st.W * c->st.local_rows, c->d_rgb, c->stream);
     HIP_TRY(c, hipGetLastError());
     return EVPLP_OK;
 }
@@ -1124,6 +1144,10 @@ static int noise_restart(evplp_context *c) {
 extern "C" int evplp_noise_track(evplp_context *c, int32_t on, const uint8_t *mask) {
     CTX_CHECK(c);
     if (!on && mask) { c->set_error("evplp_noise_track: a mask without tracking"); return EVPLP_ERR_INVALID; }
+    if (c->d_adapt_tiles && c->adapt_n > 0) {
+        c->set_error("evplp_noise_track: adaptivity is on and %lld gather(s) accumulated: the retired tiles' figures need this tracking", (long long)c->adapt_n);
+        return EVPLP_ERR_INVALID;
+    }
     { int rc_ = settle_splat(c); if (rc_) return rc_; }            // (the snapshot sees every splat enqueued so far)
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));                   // (no fold or estimate of an earlier call still reads the old planes)
@@ -1154,8 +1178,11 @@ extern "C" int evplp_noise_fold(evplp_context *c, int32_t iterations) {
     if (iterations < 1) { c->set_error("evplp_noise_fold: a batch holds >= 1 iterations, not %d", iterations); return EVPLP_ERR_INVALID; }
     { int rc_ = settle_splat(c); if (rc_) return rc_; }            // (every splat of the batch has its verdict; a re-run is enqueued before the fold)
     HIP_TRY(c, hipSetDevice(c->cfg.device));
-    launch_noise_fold(evplp::noise_planes(c), (const float4 *)c->buf[EVPLP_BUF_VPL_ACCUM], (const float4 *)c->buf[EVPLP_BUF_PHOTON_ACCUM],
-                      (size_t)c->st.W * c->st.local_rows, iterations, c->stream);
+    if (c->d_adapt_tiles)          // (retired pixels keep their Q and c_prev)
+        launch_noise_fold_adaptive(evplp::noise_planes(c), (const float4 *)c->buf[EVPLP_BUF_VPL_ACCUM], (const float4 *)c->buf[EVPLP_BUF_PHOTON_ACCUM],
+                                   c->st, evplp::adapt_view(c, 1.0f), iterations, c->stream);
+    else launch_noise_fold(evplp::noise_planes(c), (const float4 *)c->buf[EVPLP_BUF_VPL_ACCUM], (const float4 *)c->buf[EVPLP_BUF_PHOTON_ACCUM],
+                           (size_t)c->st.W * c->st.local_rows, iterations, c->stream);
     HIP_TRY(c, hipGetLastError());
     c->noise_k += iterations; c->noise_b += 1;
     return EVPLP_OK;
@@ -1186,6 +1213,93 @@ extern "C" int evplp_noise_variance(evplp_context *c, float scale, float *out_rg
     HIP_TRY(c, hipMemcpyAsync(out_rgb, c->d_rgb, sizeof(float) * 3 * (size_t)c->st.W * c->st.local_rows, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return EVPLP_OK;
+}
+
+// ---- adaptive gather: tiles retire once their estimated noise is low enough (include/evplp.h evplp_adaptive_*)
+static void release_adapt(evplp_context *c) {
+    hipFree(c->d_adapt_tiles); hipFree(c->d_adapt_snap);
+    c->d_adapt_tiles = nullptr; c->d_adapt_snap = nullptr; c->adapt_tiles.clear();
+}
+static size_t adapt_tile_count(const evplp_context *c) { return (size_t)c->tiles_x * (size_t)c->tiles_y; }
+// every tile active (stream order); the records are (re)allocated when the planes' tiles have changed (a new block table)
+static int adapt_reset(evplp_context *c) {
+    const size_t nt = adapt_tile_count(c), px = (size_t)c->st.W * c->st.local_rows;
+    if (c->adapt_tiles.size() != nt) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        hipFree(c->d_adapt_tiles); hipFree(c->d_adapt_snap); c->d_adapt_tiles = nullptr; c->d_adapt_snap = nullptr;
+        hipError_t e = hipMalloc((void **)&c->d_adapt_tiles, sizeof(int4) * std::max<size_t>(nt, 1));
+        if (e == hipSuccess) e = hipMalloc((void **)&c->d_adapt_snap, sizeof(float4) * std::max<size_t>(px, 1));
+        if (e != hipSuccess) {
+            (void)hipGetLastError(); release_adapt(c);
+            c->set_error("evplp_adaptive_enable: cannot allocate %zu bytes: %s", sizeof(int4) * nt + sizeof(float4) * px, hipGetErrorString(e));
+            return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP;
+        }
+    }
+    c->adapt_tiles.assign(nt, make_int4(0, 0, 0, 0));
+    HIP_TRY(c, hipMemsetAsync(c->d_adapt_tiles, 0, sizeof(int4) * std::max<size_t>(nt, 1), c->stream));
+    return EVPLP_OK;
+}
+extern "C" int evplp_adaptive_enable(evplp_context *c, int32_t on) {
+    CTX_CHECK(c);
+    if (c->adapt_n > 0) {
+        c->set_error("evplp_adaptive_enable: %lld gather(s) have accumulated since the last clear: switch adaptivity before the first", (long long)c->adapt_n);
+        return EVPLP_ERR_INVALID;
+    }
+    if (on && !c->d_noise) { c->set_error("evplp_adaptive_enable: noise tracking is off (evplp_noise_track): retirement needs its estimate"); return EVPLP_ERR_INVALID; }
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    if (!on) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        release_adapt(c);
+        return EVPLP_OK;
+    }
+    return adapt_reset(c);
+}
+extern "C" int evplp_adaptive_retire(evplp_context *c, float scale, float ls, int32_t mask_emitter, double tau, int32_t min_batches) {
+    CTX_CHECK(c);
+    if (!c->d_adapt_tiles) { c->set_error("evplp_adaptive_retire: adaptivity is off (evplp_adaptive_enable)"); return EVPLP_ERR_INVALID; }
+    if (!c->d_noise) { c->set_error("evplp_adaptive_retire: noise tracking is off (evplp_noise_track)"); return EVPLP_ERR_INVALID; }
+    if (!(tau >= 0.0)) { c->set_error("evplp_adaptive_retire: tile_rel_mse must be >= 0, not %g", tau); return EVPLP_ERR_INVALID; }
+    if (min_batches < 2) { c->set_error("evplp_adaptive_retire: min_batches must be >= 2, not %d", min_batches); return EVPLP_ERR_INVALID; }
+    c->adapt_last = 0;
+    if (c->noise_b < min_batches || c->adapt_n < 1) return 0;
+    // (the composite the estimate measures; the pending splat's verdict first, as a fold waits for it)
+    int rc = evplp::resolve_to_device(c, scale, scale, ls, mask_emitter, 0, true, false);
+    if (rc) return rc;
+    const double K = (double)c->noise_k, B = (double)c->noise_b;
+    launch_adaptive_retire(c->st, evplp::noise_moments_of(c), K, B, (double)scale * (double)scale * K, (const float4 *)c->buf[EVPLP_BUF_LIGHT], ls, mask_emitter,
+                           c->d_rgb, tau, c->d_adapt_tiles, c->tiles_x, c->tiles_y, (int32_t)c->adapt_n, (const float4 *)c->buf[EVPLP_BUF_VPL_ACCUM], c->d_adapt_snap, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    const size_t nt = adapt_tile_count(c);
+    std::vector<int4> now(nt);
+    if (nt) HIP_TRY(c, hipMemcpyAsync(now.data(), c->d_adapt_tiles, sizeof(int4) * nt, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    int32_t fresh = 0;
+    for (size_t t = 0; t < nt; t++) fresh += (c->adapt_tiles[t].x == 0 && now[t].x != 0) ? 1 : 0;
+    c->adapt_tiles.swap(now);
+    c->adapt_last = fresh;
+    return fresh;
+}
+namespace evplp {
+void adaptive_tiles_into(const evplp_context *c, int32_t *out) {
+    const int itx = (c->st.W + 7) / 8;
+    for (int ty = 0; ty < c->tiles_y; ty++) {
+        const int y = c->st.global_row(ty * 8);
+        if (y < 0 || y >= c->st.H) continue;
+        for (int tx = 0; tx < c->tiles_x; tx++) {
+            const int32_t nt = c->adapt_tiles[(size_t)ty * c->tiles_x + tx].x;
+            out[(size_t)(y / 8) * itx + tx] = nt != 0 ? nt : (int32_t)c->adapt_n;
+        }
+    }
+}
+}
+extern "C" int evplp_adaptive_tiles(evplp_context *c, int32_t *out, int32_t capacity) {
+    CTX_CHECK(c);
+    if (!c->d_adapt_tiles) { c->set_error("evplp_adaptive_tiles: adaptivity is off (evplp_adaptive_enable)"); return EVPLP_ERR_INVALID; }
+    const int64_t n = (int64_t)((c->st.W + 7) / 8) * ((c->st.H + 7) / 8);
+    if (!out || capacity < n) { c->set_error("evplp_adaptive_tiles: the image has %lld tiles, the output holds %d", (long long)n, capacity); return EVPLP_ERR_INVALID; }
+    std::fill(out, out + n, 0);
+    evplp::adaptive_tiles_into(c, out);
+    return (int)n;
 }
 
 static void count_rows_in_image(evplp_context *c) {
@@ -1270,6 +1384,8 @@ extern "C" int evplp_clear_accumulators(evplp_context *c) {
     HIP_TRY(c, hipMemsetAsync(c->buf[EVPLP_BUF_VPL_ACCUM], 0, buffer_bytes(c, EVPLP_BUF_VPL_ACCUM), c->stream));
     HIP_TRY(c, hipMemsetAsync(c->buf[EVPLP_BUF_PHOTON_ACCUM], 0, buffer_bytes(c, EVPLP_BUF_PHOTON_ACCUM), c->stream));
     HIP_TRY(c, hipMemsetAsync(c->buf[EVPLP_BUF_LIGHT], 0, buffer_bytes(c, EVPLP_BUF_LIGHT), c->stream));
+    c->adapt_n = 0;
+    if (c->d_adapt_tiles) { int rc_ = adapt_reset(c); if (rc_) return rc_; }     // (every tile is active again)
     if (c->d_noise) return noise_restart(c);                                  // (noise tracking starts again from the empty sums)
     return EVPLP_OK;
 }

@@ -34,6 +34,8 @@ size_t noise_bytes(const evplp_context *c);                      // the NoisePla
 int noise_rows(evplp_context *c, const NoiseMoments &m, const float4 *light, double K, double B, float scale, float ls, int32_t mask_emitter);
 // the variance image of the moments m into d_rgb (stream order)
 int noise_variance_to_device(evplp_context *c, const NoiseMoments &m, double K, double B, float scale);
+// evplp_adaptive_tiles' map of this context's tiles written into out [ceil(H / 8)][ceil(W / 8)] (rows from the bottom); other tiles untouched
+void adaptive_tiles_into(const evplp_context *c, int32_t *out);
 }
 
 struct evplp_context {
@@ -138,6 +140,11 @@ struct evplp_context {
     char *d_noise = nullptr; size_t noise_stride = 0; uint8_t *d_noise_keep = nullptr;
     evplp::RowError *d_noise_rows = nullptr; std::vector<evplp::RowError> noise_rows;
     int64_t noise_k = 0, noise_b = 0;
+    // evplp_adaptive_*: adapt_n = N, the accumulating gather calls since the accumulators were last cleared (counted whether adaptivity is on
+    // or not); the tile records [tiles_x * tiles_y] (kernels.h AdaptTiles; null: adaptivity is off), their host copy (they change only in
+    // evplp_adaptive_retire and at a clear), the retired pixels' snapshot of VPL_ACCUM [W * local_rows]; adapt_last: tiles retired by the
+    // last evplp_adaptive_retire (the group's workers leave it here)
+    int64_t adapt_n = 0; int4 *d_adapt_tiles = nullptr; float4 *d_adapt_snap = nullptr; std::vector<int4> adapt_tiles; int32_t adapt_last = 0;
 
     char error[512] = "";
     void set_error(const char *fmt, ...);

@@ -64,13 +64,14 @@ struct Rccl {
 };
 
 enum Op { OP_QUIT = 0, OP_CLEAR, OP_SYNC, OP_PRIMARY, OP_TRACE, OP_GATHER, OP_SPLAT, OP_PATH_TRACE, OP_PRESENT, OP_LOAD_SCENE, OP_SET_PROXY, OP_ASSEMBLE, OP_REDUCE, OP_SET_REFERENCE, OP_FRAME_ERROR,
-          OP_NOISE_TRACK, OP_NOISE_FOLD, OP_NOISE_POOL, OP_NOISE_ROWS, OP_NOISE_VARIANCE };
+          OP_NOISE_TRACK, OP_NOISE_FOLD, OP_NOISE_POOL, OP_NOISE_ROWS, OP_NOISE_VARIANCE, OP_ADAPT_ENABLE, OP_ADAPT_RETIRE };
 // One posted call: plain data, copied into the ring (pointers must stay valid until the caller has drained: load_scene, set_proxy, resolve do)
 struct Cmd {
     int op = OP_QUIT;
     evplp_frame_params fp{};
     float f[4] = {}; int32_t i[4] = {}; uint32_t u[4] = {};
     const void *p0 = nullptr, *p1 = nullptr; void *out = nullptr;
+    double d = 0.0;
 };
 constexpr int kRing = 64;
 constexpr int kSpinBeforeSleep = 200000;     // ~1-2 ms of polling before an idle worker goes to sleep on its condition variable
@@ -129,6 +130,7 @@ struct evplp_group {
     bool iterations = false; int selected = 0; bool sums_fresh = false;
     bool have_reference = false;            // evplp_group_set_error_reference has given every rank an image (caller's thread)
     bool noise_on = false;                  // evplp_group_noise_track is on on every rank (caller's thread)
+    bool adapt_on = false;                  // evplp_group_adaptive_enable is on on every rank (caller's thread)
     // EVPLP_PARTITION_ITERATIONS, evplp_group_noise_*: rank 0's pooled moments (Q then S, [3][stride] fp64 each) and K / B summed over the
     // ranks (written by rank 0's worker); RCCL only: per rank [n][noise_bytes] every rank's NoisePlanes (all-gathered)
     double *d_noise_pool = nullptr; double pool_k = 0.0, pool_b = 0.0;
@@ -344,6 +346,9 @@ static void worker_run(Worker *w, const Cmd &cmd) {
             if (cmd.i[1]) rc = evplp::noise_rows(c, noise_pooled(g, c), g->d_sum[0] + 2 * g->plane_px, g->pool_k, g->pool_b, cmd.f[0], cmd.f[1], cmd.i[0]);
             else rc = evplp::noise_rows(c, evplp::noise_moments_of(c), (const float4 *)c->buf[EVPLP_BUF_LIGHT], (double)c->noise_k, (double)c->noise_b, cmd.f[0], cmd.f[1], cmd.i[0]);
             break;
+        case OP_ADAPT_ENABLE: rc = evplp_adaptive_enable(c, cmd.i[0]); break;
+        // (the count of tiles it retired stays in c->adapt_last)
+        case OP_ADAPT_RETIRE: rc = evplp_adaptive_retire(c, cmd.f[0], cmd.f[1], cmd.i[0], cmd.d, cmd.i[1]); if (rc > 0) rc = EVPLP_OK; break;
         case OP_NOISE_VARIANCE:
             if (cmd.i[1]) rc = evplp::noise_variance_to_device(c, noise_pooled(g, c), g->pool_k, g->pool_b, cmd.f[0]);
             else rc = evplp::noise_variance_to_device(c, evplp::noise_moments_of(c), (double)c->noise_k, (double)c->noise_b, cmd.f[0]);
@@ -681,6 +686,9 @@ extern "C" int evplp_group_gather(evplp_group *g, const evplp_frame_params *fp, 
     if (kind < 0 || kind > 2) { g->set_error("evplp_group_gather: kind must be 0 (VPL), 1 (VSL) or 2 (light-path windows)"); return EVPLP_ERR_INVALID; }
     if (!fp) { g->set_error("evplp_group_gather: null frame params"); return EVPLP_ERR_INVALID; }
     { int rc = check_frame_params(g, fp, "evplp_group_gather", false); if (rc < 0) return rc; }
+    if (g->adapt_on && (kind == 2 || fp->do_accumulate == 0)) {
+        g->set_error("evplp_group_gather: adaptivity is on (evplp_group_adaptive_enable): accumulating VPL and VSL gathers only"); return EVPLP_ERR_INVALID;
+    }
     Cmd c; c.op = OP_GATHER; c.fp = *fp; c.i[0] = kind;
     return post_pass(g, c);
 }
@@ -699,6 +707,7 @@ extern "C" int evplp_group_set_splat_proxy(evplp_group *g, const float *vertices
 extern "C" int evplp_group_path_trace(evplp_group *g, const float camera_pos[3], uint32_t rng_seed, uint32_t max_bounces, int32_t do_accumulate) {
     GRP_CHECK(g);
     if (!camera_pos) { g->set_error("evplp_group_path_trace: null camera position"); return EVPLP_ERR_INVALID; }
+    if (g->adapt_on) { g->set_error("evplp_group_path_trace: adaptivity is on (evplp_group_adaptive_enable): VPL and VSL gathers only"); return EVPLP_ERR_INVALID; }
     Cmd c; c.op = OP_PATH_TRACE; c.f[0] = camera_pos[0]; c.f[1] = camera_pos[1]; c.f[2] = camera_pos[2]; c.u[0] = rng_seed; c.u[1] = max_bounces; c.i[0] = do_accumulate;
     return post_pass(g, c);
 }
@@ -790,6 +799,11 @@ extern "C" int evplp_group_frame_error(evplp_group *g, float vs, float ps, float
 extern "C" int evplp_group_noise_track(evplp_group *g, int32_t on, const uint8_t *mask) {
     GRP_CHECK(g);
     if (!on && mask) { g->set_error("evplp_group_noise_track: a mask without tracking"); return EVPLP_ERR_INVALID; }
+    if (g->adapt_on) {
+        drain(g);
+        for (evplp_context *x : g->ctx)
+            if (x->adapt_n > 0) { g->set_error("evplp_group_noise_track: adaptivity is on and %lld gather(s) accumulated", (long long)x->adapt_n); return EVPLP_ERR_INVALID; }
+    }
     Cmd c; c.op = OP_NOISE_TRACK; c.i[0] = on; c.p0 = mask;
     const int rc = post_and_wait(g, c);             // (the caller's mask is read before the call returns)
     g->noise_on = rc >= 0 && on != 0;
@@ -863,4 +877,49 @@ extern "C" int evplp_group_noise_variance(evplp_group *g, float scale, float *ou
     post(g->workers[0], a);
     drain(g);
     return group_status(g);
+}
+
+// Adaptive gather (include/evplp.h evplp_adaptive_*).  Row strips only: every rank decides for its own tiles; the counts are summed and the
+// tile map is put together from the block owners.  The iteration partition would have to pool its ranks' decisions: refused.
+static int adapt_group_ready(evplp_group *g, const char *name) {
+    if (g->iterations) { g->set_error("%s: not under EVPLP_PARTITION_ITERATIONS (the ranks' decisions are not pooled)", name); return EVPLP_ERR_INVALID; }
+    drain(g);
+    return group_status(g);
+}
+extern "C" int evplp_group_adaptive_enable(evplp_group *g, int32_t on) {
+    GRP_CHECK(g);
+    int rc = adapt_group_ready(g, "evplp_group_adaptive_enable");
+    if (rc < 0) return rc;
+    for (evplp_context *c : g->ctx)
+        if (c->adapt_n > 0) { g->set_error("evplp_group_adaptive_enable: %lld gather(s) have accumulated since the last clear", (long long)c->adapt_n); return EVPLP_ERR_INVALID; }
+    if (on && !g->noise_on) { g->set_error("evplp_group_adaptive_enable: noise tracking is off (evplp_group_noise_track)"); return EVPLP_ERR_INVALID; }
+    Cmd c; c.op = OP_ADAPT_ENABLE; c.i[0] = on;
+    rc = post_and_wait(g, c);
+    g->adapt_on = rc >= 0 && on != 0;
+    return rc;
+}
+extern "C" int evplp_group_adaptive_retire(evplp_group *g, float scale, float ls, int32_t mask_emitter, double tau, int32_t min_batches) {
+    GRP_CHECK(g);
+    int rc = adapt_group_ready(g, "evplp_group_adaptive_retire");
+    if (rc < 0) return rc;
+    if (!g->ctx[0]->d_adapt_tiles) { g->set_error("evplp_group_adaptive_retire: adaptivity is off (evplp_group_adaptive_enable)"); return EVPLP_ERR_INVALID; }
+    if (!(tau >= 0.0)) { g->set_error("evplp_group_adaptive_retire: tile_rel_mse must be >= 0, not %g", tau); return EVPLP_ERR_INVALID; }
+    if (min_batches < 2) { g->set_error("evplp_group_adaptive_retire: min_batches must be >= 2, not %d", min_batches); return EVPLP_ERR_INVALID; }
+    Cmd c; c.op = OP_ADAPT_RETIRE; c.f[0] = scale; c.f[1] = ls; c.i[0] = mask_emitter; c.i[1] = min_batches; c.d = tau;
+    if ((rc = post_and_wait(g, c)) < 0) return rc;
+    int32_t n = 0;
+    for (evplp_context *x : g->ctx) n += x->adapt_last;
+    return n;
+}
+extern "C" int evplp_group_adaptive_tiles(evplp_group *g, int32_t *out, int32_t capacity) {
+    GRP_CHECK(g);
+    int rc = adapt_group_ready(g, "evplp_group_adaptive_tiles");
+    if (rc < 0) return rc;
+    const evplp_context *c0 = g->ctx[0];
+    if (!c0->d_adapt_tiles) { g->set_error("evplp_group_adaptive_tiles: adaptivity is off (evplp_group_adaptive_enable)"); return EVPLP_ERR_INVALID; }
+    const int64_t n = (int64_t)((c0->st.W + 7) / 8) * ((c0->st.H + 7) / 8);
+    if (!out || capacity < n) { g->set_error("evplp_group_adaptive_tiles: the image has %lld tiles, the output holds %d", (long long)n, capacity); return EVPLP_ERR_INVALID; }
+    std::fill(out, out + n, 0);
+    for (const evplp_context *c : g->ctx) evplp::adaptive_tiles_into(c, out);
+    return (int)n;
 }

@@ -310,6 +310,9 @@ private:
 class Noise {
 public:
     bool on = false;
+    // the "adaptive" block's tile counts (Adaptive below): written into every checkpoint when `adaptive` is set
+    bool adaptive = false; long long retired_tiles = 0, image_tiles = 0;
+    long long batch_iterations() const { return batch; }
     void parse(const Json &tech, const std::string &json_dir, const std::string &out_dir, int W, int H, int frame_mode) {
         if (!tech.has("noise")) return;
         const Json &c = tech.at("noise");
@@ -371,7 +374,7 @@ public:
     bool checkpoint(evplp_group *g, int i, WaitAndClock wait_and_clock, float scale, float ls, int32_t mask_emitter) {
         const double t = wait_and_clock();
         const auto t0 = std::chrono::steady_clock::now();
-        Point p; p.iteration = i; p.time_ms = t; p.batches = batches;
+        Point p; p.iteration = i; p.time_ms = t; p.batches = batches; p.retired = retired_tiles;
         check(g, evplp_group_noise_estimate(g, scale, ls, mask_emitter, p.e), "noise");
         overhead_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         points.push_back(p);
@@ -397,6 +400,7 @@ public:
             s += std::string(k ? ",\n" : "\n") + "        {\"iteration\": " + std::to_string(p.iteration) + ", \"timeMs\": " + num(p.time_ms) +
                  ", \"batches\": " + std::to_string(p.batches) + ", \"mse\": " + num(p.e[0]) + ", \"relMse\": " + num(p.e[1]);
             if (!mask.empty()) s += ", \"relMseMasked\": " + num(p.e[2]);
+            if (adaptive) s += ", \"retiredTiles\": " + std::to_string(p.retired) + ", \"activeTiles\": " + std::to_string(image_tiles - p.retired);
             s += "}";
         }
         s += "\n    ]\n}\n";
@@ -411,7 +415,7 @@ public:
     }
 
 private:
-    struct Point { int iteration = 0; double time_ms = 0.0; long long batches = 0; double e[3] = { 0.0, 0.0, 0.0 }; };
+    struct Point { int iteration = 0; double time_ms = 0.0; long long batches = 0; double e[3] = { 0.0, 0.0, 0.0 }; long long retired = 0; };
     static std::string num(double v) { if (!std::isfinite(v)) return "null"; char b[40]; std::snprintf(b, sizeof b, "%.17g", v); return b; }     // (every bit of the double)
     void fold(evplp_group *g, size_t r, long long k) {
         check(g, evplp_group_noise_fold(g, (int32_t)k), "noise fold");
@@ -424,6 +428,77 @@ private:
     double every_ms = 0.0, next_ms = 0.0, stop_rel_mse = -1.0, overhead_ms = 0.0;
     std::vector<long long> own, folded;      // per shard: iterations run, iterations folded
     std::vector<Point> points;
+};
+
+// Build-only key "adaptive" (photonfam, VPL and VSL gathers): tiles whose estimated noise has converged stop receiving gather work
+// (evplp_group_adaptive_*).  {"tileRelMse": 0.002, "everyIterations": 10, "minBatches": 4, "iterationsFilename": "iters.pfm"}
+// tileRelMse is required (>= 0); everyIterations (default: noise.batchIterations) is a multiple of noise.batchIterations: at every fold whose
+// iteration count it divides, the group retires -- with the loop's own 1 / i scale -- the tiles whose mean relative variance is <= tileRelMse
+// once the tracker has >= minBatches (default 2, >= 2) folds.  Needs the "noise" block, whose checkpoints then carry "retiredTiles" /
+// "activeTiles"; refused for lvcphotonfam and pt, under "partition": "iterations" and with frameMode "cleareveryframe".  iterationsFilename:
+// every pixel's n_t / N (1 where its tile never retired), rows top to bottom.  Everything is validated before the group exists.
+class Adaptive {
+public:
+    bool on = false;
+    void parse(const Json &tech, const std::string &out_dir, int frame_mode, bool lvc, bool iterations_partition, Noise &noise) {
+        if (!tech.has("adaptive")) return;
+        const Json &c = tech.at("adaptive");
+        if (!c.is_object()) throw JsonError("adaptive: expected an object");
+        if (lvc) throw JsonError("adaptive: not for lvcphotonfam (VPL and VSL gathers only)");
+        if (!noise.on) throw JsonError("adaptive: needs a \"noise\" block (retirement uses its estimate)");
+        if (frame_mode == 2) throw JsonError("adaptive: frameMode \"cleareveryframe\" keeps no running sum");
+        if (iterations_partition) throw JsonError("adaptive: not under \"partition\": \"iterations\" (the ranks' decisions are not pooled)");
+        if (!c.has("tileRelMse")) throw JsonError("adaptive.tileRelMse: missing required key");
+        tau = c.at("tileRelMse").as_number("adaptive.tileRelMse");
+        if (!(tau >= 0.0)) throw JsonError("adaptive.tileRelMse: must be >= 0");
+        every = noise.batch_iterations();
+        if (c.has("everyIterations")) {
+            every = c.at("everyIterations").as_int("adaptive.everyIterations");
+            if (every <= 0) throw JsonError("adaptive.everyIterations: must be > 0");
+            if (every % noise.batch_iterations() != 0) throw JsonError("adaptive.everyIterations: must be a multiple of noise.batchIterations");
+        }
+        if (c.has("minBatches")) {
+            const long long mb = c.at("minBatches").as_int("adaptive.minBatches");
+            if (mb < 2 || mb > INT32_MAX) throw JsonError("adaptive.minBatches: must be >= 2");
+            min_batches = (int32_t)mb;
+        }
+        if (c.has("iterationsFilename")) iterations_filename = output_path(out_dir, c.at("iterationsFilename").as_string("adaptive.iterationsFilename"));
+        noise.adaptive = true;
+        on = true;
+    }
+    // before the loop's first gather (after the clear and any rebalance: N = 0)
+    void start(evplp_group *g, int W, int H, Noise &noise) {
+        if (!on) return;
+        check(g, evplp_group_adaptive_enable(g, 1), "adaptive");
+        noise.image_tiles = (long long)((W + 7) / 8) * ((H + 7) / 8);
+    }
+    // after the fold of iteration i (folded_now): the retirement, when due
+    void after_fold(evplp_group *g, int i, bool folded_now, float scale, Noise &noise) {
+        if (!on || !folded_now || i % every != 0) return;
+        const int rc = evplp_group_adaptive_retire(g, scale, 1.0f, 0, tau, min_batches);
+        check(g, rc, "adaptive retire");
+        noise.retired_tiles += rc;
+    }
+    void finish(evplp_group *g, int n, int W, int H) {
+        if (!on || iterations_filename.empty()) return;
+        const int tx = (W + 7) / 8, ty = (H + 7) / 8;
+        std::vector<int32_t> tiles((size_t)tx * ty);
+        check(g, evplp_group_adaptive_tiles(g, tiles.data(), (int32_t)tiles.size()), "adaptive tiles");
+        std::vector<float> rgb((size_t)W * H * 3);
+        for (int y = 0; y < H; y++)                  // (y = 0 at the bottom, as the tile map's rows)
+            for (int x = 0; x < W; x++) {
+                const float v = n > 0 ? (float)((double)tiles[(size_t)(y / 8) * tx + x / 8] / (double)n) : 1.0f;
+                for (int ch = 0; ch < 3; ch++) rgb[((size_t)y * W + x) * 3 + ch] = v;
+            }
+        std::vector<float> top = flip_y(rgb, W, H);
+        if (save_image(iterations_filename.c_str(), W, H, top.data()) != EVPLP_OK) throw std::runtime_error("cannot write " + iterations_filename);
+    }
+
+private:
+    double tau = 0.0;
+    long long every = 1;
+    int32_t min_batches = 2;
+    std::string iterations_filename;
 };
 } // namespace
 
@@ -453,6 +528,7 @@ public:
         if (json.has("bvhBuilder")) bvh_builder = parse_bvh_builder(json.at("bvhBuilder").as_string("bvhBuilder"));
         conv.parse(json, out_dir, out_dir, res_x, res_y);
         noise.parse(json, out_dir, out_dir, res_x, res_y, frame_mode);
+        if (json.has("adaptive")) throw JsonError("adaptive: not for pt (VPL and VSL gathers only)");
 
         evplp_config cfg; std::memset(&cfg, 0, sizeof(cfg));
         cfg.abi_version = EVPLP_ABI_VERSION; cfg.device = device; cfg.res_x = res_x; cfg.res_y = res_y;
@@ -603,6 +679,7 @@ public:
             if (d.has("vslMaskGB")) cfg.vsl_mask_bytes = (uint64_t)(std::max(d.at("vslMaskGB").as_float("device.vslMaskGB"), 0.0f) * 1073741824.0);
         }
         run_opts = run_options(json);
+        adaptive.parse(json, out_dir, frame_mode, lvc, run_opts.shard_iterations, noise);                          // build-only key
         const int gpus = device_gpus(json);
         if (run_opts.shard_iterations && (frame_mode != 1 || gpus < 2)) {
             if (gpus >= 2) std::printf("note: device.partition \"iterations\" needs frameMode \"accumulate\"; running on row strips\n");
@@ -687,6 +764,7 @@ private:
         check(h, evplp_group_profile_passes(h, always_profile ? 1 : 0), "profile");
         bool profiling = always_profile;
         noise.start(h, S);
+        adaptive.start(h, W, H, noise);
         for (;;) {
             if (num_iterations == num_max_iteration) break;                                   // :938-941
             if (run_opts.shard_iterations) check(h, evplp_group_select_rank(h, num_iterations % S), "select rank");   // (this iteration's rank)
@@ -736,6 +814,7 @@ private:
             // (the fold of the rank this iteration ran on; the checkpoint, like conv's, measures the combinedFilename composite)
             if (noise.on) {
                 const bool folded = noise.after_iteration(h, (num_iterations - 1) % S);
+                adaptive.after_fold(h, num_iterations, folded, saved_param(num_iterations), noise);
                 if (noise.due(num_iterations, elapsed_ms(), folded) &&
                     noise.checkpoint(h, num_iterations, [&] { wait_for_next(); return (double)elapsed_ms(); }, saved_param(num_iterations), 1.0f, 0)) break;
             }
@@ -745,6 +824,7 @@ private:
         float time = elapsed_ms();
         conv.finish(h, num_iterations, elapsed_ms(), saved_param(num_iterations), saved_param(num_iterations), 1.0f, 0);
         noise.finish(h, num_iterations, elapsed_ms(), saved_param(num_iterations), 1.0f, 0, W, H);
+        adaptive.finish(h, num_iterations, W, H);
         check(h, evplp_group_profile_passes(h, 1), "profile");
         if (use_stat) {                                                                       // :1109-1119
             Json st = Json::object();
@@ -795,6 +875,7 @@ private:
     RunOptions run_opts;
     Convergence conv;
     Noise noise;
+    Adaptive adaptive;
     int bvh_builder = EVPLP_BVH_SAH;   // measured 9% faster frames than the Morton LBVH on the conference stand-in; "bvhBuilder": "lbvh" selects the LBVH
 };
 

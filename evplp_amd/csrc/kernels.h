@@ -90,6 +90,10 @@ struct GatherArgs {
     // its local block's counter -- what evplp_group_rebalance deals the blocks by
     unsigned long long *block_cost;
 };
+// evplp_adaptive_enable: the gather kernels' last argument (read by their ADAPT variants only; tiles = null: adaptivity is off) -- the tile
+// records of the context's planes [tiles_x * tiles_y] (AdaptTiles below), the retired pixels' snapshot of VPL_ACCUM [W * local_rows], and
+// N + 1 (N: the accumulating gather calls before this one).  (A separate argument: GatherArgs, and with it every default kernel, stays as it was.)
+struct AdaptArgs { const int4 *tiles; const float4 *snap; int32_t n1, pad; };
 // Entry cuts.  A frustum around ALL segments between one VPL and the pixels of a group of 2 x 2 tiles (the box of their end points
 // + four planes through the VPL) descends the tree breadth-first, dropping every subtree it cannot reach, until the surviving cut
 // would exceed kCutEntries; the group's (tile, VPL) packet walks then start from the cut -- two cut entries per synthetic node, in
@@ -108,6 +112,7 @@ struct CutArgs {
     int32_t group_row_first, pad;     // first row of groups of this launch (slot 0 of `cuts` belongs to its first group)
     const evplp_record *vpls; const uint32_t *nvpl; uint32_t vpl_stride;     // compacted usable VPLs; slots per group in `cuts`
     char *cuts;
+    const int4 *adapt_tiles;          // non-null: skip the groups whose tiles are all retired (evplp_adaptive_retire; tile records as GatherArgs)
 };
 void launch_gather_cuts(const CutArgs &a, hipStream_t s);
 void launch_tile_boxes(const StripDev &st, const float4 *g_pos, float4 *tile_box, int tiles_x, int tiles_y, hipStream_t s);
@@ -218,10 +223,10 @@ void launch_light_trace(const LightTraceArgs &a, hipStream_t s);
 void launch_compact_vpl(const evplp_record *records, uint32_t nrec, evplp_record *out, uint32_t *src_index,
                         uint32_t *count_out, hipStream_t s);
 // VPL / VSL gather = the items, then one reduce
-void launch_gather_vpl_items(const GatherArgs &a, hipStream_t s);
-void launch_gather_vsl(const GatherArgs &a, hipStream_t s);        // walks, then estimators, of the launch's group range
+void launch_gather_vpl_items(const GatherArgs &a, hipStream_t s, const AdaptArgs &ad = AdaptArgs{});
+void launch_gather_vsl(const GatherArgs &a, hipStream_t s, const AdaptArgs &ad = AdaptArgs{});        // walks, then estimators, of the launch's group range
 int gather_launch_tiles(const GatherArgs &a);                      // tiles a gather launch enumerates (whole blocks)
-void launch_gather_reduce(const GatherArgs &a, int stencil_test, hipStream_t s);
+void launch_gather_reduce(const GatherArgs &a, int stencil_test, hipStream_t s, const AdaptArgs &ad = AdaptArgs{});
 void launch_gather_lvc(const GatherArgs &a, const evplp_record *records, hipStream_t s);
 void launch_path_trace(const PathTraceArgs &a, hipStream_t s);
 // binning (tile depth ranges, compact photons + bin fill, summary); then the per-tile accumulation
@@ -255,5 +260,19 @@ void launch_noise_rows(const StripDev &st, const NoiseMoments &m, double K, doub
                        const float *rgb, const uint8_t *keep, RowError *rows, hipStream_t s);
 // the variance of every plane pixel, 3 floats each (resolve's layout)
 void launch_noise_variance(const NoiseMoments &m, double K, double B, double s2K, size_t n, float *out_rgb, hipStream_t s);
+// evplp_adaptive_*: one record per 8 x 8 tile of a context's planes, tile (tx, ty) of local rows 8 ty .. 8 ty + 7 at ty * tiles_x + tx:
+// int4 { n_t (0: active; the N at retirement), K_t, B_t (the noise tracker's K and B at retirement), 0 }.  tiles = null: adaptivity is off
+// and the noise kernels take their default paths.  n = N, scale: the composite's, both for the retired pixels' frozen variance.
+struct AdaptTiles { const int4 *tiles; int32_t tiles_x, pad; double n, scale; };
+// the noise kernels' variants with retired tiles (at.tiles != null): the fold leaves a retired pixel's Q and c_prev as they are; the
+// figures and the variance image take a retired pixel's variance as noise_var(Q, S, K_t, B_t - 1, (scale N / n_t)^2 K_t)
+void launch_noise_fold_adaptive(const NoisePlanes &m, const float4 *vpl, const float4 *pm, const StripDev &st, const AdaptTiles &at, int32_t k, hipStream_t s);
+void launch_noise_rows_adaptive(const StripDev &st, const NoiseMoments &m, double K, double B, double s2K, const float4 *light, float ls, int mask_emitter,
+                                const float *rgb, const uint8_t *keep, RowError *rows, const AdaptTiles &at, hipStream_t s);
+void launch_noise_variance_adaptive(const StripDev &st, const NoiseMoments &m, double K, double B, double s2K, float *out_rgb, const AdaptTiles &at, hipStream_t s);
+// evplp_adaptive_retire: every active tile whose mean relative variance over its in-image pixels (noise_rows_kernel's rel, fp64, summed in a
+// fixed tree over the tile's 64 lanes) is <= tau gets the record { n, K, B, 0 } and the snapshot snap = vpl of its pixels
+void launch_adaptive_retire(const StripDev &st, const NoiseMoments &m, double K, double B, double s2K, const float4 *light, float ls, int mask_emitter,
+                            const float *rgb, double tau, int4 *tiles, int32_t tiles_x, int32_t tiles_y, int32_t n, const float4 *vpl, float4 *snap, hipStream_t s);
 
 } // namespace evplp

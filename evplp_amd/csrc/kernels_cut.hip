@@ -145,6 +145,9 @@ EV_DEV void cut_descend_and_store(const BvhNode *nodes, const CutFrustum &F, cha
 // VPL for one group: 64 unrelated apexes per wave, half of them done after a few steps -- 39.5 % of the lanes busy, 7.6 ms; the kernel
 // is bound by vector-instruction issue, profiles/r04a_bench_ir_pmc_first_cuts.txt).  Blocks are ordered VPL-fastest: the waves of a
 // block of groups run back to back.
+// ADAPT (a.adapt_tiles set, evplp_adaptive_retire): a group whose tiles are all retired gets no slots -- no item of those tiles walks any
+// more; a group with an active tile is cut as before
+template <bool ADAPT = false>
 __global__ __launch_bounds__(64) void gather_cut_kernel(CutArgs a) {
     __shared__ int32_t s_ref[kCutRing][64];      // child reference of a cut entry (inner node index >= 0, leaf < 0)
     __shared__ uint32_t s_src[kCutRing][64];     // where its box is: parent node index << 1 | child
@@ -154,7 +157,16 @@ __global__ __launch_bounds__(64) void gather_cut_kernel(CutArgs a) {
     if (i >= nvpl) return;                                               // (wave-uniform)
     const int gblocks_x = (a.groups_x + 7) >> 3;
     const int gx = (int)(gb % (uint32_t)gblocks_x) * 8 + (lane & 7), gyl = (int)(gb / (uint32_t)gblocks_x) * 8 + (lane >> 3);
-    const bool live = gx < a.groups_x && gyl < a.groups_y;
+    bool live = gx < a.groups_x && gyl < a.groups_y;
+    if constexpr (ADAPT) {
+        if (live) {
+            const int gw = 1 << a.gw_log2, gh = 1 << a.gh_log2, gyi = a.group_row_first + gyl;
+            bool retired = true;
+            for (int ty = gyi * gh; ty < min((gyi + 1) * gh, a.tiles_y); ty++)
+                for (int tx = gx * gw; tx < min((gx + 1) * gw, a.tiles_x); tx++) retired = retired && a.adapt_tiles[ty * a.tiles_x + tx].x != 0;
+            live = !retired;
+        }
+    }
     if (__builtin_amdgcn_ballot_w64(live) == 0ull) return;
     const uint32_t g = (uint32_t)(min(gyl, a.groups_y - 1) * a.groups_x + min(gx, a.groups_x - 1));
     const int gy = a.group_row_first + min(gyl, a.groups_y - 1);
@@ -264,7 +276,8 @@ void launch_primary_cuts(const PrimaryCutArgs &a, hipStream_t s) {
 void launch_gather_cuts(const CutArgs &a, hipStream_t s) {
     const uint32_t gblocks = (uint32_t)(((a.groups_x + 7) >> 3) * ((a.groups_y + 7) >> 3));
     if (a.vpl_stride == 0u || gblocks == 0u) return;
-    hipLaunchKernelGGL(gather_cut_kernel, dim3(gblocks * a.vpl_stride), dim3(64), 0, s, a);
+    if (a.adapt_tiles) hipLaunchKernelGGL(gather_cut_kernel<true>, dim3(gblocks * a.vpl_stride), dim3(64), 0, s, a);
+    else hipLaunchKernelGGL(gather_cut_kernel<false>, dim3(gblocks * a.vpl_stride), dim3(64), 0, s, a);
 }
 
 } // namespace evplp

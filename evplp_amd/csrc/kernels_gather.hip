@@ -190,6 +190,15 @@ EV_DEV uint32_t item_cut_group(const GatherArgs &a, const Item &t) {
     const int tx = __builtin_amdgcn_readfirstlane(t.x) >> 3, ty = __builtin_amdgcn_readfirstlane(t.ly) >> 3;
     return (uint32_t)(((ty >> a.cut_gh_log2) - a.cut_group_row_first) * a.cut_groups_x + (tx >> a.cut_gw_log2));
 }
+// ADAPT variants (evplp_adaptive_retire): has the item's tile been retired?  One wave-uniform scalar read of its record's n_t (kernels.h
+// AdaptTiles), right after the has_tile test: a retired tile's items end there, and gather_reduce_kernel<true> writes its pixels
+EV_DEV bool tile_retired(const GatherArgs &a, const AdaptArgs &ad, const Item &t) {
+    const int tx = __builtin_amdgcn_readfirstlane(t.x) >> 3, ty = __builtin_amdgcn_readfirstlane(t.ly) >> 3;
+    const uint32_t off = (uint32_t)(ty * ((a.st.W + 7) >> 3) + tx) * (uint32_t)sizeof(int4);
+    int nt;
+    asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(nt) : "s"(ad.tiles), "s"(off) : "memory");
+    return nt != 0;
+}
 
 #ifndef EVPLP_CUT_RING
 #define EVPLP_CUT_RING 3          // LDS buffers of the cut-slot ring of a gather wave (512 B each): EVPLP_CUT_RING - 1 slots in flight ahead of the walk
@@ -241,11 +250,11 @@ EV_DEV void item_cost_add(const GatherArgs &a, int ty, unsigned long long t0, in
     // (kernels of different residency add up as launch time does: ticks x 8 / waves per SIMD)
     if (threadIdx.x == 0) atomicAdd(&a.block_cost[(ty * 8) / a.st.strip_rows], dt * 8ull / (unsigned long long)waves);
 }
-template <bool CUT, bool COST = false>
+template <bool CUT, bool COST = false, bool ADAPT = false>
 #if EVPLP_WALK_ASM && !EVPLP_TRAVERSAL_STATS
 __attribute__((amdgpu_num_vgpr(52)))      // v[52:63] belong to the hand-written node visit (device_common.hpp)
 #endif
-__global__ __launch_bounds__(64, EVPLP_GATHER_WAVES) void gather_vpl_kernel(GatherArgs a) {
+__global__ __launch_bounds__(64, EVPLP_GATHER_WAVES) void gather_vpl_kernel(GatherArgs a, AdaptArgs ad) {
     unsigned long long t_cost = 0ull;
     if constexpr (COST) t_cost = __builtin_amdgcn_s_memrealtime();
 #if EVPLP_GATHER_TIMES
@@ -259,6 +268,7 @@ __global__ __launch_bounds__(64, EVPLP_GATHER_WAVES) void gather_vpl_kernel(Gath
     const int lane = threadIdx.x;
     const Item t = item_setup(a, lane, (int)blockIdx.x);
     if (!t.has_tile) return;   // padding of the block grid
+    if constexpr (ADAPT) { if (tile_retired(a, ad, t)) return; }
     const uint32_t p = t.p;
 
     Pixel px;
@@ -424,18 +434,35 @@ __global__ __launch_bounds__(64, EVPLP_GATHER_WAVES) void gather_vpl_kernel(Gath
 }
 
 // out = (balanced-tree sum of the per-group partials) / numVplLightPaths + doAccumulate * out   (lighttracing.cu:378);
-// the shadow-ray / unoccluded-pair counts of the items are summed here too (64 counter shards, summed by the host)
-__global__ __launch_bounds__(256) void gather_reduce_kernel(GatherArgs a, int stencil_test) {
+// the shadow-ray / unoccluded-pair counts of the items are summed here too (64 counter shards, summed by the host).
+// The last step of a pixel: (the tree sum r) / numVplLightPaths + doAccumulate * old -- one function for both variants of the kernel below
+// (this file is built with contraction on: an active pixel of the ADAPT variant is rounded exactly as in the default one)
+EV_DEV float4 reduce_out(V3 r, float inv, float acc, float4 old) {
+    return make_float4(r.x / inv + acc * old.x, r.y / inv + acc * old.y, r.z / inv + acc * old.z, 0.0f + acc * old.w);
+}
+// ADAPT (evplp_adaptive_retire): every in-image pixel of a retired tile -- whatever the stencil says -- becomes its snapshot R extrapolated
+// to N + 1 iterations, (float)(R * ((N + 1) / n_t)) per channel in fp64, and adds nothing to the counters; active pixels as above
+template <bool ADAPT = false>
+__global__ __launch_bounds__(256) void gather_reduce_kernel(GatherArgs a, int stencil_test, AdaptArgs ad) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     const size_t n = (size_t)a.st.W * a.st.local_rows;
     unsigned long long rays = 0ull, shaded = 0ull;
     bool writes = i < n;
+    int nt = 0;
     if (writes) {
         const int ly = (int)(i / a.st.W);
         if (a.st.global_row(ly) >= a.st.H) writes = false;
-        else if (stencil_test && a.g_pos[i].w == 0.0f) writes = false;      // splatColor returns before writing (:354)
+        else {
+            if constexpr (ADAPT) nt = ad.tiles[(ly >> 3) * ((a.st.W + 7) >> 3) + ((int)(i - (size_t)ly * a.st.W) >> 3)].x;
+            if (nt == 0 && stencil_test && a.g_pos[i].w == 0.0f) writes = false;      // splatColor returns before writing (:354)
+        }
     }
-    if (writes) {
+    if (ADAPT && writes && nt != 0) {
+        const float4 R = ad.snap[i];
+        const double f = __ddiv_rn((double)ad.n1, (double)nt);
+        a.out[i] = make_float4(__double2float_rn(__dmul_rn((double)R.x, f)), __double2float_rn(__dmul_rn((double)R.y, f)),
+                               __double2float_rn(__dmul_rn((double)R.z, f)), __double2float_rn(__dmul_rn((double)R.w, f)));
+    } else if (writes) {
         const int groups = kVplSplit / a.splits_per_wave;
         V3 r = v3(0.f, 0.f, 0.f), lv0 = r, lv1 = r, lv2 = r, lv3 = r, lv4 = r, lv5 = r, lv6 = r;
         for (int g = 0; g < groups; g++) {
@@ -448,9 +475,7 @@ __global__ __launch_bounds__(256) void gather_reduce_kernel(GatherArgs a, int st
             EV_MERGE(0, EV_MERGE(1, EV_MERGE(2, EV_MERGE(3, EV_MERGE(4, EV_MERGE(5, EV_MERGE(6, ;)))))))
 #undef EV_MERGE
         }
-        const float inv = (float)a.fp.num_vpl_light_paths, acc = (float)a.fp.do_accumulate;
-        float4 old = a.out[i];
-        a.out[i] = make_float4(r.x / inv + acc * old.x, r.y / inv + acc * old.y, r.z / inv + acc * old.z, 0.0f + acc * old.w);
+        a.out[i] = reduce_out(r, (float)a.fp.num_vpl_light_paths, (float)a.fp.do_accumulate, a.out[i]);
     }
     __shared__ unsigned long long s_sum[2];
     if (threadIdx.x < 2) s_sum[threadIdx.x] = 0ull;
@@ -751,17 +776,18 @@ EV_DEV size_t vsl_mask_base(const GatherArgs &a, int tile_in_launch_order, int g
 }
 EV_DEV int launch_tile(const GatherArgs &a) { return item_index<true>(a, (int)blockIdx.x).tile_l; }      // the tile's index in launch order
 
-template <bool CUT, bool COST = false>
+template <bool CUT, bool COST = false, bool ADAPT = false>
 #if EVPLP_WALK_ASM && !EVPLP_TRAVERSAL_STATS
 __attribute__((amdgpu_num_vgpr(52)))      // v[52:63] belong to the hand-written node visit (device_common.hpp)
 #endif
-__global__ __launch_bounds__(64, EVPLP_GATHER_WAVES) void gather_vsl_walk_kernel(GatherArgs a) {
+__global__ __launch_bounds__(64, EVPLP_GATHER_WAVES) void gather_vsl_walk_kernel(GatherArgs a, AdaptArgs ad) {
     unsigned long long t_cost = 0ull;
     if constexpr (COST) t_cost = __builtin_amdgcn_s_memrealtime();
     __shared__ unsigned long long s_lit[kVslChunk];
     const int lane = threadIdx.x;
     const Item t = item_setup<true>(a, lane, (int)blockIdx.x);
     if (!t.has_tile) return;
+    if constexpr (ADAPT) { if (tile_retired(a, ad, t)) return; }
     const bool valid = t.in_image;                      // no stencil test in splatSplotch (:694-695)
     const uint32_t nvpl = *a.nvpl;
     const int k = a.splits_per_wave;
@@ -842,8 +868,8 @@ __global__ __launch_bounds__(64, EVPLP_GATHER_WAVES) void gather_vsl_walk_kernel
     if constexpr (COST) item_cost_add(a, item_index<true>(a, (int)blockIdx.x).ty, t_cost, EVPLP_GATHER_WAVES);
 }
 
-template <bool COST = false>
-__global__ __launch_bounds__(64, EVPLP_VSL_WAVES) void gather_vsl_shade_kernel(GatherArgs a) {
+template <bool COST = false, bool ADAPT = false>
+__global__ __launch_bounds__(64, EVPLP_VSL_WAVES) void gather_vsl_shade_kernel(GatherArgs a, AdaptArgs ad) {
     unsigned long long t_cost = 0ull;
     if constexpr (COST) t_cost = __builtin_amdgcn_s_memrealtime();
     extern __shared__ float s_lvl[];                   // one [192] block per level of the k-split fold
@@ -852,6 +878,7 @@ __global__ __launch_bounds__(64, EVPLP_VSL_WAVES) void gather_vsl_shade_kernel(G
     const int W = a.st.W;
     const Item t = item_setup<true>(a, lane, (int)blockIdx.x);
     if (!t.has_tile) return;
+    if constexpr (ADAPT) { if (tile_retired(a, ad, t)) return; }
     const bool valid = t.in_image;
     const uint32_t pixel_id = (uint32_t)t.gy * (uint32_t)W + (uint32_t)t.x;  // launchIndex.y * dim.x + launchIndex.x (:711)
     const uint64_t pixel_key = vsl_key(((uint64_t)a.fp.rng_seed << 32) | (uint64_t)pixel_id);
@@ -983,33 +1010,46 @@ static dim3 gather_grid(const GatherArgs &a) {
     const int groups = a.group_count > 0 ? a.group_count : kVplSplit / a.splits_per_wave;
     return dim3((unsigned)(gather_launch_tiles(a) * groups));     // tile = tile_j * 8 + xcd
 }
-void launch_gather_reduce(const GatherArgs &a, int stencil_test, hipStream_t s) {
+void launch_gather_reduce(const GatherArgs &a, int stencil_test, hipStream_t s, const AdaptArgs &ad) {
     size_t n = (size_t)a.st.W * a.st.local_rows;
-    hipLaunchKernelGGL(gather_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, stencil_test);
+    if (ad.tiles) hipLaunchKernelGGL(gather_reduce_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, stencil_test, ad);
+    else hipLaunchKernelGGL(gather_reduce_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, stencil_test, ad);
 }
 static size_t fold_lds_bytes(const GatherArgs &a, int extra_floats) {
     int levels = 1; while ((1 << (levels - 1)) < a.splits_per_wave) levels++;       // log2 k + 1
     return (size_t)(levels * 192 + extra_floats) * sizeof(float);
 }
-// (a.block_cost set: the calibration variants of the same kernels -- same results, every item also clocks itself)
-void launch_gather_vpl_items(const GatherArgs &a, hipStream_t s) {
+// (a.block_cost set: the calibration variants of the same kernels -- same results, every item also clocks itself; they gather every tile,
+// retired or not: gather_reduce_kernel<true> ignores what they leave for retired pixels.  ad.tiles set otherwise: the ADAPT variants)
+void launch_gather_vpl_items(const GatherArgs &a, hipStream_t s, const AdaptArgs &ad) {
     const size_t lds = fold_lds_bytes(a, kGatherPxFloats);
-    if (a.block_cost) {
-        if (a.cuts) hipLaunchKernelGGL((gather_vpl_kernel<true, true>), gather_grid(a), dim3(64), lds, s, a);
-        else hipLaunchKernelGGL((gather_vpl_kernel<false, true>), gather_grid(a), dim3(64), lds, s, a);
-    } else if (a.cuts) hipLaunchKernelGGL((gather_vpl_kernel<true>), gather_grid(a), dim3(64), lds, s, a);
-    else hipLaunchKernelGGL((gather_vpl_kernel<false>), gather_grid(a), dim3(64), lds, s, a);
-}
-void launch_gather_vsl(const GatherArgs &a, hipStream_t s) {
-    if (a.block_cost) {
-        if (a.cuts) hipLaunchKernelGGL((gather_vsl_walk_kernel<true, true>), gather_grid(a), dim3(64), 0, s, a);
-        else hipLaunchKernelGGL((gather_vsl_walk_kernel<false, true>), gather_grid(a), dim3(64), 0, s, a);
-        hipLaunchKernelGGL((gather_vsl_shade_kernel<true>), gather_grid(a), dim3(64), fold_lds_bytes(a, 0), s, a);
+    if (ad.tiles && !a.block_cost) {
+        if (a.cuts) hipLaunchKernelGGL((gather_vpl_kernel<true, false, true>), gather_grid(a), dim3(64), lds, s, a, ad);
+        else hipLaunchKernelGGL((gather_vpl_kernel<false, false, true>), gather_grid(a), dim3(64), lds, s, a, ad);
         return;
     }
-    if (a.cuts) hipLaunchKernelGGL((gather_vsl_walk_kernel<true>), gather_grid(a), dim3(64), 0, s, a);
-    else hipLaunchKernelGGL((gather_vsl_walk_kernel<false>), gather_grid(a), dim3(64), 0, s, a);
-    hipLaunchKernelGGL((gather_vsl_shade_kernel<false>), gather_grid(a), dim3(64), fold_lds_bytes(a, 0), s, a);
+    if (a.block_cost) {
+        if (a.cuts) hipLaunchKernelGGL((gather_vpl_kernel<true, true>), gather_grid(a), dim3(64), lds, s, a, ad);
+        else hipLaunchKernelGGL((gather_vpl_kernel<false, true>), gather_grid(a), dim3(64), lds, s, a, ad);
+    } else if (a.cuts) hipLaunchKernelGGL((gather_vpl_kernel<true>), gather_grid(a), dim3(64), lds, s, a, ad);
+    else hipLaunchKernelGGL((gather_vpl_kernel<false>), gather_grid(a), dim3(64), lds, s, a, ad);
+}
+void launch_gather_vsl(const GatherArgs &a, hipStream_t s, const AdaptArgs &ad) {
+    if (a.block_cost) {
+        if (a.cuts) hipLaunchKernelGGL((gather_vsl_walk_kernel<true, true>), gather_grid(a), dim3(64), 0, s, a, ad);
+        else hipLaunchKernelGGL((gather_vsl_walk_kernel<false, true>), gather_grid(a), dim3(64), 0, s, a, ad);
+        hipLaunchKernelGGL((gather_vsl_shade_kernel<true>), gather_grid(a), dim3(64), fold_lds_bytes(a, 0), s, a, ad);
+        return;
+    }
+    if (ad.tiles) {
+        if (a.cuts) hipLaunchKernelGGL((gather_vsl_walk_kernel<true, false, true>), gather_grid(a), dim3(64), 0, s, a, ad);
+        else hipLaunchKernelGGL((gather_vsl_walk_kernel<false, false, true>), gather_grid(a), dim3(64), 0, s, a, ad);
+        hipLaunchKernelGGL((gather_vsl_shade_kernel<false, true>), gather_grid(a), dim3(64), fold_lds_bytes(a, 0), s, a, ad);
+        return;
+    }
+    if (a.cuts) hipLaunchKernelGGL((gather_vsl_walk_kernel<true>), gather_grid(a), dim3(64), 0, s, a, ad);
+    else hipLaunchKernelGGL((gather_vsl_walk_kernel<false>), gather_grid(a), dim3(64), 0, s, a, ad);
+    hipLaunchKernelGGL((gather_vsl_shade_kernel<false>), gather_grid(a), dim3(64), fold_lds_bytes(a, 0), s, a, ad);
 }
 
 } // namespace evplp

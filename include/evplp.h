@@ -120,6 +120,7 @@ typedef struct evplp_config {
      *   scene (331 k triangles)         0.1 GB everywhere (nodes, leaf blocks in two layouts, attributes; textures on top)
      *   error reference (if set)        12 B + 1 B (mask) per pixel of the WHOLE image on every context (evplp_set_error_reference)
      *   noise tracking (if on)          56 B per pixel of the context's planes (+ 1 B per image pixel with a mask; evplp_noise_track)
+     *   adaptive gather (if enabled)    16 B per pixel of the context's planes (snapshot) + 16 B per 8 x 8 tile (evplp_adaptive_enable)
      * A caller that has the device to itself sets cut_scratch_bytes = 72 GB, vsl_mask_bytes = 14 GB for config #5 (one band, one launch). */
     uint64_t cut_scratch_bytes;
     uint64_t vsl_mask_bytes;
@@ -337,6 +338,36 @@ int evplp_noise_estimate(evplp_context *ctx, float scale, float light_scale, int
  * Tracking off or fewer than two folds: EVPLP_ERR_INVALID. */
 int evplp_noise_variance(evplp_context *ctx, float scale, float *out_rgb);
 
+/* Adaptive gather: tiles whose estimated noise has converged stop receiving gather work (off by default; a run without it is unchanged).
+ * Tile: an 8 x 8 pixel tile of the context's local rows (strip_rows is a multiple of 8: a tile never straddles two row blocks); one decision
+ * per tile, independent of the partition.  N: the context's accumulating gather calls (evplp_gather_vpl / _vsl with do_accumulate != 0)
+ * since the accumulators were last cleared; evplp_clear_accumulators and evplp_set_blocks (so also a group's rebalance) reset N to 0 and make
+ * every tile active again.
+ * evplp_adaptive_retire retires an active tile when the noise tracker has closed B >= min_batches (>= 2) batches and the mean over the tile's
+ * in-image pixels of the per-pixel relative variance -- rel = num / den exactly as evplp_noise_estimate forms it, with the same scale,
+ * light_scale, mask_emitter and composite; the mean in fp64, summed in a fixed order (a shuffle-down tree over the tile's 64 lanes, lane =
+ * (y % 8) * 8 + x % 8, 0 outside the image; divided by the count of in-image pixels) -- is <= tile_rel_mse.  Retirement is one-way until
+ * the next clear: the tile records n_t = N and the tracker's K_t = K and B_t = B, and snapshots R = VPL_ACCUM of its pixels.  It settles
+ * the pending photon splat first, as a fold does.  Returns the number of tiles this call retired (>= 0).
+ * Later accumulating gathers skip a retired tile's items; the reduce writes VPL_ACCUM = (float)((double)R * ((double)(N + 1) / (double)n_t))
+ * per channel (each operation rounded to nearest) for every in-image pixel of the tile, whatever that iteration's stencil says, and the
+ * shadow-ray and pair counters get nothing from it: the accumulator always reads as a sum over N iterations (resolve, present, frame_error,
+ * the strip exchange need nothing new).  Active tiles stay bit-identical to a run without adaptivity (VPL and photon accumulators, G-buffer,
+ * light plane): a pixel's gather depends only on the pixel and the iteration's VPLs / VSLs.
+ * Noise of a retired pixel: the fold leaves its Q and c_prev alone; evplp_noise_estimate and evplp_noise_variance take its variance as
+ * noise_var(Q, S, K_t, B_t - 1, s2K_t) with s2K_t = ((scale * N) / n_t)^2 * K_t (fp64) -- the figure at retirement rescaled to today's
+ * composite: at scale = 1 / N it equals the figure at retirement and it never shrinks.  With photons a retired pixel's photon part keeps
+ * improving, so its figure is an upper bound.
+ * Refused with EVPLP_ERR_INVALID (the context stays usable): evplp_adaptive_enable with N > 0, or on = 1 without noise tracking; while it
+ * is on: evplp_gather_lvc, evplp_path_trace, a gather with do_accumulate == 0, evplp_noise_track (off, or a restart) with N > 0.
+ * A calibration frame (evplp_calibrate_blocks) gathers every tile; the reduce still writes retired pixels from their snapshots. */
+int evplp_adaptive_enable(evplp_context *ctx, int32_t on);
+int evplp_adaptive_retire(evplp_context *ctx, float scale, float light_scale, int32_t mask_emitter,
+                          double tile_rel_mse, int32_t min_batches);          /* >= 0: tiles retired by this call */
+/* Per image tile, ceil(W / 8) x ceil(H / 8) in the planes' row order (tile row 0 = image rows 0..7 from the bottom): n_t for a retired tile,
+ * N for an active one, 0 for tiles another rank owns.  Returns the number of tiles; adaptivity off or capacity too small: EVPLP_ERR_INVALID. */
+int evplp_adaptive_tiles(evplp_context *ctx, int32_t *iterations_per_image_tile, int32_t capacity);
+
 /* Row-strip contexts (strip_count > 1): which blocks of strip_rows image rows this context owns.  By default block b belongs to rank
  * b % strip_count.  evplp_set_blocks replaces that by a table: local block l holds image block image_blocks[l], l < count <= the context's
  * capacity (evplp_config.strip_capacity_rows / strip_rows); image_blocks = NULL restores the default.  Every kernel, statistic and buffer
@@ -524,6 +555,13 @@ int evplp_group_noise_track(evplp_group *g, int32_t on, const uint8_t *mask_rgb8
 int evplp_group_noise_fold(evplp_group *g, int32_t iterations);
 int evplp_group_noise_estimate(evplp_group *g, float scale, float light_scale, int32_t mask_emitter, double out[3]);
 int evplp_group_noise_variance(evplp_group *g, float scale, float *out_rgb);
+/* evplp_adaptive_* for a group.  EVPLP_PARTITION_STRIPS: every rank decides for its own tiles, the retire call returns the sum of the ranks'
+ * counts, and the tile map is assembled from the block owners (the whole image).  EVPLP_PARTITION_ITERATIONS: every call is refused --
+ * pooling the ranks' decisions is not supported.  Refusals come on the caller's thread and leave the group usable. */
+int evplp_group_adaptive_enable(evplp_group *g, int32_t on);
+int evplp_group_adaptive_retire(evplp_group *g, float scale, float light_scale, int32_t mask_emitter,
+                                double tile_rel_mse, int32_t min_batches);
+int evplp_group_adaptive_tiles(evplp_group *g, int32_t *iterations_per_image_tile, int32_t capacity);
 
 /* ---- host side of the reference interface (no GPU needed for these) ---- */
 /* The anti-aliasing jitters of the first `count` iterations of a technique run with this rngOffset: NDC translations (x, y) =

@@ -1,0 +1,141 @@
+"""Does retiring converged tiles pay (evplp_group_adaptive_*)?  One JSON line at the end of stdout.
+
+Config #2 of BASELINE on the furnished stand-in (evplp_synth_scene, style "hard", 331 k triangles), one rank: 1024 x 1024, Instant
+Radiosity (1024 VPL paths, 3 bounces, misMode one, no photon splat).  Every run folds the noise tracker after each iteration.
+  * reference: a long plain run (--ref-iters) in the same process; its composite is the reference of evplp_group_frame_error.
+  * curves: a plain run and adaptive runs at each --taus value (tileRelMse), --iters iterations each, retiring every --every iterations with
+    the loop's 1 / i scale after --min-batches folds.  Every --every iterations: the wall time of the run so far (host clock around
+    synchronised iterations; the measurements themselves are not counted), relMSE against the reference, tiles retired, and the gather pass's
+    own time (pass statistics) of that iteration.
+  * where noise sits relative to cost: per run, the fraction of tiles retired against the fraction of gather time saved at the end -- a
+    saving smaller than the retired fraction means the cheap tiles converged first.
+  * floor: the gather call with every tile retired (tileRelMse huge), its pass time and its host wall time, against a full gather's.
+
+usage: python tools/adaptive_convergence.py [--iters N] [--ref-iters N] [--taus 0.002,0.0005] [--every N] [--min-batches N]"""
+import argparse
+import json
+import math
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import torch  # noqa: E402,F401  (first, so libevplp_hip.so binds to the HIP runtime torch loaded)
+import numpy as np  # noqa: E402
+import evplp_amd as ev  # noqa: E402
+import scenes  # noqa: E402
+
+W, H, NL, NV, P = 1024, 1024, 1024, 1024, 4
+
+
+class Runner:
+    def __init__(self, g, sd, total):
+        self.g, self.sd, self.total = g, sd, total
+        self.js = ev.jitter_sequence(0, 4096, W, H)
+
+    def iteration(self, i):
+        fp = ev.frame_params(camera_pos=self.sd.cam_origin, mis_mode="one", clamping_value=1.0 / self.total, num_light_paths=NL,
+                             num_vpl_light_paths=NV, photons_per_path=P, do_accumulate=1, rng_seed=i, jitter=tuple(float(x) for x in self.js[i]))
+        self.g.primary(tuple(self.js[i])); self.g.trace_light_paths(i); self.g.gather(fp, 0)
+
+
+def gather_ms(g):
+    return g.context(0).pass_stats(ev.PASS_GATHER_VPL)["ms"]
+
+
+def curve(g, run, iters, every, tau, min_batches, tiles):
+    g.clear_accumulators(); g.noise_track(True)
+    if tau is not None:
+        g.adaptive_enable(True)
+    g.synchronize()
+    wall = 0.0; pts = []; retired = 0; gms = []
+    for i in range(iters):
+        t0 = time.perf_counter()
+        run.iteration(i); g.noise_fold(1)
+        if tau is not None and (i + 1) % every == 0:
+            retired += g.adaptive_retire(1.0 / (i + 1), tau, min_batches)
+        g.synchronize()
+        wall += (time.perf_counter() - t0) * 1e3
+        gms.append(gather_ms(g))
+        if (i + 1) % every == 0:
+            s = 1.0 / (i + 1)
+            e = g.frame_error(s, s, 1.0)
+            pts.append({"iteration": i + 1, "wall_ms": wall, "rel_mse": e[1], "retired_tiles": retired,
+                        "gather_ms": statistics.median(gms[-every:])})
+    return pts, retired
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=128)
+    ap.add_argument("--ref-iters", type=int, default=512)
+    ap.add_argument("--taus", default="0.002,0.0005,0.0001")
+    ap.add_argument("--every", type=int, default=8)
+    ap.add_argument("--min-batches", type=int, default=4)
+    a = ap.parse_args()
+    tiles = ((W + 7) // 8) * ((H + 7) // 8)
+    res = {"shape": {"W": W, "H": H, "numLightPaths": NL, "numVplLightPaths": NV, "scene": "hard, 331000 triangles"}, "tiles": tiles}
+    with tempfile.TemporaryDirectory() as d:
+        jp = ev.synth_scene(d, "conference_synth", 331000, 1234, W, H, style="hard")
+        sd, _ = scenes.load_obj_scene(jp)
+        with ev.Group(W, H, NL, NV, P, 1, devices=[0], overlap_light_tracing=True) as g:
+            g.load_scene_json(jp)
+            bsr, total, _ = g.context(0).scene_metrics()
+            run = Runner(g, sd, total)
+            # the reference: a long plain run
+            g.clear_accumulators()
+            for i in range(a.ref_iters):
+                run.iteration(i)
+            s = 1.0 / a.ref_iters
+            ref = np.ascontiguousarray(g.resolve(s, s, 1.0)[::-1]).astype(np.float32)
+            g.set_error_reference(ref)
+            res["reference_iterations"] = a.ref_iters
+            runs = {}
+            for tau in [None] + [float(x) for x in a.taus.split(",") if x]:
+                g.clear_accumulators()                           # (N = 0: adaptivity can be switched)
+                g.adaptive_enable(False)
+                pts, retired = curve(g, run, a.iters, a.every, tau, a.min_batches, tiles)
+                name = "plain" if tau is None else f"tileRelMse_{tau:g}"
+                runs[name] = {"points": pts, "retired_tiles": retired}
+            g.clear_accumulators(); g.adaptive_enable(False)
+            base = runs["plain"]["points"]
+            for name, r in runs.items():
+                last = r["points"][-1]
+                r["retired_fraction"] = r["retired_tiles"] / tiles
+                r["gather_time_saved_fraction"] = 1.0 - last["gather_ms"] / base[-1]["gather_ms"]
+                # time to reach the plain run's final relMSE (linear interpolation between checkpoints; null when not reached)
+                target = base[-1]["rel_mse"]
+                hit = None
+                for p0, p1 in zip([{"wall_ms": 0.0, "rel_mse": math.inf}] + r["points"], r["points"]):
+                    if p1["rel_mse"] <= target:
+                        t = 1.0 if not math.isfinite(p0["rel_mse"]) else (p0["rel_mse"] - target) / max(p0["rel_mse"] - p1["rel_mse"], 1e-300)
+                        hit = p0["wall_ms"] + t * (p1["wall_ms"] - p0["wall_ms"]); break
+                r["ms_to_plain_final_rel_mse"] = hit
+            res["runs"] = runs
+            # the floor: every tile retired
+            g.clear_accumulators(); g.noise_track(True); g.adaptive_enable(True)
+            for i in range(4):
+                run.iteration(i); g.noise_fold(1)
+            full_pass = gather_ms(g)
+            assert g.adaptive_retire(0.25, 1e300, 2) == tiles
+            walls, passes = [], []
+            for i in range(4, 24):
+                g.synchronize()
+                t0 = time.perf_counter()
+                fp = ev.frame_params(camera_pos=sd.cam_origin, mis_mode="one", clamping_value=1.0 / total, num_light_paths=NL,
+                                     num_vpl_light_paths=NV, photons_per_path=P, do_accumulate=1, rng_seed=i)
+                g.gather(fp, 0); g.synchronize()
+                walls.append((time.perf_counter() - t0) * 1e3); passes.append(gather_ms(g))
+            res["floor"] = {"all_retired_gather_pass_ms": statistics.median(passes), "all_retired_gather_wall_ms": statistics.median(walls),
+                            "full_gather_pass_ms": full_pass, "floor_fraction": statistics.median(passes) / full_pass}
+            g.clear_accumulators(); g.adaptive_enable(False)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
