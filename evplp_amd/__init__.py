@@ -84,6 +84,12 @@ PARTITION_STRIPS, PARTITION_ITERATIONS = 0, 2
 PARTITIONS = {"strips": PARTITION_STRIPS, "iterations": PARTITION_ITERATIONS}
 
 
+class DenoiseParams(C.Structure):
+    """evplp_denoise_params: a zero field is the library's default (levels 5, sigma_luminance 4, sigma_normal 128, sigma_position 0.01)"""
+    _fields_ = [("levels", C.c_int32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float), ("sigma_position", C.c_float),
+                ("reserved", C.c_int32 * 4)]
+
+
 class PassStats(C.Structure):
     _fields_ = [("ms", C.c_float), ("pairs", C.c_uint64), ("rays", C.c_uint64), ("usable", C.c_uint64),
                 ("dominant_kernel_ms", C.c_float), ("reserved", C.c_uint32 * 3), ("shaded", C.c_uint64), ("launches", C.c_uint32),
@@ -126,6 +132,7 @@ _SIGNATURES = {
     "evplp_noise_fold": (C.c_int, [_P, C.c_int32]),
     "evplp_noise_estimate": (C.c_int, [_P, C.c_float, C.c_float, C.c_int32, C.POINTER(C.c_double * 3)]),
     "evplp_noise_variance": (C.c_int, [_P, C.c_float, _P]),
+    "evplp_denoise": (C.c_int, [_P, C.c_float, C.c_float, C.c_int32, C.POINTER(DenoiseParams), _P]),
     "evplp_adaptive_enable": (C.c_int, [_P, C.c_int32]),
     "evplp_adaptive_retire": (C.c_int, [_P, C.c_float, C.c_float, C.c_int32, C.c_double, C.c_int32]),
     "evplp_adaptive_tiles": (C.c_int, [_P, _P, C.c_int32]),
@@ -180,6 +187,7 @@ _SIGNATURES = {
     "evplp_group_noise_fold": (C.c_int, [_P, C.c_int32]),
     "evplp_group_noise_estimate": (C.c_int, [_P, C.c_float, C.c_float, C.c_int32, C.POINTER(C.c_double * 3)]),
     "evplp_group_noise_variance": (C.c_int, [_P, C.c_float, _P]),
+    "evplp_group_denoise": (C.c_int, [_P, C.c_float, C.c_float, C.c_int32, C.POINTER(DenoiseParams), _P]),
     "evplp_group_adaptive_enable": (C.c_int, [_P, C.c_int32]),
     "evplp_group_adaptive_retire": (C.c_int, [_P, C.c_float, C.c_float, C.c_int32, C.c_double, C.c_int32]),
     "evplp_group_adaptive_tiles": (C.c_int, [_P, _P, C.c_int32]),
@@ -262,6 +270,13 @@ def _noise_track_args(on, mask, W: int, H: int):
                              f"{getattr(mask, 'dtype', type(mask).__name__)} {getattr(mask, 'shape', None)}")
         mask = np.ascontiguousarray(mask)
     return int(bool(on)), mask
+
+
+def _denoise_params(levels, sigma_luminance, sigma_normal, sigma_position) -> DenoiseParams:
+    """evplp_denoise_params from the keyword arguments of denoise (0 = the default; the library checks the ranges)"""
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)):
+        raise ValueError(f"denoise: levels must be an int, got {levels!r}")
+    return DenoiseParams(int(levels), float(sigma_luminance), float(sigma_normal), float(sigma_position))
 
 
 def _fold_iterations(iterations) -> int:
@@ -515,6 +530,14 @@ class Context:
         """per-pixel variance of scale * sums, float32 (local_rows, W, 3), y = 0 at the bottom"""
         out = np.empty((self.local_rows, self.W, 3), dtype=np.float32)
         self._check(self._lib.evplp_noise_variance(self._h, float(scale), _ptr(out)))
+        return out
+
+    def denoise(self, scale, light_scale=1.0, mask_emitter=False, levels=0, sigma_luminance=0, sigma_normal=0, sigma_position=0) -> np.ndarray:
+        """the composite of noise_estimate's arguments, filtered by the variance-guided a-trous denoiser (include/evplp.h evplp_denoise):
+        float32 (local_rows, W, 3), y = 0 at the bottom, linear.  0 = the library's default for levels and every sigma."""
+        p = _denoise_params(levels, sigma_luminance, sigma_normal, sigma_position)
+        out = np.empty((self.local_rows, self.W, 3), dtype=np.float32)
+        self._check(self._lib.evplp_denoise(self._h, float(scale), float(light_scale), int(mask_emitter), C.byref(p), _ptr(out)))
         return out
 
     def adaptive_enable(self, on=True):
@@ -799,6 +822,13 @@ class Group:
         """per-pixel variance of scale * sums, float32 (H, W, 3), y = 0 at the bottom"""
         out = np.empty((self.H, self.W, 3), dtype=np.float32)
         self._check(self._lib.evplp_group_noise_variance(self._h, float(scale), _ptr(out)))
+        return out
+
+    def denoise(self, scale, light_scale=1.0, mask_emitter=False, levels=0, sigma_luminance=0, sigma_normal=0, sigma_position=0) -> np.ndarray:
+        """Context.denoise for the whole frame, float32 (H, W, 3), y = 0 at the bottom (strips: equal to one context's, bit for bit)"""
+        p = _denoise_params(levels, sigma_luminance, sigma_normal, sigma_position)
+        out = np.empty((self.H, self.W, 3), dtype=np.float32)
+        self._check(self._lib.evplp_group_denoise(self._h, float(scale), float(light_scale), int(mask_emitter), C.byref(p), _ptr(out)))
         return out
 
     def adaptive_enable(self, on=True):

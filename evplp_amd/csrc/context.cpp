@@ -206,6 +206,7 @@ extern "C" void evplp_destroy(evplp_context *c) {
     hipFree(c->d_err_ref); hipFree(c->d_err_keep); hipFree(c->d_err_rows);
     hipFree(c->d_noise); hipFree(c->d_noise_keep); hipFree(c->d_noise_rows);
     hipFree(c->d_adapt_tiles); hipFree(c->d_adapt_snap);
+    hipFree(c->d_dn_var); hipFree(c->d_dn_pack); hipFree(c->d_dn_u);
     for (int i = 0; i < EVPLP_PASS_COUNT; i++) {
         if (c->ev_begin[i]) hipEventDestroy(c->ev_begin[i]);
         if (c->ev_end[i]) hipEventDestroy(c->ev_end[i]);
@@ -1210,6 +1211,94 @@ extern "C" int evplp_noise_variance(evplp_context *c, float scale, float *out_rg
     int rc = noise_ready(c, "evplp_noise_variance");
     if (rc) return rc;
     if ((rc = evplp::noise_variance_to_device(c, evplp::noise_moments_of(c), (double)c->noise_k, (double)c->noise_b, scale))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(out_rgb, c->d_rgb, sizeof(float) * 3 * (size_t)c->st.W * c->st.local_rows, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return EVPLP_OK;
+}
+
+// ---- the denoiser of a written frame (include/evplp.h evplp_denoise, kernels_denoise.hip)
+namespace evplp {
+bool denoise_settings(const evplp_denoise_params *p, DenoiseSettings *out, char *why, size_t cap) {
+    DenoiseSettings d{ 5, 4.0f, 128.0f, 0.01f };
+    if (p) {
+        if (p->levels != 0) d.levels = p->levels;
+        const float sig[3] = { p->sigma_luminance, p->sigma_normal, p->sigma_position };
+        const char *names[3] = { "sigma_luminance", "sigma_normal", "sigma_position" };
+        for (int k = 0; k < 3; k++)
+            if (!std::isfinite(sig[k]) || sig[k] < 0.0f) { std::snprintf(why, cap, "%s must be finite and >= 0 (0 = the default), not %g", names[k], (double)sig[k]); return false; }
+        if (p->sigma_luminance != 0.0f) d.sigma_l = p->sigma_luminance;
+        if (p->sigma_normal != 0.0f) d.sigma_n = p->sigma_normal;
+        if (p->sigma_position != 0.0f) d.sigma_x = p->sigma_position;
+    }
+    if (d.levels < 1 || d.levels > 10) { std::snprintf(why, cap, "levels must be 1..10 (0 = the default 5), not %d", d.levels); return false; }
+    *out = d;
+    return true;
+}
+static int denoise_alloc(evplp_context *c, void **p, size_t bytes) {
+    if (*p) return EVPLP_OK;
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e == hipSuccess) return EVPLP_OK;
+    (void)hipGetLastError(); *p = nullptr;
+    c->set_error("evplp_denoise: cannot allocate %zu bytes: %s", bytes, hipGetErrorString(e));
+    return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP;
+}
+int denoise_keep_variance(evplp_context *c) {
+    const size_t px = (size_t)c->st.W * c->st.local_rows;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    int rc = denoise_alloc(c, (void **)&c->d_dn_var, sizeof(float) * 3 * std::max<size_t>(px, 1));
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->d_dn_var, c->d_rgb, sizeof(float) * 3 * px, hipMemcpyDeviceToDevice, c->stream));
+    return EVPLP_OK;
+}
+int denoise_prepare(evplp_context *c, const float4 *pos, const float4 *nrm, const float4 *dif, const float4 *phg, const float4 *light) {
+    const size_t px = (size_t)c->st.W * c->st.local_rows;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    int rc = denoise_alloc(c, (void **)&c->d_dn_pack, sizeof(DenoisePixel) * std::max<size_t>(px, 1));
+    if (rc) return rc;
+    launch_denoise_prepare(c->st, c->d_rgb, c->d_dn_var, pos, nrm, dif, phg, light, (float4 *)c->d_dn_pack, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return EVPLP_OK;
+}
+int denoise_filter(evplp_context *c, const DenoisePixel *frame, int rows, const DenoiseSettings &ds, float radius, float *out_rgb) {
+    const size_t px = (size_t)c->st.W * rows;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    if (c->d_dn_u && c->dn_u_px < px) { hipFree(c->d_dn_u); c->d_dn_u = nullptr; }
+    int rc = denoise_alloc(c, (void **)&c->d_dn_u, sizeof(float4) * 2 * std::max<size_t>(px, 1));
+    if (rc) return rc;
+    c->dn_u_px = std::max(c->dn_u_px, px);
+    DenoiseLevelArgs a{};
+    a.frame = frame; a.W = c->st.W; a.rows = rows;
+    a.sigma_l = ds.sigma_l; a.sigma_n = ds.sigma_n; a.sigma_x_r = ds.sigma_x * radius;
+    for (int i = 0; i < ds.levels; i++) {
+        a.in = i == 0 ? &frame->u : c->d_dn_u + (size_t)((i - 1) & 1) * px;
+        a.in_step = i == 0 ? kDenoiseFloats / 4 : 1;
+        a.out = c->d_dn_u + (size_t)(i & 1) * px;
+        a.h = 1 << i;
+        launch_denoise_level(a, c->stream);
+    }
+    launch_denoise_finish(frame, c->d_dn_u + (size_t)((ds.levels - 1) & 1) * px, px, out_rgb, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return EVPLP_OK;
+}
+} // namespace evplp
+extern "C" int evplp_denoise(evplp_context *c, float scale, float ls, int32_t mask_emitter, const evplp_denoise_params *p, float *out_rgb) {
+    CTX_CHECK(c);
+    evplp::DenoiseSettings ds; char why[200];
+    if (!evplp::denoise_settings(p, &ds, why, sizeof why)) { c->set_error("evplp_denoise: %s", why); return EVPLP_ERR_INVALID; }
+    if (!out_rgb) { c->set_error("evplp_denoise: null output"); return EVPLP_ERR_INVALID; }
+    if (c->st.strip_count > 1) {
+        c->set_error("evplp_denoise: a row-strip context (strip_count %d) cannot see its neighbours' rows: use evplp_group_denoise", c->st.strip_count);
+        return EVPLP_ERR_INVALID;
+    }
+    if (!c->accel_built) { c->set_error("evplp_denoise: no scene (evplp_build_accel): the position term needs its bounding sphere"); return EVPLP_ERR_INVALID; }
+    int rc = noise_ready(c, "evplp_denoise");
+    if (rc) return rc;
+    if ((rc = evplp::noise_variance_to_device(c, evplp::noise_moments_of(c), (double)c->noise_k, (double)c->noise_b, scale))) return rc;
+    if ((rc = evplp::denoise_keep_variance(c))) return rc;
+    if ((rc = evplp::resolve_to_device(c, scale, scale, ls, mask_emitter, 0, true, false))) return rc;
+    if ((rc = evplp::denoise_prepare(c, (const float4 *)c->buf[EVPLP_BUF_GBUF_POSITION], (const float4 *)c->buf[EVPLP_BUF_GBUF_NORMAL],
+                                     (const float4 *)c->buf[EVPLP_BUF_GBUF_DIFFUSE], (const float4 *)c->buf[EVPLP_BUF_GBUF_PHONG], (const float4 *)c->buf[EVPLP_BUF_LIGHT]))) return rc;
+    if ((rc = evplp::denoise_filter(c, c->d_dn_pack, c->st.local_rows, ds, c->bounding_radius, c->d_rgb))) return rc;
     HIP_TRY(c, hipMemcpyAsync(out_rgb, c->d_rgb, sizeof(float) * 3 * (size_t)c->st.W * c->st.local_rows, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return EVPLP_OK;

@@ -36,6 +36,17 @@ int noise_rows(evplp_context *c, const NoiseMoments &m, const float4 *light, dou
 int noise_variance_to_device(evplp_context *c, const NoiseMoments &m, double K, double B, float scale);
 // evplp_adaptive_tiles' map of this context's tiles written into out [ceil(H / 8)][ceil(W / 8)] (rows from the bottom); other tiles untouched
 void adaptive_tiles_into(const evplp_context *c, int32_t *out);
+// evplp_denoise (context.cpp), for the group's workers as well.  The parameters with the defaults filled in, checked: false and the reason in
+// why when they are refused.
+struct DenoiseSettings { int32_t levels; float sigma_l, sigma_n, sigma_x; };
+bool denoise_settings(const evplp_denoise_params *p, DenoiseSettings *out, char *why, size_t cap);
+// the variance image in d_rgb kept in d_dn_var (stream order)
+int denoise_keep_variance(evplp_context *c);
+// the composite in d_rgb, the kept variance and the given guides / light plane of this context's planes -> d_dn_pack (stream order)
+int denoise_prepare(evplp_context *c, const float4 *pos, const float4 *nrm, const float4 *dif, const float4 *phg, const float4 *light);
+// the a-trous passes and the remodulation over a frame of W x rows packed pixels on this context's device -> out_rgb (device, 3 floats per
+// pixel; stream order).  radius: the scene's bounding-sphere radius
+int denoise_filter(evplp_context *c, const DenoisePixel *frame, int rows, const DenoiseSettings &ds, float radius, float *out_rgb);
 }
 
 struct evplp_context {
@@ -145,6 +156,10 @@ struct evplp_context {
     // evplp_adaptive_retire and at a clear), the retired pixels' snapshot of VPL_ACCUM [W * local_rows]; adapt_last: tiles retired by the
     // last evplp_adaptive_retire (the group's workers leave it here)
     int64_t adapt_n = 0; int4 *d_adapt_tiles = nullptr; float4 *d_adapt_snap = nullptr; std::vector<int4> adapt_tiles; int32_t adapt_last = 0;
+    // evplp_denoise: the variance image [W * local_rows][3], the packed pixels of the planes [W * local_rows] (kernels.h DenoisePixel), and
+    // the two (u, s) planes of the a-trous passes [2][dn_u_px] (the frame the context filters: its planes, or a group's whole image on rank 0);
+    // allocated on the first call, kept until evplp_destroy
+    float *d_dn_var = nullptr; evplp::DenoisePixel *d_dn_pack = nullptr; float4 *d_dn_u = nullptr; size_t dn_u_px = 0;
 
     char error[512] = "";
     void set_error(const char *fmt, ...);

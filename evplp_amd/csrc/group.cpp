@@ -64,7 +64,7 @@ struct Rccl {
 };
 
 enum Op { OP_QUIT = 0, OP_CLEAR, OP_SYNC, OP_PRIMARY, OP_TRACE, OP_GATHER, OP_SPLAT, OP_PATH_TRACE, OP_PRESENT, OP_LOAD_SCENE, OP_SET_PROXY, OP_ASSEMBLE, OP_REDUCE, OP_SET_REFERENCE, OP_FRAME_ERROR,
-          OP_NOISE_TRACK, OP_NOISE_FOLD, OP_NOISE_POOL, OP_NOISE_ROWS, OP_NOISE_VARIANCE, OP_ADAPT_ENABLE, OP_ADAPT_RETIRE };
+          OP_NOISE_TRACK, OP_NOISE_FOLD, OP_NOISE_POOL, OP_NOISE_ROWS, OP_NOISE_VARIANCE, OP_ADAPT_ENABLE, OP_ADAPT_RETIRE, OP_DENOISE_PREP, OP_DENOISE_FILTER };
 // One posted call: plain data, copied into the ring (pointers must stay valid until the caller has drained: load_scene, set_proxy, resolve do)
 struct Cmd {
     int op = OP_QUIT;
@@ -135,6 +135,13 @@ struct evplp_group {
     // ranks (written by rank 0's worker); RCCL only: per rank [n][noise_bytes] every rank's NoisePlanes (all-gathered)
     double *d_noise_pool = nullptr; double pool_k = 0.0, pool_b = 0.0;
     std::vector<char *> d_noise_stage;
+    // evplp_group_denoise.  Strips: per rank [n][chunk rows * W] packed pixels (kernels.h DenoisePixel) all-gathered from the ranks, and rank 0's
+    // assembled frame [H * W].  Iterations: last_primary = the rank the last evplp_group_primary went to (caller's thread), and on rank 0 the
+    // four G-buffer planes copied from it when it is another device ([4][plane_px])
+    std::vector<float *> d_dn_recv;
+    evplp::DenoisePixel *d_dn_frame = nullptr;
+    int last_primary = 0;
+    float4 *d_dn_guides = nullptr;
     size_t plane_px = 0;                    // W * local_rows: the pixels of one accumulator plane
     std::vector<float4 *> d_sum;            // per rank: [3][plane_px] VPL, photon and light planes reduced over the ranks (the first reduction)
     std::vector<float4 *> d_stage;          // per rank, RCCL only: [n][plane_px] one plane of every rank (all-gathered)
@@ -308,11 +315,64 @@ static void worker_noise_pool(Worker *w) {
 static evplp::NoiseMoments noise_pooled(const evplp_group *g, const evplp_context *c0) {
     return evplp::NoiseMoments{ g->d_noise_pool, g->d_noise_pool + 3 * c0->noise_stride, nullptr, nullptr, c0->noise_stride };
 }
+// evplp_group_denoise.  Strips (every rank, then the all-gather in worker_run): this rank's variance, composite and packed pixels.
+// Iterations (rank 0, behind the pooled variance and the reduction): the packed pixels of the reduced composite and light plane with the
+// guides of rank cmd.i[2], copied to rank 0's device first when that is another GPU.
+static int worker_denoise_prep(Worker *w, const Cmd &cmd) {
+    evplp_group *g = w->g; const int r = w->rank; evplp_context *c = g->ctx[(size_t)r];
+    const float4 *gb[4]; const float4 *light;
+    int rc;
+    if (!g->iterations) {
+        if ((rc = evplp::noise_variance_to_device(c, evplp::noise_moments_of(c), (double)c->noise_k, (double)c->noise_b, cmd.f[0])) < 0) return rc;
+        if ((rc = evplp::denoise_keep_variance(c)) < 0) return rc;
+        if ((rc = evplp::resolve_to_device(c, cmd.f[0], cmd.f[0], cmd.f[1], cmd.i[0], 0, true, false)) < 0) return rc;
+        for (int k = 0; k < 4; k++) gb[k] = (const float4 *)c->buf[EVPLP_BUF_GBUF_POSITION + k];
+        light = (const float4 *)c->buf[EVPLP_BUF_LIGHT];
+    } else {
+        const evplp_context *src = g->ctx[(size_t)cmd.i[2]];
+        const size_t px = g->plane_px;
+        for (int k = 0; k < 4; k++) gb[k] = (const float4 *)src->buf[EVPLP_BUF_GBUF_POSITION + k];
+        if (src != c && g->device[(size_t)cmd.i[2]] != g->device[0]) {
+            hipError_t e = hipSuccess;
+            if (!g->d_dn_guides) e = hipMalloc((void **)&g->d_dn_guides, sizeof(float4) * 4 * px);
+            for (int k = 0; k < 4 && e == hipSuccess; k++)
+                e = hipMemcpyPeerAsync(g->d_dn_guides + (size_t)k * px, g->device[0], gb[k], g->device[(size_t)cmd.i[2]], sizeof(float4) * px, c->stream);
+            if (e != hipSuccess) { (void)hipGetLastError(); c->set_error("evplp_group_denoise: guides of rank %d: %s", cmd.i[2], hipGetErrorString(e)); return EVPLP_ERR_HIP; }
+            for (int k = 0; k < 4; k++) gb[k] = g->d_dn_guides + (size_t)k * px;
+        }
+        light = g->d_sum[0] + 2 * px;
+    }
+    return evplp::denoise_prepare(c, gb[0], gb[1], gb[2], gb[3], light);
+}
+// rank 0: the frame of packed pixels (strips: assembled from the all-gathered rows), the passes, the frame to the caller (cmd.out)
+static int worker_denoise_filter(Worker *w, const Cmd &cmd) {
+    evplp_group *g = w->g; evplp_context *c = g->ctx[0];
+    const size_t frame_px = (size_t)c->st.W * c->st.H;
+    evplp::DenoiseSettings ds{ cmd.i[0], cmd.f[0], cmd.f[1], cmd.f[2] };
+    const evplp::DenoisePixel *frame = c->d_dn_pack;
+    int rows = c->st.local_rows;
+    float *out = c->d_rgb;
+    hipError_t e = hipSuccess;
+    if (!g->iterations) {
+        if (!g->d_dn_frame) e = hipMalloc((void **)&g->d_dn_frame, sizeof(evplp::DenoisePixel) * frame_px);
+        if (e == hipSuccess && !g->d_assembled) e = hipMalloc((void **)&g->d_assembled, sizeof(float) * 3 * frame_px);
+        if (e != hipSuccess) { (void)hipGetLastError(); c->set_error("evplp_group_denoise: %s", hipGetErrorString(e)); return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP; }
+        evplp::launch_assemble_strips(c->st, g->n, g->owner.empty() ? nullptr : g->d_owner, (int)(g->strip_floats / ((size_t)c->st.W * 3)), g->d_dn_recv[0],
+                                      (float *)g->d_dn_frame, c->stream, evplp::kDenoiseFloats);
+        frame = g->d_dn_frame; rows = c->st.H; out = g->d_assembled;
+    }
+    int rc = evplp::denoise_filter(c, frame, rows, ds, c->bounding_radius, out);
+    if (rc < 0) return rc;
+    e = hipMemcpyAsync(cmd.out, out, sizeof(float) * 3 * frame_px, hipMemcpyDeviceToHost, c->stream);     // (rows 0 .. H - 1 in image order)
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { c->set_error("evplp_group_denoise: %s", hipGetErrorString(e)); return EVPLP_ERR_HIP; }
+    return EVPLP_OK;
+}
 static void worker_run(Worker *w, const Cmd &cmd) {
     if (cmd.op == OP_REDUCE) { worker_reduce(w, cmd); return; }
     if (cmd.op == OP_NOISE_POOL) { worker_noise_pool(w); return; }
     evplp_group *g = w->g; const int r = w->rank; evplp_context *c = g->ctx[(size_t)r];
-    const bool collective = ((cmd.op == OP_PRESENT || cmd.op == OP_NOISE_VARIANCE) && cmd.i[3] != 0) || (cmd.op == OP_TRACE && g->split_paths);
+    const bool collective = ((cmd.op == OP_PRESENT || cmd.op == OP_NOISE_VARIANCE || cmd.op == OP_DENOISE_PREP) && cmd.i[3] != 0) || (cmd.op == OP_TRACE && g->split_paths);
     int rc = EVPLP_OK;
     const double t0 = now_ms();
     if (w->status.load(std::memory_order_relaxed) == 0) {
@@ -352,7 +412,10 @@ static void worker_run(Worker *w, const Cmd &cmd) {
         case OP_NOISE_VARIANCE:
             if (cmd.i[1]) rc = evplp::noise_variance_to_device(c, noise_pooled(g, c), g->pool_k, g->pool_b, cmd.f[0]);
             else rc = evplp::noise_variance_to_device(c, evplp::noise_moments_of(c), (double)c->noise_k, (double)c->noise_b, cmd.f[0]);
+            if (rc >= 0 && cmd.i[2]) rc = evplp::denoise_keep_variance(c);        // (i[2]: evplp_group_denoise's variance)
             break;
+        case OP_DENOISE_PREP: rc = worker_denoise_prep(w, cmd); break;
+        case OP_DENOISE_FILTER: rc = worker_denoise_filter(w, cmd); break;
         case OP_ASSEMBLE: {
             // rank 0 puts the strips into image order on the device; one copy lands the frame in the caller's buffer (no host-side assembly:
             // a run that writes every frame resolves every iteration)
@@ -381,6 +444,9 @@ static void worker_run(Worker *w, const Cmd &cmd) {
             const size_t chunk = (size_t)g->per_rank_paths * c->cfg.photons_per_path * (sizeof(evplp_record) / sizeof(float));
             for (int q = 0; q < g->n; q++) all[(size_t)q] = (const float *)g->ctx[(size_t)q]->buf[EVPLP_BUF_RECORDS] + (size_t)q * chunk;
             worker_all_gather(w, (float *)c->buf[EVPLP_BUF_RECORDS], chunk, all);
+        } else if (cmd.op == OP_DENOISE_PREP) {          // (the packed pixels of the rows an exchange moves)
+            for (int q = 0; q < g->n; q++) all[(size_t)q] = (const float *)g->ctx[(size_t)q]->d_dn_pack;
+            worker_all_gather(w, g->d_dn_recv[(size_t)r], g->strip_floats / 3 * evplp::kDenoiseFloats, all);
         } else {
             for (int q = 0; q < g->n; q++) all[(size_t)q] = g->ctx[(size_t)q]->d_rgb;
             worker_all_gather(w, g->d_frame[(size_t)r], g->strip_floats, all);
@@ -506,6 +572,8 @@ extern "C" void evplp_group_destroy(evplp_group *g) {
     for (int r = 0; r < (int)g->d_frame.size(); r++) if (g->d_frame[(size_t)r]) { hipSetDevice(g->device[(size_t)r]); hipFree(g->d_frame[(size_t)r]); }
     for (int r = 0; r < (int)g->d_sum.size(); r++) if (g->d_sum[(size_t)r] || g->d_stage[(size_t)r]) { hipSetDevice(g->device[(size_t)r]); hipFree(g->d_sum[(size_t)r]); hipFree(g->d_stage[(size_t)r]); }
     for (int r = 0; r < (int)g->d_noise_stage.size(); r++) if (g->d_noise_stage[(size_t)r]) { hipSetDevice(g->device[(size_t)r]); hipFree(g->d_noise_stage[(size_t)r]); }
+    for (int r = 0; r < (int)g->d_dn_recv.size(); r++) if (g->d_dn_recv[(size_t)r]) { hipSetDevice(g->device[(size_t)r]); hipFree(g->d_dn_recv[(size_t)r]); }
+    if (g->d_dn_frame || g->d_dn_guides) { hipSetDevice(g->device[0]); hipFree(g->d_dn_frame); hipFree(g->d_dn_guides); }
     if (g->d_assembled || g->d_owner || g->d_noise_pool) { hipSetDevice(g->device[0]); hipFree(g->d_assembled); hipFree(g->d_owner); hipFree(g->d_noise_pool); }
     for (ncclComm_t c : g->comms) if (c && g->rccl.CommDestroy) g->rccl.CommDestroy(c);
     for (evplp_context *c : g->ctx) { c->quiesce = nullptr; evplp_destroy(c); }
@@ -557,7 +625,7 @@ extern "C" int evplp_group_create(const evplp_config *cfg, const evplp_group_con
     g->strip_floats = g->n == 1 ? g->strip_floats_cap : round_robin_floats(g);
     g->d_frame.assign((size_t)g->n, nullptr);
     g->plane_px = (size_t)g->ctx[0]->st.W * g->ctx[0]->st.local_rows;
-    g->d_sum.assign((size_t)g->n, nullptr); g->d_stage.assign((size_t)g->n, nullptr); g->d_noise_stage.assign((size_t)g->n, nullptr); g->num_cus.assign((size_t)g->n, 256);
+    g->d_sum.assign((size_t)g->n, nullptr); g->d_stage.assign((size_t)g->n, nullptr); g->d_noise_stage.assign((size_t)g->n, nullptr); g->d_dn_recv.assign((size_t)g->n, nullptr); g->num_cus.assign((size_t)g->n, 256);
     for (int r = 0; r < g->n; r++) {
         hipSetDevice(g->device[(size_t)r]);
         int cus = 0;
@@ -678,6 +746,7 @@ extern "C" int evplp_group_synchronize(evplp_group *g) { GRP_CHECK(g); Cmd c; c.
 extern "C" int evplp_group_primary(evplp_group *g, const float jitter[2], int32_t light_flags) {
     GRP_CHECK(g);
     Cmd c; c.op = OP_PRIMARY; c.f[0] = jitter ? jitter[0] : 0.f; c.f[1] = jitter ? jitter[1] : 0.f; c.i[0] = light_flags;
+    if (g->iterations) g->last_primary = g->selected;          // (whose G-buffer evplp_group_denoise reads)
     return post_pass(g, c);
 }
 extern "C" int evplp_group_trace_light_paths(evplp_group *g, uint32_t rng_seed) { GRP_CHECK(g); Cmd c; c.op = OP_TRACE; c.u[0] = rng_seed; return post_pass(g, c); }
@@ -875,6 +944,48 @@ extern "C" int evplp_group_noise_variance(evplp_group *g, float scale, float *ou
     if (rc < 0) return rc;
     Cmd a; a.op = OP_ASSEMBLE; a.out = out_rgb;
     post(g->workers[0], a);
+    drain(g);
+    return group_status(g);
+}
+
+// The denoiser of a written frame (include/evplp.h evplp_group_denoise).  Strips: every rank packs its rows, the packed rows are all-gathered
+// and assembled on rank 0 as a resolve's strips are, and rank 0 filters the frame.  Iterations: rank 0 packs the pooled variance, the reduced
+// composite and light plane and the guides of the rank of the last primary, and filters them.
+extern "C" int evplp_group_denoise(evplp_group *g, float scale, float ls, int32_t mask_emitter, const evplp_denoise_params *p, float *out_rgb) {
+    GRP_CHECK(g);
+    evplp::DenoiseSettings ds; char why[200];
+    if (!evplp::denoise_settings(p, &ds, why, sizeof why)) { g->set_error("evplp_group_denoise: %s", why); return EVPLP_ERR_INVALID; }
+    if (!out_rgb) { g->set_error("evplp_group_denoise: null output"); return EVPLP_ERR_INVALID; }
+    int rc = noise_group_ready(g, "evplp_group_denoise");
+    if (rc < 0) return rc;
+    if (!g->ctx[0]->accel_built) { g->set_error("evplp_group_denoise: no scene (evplp_group_load_scene_json / evplp_build_accel)"); return EVPLP_ERR_INVALID; }
+    if (!g->iterations) {
+        // every rank's packed pixels and receive buffer exist before any worker names them in the all-gather (the workers are idle here)
+        for (int r = 0; r < g->n; r++) {
+            evplp_context *c = g->ctx[(size_t)r];
+            const size_t px = std::max<size_t>((size_t)c->st.W * c->st.local_rows, 1);
+            hipError_t e = hipSetDevice(g->device[(size_t)r]);
+            if (e == hipSuccess && !c->d_dn_pack) e = hipMalloc((void **)&c->d_dn_pack, sizeof(evplp::DenoisePixel) * px);
+            if (e == hipSuccess && !g->d_dn_recv[(size_t)r]) e = hipMalloc((void **)&g->d_dn_recv[(size_t)r], sizeof(float) * (g->strip_floats_cap / 3) * evplp::kDenoiseFloats * (size_t)g->n);
+            if (e != hipSuccess) { (void)hipGetLastError(); g->set_error("evplp_group_denoise: rank %d: %s", r, hipGetErrorString(e)); return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP; }
+        }
+    }
+    Cmd prep; prep.op = OP_DENOISE_PREP; prep.f[0] = scale; prep.f[1] = ls; prep.i[0] = mask_emitter;
+    if (g->iterations) {
+        Cmd pool; pool.op = OP_NOISE_POOL;
+        rc = post_all(g, pool);
+        Cmd v; v.op = OP_NOISE_VARIANCE; v.f[0] = scale; v.i[1] = 1; v.i[2] = 1;
+        if (rc >= 0) post(g->workers[0], v);
+        if (rc >= 0) rc = post_reduce(g, scale, scale, ls, mask_emitter, 0);
+        prep.i[2] = g->last_primary;
+        if (rc >= 0) post(g->workers[0], prep);
+    } else {
+        prep.i[3] = 1;
+        rc = post_all(g, prep);
+    }
+    if (rc < 0) return rc;
+    Cmd f; f.op = OP_DENOISE_FILTER; f.i[0] = ds.levels; f.f[0] = ds.sigma_l; f.f[1] = ds.sigma_n; f.f[2] = ds.sigma_x; f.out = out_rgb;
+    post(g->workers[0], f);
     drain(g);
     return group_status(g);
 }

@@ -313,6 +313,7 @@ public:
     // the "adaptive" block's tile counts (Adaptive below): written into every checkpoint when `adaptive` is set
     bool adaptive = false; long long retired_tiles = 0, image_tiles = 0;
     long long batch_iterations() const { return batch; }
+    long long batch_count() const { return batches; }
     void parse(const Json &tech, const std::string &json_dir, const std::string &out_dir, int W, int H, int frame_mode) {
         if (!tech.has("noise")) return;
         const Json &c = tech.at("noise");
@@ -430,6 +431,58 @@ private:
     std::vector<Point> points;
 };
 
+// A run whose outputs are written but whose request cannot be met (evplp_render_json returns EVPLP_ERR_INVALID)
+struct InvalidError : std::runtime_error { using std::runtime_error::runtime_error; };
+
+// Build-only key "denoise" (photonfam, lvcphotonfam, pt): the saved composite filtered by the variance-guided a-trous denoiser
+// (evplp_group_denoise) and written as one more image, rows top to bottom, in the format of the file's extension.
+//   {"filename": "denoised.pfm", "levels": 5, "sigmaLuminance": 4, "sigmaNormal": 128, "sigmaPosition": 0.01}
+// filename is required; the others default to the library's (include/evplp.h).  Needs the "noise" block, whose variance guides the filter
+// (so frameMode "cleareveryframe" is refused).  Validated before the group exists.  Written after every other output, behind the noise
+// block's last fold; with fewer than two folds the other outputs are written and the run fails with EVPLP_ERR_INVALID.
+class Denoise {
+public:
+    bool on = false;
+    // (before Noise::parse: a "cleareveryframe" run with both blocks is refused under this block's name)
+    void parse(const Json &tech, const std::string &out_dir, int frame_mode) {
+        if (!tech.has("denoise")) return;
+        const Json &c = tech.at("denoise");
+        if (!c.is_object()) throw JsonError("denoise: expected an object");
+        if (!c.has("filename")) throw JsonError("denoise.filename: missing required key");
+        filename = output_path(out_dir, c.at("filename").as_string("denoise.filename"));
+        if (frame_mode == 2) throw JsonError("denoise: frameMode \"cleareveryframe\" keeps no running sum for the noise block to fold");
+        if (!tech.has("noise")) throw JsonError("denoise: needs a \"noise\" block (its per-pixel variance guides the filter)");
+        if (c.has("levels")) {
+            const long long l = c.at("levels").as_int("denoise.levels");
+            if (l < 1 || l > 10) throw JsonError("denoise.levels: must be 1..10");
+            p.levels = (int32_t)l;
+        }
+        sigma(c, "sigmaLuminance", p.sigma_luminance);
+        sigma(c, "sigmaNormal", p.sigma_normal);
+        sigma(c, "sigmaPosition", p.sigma_position);
+        on = true;
+    }
+    void write(evplp_group *g, int W, int H, long long batches, float scale, float ls, int32_t mask_emitter) {
+        if (!on) return;
+        if (batches < 2)
+            throw InvalidError("denoise: " + std::to_string(batches) + " noise batch(es) closed, the filter needs >= 2: " + filename + " is not written");
+        std::vector<float> rgb((size_t)W * H * 3);
+        check(g, evplp_group_denoise(g, scale, ls, mask_emitter, &p, rgb.data()), "denoise");
+        std::vector<float> top = flip_y(rgb, W, H);
+        if (save_image(filename.c_str(), W, H, top.data()) != EVPLP_OK) throw std::runtime_error("cannot write " + filename);
+    }
+
+private:
+    static void sigma(const Json &c, const char *key, float &out) {
+        if (!c.has(key)) return;
+        const double v = c.at(key).as_number((std::string("denoise.") + key).c_str());
+        if (!std::isfinite(v) || !(v > 0.0)) throw JsonError(std::string("denoise.") + key + ": must be > 0");
+        out = (float)v;
+    }
+    std::string filename;
+    evplp_denoise_params p{};
+};
+
 // Build-only key "adaptive" (photonfam, VPL and VSL gathers): tiles whose estimated noise has converged stop receiving gather work
 // (evplp_group_adaptive_*).  {"tileRelMse": 0.002, "everyIterations": 10, "minBatches": 4, "iterationsFilename": "iters.pfm"}
 // tileRelMse is required (>= 0); everyIterations (default: noise.batchIterations) is a multiple of noise.batchIterations: at every fold whose
@@ -527,6 +580,7 @@ public:
         int bvh_builder = EVPLP_BVH_SAH;
         if (json.has("bvhBuilder")) bvh_builder = parse_bvh_builder(json.at("bvhBuilder").as_string("bvhBuilder"));
         conv.parse(json, out_dir, out_dir, res_x, res_y);
+        denoise.parse(json, out_dir, frame_mode);
         noise.parse(json, out_dir, out_dir, res_x, res_y, frame_mode);
         if (json.has("adaptive")) throw JsonError("adaptive: not for pt (VPL and VSL gathers only)");
 
@@ -590,6 +644,7 @@ private:
             of << st.dump() << "\n";
         }
         save(h, W, H, num_iterations, output_filename, rgb);                                  // :706-719
+        { const Composite k = composite(num_iterations); denoise.write(h, W, H, noise.batch_count(), k.vs, k.ls, k.mask_emitter); }
     }
     // clear-every-frame: the composite as shown (masked emitter); accumulate: light image + path-traced image / n
     struct Composite { float vs, ps, ls; int32_t mask_emitter; };
@@ -607,6 +662,7 @@ private:
     std::string output_filename, stat_filename;
     Convergence conv;
     Noise noise;
+    Denoise denoise;
 };
 
 class ComPhotonTechnique {
@@ -663,6 +719,7 @@ public:
         if (!lvc && json.has("forceVsl")) force_vsl = json.at("forceVsl").as_bool("forceVsl");
         if (json.has("bvhBuilder")) bvh_builder = parse_bvh_builder(json.at("bvhBuilder").as_string("bvhBuilder"));   // build-only key
         conv.parse(json, out_dir, out_dir, res_x, res_y);                                                          // build-only key
+        denoise.parse(json, out_dir, frame_mode);                                                                   // build-only key
         noise.parse(json, out_dir, out_dir, res_x, res_y, frame_mode);                                             // build-only key
 
         // ---- setup(): context + scene upload (replaces GL/OptiX setup :646-708)
@@ -847,6 +904,7 @@ private:
         if (save_image(combined_filename.c_str(), W, H, combined.data()) != EVPLP_OK) throw std::runtime_error("cannot write " + combined_filename);
         if (save_image(weighted_vpl_filename.c_str(), W, H, vpl.data()) != EVPLP_OK) throw std::runtime_error("cannot write " + weighted_vpl_filename);
         if (save_image(weighted_photon_filename.c_str(), W, H, pm.data()) != EVPLP_OK) throw std::runtime_error("cannot write " + weighted_photon_filename);
+        denoise.write(h, W, H, noise.batch_count(), param, 1.0f, 0);                         // (the combinedFilename composite, filtered)
     }
 
     float saved_param(int n) const { return frame_mode == 2 ? 1.0f : 1.0f / (float)std::max(n, 1); }     // :1122
@@ -876,6 +934,7 @@ private:
     Convergence conv;
     Noise noise;
     Adaptive adaptive;
+    Denoise denoise;
     int bvh_builder = EVPLP_BVH_SAH;   // measured 9% faster frames than the Morton LBVH on the conference stand-in; "bvhBuilder": "lbvh" selects the LBVH
 };
 
@@ -971,6 +1030,7 @@ extern "C" int evplp_render_json(const char *json_path, const char *json_overrid
         if (!ran) return fail(EVPLP_ERR_PARSE, "no technique block (\"pt\", \"photonfam\", \"lvcphotonfam\") in the scene JSON");
     } catch (const JsonError &e) { return fail(EVPLP_ERR_PARSE, e.what()); }
     catch (const IoError &e) { return fail(EVPLP_ERR_IO, e.what()); }
+    catch (const InvalidError &e) { return fail(EVPLP_ERR_INVALID, e.what()); }
     catch (const std::exception &e) { return fail(EVPLP_ERR_HIP, e.what()); }
     return EVPLP_OK;
 }

@@ -234,7 +234,8 @@ void launch_splat_bin(const SplatArgs &a, hipStream_t s);
 void launch_splat_tiles(const SplatArgs &a, bool split_tiles, hipStream_t s, hipEvent_t dominant_begin, hipEvent_t dominant_end);
 void launch_resolve(const StripDev &st, const float4 *vpl, const float4 *pm, const float4 *light,
                     float vs, float ps, float ls, int mask_emitter, int gamma, float *out_rgb, hipStream_t s);
-void launch_assemble_strips(const StripDev &st, int nranks, const uint32_t *owner, int chunk_rows, const float *gathered, float *frame, hipStream_t s);
+// channels: floats per pixel of the gathered strips and of the frame (3: composites; kDenoiseFloats: evplp_group_denoise's packed pixels)
+void launch_assemble_strips(const StripDev &st, int nranks, const uint32_t *owner, int chunk_rows, const float *gathered, float *frame, hipStream_t s, int channels = 3);
 // EVPLP_PARTITION_ITERATIONS: out = the n planes summed in rank order (fp32, every add rounded), or the first non-zero pixel in rank order
 struct ShardPlanes { const float4 *p[64]; };
 void launch_reduce_shards(const ShardPlanes &src, int n, int first_nonzero, size_t count, float4 *out, int num_cus, hipStream_t s);
@@ -274,5 +275,25 @@ void launch_noise_variance_adaptive(const StripDev &st, const NoiseMoments &m, d
 // fixed tree over the tile's 64 lanes) is <= tau gets the record { n, K, B, 0 } and the snapshot snap = vpl of its pixels
 void launch_adaptive_retire(const StripDev &st, const NoiseMoments &m, double K, double B, double s2K, const float4 *light, float ls, int mask_emitter,
                             const float *rgb, double tau, int4 *tiles, int32_t tiles_x, int32_t tiles_y, int32_t n, const float4 *vpl, float4 *snap, hipStream_t s);
+
+// evplp_denoise (kernels_denoise.hip): one pixel as the a-trous passes read it.  u = (c / albedo, luminance variance s) of a filtered pixel,
+// (composite, 0) of any other; pos.w = 1 for a filtered pixel, 0 otherwise; albedo = max(diffuse + phong, 1e-3); rgb = the composite.
+// 80 B, 20 floats: the strips of a group are exchanged and assembled as floats (assemble_strips_kernel, kDenoiseFloats channels).
+struct DenoisePixel { float4 u, pos, nrm, albedo, rgb; };
+static_assert(sizeof(DenoisePixel) == 80, "DenoisePixel must be 80 bytes");
+constexpr int kDenoiseFloats = (int)(sizeof(DenoisePixel) / sizeof(float));
+// the packed pixels of a context's planes (local rows): rgb = the composite, var = the noise tracker's variance, 3 floats per pixel each;
+// out: [W * local_rows] DenoisePixel
+void launch_denoise_prepare(const StripDev &st, const float *rgb, const float *var, const float4 *pos, const float4 *nrm, const float4 *dif,
+                            const float4 *phg, const float4 *light, float4 *out, hipStream_t s);
+// one a-trous pass over a frame of W x rows packed pixels (rows from the bottom); in: (u, s) every in_step float4, out: a plane of (u', s')
+struct DenoiseLevelArgs {
+    const DenoisePixel *frame; const float4 *in; float4 *out;
+    int32_t W, rows, in_step, h;
+    float sigma_l, sigma_n, sigma_x_r, pad;      // sigma_x_r = sigma_position * the bounding-sphere radius
+};
+void launch_denoise_level(const DenoiseLevelArgs &a, hipStream_t s);
+// out_rgb [n][3]: albedo * u of a filtered pixel, the composite of any other
+void launch_denoise_finish(const DenoisePixel *frame, const float4 *u, size_t n, float *out_rgb, hipStream_t s);
 
 } // namespace evplp

@@ -890,12 +890,13 @@ void launch_reduce_shards(const ShardPlanes &src, int n, int first_nonzero, size
     if (first_nonzero) hipLaunchKernelGGL(reduce_shards_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, src, n, count, out);
     else hipLaunchKernelGGL(reduce_shards_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, src, n, count, out);
 }
-// De-interleave of the all-gathered row strips (evplp_group_resolve): gathered = [n ranks][chunk_rows][W][3] (the rows an exchange moves: <= local_rows), rank r's local row l
-// is image row StripDev{rank r}.global_row(l); frame = [H][W][3].  One thread per float of the frame.
+// De-interleave of the all-gathered row strips (evplp_group_resolve): gathered = [n ranks][chunk_rows][W][channels] (the rows an exchange moves: <= local_rows), rank r's
+// local row l is image row StripDev{rank r}.global_row(l); frame = [H][W][channels].  One thread per float of the frame.  channels: 3 for the composites,
+// kDenoiseFloats for evplp_group_denoise's packed pixels.
 // owner: the dealt blocks of the group (evplp_group_rebalance), owner[b] = rank << 16 | local block of image block b; null = round-robin
-__global__ __launch_bounds__(256) void assemble_strips_kernel(StripDev st, int nranks, const uint32_t *owner, int chunk_rows, const float *gathered, float *frame) {
+__global__ __launch_bounds__(256) void assemble_strips_kernel(StripDev st, int nranks, const uint32_t *owner, int chunk_rows, const float *gathered, float *frame, int channels) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const size_t row_floats = (size_t)st.W * 3, n = row_floats * (size_t)st.H;
+    const size_t row_floats = (size_t)st.W * channels, n = row_floats * (size_t)st.H;
     if (i >= n) return;
     const int y = (int)(i / row_floats); const size_t x = i - (size_t)y * row_floats;
     const int blk = y / st.strip_rows; int r, lb;
@@ -903,9 +904,9 @@ __global__ __launch_bounds__(256) void assemble_strips_kernel(StripDev st, int n
     const int l = lb * st.strip_rows + (y - blk * st.strip_rows);
     frame[i] = gathered[((size_t)r * chunk_rows + l) * row_floats + x];
 }
-void launch_assemble_strips(const StripDev &st, int nranks, const uint32_t *owner, int chunk_rows, const float *gathered, float *frame, hipStream_t s) {
-    const size_t n = (size_t)st.W * 3 * st.H;
-    hipLaunchKernelGGL(assemble_strips_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, st, nranks, owner, chunk_rows, gathered, frame);
+void launch_assemble_strips(const StripDev &st, int nranks, const uint32_t *owner, int chunk_rows, const float *gathered, float *frame, hipStream_t s, int channels) {
+    const size_t n = (size_t)st.W * channels * st.H;
+    hipLaunchKernelGGL(assemble_strips_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, st, nranks, owner, chunk_rows, gathered, frame, channels);
 }
 void launch_fill_zero(void *p, size_t bytes, hipStream_t s) { hipMemsetAsync(p, 0, bytes, s); }
 

@@ -121,6 +121,8 @@ typedef struct evplp_config {
      *   error reference (if set)        12 B + 1 B (mask) per pixel of the WHOLE image on every context (evplp_set_error_reference)
      *   noise tracking (if on)          56 B per pixel of the context's planes (+ 1 B per image pixel with a mask; evplp_noise_track)
      *   adaptive gather (if enabled)    16 B per pixel of the context's planes (snapshot) + 16 B per 8 x 8 tile (evplp_adaptive_enable)
+     *   denoiser (after a call)         124 B per pixel of the context's planes (evplp_denoise); a group's rank: 92 B per pixel of its planes
+     *                                   + n x 80 B per pixel of the exchanged rows, and rank 0 + 112 B per image pixel (evplp_group_denoise)
      * A caller that has the device to itself sets cut_scratch_bytes = 72 GB, vsl_mask_bytes = 14 GB for config #5 (one band, one launch). */
     uint64_t cut_scratch_bytes;
     uint64_t vsl_mask_bytes;
@@ -337,6 +339,32 @@ int evplp_noise_estimate(evplp_context *ctx, float scale, float light_scale, int
 /* The per-pixel variance scale^2 * K * s2 (fp32 per channel) in evplp_resolve's layout: local_rows x W x 3, y = 0 at the bottom.
  * Tracking off or fewer than two folds: EVPLP_ERR_INVALID. */
 int evplp_noise_variance(evplp_context *ctx, float scale, float *out_rgb);
+/* Denoiser of a written frame: the spatial part of SVGF (Schied et al. 2017), an a-trous wavelet filter (Dammertz et al. 2010) of the
+ * composite evplp_noise_estimate describes -- (scale, light_scale, mask_emitter) mean what they mean there, so (1 / N, 1, 0) is the image
+ * a photonfam run saves -- guided by the G-buffer and by the noise tracker's per-pixel variance (evplp_noise_variance at `scale`; with
+ * adaptivity on, the retired tiles' frozen-rescaled variance).  It adds bias: evplp_noise_estimate does not describe the denoised image.
+ * A pixel is filtered when its G-buffer position has w != 0, its light plane is zero in all three channels and it lies in the image; every
+ * other pixel is the composite evplp_resolve(scale, scale, light_scale, mask_emitter, 0) gives, bit for bit, and is never a neighbour.
+ * With c = the composite, v = its variance, a = max(diffuse + phong, 1e-3) per channel: u = c / a, s = sum_ch y_ch^2 v_ch / a_ch^2 with
+ * y = (0.2126, 0.7152, 0.0722) (luminance l(u) = y . u).  Pass i = 0 .. levels - 1 at step h = 2^i: 5 x 5 taps at h (dx, dy), dy outer,
+ * k = b(dx) b(dy) with b = [1, 4, 6, 4, 1] / 16, g_p = the 3 x 3 [1/4, 1/2, 1/4]^2 blur of s over filtered pixels (normalised), and
+ *     w = k exp(-|l_p - l_q| / (sigma_luminance sqrt(g_p) + 1e-10) - |n_p . (x_q - x_p)| / (sigma_position R)) max(0, n_p . n_q)^sigma_normal
+ * (R: evplp_scene_metrics' bounding-sphere radius); u' = sum w u_q / sum w, s' = sum w^2 s_q / (sum w)^2.  Output: a u (linear, no gamma).
+ * Fixed summation order, no atomics: a call is bit-reproducible.  Output layout: evplp_resolve's (local_rows x W x 3, y = 0 at the bottom).
+ * params: NULL or a zero field = the default (levels 5, sigma_luminance 4, sigma_normal 128, sigma_position 0.01).
+ * Refused with EVPLP_ERR_INVALID (the context stays usable): tracking off, fewer than two folds, levels outside 1..10, a negative or
+ * non-finite sigma, a null output, no scene (evplp_build_accel), and a row-strip context (strip_count > 1): a strip cannot see its
+ * neighbours' rows -- evplp_group_denoise filters the whole frame.
+ * Device memory, allocated on the first call and kept until evplp_destroy: 124 B per pixel of the context's planes (variance 12 B, packed
+ * pixel 80 B, two pass planes 32 B). */
+typedef struct evplp_denoise_params {
+    int32_t levels;             /* a-trous passes, 1..10; 0 = 5 */
+    float sigma_luminance;      /* 0 = 4 */
+    float sigma_normal;         /* exponent of the normal term; 0 = 128 */
+    float sigma_position;       /* plane distance in units of the bounding-sphere radius; 0 = 0.01 */
+    int32_t reserved[4];
+} evplp_denoise_params;
+int evplp_denoise(evplp_context *ctx, float scale, float light_scale, int32_t mask_emitter, const evplp_denoise_params *p, float *out_rgb);
 
 /* Adaptive gather: tiles whose estimated noise has converged stop receiving gather work (off by default; a run without it is unchanged).
  * Tile: an 8 x 8 pixel tile of the context's local rows (strip_rows is a multiple of 8: a tile never straddles two row blocks); one decision
@@ -555,6 +583,13 @@ int evplp_group_noise_track(evplp_group *g, int32_t on, const uint8_t *mask_rgb8
 int evplp_group_noise_fold(evplp_group *g, int32_t iterations);
 int evplp_group_noise_estimate(evplp_group *g, float scale, float light_scale, int32_t mask_emitter, double out[3]);
 int evplp_group_noise_variance(evplp_group *g, float scale, float *out_rgb);
+/* evplp_denoise for the whole frame, in evplp_group_resolve's layout, filtered on rank 0's GPU.  EVPLP_PARTITION_STRIPS: every rank packs
+ * its rows (composite, variance, guides) and the packed rows are all-gathered and assembled as a resolve's strips are (80 B per pixel, and
+ * n x a rank's rows on every rank); the inputs do not depend on the partition, so the output equals one context's over the same frame, bit for
+ * bit, for any block table.  EVPLP_PARTITION_ITERATIONS: the composite and the light plane of evplp_group_resolve's reduction, the variance of
+ * the pooled moments (evplp_group_noise_variance), and the guides of the rank that ran the last evplp_group_primary.  Device memory: see
+ * the table of evplp_config.  Refusals as evplp_denoise's (strip_count aside), on the caller's thread; the group stays usable. */
+int evplp_group_denoise(evplp_group *g, float scale, float light_scale, int32_t mask_emitter, const evplp_denoise_params *p, float *out_rgb);
 /* evplp_adaptive_* for a group.  EVPLP_PARTITION_STRIPS: every rank decides for its own tiles, the retire call returns the sum of the ranks'
  * counts, and the tile map is assembled from the block owners (the whole image).  EVPLP_PARTITION_ITERATIONS: every call is refused --
  * pooling the ranks' decisions is not supported.  Refusals come on the caller's thread and leave the group usable. */
