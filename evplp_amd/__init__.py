@@ -134,6 +134,7 @@ _SIGNATURES = {
     "evplp_noise_variance": (C.c_int, [_P, C.c_float, _P]),
     "evplp_denoise": (C.c_int, [_P, C.c_float, C.c_float, C.c_int32, C.POINTER(DenoiseParams), _P]),
     "evplp_adaptive_enable": (C.c_int, [_P, C.c_int32]),
+    "evplp_adaptive_enable_pt": (C.c_int, [_P, C.c_int32]),
     "evplp_adaptive_retire": (C.c_int, [_P, C.c_float, C.c_float, C.c_int32, C.c_double, C.c_int32]),
     "evplp_adaptive_tiles": (C.c_int, [_P, _P, C.c_int32]),
     "evplp_clear_accumulators": (C.c_int, [_P]),
@@ -189,6 +190,7 @@ _SIGNATURES = {
     "evplp_group_noise_variance": (C.c_int, [_P, C.c_float, _P]),
     "evplp_group_denoise": (C.c_int, [_P, C.c_float, C.c_float, C.c_int32, C.POINTER(DenoiseParams), _P]),
     "evplp_group_adaptive_enable": (C.c_int, [_P, C.c_int32]),
+    "evplp_group_adaptive_enable_pt": (C.c_int, [_P, C.c_int32]),
     "evplp_group_adaptive_retire": (C.c_int, [_P, C.c_float, C.c_float, C.c_int32, C.c_double, C.c_int32]),
     "evplp_group_adaptive_tiles": (C.c_int, [_P, _P, C.c_int32]),
     "evplp_jitter_sequence": (C.c_int, [C.c_uint32, C.c_int32, C.c_int32, C.c_int32, _P]),
@@ -540,9 +542,11 @@ class Context:
         self._check(self._lib.evplp_denoise(self._h, float(scale), float(light_scale), int(mask_emitter), C.byref(p), _ptr(out)))
         return out
 
-    def adaptive_enable(self, on=True):
-        """Switch the adaptive gather on or off (before the first accumulating gather since the last clear; needs noise tracking; include/evplp.h)"""
-        self._check(self._lib.evplp_adaptive_enable(self._h, int(bool(on))))
+    def adaptive_enable(self, on=True, path_trace=False):
+        """Switch the adaptive gather on or off (before the first accumulating gather since the last clear; needs noise tracking; include/evplp.h).
+        path_trace=True: path-trace mode instead (evplp_adaptive_enable_pt) -- path_trace() honours retirement and the gathers are refused"""
+        f = self._lib.evplp_adaptive_enable_pt if path_trace else self._lib.evplp_adaptive_enable
+        self._check(f(self._h, int(bool(on))))
 
     def adaptive_retire(self, scale, tile_rel_mse, min_batches=2, light_scale=1.0, mask_emitter=False) -> int:
         """retire the active tiles whose mean relative variance of scale * sums + light_scale * light is <= tile_rel_mse; returns how many"""
@@ -725,6 +729,10 @@ class Group:
     def gather(self, fp, kind=0):
         self._check(self._lib.evplp_group_gather(self._h, C.byref(fp), kind))
 
+    def path_trace(self, camera_pos, rng_seed: int, max_bounces: int, accumulate=True):
+        cp = (C.c_float * 3)(*[float(v) for v in camera_pos])
+        self._check(self._lib.evplp_group_path_trace(self._h, C.byref(cp), rng_seed, max_bounces, int(accumulate)))
+
     def splat_photons(self, fp, clear=False):
         self._check(self._lib.evplp_group_splat_photons(self._h, C.byref(fp), int(clear)))
 
@@ -831,9 +839,11 @@ class Group:
         self._check(self._lib.evplp_group_denoise(self._h, float(scale), float(light_scale), int(mask_emitter), C.byref(p), _ptr(out)))
         return out
 
-    def adaptive_enable(self, on=True):
-        """Switch the adaptive gather on or off (before the first accumulating gather since the last clear; needs noise tracking; include/evplp.h)"""
-        self._check(self._lib.evplp_group_adaptive_enable(self._h, int(bool(on))))
+    def adaptive_enable(self, on=True, path_trace=False):
+        """Switch the adaptive gather on or off (before the first accumulating gather since the last clear; needs noise tracking; include/evplp.h).
+        path_trace=True: path-trace mode instead (evplp_group_adaptive_enable_pt) -- path_trace() honours retirement and gather() is refused"""
+        f = self._lib.evplp_group_adaptive_enable_pt if path_trace else self._lib.evplp_group_adaptive_enable
+        self._check(f(self._h, int(bool(on))))
 
     def adaptive_retire(self, scale, tile_rel_mse, min_batches=2, light_scale=1.0, mask_emitter=False) -> int:
         """retire the active tiles whose mean relative variance of scale * sums + light_scale * light is <= tile_rel_mse; returns how many"""

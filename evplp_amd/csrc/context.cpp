@@ -728,6 +728,7 @@ static int run_gather(evplp_context *c, const evplp_frame_params *fp, bool vsl) 
     int rc = pass_ready(c, name, false); if (rc) return rc;
     if ((rc = check_fp(c, fp, name))) return rc;
     if (fp->num_vpl_light_paths == 0) { c->set_error("%s: num_vpl_light_paths is 0 (the reference disables the pass, rtcomphoton.h:200-203)", name); return EVPLP_ERR_INVALID; }
+    if (c->adapt_pt) { c->set_error("%s: adaptivity is on in path-trace mode (evplp_adaptive_enable_pt): evplp_path_trace only", name); return EVPLP_ERR_INVALID; }
     if (c->d_adapt_tiles && fp->do_accumulate == 0) { c->set_error("%s: adaptivity is on (evplp_adaptive_enable): a gather must accumulate", name); return EVPLP_ERR_INVALID; }
     GatherArgs a; fill_gather_args(c, fp, a, pass);
     // adaptivity (evplp_adaptive_enable): retired tiles' items end at once and the reduce writes their pixels from the snapshot.  A calibration
@@ -859,6 +860,7 @@ extern "C" int evplp_gather_vsl(evplp_context *c, const evplp_frame_params *fp) 
 extern "C" int evplp_gather_lvc(evplp_context *c, const evplp_frame_params *fp) {
     CTX_CHECK(c);
     const int pass = EVPLP_PASS_GATHER_LVC;
+    if (c->adapt_pt) { c->set_error("evplp_gather_lvc: adaptivity is on in path-trace mode (evplp_adaptive_enable_pt): evplp_path_trace only"); return EVPLP_ERR_INVALID; }
     if (c->d_adapt_tiles) { c->set_error("evplp_gather_lvc: adaptivity is on (evplp_adaptive_enable): VPL and VSL gathers only"); return EVPLP_ERR_INVALID; }
     int rc = pass_ready(c, "evplp_gather_lvc", false); if (rc) return rc;
     if ((rc = check_fp(c, fp, "evplp_gather_lvc"))) return rc;
@@ -871,7 +873,8 @@ extern "C" int evplp_gather_lvc(evplp_context *c, const evplp_frame_params *fp) 
 
 extern "C" int evplp_path_trace(evplp_context *c, const float camera_pos[3], uint32_t rng_seed, uint32_t max_bounces, int32_t do_accumulate) {
     CTX_CHECK(c);
-    if (c->d_adapt_tiles) { c->set_error("evplp_path_trace: adaptivity is on (evplp_adaptive_enable): VPL and VSL gathers only"); return EVPLP_ERR_INVALID; }
+    if (c->d_adapt_tiles && !c->adapt_pt) { c->set_error("evplp_path_trace: adaptivity is on (evplp_adaptive_enable): VPL and VSL gathers only"); return EVPLP_ERR_INVALID; }
+    if (c->adapt_pt && !do_accumulate) { c->set_error("evplp_path_trace: adaptivity is on (evplp_adaptive_enable_pt): a sample must accumulate"); return EVPLP_ERR_INVALID; }
     int rc = pass_ready(c, "evplp_path_trace", false); if (rc) return rc;
     if (!camera_pos) { c->set_error("evplp_path_trace: null camera position"); return EVPLP_ERR_INVALID; }
     PathTraceArgs a; std::memset(&a, 0, sizeof(a));
@@ -883,8 +886,13 @@ extern "C" int evplp_path_trace(evplp_context *c, const float camera_pos[3], uin
     a.out = (float4 *)c->buf[EVPLP_BUF_VPL_ACCUM];
     a.counters = &c->d_counters[EVPLP_PASS_PATH_TRACE];
     if ((rc = pass_begin(c, EVPLP_PASS_PATH_TRACE))) return rc;
-    launch_path_trace(a, c->stream);
-    return pass_end(c, EVPLP_PASS_PATH_TRACE);
+    // path-trace mode (evplp_adaptive_enable_pt): retired tiles trace nothing and are written from the snapshot
+    AdaptArgs ad{};
+    if (c->adapt_pt) { ad.tiles = c->d_adapt_tiles; ad.snap = c->d_adapt_snap; ad.n1 = (int32_t)(c->adapt_n + 1); }
+    launch_path_trace(a, c->stream, ad);
+    if ((rc = pass_end(c, EVPLP_PASS_PATH_TRACE))) return rc;
+    if (do_accumulate) c->adapt_n++;
+    return EVPLP_OK;
 }
 
 // setupPhotonSplatIcosohedron (rtcomphoton.h:632-644): the proxy mesh of EVPLP_FOOTPRINT_PROXY -> slabs on the device
@@ -1307,7 +1315,7 @@ extern "C" int evplp_denoise(evplp_context *c, float scale, float ls, int32_t ma
 // ---- adaptive gather: tiles retire once their estimated noise is low enough (include/evplp.h evplp_adaptive_*)
 static void release_adapt(evplp_context *c) {
     hipFree(c->d_adapt_tiles); hipFree(c->d_adapt_snap);
-    c->d_adapt_tiles = nullptr; c->d_adapt_snap = nullptr; c->adapt_tiles.clear();
+    c->d_adapt_tiles = nullptr; c->d_adapt_snap = nullptr; c->adapt_tiles.clear(); c->adapt_pt = false;
 }
 static size_t adapt_tile_count(const evplp_context *c) { return (size_t)c->tiles_x * (size_t)c->tiles_y; }
 // every tile active (stream order); the records are (re)allocated when the planes' tiles have changed (a new block table)
@@ -1328,21 +1336,25 @@ static int adapt_reset(evplp_context *c) {
     HIP_TRY(c, hipMemsetAsync(c->d_adapt_tiles, 0, sizeof(int4) * std::max<size_t>(nt, 1), c->stream));
     return EVPLP_OK;
 }
-extern "C" int evplp_adaptive_enable(evplp_context *c, int32_t on) {
-    CTX_CHECK(c);
+// pt: path-trace mode (evplp_adaptive_enable_pt) -- the same records and snapshot; what differs is the pass that honours them
+static int adaptive_enable_mode(evplp_context *c, int32_t on, bool pt, const char *name) {
     if (c->adapt_n > 0) {
-        c->set_error("evplp_adaptive_enable: %lld gather(s) have accumulated since the last clear: switch adaptivity before the first", (long long)c->adapt_n);
+        c->set_error("%s: %lld gather(s) have accumulated since the last clear: switch adaptivity before the first", name, (long long)c->adapt_n);
         return EVPLP_ERR_INVALID;
     }
-    if (on && !c->d_noise) { c->set_error("evplp_adaptive_enable: noise tracking is off (evplp_noise_track): retirement needs its estimate"); return EVPLP_ERR_INVALID; }
+    if (on && !c->d_noise) { c->set_error("%s: noise tracking is off (evplp_noise_track): retirement needs its estimate", name); return EVPLP_ERR_INVALID; }
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     if (!on) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         release_adapt(c);
         return EVPLP_OK;
     }
-    return adapt_reset(c);
+    const int rc = adapt_reset(c);
+    if (rc == EVPLP_OK) c->adapt_pt = pt;
+    return rc;
 }
+extern "C" int evplp_adaptive_enable(evplp_context *c, int32_t on) { CTX_CHECK(c); return adaptive_enable_mode(c, on, false, "evplp_adaptive_enable"); }
+extern "C" int evplp_adaptive_enable_pt(evplp_context *c, int32_t on) { CTX_CHECK(c); return adaptive_enable_mode(c, on, true, "evplp_adaptive_enable_pt"); }
 extern "C" int evplp_adaptive_retire(evplp_context *c, float scale, float ls, int32_t mask_emitter, double tau, int32_t min_batches) {
     CTX_CHECK(c);
     if (!c->d_adapt_tiles) { c->set_error("evplp_adaptive_retire: adaptivity is off (evplp_adaptive_enable)"); return EVPLP_ERR_INVALID; }

@@ -151,11 +151,12 @@ struct evplp_context {
     char *d_noise = nullptr; size_t noise_stride = 0; uint8_t *d_noise_keep = nullptr;
     evplp::RowError *d_noise_rows = nullptr; std::vector<evplp::RowError> noise_rows;
     int64_t noise_k = 0, noise_b = 0;
-    // evplp_adaptive_*: adapt_n = N, the accumulating gather calls since the accumulators were last cleared (counted whether adaptivity is on
+    // evplp_adaptive_*: adapt_n = N, the accumulating gather and path-tracing calls since the accumulators were last cleared (counted whether adaptivity is on
     // or not); the tile records [tiles_x * tiles_y] (kernels.h AdaptTiles; null: adaptivity is off), their host copy (they change only in
     // evplp_adaptive_retire and at a clear), the retired pixels' snapshot of VPL_ACCUM [W * local_rows]; adapt_last: tiles retired by the
     // last evplp_adaptive_retire (the group's workers leave it here)
     int64_t adapt_n = 0; int4 *d_adapt_tiles = nullptr; float4 *d_adapt_snap = nullptr; std::vector<int4> adapt_tiles; int32_t adapt_last = 0;
+    bool adapt_pt = false;          // evplp_adaptive_enable_pt: evplp_path_trace owns the retirement (the gathers are refused)
     // evplp_denoise: the variance image [W * local_rows][3], the packed pixels of the planes [W * local_rows] (kernels.h DenoisePixel), and
     // the two (u, s) planes of the a-trous passes [2][dn_u_px] (the frame the context filters: its planes, or a group's whole image on rank 0);
     // allocated on the first call, kept until evplp_destroy

@@ -131,6 +131,7 @@ struct evplp_group {
     bool have_reference = false;            // evplp_group_set_error_reference has given every rank an image (caller's thread)
     bool noise_on = false;                  // evplp_group_noise_track is on on every rank (caller's thread)
     bool adapt_on = false;                  // evplp_group_adaptive_enable is on on every rank (caller's thread)
+    bool adapt_pt = false;                  // ... and in path-trace mode (evplp_group_adaptive_enable_pt)
     // EVPLP_PARTITION_ITERATIONS, evplp_group_noise_*: rank 0's pooled moments (Q then S, [3][stride] fp64 each) and K / B summed over the
     // ranks (written by rank 0's worker); RCCL only: per rank [n][noise_bytes] every rank's NoisePlanes (all-gathered)
     double *d_noise_pool = nullptr; double pool_k = 0.0, pool_b = 0.0;
@@ -406,7 +407,7 @@ static void worker_run(Worker *w, const Cmd &cmd) {
             if (cmd.i[1]) rc = evplp::noise_rows(c, noise_pooled(g, c), g->d_sum[0] + 2 * g->plane_px, g->pool_k, g->pool_b, cmd.f[0], cmd.f[1], cmd.i[0]);
             else rc = evplp::noise_rows(c, evplp::noise_moments_of(c), (const float4 *)c->buf[EVPLP_BUF_LIGHT], (double)c->noise_k, (double)c->noise_b, cmd.f[0], cmd.f[1], cmd.i[0]);
             break;
-        case OP_ADAPT_ENABLE: rc = evplp_adaptive_enable(c, cmd.i[0]); break;
+        case OP_ADAPT_ENABLE: rc = cmd.i[1] ? evplp_adaptive_enable_pt(c, cmd.i[0]) : evplp_adaptive_enable(c, cmd.i[0]); break;
         // (the count of tiles it retired stays in c->adapt_last)
         case OP_ADAPT_RETIRE: rc = evplp_adaptive_retire(c, cmd.f[0], cmd.f[1], cmd.i[0], cmd.d, cmd.i[1]); if (rc > 0) rc = EVPLP_OK; break;
         case OP_NOISE_VARIANCE:
@@ -755,6 +756,7 @@ extern "C" int evplp_group_gather(evplp_group *g, const evplp_frame_params *fp, 
     if (kind < 0 || kind > 2) { g->set_error("evplp_group_gather: kind must be 0 (VPL), 1 (VSL) or 2 (light-path windows)"); return EVPLP_ERR_INVALID; }
     if (!fp) { g->set_error("evplp_group_gather: null frame params"); return EVPLP_ERR_INVALID; }
     { int rc = check_frame_params(g, fp, "evplp_group_gather", false); if (rc < 0) return rc; }
+    if (g->adapt_pt) { g->set_error("evplp_group_gather: adaptivity is on in path-trace mode (evplp_group_adaptive_enable_pt): evplp_group_path_trace only"); return EVPLP_ERR_INVALID; }
     if (g->adapt_on && (kind == 2 || fp->do_accumulate == 0)) {
         g->set_error("evplp_group_gather: adaptivity is on (evplp_group_adaptive_enable): accumulating VPL and VSL gathers only"); return EVPLP_ERR_INVALID;
     }
@@ -776,7 +778,8 @@ extern "C" int evplp_group_set_splat_proxy(evplp_group *g, const float *vertices
 extern "C" int evplp_group_path_trace(evplp_group *g, const float camera_pos[3], uint32_t rng_seed, uint32_t max_bounces, int32_t do_accumulate) {
     GRP_CHECK(g);
     if (!camera_pos) { g->set_error("evplp_group_path_trace: null camera position"); return EVPLP_ERR_INVALID; }
-    if (g->adapt_on) { g->set_error("evplp_group_path_trace: adaptivity is on (evplp_group_adaptive_enable): VPL and VSL gathers only"); return EVPLP_ERR_INVALID; }
+    if (g->adapt_on && !g->adapt_pt) { g->set_error("evplp_group_path_trace: adaptivity is on (evplp_group_adaptive_enable): VPL and VSL gathers only"); return EVPLP_ERR_INVALID; }
+    if (g->adapt_pt && !do_accumulate) { g->set_error("evplp_group_path_trace: adaptivity is on (evplp_group_adaptive_enable_pt): a sample must accumulate"); return EVPLP_ERR_INVALID; }
     Cmd c; c.op = OP_PATH_TRACE; c.f[0] = camera_pos[0]; c.f[1] = camera_pos[1]; c.f[2] = camera_pos[2]; c.u[0] = rng_seed; c.u[1] = max_bounces; c.i[0] = do_accumulate;
     return post_pass(g, c);
 }
@@ -997,18 +1000,20 @@ static int adapt_group_ready(evplp_group *g, const char *name) {
     drain(g);
     return group_status(g);
 }
-extern "C" int evplp_group_adaptive_enable(evplp_group *g, int32_t on) {
-    GRP_CHECK(g);
-    int rc = adapt_group_ready(g, "evplp_group_adaptive_enable");
+static int group_adaptive_enable(evplp_group *g, int32_t on, bool pt, const char *name) {
+    int rc = adapt_group_ready(g, name);
     if (rc < 0) return rc;
     for (evplp_context *c : g->ctx)
-        if (c->adapt_n > 0) { g->set_error("evplp_group_adaptive_enable: %lld gather(s) have accumulated since the last clear", (long long)c->adapt_n); return EVPLP_ERR_INVALID; }
-    if (on && !g->noise_on) { g->set_error("evplp_group_adaptive_enable: noise tracking is off (evplp_group_noise_track)"); return EVPLP_ERR_INVALID; }
-    Cmd c; c.op = OP_ADAPT_ENABLE; c.i[0] = on;
+        if (c->adapt_n > 0) { g->set_error("%s: %lld gather(s) have accumulated since the last clear", name, (long long)c->adapt_n); return EVPLP_ERR_INVALID; }
+    if (on && !g->noise_on) { g->set_error("%s: noise tracking is off (evplp_group_noise_track)", name); return EVPLP_ERR_INVALID; }
+    Cmd c; c.op = OP_ADAPT_ENABLE; c.i[0] = on; c.i[1] = pt ? 1 : 0;
     rc = post_and_wait(g, c);
     g->adapt_on = rc >= 0 && on != 0;
+    g->adapt_pt = g->adapt_on && pt;
     return rc;
 }
+extern "C" int evplp_group_adaptive_enable(evplp_group *g, int32_t on) { GRP_CHECK(g); return group_adaptive_enable(g, on, false, "evplp_group_adaptive_enable"); }
+extern "C" int evplp_group_adaptive_enable_pt(evplp_group *g, int32_t on) { GRP_CHECK(g); return group_adaptive_enable(g, on, true, "evplp_group_adaptive_enable_pt"); }
 extern "C" int evplp_group_adaptive_retire(evplp_group *g, float scale, float ls, int32_t mask_emitter, double tau, int32_t min_batches) {
     GRP_CHECK(g);
     int rc = adapt_group_ready(g, "evplp_group_adaptive_retire");

@@ -490,39 +490,44 @@ private:
 // once the tracker has >= minBatches (default 2, >= 2) folds.  Needs the "noise" block, whose checkpoints then carry "retiredTiles" /
 // "activeTiles"; refused for lvcphotonfam and pt, under "partition": "iterations" and with frameMode "cleareveryframe".  iterationsFilename:
 // every pixel's n_t / N (1 where its tile never retired), rows top to bottom.  Everything is validated before the group exists.
+// pt takes the same block under the key "adaptiveSampling" (the path tracer retires the tiles; its loop ends once none is active).
 class Adaptive {
 public:
+    // key: "adaptive" (photonfam: the gathers retire tiles) or "adaptiveSampling" (pt: the path tracer does, evplp_group_adaptive_enable_pt)
+    explicit Adaptive(const char *block_key = "adaptive", bool path_trace = false) : key(block_key), pt(path_trace) {}
     bool on = false;
+    // pt: no tile is active any more -- the loop has nothing left to sample
+    bool all_retired(const Noise &noise) const { return on && noise.image_tiles > 0 && noise.retired_tiles >= noise.image_tiles; }
     void parse(const Json &tech, const std::string &out_dir, int frame_mode, bool lvc, bool iterations_partition, Noise &noise) {
-        if (!tech.has("adaptive")) return;
-        const Json &c = tech.at("adaptive");
-        if (!c.is_object()) throw JsonError("adaptive: expected an object");
-        if (lvc) throw JsonError("adaptive: not for lvcphotonfam (VPL and VSL gathers only)");
-        if (!noise.on) throw JsonError("adaptive: needs a \"noise\" block (retirement uses its estimate)");
-        if (frame_mode == 2) throw JsonError("adaptive: frameMode \"cleareveryframe\" keeps no running sum");
-        if (iterations_partition) throw JsonError("adaptive: not under \"partition\": \"iterations\" (the ranks' decisions are not pooled)");
-        if (!c.has("tileRelMse")) throw JsonError("adaptive.tileRelMse: missing required key");
-        tau = c.at("tileRelMse").as_number("adaptive.tileRelMse");
-        if (!(tau >= 0.0)) throw JsonError("adaptive.tileRelMse: must be >= 0");
+        if (!tech.has(key)) return;
+        const Json &c = tech.at(key);
+        if (!c.is_object()) throw JsonError(key + ": expected an object");
+        if (lvc) throw JsonError(key + ": not for lvcphotonfam (VPL and VSL gathers only)");
+        if (!noise.on) throw JsonError(key + ": needs a \"noise\" block (retirement uses its estimate)");
+        if (frame_mode == 2) throw JsonError(key + ": frameMode \"cleareveryframe\" keeps no running sum");
+        if (iterations_partition) throw JsonError(key + ": not under \"partition\": \"iterations\" (the ranks' decisions are not pooled)");
+        if (!c.has("tileRelMse")) throw JsonError(key + ".tileRelMse: missing required key");
+        tau = c.at("tileRelMse").as_number((key + ".tileRelMse").c_str());
+        if (!(tau >= 0.0)) throw JsonError(key + ".tileRelMse: must be >= 0");
         every = noise.batch_iterations();
         if (c.has("everyIterations")) {
-            every = c.at("everyIterations").as_int("adaptive.everyIterations");
-            if (every <= 0) throw JsonError("adaptive.everyIterations: must be > 0");
-            if (every % noise.batch_iterations() != 0) throw JsonError("adaptive.everyIterations: must be a multiple of noise.batchIterations");
+            every = c.at("everyIterations").as_int((key + ".everyIterations").c_str());
+            if (every <= 0) throw JsonError(key + ".everyIterations: must be > 0");
+            if (every % noise.batch_iterations() != 0) throw JsonError(key + ".everyIterations: must be a multiple of noise.batchIterations");
         }
         if (c.has("minBatches")) {
-            const long long mb = c.at("minBatches").as_int("adaptive.minBatches");
-            if (mb < 2 || mb > INT32_MAX) throw JsonError("adaptive.minBatches: must be >= 2");
+            const long long mb = c.at("minBatches").as_int((key + ".minBatches").c_str());
+            if (mb < 2 || mb > INT32_MAX) throw JsonError(key + ".minBatches: must be >= 2");
             min_batches = (int32_t)mb;
         }
-        if (c.has("iterationsFilename")) iterations_filename = output_path(out_dir, c.at("iterationsFilename").as_string("adaptive.iterationsFilename"));
+        if (c.has("iterationsFilename")) iterations_filename = output_path(out_dir, c.at("iterationsFilename").as_string((key + ".iterationsFilename").c_str()));
         noise.adaptive = true;
         on = true;
     }
     // before the loop's first gather (after the clear and any rebalance: N = 0)
     void start(evplp_group *g, int W, int H, Noise &noise) {
         if (!on) return;
-        check(g, evplp_group_adaptive_enable(g, 1), "adaptive");
+        check(g, pt ? evplp_group_adaptive_enable_pt(g, 1) : evplp_group_adaptive_enable(g, 1), key.c_str());
         noise.image_tiles = (long long)((W + 7) / 8) * ((H + 7) / 8);
     }
     // after the fold of iteration i (folded_now): the retirement, when due
@@ -548,6 +553,7 @@ public:
     }
 
 private:
+    std::string key; bool pt;
     double tau = 0.0;
     long long every = 1;
     int32_t min_batches = 2;
@@ -581,8 +587,11 @@ public:
         if (json.has("bvhBuilder")) bvh_builder = parse_bvh_builder(json.at("bvhBuilder").as_string("bvhBuilder"));
         conv.parse(json, out_dir, out_dir, res_x, res_y);
         denoise.parse(json, out_dir, frame_mode);
+        // (before Noise::parse, as Denoise::parse: a "cleareveryframe" run with both blocks is refused under this block's name)
+        if (frame_mode == 2 && json.has("adaptiveSampling")) throw JsonError("adaptiveSampling: frameMode \"cleareveryframe\" keeps no running sum");
         noise.parse(json, out_dir, out_dir, res_x, res_y, frame_mode);
-        if (json.has("adaptive")) throw JsonError("adaptive: not for pt (VPL and VSL gathers only)");
+        if (json.has("adaptive")) throw JsonError("adaptive: not for pt (VPL and VSL gathers only; pt takes \"adaptiveSampling\")");
+        adaptive.parse(json, out_dir, frame_mode, false, run_options(json).shard_iterations, noise);                // build-only key "adaptiveSampling"
 
         evplp_config cfg; std::memset(&cfg, 0, sizeof(cfg));
         cfg.abi_version = EVPLP_ABI_VERSION; cfg.device = device; cfg.res_x = res_x; cfg.res_y = res_y;
@@ -601,6 +610,7 @@ private:
         JitterSampler sampler(rng_offset);
         check(h, evplp_group_clear_accumulators(h), "clear");
         noise.start(h, 1);
+        adaptive.start(h, W, H, noise);
         int num_iterations = 0;
         auto t0 = std::chrono::steady_clock::now();
         auto elapsed_ms = [&]() { return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
@@ -626,8 +636,10 @@ private:
             if (noise.on) {
                 const bool folded = noise.after_iteration(h, 0);
                 const Composite k = composite(num_iterations);
+                adaptive.after_fold(h, num_iterations, folded, k.vs, noise);
                 if (noise.due(num_iterations, elapsed_ms(), folded) &&
                     noise.checkpoint(h, num_iterations, [&] { check(h, evplp_group_synchronize(h), "sync"); return (double)elapsed_ms(); }, k.vs, k.ls, k.mask_emitter)) break;
+                if (adaptive.all_retired(noise)) break;                                       // every tile retired: nothing left to sample
             }
             if (elapsed_ms() >= time_limit_ms) break;                                         // :667
         }
@@ -644,6 +656,7 @@ private:
             of << st.dump() << "\n";
         }
         save(h, W, H, num_iterations, output_filename, rgb);                                  // :706-719
+        adaptive.finish(h, num_iterations, W, H);
         { const Composite k = composite(num_iterations); denoise.write(h, W, H, noise.batch_count(), k.vs, k.ls, k.mask_emitter); }
     }
     // clear-every-frame: the composite as shown (masked emitter); accumulate: light image + path-traced image / n
@@ -663,6 +676,7 @@ private:
     Convergence conv;
     Noise noise;
     Denoise denoise;
+    Adaptive adaptive{"adaptiveSampling", true};
 };
 
 class ComPhotonTechnique {

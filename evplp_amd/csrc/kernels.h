@@ -228,7 +228,7 @@ void launch_gather_vsl(const GatherArgs &a, hipStream_t s, const AdaptArgs &ad =
 int gather_launch_tiles(const GatherArgs &a);                      // tiles a gather launch enumerates (whole blocks)
 void launch_gather_reduce(const GatherArgs &a, int stencil_test, hipStream_t s, const AdaptArgs &ad = AdaptArgs{});
 void launch_gather_lvc(const GatherArgs &a, const evplp_record *records, hipStream_t s);
-void launch_path_trace(const PathTraceArgs &a, hipStream_t s);
+void launch_path_trace(const PathTraceArgs &a, hipStream_t s, const AdaptArgs &ad = AdaptArgs{});     // ad.tiles set: evplp_adaptive_enable_pt's variant
 // binning (tile depth ranges, compact photons + bin fill, summary); then the per-tile accumulation
 void launch_splat_bin(const SplatArgs &a, hipStream_t s);
 void launch_splat_tiles(const SplatArgs &a, bool split_tiles, hipStream_t s, hipEvent_t dominant_begin, hipEvent_t dominant_end);

@@ -155,7 +155,12 @@ EV_DEV unsigned long long path_trace_pixel(const PathTraceArgs &a, int x, int y,
 #ifndef EVPLP_PT_WAVES
 #define EVPLP_PT_WAVES 4   // 128 VGPRs, zero scratch (126 needed): 1.61 ms per sample per pixel at 1024^2 against 1.59 ms at 6 waves with 65 spilled registers
 #endif
-__global__ __launch_bounds__(64, EVPLP_PT_WAVES) void path_trace_kernel(PathTraceArgs a) {
+// ADAPT (evplp_adaptive_enable_pt): one wave-uniform scalar read of the tile's record (kernels.h AdaptTiles; .x = n_t, 0: active) right after
+// the tile index is known.  A retired tile reads neither the G-buffer nor the LDS stack, traces nothing and adds nothing to the counters: its
+// pixels inside the strip -- whatever the stencil says -- become the snapshot R extrapolated to N + 1 iterations, in gather_reduce_kernel<true>'s
+// arithmetic: (float)(R * ((N + 1) / n_t)) per channel in fp64.  An active tile runs as in the default; ad is read by this variant only.
+template <bool ADAPT = false>
+__global__ __launch_bounds__(64, EVPLP_PT_WAVES) void path_trace_kernel(PathTraceArgs a, AdaptArgs ad) {
     extern __shared__ int32_t lds_stack[];   // [bvh_depth + 2][64 lanes]
     const int lane = threadIdx.x;
     const int tiles_x = (a.st.W + 7) >> 3;
@@ -166,6 +171,18 @@ __global__ __launch_bounds__(64, EVPLP_PT_WAVES) void path_trace_kernel(PathTrac
     const int y = a.st.global_row(min(ly, a.st.local_rows - 1));
     const bool in_image = x < a.st.W && ly < a.st.local_rows && y < a.st.H;
     const size_t p = (size_t)min(ly, a.st.local_rows - 1) * a.st.W + min(x, a.st.W - 1);
+    if constexpr (ADAPT) {
+        const int nt = __builtin_amdgcn_readfirstlane(ad.tiles[tile].x);
+        if (nt != 0) {
+            if (in_image) {
+                const float4 R = ad.snap[p];
+                const double f = __ddiv_rn((double)ad.n1, (double)nt);
+                a.out[p] = make_float4(__double2float_rn(__dmul_rn((double)R.x, f)), __double2float_rn(__dmul_rn((double)R.y, f)),
+                                       __double2float_rn(__dmul_rn((double)R.z, f)), __double2float_rn(__dmul_rn((double)R.w, f)));
+            }
+            return;
+        }
+    }
     const float4 gp = a.g_pos[p];
     const bool valid = in_image && gp.w != 0.0f;                          // stencil (:357)
     unsigned long long rays = 0, paths = valid ? 1ull : 0ull;
@@ -175,10 +192,13 @@ __global__ __launch_bounds__(64, EVPLP_PT_WAVES) void path_trace_kernel(PathTrac
     if (lane == 0 && a.counters && paths) { atomicAdd(&a.counters->rays, rays); atomicAdd(&a.counters->pairs, paths); }
 }
 
-void launch_path_trace(const PathTraceArgs &a, hipStream_t s) {
+// ad.tiles set: the ADAPT variant (evplp_path_trace in path-trace mode); the same tile grid either way
+void launch_path_trace(const PathTraceArgs &a, hipStream_t s, const AdaptArgs &ad) {
     int tiles_x = (a.st.W + 7) / 8, tiles_y = (a.st.local_rows + 7) / 8;
     if (tiles_x * tiles_y == 0) return;
-    hipLaunchKernelGGL(path_trace_kernel, dim3(tiles_x * tiles_y), dim3(64), EVPLP_PT_WIDE ? lane_stack_bytes4(a.sc) : lane_stack_bytes(a.sc), s, a);
+    const size_t lds = EVPLP_PT_WIDE ? lane_stack_bytes4(a.sc) : lane_stack_bytes(a.sc);
+    if (ad.tiles) hipLaunchKernelGGL(path_trace_kernel<true>, dim3(tiles_x * tiles_y), dim3(64), lds, s, a, ad);
+    else hipLaunchKernelGGL(path_trace_kernel<false>, dim3(tiles_x * tiles_y), dim3(64), lds, s, a, ad);
 }
 
 } // namespace evplp

@@ -120,7 +120,8 @@ typedef struct evplp_config {
      *   scene (331 k triangles)         0.1 GB everywhere (nodes, leaf blocks in two layouts, attributes; textures on top)
      *   error reference (if set)        12 B + 1 B (mask) per pixel of the WHOLE image on every context (evplp_set_error_reference)
      *   noise tracking (if on)          56 B per pixel of the context's planes (+ 1 B per image pixel with a mask; evplp_noise_track)
-     *   adaptive gather (if enabled)    16 B per pixel of the context's planes (snapshot) + 16 B per 8 x 8 tile (evplp_adaptive_enable)
+     *   adaptive gather (if enabled)    16 B per pixel of the context's planes (snapshot) + 16 B per 8 x 8 tile (evplp_adaptive_enable; the same for
+     *                                   adaptive path tracing, evplp_adaptive_enable_pt: one mode at a time, one allocation)
      *   denoiser (after a call)         124 B per pixel of the context's planes (evplp_denoise); a group's rank: 92 B per pixel of its planes
      *                                   + n x 80 B per pixel of the exchanged rows, and rank 0 + 112 B per image pixel (evplp_group_denoise)
      * A caller that has the device to itself sets cut_scratch_bytes = 72 GB, vsl_mask_bytes = 14 GB for config #5 (one band, one launch). */
@@ -368,8 +369,8 @@ int evplp_denoise(evplp_context *ctx, float scale, float light_scale, int32_t ma
 
 /* Adaptive gather: tiles whose estimated noise has converged stop receiving gather work (off by default; a run without it is unchanged).
  * Tile: an 8 x 8 pixel tile of the context's local rows (strip_rows is a multiple of 8: a tile never straddles two row blocks); one decision
- * per tile, independent of the partition.  N: the context's accumulating gather calls (evplp_gather_vpl / _vsl with do_accumulate != 0)
- * since the accumulators were last cleared; evplp_clear_accumulators and evplp_set_blocks (so also a group's rebalance) reset N to 0 and make
+ * per tile, independent of the partition.  N: the context's accumulating calls into EVPLP_BUF_VPL_ACCUM (evplp_gather_vpl / _vsl and
+ * evplp_path_trace with do_accumulate != 0; so enabling either mode after an accumulated path-tracing sample without a clear is refused) since the accumulators were last cleared; evplp_clear_accumulators and evplp_set_blocks (so also a group's rebalance) reset N to 0 and make
  * every tile active again.
  * evplp_adaptive_retire retires an active tile when the noise tracker has closed B >= min_batches (>= 2) batches and the mean over the tile's
  * in-image pixels of the per-pixel relative variance -- rel = num / den exactly as evplp_noise_estimate forms it, with the same scale,
@@ -390,6 +391,16 @@ int evplp_denoise(evplp_context *ctx, float scale, float light_scale, int32_t ma
  * is on: evplp_gather_lvc, evplp_path_trace, a gather with do_accumulate == 0, evplp_noise_track (off, or a restart) with N > 0.
  * A calibration frame (evplp_calibrate_blocks) gathers every tile; the reduce still writes retired pixels from their snapshots. */
 int evplp_adaptive_enable(evplp_context *ctx, int32_t on);
+/* Adaptive sampling for the path tracer ("render until every tile is at noise level x"): the same records, snapshot, pre-conditions and
+ * memory as evplp_adaptive_enable (on = 0 releases), in path-trace mode: an accumulating evplp_path_trace honours retirement -- a retired
+ * tile reads no G-buffer, traces no ray, adds nothing to the pass counters, and its in-image pixels are written as
+ * (float)((double)R * ((double)(N + 1) / (double)n_t)), exactly as the gather's reduce writes them; an active tile is bit-identical to a run
+ * without adaptivity (a pixel's generator is keyed by pixel and seed alone).  For the path tracer the noise figure is the error itself (no
+ * clamping, no photon radius), so a retired tile's frozen figure is its error at retirement.  evplp_adaptive_retire and
+ * evplp_adaptive_tiles serve both modes.  Refused with EVPLP_ERR_INVALID in this mode (the context stays usable): evplp_gather_vpl,
+ * evplp_gather_vsl, evplp_gather_lvc, evplp_path_trace with do_accumulate == 0 (the snapshot describes the one plane the mode's pass owns),
+ * and as above a switch of the mode or of the tracker with N > 0. */
+int evplp_adaptive_enable_pt(evplp_context *ctx, int32_t on);
 int evplp_adaptive_retire(evplp_context *ctx, float scale, float light_scale, int32_t mask_emitter,
                           double tile_rel_mse, int32_t min_batches);          /* >= 0: tiles retired by this call */
 /* Per image tile, ceil(W / 8) x ceil(H / 8) in the planes' row order (tile row 0 = image rows 0..7 from the bottom): n_t for a retired tile,
@@ -594,6 +605,7 @@ int evplp_group_denoise(evplp_group *g, float scale, float light_scale, int32_t 
  * counts, and the tile map is assembled from the block owners (the whole image).  EVPLP_PARTITION_ITERATIONS: every call is refused --
  * pooling the ranks' decisions is not supported.  Refusals come on the caller's thread and leave the group usable. */
 int evplp_group_adaptive_enable(evplp_group *g, int32_t on);
+int evplp_group_adaptive_enable_pt(evplp_group *g, int32_t on);    /* path-trace mode: evplp_group_path_trace (accumulating) yes, evplp_group_gather no */
 int evplp_group_adaptive_retire(evplp_group *g, float scale, float light_scale, int32_t mask_emitter,
                                 double tile_rel_mse, int32_t min_batches);
 int evplp_group_adaptive_tiles(evplp_group *g, int32_t *iterations_per_image_tile, int32_t capacity);

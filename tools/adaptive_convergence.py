@@ -11,7 +11,17 @@ Radiosity (1024 VPL paths, 3 bounces, misMode one, no photon splat).  Every run 
     saving smaller than the retired fraction means the cheap tiles converged first.
   * floor: the gather call with every tile retired (tileRelMse huge), its pass time and its host wall time, against a full gather's.
 
-usage: python tools/adaptive_convergence.py [--iters N] [--ref-iters N] [--taus 0.002,0.0005] [--every N] [--min-batches N]"""
+--technique pt: the same questions for the path tracer in path-trace mode (evplp_group_adaptive_enable_pt), 3 bounces, one sample per pixel
+per call, on the same scene.  Curves and reference as above with the path-tracing pass in the gather's place; then, with a plain group and an
+adaptive group alternating call by call in this process (--calls each; host clock around a synchronised call, and the pass's own time;
+median and p10 - p90):
+  * floor: a call with every tile retired against a plain call;
+  * active: call time at about 100 / 50 / 25 / 10 / 5 % active tiles (tileRelMse taken from the quantiles of the tile means after four
+    samples); its first row is a control with adaptivity off on both groups.
+--plain-calls N: nothing but N plain path-tracing calls, timed the same way (for a side-by-side of two builds of the library, EVPLP_LIB).
+
+usage: python tools/adaptive_convergence.py [--technique photonfam|pt] [--iters N] [--ref-iters N] [--taus 0.002,0.0005] [--every N]
+                                            [--min-batches N] [--calls N] [--plain-calls N]"""
 import argparse
 import json
 import math
@@ -44,14 +54,74 @@ class Runner:
         self.g.primary(tuple(self.js[i])); self.g.trace_light_paths(i); self.g.gather(fp, 0)
 
 
+class PtRunner:
+    """one path-traced sample per pixel per iteration (the pt technique's loop: jitter i, seed i, 3 bounces)"""
+    def __init__(self, g, sd):
+        self.g, self.sd = g, sd
+        self.js = ev.jitter_sequence(0, 4096, W, H)
+
+    def iteration(self, i):
+        self.g.primary(tuple(self.js[i % len(self.js)])); self.g.path_trace(self.sd.cam_origin, i, 3)
+
+
+PASS = ev.PASS_GATHER_VPL          # the pass whose work retirement saves (main() switches it for --technique pt)
+
+
 def gather_ms(g):
-    return g.context(0).pass_stats(ev.PASS_GATHER_VPL)["ms"]
+    return g.context(0).pass_stats(PASS)["ms"]
+
+
+def spread(v):
+    q = statistics.quantiles(v, n=10)
+    return {"median": statistics.median(v), "p10": q[0], "p90": q[-1]}
+
+
+def timed_calls(groups, sd, first, calls):
+    """`calls` path-tracing calls on each group in turn (alternating call by call): host wall time around a synchronised call, and the pass time"""
+    out = [{"wall": [], "pass": []} for _ in groups]
+    for i in range(first, first + calls):
+        for g, o in zip(groups, out):
+            g.synchronize()
+            t0 = time.perf_counter()
+            g.path_trace(sd.cam_origin, i, 3); g.synchronize()
+            o["wall"].append((time.perf_counter() - t0) * 1e3); o["pass"].append(gather_ms(g))
+    return [{"wall_ms": spread(o["wall"]), "pass_ms": spread(o["pass"])} for o in out]
+
+
+def tile_means_of(g, n):
+    """per-tile mean relative variance of the composite at 1 / n, as evplp_adaptive_retire forms it (numpy, not bit for bit: for quantiles)"""
+    s = 1.0 / n
+    var = g.noise_variance(s).astype(np.float64).sum(-1)
+    c = g.resolve(s, s, 1.0).astype(np.float64)
+    rel = var / ((c * c).sum(-1) + 0.001)
+    return rel.reshape(H // 8, 8, W // 8, 8).mean(axis=(1, 3))
+
+
+def pt_tables(g, plain, sd, tiles, calls):
+    """the floor and the active-fraction table: g adaptive, `plain` a second group without adaptivity, alternating"""
+    runs = {"adaptive": PtRunner(g, sd), "plain": PtRunner(plain, sd)}
+    rows = []
+    for want in (None, 1.0, 0.5, 0.25, 0.10, 0.05, 0.0):       # None: the control -- both groups plain (what two groups differ by on their own)
+        for name, grp in (("adaptive", g), ("plain", plain)):
+            grp.clear_accumulators(); grp.noise_track(True)
+            if name == "adaptive" and want is not None:
+                grp.adaptive_enable(True, path_trace=True)
+            for i in range(4):
+                runs[name].iteration(i); grp.noise_fold(1)
+        tau = 1e300 if want == 0.0 else (-1.0 if want in (None, 1.0) else float(np.quantile(tile_means_of(g, 4), 1.0 - want)))
+        retired = g.adaptive_retire(0.25, tau, 2) if tau >= 0.0 else 0
+        g.primary(tuple(runs["adaptive"].js[4])); plain.primary(tuple(runs["plain"].js[4]))
+        a, p = timed_calls([g, plain], sd, 4, calls)
+        rows.append({"adaptivity": want is not None, "active_fraction": 1.0 - retired / tiles, "adaptive": a, "plain": p,
+                     "pass_fraction_of_plain": a["pass_ms"]["median"] / p["pass_ms"]["median"]})
+        g.clear_accumulators(); g.adaptive_enable(False, path_trace=True)
+    return rows[:-1], rows[-1]
 
 
 def curve(g, run, iters, every, tau, min_batches, tiles):
     g.clear_accumulators(); g.noise_track(True)
     if tau is not None:
-        g.adaptive_enable(True)
+        g.adaptive_enable(True, path_trace=PASS == ev.PASS_PATH_TRACE)
     g.synchronize()
     wall = 0.0; pts = []; retired = 0; gms = []
     for i in range(iters):
@@ -77,7 +147,14 @@ def main():
     ap.add_argument("--taus", default="0.002,0.0005,0.0001")
     ap.add_argument("--every", type=int, default=8)
     ap.add_argument("--min-batches", type=int, default=4)
+    ap.add_argument("--technique", choices=("photonfam", "pt"), default="photonfam")
+    ap.add_argument("--calls", type=int, default=40)
+    ap.add_argument("--plain-calls", type=int, default=0)
     a = ap.parse_args()
+    pt = a.technique == "pt" or a.plain_calls > 0
+    if pt:
+        global PASS
+        PASS = ev.PASS_PATH_TRACE
     tiles = ((W + 7) // 8) * ((H + 7) // 8)
     res = {"shape": {"W": W, "H": H, "numLightPaths": NL, "numVplLightPaths": NV, "scene": "hard, 331000 triangles"}, "tiles": tiles}
     with tempfile.TemporaryDirectory() as d:
@@ -86,11 +163,17 @@ def main():
         with ev.Group(W, H, NL, NV, P, 1, devices=[0], overlap_light_tracing=True) as g:
             g.load_scene_json(jp)
             bsr, total, _ = g.context(0).scene_metrics()
-            run = Runner(g, sd, total)
+            run = PtRunner(g, sd) if pt else Runner(g, sd, total)
+            if a.plain_calls > 0:
+                g.clear_accumulators()
+                for i in range(4):
+                    run.iteration(i)
+                print(json.dumps({"library": ev.LIB_PATH, "plain_path_trace_call": timed_calls([g], sd, 4, a.plain_calls)[0]}))
+                return
             # the reference: a long plain run
             g.clear_accumulators()
             for i in range(a.ref_iters):
-                run.iteration(i)
+                run.iteration(i + (1 << 20) if pt else i)        # (pt: samples of its own, so that no curve shares any with the reference)
             s = 1.0 / a.ref_iters
             ref = np.ascontiguousarray(g.resolve(s, s, 1.0)[::-1]).astype(np.float32)
             g.set_error_reference(ref)
@@ -117,6 +200,12 @@ def main():
                         hit = p0["wall_ms"] + t * (p1["wall_ms"] - p0["wall_ms"]); break
                 r["ms_to_plain_final_rel_mse"] = hit
             res["runs"] = runs
+            if pt:
+                with ev.Group(W, H, NL, NV, P, 1, devices=[0]) as plain:
+                    plain.load_scene_json(jp)
+                    res["active"], res["floor"] = pt_tables(g, plain, sd, tiles, a.calls)
+                print(json.dumps(res))
+                return
             # the floor: every tile retired
             g.clear_accumulators(); g.noise_track(True); g.adaptive_enable(True)
             for i in range(4):
