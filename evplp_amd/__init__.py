@@ -120,6 +120,8 @@ _SIGNATURES = {
     "evplp_gather_vsl": (C.c_int, [_P, C.POINTER(FrameParams)]),
     "evplp_gather_lvc": (C.c_int, [_P, C.POINTER(FrameParams)]),
     "evplp_path_trace": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_int32]),
+    "evplp_path_trace_batch": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_uint32]),
+    "evplp_path_trace_batch_scratch": (C.c_int, [_P, C.c_uint64]),
     "evplp_splat_photons": (C.c_int, [_P, C.POINTER(FrameParams), C.c_int32]),
     "evplp_set_splat_proxy": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32]),
     "evplp_group_set_splat_proxy": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32]),
@@ -171,6 +173,8 @@ _SIGNATURES = {
     "evplp_group_gather": (C.c_int, [_P, C.POINTER(FrameParams), C.c_int32]),
     "evplp_group_splat_photons": (C.c_int, [_P, C.POINTER(FrameParams), C.c_int32]),
     "evplp_group_path_trace": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_int32]),
+    "evplp_group_path_trace_batch": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_uint32]),
+    "evplp_group_path_trace_batch_scratch": (C.c_int, [_P, C.c_uint64]),
     "evplp_group_synchronize": (C.c_int, [_P]),
     "evplp_group_select_rank": (C.c_int, [_P, C.c_int32]),
     "evplp_group_synchronize_rank": (C.c_int, [_P, C.c_int32]),
@@ -317,6 +321,15 @@ def default_splat_proxy():
     n = lib().evplp_default_splat_proxy(_ptr(v), _ptr(t))
     assert n == 80
     return v, t
+
+
+def _batch_arrays(jitters, rng_seeds):
+    """(samples, jitters [S][2] float32, seeds [S] uint32) of a path_trace_batch call; the C side checks the count"""
+    j = np.ascontiguousarray(np.asarray(jitters, np.float32).reshape(-1, 2))
+    r = np.ascontiguousarray(np.asarray(rng_seeds, np.uint32).reshape(-1))
+    if len(j) != len(r):
+        raise ValueError(f"path_trace_batch: {len(j)} jitters but {len(r)} seeds")
+    return len(r), j, r
 
 
 class Context:
@@ -478,6 +491,17 @@ class Context:
     def path_trace(self, camera_pos, rng_seed: int, max_bounces: int, accumulate=True):
         cp = (C.c_float * 3)(*[float(v) for v in camera_pos])
         self._check(self._lib.evplp_path_trace(self._h, C.byref(cp), rng_seed, max_bounces, int(accumulate)))
+
+    def path_trace_batch(self, camera_pos, jitters, rng_seeds, max_bounces: int):
+        """S accumulating iterations in one call: primary(jitters[s], 0) + path_trace(camera_pos, rng_seeds[s], max_bounces) for every s,
+        over the active tiles only (evplp_path_trace_batch)"""
+        cp = (C.c_float * 3)(*[float(v) for v in camera_pos])
+        n, j, r = _batch_arrays(jitters, rng_seeds)
+        self._check(self._lib.evplp_path_trace_batch(self._h, C.byref(cp), n, j.ctypes.data, r.ctypes.data, max_bounces))
+
+    def path_trace_batch_scratch(self, nbytes: int):
+        """bound of the batch's staging buffer in bytes (default 1 GiB); smaller bounds mean more chunks, never other bits"""
+        self._check(self._lib.evplp_path_trace_batch_scratch(self._h, int(nbytes)))
 
     def splat_photons(self, fp: FrameParams, clear=False):
         self._check(self._lib.evplp_splat_photons(self._h, C.byref(fp), int(clear)))
@@ -732,6 +756,17 @@ class Group:
     def path_trace(self, camera_pos, rng_seed: int, max_bounces: int, accumulate=True):
         cp = (C.c_float * 3)(*[float(v) for v in camera_pos])
         self._check(self._lib.evplp_group_path_trace(self._h, C.byref(cp), rng_seed, max_bounces, int(accumulate)))
+
+    def path_trace_batch(self, camera_pos, jitters, rng_seeds, max_bounces: int):
+        """S accumulating iterations in one call: primary(jitters[s], 0) + path_trace(camera_pos, rng_seeds[s], max_bounces) for every s,
+        over the active tiles only (evplp_group_path_trace_batch)"""
+        cp = (C.c_float * 3)(*[float(v) for v in camera_pos])
+        n, j, r = _batch_arrays(jitters, rng_seeds)
+        self._check(self._lib.evplp_group_path_trace_batch(self._h, C.byref(cp), n, j.ctypes.data, r.ctypes.data, max_bounces))
+
+    def path_trace_batch_scratch(self, nbytes: int):
+        """bound of the batch's staging buffer in bytes (default 1 GiB); smaller bounds mean more chunks, never other bits"""
+        self._check(self._lib.evplp_group_path_trace_batch_scratch(self._h, int(nbytes)))
 
     def splat_photons(self, fp, clear=False):
         self._check(self._lib.evplp_group_splat_photons(self._h, C.byref(fp), int(clear)))

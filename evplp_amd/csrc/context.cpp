@@ -207,6 +207,7 @@ extern "C" void evplp_destroy(evplp_context *c) {
     hipFree(c->d_noise); hipFree(c->d_noise_keep); hipFree(c->d_noise_rows);
     hipFree(c->d_adapt_tiles); hipFree(c->d_adapt_snap);
     hipFree(c->d_dn_var); hipFree(c->d_dn_pack); hipFree(c->d_dn_u);
+    hipFree(c->d_pt_batch); hipFree(c->d_pt_list);
     for (int i = 0; i < EVPLP_PASS_COUNT; i++) {
         if (c->ev_begin[i]) hipEventDestroy(c->ev_begin[i]);
         if (c->ev_end[i]) hipEventDestroy(c->ev_end[i]);
@@ -563,6 +564,28 @@ static int pass_end(evplp_context *c, int pass) {
     return EVPLP_OK;
 }
 
+static bool jitter_within_cuts(const evplp_context *c, const float jitter[2]) {
+    return std::fabs(jitter[0]) <= 1.99f / (float)c->st.W && std::fabs(jitter[1]) <= 1.99f / (float)c->st.H;
+}
+// the eye's entry cuts: once per camera / tree (they hold for every jitter up to a pixel), 256 B per group of 2 x 2 tiles (2 x 1 where a
+// strip's tile rows are not neighbours in the image); built on the stream if they are stale, and named in a (left alone if they cannot be had)
+static void primary_cuts_into(evplp_context *c, PrimaryArgs &a) {
+    PrimaryCutArgs pc; std::memset(&pc, 0, sizeof(pc));
+    pc.nodes = c->sc.nodes; pc.st = c->st; pc.cam = c->cam; pc.tiles_x = c->tiles_x; pc.tiles_y = c->tiles_y;
+    pc.gw_log2 = 1; pc.gh_log2 = (c->st.strip_count == 1 || c->st.strip_rows >= 16) ? 1 : 0;
+    pc.groups_x = (c->tiles_x + (1 << pc.gw_log2) - 1) >> pc.gw_log2; pc.groups_y = (c->tiles_y + (1 << pc.gh_log2) - 1) >> pc.gh_log2;
+    if (!c->d_primary_cuts) {
+        hipError_t me = hipMalloc((void **)&c->d_primary_cuts, (size_t)pc.groups_x * pc.groups_y * (size_t)kCutSlotBytes);
+        if (me != hipSuccess) { (void)hipGetLastError(); c->d_primary_cuts = nullptr; }
+        c->primary_cuts_valid = false;
+    }
+    if (c->d_primary_cuts) {
+        pc.cuts = c->d_primary_cuts;
+        if (!c->primary_cuts_valid) { launch_primary_cuts(pc, c->stream); c->primary_cuts_valid = true; }
+        a.cuts = c->d_primary_cuts; a.cut_gw_log2 = pc.gw_log2; a.cut_gh_log2 = pc.gh_log2; a.cut_groups_x = pc.groups_x;
+    }
+}
+
 extern "C" int evplp_primary(evplp_context *c, const float jitter[2], int32_t clear_light) {
     CTX_CHECK(c);
     // A pending photon splat may have to run again from the G-buffer it was given (settle_splat).  With overlap_light_tracing the
@@ -596,25 +619,7 @@ extern "C" int evplp_primary(evplp_context *c, const float jitter[2], int32_t cl
     // The eye's cuts are built for a pyramid opened by ONE PIXEL (2 / W, 2 / H in NDC) around every tile group (primary_cut_kernel): they
     // hold for the reference's jitter, (2u - 1) / resolution -- half a pixel at most (rtcomphoton.h:949) -- and for anything up to a whole
     // pixel.  A larger translation (the ABI takes any float) moves rays out of their group's pyramid: that call walks from the root.
-    const bool jitter_within_cuts = std::fabs(a.jitter[0]) <= 1.99f / (float)c->st.W && std::fabs(a.jitter[1]) <= 1.99f / (float)c->st.H;
-    if (c->env_cuts != 0 && c->tiles_x * c->tiles_y > 0 && jitter_within_cuts) {
-        // the eye's entry cuts: once per camera / tree (they hold for every jitter up to a pixel), 256 B per group of 2 x 2 tiles (2 x 1 where a
-        // strip's tile rows are not neighbours in the image)
-        PrimaryCutArgs pc; std::memset(&pc, 0, sizeof(pc));
-        pc.nodes = c->sc.nodes; pc.st = c->st; pc.cam = c->cam; pc.tiles_x = c->tiles_x; pc.tiles_y = c->tiles_y;
-        pc.gw_log2 = 1; pc.gh_log2 = (c->st.strip_count == 1 || c->st.strip_rows >= 16) ? 1 : 0;
-        pc.groups_x = (c->tiles_x + (1 << pc.gw_log2) - 1) >> pc.gw_log2; pc.groups_y = (c->tiles_y + (1 << pc.gh_log2) - 1) >> pc.gh_log2;
-        if (!c->d_primary_cuts) {
-            hipError_t me = hipMalloc((void **)&c->d_primary_cuts, (size_t)pc.groups_x * pc.groups_y * (size_t)kCutSlotBytes);
-            if (me != hipSuccess) { (void)hipGetLastError(); c->d_primary_cuts = nullptr; }
-            c->primary_cuts_valid = false;
-        }
-        if (c->d_primary_cuts) {
-            pc.cuts = c->d_primary_cuts;
-            if (!c->primary_cuts_valid) { launch_primary_cuts(pc, c->stream); c->primary_cuts_valid = true; }
-            a.cuts = c->d_primary_cuts; a.cut_gw_log2 = pc.gw_log2; a.cut_gh_log2 = pc.gh_log2; a.cut_groups_x = pc.groups_x;
-        }
-    }
+    if (c->env_cuts != 0 && c->tiles_x * c->tiles_y > 0 && jitter_within_cuts(c, a.jitter)) primary_cuts_into(c, a);
     if ((rc = pass_begin(c, EVPLP_PASS_PRIMARY))) return rc;
     launch_primary(a, c->stream);
     c->tile_box_valid = !c->gbuf_pos_exposed;
@@ -893,6 +898,84 @@ extern "C" int evplp_path_trace(evplp_context *c, const float camera_pos[3], uin
     if ((rc = pass_end(c, EVPLP_PASS_PATH_TRACE))) return rc;
     if (do_accumulate) c->adapt_n++;
     return EVPLP_OK;
+}
+
+// evplp_path_trace_batch (include/evplp.h has the contract; kernels.h PtBatchChunk the device side).  The staging buffer holds the slots of
+// one chunk.  With E = the tiles of the planes and C = the slots the scratch bound allows: E x S <= C is one chunk; otherwise the list is
+// cut into runs of C / S entries with all S samples each; and where not even one entry's S samples fit (C < S), every entry runs its
+// samples C at a time.  A chunk is primary -> trace -> reduce on the stream, so the adds to a pixel stay in increasing s whatever the cut.
+extern "C" int evplp_path_trace_batch_scratch(evplp_context *c, uint64_t bytes) { CTX_CHECK(c); c->pt_batch_cap = bytes; return EVPLP_OK; }
+extern "C" int evplp_path_trace_batch(evplp_context *c, const float camera_pos[3], int32_t samples, const float *jitters, const uint32_t *rng_seeds, uint32_t max_bounces) {
+    CTX_CHECK(c);
+    const char *name = "evplp_path_trace_batch";
+    if (samples < 1 || samples > kPtBatchMaxSamples) { c->set_error("%s: samples must be 1 .. %d (got %d)", name, kPtBatchMaxSamples, samples); return EVPLP_ERR_INVALID; }
+    if (!camera_pos || !jitters || !rng_seeds) { c->set_error("%s: null camera position, jitters or seeds", name); return EVPLP_ERR_INVALID; }
+    if (c->d_adapt_tiles && !c->adapt_pt) { c->set_error("%s: adaptivity is on (evplp_adaptive_enable): VPL and VSL gathers only", name); return EVPLP_ERR_INVALID; }
+    if (c->pt_batch_cap < kPtBatchSlotBytes) {
+        c->set_error("%s: the scratch bound (%llu B, evplp_path_trace_batch_scratch) is below one tile x one sample (%zu B)", name, (unsigned long long)c->pt_batch_cap, kPtBatchSlotBytes);
+        return EVPLP_ERR_INVALID;
+    }
+    PtBatchSamples sm; std::memset(&sm, 0, sizeof(sm));
+    unsigned long long cut_mask = 0;
+    for (int s = 0; s < samples; s++) {
+        sm.jitter[s][0] = jitters[2 * s]; sm.jitter[s][1] = jitters[2 * s + 1]; sm.seed[s] = rng_seeds[s];
+        if (!std::isfinite(sm.jitter[s][0]) || !std::isfinite(sm.jitter[s][1])) { c->set_error("%s: jitter %d is not finite", name, s); return EVPLP_ERR_INVALID; }
+        if (jitter_within_cuts(c, sm.jitter[s])) cut_mask |= 1ull << s;
+    }
+    int rc = pass_ready(c, name, true); if (rc) return rc;
+    const int32_t ntiles = c->tiles_x * c->tiles_y;
+    if (ntiles > 0) {
+        // the staging buffer: what the call needs, within the bound; it only grows, unless the bound came down below it
+        const uint64_t cap_slots = std::min<uint64_t>(c->pt_batch_cap / kPtBatchSlotBytes, 1u << 30);
+        const uint64_t slots = std::min<uint64_t>((uint64_t)ntiles * (uint64_t)samples, cap_slots);
+        if (c->pt_batch_bytes < slots * kPtBatchSlotBytes || c->pt_batch_bytes > cap_slots * kPtBatchSlotBytes) {
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            if (c->d_pt_batch) { hipFree(c->d_pt_batch); c->d_pt_batch = nullptr; c->pt_batch_bytes = 0; }
+            if (hipMalloc((void **)&c->d_pt_batch, slots * kPtBatchSlotBytes) != hipSuccess) {
+                (void)hipGetLastError(); c->d_pt_batch = nullptr;
+                c->set_error("%s: cannot allocate %llu B of staging (bound it with evplp_path_trace_batch_scratch)", name, (unsigned long long)(slots * kPtBatchSlotBytes));
+                return EVPLP_ERR_OOM;
+            }
+            c->pt_batch_bytes = slots * kPtBatchSlotBytes;
+        }
+        if (c->adapt_pt && !c->d_pt_list) HIP_TRY(c, hipMalloc((void **)&c->d_pt_list, sizeof(int32_t) * ((size_t)ntiles + 1)));
+        const uint64_t have = c->pt_batch_bytes / kPtBatchSlotBytes;
+        const int32_t chunk_entries = (int32_t)std::max<uint64_t>(1, std::min<uint64_t>(have / (uint64_t)samples, (uint64_t)ntiles));
+        const int32_t chunk_samples = (int32_t)std::min<uint64_t>(have, (uint64_t)samples);
+
+        PrimaryArgs pa; std::memset(&pa, 0, sizeof(pa));
+        pa.sc = c->sc; pa.st = c->st; pa.cam = c->cam; pa.g_light = (float4 *)c->buf[EVPLP_BUF_LIGHT];
+        if (c->env_cuts != 0 && cut_mask) primary_cuts_into(c, pa);
+        PathTraceArgs ta; std::memset(&ta, 0, sizeof(ta));
+        ta.sc = c->sc; ta.st = c->st;
+        for (int k = 0; k < 3; k++) ta.camera_pos[k] = camera_pos[k];
+        ta.max_bounces = max_bounces; ta.do_accumulate = 0u;                  // (a sample's radiance goes to its staging slot as 0 + radiance: kernels_ptbatch.hip)
+        ta.counters = &c->d_counters[EVPLP_PASS_PATH_TRACE];
+        float4 *out = (float4 *)c->buf[EVPLP_BUF_VPL_ACCUM];
+        if ((rc = pass_begin(c, EVPLP_PASS_PATH_TRACE))) return rc;
+        PtBatchChunk ch; std::memset(&ch, 0, sizeof(ch));
+        ch.tiles = ntiles; ch.staging = (float4 *)c->d_pt_batch; ch.cut_mask = cut_mask;
+        if (c->adapt_pt) {
+            // path-trace mode: the active tiles as a list (its count stays on the device: the launches are sized from the tile total and the
+            // surplus items exit); the retired tiles are written once from the snapshot, for N + S
+            launch_pt_batch_list(c->d_adapt_tiles, ntiles, c->d_pt_list, c->d_pt_list + ntiles, c->stream);
+            ch.list = c->d_pt_list; ch.count = c->d_pt_list + ntiles;
+            AdaptArgs ad{}; ad.tiles = c->d_adapt_tiles; ad.snap = c->d_adapt_snap; ad.n1 = (int32_t)(c->adapt_n + samples);
+            launch_pt_batch_rescale(c->st, out, ad, ntiles, c->stream);
+        }
+        for (int32_t e0 = 0; e0 < ntiles; e0 += chunk_entries)
+            for (int32_t s0 = 0; s0 < samples; s0 += chunk_samples) {
+                ch.entry_first = e0; ch.entry_count = std::min(chunk_entries, ntiles - e0);
+                ch.sample_first = s0; ch.sample_count = std::min(chunk_samples, samples - s0);
+                launch_pt_batch_primary(pa, sm, ch, c->stream);
+                launch_pt_batch_trace(ta, sm, ch, c->stream);
+                launch_pt_batch_reduce(c->st, out, ch, c->stream);
+            }
+        if ((rc = pass_end(c, EVPLP_PASS_PATH_TRACE))) return rc;
+    }
+    c->adapt_n += samples;
+    // the whole-frame primary pass at the last jitter: G-buffer planes, tile boxes and pass record are then those of S single calls
+    return evplp_primary(c, sm.jitter[samples - 1], 0);
 }
 
 // setupPhotonSplatIcosohedron (rtcomphoton.h:632-644): the proxy mesh of EVPLP_FOOTPRINT_PROXY -> slabs on the device

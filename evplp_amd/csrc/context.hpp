@@ -157,6 +157,9 @@ struct evplp_context {
     // last evplp_adaptive_retire (the group's workers leave it here)
     int64_t adapt_n = 0; int4 *d_adapt_tiles = nullptr; float4 *d_adapt_snap = nullptr; std::vector<int4> adapt_tiles; int32_t adapt_last = 0;
     bool adapt_pt = false;          // evplp_adaptive_enable_pt: evplp_path_trace owns the retirement (the gathers are refused)
+    // evplp_path_trace_batch: the staging slots of one chunk (kernels.h PtBatchChunk; allocated on the first call, bounded by pt_batch_cap --
+    // evplp_path_trace_batch_scratch) and, in path-trace adaptive mode, the active-tile list [tiles] followed by its count [1]
+    char *d_pt_batch = nullptr; size_t pt_batch_bytes = 0; uint64_t pt_batch_cap = 1ull << 30; int32_t *d_pt_list = nullptr;
     // evplp_denoise: the variance image [W * local_rows][3], the packed pixels of the planes [W * local_rows] (kernels.h DenoisePixel), and
     // the two (u, s) planes of the a-trous passes [2][dn_u_px] (the frame the context filters: its planes, or a group's whole image on rank 0);
     // allocated on the first call, kept until evplp_destroy

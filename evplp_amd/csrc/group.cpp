@@ -29,11 +29,13 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <dlfcn.h>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -64,14 +66,17 @@ struct Rccl {
 };
 
 enum Op { OP_QUIT = 0, OP_CLEAR, OP_SYNC, OP_PRIMARY, OP_TRACE, OP_GATHER, OP_SPLAT, OP_PATH_TRACE, OP_PRESENT, OP_LOAD_SCENE, OP_SET_PROXY, OP_ASSEMBLE, OP_REDUCE, OP_SET_REFERENCE, OP_FRAME_ERROR,
-          OP_NOISE_TRACK, OP_NOISE_FOLD, OP_NOISE_POOL, OP_NOISE_ROWS, OP_NOISE_VARIANCE, OP_ADAPT_ENABLE, OP_ADAPT_RETIRE, OP_DENOISE_PREP, OP_DENOISE_FILTER };
-// One posted call: plain data, copied into the ring (pointers must stay valid until the caller has drained: load_scene, set_proxy, resolve do)
+          OP_NOISE_TRACK, OP_NOISE_FOLD, OP_NOISE_POOL, OP_NOISE_ROWS, OP_NOISE_VARIANCE, OP_ADAPT_ENABLE, OP_ADAPT_RETIRE, OP_DENOISE_PREP, OP_DENOISE_FILTER, OP_PATH_TRACE_BATCH };
+// One posted call, copied into the ring by assignment: plain data (pointers must stay valid until the caller has drained: load_scene, set_proxy,
+// resolve do) but for `batch`, a shared pointer -- so every post and every worker-side copy of a command pays one atomic reference count, null or not.
 struct Cmd {
     int op = OP_QUIT;
     evplp_frame_params fp{};
     float f[4] = {}; int32_t i[4] = {}; uint32_t u[4] = {};
     const void *p0 = nullptr, *p1 = nullptr; void *out = nullptr;
     double d = 0.0;
+    // OP_PATH_TRACE_BATCH: the call's jitters and seeds, copied (the call returns before the workers run it; the ring slot keeps the 768 B alive until it is reused)
+    std::shared_ptr<const evplp::PtBatchSamples> batch;
 };
 constexpr int kRing = 64;
 constexpr int kSpinBeforeSleep = 200000;     // ~1-2 ms of polling before an idle worker goes to sleep on its condition variable
@@ -132,6 +137,7 @@ struct evplp_group {
     bool noise_on = false;                  // evplp_group_noise_track is on on every rank (caller's thread)
     bool adapt_on = false;                  // evplp_group_adaptive_enable is on on every rank (caller's thread)
     bool adapt_pt = false;                  // ... and in path-trace mode (evplp_group_adaptive_enable_pt)
+    uint64_t pt_batch_cap = 1ull << 30;     // evplp_group_path_trace_batch_scratch: every rank's bound (caller's thread)
     // EVPLP_PARTITION_ITERATIONS, evplp_group_noise_*: rank 0's pooled moments (Q then S, [3][stride] fp64 each) and K / B summed over the
     // ranks (written by rank 0's worker); RCCL only: per rank [n][noise_bytes] every rank's NoisePlanes (all-gathered)
     double *d_noise_pool = nullptr; double pool_k = 0.0, pool_b = 0.0;
@@ -395,6 +401,7 @@ static void worker_run(Worker *w, const Cmd &cmd) {
         case OP_GATHER: rc = cmd.i[0] == 0 ? evplp_gather_vpl(c, &cmd.fp) : cmd.i[0] == 1 ? evplp_gather_vsl(c, &cmd.fp) : evplp_gather_lvc(c, &cmd.fp); break;
         case OP_SPLAT: rc = evplp_splat_photons(c, &cmd.fp, cmd.i[0]); break;
         case OP_PATH_TRACE: rc = evplp_path_trace(c, cmd.f, cmd.u[0], cmd.u[1], cmd.i[0]); break;
+        case OP_PATH_TRACE_BATCH: rc = evplp_path_trace_batch(c, cmd.f, cmd.i[0], &cmd.batch->jitter[0][0], cmd.batch->seed, cmd.u[1]); break;
         case OP_PRESENT: rc = evplp::resolve_to_device(c, cmd.f[0], cmd.f[1], cmd.f[2], cmd.i[0], cmd.i[1], cmd.i[2] != 0 || !c->aux_stream, cmd.u[0] == 0); break;   // (u[0]: the composite evplp_group_frame_error measures)
         case OP_LOAD_SCENE: rc = evplp_load_scene_json(c, (const char *)cmd.p0); break;
         case OP_SET_PROXY: rc = evplp_set_splat_proxy(c, (const float *)cmd.p0, cmd.i[0], (const int32_t *)cmd.p1, cmd.i[1]); break;
@@ -782,6 +789,38 @@ extern "C" int evplp_group_path_trace(evplp_group *g, const float camera_pos[3],
     if (g->adapt_pt && !do_accumulate) { g->set_error("evplp_group_path_trace: adaptivity is on (evplp_group_adaptive_enable_pt): a sample must accumulate"); return EVPLP_ERR_INVALID; }
     Cmd c; c.op = OP_PATH_TRACE; c.f[0] = camera_pos[0]; c.f[1] = camera_pos[1]; c.f[2] = camera_pos[2]; c.u[0] = rng_seed; c.u[1] = max_bounces; c.i[0] = do_accumulate;
     return post_pass(g, c);
+}
+
+// Refused here, on the caller's thread, as the context refuses them (the workers' failures are sticky): the sample count, null arrays, a
+// jitter that is not finite, gather-mode adaptivity, a scratch bound below one slot.  Strips: every rank runs the call for its own rows
+// (a rank's active-tile list is over its own tiles); iterations: the selected rank.
+extern "C" int evplp_group_path_trace_batch(evplp_group *g, const float camera_pos[3], int32_t samples, const float *jitters, const uint32_t *rng_seeds, uint32_t max_bounces) {
+    GRP_CHECK(g);
+    const char *name = "evplp_group_path_trace_batch";
+    if (samples < 1 || samples > evplp::kPtBatchMaxSamples) { g->set_error("%s: samples must be 1 .. %d (got %d)", name, evplp::kPtBatchMaxSamples, samples); return EVPLP_ERR_INVALID; }
+    if (!camera_pos || !jitters || !rng_seeds) { g->set_error("%s: null camera position, jitters or seeds", name); return EVPLP_ERR_INVALID; }
+    if (g->adapt_on && !g->adapt_pt) { g->set_error("%s: adaptivity is on (evplp_group_adaptive_enable): VPL and VSL gathers only", name); return EVPLP_ERR_INVALID; }
+    if (g->pt_batch_cap < evplp::kPtBatchSlotBytes) {
+        g->set_error("%s: the scratch bound (%llu B, evplp_group_path_trace_batch_scratch) is below one tile x one sample (%zu B)", name, (unsigned long long)g->pt_batch_cap, evplp::kPtBatchSlotBytes);
+        return EVPLP_ERR_INVALID;
+    }
+    auto sm = std::make_shared<evplp::PtBatchSamples>();
+    std::memset(sm.get(), 0, sizeof(*sm));
+    for (int s = 0; s < samples; s++) {
+        sm->jitter[s][0] = jitters[2 * s]; sm->jitter[s][1] = jitters[2 * s + 1]; sm->seed[s] = rng_seeds[s];
+        if (!std::isfinite(sm->jitter[s][0]) || !std::isfinite(sm->jitter[s][1])) { g->set_error("%s: jitter %d is not finite", name, s); return EVPLP_ERR_INVALID; }
+    }
+    Cmd c; c.op = OP_PATH_TRACE_BATCH; c.f[0] = camera_pos[0]; c.f[1] = camera_pos[1]; c.f[2] = camera_pos[2]; c.i[0] = samples; c.u[1] = max_bounces; c.batch = sm;
+    if (g->iterations) g->last_primary = g->selected;          // (the call ends with a primary pass: whose G-buffer evplp_group_denoise reads)
+    return post_pass(g, c);
+}
+extern "C" int evplp_group_path_trace_batch_scratch(evplp_group *g, uint64_t bytes) {
+    GRP_CHECK(g);
+    drain(g);
+    int rc = group_status(g); if (rc < 0) return rc;
+    for (int r = 0; r < g->n; r++) evplp_path_trace_batch_scratch(g->ctx[(size_t)r], bytes);
+    g->pt_batch_cap = bytes;
+    return EVPLP_OK;
 }
 
 // Composite every strip on its GPU and all-gather the strips: every GPU then holds the frame, strip by strip.  This is

@@ -592,6 +592,20 @@ public:
         noise.parse(json, out_dir, out_dir, res_x, res_y, frame_mode);
         if (json.has("adaptive")) throw JsonError("adaptive: not for pt (VPL and VSL gathers only; pt takes \"adaptiveSampling\")");
         adaptive.parse(json, out_dir, frame_mode, false, run_options(json).shard_iterations, noise);                // build-only key "adaptiveSampling"
+        // build-only key "samplesPerCall": S iterations per evplp_group_path_trace_batch call (default 1: the loop below as it always was).
+        // Folds and retirements must fall on the iteration numbers they have with S = 1 -- a run is then the same bits for every S -- so
+        // batchIterations (and with it everyIterations of both blocks, its multiples) must be a multiple of S
+        if (json.has("samplesPerCall")) {
+            const long long spc = json.at("samplesPerCall").as_int("samplesPerCall");
+            if (spc < 1 || spc > 64) throw JsonError("samplesPerCall: must be 1 .. 64");
+            samples_per_call = (int)spc;
+        }
+        if (samples_per_call > 1) {
+            if (frame_mode == 2) throw JsonError("samplesPerCall: frameMode \"cleareveryframe\" shows single samples (a batch always accumulates)");
+            if (write_every_frame) throw JsonError("samplesPerCall: writeEveryFrame needs every iteration's frame (use samplesPerCall 1)");
+            if (noise.on && noise.batch_iterations() % samples_per_call != 0)
+                throw JsonError(std::string("samplesPerCall: noise.batchIterations") + (adaptive.on ? " (adaptiveSampling folds with it)" : "") + " must be a multiple of it");
+        }
 
         evplp_config cfg; std::memset(&cfg, 0, sizeof(cfg));
         cfg.abi_version = EVPLP_ABI_VERSION; cfg.device = device; cfg.res_x = res_x; cfg.res_y = res_y;
@@ -616,7 +630,39 @@ private:
         auto elapsed_ms = [&]() { return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
         std::vector<float> rgb((size_t)W * H * 3);
         const bool clear_every_frame = frame_mode == 2;
-        for (;;) {
+        // samplesPerCall > 1: a batch of S iterations per call -- the same jitter stream and seeds as the loop below; the last batch is trimmed
+        // at numMaxIteration; the time limit and the checkpoints are looked at once per batch (a convergence checkpoint that falls inside a
+        // batch is taken at the batch's end, under that iteration number; folds and retirements fall on batch ends by construction)
+        while (samples_per_call > 1) {
+            if (num_iterations >= num_max_iteration) break;
+            const int n = std::min(samples_per_call, num_max_iteration - num_iterations);
+            float jitters[64][2] = {}; uint32_t seeds[64];
+            for (int i = 0; i < n; i++) {
+                if (use_jitter) sampler.next_jitter(W, H, jitters[i]);
+                seeds[i] = (uint32_t)(num_iterations + i) + rng_offset;
+            }
+            check(h, evplp_group_path_trace_batch(h, scene.camera.origin, n, &jitters[0][0], seeds, (uint32_t)num_max_bounce), "path trace batch");
+            const int first = num_iterations + 1;
+            num_iterations += n;
+            if (time_limit_ms < 1e8f) check(h, evplp_group_synchronize(h), "sync");
+            bool conv_due = false;
+            for (int i = first; i <= num_iterations && !conv_due; i++) conv_due = conv.due(i, elapsed_ms());
+            if (conv_due) {
+                const Composite k = composite(num_iterations);
+                if (conv.checkpoint(h, num_iterations, [&] { check(h, evplp_group_synchronize(h), "sync"); return (double)elapsed_ms(); }, k.vs, k.ps, k.ls, k.mask_emitter)) break;
+            }
+            if (noise.on) {
+                bool folded = false;
+                for (int i = 0; i < n; i++) folded = noise.after_iteration(h, 0) || folded;       // (a fold can only fall on the batch's last iteration)
+                const Composite k = composite(num_iterations);
+                adaptive.after_fold(h, num_iterations, folded, k.vs, noise);
+                if (noise.due(num_iterations, elapsed_ms(), folded) &&
+                    noise.checkpoint(h, num_iterations, [&] { check(h, evplp_group_synchronize(h), "sync"); return (double)elapsed_ms(); }, k.vs, k.ls, k.mask_emitter)) break;
+                if (adaptive.all_retired(noise)) break;
+            }
+            if (elapsed_ms() >= time_limit_ms) break;
+        }
+        if (samples_per_call <= 1) for (;;) {
             if (num_iterations == num_max_iteration) break;                                   // :610-613
             float jitter[2] = { 0.f, 0.f };
             if (use_jitter) sampler.next_jitter(W, H, jitter);                                // :618-624
@@ -669,7 +715,7 @@ private:
         if (save_image(path.c_str(), W, H, top.data()) != EVPLP_OK) throw std::runtime_error("cannot write " + path);
     }
 
-    uint32_t rng_offset = 0; int num_max_iteration = 0, num_max_bounce = 0, frame_mode = 1;
+    uint32_t rng_offset = 0; int num_max_iteration = 0, num_max_bounce = 0, frame_mode = 1, samples_per_call = 1;
     float time_limit_ms = 0.f;
     bool use_jitter = false, use_stat = false, write_every_frame = false;
     std::string output_filename, stat_filename;

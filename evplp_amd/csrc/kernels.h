@@ -139,6 +139,31 @@ struct PathTraceArgs {
     PassCounters *counters;
 };
 
+// evplp_path_trace_batch: S complete iterations (primary visibility + one camera path) of the ACTIVE tiles in one call.  The active tiles
+// are a compacted list (pt_batch_list_kernel; its count stays on the device) and the work is enumerated as (list entry, sample) items, one
+// wavefront each, lane = pixel: a thin tail of noisy tiles still fills the machine.  An item owns one staging SLOT, [4 planes][64 lanes]
+// float4: the batched primary writes the sample's four texels there, the batched trace reads them and puts (r, g, b, valid) of the sample
+// into plane 0, and the reduce adds the samples to VPL_ACCUM one at a time in increasing s -- the order of S single calls.
+constexpr int kPtBatchMaxSamples = 64;
+constexpr size_t kPtBatchSlotBytes = 4 * 64 * sizeof(float4);      // 64 B per pixel-sample
+struct PtBatchSamples { float jitter[kPtBatchMaxSamples][2]; uint32_t seed[kPtBatchMaxSamples]; };
+// one chunk of a call: the list entries [entry_first, entry_first + entry_count) x the samples [sample_first, sample_first + sample_count);
+// item = (entry - entry_first) * sample_count + (sample - sample_first), and slot = item.  A tile's samples follow each other in the
+// grid, so the workgroup dispatcher's round-robin deals them over all eight XCDs (as the gather's item_deal = 1 does for small launches).
+struct PtBatchChunk {
+    const int32_t *list, *count;      // the active tiles in increasing order and how many; null: every tile of the planes (adaptivity off)
+    int32_t tiles;                    // tiles of the context's planes: entries at or beyond the count exit
+    int32_t entry_first, entry_count, sample_first, sample_count, pad;
+    float4 *staging;                  // [entry_count * sample_count] slots
+    unsigned long long cut_mask;      // bit s: sample s's jitter lies within the eye's entry cuts (evplp_primary's test); else it walks from the root
+};
+void launch_pt_batch_list(const int4 *tiles, int32_t ntiles, int32_t *list, int32_t *count, hipStream_t s);
+void launch_pt_batch_primary(const PrimaryArgs &a, const PtBatchSamples &sm, const PtBatchChunk &ch, hipStream_t s);      // a.jitter, a.clear_light, the planes but g_light: unused
+void launch_pt_batch_trace(const PathTraceArgs &a, const PtBatchSamples &sm, const PtBatchChunk &ch, hipStream_t s);      // a.rng_seed, the planes, a.out: unused; a.do_accumulate must be 0
+void launch_pt_batch_reduce(const StripDev &st, float4 *out, const PtBatchChunk &ch, hipStream_t s);
+// the retired tiles' pixels: (float)(R * (ad.n1 / n_t)) in fp64, ad.n1 = N + S (path_trace_kernel<true>'s arithmetic)
+void launch_pt_batch_rescale(const StripDev &st, float4 *out, const AdaptArgs &ad, int32_t ntiles, hipStream_t s);
+
 constexpr int kSummaryShards = 1024, kSummaryStride = 32, kSummaryFinal = kSummaryShards * kSummaryStride;
 constexpr int kSummaryHeavy = kSummaryFinal + 8;     // tiles on the heavy list of this pass (splat_heavy_kernel)
 // Two-level binning of the photon splat, without contended atomics.  Measured (tools/ub/atomics.hip): returning atomics on

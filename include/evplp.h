@@ -122,6 +122,9 @@ typedef struct evplp_config {
      *   noise tracking (if on)          56 B per pixel of the context's planes (+ 1 B per image pixel with a mask; evplp_noise_track)
      *   adaptive gather (if enabled)    16 B per pixel of the context's planes (snapshot) + 16 B per 8 x 8 tile (evplp_adaptive_enable; the same for
      *                                   adaptive path tracing, evplp_adaptive_enable_pt: one mode at a time, one allocation)
+     *   batched path tracing            64 B per pixel-sample of one chunk: min(tiles x S, bound / 4096) slots of 4 KB, allocated on the first
+     *   (after a call)                  evplp_path_trace_batch, bounded by evplp_path_trace_batch_scratch (default 1 GB: 1024^2 at S = 16 in one chunk),
+     *                                   + 4 B per tile in path-trace adaptive mode (the active-tile list)
      *   denoiser (after a call)         124 B per pixel of the context's planes (evplp_denoise); a group's rank: 92 B per pixel of its planes
      *                                   + n x 80 B per pixel of the exchanged rows, and rank 0 + 112 B per image pixel (evplp_group_denoise)
      * A caller that has the device to itself sets cut_scratch_bytes = 72 GB, vsl_mask_bytes = 14 GB for config #5 (one band, one launch). */
@@ -274,6 +277,43 @@ int evplp_gather_lvc(evplp_context *ctx, const evplp_frame_params *fp);
  * visible pixel continued from the G-buffer for at most max_bounces bounces, next-event estimation at every
  * vertex; radiance is ADDED to EVPLP_BUF_VPL_ACCUM when do_accumulate != 0, else replaces it ("outputBuffer"). */
 int evplp_path_trace(evplp_context *ctx, const float camera_pos[3], uint32_t rng_seed, uint32_t max_bounces, int32_t do_accumulate);
+/* S complete iterations of the "pt" technique in one call, for the ACTIVE tiles only.  It always accumulates, and the context's state after
+ * the call is its state after
+ *     for s in 0 .. samples - 1: evplp_primary(ctx, jitters + 2 s, 0); evplp_path_trace(ctx, camera_pos, rng_seeds[s], max_bounces, 1);
+ * jitters: [samples][2], rng_seeds: [samples]; both are read before the call returns.  The work is enumerated as (active tile, sample) items
+ * from a compacted list of the active 8 x 8 tiles (every tile when adaptivity is off): one wavefront each, so a thin tail of noisy tiles
+ * still fills the device and a retired tile costs nothing in either pass; there is no whole-frame G-buffer round trip between samples.
+ * Point by point:
+ *  - EVPLP_BUF_VPL_ACCUM, active tiles (every tile with adaptivity off): every in-image pixel is bit-identical to the sequence.  The samples
+ *    are added to the old value one at a time, in fp32, in increasing s; this is why the per-sample results are staged and not summed
+ *    first: out + r0 + r1 is not out + (r0 + r1).  A pixel whose stencil rejects sample s gains nothing for that s.
+ *  - EVPLP_BUF_VPL_ACCUM, retired tiles (evplp_adaptive_enable_pt; retired before the call): written once as
+ *    (float)((double)R * ((double)(N + samples) / (double)n_t)), the arithmetic of evplp_path_trace in that mode -- which is what the
+ *    sequence leaves, since every step of it rewrites the pixel from R.
+ *  - N advances by samples: evplp_adaptive_tiles, evplp_noise_fold(ctx, samples) and the frozen noise figures agree with the sequence.
+ *  - The four G-buffer planes and the tile boxes equal the sequence's: the call ends with the ordinary whole-frame evplp_primary at
+ *    jitters[samples - 1], flags 0 (the samples' own texels live in the staging buffer only).  The denoiser's guides and every other reader
+ *    of the planes see no difference.
+ *  - EVPLP_BUF_LIGHT, active tiles: bit-identical to the sequence -- every sample writes the emitter colour where evplp_primary would (all
+ *    samples write the same colour, so the concurrent writes do not race).
+ *  - EVPLP_BUF_LIGHT, retired tiles: a tile retired before the call receives only the closing pass's jitter, not the other samples'; every
+ *    non-zero pixel it has equals the sequence's pixel, but an emitter edge pixel that only an earlier sample's jitter would have lit may
+ *    stay as it was.
+ *  - Pass statistics: the call is ONE EVPLP_PASS_PATH_TRACE pass whose rays and pairs are the sums of the sequence's per-call figures
+ *    (retired tiles add nothing), and one EVPLP_PASS_PRIMARY pass (the closing one).
+ *  - Staging: 64 B per pixel-sample, 4 KB per (tile, sample), allocated on the first call and bounded by evplp_path_trace_batch_scratch
+ *    (default 1 GB).  If tiles x samples does not fit, the call runs the list in chunks (primary -> trace -> reduce each), down to one
+ *    (tile, sample) per chunk; the chunking changes no bit.  The launches are sized from the tile total -- the active count stays on the
+ *    device, there is no host round trip -- so with a small bound and few active tiles most chunks are empty launches.
+ *  - Refused with EVPLP_ERR_INVALID, the context staying usable: samples < 1 or > 64; a null array or camera position; a jitter that is not
+ *    finite; adaptivity on in gather mode (evplp_adaptive_enable), as evplp_path_trace is; a scratch bound below one (tile, sample), 4096 B.
+ * The trace kernel of this call inlines the same source as evplp_path_trace's and is held to the same choice of fused multiply-adds
+ * ("Adaptive path tracing, batched"; tests/test_pt_batch_same_arithmetic.py): a sample has evplp_path_trace's bits.
+ * evplp_path_trace_batch_scratch sets the bound for the calls that follow (any value is taken; a buffer above a lowered bound is released
+ * by the next call). */
+int evplp_path_trace_batch(evplp_context *ctx, const float camera_pos[3], int32_t samples, const float *jitters /* [samples][2] */,
+                           const uint32_t *rng_seeds /* [samples] */, uint32_t max_bounces);
+int evplp_path_trace_batch_scratch(evplp_context *ctx, uint64_t bytes);
 /* [photonSplat]: runPhotonSplat (:789-837); clear != 0 = cleareveryframe (:978-981); fp->splat_footprint selects the coverage rule */
 int evplp_splat_photons(evplp_context *ctx, const evplp_frame_params *fp, int32_t clear);
 /* setupPhotonSplatIcosohedron (rtcomphoton.h:632-644, called with "sphere/icosphere.obj" at :677): the proxy mesh of
@@ -539,6 +579,13 @@ int evplp_group_gather(evplp_group *g, const evplp_frame_params *fp, int32_t kin
 int evplp_group_splat_photons(evplp_group *g, const evplp_frame_params *fp, int32_t clear);
 int evplp_group_set_splat_proxy(evplp_group *g, const float *vertices, int32_t nverts, const int32_t *indices, int32_t ntris);
 int evplp_group_path_trace(evplp_group *g, const float camera_pos[3], uint32_t rng_seed, uint32_t max_bounces, int32_t do_accumulate);
+/* evplp_path_trace_batch, routed like evplp_group_path_trace: a strips group runs it on every rank for its own rows (the result equals one
+ * context's bit for bit; evplp_set_blocks / evplp_group_rebalance behave as for evplp_group_path_trace), an iterations group on the selected
+ * rank.  The arrays are copied before the call returns.  Every refusal of evplp_path_trace_batch is raised here, on the caller's thread, and
+ * leaves the group usable.  The scratch bound is per rank. */
+int evplp_group_path_trace_batch(evplp_group *g, const float camera_pos[3], int32_t samples, const float *jitters /* [samples][2] */,
+                                 const uint32_t *rng_seeds /* [samples] */, uint32_t max_bounces);
+int evplp_group_path_trace_batch_scratch(evplp_group *g, uint64_t bytes);
 int evplp_group_synchronize(evplp_group *g);
 /* EVPLP_PARTITION_ITERATIONS: the rank the single-rank pass calls go to from now on (see the partition enum).  Other partitions, or a rank out
  * of range: EVPLP_ERR_INVALID. */

@@ -1,0 +1,80 @@
+"""No GPU needed: the code objects of the batched path tracer (evplp_path_trace_batch).  Its kernels live in two new translation units --
+kernels_ptbatch_primary.hip, built like kernels_trace.hip with -ffp-contract=off for the whole unit, and kernels_ptbatch.hip with the
+path tracer's default flags -- and are held to zero scratch, no VGPR spills, 64 registers for the batched primary (eight waves per SIMD, as
+primary_kernel) and 128 for the batched trace (four, as path_trace_kernel).  kernels_pt.hip and kernels_trace.hip keep exactly their kernels."""
+import os
+import re
+import subprocess
+
+import pytest
+
+from test_kernel_resources import FLAGS, HIPCC, ROOT, kernel_table
+
+pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+
+FIELDS = r"\s+\.(name|private_segment_fixed_size|vgpr_count|vgpr_spill_count|sgpr_spill_count|group_segment_fixed_size):\s+(\S+)"
+
+
+def table_of(src, extra=()):
+    """kernel_table of tests/test_kernel_resources.py with extra flags (it knows -ffp-contract=off for kernels_trace.hip only)"""
+    out = subprocess.run([HIPCC] + FLAGS + list(extra) + ["-o", "-", os.path.join(ROOT, "evplp_amd", "csrc", src)], capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    table, cur = {}, {}
+    for line in out.stdout.splitlines():
+        m = re.match(FIELDS, line)
+        if not m:
+            continue
+        cur[m.group(1)] = m.group(2)
+        if m.group(1) == "vgpr_spill_count":
+            table[cur.get("name", "?")] = {k: int(v) for k, v in cur.items() if k != "name"}
+            cur = {}
+    return table
+
+
+def only(table, want):
+    hits = [k for k in table if want in k]
+    assert len(hits) == 1, (want, sorted(table))
+    return table[hits[0]]
+
+
+def test_the_makefile_builds_the_batched_primary_without_contraction():
+    mk = open(os.path.join(ROOT, "Makefile")).read()
+    assert re.search(r"^\$\(BUILD\)/kernels_ptbatch_primary\.o: HIPFLAGS \+= -ffp-contract=off\s*$", mk, re.M)
+    assert not re.search(r"^\$\(BUILD\)/kernels_ptbatch\.o:.*-ffp-contract=off", mk, re.M)       # the trace keeps path_trace_kernel's flags
+    for src in ("kernels_ptbatch.hip", "kernels_ptbatch_primary.hip"):
+        assert "$(CSRC)/" + src in mk, src
+
+
+def test_batched_primary_keeps_the_budget():
+    table = table_of("kernels_ptbatch_primary.hip", ["-ffp-contract=off"])
+    assert len(table) == 1, sorted(table)
+    t = only(table, "pt_batch_primary_kernel")
+    assert t["private_segment_fixed_size"] == 0 and t["vgpr_spill_count"] == 0, t
+    assert t["vgpr_count"] <= 64, t
+
+
+def test_batched_trace_list_reduce_and_rescale_keep_their_budgets():
+    table = table_of("kernels_ptbatch.hip")
+    names = ("pt_batch_list_kernel", "pt_batch_trace_kernel", "pt_batch_reduce_kernel", "pt_batch_rescale_kernel")
+    assert len(table) == len(names), sorted(table)
+    for n in names:
+        t = only(table, n)
+        assert t["private_segment_fixed_size"] == 0 and t["vgpr_spill_count"] == 0, (n, t)
+    assert only(table, "pt_batch_trace_kernel")["vgpr_count"] <= 128
+    assert only(table, "pt_batch_list_kernel")["group_segment_fixed_size"] <= 128              # (the scan's wave counts: no atomics, no big LDS)
+
+
+def test_the_existing_units_keep_exactly_their_kernels():
+    pt = kernel_table("kernels_pt.hip")
+    assert len(pt) == 2 and all("path_trace_kernelILb" in k for k in pt), sorted(pt)
+    trace = kernel_table("kernels_trace.hip")
+    want = ["primary_kernel", "light_trace_kernel", "compact_vpl_kernel", "frame_error_kernel", "noise_fold_frozen_kernel", "noise_pool_kernel",
+            "noise_rows_kernel", "noise_rows_frozen_kernel", "noise_variance_kernel", "noise_variance_frozen_kernel", "adaptive_retire_kernel",
+            "noise_fold_kernelILb1E", "noise_fold_kernelILb0E"]
+    assert len(trace) == len(want), sorted(trace)
+    for n in want:
+        assert sum(1 for k in trace if re.search(r"\d" + n, k)) == 1, (n, sorted(trace))
+    assert not [k for k in list(pt) + list(trace) if "pt_batch" in k]
+    p, lt = only(trace, "14primary_kernel"), only(trace, "light_trace_kernel")
+    assert p["private_segment_fixed_size"] == 0 and p["vgpr_spill_count"] == 0 and p["vgpr_count"] <= 64, p
+    assert lt["private_segment_fixed_size"] == 0 and lt["vgpr_spill_count"] == 0 and lt["vgpr_count"] <= 128, lt

@@ -19,6 +19,9 @@ median and p10 - p90):
   * active: call time at about 100 / 50 / 25 / 10 / 5 % active tiles (tileRelMse taken from the quantiles of the tile means after four
     samples); its first row is a control with adaptivity off on both groups.
 --plain-calls N: nothing but N plain path-tracing calls, timed the same way (for a side-by-side of two builds of the library, EVPLP_LIB).
+--pair-calls N: nothing but N pairs evplp_primary + evplp_path_trace in path-trace mode with nothing retired (the same, for two checkouts).
+--samples-per-call 4,16: the per-sample time of evplp_path_trace_batch against the active fraction, beside the pair's; prints it and ends.
+--curve-batch S: the curves (not the reference) run S iterations per call through evplp_path_trace_batch; --no-tables: the curves only.
 
 usage: python tools/adaptive_convergence.py [--technique photonfam|pt] [--iters N] [--ref-iters N] [--taus 0.002,0.0005] [--every N]
                                             [--min-batches N] [--calls N] [--plain-calls N]"""
@@ -62,6 +65,11 @@ class PtRunner:
 
     def iteration(self, i):
         self.g.primary(tuple(self.js[i % len(self.js)])); self.g.path_trace(self.sd.cam_origin, i, 3)
+
+    def batch(self, i, S):
+        """iterations i .. i + S - 1 as one evplp_path_trace_batch: the same jitters and seeds, the same bits"""
+        js = np.array([self.js[(i + k) % len(self.js)] for k in range(S)], np.float32)
+        self.g.path_trace_batch(self.sd.cam_origin, js, np.arange(i, i + S, dtype=np.uint32), 3)
 
 
 PASS = ev.PASS_GATHER_VPL          # the pass whose work retirement saves (main() switches it for --technique pt)
@@ -118,25 +126,74 @@ def pt_tables(g, plain, sd, tiles, calls):
     return rows[:-1], rows[-1]
 
 
-def curve(g, run, iters, every, tau, min_batches, tiles):
+def batch_table(g, sd, tiles, calls, sizes):
+    """--samples-per-call: host wall time PER SAMPLE of a synchronised iteration against the fraction of active tiles -- through the pair of
+    calls (primary + path_trace) and through evplp_path_trace_batch with S samples, alternating call by call in one process"""
+    run = PtRunner(g, sd)
+    cam = sd.cam_origin
+    rows = []
+    for want in (1.0, 0.5, 0.25, 0.10, 0.05):
+        g.clear_accumulators(); g.noise_track(True); g.adaptive_enable(True, path_trace=True)
+        for i in range(4):
+            run.iteration(i); g.noise_fold(1)
+        retired = g.adaptive_retire(0.25, float(np.quantile(tile_means_of(g, 4), 1.0 - want)), 2) if want < 1.0 else 0
+        out = {"pair": []}
+        out.update({f"batch_{S}": [] for S in sizes})
+        i = 4
+        for _ in range(calls):
+            g.synchronize(); t0 = time.perf_counter()
+            run.iteration(i); g.synchronize()
+            out["pair"].append((time.perf_counter() - t0) * 1e3); i += 1
+            for S in sizes:
+                js = np.array([run.js[(i + k) % len(run.js)] for k in range(S)], np.float32)
+                seeds = np.arange(i, i + S, dtype=np.uint32)
+                g.synchronize(); t0 = time.perf_counter()
+                g.path_trace_batch(cam, js, seeds, 3); g.synchronize()
+                out[f"batch_{S}"].append((time.perf_counter() - t0) * 1e3 / S); i += S
+        rows.append({"active_fraction": 1.0 - retired / tiles, "ms_per_sample": {k: spread(v) for k, v in out.items()}})
+        g.clear_accumulators(); g.adaptive_enable(False, path_trace=True)
+    return rows
+
+
+def pair_calls(g, run, calls):
+    """--pair-calls: `calls` synchronised pairs evplp_primary + evplp_path_trace in path-trace adaptive mode with nothing retired (the
+    100 % row of the batch table), host wall time and the two passes' own times: uses only calls that the parent build has too"""
+    g.clear_accumulators(); g.noise_track(True); g.adaptive_enable(True, path_trace=True)
+    for i in range(4):
+        run.iteration(i); g.noise_fold(1)
+    wall, pt, pr = [], [], []
+    for i in range(4, 4 + calls):
+        g.synchronize(); t0 = time.perf_counter()
+        run.iteration(i); g.synchronize()
+        wall.append((time.perf_counter() - t0) * 1e3)
+        pt.append(g.context(0).pass_stats(ev.PASS_PATH_TRACE)["ms"]); pr.append(g.context(0).pass_stats(ev.PASS_PRIMARY)["ms"])
+    checksum = float(g.resolve(1.0, 0.0, 0.0).astype(np.float64).sum())
+    g.clear_accumulators(); g.adaptive_enable(False, path_trace=True)
+    return {"wall_ms": spread(wall), "path_trace_pass_ms": spread(pt), "primary_pass_ms": spread(pr), "accumulator_sum": checksum}
+
+
+def curve(g, run, iters, every, tau, min_batches, tiles, S=1):
     g.clear_accumulators(); g.noise_track(True)
     if tau is not None:
         g.adaptive_enable(True, path_trace=PASS == ev.PASS_PATH_TRACE)
     g.synchronize()
     wall = 0.0; pts = []; retired = 0; gms = []
-    for i in range(iters):
+    for i in range(S - 1, iters, S):                             # i: the last iteration of this step (S = 1: every iteration)
         t0 = time.perf_counter()
-        run.iteration(i); g.noise_fold(1)
+        if S == 1:
+            run.iteration(i); g.noise_fold(1)
+        else:
+            run.batch(i - S + 1, S); g.noise_fold(S)
         if tau is not None and (i + 1) % every == 0:
             retired += g.adaptive_retire(1.0 / (i + 1), tau, min_batches)
         g.synchronize()
         wall += (time.perf_counter() - t0) * 1e3
-        gms.append(gather_ms(g))
+        gms.append(gather_ms(g) / S)
         if (i + 1) % every == 0:
             s = 1.0 / (i + 1)
             e = g.frame_error(s, s, 1.0)
             pts.append({"iteration": i + 1, "wall_ms": wall, "rel_mse": e[1], "retired_tiles": retired,
-                        "gather_ms": statistics.median(gms[-every:])})
+                        "gather_ms": statistics.median(gms[-(every // S):])})
     return pts, retired
 
 
@@ -150,8 +207,14 @@ def main():
     ap.add_argument("--technique", choices=("photonfam", "pt"), default="photonfam")
     ap.add_argument("--calls", type=int, default=40)
     ap.add_argument("--plain-calls", type=int, default=0)
+    ap.add_argument("--samples-per-call", default="", help="pt: comma-separated batch sizes; prints the per-sample time table against the active fraction and ends")
+    ap.add_argument("--curve-batch", type=int, default=1, help="pt: the curves run S iterations per call through evplp_path_trace_batch (S divides --every and --iters); "
+                    "--min-batches then counts folds of S")
+    ap.add_argument("--pair-calls", type=int, default=0, help="pt: nothing but N pairs primary + path_trace in path-trace mode, nothing retired (for two builds side by side)")
+    ap.add_argument("--no-tables", action="store_true", help="pt: the curves only")
     a = ap.parse_args()
-    pt = a.technique == "pt" or a.plain_calls > 0
+    assert a.curve_batch >= 1 and a.every % a.curve_batch == 0 and a.iters % a.curve_batch == 0, "--curve-batch must divide --every and --iters"
+    pt = a.technique == "pt" or a.plain_calls > 0 or a.pair_calls > 0 or bool(a.samples_per_call)
     if pt:
         global PASS
         PASS = ev.PASS_PATH_TRACE
@@ -164,6 +227,13 @@ def main():
             g.load_scene_json(jp)
             bsr, total, _ = g.context(0).scene_metrics()
             run = PtRunner(g, sd) if pt else Runner(g, sd, total)
+            if a.samples_per_call:
+                sizes = [int(x) for x in a.samples_per_call.split(",") if x]
+                print(json.dumps({"library": ev.LIB_PATH, "shape": res["shape"], "tiles": tiles, "calls": a.calls, "batch_table": batch_table(g, sd, tiles, a.calls, sizes)}))
+                return
+            if a.pair_calls > 0:
+                print(json.dumps({"library": ev.LIB_PATH, "pair_of_calls": pair_calls(g, run, a.pair_calls)}))
+                return
             if a.plain_calls > 0:
                 g.clear_accumulators()
                 for i in range(4):
@@ -182,7 +252,7 @@ def main():
             for tau in [None] + [float(x) for x in a.taus.split(",") if x]:
                 g.clear_accumulators()                           # (N = 0: adaptivity can be switched)
                 g.adaptive_enable(False)
-                pts, retired = curve(g, run, a.iters, a.every, tau, a.min_batches, tiles)
+                pts, retired = curve(g, run, a.iters, a.every, tau, a.min_batches, tiles, a.curve_batch)
                 name = "plain" if tau is None else f"tileRelMse_{tau:g}"
                 runs[name] = {"points": pts, "retired_tiles": retired}
             g.clear_accumulators(); g.adaptive_enable(False)
@@ -200,6 +270,10 @@ def main():
                         hit = p0["wall_ms"] + t * (p1["wall_ms"] - p0["wall_ms"]); break
                 r["ms_to_plain_final_rel_mse"] = hit
             res["runs"] = runs
+            res["curve_samples_per_call"] = a.curve_batch
+            if pt and a.no_tables:
+                print(json.dumps(res))
+                return
             if pt:
                 with ev.Group(W, H, NL, NV, P, 1, devices=[0]) as plain:
                     plain.load_scene_json(jp)
