@@ -139,6 +139,10 @@ _SIGNATURES = {
     "evplp_adaptive_enable_pt": (C.c_int, [_P, C.c_int32]),
     "evplp_adaptive_retire": (C.c_int, [_P, C.c_float, C.c_float, C.c_int32, C.c_double, C.c_int32]),
     "evplp_adaptive_tiles": (C.c_int, [_P, _P, C.c_int32]),
+    "evplp_adaptive_set_budgets": (C.c_int, [_P, _P, C.c_int32]),
+    "evplp_adaptive_budgets": (C.c_int, [_P, _P, C.c_int32]),
+    "evplp_adaptive_tile_noise": (C.c_int, [_P, C.c_float, C.c_float, C.c_int32, _P, C.c_int32]),
+    "evplp_plan_budgets": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P]),
     "evplp_clear_accumulators": (C.c_int, [_P]),
     "evplp_set_blocks": (C.c_int, [_P, _P, C.c_int32]),
     "evplp_get_blocks": (C.c_int, [_P, _P, C.c_int32]),
@@ -197,6 +201,9 @@ _SIGNATURES = {
     "evplp_group_adaptive_enable_pt": (C.c_int, [_P, C.c_int32]),
     "evplp_group_adaptive_retire": (C.c_int, [_P, C.c_float, C.c_float, C.c_int32, C.c_double, C.c_int32]),
     "evplp_group_adaptive_tiles": (C.c_int, [_P, _P, C.c_int32]),
+    "evplp_group_adaptive_set_budgets": (C.c_int, [_P, _P, C.c_int32]),
+    "evplp_group_adaptive_budgets": (C.c_int, [_P, _P, C.c_int32]),
+    "evplp_group_adaptive_tile_noise": (C.c_int, [_P, C.c_float, C.c_float, C.c_int32, _P, C.c_int32]),
     "evplp_jitter_sequence": (C.c_int, [C.c_uint32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "evplp_json_query": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int32, C.POINTER(C.c_double), C.c_char_p, C.c_int32]),
     "evplp_progressive_step": (None, [C.c_int32, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.POINTER(C.c_float),
@@ -566,9 +573,11 @@ class Context:
         self._check(self._lib.evplp_denoise(self._h, float(scale), float(light_scale), int(mask_emitter), C.byref(p), _ptr(out)))
         return out
 
-    def adaptive_enable(self, on=True, path_trace=False):
+    def adaptive_enable(self, on=True, path_trace=False, budget=False):
         """Switch the adaptive gather on or off (before the first accumulating gather since the last clear; needs noise tracking; include/evplp.h).
         path_trace=True: path-trace mode instead (evplp_adaptive_enable_pt) -- path_trace() honours retirement and the gathers are refused"""
+        if budget:        # budget mode (evplp_adaptive_enable_pt(.., 2)): every tile takes its own number of samples of a path_trace_batch call
+            self._check(self._lib.evplp_adaptive_enable_pt(self._h, 2 if on else 0)); return
         f = self._lib.evplp_adaptive_enable_pt if path_trace else self._lib.evplp_adaptive_enable
         self._check(f(self._h, int(bool(on))))
 
@@ -581,6 +590,23 @@ class Context:
         """int32 (ceil(H / 8), ceil(W / 8)), tile rows from the bottom: n_t of a retired tile, N of an active one (0: another rank's)"""
         out = np.zeros(((self.H + 7) // 8, (self.W + 7) // 8), dtype=np.int32)
         self._check(self._lib.evplp_adaptive_tiles(self._h, _ptr(out), out.size))
+        return out
+
+    def adaptive_set_budgets(self, samples_per_tile):
+        """budget mode: samples of the next path_trace_batch calls per image tile, int32 (ceil(H / 8), ceil(W / 8)) in adaptive_tiles' layout, 0 .. 64"""
+        b = np.ascontiguousarray(samples_per_tile, dtype=np.int32)
+        self._check(self._lib.evplp_adaptive_set_budgets(self._h, _ptr(b), b.size))
+
+    def adaptive_budgets(self) -> np.ndarray:
+        """int32 (ceil(H / 8), ceil(W / 8)): the tiles' budgets, -1 = every sample of a call (0: another rank's)"""
+        out = np.zeros(((self.H + 7) // 8, (self.W + 7) // 8), dtype=np.int32)
+        self._check(self._lib.evplp_adaptive_budgets(self._h, _ptr(out), out.size))
+        return out
+
+    def adaptive_tile_noise(self, scale, light_scale=1.0, mask_emitter=False) -> np.ndarray:
+        """float64 (ceil(H / 8), ceil(W / 8)): the mean relative variance of every tile, the figure adaptive_retire compares with tile_rel_mse"""
+        out = np.zeros(((self.H + 7) // 8, (self.W + 7) // 8), dtype=np.float64)
+        self._check(self._lib.evplp_adaptive_tile_noise(self._h, float(scale), float(light_scale), int(mask_emitter), _ptr(out), out.size))
         return out
 
     def set_blocks(self, image_blocks=None):
@@ -673,6 +699,20 @@ def deal_blocks(costs, n_ranks: int, capacity_blocks: int) -> np.ndarray:
     if rc < 0:
         raise EvplpError(rc, "evplp_deal_blocks: the blocks do not fit the ranks' capacity")
     return owner
+
+
+def plan_budgets(rel, n_t, samples: int, min_samples: int = 1, tile_rel_mse: float = 0.0, reference_quantile: float = 1.0) -> np.ndarray:
+    """evplp_plan_budgets: samples of the next call per tile from the tiles' noise (adaptive_tile_noise) and sample counts (adaptive_tiles),
+    in the shape of n_t (host only, deterministic)"""
+    r = np.ascontiguousarray(rel, dtype=np.float64)
+    n = np.ascontiguousarray(n_t, dtype=np.int32)
+    if r.size != n.size:
+        raise ValueError(f"plan_budgets: {r.size} noise figures but {n.size} sample counts")
+    out = np.zeros(n.shape, dtype=np.int32)
+    rc = lib().evplp_plan_budgets(_ptr(r), _ptr(n), n.size, int(samples), int(min_samples), float(tile_rel_mse), float(reference_quantile), _ptr(out))
+    if rc < 0:
+        raise EvplpError(rc, "evplp_plan_budgets: samples 1 .. 64, min_samples 0 .. samples, reference_quantile in (0, 1], finite rel >= 0, >= 1 tile")
+    return out
 
 
 def split_model(num_light_paths: int, photons_per_path: int, n_ranks: int):
@@ -874,9 +914,11 @@ class Group:
         self._check(self._lib.evplp_group_denoise(self._h, float(scale), float(light_scale), int(mask_emitter), C.byref(p), _ptr(out)))
         return out
 
-    def adaptive_enable(self, on=True, path_trace=False):
+    def adaptive_enable(self, on=True, path_trace=False, budget=False):
         """Switch the adaptive gather on or off (before the first accumulating gather since the last clear; needs noise tracking; include/evplp.h).
         path_trace=True: path-trace mode instead (evplp_group_adaptive_enable_pt) -- path_trace() honours retirement and gather() is refused"""
+        if budget:        # budget mode (evplp_group_adaptive_enable_pt(.., 2)): every tile takes its own number of samples of a path_trace_batch call
+            self._check(self._lib.evplp_group_adaptive_enable_pt(self._h, 2 if on else 0)); return
         f = self._lib.evplp_group_adaptive_enable_pt if path_trace else self._lib.evplp_group_adaptive_enable
         self._check(f(self._h, int(bool(on))))
 
@@ -889,6 +931,23 @@ class Group:
         """int32 (ceil(H / 8), ceil(W / 8)), tile rows from the bottom: n_t of a retired tile, N of an active one (0: another rank's)"""
         out = np.zeros(((self.H + 7) // 8, (self.W + 7) // 8), dtype=np.int32)
         self._check(self._lib.evplp_group_adaptive_tiles(self._h, _ptr(out), out.size))
+        return out
+
+    def adaptive_set_budgets(self, samples_per_tile):
+        """budget mode: samples of the next path_trace_batch calls per image tile, int32 (ceil(H / 8), ceil(W / 8)) in adaptive_tiles' layout, 0 .. 64"""
+        b = np.ascontiguousarray(samples_per_tile, dtype=np.int32)
+        self._check(self._lib.evplp_group_adaptive_set_budgets(self._h, _ptr(b), b.size))
+
+    def adaptive_budgets(self) -> np.ndarray:
+        """int32 (ceil(H / 8), ceil(W / 8)): the tiles' budgets, -1 = every sample of a call (0: another rank's)"""
+        out = np.zeros(((self.H + 7) // 8, (self.W + 7) // 8), dtype=np.int32)
+        self._check(self._lib.evplp_group_adaptive_budgets(self._h, _ptr(out), out.size))
+        return out
+
+    def adaptive_tile_noise(self, scale, light_scale=1.0, mask_emitter=False) -> np.ndarray:
+        """float64 (ceil(H / 8), ceil(W / 8)): the mean relative variance of every tile, the figure adaptive_retire compares with tile_rel_mse"""
+        out = np.zeros(((self.H + 7) // 8, (self.W + 7) // 8), dtype=np.float64)
+        self._check(self._lib.evplp_group_adaptive_tile_noise(self._h, float(scale), float(light_scale), int(mask_emitter), _ptr(out), out.size))
         return out
 
 

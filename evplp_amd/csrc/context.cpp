@@ -207,7 +207,7 @@ extern "C" void evplp_destroy(evplp_context *c) {
     hipFree(c->d_noise); hipFree(c->d_noise_keep); hipFree(c->d_noise_rows);
     hipFree(c->d_adapt_tiles); hipFree(c->d_adapt_snap);
     hipFree(c->d_dn_var); hipFree(c->d_dn_pack); hipFree(c->d_dn_u);
-    hipFree(c->d_pt_batch); hipFree(c->d_pt_list);
+    hipFree(c->d_pt_batch); hipFree(c->d_pt_list); hipFree(c->d_pt_first); hipFree(c->d_pt_table); hipFree(c->d_tile_noise);
     for (int i = 0; i < EVPLP_PASS_COUNT; i++) {
         if (c->ev_begin[i]) hipEventDestroy(c->ev_begin[i]);
         if (c->ev_end[i]) hipEventDestroy(c->ev_end[i]);
@@ -879,6 +879,7 @@ extern "C" int evplp_gather_lvc(evplp_context *c, const evplp_frame_params *fp) 
 extern "C" int evplp_path_trace(evplp_context *c, const float camera_pos[3], uint32_t rng_seed, uint32_t max_bounces, int32_t do_accumulate) {
     CTX_CHECK(c);
     if (c->d_adapt_tiles && !c->adapt_pt) { c->set_error("evplp_path_trace: adaptivity is on (evplp_adaptive_enable): VPL and VSL gathers only"); return EVPLP_ERR_INVALID; }
+    if (c->adapt_budget) { c->set_error("evplp_path_trace: budget mode (evplp_adaptive_enable_pt(ctx, 2)): evplp_path_trace_batch only"); return EVPLP_ERR_INVALID; }
     if (c->adapt_pt && !do_accumulate) { c->set_error("evplp_path_trace: adaptivity is on (evplp_adaptive_enable_pt): a sample must accumulate"); return EVPLP_ERR_INVALID; }
     int rc = pass_ready(c, "evplp_path_trace", false); if (rc) return rc;
     if (!camera_pos) { c->set_error("evplp_path_trace: null camera position"); return EVPLP_ERR_INVALID; }
@@ -927,7 +928,10 @@ extern "C" int evplp_path_trace_batch(evplp_context *c, const float camera_pos[3
     if (ntiles > 0) {
         // the staging buffer: what the call needs, within the bound; it only grows, unless the bound came down below it
         const uint64_t cap_slots = std::min<uint64_t>(c->pt_batch_cap / kPtBatchSlotBytes, 1u << 30);
-        const uint64_t slots = std::min<uint64_t>((uint64_t)ntiles * (uint64_t)samples, cap_slots);
+        // (budget mode: the items are the tiles' own sample counts, known from the records' host copy; the device builds the table itself)
+        uint64_t budget_items = 0;
+        if (c->adapt_budget) for (const int4 &r : c->adapt_tiles) budget_items += (uint64_t)(r.w < 0 ? samples : std::min(r.w, samples));
+        const uint64_t slots = std::min<uint64_t>(c->adapt_budget ? std::max<uint64_t>(budget_items, 1) : (uint64_t)ntiles * (uint64_t)samples, cap_slots);
         if (c->pt_batch_bytes < slots * kPtBatchSlotBytes || c->pt_batch_bytes > cap_slots * kPtBatchSlotBytes) {
             HIP_TRY(c, hipStreamSynchronize(c->stream));
             if (c->d_pt_batch) { hipFree(c->d_pt_batch); c->d_pt_batch = nullptr; c->pt_batch_bytes = 0; }
@@ -938,7 +942,7 @@ extern "C" int evplp_path_trace_batch(evplp_context *c, const float camera_pos[3
             }
             c->pt_batch_bytes = slots * kPtBatchSlotBytes;
         }
-        if (c->adapt_pt && !c->d_pt_list) HIP_TRY(c, hipMalloc((void **)&c->d_pt_list, sizeof(int32_t) * ((size_t)ntiles + 1)));
+        if (c->adapt_pt && !c->adapt_budget && !c->d_pt_list) HIP_TRY(c, hipMalloc((void **)&c->d_pt_list, sizeof(int32_t) * ((size_t)ntiles + 1)));
         const uint64_t have = c->pt_batch_bytes / kPtBatchSlotBytes;
         const int32_t chunk_entries = (int32_t)std::max<uint64_t>(1, std::min<uint64_t>(have / (uint64_t)samples, (uint64_t)ntiles));
         const int32_t chunk_samples = (int32_t)std::min<uint64_t>(have, (uint64_t)samples);
@@ -955,7 +959,28 @@ extern "C" int evplp_path_trace_batch(evplp_context *c, const float camera_pos[3
         if ((rc = pass_begin(c, EVPLP_PASS_PATH_TRACE))) return rc;
         PtBatchChunk ch; std::memset(&ch, 0, sizeof(ch));
         ch.tiles = ntiles; ch.staging = (float4 *)c->d_pt_batch; ch.cut_mask = cut_mask;
-        if (c->adapt_pt) {
+        if (c->adapt_budget) {
+            if (!c->d_pt_first) HIP_TRY(c, hipMalloc((void **)&c->d_pt_first, sizeof(int32_t) * ((size_t)ntiles + 1)));
+            if (c->pt_table_items < budget_items) {
+                HIP_TRY(c, hipStreamSynchronize(c->stream));
+                hipFree(c->d_pt_table); c->d_pt_table = nullptr; c->pt_table_items = 0;
+                HIP_TRY(c, hipMalloc((void **)&c->d_pt_table, sizeof(uint32_t) * budget_items));
+                c->pt_table_items = budget_items;
+            }
+            float4 *snap = c->d_adapt_snap;
+            launch_pt_budget_table(c->d_adapt_tiles, ntiles, samples, c->d_pt_first, c->d_pt_table, c->stream);
+            PtBudgetChunk bc; std::memset(&bc, 0, sizeof(bc));
+            bc.table = c->d_pt_table; bc.total = c->d_pt_first + ntiles; bc.staging = (float4 *)c->d_pt_batch; bc.cut_mask = cut_mask;
+            // a chunk is primary -> trace -> accumulate on the stream, so the adds to a pixel of R stay in increasing s whatever the cut
+            for (uint64_t i0 = 0; i0 < budget_items; i0 += have) {
+                bc.item_first = (int32_t)i0; bc.item_count = (int32_t)std::min<uint64_t>(have, budget_items - i0);
+                launch_pt_budget_primary(pa, sm, bc, c->stream);
+                launch_pt_budget_trace(ta, sm, bc, c->stream);
+                launch_pt_budget_accumulate(c->st, snap, c->d_pt_first, ntiles, bc, c->stream);
+            }
+            launch_pt_budget_finish(c->st, c->d_adapt_tiles, c->d_pt_first, snap, out, (int32_t)(c->adapt_n + samples), ntiles, c->stream);
+            for (int4 &r : c->adapt_tiles) r.x += r.w < 0 ? samples : std::min(r.w, samples);
+        } else if (c->adapt_pt) {
             // path-trace mode: the active tiles as a list (its count stays on the device: the launches are sized from the tile total and the
             // surplus items exit); the retired tiles are written once from the snapshot, for N + S
             launch_pt_batch_list(c->d_adapt_tiles, ntiles, c->d_pt_list, c->d_pt_list + ntiles, c->stream);
@@ -963,7 +988,7 @@ extern "C" int evplp_path_trace_batch(evplp_context *c, const float camera_pos[3
             AdaptArgs ad{}; ad.tiles = c->d_adapt_tiles; ad.snap = c->d_adapt_snap; ad.n1 = (int32_t)(c->adapt_n + samples);
             launch_pt_batch_rescale(c->st, out, ad, ntiles, c->stream);
         }
-        for (int32_t e0 = 0; e0 < ntiles; e0 += chunk_entries)
+        for (int32_t e0 = 0; e0 < ntiles && !c->adapt_budget; e0 += chunk_entries)
             for (int32_t s0 = 0; s0 < samples; s0 += chunk_samples) {
                 ch.entry_first = e0; ch.entry_count = std::min(chunk_entries, ntiles - e0);
                 ch.sample_first = s0; ch.sample_count = std::min(chunk_samples, samples - s0);
@@ -1270,7 +1295,10 @@ extern "C" int evplp_noise_fold(evplp_context *c, int32_t iterations) {
     if (iterations < 1) { c->set_error("evplp_noise_fold: a batch holds >= 1 iterations, not %d", iterations); return EVPLP_ERR_INVALID; }
     { int rc_ = settle_splat(c); if (rc_) return rc_; }            // (every splat of the batch has its verdict; a re-run is enqueued before the fold)
     HIP_TRY(c, hipSetDevice(c->cfg.device));
-    if (c->d_adapt_tiles)          // (retired pixels keep their Q and c_prev)
+    if (c->adapt_budget) {         // (per tile, k_t = n_t - K_t; the host copy of the records follows)
+        launch_noise_fold_budget(evplp::noise_planes(c), c->st, c->d_adapt_tiles, c->d_adapt_snap, c->tiles_x * c->tiles_y, c->stream);
+        for (int4 &r : c->adapt_tiles) if (r.x != r.y) { r.y = r.x; r.z += 1; }
+    } else if (c->d_adapt_tiles)          // (retired pixels keep their Q and c_prev)
         launch_noise_fold_adaptive(evplp::noise_planes(c), (const float4 *)c->buf[EVPLP_BUF_VPL_ACCUM], (const float4 *)c->buf[EVPLP_BUF_PHOTON_ACCUM],
                                    c->st, evplp::adapt_view(c, 1.0f), iterations, c->stream);
     else launch_noise_fold(evplp::noise_planes(c), (const float4 *)c->buf[EVPLP_BUF_VPL_ACCUM], (const float4 *)c->buf[EVPLP_BUF_PHOTON_ACCUM],
@@ -1398,7 +1426,7 @@ extern "C" int evplp_denoise(evplp_context *c, float scale, float ls, int32_t ma
 // ---- adaptive gather: tiles retire once their estimated noise is low enough (include/evplp.h evplp_adaptive_*)
 static void release_adapt(evplp_context *c) {
     hipFree(c->d_adapt_tiles); hipFree(c->d_adapt_snap);
-    c->d_adapt_tiles = nullptr; c->d_adapt_snap = nullptr; c->adapt_tiles.clear(); c->adapt_pt = false;
+    c->d_adapt_tiles = nullptr; c->d_adapt_snap = nullptr; c->adapt_tiles.clear(); c->adapt_pt = false; c->adapt_budget = false;
 }
 static size_t adapt_tile_count(const evplp_context *c) { return (size_t)c->tiles_x * (size_t)c->tiles_y; }
 // every tile active (stream order); the records are (re)allocated when the planes' tiles have changed (a new block table)
@@ -1407,6 +1435,7 @@ static int adapt_reset(evplp_context *c) {
     if (c->adapt_tiles.size() != nt) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         hipFree(c->d_adapt_tiles); hipFree(c->d_adapt_snap); c->d_adapt_tiles = nullptr; c->d_adapt_snap = nullptr;
+        hipFree(c->d_pt_first); hipFree(c->d_tile_noise); c->d_pt_first = nullptr; c->d_tile_noise = nullptr;       // (sized by the tile count too)
         hipError_t e = hipMalloc((void **)&c->d_adapt_tiles, sizeof(int4) * std::max<size_t>(nt, 1));
         if (e == hipSuccess) e = hipMalloc((void **)&c->d_adapt_snap, sizeof(float4) * std::max<size_t>(px, 1));
         if (e != hipSuccess) {
@@ -1415,7 +1444,14 @@ static int adapt_reset(evplp_context *c) {
             return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP;
         }
     }
-    c->adapt_tiles.assign(nt, make_int4(0, 0, 0, 0));
+    c->adapt_tiles.assign(nt, make_int4(0, 0, 0, c->adapt_budget ? -1 : 0));
+    if (c->adapt_budget) {
+        // budget mode: every record { 0, 0, 0, -1 } (all samples of a call), and the raw sums R start as the accumulator itself (N = 0)
+        if (nt) HIP_TRY(c, hipMemcpyAsync(c->d_adapt_tiles, c->adapt_tiles.data(), sizeof(int4) * nt, hipMemcpyHostToDevice, c->stream));
+        if (px) HIP_TRY(c, hipMemcpyAsync(c->d_adapt_snap, c->buf[EVPLP_BUF_VPL_ACCUM], sizeof(float4) * px, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return EVPLP_OK;
+    }
     HIP_TRY(c, hipMemsetAsync(c->d_adapt_tiles, 0, sizeof(int4) * std::max<size_t>(nt, 1), c->stream));
     return EVPLP_OK;
 }
@@ -1432,8 +1468,13 @@ static int adaptive_enable_mode(evplp_context *c, int32_t on, bool pt, const cha
         release_adapt(c);
         return EVPLP_OK;
     }
+    const bool budget = pt && on == 2;
+    if (budget && adapt_tile_count(c) >= (size_t)kPtBudgetMaxTiles) { c->set_error("%s: budget mode holds at most %d tiles", name, kPtBudgetMaxTiles - 1); return EVPLP_ERR_INVALID; }
+    const bool was = c->adapt_budget;
+    c->adapt_budget = budget;
     const int rc = adapt_reset(c);
     if (rc == EVPLP_OK) c->adapt_pt = pt;
+    else c->adapt_budget = c->d_adapt_tiles ? was : false;
     return rc;
 }
 extern "C" int evplp_adaptive_enable(evplp_context *c, int32_t on) { CTX_CHECK(c); return adaptive_enable_mode(c, on, false, "evplp_adaptive_enable"); }
@@ -1441,6 +1482,7 @@ extern "C" int evplp_adaptive_enable_pt(evplp_context *c, int32_t on) { CTX_CHEC
 extern "C" int evplp_adaptive_retire(evplp_context *c, float scale, float ls, int32_t mask_emitter, double tau, int32_t min_batches) {
     CTX_CHECK(c);
     if (!c->d_adapt_tiles) { c->set_error("evplp_adaptive_retire: adaptivity is off (evplp_adaptive_enable)"); return EVPLP_ERR_INVALID; }
+    if (c->adapt_budget) { c->set_error("evplp_adaptive_retire: budget mode (evplp_adaptive_enable_pt(ctx, 2)): set the tile's budget to 0 instead (evplp_adaptive_set_budgets)"); return EVPLP_ERR_INVALID; }
     if (!c->d_noise) { c->set_error("evplp_adaptive_retire: noise tracking is off (evplp_noise_track)"); return EVPLP_ERR_INVALID; }
     if (!(tau >= 0.0)) { c->set_error("evplp_adaptive_retire: tile_rel_mse must be >= 0, not %g", tau); return EVPLP_ERR_INVALID; }
     if (min_batches < 2) { c->set_error("evplp_adaptive_retire: min_batches must be >= 2, not %d", min_batches); return EVPLP_ERR_INVALID; }
@@ -1471,7 +1513,7 @@ void adaptive_tiles_into(const evplp_context *c, int32_t *out) {
         if (y < 0 || y >= c->st.H) continue;
         for (int tx = 0; tx < c->tiles_x; tx++) {
             const int32_t nt = c->adapt_tiles[(size_t)ty * c->tiles_x + tx].x;
-            out[(size_t)(y / 8) * itx + tx] = nt != 0 ? nt : (int32_t)c->adapt_n;
+            out[(size_t)(y / 8) * itx + tx] = nt != 0 || c->adapt_budget ? nt : (int32_t)c->adapt_n;
         }
     }
 }
@@ -1483,6 +1525,81 @@ extern "C" int evplp_adaptive_tiles(evplp_context *c, int32_t *out, int32_t capa
     if (!out || capacity < n) { c->set_error("evplp_adaptive_tiles: the image has %lld tiles, the output holds %d", (long long)n, capacity); return EVPLP_ERR_INVALID; }
     std::fill(out, out + n, 0);
     evplp::adaptive_tiles_into(c, out);
+    return (int)n;
+}
+
+// ---- budget mode of the path tracer (include/evplp.h evplp_adaptive_set_budgets): the image-tile layout is evplp_adaptive_tiles'
+static int64_t image_tile_count(const evplp_context *c) { return (int64_t)((c->st.W + 7) / 8) * ((c->st.H + 7) / 8); }
+// f(local tile, image tile) for every tile of the planes that lies in the image
+template <class F> static void for_own_tiles(const evplp_context *c, F f) {
+    const int itx = (c->st.W + 7) / 8;
+    for (int ty = 0; ty < c->tiles_y; ty++) {
+        const int y = c->st.global_row(ty * 8);
+        if (y < 0 || y >= c->st.H) continue;
+        for (int tx = 0; tx < c->tiles_x; tx++) f((size_t)ty * c->tiles_x + tx, (size_t)(y / 8) * itx + tx);
+    }
+}
+extern "C" int evplp_adaptive_set_budgets(evplp_context *c, const int32_t *samples_per_image_tile, int32_t count) {
+    CTX_CHECK(c);
+    const char *name = "evplp_adaptive_set_budgets";
+    if (!c->adapt_budget) { c->set_error("%s: budget mode is off (evplp_adaptive_enable_pt(ctx, 2))", name); return EVPLP_ERR_INVALID; }
+    const int64_t n = image_tile_count(c);
+    if (!samples_per_image_tile || count != n) { c->set_error("%s: the image has %lld tiles, the call gives %d", name, (long long)n, samples_per_image_tile ? count : 0); return EVPLP_ERR_INVALID; }
+    for (int64_t t = 0; t < n; t++)
+        if (samples_per_image_tile[t] < 0 || samples_per_image_tile[t] > kPtBatchMaxSamples) {
+            c->set_error("%s: tile %lld: a budget is 0 .. %d samples, not %d", name, (long long)t, kPtBatchMaxSamples, samples_per_image_tile[t]); return EVPLP_ERR_INVALID;
+        }
+    // (every tile then has B_t >= 2 and n_t >= 1 before one can fall behind: B_t - 1 and n_t are denominators)
+    if (c->noise_b < 2) { c->set_error("%s: %lld fold(s): budgets need >= 2 (evplp_noise_fold)", name, (long long)c->noise_b); return EVPLP_ERR_INVALID; }
+    if (c->noise_k != c->adapt_n) { c->set_error("%s: %lld of %lld samples are folded: fold first (evplp_noise_fold)", name, (long long)c->noise_k, (long long)c->adapt_n); return EVPLP_ERR_INVALID; }
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    for_own_tiles(c, [&](size_t local, size_t image) { c->adapt_tiles[local].w = samples_per_image_tile[image]; });
+    const size_t nt = adapt_tile_count(c);
+    if (nt) HIP_TRY(c, hipMemcpyAsync(c->d_adapt_tiles, c->adapt_tiles.data(), sizeof(int4) * nt, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return EVPLP_OK;
+}
+extern "C" int evplp_adaptive_budgets(evplp_context *c, int32_t *out, int32_t capacity) {
+    CTX_CHECK(c);
+    if (!c->adapt_budget) { c->set_error("evplp_adaptive_budgets: budget mode is off (evplp_adaptive_enable_pt(ctx, 2))"); return EVPLP_ERR_INVALID; }
+    const int64_t n = image_tile_count(c);
+    if (!out || capacity < n) { c->set_error("evplp_adaptive_budgets: the image has %lld tiles, the output holds %d", (long long)n, capacity); return EVPLP_ERR_INVALID; }
+    std::fill(out, out + n, 0);
+    evplp::adaptive_budgets_into(c, out);
+    return (int)n;
+}
+namespace evplp {
+void adaptive_budgets_into(const evplp_context *c, int32_t *out) {
+    for_own_tiles(c, [&](size_t local, size_t image) { out[image] = c->adapt_tiles[local].w; });
+}
+// (the composite the estimate measures first, as evplp_adaptive_retire forms it)
+int adaptive_tile_noise_into(evplp_context *c, float scale, float ls, int32_t mask_emitter, double *out) {
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    const size_t nt = adapt_tile_count(c);
+    if (nt && !c->d_tile_noise) HIP_TRY(c, hipMalloc((void **)&c->d_tile_noise, sizeof(double) * nt));
+    int rc = resolve_to_device(c, scale, scale, ls, mask_emitter, 0, true, false);
+    if (rc) return rc;
+    const double K = (double)c->noise_k, B = (double)c->noise_b;
+    launch_tile_noise(c->st, noise_moments_of(c), K, B, (double)scale * (double)scale * K, (const float4 *)c->buf[EVPLP_BUF_LIGHT], ls, mask_emitter,
+                      c->d_rgb, adapt_view(c, scale), (int32_t)nt, c->d_tile_noise, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<double> local(nt);
+    if (nt) HIP_TRY(c, hipMemcpyAsync(local.data(), c->d_tile_noise, sizeof(double) * nt, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for_own_tiles(c, [&](size_t l, size_t image) { out[image] = local[l]; });
+    return EVPLP_OK;
+}
+}
+extern "C" int evplp_adaptive_tile_noise(evplp_context *c, float scale, float ls, int32_t mask_emitter, double *rel_per_image_tile, int32_t capacity) {
+    CTX_CHECK(c);
+    const char *name = "evplp_adaptive_tile_noise";
+    if (!c->d_adapt_tiles) { c->set_error("%s: adaptivity is off (evplp_adaptive_enable)", name); return EVPLP_ERR_INVALID; }
+    const int64_t n = image_tile_count(c);
+    if (!rel_per_image_tile || capacity < n) { c->set_error("%s: the image has %lld tiles, the output holds %d", name, (long long)n, capacity); return EVPLP_ERR_INVALID; }
+    int rc = noise_ready(c, name);
+    if (rc) return rc;
+    std::fill(rel_per_image_tile, rel_per_image_tile + n, 0.0);
+    if ((rc = evplp::adaptive_tile_noise_into(c, scale, ls, mask_emitter, rel_per_image_tile))) return rc;
     return (int)n;
 }
 

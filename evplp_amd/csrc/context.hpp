@@ -36,6 +36,10 @@ int noise_rows(evplp_context *c, const NoiseMoments &m, const float4 *light, dou
 int noise_variance_to_device(evplp_context *c, const NoiseMoments &m, double K, double B, float scale);
 // evplp_adaptive_tiles' map of this context's tiles written into out [ceil(H / 8)][ceil(W / 8)] (rows from the bottom); other tiles untouched
 void adaptive_tiles_into(const evplp_context *c, int32_t *out);
+// budget mode: the own tiles' budgets / per-tile noise figures into a whole-image array (the other tiles are left as they are: a group's
+// ranks fill one array); set_budgets checks nothing but takes the own tiles from the array
+void adaptive_budgets_into(const evplp_context *c, int32_t *out);
+int adaptive_tile_noise_into(evplp_context *c, float scale, float ls, int32_t mask_emitter, double *out);
 // evplp_denoise (context.cpp), for the group's workers as well.  The parameters with the defaults filled in, checked: false and the reason in
 // why when they are refused.
 struct DenoiseSettings { int32_t levels; float sigma_l, sigma_n, sigma_x; };
@@ -160,6 +164,10 @@ struct evplp_context {
     // evplp_path_trace_batch: the staging slots of one chunk (kernels.h PtBatchChunk; allocated on the first call, bounded by pt_batch_cap --
     // evplp_path_trace_batch_scratch) and, in path-trace adaptive mode, the active-tile list [tiles] followed by its count [1]
     char *d_pt_batch = nullptr; size_t pt_batch_bytes = 0; uint64_t pt_batch_cap = 1ull << 30; int32_t *d_pt_list = nullptr;
+    // budget mode (evplp_adaptive_enable_pt(ctx, 2); kernels.h PtBudgetChunk): adapt_pt is set too; the records' host copy follows the device's
+    // in every field (a call adds s_t to n_t, a fold closes K_t and B_t: both are functions of the records alone); first [tiles + 1] and the
+    // item table [pt_table_items], which only grows; evplp_adaptive_tile_noise's per-tile doubles [tiles]
+    bool adapt_budget = false; int32_t *d_pt_first = nullptr; uint32_t *d_pt_table = nullptr; size_t pt_table_items = 0; double *d_tile_noise = nullptr;
     // evplp_denoise: the variance image [W * local_rows][3], the packed pixels of the planes [W * local_rows] (kernels.h DenoisePixel), and
     // the two (u, s) planes of the a-trous passes [2][dn_u_px] (the frame the context filters: its planes, or a group's whole image on rank 0);
     // allocated on the first call, kept until evplp_destroy

@@ -66,7 +66,7 @@ struct Rccl {
 };
 
 enum Op { OP_QUIT = 0, OP_CLEAR, OP_SYNC, OP_PRIMARY, OP_TRACE, OP_GATHER, OP_SPLAT, OP_PATH_TRACE, OP_PRESENT, OP_LOAD_SCENE, OP_SET_PROXY, OP_ASSEMBLE, OP_REDUCE, OP_SET_REFERENCE, OP_FRAME_ERROR,
-          OP_NOISE_TRACK, OP_NOISE_FOLD, OP_NOISE_POOL, OP_NOISE_ROWS, OP_NOISE_VARIANCE, OP_ADAPT_ENABLE, OP_ADAPT_RETIRE, OP_DENOISE_PREP, OP_DENOISE_FILTER, OP_PATH_TRACE_BATCH };
+          OP_NOISE_TRACK, OP_NOISE_FOLD, OP_NOISE_POOL, OP_NOISE_ROWS, OP_NOISE_VARIANCE, OP_ADAPT_ENABLE, OP_ADAPT_RETIRE, OP_DENOISE_PREP, OP_DENOISE_FILTER, OP_PATH_TRACE_BATCH, OP_ADAPT_SET_BUDGETS, OP_ADAPT_TILE_NOISE };
 // One posted call, copied into the ring by assignment: plain data (pointers must stay valid until the caller has drained: load_scene, set_proxy,
 // resolve do) but for `batch`, a shared pointer -- so every post and every worker-side copy of a command pays one atomic reference count, null or not.
 struct Cmd {
@@ -137,6 +137,7 @@ struct evplp_group {
     bool noise_on = false;                  // evplp_group_noise_track is on on every rank (caller's thread)
     bool adapt_on = false;                  // evplp_group_adaptive_enable is on on every rank (caller's thread)
     bool adapt_pt = false;                  // ... and in path-trace mode (evplp_group_adaptive_enable_pt)
+    bool adapt_budget = false;              // ... and that in budget mode (on = 2)
     uint64_t pt_batch_cap = 1ull << 30;     // evplp_group_path_trace_batch_scratch: every rank's bound (caller's thread)
     // EVPLP_PARTITION_ITERATIONS, evplp_group_noise_*: rank 0's pooled moments (Q then S, [3][stride] fp64 each) and K / B summed over the
     // ranks (written by rank 0's worker); RCCL only: per rank [n][noise_bytes] every rank's NoisePlanes (all-gathered)
@@ -417,6 +418,9 @@ static void worker_run(Worker *w, const Cmd &cmd) {
         case OP_ADAPT_ENABLE: rc = cmd.i[1] ? evplp_adaptive_enable_pt(c, cmd.i[0]) : evplp_adaptive_enable(c, cmd.i[0]); break;
         // (the count of tiles it retired stays in c->adapt_last)
         case OP_ADAPT_RETIRE: rc = evplp_adaptive_retire(c, cmd.f[0], cmd.f[1], cmd.i[0], cmd.d, cmd.i[1]); if (rc > 0) rc = EVPLP_OK; break;
+        // (every rank takes its own tiles from / puts them into the caller's whole-image array, which outlives the drain)
+        case OP_ADAPT_SET_BUDGETS: rc = evplp_adaptive_set_budgets(c, (const int32_t *)cmd.p0, cmd.i[0]); break;
+        case OP_ADAPT_TILE_NOISE: rc = evplp::adaptive_tile_noise_into(c, cmd.f[0], cmd.f[1], cmd.i[0], (double *)cmd.out); break;
         case OP_NOISE_VARIANCE:
             if (cmd.i[1]) rc = evplp::noise_variance_to_device(c, noise_pooled(g, c), g->pool_k, g->pool_b, cmd.f[0]);
             else rc = evplp::noise_variance_to_device(c, evplp::noise_moments_of(c), (double)c->noise_k, (double)c->noise_b, cmd.f[0]);
@@ -786,6 +790,7 @@ extern "C" int evplp_group_path_trace(evplp_group *g, const float camera_pos[3],
     GRP_CHECK(g);
     if (!camera_pos) { g->set_error("evplp_group_path_trace: null camera position"); return EVPLP_ERR_INVALID; }
     if (g->adapt_on && !g->adapt_pt) { g->set_error("evplp_group_path_trace: adaptivity is on (evplp_group_adaptive_enable): VPL and VSL gathers only"); return EVPLP_ERR_INVALID; }
+    if (g->adapt_budget) { g->set_error("evplp_group_path_trace: budget mode (evplp_group_adaptive_enable_pt(g, 2)): evplp_group_path_trace_batch only"); return EVPLP_ERR_INVALID; }
     if (g->adapt_pt && !do_accumulate) { g->set_error("evplp_group_path_trace: adaptivity is on (evplp_group_adaptive_enable_pt): a sample must accumulate"); return EVPLP_ERR_INVALID; }
     Cmd c; c.op = OP_PATH_TRACE; c.f[0] = camera_pos[0]; c.f[1] = camera_pos[1]; c.f[2] = camera_pos[2]; c.u[0] = rng_seed; c.u[1] = max_bounces; c.i[0] = do_accumulate;
     return post_pass(g, c);
@@ -1049,6 +1054,7 @@ static int group_adaptive_enable(evplp_group *g, int32_t on, bool pt, const char
     rc = post_and_wait(g, c);
     g->adapt_on = rc >= 0 && on != 0;
     g->adapt_pt = g->adapt_on && pt;
+    g->adapt_budget = g->adapt_pt && on == 2;
     return rc;
 }
 extern "C" int evplp_group_adaptive_enable(evplp_group *g, int32_t on) { GRP_CHECK(g); return group_adaptive_enable(g, on, false, "evplp_group_adaptive_enable"); }
@@ -1058,6 +1064,7 @@ extern "C" int evplp_group_adaptive_retire(evplp_group *g, float scale, float ls
     int rc = adapt_group_ready(g, "evplp_group_adaptive_retire");
     if (rc < 0) return rc;
     if (!g->ctx[0]->d_adapt_tiles) { g->set_error("evplp_group_adaptive_retire: adaptivity is off (evplp_group_adaptive_enable)"); return EVPLP_ERR_INVALID; }
+    if (g->adapt_budget) { g->set_error("evplp_group_adaptive_retire: budget mode (evplp_group_adaptive_enable_pt(g, 2)): set the tile's budget to 0 instead"); return EVPLP_ERR_INVALID; }
     if (!(tau >= 0.0)) { g->set_error("evplp_group_adaptive_retire: tile_rel_mse must be >= 0, not %g", tau); return EVPLP_ERR_INVALID; }
     if (min_batches < 2) { g->set_error("evplp_group_adaptive_retire: min_batches must be >= 2, not %d", min_batches); return EVPLP_ERR_INVALID; }
     Cmd c; c.op = OP_ADAPT_RETIRE; c.f[0] = scale; c.f[1] = ls; c.i[0] = mask_emitter; c.i[1] = min_batches; c.d = tau;
@@ -1076,5 +1083,54 @@ extern "C" int evplp_group_adaptive_tiles(evplp_group *g, int32_t *out, int32_t 
     if (!out || capacity < n) { g->set_error("evplp_group_adaptive_tiles: the image has %lld tiles, the output holds %d", (long long)n, capacity); return EVPLP_ERR_INVALID; }
     std::fill(out, out + n, 0);
     for (const evplp_context *c : g->ctx) evplp::adaptive_tiles_into(c, out);
+    return (int)n;
+}
+// Budget mode (include/evplp.h evplp_adaptive_set_budgets).  A tile never straddles two row blocks, so a rank decides nothing: it takes its own
+// tiles from the whole-image array, and the figures that come back are put together per tile.  What the context would refuse is refused
+// here, on the caller's thread (the workers' failures are sticky), and the group stays usable.
+static int64_t group_image_tiles(const evplp_group *g) { const evplp_context *c0 = g->ctx[0]; return (int64_t)((c0->st.W + 7) / 8) * ((c0->st.H + 7) / 8); }
+extern "C" int evplp_group_adaptive_set_budgets(evplp_group *g, const int32_t *samples_per_image_tile, int32_t count) {
+    GRP_CHECK(g);
+    const char *name = "evplp_group_adaptive_set_budgets";
+    int rc = adapt_group_ready(g, name);
+    if (rc < 0) return rc;
+    if (!g->adapt_budget) { g->set_error("%s: budget mode is off (evplp_group_adaptive_enable_pt(g, 2))", name); return EVPLP_ERR_INVALID; }
+    const int64_t n = group_image_tiles(g);
+    if (!samples_per_image_tile || count != n) { g->set_error("%s: the image has %lld tiles, the call gives %d", name, (long long)n, samples_per_image_tile ? count : 0); return EVPLP_ERR_INVALID; }
+    for (int64_t t = 0; t < n; t++)
+        if (samples_per_image_tile[t] < 0 || samples_per_image_tile[t] > evplp::kPtBatchMaxSamples) {
+            g->set_error("%s: tile %lld: a budget is 0 .. %d samples, not %d", name, (long long)t, evplp::kPtBatchMaxSamples, samples_per_image_tile[t]); return EVPLP_ERR_INVALID;
+        }
+    for (const evplp_context *c : g->ctx) {
+        if (c->noise_b < 2) { g->set_error("%s: %lld fold(s): budgets need >= 2 (evplp_group_noise_fold)", name, (long long)c->noise_b); return EVPLP_ERR_INVALID; }
+        if (c->noise_k != c->adapt_n) { g->set_error("%s: %lld of %lld samples are folded: fold first (evplp_group_noise_fold)", name, (long long)c->noise_k, (long long)c->adapt_n); return EVPLP_ERR_INVALID; }
+    }
+    Cmd c; c.op = OP_ADAPT_SET_BUDGETS; c.p0 = samples_per_image_tile; c.i[0] = count;
+    return post_and_wait(g, c);                     // (the caller's array is read before the call returns)
+}
+extern "C" int evplp_group_adaptive_budgets(evplp_group *g, int32_t *out, int32_t capacity) {
+    GRP_CHECK(g);
+    const char *name = "evplp_group_adaptive_budgets";
+    int rc = adapt_group_ready(g, name);
+    if (rc < 0) return rc;
+    if (!g->adapt_budget) { g->set_error("%s: budget mode is off (evplp_group_adaptive_enable_pt(g, 2))", name); return EVPLP_ERR_INVALID; }
+    const int64_t n = group_image_tiles(g);
+    if (!out || capacity < n) { g->set_error("%s: the image has %lld tiles, the output holds %d", name, (long long)n, capacity); return EVPLP_ERR_INVALID; }
+    std::fill(out, out + n, 0);
+    for (const evplp_context *c : g->ctx) evplp::adaptive_budgets_into(c, out);
+    return (int)n;
+}
+extern "C" int evplp_group_adaptive_tile_noise(evplp_group *g, float scale, float ls, int32_t mask_emitter, double *rel_per_image_tile, int32_t capacity) {
+    GRP_CHECK(g);
+    const char *name = "evplp_group_adaptive_tile_noise";
+    if (g->iterations) { g->set_error("%s: not under EVPLP_PARTITION_ITERATIONS (the ranks' decisions are not pooled)", name); return EVPLP_ERR_INVALID; }
+    if (!g->adapt_on) { g->set_error("%s: adaptivity is off (evplp_group_adaptive_enable)", name); return EVPLP_ERR_INVALID; }
+    const int64_t n = group_image_tiles(g);
+    if (!rel_per_image_tile || capacity < n) { g->set_error("%s: the image has %lld tiles, the output holds %d", name, (long long)n, capacity); return EVPLP_ERR_INVALID; }
+    int rc = noise_group_ready(g, name);
+    if (rc < 0) return rc;
+    std::fill(rel_per_image_tile, rel_per_image_tile + n, 0.0);
+    Cmd c; c.op = OP_ADAPT_TILE_NOISE; c.f[0] = scale; c.f[1] = ls; c.i[0] = mask_emitter; c.out = rel_per_image_tile;
+    if ((rc = post_and_wait(g, c)) < 0) return rc;
     return (int)n;
 }

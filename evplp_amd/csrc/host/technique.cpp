@@ -312,6 +312,8 @@ public:
     bool on = false;
     // the "adaptive" block's tile counts (Adaptive below): written into every checkpoint when `adaptive` is set
     bool adaptive = false; long long retired_tiles = 0, image_tiles = 0;
+    // ... and, under "adaptiveSampling.budget", the samples the next call will run (the sum of the tiles' s_t): "budgetSamples"
+    bool budget = false; long long budget_samples = 0;
     long long batch_iterations() const { return batch; }
     long long batch_count() const { return batches; }
     void parse(const Json &tech, const std::string &json_dir, const std::string &out_dir, int W, int H, int frame_mode) {
@@ -375,7 +377,7 @@ public:
     bool checkpoint(evplp_group *g, int i, WaitAndClock wait_and_clock, float scale, float ls, int32_t mask_emitter) {
         const double t = wait_and_clock();
         const auto t0 = std::chrono::steady_clock::now();
-        Point p; p.iteration = i; p.time_ms = t; p.batches = batches; p.retired = retired_tiles;
+        Point p; p.iteration = i; p.time_ms = t; p.batches = batches; p.retired = retired_tiles; p.budget_samples = budget_samples;
         check(g, evplp_group_noise_estimate(g, scale, ls, mask_emitter, p.e), "noise");
         overhead_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         points.push_back(p);
@@ -402,6 +404,7 @@ public:
                  ", \"batches\": " + std::to_string(p.batches) + ", \"mse\": " + num(p.e[0]) + ", \"relMse\": " + num(p.e[1]);
             if (!mask.empty()) s += ", \"relMseMasked\": " + num(p.e[2]);
             if (adaptive) s += ", \"retiredTiles\": " + std::to_string(p.retired) + ", \"activeTiles\": " + std::to_string(image_tiles - p.retired);
+            if (budget) s += ", \"budgetSamples\": " + std::to_string(p.budget_samples);
             s += "}";
         }
         s += "\n    ]\n}\n";
@@ -416,7 +419,7 @@ public:
     }
 
 private:
-    struct Point { int iteration = 0; double time_ms = 0.0; long long batches = 0; double e[3] = { 0.0, 0.0, 0.0 }; long long retired = 0; };
+    struct Point { int iteration = 0; double time_ms = 0.0; long long batches = 0; double e[3] = { 0.0, 0.0, 0.0 }; long long retired = 0, budget_samples = 0; };
     static std::string num(double v) { if (!std::isfinite(v)) return "null"; char b[40]; std::snprintf(b, sizeof b, "%.17g", v); return b; }     // (every bit of the double)
     void fold(evplp_group *g, size_t r, long long k) {
         check(g, evplp_group_noise_fold(g, (int32_t)k), "noise fold");
@@ -491,6 +494,10 @@ private:
 // "activeTiles"; refused for lvcphotonfam and pt, under "partition": "iterations" and with frameMode "cleareveryframe".  iterationsFilename:
 // every pixel's n_t / N (1 where its tile never retired), rows top to bottom.  Everything is validated before the group exists.
 // pt takes the same block under the key "adaptiveSampling" (the path tracer retires the tiles; its loop ends once none is active).
+// There it may hold "budget": {"minSamples": 1, "referenceQuantile": 1.0} (the defaults; needs "samplesPerCall" > 1): no tile retires; at
+// every everyIterations fold the loop reads the tiles' noise with its own 1 / i scale and their sample counts, plans with S = samplesPerCall
+// (evplp_plan_budgets) and sets the tiles' budgets for the calls that follow.  tileRelMse 0 then means "never stop a tile"; the loop ends
+// when every budget is 0.  The checkpoints gain "budgetSamples"; "activeTiles" counts the tiles whose budget is not 0.
 class Adaptive {
 public:
     // key: "adaptive" (photonfam: the gathers retire tiles) or "adaptiveSampling" (pt: the path tracer does, evplp_group_adaptive_enable_pt)
@@ -521,18 +528,50 @@ public:
             min_batches = (int32_t)mb;
         }
         if (c.has("iterationsFilename")) iterations_filename = output_path(out_dir, c.at("iterationsFilename").as_string((key + ".iterationsFilename").c_str()));
+        if (c.has("budget")) {
+            const Json &b = c.at("budget");
+            if (!pt) throw JsonError(key + ".budget: not for the gathers (pt's \"adaptiveSampling\" only)");
+            if (!b.is_object()) throw JsonError(key + ".budget: expected an object");
+            if (b.has("minSamples")) budget_min = b.at("minSamples").as_int((key + ".budget.minSamples").c_str());
+            if (b.has("referenceQuantile")) budget_q = b.at("referenceQuantile").as_number((key + ".budget.referenceQuantile").c_str());
+            if (!(budget_q > 0.0) || !(budget_q <= 1.0)) throw JsonError(key + ".budget.referenceQuantile: must be in (0, 1]");
+            budget = noise.budget = true;
+        }
         noise.adaptive = true;
         on = true;
+    }
+    // once "samplesPerCall" is known (pt parses it behind this block)
+    void parse_budget_samples(int samples_per_call) {
+        if (!budget) return;
+        if (samples_per_call <= 1) throw JsonError(key + ".budget: needs \"samplesPerCall\" > 1 (a budget is a share of a batched call)");
+        if (budget_min < 1 || budget_min > samples_per_call) throw JsonError(key + ".budget.minSamples: must be 1 .. samplesPerCall");
+        budget_samples_per_call = samples_per_call;
     }
     // before the loop's first gather (after the clear and any rebalance: N = 0)
     void start(evplp_group *g, int W, int H, Noise &noise) {
         if (!on) return;
-        check(g, pt ? evplp_group_adaptive_enable_pt(g, 1) : evplp_group_adaptive_enable(g, 1), key.c_str());
+        check(g, pt ? evplp_group_adaptive_enable_pt(g, budget ? 2 : 1) : evplp_group_adaptive_enable(g, 1), key.c_str());
         noise.image_tiles = (long long)((W + 7) / 8) * ((H + 7) / 8);
+        if (budget) {
+            noise.budget_samples = noise.image_tiles * budget_samples_per_call;
+            tile_rel.assign((size_t)noise.image_tiles, 0.0); tile_n.assign((size_t)noise.image_tiles, 0); tile_budget.assign((size_t)noise.image_tiles, 0);
+        }
     }
     // after the fold of iteration i (folded_now): the retirement, when due
     void after_fold(evplp_group *g, int i, bool folded_now, float scale, Noise &noise) {
         if (!on || !folded_now || i % every != 0) return;
+        if (budget) {
+            if (noise.batch_count() < min_batches) return;
+            const int32_t nt = (int32_t)tile_n.size();
+            check(g, evplp_group_adaptive_tile_noise(g, scale, 1.0f, 0, tile_rel.data(), nt), "adaptive tile noise");
+            check(g, evplp_group_adaptive_tiles(g, tile_n.data(), nt), "adaptive tiles");
+            if (evplp_plan_budgets(tile_rel.data(), tile_n.data(), nt, budget_samples_per_call, (int32_t)budget_min, tau, budget_q, tile_budget.data()) != EVPLP_OK)
+                throw std::runtime_error(key + ".budget: the tiles' noise figures are not finite");
+            check(g, evplp_group_adaptive_set_budgets(g, tile_budget.data(), nt), "adaptive budgets");
+            noise.retired_tiles = 0; noise.budget_samples = 0;
+            for (int32_t b : tile_budget) { noise.retired_tiles += b == 0 ? 1 : 0; noise.budget_samples += b; }
+            return;
+        }
         const int rc = evplp_group_adaptive_retire(g, scale, 1.0f, 0, tau, min_batches);
         check(g, rc, "adaptive retire");
         noise.retired_tiles += rc;
@@ -558,6 +597,8 @@ private:
     long long every = 1;
     int32_t min_batches = 2;
     std::string iterations_filename;
+    bool budget = false; long long budget_min = 1; double budget_q = 1.0; int32_t budget_samples_per_call = 0;
+    std::vector<double> tile_rel; std::vector<int32_t> tile_n, tile_budget;
 };
 } // namespace
 
@@ -600,6 +641,7 @@ public:
             if (spc < 1 || spc > 64) throw JsonError("samplesPerCall: must be 1 .. 64");
             samples_per_call = (int)spc;
         }
+        adaptive.parse_budget_samples(samples_per_call);
         if (samples_per_call > 1) {
             if (frame_mode == 2) throw JsonError("samplesPerCall: frameMode \"cleareveryframe\" shows single samples (a batch always accumulates)");
             if (write_every_frame) throw JsonError("samplesPerCall: writeEveryFrame needs every iteration's frame (use samplesPerCall 1)");

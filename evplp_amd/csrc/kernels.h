@@ -164,6 +164,26 @@ void launch_pt_batch_reduce(const StripDev &st, float4 *out, const PtBatchChunk 
 // the retired tiles' pixels: (float)(R * (ad.n1 / n_t)) in fp64, ad.n1 = N + S (path_trace_kernel<true>'s arithmetic)
 void launch_pt_batch_rescale(const StripDev &st, float4 *out, const AdaptArgs &ad, int32_t ntiles, hipStream_t s);
 
+// Budget mode (evplp_adaptive_enable_pt(ctx, 2)): every tile carries { n_t, K_t, B_t, b_t } and takes the first s_t = (b_t < 0 ? S : min(b_t, S))
+// samples of a call.  The work is an ITEM TABLE: pt_budget_scan_kernel walks the records in increasing tile index and writes first[t], the
+// exclusive prefix sum of s_t (first[tiles] = the total, which stays on the device); pt_budget_fill_kernel writes table[first[t] + s] =
+// t * 64 + s.  A tile's samples are consecutive items, as in PtBatchChunk.  A chunk is the items [item_first, item_first + item_count),
+// slot = item - item_first; items at or beyond the total exit.  The tile's raw sum R lives in the snapshot plane: per chunk
+// pt_budget_accumulate_kernel adds the chunk's part of [first[t], first[t + 1]) to R in increasing s, and once per call
+// pt_budget_finish_kernel sets n_t += s_t and writes VPL_ACCUM = (float)(R * (N / n_t)) (pt_batch_rescale_kernel's arithmetic).
+constexpr int kPtBudgetMaxTiles = 1 << 25;     // tile * 64 + s in 32 bits
+struct PtBudgetChunk {
+    const uint32_t *table; const int32_t *total;
+    int32_t item_first, item_count;
+    float4 *staging;                  // [item_count] slots
+    unsigned long long cut_mask;
+};
+void launch_pt_budget_table(const int4 *tiles, int32_t ntiles, int32_t samples, int32_t *first, uint32_t *table, hipStream_t s);   // first [ntiles + 1]
+void launch_pt_budget_primary(const PrimaryArgs &a, const PtBatchSamples &sm, const PtBudgetChunk &ch, hipStream_t s);
+void launch_pt_budget_trace(const PathTraceArgs &a, const PtBatchSamples &sm, const PtBudgetChunk &ch, hipStream_t s);
+void launch_pt_budget_accumulate(const StripDev &st, float4 *snap, const int32_t *first, int32_t ntiles, const PtBudgetChunk &ch, hipStream_t s);
+void launch_pt_budget_finish(const StripDev &st, int4 *tiles, const int32_t *first, const float4 *snap, float4 *out, int32_t n_after, int32_t ntiles, hipStream_t s);
+
 constexpr int kSummaryShards = 1024, kSummaryStride = 32, kSummaryFinal = kSummaryShards * kSummaryStride;
 constexpr int kSummaryHeavy = kSummaryFinal + 8;     // tiles on the heavy list of this pass (splat_heavy_kernel)
 // Two-level binning of the photon splat, without contended atomics.  Measured (tools/ub/atomics.hip): returning atomics on
@@ -300,6 +320,13 @@ void launch_noise_variance_adaptive(const StripDev &st, const NoiseMoments &m, d
 // fixed tree over the tile's 64 lanes) is <= tau gets the record { n, K, B, 0 } and the snapshot snap = vpl of its pixels
 void launch_adaptive_retire(const StripDev &st, const NoiseMoments &m, double K, double B, double s2K, const float4 *light, float ls, int mask_emitter,
                             const float *rgb, double tau, int4 *tiles, int32_t tiles_x, int32_t tiles_y, int32_t n, const float4 *vpl, float4 *snap, hipStream_t s);
+
+// evplp_noise_fold in budget mode, one wavefront per tile with k_t = n_t - K_t: k_t == 0 leaves the tile alone; otherwise per pixel and channel
+// D = R - c_prev (fp32), Q += D * D / k_t (fp64, noise_fold_kernel's order), c_prev = R, then lane 0 writes K_t = n_t, B_t += 1
+void launch_noise_fold_budget(const NoisePlanes &m, const StripDev &st, int4 *tiles, const float4 *snap, int32_t ntiles, hipStream_t s);
+// evplp_adaptive_tile_noise: out[tile] = the mean of rel over the tile's in-image pixels as adaptive_retire_kernel forms it (0: no such pixel)
+void launch_tile_noise(const StripDev &st, const NoiseMoments &m, double K, double B, double s2K, const float4 *light, float ls, int mask_emitter,
+                       const float *rgb, const AdaptTiles &at, int32_t ntiles, double *out, hipStream_t s);
 
 // evplp_denoise (kernels_denoise.hip): one pixel as the a-trous passes read it.  u = (c / albedo, luminance variance s) of a filtered pixel,
 // (composite, 0) of any other; pos.w = 1 for a filtered pixel, 0 otherwise; albedo = max(diffuse + phong, 1e-3); rgb = the composite.

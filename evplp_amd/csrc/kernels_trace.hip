@@ -7,6 +7,7 @@
 // the whole wave is one conflict-free ds access.
 #include "device_common.hpp"
 #include "kernels.h"
+#include "noise_common.hpp"
 
 namespace evplp {
 
@@ -364,33 +365,7 @@ void launch_noise_fold_adaptive(const NoisePlanes &m, const float4 *vpl, const f
     hipLaunchKernelGGL(noise_fold_frozen_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, m, vpl, pm, n, (double)k, at, st.W);
 }
 
-// Q and S of pixel i, per channel
-__device__ inline void noise_moments(const NoiseMoments &m, size_t i, double q[3], double s[3]) {
-    for (int ch = 0; ch < 3; ch++) q[ch] = m.q[ch * m.stride + i];
-    if (m.s) { for (int ch = 0; ch < 3; ch++) s[ch] = m.s[ch * m.stride + i]; return; }
-    const float4 a = m.prev[i], b = m.start[i];
-    s[0] = (double)__fsub_rn(a.x, b.x); s[1] = (double)__fsub_rn(a.y, b.y); s[2] = (double)__fsub_rn(a.z, b.z);
-}
-// the variance of one channel of the image scale * c: s2K * max(0, (Q - S * S / K) / (B - 1)), s2K = scale^2 * K
-__device__ inline double noise_var(double q, double s, double K, double B1, double s2K) {
-    const double v = __ddiv_rn(__dsub_rn(q, __ddiv_rn(__dmul_rn(s, s), K)), B1);
-    return __dmul_rn(s2K, v > 0.0 ? v : 0.0);
-}
-// the variance of one channel of a RETIRED pixel (tile record r): the tracker's figure at retirement, rescaled to today's composite --
-// noise_var(Q, S, K_t, B_t - 1, s2K_t), s2K_t = ((scale * N) / n_t)^2 * K_t
-__device__ inline double noise_var_retired(double q, double s, const int4 &r, const AdaptTiles &at) {
-    const double f = __ddiv_rn(__dmul_rn(at.scale, at.n), (double)r.x);
-    return noise_var(q, s, (double)r.y, (double)r.z - 1.0, __dmul_rn(__dmul_rn(f, f), (double)r.y));
-}
-// num of pixel i (tile record at ty * tiles_x + tx, Adapt only) from its moments: (var_r + var_g) + var_b, fp64
-template <bool Adapt>
-__device__ inline double noise_num(const double q[3], const double sm[3], double K, double B1, double s2K, const AdaptTiles &at, int l, int x) {
-    if constexpr (Adapt) {
-        const int4 r = at.tiles[(l >> 3) * at.tiles_x + (x >> 3)];
-        if (r.x != 0) return __dadd_rn(__dadd_rn(noise_var_retired(q[0], sm[0], r, at), noise_var_retired(q[1], sm[1], r, at)), noise_var_retired(q[2], sm[2], r, at));
-    }
-    return __dadd_rn(__dadd_rn(noise_var(q[0], sm[0], K, B1, s2K), noise_var(q[1], sm[1], K, B1, s2K)), noise_var(q[2], sm[2], K, B1, s2K));
-}
+// (noise_moments, noise_var, noise_var_retired, noise_num and a tile's mean rel: noise_common.hpp, shared with kernels_ptbudget_exact.hip)
 // Shard pooling (EVPLP_PARTITION_ITERATIONS): launched once per shard in rank order; q / s_out = first ? the shard's : + the shard's
 __global__ __launch_bounds__(256) void noise_pool_kernel(NoiseMoments src, int first, double *q, double *s_out, size_t n) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -551,21 +526,8 @@ __global__ __launch_bounds__(64) void adaptive_retire_kernel(StripDev st, NoiseM
     if (__builtin_amdgcn_readfirstlane(tiles[tile].x) != 0) return;
     const int lane = (int)threadIdx.x, x = tx * 8 + (lane & 7), l = ty * 8 + (lane >> 3);
     const bool plane = x < st.W && l < st.local_rows;
-    const bool in = plane && st.global_row(l) < st.H;
-    double rel = 0.0, cnt = in ? 1.0 : 0.0;
-    if (in) {
-        const size_t i = (size_t)l * st.W + x;
-        double num = 0.0;
-        if (!(mask_emitter && 0.0f < __fmul_rn(light[i].x, ls))) {
-            double q[3], sm[3];
-            noise_moments(m, i, q, sm);
-            num = noise_num<false>(q, sm, K, B1, s2K, AdaptTiles{}, l, x);
-        }
-        const double r = rgb[3 * i], g = rgb[3 * i + 1], b = rgb[3 * i + 2];
-        rel = __ddiv_rn(num, __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(r, r), __dmul_rn(g, g)), __dmul_rn(b, b)), 0.001));
-    }
-    for (int off = 32; off > 0; off >>= 1) { rel = __dadd_rn(rel, __shfl_down(rel, off, 64)); cnt = __dadd_rn(cnt, __shfl_down(cnt, off, 64)); }
-    rel = __shfl(rel, 0, 64); cnt = __shfl(cnt, 0, 64);
+    double rel, cnt;
+    tile_rel_sum<false>(st, m, K, B1, s2K, light, ls, mask_emitter, rgb, AdaptTiles{}, x, l, rel, cnt);
     if (!(cnt > 0.0) || !(__ddiv_rn(rel, cnt) <= tau)) return;
     if (plane) snap[(size_t)l * st.W + x] = vpl[(size_t)l * st.W + x];
     if (lane == 0) tiles[tile] = make_int4(n, ki, bi, 0);

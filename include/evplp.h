@@ -125,6 +125,8 @@ typedef struct evplp_config {
      *   batched path tracing            64 B per pixel-sample of one chunk: min(tiles x S, bound / 4096) slots of 4 KB, allocated on the first
      *   (after a call)                  evplp_path_trace_batch, bounded by evplp_path_trace_batch_scratch (default 1 GB: 1024^2 at S = 16 in one chunk),
      *                                   + 4 B per tile in path-trace adaptive mode (the active-tile list)
+     *                                   budget mode (evplp_adaptive_enable_pt(ctx, 2)): sum(s_t) slots instead of tiles x S, + 4 B per tile and
+     *                                   4 B per item of the largest call (the item table), + 8 B per tile after evplp_adaptive_tile_noise
      *   denoiser (after a call)         124 B per pixel of the context's planes (evplp_denoise); a group's rank: 92 B per pixel of its planes
      *                                   + n x 80 B per pixel of the exchanged rows, and rank 0 + 112 B per image pixel (evplp_group_denoise)
      * A caller that has the device to itself sets cut_scratch_bytes = 72 GB, vsl_mask_bytes = 14 GB for config #5 (one band, one launch). */
@@ -447,6 +449,62 @@ int evplp_adaptive_retire(evplp_context *ctx, float scale, float light_scale, in
  * N for an active one, 0 for tiles another rank owns.  Returns the number of tiles; adaptivity off or capacity too small: EVPLP_ERR_INVALID. */
 int evplp_adaptive_tiles(evplp_context *ctx, int32_t *iterations_per_image_tile, int32_t capacity);
 
+/* Budget mode of the path tracer: evplp_adaptive_enable_pt(ctx, 2).  Modes 0 and 1 know two kinds of tile, sampled at full rate or retired for
+ * good; here every tile keeps improving and the caller says how fast: "this tile gets 16 samples of the next call, that one 2".  The
+ * pre-conditions are those of on = 1 (noise tracking on, N = 0), the memory is the same plus, after the first call, 4 B per tile and 4 B
+ * per (tile, sample) item of the largest call (the item table).  Every tile carries a record { n_t, K_t, B_t, b_t }; its raw sum R lives in
+ * the snapshot plane; b_t is its budget: -1, the state after enabling, means "all samples of the call", 0 .. 64 are set by the caller.
+ * Point by point:
+ *  - A batch call: evplp_path_trace_batch(ctx, cam, S, jitters, seeds, bounces) gives tile t the FIRST s_t = (b_t < 0 ? S : min(b_t, S))
+ *    samples of the call, samples 0 .. s_t - 1 with their jitters and seeds.  N advances by S.  For every in-image pixel of the tile
+ *    R = (((R + r_0) + r_1) + ..), fp32, one sample at a time in increasing s, a sample whose stencil rejects the pixel adding nothing;
+ *    n_t += s_t; and EVPLP_BUF_VPL_ACCUM = (float)((double)R * ((double)N / (double)n_t)) per channel, each operation rounded to nearest,
+ *    N the value after the call.  A tile with n_t == N holds R itself, and the accumulator reads as a sum over N iterations everywhere:
+ *    resolve, present, frame_error, the strip exchange and the denoiser need nothing new.
+ *  - A sample of a pixel has evplp_path_trace's bits (it is keyed by pixel, jitter and seed alone), so a tile's R equals, bit for bit, what a
+ *    context with adaptivity off accumulates from a cleared accumulator when it is given exactly that tile's subsequence of (jitter, seed).
+ *  - G-buffer and tile boxes: those of evplp_primary(jitters[S - 1], 0), the whole-frame pass that closes the call as it does in every mode.
+ *  - EVPLP_BUF_LIGHT: each sample s < s_t writes the emitter colour for its tile; every non-zero pixel equals the full sequence's pixel
+ *    (the caveat stated above for retired tiles).
+ *  - Pass statistics: one EVPLP_PASS_PATH_TRACE pass whose rays and pairs cover the items actually traced, and the closing EVPLP_PASS_PRIMARY.
+ *  - Staging: 4 KB per item, so a call needs sum(s_t) slots, not tiles x S.  The item table -- each tile's first item, an exclusive prefix sum
+ *    over the records in increasing tile index, and one (tile, s) entry per item -- is built on the device without atomics and is the same
+ *    on every run; under evplp_path_trace_batch_scratch the items run in chunks, down to one (tile, sample) per chunk, and the chunking
+ *    changes no bit.
+ *  - Refused with EVPLP_ERR_INVALID in this mode, the context staying usable: evplp_path_trace (single calls); the gathers;
+ *    evplp_adaptive_retire (set the tile's budget to 0 instead); a switch of the mode or of the tracker with N > 0.
+ *  - evplp_clear_accumulators and evplp_set_blocks reset every record to { 0, 0, 0, -1 }.
+ *  - Noise: evplp_noise_fold(ctx, iterations) keeps the host counts (K += iterations, B += 1); on the device it works per tile with
+ *    k_t = n_t - K_t: a tile with k_t == 0 is left alone entirely (Q, c_prev, its record); otherwise per pixel and channel D = R - c_prev
+ *    (fp32), Q += D * D / k_t (fp64, in the default fold's order), c_prev = R, then K_t = n_t and B_t += 1.  evplp_noise_estimate,
+ *    evplp_noise_variance, the denoiser's variance and evplp_adaptive_tile_noise price EVERY tile as a retired one is priced:
+ *    noise_var(Q, S, K_t, B_t - 1, ((scale * N) / n_t)^2 * K_t).
+ * evplp_adaptive_set_budgets: the layout of evplp_adaptive_tiles (image tiles in row order); a rank takes its own tiles and ignores the
+ * others.  Refused: a value outside 0 .. 64, a wrong count, a null pointer; outside budget mode; while the tracker has closed fewer than
+ * two folds; while samples are unfolded (the tracker's K != N).  The last two guarantee every tile B_t >= 2 and n_t >= 1 before any tile
+ * can fall behind: B_t - 1 and n_t are denominators.
+ * evplp_adaptive_budgets reads the budgets back: -1 = full, 0 for tiles another rank owns; returns the number of tiles.  In this mode
+ * evplp_adaptive_tiles returns n_t for every owned tile. */
+int evplp_adaptive_set_budgets(evplp_context *ctx, const int32_t *samples_per_image_tile, int32_t count);
+int evplp_adaptive_budgets(evplp_context *ctx, int32_t *samples_per_image_tile, int32_t capacity);
+/* The per-tile mean of rel exactly as evplp_adaptive_retire forms it (the same lanes, the same shuffle-down tree, divided by the count of
+ * in-image pixels), written out instead of compared with a threshold: a tile evplp_adaptive_retire(.., tau, ..) would retire is one whose
+ * figure here is <= tau, the same doubles.  All three adaptive modes; in modes 0 and 1 a tile retired earlier reports its frozen figure.
+ * Tiles another rank owns and tiles without an in-image pixel: 0.  Returns the number of tiles.  Refused with adaptivity or tracking off, or
+ * with fewer than two folds. */
+int evplp_adaptive_tile_noise(evplp_context *ctx, float scale, float light_scale, int32_t mask_emitter, double *rel_per_image_tile, int32_t capacity);
+/* The planner (host only, no GPU; deterministic: separate processes agree).  rel: evplp_adaptive_tile_noise's figures, n_t:
+ * evplp_adaptive_tiles'.  v_t = rel_t * n_t is the tile's per-sample relative variance.  Tiles with n_t <= 0 (not in the image, or
+ * nobody's) get 0 and are left out of the quantile.  v_ref is the element at index min(m - 1, floor(q * m)) of the m remaining v_t, sorted
+ * ascending, q = reference_quantile in (0, 1].  Per remaining tile, in this order: tile_rel_mse > 0 and rel_t <= tile_rel_mse: 0 (the stopping
+ * rule "every tile at noise level x": a run ends when every budget is 0); v_ref not > 0: samples; otherwise
+ * clamp((int)ceil(samples * sqrt(v_t / v_ref)), max(1, min_samples), samples), in plain double arithmetic.  For a fixed total of samples the
+ * mean of v_t / n_t is least at n_t proportional to sqrt(v_t); with a floor of one sample no tile ever stops improving.
+ * EVPLP_ERR_INVALID: samples outside 1 .. 64, min_samples outside 0 .. samples, q outside (0, 1], a null array, ntiles < 1, a rel that is
+ * negative or not finite. */
+int evplp_plan_budgets(const double *rel, const int32_t *n_t, int32_t ntiles, int32_t samples, int32_t min_samples, double tile_rel_mse,
+                       double reference_quantile, int32_t *out_budgets);
+
 /* Row-strip contexts (strip_count > 1): which blocks of strip_rows image rows this context owns.  By default block b belongs to rank
  * b % strip_count.  evplp_set_blocks replaces that by a table: local block l holds image block image_blocks[l], l < count <= the context's
  * capacity (evplp_config.strip_capacity_rows / strip_rows); image_blocks = NULL restores the default.  Every kernel, statistic and buffer
@@ -656,6 +714,13 @@ int evplp_group_adaptive_enable_pt(evplp_group *g, int32_t on);    /* path-trace
 int evplp_group_adaptive_retire(evplp_group *g, float scale, float light_scale, int32_t mask_emitter,
                                 double tile_rel_mse, int32_t min_batches);
 int evplp_group_adaptive_tiles(evplp_group *g, int32_t *iterations_per_image_tile, int32_t capacity);
+/* Budget mode for a group: evplp_group_adaptive_enable_pt(g, 2) and the three calls below, EVPLP_PARTITION_STRIPS only (refused under
+ * EVPLP_PARTITION_ITERATIONS like every evplp_group_adaptive_* call).  A tile never straddles two row blocks, so a rank decides nothing: it
+ * takes its own tiles from the whole-image array, and the ranks' figures are put together per tile -- budgets, tile counts, tile noise and the
+ * accumulator equal one context's.  Argument errors are refused on the caller's thread and the group stays usable. */
+int evplp_group_adaptive_set_budgets(evplp_group *g, const int32_t *samples_per_image_tile, int32_t count);
+int evplp_group_adaptive_budgets(evplp_group *g, int32_t *samples_per_image_tile, int32_t capacity);
+int evplp_group_adaptive_tile_noise(evplp_group *g, float scale, float light_scale, int32_t mask_emitter, double *rel_per_image_tile, int32_t capacity);
 
 /* ---- host side of the reference interface (no GPU needed for these) ---- */
 /* The anti-aliasing jitters of the first `count` iterations of a technique run with this rngOffset: NDC translations (x, y) =

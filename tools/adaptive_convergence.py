@@ -22,6 +22,13 @@ median and p10 - p90):
 --pair-calls N: nothing but N pairs evplp_primary + evplp_path_trace in path-trace mode with nothing retired (the same, for two checkouts).
 --samples-per-call 4,16: the per-sample time of evplp_path_trace_batch against the active fraction, beside the pair's; prints it and ends.
 --curve-batch S: the curves (not the reference) run S iterations per call through evplp_path_trace_batch; --no-tables: the curves only.
+--budget: pt, budget mode (evplp_adaptive_enable_pt(.., 2)) against the plain batched run and binary retirement, one group per run, the
+  runs alternating call by call in this process: S = --curve-batch (16) samples per call, a fold per call, a plan (or a retirement) every
+  --every (16) iterations after --min-batches (4) folds; relMSE against a plain run of --ref-iters samples of other seeds.  Runs: plain;
+  tileRelMse --budget-tau (0.005); budgets with minSamples 1 at each --budget-quantiles (1,0.95,0.9).  The plain run goes --iters
+  iterations, the others until they pass its final relMSE or 3 x --iters.  Then the cost of the mode itself, --calls each: a budget-mode
+  call with every budget full against a plain batch; the budget-mode fold against the frozen fold of mode 1; one tile-noise + plan +
+  set-budgets round.
 
 usage: python tools/adaptive_convergence.py [--technique photonfam|pt] [--iters N] [--ref-iters N] [--taus 0.002,0.0005] [--every N]
                                             [--min-batches N] [--calls N] [--plain-calls N]"""
@@ -197,6 +204,103 @@ def curve(g, run, iters, every, tau, min_batches, tiles, S=1):
     return pts, retired
 
 
+def budget_runs(groups, sd, iters, every, min_batches, S, tau, quantiles):
+    """--budget: every run on its own group (reference already set), alternating one call at a time"""
+    runs = [{"name": "plain", "g": groups[0], "mode": None}, {"name": f"tileRelMse_{tau:g}", "g": groups[1], "mode": "binary"}]
+    runs += [{"name": f"budget_q{q:g}", "g": groups[2 + k], "mode": "budget", "q": q} for k, q in enumerate(quantiles)]
+    for r in runs:
+        g = r["g"]
+        g.clear_accumulators(); g.adaptive_enable(False); g.noise_track(True)
+        if r["mode"] == "binary":
+            g.adaptive_enable(True, path_trace=True)
+        if r["mode"] == "budget":
+            g.adaptive_enable(True, budget=True)
+        g.synchronize()
+        r.update(run=PtRunner(g, sd), wall=0.0, n=0, folds=0, points=[], done=False, samples=0, next_samples=g.adaptive_tiles().size * S if r["mode"] == "budget" else None)
+    target = None
+    while not all(r["done"] for r in runs):
+        for r in runs:
+            if r["done"]:
+                continue
+            g = r["g"]
+            t0 = time.perf_counter()
+            r["run"].batch(r["n"], S); g.noise_fold(S)
+            r["n"] += S; r["folds"] += 1
+            if r["mode"] == "budget":
+                r["samples"] += r["next_samples"]
+            if r["n"] % every == 0 and r["folds"] >= min_batches:
+                if r["mode"] == "binary":
+                    g.adaptive_retire(1.0 / r["n"], tau, min_batches)
+                if r["mode"] == "budget":
+                    b = ev.plan_budgets(g.adaptive_tile_noise(1.0 / r["n"]), g.adaptive_tiles(), S, 1, 0.0, r["q"])
+                    g.adaptive_set_budgets(b); r["next_samples"] = int(b.sum())
+            g.synchronize()
+            r["wall"] += (time.perf_counter() - t0) * 1e3
+            if r["n"] % every == 0:
+                s = 1.0 / r["n"]
+                p = {"iteration": r["n"], "wall_ms": r["wall"], "rel_mse": g.frame_error(s, s, 1.0)[1]}
+                if r["mode"] == "budget":
+                    p["tile_samples"] = r["samples"]; p["next_call_samples"] = r["next_samples"]
+                if r["mode"] == "binary":
+                    p["active_tiles"] = int((g.adaptive_tiles() == r["n"]).sum())
+                r["points"].append(p)
+            if r["name"] == "plain":
+                r["done"] = r["n"] >= iters
+                if r["done"]:
+                    target = r["points"][-1]["rel_mse"]
+            else:
+                r["done"] = r["n"] >= 3 * iters or (target is not None and r["n"] >= iters and r["points"] and r["points"][-1]["rel_mse"] <= target)
+    out = {}
+    for r in runs:
+        hit = None
+        for p0, p1 in zip([{"wall_ms": 0.0, "rel_mse": math.inf}] + r["points"], r["points"]):
+            if p1["rel_mse"] <= target:
+                t = 1.0 if not math.isfinite(p0["rel_mse"]) else (p0["rel_mse"] - target) / max(p0["rel_mse"] - p1["rel_mse"], 1e-300)
+                hit = p0["wall_ms"] + t * (p1["wall_ms"] - p0["wall_ms"]); break
+        out[r["name"]] = {"points": r["points"], "ms_to_plain_final_rel_mse": hit}
+    return out, target
+
+
+def budget_costs(g, plain, sd, S, calls):
+    """--budget: what the mode itself costs, alternating call by call: g in budget mode with every budget full, `plain` with adaptivity off"""
+    runs = (PtRunner(g, sd), PtRunner(plain, sd))
+    g.clear_accumulators(); g.adaptive_enable(False); g.noise_track(True); g.adaptive_enable(True, budget=True)
+    plain.clear_accumulators(); plain.adaptive_enable(False); plain.noise_track(True)
+    wall = {"budget_full_call": [], "plain_batch_call": [], "budget_fold": [], "plain_fold": [], "tile_noise_plan_set_round": []}
+    n = 0
+    for k in range(calls + 2):
+        for name, grp, run in (("budget_full_call", g, runs[0]), ("plain_batch_call", plain, runs[1])):
+            grp.synchronize(); t0 = time.perf_counter()
+            run.batch(n, S); grp.synchronize()
+            t1 = time.perf_counter()
+            grp.noise_fold(S); grp.synchronize()
+            t2 = time.perf_counter()
+            if k >= 2:
+                wall[name].append((t1 - t0) * 1e3); wall["budget_fold" if grp is g else "plain_fold"].append((t2 - t1) * 1e3)
+        n += S
+        if k >= 2:
+            t0 = time.perf_counter()
+            b = ev.plan_budgets(g.adaptive_tile_noise(1.0 / n), g.adaptive_tiles(), S, 1, 0.0, 1.0)
+            g.adaptive_set_budgets(np.full_like(b, S)); g.synchronize()          # (planned, then set full again: the next call stays a full one)
+            wall["tile_noise_plan_set_round"].append((time.perf_counter() - t0) * 1e3)
+    same = g.resolve(1.0, 0.0, 0.0).tobytes() == plain.resolve(1.0, 0.0, 0.0).tobytes()
+    # the frozen fold of mode 1 (noise_fold_frozen_kernel), nothing retired
+    plain.clear_accumulators(); plain.noise_track(True); plain.adaptive_enable(True, path_trace=True)
+    frozen = []
+    for k in range(calls + 2):
+        runs[1].batch(k * S, S); plain.synchronize()
+        t0 = time.perf_counter()
+        plain.noise_fold(S); plain.synchronize()
+        if k >= 2:
+            frozen.append((time.perf_counter() - t0) * 1e3)
+    plain.clear_accumulators(); plain.adaptive_enable(False, path_trace=True)
+    g.clear_accumulators(); g.adaptive_enable(False, path_trace=True)
+    out = {k: spread(v) for k, v in wall.items()}
+    out["frozen_fold_mode_1"] = spread(frozen)
+    out["accumulators_identical"] = same
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=128)
@@ -212,7 +316,15 @@ def main():
                     "--min-batches then counts folds of S")
     ap.add_argument("--pair-calls", type=int, default=0, help="pt: nothing but N pairs primary + path_trace in path-trace mode, nothing retired (for two builds side by side)")
     ap.add_argument("--no-tables", action="store_true", help="pt: the curves only")
+    ap.add_argument("--budget", action="store_true", help="pt: budget mode against the plain batched run and binary retirement (see the module text)")
+    ap.add_argument("--budget-tau", type=float, default=0.005)
+    ap.add_argument("--budget-quantiles", default="1,0.95,0.9")
+    ap.add_argument("--no-curves", action="store_true", help="--budget: the cost table only")
     a = ap.parse_args()
+    if a.budget:
+        a.technique = "pt"
+        if a.curve_batch == 1:
+            a.curve_batch, a.every = 16, 16
     assert a.curve_batch >= 1 and a.every % a.curve_batch == 0 and a.iters % a.curve_batch == 0, "--curve-batch must divide --every and --iters"
     pt = a.technique == "pt" or a.plain_calls > 0 or a.pair_calls > 0 or bool(a.samples_per_call)
     if pt:
@@ -233,6 +345,29 @@ def main():
                 return
             if a.pair_calls > 0:
                 print(json.dumps({"library": ev.LIB_PATH, "pair_of_calls": pair_calls(g, run, a.pair_calls)}))
+                return
+            if a.budget:
+                qs = [float(x) for x in a.budget_quantiles.split(",") if x]
+                res = {"library": ev.LIB_PATH, "shape": res["shape"], "tiles": tiles, "samples_per_call": a.curve_batch, "every": a.every, "min_batches": a.min_batches}
+                others = []
+                try:
+                    for _ in range(1 if a.no_curves else 1 + len(qs)):
+                        o = ev.Group(W, H, NL, NV, P, 1, devices=[0]); o.load_scene_json(jp); others.append(o)
+                    if not a.no_curves:
+                        g.clear_accumulators()
+                        for i in range(0, a.ref_iters, 16):
+                            run.batch(i + (1 << 20), 16)                 # (samples of its own: no curve shares any with the reference)
+                        s = 1.0 / a.ref_iters
+                        ref = np.ascontiguousarray(g.resolve(s, s, 1.0)[::-1]).astype(np.float32)
+                        for grp in [g] + others:
+                            grp.set_error_reference(ref)
+                        res["reference_iterations"] = a.ref_iters
+                        res["runs"], res["plain_final_rel_mse"] = budget_runs([g] + others, sd, a.iters, a.every, a.min_batches, a.curve_batch, a.budget_tau, qs)
+                    res["costs"] = budget_costs(g, others[0], sd, a.curve_batch, a.calls)
+                finally:
+                    for o in others:
+                        o.close()
+                print(json.dumps(res))
                 return
             if a.plain_calls > 0:
                 g.clear_accumulators()
