@@ -207,7 +207,7 @@ extern "C" void evplp_destroy(evplp_context *c) {
     hipFree(c->d_noise); hipFree(c->d_noise_keep); hipFree(c->d_noise_rows);
     hipFree(c->d_adapt_tiles); hipFree(c->d_adapt_snap);
     hipFree(c->d_dn_var); hipFree(c->d_dn_pack); hipFree(c->d_dn_u);
-    hipFree(c->d_pt_batch); hipFree(c->d_pt_list); hipFree(c->d_pt_first); hipFree(c->d_pt_table); hipFree(c->d_tile_noise);
+    hipFree(c->d_pt_batch); hipFree(c->d_pt_first); hipFree(c->d_pt_table); hipFree(c->d_tile_noise);
     for (int i = 0; i < EVPLP_PASS_COUNT; i++) {
         if (c->ev_begin[i]) hipEventDestroy(c->ev_begin[i]);
         if (c->ev_end[i]) hipEventDestroy(c->ev_end[i]);
@@ -901,10 +901,9 @@ extern "C" int evplp_path_trace(evplp_context *c, const float camera_pos[3], uin
     return EVPLP_OK;
 }
 
-// evplp_path_trace_batch (include/evplp.h has the contract; kernels.h PtBatchChunk the device side).  The staging buffer holds the slots of
-// one chunk.  With E = the tiles of the planes and C = the slots the scratch bound allows: E x S <= C is one chunk; otherwise the list is
-// cut into runs of C / S entries with all S samples each; and where not even one entry's S samples fit (C < S), every entry runs its
-// samples C at a time.  A chunk is primary -> trace -> reduce on the stream, so the adds to a pixel stay in increasing s whatever the cut.
+// evplp_path_trace_batch (include/evplp.h has the contract; kernels.h PtBatchChunk the device side).  One sequence for every mode: count the
+// items from the records' host copy, build the item table, run the items in chunks of as many as the staging buffer holds, close.  A chunk is
+// primary -> trace -> accumulate on the stream, so the adds to a pixel stay in increasing s wherever the cuts fall, inside a tile's samples too.
 extern "C" int evplp_path_trace_batch_scratch(evplp_context *c, uint64_t bytes) { CTX_CHECK(c); c->pt_batch_cap = bytes; return EVPLP_OK; }
 extern "C" int evplp_path_trace_batch(evplp_context *c, const float camera_pos[3], int32_t samples, const float *jitters, const uint32_t *rng_seeds, uint32_t max_bounces) {
     CTX_CHECK(c);
@@ -916,6 +915,8 @@ extern "C" int evplp_path_trace_batch(evplp_context *c, const float camera_pos[3
         c->set_error("%s: the scratch bound (%llu B, evplp_path_trace_batch_scratch) is below one tile x one sample (%zu B)", name, (unsigned long long)c->pt_batch_cap, kPtBatchSlotBytes);
         return EVPLP_ERR_INVALID;
     }
+    const size_t ntiles = (size_t)c->tiles_x * (size_t)c->tiles_y;
+    if (ntiles >= (size_t)kPtBatchMaxTiles) { c->set_error("%s: a context holds at most %d tiles", name, kPtBatchMaxTiles - 1); return EVPLP_ERR_INVALID; }
     PtBatchSamples sm; std::memset(&sm, 0, sizeof(sm));
     unsigned long long cut_mask = 0;
     for (int s = 0; s < samples; s++) {
@@ -924,14 +925,16 @@ extern "C" int evplp_path_trace_batch(evplp_context *c, const float camera_pos[3
         if (jitter_within_cuts(c, sm.jitter[s])) cut_mask |= 1ull << s;
     }
     int rc = pass_ready(c, name, true); if (rc) return rc;
-    const int32_t ntiles = c->tiles_x * c->tiles_y;
     if (ntiles > 0) {
+        // the items: every tile's own sample count, from the records' host copy (current in every mode: evplp_adaptive_retire reads the records
+        // back, budget mode follows them below); the device builds the table from the same function of the same records
+        const int32_t mode = c->adapt_budget ? 2 : c->adapt_pt ? 1 : 0;
+        auto tile_samples = [&](size_t t) { return pt_tile_samples(mode, mode ? c->adapt_tiles[t] : make_int4(0, 0, 0, 0), samples); };
+        uint64_t items = 0;
+        for (size_t t = 0; t < ntiles; t++) items += (uint64_t)tile_samples(t);
         // the staging buffer: what the call needs, within the bound; it only grows, unless the bound came down below it
         const uint64_t cap_slots = std::min<uint64_t>(c->pt_batch_cap / kPtBatchSlotBytes, 1u << 30);
-        // (budget mode: the items are the tiles' own sample counts, known from the records' host copy; the device builds the table itself)
-        uint64_t budget_items = 0;
-        if (c->adapt_budget) for (const int4 &r : c->adapt_tiles) budget_items += (uint64_t)(r.w < 0 ? samples : std::min(r.w, samples));
-        const uint64_t slots = std::min<uint64_t>(c->adapt_budget ? std::max<uint64_t>(budget_items, 1) : (uint64_t)ntiles * (uint64_t)samples, cap_slots);
+        const uint64_t slots = std::min<uint64_t>(std::max<uint64_t>(items, 1), cap_slots);
         if (c->pt_batch_bytes < slots * kPtBatchSlotBytes || c->pt_batch_bytes > cap_slots * kPtBatchSlotBytes) {
             HIP_TRY(c, hipStreamSynchronize(c->stream));
             if (c->d_pt_batch) { hipFree(c->d_pt_batch); c->d_pt_batch = nullptr; c->pt_batch_bytes = 0; }
@@ -942,10 +945,14 @@ extern "C" int evplp_path_trace_batch(evplp_context *c, const float camera_pos[3
             }
             c->pt_batch_bytes = slots * kPtBatchSlotBytes;
         }
-        if (c->adapt_pt && !c->adapt_budget && !c->d_pt_list) HIP_TRY(c, hipMalloc((void **)&c->d_pt_list, sizeof(int32_t) * ((size_t)ntiles + 1)));
         const uint64_t have = c->pt_batch_bytes / kPtBatchSlotBytes;
-        const int32_t chunk_entries = (int32_t)std::max<uint64_t>(1, std::min<uint64_t>(have / (uint64_t)samples, (uint64_t)ntiles));
-        const int32_t chunk_samples = (int32_t)std::min<uint64_t>(have, (uint64_t)samples);
+        if (!c->d_pt_first) HIP_TRY(c, hipMalloc((void **)&c->d_pt_first, sizeof(int32_t) * (ntiles + 1)));
+        if (c->pt_table_items < items) {
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            hipFree(c->d_pt_table); c->d_pt_table = nullptr; c->pt_table_items = 0;
+            HIP_TRY(c, hipMalloc((void **)&c->d_pt_table, sizeof(uint32_t) * items));
+            c->pt_table_items = items;
+        }
 
         PrimaryArgs pa; std::memset(&pa, 0, sizeof(pa));
         pa.sc = c->sc; pa.st = c->st; pa.cam = c->cam; pa.g_light = (float4 *)c->buf[EVPLP_BUF_LIGHT];
@@ -957,45 +964,18 @@ extern "C" int evplp_path_trace_batch(evplp_context *c, const float camera_pos[3
         ta.counters = &c->d_counters[EVPLP_PASS_PATH_TRACE];
         float4 *out = (float4 *)c->buf[EVPLP_BUF_VPL_ACCUM];
         if ((rc = pass_begin(c, EVPLP_PASS_PATH_TRACE))) return rc;
+        launch_pt_batch_table(c->d_adapt_tiles, (int32_t)ntiles, mode, samples, c->d_pt_first, c->d_pt_table, c->stream);
         PtBatchChunk ch; std::memset(&ch, 0, sizeof(ch));
-        ch.tiles = ntiles; ch.staging = (float4 *)c->d_pt_batch; ch.cut_mask = cut_mask;
-        if (c->adapt_budget) {
-            if (!c->d_pt_first) HIP_TRY(c, hipMalloc((void **)&c->d_pt_first, sizeof(int32_t) * ((size_t)ntiles + 1)));
-            if (c->pt_table_items < budget_items) {
-                HIP_TRY(c, hipStreamSynchronize(c->stream));
-                hipFree(c->d_pt_table); c->d_pt_table = nullptr; c->pt_table_items = 0;
-                HIP_TRY(c, hipMalloc((void **)&c->d_pt_table, sizeof(uint32_t) * budget_items));
-                c->pt_table_items = budget_items;
-            }
-            float4 *snap = c->d_adapt_snap;
-            launch_pt_budget_table(c->d_adapt_tiles, ntiles, samples, c->d_pt_first, c->d_pt_table, c->stream);
-            PtBudgetChunk bc; std::memset(&bc, 0, sizeof(bc));
-            bc.table = c->d_pt_table; bc.total = c->d_pt_first + ntiles; bc.staging = (float4 *)c->d_pt_batch; bc.cut_mask = cut_mask;
-            // a chunk is primary -> trace -> accumulate on the stream, so the adds to a pixel of R stay in increasing s whatever the cut
-            for (uint64_t i0 = 0; i0 < budget_items; i0 += have) {
-                bc.item_first = (int32_t)i0; bc.item_count = (int32_t)std::min<uint64_t>(have, budget_items - i0);
-                launch_pt_budget_primary(pa, sm, bc, c->stream);
-                launch_pt_budget_trace(ta, sm, bc, c->stream);
-                launch_pt_budget_accumulate(c->st, snap, c->d_pt_first, ntiles, bc, c->stream);
-            }
-            launch_pt_budget_finish(c->st, c->d_adapt_tiles, c->d_pt_first, snap, out, (int32_t)(c->adapt_n + samples), ntiles, c->stream);
-            for (int4 &r : c->adapt_tiles) r.x += r.w < 0 ? samples : std::min(r.w, samples);
-        } else if (c->adapt_pt) {
-            // path-trace mode: the active tiles as a list (its count stays on the device: the launches are sized from the tile total and the
-            // surplus items exit); the retired tiles are written once from the snapshot, for N + S
-            launch_pt_batch_list(c->d_adapt_tiles, ntiles, c->d_pt_list, c->d_pt_list + ntiles, c->stream);
-            ch.list = c->d_pt_list; ch.count = c->d_pt_list + ntiles;
-            AdaptArgs ad{}; ad.tiles = c->d_adapt_tiles; ad.snap = c->d_adapt_snap; ad.n1 = (int32_t)(c->adapt_n + samples);
-            launch_pt_batch_rescale(c->st, out, ad, ntiles, c->stream);
+        ch.table = c->d_pt_table; ch.total = c->d_pt_first + ntiles; ch.staging = (float4 *)c->d_pt_batch; ch.cut_mask = cut_mask;
+        for (uint64_t i0 = 0; i0 < items; i0 += have) {
+            ch.item_first = (int32_t)i0; ch.item_count = (int32_t)std::min<uint64_t>(have, items - i0);
+            launch_pt_batch_primary(pa, sm, ch, c->stream);
+            launch_pt_batch_trace(ta, sm, ch, c->stream);
+            launch_pt_batch_accumulate(c->st, mode == 2 ? c->d_adapt_snap : out, c->d_pt_first, (int32_t)ntiles, ch, c->stream);     // (budget mode: the raw sums R)
         }
-        for (int32_t e0 = 0; e0 < ntiles && !c->adapt_budget; e0 += chunk_entries)
-            for (int32_t s0 = 0; s0 < samples; s0 += chunk_samples) {
-                ch.entry_first = e0; ch.entry_count = std::min(chunk_entries, ntiles - e0);
-                ch.sample_first = s0; ch.sample_count = std::min(chunk_samples, samples - s0);
-                launch_pt_batch_primary(pa, sm, ch, c->stream);
-                launch_pt_batch_trace(ta, sm, ch, c->stream);
-                launch_pt_batch_reduce(c->st, out, ch, c->stream);
-            }
+        // mode 1: the retired tiles are written once from the snapshot, for N + S; mode 2: n_t += s_t on the device and here, and every tile from R
+        if (mode) launch_pt_batch_close(c->st, c->d_adapt_tiles, mode, c->d_pt_first, c->d_adapt_snap, out, (int32_t)(c->adapt_n + samples), (int32_t)ntiles, c->stream);
+        if (mode == 2) for (size_t t = 0; t < ntiles; t++) c->adapt_tiles[t].x += tile_samples(t);
         if ((rc = pass_end(c, EVPLP_PASS_PATH_TRACE))) return rc;
     }
     c->adapt_n += samples;
@@ -1469,7 +1449,6 @@ static int adaptive_enable_mode(evplp_context *c, int32_t on, bool pt, const cha
         return EVPLP_OK;
     }
     const bool budget = pt && on == 2;
-    if (budget && adapt_tile_count(c) >= (size_t)kPtBudgetMaxTiles) { c->set_error("%s: budget mode holds at most %d tiles", name, kPtBudgetMaxTiles - 1); return EVPLP_ERR_INVALID; }
     const bool was = c->adapt_budget;
     c->adapt_budget = budget;
     const int rc = adapt_reset(c);

@@ -162,12 +162,12 @@ struct evplp_context {
     int64_t adapt_n = 0; int4 *d_adapt_tiles = nullptr; float4 *d_adapt_snap = nullptr; std::vector<int4> adapt_tiles; int32_t adapt_last = 0;
     bool adapt_pt = false;          // evplp_adaptive_enable_pt: evplp_path_trace owns the retirement (the gathers are refused)
     // evplp_path_trace_batch: the staging slots of one chunk (kernels.h PtBatchChunk; allocated on the first call, bounded by pt_batch_cap --
-    // evplp_path_trace_batch_scratch) and, in path-trace adaptive mode, the active-tile list [tiles] followed by its count [1]
-    char *d_pt_batch = nullptr; size_t pt_batch_bytes = 0; uint64_t pt_batch_cap = 1ull << 30; int32_t *d_pt_list = nullptr;
-    // budget mode (evplp_adaptive_enable_pt(ctx, 2); kernels.h PtBudgetChunk): adapt_pt is set too; the records' host copy follows the device's
-    // in every field (a call adds s_t to n_t, a fold closes K_t and B_t: both are functions of the records alone); first [tiles + 1] and the
-    // item table [pt_table_items], which only grows; evplp_adaptive_tile_noise's per-tile doubles [tiles]
-    bool adapt_budget = false; int32_t *d_pt_first = nullptr; uint32_t *d_pt_table = nullptr; size_t pt_table_items = 0; double *d_tile_noise = nullptr;
+    // evplp_path_trace_batch_scratch), first [tiles + 1] and the item table [pt_table_items], which only grows
+    char *d_pt_batch = nullptr; size_t pt_batch_bytes = 0; uint64_t pt_batch_cap = 1ull << 30;
+    int32_t *d_pt_first = nullptr; uint32_t *d_pt_table = nullptr; size_t pt_table_items = 0;
+    // budget mode (evplp_adaptive_enable_pt(ctx, 2)): adapt_pt is set too; the records' host copy follows the device's in every field (a call
+    // adds s_t to n_t, a fold closes K_t and B_t: both are functions of the records alone); evplp_adaptive_tile_noise's per-tile doubles [tiles]
+    bool adapt_budget = false; double *d_tile_noise = nullptr;
     // evplp_denoise: the variance image [W * local_rows][3], the packed pixels of the planes [W * local_rows] (kernels.h DenoisePixel), and
     // the two (u, s) planes of the a-trous passes [2][dn_u_px] (the frame the context filters: its planes, or a group's whole image on rank 0);
     // allocated on the first call, kept until evplp_destroy

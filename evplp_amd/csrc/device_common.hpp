@@ -34,6 +34,24 @@ EV_DEV V3 normalize(V3 v) { float inv = 1.0f / sqrtf(dot(v, v)); return v * inv;
 EV_DEV V3 reflect(V3 i, V3 n) { float d = dot(n, i); return i - (n * 2.0f) * d; }
 EV_DEV V3 faceforward(V3 n, V3 i, V3 nref) { return n * copysignf(1.0f, dot(i, nref)); }
 EV_DEV float max_color(V3 c) { return fmaxf(fmaxf(c.x, c.y), c.z); }
+// 8 x 8 tile `tile` of planes W pixels wide, tiles numbered row by row: its (column, row) of tiles, wave-uniform where the tile is ...
+EV_DEV int2 tile_coords(int tile, int W) {
+    const int tiles_x = (W + 7) >> 3;
+    return make_int2(tile % tiles_x, tile / tiles_x);
+}
+// ... and the pixel of lane `lane` of the wavefront that owns it: (column x, local row ly).  By value: with reference results the optimiser
+// laid out path_trace_kernel's in-image test as a branch and the kernel lost its instruction stream.
+EV_DEV int2 tile_lane(int tile, int lane, int W) {
+    const int2 t = tile_coords(tile, W);
+    return make_int2(t.x * 8 + (lane & 7), t.y * 8 + (lane >> 3));
+}
+// a retired pixel's sum R over n_t iterations read as a sum over n1: (float)(R * (n1 / n_t)) per channel in fp64, every operation an explicit
+// round-to-nearest intrinsic, so it is the same bits under either contraction flag
+EV_DEV float4 extrapolate(float4 R, int32_t n1, int32_t nt) {
+    const double f = __ddiv_rn((double)n1, (double)nt);
+    return make_float4(__double2float_rn(__dmul_rn((double)R.x, f)), __double2float_rn(__dmul_rn((double)R.y, f)),
+                       __double2float_rn(__dmul_rn((double)R.z, f)), __double2float_rn(__dmul_rn((double)R.w, f)));
+}
 // (a.x b.x + a.y b.y) + a.z b.z with every product and sum rounded on its own (the oracle's dot under -ffp-contract=off): used
 // where a SIGN decides something discrete -- the cosine test of lighttracing.cu:284-288 -- so that the set of pairs that trace a
 // shadow ray is identical on CPU and GPU, not just the radiance within a tolerance

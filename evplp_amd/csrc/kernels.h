@@ -139,50 +139,38 @@ struct PathTraceArgs {
     PassCounters *counters;
 };
 
-// evplp_path_trace_batch: S complete iterations (primary visibility + one camera path) of the ACTIVE tiles in one call.  The active tiles
-// are a compacted list (pt_batch_list_kernel; its count stays on the device) and the work is enumerated as (list entry, sample) items, one
-// wavefront each, lane = pixel: a thin tail of noisy tiles still fills the machine.  An item owns one staging SLOT, [4 planes][64 lanes]
-// float4: the batched primary writes the sample's four texels there, the batched trace reads them and puts (r, g, b, valid) of the sample
-// into plane 0, and the reduce adds the samples to VPL_ACCUM one at a time in increasing s -- the order of S single calls.
+// evplp_path_trace_batch: S complete iterations (primary visibility + one camera path) in one call, every tile taking its own number of them
+// (pt_tile_samples below).  The work is an ITEM TABLE, one item per (tile, sample), one wavefront each, lane = pixel, so a thin tail of noisy
+// tiles still fills the machine: pt_batch_scan_kernel walks the tiles in increasing index and writes first[t], the exclusive prefix sum of the
+// tiles' counts (first[tiles] = the total); pt_batch_fill_kernel writes table[first[t] + s] = t * 64 + s.  A tile's samples are consecutive
+// items, so the workgroup dispatcher's round-robin deals them over all eight XCDs (as the gather's item_deal = 1 does for small launches).
+// An item owns one staging SLOT, [4 planes][64 lanes] float4: the batched primary writes the sample's four texels there, the batched trace
+// reads them and puts (r, g, b, valid) of the sample into plane 0, and pt_batch_accumulate_kernel adds the chunk's part of
+// [first[t], first[t + 1]) to the tile's pixels one sample at a time in increasing s -- the order of S single calls -- in VPL_ACCUM, or in
+// budget mode in the snapshot plane, where the tile's raw sum R lives.  Once per call pt_batch_close_kernel writes the pixels that are an
+// extrapolation: mode 1, the retired tiles' as (float)(R * ((N + S) / n_t)); mode 2, n_t += s_t and every tile's as (float)(R * (N / n_t)).
 constexpr int kPtBatchMaxSamples = 64;
+constexpr int kPtBatchMaxTiles = 1 << 25;                          // tile * 64 + s in 32 bits: evplp_path_trace_batch refuses a context with more
 constexpr size_t kPtBatchSlotBytes = 4 * 64 * sizeof(float4);      // 64 B per pixel-sample
 struct PtBatchSamples { float jitter[kPtBatchMaxSamples][2]; uint32_t seed[kPtBatchMaxSamples]; };
-// one chunk of a call: the list entries [entry_first, entry_first + entry_count) x the samples [sample_first, sample_first + sample_count);
-// item = (entry - entry_first) * sample_count + (sample - sample_first), and slot = item.  A tile's samples follow each other in the
-// grid, so the workgroup dispatcher's round-robin deals them over all eight XCDs (as the gather's item_deal = 1 does for small launches).
+// The samples 0 .. s_t - 1 of a call of S that the tile with record r takes: the scan kernel's count and the host's (staging and table sizes,
+// budget mode's n_t).  mode 0, adaptivity off (no records, r is ignored): S.  Mode 1 (evplp_adaptive_enable_pt(ctx, 1), r = { n_t, K_t, B_t, 0 }):
+// S for an active tile, 0 for a retired one.  Mode 2, budget mode (r = { n_t, K_t, B_t, b_t }): the budget, -1 = all.
+__host__ __device__ inline int32_t pt_tile_samples(int32_t mode, int4 r, int32_t S) {
+    return mode == 0 ? S : mode == 1 ? (r.x == 0 ? S : 0) : (r.w < 0 || r.w > S ? S : r.w);
+}
+// one chunk of a call: the items [item_first, item_first + item_count), slot = item - item_first; items at or beyond the total exit
 struct PtBatchChunk {
-    const int32_t *list, *count;      // the active tiles in increasing order and how many; null: every tile of the planes (adaptivity off)
-    int32_t tiles;                    // tiles of the context's planes: entries at or beyond the count exit
-    int32_t entry_first, entry_count, sample_first, sample_count, pad;
-    float4 *staging;                  // [entry_count * sample_count] slots
-    unsigned long long cut_mask;      // bit s: sample s's jitter lies within the eye's entry cuts (evplp_primary's test); else it walks from the root
-};
-void launch_pt_batch_list(const int4 *tiles, int32_t ntiles, int32_t *list, int32_t *count, hipStream_t s);
-void launch_pt_batch_primary(const PrimaryArgs &a, const PtBatchSamples &sm, const PtBatchChunk &ch, hipStream_t s);      // a.jitter, a.clear_light, the planes but g_light: unused
-void launch_pt_batch_trace(const PathTraceArgs &a, const PtBatchSamples &sm, const PtBatchChunk &ch, hipStream_t s);      // a.rng_seed, the planes, a.out: unused; a.do_accumulate must be 0
-void launch_pt_batch_reduce(const StripDev &st, float4 *out, const PtBatchChunk &ch, hipStream_t s);
-// the retired tiles' pixels: (float)(R * (ad.n1 / n_t)) in fp64, ad.n1 = N + S (path_trace_kernel<true>'s arithmetic)
-void launch_pt_batch_rescale(const StripDev &st, float4 *out, const AdaptArgs &ad, int32_t ntiles, hipStream_t s);
-
-// Budget mode (evplp_adaptive_enable_pt(ctx, 2)): every tile carries { n_t, K_t, B_t, b_t } and takes the first s_t = (b_t < 0 ? S : min(b_t, S))
-// samples of a call.  The work is an ITEM TABLE: pt_budget_scan_kernel walks the records in increasing tile index and writes first[t], the
-// exclusive prefix sum of s_t (first[tiles] = the total, which stays on the device); pt_budget_fill_kernel writes table[first[t] + s] =
-// t * 64 + s.  A tile's samples are consecutive items, as in PtBatchChunk.  A chunk is the items [item_first, item_first + item_count),
-// slot = item - item_first; items at or beyond the total exit.  The tile's raw sum R lives in the snapshot plane: per chunk
-// pt_budget_accumulate_kernel adds the chunk's part of [first[t], first[t + 1]) to R in increasing s, and once per call
-// pt_budget_finish_kernel sets n_t += s_t and writes VPL_ACCUM = (float)(R * (N / n_t)) (pt_batch_rescale_kernel's arithmetic).
-constexpr int kPtBudgetMaxTiles = 1 << 25;     // tile * 64 + s in 32 bits
-struct PtBudgetChunk {
     const uint32_t *table; const int32_t *total;
     int32_t item_first, item_count;
     float4 *staging;                  // [item_count] slots
-    unsigned long long cut_mask;
+    unsigned long long cut_mask;      // bit s: sample s's jitter lies within the eye's entry cuts (evplp_primary's test); else it walks from the root
 };
-void launch_pt_budget_table(const int4 *tiles, int32_t ntiles, int32_t samples, int32_t *first, uint32_t *table, hipStream_t s);   // first [ntiles + 1]
-void launch_pt_budget_primary(const PrimaryArgs &a, const PtBatchSamples &sm, const PtBudgetChunk &ch, hipStream_t s);
-void launch_pt_budget_trace(const PathTraceArgs &a, const PtBatchSamples &sm, const PtBudgetChunk &ch, hipStream_t s);
-void launch_pt_budget_accumulate(const StripDev &st, float4 *snap, const int32_t *first, int32_t ntiles, const PtBudgetChunk &ch, hipStream_t s);
-void launch_pt_budget_finish(const StripDev &st, int4 *tiles, const int32_t *first, const float4 *snap, float4 *out, int32_t n_after, int32_t ntiles, hipStream_t s);
+void launch_pt_batch_table(const int4 *tiles, int32_t ntiles, int32_t mode, int32_t samples, int32_t *first, uint32_t *table, hipStream_t s);   // first [ntiles + 1]
+void launch_pt_batch_primary(const PrimaryArgs &a, const PtBatchSamples &sm, const PtBatchChunk &ch, hipStream_t s);      // a.jitter, a.clear_light, the planes but g_light: unused
+void launch_pt_batch_trace(const PathTraceArgs &a, const PtBatchSamples &sm, const PtBatchChunk &ch, hipStream_t s);      // a.rng_seed, the planes, a.out: unused; a.do_accumulate must be 0
+void launch_pt_batch_accumulate(const StripDev &st, float4 *plane, const int32_t *first, int32_t ntiles, const PtBatchChunk &ch, hipStream_t s);
+void launch_pt_batch_close(const StripDev &st, int4 *tiles, int32_t mode, const int32_t *first, const float4 *snap, float4 *out, int32_t n_after, int32_t ntiles, hipStream_t s);
 
 constexpr int kSummaryShards = 1024, kSummaryStride = 32, kSummaryFinal = kSummaryShards * kSummaryStride;
 constexpr int kSummaryHeavy = kSummaryFinal + 8;     // tiles on the heavy list of this pass (splat_heavy_kernel)

@@ -458,10 +458,7 @@ __global__ __launch_bounds__(256) void gather_reduce_kernel(GatherArgs a, int st
         }
     }
     if (ADAPT && writes && nt != 0) {
-        const float4 R = ad.snap[i];
-        const double f = __ddiv_rn((double)ad.n1, (double)nt);
-        a.out[i] = make_float4(__double2float_rn(__dmul_rn((double)R.x, f)), __double2float_rn(__dmul_rn((double)R.y, f)),
-                               __double2float_rn(__dmul_rn((double)R.z, f)), __double2float_rn(__dmul_rn((double)R.w, f)));
+        a.out[i] = extrapolate(ad.snap[i], ad.n1, nt);
     } else if (writes) {
         const int groups = kVplSplit / a.splits_per_wave;
         V3 r = v3(0.f, 0.f, 0.f), lv0 = r, lv1 = r, lv2 = r, lv3 = r, lv4 = r, lv5 = r, lv6 = r;

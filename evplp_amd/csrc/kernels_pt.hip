@@ -21,23 +21,16 @@ template <bool ADAPT = false>
 __global__ __launch_bounds__(64, EVPLP_PT_WAVES) void path_trace_kernel(PathTraceArgs a, AdaptArgs ad) {
     extern __shared__ int32_t lds_stack[];   // [bvh_depth + 2][64 lanes]
     const int lane = threadIdx.x;
-    const int tiles_x = (a.st.W + 7) >> 3;
     const int tile = blockIdx.x;
-    const int tx = tile % tiles_x, ty = tile / tiles_x;
-    const int x = tx * 8 + (lane & 7);
-    const int ly = ty * 8 + (lane >> 3);
+    const int2 xl = tile_lane(tile, lane, a.st.W);
+    const int x = xl.x, ly = xl.y;
     const int y = a.st.global_row(min(ly, a.st.local_rows - 1));
     const bool in_image = x < a.st.W && ly < a.st.local_rows && y < a.st.H;
     const size_t p = (size_t)min(ly, a.st.local_rows - 1) * a.st.W + min(x, a.st.W - 1);
     if constexpr (ADAPT) {
         const int nt = __builtin_amdgcn_readfirstlane(ad.tiles[tile].x);
         if (nt != 0) {
-            if (in_image) {
-                const float4 R = ad.snap[p];
-                const double f = __ddiv_rn((double)ad.n1, (double)nt);
-                a.out[p] = make_float4(__double2float_rn(__dmul_rn((double)R.x, f)), __double2float_rn(__dmul_rn((double)R.y, f)),
-                                       __double2float_rn(__dmul_rn((double)R.z, f)), __double2float_rn(__dmul_rn((double)R.w, f)));
-            }
+            if (in_image) a.out[p] = extrapolate(ad.snap[p], ad.n1, nt);
             return;
         }
     }

@@ -365,7 +365,7 @@ void launch_noise_fold_adaptive(const NoisePlanes &m, const float4 *vpl, const f
     hipLaunchKernelGGL(noise_fold_frozen_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, m, vpl, pm, n, (double)k, at, st.W);
 }
 
-// (noise_moments, noise_var, noise_var_retired, noise_num and a tile's mean rel: noise_common.hpp, shared with kernels_ptbudget_exact.hip)
+// (noise_moments, noise_var, noise_var_retired, noise_num and a tile's mean rel: noise_common.hpp, shared with kernels_ptbatch_primary.hip)
 // Shard pooling (EVPLP_PARTITION_ITERATIONS): launched once per shard in rank order; q / s_out = first ? the shard's : + the shard's
 __global__ __launch_bounds__(256) void noise_pool_kernel(NoiseMoments src, int first, double *q, double *s_out, size_t n) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;

@@ -1,5 +1,5 @@
 // The noise tracker's per-pixel arithmetic, shared by kernels_trace.hip (the estimate, the variance image, evplp_adaptive_retire) and
-// kernels_ptbudget_exact.hip (evplp_adaptive_tile_noise).  Both units are built without contraction and every operation is an _rn intrinsic.
+// kernels_ptbatch_primary.hip (evplp_adaptive_tile_noise).  Both units are built without contraction and every operation is an _rn intrinsic.
 #pragma once
 #include "device_common.hpp"
 #include "kernels.h"

@@ -122,11 +122,12 @@ typedef struct evplp_config {
      *   noise tracking (if on)          56 B per pixel of the context's planes (+ 1 B per image pixel with a mask; evplp_noise_track)
      *   adaptive gather (if enabled)    16 B per pixel of the context's planes (snapshot) + 16 B per 8 x 8 tile (evplp_adaptive_enable; the same for
      *                                   adaptive path tracing, evplp_adaptive_enable_pt: one mode at a time, one allocation)
-     *   batched path tracing            64 B per pixel-sample of one chunk: min(tiles x S, bound / 4096) slots of 4 KB, allocated on the first
-     *   (after a call)                  evplp_path_trace_batch, bounded by evplp_path_trace_batch_scratch (default 1 GB: 1024^2 at S = 16 in one chunk),
-     *                                   + 4 B per tile in path-trace adaptive mode (the active-tile list)
-     *                                   budget mode (evplp_adaptive_enable_pt(ctx, 2)): sum(s_t) slots instead of tiles x S, + 4 B per tile and
-     *                                   4 B per item of the largest call (the item table), + 8 B per tile after evplp_adaptive_tile_noise
+     *   batched path tracing            64 B per pixel-sample of one chunk: min(items, bound / 4096) slots of 4 KB, allocated on the first
+     *   (after a call)                  evplp_path_trace_batch, bounded by evplp_path_trace_batch_scratch (default 1 GB: 1024^2 at S = 16 in one chunk);
+     *                                   items = the (tile, sample) pairs of the call: tiles x S with adaptivity off, active tiles x S in
+     *                                   path-trace adaptive mode, sum(s_t) in budget mode (evplp_adaptive_enable_pt(ctx, 2));
+     *                                   + 4 B per tile and 4 B per item of the largest call (the item table);
+     *                                   budget mode: + 8 B per tile after evplp_adaptive_tile_noise
      *   denoiser (after a call)         124 B per pixel of the context's planes (evplp_denoise); a group's rank: 92 B per pixel of its planes
      *                                   + n x 80 B per pixel of the exchanged rows, and rank 0 + 112 B per image pixel (evplp_group_denoise)
      * A caller that has the device to itself sets cut_scratch_bytes = 72 GB, vsl_mask_bytes = 14 GB for config #5 (one band, one launch). */
@@ -282,8 +283,9 @@ int evplp_path_trace(evplp_context *ctx, const float camera_pos[3], uint32_t rng
 /* S complete iterations of the "pt" technique in one call, for the ACTIVE tiles only.  It always accumulates, and the context's state after
  * the call is its state after
  *     for s in 0 .. samples - 1: evplp_primary(ctx, jitters + 2 s, 0); evplp_path_trace(ctx, camera_pos, rng_seeds[s], max_bounces, 1);
- * jitters: [samples][2], rng_seeds: [samples]; both are read before the call returns.  The work is enumerated as (active tile, sample) items
- * from a compacted list of the active 8 x 8 tiles (every tile when adaptivity is off): one wavefront each, so a thin tail of noisy tiles
+ * jitters: [samples][2], rng_seeds: [samples]; both are read before the call returns.  The work is enumerated as (tile, sample) items
+ * from a table of the samples each 8 x 8 tile takes (all of them for an active tile and for every tile when adaptivity is off, none for a
+ * retired one; budget mode, below, sets its own counts): one wavefront each, so a thin tail of noisy tiles
  * still fills the device and a retired tile costs nothing in either pass; there is no whole-frame G-buffer round trip between samples.
  * Point by point:
  *  - EVPLP_BUF_VPL_ACCUM, active tiles (every tile with adaptivity off): every in-image pixel is bit-identical to the sequence.  The samples
@@ -303,12 +305,15 @@ int evplp_path_trace(evplp_context *ctx, const float camera_pos[3], uint32_t rng
  *    stay as it was.
  *  - Pass statistics: the call is ONE EVPLP_PASS_PATH_TRACE pass whose rays and pairs are the sums of the sequence's per-call figures
  *    (retired tiles add nothing), and one EVPLP_PASS_PRIMARY pass (the closing one).
- *  - Staging: 64 B per pixel-sample, 4 KB per (tile, sample), allocated on the first call and bounded by evplp_path_trace_batch_scratch
- *    (default 1 GB).  If tiles x samples does not fit, the call runs the list in chunks (primary -> trace -> reduce each), down to one
- *    (tile, sample) per chunk; the chunking changes no bit.  The launches are sized from the tile total -- the active count stays on the
- *    device, there is no host round trip -- so with a small bound and few active tiles most chunks are empty launches.
+ *  - Staging: 64 B per pixel-sample, 4 KB per (tile, sample) item, allocated on the first call and bounded by
+ *    evplp_path_trace_batch_scratch (default 1 GB): min(items, bound / 4096) slots.  If the items do not fit, the call runs them in chunks
+ *    of as many as fit (primary -> trace -> accumulate each; a chunk may end inside a tile's samples), down to one (tile, sample) per
+ *    chunk; the chunking changes no bit.  The item table -- each tile's first item and one (tile, s) entry per item, 4 B per tile and 4 B
+ *    per item -- is built on the device without atomics and is the same on every run.  The launches are sized from the host's count of
+ *    the items (the host's copy of the tile records: there is no round trip), so no chunk is an empty launch.
  *  - Refused with EVPLP_ERR_INVALID, the context staying usable: samples < 1 or > 64; a null array or camera position; a jitter that is not
- *    finite; adaptivity on in gather mode (evplp_adaptive_enable), as evplp_path_trace is; a scratch bound below one (tile, sample), 4096 B.
+ *    finite; adaptivity on in gather mode (evplp_adaptive_enable), as evplp_path_trace is; a scratch bound below one (tile, sample), 4096 B;
+ *    a context of 2^25 tiles or more (an item is coded as tile * 64 + s in 32 bits; such planes hold more than 2^31 pixels).
  * The trace kernel of this call inlines the same source as evplp_path_trace's and is held to the same choice of fused multiply-adds
  * ("Adaptive path tracing, batched"; tests/test_pt_batch_same_arithmetic.py): a sample has evplp_path_trace's bits.
  * evplp_path_trace_batch_scratch sets the bound for the calls that follow (any value is taken; a buffer above a lowered bound is released
@@ -451,8 +456,8 @@ int evplp_adaptive_tiles(evplp_context *ctx, int32_t *iterations_per_image_tile,
 
 /* Budget mode of the path tracer: evplp_adaptive_enable_pt(ctx, 2).  Modes 0 and 1 know two kinds of tile, sampled at full rate or retired for
  * good; here every tile keeps improving and the caller says how fast: "this tile gets 16 samples of the next call, that one 2".  The
- * pre-conditions are those of on = 1 (noise tracking on, N = 0), the memory is the same plus, after the first call, 4 B per tile and 4 B
- * per (tile, sample) item of the largest call (the item table).  Every tile carries a record { n_t, K_t, B_t, b_t }; its raw sum R lives in
+ * pre-conditions are those of on = 1 (noise tracking on, N = 0), the memory is the same (the item table of evplp_path_trace_batch, 4 B per
+ * tile and 4 B per (tile, sample) item of the largest call, belongs to every mode).  Every tile carries a record { n_t, K_t, B_t, b_t }; its raw sum R lives in
  * the snapshot plane; b_t is its budget: -1, the state after enabling, means "all samples of the call", 0 .. 64 are set by the caller.
  * Point by point:
  *  - A batch call: evplp_path_trace_batch(ctx, cam, S, jitters, seeds, bounces) gives tile t the FIRST s_t = (b_t < 0 ? S : min(b_t, S))
@@ -467,10 +472,8 @@ int evplp_adaptive_tiles(evplp_context *ctx, int32_t *iterations_per_image_tile,
  *  - EVPLP_BUF_LIGHT: each sample s < s_t writes the emitter colour for its tile; every non-zero pixel equals the full sequence's pixel
  *    (the caveat stated above for retired tiles).
  *  - Pass statistics: one EVPLP_PASS_PATH_TRACE pass whose rays and pairs cover the items actually traced, and the closing EVPLP_PASS_PRIMARY.
- *  - Staging: 4 KB per item, so a call needs sum(s_t) slots, not tiles x S.  The item table -- each tile's first item, an exclusive prefix sum
- *    over the records in increasing tile index, and one (tile, s) entry per item -- is built on the device without atomics and is the same
- *    on every run; under evplp_path_trace_batch_scratch the items run in chunks, down to one (tile, sample) per chunk, and the chunking
- *    changes no bit.
+ *  - Staging: as stated at evplp_path_trace_batch, with sum(s_t) items: 4 KB per item, min(items, bound / 4096) slots; under
+ *    evplp_path_trace_batch_scratch the items run in chunks, down to one (tile, sample) per chunk, and the chunking changes no bit.
  *  - Refused with EVPLP_ERR_INVALID in this mode, the context staying usable: evplp_path_trace (single calls); the gathers;
  *    evplp_adaptive_retire (set the tile's budget to 0 instead); a switch of the mode or of the tracker with N > 0.
  *  - evplp_clear_accumulators and evplp_set_blocks reset every record to { 0, 0, 0, -1 }.

@@ -3,7 +3,8 @@ it stands for:  for s: primary(jitters[s], 0); path_trace(camera, seeds[s], boun
 
 Everything is compared exactly.  The box room of tests/scenes.py at 96 x 64 and at 100 x 52 (neither side a multiple of 8): accumulator,
 G-buffer planes, light plane and the pass counters for S = 1, 3, 8, from cleared and from filled accumulators; the same under scratch bounds
-that force three chunks and one (tile, sample) per chunk; path-trace adaptive mode with some and with all tiles retired (active tiles bit for
+that force three chunks, chunks that end inside a tile's samples (S + 3 slots for S = 8; in path-trace adaptive mode too, with some tiles
+retired) and one (tile, sample) per chunk; path-trace adaptive mode with some and with all tiles retired (active tiles bit for
 bit, retired ones at the fp64 rescale, the noise figures as doubles); row strips of 2 and 4 virtual ranks, round robin and dealt, against one
 context; every refusal; and the technique loop with samplesPerCall 4 against samplesPerCall 1, plain and adaptive, byte for byte."""
 import json
@@ -101,10 +102,11 @@ def test_chunking_changes_no_bit(evplp, w, h):
     with context(evplp, box, w, h) as a:
         ca = sequence(evplp, a, cam, J0, R0); ca2 = sequence(evplp, a, cam, J1, R1)
         want = planes(evplp, a, h)
-    # a third of the slots (rounded down to whole entries): at least three chunks of entries; then one slot: one (tile, sample) per chunk
+    # a third of the slots (rounded down to whole entries): at least three chunks of entries; S + 3 slots: the chunks end inside a tile's
+    # samples; then one slot: one (tile, sample) per chunk
     third = (tiles // 3) * S * SLOT
     assert -(-tiles // (third // SLOT // S)) >= 3
-    for bound in (third, SLOT):
+    for bound in (third, (S + 3) * SLOT, SLOT):
         with context(evplp, box, w, h) as b:
             b.path_trace_batch_scratch(bound)
             cb = batch(evplp, b, cam, J0, R0); cb2 = batch(evplp, b, cam, J1, R1)
@@ -157,11 +159,11 @@ def tile_mask(retired, w, h):
     return np.kron(retired, np.ones((8, 8), bool))[:h, :w]
 
 
-@pytest.mark.parametrize("w, h", [(W, H), ODD])
-def test_adaptive_batch_equals_the_sequence(evplp, w, h):
+def adaptive_batch_against_the_sequence(evplp, w, h, S, bound=None):
+    """path-trace adaptive mode, some tiles retired after the warm-up: one batched call of S (under the scratch bound, if given) against
+    the S single calls"""
     box = scenes.box_room(seed=7, n_boxes=4, tess=2, aspect=w / h)
     cam = box.cam_origin
-    S = 3
     tx, ty = (w + 7) // 8, (h + 7) // 8
     J, R = jitters_of(S, w, h, 5), seeds_of(S, WARM)
     with context(evplp, box, w, h) as a, context(evplp, box, w, h) as b:
@@ -174,6 +176,8 @@ def test_adaptive_batch_equals_the_sequence(evplp, w, h):
         assert 0 < na < tx * ty and na == nb                              # a fraction strictly between 0 and 1, not assumed
         snap = b.download(evplp.BUF_VPL_ACCUM)[:h].copy()                 # R: the accumulator at retirement
         ca = sequence(evplp, a, cam, J, R); a.noise_fold(S)
+        if bound is not None:
+            b.path_trace_batch_scratch(bound)
         cb = batch(evplp, b, cam, J, R); b.noise_fold(S)
         ta, tb = a.adaptive_tiles(), b.adaptive_tiles()
         assert np.array_equal(ta, tb)
@@ -194,6 +198,17 @@ def test_adaptive_batch_equals_the_sequence(evplp, w, h):
         s1 = 1.0 / (WARM + S)
         assert a.noise_estimate(s1) == b.noise_estimate(s1)               # doubles, frozen figures of the retired tiles included
         assert a.noise_variance(s1)[:h].tobytes() == b.noise_variance(s1)[:h].tobytes()
+
+
+@pytest.mark.parametrize("w, h", [(W, H), ODD])
+def test_adaptive_batch_equals_the_sequence(evplp, w, h):
+    adaptive_batch_against_the_sequence(evplp, w, h, 3)
+
+
+@pytest.mark.parametrize("w, h", [(W, H), ODD])
+def test_adaptive_chunking_changes_no_bit(evplp, w, h):
+    """S = 8 under S + 3 slots: the chunks end inside an active tile's samples, and the retired tiles have no items at all"""
+    adaptive_batch_against_the_sequence(evplp, w, h, 8, (8 + 3) * SLOT)
 
 
 def test_every_tile_retired(evplp, room):

@@ -13,7 +13,7 @@ import pytest
 import scenes
 from test_gpu_adaptive import one_iteration
 from test_gpu_convergence import NL, NV, P, params, room as synth_room
-from test_gpu_pt_batch import BOUNCES, GBUF, ODD, SLOT, H, W, _refused, _render, assert_same, batch, context, jitters_of, planes, seeds_of, tile_mask
+from test_gpu_pt_batch import BOUNCES, GBUF, ODD, SLOT, H, W, _refused, _render, assert_same, batch, context, jitters_of, planes, seeds_of, sequence, tile_mask
 
 pytestmark = pytest.mark.gpu
 
@@ -185,7 +185,7 @@ def test_chunking_changes_no_bit(evplp, mixed):
     cls = class_map(w, h)
     needed = int(cls.sum())                                               # slots of a budgeted call: sum of s_t
     third = (needed // 3) * SLOT
-    for bound in (third, SLOT):
+    for bound in (third, 11 * SLOT, SLOT):                                # (11 slots: the chunks end inside the samples of the tiles of budget 4)
         with context(evplp, box, w, h) as c:
             c.path_trace_batch_scratch(bound)
 
@@ -200,6 +200,25 @@ def test_chunking_changes_no_bit(evplp, mixed):
                 c.path_trace_batch_scratch(bound)
             mixed_run(evplp, c, cam, w, h, cls, after_warm=one_byte_short)
             check_mixed(evplp, c, refs, full, w, h)
+
+
+@pytest.mark.parametrize("w, h", [(W, H), ODD])
+def test_chunks_that_end_inside_a_tile_change_no_bit(evplp, w, h):
+    """full budgets, S = 8 under S + 3 slots of staging, from the cleared and from the filled accumulator: the sequence of single calls of a
+    context with adaptivity off, byte for byte, and its pass counters"""
+    box = scenes.box_room(seed=7, n_boxes=4, tess=2, aspect=w / h)
+    cam = box.cam_origin
+    S8 = 8
+    with context(evplp, box, w, h) as a, context(evplp, box, w, h) as b:
+        a.clear_accumulators(); start(b)
+        b.path_trace_batch_scratch((S8 + 3) * SLOT)
+        for first in (1, 50):
+            J, R = jitters_of(S8, w, h, first), seeds_of(S8, first)
+            ca = sequence(evplp, a, cam, J, R)
+            cb = batch(evplp, b, cam, J, R); b.noise_fold(S8)
+            print(f"{w}x{h} S={S8}, {S8 + 3} slots: rays {ca[0]} / {cb[0]}, paths {ca[1]} / {cb[1]}")
+            assert_same(planes(evplp, a, h), planes(evplp, b, h), (w, h, first))
+            assert ca == cb and ca[1] > 0, (first, ca, cb)
 
 
 def test_noise_is_the_written_formula(evplp, mixed):

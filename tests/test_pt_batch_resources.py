@@ -1,7 +1,9 @@
-"""No GPU needed: the code objects of the batched path tracer (evplp_path_trace_batch).  Its kernels live in two new translation units --
-kernels_ptbatch_primary.hip, built like kernels_trace.hip with -ffp-contract=off for the whole unit, and kernels_ptbatch.hip with the
-path tracer's default flags -- and are held to zero scratch, no VGPR spills, 64 registers for the batched primary (eight waves per SIMD, as
-primary_kernel) and 128 for the batched trace (four, as path_trace_kernel).  kernels_pt.hip and kernels_trace.hip keep exactly their kernels."""
+"""No GPU needed: the code objects of the batched path tracer (evplp_path_trace_batch), one item-table pipeline for adaptivity off, mode 1 and
+budget mode.  Its kernels live in two translation units -- kernels_ptbatch_primary.hip, built like kernels_trace.hip with -ffp-contract=off for
+the whole unit (the batched primary; budget mode's per-tile fold and per-tile noise figure), and kernels_ptbatch.hip with the path tracer's
+default flags (the item table, the trace, the accumulation, the closing kernel) -- and are held to zero scratch, no VGPR spills, 64 registers
+for the batched primary (eight waves per SIMD, as primary_kernel) and 128 for the batched trace (four, as path_trace_kernel).  kernels_pt.hip
+and kernels_trace.hip keep exactly their kernels.  tests/test_pt_batch_same_arithmetic.py holds the trace to path_trace_kernel's operand shapes."""
 import os
 import re
 import subprocess
@@ -31,6 +33,10 @@ def table_of(src, extra=()):
     return table
 
 
+EXACT_UNIT = ("pt_batch_primary_kernel", "noise_fold_budget_kernel", "tile_noise_kernel")
+TABLE_UNIT = ("pt_batch_scan_kernel", "pt_batch_fill_kernel", "pt_batch_trace_kernel", "pt_batch_accumulate_kernel", "pt_batch_close_kernel")
+
+
 def only(table, want):
     hits = [k for k in table if want in k]
     assert len(hits) == 1, (want, sorted(table))
@@ -46,22 +52,42 @@ def test_the_makefile_builds_the_batched_primary_without_contraction():
 
 
 def test_batched_primary_keeps_the_budget():
+    """the unit without contraction: the batched primary and budget mode's two noise kernels, nothing else"""
     table = table_of("kernels_ptbatch_primary.hip", ["-ffp-contract=off"])
-    assert len(table) == 1, sorted(table)
+    assert len(table) == 3 and all(sum(1 for k in table if n in k) == 1 for n in EXACT_UNIT), sorted(table)
     t = only(table, "pt_batch_primary_kernel")
     assert t["private_segment_fixed_size"] == 0 and t["vgpr_spill_count"] == 0, t
     assert t["vgpr_count"] <= 64, t
 
 
-def test_batched_trace_list_reduce_and_rescale_keep_their_budgets():
-    table = table_of("kernels_ptbatch.hip")
-    names = ("pt_batch_list_kernel", "pt_batch_trace_kernel", "pt_batch_reduce_kernel", "pt_batch_rescale_kernel")
-    assert len(table) == len(names), sorted(table)
-    for n in names:
+def test_budget_fold_and_tile_noise_keep_their_budgets():
+    table = table_of("kernels_ptbatch_primary.hip", ["-ffp-contract=off"])
+    for n in EXACT_UNIT[1:]:
         t = only(table, n)
         assert t["private_segment_fixed_size"] == 0 and t["vgpr_spill_count"] == 0, (n, t)
-    assert only(table, "pt_batch_trace_kernel")["vgpr_count"] <= 128
-    assert only(table, "pt_batch_list_kernel")["group_segment_fixed_size"] <= 128              # (the scan's wave counts: no atomics, no big LDS)
+
+
+def test_batched_table_accumulate_and_close_keep_their_budgets():
+    table = table_of("kernels_ptbatch.hip")
+    assert len(table) == len(TABLE_UNIT), sorted(table)
+    for n in TABLE_UNIT:
+        if n != "pt_batch_trace_kernel":
+            t = only(table, n)
+            assert t["private_segment_fixed_size"] == 0 and t["vgpr_spill_count"] == 0, (n, t)
+    assert only(table, "pt_batch_scan_kernel")["group_segment_fixed_size"] <= 128              # (the scan's wave totals: no atomics, no big LDS)
+
+
+def test_batched_trace_keeps_its_budget():
+    t = only(table_of("kernels_ptbatch.hip"), "pt_batch_trace_kernel")
+    assert t["private_segment_fixed_size"] == 0 and t["vgpr_spill_count"] == 0, t
+    assert t["vgpr_count"] <= 128, t
+
+
+def test_the_batched_kernels_use_no_atomics_but_the_pass_counters():
+    """Nothing that reaches an image or a noise figure goes through an atomic: the only ones are the trace's rays and paths, one per wave."""
+    for src, want in (("kernels_ptbatch.hip", 2), ("kernels_ptbatch_primary.hip", 0)):
+        text = open(os.path.join(ROOT, "evplp_amd", "csrc", src)).read()
+        assert len(re.findall(r"\batomic\w*\(", text)) == want, src
 
 
 def test_the_existing_units_keep_exactly_their_kernels():
