@@ -141,6 +141,7 @@ _SIGNATURES = {
     "evplp_adaptive_tiles": (C.c_int, [_P, _P, C.c_int32]),
     "evplp_adaptive_set_budgets": (C.c_int, [_P, _P, C.c_int32]),
     "evplp_adaptive_budgets": (C.c_int, [_P, _P, C.c_int32]),
+    "evplp_adaptive_budget_window": (C.c_int, [_P, C.c_int32]),
     "evplp_adaptive_tile_noise": (C.c_int, [_P, C.c_float, C.c_float, C.c_int32, _P, C.c_int32]),
     "evplp_plan_budgets": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P]),
     "evplp_clear_accumulators": (C.c_int, [_P]),
@@ -203,6 +204,7 @@ _SIGNATURES = {
     "evplp_group_adaptive_tiles": (C.c_int, [_P, _P, C.c_int32]),
     "evplp_group_adaptive_set_budgets": (C.c_int, [_P, _P, C.c_int32]),
     "evplp_group_adaptive_budgets": (C.c_int, [_P, _P, C.c_int32]),
+    "evplp_group_adaptive_budget_window": (C.c_int, [_P, C.c_int32]),
     "evplp_group_adaptive_tile_noise": (C.c_int, [_P, C.c_float, C.c_float, C.c_int32, _P, C.c_int32]),
     "evplp_jitter_sequence": (C.c_int, [C.c_uint32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "evplp_json_query": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int32, C.POINTER(C.c_double), C.c_char_p, C.c_int32]),
@@ -573,11 +575,13 @@ class Context:
         self._check(self._lib.evplp_denoise(self._h, float(scale), float(light_scale), int(mask_emitter), C.byref(p), _ptr(out)))
         return out
 
-    def adaptive_enable(self, on=True, path_trace=False, budget=False):
+    def adaptive_enable(self, on=True, path_trace=False, budget=False, gather_budget=False):
         """Switch the adaptive gather on or off (before the first accumulating gather since the last clear; needs noise tracking; include/evplp.h).
         path_trace=True: path-trace mode instead (evplp_adaptive_enable_pt) -- path_trace() honours retirement and the gathers are refused"""
         if budget:        # budget mode (evplp_adaptive_enable_pt(.., 2)): every tile takes its own number of samples of a path_trace_batch call
             self._check(self._lib.evplp_adaptive_enable_pt(self._h, 2 if on else 0)); return
+        if gather_budget:     # gather budget mode (evplp_adaptive_enable(.., 2)): every tile takes the first b_t of every window of gather calls
+            self._check(self._lib.evplp_adaptive_enable(self._h, 2 if on else 0)); return
         f = self._lib.evplp_adaptive_enable_pt if path_trace else self._lib.evplp_adaptive_enable
         self._check(f(self._h, int(bool(on))))
 
@@ -602,6 +606,10 @@ class Context:
         out = np.zeros(((self.H + 7) // 8, (self.W + 7) // 8), dtype=np.int32)
         self._check(self._lib.evplp_adaptive_budgets(self._h, _ptr(out), out.size))
         return out
+
+    def adaptive_budget_window(self, window: int):
+        """gather budget mode: the window S (1 .. 64) -- a tile with budget b takes the first min(b, S) of every S accumulating gather calls"""
+        self._check(self._lib.evplp_adaptive_budget_window(self._h, int(window)))
 
     def adaptive_tile_noise(self, scale, light_scale=1.0, mask_emitter=False) -> np.ndarray:
         """float64 (ceil(H / 8), ceil(W / 8)): the mean relative variance of every tile, the figure adaptive_retire compares with tile_rel_mse"""
@@ -914,11 +922,13 @@ class Group:
         self._check(self._lib.evplp_group_denoise(self._h, float(scale), float(light_scale), int(mask_emitter), C.byref(p), _ptr(out)))
         return out
 
-    def adaptive_enable(self, on=True, path_trace=False, budget=False):
+    def adaptive_enable(self, on=True, path_trace=False, budget=False, gather_budget=False):
         """Switch the adaptive gather on or off (before the first accumulating gather since the last clear; needs noise tracking; include/evplp.h).
         path_trace=True: path-trace mode instead (evplp_group_adaptive_enable_pt) -- path_trace() honours retirement and gather() is refused"""
         if budget:        # budget mode (evplp_group_adaptive_enable_pt(.., 2)): every tile takes its own number of samples of a path_trace_batch call
             self._check(self._lib.evplp_group_adaptive_enable_pt(self._h, 2 if on else 0)); return
+        if gather_budget:     # gather budget mode (evplp_group_adaptive_enable(.., 2)): every tile takes the first b_t of every window of gather calls
+            self._check(self._lib.evplp_group_adaptive_enable(self._h, 2 if on else 0)); return
         f = self._lib.evplp_group_adaptive_enable_pt if path_trace else self._lib.evplp_group_adaptive_enable
         self._check(f(self._h, int(bool(on))))
 
@@ -943,6 +953,10 @@ class Group:
         out = np.zeros(((self.H + 7) // 8, (self.W + 7) // 8), dtype=np.int32)
         self._check(self._lib.evplp_group_adaptive_budgets(self._h, _ptr(out), out.size))
         return out
+
+    def adaptive_budget_window(self, window: int):
+        """gather budget mode: the window S (1 .. 64) -- a tile with budget b takes the first min(b, S) of every S accumulating gather calls"""
+        self._check(self._lib.evplp_group_adaptive_budget_window(self._h, int(window)))
 
     def adaptive_tile_noise(self, scale, light_scale=1.0, mask_emitter=False) -> np.ndarray:
         """float64 (ceil(H / 8), ceil(W / 8)): the mean relative variance of every tile, the figure adaptive_retire compares with tile_rel_mse"""

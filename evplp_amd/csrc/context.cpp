@@ -205,7 +205,7 @@ extern "C" void evplp_destroy(evplp_context *c) {
     hipFree(c->d_proxy_slabs); hipFree(c->d_proxy_hm); hipFree(c->d_tile_frags); hipFree(c->d_blocks); hipFree(c->d_block_cost);
     hipFree(c->d_err_ref); hipFree(c->d_err_keep); hipFree(c->d_err_rows);
     hipFree(c->d_noise); hipFree(c->d_noise_keep); hipFree(c->d_noise_rows);
-    hipFree(c->d_adapt_tiles); hipFree(c->d_adapt_snap);
+    hipFree(c->d_adapt_tiles); hipFree(c->d_adapt_snap); hipFree(c->d_adapt_mask);
     hipFree(c->d_dn_var); hipFree(c->d_dn_pack); hipFree(c->d_dn_u);
     hipFree(c->d_pt_batch); hipFree(c->d_pt_first); hipFree(c->d_pt_table); hipFree(c->d_tile_noise);
     for (int i = 0; i < EVPLP_PASS_COUNT; i++) {
@@ -740,6 +740,11 @@ static int run_gather(evplp_context *c, const evplp_frame_params *fp, bool vsl) 
     // launch gathers every tile (its clocks price whole blocks) and so needs every cut slot: the cut kernel skips nothing then.
     AdaptArgs ad{};
     if (c->d_adapt_tiles) { ad.tiles = c->d_adapt_tiles; ad.snap = c->d_adapt_snap; ad.n1 = (int32_t)(c->adapt_n + 1); }
+    // gather budget mode (evplp_adaptive_enable(ctx, 2)): the walks and the cut kernel read this call's mask in place of the records -- a tile
+    // that skips the call looks retired to them -- and the mode's own reduce follows the same mask
+    const bool gbudget = c->adapt_gather_budget;
+    const int32_t ntiles_all = c->tiles_x * c->tiles_y, phase = (int32_t)(c->adapt_m % c->adapt_window);
+    if (gbudget) ad.tiles = c->d_adapt_mask;
     // work-item size: k consecutive splits per wavefront (fixed summation tree: the result does not depend on k).  The per-item
     // statistics need (VPLs per split) * k < 65536.
     int k = 1;
@@ -796,6 +801,7 @@ static int run_gather(evplp_context *c, const evplp_frame_params *fp, bool vsl) 
     } else use_cuts = false;
     if ((rc = pass_begin(c, pass))) return rc;
     const uint32_t nrec = fp->photons_per_path * fp->num_vpl_light_paths;   // lighttracing.cu:368
+    if (gbudget) launch_gather_budget_mask(c->d_adapt_tiles, ntiles_all, phase, c->adapt_window, c->d_adapt_mask, c->stream);
     launch_compact_vpl((const evplp_record *)c->buf[EVPLP_BUF_RECORDS], nrec, c->d_vpls, c->d_vpl_src, &c->d_scalars[0], c->stream);
     if (use_cuts && !c->tile_box_valid) {      // the G-buffer did not come from evplp_primary (or the caller may have written it): boxes of the tiles as they are now
         launch_tile_boxes(c->st, (const float4 *)c->buf[EVPLP_BUF_GBUF_POSITION], c->d_tile_box, c->tiles_x, c->tiles_y, c->stream);
@@ -852,7 +858,13 @@ static int run_gather(evplp_context *c, const evplp_frame_params *fp, bool vsl) 
     }
     a.band_first = 0; a.band_rows = 0;
     HIP_TRY(c, hipEventRecord(c->ev_dom_end[pass], c->stream));
-    launch_gather_reduce(a, vsl ? 0 : 1, c->stream, ad);
+    if (gbudget) {
+        // R and the extrapolation, then n_t += takes on the device and in the host copy (the same rule on the same records)
+        launch_gather_reduce_budget(a, vsl ? 0 : 1, c->d_adapt_tiles, c->d_adapt_mask, c->d_adapt_snap, ad.n1, c->stream);
+        launch_gather_budget_step(c->d_adapt_tiles, c->d_adapt_mask, ntiles_all, c->stream);
+        for (int4 &r : c->adapt_tiles) if (gather_tile_takes(r, phase, c->adapt_window)) r.x += 1;
+        c->adapt_m++;
+    } else launch_gather_reduce(a, vsl ? 0 : 1, c->stream, ad);
     c->pass_has_dom[pass] = true;
     if ((rc = pass_end(c, pass))) return rc;
     if (fp->do_accumulate) c->adapt_n++;
@@ -1024,6 +1036,7 @@ extern "C" int evplp_splat_photons(evplp_context *c, const evplp_frame_params *f
     // Deterministic mode never leaves a pass pending behind a younger one: the re-run of an overflowed pass would otherwise be
     // enqueued before or after the younger pass depending on when its verdict arrives, and the float sums into the photon
     // accumulator would differ between runs.
+    if (c->adapt_gather_budget) { c->set_error("evplp_splat_photons: gather budget mode (evplp_adaptive_enable(ctx, 2)): a tile's VPL part has n_t samples and its photon part N; one set of moments cannot price both"); return EVPLP_ERR_INVALID; }
     const bool relaxed = c->aux_stream && !clear && !c->cfg.deterministic;
     int rc = pass_ready(c, "evplp_splat_photons", true, !relaxed); if (rc) return rc;
     if (relaxed) {
@@ -1054,6 +1067,7 @@ extern "C" int evplp_splat_photons(evplp_context *c, const evplp_frame_params *f
     // variants it replaces): below that the heavy list stays nearly empty and its bookkeeping costs more than four waves save
     if (c->env_tile_mixed && c->last_bin_max >= c->mixed_trigger) { a.heavy_list = c->d_heavy_list; a.tile_flags = c->d_tile_flags; a.heavy_cap = c->heavy_cap; a.heavy_threshold = c->heavy_threshold; }
     if ((rc = pass_begin(c, EVPLP_PASS_SPLAT))) return rc;
+    c->splat_n++;
     if (clear) HIP_TRY(c, hipMemsetAsync(c->buf[EVPLP_BUF_PHOTON_ACCUM], 0, buffer_bytes(c, EVPLP_BUF_PHOTON_ACCUM), c->stream));
     launch_splat_bin(a, c->stream);                                       // (clears the overflow flag, the cursors and the summary)
     // Tile kernel variant.  (Round 5: when the previous pass had bins of >= mixed_trigger entries the launch is MIXED -- a.heavy_list above,
@@ -1405,8 +1419,9 @@ extern "C" int evplp_denoise(evplp_context *c, float scale, float ls, int32_t ma
 
 // ---- adaptive gather: tiles retire once their estimated noise is low enough (include/evplp.h evplp_adaptive_*)
 static void release_adapt(evplp_context *c) {
-    hipFree(c->d_adapt_tiles); hipFree(c->d_adapt_snap);
-    c->d_adapt_tiles = nullptr; c->d_adapt_snap = nullptr; c->adapt_tiles.clear(); c->adapt_pt = false; c->adapt_budget = false;
+    hipFree(c->d_adapt_tiles); hipFree(c->d_adapt_snap); hipFree(c->d_adapt_mask);
+    c->d_adapt_tiles = nullptr; c->d_adapt_snap = nullptr; c->d_adapt_mask = nullptr; c->adapt_tiles.clear(); c->adapt_pt = false; c->adapt_budget = false;
+    c->adapt_gather_budget = false; c->adapt_m = 0;
 }
 static size_t adapt_tile_count(const evplp_context *c) { return (size_t)c->tiles_x * (size_t)c->tiles_y; }
 // every tile active (stream order); the records are (re)allocated when the planes' tiles have changed (a new block table)
@@ -1414,7 +1429,7 @@ static int adapt_reset(evplp_context *c) {
     const size_t nt = adapt_tile_count(c), px = (size_t)c->st.W * c->st.local_rows;
     if (c->adapt_tiles.size() != nt) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        hipFree(c->d_adapt_tiles); hipFree(c->d_adapt_snap); c->d_adapt_tiles = nullptr; c->d_adapt_snap = nullptr;
+        hipFree(c->d_adapt_tiles); hipFree(c->d_adapt_snap); hipFree(c->d_adapt_mask); c->d_adapt_tiles = nullptr; c->d_adapt_snap = nullptr; c->d_adapt_mask = nullptr;
         hipFree(c->d_pt_first); hipFree(c->d_tile_noise); c->d_pt_first = nullptr; c->d_tile_noise = nullptr;       // (sized by the tile count too)
         hipError_t e = hipMalloc((void **)&c->d_adapt_tiles, sizeof(int4) * std::max<size_t>(nt, 1));
         if (e == hipSuccess) e = hipMalloc((void **)&c->d_adapt_snap, sizeof(float4) * std::max<size_t>(px, 1));
@@ -1424,7 +1439,17 @@ static int adapt_reset(evplp_context *c) {
             return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP;
         }
     }
+    // gather budget mode alone pays for the per-call view of the records (16 B per tile); the other modes never touch it
+    if (c->adapt_gather_budget && !c->d_adapt_mask) {
+        const hipError_t e = hipMalloc((void **)&c->d_adapt_mask, sizeof(int4) * std::max<size_t>(nt, 1));
+        if (e != hipSuccess) {
+            (void)hipGetLastError(); release_adapt(c);
+            c->set_error("evplp_adaptive_enable: cannot allocate %zu bytes: %s", sizeof(int4) * nt, hipGetErrorString(e));
+            return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP;
+        }
+    }
     c->adapt_tiles.assign(nt, make_int4(0, 0, 0, c->adapt_budget ? -1 : 0));
+    c->adapt_m = 0;
     if (c->adapt_budget) {
         // budget mode: every record { 0, 0, 0, -1 } (all samples of a call), and the raw sums R start as the accumulator itself (N = 0)
         if (nt) HIP_TRY(c, hipMemcpyAsync(c->d_adapt_tiles, c->adapt_tiles.data(), sizeof(int4) * nt, hipMemcpyHostToDevice, c->stream));
@@ -1448,12 +1473,19 @@ static int adaptive_enable_mode(evplp_context *c, int32_t on, bool pt, const cha
         release_adapt(c);
         return EVPLP_OK;
     }
-    const bool budget = pt && on == 2;
-    const bool was = c->adapt_budget;
-    c->adapt_budget = budget;
+    // on = 2: budget mode, the path tracer's (pt) or the gathers'
+    const bool budget = on == 2;
+    if (budget && !pt && c->splat_n > 0) {
+        c->set_error("%s: %lld photon splat(s) since the last clear: gather budget mode has no place for them (evplp_clear_accumulators)", name, (long long)c->splat_n);
+        return EVPLP_ERR_INVALID;
+    }
+    const bool was = c->adapt_budget, was_gather = c->adapt_gather_budget;
+    c->adapt_budget = budget; c->adapt_gather_budget = budget && !pt;       // (adapt_reset allocates by these)
     const int rc = adapt_reset(c);
-    if (rc == EVPLP_OK) c->adapt_pt = pt;
-    else c->adapt_budget = c->d_adapt_tiles ? was : false;
+    if (rc == EVPLP_OK) {
+        c->adapt_pt = pt; c->adapt_window = 16;
+        if (!c->adapt_gather_budget && c->d_adapt_mask) { hipFree(c->d_adapt_mask); c->d_adapt_mask = nullptr; }     // (left the mode with N = 0: nothing in flight reads it)
+    } else { c->adapt_budget = c->d_adapt_tiles ? was : false; c->adapt_gather_budget = c->d_adapt_tiles ? was_gather : false; }
     return rc;
 }
 extern "C" int evplp_adaptive_enable(evplp_context *c, int32_t on) { CTX_CHECK(c); return adaptive_enable_mode(c, on, false, "evplp_adaptive_enable"); }
@@ -1461,7 +1493,7 @@ extern "C" int evplp_adaptive_enable_pt(evplp_context *c, int32_t on) { CTX_CHEC
 extern "C" int evplp_adaptive_retire(evplp_context *c, float scale, float ls, int32_t mask_emitter, double tau, int32_t min_batches) {
     CTX_CHECK(c);
     if (!c->d_adapt_tiles) { c->set_error("evplp_adaptive_retire: adaptivity is off (evplp_adaptive_enable)"); return EVPLP_ERR_INVALID; }
-    if (c->adapt_budget) { c->set_error("evplp_adaptive_retire: budget mode (evplp_adaptive_enable_pt(ctx, 2)): set the tile's budget to 0 instead (evplp_adaptive_set_budgets)"); return EVPLP_ERR_INVALID; }
+    if (c->adapt_budget) { c->set_error("evplp_adaptive_retire: budget mode (evplp_adaptive_enable(ctx, 2) / evplp_adaptive_enable_pt(ctx, 2)): set the tile's budget to 0 instead (evplp_adaptive_set_budgets)"); return EVPLP_ERR_INVALID; }
     if (!c->d_noise) { c->set_error("evplp_adaptive_retire: noise tracking is off (evplp_noise_track)"); return EVPLP_ERR_INVALID; }
     if (!(tau >= 0.0)) { c->set_error("evplp_adaptive_retire: tile_rel_mse must be >= 0, not %g", tau); return EVPLP_ERR_INVALID; }
     if (min_batches < 2) { c->set_error("evplp_adaptive_retire: min_batches must be >= 2, not %d", min_batches); return EVPLP_ERR_INVALID; }
@@ -1521,7 +1553,7 @@ template <class F> static void for_own_tiles(const evplp_context *c, F f) {
 extern "C" int evplp_adaptive_set_budgets(evplp_context *c, const int32_t *samples_per_image_tile, int32_t count) {
     CTX_CHECK(c);
     const char *name = "evplp_adaptive_set_budgets";
-    if (!c->adapt_budget) { c->set_error("%s: budget mode is off (evplp_adaptive_enable_pt(ctx, 2))", name); return EVPLP_ERR_INVALID; }
+    if (!c->adapt_budget) { c->set_error("%s: budget mode is off (evplp_adaptive_enable(ctx, 2) / evplp_adaptive_enable_pt(ctx, 2))", name); return EVPLP_ERR_INVALID; }
     const int64_t n = image_tile_count(c);
     if (!samples_per_image_tile || count != n) { c->set_error("%s: the image has %lld tiles, the call gives %d", name, (long long)n, samples_per_image_tile ? count : 0); return EVPLP_ERR_INVALID; }
     for (int64_t t = 0; t < n; t++)
@@ -1533,14 +1565,23 @@ extern "C" int evplp_adaptive_set_budgets(evplp_context *c, const int32_t *sampl
     if (c->noise_k != c->adapt_n) { c->set_error("%s: %lld of %lld samples are folded: fold first (evplp_noise_fold)", name, (long long)c->noise_k, (long long)c->adapt_n); return EVPLP_ERR_INVALID; }
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     for_own_tiles(c, [&](size_t local, size_t image) { c->adapt_tiles[local].w = samples_per_image_tile[image]; });
+    c->adapt_m = 0;                 // (gather budget mode: a new window starts)
     const size_t nt = adapt_tile_count(c);
     if (nt) HIP_TRY(c, hipMemcpyAsync(c->d_adapt_tiles, c->adapt_tiles.data(), sizeof(int4) * nt, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return EVPLP_OK;
 }
+extern "C" int evplp_adaptive_budget_window(evplp_context *c, int32_t window) {
+    CTX_CHECK(c);
+    const char *name = "evplp_adaptive_budget_window";
+    if (!c->adapt_gather_budget) { c->set_error("%s: gather budget mode is off (evplp_adaptive_enable(ctx, 2))", name); return EVPLP_ERR_INVALID; }
+    if (window < 1 || window > kGatherBudgetMaxWindow) { c->set_error("%s: a window is 1 .. %d calls, not %d", name, kGatherBudgetMaxWindow, window); return EVPLP_ERR_INVALID; }
+    c->adapt_window = window; c->adapt_m = 0;
+    return EVPLP_OK;
+}
 extern "C" int evplp_adaptive_budgets(evplp_context *c, int32_t *out, int32_t capacity) {
     CTX_CHECK(c);
-    if (!c->adapt_budget) { c->set_error("evplp_adaptive_budgets: budget mode is off (evplp_adaptive_enable_pt(ctx, 2))"); return EVPLP_ERR_INVALID; }
+    if (!c->adapt_budget) { c->set_error("evplp_adaptive_budgets: budget mode is off (evplp_adaptive_enable(ctx, 2) / evplp_adaptive_enable_pt(ctx, 2))"); return EVPLP_ERR_INVALID; }
     const int64_t n = image_tile_count(c);
     if (!out || capacity < n) { c->set_error("evplp_adaptive_budgets: the image has %lld tiles, the output holds %d", (long long)n, capacity); return EVPLP_ERR_INVALID; }
     std::fill(out, out + n, 0);
@@ -1664,7 +1705,7 @@ extern "C" int evplp_clear_accumulators(evplp_context *c) {
     HIP_TRY(c, hipMemsetAsync(c->buf[EVPLP_BUF_VPL_ACCUM], 0, buffer_bytes(c, EVPLP_BUF_VPL_ACCUM), c->stream));
     HIP_TRY(c, hipMemsetAsync(c->buf[EVPLP_BUF_PHOTON_ACCUM], 0, buffer_bytes(c, EVPLP_BUF_PHOTON_ACCUM), c->stream));
     HIP_TRY(c, hipMemsetAsync(c->buf[EVPLP_BUF_LIGHT], 0, buffer_bytes(c, EVPLP_BUF_LIGHT), c->stream));
-    c->adapt_n = 0;
+    c->adapt_n = 0; c->splat_n = 0;
     if (c->d_adapt_tiles) { int rc_ = adapt_reset(c); if (rc_) return rc_; }     // (every tile is active again)
     if (c->d_noise) return noise_restart(c);                                  // (noise tracking starts again from the empty sums)
     return EVPLP_OK;

@@ -168,6 +168,10 @@ struct evplp_context {
     // budget mode (evplp_adaptive_enable_pt(ctx, 2)): adapt_pt is set too; the records' host copy follows the device's in every field (a call
     // adds s_t to n_t, a fold closes K_t and B_t: both are functions of the records alone); evplp_adaptive_tile_noise's per-tile doubles [tiles]
     bool adapt_budget = false; double *d_tile_noise = nullptr;
+    // gather budget mode (evplp_adaptive_enable(ctx, 2)): adapt_budget is set, adapt_pt is not.  Tile t takes call m of the accumulating gathers
+    // iff gather_tile_takes(record, m % S, S) (kernels.h); adapt_m restarts at set_budgets, at a new window, at a clear.  d_adapt_mask: the
+    // per-call view of the records the gather kernels read [tiles].  splat_n: photon splats since the last clear (the mode has no place for them)
+    bool adapt_gather_budget = false; int32_t adapt_window = 16; int64_t adapt_m = 0; int4 *d_adapt_mask = nullptr; int64_t splat_n = 0;
     // evplp_denoise: the variance image [W * local_rows][3], the packed pixels of the planes [W * local_rows] (kernels.h DenoisePixel), and
     // the two (u, s) planes of the a-trous passes [2][dn_u_px] (the frame the context filters: its planes, or a group's whole image on rank 0);
     // allocated on the first call, kept until evplp_destroy

@@ -137,7 +137,8 @@ struct evplp_group {
     bool noise_on = false;                  // evplp_group_noise_track is on on every rank (caller's thread)
     bool adapt_on = false;                  // evplp_group_adaptive_enable is on on every rank (caller's thread)
     bool adapt_pt = false;                  // ... and in path-trace mode (evplp_group_adaptive_enable_pt)
-    bool adapt_budget = false;              // ... and that in budget mode (on = 2)
+    bool adapt_budget = false;              // budget mode (on = 2), the path tracer's or the gathers'
+    bool adapt_gather_budget = false;       // ... the gathers' (evplp_group_adaptive_enable(g, 2))
     uint64_t pt_batch_cap = 1ull << 30;     // evplp_group_path_trace_batch_scratch: every rank's bound (caller's thread)
     // EVPLP_PARTITION_ITERATIONS, evplp_group_noise_*: rank 0's pooled moments (Q then S, [3][stride] fp64 each) and K / B summed over the
     // ranks (written by rank 0's worker); RCCL only: per rank [n][noise_bytes] every rank's NoisePlanes (all-gathered)
@@ -778,6 +779,7 @@ extern "C" int evplp_group_splat_photons(evplp_group *g, const evplp_frame_param
     GRP_CHECK(g);
     if (!fp) { g->set_error("evplp_group_splat_photons: null frame params"); return EVPLP_ERR_INVALID; }
     { int rc = check_frame_params(g, fp, "evplp_group_splat_photons", true); if (rc < 0) return rc; }
+    if (g->adapt_gather_budget) { g->set_error("evplp_group_splat_photons: gather budget mode (evplp_group_adaptive_enable(g, 2)): one set of moments cannot price n_t VPL samples and N photon passes"); return EVPLP_ERR_INVALID; }
     Cmd c; c.op = OP_SPLAT; c.fp = *fp; c.i[0] = clear;
     return post_pass(g, c);
 }
@@ -1050,11 +1052,15 @@ static int group_adaptive_enable(evplp_group *g, int32_t on, bool pt, const char
     for (evplp_context *c : g->ctx)
         if (c->adapt_n > 0) { g->set_error("%s: %lld gather(s) have accumulated since the last clear", name, (long long)c->adapt_n); return EVPLP_ERR_INVALID; }
     if (on && !g->noise_on) { g->set_error("%s: noise tracking is off (evplp_group_noise_track)", name); return EVPLP_ERR_INVALID; }
+    if (on == 2 && !pt)
+        for (evplp_context *c : g->ctx)
+            if (c->splat_n > 0) { g->set_error("%s: %lld photon splat(s) since the last clear: gather budget mode has no place for them", name, (long long)c->splat_n); return EVPLP_ERR_INVALID; }
     Cmd c; c.op = OP_ADAPT_ENABLE; c.i[0] = on; c.i[1] = pt ? 1 : 0;
     rc = post_and_wait(g, c);
     g->adapt_on = rc >= 0 && on != 0;
     g->adapt_pt = g->adapt_on && pt;
-    g->adapt_budget = g->adapt_pt && on == 2;
+    g->adapt_budget = g->adapt_on && on == 2;
+    g->adapt_gather_budget = g->adapt_budget && !pt;
     return rc;
 }
 extern "C" int evplp_group_adaptive_enable(evplp_group *g, int32_t on) { GRP_CHECK(g); return group_adaptive_enable(g, on, false, "evplp_group_adaptive_enable"); }
@@ -1064,7 +1070,7 @@ extern "C" int evplp_group_adaptive_retire(evplp_group *g, float scale, float ls
     int rc = adapt_group_ready(g, "evplp_group_adaptive_retire");
     if (rc < 0) return rc;
     if (!g->ctx[0]->d_adapt_tiles) { g->set_error("evplp_group_adaptive_retire: adaptivity is off (evplp_group_adaptive_enable)"); return EVPLP_ERR_INVALID; }
-    if (g->adapt_budget) { g->set_error("evplp_group_adaptive_retire: budget mode (evplp_group_adaptive_enable_pt(g, 2)): set the tile's budget to 0 instead"); return EVPLP_ERR_INVALID; }
+    if (g->adapt_budget) { g->set_error("evplp_group_adaptive_retire: budget mode (evplp_group_adaptive_enable(g, 2) / evplp_group_adaptive_enable_pt(g, 2)): set the tile's budget to 0 instead"); return EVPLP_ERR_INVALID; }
     if (!(tau >= 0.0)) { g->set_error("evplp_group_adaptive_retire: tile_rel_mse must be >= 0, not %g", tau); return EVPLP_ERR_INVALID; }
     if (min_batches < 2) { g->set_error("evplp_group_adaptive_retire: min_batches must be >= 2, not %d", min_batches); return EVPLP_ERR_INVALID; }
     Cmd c; c.op = OP_ADAPT_RETIRE; c.f[0] = scale; c.f[1] = ls; c.i[0] = mask_emitter; c.i[1] = min_batches; c.d = tau;
@@ -1094,7 +1100,7 @@ extern "C" int evplp_group_adaptive_set_budgets(evplp_group *g, const int32_t *s
     const char *name = "evplp_group_adaptive_set_budgets";
     int rc = adapt_group_ready(g, name);
     if (rc < 0) return rc;
-    if (!g->adapt_budget) { g->set_error("%s: budget mode is off (evplp_group_adaptive_enable_pt(g, 2))", name); return EVPLP_ERR_INVALID; }
+    if (!g->adapt_budget) { g->set_error("%s: budget mode is off (evplp_group_adaptive_enable(g, 2) / evplp_group_adaptive_enable_pt(g, 2))", name); return EVPLP_ERR_INVALID; }
     const int64_t n = group_image_tiles(g);
     if (!samples_per_image_tile || count != n) { g->set_error("%s: the image has %lld tiles, the call gives %d", name, (long long)n, samples_per_image_tile ? count : 0); return EVPLP_ERR_INVALID; }
     for (int64_t t = 0; t < n; t++)
@@ -1108,12 +1114,23 @@ extern "C" int evplp_group_adaptive_set_budgets(evplp_group *g, const int32_t *s
     Cmd c; c.op = OP_ADAPT_SET_BUDGETS; c.p0 = samples_per_image_tile; c.i[0] = count;
     return post_and_wait(g, c);                     // (the caller's array is read before the call returns)
 }
+// (host state of the contexts only: set on the caller's thread once the workers are idle, as evplp_group_path_trace_batch_scratch does)
+extern "C" int evplp_group_adaptive_budget_window(evplp_group *g, int32_t window) {
+    GRP_CHECK(g);
+    const char *name = "evplp_group_adaptive_budget_window";
+    int rc = adapt_group_ready(g, name);
+    if (rc < 0) return rc;
+    if (!g->adapt_gather_budget) { g->set_error("%s: gather budget mode is off (evplp_group_adaptive_enable(g, 2))", name); return EVPLP_ERR_INVALID; }
+    if (window < 1 || window > evplp::kGatherBudgetMaxWindow) { g->set_error("%s: a window is 1 .. %d calls, not %d", name, evplp::kGatherBudgetMaxWindow, window); return EVPLP_ERR_INVALID; }
+    for (evplp_context *c : g->ctx) { c->adapt_window = window; c->adapt_m = 0; }
+    return EVPLP_OK;
+}
 extern "C" int evplp_group_adaptive_budgets(evplp_group *g, int32_t *out, int32_t capacity) {
     GRP_CHECK(g);
     const char *name = "evplp_group_adaptive_budgets";
     int rc = adapt_group_ready(g, name);
     if (rc < 0) return rc;
-    if (!g->adapt_budget) { g->set_error("%s: budget mode is off (evplp_group_adaptive_enable_pt(g, 2))", name); return EVPLP_ERR_INVALID; }
+    if (!g->adapt_budget) { g->set_error("%s: budget mode is off (evplp_group_adaptive_enable(g, 2) / evplp_group_adaptive_enable_pt(g, 2))", name); return EVPLP_ERR_INVALID; }
     const int64_t n = group_image_tiles(g);
     if (!out || capacity < n) { g->set_error("%s: the image has %lld tiles, the output holds %d", name, (long long)n, capacity); return EVPLP_ERR_INVALID; }
     std::fill(out, out + n, 0);

@@ -498,6 +498,9 @@ private:
 // every everyIterations fold the loop reads the tiles' noise with its own 1 / i scale and their sample counts, plans with S = samplesPerCall
 // (evplp_plan_budgets) and sets the tiles' budgets for the calls that follow.  tileRelMse 0 then means "never stop a tile"; the loop ends
 // when every budget is 0.  The checkpoints gain "budgetSamples"; "activeTiles" counts the tiles whose budget is not 0.
+// photonfam's "adaptive" takes "budget" too: {"window": 16, "minSamples": 1, "referenceQuantile": 1.0} -- gather budget mode
+// (evplp_group_adaptive_enable(g, 2)): a tile takes the first b_t of every `window` gathers; everyIterations is a multiple of window, the plan
+// uses S = window, the loop ends when every budget is 0.  Refused where the loop would splat photons (the mode has no place for them).
 class Adaptive {
 public:
     // key: "adaptive" (photonfam: the gathers retire tiles) or "adaptiveSampling" (pt: the path tracer does, evplp_group_adaptive_enable_pt)
@@ -505,7 +508,9 @@ public:
     bool on = false;
     // pt: no tile is active any more -- the loop has nothing left to sample
     bool all_retired(const Noise &noise) const { return on && noise.image_tiles > 0 && noise.retired_tiles >= noise.image_tiles; }
-    void parse(const Json &tech, const std::string &out_dir, int frame_mode, bool lvc, bool iterations_partition, Noise &noise) {
+    // gathers only: every budget is 0 -- the loop has nothing left to gather (retirement alone never ends photonfam's loop: photons go on)
+    bool budget_spent(const Noise &noise) const { return budget && all_retired(noise); }
+    void parse(const Json &tech, const std::string &out_dir, int frame_mode, bool lvc, bool iterations_partition, Noise &noise, bool splats_photons = false) {
         if (!tech.has(key)) return;
         const Json &c = tech.at(key);
         if (!c.is_object()) throw JsonError(key + ": expected an object");
@@ -530,11 +535,19 @@ public:
         if (c.has("iterationsFilename")) iterations_filename = output_path(out_dir, c.at("iterationsFilename").as_string((key + ".iterationsFilename").c_str()));
         if (c.has("budget")) {
             const Json &b = c.at("budget");
-            if (!pt) throw JsonError(key + ".budget: not for the gathers (pt's \"adaptiveSampling\" only)");
             if (!b.is_object()) throw JsonError(key + ".budget: expected an object");
+            if (!pt && splats_photons) throw JsonError(key + ".budget: not with the photon splat (run.photonSplat and a photon radius > 0): a tile's VPL part would have n_t samples and its photon part N");
             if (b.has("minSamples")) budget_min = b.at("minSamples").as_int((key + ".budget.minSamples").c_str());
             if (b.has("referenceQuantile")) budget_q = b.at("referenceQuantile").as_number((key + ".budget.referenceQuantile").c_str());
             if (!(budget_q > 0.0) || !(budget_q <= 1.0)) throw JsonError(key + ".budget.referenceQuantile: must be in (0, 1]");
+            if (!pt) {      // the gathers: the window takes samplesPerCall's place
+                long long window = 16;
+                if (b.has("window")) window = b.at("window").as_int((key + ".budget.window").c_str());
+                if (window < 1 || window > 64) throw JsonError(key + ".budget.window: must be 1 .. 64");
+                if (every % window != 0) throw JsonError(key + ".everyIterations: must be a multiple of " + key + ".budget.window");
+                if (budget_min < 1 || budget_min > window) throw JsonError(key + ".budget.minSamples: must be 1 .. window");
+                budget_samples_per_call = (int32_t)window;
+            } else if (b.has("window")) throw JsonError(key + ".budget.window: the gathers' key (pt's window is samplesPerCall)");
             budget = noise.budget = true;
         }
         noise.adaptive = true;
@@ -542,7 +555,7 @@ public:
     }
     // once "samplesPerCall" is known (pt parses it behind this block)
     void parse_budget_samples(int samples_per_call) {
-        if (!budget) return;
+        if (!budget || !pt) return;
         if (samples_per_call <= 1) throw JsonError(key + ".budget: needs \"samplesPerCall\" > 1 (a budget is a share of a batched call)");
         if (budget_min < 1 || budget_min > samples_per_call) throw JsonError(key + ".budget.minSamples: must be 1 .. samplesPerCall");
         budget_samples_per_call = samples_per_call;
@@ -550,7 +563,8 @@ public:
     // before the loop's first gather (after the clear and any rebalance: N = 0)
     void start(evplp_group *g, int W, int H, Noise &noise) {
         if (!on) return;
-        check(g, pt ? evplp_group_adaptive_enable_pt(g, budget ? 2 : 1) : evplp_group_adaptive_enable(g, 1), key.c_str());
+        check(g, pt ? evplp_group_adaptive_enable_pt(g, budget ? 2 : 1) : evplp_group_adaptive_enable(g, budget ? 2 : 1), key.c_str());
+        if (budget && !pt) check(g, evplp_group_adaptive_budget_window(g, budget_samples_per_call), (key + ".budget.window").c_str());
         noise.image_tiles = (long long)((W + 7) / 8) * ((H + 7) / 8);
         if (budget) {
             noise.budget_samples = noise.image_tiles * budget_samples_per_call;
@@ -838,7 +852,7 @@ public:
             if (d.has("vslMaskGB")) cfg.vsl_mask_bytes = (uint64_t)(std::max(d.at("vslMaskGB").as_float("device.vslMaskGB"), 0.0f) * 1073741824.0);
         }
         run_opts = run_options(json);
-        adaptive.parse(json, out_dir, frame_mode, lvc, run_opts.shard_iterations, noise);                          // build-only key
+        adaptive.parse(json, out_dir, frame_mode, lvc, run_opts.shard_iterations, noise, do_photon_splat && radius_percentage > 0.0f);   // build-only key
         const int gpus = device_gpus(json);
         if (run_opts.shard_iterations && (frame_mode != 1 || gpus < 2)) {
             if (gpus >= 2) std::printf("note: device.partition \"iterations\" needs frameMode \"accumulate\"; running on row strips\n");
@@ -976,6 +990,7 @@ private:
                 adaptive.after_fold(h, num_iterations, folded, saved_param(num_iterations), noise);
                 if (noise.due(num_iterations, elapsed_ms(), folded) &&
                     noise.checkpoint(h, num_iterations, [&] { wait_for_next(); return (double)elapsed_ms(); }, saved_param(num_iterations), 1.0f, 0)) break;
+                if (adaptive.budget_spent(noise)) break;                                  // gather budget mode: every budget is 0
             }
             if (elapsed_ms() >= time_limit_ms) break;                                         // :1065
         }

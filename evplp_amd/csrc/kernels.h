@@ -159,6 +159,19 @@ struct PtBatchSamples { float jitter[kPtBatchMaxSamples][2]; uint32_t seed[kPtBa
 __host__ __device__ inline int32_t pt_tile_samples(int32_t mode, int4 r, int32_t S) {
     return mode == 0 ? S : mode == 1 ? (r.x == 0 ? S : 0) : (r.w < 0 || r.w > S ? S : r.w);
 }
+// Gather budget mode (evplp_adaptive_enable(ctx, 2), r = { n_t, K_t, B_t, b_t }): does the tile take the accumulating gather call at `phase` =
+// m % S of its window of S calls?  The first min(b_t, S) calls of every window, -1 = all: the mask kernel's rule and the host's (n_t).
+__host__ __device__ inline bool gather_tile_takes(int4 r, int32_t phase, int32_t S) {
+    return r.w < 0 || phase < (r.w < S ? r.w : S);
+}
+constexpr int kGatherBudgetMaxWindow = 64;
+// The mode's three kernels (kernels_gather.hip).  mask[t] = { takes ? 0 : max(n_t, 1), takes, 0, 0 }: .x is what the gathers' ADAPT variants and
+// the cut kernel read in place of the records, so a skipping tile looks retired to them for this call; .y is what the reduce and the step read.  The reduce writes R = reduce_out(tree, .., R) into the
+// snapshot plane for the written pixels of a taking tile and VPL_ACCUM = extrapolate(R, n1, n_t + takes) for every in-image pixel; the step
+// kernel then does n_t += takes (one thread per tile, after the reduce: a tile's pixels lie in several of the reduce's workgroups).
+void launch_gather_budget_mask(const int4 *tiles, int32_t ntiles, int32_t phase, int32_t window, int4 *mask, hipStream_t s);
+void launch_gather_budget_step(int4 *tiles, const int4 *mask, int32_t ntiles, hipStream_t s);
+void launch_gather_reduce_budget(const GatherArgs &a, int stencil_test, const int4 *tiles, const int4 *mask, float4 *snap, int32_t n1, hipStream_t s);
 // one chunk of a call: the items [item_first, item_first + item_count), slot = item - item_first; items at or beyond the total exit
 struct PtBatchChunk {
     const uint32_t *table; const int32_t *total;

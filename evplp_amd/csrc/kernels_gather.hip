@@ -460,19 +460,66 @@ __global__ __launch_bounds__(256) void gather_reduce_kernel(GatherArgs a, int st
     if (ADAPT && writes && nt != 0) {
         a.out[i] = extrapolate(ad.snap[i], ad.n1, nt);
     } else if (writes) {
-        const int groups = kVplSplit / a.splits_per_wave;
-        V3 r = v3(0.f, 0.f, 0.f), lv0 = r, lv1 = r, lv2 = r, lv3 = r, lv4 = r, lv5 = r, lv6 = r;
-        for (int g = 0; g < groups; g++) {
-            float4 q = a.partial[(size_t)g * a.partial_stride + i];
-            const uint32_t st = __float_as_uint(q.w);
-            rays += st & 0xffffu; shaded += st >> 16;
-            r = v3(q.x, q.y, q.z);
-            // binary counter over g (level j holds the sum of 2^j consecutive partials): merge while the low bits of g are ones
-#define EV_MERGE(L, NEXT) if (((g >> L) & 1) == 0) lv##L = r; else { r = lv##L + r; NEXT }
-            EV_MERGE(0, EV_MERGE(1, EV_MERGE(2, EV_MERGE(3, EV_MERGE(4, EV_MERGE(5, EV_MERGE(6, ;)))))))
-#undef EV_MERGE
-        }
+#include "reduce_tree_body.hpp"
         a.out[i] = reduce_out(r, (float)a.fp.num_vpl_light_paths, (float)a.fp.do_accumulate, a.out[i]);
+    }
+    __shared__ unsigned long long s_sum[2];
+    if (threadIdx.x < 2) s_sum[threadIdx.x] = 0ull;
+    __syncthreads();
+    for (int off = 32; off > 0; off >>= 1) { rays += __shfl_down(rays, off); shaded += __shfl_down(shaded, off); }
+    if ((threadIdx.x & 63) == 0) { atomicAdd(&s_sum[0], rays); atomicAdd(&s_sum[1], shaded); }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int shard = blockIdx.x & (kCounterShards - 1);
+        atomicAdd(&a.counters->shard_rays[shard], s_sum[0]);
+        atomicAdd(&a.counters->shard_shaded[shard], s_sum[1]);
+    }
+}
+
+// Gather budget mode (evplp_adaptive_enable(ctx, 2); kernels.h gather_tile_takes).  One thread per tile: the per-call view of the records that
+// tile_retired, the VSL kernels and gather_cut_kernel<true> read -- a tile that skips this call shows a non-zero .x where a retired tile would
+// show its n_t (max(n_t, 1): a skipping tile that has not taken a call yet must not read as taking).  .y = takes, for the mode's own kernels.
+__global__ __launch_bounds__(256) void gather_budget_mask_kernel(const int4 *tiles, int32_t ntiles, int32_t phase, int32_t window, int4 *mask) {
+    const int t = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (t >= ntiles) return;
+    const int4 r = tiles[t];
+    const bool takes = gather_tile_takes(r, phase, window);
+    mask[t] = make_int4(takes ? 0 : max(r.x, 1), takes ? 1 : 0, 0, 0);
+}
+// n_t += takes, after the reduce has read n_t (stream order)
+__global__ __launch_bounds__(256) void gather_budget_step_kernel(int4 *tiles, const int4 *mask, int32_t ntiles) {
+    const int t = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (t >= ntiles) return;
+    if (mask[t].y != 0) tiles[t].x += 1;
+}
+// The mode's reduce: gather_reduce_kernel's tree and reduce_out, on the raw sums.  A pixel the plain reduce would write, in a tile that takes
+// the call: R = reduce_out(tree, numVplLightPaths, do_accumulate (1 in the mode), R), into the snapshot plane.  Every in-image pixel of every
+// tile: VPL_ACCUM = extrapolate(R, n1, n_t + takes) -- R itself where the tile has taken every call.  A skipping tile's partials are never read
+// and add nothing to the counters.
+__global__ __launch_bounds__(256) void gather_reduce_budget_kernel(GatherArgs a, int stencil_test, const int4 *tiles, const int4 *mask, float4 *snap, int32_t n1) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t n = (size_t)a.st.W * a.st.local_rows;
+    unsigned long long rays = 0ull, shaded = 0ull;
+    bool in_image = i < n, sums = false;
+    int nt = 0;
+    if (in_image) {
+        const int ly = (int)(i / a.st.W);
+        if (a.st.global_row(ly) >= a.st.H) in_image = false;
+        else {
+            const int t = (ly >> 3) * ((a.st.W + 7) >> 3) + ((int)(i - (size_t)ly * a.st.W) >> 3);
+            const bool takes = mask[t].y != 0;
+            nt = tiles[t].x + (takes ? 1 : 0);
+            sums = takes && !(stencil_test && a.g_pos[i].w == 0.0f);      // splatColor returns before writing (:354)
+        }
+    }
+    if (in_image) {
+        float4 R = snap[i];
+        if (sums) {
+#include "reduce_tree_body.hpp"
+            R = reduce_out(r, (float)a.fp.num_vpl_light_paths, (float)a.fp.do_accumulate, R);
+            snap[i] = R;
+        }
+        a.out[i] = nt > 0 ? extrapolate(R, n1, nt) : R;
     }
     __shared__ unsigned long long s_sum[2];
     if (threadIdx.x < 2) s_sum[threadIdx.x] = 0ull;
@@ -1011,6 +1058,18 @@ void launch_gather_reduce(const GatherArgs &a, int stencil_test, hipStream_t s, 
     size_t n = (size_t)a.st.W * a.st.local_rows;
     if (ad.tiles) hipLaunchKernelGGL(gather_reduce_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, stencil_test, ad);
     else hipLaunchKernelGGL(gather_reduce_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, stencil_test, ad);
+}
+void launch_gather_budget_mask(const int4 *tiles, int32_t ntiles, int32_t phase, int32_t window, int4 *mask, hipStream_t s) {
+    if (ntiles <= 0) return;
+    hipLaunchKernelGGL(gather_budget_mask_kernel, dim3((unsigned)((ntiles + 255) / 256)), dim3(256), 0, s, tiles, ntiles, phase, window, mask);
+}
+void launch_gather_budget_step(int4 *tiles, const int4 *mask, int32_t ntiles, hipStream_t s) {
+    if (ntiles <= 0) return;
+    hipLaunchKernelGGL(gather_budget_step_kernel, dim3((unsigned)((ntiles + 255) / 256)), dim3(256), 0, s, tiles, mask, ntiles);
+}
+void launch_gather_reduce_budget(const GatherArgs &a, int stencil_test, const int4 *tiles, const int4 *mask, float4 *snap, int32_t n1, hipStream_t s) {
+    const size_t n = (size_t)a.st.W * a.st.local_rows;
+    hipLaunchKernelGGL(gather_reduce_budget_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, stencil_test, tiles, mask, snap, n1);
 }
 static size_t fold_lds_bytes(const GatherArgs &a, int extra_floats) {
     int levels = 1; while ((1 << (levels - 1)) < a.splits_per_wave) levels++;       // log2 k + 1

@@ -436,7 +436,9 @@ int evplp_denoise(evplp_context *ctx, float scale, float light_scale, int32_t ma
  * improving, so its figure is an upper bound.
  * Refused with EVPLP_ERR_INVALID (the context stays usable): evplp_adaptive_enable with N > 0, or on = 1 without noise tracking; while it
  * is on: evplp_gather_lvc, evplp_path_trace, a gather with do_accumulate == 0, evplp_noise_track (off, or a restart) with N > 0.
- * A calibration frame (evplp_calibrate_blocks) gathers every tile; the reduce still writes retired pixels from their snapshots. */
+ * A calibration frame (evplp_calibrate_blocks) gathers every tile; the reduce still writes retired pixels from their snapshots.
+ * on: 0 = off (releases the memory), 1 = the retirement mode described here, 2 = gather budget mode (described below, after the path
+ * tracer's budget mode). */
 int evplp_adaptive_enable(evplp_context *ctx, int32_t on);
 /* Adaptive sampling for the path tracer ("render until every tile is at noise level x"): the same records, snapshot, pre-conditions and
  * memory as evplp_adaptive_enable (on = 0 releases), in path-trace mode: an accumulating evplp_path_trace honours retirement -- a retired
@@ -490,6 +492,32 @@ int evplp_adaptive_tiles(evplp_context *ctx, int32_t *iterations_per_image_tile,
  * evplp_adaptive_tiles returns n_t for every owned tile. */
 int evplp_adaptive_set_budgets(evplp_context *ctx, const int32_t *samples_per_image_tile, int32_t count);
 int evplp_adaptive_budgets(evplp_context *ctx, int32_t *samples_per_image_tile, int32_t capacity);
+/* Gather budget mode: evplp_adaptive_enable(ctx, 2).  Retirement (on = 1) freezes a tile for good, so every threshold has an error floor;
+ * here no tile stops improving and the noisy ones improve faster: a tile takes the first b_t of every S accumulating gather calls.  The
+ * records { n_t, K_t, B_t, b_t }, the raw sums R in the snapshot plane, evplp_adaptive_set_budgets / _budgets / _tiles / _tile_noise and
+ * evplp_plan_budgets (with samples = S) are those of the path tracer's budget mode above.  Point by point:
+ *  - Entering: the pre-conditions and the memory of on = 1 (noise tracking on, N = 0; + 16 B per tile for the per-call mask), and no
+ *    evplp_splat_photons since the last clear.  Every record starts as { 0, 0, 0, -1 } and R as the accumulator itself.
+ *  - The window: evplp_adaptive_budget_window(ctx, S), S in 1 .. 64, 16 after entering (the path tracer's tool uses that S; a default, not
+ *    a tuned number).  Gather budget mode only.
+ *  - Which calls a tile takes: m counts the accumulating gather calls since the last evplp_adaptive_set_budgets,
+ *    evplp_adaptive_budget_window, clear or evplp_set_blocks.  Tile t takes call m iff b_t < 0 || (m % S) < min(b_t, S).
+ *  - A call: evplp_gather_vpl or evplp_gather_vsl with do_accumulate = 1; N becomes N + 1.  A tile that takes it: every in-image pixel the
+ *    plain reduce would write (the plain call's stencil rule) gets R = (tree sum) / numVplLightPaths + R, the plain call's arithmetic, and
+ *    n_t += 1.  A tile that skips it: its items end at once, the cut kernel gives no slots to a group whose tiles all skip, and the
+ *    shadow-ray and pair counters get nothing from it.  Every in-image pixel of every tile:
+ *    EVPLP_BUF_VPL_ACCUM = (float)((double)R * ((double)N / (double)n_t)) per channel, each operation rounded to nearest, N the value after
+ *    the call.  A tile with n_t == N holds R itself; with budgets never set the mode equals a plain run in every bit.
+ *  - A tile's R equals, bit for bit, what a context with adaptivity off accumulates from exactly that tile's subsequence of iterations.
+ *  - Noise: the fold, the estimate, the variance image, the denoiser's variance and evplp_adaptive_tile_noise are those of the path
+ *    tracer's budget mode (per tile k_t = n_t - K_t; every tile priced as a retired one).
+ *  - evplp_adaptive_set_budgets (values 0 .. 64, refused with fewer than two folds or K != N), evplp_adaptive_budgets and
+ *    evplp_adaptive_tiles (n_t) serve the mode unchanged.
+ *  - Refused with EVPLP_ERR_INVALID, the context staying usable: evplp_splat_photons (the VPL part of a tile would have n_t samples and
+ *    its photon part N, and one set of moments cannot price both); evplp_gather_lvc, evplp_path_trace, evplp_path_trace_batch; a gather
+ *    with do_accumulate == 0; evplp_adaptive_retire (set the budget to 0 instead); a switch of the mode or of the tracker with N > 0.
+ *  - A calibration frame (evplp_calibrate_blocks) walks every tile, as under on = 1; the reduce still follows the schedule. */
+int evplp_adaptive_budget_window(evplp_context *ctx, int32_t window);
 /* The per-tile mean of rel exactly as evplp_adaptive_retire forms it (the same lanes, the same shuffle-down tree, divided by the count of
  * in-image pixels), written out instead of compared with a threshold: a tile evplp_adaptive_retire(.., tau, ..) would retire is one whose
  * figure here is <= tau, the same doubles.  All three adaptive modes; in modes 0 and 1 a tile retired earlier reports its frozen figure.
@@ -723,6 +751,9 @@ int evplp_group_adaptive_tiles(evplp_group *g, int32_t *iterations_per_image_til
  * accumulator equal one context's.  Argument errors are refused on the caller's thread and the group stays usable. */
 int evplp_group_adaptive_set_budgets(evplp_group *g, const int32_t *samples_per_image_tile, int32_t count);
 int evplp_group_adaptive_budgets(evplp_group *g, int32_t *samples_per_image_tile, int32_t capacity);
+/* Gather budget mode for a group: evplp_group_adaptive_enable(g, 2), the window for every rank; row strips only.  evplp_group_splat_photons,
+ * evplp_group_path_trace(_batch), a gather of kind 2 or without accumulation and evplp_group_adaptive_retire are refused in it. */
+int evplp_group_adaptive_budget_window(evplp_group *g, int32_t window);
 int evplp_group_adaptive_tile_noise(evplp_group *g, float scale, float light_scale, int32_t mask_emitter, double *rel_per_image_tile, int32_t capacity);
 
 /* ---- host side of the reference interface (no GPU needed for these) ---- */

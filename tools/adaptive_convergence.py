@@ -22,7 +22,13 @@ median and p10 - p90):
 --pair-calls N: nothing but N pairs evplp_primary + evplp_path_trace in path-trace mode with nothing retired (the same, for two checkouts).
 --samples-per-call 4,16: the per-sample time of evplp_path_trace_batch against the active fraction, beside the pair's; prints it and ends.
 --curve-batch S: the curves (not the reference) run S iterations per call through evplp_path_trace_batch; --no-tables: the curves only.
---budget: pt, budget mode (evplp_adaptive_enable_pt(.., 2)) against the plain batched run and binary retirement, one group per run, the
+--budget (photonfam): gather budget mode (evplp_adaptive_enable(.., 2)) against the plain run and binary retirement, one group per run, the
+  runs alternating iteration by iteration in this process; a fold every iteration; relMSE against the plain reference of --ref-iters.
+  Runs: plain; tileRelMse at each --taus value (retiring every --every iterations after --min-batches folds); budgets with window
+  --budget-window (16), minSamples 1, at each --budget-quantiles (1,0.9), planned every window iterations after --min-batches folds.  The
+  plain run goes --iters iterations, the others until they pass its final relMSE or 2 x --iters.  Then --calls calls each, alternating: a
+  budget-mode gather with every budget full against a plain gather (host wall time around a synchronised call, and the pass's own time).
+--technique pt --budget: budget mode (evplp_adaptive_enable_pt(.., 2)) against the plain batched run and binary retirement, one group per run, the
   runs alternating call by call in this process: S = --curve-batch (16) samples per call, a fold per call, a plan (or a retirement) every
   --every (16) iterations after --min-batches (4) folds; relMSE against a plain run of --ref-iters samples of other seeds.  Runs: plain;
   tileRelMse --budget-tau (0.005); budgets with minSamples 1 at each --budget-quantiles (1,0.95,0.9).  The plain run goes --iters
@@ -261,6 +267,83 @@ def budget_runs(groups, sd, iters, every, min_batches, S, tau, quantiles):
     return out, target
 
 
+def gather_budget_runs(groups, sd, total, iters, every, min_batches, taus, window, quantiles):
+    """--budget (photonfam): every run on its own group (reference already set), alternating one iteration at a time"""
+    runs = [{"name": "plain", "mode": None}] + [{"name": f"tileRelMse_{t:g}", "mode": "binary", "tau": t} for t in taus]
+    runs += [{"name": f"budget_q{q:g}", "mode": "budget", "q": q} for q in quantiles]
+    for r, g in zip(runs, groups):
+        g.clear_accumulators(); g.adaptive_enable(False); g.noise_track(True)
+        if r["mode"] == "binary":
+            g.adaptive_enable(True)
+        if r["mode"] == "budget":
+            g.adaptive_enable(True, gather_budget=True); g.adaptive_budget_window(window)
+        g.synchronize()
+        r.update(g=g, run=Runner(g, sd, total), wall=0.0, n=0, points=[], done=False, gms=[], calls=0)
+    ntiles = ((W + 7) // 8) * ((H + 7) // 8)
+    target = None
+    while not all(r["done"] for r in runs):
+        for r in runs:
+            if r["done"]:
+                continue
+            g = r["g"]
+            t0 = time.perf_counter()
+            r["run"].iteration(r["n"]); g.noise_fold(1)
+            r["n"] += 1
+            if r["mode"] == "binary" and r["n"] % every == 0:
+                g.adaptive_retire(1.0 / r["n"], r["tau"], min_batches)
+            if r["mode"] == "budget" and r["n"] % window == 0 and r["n"] >= min_batches:
+                b = ev.plan_budgets(g.adaptive_tile_noise(1.0 / r["n"]), g.adaptive_tiles(), window, 1, 0.0, r["q"])
+                g.adaptive_set_budgets(b); r["next"] = int(b.sum())
+            g.synchronize()
+            r["wall"] += (time.perf_counter() - t0) * 1e3
+            r["gms"].append(gather_ms(g))
+            if r["n"] % every == 0:
+                s = 1.0 / r["n"]
+                p = {"iteration": r["n"], "wall_ms": r["wall"], "rel_mse": g.frame_error(s, s, 1.0)[1], "gather_ms": statistics.median(r["gms"][-every:])}
+                if r["mode"] == "budget":
+                    p["tile_calls"] = int(g.adaptive_tiles().sum()); p["window_tile_calls"] = r.get("next", ntiles * window)
+                if r["mode"] == "binary":
+                    p["active_tiles"] = int((g.adaptive_tiles() == r["n"]).sum())
+                r["points"].append(p)
+            if r["name"] == "plain":
+                r["done"] = r["n"] >= iters
+                if r["done"]:
+                    target = r["points"][-1]["rel_mse"]
+            else:
+                r["done"] = r["n"] >= 2 * iters or (target is not None and r["n"] >= iters and r["points"] and r["points"][-1]["rel_mse"] <= target)
+    out = {}
+    for r in runs:
+        hit = None
+        for p0, p1 in zip([{"wall_ms": 0.0, "rel_mse": math.inf}] + r["points"], r["points"]):
+            if p1["rel_mse"] <= target:
+                t = 1.0 if not math.isfinite(p0["rel_mse"]) else (p0["rel_mse"] - target) / max(p0["rel_mse"] - p1["rel_mse"], 1e-300)
+                hit = p0["wall_ms"] + t * (p1["wall_ms"] - p0["wall_ms"]); break
+        out[r["name"]] = {"points": r["points"], "ms_to_plain_final_rel_mse": hit, "iterations": r["n"], "wall_ms": r["wall"],
+                          "best_rel_mse": min(p["rel_mse"] for p in r["points"])}
+    return out, target
+
+
+def gather_budget_costs(g, plain, sd, total, calls):
+    """--budget (photonfam): a budget-mode gather with every budget full against a plain gather, alternating call by call"""
+    runs = (Runner(g, sd, total), Runner(plain, sd, total))
+    g.clear_accumulators(); g.adaptive_enable(False); g.noise_track(True); g.adaptive_enable(True, gather_budget=True)
+    plain.clear_accumulators(); plain.adaptive_enable(False); plain.noise_track(True)
+    out = {"budget_full_call": {"wall": [], "pass": []}, "plain_call": {"wall": [], "pass": []}}
+    for k in range(calls + 2):
+        for name, grp, run in (("budget_full_call", g, runs[0]), ("plain_call", plain, runs[1])):
+            grp.synchronize(); t0 = time.perf_counter()
+            run.iteration(k); grp.synchronize()
+            t1 = time.perf_counter()
+            grp.noise_fold(1)
+            if k >= 2:
+                out[name]["wall"].append((t1 - t0) * 1e3); out[name]["pass"].append(gather_ms(grp))
+    same = g.resolve(1.0, 0.0, 0.0).tobytes() == plain.resolve(1.0, 0.0, 0.0).tobytes()
+    g.clear_accumulators(); g.adaptive_enable(False); plain.clear_accumulators()
+    res = {k: {"wall_ms": spread(v["wall"]), "gather_pass_ms": spread(v["pass"])} for k, v in out.items()}
+    res["accumulators_identical"] = same
+    return res
+
+
 def budget_costs(g, plain, sd, S, calls):
     """--budget: what the mode itself costs, alternating call by call: g in budget mode with every budget full, `plain` with adaptivity off"""
     runs = (PtRunner(g, sd), PtRunner(plain, sd))
@@ -316,13 +399,15 @@ def main():
                     "--min-batches then counts folds of S")
     ap.add_argument("--pair-calls", type=int, default=0, help="pt: nothing but N pairs primary + path_trace in path-trace mode, nothing retired (for two builds side by side)")
     ap.add_argument("--no-tables", action="store_true", help="pt: the curves only")
-    ap.add_argument("--budget", action="store_true", help="pt: budget mode against the plain batched run and binary retirement (see the module text)")
+    ap.add_argument("--budget", action="store_true", help="budget mode against the plain run and binary retirement: the gathers', or with --technique pt the path tracer's (see the module text)")
     ap.add_argument("--budget-tau", type=float, default=0.005)
-    ap.add_argument("--budget-quantiles", default="1,0.95,0.9")
+    ap.add_argument("--budget-quantiles", default="", help="default: 1,0.9 for the gathers, 1,0.95,0.9 for pt")
+    ap.add_argument("--budget-window", type=int, default=16, help="--budget (photonfam): the window S")
     ap.add_argument("--no-curves", action="store_true", help="--budget: the cost table only")
     a = ap.parse_args()
-    if a.budget:
-        a.technique = "pt"
+    if not a.budget_quantiles:
+        a.budget_quantiles = "1,0.95,0.9" if a.technique == "pt" else "1,0.9"
+    if a.budget and a.technique == "pt":
         if a.curve_batch == 1:
             a.curve_batch, a.every = 16, 16
     assert a.curve_batch >= 1 and a.every % a.curve_batch == 0 and a.iters % a.curve_batch == 0, "--curve-batch must divide --every and --iters"
@@ -345,6 +430,33 @@ def main():
                 return
             if a.pair_calls > 0:
                 print(json.dumps({"library": ev.LIB_PATH, "pair_of_calls": pair_calls(g, run, a.pair_calls)}))
+                return
+            if a.budget and not pt:
+                qs = [float(x) for x in a.budget_quantiles.split(",") if x]
+                taus = [float(x) for x in a.taus.split(",") if x]
+                res = {"library": ev.LIB_PATH, "shape": res["shape"], "tiles": tiles, "window": a.budget_window, "every": a.every, "min_batches": a.min_batches}
+                others = []
+                try:
+                    for _ in range(1 if a.no_curves else len(taus) + len(qs)):
+                        o = ev.Group(W, H, NL, NV, P, 1, devices=[0], overlap_light_tracing=True); o.load_scene_json(jp); others.append(o)
+                    if not a.no_curves:
+                        g.clear_accumulators()
+                        for i in range(a.ref_iters):
+                            run.iteration(i)
+                        s = 1.0 / a.ref_iters
+                        ref = np.ascontiguousarray(g.resolve(s, s, 1.0)[::-1]).astype(np.float32)
+                        for grp in [g] + others:
+                            grp.set_error_reference(ref)
+                        res["reference_iterations"] = a.ref_iters
+                        # (a plain run of iterations 0 .. ref_iters - 1, as the issue and DESIGN's earlier gather rows have it: every curve's
+                        # samples are among the reference's, unlike the pt branch below, whose reference has seeds of its own)
+                        res["reference_shares_samples_with_curves"] = True
+                        res["runs"], res["plain_final_rel_mse"] = gather_budget_runs([g] + others, sd, total, a.iters, a.every, a.min_batches, taus, a.budget_window, qs)
+                    res["costs"] = gather_budget_costs(g, others[0], sd, total, a.calls)
+                finally:
+                    for o in others:
+                        o.close()
+                print(json.dumps(res))
                 return
             if a.budget:
                 qs = [float(x) for x in a.budget_quantiles.split(",") if x]
