@@ -7,7 +7,7 @@ OUT = evplp_amd/lib
 HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-variable -Wno-unused-value -munsafe-fp-atomics -fno-slp-vectorize $(EXTRA_HIPFLAGS)
 HOSTFLAGS = -O2 -std=c++17 -fPIC -Wall -Wno-unused-value -ffp-contract=off
 
-HIP_SRCS = $(CSRC)/kernels_trace.hip $(CSRC)/kernels_gather.hip $(CSRC)/kernels_cut.hip $(CSRC)/kernels_splat.hip $(CSRC)/kernels_pt.hip $(CSRC)/kernels_ptbatch.hip $(CSRC)/kernels_ptbatch_primary.hip $(CSRC)/kernels_denoise.hip $(CSRC)/bvh_gpu.hip $(CSRC)/selftest.hip
+HIP_SRCS = $(CSRC)/kernels_trace.hip $(CSRC)/kernels_gather.hip $(CSRC)/kernels_cut.hip $(CSRC)/kernels_splat.hip $(CSRC)/kernels_pt.hip $(CSRC)/kernels_ptbatch.hip $(CSRC)/kernels_ptbatch_primary.hip $(CSRC)/kernels_stats.hip $(CSRC)/kernels_denoise.hip $(CSRC)/bvh_gpu.hip $(CSRC)/selftest.hip
 CPP_SRCS = $(CSRC)/context.cpp $(CSRC)/group.cpp $(CSRC)/bvh_build.cpp $(wildcard $(CSRC)/host/*.cpp)
 # VARIANT selects a separate object directory and library name (developer builds, e.g. `make stats`)
 VARIANT ?=
@@ -36,9 +36,11 @@ nan:
 # so G-buffers and light-path records can be compared bit for bit; the hot kernels keep contraction (radiance is toleranced)
 $(BUILD)/kernels_trace.o: HIPFLAGS += -ffp-contract=off $(TRACE_FLAGS)
 $(BUILD)/kernels_gather.o: HIPFLAGS += $(GATHER_FLAGS)
-# (the batched primary of evplp_path_trace_batch must give the G-buffer texels evplp_primary's bits: the same flag for the whole unit, which
-# holds budget mode's fold and tile-noise kernels too; the batched trace, in kernels_ptbatch.hip, keeps path_trace_kernel's flags)
+# (the batched primary of evplp_path_trace_batch must give the G-buffer texels evplp_primary's bits: the same flag for the whole unit;
+# the batched trace, in kernels_ptbatch.hip, keeps path_trace_kernel's flags)
 $(BUILD)/kernels_ptbatch_primary.o: HIPFLAGS += -ffp-contract=off
+# (frame error, noise and retirement statistics: tests restate every one of their operations in numpy)
+$(BUILD)/kernels_stats.o: HIPFLAGS += -ffp-contract=off
 # (the denoiser likewise: tests/test_gpu_denoise.py restates it in numpy in the same operation order)
 $(BUILD)/kernels_denoise.o: HIPFLAGS += -ffp-contract=off
 $(BUILD)/%.o: $(CSRC)/%.hip $(HDRS)

@@ -1224,13 +1224,15 @@ NoiseMoments noise_moments_of(const evplp_context *c) {
     const NoisePlanes m = noise_planes(c);
     return NoiseMoments{ m.q, nullptr, m.prev, m.start, m.stride };
 }
+// the records an estimate of the moments m reads: a context's own moments see its retired tiles; pooled shards (m.s) never have any
+static AdaptTiles noise_adapt_view(const evplp_context *c, const NoiseMoments &m, float scale) {
+    return (c->d_adapt_tiles && !m.s) ? adapt_view(c, scale) : AdaptTiles{};
+}
 size_t noise_bytes(const evplp_context *c) { return sizeof(double) * 3 * c->noise_stride + sizeof(float4) * 2 * (size_t)c->st.W * c->st.local_rows; }
 int noise_rows(evplp_context *c, const NoiseMoments &m, const float4 *light, double K, double B, float scale, float ls, int32_t mask_emitter) {
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     const double s2K = (double)scale * (double)scale * K;
-    if (c->d_adapt_tiles && !m.s)      // (a context's own moments with retired tiles; pooled shards never have any)
-        launch_noise_rows_adaptive(c->st, m, K, B, s2K, light, ls, mask_emitter, c->d_rgb, c->d_noise_keep, c->d_noise_rows, adapt_view(c, scale), c->stream);
-    else launch_noise_rows(c->st, m, K, B, s2K, light, ls, mask_emitter, c->d_rgb, c->d_noise_keep, c->d_noise_rows, c->stream);
+    launch_noise_rows(c->st, m, K, B, s2K, light, ls, mask_emitter, c->d_rgb, c->d_noise_keep, c->d_noise_rows, noise_adapt_view(c, m, scale), c->stream);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(c->noise_rows.data(), c->d_noise_rows, sizeof(RowError) * (size_t)c->st.local_rows, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1238,8 +1240,7 @@ int noise_rows(evplp_context *c, const NoiseMoments &m, const float4 *light, dou
 }
 int noise_variance_to_device(evplp_context *c, const NoiseMoments &m, double K, double B, float scale) {
     HIP_TRY(c, hipSetDevice(c->cfg.device));
-    if (c->d_adapt_tiles && !m.s) launch_noise_variance_adaptive(c->st, m, K, B, (double)scale * (double)scale * K, c->d_rgb, adapt_view(c, scale), c->stream);
-    else launch_noise_variance(m, K, B, (double)scale * (double)scale * K, (size_t)c->st.W * c->st.local_rows, c->d_rgb, c->stream);
+    launch_noise_variance(c->st, m, K, B, (double)scale * (double)scale * K, c->d_rgb, noise_adapt_view(c, m, scale), c->stream);
     HIP_TRY(c, hipGetLastError());
     return EVPLP_OK;
 }
@@ -1248,7 +1249,7 @@ int noise_variance_to_device(evplp_context *c, const NoiseMoments &m, double K, 
 static int noise_restart(evplp_context *c) {
     c->noise_k = c->noise_b = 0;
     launch_noise_fold(evplp::noise_planes(c), (const float4 *)c->buf[EVPLP_BUF_VPL_ACCUM], (const float4 *)c->buf[EVPLP_BUF_PHOTON_ACCUM],
-                      (size_t)c->st.W * c->st.local_rows, 0, c->stream);
+                      c->st, evplp::adapt_view(c, 1.0f), 0, c->stream);
     HIP_TRY(c, hipGetLastError());
     return EVPLP_OK;
 }
@@ -1292,11 +1293,9 @@ extern "C" int evplp_noise_fold(evplp_context *c, int32_t iterations) {
     if (c->adapt_budget) {         // (per tile, k_t = n_t - K_t; the host copy of the records follows)
         launch_noise_fold_budget(evplp::noise_planes(c), c->st, c->d_adapt_tiles, c->d_adapt_snap, c->tiles_x * c->tiles_y, c->stream);
         for (int4 &r : c->adapt_tiles) if (r.x != r.y) { r.y = r.x; r.z += 1; }
-    } else if (c->d_adapt_tiles)          // (retired pixels keep their Q and c_prev)
-        launch_noise_fold_adaptive(evplp::noise_planes(c), (const float4 *)c->buf[EVPLP_BUF_VPL_ACCUM], (const float4 *)c->buf[EVPLP_BUF_PHOTON_ACCUM],
-                                   c->st, evplp::adapt_view(c, 1.0f), iterations, c->stream);
-    else launch_noise_fold(evplp::noise_planes(c), (const float4 *)c->buf[EVPLP_BUF_VPL_ACCUM], (const float4 *)c->buf[EVPLP_BUF_PHOTON_ACCUM],
-                           (size_t)c->st.W * c->st.local_rows, iterations, c->stream);
+    } else          // (with adaptivity on, retired pixels keep their Q and c_prev)
+        launch_noise_fold(evplp::noise_planes(c), (const float4 *)c->buf[EVPLP_BUF_VPL_ACCUM], (const float4 *)c->buf[EVPLP_BUF_PHOTON_ACCUM],
+                          c->st, evplp::adapt_view(c, 1.0f), iterations, c->stream);
     HIP_TRY(c, hipGetLastError());
     c->noise_k += iterations; c->noise_b += 1;
     return EVPLP_OK;

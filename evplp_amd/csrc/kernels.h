@@ -286,7 +286,7 @@ void launch_assemble_strips(const StripDev &st, int nranks, const uint32_t *owne
 struct ShardPlanes { const float4 *p[64]; };
 void launch_reduce_shards(const ShardPlanes &src, int n, int first_nonzero, size_t count, float4 *out, int num_cus, hipStream_t s);
 void launch_fill_zero(void *p, size_t bytes, hipStream_t s);
-// evplp_frame_error: one image row's figures against the reference (frame_error_kernel, kernels_trace.hip); kept = pixels the mask keeps
+// evplp_frame_error: one image row's figures against the reference (frame_error_kernel, kernels_stats.hip); kept = pixels the mask keeps
 struct RowError { double num, rel, rel_kept, kept; };
 static_assert(sizeof(RowError) == 32, "RowError must be 32 bytes");
 // rgb: the composite (local rows, y = 0 at the bottom); ref: [H][W][3] and keep: [H][W] (null = every pixel), both rows top to bottom;
@@ -298,25 +298,22 @@ struct NoisePlanes { double *q; float4 *prev, *start; size_t stride; };
 // the moments an estimate reads: one context's (s = null: S = c_prev - c_start, per channel in fp32) or the shards' pooled ones (q and s
 // [3][stride] fp64, summed in rank order)
 struct NoiseMoments { const double *q, *s; const float4 *prev, *start; size_t stride; };
-// k = 0: c_prev = c_start = c, Q = 0 (tracking starts); k >= 1: a batch of k iterations closes (noise_fold_kernel, kernels_trace.hip)
-void launch_noise_fold(const NoisePlanes &m, const float4 *vpl, const float4 *pm, size_t n, int32_t k, hipStream_t s);
 // out q / s [3][stride]: first ? src : out + src (one shard of the pooling, every add rounded)
 void launch_noise_pool(const NoiseMoments &src, bool first, double *q, double *s_out, size_t n, hipStream_t s);
-// per local row: { sum num, sum rel, sum rel over kept pixels, kept pixels } of the variance against the composite rgb (layout as frame_error)
-void launch_noise_rows(const StripDev &st, const NoiseMoments &m, double K, double B, double s2K, const float4 *light, float ls, int mask_emitter,
-                       const float *rgb, const uint8_t *keep, RowError *rows, hipStream_t s);
-// the variance of every plane pixel, 3 floats each (resolve's layout)
-void launch_noise_variance(const NoiseMoments &m, double K, double B, double s2K, size_t n, float *out_rgb, hipStream_t s);
 // evplp_adaptive_*: one record per 8 x 8 tile of a context's planes, tile (tx, ty) of local rows 8 ty .. 8 ty + 7 at ty * tiles_x + tx:
 // int4 { n_t (0: active; the N at retirement), K_t, B_t (the noise tracker's K and B at retirement), 0 }.  tiles = null: adaptivity is off
 // and the noise kernels take their default paths.  n = N, scale: the composite's, both for the retired pixels' frozen variance.
 struct AdaptTiles { const int4 *tiles; int32_t tiles_x, pad; double n, scale; };
-// the noise kernels' variants with retired tiles (at.tiles != null): the fold leaves a retired pixel's Q and c_prev as they are; the
-// figures and the variance image take a retired pixel's variance as noise_var(Q, S, K_t, B_t - 1, (scale N / n_t)^2 K_t)
-void launch_noise_fold_adaptive(const NoisePlanes &m, const float4 *vpl, const float4 *pm, const StripDev &st, const AdaptTiles &at, int32_t k, hipStream_t s);
-void launch_noise_rows_adaptive(const StripDev &st, const NoiseMoments &m, double K, double B, double s2K, const float4 *light, float ls, int mask_emitter,
-                                const float *rgb, const uint8_t *keep, RowError *rows, const AdaptTiles &at, hipStream_t s);
-void launch_noise_variance_adaptive(const StripDev &st, const NoiseMoments &m, double K, double B, double s2K, float *out_rgb, const AdaptTiles &at, hipStream_t s);
+// the noise launchers (at.tiles == null: the plain kernels; otherwise the variants with retired tiles): the fold leaves a retired pixel's Q
+// and c_prev as they are (k = 0 starts tracking whatever at says); the figures and the variance image take a retired pixel's variance as
+// noise_var(Q, S, K_t, B_t - 1, (scale N / n_t)^2 K_t)
+// fold, k = 0: c_prev = c_start = c, Q = 0 (tracking starts); k >= 1: a batch of k iterations closes (noise_fold_kernel, kernels_stats.hip)
+void launch_noise_fold(const NoisePlanes &m, const float4 *vpl, const float4 *pm, const StripDev &st, const AdaptTiles &at, int32_t k, hipStream_t s);
+// rows, per local row: { sum num, sum rel, sum rel over kept pixels, kept pixels } of the variance against the composite rgb (layout as frame_error)
+void launch_noise_rows(const StripDev &st, const NoiseMoments &m, double K, double B, double s2K, const float4 *light, float ls, int mask_emitter,
+                       const float *rgb, const uint8_t *keep, RowError *rows, const AdaptTiles &at, hipStream_t s);
+// the variance of every plane pixel, 3 floats each (resolve's layout)
+void launch_noise_variance(const StripDev &st, const NoiseMoments &m, double K, double B, double s2K, float *out_rgb, const AdaptTiles &at, hipStream_t s);
 // evplp_adaptive_retire: every active tile whose mean relative variance over its in-image pixels (noise_rows_kernel's rel, fp64, summed in a
 // fixed tree over the tile's 64 lanes) is <= tau gets the record { n, K, B, 0 } and the snapshot snap = vpl of its pixels
 void launch_adaptive_retire(const StripDev &st, const NoiseMoments &m, double K, double B, double s2K, const float4 *light, float ls, int mask_emitter,

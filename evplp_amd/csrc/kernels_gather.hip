@@ -440,6 +440,40 @@ __global__ __launch_bounds__(64, EVPLP_GATHER_WAVES) void gather_vpl_kernel(Gath
 EV_DEV float4 reduce_out(V3 r, float inv, float acc, float4 old) {
     return make_float4(r.x / inv + acc * old.x, r.y / inv + acc * old.y, r.z / inv + acc * old.z, 0.0f + acc * old.w);
 }
+// the 8 x 8 tile (of the context's planes) that holds plane pixel i of local row ly
+EV_DEV int pixel_tile(const StripDev &st, int ly, size_t i) { return (ly >> 3) * ((st.W + 7) >> 3) + ((int)(i - (size_t)ly * st.W) >> 3); }
+// The balanced-tree sum of pixel i's per-group partials: one function, so that every reduce sums in one order.  The items' statistics (the
+// partials' fourth component) are added to rays and shaded.
+EV_DEV V3 reduce_tree(const GatherArgs &a, size_t i, unsigned long long &rays, unsigned long long &shaded) {
+    const int groups = kVplSplit / a.splits_per_wave;
+    V3 r = v3(0.f, 0.f, 0.f), lv0 = r, lv1 = r, lv2 = r, lv3 = r, lv4 = r, lv5 = r, lv6 = r;
+    for (int g = 0; g < groups; g++) {
+        float4 q = a.partial[(size_t)g * a.partial_stride + i];
+        const uint32_t st = __float_as_uint(q.w);
+        rays += st & 0xffffu; shaded += st >> 16;
+        r = v3(q.x, q.y, q.z);
+        // binary counter over g (level j holds the sum of 2^j consecutive partials): merge while the low bits of g are ones
+#define EV_MERGE(L, NEXT) if (((g >> L) & 1) == 0) lv##L = r; else { r = lv##L + r; NEXT }
+        EV_MERGE(0, EV_MERGE(1, EV_MERGE(2, EV_MERGE(3, EV_MERGE(4, EV_MERGE(5, EV_MERGE(6, ;)))))))
+#undef EV_MERGE
+    }
+    return r;
+}
+// The workgroup's shadow-ray / unoccluded-pair counts into its counter shard: a wave shuffle, two LDS adds per wave, two global adds per
+// workgroup.  Every thread of the workgroup calls it (it synchronises): no early return in front of it.
+EV_DEV void reduce_counters(const GatherArgs &a, unsigned long long rays, unsigned long long shaded) {
+    __shared__ unsigned long long s_sum[2];
+    if (threadIdx.x < 2) s_sum[threadIdx.x] = 0ull;
+    __syncthreads();
+    for (int off = 32; off > 0; off >>= 1) { rays += __shfl_down(rays, off); shaded += __shfl_down(shaded, off); }
+    if ((threadIdx.x & 63) == 0) { atomicAdd(&s_sum[0], rays); atomicAdd(&s_sum[1], shaded); }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int shard = blockIdx.x & (kCounterShards - 1);
+        atomicAdd(&a.counters->shard_rays[shard], s_sum[0]);
+        atomicAdd(&a.counters->shard_shaded[shard], s_sum[1]);
+    }
+}
 // ADAPT (evplp_adaptive_retire): every in-image pixel of a retired tile -- whatever the stencil says -- becomes its snapshot R extrapolated
 // to N + 1 iterations, (float)(R * ((N + 1) / n_t)) per channel in fp64, and adds nothing to the counters; active pixels as above
 template <bool ADAPT = false>
@@ -453,27 +487,17 @@ __global__ __launch_bounds__(256) void gather_reduce_kernel(GatherArgs a, int st
         const int ly = (int)(i / a.st.W);
         if (a.st.global_row(ly) >= a.st.H) writes = false;
         else {
-            if constexpr (ADAPT) nt = ad.tiles[(ly >> 3) * ((a.st.W + 7) >> 3) + ((int)(i - (size_t)ly * a.st.W) >> 3)].x;
+            if constexpr (ADAPT) nt = ad.tiles[pixel_tile(a.st, ly, i)].x;
             if (nt == 0 && stencil_test && a.g_pos[i].w == 0.0f) writes = false;      // splatColor returns before writing (:354)
         }
     }
     if (ADAPT && writes && nt != 0) {
         a.out[i] = extrapolate(ad.snap[i], ad.n1, nt);
     } else if (writes) {
-#include "reduce_tree_body.hpp"
+        const V3 r = reduce_tree(a, i, rays, shaded);
         a.out[i] = reduce_out(r, (float)a.fp.num_vpl_light_paths, (float)a.fp.do_accumulate, a.out[i]);
     }
-    __shared__ unsigned long long s_sum[2];
-    if (threadIdx.x < 2) s_sum[threadIdx.x] = 0ull;
-    __syncthreads();
-    for (int off = 32; off > 0; off >>= 1) { rays += __shfl_down(rays, off); shaded += __shfl_down(shaded, off); }
-    if ((threadIdx.x & 63) == 0) { atomicAdd(&s_sum[0], rays); atomicAdd(&s_sum[1], shaded); }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int shard = blockIdx.x & (kCounterShards - 1);
-        atomicAdd(&a.counters->shard_rays[shard], s_sum[0]);
-        atomicAdd(&a.counters->shard_shaded[shard], s_sum[1]);
-    }
+    reduce_counters(a, rays, shaded);
 }
 
 // Gather budget mode (evplp_adaptive_enable(ctx, 2); kernels.h gather_tile_takes).  One thread per tile: the per-call view of the records that
@@ -506,7 +530,7 @@ __global__ __launch_bounds__(256) void gather_reduce_budget_kernel(GatherArgs a,
         const int ly = (int)(i / a.st.W);
         if (a.st.global_row(ly) >= a.st.H) in_image = false;
         else {
-            const int t = (ly >> 3) * ((a.st.W + 7) >> 3) + ((int)(i - (size_t)ly * a.st.W) >> 3);
+            const int t = pixel_tile(a.st, ly, i);
             const bool takes = mask[t].y != 0;
             nt = tiles[t].x + (takes ? 1 : 0);
             sums = takes && !(stencil_test && a.g_pos[i].w == 0.0f);      // splatColor returns before writing (:354)
@@ -515,23 +539,13 @@ __global__ __launch_bounds__(256) void gather_reduce_budget_kernel(GatherArgs a,
     if (in_image) {
         float4 R = snap[i];
         if (sums) {
-#include "reduce_tree_body.hpp"
+            const V3 r = reduce_tree(a, i, rays, shaded);
             R = reduce_out(r, (float)a.fp.num_vpl_light_paths, (float)a.fp.do_accumulate, R);
             snap[i] = R;
         }
         a.out[i] = nt > 0 ? extrapolate(R, n1, nt) : R;
     }
-    __shared__ unsigned long long s_sum[2];
-    if (threadIdx.x < 2) s_sum[threadIdx.x] = 0ull;
-    __syncthreads();
-    for (int off = 32; off > 0; off >>= 1) { rays += __shfl_down(rays, off); shaded += __shfl_down(shaded, off); }
-    if ((threadIdx.x & 63) == 0) { atomicAdd(&s_sum[0], rays); atomicAdd(&s_sum[1], shaded); }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int shard = blockIdx.x & (kCounterShards - 1);
-        atomicAdd(&a.counters->shard_rays[shard], s_sum[0]);
-        atomicAdd(&a.counters->shard_shaded[shard], s_sum[1]);
-    }
+    reduce_counters(a, rays, shaded);
 }
 
 // ------------------------------------------------------------------- light-subpath windows

@@ -16,7 +16,7 @@ from test_kernel_resources import HIPCC, kernel_table
      {"gather_vpl_kernelILb1ELb0ELb1E": 64, "gather_vpl_kernelILb0ELb0ELb1E": 64, "gather_vsl_walk_kernelILb1ELb0ELb1E": 64,
       "gather_vsl_walk_kernelILb0ELb0ELb1E": 64, "gather_vsl_shade_kernelILb0ELb1E": 128}),
     ("kernels_cut.hip", ["gather_cut_kernelILb1E"], {"gather_cut_kernelILb1E": 64}),
-    ("kernels_trace.hip", ["noise_fold_frozen_kernel", "noise_rows_frozen_kernel", "noise_variance_frozen_kernel", "adaptive_retire_kernel"], {}),
+    ("kernels_stats.hip", ["noise_fold_frozen_kernel", "noise_rows_frozen_kernel", "noise_variance_frozen_kernel", "adaptive_retire_kernel"], {}),
 ])
 def test_adaptive_variants_keep_their_budgets(src, kinds, budgets):
     table = kernel_table(src)

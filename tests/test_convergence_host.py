@@ -5,32 +5,15 @@ import ctypes as C
 import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from test_kernel_resources import HIPCC, kernel_table
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-fno-slp-vectorize", "-S", "--cuda-device-only", "-w"]
 W, H = 96, 64
 NEW = ("evplp_set_error_reference", "evplp_frame_error", "evplp_group_set_error_reference", "evplp_group_frame_error")
-
-
-def kernel_table(src):
-    extra = ["-ffp-contract=off"] if src == "kernels_trace.hip" else []      # (as the Makefile builds it)
-    out = subprocess.run([HIPCC] + FLAGS + extra + ["-o", "-", os.path.join(ROOT, "evplp_amd", "csrc", src)], capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    table, cur = {}, {}
-    for line in out.stdout.splitlines():
-        m = re.match(r"\s+\.(name|private_segment_fixed_size|vgpr_count|vgpr_spill_count|sgpr_spill_count|group_segment_fixed_size):\s+(\S+)", line)
-        if not m:
-            continue
-        cur[m.group(1)] = m.group(2)
-        if m.group(1) == "vgpr_spill_count":      # the last of the fields of one kernel's metadata block
-            table[cur.get("name", "?")] = {k: int(v) for k, v in cur.items() if k != "name"}
-            cur = {}
-    return table
 
 
 def _render(evplp, path, overrides=None):
@@ -57,7 +40,7 @@ def test_new_entry_points_are_exported_bound_and_refuse_null_handles(evplp):
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_frame_error_kernel_has_no_scratch_and_no_spills():
-    table = kernel_table("kernels_trace.hip")
+    table = kernel_table("kernels_stats.hip")
     hits = [k for k in table if "frame_error_kernel" in k]
     assert len(hits) == 1, sorted(table)
     t = table[hits[0]]

@@ -1,6 +1,7 @@
 """No GPU needed: the code objects of gather budget mode (evplp_adaptive_enable(ctx, 2)).  Its three kernels live in kernels_gather.hip -- the
-per-call mask, the mode's reduce and the n_t step -- and are held to zero scratch and no spills; the reduce shares the balanced tree with
-gather_reduce_kernel as text (reduce_tree_body.hpp), so the existing reduce kernels stay two and keep their names."""
+per-call mask, the mode's reduce and the n_t step -- and are held to zero scratch and no spills; the reduce shares the balanced tree
+(reduce_tree) and the counter shards (reduce_counters) with gather_reduce_kernel as functions, so the existing reduce kernels stay two and
+keep their names."""
 import os
 import re
 
@@ -36,13 +37,22 @@ def test_the_existing_gather_kernels_are_the_ones_they_were(table):
         ["_ZN5evplp20gather_reduce_kernelILb0EEEvNS_10GatherArgsEiNS_9AdaptArgsE", "_ZN5evplp20gather_reduce_kernelILb1EEEvNS_10GatherArgsEiNS_9AdaptArgsE"])
 
 
-def test_the_tree_is_shared_as_text_and_nothing_new_is_atomic():
-    src = open(os.path.join(ROOT, "evplp_amd", "csrc", "kernels_gather.hip")).read()
-    assert src.count('#include "reduce_tree_body.hpp"') == 2              # gather_reduce_kernel and gather_reduce_budget_kernel
-    assert "EV_MERGE" not in src                                          # the tree's text lives in one place
-    body = src[src.index("void gather_reduce_budget_kernel("):src.index("light-subpath windows")]
+def function_text(src, head):
+    """the text of the function whose definition starts with `head`, up to its closing brace in column 0"""
+    k = src[src.index(head):]
+    return k[:k.index("\n}\n")]
+
+
+def test_the_tree_and_the_counters_are_shared_functions_and_nothing_new_is_atomic():
+    csrc = os.path.join(ROOT, "evplp_amd", "csrc")
+    assert not os.path.exists(os.path.join(csrc, "reduce_tree_body.hpp"))
+    src = open(os.path.join(csrc, "kernels_gather.hip")).read()
+    assert src.count("#define EV_MERGE") == 1                             # the tree's text lives in one place
     # the reduce's existing counter shards and nothing else: two LDS adds per wave, two global adds per workgroup
-    assert len(re.findall(r"\batomic\w*\(", body)) == 4
+    assert len(re.findall(r"\batomic\w*\(", function_text(src, "EV_DEV void reduce_counters("))) == 4
+    for n in ("void gather_reduce_kernel(", "void gather_reduce_budget_kernel("):
+        k = function_text(src, n)
+        assert k.count("reduce_tree(") == 1 and k.count("reduce_counters(") == 1, n
+        assert "atomic" not in k, n
     for n in ("gather_budget_mask_kernel", "gather_budget_step_kernel"):
-        k = src[src.index("void " + n + "("):]
-        assert "atomic" not in k[:k.index("\n}\n")], n
+        assert "atomic" not in function_text(src, "void " + n + "("), n

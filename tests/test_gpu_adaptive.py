@@ -103,8 +103,20 @@ def pick_tau(means):
     raise AssertionError("no gap between the tile means")
 
 
-def tile_mask(retired):
-    return np.kron(retired, np.ones((8, 8), bool))[:H, :W]
+def tile_mask(retired, w=W, h=H):
+    return np.kron(retired, np.ones((8, 8), bool))[:h, :w]
+
+
+def frozen_figures(cs, retire_at, iters, pm, active_var, composite, light):
+    """numpy's restatement of tiles retired after `retire_at` of `iters` iterations (cs[j]: the plain run's sums after j iterations, one fold
+    per iteration up to the retirement), at the 1 / iters scale, for any frame shape: the frozen variance of every pixel as if its tile had
+    retired, and the three figures of the variance image that is frozen where pm (h, w) says so and active_var elsewhere"""
+    s = np.float64(np.float32(1.0 / iters))
+    v_t, K_t = moments(cs[:retire_at + 1])
+    f = (s * np.float64(iters)) / np.float64(retire_at)
+    frozen = variance(v_t, (f * f) * K_t)
+    num, rel = rel_of(np.where(pm[..., None], frozen, active_var), composite, light)
+    return frozen, (num.sum() / num.size, rel.sum() / num.size, rel.sum() / num.size)
 
 
 def run(evplp, jp, sd, tau=None, vsl=False, runner=None, dealt=False):
@@ -198,18 +210,14 @@ def test_frozen_noise_of_retired_pixels(plain_and_adaptive):
     retired = means <= tau
     pm = tile_mask(retired)
     s = np.float64(np.float32(1.0 / ITERS))
-    v_t, K_t = moments(plain["cs"][:RETIRE_AT + 1])
-    f = (s * np.float64(ITERS)) / np.float64(RETIRE_AT)
-    frozen = variance(v_t, (f * f) * K_t)
+    v, K = moments(plain["cs"])
+    # frozen figures for retired pixels, the tracker's for active ones
+    frozen, want = frozen_figures(plain["cs"], RETIRE_AT, ITERS, pm, variance(v, s * s * K), ad["composite"], plain["light"])
     assert ad["var"][pm].tobytes() == frozen.astype(np.float32)[pm].tobytes()
     assert ad["var"][~pm].tobytes() == plain["var"][~pm].tobytes()        # active pixels as the plain run
     # the retired figure stays put as the run goes on (1 / N scale: the figure at retirement)
     np.testing.assert_allclose(ad["var_8"][pm], ad["var"][pm], rtol=1e-5, atol=0)
-    # the estimate against numpy: frozen figures for retired pixels, the tracker's for active ones
-    v, K = moments(plain["cs"])
-    var = np.where(pm[..., None], frozen, variance(v, s * s * K))
-    num, rel = rel_of(var, ad["composite"], plain["light"])
-    want = (num.sum() / num.size, rel.sum() / num.size, rel.sum() / num.size)
+    # the estimate against numpy
     for g, w in zip(ad["est"], want):
         assert abs(g - w) <= 1e-12 * max(abs(w), 1e-30), (ad["est"], want)
 

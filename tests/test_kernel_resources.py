@@ -12,8 +12,14 @@ HIPCC = "/opt/rocm/bin/hipcc"
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-fno-slp-vectorize", "-S", "--cuda-device-only", "-w"]
 
 
+def uncontracted_units():
+    """the units the Makefile builds with -ffp-contract=off: its `$(BUILD)/X.o: HIPFLAGS += -ffp-contract=off ...` lines"""
+    mk = open(os.path.join(ROOT, "Makefile")).read()
+    return [x + ".hip" for x in re.findall(r"^\$\(BUILD\)/(\w+)\.o: HIPFLAGS \+= -ffp-contract=off\b", mk, re.M)]
+
+
 def kernel_table(src):
-    extra = ["-ffp-contract=off"] if src == "kernels_trace.hip" else []      # (as the Makefile builds it)
+    extra = ["-ffp-contract=off"] if src in uncontracted_units() else []      # (as the Makefile builds it)
     out = subprocess.run([HIPCC] + FLAGS + extra + ["-o", "-", os.path.join(ROOT, "evplp_amd", "csrc", src)], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     table, cur = {}, {}

@@ -9,7 +9,7 @@ import re
 import numpy as np
 import pytest
 
-from test_convergence_host import HIPCC, kernel_table
+from test_kernel_resources import HIPCC, kernel_table
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, H = 96, 64
@@ -43,7 +43,7 @@ def test_new_entry_points_are_exported_bound_and_refuse_null_handles(evplp):
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_noise_kernels_have_no_scratch_and_no_spills():
-    table = kernel_table("kernels_trace.hip")
+    table = kernel_table("kernels_stats.hip")
     hits = {k: v for k, v in table.items() if "noise_" in k}
     for kind in ("noise_fold_kernelILb0", "noise_fold_kernelILb1", "noise_pool_kernel", "noise_rows_kernel", "noise_variance_kernel"):
         assert sum(kind in k for k in hits) == 1, (kind, sorted(hits))
