@@ -172,8 +172,9 @@ struct Builder {
             }
         }
         // leaf if cheaper and it fits.  Cost model in units of one triangle test: a node visit of the packet walk costs
-        // sah_ct of them (20 vector + 27 scalar instructions and a dependent 64-byte fetch against ~25 vector instructions per
-        // triangle with the plane-distance pre-test)
+        // sah_ct of them (15 vector + 9-12 scalar instructions and a dependent 64-byte fetch against 20 vector instructions per
+        // triangle -- 40 and 6 scalar per pair, device_common.hpp EV_PAIR_TEXT -- plus ~12 scalar instructions and a dependent
+        // 128-byte fetch per leaf)
         if (count <= kMaxLeafTris) {
             float leaf_cost = (float)count * bb.area();
             if (best_axis < 0 || best_cost + sah_ct * bb.area() >= leaf_cost) return make_leaf(first, count);

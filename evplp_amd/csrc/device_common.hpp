@@ -544,57 +544,231 @@ struct WalkStats { uint32_t nodes, leaves, pairs, exact; int32_t hit_leaf; uint3
 #define EV_WALK_VISIT_ASM(T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H) EV_WALK_VISIT_ASM_("s", T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H)
 // NC: where the node's six box operands live -- "s" (a node fetched with s_load) or "v" (a synthetic node of an entry cut, read from LDS
 // with one address for all lanes: the same value in every lane of a VGPR serves as well)
+#define EV_VISIT_TEXT(CX, CY, CZ, HX, HY, HZ, C0, C1, M1, T64, P0, P1, T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H) \
+        "v_pk_fma_f32 " T0 ", " CX ", %[pa], %[pd] op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\t" \
+        "v_pk_fma_f32 " T1 ", " CY ", %[pa], %[pd] op_sel:[0,1,1] op_sel_hi:[1,1,1]\n\t" \
+        "v_pk_fma_f32 " T2 ", " CZ ", %[pb], %[pe] op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\t" \
+        "v_pk_fma_f32 " T3 ", " HX ", %[pb], " T0 " op_sel:[0,1,0] op_sel_hi:[1,1,1] neg_lo:[0,1,0] neg_hi:[0,1,0]\n\t" \
+        "v_pk_fma_f32 " T4 ", " HY ", %[pc], " T1 " op_sel:[0,0,0] op_sel_hi:[1,0,1] neg_lo:[0,1,0] neg_hi:[0,1,0]\n\t" \
+        "v_pk_fma_f32 " T5 ", " HZ ", %[pc], " T2 " op_sel:[0,1,0] op_sel_hi:[1,1,1] neg_lo:[0,1,0] neg_hi:[0,1,0]\n\t" \
+        "v_pk_fma_f32 " T0 ", " HX ", %[pb], " T0 " op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t" \
+        "v_pk_fma_f32 " T1 ", " HY ", %[pc], " T1 " op_sel:[0,0,0] op_sel_hi:[1,0,1]\n\t" \
+        "v_pk_fma_f32 " T2 ", " HZ ", %[pc], " T2 " op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t" \
+        "v_max3_f32 " T3L ", " T3L ", " T4L ", " T5L " clamp\n\t" \
+        "v_min3_f32 " T0L ", " T0L ", " T1L ", " T2L " clamp\n\t" \
+        "v_max3_f32 " T3H ", " T3H ", " T4H ", " T5H " clamp\n\t" \
+        "v_min3_f32 " T0H ", " T0H ", " T1H ", " T2H " clamp\n\t" \
+        "v_cmp_lt_f32 vcc, " T3L ", " T0L "\n\t" \
+        "v_cmp_lt_f32 " M1 ", " T3H ", " T0H "\n\t" \
+        "s_or_b64 " T64 ", vcc, " M1 "\n\t" \
+        "s_cbranch_scc0 L_pop%=\n\t" \
+        "s_cmp_eq_u64 vcc, 0\n\t" \
+        "s_cbranch_scc1 L_c1%=\n\t" \
+        "s_cmp_eq_u64 " M1 ", 0\n\t" \
+        "s_cbranch_scc1 L_c0%=\n\t" \
+        "s_bcnt1_i32_b64 " P0 ", vcc\n\t" \
+        "s_bcnt1_i32_b64 " P1 ", " M1 "\n\t" \
+        "s_cmp_ge_i32 " P0 ", " P1 "\n\t" \
+        "s_cselect_b32 " P0 ", " C1 ", " C0 "\n\t" \
+        "s_cselect_b32 %[cur], " C0 ", " C1 "\n\t" \
+        "s_mov_b32 m0, %[sp]\n\t" \
+        "s_add_i32 %[sp], %[sp], 1\n\t" \
+        "v_writelane_b32 %[vstack], " P0 ", m0\n\t" \
+        "s_branch L_end%=\n" \
+        "L_c0%=:\n\t" \
+        "s_mov_b32 %[cur], " C0 "\n\t" \
+        "s_branch L_end%=\n" \
+        "L_c1%=:\n\t" \
+        "s_mov_b32 %[cur], " C1 "\n\t" \
+        "s_branch L_end%=\n" \
+        "L_pop%=:\n\t" \
+        "s_brev_b32 %[cur], 1\n\t" \
+        "s_cmp_eq_u32 %[sp], 0\n\t" \
+        "s_cbranch_scc1 L_end%=\n\t" \
+        "s_sub_i32 %[sp], %[sp], 1\n\t" \
+        "s_nop 0\n\t" \
+        "v_readlane_b32 %[cur], %[vstack], %[sp]\n" \
+        "L_end%=:\n"
 #define EV_WALK_VISIT_ASM_(NC, T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H)                               \
     asm volatile(                                                                                                                            \
-        "v_pk_fma_f32 " T0 ", %[cx], %[pa], %[pd] op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\t"                                                                                     \
-        "v_pk_fma_f32 " T1 ", %[cy], %[pa], %[pd] op_sel:[0,1,1] op_sel_hi:[1,1,1]\n\t"                                                                                     \
-        "v_pk_fma_f32 " T2 ", %[cz], %[pb], %[pe] op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\t"                                                                                     \
-        "v_pk_fma_f32 " T3 ", %[hx], %[pb], " T0 " op_sel:[0,1,0] op_sel_hi:[1,1,1] neg_lo:[0,1,0] neg_hi:[0,1,0]\n\t"                                                        \
-        "v_pk_fma_f32 " T4 ", %[hy], %[pc], " T1 " op_sel:[0,0,0] op_sel_hi:[1,0,1] neg_lo:[0,1,0] neg_hi:[0,1,0]\n\t"                                                        \
-        "v_pk_fma_f32 " T5 ", %[hz], %[pc], " T2 " op_sel:[0,1,0] op_sel_hi:[1,1,1] neg_lo:[0,1,0] neg_hi:[0,1,0]\n\t"                                                        \
-        "v_pk_fma_f32 " T0 ", %[hx], %[pb], " T0 " op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"                                                                                     \
-        "v_pk_fma_f32 " T1 ", %[hy], %[pc], " T1 " op_sel:[0,0,0] op_sel_hi:[1,0,1]\n\t"                                                                                     \
-        "v_pk_fma_f32 " T2 ", %[hz], %[pc], " T2 " op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"                                                                                     \
-        "v_max3_f32 " T3L ", " T3L ", " T4L ", " T5L " clamp\n\t"                                                                            \
-        "v_min3_f32 " T0L ", " T0L ", " T1L ", " T2L " clamp\n\t"                                                                            \
-        "v_max3_f32 " T3H ", " T3H ", " T4H ", " T5H " clamp\n\t"                                                                            \
-        "v_min3_f32 " T0H ", " T0H ", " T1H ", " T2H " clamp\n\t"                                                                            \
-        "v_cmp_lt_f32 vcc, " T3L ", " T0L "\n\t"                                                                                             \
-        "v_cmp_lt_f32 %[m1], " T3H ", " T0H "\n\t"                                                                                           \
-        "s_or_b64 %[t64], vcc, %[m1]\n\t"                                                                                                    \
-        "s_cbranch_scc0 L_pop%=\n\t"                                                                                                         \
-        "s_cmp_eq_u64 vcc, 0\n\t"                                                                                                            \
-        "s_cbranch_scc1 L_c1%=\n\t"                                                                                                          \
-        "s_cmp_eq_u64 %[m1], 0\n\t"                                                                                                          \
-        "s_cbranch_scc1 L_c0%=\n\t"                                                                                                          \
-        "s_bcnt1_i32_b64 %[p0], vcc\n\t"                                                                                                     \
-        "s_bcnt1_i32_b64 %[p1], %[m1]\n\t"                                                                                                   \
-        "s_cmp_ge_i32 %[p0], %[p1]\n\t"                                                                                                      \
-        "s_cselect_b32 %[p0], %[c1], %[c0]\n\t"                                                                                              \
-        "s_cselect_b32 %[cur], %[c0], %[c1]\n\t"                                                                                             \
-        "s_mov_b32 m0, %[sp]\n\t"                                                                                                            \
-        "s_add_i32 %[sp], %[sp], 1\n\t"                                                                                                      \
-        "v_writelane_b32 %[vstack], %[p0], m0\n\t"                                                                                           \
-        "s_branch L_end%=\n"                                                                                                                 \
-        "L_c0%=:\n\t"                                                                                                                        \
-        "s_mov_b32 %[cur], %[c0]\n\t"                                                                                                        \
-        "s_branch L_end%=\n"                                                                                                                 \
-        "L_c1%=:\n\t"                                                                                                                        \
-        "s_mov_b32 %[cur], %[c1]\n\t"                                                                                                        \
-        "s_branch L_end%=\n"                                                                                                                 \
-        "L_pop%=:\n\t"                                                                                                                       \
-        "s_brev_b32 %[cur], 1\n\t"                                                                                                           \
-        "s_cmp_eq_u32 %[sp], 0\n\t"                                                                                                          \
-        "s_cbranch_scc1 L_end%=\n\t"                                                                                                         \
-        "s_sub_i32 %[sp], %[sp], 1\n\t"                                                                                                      \
-        "s_nop 0\n\t"                                                                                                                        \
-        "v_readlane_b32 %[cur], %[vstack], %[sp]\n"                                                                                          \
-        "L_end%=:\n"                                                                                                                         \
+        EV_VISIT_TEXT("%[cx]", "%[cy]", "%[cz]", "%[hx]", "%[hy]", "%[hz]", "%[c0]", "%[c1]", "%[m1]", "%[t64]", "%[p0]", "%[p1]",           \
+                      T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H)                                    \
         : [cur] "+s"(cur), [sp] "+s"(sp), [vstack] "+v"(vstack), [m1] "=&s"(m1_), [t64] "=&s"(t64_), [p0] "=&s"(p0_), [p1] "=&s"(p1_)          \
         : [cx] NC(cx_), [cy] NC(cy_), [cz] NC(cz_), [hx] NC(hx_), [hy] NC(hy_), [hz] NC(hz_), [c0] "s"(c0_), [c1] "s"(c1_),              \
           [pa] "v"(pa_), [pb] "v"(pb_), [pc] "v"(pc_),                                     \
           [pd] "v"(pd_), [pe] "v"(pe_), [lane] "v"(lane_id)                                                                 \
         : "vcc", "scc", "m0", T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H)
+
+// The walk below one entry (the root, or what a synthetic node let in) as ONE hand-written statement (EVPLP_LEAF_ASM=0: the compiler's loop
+// around the node visit and its leaf step around tri_pair_any, as before).  What the compiler made of the leaf step was 43 vector
+// instructions and 6 s_nop per triangle pair, and about 108 scalar instructions and 17 branches of bookkeeping per leaf (~50 and 10 on the
+// commonest path: one pair, no hit, pop) -- loop-carried masks copied in front of every leaf and back behind it, lane-mask booleans for
+// every scalar decision.  Here:
+// * EV_PAIR_TEXT is tri_pair_test instruction for instruction -- the same operations in the same order with the same operand roles, so
+//   every result bit is the compiler's, the non-finite cases of the comment above tri_pair_test included -- with three differences that
+//   touch no value: the ray rides in three register pairs {dx, dy} {dz, ox} {oy, oz} whose halves op_sel / op_sel_hi broadcast to both
+//   triangles (the compiler holds d twice, six registers, and copies the wave-uniform origin from scalar registers into a register pair
+//   in front of every p0 - o: three v_mov_b64 per pair); the two hit masks go from the compares straight into one scalar pair (the
+//   compiler's round trip was lane mask -> v_cndmask -> v_cmp_ne -> lane mask); and the p0 - o subtractions, which do not depend on the
+//   reciprocal, fill three of the eight wait states of the den -> rcp -> refinement chain (a packed or transcendental result is not
+//   read by the very next instruction: the compiler pads these, the other five stay s_nop).  40 vector instructions and 5 s_nop.
+// * the bookkeeping: hm = any & alive; none -> pop.  Otherwise alive &= ~hm (the lane's answer is read from alive behind the walk: no
+//   second mask); nobody left -> done, and the cut at its end; else the newly occluded lanes get the dead origin terms (under their own
+//   exec mask) and the walk pops.
+// * pair B of a three- or four-triangle leaf is neither fetched nor tested when pair A has occluded every live lane (any-hit).
+// Inline-asm operands cannot name the halves of a register tuple and a statement takes at most 30 operands, so the node / leaf tuples and
+// the scalar temporaries are FIXED registers s31 and s[32:65], named in the clobber list (the compiler's loop held 32 scalar registers of tuples
+// and about eight of temporaries across the same code); the vector temporaries are v[VT:VT+11] as for the node visit.
+//   s[32:47] node, or leaf dwords 0-15, then 32-47    s[48:63] leaf dwords 16-31    s[64:65] the leaf's hit mask; popcounts of a visit
+//   s31 byte offset
+// (the second mask of a visit forms in the node's two padding dwords, the hit masks of a pair's triangles in the registers of its own
+// p0x / p0y, dead by then; vcc holds what lives for two instructions).  .sgpr_count stays below 81: from there on one wave per SIMD
+// fewer is resident.  Where the block sits decides what the allocator parks in VGPR lanes around it (tests/test_adaptive_resources.py
+// holds the adaptive variants to the defaults' counts): at s32 all four walk kernels park fewer than before and the adaptive ones
+// no more than their defaults; four registers lower or higher one of them parks one or two more.
+#ifndef EVPLP_LEAF_ASM
+#define EVPLP_LEAF_ASM 1
+#endif
+#define EV_PAIR_TEXT(P0X, P0Y, P0Z, E0X, E0Y, E0Z, E1X, E1Y, E1Z, NX, NY, NZ, HA, HB, T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H) \
+        "v_pk_mul_f32 " T0 ", " NX ", %[ra] op_sel:[0,0] op_sel_hi:[1,0]\n\t"                                                                \
+        "v_pk_add_f32 " T1 ", " P0X ", %[rb] op_sel:[0,1] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]\n\t"                                     \
+        "v_pk_fma_f32 " T0 ", " NY ", %[ra], " T0 " op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"                                                    \
+        "v_pk_add_f32 " T2 ", " P0Y ", %[rc] op_sel:[0,0] op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,1]\n\t"                                     \
+        "v_pk_fma_f32 " T0 ", " NZ ", %[rb], " T0 " op_sel:[0,0,0] op_sel_hi:[1,0,1]\n\t"                                                    \
+        "v_pk_add_f32 " T3 ", " P0Z ", %[rc] op_sel:[0,1] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]\n\t"                                     \
+        "v_rcp_f32 " T4L ", " T0L "\n\t"                                                                                                     \
+        "v_rcp_f32 " T4H ", " T0H "\n\t"                                                                                                     \
+        "s_nop 0\n\t"                                                                                                                        \
+        "v_pk_fma_f32 " T5 ", " T0 ", " T4 ", 1.0 op_sel_hi:[1,1,0] neg_lo:[1,0,0] neg_hi:[1,0,0]\n\t"                                       \
+        "s_nop 0\n\t"                                                                                                                        \
+        "v_pk_fma_f32 " T4 ", " T5 ", " T4 ", " T4 "\n\t"                                                                                    \
+        "s_nop 0\n\t"                                                                                                                        \
+        "v_pk_fma_f32 " T0 ", " T0 ", " T4 ", 1.0 op_sel_hi:[1,1,0] neg_lo:[1,0,0] neg_hi:[1,0,0]\n\t"                                       \
+        "s_nop 0\n\t"                                                                                                                        \
+        "v_pk_fma_f32 " T0 ", " T0 ", " T4 ", " T4 "\n\t"                                                                                    \
+        "s_nop 0\n\t"                                                                                                                        \
+        "v_pk_mul_f32 " T1 ", " T1 ", " T0 "\n\t"                                                                                            \
+        "v_pk_mul_f32 " T2 ", " T2 ", " T0 "\n\t"                                                                                            \
+        "v_pk_mul_f32 " T3 ", " T3 ", " T0 "\n\t"                                                                                            \
+        "v_pk_mul_f32 " T4 ", %[rb], " T2 " op_sel:[0,0] op_sel_hi:[0,1] neg_lo:[0,1] neg_hi:[0,1]\n\t"                                      \
+        "v_pk_mul_f32 " T5 ", %[ra], " T3 " op_sel:[0,0] op_sel_hi:[0,1] neg_lo:[0,1] neg_hi:[0,1]\n\t"                                      \
+        "v_pk_mul_f32 " T0 ", %[ra], " T1 " op_sel:[1,0] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]\n\t"                                      \
+        "v_pk_fma_f32 " T4 ", %[ra], " T3 ", " T4 " op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"                                                    \
+        "v_pk_fma_f32 " T5 ", %[rb], " T1 ", " T5 " op_sel:[0,0,0] op_sel_hi:[0,1,1]\n\t"                                                    \
+        "v_pk_mul_f32 " T1 ", " T1 ", " NX "\n\t"                                                                                            \
+        "v_pk_fma_f32 " T0 ", %[ra], " T2 ", " T0 " op_sel:[0,0,0] op_sel_hi:[0,1,1]\n\t"                                                    \
+        "v_pk_fma_f32 " T1 ", " NY ", " T2 ", " T1 "\n\t"                                                                                    \
+        "v_pk_mul_f32 " T2 ", " T4 ", " E1X "\n\t"                                                                                           \
+        "v_pk_fma_f32 " T1 ", " NZ ", " T3 ", " T1 "\n\t"                                                                                    \
+        "v_pk_mul_f32 " T3 ", " T4 ", " E0X "\n\t"                                                                                           \
+        "v_pk_fma_f32 " T2 ", " T5 ", " E1Y ", " T2 "\n\t"                                                                                   \
+        "v_pk_fma_f32 " T3 ", " T5 ", " E0Y ", " T3 "\n\t"                                                                                   \
+        "v_pk_fma_f32 " T2 ", " T0 ", " E1Z ", " T2 "\n\t"                                                                                   \
+        "v_pk_fma_f32 " T3 ", " T0 ", " E0Z ", " T3 "\n\t"                                                                                   \
+        "v_cmp_gt_f32 vcc, %[tmax], " T1L "\n\t"                                                                                             \
+        "v_pk_add_f32 " T4 ", " T2 ", " T3 "\n\t"                                                                                            \
+        "v_cmp_lt_f32 " HA ", %[tmin], " T1L "\n\t"                                                                                        \
+        "v_pk_add_f32 " T4 ", " T4 ", 1.0 op_sel_hi:[1,0] neg_lo:[1,0] neg_hi:[1,0]\n\t"                                                     \
+        "s_and_b64 " HA ", " HA ", vcc\n\t"                                                                                              \
+        "v_cmp_gt_f32 vcc, %[tmax], " T1H "\n\t"                                                                                             \
+        "v_min3_f32 " T2L ", " T2L ", " T3L ", " T4L "\n\t"                                                                                  \
+        "v_min3_f32 " T2H ", " T2H ", " T3H ", " T4H "\n\t"                                                                                  \
+        "v_cmp_lt_f32 " HB ", %[tmin], " T1H "\n\t"                                                                                        \
+        "s_and_b64 " HB ", " HB ", vcc\n\t"                                                                                              \
+        "v_cmp_le_f32 vcc, 0, " T2L "\n\t"                                                                                                   \
+        "s_and_b64 " HA ", " HA ", vcc\n\t"                                                                                              \
+        "v_cmp_le_f32 vcc, 0, " T2H "\n\t"                                                                                                   \
+        "s_and_b64 " HB ", " HB ", vcc\n\t"
+#define EV_WALK_LOOP_ASM(T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H)                                 \
+    asm volatile(                                                                                                                            \
+        "s_cmp_lt_i32 %[cur], 0\n\t"                                                                                                         \
+        "s_cbranch_scc1 L_leaf%=\n"                                                                                                          \
+        "L_node%=:\n\t"                                                                                                                      \
+        "s_lshl_b32 s31, %[cur], 6\n\t"                                                                                                      \
+        "s_load_dwordx16 s[32:47], %[nodes], s31\n\t"                                                                                        \
+        "s_waitcnt lgkmcnt(0)\n\t"                                                                                                           \
+        EV_VISIT_TEXT("s[32:33]", "s[34:35]", "s[36:37]", "s[38:39]", "s[40:41]", "s[42:43]", "s44", "s45", "s[46:47]", "s[64:65]", "s64", "s65", \
+                      T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H)                                    \
+        "\ts_cmp_lt_i32 %[cur], 0\n\t"                                                                                                       \
+        "s_cbranch_scc0 L_node%=\n"                                                                                                          \
+        "L_leaf%=:\n\t"                                                                                                                      \
+        "s_cmp_eq_u32 %[cur], 0x80000000\n\t"                                                                                                \
+        "s_cbranch_scc1 L_done%=\n\t"                                                                                                        \
+        "s_not_b32 s31, %[cur]\n\t"                                                                                                          \
+        "s_lshr_b32 s31, s31, 2\n\t"                                                                                                         \
+        "s_mulk_i32 s31, 0xc0\n\t"                                                                                                           \
+        "s_load_dwordx16 s[32:47], %[leaves], s31\n\t"                                                                                       \
+        "s_load_dwordx16 s[48:63], %[leaves], s31 offset:0x40\n\t"                                                                           \
+        "s_waitcnt lgkmcnt(0)\n\t"                                                                                                           \
+        EV_PAIR_TEXT("s[32:33]", "s[34:35]", "s[36:37]", "s[38:39]", "s[40:41]", "s[42:43]", "s[44:45]", "s[46:47]", "s[48:49]", "s[50:51]", "s[52:53]", "s[54:55]", \
+                     "s[64:65]", "s[32:33]", T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H)                                     \
+        "s_or_b64 s[64:65], s[64:65], s[32:33]\n\t"                                                                                          \
+        "s_bitcmp1_b32 %[cur], 1\n\t"                                                                                                        \
+        "s_cbranch_scc1 L_book%=\n\t"                                                                                                        \
+        "s_andn2_b64 vcc, %[alive], s[64:65]\n\t"                                                                                             \
+        "s_cbranch_scc0 L_book%=\n\t"                                                                                                        \
+        "s_addk_i32 s31, 0x80\n\t"                                                                                                           \
+        "s_load_dwordx16 s[32:47], %[leaves], s31\n\t"                                                                                       \
+        "s_waitcnt lgkmcnt(0)\n\t"                                                                                                           \
+        EV_PAIR_TEXT("s[56:57]", "s[58:59]", "s[60:61]", "s[62:63]", "s[32:33]", "s[34:35]", "s[36:37]", "s[38:39]", "s[40:41]", "s[42:43]", "s[44:45]", "s[46:47]", \
+                     "s[58:59]", "s[56:57]", T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H)                                     \
+        "s_or_b64 s[58:59], s[58:59], s[56:57]\n\t"                                                                                          \
+        "s_or_b64 s[64:65], s[64:65], s[58:59]\n"                                                                                            \
+        "L_book%=:\n\t"                                                                                                                      \
+        "s_and_b64 s[64:65], s[64:65], %[alive]\n\t"                                                                                         \
+        "s_cbranch_scc0 L_lpop%=\n\t"                                                                                                        \
+        "s_andn2_b64 %[alive], %[alive], s[64:65]\n\t"                                                                                       \
+        "s_cbranch_scc0 L_alldead%=\n\t"                                                                                                        \
+        "v_mov_b32 " T0L ", 0x7f800000\n\t"                                                                                                  \
+        "v_mov_b32 " T0H ", 0x7f800000\n\t"                                                                                                  \
+        "s_and_saveexec_b64 vcc, s[64:65]\n\t"                                                                                                \
+        "v_mov_b64 %[pd], " T0 "\n\t"                                                                                                        \
+        "v_mov_b64 %[pe], " T0 "\n\t"                                                                                                        \
+        "s_mov_b64 exec, vcc\n"                                                                                                              \
+        "L_lpop%=:\n\t"                                                                                                                      \
+        "s_cmp_eq_u32 %[sp], 0\n\t"                                                                                                          \
+        "s_cbranch_scc1 L_empty%=\n\t"                                                                                                       \
+        "s_sub_i32 %[sp], %[sp], 1\n\t"                                                                                                      \
+        "s_nop 0\n\t"                                                                                                                        \
+        "v_readlane_b32 %[cur], %[vstack], %[sp]\n\t"                                                                                        \
+        "s_nop 0\n\t"                                                                                                                        \
+        "s_cmp_lt_i32 %[cur], 0\n\t"                                                                                                         \
+        "s_cbranch_scc0 L_node%=\n\t"                                                                                                        \
+        "s_branch L_leaf%=\n"                                                                                                                \
+        "L_alldead%=:\n\t"                                                                                                                   \
+        "s_mov_b32 %[sp], 0\n\t"                                                                                                             \
+        "s_mov_b32 %[coff], -1\n"                                                                                                           \
+        "L_empty%=:\n\t"                                                                                                                     \
+        "s_brev_b32 %[cur], 1\n"                                                                                                             \
+        "L_done%=:\n"                                                                                                                      \
+        : [cur] "+s"(cur), [sp] "+s"(sp), [vstack] "+v"(vstack), [alive] "+s"(alive), [pd] "+v"(pd_), [pe] "+v"(pe_),     \
+          [coff] "+s"(cut_off)                                                                                                               \
+        : [nodes] "s"(node_base), [leaves] "s"(leaf_base), [pa] "v"(pa_), [pb] "v"(pb_), [pc] "v"(pc_),                                      \
+          [ra] "v"(ra_), [rb] "v"(rb_), [rc] "v"(rc_), [tmin] "s"(tmin), [tmax] "s"(tmax)                                                    \
+        : "vcc", "scc", "m0", "memory", T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H,                                          \
+          "s32", "s33", "s34", "s35", "s36", "s37", "s38", "s39", "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", \
+          "s52", "s53", "s54", "s55", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s65", "s31")
+
+// EV_PAIR_TEXT on its own, for evplp_selftest(2): the two hit masks of one pair for the wave's 64 directions (the kernel keeps
+// v[VT:VT+11] free with amdgpu_num_vgpr(VT), as the walks do)
+template <int VT>
+EV_DEV void pair_hits_asm(const PairOps &P_, V3 o, V3 d, float tmin, float tmax, unsigned long long &hit_a, unsigned long long &hit_b) {
+    static_assert(VT == 52 || VT == 116, "reserved temporaries: v[52:63] or v[116:127]");
+    v2f ra_, rb_, rc_;
+    ra_.x = d.x; ra_.y = d.y; rb_.x = d.z; rb_.y = o.x; rc_.x = o.y; rc_.y = o.z;
+#define EV_PAIR_ALONE(T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H)                                    \
+    asm volatile(                                                                                                                            \
+        EV_PAIR_TEXT("%[p0x]", "%[p0y]", "%[p0z]", "%[e0x]", "%[e0y]", "%[e0z]", "%[e1x]", "%[e1y]", "%[e1z]", "%[nx]", "%[ny]", "%[nz]",    \
+                     "%[ha]", "%[hb]", T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H)                   \
+        : [ha] "=&s"(hit_a), [hb] "=&s"(hit_b)                                                                                               \
+        : [p0x] "s"(P_.p0x), [p0y] "s"(P_.p0y), [p0z] "s"(P_.p0z), [e0x] "s"(P_.e0x), [e0y] "s"(P_.e0y), [e0z] "s"(P_.e0z),                  \
+          [e1x] "s"(P_.e1x), [e1y] "s"(P_.e1y), [e1z] "s"(P_.e1z), [nx] "s"(P_.nx), [ny] "s"(P_.ny), [nz] "s"(P_.nz),                        \
+          [ra] "v"(ra_), [rb] "v"(rb_), [rc] "v"(rc_), [tmin] "s"(tmin), [tmax] "s"(tmax)                                                    \
+        : "vcc", "scc", T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H)
+    if constexpr (VT == 52) EV_PAIR_ALONE("v[52:53]", "v[54:55]", "v[56:57]", "v[58:59]", "v[60:61]", "v[62:63]", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63");
+    else EV_PAIR_ALONE("v[116:117]", "v[118:119]", "v[120:121]", "v[122:123]", "v[124:125]", "v[126:127]", "v116", "v117", "v118", "v119", "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127");
+#undef EV_PAIR_ALONE
+}
 
 // VT = first of the twelve reserved temporaries: 52 for the 64-register VPL gather, 116 for the 128-register VSL gather; 0 = the C++ loop.
 // CUT: the walk starts from an entry cut (kernels.h CutArgs: `cut` points at the synthetic nodes of this (tile group, VPL), node 0
@@ -658,6 +832,38 @@ EV_DEV bool occluded_wave(const char *node_base, const char *leaf_base, V3 o, V3
             if constexpr (VT == 52) EV_WALK_VISIT_ASM("v[52:53]", "v[54:55]", "v[56:57]", "v[58:59]", "v[60:61]", "v[62:63]", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63"); \
             else EV_WALK_VISIT_ASM("v[116:117]", "v[118:119]", "v[120:121]", "v[122:123]", "v[124:125]", "v[126:127]", "v116", "v117", "v118", "v119", "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127"); \
         }
+#if EVPLP_LEAF_ASM
+        // the ray of the pair test: {dx, dy} {dz, ox} {oy, oz}
+        v2f ra_, rb_, rc_;
+        ra_.x = d.x; ra_.y = d.y; rb_.x = d.z; rb_.y = o.x; rc_.x = o.y; rc_.y = o.z;
+        asm("" : "+v"(rc_));        // (wave-uniform: left alone, the compiler keeps it in scalar registers and copies it out in front of every pair)
+#endif
+#define EV_WALK_LOOP                                                                                                                         \
+        if constexpr (VT == 52) EV_WALK_LOOP_ASM("v[52:53]", "v[54:55]", "v[56:57]", "v[58:59]", "v[60:61]", "v[62:63]", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63"); \
+        else EV_WALK_LOOP_ASM("v[116:117]", "v[118:119]", "v[120:121]", "v[122:123]", "v[124:125]", "v[126:127]", "v116", "v117", "v118", "v119", "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127");
+#if EVPLP_LEAF_ASM
+        for (;;) {
+            if constexpr (CUT) {
+                if (cut_off >= cut_end) break;       // (also: the walk statement moved cut_off past every end when the last live lane was occluded)
+                // the synthetic node from the slot's LDS copy, as below
+                v16i syn;
+                {
+                    const float4 *q = cut_lds + 4u * cut_off;
+#pragma unroll
+                    for (int w = 0; w < 4; w++) {
+                        const float4 qq = q[w];
+                        if (w < 3 || true) { syn[4 * w] = __builtin_amdgcn_readfirstlane(__float_as_int(qq.x)); syn[4 * w + 1] = __builtin_amdgcn_readfirstlane(__float_as_int(qq.y)); }
+                        if (w < 3) { syn[4 * w + 2] = __builtin_amdgcn_readfirstlane(__float_as_int(qq.z)); syn[4 * w + 3] = __builtin_amdgcn_readfirstlane(__float_as_int(qq.w)); }
+                    }
+                    syn[14] = 0; syn[15] = 0;
+                }
+                cut_off++;
+                EV_VISIT(syn)
+            }
+            EV_WALK_LOOP        // ... until cur == kNoChild: nothing left below this entry, or no live lane left (then the cut is at its end too)
+            if constexpr (!CUT) break;
+        }
+#else
         for (;;) {
             if constexpr (CUT) {
                 if (cut_off >= cut_end) break;
@@ -707,8 +913,14 @@ EV_DEV bool occluded_wave(const char *node_base, const char *leaf_base, V3 o, V3
             }
             if constexpr (!CUT) break;
         }
+#endif
 #undef EV_VISIT
+#undef EV_WALK_LOOP
+#if EVPLP_LEAF_ASM
+        return alive_lane && ((alive >> (threadIdx.x & 63u)) & 1ull) == 0ull;      // occluded = was alive, is not any more (no second mask in the loop)
+#else
         return ((hitm >> (threadIdx.x & 63u)) & 1ull) != 0ull;
+#endif
     }
 #endif
     // the reference implementation of the same walk in C++ (EVPLP_WALK_ASM=0, and the counters build)

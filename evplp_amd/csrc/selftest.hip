@@ -48,6 +48,94 @@ __global__ __launch_bounds__(256) void selftest_pow_kernel(unsigned long long *o
     }
 }
 
+// which = 2: the hand-written triangle-pair test of the packet walks (device_common.hpp EV_PAIR_TEXT, through pair_hits_asm) against
+// tri_pair_test, its C++ statement, on the same inputs: kPairTestPairs pairs x 64 directions, generated here from a fixed seed, in six
+// classes (pair index mod 6):
+//   0 random triangles and segments                      3 scales 2^-41 .. 2^-44: the denominator n . d crosses into the denormals
+//   1 small-integer coordinates, bounds 1/8 and 1/2      4 as 0 with an all-zero B half (the padding of a one- or three-triangle leaf)
+//   2 as 1 (a quarter of the lanes: den = 0, below)      5 coordinates scaled by 1e-15, 1e-12, 1e12, 1e15
+// In every class lanes 0-31 aim at triangle A and lanes 32-63 at triangle B: at the point p0 + b (p1 - p0) + c (p2 - p0) with (b, c) from
+// a 4 x 4 grid of eighths that holds the vertices (0, 0) (1, 0) (0, 1), edge points (b = 0, c = 0, b + c = 1) and interior and exterior
+// points, reached at t = 1/4, or 1/8, or 1/2 (d = (P - o) / t: exact for the integer classes, where t then lands exactly on the
+// bounds); odd lanes of class 2 run along the plane instead (d = i e0 + j e1, den = 0 exactly).
+// out[0] lanes x triangles whose hit bit differs (both register layouts, VT = 52 and 116), out[1] cases, out[2] hits (tri_pair_test's),
+// out[3] / [4] / [5] = hits of classes 0 | 1 << 32, 2 | 3 << 32, 4 | 5 << 32.
+constexpr uint32_t kPairTestPairs = 4096u;
+struct PairTestRec { float tri[24]; float o[3]; float tmin, tmax; uint32_t cls; uint32_t pad[2]; };      // 128 bytes: two s_load_dwordx16
+static_assert(sizeof(PairTestRec) == 128, "PairTestRec");
+EV_DEV float pt_uniform(uint64_t &st) { st = splitmix64(st); return (float)(st >> 40) * (1.0f / 16777216.0f); }
+EV_DEV float pt_int(uint64_t &st, int lim) { st = splitmix64(st); return (float)((int)((st >> 33) % (uint64_t)(2 * lim + 1)) - lim); }
+__global__ __launch_bounds__(64) void selftest_pair_gen_kernel(PairTestRec *recs) {
+    const uint32_t pair = blockIdx.x * 64u + threadIdx.x;
+    if (pair >= kPairTestPairs) return;
+    PairTestRec r = {};
+    const uint32_t cls = pair % 6u;
+    uint64_t st = 0x5eedull * 0x10001ull + pair;
+    const bool ints = cls == 1u || cls == 2u;
+    float scale = 1.0f;
+    if (cls == 3u) scale = __builtin_ldexpf(1.0f, -41 - (int)((pair / 6u) & 3u));
+    if (cls == 5u) { const float sc[4] = { 1e-15f, 1e-12f, 1e12f, 1e15f }; scale = sc[(pair / 6u) & 3u]; }
+    for (int h = 0; h < 2; h++) {
+        float v[9];
+        for (int k = 0; k < 9; k++) v[k] = (ints ? pt_int(st, 4) : 2.0f * pt_uniform(st) - 1.0f) * scale;
+        if (h == 1 && cls == 4u) continue;          // the B half stays all zeros
+        // (evplp_build_accel's precompute_tri: e0 = p1 - p0, e1 = p0 - p2, n = cross(e1, e0))
+        float e0[3], e1[3];
+        for (int k = 0; k < 3; k++) { e0[k] = v[3 + k] - v[k]; e1[k] = v[k] - v[6 + k]; }
+        const float n[3] = { e1[1] * e0[2] - e1[2] * e0[1], e1[2] * e0[0] - e1[0] * e0[2], e1[0] * e0[1] - e1[1] * e0[0] };
+        for (int k = 0; k < 3; k++) { r.tri[2 * k + h] = v[k]; r.tri[6 + 2 * k + h] = e0[k]; r.tri[12 + 2 * k + h] = e1[k]; r.tri[18 + 2 * k + h] = n[k]; }
+    }
+    for (int k = 0; k < 3; k++) r.o[k] = (ints ? pt_int(st, 8) : 4.0f * pt_uniform(st) - 2.0f) * scale;
+    r.tmin = ints ? 0.125f : 0.0001f; r.tmax = ints ? 0.5f : 1.0f - 0.0001f;
+    r.cls = cls;
+    recs[pair] = r;
+}
+template <int VT> EV_DEV void selftest_pair_body(const PairTestRec *recs, unsigned long long *out) {
+#pragma clang fp contract(off)
+    const uint32_t pair = blockIdx.x, lane = threadIdx.x & 63u;
+    v16i a, b;
+    sload16x2(recs, pair * (uint32_t)sizeof(PairTestRec), a, b);
+    PairOps P;
+    P.p0x = pk(a[0], a[1]); P.p0y = pk(a[2], a[3]); P.p0z = pk(a[4], a[5]); P.e0x = pk(a[6], a[7]); P.e0y = pk(a[8], a[9]); P.e0z = pk(a[10], a[11]);
+    P.e1x = pk(a[12], a[13]); P.e1y = pk(a[14], a[15]); P.e1z = pk(b[0], b[1]); P.nx = pk(b[2], b[3]); P.ny = pk(b[4], b[5]); P.nz = pk(b[6], b[7]);
+    const V3 o = v3(f_of(b[8]), f_of(b[9]), f_of(b[10]));
+    const float tmin = f_of(b[11]), tmax = f_of(b[12]);
+    const uint32_t cls = (uint32_t)b[13];
+    // this lane's direction
+    const int h = (int)(lane >> 5);
+    const uint32_t q = lane & 31u;
+    const float p0[3] = { h ? P.p0x.y : P.p0x.x, h ? P.p0y.y : P.p0y.x, h ? P.p0z.y : P.p0z.x };
+    const float e0[3] = { h ? P.e0x.y : P.e0x.x, h ? P.e0y.y : P.e0y.x, h ? P.e0z.y : P.e0z.x };
+    const float e1[3] = { h ? P.e1x.y : P.e1x.x, h ? P.e1y.y : P.e1y.x, h ? P.e1z.y : P.e1z.x };
+    float dd[3];
+    if (cls == 2u && (q & 1u)) {
+        const float i = (float)((int)(q >> 1) % 4 - 1), j = (float)((int)(q >> 3) + 1);
+        for (int k = 0; k < 3; k++) dd[k] = i * e0[k] + j * e1[k];
+    } else {
+        const float bs[4] = { 0.0f, 0.5f, 1.0f, 0.25f }, cs[4] = { 0.0f, 0.5f, 0.25f, 1.0f };
+        const float bb = bs[q & 3u], cc = cs[(q >> 2) & 3u];
+        const float inv_t = (q >> 4) == 0u ? 4.0f : ((pair >> 3) & 1u ? 8.0f : 2.0f);
+        // P = p0 + b (p1 - p0) + c (p2 - p0) = p0 + b e0 - c e1
+        for (int k = 0; k < 3; k++) dd[k] = ((p0[k] + bb * e0[k] - cc * e1[k]) - (k == 0 ? o.x : k == 1 ? o.y : o.z)) * inv_t;
+    }
+    const V3 d = v3(dd[0], dd[1], dd[2]);
+    unsigned long long ha, hb;
+    pair_hits_asm<VT>(P, o, d, tmin, tmax, ha, hb);
+    const Hit2 ref = tri_pair_test(P.p0x, P.p0y, P.p0z, P.e0x, P.e0y, P.e0z, P.e1x, P.e1y, P.e1z, P.nx, P.ny, P.nz, o, d, tmin, tmax);
+    const unsigned long long ra = ballot64(ref.a), rb = ballot64(ref.b);
+    if (lane == 0u) {
+        const unsigned long long bad = (unsigned long long)(__builtin_popcountll(ha ^ ra) + __builtin_popcountll(hb ^ rb));
+        const unsigned long long hits = (unsigned long long)(__builtin_popcountll(ra) + __builtin_popcountll(rb));
+        if (bad) atomicAdd(&out[0], bad);
+        atomicAdd(&out[1], 128ull);
+        atomicAdd(&out[2], hits);
+        atomicAdd(&out[3 + cls / 2u], hits << (32u * (cls & 1u)));
+    }
+}
+// (the attribute takes a literal: one kernel per register layout, as the walks have)
+__attribute__((amdgpu_num_vgpr(52))) __global__ __launch_bounds__(64) void selftest_pair52_kernel(const PairTestRec *recs, unsigned long long *out) { selftest_pair_body<52>(recs, out); }
+__attribute__((amdgpu_num_vgpr(116))) __global__ __launch_bounds__(64) void selftest_pair116_kernel(const PairTestRec *recs, unsigned long long *out) { selftest_pair_body<116>(recs, out); }
+
 // evplp_debug_ev_math: ev_math.h's functions AS THE DEVICE COMPUTES THEM, on the caller's inputs.  The light-tracing records are compared with
 // the oracle's byte for byte, and the oracle #includes the same header: that comparison vouches for the walk and the draw order, not for
 // these functions -- unless the header really gives the same bits on both machines, which is what tests/test_gpu_parity.py checks with this
@@ -82,7 +170,7 @@ extern "C" int evplp_debug_ev_math(evplp_context *c, int32_t which, const float 
 }
 
 extern "C" int evplp_selftest(evplp_context *c, int32_t which, uint64_t *out, int32_t capacity) {
-    if (!c || !out || capacity < 6 || which < 0 || which > 1) { if (c) c->set_error("evplp_selftest: bad arguments"); return EVPLP_ERR_INVALID; }
+    if (!c || !out || capacity < 6 || which < 0 || which > 2) { if (c) c->set_error("evplp_selftest: bad arguments"); return EVPLP_ERR_INVALID; }
     if (hipSetDevice(c->cfg.device) != hipSuccess) return EVPLP_ERR_HIP;
     unsigned long long *d = nullptr;
     if (hipMalloc((void **)&d, 8 * sizeof(unsigned long long)) != hipSuccess) return EVPLP_ERR_OOM;
@@ -90,8 +178,19 @@ extern "C" int evplp_selftest(evplp_context *c, int32_t which, uint64_t *out, in
     hipError_t e = hipMemcpy(d, init, sizeof(init), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         if (which == 0) hipLaunchKernelGGL(evplp::selftest_rcp_kernel, dim3(4096), dim3(256), 0, c->stream, d);
-        else hipLaunchKernelGGL(evplp::selftest_pow_kernel, dim3(4096), dim3(256), 0, c->stream, d);
-        e = hipStreamSynchronize(c->stream);
+        else if (which == 1) hipLaunchKernelGGL(evplp::selftest_pow_kernel, dim3(4096), dim3(256), 0, c->stream, d);
+        else {
+            evplp::PairTestRec *recs = nullptr;
+            e = hipMalloc((void **)&recs, sizeof(evplp::PairTestRec) * evplp::kPairTestPairs);
+            if (e == hipSuccess) {
+                hipLaunchKernelGGL(evplp::selftest_pair_gen_kernel, dim3(evplp::kPairTestPairs / 64u), dim3(64), 0, c->stream, recs);
+                hipLaunchKernelGGL(evplp::selftest_pair52_kernel, dim3(evplp::kPairTestPairs), dim3(64), 0, c->stream, recs, d);
+                hipLaunchKernelGGL(evplp::selftest_pair116_kernel, dim3(evplp::kPairTestPairs), dim3(64), 0, c->stream, recs, d);
+                e = hipStreamSynchronize(c->stream);
+                hipFree(recs);
+            }
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     }
     unsigned long long h[8] = {};
     if (e == hipSuccess) e = hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);

@@ -596,6 +596,11 @@ int evplp_accel_stack_entries(const evplp_context *ctx);
  * which = 1: d^e as exp2(e log2 d) on the hardware transcendentals (Phong lobes of the VPL gather and the splat) against the
  * double-precision pow for e = 1, 5, 20, 100, 1000, 10000 over 2^22 values of d in (1e-6, 1]: out[k] = largest relative error
  * where the lobe is >= 1e-4 of its peak, in units of 1e-12.
+ * which = 2: the hand-written triangle-pair test of the packet walks against its C++ statement (tri_pair_test) on 4096 generated
+ * pairs x 64 directions in six classes (random; small integers with rays through vertices, along edges and ending on the bounds;
+ * rays in the plane; denormal denominators; an all-zero second triangle; coordinates at 1e-15 .. 1e15), for both register layouts:
+ * out[0] lanes x triangles whose hit bit differs (must be 0), [1] cases, [2] hits, [3] / [4] / [5] hits of classes 0 and 1, 2 and 3,
+ * 4 and 5 (the odd class in the upper 32 bits).
  * Returns the number of words written or a negative status. */
 int evplp_selftest(evplp_context *ctx, int32_t which, uint64_t *out, int32_t capacity);
 /* The direction-sampling functions of light tracing (csrc/ev_math.h: evm_sincosf, evm_powf) as the DEVICE computes them, on host arrays of n
