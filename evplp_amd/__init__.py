@@ -460,7 +460,9 @@ class Context:
 
     def selftest(self, which: int = 0) -> np.ndarray:
         """evplp_selftest: 0 the exact reciprocal, 1 the hardware pow, 2 the hand-written triangle-pair test against tri_pair_test
-        (mismatches, cases, hits, then the hits of classes 0|1, 2|3, 4|5 packed 32 bits each)"""
+        (mismatches, cases, hits, then the hits of classes 0|1, 2|3, 4|5 packed 32 bits each), 3 the in-place visit of a synthetic
+        node of an entry cut against the scalar-operand node visit (differences, cases, entered lanes, then the entered lanes of
+        classes 0|1, 2|3, 4|5 packed 32 bits each)"""
         out = np.zeros(8, dtype=np.uint64)
         n = self._check(self._lib.evplp_selftest(self._h, which, _ptr(out), 8))
         return out[:n]

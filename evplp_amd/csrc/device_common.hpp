@@ -532,7 +532,8 @@ struct WalkStats { uint32_t nodes, leaves, pairs, exact; int32_t hit_leaf; uint3
 // spends ~17 scalar instructions and 4-5 branches per visit on the decision alone (lane-mask booleans, s_cselect_b64 / s_and exec /
 // s_cbranch_vcc chains); this spends 6-9 and 2-3.  Inline-asm operands cannot name the halves of a register tuple: the node arrives
 // as seven 64-bit scalar operands (sub-registers of the 16-dword tuple the load fills), and the six packed temporaries live in FIXED
-// registers v[VT:VT+11], which the kernels that use this keep free with amdgpu_num_vgpr(VT).  The nine per-lane ray constants ride
+// registers v[VT:VT+11], which the kernels that use this keep free with amdgpu_num_vgpr (VT = 52: v[50:63], amdgpu_num_vgpr(50) -- the pair
+// below the temporaries belongs to the in-place visit of a synthetic node, EV_SYN_VISIT_ASM_).  The nine per-lane ray constants ride
 // in five register pairs -- {1/dx, 1/dy} {1/dz, |1/dx|} {|1/dy|, |1/dz|} {-ox/dx, -oy/dy} {-oz/dz, -} -- and op_sel / op_sel_hi
 // broadcast the wanted half to both children (the C++ loop keeps every constant in both halves of a pair of its own: 18 registers).
 // Same arithmetic and the same descent order (the child more lanes enter first) as the C++ loop below, which stays as the reference
@@ -541,25 +542,10 @@ struct WalkStats { uint32_t nodes, leaves, pairs, exact; int32_t hit_leaf; uint3
 #ifndef EVPLP_WALK_ASM
 #define EVPLP_WALK_ASM 1
 #endif
-#define EV_WALK_VISIT_ASM(T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H) EV_WALK_VISIT_ASM_("s", T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H)
-// NC: where the node's six box operands live -- "s" (a node fetched with s_load) or "v" (a synthetic node of an entry cut, read from LDS
-// with one address for all lanes: the same value in every lane of a VGPR serves as well)
-#define EV_VISIT_TEXT(CX, CY, CZ, HX, HY, HZ, C0, C1, M1, T64, P0, P1, T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H) \
-        "v_pk_fma_f32 " T0 ", " CX ", %[pa], %[pd] op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\t" \
-        "v_pk_fma_f32 " T1 ", " CY ", %[pa], %[pd] op_sel:[0,1,1] op_sel_hi:[1,1,1]\n\t" \
-        "v_pk_fma_f32 " T2 ", " CZ ", %[pb], %[pe] op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\t" \
-        "v_pk_fma_f32 " T3 ", " HX ", %[pb], " T0 " op_sel:[0,1,0] op_sel_hi:[1,1,1] neg_lo:[0,1,0] neg_hi:[0,1,0]\n\t" \
-        "v_pk_fma_f32 " T4 ", " HY ", %[pc], " T1 " op_sel:[0,0,0] op_sel_hi:[1,0,1] neg_lo:[0,1,0] neg_hi:[0,1,0]\n\t" \
-        "v_pk_fma_f32 " T5 ", " HZ ", %[pc], " T2 " op_sel:[0,1,0] op_sel_hi:[1,1,1] neg_lo:[0,1,0] neg_hi:[0,1,0]\n\t" \
-        "v_pk_fma_f32 " T0 ", " HX ", %[pb], " T0 " op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t" \
-        "v_pk_fma_f32 " T1 ", " HY ", %[pc], " T1 " op_sel:[0,0,0] op_sel_hi:[1,0,1]\n\t" \
-        "v_pk_fma_f32 " T2 ", " HZ ", %[pc], " T2 " op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t" \
-        "v_max3_f32 " T3L ", " T3L ", " T4L ", " T5L " clamp\n\t" \
-        "v_min3_f32 " T0L ", " T0L ", " T1L ", " T2L " clamp\n\t" \
-        "v_max3_f32 " T3H ", " T3H ", " T4H ", " T5H " clamp\n\t" \
-        "v_min3_f32 " T0H ", " T0H ", " T1H ", " T2H " clamp\n\t" \
-        "v_cmp_lt_f32 vcc, " T3L ", " T0L "\n\t" \
-        "v_cmp_lt_f32 " M1 ", " T3H ", " T0H "\n\t" \
+#define EV_WALK_VISIT_ASM(T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H) EV_WALK_VISIT_ASM_("s", "", T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H)
+// The descent decision that ends a visit: vcc / M1 = the lanes that enter child 0 / child 1 (C0 / C1: their references, scalar); T64, P0, P1
+// are scalar temporaries (P0 / P1 may be the halves of T64).  One text for both visits (EV_VISIT_TEXT, EV_SYN_VISIT_ASM_).
+#define EV_VISIT_DECIDE_TEXT(C0, C1, M1, T64, P0, P1) \
         "s_or_b64 " T64 ", vcc, " M1 "\n\t" \
         "s_cbranch_scc0 L_pop%=\n\t" \
         "s_cmp_eq_u64 vcc, 0\n\t" \
@@ -589,15 +575,90 @@ struct WalkStats { uint32_t nodes, leaves, pairs, exact; int32_t hit_leaf; uint3
         "s_nop 0\n\t" \
         "v_readlane_b32 %[cur], %[vstack], %[sp]\n" \
         "L_end%=:\n"
-#define EV_WALK_VISIT_ASM_(NC, T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H)                               \
+// NC: where the node's six box operands live -- "s" (a node fetched with s_load) or "v" (a synthetic node of an entry cut, read from LDS
+// with one address for all lanes: the same value in every lane of a VGPR serves as well)
+#define EV_VISIT_TEXT(CX, CY, CZ, HX, HY, HZ, C0, C1, M1, T64, P0, P1, T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H) \
+        "v_pk_fma_f32 " T0 ", " CX ", %[pa], %[pd] op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\t" \
+        "v_pk_fma_f32 " T1 ", " CY ", %[pa], %[pd] op_sel:[0,1,1] op_sel_hi:[1,1,1]\n\t" \
+        "v_pk_fma_f32 " T2 ", " CZ ", %[pb], %[pe] op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\t" \
+        "v_pk_fma_f32 " T3 ", " HX ", %[pb], " T0 " op_sel:[0,1,0] op_sel_hi:[1,1,1] neg_lo:[0,1,0] neg_hi:[0,1,0]\n\t" \
+        "v_pk_fma_f32 " T4 ", " HY ", %[pc], " T1 " op_sel:[0,0,0] op_sel_hi:[1,0,1] neg_lo:[0,1,0] neg_hi:[0,1,0]\n\t" \
+        "v_pk_fma_f32 " T5 ", " HZ ", %[pc], " T2 " op_sel:[0,1,0] op_sel_hi:[1,1,1] neg_lo:[0,1,0] neg_hi:[0,1,0]\n\t" \
+        "v_pk_fma_f32 " T0 ", " HX ", %[pb], " T0 " op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t" \
+        "v_pk_fma_f32 " T1 ", " HY ", %[pc], " T1 " op_sel:[0,0,0] op_sel_hi:[1,0,1]\n\t" \
+        "v_pk_fma_f32 " T2 ", " HZ ", %[pc], " T2 " op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t" \
+        "v_max3_f32 " T3L ", " T3L ", " T4L ", " T5L " clamp\n\t" \
+        "v_min3_f32 " T0L ", " T0L ", " T1L ", " T2L " clamp\n\t" \
+        "v_max3_f32 " T3H ", " T3H ", " T4H ", " T5H " clamp\n\t" \
+        "v_min3_f32 " T0H ", " T0H ", " T1H ", " T2H " clamp\n\t" \
+        "v_cmp_lt_f32 vcc, " T3L ", " T0L "\n\t" \
+        "v_cmp_lt_f32 " M1 ", " T3H ", " T0H "\n\t" \
+        EV_VISIT_DECIDE_TEXT(C0, C1, M1, T64, P0, P1)
+// (TAIL: text behind the visit -- empty in the walks; evplp_selftest(3) copies the first mask out of vcc there)
+#define EV_WALK_VISIT_ASM_(NC, TAIL, T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H)                         \
     asm volatile(                                                                                                                            \
         EV_VISIT_TEXT("%[cx]", "%[cy]", "%[cz]", "%[hx]", "%[hy]", "%[hz]", "%[c0]", "%[c1]", "%[m1]", "%[t64]", "%[p0]", "%[p1]",           \
                       T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H)                                    \
+        TAIL                                                                                                                                 \
         : [cur] "+s"(cur), [sp] "+s"(sp), [vstack] "+v"(vstack), [m1] "=&s"(m1_), [t64] "=&s"(t64_), [p0] "=&s"(p0_), [p1] "=&s"(p1_)          \
         : [cx] NC(cx_), [cy] NC(cy_), [cz] NC(cz_), [hx] NC(hx_), [hy] NC(hy_), [hz] NC(hz_), [c0] "s"(c0_), [c1] "s"(c1_),              \
           [pa] "v"(pa_), [pb] "v"(pb_), [pc] "v"(pc_),                                     \
           [pd] "v"(pd_), [pe] "v"(pe_), [lane] "v"(lane_id)                                                                 \
         : "vcc", "scc", "m0", T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H)
+
+// The visit of a SYNTHETIC node of an entry cut, in place (EVPLP_SYN_INPLACE=0: the node goes from LDS through fourteen v_readfirstlane
+// into scalar registers and then through EV_WALK_VISIT_ASM like a fetched node -- twelve lane-to-scalar moves per visit for operands
+// v_pk_fma_f32 reads from vector registers just as well).  One statement that does its own LDS reads -- `addr` = the byte address of
+// the node in the slot's LDS copy, the same in every lane, so every lane reads the same sixteen dwords -- straight into the visit's own
+// registers, BvhNode order:  v[52:53] cx  v[54:55] cy  v[56:57] cz  v[58:59] hx  v[60:61] hy  v[62:63] hz  v[50:51] the child references.
+// Only the references go to scalar registers (the descent decision selects between them); v[50:51] is then the one spare pair the
+// arithmetic needs, every other result lands on an operand that has just died:
+//   A_x -> v[52:53] (over cx)   A_y -> v[54:55]   A_z -> v[56:57]
+//   near_x -> v[50:51], far_x -> v[52:53]; near_y -> v[58:59] (over hx), far_y -> v[54:55]; near_z -> v[60:61] (over hy), far_z -> v[56:57]
+// The nine v_pk_fma_f32 are EV_VISIT_TEXT's -- the same operand values, op_sel / neg patterns and rounding, near and far of an axis next
+// to each other instead of the three nears first -- so both entered-lane masks are the same bits (evplp_selftest(3) compares the two
+// statements on the part).  Twelve live vector registers more in C++ cost the kernel seven spilled ones; in place it is one pair: the
+// kernels keep v[50:63] free with amdgpu_num_vgpr(50).  Nothing reads a packed result in the very next instruction (as in EV_VISIT_TEXT),
+// and the references reach the scalar unit fifteen vector instructions after their v_readfirstlane.  The references are read FIRST and
+// the waits are staged -- lgkmcnt(3) the references, (2) cx cy, (1) cz hx, (0) hy hz; LDS answers in order, and a scalar load of the
+// compiler's still in flight only makes a wait longer -- so the arithmetic starts under the later reads, as the compiler's code did:
+// behind one lgkmcnt(0) the statement gained 0.4 - 0.5 ms on the bench scenes, staged 0.6 - 0.9 (profiles/syn_visit_speed.txt).
+#ifndef EVPLP_SYN_INPLACE
+#define EVPLP_SYN_INPLACE 1
+#endif
+#define EV_SYN_VISIT_ASM_(TAIL)                                                                                                              \
+    asm volatile(                                                                                                                            \
+        "ds_read_b64 v[50:51], %[addr] offset:48\n\t"                                                                                 \
+        "ds_read_b128 v[52:55], %[addr]\n\t"                                                                                          \
+        "ds_read_b128 v[56:59], %[addr] offset:16\n\t"                                                                                \
+        "ds_read_b128 v[60:63], %[addr] offset:32\n\t"                                                                                \
+        "s_waitcnt lgkmcnt(3)\n\t"                                                                                                    \
+        "v_readfirstlane_b32 %[c0], v50\n\t"                                                                                          \
+        "v_readfirstlane_b32 %[c1], v51\n\t"                                                                                          \
+        "s_waitcnt lgkmcnt(2)\n\t"                                                                                                    \
+        "v_pk_fma_f32 v[52:53], v[52:53], %[pa], %[pd] op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\t"                                          \
+        "v_pk_fma_f32 v[54:55], v[54:55], %[pa], %[pd] op_sel:[0,1,1] op_sel_hi:[1,1,1]\n\t"                                          \
+        "s_waitcnt lgkmcnt(1)\n\t"                                                                                                    \
+        "v_pk_fma_f32 v[56:57], v[56:57], %[pb], %[pe] op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\t"                                          \
+        "v_pk_fma_f32 v[50:51], v[58:59], %[pb], v[52:53] op_sel:[0,1,0] op_sel_hi:[1,1,1] neg_lo:[0,1,0] neg_hi:[0,1,0]\n\t"         \
+        "v_pk_fma_f32 v[52:53], v[58:59], %[pb], v[52:53] op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"                                       \
+        "s_waitcnt lgkmcnt(0)\n\t"                                                                                                    \
+        "v_pk_fma_f32 v[58:59], v[60:61], %[pc], v[54:55] op_sel:[0,0,0] op_sel_hi:[1,0,1] neg_lo:[0,1,0] neg_hi:[0,1,0]\n\t"                \
+        "v_pk_fma_f32 v[54:55], v[60:61], %[pc], v[54:55] op_sel:[0,0,0] op_sel_hi:[1,0,1]\n\t"                                              \
+        "v_pk_fma_f32 v[60:61], v[62:63], %[pc], v[56:57] op_sel:[0,1,0] op_sel_hi:[1,1,1] neg_lo:[0,1,0] neg_hi:[0,1,0]\n\t"                \
+        "v_pk_fma_f32 v[56:57], v[62:63], %[pc], v[56:57] op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"                                              \
+        "v_max3_f32 v50, v50, v58, v60 clamp\n\t"                                                                                            \
+        "v_min3_f32 v52, v52, v54, v56 clamp\n\t"                                                                                            \
+        "v_max3_f32 v51, v51, v59, v61 clamp\n\t"                                                                                            \
+        "v_min3_f32 v53, v53, v55, v57 clamp\n\t"                                                                                            \
+        "v_cmp_lt_f32 vcc, v50, v52\n\t"                                                                                                     \
+        "v_cmp_lt_f32 %[m1], v51, v53\n\t"                                                                                                   \
+        EV_VISIT_DECIDE_TEXT("%[c0]", "%[c1]", "%[m1]", "%[t64]", "%[p0]", "%[p1]")                                                          \
+        TAIL                                                                                                                                 \
+        : [cur] "+s"(cur), [sp] "+s"(sp), [vstack] "+v"(vstack), [m1] "=&s"(m1_), [t64] "=&s"(t64_), [p0] "=&s"(p0_), [p1] "=&s"(p1_),         \
+          [c0] "=&s"(c0_), [c1] "=&s"(c1_)                                                                                                   \
+        : [addr] "v"(syn_addr_), [pa] "v"(pa_), [pb] "v"(pb_), [pc] "v"(pc_), [pd] "v"(pd_), [pe] "v"(pe_)                                   \
+        : "vcc", "scc", "m0", "memory", "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63")
 
 // The walk below one entry (the root, or what a synthetic node let in) as ONE hand-written statement (EVPLP_LEAF_ASM=0: the compiler's loop
 // around the node visit and its leaf step around tri_pair_any, as before).  What the compiler made of the leaf step was 43 vector
@@ -750,10 +811,10 @@ struct WalkStats { uint32_t nodes, leaves, pairs, exact; int32_t hit_leaf; uint3
           "s52", "s53", "s54", "s55", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s65", "s31")
 
 // EV_PAIR_TEXT on its own, for evplp_selftest(2): the two hit masks of one pair for the wave's 64 directions (the kernel keeps
-// v[VT:VT+11] free with amdgpu_num_vgpr(VT), as the walks do)
+// v[VT:VT+11] free with amdgpu_num_vgpr, as the walks do)
 template <int VT>
 EV_DEV void pair_hits_asm(const PairOps &P_, V3 o, V3 d, float tmin, float tmax, unsigned long long &hit_a, unsigned long long &hit_b) {
-    static_assert(VT == 52 || VT == 116, "reserved temporaries: v[52:63] or v[116:127]");
+    static_assert(VT == 52 || VT == 116, "reserved temporaries: v[52:63] (of the reserved v[50:63]) or v[116:127]");
     v2f ra_, rb_, rc_;
     ra_.x = d.x; ra_.y = d.y; rb_.x = d.z; rb_.y = o.x; rc_.x = o.y; rc_.y = o.z;
 #define EV_PAIR_ALONE(T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H)                                    \
@@ -819,7 +880,7 @@ EV_DEV bool occluded_wave(const char *node_base, const char *leaf_base, V3 o, V3
     int32_t cur = 0;  // root is always an inner node
 #if EVPLP_WALK_ASM && !EVPLP_TRAVERSAL_STATS
     if constexpr (VT != 0) {
-        static_assert(VT == 52 || VT == 116, "reserved temporaries: v[52:63] or v[116:127]");
+        static_assert(VT == 52 || VT == 116, "reserved temporaries: v[52:63] (of the reserved v[50:63]) or v[116:127]");
         const int lane_id = (int)(threadIdx.x & 63u);
         v2f pa_, pb_, pc_, pd_, pe_;
         pa_.x = ivx.x; pa_.y = ivy.x; pb_.x = ivz.x; pb_.y = avx.x; pc_.x = avy.x; pc_.y = avz.x;
@@ -845,6 +906,16 @@ EV_DEV bool occluded_wave(const char *node_base, const char *leaf_base, V3 o, V3
         for (;;) {
             if constexpr (CUT) {
                 if (cut_off >= cut_end) break;       // (also: the walk statement moved cut_off past every end when the last live lane was occluded)
+#if EVPLP_SYN_INPLACE
+                if constexpr (VT == 52) {
+                    // the synthetic node straight from the slot's LDS copy into the visit's registers (EV_SYN_VISIT_ASM_)
+                    const uint32_t syn_addr_ = lds_offset(cut_lds) + (cut_off << 6);
+                    cut_off++;
+                    unsigned long long m1_, t64_; int32_t p0_, p1_, c0_, c1_;
+                    EV_SYN_VISIT_ASM_("");
+                } else
+#endif
+                {
                 // the synthetic node from the slot's LDS copy, as below
                 v16i syn;
                 {
@@ -859,6 +930,7 @@ EV_DEV bool occluded_wave(const char *node_base, const char *leaf_base, V3 o, V3
                 }
                 cut_off++;
                 EV_VISIT(syn)
+                }
             }
             EV_WALK_LOOP        // ... until cur == kNoChild: nothing left below this entry, or no live lane left (then the cut is at its end too)
             if constexpr (!CUT) break;

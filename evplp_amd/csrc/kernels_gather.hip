@@ -252,7 +252,7 @@ EV_DEV void item_cost_add(const GatherArgs &a, int ty, unsigned long long t0, in
 }
 template <bool CUT, bool COST = false, bool ADAPT = false>
 #if EVPLP_WALK_ASM && !EVPLP_TRAVERSAL_STATS
-__attribute__((amdgpu_num_vgpr(52)))      // v[52:63] belong to the hand-written node visit (device_common.hpp)
+__attribute__((amdgpu_num_vgpr(50)))      // v[50:63] belong to the hand-written node visits (device_common.hpp: v[52:63] the temporaries, v[50:51] the spare pair of the in-place one)
 #endif
 __global__ __launch_bounds__(64, EVPLP_GATHER_WAVES) void gather_vpl_kernel(GatherArgs a, AdaptArgs ad) {
     unsigned long long t_cost = 0ull;
@@ -836,7 +836,7 @@ EV_DEV int launch_tile(const GatherArgs &a) { return item_index<true>(a, (int)bl
 
 template <bool CUT, bool COST = false, bool ADAPT = false>
 #if EVPLP_WALK_ASM && !EVPLP_TRAVERSAL_STATS
-__attribute__((amdgpu_num_vgpr(52)))      // v[52:63] belong to the hand-written node visit (device_common.hpp)
+__attribute__((amdgpu_num_vgpr(50)))      // v[50:63] belong to the hand-written node visits (device_common.hpp: v[52:63] the temporaries, v[50:51] the spare pair of the in-place one)
 #endif
 __global__ __launch_bounds__(64, EVPLP_GATHER_WAVES) void gather_vsl_walk_kernel(GatherArgs a, AdaptArgs ad) {
     unsigned long long t_cost = 0ull;

@@ -132,9 +132,120 @@ template <int VT> EV_DEV void selftest_pair_body(const PairTestRec *recs, unsign
         atomicAdd(&out[3 + cls / 2u], hits << (32u * (cls & 1u)));
     }
 }
-// (the attribute takes a literal: one kernel per register layout, as the walks have)
-__attribute__((amdgpu_num_vgpr(52))) __global__ __launch_bounds__(64) void selftest_pair52_kernel(const PairTestRec *recs, unsigned long long *out) { selftest_pair_body<52>(recs, out); }
+// (the attribute takes a literal: one kernel per register layout, as the walks have -- v[50:63] and v[116:127])
+__attribute__((amdgpu_num_vgpr(50))) __global__ __launch_bounds__(64) void selftest_pair52_kernel(const PairTestRec *recs, unsigned long long *out) { selftest_pair_body<52>(recs, out); }
 __attribute__((amdgpu_num_vgpr(116))) __global__ __launch_bounds__(64) void selftest_pair116_kernel(const PairTestRec *recs, unsigned long long *out) { selftest_pair_body<116>(recs, out); }
+
+// which = 3: the in-place visit of a synthetic node (device_common.hpp EV_SYN_VISIT_ASM_: the node read from LDS into the visit's own
+// registers) against the scalar-operand visit EV_WALK_VISIT_ASM on the same node and rays: kSynTestNodes nodes x 64 rays that share their
+// origin (as the lanes of a gather wave do), generated here from a fixed seed, in six classes (node index mod 6):
+//   0 random boxes around random segments                          3 child 0 ends exactly at a segment end point: its face in the plane
+//   1 the second entry absent, as the cut kernel writes an odd       of the shared origin, or of the end points (which then share their x):
+//     count: reference kNoChild, centre 0, half-size -3e38           entry == exit after the clamp, not entered from that side
+//   2 as 0, a quarter of the lanes dead (+inf origin terms)        4 child 0 with zero half-sizes (a point, or flat in x)
+//                                                                  5 as 0, coordinates scaled by 1e-15, 1e-12, 1e12, 1e15
+// Where a class shapes child 0, child 1 is a box of class 0.  Every visit starts from a stack of (node index mod 4) entries in a register
+// whose 64 lanes all differ, so that a wrong push, pop or stack pointer shows.  Compared: both entered-lane masks, the next node
+// reference, the stack pointer and the stack register (all 64 lanes: the pushed entry and everything a push must leave alone).
+// out[0] differences (mask bits + references + stack pointers + stack lanes), out[1] cases (lanes x children), out[2] entered lanes x
+// children (the reference visit's), out[3] / [4] / [5] = entered of classes 0 | 1 << 32, 2 | 3 << 32, 4 | 5 << 32.
+constexpr uint32_t kSynTestNodes = 4096u;
+struct SynTestRec { float node[12]; int32_t c0, c1; uint32_t pad0[2]; float o[3], q[3], spread; uint32_t cls, flat_x, sp0; uint32_t pad1[6]; };   // 128 bytes
+static_assert(sizeof(SynTestRec) == 128, "SynTestRec");
+__global__ __launch_bounds__(64) void selftest_syn_gen_kernel(SynTestRec *recs) {
+    const uint32_t node = blockIdx.x * 64u + threadIdx.x;
+    if (node >= kSynTestNodes) return;
+    SynTestRec r = {};
+    const uint32_t cls = node % 6u, odd = (node / 6u) & 1u;
+    uint64_t st = 0xc07ull * 0x10001ull + node;
+    float S = 1.0f;
+    if (cls == 5u) { const float sc[4] = { 1e-15f, 1e-12f, 1e12f, 1e15f }; S = sc[(node / 6u) & 3u]; }
+    float o[3], q[3];
+    // (multiples of 1/64: the faces of class 3 are then exact sums)
+    for (int k = 0; k < 3; k++) { o[k] = floorf((4.0f * pt_uniform(st) - 2.0f) * 64.0f) * (1.0f / 64.0f) * S; q[k] = floorf((4.0f * pt_uniform(st) - 2.0f) * 64.0f) * (1.0f / 64.0f) * S; }
+    for (int e = 0; e < 2; e++) {
+        // a box about a point of the segment origin -> target centre, off it by up to 0.2, half-sizes 0.1 .. 0.5; the targets of the 64
+        // lanes spread over +-1 about the centre: a third to a half of the lanes pass through it
+        const float along = 0.2f + 0.6f * pt_uniform(st);
+        for (int k = 0; k < 3; k++) {
+            r.node[2 * k + e] = o[k] + along * (q[k] - o[k]) + (pt_uniform(st) - 0.5f) * 0.4f * S;
+            r.node[6 + 2 * k + e] = (0.1f + 0.4f * pt_uniform(st)) * S;
+        }
+    }
+    r.c0 = (node & 1u) ? ~(int32_t)(node * 4u + 1u) : (int32_t)(node * 2u + 1u);       // (a leaf reference or a node index: the visit only passes them on)
+    r.c1 = (int32_t)(node * 2u + 2u);
+    if (cls == 1u) { r.c1 = kNoChild; for (int k = 0; k < 3; k++) { r.node[2 * k + 1] = 0.0f; r.node[6 + 2 * k + 1] = -3.0e38f; } }
+    if (cls == 3u) {
+        // x: [o.x - 1/2, o.x] (behind the origin of a lane that looks along +x) or [q.x, q.x + 1/2] (beyond its end point); y, z: wide
+        const float *at = odd ? q : o;
+        r.node[0] = odd ? q[0] + 0.25f : o[0] - 0.25f; r.node[6] = 0.25f;
+        for (int k = 1; k < 3; k++) { r.node[2 * k] = at[k]; r.node[6 + 2 * k] = 4.0f; }
+        r.flat_x = odd;
+    }
+    if (cls == 4u) { r.node[6] = 0.0f; if (!odd) { r.node[8] = 0.0f; r.node[10] = 0.0f; } }
+    for (int k = 0; k < 3; k++) { r.o[k] = o[k]; r.q[k] = q[k]; }
+    r.spread = 2.0f * S; r.cls = cls; r.sp0 = node & 3u;
+    recs[node] = r;
+}
+__attribute__((amdgpu_num_vgpr(50))) __global__ __launch_bounds__(64) void selftest_syn_kernel(const SynTestRec *recs, unsigned long long *out) {
+    __shared__ float4 s_node[4];
+    const uint32_t node = blockIdx.x, lane = threadIdx.x & 63u;
+    if (lane < 16u) reinterpret_cast<int32_t *>(s_node)[lane] = reinterpret_cast<const int32_t *>(recs)[node * 32u + lane];
+    __syncthreads();
+    v16i N, b;
+    sload16x2(recs, node * (uint32_t)sizeof(SynTestRec), N, b);
+    const V3 o = v3(f_of(b[0]), f_of(b[1]), f_of(b[2])), q = v3(f_of(b[3]), f_of(b[4]), f_of(b[5]));
+    const float spread = f_of(b[6]);
+    const uint32_t cls = (uint32_t)b[7], flat_x = (uint32_t)b[8];
+    const int sp0 = b[9];
+    // this lane's ray: from the shared origin to its own target about q
+    uint64_t st = 0xa11ull * 0x10001ull + (uint64_t)node * 64u + lane;
+    const float ux = pt_uniform(st) - 0.5f, uy = pt_uniform(st) - 0.5f, uz = pt_uniform(st) - 0.5f;
+    const V3 d = v3((q.x + (flat_x ? 0.0f : spread * ux)) - o.x, (q.y + spread * uy) - o.y, (q.z + spread * uz) - o.z);
+    st = splitmix64(st);
+    const bool alive_lane = !(cls == 2u && (st >> 62) == 0ull);
+    // the ray constants as occluded_wave sets them up
+    const float tmin = 0.0001f, tmax = 1.0f - 0.0001f;
+    const V3 inv0 = v3(safe_rcp(d.x), safe_rcp(d.y), safe_rcp(d.z));
+    const float ku = 1.0f / (tmax - tmin);
+    const V3 inv = inv0 * ku;
+    const float dead = __builtin_inff();
+    v2f pa_, pb_, pc_, pd_, pe_;
+    pa_.x = inv.x; pa_.y = inv.y; pb_.x = inv.z; pb_.y = fabsf(inv.x); pc_.x = fabsf(inv.y); pc_.y = fabsf(inv.z);
+    pd_.x = alive_lane ? (-(o.x * inv0.x) - tmin) * ku : dead; pd_.y = alive_lane ? (-(o.y * inv0.y) - tmin) * ku : dead;
+    pe_.x = alive_lane ? (-(o.z * inv0.z) - tmin) * ku : dead; pe_.y = pe_.x;
+    const int lane_id = (int)lane;
+    const int vstack0 = 0x01000000 + (int)(node * 64u + lane);
+    // the reference: the node in scalar registers (the first mask is copied out of vcc into the dead temporary pair)
+    unsigned long long ref_m0, ref_m1; int32_t ref_cur; int ref_sp, ref_stack;
+    {
+        const v2f cx_ = pk(N[0], N[1]), cy_ = pk(N[2], N[3]), cz_ = pk(N[4], N[5]), hx_ = pk(N[6], N[7]), hy_ = pk(N[8], N[9]), hz_ = pk(N[10], N[11]);
+        const int32_t c0_ = N[12], c1_ = N[13];
+        unsigned long long m1_, t64_; int32_t p0_, p1_;
+        int32_t cur = 0; int sp = sp0, vstack = vstack0;
+        EV_WALK_VISIT_ASM_("s", "s_mov_b64 %[t64], vcc\n", "v[52:53]", "v[54:55]", "v[56:57]", "v[58:59]", "v[60:61]", "v[62:63]", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63");
+        ref_m0 = t64_; ref_m1 = m1_; ref_cur = cur; ref_sp = sp; ref_stack = vstack;
+    }
+    // the subject: the node from LDS, in place
+    unsigned long long got_m0, got_m1; int32_t got_cur; int got_sp, got_stack;
+    {
+        const uint32_t syn_addr_ = lds_offset(&s_node[0]);
+        unsigned long long m1_, t64_; int32_t p0_, p1_, c0_, c1_;
+        int32_t cur = 0; int sp = sp0, vstack = vstack0;
+        EV_SYN_VISIT_ASM_("s_mov_b64 %[t64], vcc\n");
+        got_m0 = t64_; got_m1 = m1_; got_cur = cur; got_sp = sp; got_stack = vstack;
+    }
+    const unsigned long long stack_bad = ballot64(got_stack != ref_stack);
+    if (lane == 0u) {
+        const unsigned long long bad = (unsigned long long)(__builtin_popcountll(got_m0 ^ ref_m0) + __builtin_popcountll(got_m1 ^ ref_m1) + __builtin_popcountll(stack_bad)) +
+                                       (got_cur != ref_cur ? 1ull : 0ull) + (got_sp != ref_sp ? 1ull : 0ull);
+        const unsigned long long entered = (unsigned long long)(__builtin_popcountll(ref_m0) + __builtin_popcountll(ref_m1));
+        if (bad) atomicAdd(&out[0], bad);
+        atomicAdd(&out[1], 128ull);
+        atomicAdd(&out[2], entered);
+        atomicAdd(&out[3 + cls / 2u], entered << (32u * (cls & 1u)));
+    }
+}
 
 // evplp_debug_ev_math: ev_math.h's functions AS THE DEVICE COMPUTES THEM, on the caller's inputs.  The light-tracing records are compared with
 // the oracle's byte for byte, and the oracle #includes the same header: that comparison vouches for the walk and the draw order, not for
@@ -170,7 +281,7 @@ extern "C" int evplp_debug_ev_math(evplp_context *c, int32_t which, const float 
 }
 
 extern "C" int evplp_selftest(evplp_context *c, int32_t which, uint64_t *out, int32_t capacity) {
-    if (!c || !out || capacity < 6 || which < 0 || which > 2) { if (c) c->set_error("evplp_selftest: bad arguments"); return EVPLP_ERR_INVALID; }
+    if (!c || !out || capacity < 6 || which < 0 || which > 3) { if (c) c->set_error("evplp_selftest: bad arguments"); return EVPLP_ERR_INVALID; }
     if (hipSetDevice(c->cfg.device) != hipSuccess) return EVPLP_ERR_HIP;
     unsigned long long *d = nullptr;
     if (hipMalloc((void **)&d, 8 * sizeof(unsigned long long)) != hipSuccess) return EVPLP_ERR_OOM;
@@ -179,7 +290,16 @@ extern "C" int evplp_selftest(evplp_context *c, int32_t which, uint64_t *out, in
     if (e == hipSuccess) {
         if (which == 0) hipLaunchKernelGGL(evplp::selftest_rcp_kernel, dim3(4096), dim3(256), 0, c->stream, d);
         else if (which == 1) hipLaunchKernelGGL(evplp::selftest_pow_kernel, dim3(4096), dim3(256), 0, c->stream, d);
-        else {
+        else if (which == 3) {
+            evplp::SynTestRec *recs = nullptr;
+            e = hipMalloc((void **)&recs, sizeof(evplp::SynTestRec) * evplp::kSynTestNodes);
+            if (e == hipSuccess) {
+                hipLaunchKernelGGL(evplp::selftest_syn_gen_kernel, dim3(evplp::kSynTestNodes / 64u), dim3(64), 0, c->stream, recs);
+                hipLaunchKernelGGL(evplp::selftest_syn_kernel, dim3(evplp::kSynTestNodes), dim3(64), 0, c->stream, recs, d);
+                e = hipStreamSynchronize(c->stream);
+                hipFree(recs);
+            }
+        } else {
             evplp::PairTestRec *recs = nullptr;
             e = hipMalloc((void **)&recs, sizeof(evplp::PairTestRec) * evplp::kPairTestPairs);
             if (e == hipSuccess) {

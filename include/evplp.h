@@ -601,6 +601,12 @@ int evplp_accel_stack_entries(const evplp_context *ctx);
  * rays in the plane; denormal denominators; an all-zero second triangle; coordinates at 1e-15 .. 1e15), for both register layouts:
  * out[0] lanes x triangles whose hit bit differs (must be 0), [1] cases, [2] hits, [3] / [4] / [5] hits of classes 0 and 1, 2 and 3,
  * 4 and 5 (the odd class in the upper 32 bits).
+ * which = 3: the in-place visit of a synthetic node of an entry cut (the node read from LDS into the visit's own registers) against
+ * the scalar-operand node visit on 4096 generated nodes x 64 rays with a common origin in six classes (random boxes around random
+ * segments; an absent second entry, as the cut kernel writes an odd count; dead lanes among live ones; a box that ends exactly at a
+ * segment end point; zero half-sizes; coordinates at 1e-15 .. 1e15): out[0] differences in the two entered-lane masks, the next
+ * node, the stack pointer and the stack register (must be 0), [1] cases (lanes x children), [2] entered lanes x children of the
+ * scalar-operand visit, [3] / [4] / [5] those of classes 0 and 1, 2 and 3, 4 and 5 (the odd class in the upper 32 bits).
  * Returns the number of words written or a negative status. */
 int evplp_selftest(evplp_context *ctx, int32_t which, uint64_t *out, int32_t capacity);
 /* The direction-sampling functions of light tracing (csrc/ev_math.h: evm_sincosf, evm_powf) as the DEVICE computes them, on host arrays of n

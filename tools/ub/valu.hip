@@ -4,17 +4,19 @@
 // time of the launch (what a kernel pays), the clock the chip held inside the loop (s_memtime ticks / s_memrealtime ticks x 100 MHz,
 // median over workgroups: the chip lowers its clock under load, by instruction mix) and their product, cycles per wave-instruction.
 //   hipcc --offload-arch=gfx950 -O3 -o tools/ub/valu tools/ub/valu.hip && tools/ub/valu > profiles/ub_valu_r04.txt
+//   tools/ub/valu lanemoves > profiles/ub_valu_lanemoves.txt      (only v_readfirstlane_b32 / v_readlane_b32, with v_pk_fma_f32 beside them)
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdio>
+#include <string>
 #include <vector>
 typedef float v2f __attribute__((ext_vector_type(2)));
 
-enum { FMA, PK_FMA, PK_FMA_OPSEL, PK_MUL, MAX3, MAX3_CLAMP, CMP_VCC, CMP_SGPR, EXP, LOG, RCP, MOV, WRITELANE, MIX_VISIT, MUL_LO_U32, MAD_U64_U32, MUL_F32, SQRT, SIN, ALIGNBIT, NMODES };
+enum { FMA, PK_FMA, PK_FMA_OPSEL, PK_MUL, MAX3, MAX3_CLAMP, CMP_VCC, CMP_SGPR, EXP, LOG, RCP, MOV, WRITELANE, MIX_VISIT, MUL_LO_U32, MAD_U64_U32, MUL_F32, SQRT, SIN, ALIGNBIT, READFIRSTLANE, READLANE, NMODES };
 static const char *kNames[NMODES] = { "v_fma_f32", "v_pk_fma_f32", "v_pk_fma_f32 op_sel", "v_pk_mul_f32", "v_max3_f32", "v_max3_f32 clamp", "v_cmp_lt_f32 vcc",
                                       "v_cmp_lt_f32 s[..]", "v_exp_f32", "v_log_f32", "v_rcp_f32", "v_mov_b32", "v_writelane_b32", "node visit (9 pk_fma + 4 max3/min3 + 2 cmp)",
-                                      "v_mul_lo_u32", "v_mad_u64_u32", "v_mul_f32", "v_sqrt_f32", "v_sin_f32", "v_alignbit_b32" };
-static const int kPerIter[NMODES] = { 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 60, 64, 64, 64, 64, 64, 64 };
+                                      "v_mul_lo_u32", "v_mad_u64_u32", "v_mul_f32", "v_sqrt_f32", "v_sin_f32", "v_alignbit_b32", "v_readfirstlane_b32", "v_readlane_b32 (constant lane)" };
+static const int kPerIter[NMODES] = { 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 60, 64, 64, 64, 64, 64, 64, 64, 64 };
 
 #define R8(OP) OP(0) OP(1) OP(2) OP(3) OP(4) OP(5) OP(6) OP(7)
 template <int MODE> __global__ __launch_bounds__(256) void k(float *out, unsigned long long *cyc, float a, float b, int iters) {
@@ -22,6 +24,7 @@ template <int MODE> __global__ __launch_bounds__(256) void k(float *out, unsigne
     for (int j = 0; j < 8; j++) { x[j] = threadIdx.x + j; p[j].x = x[j]; p[j].y = x[j] + 0.5f; q[j] = threadIdx.x * 77u + j; }
     v2f pa = { a, a * 1.5f }, pb = { b, b * 0.5f };
     unsigned long long sg = 0;
+    int sl[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };      // (lane-to-scalar moves: eight destinations of their own)
     const unsigned long long r0 = __builtin_amdgcn_s_memrealtime();
     const unsigned long long t0 = __builtin_amdgcn_s_memtime();
     for (int i = 0; i < iters; i++) {
@@ -99,6 +102,10 @@ template <int MODE> __global__ __launch_bounds__(256) void k(float *out, unsigne
 #define OP(j) asm volatile("v_alignbit_b32 %0, %0, %0, %1" : "+v"(x[j]) : "v"(a));
                 R8(OP)
 #undef OP
+            } else if (MODE == READFIRSTLANE) {      // (one statement for the eight: between statements the compiler pads every lane-to-scalar move with an s_nop)
+                asm volatile("v_readfirstlane_b32 %0, %8\n\tv_readfirstlane_b32 %1, %9\n\tv_readfirstlane_b32 %2, %10\n\tv_readfirstlane_b32 %3, %11\n\tv_readfirstlane_b32 %4, %12\n\tv_readfirstlane_b32 %5, %13\n\tv_readfirstlane_b32 %6, %14\n\tv_readfirstlane_b32 %7, %15" : "=s"(sl[0]), "=s"(sl[1]), "=s"(sl[2]), "=s"(sl[3]), "=s"(sl[4]), "=s"(sl[5]), "=s"(sl[6]), "=s"(sl[7]) : "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]), "v"(x[4]), "v"(x[5]), "v"(x[6]), "v"(x[7]));
+            } else if (MODE == READLANE) {
+                asm volatile("v_readlane_b32 %0, %8, 5\n\tv_readlane_b32 %1, %9, 5\n\tv_readlane_b32 %2, %10, 5\n\tv_readlane_b32 %3, %11, 5\n\tv_readlane_b32 %4, %12, 5\n\tv_readlane_b32 %5, %13, 5\n\tv_readlane_b32 %6, %14, 5\n\tv_readlane_b32 %7, %15, 5" : "=s"(sl[0]), "=s"(sl[1]), "=s"(sl[2]), "=s"(sl[3]), "=s"(sl[4]), "=s"(sl[5]), "=s"(sl[6]), "=s"(sl[7]) : "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]), "v"(x[4]), "v"(x[5]), "v"(x[6]), "v"(x[7]));
             } else if (MODE == WRITELANE) {
                 int sp = (i + u) & 63, val = i;
 #define OP(j) asm volatile("s_mov_b32 m0, %1\n\tv_writelane_b32 %0, %2, m0" : "+v"(x[j]) : "s"(sp), "s"(val) : "m0");
@@ -135,7 +142,7 @@ template <int MODE> __global__ __launch_bounds__(256) void k(float *out, unsigne
     const unsigned long long t1 = __builtin_amdgcn_s_memtime();
     const unsigned long long r1 = __builtin_amdgcn_s_memrealtime();
     float s = (float)(sg & 1);
-    for (int j = 0; j < 8; j++) s += x[j] + p[j].x + p[j].y + (float)(q[j] & 0xffull);
+    for (int j = 0; j < 8; j++) s += x[j] + p[j].x + p[j].y + (float)(q[j] & 0xffull) + (float)(sl[j] & 1);
     out[blockIdx.x * 256 + threadIdx.x] = s;
     if (threadIdx.x == 0) { cyc[2 * blockIdx.x] = t1 - t0; cyc[2 * blockIdx.x + 1] = r1 - r0; }
 }
@@ -159,12 +166,14 @@ template <int MODE> void run(int waves_per_simd, FILE *f) {
     hipFree(out); hipFree(cyc);
 }
 template <int M> void all(FILE *f) { for (int w : { 1, 2, 4, 8 }) run<M>(w, f); std::fprintf(f, "\n"); }
-int main() {
+int main(int argc, char **argv) {
     FILE *f = stdout;
     hipDeviceProp_t pr; hipGetDeviceProperties(&pr, 0);
     std::fprintf(f, "# %s, %d CUs, clockRate %d kHz; 256-thread workgroups, one per CU per wave-per-SIMD step; eight independent registers per lane\n", pr.gcnArchName, pr.multiProcessorCount, pr.clockRate);
+    if (argc > 1 && std::string(argv[1]) == "lanemoves") { all<READFIRSTLANE>(f); all<READLANE>(f); all<PK_FMA_OPSEL>(f); return 0; }      // (the packed fma beside them: same run, same clock regime)
     all<FMA>(f); all<PK_FMA>(f); all<PK_FMA_OPSEL>(f); all<PK_MUL>(f); all<MAX3>(f); all<MAX3_CLAMP>(f); all<CMP_VCC>(f); all<CMP_SGPR>(f);
     all<EXP>(f); all<LOG>(f); all<RCP>(f); all<MOV>(f); all<WRITELANE>(f); all<MIX_VISIT>(f);
     all<MUL_LO_U32>(f); all<MAD_U64_U32>(f); all<MUL_F32>(f); all<SQRT>(f); all<SIN>(f); all<ALIGNBIT>(f);
+    all<READFIRSTLANE>(f); all<READLANE>(f);
     return 0;
 }
