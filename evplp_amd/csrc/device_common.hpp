@@ -485,25 +485,6 @@ EV_DEV LeafOps fetch_leaf(const char *leaf_base, uint32_t leafref) {
     return L;
 }
 
-// ... in two steps (the any-hit walk): the first pair's 24 dwords, then -- after the first pair has been tested -- the second pair's.
-// All 48 dwords at once are what pushed the walk's scalar registers into VGPR lanes once the entry cuts took six more of them
-// (16 v_writelane + 24 v_readlane per two-pair leaf); the second fetch waits on its own, a latency the other waves of the SIMD cover.
-EV_DEV PairOps fetch_leaf_a(const char *leaf_base, uint32_t off, v16i &b) {
-    v16i a;
-    sload16x2(leaf_base, off, a, b);
-    PairOps A;
-    A.p0x = pk(a[0], a[1]); A.p0y = pk(a[2], a[3]); A.p0z = pk(a[4], a[5]); A.e0x = pk(a[6], a[7]); A.e0y = pk(a[8], a[9]); A.e0z = pk(a[10], a[11]);
-    A.e1x = pk(a[12], a[13]); A.e1y = pk(a[14], a[15]); A.e1z = pk(b[0], b[1]); A.nx = pk(b[2], b[3]); A.ny = pk(b[4], b[5]); A.nz = pk(b[6], b[7]);
-    return A;
-}
-EV_DEV PairOps fetch_leaf_b(const char *leaf_base, uint32_t off, const v16i &b) {
-    const v16i c = sload16(leaf_base, off + 128u);
-    PairOps B;
-    B.p0x = pk(b[8], b[9]); B.p0y = pk(b[10], b[11]); B.p0z = pk(b[12], b[13]); B.e0x = pk(b[14], b[15]); B.e0y = pk(c[0], c[1]); B.e0z = pk(c[2], c[3]);
-    B.e1x = pk(c[4], c[5]); B.e1y = pk(c[6], c[7]); B.e1z = pk(c[8], c[9]); B.nx = pk(c[10], c[11]); B.ny = pk(c[12], c[13]); B.nz = pk(c[14], c[15]);
-    return B;
-}
-
 // Stack-in-a-VGPR helpers: entry k of the wave's stack is lane k of one register.  A push is a
 // compare + select against the lane id (this clang has no v_writelane builtin), a pop is v_readlane
 // with a scalar lane index; neither touches memory.
@@ -531,18 +512,26 @@ struct WalkStats { uint32_t nodes, leaves, pairs, exact; int32_t hit_leaf; uint3
 // its vector pipe in this loop (a prefetch experiment that added six scalar instructions per visit cost 9 %) and the compiler
 // spends ~17 scalar instructions and 4-5 branches per visit on the decision alone (lane-mask booleans, s_cselect_b64 / s_and exec /
 // s_cbranch_vcc chains); this spends 6-9 and 2-3.  Inline-asm operands cannot name the halves of a register tuple: the node arrives
-// as seven 64-bit scalar operands (sub-registers of the 16-dword tuple the load fills), and the six packed temporaries live in FIXED
-// registers v[VT:VT+11], which the kernels that use this keep free with amdgpu_num_vgpr (VT = 52: v[50:63], amdgpu_num_vgpr(50) -- the pair
-// below the temporaries belongs to the in-place visit of a synthetic node, EV_SYN_VISIT_ASM_).  The nine per-lane ray constants ride
+// in fixed scalar registers (EV_WALK_LOOP_ASM names the sub-registers of the 16-dword tuple its load fills), and the six packed
+// temporaries live in FIXED registers too: v[52:63] of the v[50:63] that the walk kernels keep free with amdgpu_num_vgpr(50) -- the pair
+// below the temporaries belongs to the in-place visit of a synthetic node, EV_SYN_VISIT_ASM_.  The nine per-lane ray constants ride
 // in five register pairs -- {1/dx, 1/dy} {1/dz, |1/dx|} {|1/dy|, |1/dz|} {-ox/dx, -oy/dy} {-oz/dz, -} -- and op_sel / op_sel_hi
-// broadcast the wanted half to both children (the C++ loop keeps every constant in both halves of a pair of its own: 18 registers).
-// Same arithmetic and the same descent order (the child more lanes enter first) as the C++ loop below, which stays as the reference
-// implementation (EVPLP_WALK_ASM=0, and the counters build).  Afterwards cur is the next node, a leaf reference, or kNoChild when
+// broadcast the wanted half to both children (the C++ walk keeps every constant in both halves of a pair of its own: 18 registers).
+// Same arithmetic and the same descent order (the child more lanes enter first) as occluded_wave_ref below, the reference
+// implementation in C++ (EVPLP_WALK_ASM=0, and the counters build).  Afterwards cur is the next node, a leaf reference, or kNoChild when
 // nothing was entered and the stack was empty.
 #ifndef EVPLP_WALK_ASM
 #define EVPLP_WALK_ASM 1
 #endif
-#define EV_WALK_VISIT_ASM(T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H) EV_WALK_VISIT_ASM_("s", "", T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H)
+// the hand-written walk is what the kernels run (occluded_wave); otherwise the C++ one (occluded_wave_ref)
+constexpr bool kWalkAsm = EVPLP_WALK_ASM && !EVPLP_TRAVERSAL_STATS;
+// ... and then the walk kernels leave v[50:63] to its statements: amdgpu_num_vgpr(kWalkKernelVgprs), 0 = no limit of their own
+constexpr int kWalkKernelVgprs = kWalkAsm ? 50 : 0;
+// The names of the twelve temporaries, as six pairs and as their halves (low, high): the walk's, and a second layout in which
+// evplp_selftest(2) runs EV_PAIR_TEXT as well.  EV_WITH hands such a list to a statement macro as its last eighteen arguments.
+#define EV_TMP_52 "v[52:53]", "v[54:55]", "v[56:57]", "v[58:59]", "v[60:61]", "v[62:63]", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63"
+#define EV_TMP_116 "v[116:117]", "v[118:119]", "v[120:121]", "v[122:123]", "v[124:125]", "v[126:127]", "v116", "v117", "v118", "v119", "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127"
+#define EV_WITH(M, ...) M(__VA_ARGS__)
 // The descent decision that ends a visit: vcc / M1 = the lanes that enter child 0 / child 1 (C0 / C1: their references, scalar); T64, P0, P1
 // are scalar temporaries (P0 / P1 may be the halves of T64).  One text for both visits (EV_VISIT_TEXT, EV_SYN_VISIT_ASM_).
 #define EV_VISIT_DECIDE_TEXT(C0, C1, M1, T64, P0, P1) \
@@ -575,8 +564,8 @@ struct WalkStats { uint32_t nodes, leaves, pairs, exact; int32_t hit_leaf; uint3
         "s_nop 0\n\t" \
         "v_readlane_b32 %[cur], %[vstack], %[sp]\n" \
         "L_end%=:\n"
-// NC: where the node's six box operands live -- "s" (a node fetched with s_load) or "v" (a synthetic node of an entry cut, read from LDS
-// with one address for all lanes: the same value in every lane of a VGPR serves as well)
+// The visit's text.  CX .. HZ: the node's six box operands, register pairs -- scalar ones in the walk (a node fetched with s_load);
+// evplp_selftest(3) wraps the same text in a statement with operands to compare it with the in-place visit below.
 #define EV_VISIT_TEXT(CX, CY, CZ, HX, HY, HZ, C0, C1, M1, T64, P0, P1, T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H) \
         "v_pk_fma_f32 " T0 ", " CX ", %[pa], %[pd] op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\t" \
         "v_pk_fma_f32 " T1 ", " CY ", %[pa], %[pd] op_sel:[0,1,1] op_sel_hi:[1,1,1]\n\t" \
@@ -594,21 +583,10 @@ struct WalkStats { uint32_t nodes, leaves, pairs, exact; int32_t hit_leaf; uint3
         "v_cmp_lt_f32 vcc, " T3L ", " T0L "\n\t" \
         "v_cmp_lt_f32 " M1 ", " T3H ", " T0H "\n\t" \
         EV_VISIT_DECIDE_TEXT(C0, C1, M1, T64, P0, P1)
-// (TAIL: text behind the visit -- empty in the walks; evplp_selftest(3) copies the first mask out of vcc there)
-#define EV_WALK_VISIT_ASM_(NC, TAIL, T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H)                         \
-    asm volatile(                                                                                                                            \
-        EV_VISIT_TEXT("%[cx]", "%[cy]", "%[cz]", "%[hx]", "%[hy]", "%[hz]", "%[c0]", "%[c1]", "%[m1]", "%[t64]", "%[p0]", "%[p1]",           \
-                      T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H)                                    \
-        TAIL                                                                                                                                 \
-        : [cur] "+s"(cur), [sp] "+s"(sp), [vstack] "+v"(vstack), [m1] "=&s"(m1_), [t64] "=&s"(t64_), [p0] "=&s"(p0_), [p1] "=&s"(p1_)          \
-        : [cx] NC(cx_), [cy] NC(cy_), [cz] NC(cz_), [hx] NC(hx_), [hy] NC(hy_), [hz] NC(hz_), [c0] "s"(c0_), [c1] "s"(c1_),              \
-          [pa] "v"(pa_), [pb] "v"(pb_), [pc] "v"(pc_),                                     \
-          [pd] "v"(pd_), [pe] "v"(pe_), [lane] "v"(lane_id)                                                                 \
-        : "vcc", "scc", "m0", T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H)
 
-// The visit of a SYNTHETIC node of an entry cut, in place (EVPLP_SYN_INPLACE=0: the node goes from LDS through fourteen v_readfirstlane
-// into scalar registers and then through EV_WALK_VISIT_ASM like a fetched node -- twelve lane-to-scalar moves per visit for operands
-// v_pk_fma_f32 reads from vector registers just as well).  One statement that does its own LDS reads -- `addr` = the byte address of
+// The visit of a SYNTHETIC node of an entry cut, in place (through fourteen v_readfirstlane into scalar registers and then visited
+// like a fetched node it cost twelve lane-to-scalar moves per visit for operands v_pk_fma_f32 reads from vector registers just as
+// well: profiles/syn_visit_isa.txt, syn_visit_speed.txt).  One statement that does its own LDS reads -- `addr` = the byte address of
 // the node in the slot's LDS copy, the same in every lane, so every lane reads the same sixteen dwords -- straight into the visit's own
 // registers, BvhNode order:  v[52:53] cx  v[54:55] cy  v[56:57] cz  v[58:59] hx  v[60:61] hy  v[62:63] hz  v[50:51] the child references.
 // Only the references go to scalar registers (the descent decision selects between them); v[50:51] is then the one spare pair the
@@ -623,10 +601,8 @@ struct WalkStats { uint32_t nodes, leaves, pairs, exact; int32_t hit_leaf; uint3
 // the waits are staged -- lgkmcnt(3) the references, (2) cx cy, (1) cz hx, (0) hy hz; LDS answers in order, and a scalar load of the
 // compiler's still in flight only makes a wait longer -- so the arithmetic starts under the later reads, as the compiler's code did:
 // behind one lgkmcnt(0) the statement gained 0.4 - 0.5 ms on the bench scenes, staged 0.6 - 0.9 (profiles/syn_visit_speed.txt).
-#ifndef EVPLP_SYN_INPLACE
-#define EVPLP_SYN_INPLACE 1
-#endif
-#define EV_SYN_VISIT_ASM_(TAIL)                                                                                                              \
+// (TAIL: text behind the visit -- empty in the walk; evplp_selftest(3) copies the first mask out of vcc there)
+#define EV_SYN_VISIT_ASM_(TAIL)                                                                                                            \
     asm volatile(                                                                                                                            \
         "ds_read_b64 v[50:51], %[addr] offset:48\n\t"                                                                                 \
         "ds_read_b128 v[52:55], %[addr]\n\t"                                                                                          \
@@ -660,11 +636,10 @@ struct WalkStats { uint32_t nodes, leaves, pairs, exact; int32_t hit_leaf; uint3
         : [addr] "v"(syn_addr_), [pa] "v"(pa_), [pb] "v"(pb_), [pc] "v"(pc_), [pd] "v"(pd_), [pe] "v"(pe_)                                   \
         : "vcc", "scc", "m0", "memory", "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63")
 
-// The walk below one entry (the root, or what a synthetic node let in) as ONE hand-written statement (EVPLP_LEAF_ASM=0: the compiler's loop
-// around the node visit and its leaf step around tri_pair_any, as before).  What the compiler made of the leaf step was 43 vector
-// instructions and 6 s_nop per triangle pair, and about 108 scalar instructions and 17 branches of bookkeeping per leaf (~50 and 10 on the
-// commonest path: one pair, no hit, pop) -- loop-carried masks copied in front of every leaf and back behind it, lane-mask booleans for
-// every scalar decision.  Here:
+// The walk below one entry (the root, or what a synthetic node let in) as ONE hand-written statement.  What the compiler made of the leaf
+// step around tri_pair_any was 43 vector instructions and 6 s_nop per triangle pair, and about 108 scalar instructions and 17 branches
+// of bookkeeping per leaf (~50 and 10 on the commonest path: one pair, no hit, pop) -- loop-carried masks copied in front of every leaf
+// and back behind it, lane-mask booleans for every scalar decision (profiles/leaf_step_isa.txt, leaf_step_speed.txt).  Here:
 // * EV_PAIR_TEXT is tri_pair_test instruction for instruction -- the same operations in the same order with the same operand roles, so
 //   every result bit is the compiler's, the non-finite cases of the comment above tri_pair_test included -- with three differences that
 //   touch no value: the ray rides in three register pairs {dx, dy} {dz, ox} {oy, oz} whose halves op_sel / op_sel_hi broadcast to both
@@ -679,17 +654,14 @@ struct WalkStats { uint32_t nodes, leaves, pairs, exact; int32_t hit_leaf; uint3
 // * pair B of a three- or four-triangle leaf is neither fetched nor tested when pair A has occluded every live lane (any-hit).
 // Inline-asm operands cannot name the halves of a register tuple and a statement takes at most 30 operands, so the node / leaf tuples and
 // the scalar temporaries are FIXED registers s31 and s[32:65], named in the clobber list (the compiler's loop held 32 scalar registers of tuples
-// and about eight of temporaries across the same code); the vector temporaries are v[VT:VT+11] as for the node visit.
+// and about eight of temporaries across the same code); the vector temporaries are v[52:63] as for the node visit.
 //   s[32:47] node, or leaf dwords 0-15, then 32-47    s[48:63] leaf dwords 16-31    s[64:65] the leaf's hit mask; popcounts of a visit
 //   s31 byte offset
 // (the second mask of a visit forms in the node's two padding dwords, the hit masks of a pair's triangles in the registers of its own
 // p0x / p0y, dead by then; vcc holds what lives for two instructions).  .sgpr_count stays below 81: from there on one wave per SIMD
 // fewer is resident.  Where the block sits decides what the allocator parks in VGPR lanes around it (tests/test_adaptive_resources.py
-// holds the adaptive variants to the defaults' counts): at s32 all four walk kernels park fewer than before and the adaptive ones
-// no more than their defaults; four registers lower or higher one of them parks one or two more.
-#ifndef EVPLP_LEAF_ASM
-#define EVPLP_LEAF_ASM 1
-#endif
+// holds the adaptive variants to the defaults' counts): at s32 all four walk kernels park fewer than around the compiler's loop and the
+// adaptive ones no more than their defaults; four registers lower or higher one of them parks one or two more.
 #define EV_PAIR_TEXT(P0X, P0Y, P0Z, E0X, E0Y, E0Z, E1X, E1Y, E1Z, NX, NY, NZ, HA, HB, T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H) \
         "v_pk_mul_f32 " T0 ", " NX ", %[ra] op_sel:[0,0] op_sel_hi:[1,0]\n\t"                                                                \
         "v_pk_add_f32 " T1 ", " P0X ", %[rb] op_sel:[0,1] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]\n\t"                                     \
@@ -798,12 +770,12 @@ struct WalkStats { uint32_t nodes, leaves, pairs, exact; int32_t hit_leaf; uint3
         "s_branch L_leaf%=\n"                                                                                                                \
         "L_alldead%=:\n\t"                                                                                                                   \
         "s_mov_b32 %[sp], 0\n\t"                                                                                                             \
-        "s_mov_b32 %[coff], -1\n"                                                                                                           \
+        "s_mov_b32 %[syn], -1\n"                                                                                                             \
         "L_empty%=:\n\t"                                                                                                                     \
         "s_brev_b32 %[cur], 1\n"                                                                                                             \
         "L_done%=:\n"                                                                                                                      \
         : [cur] "+s"(cur), [sp] "+s"(sp), [vstack] "+v"(vstack), [alive] "+s"(alive), [pd] "+v"(pd_), [pe] "+v"(pe_),     \
-          [coff] "+s"(cut_off)                                                                                                               \
+          [syn] "+s"(syn)                                                                                                                    \
         : [nodes] "s"(node_base), [leaves] "s"(leaf_base), [pa] "v"(pa_), [pb] "v"(pb_), [pc] "v"(pc_),                                      \
           [ra] "v"(ra_), [rb] "v"(rb_), [rc] "v"(rc_), [tmin] "s"(tmin), [tmax] "s"(tmax)                                                    \
         : "vcc", "scc", "m0", "memory", T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H,                                          \
@@ -811,7 +783,7 @@ struct WalkStats { uint32_t nodes, leaves, pairs, exact; int32_t hit_leaf; uint3
           "s52", "s53", "s54", "s55", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s65", "s31")
 
 // EV_PAIR_TEXT on its own, for evplp_selftest(2): the two hit masks of one pair for the wave's 64 directions (the kernel keeps
-// v[VT:VT+11] free with amdgpu_num_vgpr, as the walks do)
+// v[VT:VT+11] free with amdgpu_num_vgpr, as the walk kernels do)
 template <int VT>
 EV_DEV void pair_hits_asm(const PairOps &P_, V3 o, V3 d, float tmin, float tmax, unsigned long long &hit_a, unsigned long long &hit_b) {
     static_assert(VT == 52 || VT == 116, "reserved temporaries: v[52:63] (of the reserved v[50:63]) or v[116:127]");
@@ -826,18 +798,75 @@ EV_DEV void pair_hits_asm(const PairOps &P_, V3 o, V3 d, float tmin, float tmax,
           [e1x] "s"(P_.e1x), [e1y] "s"(P_.e1y), [e1z] "s"(P_.e1z), [nx] "s"(P_.nx), [ny] "s"(P_.ny), [nz] "s"(P_.nz),                        \
           [ra] "v"(ra_), [rb] "v"(rb_), [rc] "v"(rc_), [tmin] "s"(tmin), [tmax] "s"(tmax)                                                    \
         : "vcc", "scc", T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H)
-    if constexpr (VT == 52) EV_PAIR_ALONE("v[52:53]", "v[54:55]", "v[56:57]", "v[58:59]", "v[60:61]", "v[62:63]", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63");
-    else EV_PAIR_ALONE("v[116:117]", "v[118:119]", "v[120:121]", "v[122:123]", "v[124:125]", "v[126:127]", "v116", "v117", "v118", "v119", "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127");
+    if constexpr (VT == 52) EV_WITH(EV_PAIR_ALONE, EV_TMP_52);
+    else EV_WITH(EV_PAIR_ALONE, EV_TMP_116);
 #undef EV_PAIR_ALONE
 }
 
-// VT = first of the twelve reserved temporaries: 52 for the 64-register VPL gather, 116 for the 128-register VSL gather; 0 = the C++ loop.
-// CUT: the walk starts from an entry cut (kernels.h CutArgs: `cut` points at the synthetic nodes of this (tile group, VPL), node 0
-// carries their count in its first padding word) instead of from the root: every synthetic node is visited like a node -- its two
-// children are cut entries with their boxes -- and whatever it lets in is walked to the end before the next one is fetched.
-template <int VT = 0, bool CUT = false>
-EV_DEV bool occluded_wave(const char *node_base, const char *leaf_base, V3 o, V3 d, float tmin, float tmax, bool alive_lane, WalkStats *ws = nullptr, const char *cut = nullptr, uint32_t cut_off = 0u,
-                          const float4 *cut_lds = nullptr) {
+// The packet walk the kernels run, made of the hand-written statements above (kWalkAsm; occluded_wave_ref below states the same walk in
+// C++).  Its kernels keep v[50:63] free (amdgpu_num_vgpr(kWalkKernelVgprs)).
+// CUT: the walk starts from an entry cut (kernels.h CutArgs) instead of from the root: `cut_lds` is the LDS copy of the slot of this
+// (tile group, VPL) -- its synthetic nodes, node 0 carries their count in its first padding word.  Every synthetic node is visited
+// like a node -- its two children are cut entries with their boxes -- and whatever it lets in is walked to the end before the next one
+// is visited.
+template <bool CUT>
+EV_DEV bool occluded_wave(const char *node_base, const char *leaf_base, V3 o, V3 d, float tmin, float tmax, bool alive_lane, const float4 *cut_lds, uint32_t syn0) {
+    // All control state is wave-uniform (SGPRs): `alive` is a 64-bit lane mask, `cur` the node reference, `sp` the stack pointer.
+    // Per-lane registers hold only the ray: 1/d and -o/d for the slab tests (in the segment's own parameter, see occluded_wave_ref;
+    // a lane without a live ray carries +inf as its origin term and never enters a box), d and o for the triangle pairs.
+    unsigned long long alive = ballot64(alive_lane);
+    if (alive == 0ull) return false;
+    // `syn` walks over the slot's synthetic nodes, `syn_end` is their count.  The count is looked at BEFORE the ray is set up: every
+    // second walk of the bench scene starts from an empty cut, and the three exact reciprocals and the origin terms below are ~50
+    // vector instructions.
+    // Without CUT nothing reads `syn`; it is an operand of the walk statement all the same (which ends a cut by moving it past every end)
+    // and starts from `syn0`, any value the caller has in a scalar register.  (From a constant instead, the no-cuts kernels save a scalar
+    // instruction per walk and get another register allocation: a change of generated code, to be measured as one.)
+    uint32_t syn = CUT ? 0u : syn0, syn_end = 0u;
+    if constexpr (CUT) {
+        const int32_t nsyn = __builtin_amdgcn_readfirstlane(__float_as_int(cut_lds[3].z));
+        if (nsyn == 0) return false;                  // nothing between the VPL and the tile group
+        syn_end = (uint32_t)nsyn;
+    }
+    const V3 inv0 = v3(safe_rcp(d.x), safe_rcp(d.y), safe_rcp(d.z));
+    const float ku = 1.0f / (tmax - tmin);
+    const V3 inv = inv0 * ku;
+    const float dead = __builtin_inff();
+    int sp = 0;
+    int vstack = 0;
+    int32_t cur = 0;  // root is always an inner node
+    // the ray of the node visits: {1/dx, 1/dy} {1/dz, |1/dx|} {|1/dy|, |1/dz|} {-ox/dx, -oy/dy} {-oz/dz, -}
+    v2f pa_, pb_, pc_, pd_, pe_;
+    pa_.x = inv.x; pa_.y = inv.y; pb_.x = inv.z; pb_.y = fabsf(inv.x); pc_.x = fabsf(inv.y); pc_.y = fabsf(inv.z);
+    pd_.x = alive_lane ? (-(o.x * inv0.x) - tmin) * ku : dead; pd_.y = alive_lane ? (-(o.y * inv0.y) - tmin) * ku : dead;
+    pe_.x = alive_lane ? (-(o.z * inv0.z) - tmin) * ku : dead; pe_.y = pe_.x;
+    // the ray of the pair test: {dx, dy} {dz, ox} {oy, oz}
+    v2f ra_, rb_, rc_;
+    ra_.x = d.x; ra_.y = d.y; rb_.x = d.z; rb_.y = o.x; rc_.x = o.y; rc_.y = o.z;
+    asm("" : "+v"(rc_));        // (wave-uniform: left alone, the compiler keeps it in scalar registers and copies it out in front of every pair)
+    for (;;) {
+        if constexpr (CUT) {
+            if (syn >= syn_end) break;       // (also: the walk statement moved syn past every end when the last live lane was occluded)
+            // the synthetic node straight from the slot's LDS copy into the visit's registers
+            const uint32_t syn_addr_ = lds_offset(cut_lds) + (syn << 6);
+            syn++;
+            unsigned long long m1_, t64_; int32_t p0_, p1_, c0_, c1_;
+            EV_SYN_VISIT_ASM_("");
+        }
+        EV_WITH(EV_WALK_LOOP_ASM, EV_TMP_52);        // ... until cur == kNoChild: nothing left below this entry, or no live lane left (then the cut is at its end too)
+        if constexpr (!CUT) break;
+    }
+    return alive_lane && ((alive >> (threadIdx.x & 63u)) & 1ull) == 0ull;      // occluded = was alive, is not any more (no second mask in the loop)
+}
+
+// Any-hit traversal of ONE WAVE whose 64 rays share the origin `o` (a VPL), in C++: the reference implementation of occluded_wave,
+// and the walk of the counters build (`ws`) and of an EVPLP_WALK_ASM=0 build.
+// CUT: `cut` + `cut_off` = the slot of this (tile group, VPL) in global memory; `cut_off` then walks over its synthetic nodes, fetched
+// with scalar loads, `cut_end` is where they end.
+// COUNT: the caller hands in `ws` (the counters build's VPL gather; everybody else passes nullptr).  The counted walk is an instantiation
+// of its own: it shares no node-visit lambda with the uncounted walks of the same build, whose inlining would otherwise depend on it.
+template <bool CUT, bool COUNT = false>
+EV_DEV bool occluded_wave_ref(const char *node_base, const char *leaf_base, V3 o, V3 d, float tmin, float tmax, bool alive_lane, WalkStats *ws, const char *cut, uint32_t cut_off) {
     // All control state is wave-uniform (SGPRs): `alive` / `hitm` are 64-bit lane masks, `cur` the
     // node reference, `sp` the stack pointer.  Per-lane registers hold only the ray (1/d, -o/d) and its
     // far bound `tfar`: a lane that is inactive or already occluded carries tfar = -1, so its slab tests
@@ -850,16 +879,9 @@ EV_DEV bool occluded_wave(const char *node_base, const char *leaf_base, V3 o, V3
     // distance is +inf, both clamp to 1, and the lane never enters a box -- the ballots need no masking.
     unsigned long long alive = ballot64(alive_lane), hitm = 0ull;
     if (alive == 0ull) return false;
-    // `cut` + `cut_off` = the slot of this (tile group, VPL); `cut_off` then walks over its synthetic nodes, `cut_end` is where they end.
-    // The count is looked at BEFORE the ray is set up: every second walk of the bench scene starts from an empty cut, and the three
-    // exact reciprocals and the origin terms below are ~50 vector instructions.
+    // The count is looked at BEFORE the ray is set up, as in occluded_wave.
     uint32_t cut_end = 0u;
-    constexpr bool kCutLds = CUT && VT != 0 && EVPLP_WALK_ASM && !EVPLP_TRAVERSAL_STATS;   // the slot was copied to LDS ahead of the walk (gather kernels)
-    if constexpr (kCutLds) {
-        const int32_t nsyn = __builtin_amdgcn_readfirstlane(__float_as_int(cut_lds[3].z));
-        if (nsyn == 0) return false;                  // nothing between the VPL and the tile group
-        cut_off = 0u; cut_end = (uint32_t)nsyn;       // (here: node indices)
-    } else if constexpr (CUT) {
+    if constexpr (CUT) {
         // (the count alone: a synthetic node is fetched right where it is visited -- held across the walk of the previous one the
         // compiler parks its sixteen dwords in VGPR lanes, 32 cross-lane moves per synthetic node)
         int32_t nsyn;
@@ -878,124 +900,6 @@ EV_DEV bool occluded_wave(const char *node_base, const char *leaf_base, V3 o, V3
     int sp = 0;
     int vstack = 0;
     int32_t cur = 0;  // root is always an inner node
-#if EVPLP_WALK_ASM && !EVPLP_TRAVERSAL_STATS
-    if constexpr (VT != 0) {
-        static_assert(VT == 52 || VT == 116, "reserved temporaries: v[52:63] (of the reserved v[50:63]) or v[116:127]");
-        const int lane_id = (int)(threadIdx.x & 63u);
-        v2f pa_, pb_, pc_, pd_, pe_;
-        pa_.x = ivx.x; pa_.y = ivy.x; pb_.x = ivz.x; pb_.y = avx.x; pc_.x = avy.x; pc_.y = avz.x;
-        pd_.x = nox.x; pd_.y = noy.x; pe_.x = noz.x; pe_.y = noz.x;
-#define EV_VISIT(N)                                                                                                                          \
-        {                                                                                                                                    \
-            const v2f cx_ = pk(N[0], N[1]), cy_ = pk(N[2], N[3]), cz_ = pk(N[4], N[5]), hx_ = pk(N[6], N[7]), hy_ = pk(N[8], N[9]), hz_ = pk(N[10], N[11]); \
-            const int32_t c0_ = N[12], c1_ = N[13];                                                                                          \
-            unsigned long long m1_, t64_; int32_t p0_, p1_;                                                                                  \
-            if constexpr (VT == 52) EV_WALK_VISIT_ASM("v[52:53]", "v[54:55]", "v[56:57]", "v[58:59]", "v[60:61]", "v[62:63]", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63"); \
-            else EV_WALK_VISIT_ASM("v[116:117]", "v[118:119]", "v[120:121]", "v[122:123]", "v[124:125]", "v[126:127]", "v116", "v117", "v118", "v119", "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127"); \
-        }
-#if EVPLP_LEAF_ASM
-        // the ray of the pair test: {dx, dy} {dz, ox} {oy, oz}
-        v2f ra_, rb_, rc_;
-        ra_.x = d.x; ra_.y = d.y; rb_.x = d.z; rb_.y = o.x; rc_.x = o.y; rc_.y = o.z;
-        asm("" : "+v"(rc_));        // (wave-uniform: left alone, the compiler keeps it in scalar registers and copies it out in front of every pair)
-#endif
-#define EV_WALK_LOOP                                                                                                                         \
-        if constexpr (VT == 52) EV_WALK_LOOP_ASM("v[52:53]", "v[54:55]", "v[56:57]", "v[58:59]", "v[60:61]", "v[62:63]", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63"); \
-        else EV_WALK_LOOP_ASM("v[116:117]", "v[118:119]", "v[120:121]", "v[122:123]", "v[124:125]", "v[126:127]", "v116", "v117", "v118", "v119", "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127");
-#if EVPLP_LEAF_ASM
-        for (;;) {
-            if constexpr (CUT) {
-                if (cut_off >= cut_end) break;       // (also: the walk statement moved cut_off past every end when the last live lane was occluded)
-#if EVPLP_SYN_INPLACE
-                if constexpr (VT == 52) {
-                    // the synthetic node straight from the slot's LDS copy into the visit's registers (EV_SYN_VISIT_ASM_)
-                    const uint32_t syn_addr_ = lds_offset(cut_lds) + (cut_off << 6);
-                    cut_off++;
-                    unsigned long long m1_, t64_; int32_t p0_, p1_, c0_, c1_;
-                    EV_SYN_VISIT_ASM_("");
-                } else
-#endif
-                {
-                // the synthetic node from the slot's LDS copy, as below
-                v16i syn;
-                {
-                    const float4 *q = cut_lds + 4u * cut_off;
-#pragma unroll
-                    for (int w = 0; w < 4; w++) {
-                        const float4 qq = q[w];
-                        if (w < 3 || true) { syn[4 * w] = __builtin_amdgcn_readfirstlane(__float_as_int(qq.x)); syn[4 * w + 1] = __builtin_amdgcn_readfirstlane(__float_as_int(qq.y)); }
-                        if (w < 3) { syn[4 * w + 2] = __builtin_amdgcn_readfirstlane(__float_as_int(qq.z)); syn[4 * w + 3] = __builtin_amdgcn_readfirstlane(__float_as_int(qq.w)); }
-                    }
-                    syn[14] = 0; syn[15] = 0;
-                }
-                cut_off++;
-                EV_VISIT(syn)
-                }
-            }
-            EV_WALK_LOOP        // ... until cur == kNoChild: nothing left below this entry, or no live lane left (then the cut is at its end too)
-            if constexpr (!CUT) break;
-        }
-#else
-        for (;;) {
-            if constexpr (CUT) {
-                if (cut_off >= cut_end) break;
-                // the synthetic node from the slot's LDS copy: one address for all lanes (a broadcast read), then into scalar registers like a
-                // fetched node (v_readfirstlane; as VGPR operands of the visit its twelve dwords cost the kernel seven spilled registers)
-                v16i syn;
-                {
-                    const float4 *q = cut_lds + 4u * cut_off;
-#pragma unroll
-                    for (int w = 0; w < 4; w++) {
-                        const float4 qq = q[w];
-                        if (w < 3 || true) { syn[4 * w] = __builtin_amdgcn_readfirstlane(__float_as_int(qq.x)); syn[4 * w + 1] = __builtin_amdgcn_readfirstlane(__float_as_int(qq.y)); }
-                        if (w < 3) { syn[4 * w + 2] = __builtin_amdgcn_readfirstlane(__float_as_int(qq.z)); syn[4 * w + 3] = __builtin_amdgcn_readfirstlane(__float_as_int(qq.w)); }
-                    }
-                    syn[14] = 0; syn[15] = 0;
-                }
-                cut_off++;
-                EV_VISIT(syn)
-            }
-            for (;;) {
-                while (cur >= 0) {
-                    const v16i n = sload16(node_base, (uint32_t)cur << 6);
-                    EV_VISIT(n)
-                }
-                if (cur == kNoChild) break;
-                const uint32_t cnt = (((uint32_t)~cur) & 3u) + 1u, loff = (((uint32_t)~cur) >> 2) * 192u;
-                bool any;
-                if constexpr (CUT) {
-                    v16i lb;
-                    { const PairOps A = fetch_leaf_a(leaf_base, loff, lb); any = tri_pair_any(A, o, d, tmin, tmax); }
-                    if (cnt > 2u) { const PairOps B = fetch_leaf_b(leaf_base, loff, lb); any = any | tri_pair_any(B, o, d, tmin, tmax); }
-                } else {
-                    const LeafOps L = fetch_leaf(leaf_base, (uint32_t)cur);
-                    any = tri_pair_any(L.A, o, d, tmin, tmax);
-                    if (cnt > 2u) any = any | tri_pair_any(L.B, o, d, tmin, tmax);
-                }
-                const unsigned long long hm = ballot64(any) & alive;
-                if (hm != 0ull) {
-                    hitm |= hm;
-                    alive &= ~hm;
-                    if (alive == 0ull) return ((hitm >> (threadIdx.x & 63u)) & 1ull) != 0ull;
-                    if (any) { pd_ = bc(dead); pe_ = bc(dead); }     // newly occluded lanes stop driving the walk
-                }
-                if (sp == 0) break;
-                sp--;
-                cur = lane_read(vstack, sp);
-            }
-            if constexpr (!CUT) break;
-        }
-#endif
-#undef EV_VISIT
-#undef EV_WALK_LOOP
-#if EVPLP_LEAF_ASM
-        return alive_lane && ((alive >> (threadIdx.x & 63u)) & 1ull) == 0ull;      // occluded = was alive, is not any more (no second mask in the loop)
-#else
-        return ((hitm >> (threadIdx.x & 63u)) & 1ull) != 0ull;
-#endif
-    }
-#endif
-    // the reference implementation of the same walk in C++ (EVPLP_WALK_ASM=0, and the counters build)
     auto visit_cpp = [&](const v16i &n) {
         // both children at once (half 0 = child 0, half 1 = child 1), conservative slab test in
         // centre / half-size form: A = ctr/d - o/d, B = hal/|d|, entry = A - B, exit = A + B

@@ -251,9 +251,7 @@ EV_DEV void item_cost_add(const GatherArgs &a, int ty, unsigned long long t0, in
     if (threadIdx.x == 0) atomicAdd(&a.block_cost[(ty * 8) / a.st.strip_rows], dt * 8ull / (unsigned long long)waves);
 }
 template <bool CUT, bool COST = false, bool ADAPT = false>
-#if EVPLP_WALK_ASM && !EVPLP_TRAVERSAL_STATS
-__attribute__((amdgpu_num_vgpr(50)))      // v[50:63] belong to the hand-written node visits (device_common.hpp: v[52:63] the temporaries, v[50:51] the spare pair of the in-place one)
-#endif
+__attribute__((amdgpu_num_vgpr(kWalkKernelVgprs)))      // v[50:63] belong to the hand-written node visits (device_common.hpp: v[52:63] the temporaries, v[50:51] the spare pair of the in-place one)
 __global__ __launch_bounds__(64, EVPLP_GATHER_WAVES) void gather_vpl_kernel(GatherArgs a, AdaptArgs ad) {
     unsigned long long t_cost = 0ull;
     if constexpr (COST) t_cost = __builtin_amdgcn_s_memrealtime();
@@ -307,7 +305,7 @@ __global__ __launch_bounds__(64, EVPLP_GATHER_WAVES) void gather_vpl_kernel(Gath
     // The cut slots of the item's VPLs stream through a small LDS ring ahead of the walks (global_load_lds: asynchronous, counted by vmcnt,
     // no register in between).  A walk that fetched its slot itself began with two dependent scalar loads from memory no cache holds
     // (8.6 GB of slots per frame, each read once per tile): 65.6 ms against 70.6 ms without cuts although the node visits had halved.
-    constexpr bool kRing = CUT && EVPLP_WALK_ASM && !EVPLP_TRAVERSAL_STATS;
+    constexpr bool kRing = CUT && kWalkAsm;
     constexpr int kRingSlots = EVPLP_CUT_RING, kAhead = kRingSlots - 1;
     __shared__ float4 s_cut[kRing ? kRingSlots : 1][kCutSlotBytes / 16];
     int pj = 0; uint32_t pi = (uint32_t)(t.group * k), qslot = 0u;       // the prefetch position in the item's VPL sequence (split pj, VPL pi)
@@ -355,7 +353,7 @@ __global__ __launch_bounds__(64, EVPLP_GATHER_WAVES) void gather_vpl_kernel(Gath
                     cache_kill = ballot64(any) & act_m;
                 }
                 WalkStats ws = { 0u, 0u, 0u, 0u, kNoChild, 0u };
-                occ = occluded_wave<0, CUT>(node_base, leaf_base, vpos, -v12, 0.0001f, 1.0f - 0.0001f, active, &ws, cuts_g, i * (uint32_t)kCutSlotBytes);
+                occ = occluded_wave_ref<CUT, true>(node_base, leaf_base, vpos, -v12, 0.0001f, 1.0f - 0.0001f, active, &ws, cuts_g, i * (uint32_t)kCutSlotBytes);
                 const bool all_occ = ballot64(active && !occ) == 0ull;
                 const unsigned long long occ_m = ballot64(active && occ);
                 if (lane == 0) {
@@ -378,7 +376,8 @@ __global__ __launch_bounds__(64, EVPLP_GATHER_WAVES) void gather_vpl_kernel(Gath
                 if (ws.hit_leaf != kNoChild) cache_leaf = ws.hit_leaf;
                 prev_all_occ = all_occ;
 #else
-                occ = occluded_wave<EVPLP_WALK_ASM ? 52 : 0, CUT>(node_base, leaf_base, vpos, -v12, 0.0001f, 1.0f - 0.0001f, active, nullptr, cuts_g, i * (uint32_t)kCutSlotBytes, cut_lds);
+                if constexpr (kWalkAsm) occ = occluded_wave<CUT>(node_base, leaf_base, vpos, -v12, 0.0001f, 1.0f - 0.0001f, active, cut_lds, i * (uint32_t)kCutSlotBytes);
+                else occ = occluded_wave_ref<CUT>(node_base, leaf_base, vpos, -v12, 0.0001f, 1.0f - 0.0001f, active, nullptr, cuts_g, i * (uint32_t)kCutSlotBytes);
 #endif
             }
             const bool lit = active && !occ;
@@ -835,9 +834,7 @@ EV_DEV size_t vsl_mask_base(const GatherArgs &a, int tile_in_launch_order, int g
 EV_DEV int launch_tile(const GatherArgs &a) { return item_index<true>(a, (int)blockIdx.x).tile_l; }      // the tile's index in launch order
 
 template <bool CUT, bool COST = false, bool ADAPT = false>
-#if EVPLP_WALK_ASM && !EVPLP_TRAVERSAL_STATS
-__attribute__((amdgpu_num_vgpr(50)))      // v[50:63] belong to the hand-written node visits (device_common.hpp: v[52:63] the temporaries, v[50:51] the spare pair of the in-place one)
-#endif
+__attribute__((amdgpu_num_vgpr(kWalkKernelVgprs)))      // v[50:63] belong to the hand-written node visits (device_common.hpp: v[52:63] the temporaries, v[50:51] the spare pair of the in-place one)
 __global__ __launch_bounds__(64, EVPLP_GATHER_WAVES) void gather_vsl_walk_kernel(GatherArgs a, AdaptArgs ad) {
     unsigned long long t_cost = 0ull;
     if constexpr (COST) t_cost = __builtin_amdgcn_s_memrealtime();
@@ -859,7 +856,7 @@ __global__ __launch_bounds__(64, EVPLP_GATHER_WAVES) void gather_vsl_walk_kernel
     if constexpr (CUT) cuts_g = pinned(a.cuts + (size_t)item_cut_group(a, t) * a.cut_vpl_stride * (size_t)kCutSlotBytes);
     uint32_t rays = 0;
     // the cut slots of the item's VSLs stream through an LDS ring ahead of the walks (as in gather_vpl_kernel)
-    constexpr bool kRing = CUT && EVPLP_WALK_ASM && !EVPLP_TRAVERSAL_STATS;
+    constexpr bool kRing = CUT && kWalkAsm;
     constexpr int kRingSlots = EVPLP_CUT_RING, kAhead = kRingSlots - 1;
     __shared__ float4 s_cut[kRing ? kRingSlots : 1][kCutSlotBytes / 16];
     int pj = 0; uint32_t pi = (uint32_t)(t.group * k), qslot = 0u;
@@ -906,7 +903,9 @@ __global__ __launch_bounds__(64, EVPLP_GATHER_WAVES) void gather_vsl_walk_kernel
                 unsigned long long lit = 0ull;
                 if (ballot64(pre) != 0ull) {
                     rays += pre ? 1u : 0u;
-                    const bool occ = occluded_wave<EVPLP_WALK_ASM ? 52 : 0, CUT>(node_base, leaf_base, vpos, -v12, 0.0001f, 1.0f - 0.0001f, pre, nullptr, cuts_g, i * (uint32_t)kCutSlotBytes, cut_lds);   // :612-614
+                    bool occ;                                                     // :612-614
+                    if constexpr (kWalkAsm) occ = occluded_wave<CUT>(node_base, leaf_base, vpos, -v12, 0.0001f, 1.0f - 0.0001f, pre, cut_lds, i * (uint32_t)kCutSlotBytes);
+                    else occ = occluded_wave_ref<CUT>(node_base, leaf_base, vpos, -v12, 0.0001f, 1.0f - 0.0001f, pre, nullptr, cuts_g, i * (uint32_t)kCutSlotBytes);
                     lit = ballot64(pre && !occ);
                 }
                 if (lane == 0) s_lit[c] = lit;          // (single-wavefront workgroup: LDS is in order, no barrier)

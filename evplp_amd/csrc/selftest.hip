@@ -137,7 +137,7 @@ __attribute__((amdgpu_num_vgpr(50))) __global__ __launch_bounds__(64) void selft
 __attribute__((amdgpu_num_vgpr(116))) __global__ __launch_bounds__(64) void selftest_pair116_kernel(const PairTestRec *recs, unsigned long long *out) { selftest_pair_body<116>(recs, out); }
 
 // which = 3: the in-place visit of a synthetic node (device_common.hpp EV_SYN_VISIT_ASM_: the node read from LDS into the visit's own
-// registers) against the scalar-operand visit EV_WALK_VISIT_ASM on the same node and rays: kSynTestNodes nodes x 64 rays that share their
+// registers) against the scalar-operand visit EV_WALK_VISIT_ASM_ on the same node and rays: kSynTestNodes nodes x 64 rays that share their
 // origin (as the lanes of a gather wave do), generated here from a fixed seed, in six classes (node index mod 6):
 //   0 random boxes around random segments                          3 child 0 ends exactly at a segment end point: its face in the plane
 //   1 the second entry absent, as the cut kernel writes an odd       of the shared origin, or of the end points (which then share their x):
@@ -187,6 +187,20 @@ __global__ __launch_bounds__(64) void selftest_syn_gen_kernel(SynTestRec *recs) 
     r.spread = 2.0f * S; r.cls = cls; r.sp0 = node & 3u;
     recs[node] = r;
 }
+// The node visit of the walk (device_common.hpp EV_VISIT_TEXT, the very text EV_WALK_LOOP_ASM executes) as a statement of its own, with
+// operands in place of the walk's fixed scalar registers.  NC: the constraint of the node's six box operands ("s": register pairs of a
+// node fetched with a scalar load).  TAIL: text behind the visit (the first mask is copied out of vcc there).
+// (the text names no %[lane]: the operand only keeps the lane id in a register across the statement)
+#define EV_WALK_VISIT_ASM_(NC, TAIL, T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H)                         \
+    asm volatile(                                                                                                                            \
+        EV_VISIT_TEXT("%[cx]", "%[cy]", "%[cz]", "%[hx]", "%[hy]", "%[hz]", "%[c0]", "%[c1]", "%[m1]", "%[t64]", "%[p0]", "%[p1]",           \
+                      T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H)                                    \
+        TAIL                                                                                                                                 \
+        : [cur] "+s"(cur), [sp] "+s"(sp), [vstack] "+v"(vstack), [m1] "=&s"(m1_), [t64] "=&s"(t64_), [p0] "=&s"(p0_), [p1] "=&s"(p1_)          \
+        : [cx] NC(cx_), [cy] NC(cy_), [cz] NC(cz_), [hx] NC(hx_), [hy] NC(hy_), [hz] NC(hz_), [c0] "s"(c0_), [c1] "s"(c1_),              \
+          [pa] "v"(pa_), [pb] "v"(pb_), [pc] "v"(pc_),                                     \
+          [pd] "v"(pd_), [pe] "v"(pe_), [lane] "v"(lane_id)                                                                 \
+        : "vcc", "scc", "m0", T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H)
 __attribute__((amdgpu_num_vgpr(50))) __global__ __launch_bounds__(64) void selftest_syn_kernel(const SynTestRec *recs, unsigned long long *out) {
     __shared__ float4 s_node[4];
     const uint32_t node = blockIdx.x, lane = threadIdx.x & 63u;
@@ -223,7 +237,7 @@ __attribute__((amdgpu_num_vgpr(50))) __global__ __launch_bounds__(64) void selft
         const int32_t c0_ = N[12], c1_ = N[13];
         unsigned long long m1_, t64_; int32_t p0_, p1_;
         int32_t cur = 0; int sp = sp0, vstack = vstack0;
-        EV_WALK_VISIT_ASM_("s", "s_mov_b64 %[t64], vcc\n", "v[52:53]", "v[54:55]", "v[56:57]", "v[58:59]", "v[60:61]", "v[62:63]", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63");
+        EV_WITH(EV_WALK_VISIT_ASM_, "s", "s_mov_b64 %[t64], vcc\n", EV_TMP_52);
         ref_m0 = t64_; ref_m1 = m1_; ref_cur = cur; ref_sp = sp; ref_stack = vstack;
     }
     // the subject: the node from LDS, in place

@@ -1,7 +1,7 @@
 """The in-place visit of a synthetic node of an entry cut (device_common.hpp EV_SYN_VISIT_ASM_: the node goes from the slot's LDS copy
 straight into the visit's registers; only its two child references become scalars).
 
-1. evplp_selftest(3): the in-place statement against the scalar-operand visit EV_WALK_VISIT_ASM on the same device-generated nodes and
+1. evplp_selftest(3): the in-place statement against the scalar-operand visit (selftest.hip EV_WALK_VISIT_ASM_) on the same device-generated nodes and
    rays -- both entered-lane masks, the next node, the stack pointer and the whole stack register -- in six classes (random boxes around
    random segments; an absent second entry as the cut kernel writes an odd count; dead lanes among live ones; a box that ends exactly at
    a segment end point; zero half-sizes; coordinates at 1e-15 .. 1e15).
