@@ -96,6 +96,14 @@ class PassStats(C.Structure):
                 ("pad", C.c_uint32)]
 
 
+# evplp_debug_accel's records (csrc/evplp_types.h BvhNode, LeafBlock, TriFlat, BvhNode4)
+ACCEL_NODE = np.dtype([("ctr", np.float32, (3, 2)), ("hal", np.float32, (3, 2)), ("c0", np.int32), ("c1", np.int32), ("pad", np.int32, 2)])
+ACCEL_PAIR = np.dtype([("p0", np.float32, (3, 2)), ("e0", np.float32, (3, 2)), ("e1", np.float32, (3, 2)), ("n", np.float32, (3, 2))])
+ACCEL_LEAF = np.dtype([("pair", ACCEL_PAIR, 2)])
+ACCEL_TRI = np.dtype([("p0", np.float32, 3), ("e0", np.float32, 3), ("e1", np.float32, 3), ("n", np.float32, 3)])
+ACCEL_NODE4 = np.dtype([("lo", np.float32, (3, 4)), ("hi", np.float32, (3, 4)), ("child", np.int32, 4), ("pad", np.int32, 4)])
+NO_CHILD = -2 ** 31
+
 # every symbol include/evplp.h declares: (restype, argtypes)
 _P = C.c_void_p
 _SIGNATURES = {
@@ -113,6 +121,13 @@ _SIGNATURES = {
     "evplp_load_scene_json": (C.c_int, [_P, C.c_char_p]),
     "evplp_get_camera": (C.c_int, [_P, C.POINTER(Camera)]),
     "evplp_build_accel": (C.c_int, [_P]),
+    "evplp_update_mesh": (C.c_int, [_P, C.c_int32, _P, C.c_int32]),
+    "evplp_refit_accel": (C.c_int, [_P]),
+    "evplp_refit_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
+    "evplp_refit_levels": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32]),
+    "evplp_debug_accel": (C.c_int, [_P, C.c_int32, _P, C.c_size_t]),
+    "evplp_group_update_mesh": (C.c_int, [_P, C.c_int32, _P, C.c_int32]),
+    "evplp_group_refit_accel": (C.c_int, [_P]),
     "evplp_scene_metrics": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "evplp_primary": (C.c_int, [_P, C.POINTER(C.c_float * 2), C.c_int32]),
     "evplp_trace_light_paths": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32]),
@@ -436,6 +451,30 @@ class Context:
     def build_accel(self):
         self._check(self._lib.evplp_build_accel(self._h))
 
+    def update_mesh(self, mesh: int, vertices):
+        """evplp_update_mesh: new positions (n, 3) for mesh `mesh` (same vertex count); every pass is refused until refit_accel / build_accel"""
+        v = _f32(vertices).reshape(-1, 3)
+        self._check(self._lib.evplp_update_mesh(self._h, int(mesh), _ptr(v), v.shape[0]))
+
+    def refit_accel(self):
+        """evplp_refit_accel: the tree, the triangle operands and the scene's figures follow the updated vertices, on the device; the topology stays"""
+        self._check(self._lib.evplp_refit_accel(self._h))
+
+    def refit_info(self):
+        n, l, ms = C.c_int32(), C.c_int32(), C.c_float()
+        self._check(self._lib.evplp_refit_info(self._h, C.byref(n), C.byref(l), C.byref(ms)))
+        return {"refits": n.value, "levels": l.value, "last_refit_ms": ms.value}
+
+    def debug_accel(self, which: int) -> np.ndarray:
+        """evplp_debug_accel (tests): 0 nodes, 1 leaf blocks, 2 flat triangle operands, 3 slot -> triangle, 4 four-wide nodes (structured arrays
+        / int32), 5 the box pad (a float), 6 the last refit's four stage times in ms"""
+        info = self.accel_info()
+        nn, nl = max(info["nodes"], 1), max(info["leaves"], 1)
+        out = {0: lambda: np.zeros(nn, ACCEL_NODE), 1: lambda: np.zeros(nl, ACCEL_LEAF), 2: lambda: np.zeros(4 * nl, ACCEL_TRI), 3: lambda: np.zeros(4 * nl, np.int32),
+               4: lambda: np.zeros(nn, ACCEL_NODE4), 5: lambda: np.zeros(1, np.float32), 6: lambda: np.zeros(4, np.float32)}[which]()
+        self._check(self._lib.evplp_debug_accel(self._h, which, _ptr(out), out.nbytes))
+        return out[0] if which == 5 else out
+
     def load_scene_json(self, json_path: str):
         rc = self._lib.evplp_load_scene_json(self._h, json_path.encode())
         if rc < 0:
@@ -703,6 +742,21 @@ class Context:
         return strips.rows_of_blocks(self.H, self.blocks(), self.cfg.strip_rows, self.local_rows)      # (the library's table: dealt or round-robin)
 
 
+def refit_levels(nodes, level_capacity: int = 64):
+    """evplp_refit_levels: (height per node, nodes by height, level offsets [levels + 1]) of a flattened tree (ACCEL_NODE records or raw 64-byte
+    nodes); host only, deterministic.  EvplpError for an array that is not a tree of at most level_capacity heights."""
+    raw = np.ascontiguousarray(nodes).view(np.uint8).reshape(-1, 64)
+    n = raw.shape[0]
+    height, order, begin = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), np.zeros(max(level_capacity, 0) + 1, np.int32)
+    rc = lib().evplp_refit_levels(_ptr(raw), n, _ptr(height), _ptr(order), _ptr(begin), int(level_capacity))
+    if rc < 0:
+        raise EvplpError(rc, "evplp_refit_levels: not a tree (a child index out of range, a node reached twice, a cycle), or more heights than level_capacity")
+    return height[:n], order[:int(begin[rc])], begin[:rc + 1]
+
+
+Context.refit_levels = staticmethod(refit_levels)      # (the plan needs no context; it is listed with the calls it serves)
+
+
 def deal_blocks(costs, n_ranks: int, capacity_blocks: int) -> np.ndarray:
     """evplp_deal_blocks: owner rank of every image block for these per-block costs (host only, deterministic)"""
     c = np.ascontiguousarray(costs, dtype=np.uint64)
@@ -822,6 +876,13 @@ class Group:
 
     def splat_photons(self, fp, clear=False):
         self._check(self._lib.evplp_group_splat_photons(self._h, C.byref(fp), int(clear)))
+
+    def update_mesh(self, mesh: int, vertices):
+        v = _f32(vertices).reshape(-1, 3)
+        self._check(self._lib.evplp_group_update_mesh(self._h, int(mesh), _ptr(v), v.shape[0]))
+
+    def refit_accel(self):
+        self._check(self._lib.evplp_group_refit_accel(self._h))
 
     def set_splat_proxy(self, vertices=None, triangles=None):
         if vertices is None:

@@ -384,14 +384,14 @@ int build_bvh(const float *verts, int32_t ntri, int builder, BvhBuild *out) {
     Box scene; scene.reset();
     for (int32_t i = 0; i < ntri; i++) {
         const float *v = verts + 9 * (size_t)i;
-        // rt/triangleintersect.cu:62-81 meshBound: area = |cross(v1-v0, v2-v0)| must be > 0 and finite
+        // (rt/triangleintersect.cu:62-81 meshBound: a triangle is kept iff tri_has_area; the area itself weighs the face peel)
         float a[3] = { v[3] - v[0], v[4] - v[1], v[5] - v[2] }, b[3] = { v[6] - v[0], v[7] - v[1], v[8] - v[2] };
         float c[3] = { a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0] };
         float area = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
         Box &tb = B.tbox[i]; tb.reset(); tb.grow(v); tb.grow(v + 3); tb.grow(v + 6);
         for (int k = 0; k < 3; k++) B.centroid[3 * (size_t)i + k] = 0.5f * (tb.lo[k] + tb.hi[k]);
         B.tarea[i] = 0.5f * area;
-        if (area > 0.0f && !std::isinf(area)) { B.ids.push_back(i); scene.grow(tb); }
+        if (tri_has_area(v)) { B.ids.push_back(i); scene.grow(tb); }
     }
     int32_t nvalid = (int32_t)B.ids.size();
     B.nodes.reserve((size_t)3 * std::max(nvalid, 1) + 2);
@@ -417,12 +417,7 @@ int build_bvh(const float *verts, int32_t ntri, int builder, BvhBuild *out) {
     // 1e-4 of its length short of the surface it ends on (lighttracing.cu:292), and only while pad < 1e-4 |d_perp| does it stay
     // out of the leaf boxes of that surface -- with the former 2e-5 D every segment shorter than 6 units entered the leaf under
     // its end point, and a beam shaft every leaf under its tile's footprint.
-    const float pad_scale = bvh_pad_scale();
-    float diag = 0.f;
-    if (nvalid > 0) { float dx = scene.hi[0] - scene.lo[0], dy = scene.hi[1] - scene.lo[1], dz = scene.hi[2] - scene.lo[2]; diag = std::sqrt(dx * dx + dy * dy + dz * dz); }
-    float coord = 0.f;
-    if (nvalid > 0) for (int k = 0; k < 3; k++) coord = std::max(coord, std::max(std::abs(scene.lo[k]), std::abs(scene.hi[k])));
-    const float pad = pad_scale * std::max(diag, coord) + 1e-30f;
+    const float pad = bvh_pad(scene.lo, scene.hi, nvalid > 0);
 
     // flatten: inner nodes in DFS pre-order; each inner node carries both child boxes
     std::vector<BvhNode> flat; std::vector<int32_t> order; order.reserve((size_t)nvalid);   // 4 slots per leaf, -1 = empty
@@ -502,6 +497,15 @@ float bvh_pad_scale() {
     if (const char *e = std::getenv("EVPLP_BVH_PAD")) pad_scale = (float)atof(e);
 #endif
     return pad_scale;
+}
+
+float bvh_pad(const float lo[3], const float hi[3], bool any) {
+    const float pad_scale = bvh_pad_scale();
+    float diag = 0.f;
+    if (any) { float dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2]; diag = std::sqrt(dx * dx + dy * dy + dz * dz); }
+    float coord = 0.f;
+    if (any) for (int k = 0; k < 3; k++) coord = std::max(coord, std::max(std::abs(lo[k]), std::abs(hi[k])));
+    return pad_scale * std::max(diag, coord) + 1e-30f;
 }
 
 void free_bvh(BvhBuild *b) {

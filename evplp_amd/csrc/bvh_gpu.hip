@@ -14,6 +14,15 @@
 //                     nodes with more than 4 triangles are kept and renumbered by a prefix sum.
 //   6. emit         : kept nodes with both child boxes (padded, centre / half-size form), leaf blocks with the
 //                     precomputed operands of the exact triangle test.
+//
+// Refit (evplp_refit_accel, for a tree of ANY builder whose vertices moved; the topology and the leaf assignment stay):
+//   a. refit_scatter : the moved triangles' vertices from a packed staging array into TriAttr::v.
+//   b. refit_leaves  : every live leaf slot's operands again, in both layouts (the arithmetic emit_leaves_kernel uses).
+//   c. refit_level   : the boxes, one launch per height of the tree, the parents of leaves first and the root last.  The end of a
+//                      launch is the only hand-over between heights: a thread owns one node, reads its children's unpadded boxes
+//                      (a leaf's from its triangles, an inner child's from a scratch array the launch before wrote), writes its own
+//                      union there and the padded child boxes into its node -- padded once, from the exact union.
+//   d. node4         : the four-wide nodes again, into the allocation they have.
 #include "evplp_types.h"
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -47,14 +56,10 @@ __global__ __launch_bounds__(256) void tri_setup_kernel(const float *verts, int 
     uint32_t ok = 0u;
     if (i < ntri) {
         const float *v = verts + 9 * (size_t)i;
-        // rt/triangleintersect.cu:62-81 meshBound: area = |cross(v1-v0, v2-v0)| must be > 0 and finite
-        const float a[3] = { v[3] - v[0], v[4] - v[1], v[5] - v[2] }, b[3] = { v[6] - v[0], v[7] - v[1], v[8] - v[2] };
-        const float c[3] = { a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0] };
-        const float area = sqrtf(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
         Bx t;
         for (int k = 0; k < 3; k++) { t.lo[k] = fminf(fminf(v[k], v[3 + k]), v[6 + k]); t.hi[k] = fmaxf(fmaxf(v[k], v[3 + k]), v[6 + k]); }
         tbox[i] = t;
-        ok = (area > 0.0f && !isinf(area)) ? 1u : 0u;
+        ok = tri_has_area(v) ? 1u : 0u;                                   // meshBound's rule (evplp_types.h)
         valid[i] = (uint8_t)ok;
         if (ok) for (int k = 0; k < 3; k++) { const float ce = 0.5f * (t.lo[k] + t.hi[k]); clo[k] = chi[k] = ce; slo[k] = t.lo[k]; shi[k] = t.hi[k]; }
     }
@@ -230,9 +235,24 @@ __global__ __launch_bounds__(256) void emit_nodes_kernel(const Topo *topo, int n
     f.c0 = ref[0]; f.c1 = ref[1];
     nodes[new_id[i]] = f;
 }
+// The operands of the exact triangle test of one leaf slot, in both layouts: the same operation order as the host builder and the
+// oracle's tri_test: e0 = p1-p0, e1 = p0-p2, n = cross(e1, e0).  live = false: all zero (den = 0 -> the test is false).
+__device__ __forceinline__ void store_operands(const float *v, bool live, size_t slot, LeafBlock *leaves, TriFlat *tri_flat) {
+#pragma clang fp contract(off)
+    float p0[3] = { 0.f, 0.f, 0.f }, e0[3] = { 0.f, 0.f, 0.f }, e1[3] = { 0.f, 0.f, 0.f }, nn[3] = { 0.f, 0.f, 0.f };
+    if (live) {
+        for (int c = 0; c < 3; c++) { p0[c] = v[c]; e0[c] = v[3 + c] - v[c]; e1[c] = v[c] - v[6 + c]; }
+        nn[0] = e1[1] * e0[2] - e1[2] * e0[1]; nn[1] = e1[2] * e0[0] - e1[0] * e0[2]; nn[2] = e1[0] * e0[1] - e1[1] * e0[0];
+    }
+    TriPair &tp = leaves[slot >> 2].pair[(slot >> 1) & 1]; const int h = (int)(slot & 1);
+    TriFlat &tf = tri_flat[slot];
+    for (int c = 0; c < 3; c++) {
+        tp.p0[c][h] = p0[c]; tp.e0[c][h] = e0[c]; tp.e1[c][h] = e1[c]; tp.n[c][h] = nn[c];
+        tf.p0[c] = p0[c]; tf.e0[c] = e0[c]; tf.e1[c] = e1[c]; tf.n[c] = nn[c];
+    }
+}
 __global__ __launch_bounds__(256) void emit_leaves_kernel(const float *verts, const int32_t *ids, int n, const uint32_t *head, const uint32_t *block_id,
                                                           LeafBlock *leaves, TriFlat *tri_flat, int32_t *tri_index) {
-#pragma clang fp contract(off)
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= n || !head[p]) return;
     const uint32_t blk = block_id[p], cnt = head[p];
@@ -241,18 +261,59 @@ __global__ __launch_bounds__(256) void emit_leaves_kernel(const float *verts, co
         if (k >= cnt) { tri_index[slot] = -1; continue; }
         const int32_t tri = ids[p + k];
         tri_index[slot] = tri;
-        const float *v = verts + 9 * (size_t)tri;
-        // same operation order as the host builder and the oracle's tri_test: e0 = p1-p0, e1 = p0-p2, n = cross(e1, e0)
-        float e0[3], e1[3];
-        for (int c = 0; c < 3; c++) { e0[c] = v[3 + c] - v[c]; e1[c] = v[c] - v[6 + c]; }
-        const float nn[3] = { e1[1] * e0[2] - e1[2] * e0[1], e1[2] * e0[0] - e1[0] * e0[2], e1[0] * e0[1] - e1[1] * e0[0] };
-        TriPair &tp = leaves[blk].pair[(k >> 1) & 1]; const int h = (int)(k & 1);
-        TriFlat &tf = tri_flat[slot];
-        for (int c = 0; c < 3; c++) {
-            tp.p0[c][h] = v[c]; tp.e0[c][h] = e0[c]; tp.e1[c][h] = e1[c]; tp.n[c][h] = nn[c];
-            tf.p0[c] = v[c]; tf.e0[c] = e0[c]; tf.e1[c] = e1[c]; tf.n[c] = nn[c];
-        }
+        store_operands(verts + 9 * (size_t)tri, true, slot, leaves, tri_flat);
     }
+}
+
+// ---- refit
+// a. src: 9 floats per triangle of the run [first, first + count) of original triangles
+__global__ __launch_bounds__(256) void refit_scatter_kernel(const float *src, int32_t first, int32_t count, TriAttr *attrs) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= 9 * count) return;
+    attrs[(size_t)first + (size_t)(i / 9)].v[i % 9] = src[i];
+}
+// b. one thread per leaf slot.  A triangle that has become degenerate (tri_has_area: meshBound's rule) gets zero operands, which is what a
+// fresh build does by dropping it; an empty slot (tri_index < 0) is zero already and stays.
+__global__ __launch_bounds__(256) void refit_leaves_kernel(const int32_t *tri_index, int32_t nslots, const TriAttr *attrs, int32_t ntri, LeafBlock *leaves, TriFlat *tri_flat) {
+    const int slot = blockIdx.x * 256 + threadIdx.x;
+    if (slot >= nslots) return;
+    const int32_t tri = tri_index[slot];
+    if (tri < 0 || tri >= ntri) return;
+    const float *v = attrs[tri].v;
+    store_operands(v, tri_has_area(v), (size_t)slot, leaves, tri_flat);
+}
+// c. one thread per node of one height (order[0 .. count)); boxes[i] = the unpadded box of everything under node i
+__global__ __launch_bounds__(256) void refit_level_kernel(BvhNode *nodes, int32_t nnodes, const int32_t *order, int32_t count, const int32_t *tri_index, int32_t nslots,
+                                                          const TriAttr *attrs, int32_t ntri, Bx *boxes, float pad) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= count) return;
+    const int32_t i = order[t];
+    if (i < 0 || i >= nnodes) return;
+    BvhNode f = nodes[i];
+    Bx u;
+    for (int k = 0; k < 3; k++) { u.lo[k] = 3.0e38f; u.hi[k] = -3.0e38f; }
+    const int32_t ch[2] = { f.c0, f.c1 };
+    for (int s = 0; s < 2; s++) {
+        if (ch[s] == kNoChild) continue;                                  // (ctr = 0, hal = -3e38 as the builder left them)
+        Bx b;
+        for (int k = 0; k < 3; k++) { b.lo[k] = 3.0e38f; b.hi[k] = -3.0e38f; }
+        if (ch[s] >= 0) { if (ch[s] < nnodes) b = boxes[ch[s]]; }
+        else {
+            const int32_t id = ~ch[s], cnt = (id & 3) + 1;
+            for (int32_t q = 0; q < cnt; q++) {
+                const int32_t slot = (id & ~3) + q;
+                const int32_t tri = slot < nslots ? tri_index[slot] : -1;
+                if (tri < 0 || tri >= ntri) continue;
+                const float *v = attrs[tri].v;
+                if (!tri_has_area(v)) continue;
+                for (int k = 0; k < 3; k++) { b.lo[k] = fminf(b.lo[k], fminf(fminf(v[k], v[3 + k]), v[6 + k])); b.hi[k] = fmaxf(b.hi[k], fmaxf(fmaxf(v[k], v[3 + k]), v[6 + k])); }
+            }
+        }
+        set_box(f, s, b, pad);
+        for (int k = 0; k < 3; k++) { u.lo[k] = fminf(u.lo[k], b.lo[k]); u.hi[k] = fmaxf(u.hi[k], b.hi[k]); }
+    }
+    boxes[i] = u;
+    nodes[i] = f;
 }
 
 // node4[i] from binary node i: child s of i, if it is an inner node, is replaced by ITS two children (their boxes are stored in
@@ -284,16 +345,32 @@ __global__ __launch_bounds__(256) void node4_kernel(const BvhNode *nodes, int n,
 
 } // namespace
 
-// The four-wide nodes of a flattened binary tree that is already on the device (all builders); *out is a device allocation.
+// The four-wide nodes of a flattened binary tree that is already on the device (all builders), into an allocation of nnodes of them: enqueued, no wait.
+void build_nodes4_into(const BvhNode *d_nodes, int32_t nnodes, hipStream_t stream, BvhNode4 *out) {
+    if (nnodes > 0) hipLaunchKernelGGL(node4_kernel, dim3((unsigned)((nnodes + 255) / 256)), dim3(256), 0, stream, d_nodes, nnodes, out);
+}
+// ... into a device allocation of its own (*out), complete when the call returns
 int build_nodes4(const BvhNode *d_nodes, int32_t nnodes, hipStream_t stream, BvhNode4 **out) {
     BvhNode4 *p = nullptr;
     hipError_t e = hipMalloc((void **)&p, sizeof(BvhNode4) * (size_t)std::max(nnodes, 1));
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(node4_kernel, dim3((unsigned)((nnodes + 255) / 256)), dim3(256), 0, stream, d_nodes, nnodes, p);
+    build_nodes4_into(d_nodes, nnodes, stream, p);
     e = hipStreamSynchronize(stream);
     if (e != hipSuccess) { hipFree(p); return (int)e; }
     *out = p;
     return 0;
+}
+
+// The refit's launches (context.cpp evplp_refit_accel owns the memory and the order); all enqueued, none waits.
+void refit_scatter(const float *d_src, int32_t first, int32_t count, TriAttr *attrs, hipStream_t stream) {
+    if (count > 0) hipLaunchKernelGGL(refit_scatter_kernel, dim3((unsigned)((9 * (size_t)count + 255) / 256)), dim3(256), 0, stream, d_src, first, count, attrs);
+}
+void refit_leaves(const RefitScene &r, hipStream_t stream) {
+    if (r.nslots > 0) hipLaunchKernelGGL(refit_leaves_kernel, dim3((unsigned)((r.nslots + 255) / 256)), dim3(256), 0, stream, r.tri_index, r.nslots, r.attrs, r.ntri, r.leaves, r.tri_flat);
+}
+void refit_level(const RefitScene &r, const int32_t *d_order, int32_t count, float pad, hipStream_t stream) {
+    if (count > 0) hipLaunchKernelGGL(refit_level_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, r.nodes, r.nnodes, d_order, count, r.tri_index, r.nslots,
+                                      r.attrs, r.ntri, (Bx *)r.boxes, pad);
 }
 
 // Builds on `stream` from the host triangle list; the four output arrays are device allocations owned by the caller

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -189,6 +190,10 @@ static void free_scene_device(evplp_context *c) {
     hipFree((void *)c->sc.nodes); hipFree((void *)c->sc.nodes4); hipFree((void *)c->sc.leaves); hipFree((void *)c->sc.tri_flat); hipFree((void *)c->sc.tri_index); hipFree((void *)c->sc.attrs);
     hipFree((void *)c->sc.materials); hipFree((void *)c->sc.textures); hipFree((void *)c->sc.tex_pool); hipFree((void *)c->sc.light_cdf);
     std::memset(&c->sc, 0, sizeof(c->sc));
+    // the refit's plan and staging belong to the tree (made by the first evplp_refit_accel)
+    hipFree(c->d_refit_order); hipFree(c->d_refit_boxes); hipFree(c->d_refit_stage); if (c->h_refit_stage) hipHostFree(c->h_refit_stage);
+    c->d_refit_order = nullptr; c->d_refit_boxes = c->d_refit_stage = c->h_refit_stage = nullptr;
+    c->refit_levels = 0; c->refit_level_begin.clear(); std::vector<BvhNode>().swap(c->host_nodes);
 }
 
 extern "C" void evplp_destroy(evplp_context *c) {
@@ -220,6 +225,8 @@ extern "C" void evplp_destroy(evplp_context *c) {
     if (c->ev_records_read) hipEventDestroy(c->ev_records_read);
     if (c->ev_light_done) hipEventDestroy(c->ev_light_done);
     if (c->ev_back_read) hipEventDestroy(c->ev_back_read);
+    if (c->ev_refit_staged) hipEventDestroy(c->ev_refit_staged);
+    for (int i = 0; i < 5; i++) if (c->ev_refit[i]) hipEventDestroy(c->ev_refit[i]);
     hipFree(c->records_back);
     for (int k = 0; k < 4; k++) hipFree(c->gbuf_back[k]);
     hipFree(c->d_tile_box_back);
@@ -324,6 +331,65 @@ template <class T> static int upload_array(evplp_context *c, const T *host, size
     return EVPLP_OK;
 }
 
+// the triangle soup in mesh order, 9 floats per triangle; first[m] = mesh m's first triangle, first[meshes] = all of them
+static void flatten_verts(const evplp_context *c, std::vector<float> &verts, std::vector<int32_t> &first) {
+    size_t ntri = 0;
+    first.clear();
+    for (const HostMesh &m : c->meshes) { first.push_back((int32_t)ntri); ntri += m.idx.size() / 3; }
+    first.push_back((int32_t)ntri);
+    verts.resize(9 * ntri);
+    float *o = verts.data();
+    for (const HostMesh &m : c->meshes)
+        for (size_t i = 0; i < m.idx.size(); i++, o += 3) std::memcpy(o, &m.verts[3 * (size_t)m.idx[i]], 12);
+}
+// What a scene carries besides its tree, from the flattened vertices: the area-light CDF (returned), light_area and the light's padded bounds,
+// total_area, bounding_radius.  evplp_build_accel and evplp_refit_accel both come here, so a refit's figures are a fresh build's.
+static void scene_scalars(evplp_context *c, const float *verts, int32_t light_first, int32_t light_count, std::vector<float> &cdf) {
+    // area-light CDF, rt/rtcommon.h:501-531 (running float sum, then normalised); Triangle::ComputeArea
+    auto tri_area = [](const float *v) {
+        float a[3] = { v[3] - v[0], v[4] - v[1], v[5] - v[2] }, b[3] = { v[6] - v[0], v[7] - v[1], v[8] - v[2] };
+        float cx = a[1] * b[2] - a[2] * b[1], cy = a[2] * b[0] - a[0] * b[2], cz = a[0] * b[1] - a[1] * b[0];
+        return std::sqrt(cx * cx + cy * cy + cz * cz) / 2.0f;
+    };
+    cdf.resize((size_t)light_count);
+    float sum = 0.f;
+    for (int32_t i = 0; i < light_count; i++) { sum += tri_area(verts + 9 * ((size_t)light_first + i)); cdf[i] = sum; }
+    for (int32_t i = 0; i < light_count; i++) cdf[i] /= sum;
+    // scene metrics (rtcommon.h:759-768, 805-814): per-mesh float sums, bbox over all vertices
+    float total = 0.f; float lo[3] = { 3.4028235e38f, 3.4028235e38f, 3.4028235e38f }, hi[3] = { -3.4028235e38f, -3.4028235e38f, -3.4028235e38f };
+    size_t tcur = 0;
+    for (const HostMesh &m : c->meshes) {
+        float ms = 0.f;
+        for (size_t t = 0; t < m.idx.size() / 3; t++) ms += tri_area(verts + 9 * tcur++);
+        total += ms;
+        for (size_t v = 0; v < m.verts.size() / 3; v++) for (int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], m.verts[3 * v + k]); hi[k] = std::max(hi[k], m.verts[3 * v + k]); }
+    }
+    float dg[3] = { std::max(hi[0] - lo[0], 0.f), std::max(hi[1] - lo[1], 0.f), std::max(hi[2] - lo[2], 0.f) };
+    c->bounding_radius = std::sqrt(dg[0] * dg[0] + dg[1] * dg[1] + dg[2] * dg[2]) / 2.0f;
+    c->total_area = total; c->light_area = sum; c->sc.light_area = sum;
+    // bounds of the light mesh, padded by far more than the rounding of a slab test
+    float llo[3] = { 3.0e38f, 3.0e38f, 3.0e38f }, lhi[3] = { -3.0e38f, -3.0e38f, -3.0e38f };
+    for (int32_t i = 0; i < light_count; i++) for (int k = 0; k < 9; k++) {
+        const float v = verts[9 * ((size_t)light_first + i) + k];
+        llo[k % 3] = std::min(llo[k % 3], v); lhi[k % 3] = std::max(lhi[k % 3], v);
+    }
+    const float pad = 1e-4f * (2.0f * c->bounding_radius) + 1e-30f;
+    for (int k = 0; k < 3; k++) { c->sc.light_lo[k] = llo[k] - pad; c->sc.light_hi[k] = lhi[k] + pad; }
+}
+// has_area[t] = triangle t is one the builders keep (tri_has_area); returns the builders' box pad for the bounds of those
+static float scene_pad(const float *verts, int32_t ntri, std::vector<char> &has_area) {
+    float lo[3] = { 3.0e38f, 3.0e38f, 3.0e38f }, hi[3] = { -3.0e38f, -3.0e38f, -3.0e38f };
+    has_area.assign((size_t)ntri, 0);
+    bool any = false;
+    for (int32_t t = 0; t < ntri; t++) {
+        const float *v = verts + 9 * (size_t)t;
+        if (!tri_has_area(v)) continue;
+        has_area[(size_t)t] = 1; any = true;
+        for (int k = 0; k < 9; k++) { lo[k % 3] = std::min(lo[k % 3], v[k]); hi[k % 3] = std::max(hi[k % 3], v[k]); }
+    }
+    return bvh_pad(lo, hi, any);
+}
+
 extern "C" int evplp_build_accel(evplp_context *c) {
     CTX_CHECK(c);
     HIP_TRY(c, hipSetDevice(c->cfg.device));
@@ -331,23 +397,20 @@ extern "C" int evplp_build_accel(evplp_context *c) {
     if (c->light_mesh < 0) { c->set_error("evplp_build_accel: no area light set"); return EVPLP_ERR_INVALID; }
     free_scene_device(c);
     // flatten to a triangle soup in mesh order
-    std::vector<float> verts; std::vector<TriAttr> attrs;
-    int32_t light_first = 0, light_count = 0;
+    std::vector<float> verts; std::vector<int32_t> first; std::vector<TriAttr> attrs;
+    flatten_verts(c, verts, first);
+    attrs.reserve((size_t)first.back());
     for (size_t mi = 0; mi < c->meshes.size(); mi++) {
         const HostMesh &m = c->meshes[mi];
-        if ((int)mi == c->light_mesh) { light_first = (int32_t)attrs.size(); light_count = (int32_t)(m.idx.size() / 3); }
         for (size_t t = 0; t < m.idx.size() / 3; t++) {
             TriAttr a; std::memset(&a, 0, sizeof(a));
-            for (int k = 0; k < 3; k++) {
-                int32_t vi = m.idx[3 * t + k];
-                for (int j = 0; j < 3; j++) a.v[3 * k + j] = m.verts[3 * (size_t)vi + j];
-                a.uv[2 * k] = m.uvs[2 * (size_t)vi]; a.uv[2 * k + 1] = m.uvs[2 * (size_t)vi + 1];
-            }
+            std::memcpy(a.v, &verts[9 * attrs.size()], sizeof(a.v));
+            for (int k = 0; k < 3; k++) { const int32_t vi = m.idx[3 * t + k]; a.uv[2 * k] = m.uvs[2 * (size_t)vi]; a.uv[2 * k + 1] = m.uvs[2 * (size_t)vi + 1]; }
             a.material = m.material;
             attrs.push_back(a);
-            verts.insert(verts.end(), a.v, a.v + 9);
         }
     }
+    const int32_t light_first = first[(size_t)c->light_mesh], light_count = first[(size_t)c->light_mesh + 1] - light_first;
     if (light_count <= 0) { c->set_error("evplp_build_accel: the area-light mesh has no triangles"); return EVPLP_ERR_INVALID; }
     BvhBuild bb;
     int builder = c->env_bvh_builder >= 0 ? c->env_bvh_builder : c->cfg.bvh_builder;   // (override read by evplp_create)
@@ -372,28 +435,16 @@ extern "C" int evplp_build_accel(evplp_context *c) {
     c->accel_builder_used = builder;
     c->accel_nodes = bb.nnodes; c->accel_leaves = bb.nleaves; c->accel_depth = bb.depth; c->accel_build_ms = bb.build_ms;
     if (bb.depth > kMaxDepth - 2) { free_bvh(&bb); free_scene_device(c); c->set_error("BVH depth %d exceeds the traversal stack (%d)", bb.depth, kMaxDepth); return EVPLP_ERR_INVALID; }
-    // area-light CDF, rt/rtcommon.h:501-531 (running float sum, then normalised); Triangle::ComputeArea
-    auto tri_area = [](const float *v) {
-        float a[3] = { v[3] - v[0], v[4] - v[1], v[5] - v[2] }, b[3] = { v[6] - v[0], v[7] - v[1], v[8] - v[2] };
-        float cx = a[1] * b[2] - a[2] * b[1], cy = a[2] * b[0] - a[0] * b[2], cz = a[0] * b[1] - a[1] * b[0];
-        return std::sqrt(cx * cx + cy * cy + cz * cz) / 2.0f;
-    };
-    std::vector<float> cdf((size_t)light_count);
-    float sum = 0.f;
-    for (int32_t i = 0; i < light_count; i++) { sum += tri_area(attrs[(size_t)light_first + i].v); cdf[i] = sum; }
-    for (int32_t i = 0; i < light_count; i++) cdf[i] /= sum;
-    // scene metrics (rtcommon.h:759-768, 805-814): per-mesh float sums, bbox over all vertices
-    float total = 0.f; float lo[3] = { 3.4028235e38f, 3.4028235e38f, 3.4028235e38f }, hi[3] = { -3.4028235e38f, -3.4028235e38f, -3.4028235e38f };
-    size_t tcur = 0;
-    for (const HostMesh &m : c->meshes) {
-        float ms = 0.f;
-        for (size_t t = 0; t < m.idx.size() / 3; t++) ms += tri_area(attrs[tcur++].v);
-        total += ms;
-        for (size_t v = 0; v < m.verts.size() / 3; v++) for (int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], m.verts[3 * v + k]); hi[k] = std::max(hi[k], m.verts[3 * v + k]); }
+    std::vector<float> cdf;
+    scene_scalars(c, verts.data(), light_first, light_count, cdf);
+    {   // which triangles the builders dropped (a refit cannot bring one back), and the builders' pad of this scene
+        std::vector<char> has_area;
+        c->accel_pad = scene_pad(verts.data(), first.back(), has_area);
+        c->tri_dropped.resize(has_area.size());
+        for (size_t t = 0; t < has_area.size(); t++) c->tri_dropped[t] = !has_area[t];
     }
-    float dg[3] = { std::max(hi[0] - lo[0], 0.f), std::max(hi[1] - lo[1], 0.f), std::max(hi[2] - lo[2], 0.f) };
-    c->bounding_radius = std::sqrt(dg[0] * dg[0] + dg[1] * dg[1] + dg[2] * dg[2]) / 2.0f;
-    c->total_area = total; c->light_area = sum;
+    c->scene_tris = first.back();
+    const float sum = c->light_area;
 
     // textures -> one float4 pool
     std::vector<TexDesc> tdesc; std::vector<float4> pool;
@@ -414,7 +465,8 @@ extern "C" int evplp_build_accel(evplp_context *c) {
         // Worst-case stack of the four-wide per-lane walk (closest_lane4: a visit pushes every entered grandchild but the nearest) over
         // the tree that was built: need(i) = (grandchildren of i) - 1 + max over inner grandchildren g of need(g).  Inner nodes are stored in
         // pre-order (children after parents), so one backward sweep does it.  The LDS stack is what limits the occupancy of light tracing.
-        std::vector<BvhNode> host_nodes;
+        // (the device builder's nodes come back once, here; the copy is kept for the level plan of a refit)
+        std::vector<BvhNode> &host_nodes = c->host_nodes;
         const BvhNode *hn = bb.nodes;
         if (!hn) { host_nodes.resize((size_t)bb.nnodes); HIP_TRY(c, hipMemcpy(host_nodes.data(), c->sc.nodes, sizeof(BvhNode) * (size_t)bb.nnodes, hipMemcpyDeviceToHost)); hn = host_nodes.data(); }
         std::vector<int32_t> need((size_t)bb.nnodes, 0);
@@ -442,17 +494,9 @@ extern "C" int evplp_build_accel(evplp_context *c) {
     if ((rc = upload_array(c, pool.data(), pool.size(), &c->sc.tex_pool))) return rc;
     if ((rc = upload_array(c, cdf.data(), cdf.size(), &c->sc.light_cdf))) return rc;
     c->sc.light_first = light_first; c->sc.light_count = light_count; c->sc.light_area = sum;
-    {   // bounds of the light mesh, padded by far more than the rounding of a slab test
-        float llo[3] = { 3.0e38f, 3.0e38f, 3.0e38f }, lhi[3] = { -3.0e38f, -3.0e38f, -3.0e38f };
-        for (int32_t i = 0; i < light_count; i++) for (int k = 0; k < 9; k++) {
-            const float v = attrs[(size_t)light_first + i].v[k];
-            llo[k % 3] = std::min(llo[k % 3], v); lhi[k % 3] = std::max(lhi[k % 3], v);
-        }
-        const float pad = 1e-4f * (2.0f * c->bounding_radius) + 1e-30f;
-        for (int k = 0; k < 3; k++) { c->sc.light_lo[k] = llo[k] - pad; c->sc.light_hi[k] = lhi[k] + pad; }
-    }
     std::memcpy(c->sc.light_intensity, c->light_scaled, 16); std::memcpy(c->sc.light_unscaled, c->light_unscaled, 16);
     c->accel_built = true; c->primary_cuts_valid = false;
+    c->mesh_dirty.assign(c->meshes.size(), 0); c->scene_dirty = false;
     return EVPLP_OK;
 }
 
@@ -472,6 +516,176 @@ extern "C" int evplp_accel_info(evplp_context *c, int32_t *nodes, int32_t *leave
 extern "C" int evplp_accel_builder(const evplp_context *c) {
     if (!c || !c->accel_built) return -1;
     return c->accel_builder_used;
+}
+
+// ---------------------------------------------------------------------------------- moving vertices: update, refit
+static_assert(offsetof(BvhNode, c0) == 48 && offsetof(BvhNode, c1) == 52, "host/refit_levels.cpp reads the child references at these offsets");
+
+namespace evplp {
+// evplp_update_mesh's refusals, for the group's caller thread as well (false: the reason is in c's error)
+bool update_mesh_check(evplp_context *c, int32_t mesh, const float *vertices, int32_t nverts) {
+    if (!c->accel_built) { c->set_error("evplp_update_mesh: scene not built (evplp_build_accel)"); return false; }
+    if (mesh < 0 || mesh >= (int32_t)c->meshes.size()) { c->set_error("evplp_update_mesh: mesh %d out of range (%zu meshes)", mesh, c->meshes.size()); return false; }
+    if (!vertices) { c->set_error("evplp_update_mesh: null vertices"); return false; }
+    const size_t have = c->meshes[(size_t)mesh].verts.size() / 3;
+    if (nverts < 0 || (size_t)nverts != have) { c->set_error("evplp_update_mesh: mesh %d has %zu vertices, not %d (the topology stays)", mesh, have, nverts); return false; }
+    for (size_t i = 0; i < 3 * have; i++) if (!std::isfinite(vertices[i])) { c->set_error("evplp_update_mesh: vertex %zu of mesh %d is not finite", i / 3, mesh); return false; }
+    return true;
+}
+// evplp_refit_accel's refusal: a triangle the build dropped (no area) that has one now has no leaf slot to go to
+bool refit_check(evplp_context *c) {
+    if (!c->accel_built) { c->set_error("evplp_refit_accel: scene not built (evplp_build_accel)"); return false; }
+    size_t first = 0;
+    for (size_t mi = 0; mi < c->meshes.size(); first += c->meshes[mi].idx.size() / 3, mi++) {
+        if (!c->scene_dirty || !c->mesh_dirty[mi]) continue;
+        const HostMesh &m = c->meshes[mi];
+        for (size_t t = 0; t < m.idx.size() / 3; t++) {
+            if (!c->tri_dropped[first + t]) continue;
+            float v[9];
+            for (int k = 0; k < 3; k++) std::memcpy(v + 3 * k, &m.verts[3 * (size_t)m.idx[3 * t + k]], 12);
+            if (tri_has_area(v)) {
+                c->set_error("evplp_refit_accel: triangle %zu of mesh %zu had no area when the tree was built and has one now: it has no leaf to go to, call evplp_build_accel", t, mi);
+                return false;
+            }
+        }
+    }
+    return true;
+}
+}
+
+extern "C" int evplp_update_mesh(evplp_context *c, int32_t mesh, const float *vertices, int32_t nverts) {
+    CTX_CHECK(c);
+    if (!evplp::update_mesh_check(c, mesh, vertices, nverts)) return EVPLP_ERR_INVALID;
+    std::memcpy(c->meshes[(size_t)mesh].verts.data(), vertices, sizeof(float) * 3 * (size_t)nverts);
+    c->mesh_dirty[(size_t)mesh] = 1; c->scene_dirty = true;
+    return EVPLP_OK;
+}
+
+// the level plan, the scratch and the staging arrays of a tree: made by its first refit
+static int refit_prepare(evplp_context *c) {
+    if (c->refit_levels > 0) return EVPLP_OK;
+    const int32_t nn = c->accel_nodes;
+    if (c->host_nodes.empty()) {            // (a host builder's tree: its child references come back once; the device builder's were kept)
+        c->host_nodes.resize((size_t)nn);
+        HIP_TRY(c, hipMemcpyAsync(c->host_nodes.data(), c->sc.nodes, sizeof(BvhNode) * (size_t)nn, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    std::vector<int32_t> height((size_t)nn), order((size_t)nn);
+    c->refit_level_begin.assign((size_t)kMaxDepth + 1, 0);
+    const int levels = evplp_refit_levels(c->host_nodes.data(), nn, height.data(), order.data(), c->refit_level_begin.data(), kMaxDepth);
+    std::vector<BvhNode>().swap(c->host_nodes);
+    if (levels < 1) { c->set_error("evplp_refit_accel: the node array is not a tree of at most %d levels", kMaxDepth); return EVPLP_ERR_INVALID; }
+    const size_t stage = 9 * (size_t)c->scene_tris + (size_t)c->sc.light_count;
+    hipError_t e = hipMalloc((void **)&c->d_refit_order, sizeof(int32_t) * (size_t)nn);
+    if (e == hipSuccess) e = hipMalloc((void **)&c->d_refit_boxes, sizeof(float) * 6 * (size_t)nn);
+    if (e == hipSuccess) e = hipMalloc((void **)&c->d_refit_stage, sizeof(float) * stage);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_refit_stage, sizeof(float) * stage, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMemcpy(c->d_refit_order, order.data(), sizeof(int32_t) * (size_t)nn, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !c->ev_refit_staged) e = hipEventCreateWithFlags(&c->ev_refit_staged, hipEventDisableTiming);
+    for (int i = 0; i < 5 && e == hipSuccess; i++) if (!c->ev_refit[i]) e = hipEventCreate(&c->ev_refit[i]);
+    if (e != hipSuccess) { c->set_error("evplp_refit_accel: plan and staging: %s", hipGetErrorString(e)); return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP; }
+    c->refit_levels = levels;
+    return EVPLP_OK;
+}
+
+extern "C" int evplp_refit_accel(evplp_context *c) {
+    CTX_CHECK(c);
+    if (!evplp::refit_check(c)) return EVPLP_ERR_INVALID;
+    if (!c->scene_dirty) return EVPLP_OK;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    // (a photon splat whose verdict is still out is not waited for: a splat reads records and the G-buffer, never the scene)
+    int rc = refit_prepare(c); if (rc) return rc;
+    std::vector<float> verts; std::vector<int32_t> first;
+    flatten_verts(c, verts, first);
+    std::vector<char> has_area;
+    const float pad = scene_pad(verts.data(), first.back(), has_area);
+    // 5. the host's figures, by the code evplp_build_accel uses (in front of the launches, so that they follow each other without a gap)
+    std::vector<float> cdf;
+    scene_scalars(c, verts.data(), c->sc.light_first, c->sc.light_count, cdf);
+    // Everything below is enqueued on the context's stream, behind every pass it was given -- the light tracing of overlap_light_tracing
+    // included: the call that put it on the second stream made this stream wait for it.
+    const bool timed = c->profile_passes, stages = timed && c->profile_kernels;
+    if (c->refit_count > 0) HIP_TRY(c, hipEventSynchronize(c->ev_refit_staged));     // (the last refit's copies have left the pinned array: long ago)
+    // 1. the dirty meshes' triangles, packed, in one copy; one scatter per run of neighbouring dirty meshes
+    size_t staged = 0;
+    for (size_t mi = 0; mi < c->meshes.size(); mi++) if (c->mesh_dirty[mi]) {
+        const size_t n = 9 * (size_t)(first[mi + 1] - first[mi]);
+        std::memcpy(c->h_refit_stage + staged, &verts[9 * (size_t)first[mi]], sizeof(float) * n);
+        staged += n;
+    }
+    if (timed) HIP_TRY(c, hipEventRecord(c->ev_refit[0], c->stream));
+    if (staged) HIP_TRY(c, hipMemcpyAsync(c->d_refit_stage, c->h_refit_stage, sizeof(float) * staged, hipMemcpyHostToDevice, c->stream));
+    staged = 0;
+    for (size_t mi = 0; mi < c->meshes.size();) {
+        if (!c->mesh_dirty[mi]) { mi++; continue; }
+        size_t me = mi; while (me < c->meshes.size() && c->mesh_dirty[me]) me++;
+        const int32_t count = first[me] - first[mi];
+        refit_scatter(c->d_refit_stage + staged, first[mi], count, (TriAttr *)c->sc.attrs, c->stream);
+        staged += 9 * (size_t)count; mi = me;
+    }
+    if (stages) HIP_TRY(c, hipEventRecord(c->ev_refit[1], c->stream));
+    // 2. leaf operands  3. boxes, one launch per height  4. four-wide nodes
+    RefitScene r; std::memset(&r, 0, sizeof(r));
+    r.nodes = (BvhNode *)c->sc.nodes; r.nnodes = c->accel_nodes; r.leaves = (LeafBlock *)c->sc.leaves; r.tri_flat = (TriFlat *)c->sc.tri_flat; r.tri_index = c->sc.tri_index;
+    r.nslots = 4 * c->accel_leaves; r.attrs = c->sc.attrs; r.ntri = c->scene_tris; r.boxes = c->d_refit_boxes;
+    refit_leaves(r, c->stream);
+    if (stages) HIP_TRY(c, hipEventRecord(c->ev_refit[2], c->stream));
+    for (int32_t l = 0; l < c->refit_levels; l++)
+        refit_level(r, c->d_refit_order + c->refit_level_begin[(size_t)l], c->refit_level_begin[(size_t)l + 1] - c->refit_level_begin[(size_t)l], pad, c->stream);
+    if (stages) HIP_TRY(c, hipEventRecord(c->ev_refit[3], c->stream));
+    build_nodes4_into(c->sc.nodes, c->accel_nodes, c->stream, (BvhNode4 *)c->sc.nodes4);
+    // 5. ... the CDF goes up only if the light moved
+    if (c->mesh_dirty[(size_t)c->light_mesh]) {
+        float *h = c->h_refit_stage + 9 * (size_t)c->scene_tris;
+        std::memcpy(h, cdf.data(), sizeof(float) * cdf.size());
+        HIP_TRY(c, hipMemcpyAsync((void *)c->sc.light_cdf, h, sizeof(float) * cdf.size(), hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(c, hipEventRecord(c->ev_refit_staged, c->stream));
+    if (timed) HIP_TRY(c, hipEventRecord(c->ev_refit[4], c->stream));
+    if (c->aux_stream) HIP_TRY(c, hipStreamWaitEvent(c->aux_stream, c->ev_refit_staged, 0));      // (light paths given to the second stream from here on see the new tree)
+    HIP_TRY(c, hipGetLastError());
+    c->accel_pad = pad; c->refit_timed = timed; c->refit_stages_timed = stages; c->refit_count++;
+    c->primary_cuts_valid = false; c->tile_box_valid = false;
+    std::fill(c->mesh_dirty.begin(), c->mesh_dirty.end(), 0); c->scene_dirty = false;
+    return EVPLP_OK;
+}
+
+extern "C" int evplp_refit_info(evplp_context *c, int32_t *refits, int32_t *levels, float *last_refit_ms) {
+    CTX_CHECK(c);
+    if (refits) *refits = c->refit_count;
+    if (levels) *levels = c->refit_levels;
+    if (last_refit_ms) {
+        *last_refit_ms = 0.f;
+        if (c->refit_count > 0 && c->refit_timed) {
+            HIP_TRY(c, hipSetDevice(c->cfg.device));
+            HIP_TRY(c, hipEventSynchronize(c->ev_refit[4]));
+            HIP_TRY(c, hipEventElapsedTime(last_refit_ms, c->ev_refit[0], c->ev_refit[4]));
+        }
+    }
+    return EVPLP_OK;
+}
+
+extern "C" int evplp_debug_accel(evplp_context *c, int32_t which, void *host_dst, size_t bytes) {
+    CTX_CHECK(c);
+    if (!c->accel_built || !host_dst) { c->set_error("evplp_debug_accel: no scene (evplp_build_accel) or a null destination"); return EVPLP_ERR_INVALID; }
+    const size_t nn = (size_t)std::max(c->accel_nodes, 1), nl = (size_t)std::max(c->accel_leaves, 1);
+    const void *src[5] = { c->sc.nodes, c->sc.leaves, c->sc.tri_flat, c->sc.tri_index, c->sc.nodes4 };
+    const size_t want[7] = { sizeof(BvhNode) * nn, sizeof(LeafBlock) * nl, sizeof(TriFlat) * 4 * nl, sizeof(int32_t) * 4 * nl, sizeof(BvhNode4) * nn, sizeof(float), sizeof(float) * 4 };
+    if (which < 0 || which > 6 || bytes != want[which]) { c->set_error("evplp_debug_accel: array %d holds %zu bytes, not %zu", which, which >= 0 && which <= 6 ? want[which] : (size_t)0, bytes); return EVPLP_ERR_INVALID; }
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    if (which == 5) { std::memcpy(host_dst, &c->accel_pad, sizeof(float)); return EVPLP_OK; }
+    if (which == 6) {                       // the last refit's stages in ms: upload, leaf operands, boxes, four-wide nodes (zeros unless evplp_profile_kernels was on)
+        float ms[4] = { 0.f, 0.f, 0.f, 0.f };
+        if (c->refit_count > 0 && c->refit_stages_timed) {
+            HIP_TRY(c, hipEventSynchronize(c->ev_refit[4]));
+            for (int i = 0; i < 4; i++) HIP_TRY(c, hipEventElapsedTime(&ms[i], c->ev_refit[i], c->ev_refit[i + 1]));
+        }
+        std::memcpy(host_dst, ms, sizeof(ms));
+        return EVPLP_OK;
+    }
+    HIP_TRY(c, hipMemcpyAsync(host_dst, src[which], bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return EVPLP_OK;
 }
 
 // ---------------------------------------------------------------------------------- passes
@@ -536,6 +750,7 @@ static int settle_readers_of(evplp_context *c, const void *records, const void *
 }
 static int pass_ready(evplp_context *c, const char *name, bool need_camera, bool settle = true) {
     if (!c->accel_built) { c->set_error("%s: scene not built (evplp_build_accel)", name); return EVPLP_ERR_INVALID; }
+    if (c->scene_dirty) { c->set_error("%s: vertices were updated (evplp_update_mesh): call evplp_refit_accel or evplp_build_accel first", name); return EVPLP_ERR_INVALID; }
     if (need_camera && !c->camera_set) { c->set_error("%s: camera not set", name); return EVPLP_ERR_INVALID; }
     hipError_t e = hipSetDevice(c->cfg.device);
     if (e != hipSuccess) { c->set_error("hipSetDevice: %s", hipGetErrorString(e)); return EVPLP_ERR_HIP; }
@@ -1403,6 +1618,7 @@ extern "C" int evplp_denoise(evplp_context *c, float scale, float ls, int32_t ma
         return EVPLP_ERR_INVALID;
     }
     if (!c->accel_built) { c->set_error("evplp_denoise: no scene (evplp_build_accel): the position term needs its bounding sphere"); return EVPLP_ERR_INVALID; }
+    if (c->scene_dirty) { c->set_error("evplp_denoise: vertices were updated (evplp_update_mesh): call evplp_refit_accel or evplp_build_accel first"); return EVPLP_ERR_INVALID; }
     int rc = noise_ready(c, "evplp_denoise");
     if (rc) return rc;
     if ((rc = evplp::noise_variance_to_device(c, evplp::noise_moments_of(c), (double)c->noise_k, (double)c->noise_b, scale))) return rc;

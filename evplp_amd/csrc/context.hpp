@@ -11,6 +11,11 @@ namespace evplp {
 // bvh_gpu.hip: LBVH built on the device (arrays are device allocations owned by the caller)
 int build_bvh_gpu(const float *verts_host, int32_t ntri, float pad_scale, hipStream_t stream, BvhDeviceBuild *out);
 int build_nodes4(const BvhNode *d_nodes, int32_t nnodes, hipStream_t stream, BvhNode4 **out);
+void build_nodes4_into(const BvhNode *d_nodes, int32_t nnodes, hipStream_t stream, BvhNode4 *out);      // in place: enqueued, no allocation, no wait
+// bvh_gpu.hip: the launches of evplp_refit_accel (enqueued; d_src: 9 floats per triangle of the run; d_order: the nodes of one height)
+void refit_scatter(const float *d_src, int32_t first, int32_t count, TriAttr *attrs, hipStream_t stream);
+void refit_leaves(const RefitScene &r, hipStream_t stream);
+void refit_level(const RefitScene &r, const int32_t *d_order, int32_t count, float pad, hipStream_t stream);
 struct HostMesh { std::vector<float> verts, uvs; std::vector<int32_t> idx; int32_t material = 0; };
 struct HostTexture { int32_t w = 0, h = 0; std::vector<float> rgba; };
 struct HostStats { uint64_t rays = 0; };
@@ -26,6 +31,9 @@ void sum_row_errors(const std::vector<RowError> &rows, const std::vector<char> &
 
 struct evplp_context;
 namespace evplp {
+// what evplp_update_mesh / evplp_refit_accel refuse (context.cpp), for the group's caller thread as well: false and the reason in c's error
+bool update_mesh_check(evplp_context *c, int32_t mesh, const float *vertices, int32_t nverts);
+bool refit_check(evplp_context *c);
 // evplp_noise_* (context.cpp), for the group's workers as well
 NoisePlanes noise_planes(const evplp_context *c);
 NoiseMoments noise_moments_of(const evplp_context *c);           // a context's own moments (S = c_prev - c_start)
@@ -86,6 +94,17 @@ struct evplp_context {
     bool camera_set = false, accel_built = false;
     float bounding_radius = 0.f, total_area = 0.f, light_area = 0.f;
     int32_t accel_nodes = 0, accel_leaves = 0, accel_depth = 0, accel_builder_used = -1; float accel_build_ms = 0.f;
+
+    // evplp_update_mesh / evplp_refit_accel.  mesh_dirty[m]: mesh m's vertices changed since the device scene was made (scene_dirty: any of
+    // them; every pass then refuses).  tri_dropped[t]: original triangle t had no area at the build and so has no leaf slot.  The rest is
+    // made by the first refit and freed with the scene: the level plan (evplp_refit_levels over host_nodes, the node array of the build),
+    // its order on the device, 6 floats per node of scratch, a device and a pinned host staging array for the moved vertices and the light's
+    // CDF ([9 * triangles + light triangles] floats; ev_refit_staged: the last refit's copies have left the pinned one).
+    std::vector<char> mesh_dirty, tri_dropped; bool scene_dirty = false;
+    std::vector<evplp::BvhNode> host_nodes; std::vector<int32_t> refit_level_begin; int32_t refit_levels = 0;
+    int32_t *d_refit_order = nullptr; float *d_refit_boxes = nullptr, *d_refit_stage = nullptr, *h_refit_stage = nullptr;
+    hipEvent_t ev_refit_staged = nullptr, ev_refit[5] = {}; bool refit_timed = false, refit_stages_timed = false;
+    int32_t refit_count = 0, scene_tris = 0; float accel_pad = 0.f;
 
     evplp::SceneDev sc{};
     evplp_record *d_vpls = nullptr; uint32_t *d_vpl_src = nullptr;

@@ -1,5 +1,6 @@
 // Internal data layout of libevplp_hip.so (host + device).  See DESIGN.md "Data layout in HBM".
 #pragma once
+#include <math.h>
 #include <stdint.h>
 #include <hip/hip_runtime.h>
 #include "../../include/evplp.h"
@@ -135,6 +136,25 @@ struct StripDev {
     }
 };
 
+// meshBound's rule (rt/triangleintersect.cu:62-81): a triangle is in the tree iff area = |cross(v1-v0, v2-v0)| is > 0 and finite.  v: 9 floats.
+// Every operation rounds on its own (no contraction), on the host and on the device alike: the builders and a refit must agree on it.
+__host__ __device__ inline bool tri_has_area(const float *v) {
+#pragma clang fp contract(off)
+    const float a[3] = { v[3] - v[0], v[4] - v[1], v[5] - v[2] }, b[3] = { v[6] - v[0], v[7] - v[1], v[8] - v[2] };
+    const float c[3] = { a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0] };
+    const float area = sqrtf(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
+    return area > 0.0f && area <= 3.4028235e38f;                          // (> 0 and not infinite; a NaN fails the first)
+}
+
+// What the refit kernels of bvh_gpu.hip work on (evplp_refit_accel): the tree in place, the attributes with the moved vertices, and
+// boxes = 6 floats per node of scratch (the unpadded box under every node, handed from one height's launch to the next)
+struct RefitScene {
+    BvhNode *nodes; int32_t nnodes;
+    LeafBlock *leaves; TriFlat *tri_flat; const int32_t *tri_index; int32_t nslots;     // nslots = 4 * leaf blocks
+    const TriAttr *attrs; int32_t ntri;                                                // ORIGINAL triangles
+    float *boxes;
+};
+
 // Host-side acceleration structure build result
 struct BvhBuild {
     BvhNode *nodes = nullptr; int32_t nnodes = 0;
@@ -154,6 +174,8 @@ struct BvhDeviceBuild {
 int build_bvh(const float *verts, int32_t ntri, int builder, BvhBuild *out);
 // box padding of both builders, as a fraction of the scene diagonal (bvh_build.cpp explains the value)
 float bvh_pad_scale();
+// the pad itself for a scene whose valid triangles lie in [lo, hi] (any = false: there are none)
+float bvh_pad(const float lo[3], const float hi[3], bool any);
 void free_bvh(BvhBuild *b);
 
 } // namespace evplp

@@ -66,7 +66,7 @@ struct Rccl {
 };
 
 enum Op { OP_QUIT = 0, OP_CLEAR, OP_SYNC, OP_PRIMARY, OP_TRACE, OP_GATHER, OP_SPLAT, OP_PATH_TRACE, OP_PRESENT, OP_LOAD_SCENE, OP_SET_PROXY, OP_ASSEMBLE, OP_REDUCE, OP_SET_REFERENCE, OP_FRAME_ERROR,
-          OP_NOISE_TRACK, OP_NOISE_FOLD, OP_NOISE_POOL, OP_NOISE_ROWS, OP_NOISE_VARIANCE, OP_ADAPT_ENABLE, OP_ADAPT_RETIRE, OP_DENOISE_PREP, OP_DENOISE_FILTER, OP_PATH_TRACE_BATCH, OP_ADAPT_SET_BUDGETS, OP_ADAPT_TILE_NOISE };
+          OP_NOISE_TRACK, OP_NOISE_FOLD, OP_NOISE_POOL, OP_NOISE_ROWS, OP_NOISE_VARIANCE, OP_ADAPT_ENABLE, OP_ADAPT_RETIRE, OP_DENOISE_PREP, OP_DENOISE_FILTER, OP_PATH_TRACE_BATCH, OP_ADAPT_SET_BUDGETS, OP_ADAPT_TILE_NOISE, OP_UPDATE_MESH, OP_REFIT };
 // One posted call, copied into the ring by assignment: plain data (pointers must stay valid until the caller has drained: load_scene, set_proxy,
 // resolve do) but for `batch`, a shared pointer -- so every post and every worker-side copy of a command pays one atomic reference count, null or not.
 struct Cmd {
@@ -407,6 +407,8 @@ static void worker_run(Worker *w, const Cmd &cmd) {
         case OP_PRESENT: rc = evplp::resolve_to_device(c, cmd.f[0], cmd.f[1], cmd.f[2], cmd.i[0], cmd.i[1], cmd.i[2] != 0 || !c->aux_stream, cmd.u[0] == 0); break;   // (u[0]: the composite evplp_group_frame_error measures)
         case OP_LOAD_SCENE: rc = evplp_load_scene_json(c, (const char *)cmd.p0); break;
         case OP_SET_PROXY: rc = evplp_set_splat_proxy(c, (const float *)cmd.p0, cmd.i[0], (const int32_t *)cmd.p1, cmd.i[1]); break;
+        case OP_UPDATE_MESH: rc = evplp_update_mesh(c, cmd.i[0], (const float *)cmd.p0, cmd.i[1]); break;
+        case OP_REFIT: rc = evplp_refit_accel(c); break;
         case OP_SET_REFERENCE: rc = evplp_set_error_reference(c, (const float *)cmd.p0, (const uint8_t *)cmd.p1); break;
         case OP_FRAME_ERROR: rc = evplp::frame_error_rows(c); break;          // (behind this rank's composite, on its stream)
         case OP_NOISE_TRACK: rc = evplp_noise_track(c, cmd.i[0], (const uint8_t *)cmd.p0); break;
@@ -510,6 +512,8 @@ static int post_all(evplp_group *g, const Cmd &cmd) {
 }
 // a pass call: every rank (strips), or the selected rank alone (EVPLP_PARTITION_ITERATIONS; the cached sums are stale from here on)
 static int post_pass(evplp_group *g, const Cmd &cmd) {
+    // (refused here, on the caller's thread, so that a forgotten refit is not a sticky worker failure; the flag only changes in calls that wait)
+    if (g->ctx[0]->scene_dirty) { g->set_error("vertices were updated (evplp_group_update_mesh): call evplp_group_refit_accel, or evplp_build_accel on every rank, first"); return EVPLP_ERR_INVALID; }
     if (!g->iterations) return post_all(g, cmd);
     g->sums_fresh = false;
     if (g->failed.load(std::memory_order_acquire)) { drain(g); return group_status(g); }
@@ -788,6 +792,24 @@ extern "C" int evplp_group_set_splat_proxy(evplp_group *g, const float *vertices
     Cmd c; c.op = OP_SET_PROXY; c.p0 = vertices; c.p1 = indices; c.i[0] = nverts; c.i[1] = ntris;
     return post_and_wait(g, c);
 }
+// Every rank holds the whole scene (both partitions): the update and the refit go to all of them.  What the context refuses without touching
+// a device is refused here first, against rank 0's copy (the ranks' scenes are the same), so that a refusal is not a sticky worker failure.
+extern "C" int evplp_group_update_mesh(evplp_group *g, int32_t mesh, const float *vertices, int32_t nverts) {
+    GRP_CHECK(g);
+    drain(g);
+    if (!evplp::update_mesh_check(g->ctx[0], mesh, vertices, nverts)) { g->set_error("%s", g->ctx[0]->error); return EVPLP_ERR_INVALID; }
+    g->sums_fresh = false;
+    Cmd c; c.op = OP_UPDATE_MESH; c.p0 = vertices; c.i[0] = mesh; c.i[1] = nverts;
+    return post_and_wait(g, c);
+}
+extern "C" int evplp_group_refit_accel(evplp_group *g) {
+    GRP_CHECK(g);
+    drain(g);
+    if (!evplp::refit_check(g->ctx[0])) { g->set_error("%s", g->ctx[0]->error); return EVPLP_ERR_INVALID; }
+    g->sums_fresh = false;
+    Cmd c; c.op = OP_REFIT;
+    return post_and_wait(g, c);
+}
 extern "C" int evplp_group_path_trace(evplp_group *g, const float camera_pos[3], uint32_t rng_seed, uint32_t max_bounces, int32_t do_accumulate) {
     GRP_CHECK(g);
     if (!camera_pos) { g->set_error("evplp_group_path_trace: null camera position"); return EVPLP_ERR_INVALID; }
@@ -1008,6 +1030,7 @@ extern "C" int evplp_group_denoise(evplp_group *g, float scale, float ls, int32_
     int rc = noise_group_ready(g, "evplp_group_denoise");
     if (rc < 0) return rc;
     if (!g->ctx[0]->accel_built) { g->set_error("evplp_group_denoise: no scene (evplp_group_load_scene_json / evplp_build_accel)"); return EVPLP_ERR_INVALID; }
+    if (g->ctx[0]->scene_dirty) { g->set_error("evplp_group_denoise: vertices were updated (evplp_group_update_mesh): call evplp_group_refit_accel first"); return EVPLP_ERR_INVALID; }
     if (!g->iterations) {
         // every rank's packed pixels and receive buffer exist before any worker names them in the all-gather (the workers are idle here)
         for (int r = 0; r < g->n; r++) {

@@ -128,6 +128,7 @@ typedef struct evplp_config {
      *                                   path-trace adaptive mode, sum(s_t) in budget mode (evplp_adaptive_enable_pt(ctx, 2));
      *                                   + 4 B per tile and 4 B per item of the largest call (the item table);
      *                                   budget mode: + 8 B per tile after evplp_adaptive_tile_noise
+     *   refit (after a call)            28 B per node + 36 B per triangle (+ 4 B per light triangle), and the same staging bytes in pinned host memory (evplp_refit_accel)
      *   denoiser (after a call)         124 B per pixel of the context's planes (evplp_denoise); a group's rank: 92 B per pixel of its planes
      *                                   + n x 80 B per pixel of the exchanged rows, and rank 0 + 112 B per image pixel (evplp_group_denoise)
      * A caller that has the device to itself sets cut_scratch_bytes = 72 GB, vsl_mask_bytes = 14 GB for config #5 (one band, one launch). */
@@ -249,6 +250,40 @@ int evplp_get_camera(evplp_context *ctx, evplp_camera *out);
 int evplp_build_accel(evplp_context *ctx);
 /* RtScene::findBoundingSphereRadius (rtcommon.h:805-814), totalArea (:759-768), light area (:529) */
 int evplp_scene_metrics(evplp_context *ctx, float *bounding_sphere_radius, float *total_area, float *light_area);
+
+/* ---- scenes that move: new vertex positions for a mesh, then a refit of the tree on the device (INTEGRATION B7) ----
+ * evplp_update_mesh replaces the positions of mesh `mesh` (host pointer, float3[nverts], copied before the call returns); topology, texture
+ * coordinates and material stay, so nverts must be the mesh's vertex count.  It touches the host copy only and marks the mesh dirty; several
+ * calls may precede one refit.  EVPLP_ERR_INVALID, the context staying usable: no evplp_build_accel yet, mesh out of range, another vertex
+ * count, a null pointer, a coordinate that is not finite.
+ * While any mesh is dirty EVERY pass is refused (primary, light tracing, the gathers, the splat, both path tracers, the denoiser) with a
+ * message that names the two ways out: a stale tree under new vertices never renders.
+ *   evplp_refit_accel keeps the tree's topology and leaf assignment and recomputes, on the device and on the context's stream (behind every
+ *     pass already enqueued, the light tracing of overlap_light_tracing included; no host wait in the steady state): the dirty triangles'
+ *     vertices, every leaf's triangle operands, all boxes bottom-up (one launch per height of the tree, padded once from the exact union
+ *     with the builders' pad for the new scene bounds) and the four-wide nodes; and on the host the light's CDF and area, the light bounds,
+ *     total_area and bounding_radius, by the code evplp_build_accel uses.  Visibility and closest hit are exact predicates over the
+ *     triangles, so a frame over the refitted tree equals the frame of a fresh build bit for bit; what ages is the tree's quality -- after
+ *     large motions the walks visit more nodes, and evplp_build_accel is the remedy.  Nothing dirty: returns EVPLP_OK and launches nothing.
+ *     The first refit of a tree makes its plan (evplp_refit_levels) and allocates 28 B per node + 36 B per triangle on the device.
+ *   evplp_build_accel on a dirty context is the full rebuild from the updated meshes and clears the dirty state too.
+ * Degenerate triangles (meshBound's rule: area not > 0 or not finite): one that BECOMES degenerate gets all-zero operands and adds nothing
+ * to a box -- what a fresh build does by dropping it.  One that was dropped at build time and has an area now has no leaf to go to:
+ * evplp_refit_accel returns EVPLP_ERR_INVALID, the context stays dirty, and evplp_build_accel is the way out.
+ * A refit leaves the accumulators, the noise moments and the adaptive records alone: a caller who moves geometry under an accumulation
+ * clears them (evplp_clear_accumulators) as after a camera change. */
+int evplp_update_mesh(evplp_context *ctx, int32_t mesh, const float *vertices, int32_t nverts);
+int evplp_refit_accel(evplp_context *ctx);
+/* refits since evplp_create, heights of the current tree's plan (0 before its first refit), HIP-event time of the last refit (0 while
+ * evplp_profile_passes is off; waits for that refit).  Each pointer may be null. */
+int evplp_refit_info(evplp_context *ctx, int32_t *refits, int32_t *levels, float *last_refit_ms);
+/* The plan of a refit (host only, no GPU, deterministic): nodes64 = nnodes flattened nodes of 64 B, the child references two int32 at byte
+ * 48 and 52 (>= 0: a node index; < 0: a leaf or an absent child); node 0 is the root.  height[i] (nnodes ints) = 0 for a node without inner
+ * children, else 1 + the larger of its inner children's, -1 for a node the root does not reach; order (nnodes ints) = the reached nodes by
+ * height, by index within a height; level_begin (level_capacity + 1 ints): height l is order[level_begin[l] .. level_begin[l + 1]).  No
+ * storage order is assumed.  Returns the number of heights (>= 1), or EVPLP_ERR_INVALID -- always promptly -- for a child index >= nnodes, a
+ * node reached twice (two parents, a cycle), more heights than level_capacity, null arrays, nnodes < 1. */
+int evplp_refit_levels(const void *nodes64, int32_t nnodes, int32_t *height, int32_t *order, int32_t *level_begin, int32_t level_capacity);
 
 /* ---- the per-iteration passes of RtComPhoton::run() (rtcomphoton.h:936-1068) ---- */
 /* [deferredShading] + [lightRender]: runDeferredProgram (:710-754) + runLightProgram (:839-855);
@@ -581,6 +616,12 @@ int evplp_profile_passes(evplp_context *ctx, int32_t on);
 /* Raw device-side counters of the last run of `pass` (rays, node visits, pairs, aux, then the traversal histogram that
  * only -DEVPLP_TRAVERSAL_STATS=1 diagnostic builds fill).  Returns the number of 64-bit words written. */
 int evplp_debug_counters(evplp_context *ctx, int32_t pass, uint64_t *out, int32_t capacity);
+/* For tests: the acceleration structure as it is on the device, copied to the host.  which = 0 nodes (64 B each), 1 leaf blocks (192 B),
+ * 2 the flat triangle operands (48 B per slot, 4 slots per block), 3 the slots' original triangle indices (int32, -1 = empty), 4 the
+ * four-wide nodes (128 B), 5 one float: the box pad of the last build or refit (the host builders' formula), 6 four floats: the last refit's
+ * upload, leaf, box and four-wide stages in ms (zeros unless evplp_profile_kernels was on).  bytes must be the array's size exactly (counts
+ * from evplp_accel_info, at least one node and one block): EVPLP_ERR_INVALID otherwise.  Waits for the stream. */
+int evplp_debug_accel(evplp_context *ctx, int32_t which, void *host_dst, size_t bytes);
 /* Flattened acceleration structure statistics: nodes, leaves, max depth, build ms */
 int evplp_accel_info(evplp_context *ctx, int32_t *nodes, int32_t *leaves, int32_t *depth, float *build_ms);
 /* The builder evplp_build_accel actually used (an evplp_bvh_builder value): cfg.bvh_builder unless the test override
@@ -678,6 +719,10 @@ int evplp_group_trace_light_paths(evplp_group *g, uint32_t rng_seed);
 int evplp_group_gather(evplp_group *g, const evplp_frame_params *fp, int32_t kind);   /* 0 evplp_gather_vpl, 1 _vsl, 2 _lvc */
 int evplp_group_splat_photons(evplp_group *g, const evplp_frame_params *fp, int32_t clear);
 int evplp_group_set_splat_proxy(evplp_group *g, const float *vertices, int32_t nverts, const int32_t *indices, int32_t ntris);
+/* evplp_update_mesh / evplp_refit_accel on every rank (both partitions; the calls wait for the ranks).  Refused on the caller's thread, the
+ * group staying usable, where the plain context refuses. */
+int evplp_group_update_mesh(evplp_group *g, int32_t mesh, const float *vertices, int32_t nverts);
+int evplp_group_refit_accel(evplp_group *g);
 int evplp_group_path_trace(evplp_group *g, const float camera_pos[3], uint32_t rng_seed, uint32_t max_bounces, int32_t do_accumulate);
 /* evplp_path_trace_batch, routed like evplp_group_path_trace: a strips group runs it on every rank for its own rows (the result equals one
  * context's bit for bit; evplp_set_blocks / evplp_group_rebalance behave as for evplp_group_path_trace), an iterations group on the selected

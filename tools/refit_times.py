@@ -1,0 +1,168 @@
+"""What a moving scene costs (evplp_update_mesh + evplp_refit_accel) beside a rebuild.  One process, the furnished stand-in
+(evplp_synth_scene, style "hard", 331 k triangles), `reps` repetitions each, median with p10 - p90.
+
+  (1) evplp_refit_accel after moving (a) one chair's mesh, (b) every mesh by a small translation: HIP events on the context's stream
+      (evplp_refit_info; the stages -- vertex upload, leaf operands, boxes with the number of launches, four-wide nodes -- from
+      evplp_debug_accel(6) under evplp_profile_kernels) and the host's wall time of the update calls and of the refit call.
+  (2) evplp_build_accel with the default SAH builder and with the device LBVH: accel_info()["build_ms"] and the wall time of the call.
+  (3) the config-#2 gather (tools/quick_bench.py's pass: 1024 x 1024, 1024 VPL paths, misMode one) over three trees of the SAME moved scene
+      (b): the refitted SAH tree, a rebuilt SAH tree, a rebuilt device LBVH.
+  (4) the same for a large motion: every chair displaced by a metre in a seeded direction -- what the topology's ageing costs.
+
+usage: python tools/refit_times.py [--reps N] [--tris N] [--res N]"""
+import argparse
+import math
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402,F401  (first, so libevplp_hip.so binds to the HIP runtime torch loaded)
+import evplp_amd as ev  # noqa: E402
+import scenes  # noqa: E402
+
+P, NL = 4, 1024
+GPU_BUILDER = ev.BVH_LBVH_GPU
+F = np.float32
+# synth_scene.cpp places the chairs here (style "hard"); every chair is one object = one mesh
+CHAIRS = [(0.9 + 1.37 * i, y) for i in range(7) for y in (-1.9, 3.9)] + [(-1.0, 1.0), (11.0, 1.0)]
+
+
+def spread(xs):
+    xs = sorted(xs)
+    q = lambda f: xs[min(len(xs) - 1, int(round(f * (len(xs) - 1))))]
+    return "%9.3f  (%.3f - %.3f)" % (statistics.median(xs), q(0.1), q(0.9))
+
+
+def chair_meshes(sd):
+    out = []
+    for k, m in enumerate(sd.meshes):
+        lo, hi = m["verts"].min(0), m["verts"].max(0)
+        c = 0.5 * (lo + hi)
+        if k != sd.light_mesh and lo[2] < 0.1 and 1.0 < hi[2] < 1.9 and max(hi[0] - lo[0], hi[1] - lo[1]) < 1.7 and any(math.hypot(c[0] - x, c[1] - y) < 0.5 for x, y in CHAIRS):
+            out.append(k)
+    return out
+
+
+def context(sd, res, builder, verts=None):
+    c = ev.Context(res, res, NL, NL, P, bvh_builder=builder)
+    if verts is None:
+        sd.upload(c)
+    else:
+        moved = scenes.SceneData.__new__(scenes.SceneData)
+        moved.__dict__.update(sd.__dict__)
+        moved.meshes = [dict(m, verts=verts[k]) for k, m in enumerate(sd.meshes)]
+        moved.upload(c)
+    return c
+
+
+def time_refits(c, sd, meshes, sets, reps, name):
+    """alternates between the vertex sets; every refit really moves the meshes"""
+    c.profile_kernels(True)
+    ev_ms, stages, t_update, t_refit = [], [], [], []
+    for r in range(reps + 2):
+        c.synchronize()
+        t0 = time.perf_counter()
+        for m in meshes:
+            c.update_mesh(m, sets[r % 2][m])
+        t1 = time.perf_counter()
+        c.refit_accel()
+        t2 = time.perf_counter()
+        info = c.refit_info()
+        if r >= 2:                                                  # (the first builds the plan, the second warms the kernels)
+            ev_ms.append(info["last_refit_ms"]); stages.append(c.debug_accel(6).copy()); t_update.append((t1 - t0) * 1e3); t_refit.append((t2 - t1) * 1e3)
+    st = np.array(stages)
+    tris = sum(sd.meshes[m]["idx"].shape[0] for m in meshes)
+    print(f"(1) refit, {name}: {len(meshes)} mesh(es), {tris} triangles moved, {info['levels']} box launches")
+    print(f"      device, whole refit          ms {spread(ev_ms)}")
+    for k, n in enumerate(("vertex upload + scatter", "leaf operands", "boxes, all levels", "four-wide nodes")):
+        print(f"      device, {n:24s} ms {spread(st[:, k].tolist())}")
+    print(f"      host, update_mesh calls      ms {spread(t_update)}")
+    print(f"      host, refit_accel call       ms {spread(t_refit)}")
+    c.profile_kernels(False)
+    return statistics.median(ev_ms), statistics.median(t_refit)
+
+
+def time_builds(c, reps, name):
+    ms, wall = [], []
+    for _ in range(reps):
+        c.synchronize()
+        t0 = time.perf_counter(); c.build_accel(); c.synchronize(); wall.append((time.perf_counter() - t0) * 1e3)
+        ms.append(c.accel_info()["build_ms"])
+    print(f"(2) evplp_build_accel, {name}: build_ms {spread(ms)}   wall ms {spread(wall)}   {c.accel_info()}")
+    return statistics.median(wall)
+
+
+def time_gather(c, sd, reps, name):
+    bsr, total, _ = c.scene_metrics()
+    radius = 0.003 * bsr
+    kw = dict(camera_pos=sd.cam_origin, mis_mode="one", pdf_mc=1.0 / math.pi / radius ** 2, clamping_value=1.0 / total, photon_radius=radius, vsl_radius=0.05 * bsr,
+              vsl_inv_pi_radius2=1 / (math.pi * (0.05 * bsr) ** 2), num_light_paths=NL, num_vpl_light_paths=NL, photons_per_path=P, do_accumulate=1)
+    ms = []
+    for it in range(reps + 1):
+        c.primary((0, 0)); c.trace_light_paths(it); c.gather_vpl(ev.frame_params(rng_seed=it, **kw)); c.synchronize()
+        st = c.pass_stats(ev.PASS_GATHER_VPL)
+        if it:
+            ms.append(st["ms"])
+    print(f"      gather over {name:22s} ms {spread(ms)}   rays {st['rays']:.3e}")
+    return statistics.median(ms)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=40)
+    ap.add_argument("--tris", type=int, default=331000)
+    ap.add_argument("--res", type=int, default=1024)
+    a = ap.parse_args()
+    with tempfile.TemporaryDirectory(prefix="evplp_refit_") as d:
+        sd, _ = scenes.load_obj_scene(ev.synth_scene(d, "conf", a.tris, 1234, a.res, a.res, style="hard"))
+    ntri = sum(m["idx"].shape[0] for m in sd.meshes)
+    chairs = chair_meshes(sd)
+    print(f"scene: {ntri} triangles in {len(sd.meshes)} meshes, {len(chairs)} chairs found; {a.reps} repetitions; median (p10 - p90)")
+    orig = [m["verts"] for m in sd.meshes]
+    small = [(v + np.array([0.01, 0.01, 0.0], F)).astype(F) for v in orig]
+    rng = np.random.RandomState(5)
+    large = list(orig)
+    for k in chairs:
+        ang = rng.rand() * 2 * math.pi
+        large[k] = (orig[k] + np.array([math.cos(ang), math.sin(ang), 0.0], F)).astype(F)
+
+    c = context(sd, a.res, ev.BVH_SAH)
+    one = chairs[:1] if chairs else [0]
+    nudged = list(orig)
+    nudged[one[0]] = (orig[one[0]] + np.array([0.05, 0.0, 0.0], F)).astype(F)
+    time_refits(c, sd, one, (nudged, orig), a.reps, "(a) one chair")
+    every = list(range(len(sd.meshes)))
+    refit_ms, refit_wall = time_refits(c, sd, every, (small, orig), a.reps, "(b) every mesh, small translation")
+    sah_wall = time_builds(c, a.reps, "SAH (host)")
+    c.close()
+    g = context(sd, a.res, GPU_BUILDER)
+    gpu_wall = time_builds(g, a.reps, "device LBVH")
+    g.close()
+    print(f"    refit (b) / SAH rebuild, wall: {refit_wall / sah_wall:.4f}   refit (b) / device LBVH rebuild, wall: {refit_wall / gpu_wall:.4f}")
+
+    for tag, verts in (("(3) small motion (b)", small), ("(4) every chair a metre away", large)):
+        print(f"{tag}: the config-#2 gather over three trees of the same moved scene")
+        c = context(sd, a.res, ev.BVH_SAH)
+        for m in (every if verts is small else chairs):
+            c.update_mesh(m, verts[m])
+        c.refit_accel()
+        t_refit = time_gather(c, sd, a.reps, "refitted SAH")
+        c.close()
+        c = context(sd, a.res, ev.BVH_SAH, verts)
+        t_sah = time_gather(c, sd, a.reps, "rebuilt SAH")
+        c.close()
+        c = context(sd, a.res, GPU_BUILDER, verts)
+        t_gpu = time_gather(c, sd, a.reps, "rebuilt device LBVH")
+        c.close()
+        print(f"      refitted / rebuilt SAH: {t_refit / t_sah:.3f}   refitted SAH / rebuilt device LBVH: {t_refit / t_gpu:.3f}   rebuilt device LBVH / rebuilt SAH: {t_gpu / t_sah:.3f}")
+
+
+if __name__ == "__main__":
+    main()
