@@ -96,6 +96,19 @@ class PassStats(C.Structure):
                 ("pad", C.c_uint32)]
 
 
+class AccelQuality(C.Structure):
+    """struct evplp_accel_quality"""
+    _fields_ = [("cost", C.c_double), ("root_area", C.c_double), ("inner_area", C.c_double), ("leaf_pair_area", C.c_double), ("leaf_tri_area", C.c_double),
+                ("built_cost", C.c_double), ("reached_nodes", C.c_int32), ("leaf_refs", C.c_int32), ("refits_since_build", C.c_int32),
+                ("policy_rebuilds", C.c_int32), ("last_action", C.c_int32), ("pad", C.c_int32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "pad"}
+
+
+# the weights of evplp_accel_quality's cost (csrc/evplp_types.h): vector instructions of a node visit and of a pair test
+COST_NODE_VISIT, COST_PAIR_TEST = 15.0, 40.0
+
 # evplp_debug_accel's records (csrc/evplp_types.h BvhNode, LeafBlock, TriFlat, BvhNode4)
 ACCEL_NODE = np.dtype([("ctr", np.float32, (3, 2)), ("hal", np.float32, (3, 2)), ("c0", np.int32), ("c1", np.int32), ("pad", np.int32, 2)])
 ACCEL_PAIR = np.dtype([("p0", np.float32, (3, 2)), ("e0", np.float32, (3, 2)), ("e1", np.float32, (3, 2)), ("n", np.float32, (3, 2))])
@@ -128,6 +141,11 @@ _SIGNATURES = {
     "evplp_debug_accel": (C.c_int, [_P, C.c_int32, _P, C.c_size_t]),
     "evplp_group_update_mesh": (C.c_int, [_P, C.c_int32, _P, C.c_int32]),
     "evplp_group_refit_accel": (C.c_int, [_P]),
+    "evplp_accel_cost": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double)]),
+    "evplp_accel_quality": (C.c_int, [_P, C.POINTER(AccelQuality)]),
+    "evplp_set_refit_policy": (C.c_int, [_P, C.c_double, C.c_int32]),
+    "evplp_group_accel_quality": (C.c_int, [_P, C.POINTER(AccelQuality)]),
+    "evplp_group_set_refit_policy": (C.c_int, [_P, C.c_double, C.c_int32]),
     "evplp_scene_metrics": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "evplp_primary": (C.c_int, [_P, C.POINTER(C.c_float * 2), C.c_int32]),
     "evplp_trace_light_paths": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32]),
@@ -460,6 +478,18 @@ class Context:
         """evplp_refit_accel: the tree, the triangle operands and the scene's figures follow the updated vertices, on the device; the topology stays"""
         self._check(self._lib.evplp_refit_accel(self._h))
 
+    def accel_quality(self) -> dict:
+        """evplp_accel_quality: the SAH cost of the tree as it is on the device (cost, root_area, inner_area, leaf_pair_area, leaf_tri_area),
+        built_cost, reached_nodes, leaf_refs, refits_since_build, policy_rebuilds, last_action (0 none, 1 refit kept, 2 rebuilt); waits"""
+        q = AccelQuality()
+        self._check(self._lib.evplp_accel_quality(self._h, C.byref(q)))
+        return q.as_dict()
+
+    def set_refit_policy(self, max_cost_ratio: float, rebuild_builder: int = -1):
+        """evplp_set_refit_policy: refit_accel rebuilds when the cost exceeds max_cost_ratio x the built tree's (0: off, the default);
+        rebuild_builder: a BVH_* value, or -1 for the context's own"""
+        self._check(self._lib.evplp_set_refit_policy(self._h, float(max_cost_ratio), int(rebuild_builder)))
+
     def refit_info(self):
         n, l, ms = C.c_int32(), C.c_int32(), C.c_float()
         self._check(self._lib.evplp_refit_info(self._h, C.byref(n), C.byref(l), C.byref(ms)))
@@ -467,13 +497,13 @@ class Context:
 
     def debug_accel(self, which: int) -> np.ndarray:
         """evplp_debug_accel (tests): 0 nodes, 1 leaf blocks, 2 flat triangle operands, 3 slot -> triangle, 4 four-wide nodes (structured arrays
-        / int32), 5 the box pad (a float), 6 the last refit's four stage times in ms"""
+        / int32), 5 the box pad (a float), 6 the last refit's four stage times in ms, 7 the last cost measurement's time in ms (a float)"""
         info = self.accel_info()
         nn, nl = max(info["nodes"], 1), max(info["leaves"], 1)
         out = {0: lambda: np.zeros(nn, ACCEL_NODE), 1: lambda: np.zeros(nl, ACCEL_LEAF), 2: lambda: np.zeros(4 * nl, ACCEL_TRI), 3: lambda: np.zeros(4 * nl, np.int32),
-               4: lambda: np.zeros(nn, ACCEL_NODE4), 5: lambda: np.zeros(1, np.float32), 6: lambda: np.zeros(4, np.float32)}[which]()
+               4: lambda: np.zeros(nn, ACCEL_NODE4), 5: lambda: np.zeros(1, np.float32), 6: lambda: np.zeros(4, np.float32), 7: lambda: np.zeros(1, np.float32)}[which]()
         self._check(self._lib.evplp_debug_accel(self._h, which, _ptr(out), out.nbytes))
-        return out[0] if which == 5 else out
+        return out[0] if which in (5, 7) else out
 
     def load_scene_json(self, json_path: str):
         rc = self._lib.evplp_load_scene_json(self._h, json_path.encode())
@@ -754,6 +784,17 @@ def refit_levels(nodes, level_capacity: int = 64):
     return height[:n], order[:int(begin[rc])], begin[:rc + 1]
 
 
+def accel_cost(nodes) -> dict:
+    """evplp_accel_cost: the SAH cost of a flattened tree (ACCEL_NODE records or raw 64-byte nodes) on the host, in the order and shape of
+    the device's sums -- evplp_accel_quality's reference.  EvplpError for an array that is not a tree."""
+    raw = np.ascontiguousarray(nodes).view(np.uint8).reshape(-1, 64)
+    out = (C.c_double * 5)()
+    rc = lib().evplp_accel_cost(_ptr(raw), raw.shape[0], out)
+    if rc < 0:
+        raise EvplpError(rc, "evplp_accel_cost: not a tree (a child index out of range, a node reached twice, a cycle), or no nodes")
+    return {"cost": out[0], "root_area": out[1], "inner_area": out[2], "leaf_pair_area": out[3], "leaf_tri_area": out[4], "reached_nodes": rc}
+
+
 Context.refit_levels = staticmethod(refit_levels)      # (the plan needs no context; it is listed with the calls it serves)
 
 
@@ -883,6 +924,15 @@ class Group:
 
     def refit_accel(self):
         self._check(self._lib.evplp_group_refit_accel(self._h))
+
+    def accel_quality(self) -> dict:
+        """evplp_group_accel_quality: rank 0's figures; an error if any rank's differ"""
+        q = AccelQuality()
+        self._check(self._lib.evplp_group_accel_quality(self._h, C.byref(q)))
+        return q.as_dict()
+
+    def set_refit_policy(self, max_cost_ratio: float, rebuild_builder: int = -1):
+        self._check(self._lib.evplp_group_set_refit_policy(self._h, float(max_cost_ratio), int(rebuild_builder)))
 
     def set_splat_proxy(self, vertices=None, triangles=None):
         if vertices is None:

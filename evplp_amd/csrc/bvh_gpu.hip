@@ -23,6 +23,7 @@
 //                      (a leaf's from its triangles, an inner child's from a scratch array the launch before wrote), writes its own
 //                      union there and the padded child boxes into its node -- padded once, from the exact union.
 //   d. node4         : the four-wide nodes again, into the allocation they have.
+// Quality (evplp_accel_quality): accel_cost, one launch over the refit plan's order, sums the SAH cost's terms of the tree as it is.
 #include "evplp_types.h"
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -341,6 +342,37 @@ __global__ __launch_bounds__(256) void node4_kernel(const BvhNode *nodes, int n,
     out[i] = r;
 }
 
+// ---- the SAH cost of the tree as it is (evplp_accel_quality).  Thread i of workgroup k takes entry 256 k + i of the refit plan's order
+// (every node the root reaches, once) and reads that node's 64 bytes alone: the leaf counts are in the references.  The three sums of a
+// workgroup are added in one fixed shape, reduce_row's (kernels_stats.hip): shuffle-down by 32 .. 1 in each wavefront, lane 0 of each to
+// LDS, thread 0 adds waves 0 .. 3 in order and writes out[1 + 3 k ..]; the thread that holds node 0 writes the root's area to out[0].
+// Entries past the end add +0.0.  The host adds the workgroups' triples in index order after the launch, which is the only hand-over.
+__global__ __launch_bounds__(kCostChunk) void accel_cost_kernel(const BvhNode *nodes, int32_t nnodes, const int32_t *order, int32_t count, double *out) {
+    __shared__ double wave_sums[kCostChunk / 64][3];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int e = (int)blockIdx.x * kCostChunk + tid;
+    double s[3] = { 0.0, 0.0, 0.0 };
+    if (e < count) {
+        const int32_t i = order[e];
+        if (i >= 0 && i < nnodes) {
+            const BvhNode f = nodes[i];
+            accel_cost_terms(f, s);
+            if (i == 0) out[0] = accel_root_area(f);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+        for (int off = 32; off > 0; off >>= 1) s[k] += __shfl_down(s[k], off, 64);
+    if (lane == 0) for (int k = 0; k < 3; k++) wave_sums[wave][k] = s[k];
+    __syncthreads();
+    if (tid == 0)
+        for (int k = 0; k < 3; k++) {
+            double t = wave_sums[0][k];
+            for (int w = 1; w < kCostChunk / 64; w++) t += wave_sums[w][k];
+            out[1 + 3 * (size_t)blockIdx.x + k] = t;
+        }
+}
+
 #define GB_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { err = e_; goto done; } } while (0)
 
 } // namespace
@@ -371,6 +403,12 @@ void refit_leaves(const RefitScene &r, hipStream_t stream) {
 void refit_level(const RefitScene &r, const int32_t *d_order, int32_t count, float pad, hipStream_t stream) {
     if (count > 0) hipLaunchKernelGGL(refit_level_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, r.nodes, r.nnodes, d_order, count, r.tri_index, r.nslots,
                                       r.attrs, r.ntri, (Bx *)r.boxes, pad);
+}
+
+// evplp_accel_quality's launch: d_order = the refit plan's whole order (count reached nodes), d_out = 1 + 3 * ceil(count / 256) doubles
+// (accel_cost_parts); enqueued, no wait
+void accel_cost(const BvhNode *d_nodes, int32_t nnodes, const int32_t *d_order, int32_t count, double *d_out, hipStream_t stream) {
+    if (count > 0) hipLaunchKernelGGL(accel_cost_kernel, dim3((unsigned)((count + kCostChunk - 1) / kCostChunk)), dim3(kCostChunk), 0, stream, d_nodes, nnodes, d_order, count, d_out);
 }
 
 // Builds on `stream` from the host triangle list; the four output arrays are device allocations owned by the caller

@@ -194,6 +194,9 @@ static void free_scene_device(evplp_context *c) {
     hipFree(c->d_refit_order); hipFree(c->d_refit_boxes); hipFree(c->d_refit_stage); if (c->h_refit_stage) hipHostFree(c->h_refit_stage);
     c->d_refit_order = nullptr; c->d_refit_boxes = c->d_refit_stage = c->h_refit_stage = nullptr;
     c->refit_levels = 0; c->refit_level_begin.clear(); std::vector<BvhNode>().swap(c->host_nodes);
+    // ... and so does the output of the cost kernel (made by the first evplp_accel_quality)
+    hipFree(c->d_cost); if (c->h_cost) hipHostFree(c->h_cost);
+    c->d_cost = c->h_cost = nullptr; c->refit_reached = c->refit_leaf_refs = 0;
 }
 
 extern "C" void evplp_destroy(evplp_context *c) {
@@ -227,6 +230,7 @@ extern "C" void evplp_destroy(evplp_context *c) {
     if (c->ev_back_read) hipEventDestroy(c->ev_back_read);
     if (c->ev_refit_staged) hipEventDestroy(c->ev_refit_staged);
     for (int i = 0; i < 5; i++) if (c->ev_refit[i]) hipEventDestroy(c->ev_refit[i]);
+    for (int i = 0; i < 2; i++) if (c->ev_cost[i]) hipEventDestroy(c->ev_cost[i]);
     hipFree(c->records_back);
     for (int k = 0; k < 4; k++) hipFree(c->gbuf_back[k]);
     hipFree(c->d_tile_box_back);
@@ -390,8 +394,9 @@ static float scene_pad(const float *verts, int32_t ntri, std::vector<char> &has_
     return bvh_pad(lo, hi, any);
 }
 
-extern "C" int evplp_build_accel(evplp_context *c) {
-    CTX_CHECK(c);
+static int measure_cost(evplp_context *c, double out[5]);
+// evplp_build_accel, and the rebuild of a refit policy (policy_builder >= 0: that builder instead of the context's own)
+static int build_accel(evplp_context *c, int policy_builder) {
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     if (c->meshes.empty()) { c->set_error("evplp_build_accel: no meshes"); return EVPLP_ERR_INVALID; }
     if (c->light_mesh < 0) { c->set_error("evplp_build_accel: no area light set"); return EVPLP_ERR_INVALID; }
@@ -413,7 +418,7 @@ extern "C" int evplp_build_accel(evplp_context *c) {
     const int32_t light_first = first[(size_t)c->light_mesh], light_count = first[(size_t)c->light_mesh + 1] - light_first;
     if (light_count <= 0) { c->set_error("evplp_build_accel: the area-light mesh has no triangles"); return EVPLP_ERR_INVALID; }
     BvhBuild bb;
-    int builder = c->env_bvh_builder >= 0 ? c->env_bvh_builder : c->cfg.bvh_builder;   // (override read by evplp_create)
+    int builder = policy_builder >= 0 ? policy_builder : c->env_bvh_builder >= 0 ? c->env_bvh_builder : c->cfg.bvh_builder;   // (override read by evplp_create)
     if (builder == EVPLP_BVH_LBVH_GPU) {
         BvhDeviceBuild gb;
         const int e = build_bvh_gpu(verts.data(), (int32_t)attrs.size(), bvh_pad_scale(), c->stream, &gb);
@@ -497,7 +502,18 @@ extern "C" int evplp_build_accel(evplp_context *c) {
     std::memcpy(c->sc.light_intensity, c->light_scaled, 16); std::memcpy(c->sc.light_unscaled, c->light_unscaled, 16);
     c->accel_built = true; c->primary_cuts_valid = false;
     c->mesh_dirty.assign(c->meshes.size(), 0); c->scene_dirty = false;
+    c->built_cost = 0.0; c->built_cost_known = false; c->refits_since_build = 0;
+    if (c->policy_ratio > 0.0) {            // (a policy compares against the cost of the tree as built: one small launch and a wait)
+        double q[5];
+        if ((rc = measure_cost(c, q))) return rc;
+    }
     return EVPLP_OK;
+}
+extern "C" int evplp_build_accel(evplp_context *c) {
+    CTX_CHECK(c);
+    const int rc = build_accel(c, -1);
+    if (rc == EVPLP_OK) c->last_action = 0;
+    return rc;
 }
 
 extern "C" int evplp_scene_metrics(evplp_context *c, float *r, float *total, float *light) {
@@ -573,6 +589,13 @@ static int refit_prepare(evplp_context *c) {
     std::vector<int32_t> height((size_t)nn), order((size_t)nn);
     c->refit_level_begin.assign((size_t)kMaxDepth + 1, 0);
     const int levels = evplp_refit_levels(c->host_nodes.data(), nn, height.data(), order.data(), c->refit_level_begin.data(), kMaxDepth);
+    if (levels >= 1) {                      // (what evplp_accel_quality reports beside its sums: the reached nodes and their leaf references)
+        c->refit_reached = c->refit_level_begin[(size_t)levels]; c->refit_leaf_refs = 0;
+        for (int32_t k = 0; k < c->refit_reached; k++) {
+            const BvhNode &f = c->host_nodes[(size_t)order[(size_t)k]];
+            c->refit_leaf_refs += (f.c0 < 0 && f.c0 != kNoChild) + (f.c1 < 0 && f.c1 != kNoChild);
+        }
+    }
     std::vector<BvhNode>().swap(c->host_nodes);
     if (levels < 1) { c->set_error("evplp_refit_accel: the node array is not a tree of at most %d levels", kMaxDepth); return EVPLP_ERR_INVALID; }
     const size_t stage = 9 * (size_t)c->scene_tris + (size_t)c->sc.light_count;
@@ -644,9 +667,85 @@ extern "C" int evplp_refit_accel(evplp_context *c) {
     if (timed) HIP_TRY(c, hipEventRecord(c->ev_refit[4], c->stream));
     if (c->aux_stream) HIP_TRY(c, hipStreamWaitEvent(c->aux_stream, c->ev_refit_staged, 0));      // (light paths given to the second stream from here on see the new tree)
     HIP_TRY(c, hipGetLastError());
-    c->accel_pad = pad; c->refit_timed = timed; c->refit_stages_timed = stages; c->refit_count++;
+    c->accel_pad = pad; c->refit_timed = timed; c->refit_stages_timed = stages; c->refit_count++; c->refits_since_build++;
     c->primary_cuts_valid = false; c->tile_box_valid = false;
     std::fill(c->mesh_dirty.begin(), c->mesh_dirty.end(), 0); c->scene_dirty = false;
+    if (c->policy_ratio > 0.0) {
+        // The policy (evplp_set_refit_policy): the cost of the refitted tree against the cost of the tree as built.  One small launch and
+        // one host wait; a rebuild is evplp_build_accel's code (which measures the new built_cost, the policy being on).
+        double q[5];
+        if ((rc = measure_cost(c, q))) return rc;
+        if (q[0] > c->policy_ratio * c->built_cost) {
+            if ((rc = build_accel(c, c->policy_builder))) return rc;
+            c->policy_rebuilds++; c->last_action = 2;
+        } else c->last_action = 1;
+    }
+    return EVPLP_OK;
+}
+
+// ---------------------------------------------------------------------------------- the tree's SAH cost, and the refit policy
+// The cost of the tree as it is on the device into out[5], behind everything on the context's stream; waits.  The first measurement
+// since a build is kept as built_cost.
+static int measure_cost(evplp_context *c, double out[5]) {
+    int rc = refit_prepare(c); if (rc) return rc;              // (the plan is the refit's; made here if no refit has made it)
+    const int32_t nchunks = (c->refit_reached + kCostChunk - 1) / kCostChunk;
+    const size_t bytes = sizeof(double) * (1 + 3 * (size_t)nchunks);
+    if (!c->d_cost) {
+        hipError_t e = hipMalloc((void **)&c->d_cost, bytes);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_cost, bytes, hipHostMallocDefault);
+        if (e != hipSuccess) { c->set_error("evplp_accel_quality: the sums' arrays: %s", hipGetErrorString(e)); return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP; }
+    }
+    const bool timed = c->profile_passes;
+    for (int i = 0; i < 2 && timed; i++) if (!c->ev_cost[i]) HIP_TRY(c, hipEventCreate(&c->ev_cost[i]));
+    if (timed) HIP_TRY(c, hipEventRecord(c->ev_cost[0], c->stream));
+    accel_cost(c->sc.nodes, c->accel_nodes, c->d_refit_order, c->refit_reached, c->d_cost, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(c->h_cost, c->d_cost, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (timed) HIP_TRY(c, hipEventRecord(c->ev_cost[1], c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->cost_timed = timed;
+    accel_cost_finish(c->h_cost + 1, nchunks, c->h_cost[0], out);
+    if (!c->built_cost_known) { c->built_cost = out[0]; c->built_cost_known = true; }
+    return EVPLP_OK;
+}
+
+namespace evplp {
+bool accel_quality_check(evplp_context *c, const char *name) {
+    if (!c->accel_built) { c->set_error("%s: scene not built (evplp_build_accel)", name); return false; }
+    if (c->scene_dirty) { c->set_error("%s: vertices were updated (evplp_update_mesh): call evplp_refit_accel or evplp_build_accel first", name); return false; }
+    return true;
+}
+bool refit_policy_check(evplp_context *c, double max_cost_ratio, int32_t rebuild_builder) {
+    if (!(max_cost_ratio >= 0.0) || !std::isfinite(max_cost_ratio)) { c->set_error("evplp_set_refit_policy: max_cost_ratio must be finite and >= 0 (0: off)"); return false; }
+    if (rebuild_builder < -1 || rebuild_builder > EVPLP_BVH_LBVH_GPU) { c->set_error("evplp_set_refit_policy: rebuild_builder %d is neither an evplp_bvh_builder nor -1", rebuild_builder); return false; }
+    if (c->scene_dirty) { c->set_error("evplp_set_refit_policy: vertices were updated (evplp_update_mesh): call evplp_refit_accel or evplp_build_accel first"); return false; }
+    return true;
+}
+}
+
+extern "C" int evplp_accel_quality(evplp_context *c, struct evplp_accel_quality *out) {
+    CTX_CHECK(c);
+    if (!out) { c->set_error("evplp_accel_quality: null destination"); return EVPLP_ERR_INVALID; }
+    if (!evplp::accel_quality_check(c, "evplp_accel_quality")) return EVPLP_ERR_INVALID;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    double q[5];
+    const int rc = measure_cost(c, q); if (rc) return rc;
+    std::memset(out, 0, sizeof(*out));
+    out->cost = q[0]; out->root_area = q[1]; out->inner_area = q[2]; out->leaf_pair_area = q[3]; out->leaf_tri_area = q[4];
+    out->built_cost = c->built_cost; out->reached_nodes = c->refit_reached; out->leaf_refs = c->refit_leaf_refs;
+    out->refits_since_build = c->refits_since_build; out->policy_rebuilds = c->policy_rebuilds; out->last_action = c->last_action;
+    return EVPLP_OK;
+}
+
+extern "C" int evplp_set_refit_policy(evplp_context *c, double max_cost_ratio, int32_t rebuild_builder) {
+    CTX_CHECK(c);
+    if (!evplp::refit_policy_check(c, max_cost_ratio, rebuild_builder)) return EVPLP_ERR_INVALID;
+    if (max_cost_ratio > 0.0 && c->accel_built && !c->built_cost_known) {
+        HIP_TRY(c, hipSetDevice(c->cfg.device));
+        double q[5];
+        const int rc = measure_cost(c, q); if (rc) return rc;
+    }
+    c->policy_ratio = max_cost_ratio; c->policy_builder = rebuild_builder;
     return EVPLP_OK;
 }
 
@@ -670,8 +769,8 @@ extern "C" int evplp_debug_accel(evplp_context *c, int32_t which, void *host_dst
     if (!c->accel_built || !host_dst) { c->set_error("evplp_debug_accel: no scene (evplp_build_accel) or a null destination"); return EVPLP_ERR_INVALID; }
     const size_t nn = (size_t)std::max(c->accel_nodes, 1), nl = (size_t)std::max(c->accel_leaves, 1);
     const void *src[5] = { c->sc.nodes, c->sc.leaves, c->sc.tri_flat, c->sc.tri_index, c->sc.nodes4 };
-    const size_t want[7] = { sizeof(BvhNode) * nn, sizeof(LeafBlock) * nl, sizeof(TriFlat) * 4 * nl, sizeof(int32_t) * 4 * nl, sizeof(BvhNode4) * nn, sizeof(float), sizeof(float) * 4 };
-    if (which < 0 || which > 6 || bytes != want[which]) { c->set_error("evplp_debug_accel: array %d holds %zu bytes, not %zu", which, which >= 0 && which <= 6 ? want[which] : (size_t)0, bytes); return EVPLP_ERR_INVALID; }
+    const size_t want[8] = { sizeof(BvhNode) * nn, sizeof(LeafBlock) * nl, sizeof(TriFlat) * 4 * nl, sizeof(int32_t) * 4 * nl, sizeof(BvhNode4) * nn, sizeof(float), sizeof(float) * 4, sizeof(float) };
+    if (which < 0 || which > 7 || bytes != want[which]) { c->set_error("evplp_debug_accel: array %d holds %zu bytes, not %zu", which, which >= 0 && which <= 7 ? want[which] : (size_t)0, bytes); return EVPLP_ERR_INVALID; }
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     if (which == 5) { std::memcpy(host_dst, &c->accel_pad, sizeof(float)); return EVPLP_OK; }
     if (which == 6) {                       // the last refit's stages in ms: upload, leaf operands, boxes, four-wide nodes (zeros unless evplp_profile_kernels was on)
@@ -681,6 +780,12 @@ extern "C" int evplp_debug_accel(evplp_context *c, int32_t which, void *host_dst
             for (int i = 0; i < 4; i++) HIP_TRY(c, hipEventElapsedTime(&ms[i], c->ev_refit[i], c->ev_refit[i + 1]));
         }
         std::memcpy(host_dst, ms, sizeof(ms));
+        return EVPLP_OK;
+    }
+    if (which == 7) {                       // the last cost measurement in ms, the kernel and the copy of its sums (zero unless evplp_profile_passes was on)
+        float ms = 0.f;
+        if (c->cost_timed) HIP_TRY(c, hipEventElapsedTime(&ms, c->ev_cost[0], c->ev_cost[1]));
+        std::memcpy(host_dst, &ms, sizeof(ms));
         return EVPLP_OK;
     }
     HIP_TRY(c, hipMemcpyAsync(host_dst, src[which], bytes, hipMemcpyDeviceToHost, c->stream));

@@ -16,6 +16,8 @@ void build_nodes4_into(const BvhNode *d_nodes, int32_t nnodes, hipStream_t strea
 void refit_scatter(const float *d_src, int32_t first, int32_t count, TriAttr *attrs, hipStream_t stream);
 void refit_leaves(const RefitScene &r, hipStream_t stream);
 void refit_level(const RefitScene &r, const int32_t *d_order, int32_t count, float pad, hipStream_t stream);
+// bvh_gpu.hip: the launch of evplp_accel_quality (enqueued; d_out: 1 + 3 * ceil(count / 256) doubles -- the root's area, then a triple per workgroup)
+void accel_cost(const BvhNode *d_nodes, int32_t nnodes, const int32_t *d_order, int32_t count, double *d_out, hipStream_t stream);
 struct HostMesh { std::vector<float> verts, uvs; std::vector<int32_t> idx; int32_t material = 0; };
 struct HostTexture { int32_t w = 0, h = 0; std::vector<float> rgba; };
 struct HostStats { uint64_t rays = 0; };
@@ -34,6 +36,9 @@ namespace evplp {
 // what evplp_update_mesh / evplp_refit_accel refuse (context.cpp), for the group's caller thread as well: false and the reason in c's error
 bool update_mesh_check(evplp_context *c, int32_t mesh, const float *vertices, int32_t nverts);
 bool refit_check(evplp_context *c);
+// what evplp_accel_quality / evplp_set_refit_policy refuse without touching a device (name: the entry point, for the message)
+bool accel_quality_check(evplp_context *c, const char *name);
+bool refit_policy_check(evplp_context *c, double max_cost_ratio, int32_t rebuild_builder);
 // evplp_noise_* (context.cpp), for the group's workers as well
 NoisePlanes noise_planes(const evplp_context *c);
 NoiseMoments noise_moments_of(const evplp_context *c);           // a context's own moments (S = c_prev - c_start)
@@ -105,6 +110,13 @@ struct evplp_context {
     int32_t *d_refit_order = nullptr; float *d_refit_boxes = nullptr, *d_refit_stage = nullptr, *h_refit_stage = nullptr;
     hipEvent_t ev_refit_staged = nullptr, ev_refit[5] = {}; bool refit_timed = false, refit_stages_timed = false;
     int32_t refit_count = 0, scene_tris = 0; float accel_pad = 0.f;
+    // evplp_accel_quality / evplp_set_refit_policy.  The plan is the refit's (refit_reached nodes in its order, refit_leaf_refs leaf references
+    // among them); the kernel's output and its pinned host copy (1 + 3 * ceil(reached / 256) doubles each) are made by the first measurement
+    // and freed with the scene.  built_cost: the first measurement since the last evplp_build_accel (0: none yet).
+    int32_t refit_reached = 0, refit_leaf_refs = 0;
+    double *d_cost = nullptr, *h_cost = nullptr; hipEvent_t ev_cost[2] = {}; bool cost_timed = false;
+    double built_cost = 0.0, policy_ratio = 0.0; bool built_cost_known = false;
+    int32_t policy_builder = -1, refits_since_build = 0, policy_rebuilds = 0, last_action = 0;
 
     evplp::SceneDev sc{};
     evplp_record *d_vpls = nullptr; uint32_t *d_vpl_src = nullptr;

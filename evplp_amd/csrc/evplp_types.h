@@ -155,6 +155,58 @@ struct RefitScene {
     float *boxes;
 };
 
+// ---- the SAH cost of the flattened tree (evplp_accel_quality on the device, evplp_accel_cost on the host: include/evplp.h).
+// The weights are the vector instructions of a node visit and of a pair test of the packet walk.  Host and device
+// form every term with the functions below and add them in one fixed shape: entry 256 k + i of the plan's order is thread i of chunk k,
+// a chunk is reduced by halving strides within each run of 64 (the wavefront's shuffle-down), the four runs are added in order, and the
+// chunks' sums are added in index order.  Every operation rounds on its own (no contraction), so the two agree bit for bit.
+constexpr double kCostNodeVisit = 15.0, kCostPairTest = 40.0;
+constexpr int kCostChunk = 256;
+// a box with a negative half-size holds nothing (an absent child; a leaf whose triangles have all lost their area): area 0
+__host__ __device__ inline bool cost_box_present(const BvhNode &f, int s) {
+    return (s ? f.c1 : f.c0) != kNoChild && f.hal[0][s] >= 0.0f && f.hal[1][s] >= 0.0f && f.hal[2][s] >= 0.0f;
+}
+// t[0] += inner_area, t[1] += leaf_pair_area, t[2] += leaf_tri_area of node f (child 0, then child 1)
+__host__ __device__ inline void accel_cost_terms(const BvhNode &f, double t[3]) {
+#pragma clang fp contract(off)
+    for (int s = 0; s < 2; s++) {
+        if (!cost_box_present(f, s)) continue;
+        const int32_t ref = s ? f.c1 : f.c0;
+        const double hx = (double)f.hal[0][s], hy = (double)f.hal[1][s], hz = (double)f.hal[2][s];
+        const double a = 8.0 * (hx * hy + hy * hz + hz * hx);             // (fp32 x fp32 is exact in fp64)
+        if (ref >= 0) t[0] += a;
+        else {
+            const int32_t cnt = (~ref & 3) + 1;                               // a zeroed (degenerate) triangle keeps its slot: the walk still tests it
+            t[1] += a * (double)((cnt + 1) >> 1);
+            t[2] += a * (double)cnt;
+        }
+    }
+}
+// the area of the union of the root's present child boxes (0: none)
+__host__ __device__ inline double accel_root_area(const BvhNode &f) {
+#pragma clang fp contract(off)
+    double lo[3] = { 0.0, 0.0, 0.0 }, hi[3] = { 0.0, 0.0, 0.0 };
+    bool any = false;
+    for (int s = 0; s < 2; s++) {
+        if (!cost_box_present(f, s)) continue;
+        for (int k = 0; k < 3; k++) {
+            const double l = (double)f.ctr[k][s] - (double)f.hal[k][s], h = (double)f.ctr[k][s] + (double)f.hal[k][s];
+            lo[k] = any ? (l < lo[k] ? l : lo[k]) : l; hi[k] = any ? (h > hi[k] ? h : hi[k]) : h;
+        }
+        any = true;
+    }
+    const double dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
+    return any ? 2.0 * (dx * dy + dy * dz + dz * dx) : 0.0;
+}
+// out = { cost, root_area, inner_area, leaf_pair_area, leaf_tri_area } from the chunks' triples { inner, pair, tri }, added in index order
+inline void accel_cost_finish(const double *parts, int32_t nchunks, double root_area, double out[5]) {
+#pragma clang fp contract(off)
+    double t[3] = { 0.0, 0.0, 0.0 };
+    for (int32_t k = 0; k < nchunks; k++) for (int j = 0; j < 3; j++) t[j] += parts[3 * (size_t)k + j];
+    out[1] = root_area; out[2] = t[0]; out[3] = t[1]; out[4] = t[2];
+    out[0] = root_area > 0.0 ? (kCostNodeVisit * (root_area + t[0]) + kCostPairTest * t[1]) / root_area : 0.0;
+}
+
 // Host-side acceleration structure build result
 struct BvhBuild {
     BvhNode *nodes = nullptr; int32_t nnodes = 0;

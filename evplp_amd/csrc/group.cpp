@@ -66,7 +66,7 @@ struct Rccl {
 };
 
 enum Op { OP_QUIT = 0, OP_CLEAR, OP_SYNC, OP_PRIMARY, OP_TRACE, OP_GATHER, OP_SPLAT, OP_PATH_TRACE, OP_PRESENT, OP_LOAD_SCENE, OP_SET_PROXY, OP_ASSEMBLE, OP_REDUCE, OP_SET_REFERENCE, OP_FRAME_ERROR,
-          OP_NOISE_TRACK, OP_NOISE_FOLD, OP_NOISE_POOL, OP_NOISE_ROWS, OP_NOISE_VARIANCE, OP_ADAPT_ENABLE, OP_ADAPT_RETIRE, OP_DENOISE_PREP, OP_DENOISE_FILTER, OP_PATH_TRACE_BATCH, OP_ADAPT_SET_BUDGETS, OP_ADAPT_TILE_NOISE, OP_UPDATE_MESH, OP_REFIT };
+          OP_NOISE_TRACK, OP_NOISE_FOLD, OP_NOISE_POOL, OP_NOISE_ROWS, OP_NOISE_VARIANCE, OP_ADAPT_ENABLE, OP_ADAPT_RETIRE, OP_DENOISE_PREP, OP_DENOISE_FILTER, OP_PATH_TRACE_BATCH, OP_ADAPT_SET_BUDGETS, OP_ADAPT_TILE_NOISE, OP_UPDATE_MESH, OP_REFIT, OP_ACCEL_QUALITY, OP_REFIT_POLICY };
 // One posted call, copied into the ring by assignment: plain data (pointers must stay valid until the caller has drained: load_scene, set_proxy,
 // resolve do) but for `batch`, a shared pointer -- so every post and every worker-side copy of a command pays one atomic reference count, null or not.
 struct Cmd {
@@ -409,6 +409,8 @@ static void worker_run(Worker *w, const Cmd &cmd) {
         case OP_SET_PROXY: rc = evplp_set_splat_proxy(c, (const float *)cmd.p0, cmd.i[0], (const int32_t *)cmd.p1, cmd.i[1]); break;
         case OP_UPDATE_MESH: rc = evplp_update_mesh(c, cmd.i[0], (const float *)cmd.p0, cmd.i[1]); break;
         case OP_REFIT: rc = evplp_refit_accel(c); break;
+        case OP_ACCEL_QUALITY: rc = evplp_accel_quality(c, (struct evplp_accel_quality *)cmd.out + w->rank); break;      // (out: one record per rank, the caller's)
+        case OP_REFIT_POLICY: rc = evplp_set_refit_policy(c, cmd.d, cmd.i[0]); break;
         case OP_SET_REFERENCE: rc = evplp_set_error_reference(c, (const float *)cmd.p0, (const uint8_t *)cmd.p1); break;
         case OP_FRAME_ERROR: rc = evplp::frame_error_rows(c); break;          // (behind this rank's composite, on its stream)
         case OP_NOISE_TRACK: rc = evplp_noise_track(c, cmd.i[0], (const uint8_t *)cmd.p0); break;
@@ -808,6 +810,33 @@ extern "C" int evplp_group_refit_accel(evplp_group *g) {
     if (!evplp::refit_check(g->ctx[0])) { g->set_error("%s", g->ctx[0]->error); return EVPLP_ERR_INVALID; }
     g->sums_fresh = false;
     Cmd c; c.op = OP_REFIT;
+    return post_and_wait(g, c);
+}
+// The scene and the tree are replicated, so every rank measures the same doubles (and a policy decides the same on each): rank 0's are the
+// group's, and a rank that differs is an error.
+extern "C" int evplp_group_accel_quality(evplp_group *g, struct evplp_accel_quality *out) {
+    GRP_CHECK(g);
+    if (!out) { g->set_error("evplp_group_accel_quality: null destination"); return EVPLP_ERR_INVALID; }
+    drain(g);
+    if (!evplp::accel_quality_check(g->ctx[0], "evplp_group_accel_quality")) { g->set_error("%s", g->ctx[0]->error); return EVPLP_ERR_INVALID; }
+    std::vector<struct evplp_accel_quality> q((size_t)g->n);
+    Cmd c; c.op = OP_ACCEL_QUALITY; c.out = q.data();
+    const int rc = post_and_wait(g, c);
+    if (rc < 0) return rc;
+    for (int r = 1; r < g->n; r++)
+        if (std::memcmp(&q[(size_t)r], &q[0], 6 * sizeof(double)) != 0 || q[(size_t)r].last_action != q[0].last_action || q[(size_t)r].policy_rebuilds != q[0].policy_rebuilds) {
+            g->set_error("evplp_group_accel_quality: rank %d's tree differs from rank 0's (cost %.17g against %.17g, %d policy rebuilds against %d): the ranks' scenes are not the same",
+                         r, q[(size_t)r].cost, q[0].cost, q[(size_t)r].policy_rebuilds, q[0].policy_rebuilds);
+            return EVPLP_ERR_INVALID;
+        }
+    *out = q[0];
+    return EVPLP_OK;
+}
+extern "C" int evplp_group_set_refit_policy(evplp_group *g, double max_cost_ratio, int32_t rebuild_builder) {
+    GRP_CHECK(g);
+    drain(g);
+    if (!evplp::refit_policy_check(g->ctx[0], max_cost_ratio, rebuild_builder)) { g->set_error("%s", g->ctx[0]->error); return EVPLP_ERR_INVALID; }
+    Cmd c; c.op = OP_REFIT_POLICY; c.d = max_cost_ratio; c.i[0] = rebuild_builder;
     return post_and_wait(g, c);
 }
 extern "C" int evplp_group_path_trace(evplp_group *g, const float camera_pos[3], uint32_t rng_seed, uint32_t max_bounces, int32_t do_accumulate) {

@@ -129,6 +129,8 @@ typedef struct evplp_config {
      *                                   + 4 B per tile and 4 B per item of the largest call (the item table);
      *                                   budget mode: + 8 B per tile after evplp_adaptive_tile_noise
      *   refit (after a call)            28 B per node + 36 B per triangle (+ 4 B per light triangle), and the same staging bytes in pinned host memory (evplp_refit_accel)
+ *   tree cost (after a call)        24 B per 256 nodes + 8 B, and the same in pinned host memory; the refit's plan and staging (the row above) if no
+ *                                   refit of this tree has made them yet: refit_prepare makes them (evplp_accel_quality, evplp_set_refit_policy)
      *   denoiser (after a call)         124 B per pixel of the context's planes (evplp_denoise); a group's rank: 92 B per pixel of its planes
      *                                   + n x 80 B per pixel of the exchanged rows, and rank 0 + 112 B per image pixel (evplp_group_denoise)
      * A caller that has the device to itself sets cut_scratch_bytes = 72 GB, vsl_mask_bytes = 14 GB for config #5 (one band, one launch). */
@@ -259,12 +261,13 @@ int evplp_scene_metrics(evplp_context *ctx, float *bounding_sphere_radius, float
  * While any mesh is dirty EVERY pass is refused (primary, light tracing, the gathers, the splat, both path tracers, the denoiser) with a
  * message that names the two ways out: a stale tree under new vertices never renders.
  *   evplp_refit_accel keeps the tree's topology and leaf assignment and recomputes, on the device and on the context's stream (behind every
- *     pass already enqueued, the light tracing of overlap_light_tracing included; no host wait in the steady state): the dirty triangles'
+ *     pass already enqueued, the light tracing of overlap_light_tracing included; no host wait in the steady state unless a refit policy is set, below): the dirty triangles'
  *     vertices, every leaf's triangle operands, all boxes bottom-up (one launch per height of the tree, padded once from the exact union
  *     with the builders' pad for the new scene bounds) and the four-wide nodes; and on the host the light's CDF and area, the light bounds,
  *     total_area and bounding_radius, by the code evplp_build_accel uses.  Visibility and closest hit are exact predicates over the
  *     triangles, so a frame over the refitted tree equals the frame of a fresh build bit for bit; what ages is the tree's quality -- after
- *     large motions the walks visit more nodes, and evplp_build_accel is the remedy.  Nothing dirty: returns EVPLP_OK and launches nothing.
+ *     large motions the walks visit more nodes, and evplp_build_accel is the remedy (evplp_accel_quality measures it, evplp_set_refit_policy
+ *     lets the refit act on it).  Nothing dirty: returns EVPLP_OK and launches nothing.
  *     The first refit of a tree makes its plan (evplp_refit_levels) and allocates 28 B per node + 36 B per triangle on the device.
  *   evplp_build_accel on a dirty context is the full rebuild from the updated meshes and clears the dirty state too.
  * Degenerate triangles (meshBound's rule: area not > 0 or not finite): one that BECOMES degenerate gets all-zero operands and adds nothing
@@ -284,6 +287,51 @@ int evplp_refit_info(evplp_context *ctx, int32_t *refits, int32_t *levels, float
  * storage order is assumed.  Returns the number of heights (>= 1), or EVPLP_ERR_INVALID -- always promptly -- for a child index >= nnodes, a
  * node reached twice (two parents, a cycle), more heights than level_capacity, null arrays, nnodes < 1. */
 int evplp_refit_levels(const void *nodes64, int32_t nnodes, int32_t *height, int32_t *order, int32_t *level_begin, int32_t level_capacity);
+
+/* ---- how good the tree still is: its SAH cost, measured on the device, and an opt-in rebuild policy (INTEGRATION B7) ----
+ * The figure is the surface-area-heuristic cost of the flattened tree as it is on the device, from the boxes the walks test (the padded
+ * centre / half-size child boxes of the 64-byte nodes).  Over every node the root reaches and each child slot s whose reference is not
+ * absent: a = 8 (hx hy + hy hz + hz hx) in fp64 from the fp32 half-sizes; an inner child adds a to inner_area; a leaf of cnt triangles
+ * (cnt = (~reference & 3) + 1) adds a * cnt to leaf_tri_area and a * ((cnt + 1) >> 1) to leaf_pair_area -- the packet walk tests a leaf two
+ * triangles at a time.  A triangle that a refit zeroed as degenerate keeps its slot and still counts in its leaf's cnt, because the walk
+ * still tests it; a box with a negative half-size (an absent child, a leaf whose triangles have ALL lost their area) holds nothing and
+ * adds nothing.  root_area = the area of the union of the root's present child boxes, 2 (dx dy + dy dz + dz dx), 0 for the empty tree.
+ *   cost = (15 (root_area + inner_area) + 40 leaf_pair_area) / root_area, 0 where root_area is 0
+ * 15 and 40 are the vector instructions of a node visit and of a pair test of the packet walk; the three raw sums are reported so that a
+ * caller can weigh them otherwise.  The frame never depends on the figure: it is the same whatever the tree.
+ *   evplp_accel_cost is the host-only statement of that arithmetic (no GPU, deterministic): nodes64 as for evplp_refit_levels, whose order
+ *     it takes and whose refusals it shares (not a tree: EVPLP_ERR_INVALID, promptly; any number of heights is accepted).  The terms are
+ *     added in chunks of 256 entries of that order, within a chunk by halving strides over each run of 64 and then run by run, and the
+ *     chunks in index order.  out = { cost, root_area, inner_area, leaf_pair_area, leaf_tri_area }.  Returns the number of reached nodes.
+ *   evplp_accel_quality measures the same on the device: one 256-thread kernel over the refit's plan (a tree that has not been refitted
+ *     gets its plan here, with the refit's allocations) plus 24 B per 256 nodes on the device and in pinned host memory, on the context's
+ *     stream behind everything enqueued, and waits for it.  On the bytes evplp_debug_accel(ctx, 0, ...) returns, its five doubles equal
+ *     evplp_accel_cost's bit for bit.  It changes no node, no plane and no counter.  EVPLP_ERR_INVALID before evplp_build_accel, and while
+ *     vertices are dirty (as every pass: evplp_refit_accel or evplp_build_accel first).
+ *     built_cost = the cost at the first measurement since the last evplp_build_accel, kept until the next one (0: not measured yet);
+ *     reached_nodes, leaf_refs = the nodes and the leaf references the sums run over; refits_since_build = refits of this tree (counted
+ *     with or without a policy); policy_rebuilds = rebuilds the policy has made since evplp_create; last_action = what the last
+ *     evplp_refit_accel that had a policy and something to do did: 0 none, 1 refit kept, 2 rebuilt (evplp_build_accel resets it to 0).
+ *   evplp_set_refit_policy(ctx, max_cost_ratio, rebuild_builder): max_cost_ratio = 0 switches the policy off, which is the default, and
+ *     evplp_refit_accel is then exactly the call above.  With max_cost_ratio > 0 evplp_refit_accel, after its refit, measures the cost
+ *     (one small launch and ONE HOST WAIT: the call is no longer free of host waits) and, when cost > max_cost_ratio * built_cost, runs
+ *     the full rebuild -- the code of evplp_build_accel with rebuild_builder, an evplp_bvh_builder or -1 for the context's own --, measures
+ *     the new built_cost and counts policy_rebuilds.  It returns EVPLP_OK either way; last_action says which.  A rebuild is what
+ *     evplp_build_accel costs: 198 ms with the SAH builder, 13.9 ms with the device LBVH for 331 k triangles (profiles/refit_times.txt).
+ *     Like a refit, a policy rebuild leaves accumulators, noise moments and adaptive records alone.  While a policy is set
+ *     evplp_build_accel re-measures built_cost; setting one on a clean, built context without a built_cost measures it there and then.
+ *     EVPLP_ERR_INVALID: a ratio that is negative or not finite, a builder outside -1 .. 3, vertices dirty.  No ratio is recommended
+ *     here: DESIGN section 6b has what was measured. */
+struct evplp_accel_quality {            /* (the call below has the same name: C and C++ both need the word `struct` in front of the type) */
+    double cost, root_area, inner_area, leaf_pair_area, leaf_tri_area;
+    double built_cost;
+    int32_t reached_nodes, leaf_refs;
+    int32_t refits_since_build, policy_rebuilds;
+    int32_t last_action, pad;
+};
+int evplp_accel_cost(const void *nodes64, int32_t nnodes, double out[5]);
+int evplp_accel_quality(evplp_context *ctx, struct evplp_accel_quality *out);
+int evplp_set_refit_policy(evplp_context *ctx, double max_cost_ratio, int32_t rebuild_builder);
 
 /* ---- the per-iteration passes of RtComPhoton::run() (rtcomphoton.h:936-1068) ---- */
 /* [deferredShading] + [lightRender]: runDeferredProgram (:710-754) + runLightProgram (:839-855);
@@ -619,7 +667,8 @@ int evplp_debug_counters(evplp_context *ctx, int32_t pass, uint64_t *out, int32_
 /* For tests: the acceleration structure as it is on the device, copied to the host.  which = 0 nodes (64 B each), 1 leaf blocks (192 B),
  * 2 the flat triangle operands (48 B per slot, 4 slots per block), 3 the slots' original triangle indices (int32, -1 = empty), 4 the
  * four-wide nodes (128 B), 5 one float: the box pad of the last build or refit (the host builders' formula), 6 four floats: the last refit's
- * upload, leaf, box and four-wide stages in ms (zeros unless evplp_profile_kernels was on).  bytes must be the array's size exactly (counts
+ * upload, leaf, box and four-wide stages in ms (zeros unless evplp_profile_kernels was on), 7 one float: the last cost measurement
+ * (evplp_accel_quality, or a policy's) in ms, kernel and copy of its sums (zero unless evplp_profile_passes was on).  bytes must be the array's size exactly (counts
  * from evplp_accel_info, at least one node and one block): EVPLP_ERR_INVALID otherwise.  Waits for the stream. */
 int evplp_debug_accel(evplp_context *ctx, int32_t which, void *host_dst, size_t bytes);
 /* Flattened acceleration structure statistics: nodes, leaves, max depth, build ms */
@@ -723,6 +772,11 @@ int evplp_group_set_splat_proxy(evplp_group *g, const float *vertices, int32_t n
  * group staying usable, where the plain context refuses. */
 int evplp_group_update_mesh(evplp_group *g, int32_t mesh, const float *vertices, int32_t nverts);
 int evplp_group_refit_accel(evplp_group *g);
+/* evplp_accel_quality / evplp_set_refit_policy on every rank (both partitions; the calls wait for the ranks).  Scene and tree are replicated,
+ * so every rank computes the same doubles and a policy takes the same decision on each; the group returns rank 0's figures and fails
+ * (EVPLP_ERR_INVALID) if any rank's differ.  Refused on the caller's thread, the group staying usable, where the plain context refuses. */
+int evplp_group_accel_quality(evplp_group *g, struct evplp_accel_quality *out);
+int evplp_group_set_refit_policy(evplp_group *g, double max_cost_ratio, int32_t rebuild_builder);
 int evplp_group_path_trace(evplp_group *g, const float camera_pos[3], uint32_t rng_seed, uint32_t max_bounces, int32_t do_accumulate);
 /* evplp_path_trace_batch, routed like evplp_group_path_trace: a strips group runs it on every rank for its own rows (the result equals one
  * context's bit for bit; evplp_set_blocks / evplp_group_rebalance behave as for evplp_group_path_trace), an iterations group on the selected

@@ -8,8 +8,13 @@
   (3) the config-#2 gather (tools/quick_bench.py's pass: 1024 x 1024, 1024 VPL paths, misMode one) over three trees of the SAME moved scene
       (b): the refitted SAH tree, a rebuilt SAH tree, a rebuilt device LBVH.
   (4) the same for a large motion: every chair displaced by a metre in a seeded direction -- what the topology's ageing costs.
+  (5) evplp_accel_quality on the SAH tree: HIP events on the context's stream (evplp_debug_accel(7)) and the host's wall time of the call.
+  (6) does the figure track the time?  For the motions of (3) and (4) and three larger ones -- neighbouring chairs swapped (they have passed
+      through each other), the two rows of chairs swapped across the room, every chair at another chair's place (seeded) -- the SAH cost
+      (evplp_accel_quality) of the refitted SAH tree and of a rebuilt SAH tree of the same moved scene, and beside it the config-#2 gather
+      time of each.
 
-usage: python tools/refit_times.py [--reps N] [--tris N] [--res N]"""
+usage: python tools/refit_times.py [--reps N] [--tris N] [--res N] [--quality-only]"""
 import argparse
 import math
 import os
@@ -114,11 +119,69 @@ def time_gather(c, sd, reps, name):
     return statistics.median(ms)
 
 
+def time_quality(c, reps):
+    c.profile_passes(True)
+    ev_ms, wall = [], []
+    for r in range(reps + 2):
+        c.synchronize()
+        t0 = time.perf_counter(); q = c.accel_quality(); t1 = time.perf_counter()
+        if r >= 2:
+            ev_ms.append(float(c.debug_accel(7))); wall.append((t1 - t0) * 1e3)
+    print(f"(5) evplp_accel_quality: {q['reached_nodes']} nodes, {q['leaf_refs']} leaf references, cost {q['cost']:.3f} (root {q['root_area']:.2f}, inner {q['inner_area']:.1f}, "
+          f"pairs {q['leaf_pair_area']:.1f}, triangles {q['leaf_tri_area']:.1f})")
+    print(f"      device, kernel + copy of the sums ms {spread(ev_ms)}")
+    print(f"      host, the call                    ms {spread(wall)}")
+
+
+def chair_motions(sd, chairs, orig, small, large):
+    """(name, meshes that move, vertices of every mesh) for (6)"""
+    ctr = {k: 0.5 * (orig[k].min(0) + orig[k].max(0)) for k in chairs}
+    rows = [sorted((k for k in chairs if ctr[k][1] < 0.0), key=lambda k: ctr[k][0]), sorted((k for k in chairs if ctr[k][1] > 3.0), key=lambda k: ctr[k][0])]
+
+    def to_places(pairs):
+        v = list(orig)
+        for k, dst in pairs:
+            d = ctr[dst] - ctr[k]
+            v[k] = (orig[k] + np.array([d[0], d[1], 0.0], F)).astype(F)
+        return [k for k, _ in pairs], v
+    neigh = [p for row in rows for i in range(0, len(row) - 1, 2) for p in ((row[i], row[i + 1]), (row[i + 1], row[i]))]
+    across = [p for a, b in zip(*rows) for p in ((a, b), (b, a))]
+    perm = np.random.RandomState(9).permutation(len(chairs))
+    shuffle = [(k, chairs[perm[i]]) for i, k in enumerate(chairs) if chairs[perm[i]] != k]
+    return [("every mesh moved by a centimetre", list(range(len(sd.meshes))), small), ("every chair a metre away (seeded directions)", chairs, large),
+            ("neighbouring chairs swapped", *to_places(neigh)), ("the rows of chairs swapped across the room", *to_places(across)),
+            ("every chair at another chair's place (seeded)", *to_places(shuffle))]
+
+
+def quality_table(sd, a, chairs, orig, small, large):
+    print("(6) SAH cost (evplp_accel_quality) and config-#2 gather ms of the refitted SAH tree and of a rebuilt SAH tree of the same moved scene")
+    rows = []
+    for name, meshes, verts in chair_motions(sd, chairs, orig, small, large):
+        print(f"    {name}: {len(meshes)} meshes moved")
+        c = context(sd, a.res, ev.BVH_SAH)
+        built = c.accel_quality()["cost"]
+        for m in meshes:
+            c.update_mesh(m, verts[m])
+        c.refit_accel()
+        q_refit = c.accel_quality()
+        t_refit = time_gather(c, sd, a.reps, "refitted SAH")
+        c.close()
+        c = context(sd, a.res, ev.BVH_SAH, verts)
+        q_sah = c.accel_quality()
+        t_sah = time_gather(c, sd, a.reps, "rebuilt SAH")
+        c.close()
+        rows.append((name, built, q_refit["cost"], q_sah["cost"], q_refit["cost"] / q_sah["cost"], t_refit, t_sah, t_refit / t_sah))
+    print("    motion | cost as built | cost refitted | cost rebuilt | cost ratio | gather refitted ms | gather rebuilt ms | time ratio")
+    for r in rows:
+        print("    %s | %.2f | %.2f | %.2f | %.3f | %.2f | %.2f | %.3f" % r)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=40)
     ap.add_argument("--tris", type=int, default=331000)
     ap.add_argument("--res", type=int, default=1024)
+    ap.add_argument("--quality-only", action="store_true", help="parts (5) and (6) alone")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory(prefix="evplp_refit_") as d:
         sd, _ = scenes.load_obj_scene(ev.synth_scene(d, "conf", a.tris, 1234, a.res, a.res, style="hard"))
@@ -133,6 +196,12 @@ def main():
         ang = rng.rand() * 2 * math.pi
         large[k] = (orig[k] + np.array([math.cos(ang), math.sin(ang), 0.0], F)).astype(F)
 
+    if a.quality_only:
+        c = context(sd, a.res, ev.BVH_SAH)
+        time_quality(c, a.reps)
+        c.close()
+        quality_table(sd, a, chairs, orig, small, large)
+        return
     c = context(sd, a.res, ev.BVH_SAH)
     one = chairs[:1] if chairs else [0]
     nudged = list(orig)
@@ -140,6 +209,7 @@ def main():
     time_refits(c, sd, one, (nudged, orig), a.reps, "(a) one chair")
     every = list(range(len(sd.meshes)))
     refit_ms, refit_wall = time_refits(c, sd, every, (small, orig), a.reps, "(b) every mesh, small translation")
+    time_quality(c, a.reps)
     sah_wall = time_builds(c, a.reps, "SAH (host)")
     c.close()
     g = context(sd, a.res, GPU_BUILDER)
@@ -162,6 +232,7 @@ def main():
         t_gpu = time_gather(c, sd, a.reps, "rebuilt device LBVH")
         c.close()
         print(f"      refitted / rebuilt SAH: {t_refit / t_sah:.3f}   refitted SAH / rebuilt device LBVH: {t_refit / t_gpu:.3f}   rebuilt device LBVH / rebuilt SAH: {t_gpu / t_sah:.3f}")
+    quality_table(sd, a, chairs, orig, small, large)
 
 
 if __name__ == "__main__":
