@@ -27,7 +27,8 @@ OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_IO, ERR_PARSE, ERR_OOM = 0, -1, -2,
 USABLE_VPL, USABLE_PHOTON, LAMBERT_ONLY, PHONG_ONLY = 1, 2, 4, 8
 # EMis (rtcomphoton.h:64-72, string map :1199-1206)
 MIS_MODES = {"one": 0, "balance": 1, "max": 2, "power2": 3, "geometryClamp": 4, "geometryBrdfClamp": 5}
-BVH_LBVH, BVH_SAH, BVH_SBVH, BVH_LBVH_GPU = 0, 1, 2, 3
+BVH_LBVH, BVH_SAH, BVH_SBVH, BVH_LBVH_GPU, BVH_PLOC_GPU = 0, 1, 2, 3, 4
+PLOC_RADIUS, PLOC_MAX_RADIUS, PLOC_SEARCH_ITERATIONS = 16, 32, 128      # csrc/evplp_types.h
 (BUF_RECORDS, BUF_GBUF_POSITION, BUF_GBUF_NORMAL, BUF_GBUF_DIFFUSE, BUF_GBUF_PHONG, BUF_LIGHT,
  BUF_VPL_ACCUM, BUF_PHOTON_ACCUM, BUF_COUNT) = range(9)
 (PASS_PRIMARY, PASS_LIGHT_TRACE, PASS_GATHER_VPL, PASS_GATHER_VSL, PASS_SPLAT, PASS_RESOLVE, PASS_PATH_TRACE,
@@ -143,6 +144,7 @@ _SIGNATURES = {
     "evplp_group_refit_accel": (C.c_int, [_P]),
     "evplp_accel_cost": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double)]),
     "evplp_accel_quality": (C.c_int, [_P, C.POINTER(AccelQuality)]),
+    "evplp_ploc_tree": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.POINTER(C.c_int32)]),
     "evplp_set_refit_policy": (C.c_int, [_P, C.c_double, C.c_int32]),
     "evplp_group_accel_quality": (C.c_int, [_P, C.POINTER(AccelQuality)]),
     "evplp_group_set_refit_policy": (C.c_int, [_P, C.c_double, C.c_int32]),
@@ -525,7 +527,7 @@ class Context:
         self._check(self._lib.evplp_accel_info(self._h, C.byref(n), C.byref(l), C.byref(d), C.byref(ms)))
         b = self._lib.evplp_accel_builder(self._h)
         return {"nodes": n.value, "leaves": l.value, "depth": d.value, "build_ms": ms.value,
-                "builder": {0: "lbvh", 1: "sah", 2: "sbvh", 3: "gpu"}.get(b, "none"), "stack4_entries": self._lib.evplp_accel_stack_entries(self._h)}
+                "builder": {0: "lbvh", 1: "sah", 2: "sbvh", 3: "gpu", 4: "ploc"}.get(b, "none"), "stack4_entries": self._lib.evplp_accel_stack_entries(self._h)}
 
     def selftest(self, which: int = 0) -> np.ndarray:
         """evplp_selftest: 0 the exact reciprocal, 1 the hardware pow, 2 the hand-written triangle-pair test against tri_pair_test
@@ -793,6 +795,18 @@ def accel_cost(nodes) -> dict:
     if rc < 0:
         raise EvplpError(rc, "evplp_accel_cost: not a tree (a child index out of range, a node reached twice, a cycle), or no nodes")
     return {"cost": out[0], "root_area": out[1], "inner_area": out[2], "leaf_pair_area": out[3], "leaf_tri_area": out[4], "reached_nodes": rc}
+
+
+def ploc_tree(verts9, radius: int = PLOC_RADIUS, search_iterations: int = PLOC_SEARCH_ITERATIONS):
+    """evplp_ploc_tree: the tree the device PLOC builder makes, on the host (deterministic).  verts9: 9 floats per triangle.  Returns (order [n]: the
+    valid triangles in Morton order, children [n - 1, 2]: inner index or ~position, iterations)."""
+    v = np.ascontiguousarray(verts9, dtype=np.float32).reshape(-1, 9)
+    ntri = v.shape[0]
+    order, children, it = np.zeros(max(ntri, 1), np.int32), np.zeros((max(ntri - 1, 1), 2), np.int32), C.c_int32(0)
+    n = lib().evplp_ploc_tree(_ptr(v), ntri, int(radius), int(search_iterations), _ptr(order), _ptr(children), C.byref(it))
+    if n < 0:
+        raise EvplpError(n, "evplp_ploc_tree: a null pointer, or a radius outside 1 .. 32, or search_iterations outside 0 .. 128")
+    return order[:n].copy(), children[:max(n - 1, 0)].copy(), it.value
 
 
 Context.refit_levels = staticmethod(refit_levels)      # (the plan needs no context; it is listed with the calls it serves)

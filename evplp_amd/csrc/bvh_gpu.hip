@@ -10,6 +10,8 @@
 //   3. hierarchy    : Karras 2012 -- every internal node of the binary radix tree finds its range and split on its own
 //                     (keys made unique by their position).
 //   4. refit        : leaf boxes, then internal boxes bottom-up (the second thread to arrive at a node owns it).
+//   3' - 4'. PLOC   : EVPLP_BVH_PLOC_GPU replaces 3 - 4 by locally-ordered clustering over the same sort (the ploc_* kernels below);
+//                     5 - 6 consume its tree unchanged.
 //   5. collapse     : subtrees of <= 4 triangles become leaf blocks (the walks test triangles two at a time, 4 per block);
 //                     nodes with more than 4 triangles are kept and renumbered by a prefix sum.
 //   6. emit         : kept nodes with both child boxes (padded, centre / half-size form), leaf blocks with the
@@ -266,6 +268,113 @@ __global__ __launch_bounds__(256) void emit_leaves_kernel(const float *verts, co
     }
 }
 
+// ---- PLOC (EVPLP_BVH_PLOC_GPU): steps 3 - 4 by locally-ordered clustering instead of the radix tree.  The n sorted valid triangles are the
+// first clusters (position p: reference ~p, its triangle's box).  One iteration over c clusters is four launches and nothing else hands
+// over: ploc_nn (search iterations only) finds every position's nearest neighbour within `radius` positions; ploc_merge flags the mutual
+// pairs (the lower position of a pair merges, the upper is vacated); one exclusive scan of the packed flags (low word merges, high word
+// survivors) numbers both; ploc_scatter writes the new nodes -- m merges among c clusters get indices c - 1 - m + rank, so the last merge
+// of the build is node 0 -- and the surviving clusters in position order into the other half of the ping-pong.  The host reads c back.
+// ploc_place then gives every leaf and inner node its first position in the tree's own left-to-right order (up its parent chain: + the
+// left sibling's triangles wherever it is a right child) and fills what stages 5 - 6 consume.  host/ploc.cpp states the same serially.
+struct PlocKids { int32_t left, right; };
+__device__ __forceinline__ int32_t ploc_partner(const int32_t *nn, int pairing, int i, int c) { return pairing ? ((i ^ 1) < c ? (i ^ 1) : i) : nn[i]; }
+__device__ __forceinline__ int32_t ploc_count(const int32_t *ncnt, int32_t ref) { return ref < 0 ? 1 : ncnt[ref]; }
+
+__global__ __launch_bounds__(256) void ploc_init_kernel(const Bx *tbox, const int32_t *ids, int n, int32_t *cref, Bx *cbox) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    cref[p] = ~p;
+    cbox[p] = tbox[ids[p]];
+}
+// the workgroup's 256 positions and `radius` on either side, staged once (component by component: a wavefront reads 64 consecutive words)
+__global__ __launch_bounds__(256) void ploc_nn_kernel(const Bx *cbox, int c, int radius, int32_t *nn) {
+#pragma clang fp contract(off)
+    __shared__ float tile[6][256 + 2 * kPlocMaxRadius];
+    const int tid = (int)threadIdx.x, base = (int)blockIdx.x * 256 - radius;
+    for (int t = tid; t < 256 + 2 * radius; t += 256) {
+        const int p = base + t;
+        if (p >= 0 && p < c) { const Bx b = cbox[p]; for (int k = 0; k < 3; k++) { tile[k][t] = b.lo[k]; tile[3 + k][t] = b.hi[k]; } }
+    }
+    __syncthreads();
+    const int i = base + radius + tid;
+    if (i >= c) return;
+    float own[6];
+    for (int k = 0; k < 6; k++) own[k] = tile[k][tid + radius];
+    float best = 0.f; int bj = -1;
+    const int j0 = max(0, i - radius), j1 = min(c - 1, i + radius);
+    for (int j = j0; j <= j1; j++) {
+        if (j == i) continue;
+        float other[6];
+        for (int k = 0; k < 6; k++) other[k] = tile[k][j - base];
+        const float d = ploc_distance(own, other);
+        if (bj < 0 || d < best) { best = d; bj = j; }                        // ties keep the lowest j: the globally closest pair is always mutual
+    }
+    nn[i] = bj < 0 ? i : bj;
+}
+// flags[i] = (position i survives) << 32 | (position i is the lower one of a mutual pair)
+__global__ __launch_bounds__(256) void ploc_merge_kernel(const int32_t *nn, int pairing, int c, unsigned long long *flags) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= c) return;
+    const int32_t j = ploc_partner(nn, pairing, i, c);
+    const bool merged = j != i && j >= 0 && j < c && ploc_partner(nn, pairing, j, c) == i;
+    flags[i] = ((unsigned long long)((!merged || i < j) ? 1u : 0u) << 32) | (unsigned long long)((merged && i < j) ? 1u : 0u);
+}
+// scan = the exclusive sums of flags.  Only the lower position of a pair writes its node.  scal[0] = the root's height in kept nodes, scal[1] = c after this iteration
+__global__ __launch_bounds__(256) void ploc_scatter_kernel(const int32_t *nn, int pairing, int c, int n, const unsigned long long *flags, const unsigned long long *scan,
+                                                           const int32_t *cref_in, const Bx *cbox_in, int32_t *cref_out, Bx *cbox_out, PlocKids *kids, Bx *ibox,
+                                                           int32_t *ncnt, uint32_t *height, int32_t *parent_int, int32_t *parent_leaf, uint32_t *scal) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= c) return;
+    const unsigned long long total = scan[c - 1] + flags[c - 1], f = flags[i], s = scan[i];
+    const int m = (int)(uint32_t)total, cn = (int)(total >> 32);
+    if (i == c - 1) scal[1] = (uint32_t)cn;
+    if (!(f >> 32)) return;
+    const int pos = (int)(s >> 32);
+    if (pos >= cn) return;
+    int32_t ref = cref_in[i];
+    Bx box = cbox_in[i];
+    if (f & 1ull) {
+        const int32_t j = ploc_partner(nn, pairing, i, c), idx = c - 1 - m + (int)(uint32_t)s;
+        if (j < 0 || j >= c || idx < 0 || idx > n - 2) return;
+        const int32_t rref = cref_in[j];
+        const Bx rb = cbox_in[j];
+        for (int k = 0; k < 3; k++) { box.lo[k] = fminf(box.lo[k], rb.lo[k]); box.hi[k] = fmaxf(box.hi[k], rb.hi[k]); }
+        const int32_t cnt = ploc_count(ncnt, ref) + ploc_count(ncnt, rref);
+        const uint32_t hl = ref < 0 ? 0u : height[ref], hr = rref < 0 ? 0u : height[rref];
+        const uint32_t h = max(hl, hr) + (cnt > kMaxLeafTris ? 1u : 0u);     // (what refit_kernel carries up)
+        PlocKids kd; kd.left = ref; kd.right = rref;
+        kids[idx] = kd; ibox[idx] = box; ncnt[idx] = cnt; height[idx] = h;
+        if (ref < 0) parent_leaf[~ref] = idx; else parent_int[ref] = idx;
+        if (rref < 0) parent_leaf[~rref] = idx; else parent_int[rref] = idx;
+        if (idx == 0) { parent_int[0] = -1; scal[0] = h; }
+        ref = idx;
+    }
+    cref_out[pos] = ref;
+    cbox_out[pos] = box;
+}
+// thread t < n: the leaf at sorted position t; t >= n: inner node t - n.  ids_out / lbox in tree order, topo as the radix tree's
+__global__ __launch_bounds__(256) void ploc_place_kernel(int n, const PlocKids *kids, const int32_t *ncnt, const int32_t *parent_int, const int32_t *parent_leaf,
+                                                         const int32_t *ids, const Bx *tbox, int32_t *ids_out, Bx *lbox, Topo *topo) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= 2 * n - 1) return;
+    const bool leaf = t < n;
+    int32_t me = leaf ? ~t : t - n, up = leaf ? (n > 1 ? parent_leaf[t] : -1) : parent_int[t - n];
+    int32_t first = 0;
+    for (int step = 0; up >= 0 && up < n - 1 && step < n; step++) {       // (the chain is as long as the binary tree is high)
+        const PlocKids kd = kids[up];
+        if (kd.right == me) first += ploc_count(ncnt, kd.left);
+        me = up; up = parent_int[up];
+    }
+    if (first < 0 || first >= n) return;
+    if (leaf) { const int32_t tri = ids[t]; ids_out[first] = tri; lbox[first] = tbox[tri]; return; }
+    const PlocKids kd = kids[t - n];
+    const int32_t cl = ploc_count(ncnt, kd.left);
+    Topo tp;
+    tp.left = kd.left < 0 ? ~first : kd.left; tp.right = kd.right < 0 ? ~(first + cl) : kd.right;
+    tp.first = first; tp.last = first + ncnt[t - n] - 1;
+    topo[t - n] = tp;
+}
+
 // ---- refit
 // a. src: 9 floats per triangle of the run [first, first + count) of original triangles
 __global__ __launch_bounds__(256) void refit_scatter_kernel(const float *src, int32_t first, int32_t count, TriAttr *attrs) {
@@ -412,8 +521,12 @@ void accel_cost(const BvhNode *d_nodes, int32_t nnodes, const int32_t *d_order, 
 }
 
 // Builds on `stream` from the host triangle list; the four output arrays are device allocations owned by the caller
-// (hipFree).  Returns hipSuccess or the failing HIP status.
-int build_bvh_gpu(const float *verts_host, int32_t ntri, float pad_scale, hipStream_t stream, BvhDeviceBuild *out) {
+// (hipFree).  Returns hipSuccess or the failing HIP status.  ploc_radius > 0: the hierarchy by PLOC (1 .. kPlocMaxRadius, with
+// ploc_search_iterations search iterations, 0 .. kPlocSearchIterations) instead of the radix tree; out->bound_passed with hipSuccess: the
+// iterations passed ploc_iteration_bound and the build was stopped (nothing is handed over).
+// PLOC's scratch on top of the radix tree's, allocated and freed in the call: 2 n clusters in ping-pong (a 4 B reference and a 24 B box
+// each), n nearest neighbours (4 B), n packed flags and their scan (8 B each), and per inner node its children (8 B) and triangle count (4 B).
+int build_bvh_gpu(const float *verts_host, int32_t ntri, float pad_scale, hipStream_t stream, BvhDeviceBuild *out, int32_t ploc_radius, int32_t ploc_search_iterations) {
     auto t0 = std::chrono::steady_clock::now();
     hipError_t err = hipSuccess;
     const int nt = std::max(ntri, 1);
@@ -425,6 +538,12 @@ int build_bvh_gpu(const float *verts_host, int32_t ntri, float pad_scale, hipStr
     int n = 0, nnodes = 0, nblocks = 0;
     const unsigned gt = (unsigned)((nt + 255) / 256);
     BvhNode *nodes = nullptr; LeafBlock *leaves = nullptr; TriFlat *tri_flat = nullptr; int32_t *tri_index = nullptr;
+    const bool ploc = ploc_radius > 0;
+    Bx *cbox[2] = { nullptr, nullptr }; int32_t *cref[2] = { nullptr, nullptr }, *nn = nullptr, *ncnt = nullptr; PlocKids *kids = nullptr;
+    unsigned long long *pflags = nullptr, *pscan = nullptr;
+    const int32_t *leaf_ids = nullptr;                                    // triangle per position, in the order the emitted tree has
+    out->iterations = 0; out->bound_passed = false;
+    if (ploc && (ploc_radius > kPlocMaxRadius || ploc_search_iterations < 0 || ploc_search_iterations > kPlocSearchIterations)) { err = hipErrorInvalidValue; goto done; }
 
     GB_TRY(hipMalloc((void **)&d_verts, sizeof(float) * 9 * (size_t)nt));
     GB_TRY(hipMalloc((void **)&tbox, sizeof(Bx) * (size_t)nt)); GB_TRY(hipMalloc((void **)&lbox, sizeof(Bx) * (size_t)nt)); GB_TRY(hipMalloc((void **)&ibox, sizeof(Bx) * (size_t)nt));
@@ -436,6 +555,11 @@ int build_bvh_gpu(const float *verts_host, int32_t ntri, float pad_scale, hipStr
     GB_TRY(hipMalloc((void **)&visits, 4 * (size_t)nt)); GB_TRY(hipMalloc((void **)&kept, 4 * (size_t)nt)); GB_TRY(hipMalloc((void **)&new_id, 4 * (size_t)nt));
     GB_TRY(hipMalloc((void **)&head, 4 * (size_t)nt)); GB_TRY(hipMalloc((void **)&flag, 4 * (size_t)nt)); GB_TRY(hipMalloc((void **)&block_id, 4 * (size_t)nt));
     GB_TRY(hipMalloc((void **)&scal, 4 * 4));
+    if (ploc) {
+        for (int h = 0; h < 2; h++) { GB_TRY(hipMalloc((void **)&cbox[h], sizeof(Bx) * (size_t)nt)); GB_TRY(hipMalloc((void **)&cref[h], 4 * (size_t)nt)); }
+        GB_TRY(hipMalloc((void **)&nn, 4 * (size_t)nt)); GB_TRY(hipMalloc((void **)&ncnt, 4 * (size_t)nt)); GB_TRY(hipMalloc((void **)&kids, sizeof(PlocKids) * (size_t)nt));
+        GB_TRY(hipMalloc((void **)&pflags, 8 * (size_t)nt)); GB_TRY(hipMalloc((void **)&pscan, 8 * (size_t)nt));
+    }
     if (ntri > 0) GB_TRY(hipMemcpyAsync(d_verts, verts_host, sizeof(float) * 9 * (size_t)ntri, hipMemcpyHostToDevice, stream));
     {
         const uint32_t init[13] = { 0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u, 0u };
@@ -448,6 +572,7 @@ int build_bvh_gpu(const float *verts_host, int32_t ntri, float pad_scale, hipStr
         tmp_bytes = need;
         GB_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, kept, new_id, nt, stream));
         tmp_bytes = std::max(tmp_bytes, need);
+        if (ploc) { GB_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, pflags, pscan, nt, stream)); tmp_bytes = std::max(tmp_bytes, need); }
         GB_TRY(hipMalloc(&tmp, tmp_bytes));
         need = tmp_bytes;
         GB_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, need, keys, keys2, ids, ids2, ntri, 0, 64, stream));
@@ -459,8 +584,33 @@ int build_bvh_gpu(const float *verts_host, int32_t ntri, float pad_scale, hipStr
     GB_TRY(hipMemsetAsync(kept, 0, 4 * (size_t)nt, stream)); GB_TRY(hipMemsetAsync(scal, 0, 16, stream));
     if (n > 0) {
         const unsigned gn = (unsigned)((n + 255) / 256);
-        if (n > 1) hipLaunchKernelGGL(hierarchy_kernel, dim3(gn), dim3(256), 0, stream, keys2, n, topo, parent_int, parent_leaf);
-        hipLaunchKernelGGL(refit_kernel, dim3(gn), dim3(256), 0, stream, tbox, ids2, n, topo, parent_int, parent_leaf, lbox, ibox, visits, new_id /* free until the scan below: node heights */, &scal[0]);
+        leaf_ids = ids2;
+        if (ploc) {
+            hipLaunchKernelGGL(ploc_init_kernel, dim3(gn), dim3(256), 0, stream, tbox, ids2, n, cref[0], cbox[0]);
+            const int32_t bound = ploc_iteration_bound(n, ploc_search_iterations);
+            int c = n, cur = 0, it = 0;
+            while (c > 1) {
+                if (it >= bound) { out->bound_passed = true; out->iterations = it; goto done; }
+                const unsigned gc = (unsigned)((c + 255) / 256);
+                const int pairing = it >= ploc_search_iterations ? 1 : 0;
+                if (!pairing) hipLaunchKernelGGL(ploc_nn_kernel, dim3(gc), dim3(256), 0, stream, cbox[cur], c, (int)ploc_radius, nn);
+                hipLaunchKernelGGL(ploc_merge_kernel, dim3(gc), dim3(256), 0, stream, nn, pairing, c, pflags);
+                need = tmp_bytes; GB_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, need, pflags, pscan, c, stream));
+                hipLaunchKernelGGL(ploc_scatter_kernel, dim3(gc), dim3(256), 0, stream, nn, pairing, c, n, pflags, pscan, cref[cur], cbox[cur], cref[cur ^ 1], cbox[cur ^ 1], kids, ibox,
+                                   ncnt, new_id /* free until the scan below: node heights */, parent_int, parent_leaf, scal);
+                GB_TRY(hipMemcpyAsync(&h_counts[0], &scal[1], 4, hipMemcpyDeviceToHost, stream));
+                GB_TRY(hipStreamSynchronize(stream));                             // the one read-back of an iteration: c
+                const int cn = (int)h_counts[0];
+                if (cn < 1 || cn >= c) { out->bound_passed = true; out->iterations = it; goto done; }      // (an iteration that merged nothing: never, by the tie rule)
+                c = cn; cur ^= 1; it++;
+            }
+            out->iterations = it;
+            hipLaunchKernelGGL(ploc_place_kernel, dim3((unsigned)((2 * (size_t)n - 1 + 255) / 256)), dim3(256), 0, stream, n, kids, ncnt, parent_int, parent_leaf, ids2, tbox, ids, lbox, topo);
+            leaf_ids = ids;                                                   // (free since the sort)
+        } else {
+            if (n > 1) hipLaunchKernelGGL(hierarchy_kernel, dim3(gn), dim3(256), 0, stream, keys2, n, topo, parent_int, parent_leaf);
+            hipLaunchKernelGGL(refit_kernel, dim3(gn), dim3(256), 0, stream, tbox, ids2, n, topo, parent_int, parent_leaf, lbox, ibox, visits, new_id /* free until the scan below: node heights */, &scal[0]);
+        }
         if (n > 1) hipLaunchKernelGGL(collapse_kernel, dim3(gn), dim3(256), 0, stream, topo, n, kept, head);
         else GB_TRY(hipMemsetAsync(head, 0, 4, stream));
         if (n == 1) { const uint32_t one = 1u; GB_TRY(hipMemcpyAsync(head, &one, 4, hipMemcpyHostToDevice, stream)); }
@@ -487,7 +637,7 @@ int build_bvh_gpu(const float *verts_host, int32_t ntri, float pad_scale, hipStr
     if (n > 0) {
         const unsigned gn = (unsigned)((n + 255) / 256);
         hipLaunchKernelGGL(emit_nodes_kernel, dim3(gn), dim3(256), 0, stream, topo, n, kept, new_id, head, block_id, lbox, ibox, bounds, pad_scale, nodes);
-        hipLaunchKernelGGL(emit_leaves_kernel, dim3(gn), dim3(256), 0, stream, d_verts, ids2, n, head, block_id, leaves, tri_flat, tri_index);
+        hipLaunchKernelGGL(emit_leaves_kernel, dim3(gn), dim3(256), 0, stream, d_verts, leaf_ids, n, head, block_id, leaves, tri_flat, tri_index);
     } else {
         BvhNode r; std::memset(&r, 0, sizeof(r));
         for (int k = 0; k < 3; k++) { r.hal[k][0] = r.hal[k][1] = -3.0e38f; }
@@ -503,6 +653,8 @@ int build_bvh_gpu(const float *verts_host, int32_t ntri, float pad_scale, hipStr
 done:
     hipFree(d_verts); hipFree(tbox); hipFree(lbox); hipFree(ibox); hipFree(valid); hipFree(bounds); hipFree(keys); hipFree(keys2); hipFree(ids); hipFree(ids2);
     hipFree(parent_int); hipFree(parent_leaf); hipFree(topo); hipFree(visits); hipFree(kept); hipFree(new_id); hipFree(head); hipFree(flag); hipFree(block_id); hipFree(scal);
+    for (int h = 0; h < 2; h++) { hipFree(cbox[h]); hipFree(cref[h]); }
+    hipFree(nn); hipFree(ncnt); hipFree(kids); hipFree(pflags); hipFree(pscan);
     hipFree(tmp); hipFree(nodes); hipFree(leaves); hipFree(tri_flat); hipFree(tri_index);
     out->build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return (int)err;

@@ -71,10 +71,23 @@ extern "C" int evplp_create(const evplp_config *cfg, evplp_context **out) {
     e = hipSetDevice(cfg->device);
     if (e != hipSuccess) { snprintf(g_create_error, sizeof(g_create_error), "hipSetDevice: %s", hipGetErrorString(e)); return EVPLP_ERR_NO_DEVICE; }
 
+    int32_t ploc_radius = 0, ploc_iterations = -1;
+    // (developer overrides of the PLOC builder, so that tests reach the window's edges and the pairing phase on small scenes)
+    if (const char *env = std::getenv("EVPLP_PLOC_RADIUS")) {
+        char *end = nullptr; const long v = strtol(env, &end, 10);
+        if (end == env || *end || v < 1 || v > kPlocMaxRadius) { snprintf(g_create_error, sizeof(g_create_error), "evplp_create: EVPLP_PLOC_RADIUS=%s is not in 1 .. %d", env, kPlocMaxRadius); return EVPLP_ERR_INVALID; }
+        ploc_radius = (int32_t)v;
+    }
+    if (const char *env = std::getenv("EVPLP_PLOC_ITERATIONS")) {
+        char *end = nullptr; const long v = strtol(env, &end, 10);
+        if (end == env || *end || v < 0 || v > kPlocSearchIterations) { snprintf(g_create_error, sizeof(g_create_error), "evplp_create: EVPLP_PLOC_ITERATIONS=%s is not in 0 .. %d", env, kPlocSearchIterations); return EVPLP_ERR_INVALID; }
+        ploc_iterations = (int32_t)v;
+    }
     evplp_context *c = new evplp_context();
     c->cfg = *cfg; c->cfg.strip_count = strip_count; c->cfg.strip_rows = strip_rows;
     if (const char *env = std::getenv("EVPLP_BVH_BUILDER"))
-        c->env_bvh_builder = !std::strcmp(env, "sbvh") ? EVPLP_BVH_SBVH : !std::strcmp(env, "lbvh") ? EVPLP_BVH_LBVH : !std::strcmp(env, "gpu") ? EVPLP_BVH_LBVH_GPU : EVPLP_BVH_SAH;
+        c->env_bvh_builder = !std::strcmp(env, "sbvh") ? EVPLP_BVH_SBVH : !std::strcmp(env, "lbvh") ? EVPLP_BVH_LBVH : !std::strcmp(env, "gpu") ? EVPLP_BVH_LBVH_GPU : !std::strcmp(env, "ploc") ? EVPLP_BVH_PLOC_GPU : EVPLP_BVH_SAH;
+    c->env_ploc_radius = ploc_radius; c->env_ploc_iterations = ploc_iterations;
     if (const char *env = std::getenv("EVPLP_CUTS")) c->env_cuts = atoi(env) != 0 ? 1 : 0;
     if (const char *env = std::getenv("EVPLP_ITEM_DEAL")) c->env_item_deal = atoi(env) != 0 ? 1 : 0;
     if (const char *env = std::getenv("EVPLP_CUT_BYTES")) c->env_cut_bytes = (size_t)strtoull(env, nullptr, 10);      // (tests: forces the band path)
@@ -419,13 +432,18 @@ static int build_accel(evplp_context *c, int policy_builder) {
     if (light_count <= 0) { c->set_error("evplp_build_accel: the area-light mesh has no triangles"); return EVPLP_ERR_INVALID; }
     BvhBuild bb;
     int builder = policy_builder >= 0 ? policy_builder : c->env_bvh_builder >= 0 ? c->env_bvh_builder : c->cfg.bvh_builder;   // (override read by evplp_create)
-    if (builder == EVPLP_BVH_LBVH_GPU) {
+    const bool on_device = builder == EVPLP_BVH_LBVH_GPU || builder == EVPLP_BVH_PLOC_GPU;
+    if (on_device) {
         BvhDeviceBuild gb;
-        const int e = build_bvh_gpu(verts.data(), (int32_t)attrs.size(), bvh_pad_scale(), c->stream, &gb);
-        if (e != 0) { c->set_error("evplp_build_accel: device LBVH build: %s", hipGetErrorString((hipError_t)e)); return EVPLP_ERR_HIP; }
+        const bool ploc = builder == EVPLP_BVH_PLOC_GPU;
+        const int e = ploc ? build_bvh_gpu(verts.data(), (int32_t)attrs.size(), bvh_pad_scale(), c->stream, &gb, c->env_ploc_radius > 0 ? c->env_ploc_radius : kPlocRadius,
+                                           c->env_ploc_iterations >= 0 ? c->env_ploc_iterations : kPlocSearchIterations)
+                           : build_bvh_gpu(verts.data(), (int32_t)attrs.size(), bvh_pad_scale(), c->stream, &gb);
+        if (e != 0) { c->set_error("evplp_build_accel: device %s build: %s", ploc ? "PLOC" : "LBVH", hipGetErrorString((hipError_t)e)); return EVPLP_ERR_HIP; }
+        if (gb.bound_passed) { c->set_error("evplp_build_accel: device PLOC build: %d iterations and still more than one cluster (the bound is the search iterations + log2 of the triangles)", gb.iterations); return EVPLP_ERR_HIP; }
         if (gb.depth > kMaxDepth - 2) {
-            // long radix-tree chains (clustered or duplicate Morton codes) can exceed the walks' 64-entry stacks: build the
-            // binned-SAH tree on the host instead of failing the scene
+            // long radix-tree chains (clustered or duplicate Morton codes) or a tall PLOC tree can exceed the walks' 64-entry stacks: build
+            // the binned-SAH tree on the host instead of failing the scene
             hipFree(gb.nodes); hipFree(gb.leaves); hipFree(gb.tri_flat); hipFree(gb.tri_index);
             builder = EVPLP_BVH_SAH;
         } else {
@@ -433,7 +451,7 @@ static int build_accel(evplp_context *c, int policy_builder) {
             bb.nnodes = gb.nnodes; bb.nleaves = gb.nleaves; bb.depth = gb.depth; bb.build_ms = gb.build_ms; bb.ntris = gb.ntris;
         }
     }
-    if (builder != EVPLP_BVH_LBVH_GPU) {
+    if (builder != EVPLP_BVH_LBVH_GPU && builder != EVPLP_BVH_PLOC_GPU) {
         build_bvh(verts.data(), (int32_t)attrs.size(), builder, &bb);
         if (bb.depth > kMaxDepth - 2 && builder == EVPLP_BVH_LBVH) { free_bvh(&bb); bb = BvhBuild(); builder = EVPLP_BVH_SAH; build_bvh(verts.data(), (int32_t)attrs.size(), builder, &bb); }
     }
@@ -459,7 +477,7 @@ static int build_accel(evplp_context *c, int policy_builder) {
         tdesc.push_back(d);
     }
     int rc;
-    if (builder != EVPLP_BVH_LBVH_GPU) {
+    if (builder != EVPLP_BVH_LBVH_GPU && builder != EVPLP_BVH_PLOC_GPU) {
         if ((rc = upload_array(c, bb.nodes, (size_t)bb.nnodes, &c->sc.nodes))) { free_bvh(&bb); return rc; }
         if ((rc = upload_array(c, bb.leaves, (size_t)std::max(bb.nleaves, 1), &c->sc.leaves))) { free_bvh(&bb); return rc; }
         if ((rc = upload_array(c, bb.tri_index, (size_t)std::max(bb.nleaves, 1) * 4, &c->sc.tri_index))) { free_bvh(&bb); return rc; }

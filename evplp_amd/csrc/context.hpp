@@ -9,7 +9,7 @@
 
 namespace evplp {
 // bvh_gpu.hip: LBVH built on the device (arrays are device allocations owned by the caller)
-int build_bvh_gpu(const float *verts_host, int32_t ntri, float pad_scale, hipStream_t stream, BvhDeviceBuild *out);
+int build_bvh_gpu(const float *verts_host, int32_t ntri, float pad_scale, hipStream_t stream, BvhDeviceBuild *out, int32_t ploc_radius = 0, int32_t ploc_search_iterations = 0);
 int build_nodes4(const BvhNode *d_nodes, int32_t nnodes, hipStream_t stream, BvhNode4 **out);
 void build_nodes4_into(const BvhNode *d_nodes, int32_t nnodes, hipStream_t stream, BvhNode4 *out);      // in place: enqueued, no allocation, no wait
 // bvh_gpu.hip: the launches of evplp_refit_accel (enqueued; d_src: 9 floats per triangle of the run; d_order: the nodes of one height)
@@ -168,6 +168,7 @@ struct evplp_context {
 
     // Test / developer overrides, read ONCE by evplp_create (never in a pass): EVPLP_BVH_BUILDER (every suite under every builder),
     // EVPLP_BIN_STRIDE (forces the photon-bin overflow path), EVPLP_GATHER_K, EVPLP_TILE_BLOCK_LOG2.  -1 / 0 = not set.
+    int32_t env_ploc_radius = 0, env_ploc_iterations = -1;                                         // EVPLP_PLOC_RADIUS, EVPLP_PLOC_ITERATIONS (0 / -1: not set)
     int32_t env_bvh_builder = -1, env_gather_k = 0, env_tile_block_log2 = -1, env_cuts = -1;      // env_cuts: EVPLP_CUTS=0 walks from the root
     int32_t env_item_deal = -1;                // EVPLP_ITEM_DEAL: 0 tiles dealt to XCDs, 1 a tile's items over all XCDs (default: by launch size)
     int32_t env_split_min = 0;                 // EVPLP_SPLIT_MIN: fullest bin from which the splat's tile kernel runs four waves per tile

@@ -207,6 +207,26 @@ inline void accel_cost_finish(const double *parts, int32_t nchunks, double root_
     out[0] = root_area > 0.0 ? (kCostNodeVisit * (root_area + t[0]) + kCostPairTest * t[1]) / root_area : 0.0;
 }
 
+// ---- PLOC (Meister & Bittner 2018), the device builder EVPLP_BVH_PLOC_GPU of bvh_gpu.hip and its host twin evplp_ploc_tree (host/ploc.cpp).
+// kPlocRadius: positions searched on either side for the nearest neighbour (EVPLP_PLOC_RADIUS overrides it, 1 .. kPlocMaxRadius);
+// kPlocSearchIterations: search iterations before every further iteration pairs position 2k with 2k + 1 (EVPLP_PLOC_ITERATIONS, 0 .. 128).
+constexpr int kPlocRadius = 16, kPlocMaxRadius = 32, kPlocSearchIterations = 128;
+// the distance of two clusters: half the area of the union of their boxes (a, b: lo[3] then hi[3]).  fp32, every operation rounds on its
+// own, in this order, on the host and on the device: the nearest neighbour hangs on a compare of two of these.
+__host__ __device__ inline float ploc_distance(const float *a, const float *b) {
+#pragma clang fp contract(off)
+    const float ex = fmaxf(fmaxf(a[3], b[3]) - fminf(a[0], b[0]), 0.0f);
+    const float ey = fmaxf(fmaxf(a[4], b[4]) - fminf(a[1], b[1]), 0.0f);
+    const float ez = fmaxf(fmaxf(a[5], b[5]) - fminf(a[2], b[2]), 0.0f);
+    return ex * ey + ey * ez + ez * ex;
+}
+// the bound on the iterations of a build of n clusters: the search iterations, then halvings
+inline int32_t ploc_iteration_bound(int32_t n, int32_t search_iterations) {
+    int32_t lg = 0;
+    while (((int64_t)1 << lg) < (int64_t)n) lg++;
+    return search_iterations + lg;
+}
+
 // Host-side acceleration structure build result
 struct BvhBuild {
     BvhNode *nodes = nullptr; int32_t nnodes = 0;
@@ -220,6 +240,8 @@ struct BvhDeviceBuild {
     BvhNode *nodes = nullptr; LeafBlock *leaves = nullptr; TriFlat *tri_flat = nullptr; int32_t *tri_index = nullptr;
     int32_t nnodes = 0, nleaves = 0, ntris = 0, depth = 0;
     float build_ms = 0.f;
+    int32_t iterations = 0;          // PLOC: iterations run; bound_passed: the build stopped because they passed ploc_iteration_bound
+    bool bound_passed = false;
 };
 // verts: 9 floats per original triangle.  Degenerate triangles (rt/triangleintersect.cu:62-81
 // meshBound invalidates them) are dropped.  Returns 0 on success.

@@ -64,7 +64,10 @@ typedef enum evplp_bvh_builder {
     EVPLP_BVH_LBVH = 0,   /* Morton-code LBVH (Karras topology) */
     EVPLP_BVH_SAH = 1,    /* binned-SAH top-down build into the same flattened node format (default of the host side) */
     EVPLP_BVH_SBVH = 2,   /* binned SAH with spatial splits (triangle references clipped at split planes; ~20 % more leaf slots) */
-    EVPLP_BVH_LBVH_GPU = 3 /* the LBVH built on the device (Morton sort, Karras hierarchy, bottom-up refit): for scenes that change */
+    EVPLP_BVH_LBVH_GPU = 3, /* the LBVH built on the device (Morton sort, Karras hierarchy, bottom-up refit): for scenes that change */
+    EVPLP_BVH_PLOC_GPU = 4  /* built on the device by locally-ordered clustering (PLOC, Meister & Bittner 2018) over the same Morton sort: every
+                             * cluster merges with its nearest neighbour within 16 positions where the choice is mutual; one small host
+                             * read-back per iteration, so a slower build than the device LBVH and a better tree (evplp_ploc_tree is its host twin) */
 } evplp_bvh_builder;
 
 /* Creation-time configuration: what RtComPhoton::render fixes before setup()
@@ -129,6 +132,8 @@ typedef struct evplp_config {
      *                                   + 4 B per tile and 4 B per item of the largest call (the item table);
      *                                   budget mode: + 8 B per tile after evplp_adaptive_tile_noise
      *   refit (after a call)            28 B per node + 36 B per triangle (+ 4 B per light triangle), and the same staging bytes in pinned host memory (evplp_refit_accel)
+ *   PLOC build (during the call)    88 B per triangle on top of the device LBVH's scratch, freed before evplp_build_accel returns: 2 n clusters in ping-pong (28 B
+ *                                   each), n nearest neighbours (4 B), n packed flags and their scan (16 B), children and counts of the inner nodes (12 B)
  *   tree cost (after a call)        24 B per 256 nodes + 8 B, and the same in pinned host memory; the refit's plan and staging (the row above) if no
  *                                   refit of this tree has made them yet: refit_prepare makes them (evplp_accel_quality, evplp_set_refit_policy)
      *   denoiser (after a call)         124 B per pixel of the context's planes (evplp_denoise); a group's rank: 92 B per pixel of its planes
@@ -321,7 +326,8 @@ int evplp_refit_levels(const void *nodes64, int32_t nnodes, int32_t *height, int
  *     Like a refit, a policy rebuild leaves accumulators, noise moments and adaptive records alone.  While a policy is set
  *     evplp_build_accel re-measures built_cost; setting one on a clean, built context without a built_cost measures it there and then.
  *     EVPLP_ERR_INVALID: a ratio that is negative or not finite, a builder outside -1 .. 3, vertices dirty.  No ratio is recommended
- *     here: DESIGN section 6b has what was measured. */
+ *     here: DESIGN section 6b has what was measured.  rebuild_builder = EVPLP_BVH_PLOC_GPU (4) is refused too, for now; a context whose
+ *     OWN builder is PLOC gets PLOC rebuilds from the policy through rebuild_builder = -1. */
 struct evplp_accel_quality {            /* (the call below has the same name: C and C++ both need the word `struct` in front of the type) */
     double cost, root_area, inner_area, leaf_pair_area, leaf_tri_area;
     double built_cost;
@@ -332,6 +338,15 @@ struct evplp_accel_quality {            /* (the call below has the same name: C 
 int evplp_accel_cost(const void *nodes64, int32_t nnodes, double out[5]);
 int evplp_accel_quality(evplp_context *ctx, struct evplp_accel_quality *out);
 int evplp_set_refit_policy(evplp_context *ctx, double max_cost_ratio, int32_t rebuild_builder);
+/* The tree EVPLP_BVH_PLOC_GPU builds, stated on the host (no GPU, deterministic): the device builder's steps run serially, with the same
+ * Morton key, the same fp32 distance and the same tie rule, so the two produce one tree.  verts9 = 9 floats per triangle; triangles
+ * without area (meshBound's rule) are left out.  radius = 1 .. 32 positions searched on either side, search_iterations = 0 .. 128 search
+ * iterations before every further iteration pairs position 2k with 2k + 1 (0: pure pairing).  order (ntri ints; the first n are written) =
+ * the valid triangles in Morton order, equal keys in triangle order: leaf ~p is order[p].  children (2 (ntri - 1) ints; 2 (n - 1) are
+ * written) = the left and right child of inner node i at [2 i] and [2 i + 1], an inner index or ~p; node 0 is the root, and a child's
+ * index is always above its parent's.  *iterations = the iterations run, at most search_iterations + ceil(log2 n).  Returns n, the valid
+ * triangles, or EVPLP_ERR_INVALID for a null pointer, ntri < 0, a radius or search_iterations out of range. */
+int evplp_ploc_tree(const float *verts9, int32_t ntri, int32_t radius, int32_t search_iterations, int32_t *order, int32_t *children, int32_t *iterations);
 
 /* ---- the per-iteration passes of RtComPhoton::run() (rtcomphoton.h:936-1068) ---- */
 /* [deferredShading] + [lightRender]: runDeferredProgram (:710-754) + runLightProgram (:839-855);
@@ -917,7 +932,7 @@ int evplp_synth_scene_ex(const char *out_dir, const char *name, int32_t target_t
 /* main() + LoadScene + RtComPhoton::render (main.cpp:87-121, rtcomphoton.h:107-223): parse the
  * scene JSON, load OBJ/MTL, run the `photonfam` technique, write the three images + stat file.
  * json_overrides: optional JSON object text merged over the technique block (may be NULL).
- * Build-only keys of a technique block: "bvhBuilder": "sah" | "sbvh" | "lbvh" | "gpu" (evplp_bvh_builder); "deterministic": bool (photon bins accumulated in record
+ * Build-only keys of a technique block: "bvhBuilder": "sah" | "sbvh" | "lbvh" | "gpu" | "ploc" (evplp_bvh_builder); "deterministic": bool (photon bins accumulated in record
  * order); "device": {"gpus": N, "virtual": bool, "stripRows": R, "rccl": bool, "deal": "cost" | "roundRobin", "exchangeEvery": k,
  * "stripCapacityPct": p, "splitLightPaths": bool, "cutScratchGB": g, "vslMaskGB": g} -- run on an evplp_group of N row-strip ranks (GPUs device .. device+N-1; "virtual": all ranks on `device`; "rccl": a
  * single rank goes through RCCL too; "deal": row blocks dealt by the cost a calibration frame clocks -- the default when that extra frame pays for
