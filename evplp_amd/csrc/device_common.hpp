@@ -1112,7 +1112,8 @@ EV_DEV void node4_slabs(const BvhNode4 &n, V3 inv, V3 noi, float tmin, float tma
     }
 }
 // Stack of the four-wide walk: the first LDS_ENTRIES entries in LDS ([entry][lane]), the rest -- reached only by rays that defer more
-// children than any ray of the test scenes ever did -- in a per-thread column of global memory (ovf[k * ovf_stride]).  The worst case
+// children than a ray of a balanced tree does; tests/test_gpu_deep_trees.py drives nearly every light path 60 entries and more into it on
+// the chain trees of scenes.morton_chain_full -- in a per-thread column of global memory (ovf[k * ovf_stride]).  The worst case
 // for a tree (3 pushes per four-wide level: 46 entries for the 31-level tree of the bench scene, 12 KB of LDS per wave, 3 waves per
 // SIMD) would otherwise set the occupancy of every launch.  LDS_ENTRIES = 0: everything in `stack` (sized for the worst case).
 // SPEC ("speculative while-while", Aila & Laine 2009): a lane that reaches a leaf while other lanes of the wave still descend keeps the

@@ -152,6 +152,71 @@ def box_room(seed=1, n_boxes=6, tess=2, glossy=True, textured=False, aspect=1.0)
     return s
 
 
+def _chain_stage(s, aspect):
+    """What the two Morton-chain scenes share.  A floor at z = -2 and a small anchor triangle at z = 2 fix the box of the triangles' box
+    centres, which the LBVH builders quantise, to [0, 1] x [0, 1] x [-2, 2]; the light (a quad at z = -1 facing +z, box centre inside that
+    box) and the camera sit below the sheets, which are added next in the planes 0 <= z <= 1.  A light path's first segment and every
+    primary ray therefore cross the whole chain along +z.  Returns the sheets' material (diffuse plus glossy)."""
+    s.aspect = aspect
+    sheet = s.add_material((0.55, 0.5, 0.45), (0.25, 0.25, 0.25), 12.0)
+    ground = s.add_material((0.6, 0.6, 0.6))
+    lm = s.add_material((0, 0, 0))
+    s.add_quad([-4.5, -4.5, -2.0], [9.0, 0, 0], [0, 9.0, 0], ground)                                 # box centre (0, 0, -2), faces +z
+    s.add_mesh([[0.9, 0.9, 2.0], [1.0, 1.1, 2.0], [1.1, 0.9, 2.0]], [[0, 1, 2]], ground)             # box centre (1, 1, 2), faces -z
+    s.light_mesh = s.add_quad([0.3, 0.3, -1.0], [0.4, 0, 0], [0, 0.4, 0], lm)
+    s.light_intensity = [17.0, 12.0, 4.0, 4.0]                 # (an emission lobe of exponent 4 around +z)
+    s.cam_origin = [1.1, 0.2, -1.5]; s.cam_lookat = [0.3, 0.5, 1.0]; s.cam_up = [0.05, 1.0, 0.0]
+    s.fovy = math.radians(50.0)
+    return sheet
+
+
+def _sheet(cx, cy, hx, hy, z):
+    """One triangle in the plane z whose box is [cx - hx, cx + hx] x [cy - hy, cy + hy], facing -z (towards the light and the camera: light
+    tracing ends a path on a back face)"""
+    return [[cx + hx, cy - hy, z], [cx - hx, cy - hy, z], [cx, cy + hy, z]]
+
+
+def morton_chain(levels=21, per=5, aspect=1.0):
+    """Scene A: `levels` groups of `per` wide triangles whose box centres halve their distance to the origin from group to group
+    (cx = 2^-L (1 + 0.05 j / per), z = cx / 2): clustered Morton codes, so the LBVH builders make a tree that is a chain of about one level
+    per group where SAH makes a balanced one.  The sheets overlap almost completely as seen along z."""
+    s = SceneData()
+    mat = _chain_stage(s, aspect)
+    tris = []
+    for L in range(levels):
+        for j in range(per):
+            cx = 2.0 ** -L * (1.0 + 0.05 * j / per)
+            tris += _sheet(cx, 0.0, 3.0, 3.0, 0.5 * cx)
+    s.sheet_mesh = s.add_mesh(tris, np.arange(len(tris)).reshape(-1, 3), mat)
+    s.triangle_soup()
+    return s
+
+
+def morton_chain_full(clusters=58, per=5, aspect=1.0):
+    """Scene B: cluster k's Morton code has the single bit 62 - k set (beside the top z bit, which every sheet shares because the sheets
+    lie in the upper half of the z range the floor opens): the radix tree over the sorted codes is one chain with a level per cluster, up
+    to the 62 levels the builders accept.  bit % 3 = 2, 1, 0 puts the box centre on the x, y, z axis at 2^(bit / 3 - 21) of the range
+    (times 1.0000001, rounded up to a multiple of 2^-22 so that centre -+ half-size is exact in fp32); the cluster's `per` triangles share
+    that box centre exactly, with half-sizes 3 + 0.01 j.  Many triangles are coplanar and overlap: a closest hit there is decided by the
+    lowest original index alone."""
+    s = SceneData()
+    mat = _chain_stage(s, aspect)
+    tris = []
+    for k in range(clusters):
+        bit = 62 - k
+        axis = 2 - bit % 3
+        c = [0.0, 0.0, 0.0]
+        if not (axis == 2 and bit // 3 == 20):            # (z's top bit is the shared one: that cluster keeps the plain code)
+            v = float(np.float32(2.0 ** (bit // 3 - 21) * 1.0000001))
+            c[axis] = math.ceil(v * 2.0 ** 22) / 2.0 ** 22 * (4.0 if axis == 2 else 1.0)
+        for j in range(per):
+            h = float(np.float32(3.0 + 0.01 * j))
+            tris += _sheet(c[0], c[1], h, h, c[2])
+    s.sheet_mesh = s.add_mesh(tris, np.arange(len(tris)).reshape(-1, 3), mat)
+    s.triangle_soup()
+    return s
+
+
 def load_obj_scene(json_path, decode=None):
     """Independent Python reading of a scene JSON + OBJ/MTL (same semantics as csrc/host/scene_io.cpp).
     decode(path) -> uint8 (h, w, 3) top-down pixels for map_Kd / map_Ks / map_Ns (RtTexture(filepath, 1.0),
