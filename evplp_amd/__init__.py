@@ -137,6 +137,9 @@ _SIGNATURES = {
     "evplp_build_accel": (C.c_int, [_P]),
     "evplp_update_mesh": (C.c_int, [_P, C.c_int32, _P, C.c_int32]),
     "evplp_refit_accel": (C.c_int, [_P]),
+    "evplp_transform_mesh": (C.c_int, [_P, C.c_int32, _P]),
+    "evplp_transform_points": (C.c_int, [_P, _P, _P, C.c_int32]),
+    "evplp_group_transform_mesh": (C.c_int, [_P, C.c_int32, _P]),
     "evplp_refit_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     "evplp_refit_levels": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32]),
     "evplp_debug_accel": (C.c_int, [_P, C.c_int32, _P, C.c_size_t]),
@@ -476,6 +479,12 @@ class Context:
         v = _f32(vertices).reshape(-1, 3)
         self._check(self._lib.evplp_update_mesh(self._h, int(mesh), _ptr(v), v.shape[0]))
 
+    def transform_mesh(self, mesh: int, m):
+        """evplp_transform_mesh: mesh `mesh` = its rest pose under the row-major 3 x 4 matrix m (12 numbers; transforms do not compose);
+        dirty like update_mesh, but the refit uploads the matrix alone"""
+        m = _f32(m).reshape(12)
+        self._check(self._lib.evplp_transform_mesh(self._h, int(mesh), _ptr(m)))
+
     def refit_accel(self):
         """evplp_refit_accel: the tree, the triangle operands and the scene's figures follow the updated vertices, on the device; the topology stays"""
         self._check(self._lib.evplp_refit_accel(self._h))
@@ -786,6 +795,18 @@ def refit_levels(nodes, level_capacity: int = 64):
     return height[:n], order[:int(begin[rc])], begin[:rc + 1]
 
 
+def transform_points(m, pts):
+    """evplp_transform_points: the points (n, 3) under the row-major 3 x 4 matrix m, by the function evplp_transform_mesh moves a mesh with
+    (fp32, every product and sum rounded on its own; host only)"""
+    m = _f32(m).reshape(12)
+    p = _f32(pts).reshape(-1, 3)
+    out = np.empty_like(p)
+    rc = lib().evplp_transform_points(_ptr(m), _ptr(p), _ptr(out), p.shape[0])
+    if rc < 0:
+        raise EvplpError(rc, "evplp_transform_points: a null pointer")
+    return out
+
+
 def accel_cost(nodes) -> dict:
     """evplp_accel_cost: the SAH cost of a flattened tree (ACCEL_NODE records or raw 64-byte nodes) on the host, in the order and shape of
     the device's sums -- evplp_accel_quality's reference.  EvplpError for an array that is not a tree."""
@@ -935,6 +956,10 @@ class Group:
     def update_mesh(self, mesh: int, vertices):
         v = _f32(vertices).reshape(-1, 3)
         self._check(self._lib.evplp_group_update_mesh(self._h, int(mesh), _ptr(v), v.shape[0]))
+
+    def transform_mesh(self, mesh: int, m):
+        m = _f32(m).reshape(12)
+        self._check(self._lib.evplp_group_transform_mesh(self._h, int(mesh), _ptr(m)))
 
     def refit_accel(self):
         self._check(self._lib.evplp_group_refit_accel(self._h))

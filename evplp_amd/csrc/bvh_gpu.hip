@@ -19,6 +19,8 @@
 //
 // Refit (evplp_refit_accel, for a tree of ANY builder whose vertices moved; the topology and the leaf assignment stay):
 //   a. refit_scatter : the moved triangles' vertices from a packed staging array into TriAttr::v.
+//   a'. refit_transform: the triangles of meshes moved by a matrix (evplp_transform_mesh) from their rest pose on the device into
+//                      TriAttr::v, ONE launch for all such meshes of a refit (a thread finds its mesh in a small table); nothing is uploaded.
 //   b. refit_leaves  : every live leaf slot's operands again, in both layouts (the arithmetic emit_leaves_kernel uses).
 //   c. refit_level   : the boxes, one launch per height of the tree, the parents of leaves first and the root last.  The end of a
 //                      launch is the only hand-over between heights: a thread owns one node, reads its children's unpadded boxes
@@ -382,6 +384,28 @@ __global__ __launch_bounds__(256) void refit_scatter_kernel(const float *src, in
     if (i >= 9 * count) return;
     attrs[(size_t)first + (size_t)(i / 9)].v[i % 9] = src[i];
 }
+// a'. the rest pose of a mesh that is transformed for the first time, from what the device holds: the reverse of refit_scatter_kernel
+// (rest: 9 floats per original triangle of the scene)
+__global__ __launch_bounds__(256) void refit_rest_kernel(const TriAttr *attrs, int32_t first, int32_t count, float *rest) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= 9 * count) return;
+    rest[9 * (size_t)first + (size_t)i] = attrs[(size_t)first + (size_t)(i / 9)].v[i % 9];
+}
+// One thread per vertex of the moved triangles of ALL meshes of the table (total of them): the last descriptor whose run begins at or
+// before the thread's triangle is its mesh.  Reads the rest pose, writes TriAttr::v; the rest pose is never written here.
+__global__ __launch_bounds__(256) void refit_transform_kernel(const TransformDesc *table, int32_t nmesh, int32_t total, const float *rest, TriAttr *attrs, int32_t ntri) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int j = i / 3, p = i - 3 * j;
+    if (j >= total) return;
+    int lo = 0, hi = nmesh - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (table[mid].begin <= j) lo = mid; else hi = mid - 1;
+    }
+    const int32_t tri = table[lo].first + (j - table[lo].begin);
+    if (tri < 0 || tri >= ntri) return;
+    transform_point(table[lo].m, rest + 9 * (size_t)tri + 3 * p, attrs[tri].v + 3 * p);
+}
 // b. one thread per leaf slot.  A triangle that has become degenerate (tri_has_area: meshBound's rule) gets zero operands, which is what a
 // fresh build does by dropping it; an empty slot (tri_index < 0) is zero already and stays.
 __global__ __launch_bounds__(256) void refit_leaves_kernel(const int32_t *tri_index, int32_t nslots, const TriAttr *attrs, int32_t ntri, LeafBlock *leaves, TriFlat *tri_flat) {
@@ -505,6 +529,12 @@ int build_nodes4(const BvhNode *d_nodes, int32_t nnodes, hipStream_t stream, Bvh
 // The refit's launches (context.cpp evplp_refit_accel owns the memory and the order); all enqueued, none waits.
 void refit_scatter(const float *d_src, int32_t first, int32_t count, TriAttr *attrs, hipStream_t stream) {
     if (count > 0) hipLaunchKernelGGL(refit_scatter_kernel, dim3((unsigned)((9 * (size_t)count + 255) / 256)), dim3(256), 0, stream, d_src, first, count, attrs);
+}
+void refit_rest(const TriAttr *attrs, int32_t first, int32_t count, float *d_rest, hipStream_t stream) {
+    if (count > 0) hipLaunchKernelGGL(refit_rest_kernel, dim3((unsigned)((9 * (size_t)count + 255) / 256)), dim3(256), 0, stream, attrs, first, count, d_rest);
+}
+void refit_transform(const TransformDesc *d_table, int32_t nmesh, int32_t total, const float *d_rest, TriAttr *attrs, int32_t ntri, hipStream_t stream) {
+    if (nmesh > 0 && total > 0) hipLaunchKernelGGL(refit_transform_kernel, dim3((unsigned)((3 * (size_t)total + 255) / 256)), dim3(256), 0, stream, d_table, nmesh, total, d_rest, attrs, ntri);
 }
 void refit_leaves(const RefitScene &r, hipStream_t stream) {
     if (r.nslots > 0) hipLaunchKernelGGL(refit_leaves_kernel, dim3((unsigned)((r.nslots + 255) / 256)), dim3(256), 0, stream, r.tri_index, r.nslots, r.attrs, r.ntri, r.leaves, r.tri_flat);

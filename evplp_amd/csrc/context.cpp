@@ -210,6 +210,10 @@ static void free_scene_device(evplp_context *c) {
     // ... and so does the output of the cost kernel (made by the first evplp_accel_quality)
     hipFree(c->d_cost); if (c->h_cost) hipHostFree(c->h_cost);
     c->d_cost = c->h_cost = nullptr; c->refit_reached = c->refit_leaf_refs = 0;
+    // ... and the rest pose and the descriptor tables of evplp_transform_mesh (made by the first transform; the host keeps every rest pose)
+    hipFree(c->d_rest); hipFree(c->d_xform); if (c->h_xform) hipHostFree(c->h_xform);
+    c->d_rest = nullptr; c->d_xform = c->h_xform = nullptr;
+    for (HostMesh &m : c->meshes) m.rest_state = 0;
 }
 
 extern "C" void evplp_destroy(evplp_context *c) {
@@ -359,52 +363,68 @@ static void flatten_verts(const evplp_context *c, std::vector<float> &verts, std
     for (const HostMesh &m : c->meshes)
         for (size_t i = 0; i < m.idx.size(); i++, o += 3) std::memcpy(o, &m.verts[3 * (size_t)m.idx[i]], 12);
 }
-// What a scene carries besides its tree, from the flattened vertices: the area-light CDF (returned), light_area and the light's padded bounds,
-// total_area, bounding_radius.  evplp_build_accel and evplp_refit_accel both come here, so a refit's figures are a fresh build's.
-static void scene_scalars(evplp_context *c, const float *verts, int32_t light_first, int32_t light_count, std::vector<float> &cdf) {
-    // area-light CDF, rt/rtcommon.h:501-531 (running float sum, then normalised); Triangle::ComputeArea
-    auto tri_area = [](const float *v) {
-        float a[3] = { v[3] - v[0], v[4] - v[1], v[5] - v[2] }, b[3] = { v[6] - v[0], v[7] - v[1], v[8] - v[2] };
-        float cx = a[1] * b[2] - a[2] * b[1], cy = a[2] * b[0] - a[0] * b[2], cz = a[0] * b[1] - a[1] * b[0];
-        return std::sqrt(cx * cx + cy * cy + cz * cz) / 2.0f;
-    };
-    cdf.resize((size_t)light_count);
+// What a scene carries besides its tree: the area-light CDF, light_area and the light's padded bounds, total_area, bounding_radius, and the
+// builders' box pad.  All of them are folds of per-mesh figures: mesh_figures is the one body for a mesh (evplp_build_accel runs it over every
+// mesh, evplp_refit_accel over the dirty ones), light_figures the one for the light mesh, and scene_fold adds the meshes up in mesh order.
+// evplp_build_accel and evplp_refit_accel both come here, so a refit's figures are a fresh build's.
+static float tri_area(const float *v) {              // Triangle::ComputeArea
+    float a[3] = { v[3] - v[0], v[4] - v[1], v[5] - v[2] }, b[3] = { v[6] - v[0], v[7] - v[1], v[8] - v[2] };
+    float cx = a[1] * b[2] - a[2] * b[1], cy = a[2] * b[0] - a[0] * b[2], cz = a[0] * b[1] - a[1] * b[0];
+    return std::sqrt(cx * cx + cy * cy + cz * cz) / 2.0f;
+}
+// mesh m's triangles, 9 floats each, from `from` (its positions or its rest pose)
+static void flatten_mesh(const HostMesh &m, const std::vector<float> &from, float *o) {
+    for (size_t i = 0; i < m.idx.size(); i++, o += 3) std::memcpy(o, &from[3 * (size_t)m.idx[i]], 12);
+}
+// scene metrics (rtcommon.h:759-768, 805-814): the mesh's running float sum of areas and the box of all its vertices; the box of its triangles
+// that the builders keep (tri_has_area).  flat: the mesh's triangles (flatten_mesh); has_area: null, or one byte per triangle of the mesh
+static void mesh_figures(HostMesh &m, const float *flat, char *has_area) {
+    float ms = 0.f;
+    for (int k = 0; k < 3; k++) { m.lo[k] = 3.4028235e38f; m.hi[k] = -3.4028235e38f; m.alo[k] = 3.0e38f; m.ahi[k] = -3.0e38f; }
+    m.any_area = false;
+    for (size_t t = 0; t < m.idx.size() / 3; t++) {
+        const float *v = flat + 9 * t;
+        ms += tri_area(v);
+        const bool has = tri_has_area(v);
+        if (has_area) has_area[t] = has;
+        if (!has) continue;
+        m.any_area = true;
+        for (int k = 0; k < 9; k++) { m.alo[k % 3] = std::min(m.alo[k % 3], v[k]); m.ahi[k % 3] = std::max(m.ahi[k % 3], v[k]); }
+    }
+    m.area = ms;
+    for (size_t v = 0; v < m.verts.size() / 3; v++) for (int k = 0; k < 3; k++) { m.lo[k] = std::min(m.lo[k], m.verts[3 * v + k]); m.hi[k] = std::max(m.hi[k], m.verts[3 * v + k]); }
+}
+// area-light CDF, rt/rtcommon.h:501-531 (running float sum, then normalised), light_area, and the unpadded bounds of the light's triangles
+// (flat: the light mesh's triangles)
+static void light_figures(evplp_context *c, const float *flat, std::vector<float> &cdf) {
+    const size_t n = c->meshes[(size_t)c->light_mesh].idx.size() / 3;
+    cdf.resize(n);
     float sum = 0.f;
-    for (int32_t i = 0; i < light_count; i++) { sum += tri_area(verts + 9 * ((size_t)light_first + i)); cdf[i] = sum; }
-    for (int32_t i = 0; i < light_count; i++) cdf[i] /= sum;
-    // scene metrics (rtcommon.h:759-768, 805-814): per-mesh float sums, bbox over all vertices
+    for (int k = 0; k < 3; k++) { c->light_box_lo[k] = 3.0e38f; c->light_box_hi[k] = -3.0e38f; }
+    for (size_t i = 0; i < n; i++) {
+        const float *v = flat + 9 * i;
+        sum += tri_area(v); cdf[i] = sum;
+        for (int k = 0; k < 9; k++) { c->light_box_lo[k % 3] = std::min(c->light_box_lo[k % 3], v[k]); c->light_box_hi[k % 3] = std::max(c->light_box_hi[k % 3], v[k]); }
+    }
+    for (size_t i = 0; i < n; i++) cdf[i] /= sum;
+    c->light_area = sum; c->sc.light_area = sum;
+}
+// the meshes' figures in mesh order; returns the builders' box pad for the bounds of the triangles they keep
+static float scene_fold(evplp_context *c) {
     float total = 0.f; float lo[3] = { 3.4028235e38f, 3.4028235e38f, 3.4028235e38f }, hi[3] = { -3.4028235e38f, -3.4028235e38f, -3.4028235e38f };
-    size_t tcur = 0;
+    float alo[3] = { 3.0e38f, 3.0e38f, 3.0e38f }, ahi[3] = { -3.0e38f, -3.0e38f, -3.0e38f };
+    bool any = false;
     for (const HostMesh &m : c->meshes) {
-        float ms = 0.f;
-        for (size_t t = 0; t < m.idx.size() / 3; t++) ms += tri_area(verts + 9 * tcur++);
-        total += ms;
-        for (size_t v = 0; v < m.verts.size() / 3; v++) for (int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], m.verts[3 * v + k]); hi[k] = std::max(hi[k], m.verts[3 * v + k]); }
+        total += m.area; any = any || m.any_area;
+        for (int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], m.lo[k]); hi[k] = std::max(hi[k], m.hi[k]); alo[k] = std::min(alo[k], m.alo[k]); ahi[k] = std::max(ahi[k], m.ahi[k]); }
     }
     float dg[3] = { std::max(hi[0] - lo[0], 0.f), std::max(hi[1] - lo[1], 0.f), std::max(hi[2] - lo[2], 0.f) };
     c->bounding_radius = std::sqrt(dg[0] * dg[0] + dg[1] * dg[1] + dg[2] * dg[2]) / 2.0f;
-    c->total_area = total; c->light_area = sum; c->sc.light_area = sum;
+    c->total_area = total;
     // bounds of the light mesh, padded by far more than the rounding of a slab test
-    float llo[3] = { 3.0e38f, 3.0e38f, 3.0e38f }, lhi[3] = { -3.0e38f, -3.0e38f, -3.0e38f };
-    for (int32_t i = 0; i < light_count; i++) for (int k = 0; k < 9; k++) {
-        const float v = verts[9 * ((size_t)light_first + i) + k];
-        llo[k % 3] = std::min(llo[k % 3], v); lhi[k % 3] = std::max(lhi[k % 3], v);
-    }
     const float pad = 1e-4f * (2.0f * c->bounding_radius) + 1e-30f;
-    for (int k = 0; k < 3; k++) { c->sc.light_lo[k] = llo[k] - pad; c->sc.light_hi[k] = lhi[k] + pad; }
-}
-// has_area[t] = triangle t is one the builders keep (tri_has_area); returns the builders' box pad for the bounds of those
-static float scene_pad(const float *verts, int32_t ntri, std::vector<char> &has_area) {
-    float lo[3] = { 3.0e38f, 3.0e38f, 3.0e38f }, hi[3] = { -3.0e38f, -3.0e38f, -3.0e38f };
-    has_area.assign((size_t)ntri, 0);
-    bool any = false;
-    for (int32_t t = 0; t < ntri; t++) {
-        const float *v = verts + 9 * (size_t)t;
-        if (!tri_has_area(v)) continue;
-        has_area[(size_t)t] = 1; any = true;
-        for (int k = 0; k < 9; k++) { lo[k % 3] = std::min(lo[k % 3], v[k]); hi[k % 3] = std::max(hi[k % 3], v[k]); }
-    }
-    return bvh_pad(lo, hi, any);
+    for (int k = 0; k < 3; k++) { c->sc.light_lo[k] = c->light_box_lo[k] - pad; c->sc.light_hi[k] = c->light_box_hi[k] + pad; }
+    return bvh_pad(alo, ahi, any);
 }
 
 static int measure_cost(evplp_context *c, double out[5]);
@@ -459,10 +479,11 @@ static int build_accel(evplp_context *c, int policy_builder) {
     c->accel_nodes = bb.nnodes; c->accel_leaves = bb.nleaves; c->accel_depth = bb.depth; c->accel_build_ms = bb.build_ms;
     if (bb.depth > kMaxDepth - 2) { free_bvh(&bb); free_scene_device(c); c->set_error("BVH depth %d exceeds the traversal stack (%d)", bb.depth, kMaxDepth); return EVPLP_ERR_INVALID; }
     std::vector<float> cdf;
-    scene_scalars(c, verts.data(), light_first, light_count, cdf);
     {   // which triangles the builders dropped (a refit cannot bring one back), and the builders' pad of this scene
-        std::vector<char> has_area;
-        c->accel_pad = scene_pad(verts.data(), first.back(), has_area);
+        std::vector<char> has_area((size_t)first.back(), 0);
+        for (size_t mi = 0; mi < c->meshes.size(); mi++) mesh_figures(c->meshes[mi], &verts[9 * (size_t)first[mi]], has_area.data() + first[mi]);
+        light_figures(c, &verts[9 * (size_t)light_first], cdf);
+        c->accel_pad = scene_fold(c);
         c->tri_dropped.resize(has_area.size());
         for (size_t t = 0; t < has_area.size(); t++) c->tri_dropped[t] = !has_area[t];
     }
@@ -566,6 +587,21 @@ bool update_mesh_check(evplp_context *c, int32_t mesh, const float *vertices, in
     for (size_t i = 0; i < 3 * have; i++) if (!std::isfinite(vertices[i])) { c->set_error("evplp_update_mesh: vertex %zu of mesh %d is not finite", i / 3, mesh); return false; }
     return true;
 }
+// evplp_transform_mesh's refusals, likewise.  The transformed coordinates are checked on the host copy's rest pose, by the function that
+// will move it: a matrix that overflows a coordinate is refused here, not rendered.
+bool transform_mesh_check(evplp_context *c, int32_t mesh, const float *matrix) {
+    if (!c->accel_built) { c->set_error("evplp_transform_mesh: scene not built (evplp_build_accel)"); return false; }
+    if (mesh < 0 || mesh >= (int32_t)c->meshes.size()) { c->set_error("evplp_transform_mesh: mesh %d out of range (%zu meshes)", mesh, c->meshes.size()); return false; }
+    if (!matrix) { c->set_error("evplp_transform_mesh: null matrix"); return false; }
+    for (int i = 0; i < 12; i++) if (!std::isfinite(matrix[i])) { c->set_error("evplp_transform_mesh: matrix entry %d is not finite", i); return false; }
+    const HostMesh &m = c->meshes[(size_t)mesh];
+    const std::vector<float> &rest = m.rest.empty() ? m.verts : m.rest;
+    for (size_t v = 0; v < rest.size() / 3; v++) {
+        float o[3]; transform_point(matrix, &rest[3 * v], o);
+        if (!std::isfinite(o[0]) || !std::isfinite(o[1]) || !std::isfinite(o[2])) { c->set_error("evplp_transform_mesh: vertex %zu of mesh %d is not finite under the matrix", v, mesh); return false; }
+    }
+    return true;
+}
 // evplp_refit_accel's refusal: a triangle the build dropped (no area) that has one now has no leaf slot to go to
 bool refit_check(evplp_context *c) {
     if (!c->accel_built) { c->set_error("evplp_refit_accel: scene not built (evplp_build_accel)"); return false; }
@@ -590,8 +626,40 @@ bool refit_check(evplp_context *c) {
 extern "C" int evplp_update_mesh(evplp_context *c, int32_t mesh, const float *vertices, int32_t nverts) {
     CTX_CHECK(c);
     if (!evplp::update_mesh_check(c, mesh, vertices, nverts)) return EVPLP_ERR_INVALID;
-    std::memcpy(c->meshes[(size_t)mesh].verts.data(), vertices, sizeof(float) * 3 * (size_t)nverts);
+    HostMesh &m = c->meshes[(size_t)mesh];
+    std::memcpy(m.verts.data(), vertices, sizeof(float) * 3 * (size_t)nverts);
+    std::vector<float>().swap(m.rest); m.rest_state = 0;        // (a new rest pose: the matrix is forgotten, the device's copy is stale)
     c->mesh_dirty[(size_t)mesh] = 1; c->scene_dirty = true;
+    return EVPLP_OK;
+}
+
+extern "C" int evplp_transform_points(const float *m, const float *in, float *out, int32_t n) {
+    if (!m || n < 0 || (n > 0 && (!in || !out))) return EVPLP_ERR_INVALID;
+    for (int32_t i = 0; i < n; i++) { float o[3]; evplp::transform_point(m, in + 3 * (size_t)i, o); std::memcpy(out + 3 * (size_t)i, o, 12); }
+    return EVPLP_OK;
+}
+
+extern "C" int evplp_transform_mesh(evplp_context *c, int32_t mesh, const float *matrix) {
+    CTX_CHECK(c);
+    if (!evplp::transform_mesh_check(c, mesh, matrix)) return EVPLP_ERR_INVALID;
+    HostMesh &m = c->meshes[(size_t)mesh];
+    if (!c->d_rest) {               // the first transform of this scene: the rest-pose array and the two descriptor tables
+        HIP_TRY(c, hipSetDevice(c->cfg.device));
+        hipError_t e = hipMalloc((void **)&c->d_rest, sizeof(float) * 9 * (size_t)std::max(c->scene_tris, 1));
+        if (e == hipSuccess) e = hipMalloc((void **)&c->d_xform, sizeof(TransformDesc) * c->meshes.size());
+        if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_xform, sizeof(TransformDesc) * c->meshes.size(), hipHostMallocDefault);
+        if (e != hipSuccess) {
+            hipFree(c->d_rest); hipFree(c->d_xform); c->d_rest = nullptr; c->d_xform = nullptr;
+            c->set_error("evplp_transform_mesh: the rest pose on the device: %s", hipGetErrorString(e)); return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP;
+        }
+    }
+    // the device's copy of this mesh's rest pose is made by the refit: from the attributes while they still hold it (a clean mesh that has
+    // no matrix), from the host's rest pose otherwise
+    if (m.rest_state == 0) m.rest_state = (!c->mesh_dirty[(size_t)mesh] && m.rest.empty()) ? 1 : 2;
+    if (m.rest.empty()) m.rest = m.verts;
+    for (size_t v = 0; v < m.rest.size() / 3; v++) evplp::transform_point(matrix, &m.rest[3 * v], &m.verts[3 * v]);
+    std::memcpy(m.matrix, matrix, sizeof(m.matrix));
+    c->mesh_dirty[(size_t)mesh] = 2; c->scene_dirty = true;
     return EVPLP_OK;
 }
 
@@ -636,33 +704,70 @@ extern "C" int evplp_refit_accel(evplp_context *c) {
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     // (a photon splat whose verdict is still out is not waited for: a splat reads records and the G-buffer, never the scene)
     int rc = refit_prepare(c); if (rc) return rc;
-    std::vector<float> verts; std::vector<int32_t> first;
-    flatten_verts(c, verts, first);
-    std::vector<char> has_area;
-    const float pad = scene_pad(verts.data(), first.back(), has_area);
-    // 5. the host's figures, by the code evplp_build_accel uses (in front of the launches, so that they follow each other without a gap)
-    std::vector<float> cdf;
-    scene_scalars(c, verts.data(), c->sc.light_first, c->sc.light_count, cdf);
+    std::vector<int32_t> first;
+    { int32_t n = 0; for (const HostMesh &m : c->meshes) { first.push_back(n); n += (int32_t)(m.idx.size() / 3); } first.push_back(n); }
+    // 5. the host's figures, by the code evplp_build_accel uses, for the meshes that moved alone (in front of the launches, so that they
+    // follow each other without a gap)
+    // (flat: the dirty meshes' triangles, flattened once -- for the figures, and for the staging copy of those that are dirty by upload)
+    std::vector<float> cdf, flat; std::vector<size_t> flat_at(c->meshes.size(), 0);
+    { size_t n = 0; for (size_t mi = 0; mi < c->meshes.size(); mi++) if (c->mesh_dirty[mi]) { flat_at[mi] = n; n += 9 * (size_t)(first[mi + 1] - first[mi]); } flat.resize(n); }
+    for (size_t mi = 0; mi < c->meshes.size(); mi++) if (c->mesh_dirty[mi]) {
+        flatten_mesh(c->meshes[mi], c->meshes[mi].verts, flat.data() + flat_at[mi]);
+        mesh_figures(c->meshes[mi], flat.data() + flat_at[mi], nullptr);
+    }
+    if (c->mesh_dirty[(size_t)c->light_mesh]) light_figures(c, flat.data() + flat_at[(size_t)c->light_mesh], cdf);
+    const float pad = scene_fold(c);
     // Everything below is enqueued on the context's stream, behind every pass it was given -- the light tracing of overlap_light_tracing
     // included: the call that put it on the second stream made this stream wait for it.
     const bool timed = c->profile_passes, stages = timed && c->profile_kernels;
-    if (c->refit_count > 0) HIP_TRY(c, hipEventSynchronize(c->ev_refit_staged));     // (the last refit's copies have left the pinned array: long ago)
-    // 1. the dirty meshes' triangles, packed, in one copy; one scatter per run of neighbouring dirty meshes
+    if (c->refit_count > 0) HIP_TRY(c, hipEventSynchronize(c->ev_refit_staged));     // (the last refit's copies have left the pinned arrays: long ago)
+    // 1. the triangles of the meshes dirty by upload, packed, in one copy; one scatter per run of neighbouring such meshes.  Behind them in the
+    // pinned array, the rest pose of every mesh that was given a matrix and whose rest pose the device does not hold in any form.
+    // (one memcpy per mesh into the pinned array, as ever: what the copy engine then reads was written the way it was before there were matrices)
     size_t staged = 0;
-    for (size_t mi = 0; mi < c->meshes.size(); mi++) if (c->mesh_dirty[mi]) {
+    for (size_t mi = 0; mi < c->meshes.size(); mi++) if (c->mesh_dirty[mi] == 1) {
         const size_t n = 9 * (size_t)(first[mi + 1] - first[mi]);
-        std::memcpy(c->h_refit_stage + staged, &verts[9 * (size_t)first[mi]], sizeof(float) * n);
+        std::memcpy(c->h_refit_stage + staged, flat.data() + flat_at[mi], sizeof(float) * n);
+        staged += n;
+    }
+    const size_t uploaded = staged;
+    for (size_t mi = 0; mi < c->meshes.size(); mi++) if (c->mesh_dirty[mi] == 2 && c->meshes[mi].rest_state == 2) {
+        const size_t n = 9 * (size_t)(first[mi + 1] - first[mi]);
+        std::vector<float> rest(n);
+        flatten_mesh(c->meshes[mi], c->meshes[mi].rest, rest.data());
+        std::memcpy(c->h_refit_stage + staged, rest.data(), sizeof(float) * n);
         staged += n;
     }
     if (timed) HIP_TRY(c, hipEventRecord(c->ev_refit[0], c->stream));
-    if (staged) HIP_TRY(c, hipMemcpyAsync(c->d_refit_stage, c->h_refit_stage, sizeof(float) * staged, hipMemcpyHostToDevice, c->stream));
+    if (uploaded) HIP_TRY(c, hipMemcpyAsync(c->d_refit_stage, c->h_refit_stage, sizeof(float) * uploaded, hipMemcpyHostToDevice, c->stream));
     staged = 0;
     for (size_t mi = 0; mi < c->meshes.size();) {
-        if (!c->mesh_dirty[mi]) { mi++; continue; }
-        size_t me = mi; while (me < c->meshes.size() && c->mesh_dirty[me]) me++;
+        if (c->mesh_dirty[mi] != 1) { mi++; continue; }
+        size_t me = mi; while (me < c->meshes.size() && c->mesh_dirty[me] == 1) me++;
         const int32_t count = first[me] - first[mi];
         refit_scatter(c->d_refit_stage + staged, first[mi], count, (TriAttr *)c->sc.attrs, c->stream);
         staged += 9 * (size_t)count; mi = me;
+    }
+    // 1'. the meshes dirty by transform: their rest pose where the device lacks it (once per mesh and rest pose), the table of their matrices
+    // through pinned memory, and ONE launch that writes the attributes of all of them from the rest pose.  Nothing of them is staged or copied.
+    int32_t nx = 0, moved = 0;
+    for (size_t mi = 0; mi < c->meshes.size(); mi++) if (c->mesh_dirty[mi] == 2) {
+        HostMesh &m = c->meshes[mi];
+        const int32_t count = first[mi + 1] - first[mi];
+        if (m.rest_state == 1) refit_rest(c->sc.attrs, first[mi], count, c->d_rest, c->stream);
+        else if (m.rest_state == 2) {
+            if (count > 0) HIP_TRY(c, hipMemcpyAsync(c->d_rest + 9 * (size_t)first[mi], c->h_refit_stage + staged, sizeof(float) * 9 * (size_t)count, hipMemcpyHostToDevice, c->stream));
+            staged += 9 * (size_t)count;
+        }
+        m.rest_state = 3;
+        if (count <= 0) continue;
+        TransformDesc &d = c->h_xform[nx++];
+        d.first = first[mi]; d.count = count; d.begin = moved; d.pad = 0; std::memcpy(d.m, m.matrix, sizeof(d.m));
+        moved += count;
+    }
+    if (nx) {
+        HIP_TRY(c, hipMemcpyAsync(c->d_xform, c->h_xform, sizeof(TransformDesc) * (size_t)nx, hipMemcpyHostToDevice, c->stream));
+        refit_transform(c->d_xform, nx, moved, c->d_rest, (TriAttr *)c->sc.attrs, c->scene_tris, c->stream);
     }
     if (stages) HIP_TRY(c, hipEventRecord(c->ev_refit[1], c->stream));
     // 2. leaf operands  3. boxes, one launch per height  4. four-wide nodes

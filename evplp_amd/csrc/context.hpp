@@ -14,11 +14,22 @@ int build_nodes4(const BvhNode *d_nodes, int32_t nnodes, hipStream_t stream, Bvh
 void build_nodes4_into(const BvhNode *d_nodes, int32_t nnodes, hipStream_t stream, BvhNode4 *out);      // in place: enqueued, no allocation, no wait
 // bvh_gpu.hip: the launches of evplp_refit_accel (enqueued; d_src: 9 floats per triangle of the run; d_order: the nodes of one height)
 void refit_scatter(const float *d_src, int32_t first, int32_t count, TriAttr *attrs, hipStream_t stream);
+// (meshes moved by a matrix: d_rest, 9 floats per original triangle of the scene, is filled for a run from the attributes; ONE transform
+// launch per refit writes the attributes of every mesh of d_table from d_rest -- total: the moved triangles of the whole table)
+void refit_rest(const TriAttr *attrs, int32_t first, int32_t count, float *d_rest, hipStream_t stream);
+void refit_transform(const TransformDesc *d_table, int32_t nmesh, int32_t total, const float *d_rest, TriAttr *attrs, int32_t ntri, hipStream_t stream);
 void refit_leaves(const RefitScene &r, hipStream_t stream);
 void refit_level(const RefitScene &r, const int32_t *d_order, int32_t count, float pad, hipStream_t stream);
 // bvh_gpu.hip: the launch of evplp_accel_quality (enqueued; d_out: 1 + 3 * ceil(count / 256) doubles -- the root's area, then a triple per workgroup)
 void accel_cost(const BvhNode *d_nodes, int32_t nnodes, const int32_t *d_order, int32_t count, double *d_out, hipStream_t stream);
-struct HostMesh { std::vector<float> verts, uvs; std::vector<int32_t> idx; int32_t material = 0; };
+// rest: the rest pose of a mesh that evplp_transform_mesh has moved (verts = transform_point(matrix, rest)); empty: verts is the rest pose.
+// rest_state, the mesh's part of the device's rest-pose array: 0 not there, 1 to be made from the device's attributes, 2 to be made from
+// `rest`, 3 there.  area, lo / hi (all vertices), alo / ahi / any_area (triangles with an area): the mesh's share of the scene's figures.
+struct HostMesh {
+    std::vector<float> verts, uvs; std::vector<int32_t> idx; int32_t material = 0;
+    std::vector<float> rest; float matrix[12] = {}; int rest_state = 0;
+    float area = 0.f, lo[3] = {}, hi[3] = {}, alo[3] = {}, ahi[3] = {}; bool any_area = false;
+};
 struct HostTexture { int32_t w = 0, h = 0; std::vector<float> rgba; };
 struct HostStats { uint64_t rays = 0; };
 // host/proxy_mesh.cpp: the proxy mesh of EVPLP_FOOTPRINT_PROXY as slabs (kernels.h ProxyDev)
@@ -35,6 +46,7 @@ struct evplp_context;
 namespace evplp {
 // what evplp_update_mesh / evplp_refit_accel refuse (context.cpp), for the group's caller thread as well: false and the reason in c's error
 bool update_mesh_check(evplp_context *c, int32_t mesh, const float *vertices, int32_t nverts);
+bool transform_mesh_check(evplp_context *c, int32_t mesh, const float *m);
 bool refit_check(evplp_context *c);
 // what evplp_accel_quality / evplp_set_refit_policy refuse without touching a device (name: the entry point, for the message)
 bool accel_quality_check(evplp_context *c, const char *name);
@@ -98,6 +110,7 @@ struct evplp_context {
     evplp::CamBasis cam{}; evplp_camera cam_in{};
     bool camera_set = false, accel_built = false;
     float bounding_radius = 0.f, total_area = 0.f, light_area = 0.f;
+    float light_box_lo[3] = {}, light_box_hi[3] = {};     // the light's triangles, unpadded (sc.light_lo / light_hi: padded by the scene's size)
     int32_t accel_nodes = 0, accel_leaves = 0, accel_depth = 0, accel_builder_used = -1; float accel_build_ms = 0.f;
 
     // evplp_update_mesh / evplp_refit_accel.  mesh_dirty[m]: mesh m's vertices changed since the device scene was made (scene_dirty: any of
@@ -105,7 +118,11 @@ struct evplp_context {
     // made by the first refit and freed with the scene: the level plan (evplp_refit_levels over host_nodes, the node array of the build),
     // its order on the device, 6 floats per node of scratch, a device and a pinned host staging array for the moved vertices and the light's
     // CDF ([9 * triangles + light triangles] floats; ev_refit_staged: the last refit's copies have left the pinned one).
+    // mesh_dirty: 1 by evplp_update_mesh, 2 by evplp_transform_mesh.  The first transform makes d_rest (the rest pose, 9 floats per triangle of
+    // the scene; a mesh's part is filled at its first transform) and the descriptor table of a refit's one transform launch, pinned and on
+    // the device ([meshes] TransformDesc each; ev_refit_staged guards the pinned one); both are freed with the scene.
     std::vector<char> mesh_dirty, tri_dropped; bool scene_dirty = false;
+    float *d_rest = nullptr; evplp::TransformDesc *d_xform = nullptr, *h_xform = nullptr;
     std::vector<evplp::BvhNode> host_nodes; std::vector<int32_t> refit_level_begin; int32_t refit_levels = 0;
     int32_t *d_refit_order = nullptr; float *d_refit_boxes = nullptr, *d_refit_stage = nullptr, *h_refit_stage = nullptr;
     hipEvent_t ev_refit_staged = nullptr, ev_refit[5] = {}; bool refit_timed = false, refit_stages_timed = false;

@@ -220,6 +220,22 @@ __host__ __device__ inline float ploc_distance(const float *a, const float *b) {
     const float ez = fmaxf(fmaxf(a[5], b[5]) - fminf(a[2], b[2]), 0.0f);
     return ex * ey + ey * ez + ez * ex;
 }
+// ---- evplp_transform_mesh: a point under a row-major 3 x 4 matrix, out[r] = ((m[4r] x + m[4r+1] y) + m[4r+2] z) + m[4r+3].  fp32, every
+// product and every sum rounds on its own, in this order, and nothing is fused: the host copy of a mesh and refit_transform_kernel
+// (bvh_gpu.hip) both call this and nothing else, and a test restates it in numpy.  No special case for the identity (-0.0 becomes +0.0).
+__host__ __device__ inline void transform_point(const float m[12], const float p[3], float out[3]) {
+#pragma clang fp contract(off)
+    const float x = p[0], y = p[1], z = p[2];
+    for (int r = 0; r < 3; r++) {
+        const float a = m[4 * r] * x, b = m[4 * r + 1] * y, c = m[4 * r + 2] * z;
+        out[r] = ((a + b) + c) + m[4 * r + 3];
+    }
+}
+// one moved mesh of a refit, as refit_transform_kernel finds it: its run of original triangles, where the run starts among the moved
+// triangles of the launch (ascending over the table), and its matrix
+struct TransformDesc { int32_t first, count, begin, pad; float m[12]; };
+static_assert(sizeof(TransformDesc) == 64, "one descriptor per 64 bytes");
+
 // the bound on the iterations of a build of n clusters: the search iterations, then halvings
 inline int32_t ploc_iteration_bound(int32_t n, int32_t search_iterations) {
     int32_t lg = 0;

@@ -66,7 +66,7 @@ struct Rccl {
 };
 
 enum Op { OP_QUIT = 0, OP_CLEAR, OP_SYNC, OP_PRIMARY, OP_TRACE, OP_GATHER, OP_SPLAT, OP_PATH_TRACE, OP_PRESENT, OP_LOAD_SCENE, OP_SET_PROXY, OP_ASSEMBLE, OP_REDUCE, OP_SET_REFERENCE, OP_FRAME_ERROR,
-          OP_NOISE_TRACK, OP_NOISE_FOLD, OP_NOISE_POOL, OP_NOISE_ROWS, OP_NOISE_VARIANCE, OP_ADAPT_ENABLE, OP_ADAPT_RETIRE, OP_DENOISE_PREP, OP_DENOISE_FILTER, OP_PATH_TRACE_BATCH, OP_ADAPT_SET_BUDGETS, OP_ADAPT_TILE_NOISE, OP_UPDATE_MESH, OP_REFIT, OP_ACCEL_QUALITY, OP_REFIT_POLICY };
+          OP_NOISE_TRACK, OP_NOISE_FOLD, OP_NOISE_POOL, OP_NOISE_ROWS, OP_NOISE_VARIANCE, OP_ADAPT_ENABLE, OP_ADAPT_RETIRE, OP_DENOISE_PREP, OP_DENOISE_FILTER, OP_PATH_TRACE_BATCH, OP_ADAPT_SET_BUDGETS, OP_ADAPT_TILE_NOISE, OP_UPDATE_MESH, OP_TRANSFORM_MESH, OP_REFIT, OP_ACCEL_QUALITY, OP_REFIT_POLICY };
 // One posted call, copied into the ring by assignment: plain data (pointers must stay valid until the caller has drained: load_scene, set_proxy,
 // resolve do) but for `batch`, a shared pointer -- so every post and every worker-side copy of a command pays one atomic reference count, null or not.
 struct Cmd {
@@ -408,6 +408,7 @@ static void worker_run(Worker *w, const Cmd &cmd) {
         case OP_LOAD_SCENE: rc = evplp_load_scene_json(c, (const char *)cmd.p0); break;
         case OP_SET_PROXY: rc = evplp_set_splat_proxy(c, (const float *)cmd.p0, cmd.i[0], (const int32_t *)cmd.p1, cmd.i[1]); break;
         case OP_UPDATE_MESH: rc = evplp_update_mesh(c, cmd.i[0], (const float *)cmd.p0, cmd.i[1]); break;
+        case OP_TRANSFORM_MESH: rc = evplp_transform_mesh(c, cmd.i[0], (const float *)cmd.p0); break;
         case OP_REFIT: rc = evplp_refit_accel(c); break;
         case OP_ACCEL_QUALITY: rc = evplp_accel_quality(c, (struct evplp_accel_quality *)cmd.out + w->rank); break;      // (out: one record per rank, the caller's)
         case OP_REFIT_POLICY: rc = evplp_set_refit_policy(c, cmd.d, cmd.i[0]); break;
@@ -802,6 +803,14 @@ extern "C" int evplp_group_update_mesh(evplp_group *g, int32_t mesh, const float
     if (!evplp::update_mesh_check(g->ctx[0], mesh, vertices, nverts)) { g->set_error("%s", g->ctx[0]->error); return EVPLP_ERR_INVALID; }
     g->sums_fresh = false;
     Cmd c; c.op = OP_UPDATE_MESH; c.p0 = vertices; c.i[0] = mesh; c.i[1] = nverts;
+    return post_and_wait(g, c);
+}
+extern "C" int evplp_group_transform_mesh(evplp_group *g, int32_t mesh, const float *m) {
+    GRP_CHECK(g);
+    drain(g);
+    if (!evplp::transform_mesh_check(g->ctx[0], mesh, m)) { g->set_error("%s", g->ctx[0]->error); return EVPLP_ERR_INVALID; }
+    g->sums_fresh = false;
+    Cmd c; c.op = OP_TRANSFORM_MESH; c.p0 = m; c.i[0] = mesh;
     return post_and_wait(g, c);
 }
 extern "C" int evplp_group_refit_accel(evplp_group *g) {

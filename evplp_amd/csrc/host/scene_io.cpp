@@ -313,7 +313,8 @@ HostScene load_scene(const Json &root, const std::string &json_path) {
     s.res_x = (int32_t)root.at("resX").as_int("resX"); s.res_y = (int32_t)root.at("resY").as_int("resY");
     const Json &list = root.at("scene");                                     // main.cpp:46-58
     if (!list.is_array()) throw JsonError("scene: expected an array of OBJ paths");
-    for (size_t i = 0; i < list.size(); i++) add_obj(s, join_path(dir, list.at(i).as_string("scene[]")));
+    for (size_t i = 0; i < list.size(); i++) { s.object_first.push_back((int32_t)s.meshes.size()); add_obj(s, join_path(dir, list.at(i).as_string("scene[]"))); }
+    s.object_first.push_back((int32_t)s.meshes.size());
     const Json &al = root.at("arealight");                                   // main.cpp:60-67
     const Json &I = al.at("intensity");
     if (!I.is_array() || I.size() != 4) throw JsonError("arealight.intensity: expected 4 numbers");

@@ -23,6 +23,7 @@ struct HostScene {
     std::vector<evplp_material> materials;
     std::vector<TextureData> textures;
     int32_t light_mesh = -1;
+    std::vector<int32_t> object_first;   // load_scene: the first mesh of every entry of the "scene" array, then their end (an OBJ yields one mesh per material group)
     float light_intensity[4] = { 0, 0, 0, 0 };   // JSON arealight.intensity, unscaled
     evplp_camera camera{};
     bool has_camera = false;

@@ -250,6 +250,8 @@ public:
     void upload(evplp_group *g) const {
         if (on) check(g, evplp_group_set_error_reference(g, ref.data(), mask.empty() ? nullptr : mask.data()), "convergence reference");
     }
+    // "animation": this frame's file (name: Animation::frame_path)
+    template <class Name> void name_files(Name name) { filename = name(filename); }
     // after iteration i of the loop, the host clock at hand (no wait yet)
     bool due(int i, double now_ms) const {
         return on && ((every_iterations > 0 && i % every_iterations == 0) || (every_ms > 0.0 && now_ms >= next_ms));
@@ -356,6 +358,7 @@ public:
         pixels = (int64_t)W * H;
         on = true;
     }
+    template <class Name> void name_files(Name name) { filename = name(filename); if (!variance_filename.empty()) variance_filename = name(variance_filename); }
     // tracking starts from the sums as they are (after the loop's clear); shards: 1, or the ranks of an iteration partition
     void start(evplp_group *g, int shards) {
         if (!on) return;
@@ -466,6 +469,7 @@ public:
         sigma(c, "sigmaPosition", p.sigma_position);
         on = true;
     }
+    template <class Name> void name_files(Name name) { filename = name(filename); }
     void write(evplp_group *g, int W, int H, long long batches, float scale, float ls, int32_t mask_emitter) {
         if (!on) return;
         if (batches < 2)
@@ -554,6 +558,7 @@ public:
         noise.adaptive = true;
         on = true;
     }
+    template <class Name> void name_files(Name name) { if (!iterations_filename.empty()) iterations_filename = name(iterations_filename); }
     // once "samplesPerCall" is known (pt parses it behind this block)
     void parse_budget_samples(int samples_per_call) {
         if (!budget || !pt) return;
@@ -615,6 +620,129 @@ private:
     bool budget = false; long long budget_min = 1; double budget_q = 1.0; int32_t budget_samples_per_call = 0;
     std::vector<double> tile_rel; std::vector<int32_t> tile_n, tile_budget;
 };
+
+// Build-only key "animation" (photonfam, lvcphotonfam, pt; not a reference key): the scene moves between F frames, by one row-major 3 x 4
+// matrix per track and frame (evplp_group_transform_mesh: the rest pose under the matrix, nothing composes), and every frame is rendered by
+// the technique's loop from its beginning.
+//   {"frames": F, "tracks": [{"object": k, "matrices": [[12 numbers], ... F of them]}, {"mesh": i, "matrices": [...]}],
+//    "refitPolicy": {"maxCostRatio": r, "rebuildBuilder": "gpu"}}
+// "object": k addresses every mesh the k-th entry of the scene file's "scene" array produced (an OBJ yields one mesh per material group),
+// "object": "arealight" the light, "mesh": i the i-th mesh in upload order.  For frame f = 0 .. F - 1 every track's f-th matrix is applied,
+// the tree is refitted (evplp_group_refit_accel; refitPolicy is evplp_group_set_refit_policy) and the loop runs as a fresh evplp_render_json
+// of the moved scene would: accumulators, noise moments, adaptive records, iteration counter, radius schedule, jitter stream and seeds start
+// again.  Every file the block writes gets _fNNNN in front of its extension; a frame's stat file gains "frame", "refitMs" (the refit's device
+// time, while pass profiling is on), "refitLastAction" and, under a policy, "refitCostRatio" (cost / built_cost).  A frame's length must not
+// depend on the clock: a timeLimitMs that can end the loop (< 1e8) is refused and numMaxIteration must be > 0.  Validated before the group exists.
+class Animation {
+public:
+    bool on = false;
+    int frames = 1;
+    void parse(const Json &tech, const HostScene &scene, float time_limit_ms, int num_max_iteration) {
+        if (!tech.has("animation")) return;
+        const Json &a = tech.at("animation");
+        if (!a.is_object()) throw JsonError("animation: expected an object");
+        if (!a.has("frames")) throw JsonError("animation.frames: missing required key");
+        const long long F = a.at("frames").as_int("animation.frames");
+        if (F < 1 || F > 9999) throw JsonError("animation.frames: must be 1 .. 9999");
+        if (time_limit_ms < 1e8f) throw JsonError("animation: not with a timeLimitMs that can end the loop (< 1e8): a frame's length must not depend on the clock");
+        if (num_max_iteration <= 0) throw JsonError("animation: numMaxIteration must be > 0 (it alone ends a frame)");
+        if (!a.has("tracks") || !a.at("tracks").is_array()) throw JsonError("animation.tracks: expected an array");
+        const Json &ts = a.at("tracks");
+        std::vector<char> taken(scene.meshes.size(), 0);
+        for (size_t t = 0; t < ts.size(); t++) {
+            const std::string where = "animation.tracks[" + std::to_string(t) + "]";
+            const Json &tr = ts.at(t);
+            if (!tr.is_object()) throw JsonError(where + ": expected an object");
+            if (tr.has("object") == tr.has("mesh")) throw JsonError(where + ": exactly one of \"object\" and \"mesh\"");
+            Track track;
+            if (tr.has("mesh")) {
+                const long long i = tr.at("mesh").as_int((where + ".mesh").c_str());
+                if (i < 0 || i >= (long long)scene.meshes.size()) throw JsonError(where + ".mesh: " + std::to_string(i) + " is out of range (" + std::to_string(scene.meshes.size()) + " meshes)");
+                track.meshes.push_back((int32_t)i);
+            } else if (tr.at("object").type == Json::String) {
+                if (tr.at("object").str != "arealight") throw JsonError(where + ".object: an index into \"scene\", or \"arealight\"");
+                track.meshes.push_back(scene.light_mesh);
+            } else {
+                const long long k = tr.at("object").as_int((where + ".object").c_str());
+                const long long n = (long long)scene.object_first.size() - 1;
+                if (k < 0 || k >= n) throw JsonError(where + ".object: " + std::to_string(k) + " is out of range (\"scene\" has " + std::to_string(std::max(n, 0LL)) + " entries)");
+                for (int32_t m = scene.object_first[(size_t)k]; m < scene.object_first[(size_t)k + 1]; m++) track.meshes.push_back(m);
+            }
+            for (int32_t m : track.meshes) {
+                if (taken[(size_t)m]) throw JsonError(where + ": mesh " + std::to_string(m) + " is in two of the animation.tracks");
+                taken[(size_t)m] = 1;
+            }
+            const std::string mw = where + ".matrices";
+            if (!tr.has("matrices") || !tr.at("matrices").is_array() || (long long)tr.at("matrices").size() != F)
+                throw JsonError(mw + ": expected animation.frames (" + std::to_string(F) + ") matrices of 12 numbers");
+            for (size_t f = 0; f < (size_t)F; f++) {
+                const Json &m = tr.at("matrices").at(f);
+                if (!m.is_array() || m.size() != 12) throw JsonError(mw + "[" + std::to_string(f) + "]: expected 12 numbers (a row-major 3 x 4 matrix)");
+                for (size_t k = 0; k < 12; k++) {
+                    const float v = m.at(k).as_float((mw + "[" + std::to_string(f) + "]").c_str());
+                    if (!std::isfinite(v)) throw JsonError(mw + "[" + std::to_string(f) + "]: entry " + std::to_string(k) + " is not a finite fp32 number");
+                    track.matrices.push_back(v);
+                }
+            }
+            tracks.push_back(std::move(track));
+        }
+        if (a.has("refitPolicy")) {
+            const Json &p = a.at("refitPolicy");
+            if (!p.is_object() || !p.has("maxCostRatio")) throw JsonError("animation.refitPolicy.maxCostRatio: missing required key");
+            policy_ratio = p.at("maxCostRatio").as_number("animation.refitPolicy.maxCostRatio");
+            if (!std::isfinite(policy_ratio) || !(policy_ratio >= 0.0)) throw JsonError("animation.refitPolicy.maxCostRatio: must be finite and >= 0");
+            if (p.has("rebuildBuilder")) {
+                try { policy_builder = parse_bvh_builder(p.at("rebuildBuilder").as_string("animation.refitPolicy.rebuildBuilder")); }
+                catch (const JsonError &) { throw; }
+                catch (const std::exception &e) { throw JsonError(std::string("animation.refitPolicy.rebuildBuilder: ") + e.what()); }
+                // (evplp_set_refit_policy refuses PLOC as a rebuild builder for now, include/evplp.h; said here, before the group exists)
+                if (policy_builder == EVPLP_BVH_PLOC_GPU)
+                    throw JsonError("animation.refitPolicy.rebuildBuilder: \"ploc\" is not a rebuild builder yet (evplp_set_refit_policy); with \"bvhBuilder\": \"ploc\" leave it out -- the policy then rebuilds with the context's own builder");
+            }
+        }
+        frames = (int)F; on = true;
+    }
+    // path with _fNNNN in front of its extension
+    std::string frame_path(const std::string &path) const {
+        if (!on) return path;
+        char tag[16]; std::snprintf(tag, sizeof tag, "_f%04d", frame);
+        const size_t slash = path.find_last_of("/\\"), dot = path.find_last_of('.');
+        if (dot == std::string::npos || (slash != std::string::npos && dot < slash)) return path + tag;
+        return path.substr(0, dot) + tag + path.substr(dot);
+    }
+    void start(evplp_group *g) {
+        if (on && policy_ratio > 0.0) check(g, evplp_group_set_refit_policy(g, policy_ratio, policy_builder), "animation.refitPolicy");
+    }
+    // frame f: the tracks' matrices, the refit, and its figures for the frame's stat file
+    void begin_frame(evplp_group *g, int f) {
+        if (!on) return;
+        frame = f;
+        for (const Track &t : tracks)
+            for (int32_t m : t.meshes) check(g, evplp_group_transform_mesh(g, m, &t.matrices[12 * (size_t)f]), "animation: transform");
+        check(g, evplp_group_refit_accel(g), "animation: refit");
+        refit_ms = 0.f; last_action = 0; cost_ratio = 0.0;
+        evplp_context *h0 = evplp_group_context(g, 0);
+        if (evplp_refit_info(h0, nullptr, nullptr, &refit_ms) < 0) throw std::runtime_error(std::string("animation: refit info: ") + evplp_last_error(h0));
+        if (policy_ratio > 0.0) {
+            struct evplp_accel_quality q;
+            check(g, evplp_group_accel_quality(g, &q), "animation: tree cost");
+            last_action = q.last_action; cost_ratio = q.built_cost > 0.0 ? q.cost / q.built_cost : 0.0;
+        }
+    }
+    void add_stat(Json &st) const {
+        if (!on) return;
+        st.set("frame", Json::number(frame));
+        if (refit_ms > 0.f) st.set("refitMs", Json::number(refit_ms));
+        st.set("refitLastAction", Json::number(last_action));
+        if (policy_ratio > 0.0) st.set("refitCostRatio", Json::number(cost_ratio));
+    }
+
+private:
+    struct Track { std::vector<int32_t> meshes; std::vector<float> matrices; };       // matrices: [frames][12]
+    std::vector<Track> tracks;
+    double policy_ratio = 0.0; int policy_builder = -1;
+    int frame = 0; float refit_ms = 0.f; int last_action = 0; double cost_ratio = 0.0;
+};
 } // namespace
 
 // The reference's ground-truth technique: unidirectional path tracing with next-event estimation, one sample per
@@ -657,6 +785,7 @@ public:
             samples_per_call = (int)spc;
         }
         adaptive.parse_budget_samples(samples_per_call);
+        anim.parse(json, scene, time_limit_ms, num_max_iteration);                                                 // build-only key "animation"
         if (samples_per_call > 1) {
             if (frame_mode == 2) throw JsonError("samplesPerCall: frameMode \"cleareveryframe\" shows single samples (a batch always accumulates)");
             if (write_every_frame) throw JsonError("samplesPerCall: writeEveryFrame needs every iteration's frame (use samplesPerCall 1)");
@@ -672,7 +801,20 @@ public:
         Grp grp; create_group(grp, cfg, json, device);
         upload_scene_group(grp.g, scene);
         conv.upload(grp.g);
-        run(grp.g, scene, res_x, res_y);
+        anim.start(grp.g);
+        // "animation": every frame starts from the blocks as parsed, with its own file names
+        const Convergence conv0 = conv; const Noise noise0 = noise; const Denoise denoise0 = denoise; const Adaptive adaptive0 = adaptive;
+        const std::string output0 = output_filename, stat0 = stat_filename;
+        for (int f = 0; f < anim.frames; f++) {
+            if (anim.on) {
+                anim.begin_frame(grp.g, f);
+                auto name = [&](const std::string &p) { return anim.frame_path(p); };
+                conv = conv0; noise = noise0; denoise = denoise0; adaptive = adaptive0;
+                conv.name_files(name); noise.name_files(name); denoise.name_files(name); adaptive.name_files(name);
+                output_filename = name(output0); stat_filename = name(stat0);
+            }
+            run(grp.g, scene, res_x, res_y);
+        }
     }
 
 private:
@@ -754,6 +896,7 @@ private:
             Json st = Json::object();
             st.set("time", Json::number(time)); st.set("numIterations", Json::number(num_iterations));
             add_pass_times(h, st);
+            anim.add_stat(st);
             std::ofstream of(stat_filename);
             if (!of) throw std::runtime_error("cannot write " + stat_filename);
             of << st.dump() << "\n";
@@ -780,6 +923,7 @@ private:
     Noise noise;
     Denoise denoise;
     Adaptive adaptive{"adaptiveSampling", true};
+    Animation anim;
 };
 
 class ComPhotonTechnique {
@@ -838,6 +982,7 @@ public:
         conv.parse(json, out_dir, out_dir, res_x, res_y);                                                          // build-only key
         denoise.parse(json, out_dir, frame_mode);                                                                   // build-only key
         noise.parse(json, out_dir, out_dir, res_x, res_y, frame_mode);                                             // build-only key
+        anim.parse(json, scene, time_limit_ms, num_max_iteration);                                                 // build-only key
 
         // ---- setup(): context + scene upload (replaces GL/OptiX setup :646-708)
         evplp_config cfg; std::memset(&cfg, 0, sizeof(cfg));
@@ -865,23 +1010,36 @@ public:
         upload_scene_group(grp.g, scene);
         splat_footprint = setup_splat_footprint(grp.g, json, out_dir);                                           // :677
         conv.upload(grp.g);
-        float bsr = 0.f, total_area = 0.f, light_area = 0.f;
-        { evplp_context *h0 = evplp_group_context(grp.g, 0);
-          if (evplp_scene_metrics(h0, &bsr, &total_area, &light_area) < 0) throw std::runtime_error(std::string("scene metrics: ") + evplp_last_error(h0)); }
+        anim.start(grp.g);
+        // "animation": every frame starts from the blocks as parsed and from the moved scene's own figures, with its own file names
+        const Convergence conv0 = conv; const Noise noise0 = noise; const Denoise denoise0 = denoise; const Adaptive adaptive0 = adaptive;
+        const std::string combined0 = combined_filename, photon0 = weighted_photon_filename, vpl0 = weighted_vpl_filename, stat0 = stat_filename;
+        for (int f = 0; f < anim.frames; f++) {
+            if (anim.on) {
+                anim.begin_frame(grp.g, f);
+                auto name = [&](const std::string &p) { return anim.frame_path(p); };
+                conv = conv0; noise = noise0; denoise = denoise0; adaptive = adaptive0;
+                conv.name_files(name); noise.name_files(name); denoise.name_files(name); adaptive.name_files(name);
+                combined_filename = name(combined0); weighted_photon_filename = name(photon0); weighted_vpl_filename = name(vpl0); stat_filename = name(stat0);
+            }
+            float bsr = 0.f, total_area = 0.f, light_area = 0.f;
+            { evplp_context *h0 = evplp_group_context(grp.g, 0);
+              if (evplp_scene_metrics(h0, &bsr, &total_area, &light_area) < 0) throw std::runtime_error(std::string("scene metrics: ") + evplp_last_error(h0)); }
 
-        photon_radius = bsr * radius_percentage;                                                                 // :118-119
-        pdf_mc = (float)num_vpl_light_paths / (float)num_light_paths * kInvPi / (photon_radius * photon_radius); // :120
-        if (!json.has("clampingCoeff")) {                                                                        // :148-161
-            std::printf("Total area computation: %g\n", total_area);
-            clamping_value = clamping_start = 1.f / total_area;
-        } else clamping_value = clamping_start = json.at("clampingCoeff").as_float("clampingCoeff");
-        if (force_vsl) {                                                                                         // :205-218
-            float pct = json.at("vslRadiusPercentage").as_float("vslRadiusPercentage");
-            vsl_radius = bsr * pct;
-            if (vsl_radius <= 0.008f) { vsl_radius = std::max(vsl_radius, 0.008f); std::printf("warning : vslRadius is too small. clamped vslRadius\n"); }
-            vsl_inv_pi_radius2 = kInvPi / (vsl_radius * vsl_radius);
+            photon_radius = bsr * radius_percentage;                                                                 // :118-119
+            pdf_mc = (float)num_vpl_light_paths / (float)num_light_paths * kInvPi / (photon_radius * photon_radius); // :120
+            if (!json.has("clampingCoeff")) {                                                                        // :148-161
+                std::printf("Total area computation: %g\n", total_area);
+                clamping_value = clamping_start = 1.f / total_area;
+            } else clamping_value = clamping_start = json.at("clampingCoeff").as_float("clampingCoeff");
+            if (force_vsl) {                                                                                         // :205-218
+                float pct = json.at("vslRadiusPercentage").as_float("vslRadiusPercentage");
+                vsl_radius = bsr * pct;
+                if (vsl_radius <= 0.008f) { vsl_radius = std::max(vsl_radius, 0.008f); std::printf("warning : vslRadius is too small. clamped vslRadius\n"); }
+                vsl_inv_pi_radius2 = kInvPi / (vsl_radius * vsl_radius);
+            }
+            run(grp.g, scene, res_x, res_y);
         }
-        run(grp.g, scene, res_x, res_y);
     }
 
 private:
@@ -1006,6 +1164,7 @@ private:
             st.set("time", Json::number(time));
             if (!lvc) st.set("numIterations", Json::number(num_iterations));              // rtlvccomphoton.h writes the time only
             add_pass_times(h, st);
+            anim.add_stat(st);
             std::ofstream of(stat_filename);
             if (!of) throw std::runtime_error("cannot write " + stat_filename);
             of << st.dump() << "\n";
@@ -1053,6 +1212,7 @@ private:
     Noise noise;
     Adaptive adaptive;
     Denoise denoise;
+    Animation anim;
     int bvh_builder = EVPLP_BVH_SAH;   // measured 9% faster frames than the Morton LBVH on the conference stand-in; "bvhBuilder": "lbvh" selects the LBVH
 };
 

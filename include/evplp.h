@@ -132,6 +132,8 @@ typedef struct evplp_config {
      *                                   + 4 B per tile and 4 B per item of the largest call (the item table);
      *                                   budget mode: + 8 B per tile after evplp_adaptive_tile_noise
      *   refit (after a call)            28 B per node + 36 B per triangle (+ 4 B per light triangle), and the same staging bytes in pinned host memory (evplp_refit_accel)
+     *   rest pose (after a call)        36 B per triangle of the scene + 64 B per mesh, and 64 B per mesh in pinned host memory, made by the first
+     *                                   evplp_transform_mesh of a scene and freed with it; a context that never transforms allocates none of it
  *   PLOC build (during the call)    88 B per triangle on top of the device LBVH's scratch, freed before evplp_build_accel returns: 2 n clusters in ping-pong (28 B
  *                                   each), n nearest neighbours (4 B), n packed flags and their scan (16 B), children and counts of the inner nodes (12 B)
  *   tree cost (after a call)        24 B per 256 nodes + 8 B, and the same in pinned host memory; the refit's plan and staging (the row above) if no
@@ -282,6 +284,33 @@ int evplp_scene_metrics(evplp_context *ctx, float *bounding_sphere_radius, float
  * clears them (evplp_clear_accumulators) as after a camera change. */
 int evplp_update_mesh(evplp_context *ctx, int32_t mesh, const float *vertices, int32_t nverts);
 int evplp_refit_accel(evplp_context *ctx);
+/* ---- moving a mesh by a matrix: nothing is uploaded but twelve floats (INTEGRATION B7) ----
+ * m is a row-major 3 x 4 matrix.  A point p = (x, y, z) goes to out[r] = ((m[4r] x + m[4r+1] y) + m[4r+2] z) + m[4r+3]: fp32, every product and
+ * every sum rounded on its own, in this order, nothing fused (transform_point in evplp_types.h, the one function the host and the device
+ * call).  There is no special case for the identity: under it a coordinate of -0.0 becomes +0.0, everything else keeps its bits.
+ * Rest pose: the positions a mesh had at evplp_add_mesh, or the ones the last evplp_update_mesh gave it.  evplp_transform_mesh sets the
+ * mesh's current positions to transform_point(m, rest pose).  Transforms do NOT compose: a second call replaces the first, and the rest
+ * pose's own bits are never overwritten, so a hundred frames of rotation do not drift.  evplp_update_mesh sets a new rest pose and forgets
+ * the matrix.
+ * The call marks the mesh dirty exactly as evplp_update_mesh does: every pass is refused until evplp_refit_accel or evplp_build_accel, and
+ * several calls of either kind, on the same or on different meshes, may precede one refit.  The host copy of the mesh follows through the
+ * same function, so the full rebuild on a dirty context, a policy's rebuild, the refit's degenerate-triangle refusal and the scene's figures
+ * see the positions the device has.
+ * EVPLP_ERR_INVALID, nothing marked, the context staying usable: no evplp_build_accel yet, mesh out of range, a null matrix, a matrix entry
+ * that is not finite, a transformed coordinate that is not finite (checked on the host copy: refused here, never rendered).  A singular
+ * matrix is legal: its triangles lose their area and fall under the degenerate rule above, and one that was dropped at build time and is
+ * given an area is refused by the refit as above.
+ * On the device the refit treats a mesh that is dirty by transform differently from one that is dirty by upload: its triangles are neither
+ * staged nor copied (the host flattens a dirty mesh once, for the scene's figures).  The device keeps the rest pose (nine floats per triangle; a mesh's part is made at its first transform,
+ * from the attributes it already holds if the mesh is clean and has no matrix, from the host's rest pose otherwise, and again after
+ * evplp_update_mesh gave it a new one; after any evplp_build_accel or policy rebuild it is made again from the host's rest pose).  The
+ * dirty meshes go up as a table of (first triangle, count, matrix) through pinned memory on the stream, and ONE launch per refit writes
+ * the attributes of all of them; meshes dirty by upload keep the staging copy and the scatter, in the same refit.  The steady state still
+ * has no host wait.
+ * evplp_transform_points applies the same function to n points (host only, no GPU; in and out: float3[n], may be the same array):
+ * the positions evplp_transform_mesh will use, bit for bit.  EVPLP_ERR_INVALID for a null pointer or n < 0. */
+int evplp_transform_mesh(evplp_context *ctx, int32_t mesh, const float m[12]);
+int evplp_transform_points(const float m[12], const float *in, float *out, int32_t n);
 /* refits since evplp_create, heights of the current tree's plan (0 before its first refit), HIP-event time of the last refit (0 while
  * evplp_profile_passes is off; waits for that refit).  Each pointer may be null. */
 int evplp_refit_info(evplp_context *ctx, int32_t *refits, int32_t *levels, float *last_refit_ms);
@@ -787,6 +816,8 @@ int evplp_group_set_splat_proxy(evplp_group *g, const float *vertices, int32_t n
  * group staying usable, where the plain context refuses. */
 int evplp_group_update_mesh(evplp_group *g, int32_t mesh, const float *vertices, int32_t nverts);
 int evplp_group_refit_accel(evplp_group *g);
+/* evplp_transform_mesh on every rank (both partitions), refused on the caller's thread likewise; the matrix is copied before the call returns */
+int evplp_group_transform_mesh(evplp_group *g, int32_t mesh, const float m[12]);
 /* evplp_accel_quality / evplp_set_refit_policy on every rank (both partitions; the calls wait for the ranks).  Scene and tree are replicated,
  * so every rank computes the same doubles and a policy takes the same decision on each; the group returns rank 0's figures and fails
  * (EVPLP_ERR_INVALID) if any rank's differ.  Refused on the caller's thread, the group staying usable, where the plain context refuses. */

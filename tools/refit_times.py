@@ -14,7 +14,12 @@
       (evplp_accel_quality) of the refitted SAH tree and of a rebuilt SAH tree of the same moved scene, and beside it the config-#2 gather
       time of each.
 
-usage: python tools/refit_times.py [--reps N] [--tris N] [--res N] [--quality-only]"""
+  (7) --transform: the motions of (1) -- one chair, every mesh -- by upload (evplp_update_mesh) and by matrix (evplp_transform_mesh), each
+      followed by evplp_refit_accel: the host's wall time of the move calls and of the refit call, and the refit's HIP-event time.
+      --package-root DIR imports evplp_amd (and its library) from another checkout, for an A/B against it in alternating processes; a
+      checkout without evplp_transform_mesh prints the upload rows alone.
+
+usage: python tools/refit_times.py [--reps N] [--tris N] [--res N] [--quality-only | --transform] [--package-root DIR]"""
 import argparse
 import math
 import os
@@ -24,7 +29,7 @@ import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.abspath(sys.argv[sys.argv.index("--package-root") + 1]) if "--package-root" in sys.argv[1:-1] else ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import numpy as np  # noqa: E402
@@ -92,6 +97,29 @@ def time_refits(c, sd, meshes, sets, reps, name):
     print(f"      host, refit_accel call       ms {spread(t_refit)}")
     c.profile_kernels(False)
     return statistics.median(ev_ms), statistics.median(t_refit)
+
+
+def time_moves(c, sd, meshes, sets, reps, name):
+    """(7): sets = two vertex sets (by upload) or two matrices (by transform), alternated so that every refit really moves the meshes"""
+    by_matrix = not isinstance(sets[0], list)
+    ev_ms, t_move, t_refit = [], [], []
+    for r in range(reps + 2):
+        c.synchronize()
+        t0 = time.perf_counter()
+        for m in meshes:
+            c.transform_mesh(m, sets[r % 2]) if by_matrix else c.update_mesh(m, sets[r % 2][m])
+        t1 = time.perf_counter()
+        c.refit_accel()
+        t2 = time.perf_counter()
+        info = c.refit_info()
+        if r >= 2:                                                  # (the first builds the plan and the rest pose, the second warms the kernels)
+            ev_ms.append(info["last_refit_ms"]); t_move.append((t1 - t0) * 1e3); t_refit.append((t2 - t1) * 1e3)
+    tris = sum(sd.meshes[m]["idx"].shape[0] for m in meshes)
+    how = "transform_mesh" if by_matrix else "update_mesh"
+    print(f"(7) {name} by {how}: {len(meshes)} mesh(es), {tris} triangles moved")
+    print(f"      host, {how + ' calls':22s} ms {spread(t_move)}")
+    print(f"      host, refit_accel call       ms {spread(t_refit)}")
+    print(f"      device, whole refit          ms {spread(ev_ms)}")
 
 
 def time_builds(c, reps, name):
@@ -182,6 +210,8 @@ def main():
     ap.add_argument("--tris", type=int, default=331000)
     ap.add_argument("--res", type=int, default=1024)
     ap.add_argument("--quality-only", action="store_true", help="parts (5) and (6) alone")
+    ap.add_argument("--transform", action="store_true", help="part (7) alone")
+    ap.add_argument("--package-root", default=None, help="import evplp_amd from this checkout instead of the tool's own")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory(prefix="evplp_refit_") as d:
         sd, _ = scenes.load_obj_scene(ev.synth_scene(d, "conf", a.tris, 1234, a.res, a.res, style="hard"))
@@ -196,6 +226,24 @@ def main():
         ang = rng.rand() * 2 * math.pi
         large[k] = (orig[k] + np.array([math.cos(ang), math.sin(ang), 0.0], F)).astype(F)
 
+    if a.transform:
+        print(f"library: {ev.LIB_PATH}")
+        one = chairs[:1] if chairs else [0]
+        every = list(range(len(sd.meshes)))
+        nudged = list(orig)
+        nudged[one[0]] = (orig[one[0]] + np.array([0.05, 0.0, 0.0], F)).astype(F)
+        eye = np.eye(3, 4, dtype=F)
+        shift = lambda d: np.concatenate([np.eye(3, dtype=F), np.array(d, F).reshape(3, 1)], axis=1)
+        c = context(sd, a.res, ev.BVH_SAH)
+        time_moves(c, sd, one, (nudged, orig), a.reps, "one chair")
+        if hasattr(c, "transform_mesh"):
+            time_moves(c, sd, one, (shift((0.05, 0.0, 0.0)), eye), a.reps, "one chair")
+        time_moves(c, sd, every, (small, orig), a.reps, "every mesh")
+        if hasattr(c, "transform_mesh"):
+            time_moves(c, sd, every, (shift((0.01, 0.01, 0.0)), eye), a.reps, "every mesh")
+            time_moves(c, sd, one, (nudged, orig), a.reps, "one chair, after the transforms,")
+        c.close()
+        return
     if a.quality_only:
         c = context(sd, a.res, ev.BVH_SAH)
         time_quality(c, a.reps)
