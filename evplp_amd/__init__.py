@@ -151,6 +151,12 @@ _SIGNATURES = {
     "evplp_set_refit_policy": (C.c_int, [_P, C.c_double, C.c_int32]),
     "evplp_group_accel_quality": (C.c_int, [_P, C.POINTER(AccelQuality)]),
     "evplp_group_set_refit_policy": (C.c_int, [_P, C.c_double, C.c_int32]),
+    "evplp_optimize_accel": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32)]),
+    "evplp_set_refit_rotations": (C.c_int, [_P, C.c_int32]),
+    "evplp_rotation_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, C.POINTER(C.c_int32)]),
+    "evplp_rotate_tree": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, C.POINTER(C.c_int32)]),
+    "evplp_group_optimize_accel": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32)]),
+    "evplp_group_set_refit_rotations": (C.c_int, [_P, C.c_int32]),
     "evplp_scene_metrics": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "evplp_primary": (C.c_int, [_P, C.POINTER(C.c_float * 2), C.c_int32]),
     "evplp_trace_light_paths": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32]),
@@ -501,6 +507,23 @@ class Context:
         rebuild_builder: a BVH_* value, or -1 for the context's own"""
         self._check(self._lib.evplp_set_refit_policy(self._h, float(max_cost_ratio), int(rebuild_builder)))
 
+    def optimize_accel(self, passes: int = 1) -> int:
+        """evplp_optimize_accel: `passes` (1 .. 8) refit sweeps with tree rotations over the tree as it is, then the four-wide nodes; waits.
+        Returns the rotations taken."""
+        n = C.c_int32(0)
+        self._check(self._lib.evplp_optimize_accel(self._h, int(passes), C.byref(n)))
+        return n.value
+
+    def set_refit_rotations(self, passes: int):
+        """evplp_set_refit_rotations: refit_accel's own sweeps rotate, `passes` of them (0: off, the default); the refit then waits once"""
+        self._check(self._lib.evplp_set_refit_rotations(self._h, int(passes)))
+
+    def rotation_info(self) -> dict:
+        """evplp_rotation_info: rotations since the build, in the last sweeping call, per pass of it, and the refit's setting"""
+        a, b, p, per = C.c_int32(0), C.c_int32(0), C.c_int32(0), np.zeros(8, np.int32)
+        self._check(self._lib.evplp_rotation_info(self._h, C.byref(a), C.byref(b), _ptr(per), C.byref(p)))
+        return {"since_build": a.value, "last_call": b.value, "per_pass": [int(x) for x in per], "refit_passes": p.value}
+
     def refit_info(self):
         n, l, ms = C.c_int32(), C.c_int32(), C.c_float()
         self._check(self._lib.evplp_refit_info(self._h, C.byref(n), C.byref(l), C.byref(ms)))
@@ -830,6 +853,30 @@ def ploc_tree(verts9, radius: int = PLOC_RADIUS, search_iterations: int = PLOC_S
     return order[:n].copy(), children[:max(n - 1, 0)].copy(), it.value
 
 
+def rotate_tree(nodes, tri_index, verts9, passes: int = 1, level=None) -> dict:
+    """evplp_rotate_tree: the rotating refit sweep on the host (deterministic), the twin of evplp_optimize_accel.  nodes: ACCEL_NODE records or
+    raw 64-byte nodes (the child references alone are read); tri_index: 4 ints per leaf block; verts9: 9 floats per original triangle; level:
+    the plan's level per node, or None for evplp_refit_levels' heights of `nodes`.  Returns children [nnodes, 2], boxes [nnodes, 6] (lo, hi),
+    rotations (per pass), need0 (the root's four-wide stack need), levels, and nodes: a copy of the records with the new references (its
+    padded boxes are NOT updated)."""
+    raw = np.ascontiguousarray(nodes).view(np.uint8).reshape(-1, 64)
+    n = raw.shape[0]
+    ti = np.ascontiguousarray(tri_index, dtype=np.int32).reshape(-1)
+    v = np.ascontiguousarray(verts9, dtype=np.float32).reshape(-1, 9)
+    lv = None if level is None else np.ascontiguousarray(level, dtype=np.int32).reshape(-1)
+    if lv is not None and lv.shape[0] != n:
+        raise ValueError("rotate_tree: one level per node")
+    children, boxes = np.zeros((max(n, 1), 2), np.int32), np.zeros((max(n, 1), 6), np.float32)
+    rot, need0 = np.zeros(8, np.int32), C.c_int32(0)
+    rc = lib().evplp_rotate_tree(_ptr(raw), n, _ptr(ti) if ti.size else None, ti.shape[0], _ptr(v) if v.size else None, v.shape[0], None if lv is None else _ptr(lv), int(passes),
+                                 _ptr(children), _ptr(boxes), _ptr(rot), C.byref(need0))
+    if rc < 0:
+        raise EvplpError(rc, "evplp_rotate_tree: not a tree, passes outside 1 .. 8, or levels that put an inner child at or above its parent")
+    out = raw.copy()
+    out[:, 48:56] = children[:n].view(np.uint8).reshape(n, 8)
+    return {"children": children[:n], "boxes": boxes[:n], "rotations": [int(x) for x in rot[:int(passes)]], "need0": need0.value, "levels": rc, "nodes": out.reshape(-1).view(ACCEL_NODE)}
+
+
 Context.refit_levels = staticmethod(refit_levels)      # (the plan needs no context; it is listed with the calls it serves)
 
 
@@ -972,6 +1019,15 @@ class Group:
 
     def set_refit_policy(self, max_cost_ratio: float, rebuild_builder: int = -1):
         self._check(self._lib.evplp_group_set_refit_policy(self._h, float(max_cost_ratio), int(rebuild_builder)))
+
+    def optimize_accel(self, passes: int = 1) -> int:
+        """evplp_group_optimize_accel: on every rank; rank 0's rotation count, an error if any rank's differs"""
+        n = C.c_int32(0)
+        self._check(self._lib.evplp_group_optimize_accel(self._h, int(passes), C.byref(n)))
+        return n.value
+
+    def set_refit_rotations(self, passes: int):
+        self._check(self._lib.evplp_group_set_refit_rotations(self._h, int(passes)))
 
     def set_splat_proxy(self, vertices=None, triangles=None):
         if vertices is None:

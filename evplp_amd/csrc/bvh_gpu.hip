@@ -26,6 +26,8 @@
 //                      launch is the only hand-over between heights: a thread owns one node, reads its children's unpadded boxes
 //                      (a leaf's from its triangles, an inner child's from a scratch array the launch before wrote), writes its own
 //                      union there and the padded child boxes into its node -- padded once, from the exact union.
+//   c'. refit_rotate_level: c with tree rotations (evplp_optimize_accel, evplp_set_refit_rotations; off by default): where it shrinks the box
+//                      between them, a node swaps a child with a grandchild on the other side -- two node records rewritten, nothing moved.
 //   d. node4         : the four-wide nodes again, into the allocation they have.
 // Quality (evplp_accel_quality): accel_cost, one launch over the refit plan's order, sums the SAH cost's terms of the tree as it is.
 #include "evplp_types.h"
@@ -450,6 +452,122 @@ __global__ __launch_bounds__(256) void refit_level_kernel(BvhNode *nodes, int32_
     nodes[i] = f;
 }
 
+// c'. the same sweep with tree rotations (evplp_optimize_accel, evplp_set_refit_rotations): one thread per node N of one level of the PLAN.
+// It does what refit_level_kernel does and, where rotate_choice (evplp_types.h) finds a gain, swaps a child A of N with a grandchild G on the
+// other side: N.c[s] = G, B.c[q] = A, boxes[B] = A u K.  The thread that owns N writes N and its child B and nobody else touches either in
+// this launch: a rotation needs level(A) < level(B) in the plan, so every parent keeps a strictly higher plan level than its children, the
+// nodes of one launch are never parent and child, and the end of the launch stays the only hand-over.  (The plan's levels are no tight
+// heights after a rotation; nothing needs them to be.)  Two more values ride up the sweep: taken[i] = the rotations in the subtree of i in
+// this pass, need[i] = the four-wide walk's stack need of i; the root's pair goes to root_out.
+// The exact box under a child reference, as refit_level_kernel forms it: an inner node's from the scratch, a leaf's from its live triangles.
+__device__ __forceinline__ void rotate_ref_box(int32_t ref, int32_t nnodes, const Bx *boxes, const int32_t *tri_index, int32_t nslots, const TriAttr *attrs, int32_t ntri, float *out) {
+    Bx b;
+    for (int k = 0; k < 3; k++) { b.lo[k] = 3.0e38f; b.hi[k] = -3.0e38f; }
+    if (ref >= 0) { if (ref < nnodes) b = boxes[ref]; }
+    else if (ref != kNoChild) {
+        const int32_t id = ~ref, cnt = (id & 3) + 1;
+        for (int32_t q = 0; q < cnt; q++) {
+            const int32_t slot = (id & ~3) + q;
+            const int32_t tri = slot < nslots ? tri_index[slot] : -1;
+            if (tri < 0 || tri >= ntri) continue;
+            const float *v = attrs[tri].v;
+            if (!tri_has_area(v)) continue;
+            for (int k = 0; k < 3; k++) { b.lo[k] = fminf(b.lo[k], fminf(fminf(v[k], v[3 + k]), v[6 + k])); b.hi[k] = fmaxf(b.hi[k], fmaxf(fmaxf(v[k], v[3 + k]), v[6 + k])); }
+        }
+    }
+    for (int k = 0; k < 3; k++) { out[k] = b.lo[k]; out[3 + k] = b.hi[k]; }
+}
+__device__ __forceinline__ void rotate_set_box(BvhNode &f, int child, const float *b6, float pad) {
+    Bx b;
+    for (int k = 0; k < 3; k++) { b.lo[k] = b6[k]; b.hi[k] = b6[3 + k]; }
+    set_box(f, child, b, pad);
+}
+// the two child references of inner node i (kNoChild twice for anything else)
+__device__ __forceinline__ void rotate_kids(const BvhNode *nodes, int32_t nnodes, int32_t i, int32_t out[2]) {
+    out[0] = out[1] = kNoChild;
+    if (i >= 0 && i < nnodes) { out[0] = nodes[i].c0; out[1] = nodes[i].c1; }
+}
+__global__ __launch_bounds__(256) void refit_rotate_level_kernel(BvhNode *nodes, int32_t nnodes, const int32_t *order, int32_t count, const int32_t *tri_index, int32_t nslots,
+                                                                 const TriAttr *attrs, int32_t ntri, Bx *boxes, float pad, const int32_t *level, int32_t *taken, int32_t *need,
+                                                                 int32_t *root_out) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= count) return;
+    const int32_t i = order[t];
+    if (i < 0 || i >= nnodes) return;
+    BvhNode f = nodes[i];
+    int32_t ref[2] = { f.c0, f.c1 }, lvl[2], gref[2][2];
+    float box[2][6], gbox[2][2][6];
+#pragma unroll
+    for (int s = 0; s < 2; s++) {
+        rotate_ref_box(ref[s], nnodes, boxes, tri_index, nslots, attrs, ntri, box[s]);
+        lvl[s] = ref[s] >= 0 && ref[s] < nnodes ? level[ref[s]] : -1;
+        rotate_kids(nodes, nnodes, ref[s], gref[s]);
+#pragma unroll
+        for (int q = 0; q < 2; q++) rotate_ref_box(gref[s][q], nnodes, boxes, tri_index, nslots, attrs, ntri, gbox[s][q]);
+    }
+    const int pick = rotate_choice(ref, lvl, box, gref, gbox);
+    int32_t own = 0, sub[2];                                          // sub[s] = taken[] of child slot s
+#pragma unroll
+    for (int s = 0; s < 2; s++) sub[s] = ref[s] >= 0 && ref[s] < nnodes ? taken[ref[s]] : 0;
+    int32_t g4[4];                                                    // what node4 will put in N's four slots
+#pragma unroll
+    for (int s = 0; s < 2; s++) {
+        if (ref[s] >= 0) { g4[2 * s] = gref[s][0]; g4[2 * s + 1] = gref[s][1]; }
+        else { g4[2 * s] = ref[s]; g4[2 * s + 1] = kNoChild; }
+    }
+#pragma unroll
+    for (int s = 0; s < 2; s++) {
+#pragma unroll
+        for (int q = 0; q < 2; q++) {
+            if (pick != 2 * s + q) continue;
+            const int32_t a = ref[s], b = ref[1 - s], g = gref[1 - s][q], k = gref[1 - s][1 - q];
+            // B: slot q takes A (padded from A's exact box), slot 1 - q keeps K and the bytes B's own thread wrote in an earlier launch
+            BvhNode fb = nodes[b];
+            if (q == 0) fb.c0 = a; else fb.c1 = a;
+            rotate_set_box(fb, q, box[s], pad);
+            nodes[b] = fb;
+            float ub[6];
+            if (q == 0) rotate_union(box[s], gbox[1 - s][1], ub); else rotate_union(gbox[1 - s][0], box[s], ub);
+            Bx bb;
+            for (int c = 0; c < 3; c++) { bb.lo[c] = ub[c]; bb.hi[c] = ub[3 + c]; }
+            boxes[b] = bb;
+            // B's own count and need over its new children A and K
+            int32_t ka[2] = { gref[s][0], gref[s][1] }, kk[2], kg[2];
+            rotate_kids(nodes, nnodes, k, kk);
+            rotate_kids(nodes, nnodes, g, kg);
+            int32_t gb[4];
+            if (a >= 0) { gb[0] = ka[0]; gb[1] = ka[1]; } else { gb[0] = a; gb[1] = kNoChild; }
+            if (k >= 0) { gb[2] = kk[0]; gb[3] = kk[1]; } else { gb[2] = k; gb[3] = kNoChild; }
+            const int32_t need_b = rotate_need(gb, need, nnodes);
+            need[b] = need_b;
+            const int32_t taken_b = sub[1 - s] - (g >= 0 && g < nnodes ? taken[g] : 0) + sub[s];
+            taken[b] = taken_b;
+            // N: slot s takes G, slot 1 - s keeps B with its new box
+            if (g >= 0) { g4[2 * s] = kg[0]; g4[2 * s + 1] = kg[1]; } else { g4[2 * s] = g; g4[2 * s + 1] = kNoChild; }
+            g4[2 * (1 - s)] = q == 0 ? a : k; g4[2 * (1 - s) + 1] = q == 0 ? k : a;
+            sub[s] = g >= 0 && g < nnodes ? taken[g] : 0; sub[1 - s] = taken_b;
+            ref[s] = g;
+            for (int c = 0; c < 6; c++) { box[s][c] = gbox[1 - s][q][c]; box[1 - s][c] = ub[c]; }
+            own = 1;
+        }
+    }
+    f.c0 = ref[0]; f.c1 = ref[1];
+#pragma unroll
+    for (int s = 0; s < 2; s++) {
+        if (ref[s] == kNoChild) continue;                                 // (ctr = 0, hal = -3e38 as the builder left them)
+        rotate_set_box(f, s, box[s], pad);
+    }
+    float un[6];
+    rotate_union(box[0], box[1], un);
+    Bx u;
+    for (int c = 0; c < 3; c++) { u.lo[c] = un[c]; u.hi[c] = un[3 + c]; }
+    boxes[i] = u;
+    nodes[i] = f;
+    const int32_t taken_n = own + sub[0] + sub[1], need_n = rotate_need(g4, need, nnodes);
+    taken[i] = taken_n; need[i] = need_n;
+    if (i == 0) { root_out[0] = taken_n; root_out[1] = need_n; }
+}
+
 // node4[i] from binary node i: child s of i, if it is an inner node, is replaced by ITS two children (their boxes are stored in
 // that child's own record); a leaf or absent child stays.  lo / hi are computed exactly as the binary per-lane walk computes them.
 __global__ __launch_bounds__(256) void node4_kernel(const BvhNode *nodes, int n, BvhNode4 *out) {
@@ -542,6 +660,11 @@ void refit_leaves(const RefitScene &r, hipStream_t stream) {
 void refit_level(const RefitScene &r, const int32_t *d_order, int32_t count, float pad, hipStream_t stream) {
     if (count > 0) hipLaunchKernelGGL(refit_level_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, r.nodes, r.nnodes, d_order, count, r.tri_index, r.nslots,
                                       r.attrs, r.ntri, (Bx *)r.boxes, pad);
+}
+// the rotating level launch (d_level: the plan's level per node; d_taken, d_need: per-node scratch; d_root_out: two ints the root's thread writes)
+void refit_rotate_level(const RefitScene &r, const int32_t *d_order, int32_t count, float pad, const int32_t *d_level, int32_t *d_taken, int32_t *d_need, int32_t *d_root_out, hipStream_t stream) {
+    if (count > 0) hipLaunchKernelGGL(refit_rotate_level_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, r.nodes, r.nnodes, d_order, count, r.tri_index, r.nslots,
+                                      r.attrs, r.ntri, (Bx *)r.boxes, pad, d_level, d_taken, d_need, d_root_out);
 }
 
 // evplp_accel_quality's launch: d_order = the refit plan's whole order (count reached nodes), d_out = 1 + 3 * ceil(count / 256) doubles

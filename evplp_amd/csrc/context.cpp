@@ -214,6 +214,9 @@ static void free_scene_device(evplp_context *c) {
     hipFree(c->d_rest); hipFree(c->d_xform); if (c->h_xform) hipHostFree(c->h_xform);
     c->d_rest = nullptr; c->d_xform = c->h_xform = nullptr;
     for (HostMesh &m : c->meshes) m.rest_state = 0;
+    // ... and the scratch of the rotating sweep (made by the first call that asks for rotations)
+    hipFree(c->d_rotate); hipFree(c->d_rotate_out); if (c->h_rotate_out) hipHostFree(c->h_rotate_out);
+    c->d_rotate = c->d_rotate_out = c->h_rotate_out = nullptr; std::vector<int32_t>().swap(c->refit_height);
 }
 
 extern "C" void evplp_destroy(evplp_context *c) {
@@ -541,7 +544,7 @@ static int build_accel(evplp_context *c, int policy_builder) {
     std::memcpy(c->sc.light_intensity, c->light_scaled, 16); std::memcpy(c->sc.light_unscaled, c->light_unscaled, 16);
     c->accel_built = true; c->primary_cuts_valid = false;
     c->mesh_dirty.assign(c->meshes.size(), 0); c->scene_dirty = false;
-    c->built_cost = 0.0; c->built_cost_known = false; c->refits_since_build = 0;
+    c->built_cost = 0.0; c->built_cost_known = false; c->refits_since_build = 0; c->rotations_since_build = 0;
     if (c->policy_ratio > 0.0) {            // (a policy compares against the cost of the tree as built: one small launch and a wait)
         double q[5];
         if ((rc = measure_cost(c, q))) return rc;
@@ -683,6 +686,7 @@ static int refit_prepare(evplp_context *c) {
         }
     }
     std::vector<BvhNode>().swap(c->host_nodes);
+    c->refit_height.swap(height);           // (the plan's level per node: what a rotating sweep uploads, should one ever be asked for)
     if (levels < 1) { c->set_error("evplp_refit_accel: the node array is not a tree of at most %d levels", kMaxDepth); return EVPLP_ERR_INVALID; }
     const size_t stage = 9 * (size_t)c->scene_tris + (size_t)c->sc.light_count;
     hipError_t e = hipMalloc((void **)&c->d_refit_order, sizeof(int32_t) * (size_t)nn);
@@ -697,6 +701,40 @@ static int refit_prepare(evplp_context *c) {
     return EVPLP_OK;
 }
 
+// ---- tree rotations inside the sweep (evplp_optimize_accel, evplp_set_refit_rotations).  The scratch of the rotating launches, made by the
+// first call that asks for rotations: the plan's level per node goes up once -- a rotation keeps every parent above its children IN THE PLAN,
+// so the plan, its order and these levels hold for every later pass and refit of this tree, though the levels are no tight heights any more.
+static int rotate_prepare(evplp_context *c) {
+    if (c->d_rotate) return EVPLP_OK;
+    const size_t nn = (size_t)c->accel_nodes;
+    hipError_t e = hipMalloc((void **)&c->d_rotate, sizeof(int32_t) * 3 * nn);
+    if (e == hipSuccess) e = hipMalloc((void **)&c->d_rotate_out, sizeof(int32_t) * 16);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_rotate_out, sizeof(int32_t) * 16, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMemcpy(c->d_rotate, c->refit_height.data(), sizeof(int32_t) * nn, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(c->d_rotate + nn, 0, sizeof(int32_t) * 2 * nn);
+    if (e != hipSuccess) {
+        hipFree(c->d_rotate); hipFree(c->d_rotate_out); if (c->h_rotate_out) hipHostFree(c->h_rotate_out);
+        c->d_rotate = c->d_rotate_out = c->h_rotate_out = nullptr;
+        c->set_error("tree rotations: the sweep's scratch: %s", hipGetErrorString(e)); return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP;
+    }
+    return EVPLP_OK;
+}
+// `passes` sweeps, the leaves' parents first and the root last, each launch the rotating one; enqueued, none waits
+static void rotate_enqueue(evplp_context *c, const RefitScene &r, float pad, int32_t passes) {
+    const size_t nn = (size_t)c->accel_nodes;
+    for (int32_t p = 0; p < passes; p++)
+        for (int32_t l = 0; l < c->refit_levels; l++)
+            refit_rotate_level(r, c->d_refit_order + c->refit_level_begin[(size_t)l], c->refit_level_begin[(size_t)l + 1] - c->refit_level_begin[(size_t)l], pad,
+                               c->d_rotate, c->d_rotate + nn, c->d_rotate + 2 * nn, c->d_rotate_out + 2 * p, c->stream);
+}
+// after the wait: the root's { rotations, need } of every pass are in the pinned words
+static void rotate_finish(evplp_context *c, int32_t passes) {
+    c->rotations_last = 0;
+    for (int p = 0; p < 8; p++) { c->rotations_pass[p] = p < passes ? c->h_rotate_out[2 * p] : 0; c->rotations_last += c->rotations_pass[p]; }
+    c->rotations_since_build += c->rotations_last;
+    c->sc.stack4_entries = c->h_rotate_out[2 * (passes - 1) + 1] + 2;   // (kernels.h takes the smaller of this and the generic bound of the depth)
+}
+
 extern "C" int evplp_refit_accel(evplp_context *c) {
     CTX_CHECK(c);
     if (!evplp::refit_check(c)) return EVPLP_ERR_INVALID;
@@ -704,6 +742,8 @@ extern "C" int evplp_refit_accel(evplp_context *c) {
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     // (a photon splat whose verdict is still out is not waited for: a splat reads records and the G-buffer, never the scene)
     int rc = refit_prepare(c); if (rc) return rc;
+    const int32_t rot = c->rotate_passes;                       // (evplp_set_refit_rotations; 0, the default: the call is what it always was)
+    if (rot > 0 && (rc = rotate_prepare(c))) return rc;
     std::vector<int32_t> first;
     { int32_t n = 0; for (const HostMesh &m : c->meshes) { first.push_back(n); n += (int32_t)(m.idx.size() / 3); } first.push_back(n); }
     // 5. the host's figures, by the code evplp_build_accel uses, for the meshes that moved alone (in front of the launches, so that they
@@ -776,10 +816,12 @@ extern "C" int evplp_refit_accel(evplp_context *c) {
     r.nslots = 4 * c->accel_leaves; r.attrs = c->sc.attrs; r.ntri = c->scene_tris; r.boxes = c->d_refit_boxes;
     refit_leaves(r, c->stream);
     if (stages) HIP_TRY(c, hipEventRecord(c->ev_refit[2], c->stream));
-    for (int32_t l = 0; l < c->refit_levels; l++)
+    if (rot > 0) rotate_enqueue(c, r, pad, rot);             // (the first pass IS the refit's sweep; further passes repeat it)
+    else for (int32_t l = 0; l < c->refit_levels; l++)
         refit_level(r, c->d_refit_order + c->refit_level_begin[(size_t)l], c->refit_level_begin[(size_t)l + 1] - c->refit_level_begin[(size_t)l], pad, c->stream);
     if (stages) HIP_TRY(c, hipEventRecord(c->ev_refit[3], c->stream));
     build_nodes4_into(c->sc.nodes, c->accel_nodes, c->stream, (BvhNode4 *)c->sc.nodes4);
+    if (rot > 0) HIP_TRY(c, hipMemcpyAsync(c->h_rotate_out, c->d_rotate_out, sizeof(int32_t) * 2 * (size_t)rot, hipMemcpyDeviceToHost, c->stream));
     // 5. ... the CDF goes up only if the light moved
     if (c->mesh_dirty[(size_t)c->light_mesh]) {
         float *h = c->h_refit_stage + 9 * (size_t)c->scene_tris;
@@ -796,12 +838,18 @@ extern "C" int evplp_refit_accel(evplp_context *c) {
     if (c->policy_ratio > 0.0) {
         // The policy (evplp_set_refit_policy): the cost of the refitted tree against the cost of the tree as built.  One small launch and
         // one host wait; a rebuild is evplp_build_accel's code (which measures the new built_cost, the policy being on).
+        // With rotations on, the cost is the rotated tree's, and the wait is the one that brings the rotations' counts back.
         double q[5];
         if ((rc = measure_cost(c, q))) return rc;
+        if (rot > 0) rotate_finish(c, rot);
         if (q[0] > c->policy_ratio * c->built_cost) {
             if ((rc = build_accel(c, c->policy_builder))) return rc;
             c->policy_rebuilds++; c->last_action = 2;
-        } else c->last_action = 1;
+        } else c->last_action = rot > 0 ? 3 : 1;
+    } else if (rot > 0) {                   // the refit with rotations is not free of host waits: the root's counts and stack need come back
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        rotate_finish(c, rot);
+        c->last_action = 3;
     }
     return EVPLP_OK;
 }
@@ -869,6 +917,58 @@ extern "C" int evplp_set_refit_policy(evplp_context *c, double max_cost_ratio, i
         const int rc = measure_cost(c, q); if (rc) return rc;
     }
     c->policy_ratio = max_cost_ratio; c->policy_builder = rebuild_builder;
+    return EVPLP_OK;
+}
+
+// ---------------------------------------------------------------------------------- tree rotations
+namespace evplp {
+bool optimize_accel_check(evplp_context *c, const char *name, int32_t passes) {
+    if (!accel_quality_check(c, name)) return false;
+    if (passes < 1 || passes > 8) { c->set_error("%s: passes must be 1 .. 8, not %d", name, passes); return false; }
+    return true;
+}
+bool refit_rotations_check(evplp_context *c, const char *name, int32_t passes) {
+    if (passes < 0 || passes > 8) { c->set_error("%s: passes must be 0 .. 8 (0: off), not %d", name, passes); return false; }
+    return true;
+}
+}
+
+extern "C" int evplp_optimize_accel(evplp_context *c, int32_t passes, int32_t *rotations) {
+    CTX_CHECK(c);
+    if (!evplp::optimize_accel_check(c, "evplp_optimize_accel", passes)) return EVPLP_ERR_INVALID;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    int rc = refit_prepare(c); if (rc) return rc;
+    if ((rc = rotate_prepare(c))) return rc;
+    // behind everything on the context's stream: `passes` sweeps from the leaves' boxes upward (the triangles have not moved, so the leaf
+    // operands stay), the four-wide nodes again, and the root's counts back in one small copy; one host wait
+    RefitScene r; std::memset(&r, 0, sizeof(r));
+    r.nodes = (BvhNode *)c->sc.nodes; r.nnodes = c->accel_nodes; r.leaves = (LeafBlock *)c->sc.leaves; r.tri_flat = (TriFlat *)c->sc.tri_flat; r.tri_index = c->sc.tri_index;
+    r.nslots = 4 * c->accel_leaves; r.attrs = c->sc.attrs; r.ntri = c->scene_tris; r.boxes = c->d_refit_boxes;
+    rotate_enqueue(c, r, c->accel_pad, passes);
+    build_nodes4_into(c->sc.nodes, c->accel_nodes, c->stream, (BvhNode4 *)c->sc.nodes4);
+    HIP_TRY(c, hipMemcpyAsync(c->h_rotate_out, c->d_rotate_out, sizeof(int32_t) * 2 * (size_t)passes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    rotate_finish(c, passes);
+    c->primary_cuts_valid = false; c->tile_box_valid = false;
+    c->last_action = 3;
+    if (rotations) *rotations = c->rotations_last;
+    return EVPLP_OK;
+}
+
+extern "C" int evplp_set_refit_rotations(evplp_context *c, int32_t passes) {
+    CTX_CHECK(c);
+    if (!evplp::refit_rotations_check(c, "evplp_set_refit_rotations", passes)) return EVPLP_ERR_INVALID;
+    c->rotate_passes = passes;
+    return EVPLP_OK;
+}
+
+extern "C" int evplp_rotation_info(evplp_context *c, int32_t *since_build, int32_t *last_call, int32_t *per_pass, int32_t *refit_passes) {
+    CTX_CHECK(c);
+    if (since_build) *since_build = c->rotations_since_build;
+    if (last_call) *last_call = c->rotations_last;
+    if (per_pass) std::memcpy(per_pass, c->rotations_pass, sizeof(c->rotations_pass));
+    if (refit_passes) *refit_passes = c->rotate_passes;
     return EVPLP_OK;
 }
 

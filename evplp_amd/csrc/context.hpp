@@ -20,6 +20,8 @@ void refit_rest(const TriAttr *attrs, int32_t first, int32_t count, float *d_res
 void refit_transform(const TransformDesc *d_table, int32_t nmesh, int32_t total, const float *d_rest, TriAttr *attrs, int32_t ntri, hipStream_t stream);
 void refit_leaves(const RefitScene &r, hipStream_t stream);
 void refit_level(const RefitScene &r, const int32_t *d_order, int32_t count, float pad, hipStream_t stream);
+// (the level launch with tree rotations: d_level = the plan's level per node, d_taken / d_need = per-node scratch, d_root_out = { rotations, need } of the root)
+void refit_rotate_level(const RefitScene &r, const int32_t *d_order, int32_t count, float pad, const int32_t *d_level, int32_t *d_taken, int32_t *d_need, int32_t *d_root_out, hipStream_t stream);
 // bvh_gpu.hip: the launch of evplp_accel_quality (enqueued; d_out: 1 + 3 * ceil(count / 256) doubles -- the root's area, then a triple per workgroup)
 void accel_cost(const BvhNode *d_nodes, int32_t nnodes, const int32_t *d_order, int32_t count, double *d_out, hipStream_t stream);
 // rest: the rest pose of a mesh that evplp_transform_mesh has moved (verts = transform_point(matrix, rest)); empty: verts is the rest pose.
@@ -51,6 +53,9 @@ bool refit_check(evplp_context *c);
 // what evplp_accel_quality / evplp_set_refit_policy refuse without touching a device (name: the entry point, for the message)
 bool accel_quality_check(evplp_context *c, const char *name);
 bool refit_policy_check(evplp_context *c, double max_cost_ratio, int32_t rebuild_builder);
+// what evplp_optimize_accel / evplp_set_refit_rotations refuse, likewise
+bool optimize_accel_check(evplp_context *c, const char *name, int32_t passes);
+bool refit_rotations_check(evplp_context *c, const char *name, int32_t passes);
 // evplp_noise_* (context.cpp), for the group's workers as well
 NoisePlanes noise_planes(const evplp_context *c);
 NoiseMoments noise_moments_of(const evplp_context *c);           // a context's own moments (S = c_prev - c_start)
@@ -134,6 +139,12 @@ struct evplp_context {
     double *d_cost = nullptr, *h_cost = nullptr; hipEvent_t ev_cost[2] = {}; bool cost_timed = false;
     double built_cost = 0.0, policy_ratio = 0.0; bool built_cost_known = false;
     int32_t policy_builder = -1, refits_since_build = 0, policy_rebuilds = 0, last_action = 0;
+    // evplp_optimize_accel / evplp_set_refit_rotations.  refit_height: the plan's level per node, kept on the host from refit_prepare.  The
+    // first call that asks for rotations uploads it and makes the sweep's scratch -- d_rotate: [3][nodes] ints, the level, the rotations
+    // taken below a node in a pass, its four-wide stack need -- and the root's { rotations, need } per pass on the device and in pinned host
+    // memory ([2 * 8] ints each); all freed with the scene.  rotate_passes: the refit's own passes (0: off, the default).
+    std::vector<int32_t> refit_height; int32_t *d_rotate = nullptr, *d_rotate_out = nullptr, *h_rotate_out = nullptr;
+    int32_t rotate_passes = 0, rotations_since_build = 0, rotations_last = 0, rotations_pass[8] = {};
 
     evplp::SceneDev sc{};
     evplp_record *d_vpls = nullptr; uint32_t *d_vpl_src = nullptr;

@@ -231,6 +231,53 @@ __host__ __device__ inline void transform_point(const float m[12], const float p
         out[r] = ((a + b) + c) + m[4 * r + 3];
     }
 }
+// ---- tree rotations inside the refit sweep (Kensler 2008; Kopta et al. 2012): evplp_optimize_accel / evplp_set_refit_rotations on the device
+// (refit_rotate_level_kernel, bvh_gpu.hip) and evplp_rotate_tree on the host (host/rotate.cpp) both decide with rotate_choice and count the
+// four-wide walk's stack with rotate_need, and with nothing else.  A box is lo[3] then hi[3], exact and unpadded.
+// Node N, processed at level l of the refit's PLAN, has the child slots ref[0], ref[1] (box[s], lvl[s] = the plan level of an inner child, -1
+// for a leaf reference); an inner child ref[s] has the children gref[s][0], gref[s][1] with the boxes gbox[s][.] (kNoChild where ref[s] is
+// no inner node).  Candidate (s, q), visited in the order (0,0), (0,1), (1,0), (1,1): A = ref[s] moves down, B = ref[1-s] must be an inner
+// node, G = gref[1-s][q] moves up, K = gref[1-s][1-q] stays under B.  Admissible: none of A, G, K absent, none of their boxes empty
+// (hi < lo on an axis: a leaf whose triangles have all lost their area), and lvl(A) < lvl(B) -- the PLAN's levels, not the current heights:
+// every parent then keeps a strictly higher plan level than its children, so the plan stays a children-before-parents schedule, two nodes of
+// one launch are never parent and child, and no path grows longer than the plan has levels.  (The levels stop being tight heights; nothing
+// needs them to be.)  gain = area(box B) - area(box A u box K) with ploc_distance's fp32 area; the largest gain > 0 wins, ties keep the
+// first candidate.  Returns 2 s + q, or -1: nothing to take.
+__host__ __device__ inline bool rotate_box_empty(const float *b) { return b[3] < b[0] || b[4] < b[1] || b[5] < b[2]; }
+__host__ __device__ inline int rotate_choice(const int32_t ref[2], const int32_t lvl[2], const float box[2][6], const int32_t gref[2][2], const float gbox[2][2][6]) {
+#pragma clang fp contract(off)
+    int best = -1;
+    float best_gain = 0.0f;
+#pragma unroll
+    for (int s = 0; s < 2; s++) {
+        if (ref[s] == kNoChild || ref[1 - s] < 0 || !(lvl[s] < lvl[1 - s]) || rotate_box_empty(box[s])) continue;
+#pragma unroll
+        for (int q = 0; q < 2; q++) {
+            if (gref[1 - s][q] == kNoChild || gref[1 - s][1 - q] == kNoChild || rotate_box_empty(gbox[1 - s][q]) || rotate_box_empty(gbox[1 - s][1 - q])) continue;
+            const float gain = ploc_distance(box[1 - s], box[1 - s]) - ploc_distance(box[s], gbox[1 - s][1 - q]);
+            if (gain > best_gain) { best_gain = gain; best = 2 * s + q; }
+        }
+    }
+    return best;
+}
+// the union of the boxes of a node's two child slots, folded from the empty box in slot order -- as refit_level_kernel folds them
+__host__ __device__ inline void rotate_union(const float *b0, const float *b1, float *out) {
+    for (int k = 0; k < 3; k++) { out[k] = fminf(fminf(3.0e38f, b0[k]), b1[k]); out[3 + k] = fmaxf(fmaxf(-3.0e38f, b0[3 + k]), b1[3 + k]); }
+}
+// The four-wide walk's stack need of a node (evplp_build_accel's sweep): g = what node4 puts in its four slots -- the two children of an
+// inner child, or a leaf child itself and kNoChild --, need = the per-node array of the levels below.  max(valid - 1, 0) + the largest need
+// among the inner ones.
+__host__ __device__ inline int32_t rotate_need(const int32_t g[4], const int32_t *need, int32_t nnodes) {
+    int32_t valid = 0, deepest = 0;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        if (g[q] == kNoChild) continue;
+        valid++;
+        if (g[q] >= 0 && g[q] < nnodes) { const int32_t d = need[g[q]]; deepest = d > deepest ? d : deepest; }
+    }
+    return (valid > 1 ? valid - 1 : 0) + deepest;
+}
+
 // one moved mesh of a refit, as refit_transform_kernel finds it: its run of original triangles, where the run starts among the moved
 // triangles of the launch (ascending over the table), and its matrix
 struct TransformDesc { int32_t first, count, begin, pad; float m[12]; };

@@ -66,7 +66,7 @@ struct Rccl {
 };
 
 enum Op { OP_QUIT = 0, OP_CLEAR, OP_SYNC, OP_PRIMARY, OP_TRACE, OP_GATHER, OP_SPLAT, OP_PATH_TRACE, OP_PRESENT, OP_LOAD_SCENE, OP_SET_PROXY, OP_ASSEMBLE, OP_REDUCE, OP_SET_REFERENCE, OP_FRAME_ERROR,
-          OP_NOISE_TRACK, OP_NOISE_FOLD, OP_NOISE_POOL, OP_NOISE_ROWS, OP_NOISE_VARIANCE, OP_ADAPT_ENABLE, OP_ADAPT_RETIRE, OP_DENOISE_PREP, OP_DENOISE_FILTER, OP_PATH_TRACE_BATCH, OP_ADAPT_SET_BUDGETS, OP_ADAPT_TILE_NOISE, OP_UPDATE_MESH, OP_TRANSFORM_MESH, OP_REFIT, OP_ACCEL_QUALITY, OP_REFIT_POLICY };
+          OP_NOISE_TRACK, OP_NOISE_FOLD, OP_NOISE_POOL, OP_NOISE_ROWS, OP_NOISE_VARIANCE, OP_ADAPT_ENABLE, OP_ADAPT_RETIRE, OP_DENOISE_PREP, OP_DENOISE_FILTER, OP_PATH_TRACE_BATCH, OP_ADAPT_SET_BUDGETS, OP_ADAPT_TILE_NOISE, OP_UPDATE_MESH, OP_TRANSFORM_MESH, OP_REFIT, OP_ACCEL_QUALITY, OP_REFIT_POLICY, OP_OPTIMIZE_ACCEL, OP_REFIT_ROTATIONS };
 // One posted call, copied into the ring by assignment: plain data (pointers must stay valid until the caller has drained: load_scene, set_proxy,
 // resolve do) but for `batch`, a shared pointer -- so every post and every worker-side copy of a command pays one atomic reference count, null or not.
 struct Cmd {
@@ -412,6 +412,8 @@ static void worker_run(Worker *w, const Cmd &cmd) {
         case OP_REFIT: rc = evplp_refit_accel(c); break;
         case OP_ACCEL_QUALITY: rc = evplp_accel_quality(c, (struct evplp_accel_quality *)cmd.out + w->rank); break;      // (out: one record per rank, the caller's)
         case OP_REFIT_POLICY: rc = evplp_set_refit_policy(c, cmd.d, cmd.i[0]); break;
+        case OP_OPTIMIZE_ACCEL: rc = evplp_optimize_accel(c, cmd.i[0], (int32_t *)cmd.out + w->rank); break;          // (out: one count per rank, the caller's)
+        case OP_REFIT_ROTATIONS: rc = evplp_set_refit_rotations(c, cmd.i[0]); break;
         case OP_SET_REFERENCE: rc = evplp_set_error_reference(c, (const float *)cmd.p0, (const uint8_t *)cmd.p1); break;
         case OP_FRAME_ERROR: rc = evplp::frame_error_rows(c); break;          // (behind this rank's composite, on its stream)
         case OP_NOISE_TRACK: rc = evplp_noise_track(c, cmd.i[0], (const uint8_t *)cmd.p0); break;
@@ -846,6 +848,30 @@ extern "C" int evplp_group_set_refit_policy(evplp_group *g, double max_cost_rati
     drain(g);
     if (!evplp::refit_policy_check(g->ctx[0], max_cost_ratio, rebuild_builder)) { g->set_error("%s", g->ctx[0]->error); return EVPLP_ERR_INVALID; }
     Cmd c; c.op = OP_REFIT_POLICY; c.d = max_cost_ratio; c.i[0] = rebuild_builder;
+    return post_and_wait(g, c);
+}
+// Tree rotations: every rank runs the same sweeps over its copy of the tree and must take the same rotations; rank 0's count is the group's.
+extern "C" int evplp_group_optimize_accel(evplp_group *g, int32_t passes, int32_t *rotations) {
+    GRP_CHECK(g);
+    drain(g);
+    if (!evplp::optimize_accel_check(g->ctx[0], "evplp_group_optimize_accel", passes)) { g->set_error("%s", g->ctx[0]->error); return EVPLP_ERR_INVALID; }
+    std::vector<int32_t> n((size_t)g->n, 0);
+    Cmd c; c.op = OP_OPTIMIZE_ACCEL; c.i[0] = passes; c.out = n.data();
+    const int rc = post_and_wait(g, c);
+    if (rc < 0) return rc;
+    for (int r = 1; r < g->n; r++)
+        if (n[(size_t)r] != n[0]) {
+            g->set_error("evplp_group_optimize_accel: rank %d took %d rotations, rank 0 took %d: the ranks' trees are not the same", r, n[(size_t)r], n[0]);
+            return EVPLP_ERR_INVALID;
+        }
+    if (rotations) *rotations = n[0];
+    return EVPLP_OK;
+}
+extern "C" int evplp_group_set_refit_rotations(evplp_group *g, int32_t passes) {
+    GRP_CHECK(g);
+    drain(g);
+    if (!evplp::refit_rotations_check(g->ctx[0], "evplp_group_set_refit_rotations", passes)) { g->set_error("%s", g->ctx[0]->error); return EVPLP_ERR_INVALID; }
+    Cmd c; c.op = OP_REFIT_ROTATIONS; c.i[0] = passes;
     return post_and_wait(g, c);
 }
 extern "C" int evplp_group_path_trace(evplp_group *g, const float camera_pos[3], uint32_t rng_seed, uint32_t max_bounces, int32_t do_accumulate) {

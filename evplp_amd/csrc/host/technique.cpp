@@ -625,7 +625,8 @@ private:
 // matrix per track and frame (evplp_group_transform_mesh: the rest pose under the matrix, nothing composes), and every frame is rendered by
 // the technique's loop from its beginning.
 //   {"frames": F, "tracks": [{"object": k, "matrices": [[12 numbers], ... F of them]}, {"mesh": i, "matrices": [...]}],
-//    "refitPolicy": {"maxCostRatio": r, "rebuildBuilder": "gpu"}}
+//    "refitPolicy": {"maxCostRatio": r, "rebuildBuilder": "gpu"}, "rotations": k}
+// "rotations": k = 0 .. 8 (default 0: off) is evplp_group_set_refit_rotations: k passes of tree rotations inside every frame's refit.
 // "object": k addresses every mesh the k-th entry of the scene file's "scene" array produced (an OBJ yields one mesh per material group),
 // "object": "arealight" the light, "mesh": i the i-th mesh in upload order.  For frame f = 0 .. F - 1 every track's f-th matrix is applied,
 // the tree is refitted (evplp_group_refit_accel; refitPolicy is evplp_group_set_refit_policy) and the loop runs as a fresh evplp_render_json
@@ -700,6 +701,11 @@ public:
                     throw JsonError("animation.refitPolicy.rebuildBuilder: \"ploc\" is not a rebuild builder yet (evplp_set_refit_policy); with \"bvhBuilder\": \"ploc\" leave it out -- the policy then rebuilds with the context's own builder");
             }
         }
+        if (a.has("rotations")) {           // tree rotations inside every frame's refit (evplp_group_set_refit_rotations); 0, the default: off
+            const double k = a.at("rotations").as_number("animation.rotations");
+            if (a.at("rotations").type != Json::Number || !(k >= 0.0) || !(k <= 8.0) || k != std::floor(k)) throw JsonError("animation.rotations: must be an integer 0 .. 8 (rotation passes inside a frame's refit; 0: off)");
+            rotations = (int)k;
+        }
         frames = (int)F; on = true;
     }
     // path with _fNNNN in front of its extension
@@ -712,6 +718,7 @@ public:
     }
     void start(evplp_group *g) {
         if (on && policy_ratio > 0.0) check(g, evplp_group_set_refit_policy(g, policy_ratio, policy_builder), "animation.refitPolicy");
+        if (on && rotations > 0) check(g, evplp_group_set_refit_rotations(g, rotations), "animation.rotations");
     }
     // frame f: the tracks' matrices, the refit, and its figures for the frame's stat file
     void begin_frame(evplp_group *g, int f) {
@@ -740,7 +747,7 @@ public:
 private:
     struct Track { std::vector<int32_t> meshes; std::vector<float> matrices; };       // matrices: [frames][12]
     std::vector<Track> tracks;
-    double policy_ratio = 0.0; int policy_builder = -1;
+    double policy_ratio = 0.0; int policy_builder = -1; int rotations = 0;
     int frame = 0; float refit_ms = 0.f; int last_action = 0; double cost_ratio = 0.0;
 };
 } // namespace

@@ -138,6 +138,10 @@ typedef struct evplp_config {
  *                                   each), n nearest neighbours (4 B), n packed flags and their scan (16 B), children and counts of the inner nodes (12 B)
  *   tree cost (after a call)        24 B per 256 nodes + 8 B, and the same in pinned host memory; the refit's plan and staging (the row above) if no
  *                                   refit of this tree has made them yet: refit_prepare makes them (evplp_accel_quality, evplp_set_refit_policy)
+ *   tree rotations (after a call)   12 B per node (the plan's level, the rotations taken below the node, its four-wide stack need) + 64 B, and 64 B in
+ *                                   pinned host memory, made by the first evplp_optimize_accel or the first refit with evplp_set_refit_rotations > 0
+ *                                   and freed with the scene; the refit's plan and staging too if no refit has made them; a context that never asks
+ *                                   for rotations allocates and launches none of it
      *   denoiser (after a call)         124 B per pixel of the context's planes (evplp_denoise); a group's rank: 92 B per pixel of its planes
      *                                   + n x 80 B per pixel of the exchanged rows, and rank 0 + 112 B per image pixel (evplp_group_denoise)
      * A caller that has the device to itself sets cut_scratch_bytes = 72 GB, vsl_mask_bytes = 14 GB for config #5 (one band, one launch). */
@@ -367,6 +371,49 @@ struct evplp_accel_quality {            /* (the call below has the same name: C 
 int evplp_accel_cost(const void *nodes64, int32_t nnodes, double out[5]);
 int evplp_accel_quality(evplp_context *ctx, struct evplp_accel_quality *out);
 int evplp_set_refit_policy(evplp_context *ctx, double max_cost_ratio, int32_t rebuild_builder);
+/* ---- tree rotations inside the refit sweep: between "keep the aged topology" and "throw the tree away" (INTEGRATION B7) ----
+ * Opt-in and off by default (Kensler 2008; Kopta et al. 2012).  A rotating sweep is the refit's sweep -- every node once, children before
+ * parents, one launch per level of the refit's plan -- in which node N, besides its boxes, may swap one of its children with a grandchild
+ * on the other side.  N's child slots are c[0], c[1]; the candidates (s, q) are visited in the order (0,0), (0,1), (1,0), (1,1): A = c[s]
+ * moves down, B = c[1-s] must be an inner node, G = B.c[q] moves up, K = B.c[1-q] stays under B.  A candidate is admissible if none of A, G, K
+ * is absent, none of their exact (unpadded) boxes is empty, and level(A) < level(B), where level is the node's level in the refit's PLAN
+ * (evplp_refit_levels' height[] of the tree as it was when the plan was made; a leaf reference counts as -1), not its current height.
+ * gain = area(box B) - area(box A u box K), area = ex ey + ey ez + ez ex in fp32 in that order, nothing fused; the largest gain > 0 is taken,
+ * ties keep the first candidate.  Taken: N.c[s] = G, B.c[q] = A, B's box = A u K; the three touched child boxes are padded from the exact
+ * boxes with the refit's pad.  Two 64-byte node records are rewritten; no node is allocated and no leaf moves.
+ * The level condition keeps every parent on a strictly higher plan level than its children.  So the plan stays a valid schedule for this
+ * pass, for further passes and for every later refit (nothing is planned again, nothing is downloaded; the levels are no tight heights any
+ * more); two nodes of one launch are never parent and child, so the sweep needs no atomics and no fences; and no root-to-leaf path grows
+ * longer than the plan has levels, so the depth, the walks' stacks and the plan's level count stay valid.
+ * Visibility and closest hit are exact predicates over the triangles: a frame over a rotated tree equals a fresh build's bit for bit.
+ *   evplp_optimize_accel(ctx, passes, rotations): passes = 1 .. 8 full sweeps (leaf boxes upward with rotations) and the four-wide nodes,
+ *     on the context's stream behind everything enqueued, ONE host wait; *rotations (may be null) = the rotations taken in all passes.  The
+ *     four-wide walk's stack bound (evplp_accel_stack_entries) is computed in the same sweep and becomes the rotated tree's.  It leaves
+ *     accumulators, noise moments and adaptive records alone and sets evplp_accel_quality's last_action to 3.  EVPLP_ERR_INVALID, the
+ *     context staying usable: before evplp_build_accel, while vertices are dirty (as every pass), passes outside 1 .. 8.
+ *     evplp_accel_quality keeps summing in the plan's order, which after a rotation is no longer evplp_refit_levels' order of the rotated
+ *     bytes: its sums then equal evplp_accel_cost's within the rounding of the additions (reached_nodes x 2^-52 of each sum), not bit
+ *     for bit; the ranks of a group, which share the plan, still agree with each other bit for bit.
+ *   evplp_set_refit_rotations(ctx, passes): 0 = off, the default -- evplp_refit_accel is then exactly the call above.  With passes = 1 .. 8
+ *     the refit's own level launches are the rotating ones (the first pass IS the refit's sweep, further passes repeat it), and the refit
+ *     has ONE HOST WAIT, for the root's counts: it is no longer free of host waits.  With a policy set as well it is the wait the cost
+ *     measurement makes anyway, and the policy compares the cost AFTER the rotations.  last_action: 2 rebuilt, else 3 (kept, rotating
+ *     sweeps ran); 1 only without rotations.  EVPLP_ERR_INVALID: passes outside 0 .. 8.
+ *   evplp_rotation_info: rotations since the last evplp_build_accel (a policy rebuild included), rotations in the last call that swept
+ *     (evplp_optimize_accel, or a refit with rotations on), the same per pass (8 ints, zeros behind the passes run), and the refit's
+ *     setting.  Each pointer may be null.
+ *   evplp_rotate_tree is the host-only statement of the sweep (no GPU, deterministic), with the functions the kernel calls: nodes64 as for
+ *     evplp_refit_levels (the child references alone are read), tri_index = nslots ints (4 per leaf block: original triangle or -1), verts9 =
+ *     9 floats per original triangle, level = the plan's level per node or null (null: evplp_refit_levels' heights of nodes64 as it is;
+ *     given: every inner child must lie below its parent).  Out: children (2 nnodes ints, the new references), boxes (6 nnodes floats: lo,
+ *     hi of the exact box under every reached node), rotations (passes ints, per pass), *need0 (the root's four-wide stack need:
+ *     evplp_accel_stack_entries - 2).  Returns the plan's levels, or EVPLP_ERR_INVALID (not a tree, a null array, passes outside 1 .. 8,
+ *     levels that are no schedule). */
+int evplp_optimize_accel(evplp_context *ctx, int32_t passes, int32_t *rotations);
+int evplp_set_refit_rotations(evplp_context *ctx, int32_t passes);
+int evplp_rotation_info(evplp_context *ctx, int32_t *since_build, int32_t *last_call, int32_t per_pass[8], int32_t *refit_passes);
+int evplp_rotate_tree(const void *nodes64, int32_t nnodes, const int32_t *tri_index, int32_t nslots, const float *verts9, int32_t ntri, const int32_t *level,
+                      int32_t passes, int32_t *children, float *boxes, int32_t *rotations, int32_t *need0);
 /* The tree EVPLP_BVH_PLOC_GPU builds, stated on the host (no GPU, deterministic): the device builder's steps run serially, with the same
  * Morton key, the same fp32 distance and the same tie rule, so the two produce one tree.  verts9 = 9 floats per triangle; triangles
  * without area (meshBound's rule) are left out.  radius = 1 .. 32 positions searched on either side, search_iterations = 0 .. 128 search
@@ -823,6 +870,10 @@ int evplp_group_transform_mesh(evplp_group *g, int32_t mesh, const float m[12]);
  * (EVPLP_ERR_INVALID) if any rank's differ.  Refused on the caller's thread, the group staying usable, where the plain context refuses. */
 int evplp_group_accel_quality(evplp_group *g, struct evplp_accel_quality *out);
 int evplp_group_set_refit_policy(evplp_group *g, double max_cost_ratio, int32_t rebuild_builder);
+/* evplp_optimize_accel / evplp_set_refit_rotations on every rank (the tree is replicated): rank 0's rotation count is the group's, and a rank
+ * whose count differs is EVPLP_ERR_INVALID, as a differing tree cost is for evplp_group_accel_quality */
+int evplp_group_optimize_accel(evplp_group *g, int32_t passes, int32_t *rotations);
+int evplp_group_set_refit_rotations(evplp_group *g, int32_t passes);
 int evplp_group_path_trace(evplp_group *g, const float camera_pos[3], uint32_t rng_seed, uint32_t max_bounces, int32_t do_accumulate);
 /* evplp_path_trace_batch, routed like evplp_group_path_trace: a strips group runs it on every rank for its own rows (the result equals one
  * context's bit for bit; evplp_set_blocks / evplp_group_rebalance behave as for evplp_group_path_trace), an iterations group on the selected

@@ -19,7 +19,12 @@
       --package-root DIR imports evplp_amd (and its library) from another checkout, for an A/B against it in alternating processes; a
       checkout without evplp_transform_mesh prints the upload rows alone.
 
-usage: python tools/refit_times.py [--reps N] [--tris N] [--res N] [--quality-only | --transform] [--package-root DIR]"""
+  (8) --rotate: tree rotations (evplp_set_refit_rotations, evplp_optimize_accel).  For the five motions of (6): the refitted SAH tree without
+      and with 1, 2 and 4 rotation passes -- rotations taken, SAH cost, the config-#2 gather, and the refit's HIP-event and host time with
+      the passes on -- beside a rebuilt SAH tree and a PLOC rebuild of the same moved scene, all in one process, the gathers of one motion
+      taking turns; then evplp_optimize_accel over fresh device-LBVH and PLOC trees (its call time includes the tree's plan, made once).
+
+usage: python tools/refit_times.py [--reps N] [--tris N] [--res N] [--quality-only | --transform | --rotate] [--package-root DIR]"""
 import argparse
 import math
 import os
@@ -204,6 +209,90 @@ def quality_table(sd, a, chairs, orig, small, large):
         print("    %s | %.2f | %.2f | %.2f | %.3f | %.2f | %.2f | %.3f" % r)
 
 
+def gather_pass(c, sd, it):
+    """one config-#2 gather (time_gather's pass); returns its HIP-event ms"""
+    bsr, total, _ = c.scene_metrics()
+    radius = 0.003 * bsr
+    kw = dict(camera_pos=sd.cam_origin, mis_mode="one", pdf_mc=1.0 / math.pi / radius ** 2, clamping_value=1.0 / total, photon_radius=radius, vsl_radius=0.05 * bsr,
+              vsl_inv_pi_radius2=1 / (math.pi * (0.05 * bsr) ** 2), num_light_paths=NL, num_vpl_light_paths=NL, photons_per_path=P, do_accumulate=1)
+    c.primary((0, 0)); c.trace_light_paths(it); c.gather_vpl(ev.frame_params(rng_seed=it, **kw)); c.synchronize()
+    return c.pass_stats(ev.PASS_GATHER_VPL)["ms"]
+
+
+def gathers_alternating(ctxs, sd, reps):
+    """the gather over every context of `ctxs` {name: context}, the contexts taking turns within every repetition; {name: [ms]}"""
+    ms = {n: [] for n in ctxs}
+    for it in range(reps + 1):
+        for n, c in ctxs.items():
+            t = gather_pass(c, sd, it)
+            if it:
+                ms[n].append(t)
+    return ms
+
+
+def rotate_table(sd, a, chairs, orig, small, large):
+    """(8) --rotate: tree rotations inside the refit (evplp_set_refit_rotations), on the aged tree and on fresh trees"""
+    q = lambda f, xs: sorted(xs)[min(len(xs) - 1, int(round(f * (len(xs) - 1))))]
+    print("(8) tree rotations inside the refit.  Per motion: the refitted SAH tree without and with 1, 2 and 4 rotation passes, beside a rebuilt SAH tree and a")
+    print("    PLOC rebuild of the same moved scene; the gathers of one motion take turns within every repetition.  A gather difference inside the p10 - p90")
+    print("    spread of the refitted-only tree's gather is no difference.")
+    for name, meshes, verts in chair_motions(sd, chairs, orig, small, large):
+        print(f"  {name}: {len(meshes)} meshes moved")
+        ctxs, notes = {}, {}
+        for k in (0, 1, 2, 4):
+            c = context(sd, a.res, ev.BVH_SAH)
+            built = c.accel_quality()["cost"]
+            c.set_refit_rotations(k)
+            for m in meshes:
+                c.update_mesh(m, verts[m])
+            c.refit_accel()
+            n = f"refitted SAH + {k} passes" if k else "refitted SAH"
+            ctxs[n] = c
+            notes[n] = (c.rotation_info()["last_call"], c.accel_quality()["cost"], built, c.accel_info()["stack4_entries"])
+        for n, b in (("rebuilt SAH", ev.BVH_SAH), ("rebuilt PLOC", ev.BVH_PLOC_GPU)):
+            ctxs[n] = context(sd, a.res, b, verts)
+            notes[n] = (0, ctxs[n].accel_quality()["cost"], 0.0, ctxs[n].accel_info()["stack4_entries"])
+        ms = gathers_alternating(ctxs, sd, a.reps)
+        base = ms["refitted SAH"]
+        floor = 0.5 * (q(0.9, base) - q(0.1, base))
+        for n in ctxs:
+            d = statistics.median(ms[n]) - statistics.median(base)
+            verdict = "" if n == "refitted SAH" else ("   no difference (within +- %.2f ms)" % floor if abs(d) <= floor else "   %+.2f ms against the refitted-only tree" % d)
+            print(f"      {n:26s} rotations {notes[n][0]:6d}   cost {notes[n][1]:9.2f}   stack4 {notes[n][3]:3d}   gather ms {spread(ms[n])}{verdict}")
+        # what the refit costs with the passes on: the meshes go back and forth, every refit moves them (and rotates what it finds)
+        for k in (0, 1, 2, 4):
+            c = ctxs[f"refitted SAH + {k} passes" if k else "refitted SAH"]
+            ev_ms, wall, rot = [], [], []
+            for r in range(a.reps + 2):
+                src = orig if r % 2 == 0 else verts
+                for m in meshes:
+                    c.update_mesh(m, src[m])
+                c.synchronize()
+                t0 = time.perf_counter(); c.refit_accel(); t1 = time.perf_counter()
+                if r >= 2:
+                    ev_ms.append(c.refit_info()["last_refit_ms"]); wall.append((t1 - t0) * 1e3); rot.append(c.rotation_info()["last_call"] if k else 0)
+            print(f"      refit with {k} passes: device ms {spread(ev_ms)}   host call ms {spread(wall)}   rotations per refit, median {int(statistics.median(rot))}")
+        for c in ctxs.values():
+            c.close()
+    print("  fresh trees of the unmoved scene: evplp_optimize_accel over a device LBVH and a PLOC tree, beside the SAH tree")
+    ctxs, notes = {}, {}
+    ctxs["SAH"] = context(sd, a.res, ev.BVH_SAH)
+    notes["SAH"] = (0, ctxs["SAH"].accel_quality()["cost"], 0.0)
+    for bn, b in (("device LBVH", GPU_BUILDER), ("PLOC", ev.BVH_PLOC_GPU)):
+        for k in (0, 1, 2, 4):
+            c = context(sd, a.res, b)
+            c.synchronize()
+            t0 = time.perf_counter(); n = c.optimize_accel(k) if k else 0; t1 = time.perf_counter()
+            name = f"{bn} + {k} passes" if k else bn
+            ctxs[name] = c
+            notes[name] = (n, c.accel_quality()["cost"], (t1 - t0) * 1e3)
+    ms = gathers_alternating(ctxs, sd, a.reps)
+    for n in ctxs:
+        print(f"      {n:26s} rotations {notes[n][0]:6d}   cost {notes[n][1]:9.2f}   optimize call ms {notes[n][2]:8.3f}   gather ms {spread(ms[n])}")
+    for c in ctxs.values():
+        c.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=40)
@@ -211,6 +300,7 @@ def main():
     ap.add_argument("--res", type=int, default=1024)
     ap.add_argument("--quality-only", action="store_true", help="parts (5) and (6) alone")
     ap.add_argument("--transform", action="store_true", help="part (7) alone")
+    ap.add_argument("--rotate", action="store_true", help="part (8) alone: tree rotations inside the refit")
     ap.add_argument("--package-root", default=None, help="import evplp_amd from this checkout instead of the tool's own")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory(prefix="evplp_refit_") as d:
@@ -226,6 +316,9 @@ def main():
         ang = rng.rand() * 2 * math.pi
         large[k] = (orig[k] + np.array([math.cos(ang), math.sin(ang), 0.0], F)).astype(F)
 
+    if a.rotate:
+        rotate_table(sd, a, chairs, orig, small, large)
+        return
     if a.transform:
         print(f"library: {ev.LIB_PATH}")
         one = chairs[:1] if chairs else [0]
