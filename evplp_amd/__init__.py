@@ -91,6 +91,24 @@ class DenoiseParams(C.Structure):
                 ("reserved", C.c_int32 * 4)]
 
 
+class TemporalParams(C.Structure):
+    """evplp_temporal_params: a zero field is the library's default (max_history 16, normal_cos 0.9)"""
+    _fields_ = [("max_history", C.c_int32), ("normal_cos", C.c_float), ("reserved", C.c_int32 * 6)]
+
+
+class TemporalInfo(C.Structure):
+    """evplp_temporal_info"""
+    _fields_ = [("filtered", C.c_int64), ("reprojected", C.c_int64), ("disoccluded", C.c_int64), ("history_sum", C.c_int64),
+                ("frames_since_reset", C.c_int32), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+
+
+# evplp_temporal_download's planes
+TEMPORAL_HISTORY_U, TEMPORAL_HISTORY_POS, TEMPORAL_HISTORY_NRM, TEMPORAL_PREV_POS, TEMPORAL_PREV_NRM, TEMPORAL_DEBUG_HIT = range(6)
+
+
 class PassStats(C.Structure):
     _fields_ = [("ms", C.c_float), ("pairs", C.c_uint64), ("rays", C.c_uint64), ("usable", C.c_uint64),
                 ("dominant_kernel_ms", C.c_float), ("reserved", C.c_uint32 * 3), ("shaded", C.c_uint64), ("launches", C.c_uint32),
@@ -179,6 +197,11 @@ _SIGNATURES = {
     "evplp_noise_estimate": (C.c_int, [_P, C.c_float, C.c_float, C.c_int32, C.POINTER(C.c_double * 3)]),
     "evplp_noise_variance": (C.c_int, [_P, C.c_float, _P]),
     "evplp_denoise": (C.c_int, [_P, C.c_float, C.c_float, C.c_int32, C.POINTER(DenoiseParams), _P]),
+    "evplp_temporal_enable": (C.c_int, [_P, C.c_int32]),
+    "evplp_temporal_reset": (C.c_int, [_P]),
+    "evplp_denoise_temporal": (C.c_int, [_P, C.c_float, C.c_float, C.c_int32, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), _P, C.POINTER(TemporalInfo)]),
+    "evplp_temporal_download": (C.c_int, [_P, C.c_int32, _P]),
+    "evplp_project_points": (C.c_int, [C.POINTER(Camera), C.c_int32, C.c_int32, _P, C.c_int32, _P]),
     "evplp_adaptive_enable": (C.c_int, [_P, C.c_int32]),
     "evplp_adaptive_enable_pt": (C.c_int, [_P, C.c_int32]),
     "evplp_adaptive_retire": (C.c_int, [_P, C.c_float, C.c_float, C.c_int32, C.c_double, C.c_int32]),
@@ -242,6 +265,10 @@ _SIGNATURES = {
     "evplp_group_noise_estimate": (C.c_int, [_P, C.c_float, C.c_float, C.c_int32, C.POINTER(C.c_double * 3)]),
     "evplp_group_noise_variance": (C.c_int, [_P, C.c_float, _P]),
     "evplp_group_denoise": (C.c_int, [_P, C.c_float, C.c_float, C.c_int32, C.POINTER(DenoiseParams), _P]),
+    "evplp_group_temporal_enable": (C.c_int, [_P, C.c_int32]),
+    "evplp_group_temporal_reset": (C.c_int, [_P]),
+    "evplp_group_denoise_temporal": (C.c_int, [_P, C.c_float, C.c_float, C.c_int32, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), _P, C.POINTER(TemporalInfo)]),
+    "evplp_group_temporal_download": (C.c_int, [_P, C.c_int32, _P]),
     "evplp_group_adaptive_enable": (C.c_int, [_P, C.c_int32]),
     "evplp_group_adaptive_enable_pt": (C.c_int, [_P, C.c_int32]),
     "evplp_group_adaptive_retire": (C.c_int, [_P, C.c_float, C.c_float, C.c_int32, C.c_double, C.c_int32]),
@@ -336,6 +363,32 @@ def _denoise_params(levels, sigma_luminance, sigma_normal, sigma_position) -> De
     if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)):
         raise ValueError(f"denoise: levels must be an int, got {levels!r}")
     return DenoiseParams(int(levels), float(sigma_luminance), float(sigma_normal), float(sigma_position))
+
+
+def _temporal_params(max_history, normal_cos) -> TemporalParams:
+    """evplp_temporal_params from the keyword arguments of denoise_temporal (0 = the default; the library checks the ranges)"""
+    if isinstance(max_history, bool) or not isinstance(max_history, (int, np.integer)):
+        raise ValueError(f"denoise_temporal: max_history must be an int, got {max_history!r}")
+    return TemporalParams(int(max_history), float(normal_cos))
+
+
+def _camera(origin, lookat, up, fovy, aspect) -> Camera:
+    cam = Camera()
+    cam.origin = (C.c_float * 3)(*[float(x) for x in origin]); cam.lookat = (C.c_float * 3)(*[float(x) for x in lookat])
+    cam.up = (C.c_float * 3)(*[float(x) for x in up]); cam.fovy = float(fovy); cam.aspect = float(aspect)
+    return cam
+
+
+def project_points(origin, lookat, up, fovy, aspect, W: int, H: int, pts) -> np.ndarray:
+    """evplp_project_points: the world points (n, 3) on the screen of a camera (set_camera's arguments) at W x H pixels -> (n, 3) float32
+    (x, y, view depth) in pixel-centre coordinates, y from the bottom; depth <= 0: at or behind the eye, x = y = 0.  No GPU."""
+    p = _f32(pts).reshape(-1, 3)
+    out = np.empty_like(p)
+    cam = _camera(origin, lookat, up, fovy, aspect)
+    rc = lib().evplp_project_points(C.byref(cam), int(W), int(H), _ptr(p), p.shape[0], _ptr(out))
+    if rc < 0:
+        raise EvplpError(rc, "evplp_project_points: bad arguments")
+    return out
 
 
 def _fold_iterations(iterations) -> int:
@@ -680,6 +733,32 @@ class Context:
         p = _denoise_params(levels, sigma_luminance, sigma_normal, sigma_position)
         out = np.empty((self.local_rows, self.W, 3), dtype=np.float32)
         self._check(self._lib.evplp_denoise(self._h, float(scale), float(light_scale), int(mask_emitter), C.byref(p), _ptr(out)))
+        return out
+
+    def temporal_enable(self, on=True):
+        """evplp_temporal_enable: the previous pose (36 B per triangle) and the previous-pose texels (32 B per plane pixel); False releases them
+        and the history"""
+        self._check(self._lib.evplp_temporal_enable(self._h, int(bool(on))))
+
+    def temporal_reset(self):
+        """evplp_temporal_reset: the next denoise_temporal behaves as a first call"""
+        self._check(self._lib.evplp_temporal_reset(self._h))
+
+    def denoise_temporal(self, scale, light_scale=1.0, mask_emitter=False, levels=0, sigma_luminance=0, sigma_normal=0, sigma_position=0,
+                         max_history=0, normal_cos=0.0):
+        """denoise() with the temporal accumulation stage in front of the passes (include/evplp.h evplp_denoise_temporal; frames must be
+        independent samples): (float32 (local_rows, W, 3), the dict of evplp_temporal_info)"""
+        p = _denoise_params(levels, sigma_luminance, sigma_normal, sigma_position)
+        t = _temporal_params(max_history, normal_cos)
+        out = np.empty((self.local_rows, self.W, 3), dtype=np.float32)
+        info = TemporalInfo()
+        self._check(self._lib.evplp_denoise_temporal(self._h, float(scale), float(light_scale), int(mask_emitter), C.byref(p), C.byref(t), _ptr(out), C.byref(info)))
+        return out, info.as_dict()
+
+    def temporal_download(self, which: int) -> np.ndarray:
+        """evplp_temporal_download: plane TEMPORAL_* of the last denoise_temporal, float32 (local_rows, W, 4), y = 0 at the bottom"""
+        out = np.empty((self.local_rows, self.W, 4), dtype=np.float32)
+        self._check(self._lib.evplp_temporal_download(self._h, int(which), _ptr(out)))
         return out
 
     def adaptive_enable(self, on=True, path_trace=False, budget=False, gather_budget=False):
@@ -1130,6 +1209,29 @@ class Group:
         p = _denoise_params(levels, sigma_luminance, sigma_normal, sigma_position)
         out = np.empty((self.H, self.W, 3), dtype=np.float32)
         self._check(self._lib.evplp_group_denoise(self._h, float(scale), float(light_scale), int(mask_emitter), C.byref(p), _ptr(out)))
+        return out
+
+    def temporal_enable(self, on=True):
+        """evplp_group_temporal_enable: Context.temporal_enable on every rank"""
+        self._check(self._lib.evplp_group_temporal_enable(self._h, int(bool(on))))
+
+    def temporal_reset(self):
+        self._check(self._lib.evplp_group_temporal_reset(self._h))
+
+    def denoise_temporal(self, scale, light_scale=1.0, mask_emitter=False, levels=0, sigma_luminance=0, sigma_normal=0, sigma_position=0,
+                         max_history=0, normal_cos=0.0):
+        """Context.denoise_temporal for the whole frame: (float32 (H, W, 3), the info dict); strips: one context's bits for any block table"""
+        p = _denoise_params(levels, sigma_luminance, sigma_normal, sigma_position)
+        t = _temporal_params(max_history, normal_cos)
+        out = np.empty((self.H, self.W, 3), dtype=np.float32)
+        info = TemporalInfo()
+        self._check(self._lib.evplp_group_denoise_temporal(self._h, float(scale), float(light_scale), int(mask_emitter), C.byref(p), C.byref(t), _ptr(out), C.byref(info)))
+        return out, info.as_dict()
+
+    def temporal_download(self, which: int) -> np.ndarray:
+        """evplp_group_temporal_download: a history or previous-pose plane of the last denoise_temporal, float32 (H, W, 4)"""
+        out = np.empty((self.H, self.W, 4), dtype=np.float32)
+        self._check(self._lib.evplp_group_temporal_download(self._h, int(which), _ptr(out)))
         return out
 
     def adaptive_enable(self, on=True, path_trace=False, budget=False, gather_budget=False):

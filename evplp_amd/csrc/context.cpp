@@ -235,6 +235,7 @@ extern "C" void evplp_destroy(evplp_context *c) {
     hipFree(c->d_noise); hipFree(c->d_noise_keep); hipFree(c->d_noise_rows);
     hipFree(c->d_adapt_tiles); hipFree(c->d_adapt_snap); hipFree(c->d_adapt_mask);
     hipFree(c->d_dn_var); hipFree(c->d_dn_pack); hipFree(c->d_dn_u);
+    hipFree(c->d_tp_prev_v); hipFree(c->d_tp_prev); hipFree(c->d_tp_prev_frame); hipFree(c->d_tp_hist); hipFree(c->d_tp_counts);
     hipFree(c->d_pt_batch); hipFree(c->d_pt_first); hipFree(c->d_pt_table); hipFree(c->d_tile_noise);
     for (int i = 0; i < EVPLP_PASS_COUNT; i++) {
         if (c->ev_begin[i]) hipEventDestroy(c->ev_begin[i]);
@@ -321,19 +322,28 @@ extern "C" int evplp_set_arealight(evplp_context *c, int32_t mesh, const float i
     c->accel_built = false;
     return EVPLP_OK;
 }
-extern "C" int evplp_set_camera(evplp_context *c, const evplp_camera *cam) {
-    CTX_CHECK(c);
-    if (!cam) { c->set_error("evplp_set_camera: null"); return EVPLP_ERR_INVALID; }
-    // glm::lookAt (RH) basis + glm::perspective parameters (rt/rtcommon.h:586-591)
+// glm::lookAt (RH) basis + glm::perspective parameters (rt/rtcommon.h:586-591); evplp_set_camera and evplp_project_points
+static void camera_basis(const evplp_camera *cam, CamBasis *out) {
     auto norm = [](float *v) { float inv = 1.0f / std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); v[0] *= inv; v[1] *= inv; v[2] *= inv; };
     float f[3] = { cam->lookat[0] - cam->origin[0], cam->lookat[1] - cam->origin[1], cam->lookat[2] - cam->origin[2] };
     norm(f);
     float s[3] = { f[1] * cam->up[2] - f[2] * cam->up[1], f[2] * cam->up[0] - f[0] * cam->up[2], f[0] * cam->up[1] - f[1] * cam->up[0] };
     norm(s);
     float u[3] = { s[1] * f[2] - s[2] * f[1], s[2] * f[0] - s[0] * f[2], s[0] * f[1] - s[1] * f[0] };
-    std::memset(&c->cam, 0, sizeof(c->cam));
-    std::memcpy(c->cam.eye, cam->origin, 12); std::memcpy(c->cam.s, s, 12); std::memcpy(c->cam.u, u, 12); std::memcpy(c->cam.f, f, 12);
-    c->cam.tan_half = std::tan(cam->fovy / 2.0f); c->cam.aspect = cam->aspect;
+    std::memset(out, 0, sizeof(*out));
+    std::memcpy(out->eye, cam->origin, 12); std::memcpy(out->s, s, 12); std::memcpy(out->u, u, 12); std::memcpy(out->f, f, 12);
+    out->tan_half = std::tan(cam->fovy / 2.0f); out->aspect = cam->aspect;
+}
+extern "C" int evplp_project_points(const evplp_camera *cam, int32_t W, int32_t H, const float *xyz, int32_t n, float *out_xyd) {
+    if (!cam || W < 1 || H < 1 || n < 0 || (n > 0 && (!xyz || !out_xyd))) return EVPLP_ERR_INVALID;
+    CamBasis b; camera_basis(cam, &b);
+    for (int32_t i = 0; i < n; i++) { float o[3]; evplp::project_point(b, W, H, xyz + 3 * (size_t)i, o); std::memcpy(out_xyd + 3 * (size_t)i, o, 12); }
+    return EVPLP_OK;
+}
+extern "C" int evplp_set_camera(evplp_context *c, const evplp_camera *cam) {
+    CTX_CHECK(c);
+    if (!cam) { c->set_error("evplp_set_camera: null"); return EVPLP_ERR_INVALID; }
+    camera_basis(cam, &c->cam);
     c->cam_in = *cam;
     c->camera_set = true; c->primary_cuts_valid = false;
     return EVPLP_OK;
@@ -542,7 +552,7 @@ static int build_accel(evplp_context *c, int policy_builder) {
     if ((rc = upload_array(c, cdf.data(), cdf.size(), &c->sc.light_cdf))) return rc;
     c->sc.light_first = light_first; c->sc.light_count = light_count; c->sc.light_area = sum;
     std::memcpy(c->sc.light_intensity, c->light_scaled, 16); std::memcpy(c->sc.light_unscaled, c->light_unscaled, 16);
-    c->accel_built = true; c->primary_cuts_valid = false;
+    c->accel_built = true; c->primary_cuts_valid = false; c->primary_current = false;
     c->mesh_dirty.assign(c->meshes.size(), 0); c->scene_dirty = false;
     c->built_cost = 0.0; c->built_cost_known = false; c->refits_since_build = 0; c->rotations_since_build = 0;
     if (c->policy_ratio > 0.0) {            // (a policy compares against the cost of the tree as built: one small launch and a wait)
@@ -833,7 +843,7 @@ extern "C" int evplp_refit_accel(evplp_context *c) {
     if (c->aux_stream) HIP_TRY(c, hipStreamWaitEvent(c->aux_stream, c->ev_refit_staged, 0));      // (light paths given to the second stream from here on see the new tree)
     HIP_TRY(c, hipGetLastError());
     c->accel_pad = pad; c->refit_timed = timed; c->refit_stages_timed = stages; c->refit_count++; c->refits_since_build++;
-    c->primary_cuts_valid = false; c->tile_box_valid = false;
+    c->primary_cuts_valid = false; c->tile_box_valid = false; c->primary_current = false;
     std::fill(c->mesh_dirty.begin(), c->mesh_dirty.end(), 0); c->scene_dirty = false;
     if (c->policy_ratio > 0.0) {
         // The policy (evplp_set_refit_policy): the cost of the refitted tree against the cost of the tree as built.  One small launch and
@@ -950,7 +960,7 @@ extern "C" int evplp_optimize_accel(evplp_context *c, int32_t passes, int32_t *r
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     rotate_finish(c, passes);
-    c->primary_cuts_valid = false; c->tile_box_valid = false;
+    c->primary_cuts_valid = false; c->tile_box_valid = false; c->primary_current = false;
     c->last_action = 3;
     if (rotations) *rotations = c->rotations_last;
     return EVPLP_OK;
@@ -1166,6 +1176,9 @@ extern "C" int evplp_primary(evplp_context *c, const float jitter[2], int32_t cl
     if ((rc = pass_begin(c, EVPLP_PASS_PRIMARY))) return rc;
     launch_primary(a, c->stream);
     c->tile_box_valid = !c->gbuf_pos_exposed;
+    // (evplp_denoise_temporal repeats this walk: its jitter and flags, and whether the position plane in memory is this pass's own)
+    c->primary_jitter[0] = a.jitter[0]; c->primary_jitter[1] = a.jitter[1]; c->primary_flags = clear_light;
+    c->primary_current = c->buf_owned[EVPLP_BUF_GBUF_POSITION] && !c->gbuf_pos_exposed;
     c->stats_host[EVPLP_PASS_PRIMARY].rays = 2ull * (uint64_t)c->st.W * c->rows_in_image;
     return pass_end(c, EVPLP_PASS_PRIMARY);
 }
@@ -1960,6 +1973,204 @@ extern "C" int evplp_denoise(evplp_context *c, float scale, float ls, int32_t ma
     return EVPLP_OK;
 }
 
+// ---- temporal accumulation in front of the a-trous passes (include/evplp.h evplp_denoise_temporal, kernels_temporal.hip)
+namespace evplp {
+bool temporal_settings(const evplp_temporal_params *p, TemporalSettings *out, char *why, size_t cap) {
+    TemporalSettings t{ 16, 0.9f };
+    if (p) {
+        if (p->max_history != 0) t.max_history = p->max_history;
+        if (!std::isfinite(p->normal_cos)) { std::snprintf(why, cap, "normal_cos must be in (0, 1] (0 = the default 0.9), not %g", (double)p->normal_cos); return false; }
+        if (p->normal_cos != 0.0f) t.normal_cos = p->normal_cos;
+    }
+    if (t.max_history < 1 || t.max_history > 1024) { std::snprintf(why, cap, "max_history must be 1..1024 (0 = the default 16), not %d", t.max_history); return false; }
+    if (!(t.normal_cos > 0.0f) || t.normal_cos > 1.0f) { std::snprintf(why, cap, "normal_cos must be in (0, 1] (0 = the default 0.9), not %g", (double)t.normal_cos); return false; }
+    *out = t;
+    return true;
+}
+bool temporal_check(evplp_context *c, const char *name, bool needs_primary) {
+    if (!c->tp_on) { c->set_error("%s: temporal accumulation is off (evplp_temporal_enable)", name); return false; }
+    if (!needs_primary) return true;
+    if (c->gbuf_pos_exposed || !c->buf_owned[EVPLP_BUF_GBUF_POSITION]) {
+        c->set_error("%s: EVPLP_BUF_GBUF_POSITION is bound or exposed to the caller: the previous-pose walk cannot vouch for a plane it did not write", name);
+        return false;
+    }
+    if (!c->primary_current) {
+        c->set_error("%s: no evplp_primary has written the G-buffer since the last evplp_build_accel / evplp_refit_accel / upload of the position plane", name);
+        return false;
+    }
+    return true;
+}
+void temporal_forget(evplp_context *c) { c->tp_frames = 0; }
+static void temporal_release(evplp_context *c) {
+    hipFree(c->d_tp_prev_v); hipFree(c->d_tp_prev); hipFree(c->d_tp_prev_frame); hipFree(c->d_tp_hist); hipFree(c->d_tp_counts);
+    c->d_tp_prev_v = nullptr; c->d_tp_prev = c->d_tp_prev_frame = nullptr; c->d_tp_hist = nullptr; c->d_tp_counts = nullptr;
+    c->tp_tris = 0; c->tp_hist_px = 0; c->tp_count_slots = 0; c->tp_frames = 0; c->tp_cur = 0; c->tp_on = false;
+}
+static int temporal_alloc(evplp_context *c, void **p, size_t bytes) {
+    if (*p) return EVPLP_OK;
+    const hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16));
+    if (e == hipSuccess) return EVPLP_OK;
+    (void)hipGetLastError(); *p = nullptr;
+    c->set_error("evplp_denoise_temporal: cannot allocate %zu bytes: %s", bytes, hipGetErrorString(e));
+    return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP;
+}
+// the previous pose follows the scene's triangle count: another count forgets the history and makes the array anew
+int temporal_pose_array(evplp_context *c) {
+    if (c->d_tp_prev_v && c->tp_tris == c->scene_tris) return EVPLP_OK;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    hipFree(c->d_tp_prev_v); c->d_tp_prev_v = nullptr; c->tp_frames = 0;
+    c->tp_tris = c->scene_tris;
+    return temporal_alloc(c, (void **)&c->d_tp_prev_v, sizeof(float) * 9 * (size_t)std::max(c->scene_tris, 1));
+}
+int temporal_enable(evplp_context *c, int32_t on) {
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    if (!on) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        temporal_release(c);
+        return EVPLP_OK;
+    }
+    if (c->tp_on) return EVPLP_OK;
+    int rc = temporal_pose_array(c);
+    if (!rc) rc = temporal_alloc(c, (void **)&c->d_tp_prev, sizeof(TemporalPrev) * (size_t)c->st.W * c->st.local_rows);
+    if (rc) { temporal_release(c); return rc; }
+    c->tp_on = true; c->tp_frames = 0;
+    return EVPLP_OK;
+}
+static void temporal_primary_args(evplp_context *c, PrimaryArgs &a) {
+    std::memset(&a, 0, sizeof(a));
+    a.sc = c->sc; a.st = c->st; a.cam = c->cam;
+    a.jitter[0] = c->primary_jitter[0]; a.jitter[1] = c->primary_jitter[1]; a.clear_light = c->primary_flags;
+    // (the walk starts where evplp_primary's did: from the eye's entry cuts under the same test)
+    if (c->env_cuts != 0 && c->tiles_x * c->tiles_y > 0 && jitter_within_cuts(c, a.jitter)) primary_cuts_into(c, a);
+}
+int temporal_prev_pose(evplp_context *c) {
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    PrimaryArgs a; temporal_primary_args(c, a);
+    launch_prev_pose(a, c->d_tp_prev_v, c->d_tp_prev, nullptr, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return EVPLP_OK;
+}
+int temporal_accumulate(evplp_context *c, DenoisePixel *frame, const TemporalPrev *prev, int rows, const DenoiseSettings &ds, const TemporalSettings &ts, float radius) {
+    const size_t px = std::max<size_t>((size_t)c->st.W * rows, 1);
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    if (c->d_tp_hist && c->tp_hist_px != px) { HIP_TRY(c, hipStreamSynchronize(c->stream)); hipFree(c->d_tp_hist); c->d_tp_hist = nullptr; c->tp_frames = 0; }
+    int rc = temporal_alloc(c, (void **)&c->d_tp_hist, sizeof(float4) * 6 * px);
+    const int slots = temporal_count_slots(c->st.W, rows);
+    if (c->d_tp_counts && c->tp_count_slots < slots) { HIP_TRY(c, hipStreamSynchronize(c->stream)); hipFree(c->d_tp_counts); c->d_tp_counts = nullptr; }
+    if (!rc) rc = temporal_alloc(c, (void **)&c->d_tp_counts, sizeof(uint4) * (size_t)slots);
+    if (rc) return rc;
+    c->tp_hist_px = px; c->tp_count_slots = slots;
+    TemporalArgs a{};
+    a.frame = frame; a.prev = prev; a.px = px;
+    a.h_in = c->d_tp_hist + (size_t)c->tp_cur * 3 * px; a.h_out = c->d_tp_hist + (size_t)(c->tp_cur ^ 1) * 3 * px;
+    a.counts = c->d_tp_counts;
+    a.W = c->st.W; a.rows = rows; a.H = c->st.H; a.has_history = c->tp_frames > 0 ? 1 : 0;
+    a.cam = c->cam; a.prev_cam = c->tp_prev_cam;
+    a.sigma_x_r = ds.sigma_x * radius; a.normal_cos = ts.normal_cos; a.max_history = (float)ts.max_history;
+    launch_temporal_accumulate(a, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    c->tp_cur ^= 1;
+    return EVPLP_OK;
+}
+int temporal_snapshot(evplp_context *c) {
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    launch_pose_snapshot(c->sc.attrs, c->tp_tris, c->d_tp_prev_v, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    c->tp_prev_cam = c->cam;
+    c->tp_frames++;
+    return EVPLP_OK;
+}
+int temporal_info(evplp_context *c, evplp_temporal_info *out) {
+    unsigned long long n[4] = { 0, 0, 0, 0 };
+    std::vector<uint4> slots((size_t)c->tp_count_slots);
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipMemcpyAsync(slots.data(), c->d_tp_counts, sizeof(uint4) * slots.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (const uint4 &s : slots) { n[0] += s.x; n[1] += s.y; n[2] += s.z; n[3] += s.w; }
+    std::memset(out, 0, sizeof(*out));
+    out->filtered = (int64_t)n[0]; out->reprojected = (int64_t)n[1]; out->disoccluded = (int64_t)n[2]; out->history_sum = (int64_t)n[3];
+    out->frames_since_reset = c->tp_frames;
+    return EVPLP_OK;
+}
+} // namespace evplp
+extern "C" int evplp_temporal_enable(evplp_context *c, int32_t on) {
+    CTX_CHECK(c);
+    return evplp::temporal_enable(c, on);
+}
+extern "C" int evplp_temporal_reset(evplp_context *c) {
+    CTX_CHECK(c);
+    if (!c->tp_on) { c->set_error("evplp_temporal_reset: temporal accumulation is off (evplp_temporal_enable)"); return EVPLP_ERR_INVALID; }
+    evplp::temporal_forget(c);
+    return EVPLP_OK;
+}
+extern "C" int evplp_denoise_temporal(evplp_context *c, float scale, float ls, int32_t mask_emitter, const evplp_denoise_params *p,
+                                      const evplp_temporal_params *t, float *out_rgb, evplp_temporal_info *info) {
+    CTX_CHECK(c);
+    const char *name = "evplp_denoise_temporal";
+    evplp::DenoiseSettings ds; evplp::TemporalSettings ts; char why[200];
+    if (!evplp::denoise_settings(p, &ds, why, sizeof why) || !evplp::temporal_settings(t, &ts, why, sizeof why)) { c->set_error("%s: %s", name, why); return EVPLP_ERR_INVALID; }
+    if (!out_rgb) { c->set_error("%s: null output", name); return EVPLP_ERR_INVALID; }
+    if (c->st.strip_count > 1) {
+        c->set_error("%s: a row-strip context (strip_count %d) cannot see its neighbours' rows: use evplp_group_denoise_temporal", name, c->st.strip_count);
+        return EVPLP_ERR_INVALID;
+    }
+    if (!c->accel_built) { c->set_error("%s: no scene (evplp_build_accel)", name); return EVPLP_ERR_INVALID; }
+    if (c->scene_dirty) { c->set_error("%s: vertices were updated (evplp_update_mesh): call evplp_refit_accel or evplp_build_accel first", name); return EVPLP_ERR_INVALID; }
+    int rc = noise_ready(c, name);
+    if (rc) return rc;
+    if (!evplp::temporal_check(c, name, true)) return EVPLP_ERR_INVALID;
+    if ((rc = evplp::temporal_pose_array(c))) return rc;                     // (another triangle count: a first call)
+    if ((rc = evplp::noise_variance_to_device(c, evplp::noise_moments_of(c), (double)c->noise_k, (double)c->noise_b, scale))) return rc;
+    if ((rc = evplp::denoise_keep_variance(c))) return rc;
+    if ((rc = evplp::resolve_to_device(c, scale, scale, ls, mask_emitter, 0, true, false))) return rc;
+    if ((rc = evplp::denoise_prepare(c, (const float4 *)c->buf[EVPLP_BUF_GBUF_POSITION], (const float4 *)c->buf[EVPLP_BUF_GBUF_NORMAL],
+                                     (const float4 *)c->buf[EVPLP_BUF_GBUF_DIFFUSE], (const float4 *)c->buf[EVPLP_BUF_GBUF_PHONG], (const float4 *)c->buf[EVPLP_BUF_LIGHT]))) return rc;
+    if (c->tp_frames > 0) { if ((rc = evplp::temporal_prev_pose(c))) return rc; }
+    else HIP_TRY(c, hipMemsetAsync(c->d_tp_prev, 0, sizeof(evplp::TemporalPrev) * (size_t)c->st.W * c->st.local_rows, c->stream));
+    if ((rc = evplp::temporal_accumulate(c, c->d_dn_pack, c->d_tp_prev, c->st.local_rows, ds, ts, c->bounding_radius))) return rc;
+    if ((rc = evplp::denoise_filter(c, c->d_dn_pack, c->st.local_rows, ds, c->bounding_radius, c->d_rgb))) return rc;
+    if ((rc = evplp::temporal_snapshot(c))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(out_rgb, c->d_rgb, sizeof(float) * 3 * (size_t)c->st.W * c->st.local_rows, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (info) return evplp::temporal_info(c, info);
+    return EVPLP_OK;
+}
+extern "C" int evplp_temporal_download(evplp_context *c, int32_t which, float *out) {
+    CTX_CHECK(c);
+    const char *name = "evplp_temporal_download";
+    if (!out || which < EVPLP_TEMPORAL_HISTORY_U || which > EVPLP_TEMPORAL_DEBUG_HIT) { c->set_error("%s: a null output or an unknown plane %d", name, which); return EVPLP_ERR_INVALID; }
+    if (!evplp::temporal_check(c, name, false)) return EVPLP_ERR_INVALID;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    const size_t px = (size_t)c->st.W * c->st.local_rows;
+    if (which <= EVPLP_TEMPORAL_HISTORY_NRM) {
+        if (!c->d_tp_hist || c->tp_frames == 0 || c->tp_hist_px != std::max<size_t>(px, 1)) { c->set_error("%s: this context holds no history of its planes", name); return EVPLP_ERR_INVALID; }
+        HIP_TRY(c, hipMemcpyAsync(out, c->d_tp_hist + ((size_t)c->tp_cur * 3 + (size_t)which) * c->tp_hist_px, sizeof(float4) * px, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return EVPLP_OK;
+    }
+    if (which == EVPLP_TEMPORAL_DEBUG_HIT) {
+        if (!c->accel_built || c->scene_dirty) { c->set_error("%s: no scene, or vertices were updated since its last refit", name); return EVPLP_ERR_INVALID; }
+        if (!evplp::temporal_check(c, name, true)) return EVPLP_ERR_INVALID;
+        float4 *d = nullptr;
+        HIP_TRY(c, hipMalloc((void **)&d, sizeof(float4) * std::max<size_t>(px, 1)));
+        HIP_TRY(c, hipMemsetAsync(d, 0, sizeof(float4) * std::max<size_t>(px, 1), c->stream));
+        PrimaryArgs a; evplp::temporal_primary_args(c, a);
+        launch_prev_pose(a, c->d_tp_prev_v, nullptr, d, c->stream);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(out, d, sizeof(float4) * px, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        hipFree(d);
+        if (e != hipSuccess) { c->set_error("%s: %s", name, hipGetErrorString(e)); return EVPLP_ERR_HIP; }
+        return EVPLP_OK;
+    }
+    std::vector<evplp::TemporalPrev> host(px);
+    HIP_TRY(c, hipMemcpyAsync(host.data(), c->d_tp_prev, sizeof(evplp::TemporalPrev) * px, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < px; i++) std::memcpy(out + 4 * i, which == EVPLP_TEMPORAL_PREV_POS ? &host[i].pos : &host[i].nrm, 16);
+    return EVPLP_OK;
+}
+
 // ---- adaptive gather: tiles retire once their estimated noise is low enough (include/evplp.h evplp_adaptive_*)
 static void release_adapt(evplp_context *c) {
     hipFree(c->d_adapt_tiles); hipFree(c->d_adapt_snap); hipFree(c->d_adapt_mask);
@@ -2197,7 +2408,7 @@ extern "C" int evplp_set_blocks(evplp_context *c, const int32_t *image_blocks, i
         c->st.blocks = c->d_blocks; c->st.blocks_host = c->blocks_host.data();
     } else { c->st.blocks = nullptr; c->st.blocks_host = nullptr; c->blocks_host.clear(); }       // back to block b -> rank b % strip_count
     count_rows_in_image(c);
-    c->primary_cuts_valid = false; c->tile_box_valid = false;
+    c->primary_cuts_valid = false; c->tile_box_valid = false; c->primary_current = false;
     return evplp_clear_accumulators(c);
 }
 extern "C" int evplp_get_blocks(evplp_context *c, int32_t *image_blocks, int32_t capacity) {
@@ -2262,7 +2473,7 @@ extern "C" int evplp_buffer_info(evplp_context *c, int32_t which, void **ptr, si
     if (which < 0 || which >= EVPLP_BUF_COUNT) { c->set_error("evplp_buffer_info: bad buffer id %d", which); return EVPLP_ERR_INVALID; }
     if (ptr) {
         *ptr = c->buf[which];
-        if (which == EVPLP_BUF_GBUF_POSITION) { c->gbuf_pos_exposed = true; c->tile_box_valid = false; }
+        if (which == EVPLP_BUF_GBUF_POSITION) { c->gbuf_pos_exposed = true; c->tile_box_valid = false; c->primary_current = false; }
         if (which >= EVPLP_BUF_GBUF_POSITION && which <= EVPLP_BUF_GBUF_PHONG) c->gbuf_exposed = true;
         if (which == EVPLP_BUF_RECORDS) c->records_exposed = true;       // the pointer must stay the record buffer: no double buffering
     }
@@ -2279,7 +2490,7 @@ extern "C" int evplp_bind_buffer(evplp_context *c, int32_t which, void *ptr, siz
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (c->buf_owned[which]) hipFree(c->buf[which]);
     c->buf[which] = ptr; c->buf_owned[which] = false;
-    if (which == EVPLP_BUF_GBUF_POSITION) { c->gbuf_pos_exposed = true; c->tile_box_valid = false; }
+    if (which == EVPLP_BUF_GBUF_POSITION) { c->gbuf_pos_exposed = true; c->tile_box_valid = false; c->primary_current = false; }
     if (which >= EVPLP_BUF_GBUF_POSITION && which <= EVPLP_BUF_GBUF_PHONG) c->gbuf_exposed = true;
     return EVPLP_OK;
 }
@@ -2299,7 +2510,7 @@ extern "C" int evplp_upload(evplp_context *c, int32_t which, const void *src, si
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     HIP_TRY(c, hipMemcpyAsync(c->buf[which], src, bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (which == EVPLP_BUF_GBUF_POSITION) c->tile_box_valid = false;
+    if (which == EVPLP_BUF_GBUF_POSITION) { c->tile_box_valid = false; c->primary_current = false; }
     return EVPLP_OK;
 }
 

@@ -81,6 +81,25 @@ int denoise_prepare(evplp_context *c, const float4 *pos, const float4 *nrm, cons
 // the a-trous passes and the remodulation over a frame of W x rows packed pixels on this context's device -> out_rgb (device, 3 floats per
 // pixel; stream order).  radius: the scene's bounding-sphere radius
 int denoise_filter(evplp_context *c, const DenoisePixel *frame, int rows, const DenoiseSettings &ds, float radius, float *out_rgb);
+// evplp_denoise_temporal (context.cpp), for the group's workers as well.  The parameters with the defaults filled in, checked like
+// denoise_settings.
+struct TemporalSettings { int32_t max_history; float normal_cos; };
+bool temporal_settings(const evplp_temporal_params *p, TemporalSettings *out, char *why, size_t cap);
+// what the call refuses on one context beyond evplp_denoise's refusals (name: the entry point): false and the reason in c's error
+bool temporal_check(evplp_context *c, const char *name, bool needs_primary);
+int temporal_enable(evplp_context *c, int32_t on);
+// the previous-pose array follows the scene's triangle count: another count makes it anew and forgets the history (waits then)
+int temporal_pose_array(evplp_context *c);
+// this context's hits evaluated on the previous pose -> d_tp_prev (stream order; needs tp_frames > 0)
+int temporal_prev_pose(evplp_context *c);
+// the accumulation stage over a frame of W x rows packed pixels with the previous-pose texels `prev` of the same pixels, on the context that
+// filters (stream order): frame[i].u becomes the accumulated (u, s), the other history becomes the current one; counts to the device
+int temporal_accumulate(evplp_context *c, DenoisePixel *frame, const TemporalPrev *prev, int rows, const DenoiseSettings &ds, const TemporalSettings &ts, float radius);
+// the end of a successful call: pose and camera become the previous ones (stream order)
+int temporal_snapshot(evplp_context *c);
+// the last call's counts (waits)
+int temporal_info(evplp_context *c, evplp_temporal_info *out);
+void temporal_forget(evplp_context *c);
 }
 
 struct evplp_context {
@@ -236,6 +255,18 @@ struct evplp_context {
     // the two (u, s) planes of the a-trous passes [2][dn_u_px] (the frame the context filters: its planes, or a group's whole image on rank 0);
     // allocated on the first call, kept until evplp_destroy
     float *d_dn_var = nullptr; evplp::DenoisePixel *d_dn_pack = nullptr; float4 *d_dn_u = nullptr; size_t dn_u_px = 0;
+    // evplp_primary's jitter and light flags of its last call (evplp_path_trace_batch ends with one), for prev_pose_kernel to repeat that walk;
+    // primary_current: that pass wrote the G-buffer in memory and nothing has touched the tree or the position plane since (a build, a refit,
+    // evplp_upload / evplp_bind_buffer of EVPLP_BUF_GBUF_POSITION clear it)
+    float primary_jitter[2] = {}; int32_t primary_flags = 0; bool primary_current = false;
+    // evplp_temporal_enable (tp_on): the previous pose [9 * tp_tris] floats and the previous-pose texels of the planes [W * local_rows]
+    // (kernels.h TemporalPrev), both made by the enable; the camera of the previous call.  The context that filters also holds the two
+    // histories [2][3][tp_hist_px] float4 (tp_cur: the one the last call wrote), the stage's counts per workgroup, and -- a group's rank 0 under
+    // strips -- the assembled previous-pose texels of the frame; made by its first call.  tp_frames: successful calls since the last reset
+    // (0: the next call is a first call).  All released by evplp_temporal_enable(ctx, 0) and evplp_destroy.
+    bool tp_on = false; float *d_tp_prev_v = nullptr; int32_t tp_tris = 0; evplp::TemporalPrev *d_tp_prev = nullptr, *d_tp_prev_frame = nullptr;
+    evplp::CamBasis tp_prev_cam{}; float4 *d_tp_hist = nullptr; size_t tp_hist_px = 0; int tp_cur = 0; int32_t tp_frames = 0;
+    uint4 *d_tp_counts = nullptr; int tp_count_slots = 0;           // (one slot per workgroup of the stage's last launch)
 
     char error[512] = "";
     void set_error(const char *fmt, ...);

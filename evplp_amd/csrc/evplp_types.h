@@ -231,6 +231,29 @@ __host__ __device__ inline void transform_point(const float m[12], const float p
         out[r] = ((a + b) + c) + m[4 * r + 3];
     }
 }
+// ---- evplp_project_points / evplp_denoise_temporal: a world point on the screen of a camera, in pixel-centre coordinates (x to the right, y
+// from the bottom: pixel (i, j) has its centre at (i, j)) and its view depth.  fp32, every product and every sum rounds on its own, in this
+// order, and nothing is fused:
+//   d = p - eye;  z = (d.x f.x + d.y f.y) + d.z f.z;  a = (d.x s.x + d.y s.y) + d.z s.z;  b = (d.x u.x + d.y u.y) + d.z u.z
+//   cx = (a / z) / (aspect * tan_half);  cy = (b / z) / tan_half;  x = ((cx + 1) * W) / 2 - 0.5;  y = ((cy + 1) * H) / 2 - 0.5
+// out = { x, y, z } and true; z <= 0 (or not a number): out = { 0, 0, z } and false -- the point is at or behind the eye.  The host entry
+// point and temporal_accumulate_kernel (kernels_temporal.hip) both call this and nothing else, and a test restates it in numpy.
+__host__ __device__ inline bool project_point(const CamBasis &cam, int32_t W, int32_t H, const float p[3], float out[3]) {
+#pragma clang fp contract(off)
+    const float dx = p[0] - cam.eye[0], dy = p[1] - cam.eye[1], dz = p[2] - cam.eye[2];
+    const float zx = dx * cam.f[0], zy = dy * cam.f[1], zz = dz * cam.f[2];
+    const float z = (zx + zy) + zz;
+    out[0] = 0.0f; out[1] = 0.0f; out[2] = z;
+    if (!(z > 0.0f)) return false;
+    const float ax = dx * cam.s[0], ay = dy * cam.s[1], az = dz * cam.s[2];
+    const float bx = dx * cam.u[0], by = dy * cam.u[1], bz = dz * cam.u[2];
+    const float a = (ax + ay) + az, b = (bx + by) + bz;
+    const float at = cam.aspect * cam.tan_half;
+    const float cx = (a / z) / at, cy = (b / z) / cam.tan_half;
+    const float sx = (cx + 1.0f) * (float)W, sy = (cy + 1.0f) * (float)H;
+    out[0] = sx / 2.0f - 0.5f; out[1] = sy / 2.0f - 0.5f;
+    return true;
+}
 // ---- tree rotations inside the refit sweep (Kensler 2008; Kopta et al. 2012): evplp_optimize_accel / evplp_set_refit_rotations on the device
 // (refit_rotate_level_kernel, bvh_gpu.hip) and evplp_rotate_tree on the host (host/rotate.cpp) both decide with rotate_choice and count the
 // four-wide walk's stack with rotate_need, and with nothing else.  A box is lo[3] then hi[3], exact and unpadded.

@@ -66,7 +66,8 @@ struct Rccl {
 };
 
 enum Op { OP_QUIT = 0, OP_CLEAR, OP_SYNC, OP_PRIMARY, OP_TRACE, OP_GATHER, OP_SPLAT, OP_PATH_TRACE, OP_PRESENT, OP_LOAD_SCENE, OP_SET_PROXY, OP_ASSEMBLE, OP_REDUCE, OP_SET_REFERENCE, OP_FRAME_ERROR,
-          OP_NOISE_TRACK, OP_NOISE_FOLD, OP_NOISE_POOL, OP_NOISE_ROWS, OP_NOISE_VARIANCE, OP_ADAPT_ENABLE, OP_ADAPT_RETIRE, OP_DENOISE_PREP, OP_DENOISE_FILTER, OP_PATH_TRACE_BATCH, OP_ADAPT_SET_BUDGETS, OP_ADAPT_TILE_NOISE, OP_UPDATE_MESH, OP_TRANSFORM_MESH, OP_REFIT, OP_ACCEL_QUALITY, OP_REFIT_POLICY, OP_OPTIMIZE_ACCEL, OP_REFIT_ROTATIONS };
+          OP_NOISE_TRACK, OP_NOISE_FOLD, OP_NOISE_POOL, OP_NOISE_ROWS, OP_NOISE_VARIANCE, OP_ADAPT_ENABLE, OP_ADAPT_RETIRE, OP_DENOISE_PREP, OP_DENOISE_FILTER, OP_PATH_TRACE_BATCH, OP_ADAPT_SET_BUDGETS, OP_ADAPT_TILE_NOISE, OP_UPDATE_MESH, OP_TRANSFORM_MESH, OP_REFIT, OP_ACCEL_QUALITY, OP_REFIT_POLICY, OP_OPTIMIZE_ACCEL, OP_REFIT_ROTATIONS,
+          OP_TEMPORAL_ENABLE, OP_TEMPORAL_RESET, OP_TEMPORAL_POSE, OP_TEMPORAL_SNAPSHOT };
 // One posted call, copied into the ring by assignment: plain data (pointers must stay valid until the caller has drained: load_scene, set_proxy,
 // resolve do) but for `batch`, a shared pointer -- so every post and every worker-side copy of a command pays one atomic reference count, null or not.
 struct Cmd {
@@ -151,6 +152,12 @@ struct evplp_group {
     evplp::DenoisePixel *d_dn_frame = nullptr;
     int last_primary = 0;
     float4 *d_dn_guides = nullptr;
+    // evplp_group_denoise_temporal (temporal_on: enabled on every rank; caller's thread).  Strips: per rank [n][chunk rows * W] previous-pose
+    // texels (kernels.h TemporalPrev) all-gathered beside the packed pixels; rank 0 assembles them into its context's d_tp_prev_frame and keeps
+    // the history in image layout (its context's d_tp_hist), so a rebalance between two frames does not disturb it.  Iterations: rank 0 reads
+    // the texels of the rank of the last primary.
+    bool temporal_on = false;
+    std::vector<float *> d_tp_recv;
     size_t plane_px = 0;                    // W * local_rows: the pixels of one accumulator plane
     std::vector<float4 *> d_sum;            // per rank: [3][plane_px] VPL, photon and light planes reduced over the ranks (the first reduction)
     std::vector<float4 *> d_stage;          // per rank, RCCL only: [n][plane_px] one plane of every rank (all-gathered)
@@ -327,6 +334,13 @@ static evplp::NoiseMoments noise_pooled(const evplp_group *g, const evplp_contex
 // evplp_group_denoise.  Strips (every rank, then the all-gather in worker_run): this rank's variance, composite and packed pixels.
 // Iterations (rank 0, behind the pooled variance and the reduction): the packed pixels of the reduced composite and light plane with the
 // guides of rank cmd.i[2], copied to rank 0's device first when that is another GPU.
+// this context's previous-pose texels (zeros on a first call), stream order
+static int worker_temporal_pose(evplp_context *c) {
+    if (c->tp_frames > 0) return evplp::temporal_prev_pose(c);
+    const hipError_t e = hipMemsetAsync(c->d_tp_prev, 0, sizeof(evplp::TemporalPrev) * (size_t)c->st.W * c->st.local_rows, c->stream);
+    if (e != hipSuccess) { c->set_error("evplp_group_denoise_temporal: %s", hipGetErrorString(e)); return EVPLP_ERR_HIP; }
+    return EVPLP_OK;
+}
 static int worker_denoise_prep(Worker *w, const Cmd &cmd) {
     evplp_group *g = w->g; const int r = w->rank; evplp_context *c = g->ctx[(size_t)r];
     const float4 *gb[4]; const float4 *light;
@@ -351,7 +365,9 @@ static int worker_denoise_prep(Worker *w, const Cmd &cmd) {
         }
         light = g->d_sum[0] + 2 * px;
     }
-    return evplp::denoise_prepare(c, gb[0], gb[1], gb[2], gb[3], light);
+    rc = evplp::denoise_prepare(c, gb[0], gb[1], gb[2], gb[3], light);
+    if (rc >= 0 && cmd.i[1] && !g->iterations) rc = worker_temporal_pose(c);      // (evplp_group_denoise_temporal: this rank's rows on the previous pose)
+    return rc;
 }
 // rank 0: the frame of packed pixels (strips: assembled from the all-gathered rows), the passes, the frame to the caller (cmd.out)
 static int worker_denoise_filter(Worker *w, const Cmd &cmd) {
@@ -370,7 +386,28 @@ static int worker_denoise_filter(Worker *w, const Cmd &cmd) {
                                       (float *)g->d_dn_frame, c->stream, evplp::kDenoiseFloats);
         frame = g->d_dn_frame; rows = c->st.H; out = g->d_assembled;
     }
-    int rc = evplp::denoise_filter(c, frame, rows, ds, c->bounding_radius, out);
+    int rc;
+    if (cmd.i[1]) {            // evplp_group_denoise_temporal: the accumulation stage in front of the passes (i[2] = max_history, f[3] = normal_cos, u[0] = the texels' rank)
+        const evplp::TemporalPrev *prev = c->d_tp_prev;
+        if (!g->iterations) {
+            if (!c->d_tp_prev_frame) e = hipMalloc((void **)&c->d_tp_prev_frame, sizeof(evplp::TemporalPrev) * frame_px);
+            if (e != hipSuccess) { (void)hipGetLastError(); c->d_tp_prev_frame = nullptr; c->set_error("evplp_group_denoise_temporal: %s", hipGetErrorString(e)); return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP; }
+            evplp::launch_assemble_strips(c->st, g->n, g->owner.empty() ? nullptr : g->d_owner, (int)(g->strip_floats / ((size_t)c->st.W * 3)), g->d_tp_recv[0],
+                                          (float *)c->d_tp_prev_frame, c->stream, evplp::kTemporalPrevFloats);
+            prev = c->d_tp_prev_frame;
+        } else if (cmd.u[0] != 0) {
+            const evplp_context *src = g->ctx[(size_t)cmd.u[0]];
+            prev = src->d_tp_prev;
+            if (g->device[(size_t)cmd.u[0]] != g->device[0]) {
+                e = hipMemcpyPeerAsync(c->d_tp_prev, g->device[0], src->d_tp_prev, g->device[(size_t)cmd.u[0]], sizeof(evplp::TemporalPrev) * g->plane_px, c->stream);
+                if (e != hipSuccess) { (void)hipGetLastError(); c->set_error("evplp_group_denoise_temporal: texels of rank %u: %s", cmd.u[0], hipGetErrorString(e)); return EVPLP_ERR_HIP; }
+                prev = c->d_tp_prev;
+            }
+        }
+        const evplp::TemporalSettings ts{ cmd.i[2], cmd.f[3] };
+        if ((rc = evplp::temporal_accumulate(c, const_cast<evplp::DenoisePixel *>(frame), prev, rows, ds, ts, c->bounding_radius)) < 0) return rc;
+    }
+    rc = evplp::denoise_filter(c, frame, rows, ds, c->bounding_radius, out);
     if (rc < 0) return rc;
     e = hipMemcpyAsync(cmd.out, out, sizeof(float) * 3 * frame_px, hipMemcpyDeviceToHost, c->stream);     // (rows 0 .. H - 1 in image order)
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -436,6 +473,11 @@ static void worker_run(Worker *w, const Cmd &cmd) {
             break;
         case OP_DENOISE_PREP: rc = worker_denoise_prep(w, cmd); break;
         case OP_DENOISE_FILTER: rc = worker_denoise_filter(w, cmd); break;
+        case OP_TEMPORAL_ENABLE: rc = evplp::temporal_enable(c, cmd.i[0]); break;
+        case OP_TEMPORAL_RESET: evplp::temporal_forget(c); break;
+        // (iterations: the rank of the last primary; it waits, so that rank 0 -- behind the reduction's barrier -- reads finished texels)
+        case OP_TEMPORAL_POSE: rc = worker_temporal_pose(c); if (rc >= 0) rc = evplp_synchronize(c); break;
+        case OP_TEMPORAL_SNAPSHOT: rc = evplp::temporal_snapshot(c); break;
         case OP_ASSEMBLE: {
             // rank 0 puts the strips into image order on the device; one copy lands the frame in the caller's buffer (no host-side assembly:
             // a run that writes every frame resolves every iteration)
@@ -467,6 +509,10 @@ static void worker_run(Worker *w, const Cmd &cmd) {
         } else if (cmd.op == OP_DENOISE_PREP) {          // (the packed pixels of the rows an exchange moves)
             for (int q = 0; q < g->n; q++) all[(size_t)q] = (const float *)g->ctx[(size_t)q]->d_dn_pack;
             worker_all_gather(w, g->d_dn_recv[(size_t)r], g->strip_floats / 3 * evplp::kDenoiseFloats, all);
+            if (cmd.i[1]) {                               // (... and their previous-pose texels)
+                for (int q = 0; q < g->n; q++) all[(size_t)q] = (const float *)g->ctx[(size_t)q]->d_tp_prev;
+                worker_all_gather(w, g->d_tp_recv[(size_t)r], g->strip_floats / 3 * evplp::kTemporalPrevFloats, all);
+            }
         } else {
             for (int q = 0; q < g->n; q++) all[(size_t)q] = g->ctx[(size_t)q]->d_rgb;
             worker_all_gather(w, g->d_frame[(size_t)r], g->strip_floats, all);
@@ -595,6 +641,7 @@ extern "C" void evplp_group_destroy(evplp_group *g) {
     for (int r = 0; r < (int)g->d_sum.size(); r++) if (g->d_sum[(size_t)r] || g->d_stage[(size_t)r]) { hipSetDevice(g->device[(size_t)r]); hipFree(g->d_sum[(size_t)r]); hipFree(g->d_stage[(size_t)r]); }
     for (int r = 0; r < (int)g->d_noise_stage.size(); r++) if (g->d_noise_stage[(size_t)r]) { hipSetDevice(g->device[(size_t)r]); hipFree(g->d_noise_stage[(size_t)r]); }
     for (int r = 0; r < (int)g->d_dn_recv.size(); r++) if (g->d_dn_recv[(size_t)r]) { hipSetDevice(g->device[(size_t)r]); hipFree(g->d_dn_recv[(size_t)r]); }
+    for (int r = 0; r < (int)g->d_tp_recv.size(); r++) if (g->d_tp_recv[(size_t)r]) { hipSetDevice(g->device[(size_t)r]); hipFree(g->d_tp_recv[(size_t)r]); }
     if (g->d_dn_frame || g->d_dn_guides) { hipSetDevice(g->device[0]); hipFree(g->d_dn_frame); hipFree(g->d_dn_guides); }
     if (g->d_assembled || g->d_owner || g->d_noise_pool) { hipSetDevice(g->device[0]); hipFree(g->d_assembled); hipFree(g->d_owner); hipFree(g->d_noise_pool); }
     for (ncclComm_t c : g->comms) if (c && g->rccl.CommDestroy) g->rccl.CommDestroy(c);
@@ -647,7 +694,7 @@ extern "C" int evplp_group_create(const evplp_config *cfg, const evplp_group_con
     g->strip_floats = g->n == 1 ? g->strip_floats_cap : round_robin_floats(g);
     g->d_frame.assign((size_t)g->n, nullptr);
     g->plane_px = (size_t)g->ctx[0]->st.W * g->ctx[0]->st.local_rows;
-    g->d_sum.assign((size_t)g->n, nullptr); g->d_stage.assign((size_t)g->n, nullptr); g->d_noise_stage.assign((size_t)g->n, nullptr); g->d_dn_recv.assign((size_t)g->n, nullptr); g->num_cus.assign((size_t)g->n, 256);
+    g->d_sum.assign((size_t)g->n, nullptr); g->d_stage.assign((size_t)g->n, nullptr); g->d_noise_stage.assign((size_t)g->n, nullptr); g->d_dn_recv.assign((size_t)g->n, nullptr); g->d_tp_recv.assign((size_t)g->n, nullptr); g->num_cus.assign((size_t)g->n, 256);
     for (int r = 0; r < g->n; r++) {
         hipSetDevice(g->device[(size_t)r]);
         int cus = 0;
@@ -1086,15 +1133,25 @@ extern "C" int evplp_group_noise_variance(evplp_group *g, float scale, float *ou
 // The denoiser of a written frame (include/evplp.h evplp_group_denoise).  Strips: every rank packs its rows, the packed rows are all-gathered
 // and assembled on rank 0 as a resolve's strips are, and rank 0 filters the frame.  Iterations: rank 0 packs the pooled variance, the reduced
 // composite and light plane and the guides of the rank of the last primary, and filters them.
-extern "C" int evplp_group_denoise(evplp_group *g, float scale, float ls, int32_t mask_emitter, const evplp_denoise_params *p, float *out_rgb) {
-    GRP_CHECK(g);
-    evplp::DenoiseSettings ds; char why[200];
-    if (!evplp::denoise_settings(p, &ds, why, sizeof why)) { g->set_error("evplp_group_denoise: %s", why); return EVPLP_ERR_INVALID; }
-    if (!out_rgb) { g->set_error("evplp_group_denoise: null output"); return EVPLP_ERR_INVALID; }
-    int rc = noise_group_ready(g, "evplp_group_denoise");
+static int group_denoise(evplp_group *g, const char *name, float scale, float ls, int32_t mask_emitter, const evplp_denoise_params *p, const evplp_temporal_params *t,
+                         bool temporal, float *out_rgb, evplp_temporal_info *info) {
+    evplp::DenoiseSettings ds; evplp::TemporalSettings ts{ 0, 0.f }; char why[200];
+    if (!evplp::denoise_settings(p, &ds, why, sizeof why) || (temporal && !evplp::temporal_settings(t, &ts, why, sizeof why))) { g->set_error("%s: %s", name, why); return EVPLP_ERR_INVALID; }
+    if (!out_rgb) { g->set_error("%s: null output", name); return EVPLP_ERR_INVALID; }
+    int rc = noise_group_ready(g, name);
     if (rc < 0) return rc;
-    if (!g->ctx[0]->accel_built) { g->set_error("evplp_group_denoise: no scene (evplp_group_load_scene_json / evplp_build_accel)"); return EVPLP_ERR_INVALID; }
-    if (g->ctx[0]->scene_dirty) { g->set_error("evplp_group_denoise: vertices were updated (evplp_group_update_mesh): call evplp_group_refit_accel first"); return EVPLP_ERR_INVALID; }
+    if (!g->ctx[0]->accel_built) { g->set_error("%s: no scene (evplp_group_load_scene_json / evplp_build_accel)", name); return EVPLP_ERR_INVALID; }
+    if (g->ctx[0]->scene_dirty) { g->set_error("%s: vertices were updated (evplp_group_update_mesh): call evplp_group_refit_accel first", name); return EVPLP_ERR_INVALID; }
+    if (temporal) {
+        // (the workers are idle: noise_group_ready has drained them).  The ranks whose walk is repeated must hold the G-buffer of their last primary
+        if (!g->temporal_on) { g->set_error("%s: temporal accumulation is off (evplp_group_temporal_enable)", name); return EVPLP_ERR_INVALID; }
+        for (int r = 0; r < g->n; r++) {
+            evplp_context *c = g->ctx[(size_t)r];
+            if (!evplp::temporal_check(c, name, !g->iterations || r == g->last_primary)) { g->set_error("%s", c->error); return EVPLP_ERR_INVALID; }
+        }
+        // (another triangle count since the last call: every rank makes its previous pose anew and the call is a first call)
+        for (int r = 0; r < g->n; r++) if ((rc = evplp::temporal_pose_array(g->ctx[(size_t)r])) < 0) { g->set_error("%s", g->ctx[(size_t)r]->error); return rc; }
+    }
     if (!g->iterations) {
         // every rank's packed pixels and receive buffer exist before any worker names them in the all-gather (the workers are idle here)
         for (int r = 0; r < g->n; r++) {
@@ -1103,11 +1160,13 @@ extern "C" int evplp_group_denoise(evplp_group *g, float scale, float ls, int32_
             hipError_t e = hipSetDevice(g->device[(size_t)r]);
             if (e == hipSuccess && !c->d_dn_pack) e = hipMalloc((void **)&c->d_dn_pack, sizeof(evplp::DenoisePixel) * px);
             if (e == hipSuccess && !g->d_dn_recv[(size_t)r]) e = hipMalloc((void **)&g->d_dn_recv[(size_t)r], sizeof(float) * (g->strip_floats_cap / 3) * evplp::kDenoiseFloats * (size_t)g->n);
-            if (e != hipSuccess) { (void)hipGetLastError(); g->set_error("evplp_group_denoise: rank %d: %s", r, hipGetErrorString(e)); return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP; }
+            if (e == hipSuccess && temporal && !g->d_tp_recv[(size_t)r]) e = hipMalloc((void **)&g->d_tp_recv[(size_t)r], sizeof(float) * (g->strip_floats_cap / 3) * evplp::kTemporalPrevFloats * (size_t)g->n);
+            if (e != hipSuccess) { (void)hipGetLastError(); g->set_error("%s: rank %d: %s", name, r, hipGetErrorString(e)); return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP; }
         }
     }
-    Cmd prep; prep.op = OP_DENOISE_PREP; prep.f[0] = scale; prep.f[1] = ls; prep.i[0] = mask_emitter;
+    Cmd prep; prep.op = OP_DENOISE_PREP; prep.f[0] = scale; prep.f[1] = ls; prep.i[0] = mask_emitter; prep.i[1] = temporal ? 1 : 0;
     if (g->iterations) {
+        if (temporal) { Cmd pose; pose.op = OP_TEMPORAL_POSE; post(g->workers[(size_t)g->last_primary], pose); }
         Cmd pool; pool.op = OP_NOISE_POOL;
         rc = post_all(g, pool);
         Cmd v; v.op = OP_NOISE_VARIANCE; v.f[0] = scale; v.i[1] = 1; v.i[2] = 1;
@@ -1121,9 +1180,63 @@ extern "C" int evplp_group_denoise(evplp_group *g, float scale, float ls, int32_
     }
     if (rc < 0) return rc;
     Cmd f; f.op = OP_DENOISE_FILTER; f.i[0] = ds.levels; f.f[0] = ds.sigma_l; f.f[1] = ds.sigma_n; f.f[2] = ds.sigma_x; f.out = out_rgb;
+    f.i[1] = temporal ? 1 : 0; f.i[2] = ts.max_history; f.f[3] = ts.normal_cos; f.u[0] = g->iterations ? (uint32_t)g->last_primary : 0u;
     post(g->workers[0], f);
+    if (temporal) { Cmd snap; snap.op = OP_TEMPORAL_SNAPSHOT; rc = post_all(g, snap); if (rc < 0) return rc; }
     drain(g);
-    return group_status(g);
+    rc = group_status(g);
+    if (rc >= 0 && temporal && info) { rc = evplp::temporal_info(g->ctx[0], info); if (rc < 0) g->set_error("%s", g->ctx[0]->error); }
+    return rc;
+}
+extern "C" int evplp_group_denoise(evplp_group *g, float scale, float ls, int32_t mask_emitter, const evplp_denoise_params *p, float *out_rgb) {
+    GRP_CHECK(g);
+    return group_denoise(g, "evplp_group_denoise", scale, ls, mask_emitter, p, nullptr, false, out_rgb, nullptr);
+}
+// Temporal accumulation for the whole frame (include/evplp.h evplp_group_denoise_temporal): every rank keeps the previous pose and camera and
+// evaluates its own rows on it; rank 0 holds the history in image layout and runs the stage in front of the passes.
+extern "C" int evplp_group_temporal_enable(evplp_group *g, int32_t on) {
+    GRP_CHECK(g);
+    drain(g);
+    Cmd c; c.op = OP_TEMPORAL_ENABLE; c.i[0] = on;
+    const int rc = post_and_wait(g, c);
+    g->temporal_on = rc >= 0 && on != 0;
+    return rc;
+}
+extern "C" int evplp_group_temporal_reset(evplp_group *g) {
+    GRP_CHECK(g);
+    if (!g->temporal_on) { g->set_error("evplp_group_temporal_reset: temporal accumulation is off (evplp_group_temporal_enable)"); return EVPLP_ERR_INVALID; }
+    Cmd c; c.op = OP_TEMPORAL_RESET;
+    return post_and_wait(g, c);
+}
+extern "C" int evplp_group_denoise_temporal(evplp_group *g, float scale, float ls, int32_t mask_emitter, const evplp_denoise_params *p,
+                                            const evplp_temporal_params *t, float *out_rgb, evplp_temporal_info *info) {
+    GRP_CHECK(g);
+    return group_denoise(g, "evplp_group_denoise_temporal", scale, ls, mask_emitter, p, t, true, out_rgb, info);
+}
+extern "C" int evplp_group_temporal_download(evplp_group *g, int32_t which, float *out) {
+    GRP_CHECK(g);
+    const char *name = "evplp_group_temporal_download";
+    if (!out || which < EVPLP_TEMPORAL_HISTORY_U || which > EVPLP_TEMPORAL_PREV_NRM) { g->set_error("%s: a null output or a plane the group does not hold (%d)", name, which); return EVPLP_ERR_INVALID; }
+    if (!g->temporal_on) { g->set_error("%s: temporal accumulation is off (evplp_group_temporal_enable)", name); return EVPLP_ERR_INVALID; }
+    drain(g);
+    int rc = group_status(g);
+    if (rc < 0) return rc;
+    evplp_context *c = g->ctx[0];
+    const size_t frame_px = (size_t)c->st.W * c->st.H;
+    hipError_t e = hipSetDevice(g->device[0]);
+    if (which <= EVPLP_TEMPORAL_HISTORY_NRM) {
+        if (!c->d_tp_hist || c->tp_frames == 0) { g->set_error("%s: no call has written a history", name); return EVPLP_ERR_INVALID; }
+        if (e == hipSuccess) e = hipMemcpy(out, c->d_tp_hist + ((size_t)c->tp_cur * 3 + (size_t)which) * c->tp_hist_px, sizeof(float4) * frame_px, hipMemcpyDeviceToHost);
+    } else {
+        const evplp::TemporalPrev *src = g->iterations ? g->ctx[(size_t)g->last_primary]->d_tp_prev : c->d_tp_prev_frame;
+        if (!src) { g->set_error("%s: no call has evaluated a previous pose", name); return EVPLP_ERR_INVALID; }
+        if (g->iterations) e = hipSetDevice(g->device[(size_t)g->last_primary]);
+        std::vector<evplp::TemporalPrev> host(frame_px);
+        if (e == hipSuccess) e = hipMemcpy(host.data(), src, sizeof(evplp::TemporalPrev) * frame_px, hipMemcpyDeviceToHost);
+        for (size_t i = 0; i < frame_px; i++) std::memcpy(out + 4 * i, which == EVPLP_TEMPORAL_PREV_POS ? &host[i].pos : &host[i].nrm, 16);
+    }
+    if (e != hipSuccess) { g->set_error("%s: %s", name, hipGetErrorString(e)); return EVPLP_ERR_HIP; }
+    return EVPLP_OK;
 }
 
 // Adaptive gather (include/evplp.h evplp_adaptive_*).  Row strips only: every rank decides for its own tiles; the counts are summed and the

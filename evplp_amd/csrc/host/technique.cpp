@@ -447,6 +447,12 @@ struct InvalidError : std::runtime_error { using std::runtime_error::runtime_err
 // filename is required; the others default to the library's (include/evplp.h).  Needs the "noise" block, whose variance guides the filter
 // (so frameMode "cleareveryframe" is refused).  Validated before the group exists.  Written after every other output, behind the noise
 // block's last fold; with fewer than two folds the other outputs are written and the run fails with EVPLP_ERR_INVALID.
+//   "temporal": {"maxHistory": 16, "normalCos": 0.9}   (both optional; only with an "animation" block)
+// accumulates over the frames of the animation in front of the filter (evplp_group_denoise_temporal): every frame's file comes from that
+// call, frame 0's is the file of the run without the key, and a frame's stat file gains "temporalReprojected", "temporalDisoccluded" and
+// "temporalMeanHistory".  The accumulation takes the frames for independent samples: set "animation": {"rngAdvance": k} with
+// k >= numMaxIteration, or every frame repeats the same noise pattern and nothing is gained.  Refused without an "animation" block (a single
+// frame has no history), with an unknown key inside and with values out of range (maxHistory 1 .. 1024, normalCos in (0, 1]).
 class Denoise {
 public:
     bool on = false;
@@ -467,15 +473,48 @@ public:
         sigma(c, "sigmaLuminance", p.sigma_luminance);
         sigma(c, "sigmaNormal", p.sigma_normal);
         sigma(c, "sigmaPosition", p.sigma_position);
+        if (c.has("temporal")) {
+            const Json &t = c.at("temporal");
+            if (!t.is_object()) throw JsonError("denoise.temporal: expected an object");
+            if (!tech.has("animation")) throw JsonError("denoise.temporal: needs an \"animation\" block (a single frame has no history to accumulate)");
+            for (const auto &kv : t.obj)
+                if (kv.first != "maxHistory" && kv.first != "normalCos") throw JsonError("denoise.temporal." + kv.first + ": unknown key (maxHistory, normalCos)");
+            if (t.has("maxHistory")) {
+                const double m = t.at("maxHistory").as_number("denoise.temporal.maxHistory");
+                if (!(m >= 1.0) || !(m <= 1024.0) || m != std::floor(m)) throw JsonError("denoise.temporal.maxHistory: must be an integer 1 .. 1024");
+                tp.max_history = (int32_t)m;
+            }
+            if (t.has("normalCos")) {
+                const double v = t.at("normalCos").as_number("denoise.temporal.normalCos");
+                if (!std::isfinite(v) || !(v > 0.0) || v > 1.0) throw JsonError("denoise.temporal.normalCos: must be in (0, 1]");
+                tp.normal_cos = (float)v;
+            }
+            temporal = true;
+        }
         on = true;
     }
     template <class Name> void name_files(Name name) { filename = name(filename); }
+    // "temporal": enabled on the group once, before the first frame
+    void start(evplp_group *g) { if (on && temporal) check(g, evplp_group_temporal_enable(g, 1), "denoise.temporal"); }
+    // "temporal": the frame's image, in front of its stat file (which reports the call's counts); write() saves it
+    void accumulate(evplp_group *g, int W, int H, long long batches, float scale, float ls, int32_t mask_emitter) {
+        if (!on || !temporal || batches < 2) return;
+        held.assign((size_t)W * H * 3, 0.f);
+        check(g, evplp_group_denoise_temporal(g, scale, ls, mask_emitter, &p, &tp, held.data(), &info), "denoise.temporal");
+    }
+    void add_stat(Json &st) const {
+        if (held.empty()) return;
+        st.set("temporalReprojected", Json::number((double)info.reprojected));
+        st.set("temporalDisoccluded", Json::number((double)info.disoccluded));
+        st.set("temporalMeanHistory", Json::number(info.filtered > 0 ? (double)info.history_sum / (double)info.filtered : 0.0));
+    }
     void write(evplp_group *g, int W, int H, long long batches, float scale, float ls, int32_t mask_emitter) {
         if (!on) return;
         if (batches < 2)
             throw InvalidError("denoise: " + std::to_string(batches) + " noise batch(es) closed, the filter needs >= 2: " + filename + " is not written");
         std::vector<float> rgb((size_t)W * H * 3);
-        check(g, evplp_group_denoise(g, scale, ls, mask_emitter, &p, rgb.data()), "denoise");
+        if (!held.empty()) rgb = held;
+        else check(g, evplp_group_denoise(g, scale, ls, mask_emitter, &p, rgb.data()), "denoise");
         std::vector<float> top = flip_y(rgb, W, H);
         if (save_image(filename.c_str(), W, H, top.data()) != EVPLP_OK) throw std::runtime_error("cannot write " + filename);
     }
@@ -489,6 +528,7 @@ private:
     }
     std::string filename;
     evplp_denoise_params p{};
+    bool temporal = false; evplp_temporal_params tp{}; evplp_temporal_info info{}; std::vector<float> held;
 };
 
 // Build-only key "adaptive" (photonfam, VPL and VSL gathers): tiles whose estimated noise has converged stop receiving gather work
@@ -625,7 +665,9 @@ private:
 // matrix per track and frame (evplp_group_transform_mesh: the rest pose under the matrix, nothing composes), and every frame is rendered by
 // the technique's loop from its beginning.
 //   {"frames": F, "tracks": [{"object": k, "matrices": [[12 numbers], ... F of them]}, {"mesh": i, "matrices": [...]}],
-//    "refitPolicy": {"maxCostRatio": r, "rebuildBuilder": "gpu"}, "rotations": k}
+//    "refitPolicy": {"maxCostRatio": r, "rebuildBuilder": "gpu"}, "rotations": k, "rngAdvance": k}
+// "rngAdvance": k >= 0 (default 0): frame f runs with rngOffset + f k, seeds and jitter stream both, so that its files are those of a fresh
+// evplp_render_json of the moved scene with that rngOffset; with 0 every frame uses the same seeds.
 // "rotations": k = 0 .. 8 (default 0: off) is evplp_group_set_refit_rotations: k passes of tree rotations inside every frame's refit.
 // "object": k addresses every mesh the k-th entry of the scene file's "scene" array produced (an OBJ yields one mesh per material group),
 // "object": "arealight" the light, "mesh": i the i-th mesh in upload order.  For frame f = 0 .. F - 1 every track's f-th matrix is applied,
@@ -706,8 +748,15 @@ public:
             if (a.at("rotations").type != Json::Number || !(k >= 0.0) || !(k <= 8.0) || k != std::floor(k)) throw JsonError("animation.rotations: must be an integer 0 .. 8 (rotation passes inside a frame's refit; 0: off)");
             rotations = (int)k;
         }
+        if (a.has("rngAdvance")) {
+            const double k = a.at("rngAdvance").as_number("animation.rngAdvance");
+            if (a.at("rngAdvance").type != Json::Number || !(k >= 0.0) || !(k <= 1.0e6) || k != std::floor(k)) throw JsonError("animation.rngAdvance: must be an integer 0 .. 1000000 (frame f runs with rngOffset + f * rngAdvance)");
+            rng_advance = (uint32_t)k;
+        }
         frames = (int)F; on = true;
     }
+    // frame f's rngOffset
+    uint32_t frame_rng_offset(uint32_t rng_offset, int f) const { return rng_offset + (uint32_t)f * rng_advance; }
     // path with _fNNNN in front of its extension
     std::string frame_path(const std::string &path) const {
         if (!on) return path;
@@ -747,7 +796,7 @@ public:
 private:
     struct Track { std::vector<int32_t> meshes; std::vector<float> matrices; };       // matrices: [frames][12]
     std::vector<Track> tracks;
-    double policy_ratio = 0.0; int policy_builder = -1; int rotations = 0;
+    double policy_ratio = 0.0; int policy_builder = -1; int rotations = 0; uint32_t rng_advance = 0;
     int frame = 0; float refit_ms = 0.f; int last_action = 0; double cost_ratio = 0.0;
 };
 } // namespace
@@ -809,12 +858,15 @@ public:
         upload_scene_group(grp.g, scene);
         conv.upload(grp.g);
         anim.start(grp.g);
+        denoise.start(grp.g);
         // "animation": every frame starts from the blocks as parsed, with its own file names
         const Convergence conv0 = conv; const Noise noise0 = noise; const Denoise denoise0 = denoise; const Adaptive adaptive0 = adaptive;
         const std::string output0 = output_filename, stat0 = stat_filename;
+        const uint32_t rng_offset0 = rng_offset;
         for (int f = 0; f < anim.frames; f++) {
             if (anim.on) {
                 anim.begin_frame(grp.g, f);
+                rng_offset = anim.frame_rng_offset(rng_offset0, f);
                 auto name = [&](const std::string &p) { return anim.frame_path(p); };
                 conv = conv0; noise = noise0; denoise = denoise0; adaptive = adaptive0;
                 conv.name_files(name); noise.name_files(name); denoise.name_files(name); adaptive.name_files(name);
@@ -898,12 +950,14 @@ private:
         check(h, evplp_group_synchronize(h), "sync");
         float time = elapsed_ms();
         { const Composite k = composite(num_iterations); conv.finish(h, num_iterations, elapsed_ms(), k.vs, k.ps, k.ls, k.mask_emitter);
-          noise.finish(h, num_iterations, elapsed_ms(), k.vs, k.ls, k.mask_emitter, W, H); }
+          noise.finish(h, num_iterations, elapsed_ms(), k.vs, k.ls, k.mask_emitter, W, H);
+          denoise.accumulate(h, W, H, noise.batch_count(), k.vs, k.ls, k.mask_emitter); }
         if (use_stat) {                                                                       // :694-704
             Json st = Json::object();
             st.set("time", Json::number(time)); st.set("numIterations", Json::number(num_iterations));
             add_pass_times(h, st);
             anim.add_stat(st);
+            denoise.add_stat(st);
             std::ofstream of(stat_filename);
             if (!of) throw std::runtime_error("cannot write " + stat_filename);
             of << st.dump() << "\n";
@@ -1018,12 +1072,15 @@ public:
         splat_footprint = setup_splat_footprint(grp.g, json, out_dir);                                           // :677
         conv.upload(grp.g);
         anim.start(grp.g);
+        denoise.start(grp.g);
         // "animation": every frame starts from the blocks as parsed and from the moved scene's own figures, with its own file names
         const Convergence conv0 = conv; const Noise noise0 = noise; const Denoise denoise0 = denoise; const Adaptive adaptive0 = adaptive;
         const std::string combined0 = combined_filename, photon0 = weighted_photon_filename, vpl0 = weighted_vpl_filename, stat0 = stat_filename;
+        const uint32_t rng_offset0 = rng_offset;
         for (int f = 0; f < anim.frames; f++) {
             if (anim.on) {
                 anim.begin_frame(grp.g, f);
+                rng_offset = anim.frame_rng_offset(rng_offset0, f);
                 auto name = [&](const std::string &p) { return anim.frame_path(p); };
                 conv = conv0; noise = noise0; denoise = denoise0; adaptive = adaptive0;
                 conv.name_files(name); noise.name_files(name); denoise.name_files(name); adaptive.name_files(name);
@@ -1166,12 +1223,14 @@ private:
         noise.finish(h, num_iterations, elapsed_ms(), saved_param(num_iterations), 1.0f, 0, W, H);
         adaptive.finish(h, num_iterations, W, H);
         check(h, evplp_group_profile_passes(h, 1), "profile");
+        denoise.accumulate(h, W, H, noise.batch_count(), saved_param(num_iterations), 1.0f, 0);
         if (use_stat) {                                                                       // :1109-1119
             Json st = Json::object();
             st.set("time", Json::number(time));
             if (!lvc) st.set("numIterations", Json::number(num_iterations));              // rtlvccomphoton.h writes the time only
             add_pass_times(h, st);
             anim.add_stat(st);
+            denoise.add_stat(st);
             std::ofstream of(stat_filename);
             if (!of) throw std::runtime_error("cannot write " + stat_filename);
             of << st.dump() << "\n";

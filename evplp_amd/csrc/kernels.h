@@ -20,6 +20,13 @@ struct PrimaryCutArgs {
     char *cuts;
 };
 void launch_primary_cuts(const PrimaryCutArgs &a, hipStream_t s);
+// the deal of primary_kernel's tiles to workgroups (kernels_trace.hip; prev_pose_kernel, kernels_temporal.hip, follows it)
+#ifndef EVPLP_PRIMARY_BLOCKS
+#define EVPLP_PRIMARY_BLOCKS 1
+#endif
+#ifndef EVPLP_PRIMARY_BLOCK_LOG2
+#define EVPLP_PRIMARY_BLOCK_LOG2 2     // 4 x 4 tiles
+#endif
 
 struct LightTraceArgs {
     SceneDev sc;
@@ -345,5 +352,28 @@ struct DenoiseLevelArgs {
 void launch_denoise_level(const DenoiseLevelArgs &a, hipStream_t s);
 // out_rgb [n][3]: albedo * u of a filtered pixel, the composite of any other
 void launch_denoise_finish(const DenoisePixel *frame, const float4 *u, size_t n, float *out_rgb, hipStream_t s);
+
+// evplp_denoise_temporal (kernels_temporal.hip).  prev_pose_kernel walks like primary_kernel (same arguments, the jitter and light flags of
+// the pass that wrote the G-buffer in memory) and evaluates every pixel's hit (tri, b, g) on prev_v, 9 floats per original triangle: the
+// pose at the end of the previous call.  pos = (P_prev, tri >= 0 ? 1 : 0), nrm = (N_prev, 0); 32 B per plane pixel, exchanged and assembled
+// as floats like the packed pixels.  debug (tests; null otherwise): (bits of tri, b, g, 0).  prev null: the debug plane alone.
+struct TemporalPrev { float4 pos, nrm; };
+constexpr int kTemporalPrevFloats = (int)(sizeof(TemporalPrev) / sizeof(float));
+void launch_prev_pose(const PrimaryArgs &a, const float *prev_v, TemporalPrev *prev, float4 *debug, hipStream_t s);
+// prev_v[9 t + k] = attrs[t].v[k]
+void launch_pose_snapshot(const TriAttr *attrs, int32_t ntri, float *prev_v, hipStream_t s);
+// The accumulation stage over a frame of W x rows packed pixels (rows from the bottom, image rows 0 .. H - 1): writes (u_out, s_out) into
+// frame[i].u and the new history.  A history is three planes of `px` float4: (u, s), (X, filtered), (n, length).  has_history = 0: every
+// filtered pixel starts a history.  counts: { filtered, reprojected, disoccluded, summed history length } of every workgroup of 16 x 16
+// pixels, [temporal_count_slots(W, rows)]; the host adds the slots.
+int temporal_count_slots(int W, int rows);
+struct TemporalArgs {
+    DenoisePixel *frame; const TemporalPrev *prev; const float4 *h_in; float4 *h_out; uint4 *counts;
+    size_t px;
+    int32_t W, rows, H, has_history;
+    CamBasis cam, prev_cam;
+    float sigma_x_r, normal_cos, max_history, pad;
+};
+void launch_temporal_accumulate(const TemporalArgs &a, hipStream_t s);
 
 } // namespace evplp

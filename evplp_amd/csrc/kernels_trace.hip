@@ -10,12 +10,6 @@
 
 namespace evplp {
 
-#ifndef EVPLP_PRIMARY_BLOCKS
-#define EVPLP_PRIMARY_BLOCKS 1
-#endif
-#ifndef EVPLP_PRIMARY_BLOCK_LOG2
-#define EVPLP_PRIMARY_BLOCK_LOG2 2     // 4 x 4 tiles
-#endif
 #if EVPLP_PRIMARY_TIMES      // developer build (tools/primary_times.py): start / end of every tile's wavefront, s_memrealtime ticks (100 MHz)
 __device__ unsigned long long g_primary_times[2 * 65536];
 extern "C" int evplp_debug_primary_times(unsigned long long *out, int n) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_primary_times), sizeof(unsigned long long) * (size_t)n); }

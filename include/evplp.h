@@ -144,6 +144,9 @@ typedef struct evplp_config {
  *                                   for rotations allocates and launches none of it
      *   denoiser (after a call)         124 B per pixel of the context's planes (evplp_denoise); a group's rank: 92 B per pixel of its planes
      *                                   + n x 80 B per pixel of the exchanged rows, and rank 0 + 112 B per image pixel (evplp_group_denoise)
+     *   temporal accumulation (if on)   36 B per triangle + 32 B per pixel of the context's planes (evplp_temporal_enable), and on the context that
+     *                                   filters 96 B per pixel of its frame after its first evplp_denoise_temporal; a group's rank under strips:
+     *                                   + n x 32 B per pixel of the exchanged rows, and rank 0 + 32 B per image pixel (evplp_group_denoise_temporal)
      * A caller that has the device to itself sets cut_scratch_bytes = 72 GB, vsl_mask_bytes = 14 GB for config #5 (one band, one launch). */
     uint64_t cut_scratch_bytes;
     uint64_t vsl_mask_bytes;
@@ -588,7 +591,80 @@ typedef struct evplp_denoise_params {
 } evplp_denoise_params;
 int evplp_denoise(evplp_context *ctx, float scale, float light_scale, int32_t mask_emitter, const evplp_denoise_params *p, float *out_rgb);
 
-/* Adaptive gather: tiles whose estimated noise has converged stop receiving gather work (off by default; a run without it is unchanged).
+/* Temporal accumulation across the frames of a moving scene: the temporal half of SVGF, by backward reprojection, in front of evplp_denoise's
+ * a-trous passes.  Off by default; evplp_denoise and every other call are unchanged by it.
+ *
+ * evplp_temporal_enable(ctx, 1) allocates 36 B per original triangle (the previous pose) and 32 B per pixel of the context's planes (the
+ * hits evaluated on that pose); 0 releases them and the history.  A context that never enables it allocates nothing.  The context that
+ * filters also holds the history, double-buffered, 2 x 48 B per pixel of the frame, allocated by its first evplp_denoise_temporal.
+ * "Previous" is the state at the END of the previous successful evplp_denoise_temporal of this context: that call copies every
+ * triangle's vertices as they then are on the device and remembers the camera.  Any number of evplp_update_mesh, evplp_transform_mesh,
+ * evplp_refit_accel (rebuilds by its policy included), evplp_build_accel and evplp_set_camera calls may lie between two frames.
+ * evplp_temporal_reset forgets the history: the next call behaves as a first call.  So does a change of the scene's triangle count.
+ *
+ * evplp_denoise_temporal(ctx, scale, light_scale, mask_emitter, denoise params, temporal params, out_rgb, info) is evplp_denoise with one
+ * stage between the packing of the pixels and the first pass.  With (u, s), X, n the demodulated colour and luminance variance, the
+ * position and the normal of a filtered pixel i = (x, y), and the history of the previous call per pixel h_u = (u, s), h_pos = (X,
+ * filtered ? 1 : 0), h_nrm = (n, history length):
+ *  1. The walk of the last evplp_primary is repeated (the same jitter, light flags and entry cuts: the hit (triangle, b, g) is the one of
+ *     the G-buffer in memory) and the hit is evaluated on the previous pose: P_prev, N_prev by the G-buffer's own two expressions.  On a
+ *     scene that did not move these equal EVPLP_BUF_GBUF_POSITION / _NORMAL bit for bit.
+ *  2. Motion m = project(previous camera, P_prev) - project(camera, X) in pixels (evplp_project_points' function), (fx, fy) = (x, y) + m:
+ *     the jitter cancels in the difference, and an unmoved point under an unmoved camera has m = 0 exactly.  No history (step 4 with n = 1,
+ *     u_out = u, s_out = s) on a first call, for a P_prev at or behind the previous eye, and for (fx, fy) outside (-1, W) x (-1, H).
+ *  3. Taps: (fx, fy) integral -> the one pixel, weight 1; otherwise the four pixels (floor fx + 0 / 1, floor fy + 0 / 1), x inner, with the
+ *     bilinear weights ((1 - tx) or tx) * ((1 - ty) or ty).  A tap q counts when it lies in the image, h_pos[q].w != 0,
+ *     |n_q . (P_prev - X_q)| <= sigma_position R and |N_prev . (X_q - P_prev)| <= sigma_position R (R and sigma_position: the a-trous
+ *     passes'), and N_prev . n_q >= normal_cos.  With sw = the sum of the counted weights > 0: hist_u = sum w u_q / sw, hist_s = sum w^2 s_q
+ *     / sw^2, n_hist = the smallest history length among the counted taps.  sw = 0: no history.
+ *  4. n = min(n_hist + 1, max_history), a = 1 / n, u_out = (1 - a) hist_u + a u, s_out = (1 - a)^2 hist_s + a^2 s.  The variance rule
+ *     ASSUMES THAT THE FRAMES ARE INDEPENDENT SAMPLES: render frame f with seeds and jitters no other frame within max_history uses (the
+ *     technique JSON: "animation": {"rngAdvance": k} with k >= numMaxIteration).  With the same seeds in every frame the frames' noise is
+ *     one pattern, accumulation removes none of it, and s_out understates what is left.
+ *  5. (u_out, s_out) replace (u, s) for the passes, which run unchanged, and become the new history with X, n and the length n.  The
+ *     history is the accumulated, unfiltered signal.  A pixel that is not filtered is copied and stores h_pos.w = 0.
+ * Every operation is + - * /, floor, min, max or a compare in fp32, each rounded on its own, in a fixed order; the four counts of info are
+ * integer sums.  A call is bit-reproducible, and the first call after a reset gives evplp_denoise's bytes.
+ * Bias and lag: a surface whose shading changes (a moving shadow, a moving light's highlight) keeps up to max_history frames of its old
+ * shading at weight (1 - 1 / n); lower max_history to trade noise for lag.  Bilinear taps blur the history slightly on every moving frame.
+ * info (may be NULL): filtered pixels; those that found a history (reprojected); those that found none although the call had one
+ * (disoccluded); the sum of the new history lengths over the filtered pixels; successful calls since the last reset, this one included.
+ * Refused with EVPLP_ERR_INVALID, leaving the context usable and the history and the previous pose as they were: every refusal of
+ * evplp_denoise; temporal not enabled; no evplp_primary since the last evplp_build_accel / evplp_refit_accel (the G-buffer in memory is
+ * not the tree's); EVPLP_BUF_GBUF_POSITION bound, exposed (evplp_buffer_info) or uploaded by the caller -- the walk cannot vouch for a
+ * plane it did not write; max_history outside 1..1024 (0 = 16) or normal_cos outside (0, 1] (0 = 0.9) or not finite.
+ * evplp_temporal_download (tests and tools; waits): plane `which` of the last call, 4 floats per pixel of the context's planes, y = 0 at the
+ * bottom: EVPLP_TEMPORAL_HISTORY_U / _POS / _NRM the history it wrote, EVPLP_TEMPORAL_PREV_POS / _PREV_NRM the hits on the previous pose
+ * (zeros after a first call), EVPLP_TEMPORAL_DEBUG_HIT (the bits of the triangle index or of -1, b, g, 0) of the walk as it would run now
+ * -- that plane is allocated for the call alone. */
+typedef struct evplp_temporal_params {
+    int32_t max_history;        /* longest history length, 1..1024; 0 = 16 */
+    float normal_cos;           /* least cosine between N_prev and a tap's normal, (0, 1]; 0 = 0.9 */
+    int32_t reserved[6];
+} evplp_temporal_params;        /* 32 bytes */
+typedef struct evplp_temporal_info {
+    int64_t filtered, reprojected, disoccluded, history_sum;
+    int32_t frames_since_reset, reserved;
+} evplp_temporal_info;          /* 40 bytes */
+#define EVPLP_TEMPORAL_HISTORY_U 0
+#define EVPLP_TEMPORAL_HISTORY_POS 1
+#define EVPLP_TEMPORAL_HISTORY_NRM 2
+#define EVPLP_TEMPORAL_PREV_POS 3
+#define EVPLP_TEMPORAL_PREV_NRM 4
+#define EVPLP_TEMPORAL_DEBUG_HIT 5
+int evplp_temporal_enable(evplp_context *ctx, int32_t on);
+int evplp_temporal_reset(evplp_context *ctx);
+int evplp_denoise_temporal(evplp_context *ctx, float scale, float light_scale, int32_t mask_emitter, const evplp_denoise_params *p,
+                           const evplp_temporal_params *t, float *out_rgb, evplp_temporal_info *info);
+int evplp_temporal_download(evplp_context *ctx, int32_t which, float *out);
+/* n world points (3 floats each) on the screen of `cam` at W x H pixels: out_xyd = (x, y, view depth) per point, pixel-centre coordinates
+ * (pixel (i, j) of a y-up image has its centre at (i, j); x to the right, y from the bottom).  With d = p - eye and (s, u, f) the
+ * camera's right, up and forward: z = d . f, x = (((d . s / z) / (aspect tan(fovy / 2))) + 1) W / 2 - 0.5 and likewise y with u, H and no
+ * aspect; fp32, every product and sum rounded on its own (dot products (x + y) + z).  A point with z <= 0 is at or behind the eye: (0, 0, z).
+ * The function evplp_denoise_temporal measures motion with.  No GPU, no context.  EVPLP_ERR_INVALID: a null pointer, n < 0, W or H < 1. */
+int evplp_project_points(const evplp_camera *cam, int32_t W, int32_t H, const float *xyz, int32_t n, float *out_xyd);
+
+/* Adaptive gather:tiles whose estimated noise has converged stop receiving gather work (off by default; a run without it is unchanged).
  * Tile: an 8 x 8 pixel tile of the context's local rows (strip_rows is a multiple of 8: a tile never straddles two row blocks); one decision
  * per tile, independent of the partition.  N: the context's accumulating calls into EVPLP_BUF_VPL_ACCUM (evplp_gather_vpl / _vsl and
  * evplp_path_trace with do_accumulate != 0; so enabling either mode after an accumulated path-tracing sample without a clear is refused) since the accumulators were last cleared; evplp_clear_accumulators and evplp_set_blocks (so also a group's rebalance) reset N to 0 and make
@@ -944,6 +1020,19 @@ int evplp_group_noise_variance(evplp_group *g, float scale, float *out_rgb);
  * the pooled moments (evplp_group_noise_variance), and the guides of the rank that ran the last evplp_group_primary.  Device memory: see
  * the table of evplp_config.  Refusals as evplp_denoise's (strip_count aside), on the caller's thread; the group stays usable. */
 int evplp_group_denoise(evplp_group *g, float scale, float light_scale, int32_t mask_emitter, const evplp_denoise_params *p, float *out_rgb);
+/* evplp_temporal_enable / _reset / evplp_denoise_temporal / evplp_temporal_download for the whole frame, in evplp_group_resolve's layout (H x W,
+ * y = 0 at the bottom).  Every rank keeps the previous pose and camera (36 B per triangle and 32 B per pixel of its planes each) and
+ * evaluates its own rows on it.  EVPLP_PARTITION_STRIPS: the texels travel beside the packed pixels (one more all-gather, n x 32 B per
+ * pixel of the exchanged rows per rank) and rank 0 assembles them (32 B per image pixel); rank 0 holds the history in IMAGE layout (96 B
+ * per image pixel), so evplp_group_rebalance between two frames does not disturb it, and a group gives the single context's bits for any
+ * block table.  EVPLP_PARTITION_ITERATIONS: the texels are those of the rank the last evplp_group_primary went to, whose G-buffer the
+ * group's denoiser reads.  Refusals as evplp_denoise_temporal's, on the caller's thread.  evplp_group_temporal_download gives the three
+ * history planes and the two previous-pose planes (not EVPLP_TEMPORAL_DEBUG_HIT: ask the rank's context). */
+int evplp_group_temporal_enable(evplp_group *g, int32_t on);
+int evplp_group_temporal_reset(evplp_group *g);
+int evplp_group_denoise_temporal(evplp_group *g, float scale, float light_scale, int32_t mask_emitter, const evplp_denoise_params *p,
+                                 const evplp_temporal_params *t, float *out_rgb, evplp_temporal_info *info);
+int evplp_group_temporal_download(evplp_group *g, int32_t which, float *out);
 /* evplp_adaptive_* for a group.  EVPLP_PARTITION_STRIPS: every rank decides for its own tiles, the retire call returns the sum of the ranks'
  * counts, and the tile map is assembled from the block owners (the whole image).  EVPLP_PARTITION_ITERATIONS: every call is refused --
  * pooling the ranks' decisions is not supported.  Refusals come on the caller's thread and leave the group usable. */
