@@ -618,7 +618,8 @@ class Context:
         """evplp_selftest: 0 the exact reciprocal, 1 the hardware pow, 2 the hand-written triangle-pair test against tri_pair_test
         (mismatches, cases, hits, then the hits of classes 0|1, 2|3, 4|5 packed 32 bits each), 3 the in-place visit of a synthetic
         node of an entry cut against the scalar-operand node visit (differences, cases, entered lanes, then the entered lanes of
-        classes 0|1, 2|3, 4|5 packed 32 bits each)"""
+        classes 0|1, 2|3, 4|5 packed 32 bits each), 4 the hardware primitives of the VSL estimators against double precision, maxima
+        in units of 1e-12 (absolute: v_sin, v_cos, the Phong samples' cos_t; relative: v_rcp, v_rsq, v_sqrt)"""
         out = np.zeros(8, dtype=np.uint64)
         n = self._check(self._lib.evplp_selftest(self._h, which, _ptr(out), 8))
         return out[:n]

@@ -261,6 +261,40 @@ __attribute__((amdgpu_num_vgpr(50))) __global__ __launch_bounds__(64) void selft
     }
 }
 
+// which = 4: the hardware primitives of the VSL estimators (kernels_gather.hip, namespace vslm) against double precision; maxima in
+// units of 1e-12:
+//   out[0] / out[1]  |v_sin_f32(u) - sin(2 pi u)| / |v_cos_f32(u) - cos(2 pi u)| over all 2^24 uniforms u = (k + 1) 2^-24 (the
+//                    azimuth of every sampled direction: square_to_solid_angle, lambert_local, phong_local)
+//   out[2]           |exp2(log2(u) rcp(e + 1)) - u^(1 / (e + 1))| (phong_local's cos_t) for e = 0, 0.5, 1, 20, 200, 1000, 10000 over the
+//                    2^22 uniforms u = (k + 1) 2^-22
+//   out[3] / [4] / [5]  relative error of v_rcp_f32 / v_rsq_f32 / v_sqrt_f32 over 2^22 arguments spread evenly in the exponent over
+//                    [2^-20, 2^20]
+__global__ __launch_bounds__(256) void selftest_vsl_primitives_kernel(unsigned long long *out) {
+    const float es[7] = { 0.0f, 0.5f, 1.0f, 20.0f, 200.0f, 1000.0f, 10000.0f };
+    const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+    double m[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
+    for (uint32_t k = tid; k < (1u << 24); k += stride) {
+        const float u = (float)(k + 1u) * (1.0f / 16777216.0f);
+        m[0] = fmax(m[0], fabs((double)__builtin_amdgcn_sinf(u) - sinpi(2.0 * (double)u)));
+        m[1] = fmax(m[1], fabs((double)__builtin_amdgcn_cosf(u) - cospi(2.0 * (double)u)));
+    }
+    const uint32_t n = 1u << 22;
+    for (uint32_t k = tid; k < n; k += stride) {
+        const float u = (float)(k + 1u) * (1.0f / 4194304.0f);
+        for (int j = 0; j < 7; j++) {
+            float e1 = es[j] + 1.0f;
+            asm volatile("" : "+v"(e1));               // (a run-time value, as in the kernels: the reciprocal of a constant would be folded, correctly rounded)
+            const float got = __builtin_amdgcn_exp2f(__builtin_amdgcn_rcpf(e1) * __builtin_amdgcn_logf(u));
+            m[2] = fmax(m[2], fabs((double)got - pow((double)u, 1.0 / ((double)es[j] + 1.0))));
+        }
+        const float x = (float)exp2(-20.0 + 40.0 * (double)k / (double)(n - 1u));
+        m[3] = fmax(m[3], fabs((double)__builtin_amdgcn_rcpf(x) * (double)x - 1.0));
+        m[4] = fmax(m[4], fabs((double)__builtin_amdgcn_rsqf(x) * sqrt((double)x) - 1.0));
+        m[5] = fmax(m[5], fabs((double)__builtin_amdgcn_sqrtf(x) / sqrt((double)x) - 1.0));
+    }
+    for (int j = 0; j < 6; j++) atomicMax(&out[j], (unsigned long long)(m[j] * 1e12));
+}
+
 // evplp_debug_ev_math: ev_math.h's functions AS THE DEVICE COMPUTES THEM, on the caller's inputs.  The light-tracing records are compared with
 // the oracle's byte for byte, and the oracle #includes the same header: that comparison vouches for the walk and the draw order, not for
 // these functions -- unless the header really gives the same bits on both machines, which is what tests/test_gpu_parity.py checks with this
@@ -295,7 +329,7 @@ extern "C" int evplp_debug_ev_math(evplp_context *c, int32_t which, const float 
 }
 
 extern "C" int evplp_selftest(evplp_context *c, int32_t which, uint64_t *out, int32_t capacity) {
-    if (!c || !out || capacity < 6 || which < 0 || which > 3) { if (c) c->set_error("evplp_selftest: bad arguments"); return EVPLP_ERR_INVALID; }
+    if (!c || !out || capacity < 6 || which < 0 || which > 4) { if (c) c->set_error("evplp_selftest: bad arguments"); return EVPLP_ERR_INVALID; }
     if (hipSetDevice(c->cfg.device) != hipSuccess) return EVPLP_ERR_HIP;
     unsigned long long *d = nullptr;
     if (hipMalloc((void **)&d, 8 * sizeof(unsigned long long)) != hipSuccess) return EVPLP_ERR_OOM;
@@ -304,6 +338,7 @@ extern "C" int evplp_selftest(evplp_context *c, int32_t which, uint64_t *out, in
     if (e == hipSuccess) {
         if (which == 0) hipLaunchKernelGGL(evplp::selftest_rcp_kernel, dim3(4096), dim3(256), 0, c->stream, d);
         else if (which == 1) hipLaunchKernelGGL(evplp::selftest_pow_kernel, dim3(4096), dim3(256), 0, c->stream, d);
+        else if (which == 4) hipLaunchKernelGGL(evplp::selftest_vsl_primitives_kernel, dim3(4096), dim3(256), 0, c->stream, d);
         else if (which == 3) {
             evplp::SynTestRec *recs = nullptr;
             e = hipMalloc((void **)&recs, sizeof(evplp::SynTestRec) * evplp::kSynTestNodes);

@@ -864,6 +864,10 @@ int evplp_accel_stack_entries(const evplp_context *ctx);
  * segment end point; zero half-sizes; coordinates at 1e-15 .. 1e15): out[0] differences in the two entered-lane masks, the next
  * node, the stack pointer and the stack register (must be 0), [1] cases (lanes x children), [2] entered lanes x children of the
  * scalar-operand visit, [3] / [4] / [5] those of classes 0 and 1, 2 and 3, 4 and 5 (the odd class in the upper 32 bits).
+ * which = 4: the hardware primitives of the VSL estimators against double precision, maxima in units of 1e-12: out[0] / [1] the absolute
+ * error of v_sin_f32(u) / v_cos_f32(u) against sin / cos(2 pi u) over all 2^24 uniforms u = (k + 1) 2^-24; [2] the absolute error of
+ * cos_t = exp2(log2(u) rcp(e + 1)) against u^(1 / (e + 1)) for e = 0, 0.5, 1, 20, 200, 1000, 10000 over 2^22 uniforms; [3] / [4] / [5] the
+ * relative error of v_rcp_f32 / v_rsq_f32 / v_sqrt_f32 over 2^22 arguments in [2^-20, 2^20].
  * Returns the number of words written or a negative status. */
 int evplp_selftest(evplp_context *ctx, int32_t which, uint64_t *out, int32_t capacity);
 /* The direction-sampling functions of light tracing (csrc/ev_math.h: evm_sincosf, evm_powf) as the DEVICE computes them, on host arrays of n

@@ -123,6 +123,22 @@ def test_hardware_power_function_of_the_phong_lobes(ctx):
     assert len(err) == 6 and (err > 0).all() and err.max() <= 2e-6, err
 
 
+def test_hardware_primitives_of_the_vsl_estimators(ctx):
+    """The VSL estimators take every sampled direction with v_sin_f32 / v_cos_f32 (in revolutions), the Phong samples' cos_t with
+    exp2(log2(u) rcp(e + 1)), and their reciprocals and square roots with the 1-ulp v_rcp_f32 / v_rsq_f32 / v_sqrt_f32 (kernels_gather.hip,
+    namespace vslm).  evplp_selftest(4) measures them on the part against double precision -- all 2^24 uniforms for sin / cos, 2^22 for cos_t
+    with e in the material domain's E_SET and 10 000, 2^22 arguments in [2^-20, 2^20] for the three others -- and the float64 comparison of
+    the estimators (test_gpu_shading_domain.py) rests on the constants asserted here: they enter its direction-error term."""
+    import shading_domain as sd
+    err = ctx.selftest(4).astype(np.float64) * 1e-12
+    assert len(err) == 6 and (err > 0).all(), err
+    v_sin, v_cos, cos_t, rcp, rsq, sqrt = err
+    print(f"\nselftest(4): |v_sin - sin| {v_sin:.3e}, |v_cos - cos| {v_cos:.3e}, |cos_t - u^(1/(e+1))| {cos_t:.3e}; relative: rcp {rcp:.3e}, rsq {rsq:.3e}, sqrt {sqrt:.3e}")
+    assert v_sin <= sd.A_SINCOS and v_cos <= sd.A_SINCOS, (v_sin, v_cos, sd.A_SINCOS)
+    assert cos_t <= sd.A_POW, (cos_t, sd.A_POW)
+    assert max(rcp, rsq, sqrt) <= 2.0 ** -23, (rcp, rsq, sqrt)          # the 1-ulp claims
+
+
 def test_direction_sampling_functions_give_the_oracles_bits_on_the_device(ctx, oracle):
     """What the byte-equality of the light-path records does NOT prove by itself: the oracle #includes the product's csrc/ev_math.h, so the
     sampled directions' sin / cos / pow agree by construction IF that header computes the same bits under gcc on the host and under clang on

@@ -8,6 +8,7 @@ import pytest
 
 import oracle_api as oa
 import scenes
+from shading_domain import vsl_stream as _vsl_stream     # the estimators' generator restated in integers, beside its vectorised form
 
 
 @pytest.fixture(scope="module")
@@ -55,32 +56,6 @@ def test_rng_known_answers(oracle):
     oracle.evo_rng_init(C.byref(r), 1, 2, 3)
     u = np.array([oracle.evo_rng_uniform(C.byref(r)) for _ in range(20000)])
     assert u.min() > 0.0 and u.max() <= 1.0 and abs(u.mean() - 0.5) < 0.01      # (0,1] like curand_uniform
-
-
-_M64 = (1 << 64) - 1
-
-
-def _splitmix64(x):
-    x = (x + 0x9E3779B97F4A7C15) & _M64
-    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
-    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
-    return x ^ (x >> 31)
-
-
-def _vsl_stream(index, seq, sub, steps):
-    """Pure-python restatement of the estimators' generator (oracle: evo_vsl_rng_init / evo_vsl_rng_step): xoroshiro64, the state
-    words after every step."""
-    pk, rk = _splitmix64((seq << 32) | index), _splitmix64((sub * 0xD1B54A32D192ED03) & _M64)
-    a, b = (pk ^ rk) & 0xFFFFFFFF, ((pk >> 32) ^ (rk >> 32)) & 0xFFFFFFFF
-    t = a * (b | 1)
-    s0, s1 = (t & 0xFFFFFFFF) ^ b, ((t >> 32) ^ a) | 0x80000000
-    rotl = lambda x, k: ((x << k) | (x >> (32 - k))) & 0xFFFFFFFF
-    out = []
-    for _ in range(steps):
-        t = s1 ^ s0
-        s0, s1 = rotl(s0, 26) ^ t ^ ((t << 9) & 0xFFFFFFFF), rotl(t, 13)
-        out.append((s0, s1))
-    return out
 
 
 def test_vsl_rng_known_answers_and_statistics(oracle):

@@ -1,5 +1,9 @@
 """The oracle's pair shading against its float64 restatement, on inputs that visit every arm (tests/shading_domain.py).
 
+The VSL estimators (evo_gather_vsl, evo_vsl_splat_pair) are compared with vsl_pair_f64 on every (pixel, record, seed) under
+    |x - f64| <= sum over terms of (K 2^-24 kappa_term) |term| + K 2^-24 kappa_pair |f64| + n_terms 2^-24 sum |term| + 1e-20
+(shading_domain.bar_vsl); the rest of this text is about the VPL / LVC gather and the splat.
+
 evo_vpl_splat_pair / evo_photon_frag (and the whole-frame evo_gather_vpl / evo_splat_photons, which tile-level mistakes would show in)
 are compared with vpl_pair_f64 / photon_frag_f64 on every (pixel, record, mode):
     |x - f64| <= (K 2^-24 kappa) |f64| + 1e-20        on decided pairs
@@ -22,6 +26,12 @@ import shading_domain as sd
 # splat 0 of 415 pairs inside the radius, no pixel within 1e-4 r of it; 37 VPL records, 24 photons.
 K_ORACLE_GATHER = 4
 K_ORACLE_SPLAT = 9
+# The VSL estimators (evo_gather_vsl with one slot usable, against vsl_pair_f64 under bar_vsl), measured 2026-10-19 with the same command:
+# worst error / (2^-24 (sum kappa_term |term| + kappa_pair |f64|)), after what K does not multiply, 0.589 under seed 11 (lambert_h0.05) and
+# 0.639 (lambert_h0.001) under seed 0x9E3779B9; each estimator alone (evo_vsl_splat_pair, only = 1 / 2 / 3) 0.524 / 0.175 / 0.276.  The smallest integer that
+# holds is 1: kappa_term carries the sampled direction's error in units of 2^-24 (6 - 60 of them), which the oracle's libm does not use up.
+# The caps, same run: 3 undecided pixels under the worst record and 26 of 43120 lit pairs under seed 11, 2 and 13 under the other; 39 records (caps: 16, and 0.5 %).
+K_ORACLE_VSL = 1
 
 MODES = [0, 1, 2, 3, 4, 5]
 HW = (sd.H, sd.W)
@@ -200,3 +210,114 @@ def test_arms_are_visited(dom):
     assert not dom.photon_ref(0, pb["mix_w_zero"])[0].any() and dom.photon_ref(0, pb["cc_zero"])[0].any() and not dom.photon_ref(4, pb["cc_zero"])[0].any()
     v5 = dom.photon_ref(5, pb["brdf2_zero_channel"])[0]
     assert not v5[..., 1].any() and v5[..., 0].any()
+
+
+# ------------------------------------------------------------------------------------------------------------------ VSL
+def _vsl_check(got, r, K, what, parts=None):
+    """the bar on the decided pixels of one (record, seed): of the MIS-combined value, or of estimator `parts` alone"""
+    val, (A, L, S, n) = (r.value, (r.A, r.L, r.S, r.n)) if parts is None else (r.parts[parts], r.part_bars[parts])
+    ratio = sd.worst_ratio_vsl(got, val, A, L, S, n, r.kappa_pair, r.decided)
+    ok = np.abs(got - val) <= sd.bar_vsl(val, A, L, S, n, r.kappa_pair, K, False)
+    bad = np.argwhere(~ok.all(-1) & r.decided)
+    assert bad.size == 0, (what, ratio, bad[:4].tolist(), got[tuple(bad[0])], val[tuple(bad[0])])
+    return ratio
+
+
+@pytest.mark.parametrize("seed", sd.VSL_SEEDS)
+def test_vsl_per_record(dom, seed):
+    """evo_gather_vsl with one slot usable against vsl_pair_f64 on every record: the bar under K_ORACLE_VSL, the exact zeros, the shaded
+    stencilled-out pixels, the pair count (every pixel: no stencil test) and the caps on the undecided"""
+    fp = oa.frame_params(**sd.vsl_params(seed))
+    names = dom.vsl_pixel_names
+    black = np.array([["black" in t for t in row] for row in names])
+    off = np.array([["stencil_off_shaded" in t for t in row] for row in names])
+    assert black.sum() == len(sd.VSL_BLACK_PIXELS) and off.sum() > 10 and not dom.vsl_pixel.stencil[off].any()
+    worst, worst_name, und, lit_pairs, samples, off_lit, off_shaded = 0.0, "", [], 0, 0, 0, 0
+    for k, name in enumerate(dom.vsl_names):
+        r = dom.vsl_ref(seed, k)
+        img, pairs = dom.oracle_scene.gather(fp, sd.W, sd.H, dom.vsl_gbuf, sd.only_slot(dom.vsls, k, 1), vsl=True)
+        assert pairs == sd.W * sd.H, (name, pairs)
+        assert np.all(img[..., 3] == 0.0)
+        got = img[..., :3].astype(np.float64) * sd.NPATHS
+        ratio = _vsl_check(got, r, K_ORACLE_VSL, ("evo_gather_vsl", seed, name))
+        if ratio > worst: worst, worst_name = ratio, name
+        assert np.all(got[~r.lit] == 0.0) and np.all(got[black] == 0.0), (seed, name)
+        assert np.all(r.value[black] == 0.0) and r.lit[black].any() == r.lit.any()
+        if name in sd.VSL_DARK:
+            assert np.all(got == 0.0) and np.all(r.value == 0.0), (seed, name)
+        else:
+            shaded = off & r.lit & r.decided
+            # (a lit pair may still be exactly 0 -- every cone sample of a grazing pair under c1 c2 <= 1e-9, no BRDF sample in the cone -- so:
+            # non-zero wherever float64 is, and that is nearly everywhere)
+            assert np.array_equal(got[shaded].sum(-1) > 0.0, r.value[shaded].sum(-1) > 0.0), (seed, name, "a stencilled-out pixel is not shaded")
+            off_lit += int(shaded.sum()); off_shaded += int((got[shaded].sum(-1) > 0.0).sum())
+            assert (got[shaded].sum(-1) > 0.0).any() or not shaded.any(), (seed, name)
+        und.append(int((~r.decided & r.lit).sum())); lit_pairs += int(r.lit.sum())
+        samples += sd.vsl_samples(r)
+    caps = sd.check_caps(und, lit_pairs, per_record=16)
+    print(f"\nevo_gather_vsl seed {seed:#x}: K_ORACLE_VSL measurement: worst error / (2^-24 (sum kappa |term| + kappa_pair |f64|)) = {worst:.3f} ({worst_name}); "
+          f"undecided: worst record {caps[0]}, all {caps[1]} of {lit_pairs} lit pairs; {samples} sample-iterations on lit decided pairs")
+    assert lit_pairs > 40000 and off_shaded > 0.95 * off_lit > 500, (off_shaded, off_lit)
+
+
+def test_vsl_each_estimator_alone(dom, oracle):
+    """evo_vsl_splat_pair with only = 1 / 2 / 3 (the cone, the pixel-BRDF, the VSL-BRDF estimator alone, weight 1) on a sample of pixels of
+    every tile class, whole and ragged, and the black and stencilled-out pixels, against the restatement's three partial sums"""
+    seed = sd.VSL_SEEDS[0]
+    fp = oa.frame_params(**sd.vsl_params(seed))
+    pos, nrm, dif, phg = dom.vsl_gbuf
+    wi = wi10_f32(pos)
+    a = lambda arr: arr.ctypes.data
+    fn, fpp = oracle.evo_vsl_splat_pair, C.addressof(fp)
+    pick = np.zeros(HW, bool)
+    seen = set()
+    for ty in range(4):
+        for tx in range(6):
+            key = (sd.TILES[ty][tx], ty == 3 or tx == 5)
+            if key in seen:
+                continue
+            seen.add(key)
+            for lane in (0, 9, 18, 27, 36, 45, 54, 63, 5, 58):
+                y, x = ty * 8 + (lane >> 3), tx * 8 + (lane & 7)
+                if y < sd.H and x < sd.W:
+                    pick[y, x] = True
+    for y, x in sd.VSL_BLACK_PIXELS:
+        pick[y, x] = True
+    pick |= np.array([["stencil_off_shaded" in t for t in row] for row in dom.vsl_pixel_names])
+    assert {c for c, _ in seen} == set(sd.TILE_CLASSES) and pick.sum() > 120
+    out = np.zeros(3, np.float32)
+    worst = [0.0, 0.0, 0.0]; nonzero = [0, 0, 0]
+    for k, name in enumerate(dom.vsl_names):
+        r = dom.vsl_ref(seed, k)
+        rec = dom.vsls[k:k + 1].copy()
+        for only in (1, 2, 3):
+            got = r.parts[only - 1].copy()          # (the pixels that are not picked compare with themselves)
+            for y, x in np.argwhere(pick):
+                i = int(y) * sd.W + int(x)
+                fn(fpp, a(wi) + 12 * i, a(pos) + 16 * i, a(nrm) + 16 * i, a(dif) + 16 * i, a(phg) + 16 * i, float(phg[y, x, 3]), a(rec), 1,
+                   i, seed, 1 + k, only, 0, a(out))
+                got[y, x] = out
+            worst[only - 1] = max(worst[only - 1], _vsl_check(got, r, K_ORACLE_VSL, ("evo_vsl_splat_pair", only, name), parts=only - 1))
+            assert np.all(got[pick & ~r.lit] == 0.0), (only, name)
+            nonzero[only - 1] += int((got[pick].sum(-1) > 0.0).sum())
+    assert min(nonzero) > 100, nonzero            # (the BRDF samples hit a cone rarely: most of their pairs are 0; measured 4557 / 174 / 217)
+    print(f"\nevo_vsl_splat_pair alone: worst ratio cone {worst[0]:.3f}, pixel-BRDF {worst[1]:.3f}, VSL-BRDF {worst[2]:.3f}; non-zero pairs {nonzero} of {int(pick.sum())} pixels x {len(dom.vsl_names)} records")
+
+
+def test_vsl_arms_are_visited(dom):
+    """the VSL inputs reach the arms the estimators have: hemispherical cones (101 samples) down to one-sample cones with 1 - cos ~ 5e-5,
+    both forms of the generator's consumption rules, both lobe choices on both sides"""
+    seed = sd.VSL_SEEDS[0]
+    by = {n: k for k, n in enumerate(dom.vsl_names)}
+    ns = np.concatenate([dom.vsl_ref(seed, k).num_samples[dom.vsl_ref(seed, k).lit] for k in range(len(dom.vsl_names))])
+    assert ns.max() == 101 and ns.min() == 1 and len(np.unique(ns)) > 50
+    r = dom.vsl_ref(seed, by["lambert_h50"])
+    assert 1.9e4 < r.kappa_pair[r.lit].min() - 1.0 < 2.1e4 and r.num_samples.max() == 1        # 1 - cos ~ 5e-5
+    hemi = [int((dom.vsl_ref(seed, k).kappa_pair[dom.vsl_ref(seed, k).lit] < 2.001).sum()) for k in range(len(dom.vsl_names))]
+    assert hemi[by["lambert_h0.001"]] >= 3 and sum(hemi) >= 12, hemi      # rdratio >= 1, the hemisphere: the pixels within 0.5 of a record (0.41 apart)
+    for name in ("psel_lies", "glossy_e20_p0.3", "lambert_h0.5"):   # every estimator contributes somewhere
+        r = dom.vsl_ref(seed, by[name])
+        assert all((p.sum(-1) > 0).sum() > 5 for p in r.parts), name
+    rec = dom.vsls[by["psel_lies"]]
+    true = rec["rho_d"].max() / (rec["rho_d"].max() + rec["rho_s"].max())
+    assert abs(float(rec["p_select_lambert"]) - float(true)) > 0.2
