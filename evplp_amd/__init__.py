@@ -158,6 +158,14 @@ _SIGNATURES = {
     "evplp_transform_mesh": (C.c_int, [_P, C.c_int32, _P]),
     "evplp_transform_points": (C.c_int, [_P, _P, _P, C.c_int32]),
     "evplp_group_transform_mesh": (C.c_int, [_P, C.c_int32, _P]),
+    "evplp_set_mesh_skin": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, C.c_int32]),
+    "evplp_pose_mesh": (C.c_int, [_P, C.c_int32, _P, C.c_int32]),
+    "evplp_skin_points": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, C.c_int32]),
+    "evplp_mesh_count": (C.c_int, [_P]),
+    "evplp_mesh_info": (C.c_int, [_P, C.c_int32, _P, _P, _P]),
+    "evplp_mesh_vertices": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32]),
+    "evplp_group_set_mesh_skin": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, C.c_int32]),
+    "evplp_group_pose_mesh": (C.c_int, [_P, C.c_int32, _P, C.c_int32]),
     "evplp_refit_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     "evplp_refit_levels": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32]),
     "evplp_debug_accel": (C.c_int, [_P, C.c_int32, _P, C.c_size_t]),
@@ -544,6 +552,38 @@ class Context:
         m = _f32(m).reshape(12)
         self._check(self._lib.evplp_transform_mesh(self._h, int(mesh), _ptr(m)))
 
+    def set_mesh_skin(self, mesh: int, nbones: int, bone_index=None, weight=None):
+        """evplp_set_mesh_skin: four bone indices (n, 4) and four weights (n, 4) per vertex of mesh `mesh` over nbones bones; constant for the
+        topology, moves nothing, marks nothing dirty; nbones = 0 removes the skin"""
+        if int(nbones) == 0 and bone_index is None and weight is None:
+            return self._check(self._lib.evplp_set_mesh_skin(self._h, int(mesh), 0, None, None, 0))
+        b = np.ascontiguousarray(bone_index, np.int32).reshape(-1, 4)
+        w = _f32(weight).reshape(-1, 4)
+        if b.shape != w.shape:
+            raise ValueError("set_mesh_skin: bone_index and weight must both be (nverts, 4)")
+        self._check(self._lib.evplp_set_mesh_skin(self._h, int(mesh), int(nbones), _ptr(b), _ptr(w), b.shape[0]))
+
+    def pose_mesh(self, mesh: int, bone_matrices):
+        """evplp_pose_mesh: mesh `mesh` = its rest pose skinned under the palette (nbones, 12) of row-major 3 x 4 matrices (poses do not
+        compose); dirty like update_mesh, but the refit uploads the palette alone"""
+        m = _f32(bone_matrices).reshape(-1, 12)
+        self._check(self._lib.evplp_pose_mesh(self._h, int(mesh), _ptr(m), m.shape[0]))
+
+    def mesh_count(self) -> int:
+        return self._check(self._lib.evplp_mesh_count(self._h))
+
+    def mesh_info(self, mesh: int) -> dict:
+        """evplp_mesh_info: nverts, ntris, material of mesh `mesh` as the host copy holds it"""
+        nv, nt, mat = C.c_int32(), C.c_int32(), C.c_int32()
+        self._check(self._lib.evplp_mesh_info(self._h, int(mesh), C.byref(nv), C.byref(nt), C.byref(mat)))
+        return dict(nverts=nv.value, ntris=nt.value, material=mat.value)
+
+    def mesh_vertices(self, mesh: int, which: int = 0):
+        """evplp_mesh_vertices: the positions (nverts, 3) of mesh `mesh` in the numbering update_mesh expects; which = 0 current, 1 rest pose"""
+        out = np.empty((self.mesh_info(mesh)["nverts"], 3), np.float32)
+        self._check(self._lib.evplp_mesh_vertices(self._h, int(mesh), int(which), _ptr(out), out.shape[0]))
+        return out
+
     def refit_accel(self):
         """evplp_refit_accel: the tree, the triangle operands and the scene's figures follow the updated vertices, on the device; the topology stays"""
         self._check(self._lib.evplp_refit_accel(self._h))
@@ -910,6 +950,22 @@ def transform_points(m, pts):
     return out
 
 
+def skin_points(bone_matrices, bone_index, weight, pts):
+    """evplp_skin_points: the points (n, 3) under the palette (nbones, 12) with four bone indices (n, 4) and weights (n, 4) each, by the
+    function evplp_pose_mesh moves a mesh with (fp32, every product and sum rounded on its own; host only)"""
+    m = _f32(bone_matrices).reshape(-1, 12)
+    p = _f32(pts).reshape(-1, 3)
+    b = np.ascontiguousarray(bone_index, np.int32).reshape(-1, 4)
+    w = _f32(weight).reshape(-1, 4)
+    if b.shape[0] != p.shape[0] or w.shape[0] != p.shape[0]:
+        raise ValueError("skin_points: bone_index and weight must be (n, 4) for (n, 3) points")
+    out = np.empty_like(p)
+    rc = lib().evplp_skin_points(_ptr(m), m.shape[0], _ptr(b), _ptr(w), _ptr(p), _ptr(out), p.shape[0])
+    if rc < 0:
+        raise EvplpError(rc, "evplp_skin_points: a null pointer, nbones outside 1 .. 1024, a bone index out of range, a bad weight, or a matrix entry or result that is not finite")
+    return out
+
+
 def accel_cost(nodes) -> dict:
     """evplp_accel_cost: the SAH cost of a flattened tree (ACCEL_NODE records or raw 64-byte nodes) on the host, in the order and shape of
     the device's sums -- evplp_accel_quality's reference.  EvplpError for an array that is not a tree."""
@@ -1087,6 +1143,19 @@ class Group:
     def transform_mesh(self, mesh: int, m):
         m = _f32(m).reshape(12)
         self._check(self._lib.evplp_group_transform_mesh(self._h, int(mesh), _ptr(m)))
+
+    def set_mesh_skin(self, mesh: int, nbones: int, bone_index=None, weight=None):
+        if int(nbones) == 0 and bone_index is None and weight is None:
+            return self._check(self._lib.evplp_group_set_mesh_skin(self._h, int(mesh), 0, None, None, 0))
+        b = np.ascontiguousarray(bone_index, np.int32).reshape(-1, 4)
+        w = _f32(weight).reshape(-1, 4)
+        if b.shape != w.shape:
+            raise ValueError("set_mesh_skin: bone_index and weight must both be (nverts, 4)")
+        self._check(self._lib.evplp_group_set_mesh_skin(self._h, int(mesh), int(nbones), _ptr(b), _ptr(w), b.shape[0]))
+
+    def pose_mesh(self, mesh: int, bone_matrices):
+        m = _f32(bone_matrices).reshape(-1, 12)
+        self._check(self._lib.evplp_group_pose_mesh(self._h, int(mesh), _ptr(m), m.shape[0]))
 
     def refit_accel(self):
         self._check(self._lib.evplp_group_refit_accel(self._h))

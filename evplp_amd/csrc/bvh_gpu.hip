@@ -21,6 +21,8 @@
 //   a. refit_scatter : the moved triangles' vertices from a packed staging array into TriAttr::v.
 //   a'. refit_transform: the triangles of meshes moved by a matrix (evplp_transform_mesh) from their rest pose on the device into
 //                      TriAttr::v, ONE launch for all such meshes of a refit (a thread finds its mesh in a small table); nothing is uploaded.
+//   a''. refit_skin  : the triangles of meshes posed by bones (evplp_pose_mesh) likewise, from the rest pose, the corner skin and the refit's
+//                      palettes, ONE launch for all such meshes of a refit; 48 B per bone are uploaded.
 //   b. refit_leaves  : every live leaf slot's operands again, in both layouts (the arithmetic emit_leaves_kernel uses).
 //   c. refit_level   : the boxes, one launch per height of the tree, the parents of leaves first and the root last.  The end of a
 //                      launch is the only hand-over between heights: a thread owns one node, reads its children's unpadded boxes
@@ -408,6 +410,30 @@ __global__ __launch_bounds__(256) void refit_transform_kernel(const TransformDes
     if (tri < 0 || tri >= ntri) return;
     transform_point(table[lo].m, rest + 9 * (size_t)tri + 3 * p, attrs[tri].v + 3 * p);
 }
+// The same for the meshes posed by bones (evplp_pose_mesh): one thread per corner of the posed triangles of ALL meshes of the table, its mesh
+// found by the same bisection.  Reads the rest pose, the corner's four indices and weights (skin: nskin corners) and four matrices of the
+// mesh's palette (bones: the refit's palettes one behind the other; a gather from at most 48 KB per mesh, which stays in cache), writes
+// TriAttr::v through skin_point; the rest pose is never written here.  evplp_set_mesh_skin keeps every index below the mesh's bone count;
+// an index at or beyond it reads bone 0 of the mesh rather than memory past the palette.
+__global__ __launch_bounds__(256) void refit_skin_kernel(const SkinDesc *table, int32_t nmesh, int32_t total, const float *rest, const CornerSkin *skin, int32_t nskin, const float *bones,
+                                                         TriAttr *attrs, int32_t ntri) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int j = i / 3, p = i - 3 * j;
+    if (j >= total) return;
+    int lo = 0, hi = nmesh - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (table[mid].begin <= j) lo = mid; else hi = mid - 1;
+    }
+    const SkinDesc d = table[lo];
+    const int32_t tri = d.first + (j - d.begin), corner = d.skin_at + 3 * (j - d.begin) + p;
+    if (j - d.begin >= d.count || tri < 0 || tri >= ntri || corner < 0 || corner >= nskin) return;      // (count: a bad table cannot reach a neighbour's triangles)
+    const CornerSkin s = skin[corner];
+    int32_t b[4];
+    for (int k = 0; k < 4; k++) b[k] = (int32_t)s.b[k] < d.nbones ? (int32_t)s.b[k] : 0;
+    skin_point(bones + 12 * (size_t)d.bone_at, b, s.w, rest + 9 * (size_t)tri + 3 * p, attrs[tri].v + 3 * p);
+}
 // b. one thread per leaf slot.  A triangle that has become degenerate (tri_has_area: meshBound's rule) gets zero operands, which is what a
 // fresh build does by dropping it; an empty slot (tri_index < 0) is zero already and stays.
 __global__ __launch_bounds__(256) void refit_leaves_kernel(const int32_t *tri_index, int32_t nslots, const TriAttr *attrs, int32_t ntri, LeafBlock *leaves, TriFlat *tri_flat) {
@@ -653,6 +679,10 @@ void refit_rest(const TriAttr *attrs, int32_t first, int32_t count, float *d_res
 }
 void refit_transform(const TransformDesc *d_table, int32_t nmesh, int32_t total, const float *d_rest, TriAttr *attrs, int32_t ntri, hipStream_t stream) {
     if (nmesh > 0 && total > 0) hipLaunchKernelGGL(refit_transform_kernel, dim3((unsigned)((3 * (size_t)total + 255) / 256)), dim3(256), 0, stream, d_table, nmesh, total, d_rest, attrs, ntri);
+}
+void refit_skin(const SkinDesc *d_table, int32_t nmesh, int32_t total, const float *d_rest, const CornerSkin *d_skin, int32_t nskin, const float *d_bones, TriAttr *attrs, int32_t ntri, hipStream_t stream) {
+    if (nmesh > 0 && total > 0)
+        hipLaunchKernelGGL(refit_skin_kernel, dim3((unsigned)((3 * (size_t)total + 255) / 256)), dim3(256), 0, stream, d_table, nmesh, total, d_rest, d_skin, nskin, d_bones, attrs, ntri);
 }
 void refit_leaves(const RefitScene &r, hipStream_t stream) {
     if (r.nslots > 0) hipLaunchKernelGGL(refit_leaves_kernel, dim3((unsigned)((r.nslots + 255) / 256)), dim3(256), 0, stream, r.tri_index, r.nslots, r.attrs, r.ntri, r.leaves, r.tri_flat);

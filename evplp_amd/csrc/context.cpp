@@ -1,6 +1,7 @@
 // C-ABI implementation (include/evplp.h): context, scene upload, pass launchers, statistics.
 // There is deliberately no CPU execution path here: every pass is a HIP kernel launch.
 #include "context.hpp"
+#include "host/skin.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -214,6 +215,10 @@ static void free_scene_device(evplp_context *c) {
     hipFree(c->d_rest); hipFree(c->d_xform); if (c->h_xform) hipHostFree(c->h_xform);
     c->d_rest = nullptr; c->d_xform = c->h_xform = nullptr;
     for (HostMesh &m : c->meshes) m.rest_state = 0;
+    // ... and the corner skins, the palettes and the descriptor tables of evplp_pose_mesh (made by the first posed refit; the host keeps every skin)
+    hipFree(c->d_skin); hipFree(c->d_bones); hipFree(c->d_sdesc); if (c->h_bones) hipHostFree(c->h_bones); if (c->h_sdesc) hipHostFree(c->h_sdesc);
+    c->d_skin = nullptr; c->d_bones = c->h_bones = nullptr; c->d_sdesc = c->h_sdesc = nullptr; c->skin_cap = c->bone_cap = 0; c->skin_stale = true;
+    for (HostMesh &m : c->meshes) m.skin_at = -1;
     // ... and the scratch of the rotating sweep (made by the first call that asks for rotations)
     hipFree(c->d_rotate); hipFree(c->d_rotate_out); if (c->h_rotate_out) hipHostFree(c->h_rotate_out);
     c->d_rotate = c->d_rotate_out = c->h_rotate_out = nullptr; std::vector<int32_t>().swap(c->refit_height);
@@ -615,6 +620,34 @@ bool transform_mesh_check(evplp_context *c, int32_t mesh, const float *matrix) {
     }
     return true;
 }
+// evplp_set_mesh_skin's and evplp_pose_mesh's refusals, likewise (the arrays' own by host/skin.cpp).  The posed coordinates are checked on the
+// host copy's rest pose, by the function that will move it.
+bool set_mesh_skin_check(evplp_context *c, int32_t mesh, int32_t nbones, const int32_t *bone_index, const float *weight, int32_t nverts) {
+    if (!c->accel_built) { c->set_error("evplp_set_mesh_skin: scene not built (evplp_build_accel)"); return false; }
+    if (mesh < 0 || mesh >= (int32_t)c->meshes.size()) { c->set_error("evplp_set_mesh_skin: mesh %d out of range (%zu meshes)", mesh, c->meshes.size()); return false; }
+    if (nbones == 0) return true;                   // (the skin is removed: the arrays are not looked at)
+    const size_t have = c->meshes[(size_t)mesh].verts.size() / 3;
+    if (nverts < 0 || (size_t)nverts != have) { c->set_error("evplp_set_mesh_skin: mesh %d has %zu vertices, not %d", mesh, have, nverts); return false; }
+    if (!bone_index || !weight) { c->set_error("evplp_set_mesh_skin: null %s", !bone_index ? "bone_index" : "weight"); return false; }
+    char why[256];
+    if (!skin_arrays_ok(nbones, bone_index, weight, nverts, why, sizeof(why))) { c->set_error("evplp_set_mesh_skin: mesh %d: %s", mesh, why); return false; }
+    return true;
+}
+bool pose_mesh_check(evplp_context *c, int32_t mesh, const float *bone_matrices, int32_t nbones, std::vector<float> *posed_out) {
+    if (!c->accel_built) { c->set_error("evplp_pose_mesh: scene not built (evplp_build_accel)"); return false; }
+    if (mesh < 0 || mesh >= (int32_t)c->meshes.size()) { c->set_error("evplp_pose_mesh: mesh %d out of range (%zu meshes)", mesh, c->meshes.size()); return false; }
+    const HostMesh &m = c->meshes[(size_t)mesh];
+    if (m.skin_bones <= 0) { c->set_error("evplp_pose_mesh: mesh %d has no skin (evplp_set_mesh_skin)", mesh); return false; }
+    if (nbones != m.skin_bones) { c->set_error("evplp_pose_mesh: the skin of mesh %d has %d bones, not %d", mesh, m.skin_bones, nbones); return false; }
+    char why[256];
+    if (!skin_palette_ok(bone_matrices, nbones, why, sizeof(why))) { c->set_error("evplp_pose_mesh: mesh %d: %s", mesh, why); return false; }
+    const std::vector<float> &rest = m.rest.empty() ? m.verts : m.rest;
+    std::vector<float> posed(rest.size());
+    const int64_t bad = skin_apply(bone_matrices, m.skin_index.data(), m.skin_weight.data(), rest.data(), posed.data(), rest.size() / 3);
+    if (bad >= 0) { c->set_error("evplp_pose_mesh: vertex %lld of mesh %d is not finite under the palette", (long long)bad, mesh); return false; }
+    if (posed_out) posed_out->swap(posed);          // (the context's own call keeps the positions the check has just made)
+    return true;
+}
 // evplp_refit_accel's refusal: a triangle the build dropped (no area) that has one now has no leaf slot to go to
 bool refit_check(evplp_context *c) {
     if (!c->accel_built) { c->set_error("evplp_refit_accel: scene not built (evplp_build_accel)"); return false; }
@@ -642,6 +675,7 @@ extern "C" int evplp_update_mesh(evplp_context *c, int32_t mesh, const float *ve
     HostMesh &m = c->meshes[(size_t)mesh];
     std::memcpy(m.verts.data(), vertices, sizeof(float) * 3 * (size_t)nverts);
     std::vector<float>().swap(m.rest); m.rest_state = 0;        // (a new rest pose: the matrix is forgotten, the device's copy is stale)
+    std::vector<float>().swap(m.palette);                       // (... and so is a pose; the skin stays)
     c->mesh_dirty[(size_t)mesh] = 1; c->scene_dirty = true;
     return EVPLP_OK;
 }
@@ -652,27 +686,97 @@ extern "C" int evplp_transform_points(const float *m, const float *in, float *ou
     return EVPLP_OK;
 }
 
+// the first transform or pose of this scene: the rest-pose array and the two descriptor tables of the transform launch
+static int rest_prepare(evplp_context *c, const char *name) {
+    if (c->d_rest) return EVPLP_OK;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipError_t e = hipMalloc((void **)&c->d_rest, sizeof(float) * 9 * (size_t)std::max(c->scene_tris, 1));
+    if (e == hipSuccess) e = hipMalloc((void **)&c->d_xform, sizeof(TransformDesc) * c->meshes.size());
+    if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_xform, sizeof(TransformDesc) * c->meshes.size(), hipHostMallocDefault);
+    if (e != hipSuccess) {
+        hipFree(c->d_rest); hipFree(c->d_xform); c->d_rest = nullptr; c->d_xform = nullptr;
+        c->set_error("%s: the rest pose on the device: %s", name, hipGetErrorString(e)); return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP;
+    }
+    return EVPLP_OK;
+}
+
 extern "C" int evplp_transform_mesh(evplp_context *c, int32_t mesh, const float *matrix) {
     CTX_CHECK(c);
     if (!evplp::transform_mesh_check(c, mesh, matrix)) return EVPLP_ERR_INVALID;
     HostMesh &m = c->meshes[(size_t)mesh];
-    if (!c->d_rest) {               // the first transform of this scene: the rest-pose array and the two descriptor tables
-        HIP_TRY(c, hipSetDevice(c->cfg.device));
-        hipError_t e = hipMalloc((void **)&c->d_rest, sizeof(float) * 9 * (size_t)std::max(c->scene_tris, 1));
-        if (e == hipSuccess) e = hipMalloc((void **)&c->d_xform, sizeof(TransformDesc) * c->meshes.size());
-        if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_xform, sizeof(TransformDesc) * c->meshes.size(), hipHostMallocDefault);
-        if (e != hipSuccess) {
-            hipFree(c->d_rest); hipFree(c->d_xform); c->d_rest = nullptr; c->d_xform = nullptr;
-            c->set_error("evplp_transform_mesh: the rest pose on the device: %s", hipGetErrorString(e)); return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP;
-        }
-    }
+    { const int rc = rest_prepare(c, "evplp_transform_mesh"); if (rc) return rc; }
     // the device's copy of this mesh's rest pose is made by the refit: from the attributes while they still hold it (a clean mesh that has
     // no matrix), from the host's rest pose otherwise
     if (m.rest_state == 0) m.rest_state = (!c->mesh_dirty[(size_t)mesh] && m.rest.empty()) ? 1 : 2;
     if (m.rest.empty()) m.rest = m.verts;
     for (size_t v = 0; v < m.rest.size() / 3; v++) evplp::transform_point(matrix, &m.rest[3 * v], &m.verts[3 * v]);
     std::memcpy(m.matrix, matrix, sizeof(m.matrix));
+    std::vector<float>().swap(m.palette);                       // (a matrix replaces a pose)
     c->mesh_dirty[(size_t)mesh] = 2; c->scene_dirty = true;
+    return EVPLP_OK;
+}
+
+// ---- moving a mesh by bones: the skin (constant for the topology), the pose (a palette of matrices over the rest pose), and the queries a
+// caller needs to build a skin for a scene the library loaded
+extern "C" int evplp_set_mesh_skin(evplp_context *c, int32_t mesh, int32_t nbones, const int32_t *bone_index, const float *weight, int32_t nverts) {
+    CTX_CHECK(c);
+    if (!evplp::set_mesh_skin_check(c, mesh, nbones, bone_index, weight, nverts)) return EVPLP_ERR_INVALID;
+    HostMesh &m = c->meshes[(size_t)mesh];
+    // A pose that no refit has taken to the device yet stays what it is on the host copy: the mesh goes up by upload instead (its rest pose is kept)
+    // -- and the upload overwrites the attributes, so a rest pose that was still to be taken from them (rest_state 1) comes from the host's instead
+    if (c->mesh_dirty[(size_t)mesh] == 3) { c->mesh_dirty[(size_t)mesh] = 1; if (m.rest_state == 1) m.rest_state = 2; }
+    std::vector<float>().swap(m.palette);
+    m.skin_bones = nbones; m.skin_at = -1; c->skin_stale = true;
+    if (nbones == 0) { std::vector<int32_t>().swap(m.skin_index); std::vector<float>().swap(m.skin_weight); return EVPLP_OK; }
+    m.skin_index.assign(bone_index, bone_index + 4 * (size_t)nverts);
+    m.skin_weight.assign(weight, weight + 4 * (size_t)nverts);
+    return EVPLP_OK;
+}
+
+namespace evplp {
+// evplp_pose_mesh behind its check: posed = the mesh's posed positions as pose_mesh_check made them (float3 per vertex).  The group checks once,
+// on the caller's thread against rank 0's copy, and hands the same positions to every rank: the ranks' scenes are the same.
+int pose_mesh_apply(evplp_context *c, int32_t mesh, const float *bone_matrices, int32_t nbones, const float *posed) {
+    HostMesh &m = c->meshes[(size_t)mesh];
+    { const int rc = rest_prepare(c, "evplp_pose_mesh"); if (rc) return rc; }
+    // (the device's copy of the rest pose: as for a matrix)
+    if (m.rest_state == 0) m.rest_state = (!c->mesh_dirty[(size_t)mesh] && m.rest.empty()) ? 1 : 2;
+    if (m.rest.empty()) m.rest = m.verts;
+    std::memcpy(m.verts.data(), posed, sizeof(float) * m.verts.size());    // (skin_apply of the rest pose, by the check)
+    m.palette.assign(bone_matrices, bone_matrices + 12 * (size_t)nbones);   // (a pose replaces a matrix)
+    c->mesh_dirty[(size_t)mesh] = 3; c->scene_dirty = true;
+    return EVPLP_OK;
+}
+}
+
+extern "C" int evplp_pose_mesh(evplp_context *c, int32_t mesh, const float *bone_matrices, int32_t nbones) {
+    CTX_CHECK(c);
+    std::vector<float> posed;
+    if (!evplp::pose_mesh_check(c, mesh, bone_matrices, nbones, &posed)) return EVPLP_ERR_INVALID;
+    return evplp::pose_mesh_apply(c, mesh, bone_matrices, nbones, posed.data());
+}
+
+extern "C" int evplp_mesh_count(evplp_context *c) {
+    CTX_CHECK(c);
+    return (int)c->meshes.size();
+}
+extern "C" int evplp_mesh_info(evplp_context *c, int32_t mesh, int32_t *nverts, int32_t *ntris, int32_t *material) {
+    CTX_CHECK(c);
+    if (mesh < 0 || mesh >= (int32_t)c->meshes.size()) { c->set_error("evplp_mesh_info: mesh %d out of range (%zu meshes)", mesh, c->meshes.size()); return EVPLP_ERR_INVALID; }
+    const HostMesh &m = c->meshes[(size_t)mesh];
+    if (nverts) *nverts = (int32_t)(m.verts.size() / 3);
+    if (ntris) *ntris = (int32_t)(m.idx.size() / 3);
+    if (material) *material = m.material;
+    return EVPLP_OK;
+}
+extern "C" int evplp_mesh_vertices(evplp_context *c, int32_t mesh, int32_t which, float *out_xyz, int32_t capacity_verts) {
+    CTX_CHECK(c);
+    if (mesh < 0 || mesh >= (int32_t)c->meshes.size()) { c->set_error("evplp_mesh_vertices: mesh %d out of range (%zu meshes)", mesh, c->meshes.size()); return EVPLP_ERR_INVALID; }
+    if (which != 0 && which != 1) { c->set_error("evplp_mesh_vertices: which must be 0 (current) or 1 (rest pose), not %d", which); return EVPLP_ERR_INVALID; }
+    const HostMesh &m = c->meshes[(size_t)mesh];
+    const std::vector<float> &src = (which == 1 && !m.rest.empty()) ? m.rest : m.verts;
+    if (!out_xyz || capacity_verts < 0 || (size_t)capacity_verts < src.size() / 3) { c->set_error("evplp_mesh_vertices: mesh %d has %zu vertices: a null destination or too small a capacity (%d)", mesh, src.size() / 3, capacity_verts); return EVPLP_ERR_INVALID; }
+    std::memcpy(out_xyz, src.data(), sizeof(float) * src.size());
     return EVPLP_OK;
 }
 
@@ -745,6 +849,46 @@ static void rotate_finish(evplp_context *c, int32_t passes) {
     c->sc.stack4_entries = c->h_rotate_out[2 * (passes - 1) + 1] + 2;   // (kernels.h takes the smaller of this and the generic bound of the depth)
 }
 
+// A refit with posed meshes (behind the wait for the last refit's copies).  begin[mi]: where skinned mesh mi's corner skin lies in d_skin --
+// the skinned meshes one behind the other, in corners.  When the set of skinned meshes has changed (or nothing is there yet) the arrays are
+// made for it: the corner skins, the palette array for all skinned meshes' bones on the device and in pinned memory, the descriptor tables;
+// every mesh's part then goes up again at its next posed refit.  src[mi]: where the part of a posed mesh the device lacks lies in
+// c->skin_upload, expanded here from the per-vertex skin through the mesh's index array.
+static int skin_prepare(evplp_context *c, const std::vector<int32_t> &first, std::vector<int32_t> &begin, std::vector<size_t> &src) {
+    const size_t nm = c->meshes.size();
+    begin.assign(nm, 0); src.assign(nm, 0);
+    int64_t corners = 0, bones = 0;
+    for (size_t mi = 0; mi < nm; mi++) if (c->meshes[mi].skin_bones > 0) { begin[mi] = (int32_t)corners; corners += 3 * (int64_t)(first[mi + 1] - first[mi]); bones += c->meshes[mi].skin_bones; }
+    if (corners > INT32_MAX) { c->set_error("evplp_refit_accel: %lld skinned triangle corners are more than the skin launch indexes", (long long)corners); return EVPLP_ERR_INVALID; }
+    if (c->skin_stale) {
+        for (HostMesh &m : c->meshes) m.skin_at = -1;
+        if (!c->d_sdesc || corners > c->skin_cap || bones > c->bone_cap) {
+            hipFree(c->d_skin); hipFree(c->d_bones); hipFree(c->d_sdesc); if (c->h_bones) hipHostFree(c->h_bones); if (c->h_sdesc) hipHostFree(c->h_sdesc);
+            c->d_skin = nullptr; c->d_bones = c->h_bones = nullptr; c->d_sdesc = c->h_sdesc = nullptr; c->skin_cap = c->bone_cap = 0;
+            hipError_t e = hipMalloc((void **)&c->d_skin, sizeof(CornerSkin) * (size_t)std::max<int64_t>(corners, 1));
+            if (e == hipSuccess) e = hipMalloc((void **)&c->d_bones, sizeof(float) * 12 * (size_t)std::max<int64_t>(bones, 1));
+            if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_bones, sizeof(float) * 12 * (size_t)std::max<int64_t>(bones, 1), hipHostMallocDefault);
+            if (e == hipSuccess) e = hipMalloc((void **)&c->d_sdesc, sizeof(SkinDesc) * nm);
+            if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_sdesc, sizeof(SkinDesc) * nm, hipHostMallocDefault);
+            if (e != hipSuccess) { c->set_error("evplp_refit_accel: the skins on the device: %s", hipGetErrorString(e)); return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP; }
+            c->skin_cap = (int32_t)corners; c->bone_cap = (int32_t)bones;
+        }
+        c->skin_stale = false;
+    }
+    c->skin_upload.clear();
+    for (size_t mi = 0; mi < nm; mi++) if (c->mesh_dirty[mi] == 3 && c->meshes[mi].skin_at < 0) {
+        const HostMesh &m = c->meshes[mi];
+        src[mi] = c->skin_upload.size();
+        for (size_t k = 0; k < m.idx.size(); k++) {
+            const size_t v = (size_t)m.idx[k];
+            CornerSkin s;
+            for (int q = 0; q < 4; q++) { s.b[q] = (uint16_t)m.skin_index[4 * v + q]; s.w[q] = m.skin_weight[4 * v + q]; }
+            c->skin_upload.push_back(s);
+        }
+    }
+    return EVPLP_OK;
+}
+
 extern "C" int evplp_refit_accel(evplp_context *c) {
     CTX_CHECK(c);
     if (!evplp::refit_check(c)) return EVPLP_ERR_INVALID;
@@ -771,6 +915,8 @@ extern "C" int evplp_refit_accel(evplp_context *c) {
     // included: the call that put it on the second stream made this stream wait for it.
     const bool timed = c->profile_passes, stages = timed && c->profile_kernels;
     if (c->refit_count > 0) HIP_TRY(c, hipEventSynchronize(c->ev_refit_staged));     // (the last refit's copies have left the pinned arrays: long ago)
+    std::vector<int32_t> skin_begin; std::vector<size_t> skin_src;
+    if (std::find(c->mesh_dirty.begin(), c->mesh_dirty.end(), (char)3) != c->mesh_dirty.end() && (rc = skin_prepare(c, first, skin_begin, skin_src))) return rc;
     // 1. the triangles of the meshes dirty by upload, packed, in one copy; one scatter per run of neighbouring such meshes.  Behind them in the
     // pinned array, the rest pose of every mesh that was given a matrix and whose rest pose the device does not hold in any form.
     // (one memcpy per mesh into the pinned array, as ever: what the copy engine then reads was written the way it was before there were matrices)
@@ -781,7 +927,7 @@ extern "C" int evplp_refit_accel(evplp_context *c) {
         staged += n;
     }
     const size_t uploaded = staged;
-    for (size_t mi = 0; mi < c->meshes.size(); mi++) if (c->mesh_dirty[mi] == 2 && c->meshes[mi].rest_state == 2) {
+    for (size_t mi = 0; mi < c->meshes.size(); mi++) if (c->mesh_dirty[mi] >= 2 && c->meshes[mi].rest_state == 2) {
         const size_t n = 9 * (size_t)(first[mi + 1] - first[mi]);
         std::vector<float> rest(n);
         flatten_mesh(c->meshes[mi], c->meshes[mi].rest, rest.data());
@@ -800,8 +946,10 @@ extern "C" int evplp_refit_accel(evplp_context *c) {
     }
     // 1'. the meshes dirty by transform: their rest pose where the device lacks it (once per mesh and rest pose), the table of their matrices
     // through pinned memory, and ONE launch that writes the attributes of all of them from the rest pose.  Nothing of them is staged or copied.
-    int32_t nx = 0, moved = 0;
-    for (size_t mi = 0; mi < c->meshes.size(); mi++) if (c->mesh_dirty[mi] == 2) {
+    // 1''. the meshes dirty by pose likewise: the same rest pose, each mesh's corner skin where the device lacks it (once per mesh and skin),
+    // the palettes one behind the other and the table of their places through pinned memory, and ONE launch that writes all of them.
+    int32_t nx = 0, moved = 0, ns = 0, posed = 0, nbone = 0;
+    for (size_t mi = 0; mi < c->meshes.size(); mi++) if (c->mesh_dirty[mi] >= 2) {
         HostMesh &m = c->meshes[mi];
         const int32_t count = first[mi + 1] - first[mi];
         if (m.rest_state == 1) refit_rest(c->sc.attrs, first[mi], count, c->d_rest, c->stream);
@@ -811,6 +959,17 @@ extern "C" int evplp_refit_accel(evplp_context *c) {
         }
         m.rest_state = 3;
         if (count <= 0) continue;
+        if (c->mesh_dirty[mi] == 3) {
+            if (m.skin_at < 0) {
+                m.skin_at = skin_begin[mi];
+                HIP_TRY(c, hipMemcpyAsync(c->d_skin + m.skin_at, c->skin_upload.data() + skin_src[mi], sizeof(CornerSkin) * 3 * (size_t)count, hipMemcpyHostToDevice, c->stream));
+            }
+            SkinDesc &s = c->h_sdesc[ns++];
+            s.first = first[mi]; s.count = count; s.begin = posed; s.bone_at = nbone; s.nbones = m.skin_bones; s.skin_at = m.skin_at; s.pad[0] = s.pad[1] = 0;
+            std::memcpy(c->h_bones + 12 * (size_t)nbone, m.palette.data(), sizeof(float) * 12 * (size_t)m.skin_bones);
+            posed += count; nbone += m.skin_bones;
+            continue;
+        }
         TransformDesc &d = c->h_xform[nx++];
         d.first = first[mi]; d.count = count; d.begin = moved; d.pad = 0; std::memcpy(d.m, m.matrix, sizeof(d.m));
         moved += count;
@@ -818,6 +977,11 @@ extern "C" int evplp_refit_accel(evplp_context *c) {
     if (nx) {
         HIP_TRY(c, hipMemcpyAsync(c->d_xform, c->h_xform, sizeof(TransformDesc) * (size_t)nx, hipMemcpyHostToDevice, c->stream));
         refit_transform(c->d_xform, nx, moved, c->d_rest, (TriAttr *)c->sc.attrs, c->scene_tris, c->stream);
+    }
+    if (ns) {
+        HIP_TRY(c, hipMemcpyAsync(c->d_sdesc, c->h_sdesc, sizeof(SkinDesc) * (size_t)ns, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->d_bones, c->h_bones, sizeof(float) * 12 * (size_t)nbone, hipMemcpyHostToDevice, c->stream));
+        refit_skin(c->d_sdesc, ns, posed, c->d_rest, c->d_skin, c->skin_cap, c->d_bones, (TriAttr *)c->sc.attrs, c->scene_tris, c->stream);
     }
     if (stages) HIP_TRY(c, hipEventRecord(c->ev_refit[1], c->stream));
     // 2. leaf operands  3. boxes, one launch per height  4. four-wide nodes

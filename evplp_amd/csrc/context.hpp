@@ -18,6 +18,9 @@ void refit_scatter(const float *d_src, int32_t first, int32_t count, TriAttr *at
 // launch per refit writes the attributes of every mesh of d_table from d_rest -- total: the moved triangles of the whole table)
 void refit_rest(const TriAttr *attrs, int32_t first, int32_t count, float *d_rest, hipStream_t stream);
 void refit_transform(const TransformDesc *d_table, int32_t nmesh, int32_t total, const float *d_rest, TriAttr *attrs, int32_t ntri, hipStream_t stream);
+// (meshes posed by bones: ONE skin launch per refit writes the attributes of every mesh of d_table from d_rest, the corner skins d_skin
+// (nskin corners) and the refit's palettes d_bones -- total: the posed triangles of the whole table)
+void refit_skin(const SkinDesc *d_table, int32_t nmesh, int32_t total, const float *d_rest, const CornerSkin *d_skin, int32_t nskin, const float *d_bones, TriAttr *attrs, int32_t ntri, hipStream_t stream);
 void refit_leaves(const RefitScene &r, hipStream_t stream);
 void refit_level(const RefitScene &r, const int32_t *d_order, int32_t count, float pad, hipStream_t stream);
 // (the level launch with tree rotations: d_level = the plan's level per node, d_taken / d_need = per-node scratch, d_root_out = { rotations, need } of the root)
@@ -26,11 +29,14 @@ void refit_rotate_level(const RefitScene &r, const int32_t *d_order, int32_t cou
 void accel_cost(const BvhNode *d_nodes, int32_t nnodes, const int32_t *d_order, int32_t count, double *d_out, hipStream_t stream);
 // rest: the rest pose of a mesh that evplp_transform_mesh has moved (verts = transform_point(matrix, rest)); empty: verts is the rest pose.
 // rest_state, the mesh's part of the device's rest-pose array: 0 not there, 1 to be made from the device's attributes, 2 to be made from
-// `rest`, 3 there.  area, lo / hi (all vertices), alo / ahi / any_area (triangles with an area): the mesh's share of the scene's figures.
+// `rest`, 3 there.  skin_bones > 0: the mesh has a skin (evplp_set_mesh_skin) -- four bone indices and four weights per vertex; palette: the
+// bone matrices of the last evplp_pose_mesh (verts = skin_point(rest) under them) until a matrix or new vertices replace the pose;
+// skin_at: where the mesh's corner skin lies in the device's array (in corners), -1 not there.  area, lo / hi (all vertices), alo / ahi / any_area (triangles with an area): the mesh's share of the scene's figures.
 struct HostMesh {
     std::vector<float> verts, uvs; std::vector<int32_t> idx; int32_t material = 0;
     std::vector<float> rest; float matrix[12] = {}; int rest_state = 0;
     float area = 0.f, lo[3] = {}, hi[3] = {}, alo[3] = {}, ahi[3] = {}; bool any_area = false;
+    int32_t skin_bones = 0, skin_at = -1; std::vector<int32_t> skin_index; std::vector<float> skin_weight, palette;
 };
 struct HostTexture { int32_t w = 0, h = 0; std::vector<float> rgba; };
 struct HostStats { uint64_t rays = 0; };
@@ -49,6 +55,9 @@ namespace evplp {
 // what evplp_update_mesh / evplp_refit_accel refuse (context.cpp), for the group's caller thread as well: false and the reason in c's error
 bool update_mesh_check(evplp_context *c, int32_t mesh, const float *vertices, int32_t nverts);
 bool transform_mesh_check(evplp_context *c, int32_t mesh, const float *m);
+bool set_mesh_skin_check(evplp_context *c, int32_t mesh, int32_t nbones, const int32_t *bone_index, const float *weight, int32_t nverts);
+bool pose_mesh_check(evplp_context *c, int32_t mesh, const float *bone_matrices, int32_t nbones, std::vector<float> *posed_out = nullptr);   // (posed_out: the posed positions)
+int pose_mesh_apply(evplp_context *c, int32_t mesh, const float *bone_matrices, int32_t nbones, const float *posed);   // (behind the check, with its positions)
 bool refit_check(evplp_context *c);
 // what evplp_accel_quality / evplp_set_refit_policy refuse without touching a device (name: the entry point, for the message)
 bool accel_quality_check(evplp_context *c, const char *name);
@@ -147,6 +156,13 @@ struct evplp_context {
     // the device ([meshes] TransformDesc each; ev_refit_staged guards the pinned one); both are freed with the scene.
     std::vector<char> mesh_dirty, tri_dropped; bool scene_dirty = false;
     float *d_rest = nullptr; evplp::TransformDesc *d_xform = nullptr, *h_xform = nullptr;
+    // mesh_dirty: 3 by evplp_pose_mesh.  The first refit with a posed mesh (and the first after the set of skinned meshes changed: skin_stale)
+    // lays the skinned meshes' corner skins out one behind the other in d_skin (skin_cap corners, 24 B each; a mesh's part goes up at its first
+    // posed refit, from skin_upload, which the stream may read until ev_refit_staged) and sizes, for the bones of all skinned meshes together
+    // (bone_cap matrices), the refit's palette array on the device and in pinned host memory, and the descriptor table of the one skin launch
+    // likewise ([meshes] SkinDesc each).  All freed with the scene; a context that never poses allocates none of it.
+    evplp::CornerSkin *d_skin = nullptr; int32_t skin_cap = 0, bone_cap = 0; bool skin_stale = true; std::vector<evplp::CornerSkin> skin_upload;
+    float *d_bones = nullptr, *h_bones = nullptr; evplp::SkinDesc *d_sdesc = nullptr, *h_sdesc = nullptr;
     std::vector<evplp::BvhNode> host_nodes; std::vector<int32_t> refit_level_begin; int32_t refit_levels = 0;
     int32_t *d_refit_order = nullptr; float *d_refit_boxes = nullptr, *d_refit_stage = nullptr, *h_refit_stage = nullptr;
     hipEvent_t ev_refit_staged = nullptr, ev_refit[5] = {}; bool refit_timed = false, refit_stages_timed = false;

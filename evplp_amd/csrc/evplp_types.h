@@ -231,6 +231,21 @@ __host__ __device__ inline void transform_point(const float m[12], const float p
         out[r] = ((a + b) + c) + m[4 * r + 3];
     }
 }
+// ---- evplp_pose_mesh: a point under linear-blend skinning.  bones: a palette of row-major 3 x 4 matrices, b / w: the point's four bone
+// indices and weights.  q_k = transform_point(bones + 12 b[k], p), out[r] = ((w[0] q_0[r] + w[1] q_1[r]) + w[2] q_2[r]) + w[3] q_3[r]: fp32,
+// every product and every sum rounds on its own, in this order, and nothing is fused.  All four influences are always evaluated -- no special
+// case for a zero weight, a repeated bone or the identity -- and nothing is renormalised, so weights (1, 0, 0, 0) over finite matrices give
+// transform_point of bone b[0] value for value (the sign of a zero may differ).  The host copy of a mesh, evplp_skin_points (host/skin.cpp)
+// and refit_skin_kernel (bvh_gpu.hip) call this and nothing else, and a test restates it in numpy.  out may be p.
+__host__ __device__ inline void skin_point(const float *bones, const int32_t b[4], const float w[4], const float p[3], float out[3]) {
+#pragma clang fp contract(off)
+    float q[4][3];
+    for (int k = 0; k < 4; k++) transform_point(bones + 12 * (size_t)b[k], p, q[k]);
+    for (int r = 0; r < 3; r++) {
+        const float a0 = w[0] * q[0][r], a1 = w[1] * q[1][r], a2 = w[2] * q[2][r], a3 = w[3] * q[3][r];
+        out[r] = ((a0 + a1) + a2) + a3;
+    }
+}
 // ---- evplp_project_points / evplp_denoise_temporal: a world point on the screen of a camera, in pixel-centre coordinates (x to the right, y
 // from the bottom: pixel (i, j) has its centre at (i, j)) and its view depth.  fp32, every product and every sum rounds on its own, in this
 // order, and nothing is fused:
@@ -305,6 +320,16 @@ __host__ __device__ inline int32_t rotate_need(const int32_t g[4], const int32_t
 // triangles of the launch (ascending over the table), and its matrix
 struct TransformDesc { int32_t first, count, begin, pad; float m[12]; };
 static_assert(sizeof(TransformDesc) == 64, "one descriptor per 64 bytes");
+// evplp_set_mesh_skin on the device: the skin of one triangle corner -- the vertex's four bone indices (evplp_set_mesh_skin keeps them below
+// 1024) and its four weights as given.  Expanded per corner because TriAttr and the rest pose are per triangle: 72 B per triangle.
+struct CornerSkin { uint16_t b[4]; float w[4]; };
+static_assert(sizeof(CornerSkin) == 24, "one corner per 24 bytes");
+constexpr int32_t kMaxSkinBones = 1024;
+// one posed mesh of a refit, as refit_skin_kernel finds it: its run of original triangles, where the run starts among the posed triangles of
+// the launch (ascending over the table), where its palette starts in the refit's bone array (in matrices) and has how many, and where its
+// corner skin starts (in corners)
+struct SkinDesc { int32_t first, count, begin, bone_at, nbones, skin_at, pad[2]; };
+static_assert(sizeof(SkinDesc) == 32, "one descriptor per 32 bytes");
 
 // the bound on the iterations of a build of n clusters: the search iterations, then halvings
 inline int32_t ploc_iteration_bound(int32_t n, int32_t search_iterations) {

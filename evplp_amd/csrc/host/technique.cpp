@@ -669,6 +669,7 @@ private:
 // "rngAdvance": k >= 0 (default 0): frame f runs with rngOffset + f k, seeds and jitter stream both, so that its files are those of a fresh
 // evplp_render_json of the moved scene with that rngOffset; with 0 every frame uses the same seeds.
 // "rotations": k = 0 .. 8 (default 0: off) is evplp_group_set_refit_rotations: k passes of tree rotations inside every frame's refit.
+// A track may carry, in place of "matrices", "skin" and "poses" (below, parse_poses): its mesh is then posed by bones, one palette per frame.
 // "object": k addresses every mesh the k-th entry of the scene file's "scene" array produced (an OBJ yields one mesh per material group),
 // "object": "arealight" the light, "mesh": i the i-th mesh in upload order.  For frame f = 0 .. F - 1 every track's f-th matrix is applied,
 // the tree is refitted (evplp_group_refit_accel; refitPolicy is evplp_group_set_refit_policy) and the loop runs as a fresh evplp_render_json
@@ -715,9 +716,16 @@ public:
                 if (taken[(size_t)m]) throw JsonError(where + ": mesh " + std::to_string(m) + " is in two of the animation.tracks");
                 taken[(size_t)m] = 1;
             }
+            if (tr.has("matrices") && tr.has("poses")) throw JsonError(where + ".poses: not beside \"matrices\" (a track has exactly one of the two)");
+            if (tr.has("poses")) {
+                parse_poses(tr, where, (size_t)F, track);
+                tracks.push_back(std::move(track));
+                continue;
+            }
+            if (tr.has("skin")) throw JsonError(where + ".skin: only with \"poses\"");
             const std::string mw = where + ".matrices";
             if (!tr.has("matrices") || !tr.at("matrices").is_array() || (long long)tr.at("matrices").size() != F)
-                throw JsonError(mw + ": expected animation.frames (" + std::to_string(F) + ") matrices of 12 numbers");
+                throw JsonError(mw + ": expected animation.frames (" + std::to_string(F) + ") matrices of 12 numbers (or, in its place, \"skin\" and \"poses\")");
             for (size_t f = 0; f < (size_t)F; f++) {
                 const Json &m = tr.at("matrices").at(f);
                 if (!m.is_array() || m.size() != 12) throw JsonError(mw + "[" + std::to_string(f) + "]: expected 12 numbers (a row-major 3 x 4 matrix)");
@@ -766,6 +774,10 @@ public:
         return path.substr(0, dot) + tag + path.substr(dot);
     }
     void start(evplp_group *g) {
+        // (the skins of the "poses" tracks, once: what evplp_set_mesh_skin refuses about the loaded scene -- the vertex count -- is refused here)
+        for (size_t t = 0; on && t < tracks.size(); t++) if (tracks[t].bones > 0)
+            check(g, evplp_group_set_mesh_skin(g, tracks[t].meshes[0], tracks[t].bones, tracks[t].indices.data(), tracks[t].weights.data(), (int32_t)(tracks[t].indices.size() / 4)),
+                  ("animation.tracks[" + std::to_string(t) + "].skin").c_str());
         if (on && policy_ratio > 0.0) check(g, evplp_group_set_refit_policy(g, policy_ratio, policy_builder), "animation.refitPolicy");
         if (on && rotations > 0) check(g, evplp_group_set_refit_rotations(g, rotations), "animation.rotations");
     }
@@ -773,8 +785,10 @@ public:
     void begin_frame(evplp_group *g, int f) {
         if (!on) return;
         frame = f;
-        for (const Track &t : tracks)
+        for (const Track &t : tracks) {
+            if (t.bones > 0) { check(g, evplp_group_pose_mesh(g, t.meshes[0], &t.matrices[12 * (size_t)t.bones * (size_t)f], t.bones), "animation: pose"); continue; }
             for (int32_t m : t.meshes) check(g, evplp_group_transform_mesh(g, m, &t.matrices[12 * (size_t)f]), "animation: transform");
+        }
         check(g, evplp_group_refit_accel(g), "animation: refit");
         refit_ms = 0.f; last_action = 0; cost_ratio = 0.0;
         evplp_context *h0 = evplp_group_context(g, 0);
@@ -794,7 +808,55 @@ public:
     }
 
 private:
-    struct Track { std::vector<int32_t> meshes; std::vector<float> matrices; };       // matrices: [frames][12]
+    // matrices: [frames][12]; a "poses" track (bones > 0): [frames][bones][12], and the skin of its one mesh, [vertices][4] each
+    struct Track { std::vector<int32_t> meshes; std::vector<float> matrices; int32_t bones = 0; std::vector<int32_t> indices; std::vector<float> weights; };
+    // {"mesh": i, "skin": {"bones": B, "indices": [[b0, b1, b2, b3], ... one per vertex], "weights": [[w0, w1, w2, w3], ...]},
+    //  "poses": [[[12 numbers] x B] x F]}: frame f poses the mesh by its f-th palette (evplp_group_pose_mesh: the rest pose skinned, nothing
+    // composes); the skin is set once (evplp_group_set_mesh_skin).  Vertex v is the loader's numbering (evplp_mesh_vertices returns it), so only
+    // "mesh" can carry a skin: one "object" yields several meshes.
+    static void parse_poses(const Json &tr, const std::string &where, size_t F, Track &track) {
+        if (tr.has("object")) throw JsonError(where + ".poses: not with \"object\" (one entry of \"scene\" yields several meshes: per-vertex data needs \"mesh\")");
+        if (!tr.has("skin") || !tr.at("skin").is_object()) throw JsonError(where + ".skin: \"poses\" needs a skin ({\"bones\", \"indices\", \"weights\"})");
+        const Json &sk = tr.at("skin");
+        if (!sk.has("bones")) throw JsonError(where + ".skin.bones: missing required key");
+        const long long B = sk.at("bones").as_int((where + ".skin.bones").c_str());
+        if (B < 1 || B > 1024) throw JsonError(where + ".skin.bones: must be 1 .. 1024");
+        const std::string iw = where + ".skin.indices", ww = where + ".skin.weights";
+        if (!sk.has("indices") || !sk.at("indices").is_array()) throw JsonError(iw + ": expected one list of four bone indices per vertex");
+        if (!sk.has("weights") || !sk.at("weights").is_array()) throw JsonError(ww + ": expected one list of four weights per vertex");
+        if (sk.at("indices").size() != sk.at("weights").size())
+            throw JsonError(ww + ": " + std::to_string(sk.at("weights").size()) + " entries beside " + std::to_string(sk.at("indices").size()) + " of " + iw + " (one of each per vertex)");
+        for (size_t v = 0; v < sk.at("indices").size(); v++) {
+            const Json &bi = sk.at("indices").at(v), &wi = sk.at("weights").at(v);
+            if (!bi.is_array() || bi.size() != 4) throw JsonError(iw + "[" + std::to_string(v) + "]: expected four bone indices");
+            if (!wi.is_array() || wi.size() != 4) throw JsonError(ww + "[" + std::to_string(v) + "]: expected four weights");
+            for (size_t k = 0; k < 4; k++) {
+                const long long b = bi.at(k).as_int((iw + "[" + std::to_string(v) + "]").c_str());
+                if (b < 0 || b >= B) throw JsonError(iw + "[" + std::to_string(v) + "]: bone " + std::to_string(b) + " is outside [0, " + std::to_string(B) + ")");
+                track.indices.push_back((int32_t)b);
+                track.weights.push_back(wi.at(k).as_float((ww + "[" + std::to_string(v) + "]").c_str()));
+            }
+        }
+        const std::string pw = where + ".poses";
+        if (!tr.at("poses").is_array() || tr.at("poses").size() != F)
+            throw JsonError(pw + ": expected animation.frames (" + std::to_string(F) + ") palettes of " + std::to_string(B) + " matrices of 12 numbers");
+        for (size_t f = 0; f < F; f++) {
+            const Json &pal = tr.at("poses").at(f);
+            const std::string fw = pw + "[" + std::to_string(f) + "]";
+            if (!pal.is_array() || (long long)pal.size() != B) throw JsonError(fw + ": expected skin.bones (" + std::to_string(B) + ") matrices of 12 numbers");
+            for (size_t b = 0; b < (size_t)B; b++) {
+                const Json &m = pal.at(b);
+                const std::string bw = fw + "[" + std::to_string(b) + "]";
+                if (!m.is_array() || m.size() != 12) throw JsonError(bw + ": expected 12 numbers (a row-major 3 x 4 matrix)");
+                for (size_t k = 0; k < 12; k++) {
+                    const float v = m.at(k).as_float(bw.c_str());
+                    if (!std::isfinite(v)) throw JsonError(bw + ": entry " + std::to_string(k) + " is not a finite fp32 number");
+                    track.matrices.push_back(v);
+                }
+            }
+        }
+        track.bones = (int32_t)B;
+    }
     std::vector<Track> tracks;
     double policy_ratio = 0.0; int policy_builder = -1; int rotations = 0; uint32_t rng_advance = 0;
     int frame = 0; float refit_ms = 0.f; int last_action = 0; double cost_ratio = 0.0;

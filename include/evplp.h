@@ -134,6 +134,11 @@ typedef struct evplp_config {
      *   refit (after a call)            28 B per node + 36 B per triangle (+ 4 B per light triangle), and the same staging bytes in pinned host memory (evplp_refit_accel)
      *   rest pose (after a call)        36 B per triangle of the scene + 64 B per mesh, and 64 B per mesh in pinned host memory, made by the first
      *                                   evplp_transform_mesh of a scene and freed with it; a context that never transforms allocates none of it
+     *                                   (evplp_pose_mesh counts as a transform here: the first of either makes it)
+     *   skins (after a call)            72 B per triangle of the skinned meshes (per corner four 16-bit bone indices and four float weights) + 48 B
+     *                                   per bone of their skins + 32 B per mesh, and the last two again in pinned host memory, made by the first
+     *                                   refit behind an evplp_pose_mesh and freed with the scene; on the host 32 B per skinned vertex, and 72 B per
+     *                                   triangle of the meshes whose corner skin the last posed refit sent; a context that never poses allocates none
  *   PLOC build (during the call)    88 B per triangle on top of the device LBVH's scratch, freed before evplp_build_accel returns: 2 n clusters in ping-pong (28 B
  *                                   each), n nearest neighbours (4 B), n packed flags and their scan (16 B), children and counts of the inner nodes (12 B)
  *   tree cost (after a call)        24 B per 256 nodes + 8 B, and the same in pinned host memory; the refit's plan and staging (the row above) if no
@@ -318,6 +323,52 @@ int evplp_refit_accel(evplp_context *ctx);
  * the positions evplp_transform_mesh will use, bit for bit.  EVPLP_ERR_INVALID for a null pointer or n < 0. */
 int evplp_transform_mesh(evplp_context *ctx, int32_t mesh, const float m[12]);
 int evplp_transform_points(const float m[12], const float *in, float *out, int32_t n);
+/* ---- moving a mesh by bones: linear-blend skinning of the rest pose on the device; 48 B per bone go up (INTEGRATION B7) ----
+ * A skin gives every vertex four bone indices b[4] and four weights w[4]; a pose is a palette bones[nbones][12] of row-major 3 x 4 matrices.
+ * A point p goes to
+ *   q_k = transform_point(bones + 12 b[k], p) for k = 0 .. 3,   out[r] = ((w[0] q_0[r] + w[1] q_1[r]) + w[2] q_2[r]) + w[3] q_3[r]
+ * in fp32, every product and every sum rounded on its own, in this order, nothing fused (skin_point in evplp_types.h, the one function the
+ * host and the device call).  All four influences are always evaluated -- no special case for a zero weight, a repeated bone or the
+ * identity -- and nothing is renormalised: the weights are used as given.  With weights (1, 0, 0, 0) and finite matrices the result is
+ * transform_point of bone b[0] value for value (the sign of a zero may differ).
+ * evplp_set_mesh_skin attaches a skin to mesh `mesh` (host pointers, int32[nverts][4] and float[nverts][4] in the vertex numbering of
+ * evplp_update_mesh, copied before the call returns).  A skin is constant for the topology: the call moves nothing and marks nothing dirty,
+ * and the skin survives evplp_update_mesh (a new rest pose under the same skin), evplp_build_accel and a policy's rebuild.  nbones = 0
+ * removes the skin (the arrays are not looked at).  EVPLP_ERR_INVALID, nothing changed, the context staying usable: no evplp_build_accel yet,
+ * mesh out of range, a vertex count other than the mesh's, a null pointer, nbones outside 0 .. 1024, an index outside [0, nbones) (also
+ * where its weight is 0), a weight that is not finite or is negative, a vertex whose four weights, added in double, differ from 1 by more
+ * than 1e-3 (the bound only keeps a wrong array out).  A new skin for a mesh whose pose no refit has taken yet leaves the posed positions
+ * in place: that mesh goes up by upload.
+ * evplp_pose_mesh sets the mesh's current positions to skin_point(rest pose) under the palette.  The rest pose is evplp_transform_mesh's:
+ * what evplp_add_mesh or the last evplp_update_mesh gave, never overwritten, so poses do NOT compose and do not drift.  A pose replaces a
+ * matrix of evplp_transform_mesh and a matrix replaces a pose; evplp_update_mesh forgets both and keeps the skin.  The mesh is dirty exactly
+ * as after evplp_update_mesh (every pass is refused until the refit), and the host copy follows through the same function, so bounds, areas,
+ * the light's CDF, evplp_scene_metrics, a rebuild and the refit's degenerate-triangle refusal see the positions the device has.
+ * EVPLP_ERR_INVALID, nothing marked: not built, mesh out of range, the mesh has no skin, nbones is not the skin's, a null pointer, a matrix
+ * entry that is not finite, a posed coordinate that is not finite (checked on the host copy).  A palette that collapses triangles is legal:
+ * they fall under the degenerate rule above.
+ * On the device the skin is expanded per triangle corner, because the attributes and the rest pose are per triangle: four 16-bit indices and
+ * four floats, 24 B per corner, the skinned meshes one behind the other; a mesh's part is made by its first posed refit (and again after a
+ * rebuild or a change of the set of skinned meshes).  A refit uploads nbones x 48 B per posed mesh and a table of (first triangle, count,
+ * palette, corner skin) through pinned memory, and ONE launch writes the attributes of all posed meshes from the shared rest-pose array,
+ * which it never writes; uploaded, transformed and posed meshes may share one refit, and the steady state still has no host wait (the
+ * refit that sends a mesh's corner skin copies it from pageable memory and may wait for that copy).
+ * evplp_skin_points applies the same function to n points (host only, no GPU; bone_index / weight: [n][4]; in and out: float3[n], may be the
+ * same array): the positions evplp_pose_mesh will use, bit for bit.  It has the refusals above that apply to its arguments (here nbones is
+ * 1 .. 1024, n >= 0), and a refused call writes nothing to out. */
+int evplp_set_mesh_skin(evplp_context *ctx, int32_t mesh, int32_t nbones, const int32_t *bone_index /* [nverts][4] */,
+                        const float *weight /* [nverts][4] */, int32_t nverts);
+int evplp_pose_mesh(evplp_context *ctx, int32_t mesh, const float *bone_matrices /* [nbones][12] */, int32_t nbones);
+int evplp_skin_points(const float *bone_matrices, int32_t nbones, const int32_t *bone_index, const float *weight,
+                      const float *in, float *out, int32_t n);
+/* The meshes as the host copy holds them, in the numbering evplp_update_mesh and evplp_set_mesh_skin expect -- what a caller of
+ * evplp_load_scene_json needs to build a skin (the OBJ reader de-duplicates (v, vt) pairs per material group).  evplp_mesh_count: the number
+ * of meshes (negative: an error code).  evplp_mesh_info: each pointer may be null.  evplp_mesh_vertices: float3[nverts] into out_xyz, which
+ * holds capacity_verts vertices; which = 0 the current positions, 1 the rest pose (the same until a matrix or a pose moves the mesh).
+ * EVPLP_ERR_INVALID: mesh out of range, another `which`, a null destination, too small a capacity. */
+int evplp_mesh_count(evplp_context *ctx);
+int evplp_mesh_info(evplp_context *ctx, int32_t mesh, int32_t *nverts, int32_t *ntris, int32_t *material);
+int evplp_mesh_vertices(evplp_context *ctx, int32_t mesh, int32_t which /* 0 current, 1 rest pose */, float *out_xyz, int32_t capacity_verts);
 /* refits since evplp_create, heights of the current tree's plan (0 before its first refit), HIP-event time of the last refit (0 while
  * evplp_profile_passes is off; waits for that refit).  Each pointer may be null. */
 int evplp_refit_info(evplp_context *ctx, int32_t *refits, int32_t *levels, float *last_refit_ms);
@@ -945,6 +996,10 @@ int evplp_group_update_mesh(evplp_group *g, int32_t mesh, const float *vertices,
 int evplp_group_refit_accel(evplp_group *g);
 /* evplp_transform_mesh on every rank (both partitions), refused on the caller's thread likewise; the matrix is copied before the call returns */
 int evplp_group_transform_mesh(evplp_group *g, int32_t mesh, const float m[12]);
+/* evplp_set_mesh_skin / evplp_pose_mesh on every rank (both partitions), refused on the caller's thread likewise; the arrays are copied
+ * before the call returns */
+int evplp_group_set_mesh_skin(evplp_group *g, int32_t mesh, int32_t nbones, const int32_t *bone_index, const float *weight, int32_t nverts);
+int evplp_group_pose_mesh(evplp_group *g, int32_t mesh, const float *bone_matrices, int32_t nbones);
 /* evplp_accel_quality / evplp_set_refit_policy on every rank (both partitions; the calls wait for the ranks).  Scene and tree are replicated,
  * so every rank computes the same doubles and a policy takes the same decision on each; the group returns rank 0's figures and fails
  * (EVPLP_ERR_INVALID) if any rank's differ.  Refused on the caller's thread, the group staying usable, where the plain context refuses. */
