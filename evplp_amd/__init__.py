@@ -166,6 +166,11 @@ _SIGNATURES = {
     "evplp_mesh_vertices": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32]),
     "evplp_group_set_mesh_skin": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, C.c_int32]),
     "evplp_group_pose_mesh": (C.c_int, [_P, C.c_int32, _P, C.c_int32]),
+    "evplp_set_mesh_morph": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32]),
+    "evplp_morph_mesh": (C.c_int, [_P, C.c_int32, _P, C.c_int32]),
+    "evplp_morph_points": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P]),
+    "evplp_group_set_mesh_morph": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32]),
+    "evplp_group_morph_mesh": (C.c_int, [_P, C.c_int32, _P, C.c_int32]),
     "evplp_refit_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     "evplp_refit_levels": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32]),
     "evplp_debug_accel": (C.c_int, [_P, C.c_int32, _P, C.c_size_t]),
@@ -569,6 +574,24 @@ class Context:
         m = _f32(bone_matrices).reshape(-1, 12)
         self._check(self._lib.evplp_pose_mesh(self._h, int(mesh), _ptr(m), m.shape[0]))
 
+    def set_mesh_morph(self, mesh: int, deltas=None):
+        """evplp_set_mesh_morph: morph targets (T, nverts, 3) for mesh `mesh`, T = 1 .. 64; constant for the topology, moves nothing, marks
+        nothing dirty; None removes the targets.  Refused while weights are in force on the mesh"""
+        if deltas is None:
+            return self._check(self._lib.evplp_set_mesh_morph(self._h, int(mesh), 0, None, 0))
+        d = _f32(deltas)
+        if d.ndim != 3 or d.shape[2] != 3:
+            raise ValueError("set_mesh_morph: deltas must be (ntargets, nverts, 3)")
+        self._check(self._lib.evplp_set_mesh_morph(self._h, int(mesh), d.shape[0], _ptr(d), d.shape[1]))
+
+    def morph_mesh(self, mesh: int, weights=None):
+        """evplp_morph_mesh: the base of mesh `mesh` = its rest pose + the weighted deltas (weights do not compose), and its positions that
+        base under the matrix or the pose in force; dirty like update_mesh, but the refit uploads the weights alone.  None takes the weights away"""
+        if weights is None:
+            return self._check(self._lib.evplp_morph_mesh(self._h, int(mesh), None, 0))
+        w = _f32(weights).reshape(-1)
+        self._check(self._lib.evplp_morph_mesh(self._h, int(mesh), _ptr(w), w.shape[0]))
+
     def mesh_count(self) -> int:
         return self._check(self._lib.evplp_mesh_count(self._h))
 
@@ -579,7 +602,7 @@ class Context:
         return dict(nverts=nv.value, ntris=nt.value, material=mat.value)
 
     def mesh_vertices(self, mesh: int, which: int = 0):
-        """evplp_mesh_vertices: the positions (nverts, 3) of mesh `mesh` in the numbering update_mesh expects; which = 0 current, 1 rest pose"""
+        """evplp_mesh_vertices: the positions (nverts, 3) of mesh `mesh` in the numbering update_mesh expects; which = 0 current, 1 rest pose, 2 the morphed base"""
         out = np.empty((self.mesh_info(mesh)["nverts"], 3), np.float32)
         self._check(self._lib.evplp_mesh_vertices(self._h, int(mesh), int(which), _ptr(out), out.shape[0]))
         return out
@@ -966,6 +989,21 @@ def skin_points(bone_matrices, bone_index, weight, pts):
     return out
 
 
+def morph_points(pts, deltas, weights):
+    """evplp_morph_points: the points (n, 3) + the weighted deltas (T, n, 3), by the function evplp_morph_mesh makes a mesh's base with (fp32,
+    every product and sum rounded on its own, in index order; host only)"""
+    p = _f32(pts).reshape(-1, 3)
+    d = _f32(deltas)
+    w = _f32(weights).reshape(-1)
+    if d.ndim != 3 or d.shape[1:] != p.shape or d.shape[0] != w.shape[0]:
+        raise ValueError("morph_points: deltas must be (T, n, 3) for (n, 3) points and T weights")
+    out = np.empty_like(p)
+    rc = lib().evplp_morph_points(_ptr(p), _ptr(d), _ptr(w), w.shape[0], p.shape[0], _ptr(out))
+    if rc < 0:
+        raise EvplpError(rc, "evplp_morph_points: a null pointer, ntargets outside 1 .. 64, or a point, a delta, a weight or a result that is not finite")
+    return out
+
+
 def accel_cost(nodes) -> dict:
     """evplp_accel_cost: the SAH cost of a flattened tree (ACCEL_NODE records or raw 64-byte nodes) on the host, in the order and shape of
     the device's sums -- evplp_accel_quality's reference.  EvplpError for an array that is not a tree."""
@@ -1156,6 +1194,20 @@ class Group:
     def pose_mesh(self, mesh: int, bone_matrices):
         m = _f32(bone_matrices).reshape(-1, 12)
         self._check(self._lib.evplp_group_pose_mesh(self._h, int(mesh), _ptr(m), m.shape[0]))
+
+    def set_mesh_morph(self, mesh: int, deltas=None):
+        if deltas is None:
+            return self._check(self._lib.evplp_group_set_mesh_morph(self._h, int(mesh), 0, None, 0))
+        d = _f32(deltas)
+        if d.ndim != 3 or d.shape[2] != 3:
+            raise ValueError("set_mesh_morph: deltas must be (ntargets, nverts, 3)")
+        self._check(self._lib.evplp_group_set_mesh_morph(self._h, int(mesh), d.shape[0], _ptr(d), d.shape[1]))
+
+    def morph_mesh(self, mesh: int, weights=None):
+        if weights is None:
+            return self._check(self._lib.evplp_group_morph_mesh(self._h, int(mesh), None, 0))
+        w = _f32(weights).reshape(-1)
+        self._check(self._lib.evplp_group_morph_mesh(self._h, int(mesh), _ptr(w), w.shape[0]))
 
     def refit_accel(self):
         self._check(self._lib.evplp_group_refit_accel(self._h))

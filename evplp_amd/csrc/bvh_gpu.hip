@@ -23,6 +23,9 @@
 //                      TriAttr::v, ONE launch for all such meshes of a refit (a thread finds its mesh in a small table); nothing is uploaded.
 //   a''. refit_skin  : the triangles of meshes posed by bones (evplp_pose_mesh) likewise, from the rest pose, the corner skin and the refit's
 //                      palettes, ONE launch for all such meshes of a refit; 48 B per bone are uploaded.
+//   a*. refit_morph  : the triangles of meshes under morph weights (evplp_morph_mesh), rest pose + the weighted deltas, ONE launch for all such
+//                      meshes of a refit, BEFORE a' and a'': into TriAttr::v where no matrix and no pose is in force, else into the base
+//                      array, which a' and a'' then read in place of the rest pose; 4 B per target are uploaded.
 //   b. refit_leaves  : every live leaf slot's operands again, in both layouts (the arithmetic emit_leaves_kernel uses).
 //   c. refit_level   : the boxes, one launch per height of the tree, the parents of leaves first and the root last.  The end of a
 //                      launch is the only hand-over between heights: a thread owns one node, reads its children's unpadded boxes
@@ -434,6 +437,32 @@ __global__ __launch_bounds__(256) void refit_skin_kernel(const SkinDesc *table, 
     for (int k = 0; k < 4; k++) b[k] = (int32_t)s.b[k] < d.nbones ? (int32_t)s.b[k] : 0;
     skin_point(bones + 12 * (size_t)d.bone_at, b, s.w, rest + 9 * (size_t)tri + 3 * p, attrs[tri].v + 3 * p);
 }
+// Morph targets (evplp_morph_mesh): one thread per corner of the morphed triangles of ALL meshes of the table, its mesh found by the same
+// bisection; launched before the two launches above, which then read the base array in place of the rest pose.  Reads the rest pose, the
+// mesh's T weights (weights: the refit's weight sets one behind the other, nweights floats) and the corner's T deltas (deltas: ndelta float3,
+// per mesh target-major [T][3 count], so that neighbouring threads read neighbouring 12 bytes of one target's plane), and writes through
+// morph_point either TriAttr::v (a mesh with no matrix and no pose in force) or the base array (indexed like the rest pose).  A descriptor
+// whose weights or deltas would lie outside their arrays writes nothing.
+__global__ __launch_bounds__(256) void refit_morph_kernel(const MorphDesc *table, int32_t nmesh, int32_t total, const float *rest, const float *weights, int32_t nweights, const float *deltas,
+                                                          int64_t ndelta, float *base, TriAttr *attrs, int32_t ntri) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int j = i / 3, p = i - 3 * j;
+    if (j >= total) return;
+    int lo = 0, hi = nmesh - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (table[mid].begin <= j) lo = mid; else hi = mid - 1;
+    }
+    const MorphDesc d = table[lo];
+    const int32_t tri = d.first + (j - d.begin);
+    if (j - d.begin >= d.count || j < d.begin || tri < 0 || tri >= ntri) return;                             // (count: a bad table cannot reach a neighbour's triangles)
+    const int64_t plane = 3 * (int64_t)d.count;                                                              // (one target's plane of the mesh, in float3)
+    if (d.ntargets < 1 || d.ntargets > kMaxMorphTargets || d.weight_at < 0 || d.weight_at + d.ntargets > nweights || d.delta_at < 0 || d.delta_at + d.ntargets * plane > ndelta) return;
+    const size_t at = 9 * (size_t)tri + 3 * p;
+    float *out = d.to_base ? base + at : attrs[tri].v + 3 * p;
+    morph_point(rest + at, deltas + 3 * ((size_t)d.delta_at + 3 * (size_t)(j - d.begin) + p), (size_t)(3 * plane), weights + d.weight_at, d.ntargets, out);
+}
 // b. one thread per leaf slot.  A triangle that has become degenerate (tri_has_area: meshBound's rule) gets zero operands, which is what a
 // fresh build does by dropping it; an empty slot (tri_index < 0) is zero already and stays.
 __global__ __launch_bounds__(256) void refit_leaves_kernel(const int32_t *tri_index, int32_t nslots, const TriAttr *attrs, int32_t ntri, LeafBlock *leaves, TriFlat *tri_flat) {
@@ -683,6 +712,11 @@ void refit_transform(const TransformDesc *d_table, int32_t nmesh, int32_t total,
 void refit_skin(const SkinDesc *d_table, int32_t nmesh, int32_t total, const float *d_rest, const CornerSkin *d_skin, int32_t nskin, const float *d_bones, TriAttr *attrs, int32_t ntri, hipStream_t stream) {
     if (nmesh > 0 && total > 0)
         hipLaunchKernelGGL(refit_skin_kernel, dim3((unsigned)((3 * (size_t)total + 255) / 256)), dim3(256), 0, stream, d_table, nmesh, total, d_rest, d_skin, nskin, d_bones, attrs, ntri);
+}
+void refit_morph(const MorphDesc *d_table, int32_t nmesh, int32_t total, const float *d_rest, const float *d_weights, int32_t nweights, const float *d_deltas, int64_t ndelta, float *d_base, TriAttr *attrs,
+                 int32_t ntri, hipStream_t stream) {
+    if (nmesh > 0 && total > 0)
+        hipLaunchKernelGGL(refit_morph_kernel, dim3((unsigned)((3 * (size_t)total + 255) / 256)), dim3(256), 0, stream, d_table, nmesh, total, d_rest, d_weights, nweights, d_deltas, ndelta, d_base, attrs, ntri);
 }
 void refit_leaves(const RefitScene &r, hipStream_t stream) {
     if (r.nslots > 0) hipLaunchKernelGGL(refit_leaves_kernel, dim3((unsigned)((r.nslots + 255) / 256)), dim3(256), 0, stream, r.tri_index, r.nslots, r.attrs, r.ntri, r.leaves, r.tri_flat);

@@ -1,6 +1,7 @@
 // C-ABI implementation (include/evplp.h): context, scene upload, pass launchers, statistics.
 // There is deliberately no CPU execution path here: every pass is a HIP kernel launch.
 #include "context.hpp"
+#include "host/morph.hpp"
 #include "host/skin.hpp"
 
 #include <algorithm>
@@ -219,6 +220,10 @@ static void free_scene_device(evplp_context *c) {
     hipFree(c->d_skin); hipFree(c->d_bones); hipFree(c->d_sdesc); if (c->h_bones) hipHostFree(c->h_bones); if (c->h_sdesc) hipHostFree(c->h_sdesc);
     c->d_skin = nullptr; c->d_bones = c->h_bones = nullptr; c->d_sdesc = c->h_sdesc = nullptr; c->skin_cap = c->bone_cap = 0; c->skin_stale = true;
     for (HostMesh &m : c->meshes) m.skin_at = -1;
+    // ... and the corner deltas, the base array, the weight sets and the descriptor tables of evplp_morph_mesh (made by the first morphed refit; the host keeps every target)
+    hipFree(c->d_morph); hipFree(c->d_base); hipFree(c->d_mweights); hipFree(c->d_mdesc); if (c->h_mweights) hipHostFree(c->h_mweights); if (c->h_mdesc) hipHostFree(c->h_mdesc);
+    c->d_morph = c->d_base = c->d_mweights = c->h_mweights = nullptr; c->d_mdesc = c->h_mdesc = nullptr; c->morph_cap = 0; c->weight_cap = 0; c->morph_stale = true;
+    for (HostMesh &m : c->meshes) { m.morph_at = -1; m.base_state = 0; }
     // ... and the scratch of the rotating sweep (made by the first call that asks for rotations)
     hipFree(c->d_rotate); hipFree(c->d_rotate_out); if (c->h_rotate_out) hipHostFree(c->h_rotate_out);
     c->d_rotate = c->d_rotate_out = c->h_rotate_out = nullptr; std::vector<int32_t>().swap(c->refit_height);
@@ -613,7 +618,7 @@ bool transform_mesh_check(evplp_context *c, int32_t mesh, const float *matrix) {
     if (!matrix) { c->set_error("evplp_transform_mesh: null matrix"); return false; }
     for (int i = 0; i < 12; i++) if (!std::isfinite(matrix[i])) { c->set_error("evplp_transform_mesh: matrix entry %d is not finite", i); return false; }
     const HostMesh &m = c->meshes[(size_t)mesh];
-    const std::vector<float> &rest = m.rest.empty() ? m.verts : m.rest;
+    const std::vector<float> &rest = mesh_base(m);             // (the morphed base while morph weights are in force)
     for (size_t v = 0; v < rest.size() / 3; v++) {
         float o[3]; transform_point(matrix, &rest[3 * v], o);
         if (!std::isfinite(o[0]) || !std::isfinite(o[1]) || !std::isfinite(o[2])) { c->set_error("evplp_transform_mesh: vertex %zu of mesh %d is not finite under the matrix", v, mesh); return false; }
@@ -641,11 +646,52 @@ bool pose_mesh_check(evplp_context *c, int32_t mesh, const float *bone_matrices,
     if (nbones != m.skin_bones) { c->set_error("evplp_pose_mesh: the skin of mesh %d has %d bones, not %d", mesh, m.skin_bones, nbones); return false; }
     char why[256];
     if (!skin_palette_ok(bone_matrices, nbones, why, sizeof(why))) { c->set_error("evplp_pose_mesh: mesh %d: %s", mesh, why); return false; }
-    const std::vector<float> &rest = m.rest.empty() ? m.verts : m.rest;
+    const std::vector<float> &rest = mesh_base(m);             // (the morphed base while morph weights are in force)
     std::vector<float> posed(rest.size());
     const int64_t bad = skin_apply(bone_matrices, m.skin_index.data(), m.skin_weight.data(), rest.data(), posed.data(), rest.size() / 3);
     if (bad >= 0) { c->set_error("evplp_pose_mesh: vertex %lld of mesh %d is not finite under the palette", (long long)bad, mesh); return false; }
     if (posed_out) posed_out->swap(posed);          // (the context's own call keeps the positions the check has just made)
+    return true;
+}
+// evplp_set_mesh_morph's and evplp_morph_mesh's refusals, likewise (the arrays' own, and every loop over the vertices, by host/morph.cpp).  The
+// final coordinates -- the morphed base under the matrix or the pose in force -- are checked on the host copy, by the functions that move it.
+bool set_mesh_morph_check(evplp_context *c, int32_t mesh, int32_t ntargets, const float *deltas, int32_t nverts) {
+    if (!c->accel_built) { c->set_error("evplp_set_mesh_morph: scene not built (evplp_build_accel)"); return false; }
+    if (mesh < 0 || mesh >= (int32_t)c->meshes.size()) { c->set_error("evplp_set_mesh_morph: mesh %d out of range (%zu meshes)", mesh, c->meshes.size()); return false; }
+    const HostMesh &m = c->meshes[(size_t)mesh];
+    if (!m.morph_w.empty()) { c->set_error("evplp_set_mesh_morph: mesh %d has morph weights in force: take them away first (evplp_morph_mesh(ctx, mesh, NULL, 0))", mesh); return false; }
+    if (ntargets == 0) return true;                 // (the targets are removed: the array is not looked at)
+    const size_t have = m.verts.size() / 3;
+    if (nverts < 0 || (size_t)nverts != have) { c->set_error("evplp_set_mesh_morph: mesh %d has %zu vertices, not %d", mesh, have, nverts); return false; }
+    if (!deltas) { c->set_error("evplp_set_mesh_morph: null deltas"); return false; }
+    char why[256];
+    if (!morph_deltas_ok(ntargets, deltas, nverts, why, sizeof(why))) { c->set_error("evplp_set_mesh_morph: mesh %d: %s", mesh, why); return false; }
+    return true;
+}
+bool morph_mesh_check(evplp_context *c, int32_t mesh, const float *weights, int32_t ntargets, std::vector<float> *base_out, std::vector<float> *moved_out) {
+    if (!c->accel_built) { c->set_error("evplp_morph_mesh: scene not built (evplp_build_accel)"); return false; }
+    if (mesh < 0 || mesh >= (int32_t)c->meshes.size()) { c->set_error("evplp_morph_mesh: mesh %d out of range (%zu meshes)", mesh, c->meshes.size()); return false; }
+    const HostMesh &m = c->meshes[(size_t)mesh];
+    const std::vector<float> &rest = m.rest.empty() ? m.verts : m.rest;
+    const size_t n = rest.size() / 3;
+    std::vector<float> base, moved(rest.size());
+    if (ntargets != 0 || weights) {                 // (NULL, 0 takes the weights away: the positions are the rest pose's again)
+        if (m.morph_targets <= 0) { c->set_error("evplp_morph_mesh: mesh %d has no morph targets (evplp_set_mesh_morph)", mesh); return false; }
+        if (ntargets != m.morph_targets) { c->set_error("evplp_morph_mesh: mesh %d has %d morph targets, not %d", mesh, m.morph_targets, ntargets); return false; }
+        char why[256];
+        if (!morph_weights_ok(weights, ntargets, why, sizeof(why))) { c->set_error("evplp_morph_mesh: mesh %d: %s", mesh, why); return false; }
+        base.resize(rest.size());
+        const int64_t bad = morph_apply(m.morph_delta.data(), weights, ntargets, rest.data(), base.data(), n);
+        if (bad >= 0) { c->set_error("evplp_morph_mesh: vertex %lld of mesh %d is not finite under the weights", (long long)bad, mesh); return false; }
+    } else if (m.morph_w.empty()) {                 // (none in force: nothing moves)
+        if (base_out) base_out->clear(); if (moved_out) moved_out->clear();
+        return true;
+    }
+    const int64_t bad = morph_deform(base.empty() ? rest.data() : base.data(), m.palette.empty() && m.has_matrix ? m.matrix : nullptr, m.palette.empty() ? nullptr : m.palette.data(),
+                                     m.skin_index.data(), m.skin_weight.data(), moved.data(), n);
+    if (bad >= 0) { c->set_error("evplp_morph_mesh: vertex %lld of mesh %d is not finite under the weights and the %s in force", (long long)bad, mesh, m.palette.empty() ? "matrix" : "pose"); return false; }
+    if (base_out) base_out->swap(base);
+    if (moved_out) moved_out->swap(moved);
     return true;
 }
 // evplp_refit_accel's refusal: a triangle the build dropped (no area) that has one now has no leaf slot to go to
@@ -675,7 +721,8 @@ extern "C" int evplp_update_mesh(evplp_context *c, int32_t mesh, const float *ve
     HostMesh &m = c->meshes[(size_t)mesh];
     std::memcpy(m.verts.data(), vertices, sizeof(float) * 3 * (size_t)nverts);
     std::vector<float>().swap(m.rest); m.rest_state = 0;        // (a new rest pose: the matrix is forgotten, the device's copy is stale)
-    std::vector<float>().swap(m.palette);                       // (... and so is a pose; the skin stays)
+    std::vector<float>().swap(m.palette); m.has_matrix = false; // (... and so is a pose; the skin stays)
+    std::vector<float>().swap(m.morph_w); std::vector<float>().swap(m.base); if (m.base_state == 1) m.base_state = 2;   // (... and so are morph weights; the targets stay)
     c->mesh_dirty[(size_t)mesh] = 1; c->scene_dirty = true;
     return EVPLP_OK;
 }
@@ -709,8 +756,9 @@ extern "C" int evplp_transform_mesh(evplp_context *c, int32_t mesh, const float 
     // no matrix), from the host's rest pose otherwise
     if (m.rest_state == 0) m.rest_state = (!c->mesh_dirty[(size_t)mesh] && m.rest.empty()) ? 1 : 2;
     if (m.rest.empty()) m.rest = m.verts;
-    for (size_t v = 0; v < m.rest.size() / 3; v++) evplp::transform_point(matrix, &m.rest[3 * v], &m.verts[3 * v]);
-    std::memcpy(m.matrix, matrix, sizeof(m.matrix));
+    const std::vector<float> &from = evplp::mesh_base(m);       // (morphed first, then moved: the base while morph weights are in force)
+    for (size_t v = 0; v < from.size() / 3; v++) evplp::transform_point(matrix, &from[3 * v], &m.verts[3 * v]);
+    std::memcpy(m.matrix, matrix, sizeof(m.matrix)); m.has_matrix = true;
     std::vector<float>().swap(m.palette);                       // (a matrix replaces a pose)
     c->mesh_dirty[(size_t)mesh] = 2; c->scene_dirty = true;
     return EVPLP_OK;
@@ -743,7 +791,7 @@ int pose_mesh_apply(evplp_context *c, int32_t mesh, const float *bone_matrices, 
     if (m.rest_state == 0) m.rest_state = (!c->mesh_dirty[(size_t)mesh] && m.rest.empty()) ? 1 : 2;
     if (m.rest.empty()) m.rest = m.verts;
     std::memcpy(m.verts.data(), posed, sizeof(float) * m.verts.size());    // (skin_apply of the rest pose, by the check)
-    m.palette.assign(bone_matrices, bone_matrices + 12 * (size_t)nbones);   // (a pose replaces a matrix)
+    m.palette.assign(bone_matrices, bone_matrices + 12 * (size_t)nbones); m.has_matrix = false;   // (a pose replaces a matrix)
     c->mesh_dirty[(size_t)mesh] = 3; c->scene_dirty = true;
     return EVPLP_OK;
 }
@@ -754,6 +802,54 @@ extern "C" int evplp_pose_mesh(evplp_context *c, int32_t mesh, const float *bone
     std::vector<float> posed;
     if (!evplp::pose_mesh_check(c, mesh, bone_matrices, nbones, &posed)) return EVPLP_ERR_INVALID;
     return evplp::pose_mesh_apply(c, mesh, bone_matrices, nbones, posed.data());
+}
+
+// ---- moving a mesh by morph targets: the targets (constant for the topology) and the weights, a state of their own beside matrix and pose:
+// the weights make the mesh's base from its rest pose, and the matrix or the pose in force acts on that base (morphed first, then moved)
+extern "C" int evplp_set_mesh_morph(evplp_context *c, int32_t mesh, int32_t ntargets, const float *deltas, int32_t nverts) {
+    CTX_CHECK(c);
+    if (!evplp::set_mesh_morph_check(c, mesh, ntargets, deltas, nverts)) return EVPLP_ERR_INVALID;
+    HostMesh &m = c->meshes[(size_t)mesh];
+    m.morph_targets = ntargets; m.morph_at = -1; c->morph_stale = true;
+    if (ntargets == 0) std::vector<float>().swap(m.morph_delta);
+    else m.morph_delta.assign(deltas, deltas + 3 * (size_t)nverts * (size_t)ntargets);
+    return EVPLP_OK;
+}
+
+namespace evplp {
+// evplp_morph_mesh behind its check: base / moved = the mesh's morphed base and its positions as morph_mesh_check made them (float3 per vertex;
+// ntargets = 0: moved alone, the positions without weights).  The group checks once, on the caller's thread against rank 0's copy, and hands
+// the same positions to every rank.
+int morph_mesh_apply(evplp_context *c, int32_t mesh, const float *weights, int32_t ntargets, const float *base, const float *moved) {
+    HostMesh &m = c->meshes[(size_t)mesh];
+    const int kind = !m.palette.empty() ? 3 : m.has_matrix ? 2 : 4;
+    if (ntargets == 0 && m.morph_w.empty()) return EVPLP_OK;     // (none were in force: nothing moves, nothing is dirty)
+    { const int rc = rest_prepare(c, "evplp_morph_mesh"); if (rc) return rc; }
+    // (the device's copy of the rest pose: as for a matrix)
+    if (m.rest_state == 0) m.rest_state = (!c->mesh_dirty[(size_t)mesh] && m.rest.empty()) ? 1 : 2;
+    if (m.rest.empty()) m.rest = m.verts;
+    if (ntargets == 0) {
+        std::vector<float>().swap(m.morph_w); std::vector<float>().swap(m.base);
+        if (m.base_state == 1) m.base_state = 2;
+        std::memcpy(m.verts.data(), moved, sizeof(float) * m.verts.size());
+        // (a mesh that nothing moves any more is at its rest pose: that goes up by upload, like new vertices, and the device's rest pose stays)
+        c->mesh_dirty[(size_t)mesh] = kind == 4 ? 1 : (char)kind; c->scene_dirty = true;
+        return EVPLP_OK;
+    }
+    m.morph_w.assign(weights, weights + ntargets);
+    m.base.assign(base, base + m.verts.size());
+    if (m.base_state == 1) m.base_state = 2;        // (the device's base, if it holds one, is that of other weights)
+    std::memcpy(m.verts.data(), moved, sizeof(float) * m.verts.size());
+    c->mesh_dirty[(size_t)mesh] = (char)kind; c->scene_dirty = true;
+    return EVPLP_OK;
+}
+}
+
+extern "C" int evplp_morph_mesh(evplp_context *c, int32_t mesh, const float *weights, int32_t ntargets) {
+    CTX_CHECK(c);
+    std::vector<float> base, moved;
+    if (!evplp::morph_mesh_check(c, mesh, weights, ntargets, &base, &moved)) return EVPLP_ERR_INVALID;
+    return evplp::morph_mesh_apply(c, mesh, weights, ntargets, base.data(), moved.data());
 }
 
 extern "C" int evplp_mesh_count(evplp_context *c) {
@@ -772,9 +868,11 @@ extern "C" int evplp_mesh_info(evplp_context *c, int32_t mesh, int32_t *nverts, 
 extern "C" int evplp_mesh_vertices(evplp_context *c, int32_t mesh, int32_t which, float *out_xyz, int32_t capacity_verts) {
     CTX_CHECK(c);
     if (mesh < 0 || mesh >= (int32_t)c->meshes.size()) { c->set_error("evplp_mesh_vertices: mesh %d out of range (%zu meshes)", mesh, c->meshes.size()); return EVPLP_ERR_INVALID; }
-    if (which != 0 && which != 1) { c->set_error("evplp_mesh_vertices: which must be 0 (current) or 1 (rest pose), not %d", which); return EVPLP_ERR_INVALID; }
+    if (which < 0 || which > 2) { c->set_error("evplp_mesh_vertices: which must be 0 (current), 1 (rest pose) or 2 (morphed base), not %d", which); return EVPLP_ERR_INVALID; }
     const HostMesh &m = c->meshes[(size_t)mesh];
-    const std::vector<float> &src = (which == 1 && !m.rest.empty()) ? m.rest : m.verts;
+    // (a mesh without morph targets has no morphed base: for it `which` is what it was before there were targets, 0 or 1)
+    if (which == 2 && m.morph_targets <= 0) { c->set_error("evplp_mesh_vertices: which = 2 (morphed base): mesh %d has no morph targets (evplp_set_mesh_morph); which must be 0 (current) or 1 (rest pose)", mesh); return EVPLP_ERR_INVALID; }
+    const std::vector<float> &src = which == 2 ? evplp::mesh_base(m) : (which == 1 && !m.rest.empty()) ? m.rest : m.verts;
     if (!out_xyz || capacity_verts < 0 || (size_t)capacity_verts < src.size() / 3) { c->set_error("evplp_mesh_vertices: mesh %d has %zu vertices: a null destination or too small a capacity (%d)", mesh, src.size() / 3, capacity_verts); return EVPLP_ERR_INVALID; }
     std::memcpy(out_xyz, src.data(), sizeof(float) * src.size());
     return EVPLP_OK;
@@ -889,6 +987,56 @@ static int skin_prepare(evplp_context *c, const std::vector<int32_t> &first, std
     return EVPLP_OK;
 }
 
+// A refit with meshes under morph weights (behind the wait for the last refit's copies), the twin of skin_prepare.  begin[mi]: where mesh mi's
+// corner deltas lie in d_morph -- the meshes with targets one behind the other, in float3, each target-major [T][3 count].  When the set of
+// meshes with targets has changed (or nothing is there yet) the arrays are made for it; every mesh's part then goes up again at its next
+// morphed refit.  src[mi]: where the part of a morphed mesh the device lacks lies in c->morph_upload, expanded here from the per-vertex deltas
+// through the mesh's index array.  need_base: a mesh under weights is also moved by a matrix or a pose -- the base array is made, as a copy of
+// the rest-pose array as the stream finds it here.
+static int morph_prepare(evplp_context *c, const std::vector<int32_t> &first, bool need_base, std::vector<int32_t> &begin, std::vector<size_t> &src) {
+    const size_t nm = c->meshes.size();
+    begin.assign(nm, 0); src.assign(nm, 0);
+    int64_t vectors = 0, weights = 0;
+    for (size_t mi = 0; mi < nm; mi++) if (c->meshes[mi].morph_targets > 0) {
+        begin[mi] = (int32_t)vectors; vectors += 3 * (int64_t)(first[mi + 1] - first[mi]) * c->meshes[mi].morph_targets; weights += c->meshes[mi].morph_targets;
+        if (vectors > INT32_MAX) { c->set_error("evplp_refit_accel: the corner deltas of the morph targets are more than the morph launch indexes"); return EVPLP_ERR_INVALID; }
+    }
+    if (c->morph_stale) {
+        for (HostMesh &m : c->meshes) m.morph_at = -1;
+        if (!c->d_mdesc || vectors > c->morph_cap || weights > c->weight_cap) {
+            hipFree(c->d_morph); hipFree(c->d_mweights); hipFree(c->d_mdesc); if (c->h_mweights) hipHostFree(c->h_mweights); if (c->h_mdesc) hipHostFree(c->h_mdesc);
+            c->d_morph = c->d_mweights = c->h_mweights = nullptr; c->d_mdesc = c->h_mdesc = nullptr; c->morph_cap = 0; c->weight_cap = 0;
+            hipError_t e = hipMalloc((void **)&c->d_morph, sizeof(float) * 3 * (size_t)std::max<int64_t>(vectors, 1));
+            if (e == hipSuccess) e = hipMalloc((void **)&c->d_mweights, sizeof(float) * (size_t)std::max<int64_t>(weights, 1));
+            if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_mweights, sizeof(float) * (size_t)std::max<int64_t>(weights, 1), hipHostMallocDefault);
+            if (e == hipSuccess) e = hipMalloc((void **)&c->d_mdesc, sizeof(MorphDesc) * nm);
+            if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_mdesc, sizeof(MorphDesc) * nm, hipHostMallocDefault);
+            if (e != hipSuccess) { c->set_error("evplp_refit_accel: the morph targets on the device: %s", hipGetErrorString(e)); return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP; }
+            c->morph_cap = vectors; c->weight_cap = (int32_t)weights;
+        }
+        c->morph_stale = false;
+    }
+    if (need_base && !c->d_base) {
+        const size_t bytes = sizeof(float) * 9 * (size_t)std::max(c->scene_tris, 1);
+        hipError_t e = hipMalloc((void **)&c->d_base, bytes);
+        if (e != hipSuccess) { c->d_base = nullptr; c->set_error("evplp_refit_accel: the morphed base on the device: %s", hipGetErrorString(e)); return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP; }
+        HIP_TRY(c, hipMemcpyAsync(c->d_base, c->d_rest, bytes, hipMemcpyDeviceToDevice, c->stream));
+        for (HostMesh &m : c->meshes) m.base_state = 0;
+    }
+    c->morph_upload.clear();
+    for (size_t mi = 0; mi < nm; mi++) if (c->mesh_dirty[mi] >= 2 && !c->meshes[mi].morph_w.empty() && c->meshes[mi].morph_at < 0) {
+        const HostMesh &m = c->meshes[mi];
+        const size_t nv = m.verts.size() / 3;
+        src[mi] = c->morph_upload.size();
+        for (int32_t k = 0; k < m.morph_targets; k++)
+            for (size_t q = 0; q < m.idx.size(); q++) {
+                const float *d = &m.morph_delta[3 * ((size_t)k * nv + (size_t)m.idx[q])];
+                c->morph_upload.insert(c->morph_upload.end(), d, d + 3);
+            }
+    }
+    return EVPLP_OK;
+}
+
 extern "C" int evplp_refit_accel(evplp_context *c) {
     CTX_CHECK(c);
     if (!evplp::refit_check(c)) return EVPLP_ERR_INVALID;
@@ -917,6 +1065,10 @@ extern "C" int evplp_refit_accel(evplp_context *c) {
     if (c->refit_count > 0) HIP_TRY(c, hipEventSynchronize(c->ev_refit_staged));     // (the last refit's copies have left the pinned arrays: long ago)
     std::vector<int32_t> skin_begin; std::vector<size_t> skin_src;
     if (std::find(c->mesh_dirty.begin(), c->mesh_dirty.end(), (char)3) != c->mesh_dirty.end() && (rc = skin_prepare(c, first, skin_begin, skin_src))) return rc;
+    std::vector<int32_t> morph_begin; std::vector<size_t> morph_src;
+    { bool any = false, need_base = false;
+      for (size_t mi = 0; mi < c->meshes.size(); mi++) if (c->mesh_dirty[mi] >= 2 && !c->meshes[mi].morph_w.empty()) { any = true; need_base = need_base || c->mesh_dirty[mi] != 4; }
+      if (any && (rc = morph_prepare(c, first, need_base, morph_begin, morph_src))) return rc; }
     // 1. the triangles of the meshes dirty by upload, packed, in one copy; one scatter per run of neighbouring such meshes.  Behind them in the
     // pinned array, the rest pose of every mesh that was given a matrix and whose rest pose the device does not hold in any form.
     // (one memcpy per mesh into the pinned array, as ever: what the copy engine then reads was written the way it was before there were matrices)
@@ -948,7 +1100,11 @@ extern "C" int evplp_refit_accel(evplp_context *c) {
     // through pinned memory, and ONE launch that writes the attributes of all of them from the rest pose.  Nothing of them is staged or copied.
     // 1''. the meshes dirty by pose likewise: the same rest pose, each mesh's corner skin where the device lacks it (once per mesh and skin),
     // the palettes one behind the other and the table of their places through pinned memory, and ONE launch that writes all of them.
-    int32_t nx = 0, moved = 0, ns = 0, posed = 0, nbone = 0;
+    // 1*. the meshes under morph weights: each mesh's corner deltas where the device lacks them (once per mesh and set of targets), the weight
+    // sets one behind the other and the table through pinned memory, and ONE launch, in front of the two above, that writes the attributes of
+    // the meshes nothing else moves and the base of the others -- which the two launches then read in place of the rest pose: the base array
+    // is a copy of the rest-pose array but for those meshes' parts, kept in step here.  A mesh whose base the device holds is not written again.
+    int32_t nx = 0, moved = 0, ns = 0, posed = 0, nbone = 0, nmo = 0, morphed = 0, nweight = 0;
     for (size_t mi = 0; mi < c->meshes.size(); mi++) if (c->mesh_dirty[mi] >= 2) {
         HostMesh &m = c->meshes[mi];
         const int32_t count = first[mi + 1] - first[mi];
@@ -957,8 +1113,27 @@ extern "C" int evplp_refit_accel(evplp_context *c) {
             if (count > 0) HIP_TRY(c, hipMemcpyAsync(c->d_rest + 9 * (size_t)first[mi], c->h_refit_stage + staged, sizeof(float) * 9 * (size_t)count, hipMemcpyHostToDevice, c->stream));
             staged += 9 * (size_t)count;
         }
+        if (m.rest_state != 3 && c->d_base) {
+            if (count > 0) HIP_TRY(c, hipMemcpyAsync(c->d_base + 9 * (size_t)first[mi], c->d_rest + 9 * (size_t)first[mi], sizeof(float) * 9 * (size_t)count, hipMemcpyDeviceToDevice, c->stream));
+            m.base_state = 0;
+        }
         m.rest_state = 3;
         if (count <= 0) continue;
+        if (!m.morph_w.empty() && (c->mesh_dirty[mi] == 4 || m.base_state != 1)) {
+            if (m.morph_at < 0) {
+                m.morph_at = morph_begin[mi];
+                HIP_TRY(c, hipMemcpyAsync(c->d_morph + 3 * (size_t)m.morph_at, c->morph_upload.data() + morph_src[mi], sizeof(float) * 9 * (size_t)count * (size_t)m.morph_targets, hipMemcpyHostToDevice, c->stream));
+            }
+            MorphDesc &d = c->h_mdesc[nmo++];
+            d.first = first[mi]; d.count = count; d.begin = morphed; d.weight_at = nweight; d.delta_at = m.morph_at; d.ntargets = m.morph_targets; d.to_base = c->mesh_dirty[mi] != 4; d.pad = 0;
+            std::memcpy(c->h_mweights + nweight, m.morph_w.data(), sizeof(float) * (size_t)m.morph_targets);
+            morphed += count; nweight += m.morph_targets;
+            if (d.to_base) m.base_state = 1;
+        } else if (m.morph_w.empty() && c->d_base && m.base_state != 0) {       // (the weights were taken away: the base is the rest pose again)
+            HIP_TRY(c, hipMemcpyAsync(c->d_base + 9 * (size_t)first[mi], c->d_rest + 9 * (size_t)first[mi], sizeof(float) * 9 * (size_t)count, hipMemcpyDeviceToDevice, c->stream));
+            m.base_state = 0;
+        }
+        if (c->mesh_dirty[mi] == 4) continue;
         if (c->mesh_dirty[mi] == 3) {
             if (m.skin_at < 0) {
                 m.skin_at = skin_begin[mi];
@@ -974,14 +1149,20 @@ extern "C" int evplp_refit_accel(evplp_context *c) {
         d.first = first[mi]; d.count = count; d.begin = moved; d.pad = 0; std::memcpy(d.m, m.matrix, sizeof(d.m));
         moved += count;
     }
+    if (nmo) {
+        HIP_TRY(c, hipMemcpyAsync(c->d_mdesc, c->h_mdesc, sizeof(MorphDesc) * (size_t)nmo, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->d_mweights, c->h_mweights, sizeof(float) * (size_t)nweight, hipMemcpyHostToDevice, c->stream));
+        refit_morph(c->d_mdesc, nmo, morphed, c->d_rest, c->d_mweights, c->weight_cap, c->d_morph, c->morph_cap, c->d_base, (TriAttr *)c->sc.attrs, c->scene_tris, c->stream);
+    }
+    const float *based = c->d_base ? c->d_base : c->d_rest;     // (what a matrix and a pose act on)
     if (nx) {
         HIP_TRY(c, hipMemcpyAsync(c->d_xform, c->h_xform, sizeof(TransformDesc) * (size_t)nx, hipMemcpyHostToDevice, c->stream));
-        refit_transform(c->d_xform, nx, moved, c->d_rest, (TriAttr *)c->sc.attrs, c->scene_tris, c->stream);
+        refit_transform(c->d_xform, nx, moved, based, (TriAttr *)c->sc.attrs, c->scene_tris, c->stream);
     }
     if (ns) {
         HIP_TRY(c, hipMemcpyAsync(c->d_sdesc, c->h_sdesc, sizeof(SkinDesc) * (size_t)ns, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipMemcpyAsync(c->d_bones, c->h_bones, sizeof(float) * 12 * (size_t)nbone, hipMemcpyHostToDevice, c->stream));
-        refit_skin(c->d_sdesc, ns, posed, c->d_rest, c->d_skin, c->skin_cap, c->d_bones, (TriAttr *)c->sc.attrs, c->scene_tris, c->stream);
+        refit_skin(c->d_sdesc, ns, posed, based, c->d_skin, c->skin_cap, c->d_bones, (TriAttr *)c->sc.attrs, c->scene_tris, c->stream);
     }
     if (stages) HIP_TRY(c, hipEventRecord(c->ev_refit[1], c->stream));
     // 2. leaf operands  3. boxes, one launch per height  4. four-wide nodes

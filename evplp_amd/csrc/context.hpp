@@ -21,6 +21,11 @@ void refit_transform(const TransformDesc *d_table, int32_t nmesh, int32_t total,
 // (meshes posed by bones: ONE skin launch per refit writes the attributes of every mesh of d_table from d_rest, the corner skins d_skin
 // (nskin corners) and the refit's palettes d_bones -- total: the posed triangles of the whole table)
 void refit_skin(const SkinDesc *d_table, int32_t nmesh, int32_t total, const float *d_rest, const CornerSkin *d_skin, int32_t nskin, const float *d_bones, TriAttr *attrs, int32_t ntri, hipStream_t stream);
+// (meshes under morph weights: ONE morph launch per refit, in front of the two above, writes every mesh of d_table from d_rest, the refit's
+// weight sets d_weights (nweights floats) and the corner deltas d_deltas (ndelta float3) -- into the attributes, or into d_base (indexed like
+// d_rest) for a mesh that a matrix or a pose then moves; total: the morphed triangles of the whole table)
+void refit_morph(const MorphDesc *d_table, int32_t nmesh, int32_t total, const float *d_rest, const float *d_weights, int32_t nweights, const float *d_deltas, int64_t ndelta, float *d_base, TriAttr *attrs,
+                 int32_t ntri, hipStream_t stream);
 void refit_leaves(const RefitScene &r, hipStream_t stream);
 void refit_level(const RefitScene &r, const int32_t *d_order, int32_t count, float pad, hipStream_t stream);
 // (the level launch with tree rotations: d_level = the plan's level per node, d_taken / d_need = per-node scratch, d_root_out = { rotations, need } of the root)
@@ -37,7 +42,16 @@ struct HostMesh {
     std::vector<float> rest; float matrix[12] = {}; int rest_state = 0;
     float area = 0.f, lo[3] = {}, hi[3] = {}, alo[3] = {}, ahi[3] = {}; bool any_area = false;
     int32_t skin_bones = 0, skin_at = -1; std::vector<int32_t> skin_index; std::vector<float> skin_weight, palette;
+    // has_matrix: a matrix of evplp_transform_mesh is in force (palette not empty: a pose is).  morph_targets > 0: the mesh has morph targets
+    // (evplp_set_mesh_morph), morph_delta [targets][vertices][3]; morph_w: the weights in force (evplp_morph_mesh), empty: none; base: the
+    // morphed rest pose while weights are in force (verts = base under the matrix or the pose in force), empty otherwise.  morph_at: where
+    // the mesh's corner deltas lie in the device's array (in float3), -1 not there.  base_state, the mesh's part of the device's base array
+    // (once there is one): 0 the rest pose, 1 `base` under the weights in force, 2 the base of weights that are no longer in force.
+    bool has_matrix = false; int32_t morph_targets = 0, morph_at = -1; int base_state = 0;
+    std::vector<float> morph_delta, morph_w, base;
 };
+// what a matrix or a pose acts on: the morphed base while weights are in force, else the rest pose
+inline const std::vector<float> &mesh_base(const HostMesh &m) { return !m.base.empty() ? m.base : m.rest.empty() ? m.verts : m.rest; }
 struct HostTexture { int32_t w = 0, h = 0; std::vector<float> rgba; };
 struct HostStats { uint64_t rays = 0; };
 // host/proxy_mesh.cpp: the proxy mesh of EVPLP_FOOTPRINT_PROXY as slabs (kernels.h ProxyDev)
@@ -58,6 +72,10 @@ bool transform_mesh_check(evplp_context *c, int32_t mesh, const float *m);
 bool set_mesh_skin_check(evplp_context *c, int32_t mesh, int32_t nbones, const int32_t *bone_index, const float *weight, int32_t nverts);
 bool pose_mesh_check(evplp_context *c, int32_t mesh, const float *bone_matrices, int32_t nbones, std::vector<float> *posed_out = nullptr);   // (posed_out: the posed positions)
 int pose_mesh_apply(evplp_context *c, int32_t mesh, const float *bone_matrices, int32_t nbones, const float *posed);   // (behind the check, with its positions)
+// (evplp_set_mesh_morph / evplp_morph_mesh; moved_out: the positions under the weights and whatever moves the mesh, base_out: the morphed base)
+bool set_mesh_morph_check(evplp_context *c, int32_t mesh, int32_t ntargets, const float *deltas, int32_t nverts);
+bool morph_mesh_check(evplp_context *c, int32_t mesh, const float *weights, int32_t ntargets, std::vector<float> *base_out = nullptr, std::vector<float> *moved_out = nullptr);
+int morph_mesh_apply(evplp_context *c, int32_t mesh, const float *weights, int32_t ntargets, const float *base, const float *moved);    // (behind the check, with its positions)
 bool refit_check(evplp_context *c);
 // what evplp_accel_quality / evplp_set_refit_policy refuse without touching a device (name: the entry point, for the message)
 bool accel_quality_check(evplp_context *c, const char *name);
@@ -163,6 +181,15 @@ struct evplp_context {
     // likewise ([meshes] SkinDesc each).  All freed with the scene; a context that never poses allocates none of it.
     evplp::CornerSkin *d_skin = nullptr; int32_t skin_cap = 0, bone_cap = 0; bool skin_stale = true; std::vector<evplp::CornerSkin> skin_upload;
     float *d_bones = nullptr, *h_bones = nullptr; evplp::SkinDesc *d_sdesc = nullptr, *h_sdesc = nullptr;
+    // mesh_dirty: 4 by evplp_morph_mesh on a mesh that nothing else moves (2 and 3 stand for a mesh under weights as well).  The first refit
+    // with a mesh under weights (and the first after the set of meshes with targets changed: morph_stale) lays those meshes' corner deltas out one
+    // behind the other in d_morph (morph_cap float3; a mesh's part goes up at its first morphed refit, from morph_upload, which the stream may
+    // read until ev_refit_staged) and sizes the refit's weight array (weight_cap floats) and the descriptor table of the one morph launch
+    // ([meshes] MorphDesc each), on the device and in pinned host memory.  d_base: a copy of d_rest in which the part of a mesh under weights
+    // AND a matrix or a pose holds its morphed base; made by the first refit with such a mesh, kept in step with d_rest, and from then on
+    // what the transform and the skin launch read.  All freed with the scene; a context that never morphs allocates none of it.
+    float *d_morph = nullptr, *d_base = nullptr, *d_mweights = nullptr, *h_mweights = nullptr; evplp::MorphDesc *d_mdesc = nullptr, *h_mdesc = nullptr;
+    int64_t morph_cap = 0; int32_t weight_cap = 0; bool morph_stale = true; std::vector<float> morph_upload;
     std::vector<evplp::BvhNode> host_nodes; std::vector<int32_t> refit_level_begin; int32_t refit_levels = 0;
     int32_t *d_refit_order = nullptr; float *d_refit_boxes = nullptr, *d_refit_stage = nullptr, *h_refit_stage = nullptr;
     hipEvent_t ev_refit_staged = nullptr, ev_refit[5] = {}; bool refit_timed = false, refit_stages_timed = false;

@@ -246,6 +246,22 @@ __host__ __device__ inline void skin_point(const float *bones, const int32_t b[4
         out[r] = ((a0 + a1) + a2) + a3;
     }
 }
+// ---- evplp_morph_mesh: a point under morph targets (blend shapes).  delta: the point's offset in target 0 -- target k's lies `stride` floats
+// further on each -- and w: the T weights.  out[r] = (((p[r] + w[0] d_0[r]) + w[1] d_1[r]) + ...) + w[T-1] d_{T-1}[r]: fp32, every product and
+// every sum rounds on its own, in index order, and nothing is fused.  All targets are always evaluated -- no shortcut for a zero weight, so
+// -0.0 may become +0.0 and every other bit of p is kept -- and the weights are used as given (negative and beyond 1 are legal).  The host copy
+// of a mesh and evplp_morph_points (both through host/morph.cpp) and refit_morph_kernel (bvh_gpu.hip) call this and nothing else, and a test
+// restates it in numpy.  out may be p.
+__host__ __device__ inline void morph_point(const float *p, const float *delta, size_t stride, const float *w, int32_t T, float *out) {
+#pragma clang fp contract(off)
+    float x = p[0], y = p[1], z = p[2];
+    for (int32_t k = 0; k < T; k++) {
+        const float *d = delta + (size_t)k * stride;
+        const float a = w[k] * d[0], b = w[k] * d[1], c = w[k] * d[2];
+        x = x + a; y = y + b; z = z + c;
+    }
+    out[0] = x; out[1] = y; out[2] = z;
+}
 // ---- evplp_project_points / evplp_denoise_temporal: a world point on the screen of a camera, in pixel-centre coordinates (x to the right, y
 // from the bottom: pixel (i, j) has its centre at (i, j)) and its view depth.  fp32, every product and every sum rounds on its own, in this
 // order, and nothing is fused:
@@ -330,6 +346,12 @@ constexpr int32_t kMaxSkinBones = 1024;
 // corner skin starts (in corners)
 struct SkinDesc { int32_t first, count, begin, bone_at, nbones, skin_at, pad[2]; };
 static_assert(sizeof(SkinDesc) == 32, "one descriptor per 32 bytes");
+constexpr int32_t kMaxMorphTargets = 64;
+// one morphed mesh of a refit, as refit_morph_kernel finds it: its run of original triangles, where the run starts among the morphed triangles
+// of the launch (ascending over the table), where its weights start in the refit's weight array (in floats) and its deltas in the delta array
+// (in float3: target-major, [T][3 count corners]), T, and where the result goes: 0 TriAttr::v, 1 the base array (indexed like the rest pose)
+struct MorphDesc { int32_t first, count, begin, weight_at, delta_at, ntargets, to_base, pad; };
+static_assert(sizeof(MorphDesc) == 32, "one descriptor per 32 bytes");
 
 // the bound on the iterations of a build of n clusters: the search iterations, then halvings
 inline int32_t ploc_iteration_bound(int32_t n, int32_t search_iterations) {

@@ -66,7 +66,7 @@ struct Rccl {
 };
 
 enum Op { OP_QUIT = 0, OP_CLEAR, OP_SYNC, OP_PRIMARY, OP_TRACE, OP_GATHER, OP_SPLAT, OP_PATH_TRACE, OP_PRESENT, OP_LOAD_SCENE, OP_SET_PROXY, OP_ASSEMBLE, OP_REDUCE, OP_SET_REFERENCE, OP_FRAME_ERROR,
-          OP_NOISE_TRACK, OP_NOISE_FOLD, OP_NOISE_POOL, OP_NOISE_ROWS, OP_NOISE_VARIANCE, OP_ADAPT_ENABLE, OP_ADAPT_RETIRE, OP_DENOISE_PREP, OP_DENOISE_FILTER, OP_PATH_TRACE_BATCH, OP_ADAPT_SET_BUDGETS, OP_ADAPT_TILE_NOISE, OP_UPDATE_MESH, OP_TRANSFORM_MESH, OP_SET_MESH_SKIN, OP_POSE_MESH, OP_REFIT, OP_ACCEL_QUALITY, OP_REFIT_POLICY, OP_OPTIMIZE_ACCEL, OP_REFIT_ROTATIONS,
+          OP_NOISE_TRACK, OP_NOISE_FOLD, OP_NOISE_POOL, OP_NOISE_ROWS, OP_NOISE_VARIANCE, OP_ADAPT_ENABLE, OP_ADAPT_RETIRE, OP_DENOISE_PREP, OP_DENOISE_FILTER, OP_PATH_TRACE_BATCH, OP_ADAPT_SET_BUDGETS, OP_ADAPT_TILE_NOISE, OP_UPDATE_MESH, OP_TRANSFORM_MESH, OP_SET_MESH_SKIN, OP_POSE_MESH, OP_SET_MESH_MORPH, OP_MORPH_MESH, OP_REFIT, OP_ACCEL_QUALITY, OP_REFIT_POLICY, OP_OPTIMIZE_ACCEL, OP_REFIT_ROTATIONS,
           OP_TEMPORAL_ENABLE, OP_TEMPORAL_RESET, OP_TEMPORAL_POSE, OP_TEMPORAL_SNAPSHOT };
 // One posted call, copied into the ring by assignment: plain data (pointers must stay valid until the caller has drained: load_scene, set_proxy,
 // resolve do) but for `batch`, a shared pointer -- so every post and every worker-side copy of a command pays one atomic reference count, null or not.
@@ -448,6 +448,9 @@ static void worker_run(Worker *w, const Cmd &cmd) {
         case OP_TRANSFORM_MESH: rc = evplp_transform_mesh(c, cmd.i[0], (const float *)cmd.p0); break;
         case OP_SET_MESH_SKIN: rc = evplp_set_mesh_skin(c, cmd.i[0], cmd.i[1], (const int32_t *)cmd.p0, (const float *)cmd.p1, cmd.i[2]); break;
         case OP_POSE_MESH: rc = evplp::pose_mesh_apply(c, cmd.i[0], (const float *)cmd.p0, cmd.i[1], (const float *)cmd.p1); break;   // (checked, and skinned once, by the caller's thread)
+        case OP_SET_MESH_MORPH: rc = evplp_set_mesh_morph(c, cmd.i[0], cmd.i[1], (const float *)cmd.p0, cmd.i[2]); break;
+        // (checked, and morphed once, by the caller's thread: p1 = the base, then the positions, i[2] floats each)
+        case OP_MORPH_MESH: rc = evplp::morph_mesh_apply(c, cmd.i[0], (const float *)cmd.p0, cmd.i[1], (const float *)cmd.p1, (const float *)cmd.p1 + cmd.i[2]); break;
         case OP_REFIT: rc = evplp_refit_accel(c); break;
         case OP_ACCEL_QUALITY: rc = evplp_accel_quality(c, (struct evplp_accel_quality *)cmd.out + w->rank); break;      // (out: one record per rank, the caller's)
         case OP_REFIT_POLICY: rc = evplp_set_refit_policy(c, cmd.d, cmd.i[0]); break;
@@ -881,6 +884,27 @@ extern "C" int evplp_group_pose_mesh(evplp_group *g, int32_t mesh, const float *
     Cmd c; c.op = OP_POSE_MESH; c.p0 = bone_matrices; c.p1 = posed.data(); c.i[0] = mesh; c.i[1] = nbones;
     const int rc = post_and_wait(g, c);
     drain(g);                           // (whatever the outcome, no worker reads `posed` behind this line)
+    return rc;
+}
+// (the targets and the weights are copied by every rank before the call returns: it waits for the workers)
+extern "C" int evplp_group_set_mesh_morph(evplp_group *g, int32_t mesh, int32_t ntargets, const float *deltas, int32_t nverts) {
+    GRP_CHECK(g);
+    drain(g);
+    if (!evplp::set_mesh_morph_check(g->ctx[0], mesh, ntargets, deltas, nverts)) { g->set_error("%s", g->ctx[0]->error); return EVPLP_ERR_INVALID; }
+    Cmd c; c.op = OP_SET_MESH_MORPH; c.p0 = deltas; c.i[0] = mesh; c.i[1] = ntargets; c.i[2] = nverts;
+    return post_and_wait(g, c);
+}
+extern "C" int evplp_group_morph_mesh(evplp_group *g, int32_t mesh, const float *weights, int32_t ntargets) {
+    GRP_CHECK(g);
+    drain(g);
+    std::vector<float> base, moved;     // (the check morphs rank 0's rest pose; every rank takes these positions: the call waits for the workers)
+    if (!evplp::morph_mesh_check(g->ctx[0], mesh, weights, ntargets, &base, &moved)) { g->set_error("%s", g->ctx[0]->error); return EVPLP_ERR_INVALID; }
+    g->sums_fresh = false;
+    const size_t n = moved.size();
+    base.resize(n); base.insert(base.end(), moved.begin(), moved.end());          // (one array: the base -- unused without weights --, then the positions)
+    Cmd c; c.op = OP_MORPH_MESH; c.p0 = weights; c.p1 = base.data(); c.i[0] = mesh; c.i[1] = ntargets; c.i[2] = (int32_t)n;
+    const int rc = post_and_wait(g, c);
+    drain(g);                           // (whatever the outcome, no worker reads the positions behind this line)
     return rc;
 }
 extern "C" int evplp_group_refit_accel(evplp_group *g) {

@@ -670,6 +670,9 @@ private:
 // evplp_render_json of the moved scene with that rngOffset; with 0 every frame uses the same seeds.
 // "rotations": k = 0 .. 8 (default 0: off) is evplp_group_set_refit_rotations: k passes of tree rotations inside every frame's refit.
 // A track may carry, in place of "matrices", "skin" and "poses" (below, parse_poses): its mesh is then posed by bones, one palette per frame.
+// A "mesh" track may also carry "morph" and "weights" (below, parse_morph) -- alone, beside "matrices", or beside "skin" + "poses": its mesh
+// is then morphed by one weight set per frame, and the matrix or the pose acts on the morphed base (per frame: weights, then matrix or pose,
+// then the refit).
 // "object": k addresses every mesh the k-th entry of the scene file's "scene" array produced (an OBJ yields one mesh per material group),
 // "object": "arealight" the light, "mesh": i the i-th mesh in upload order.  For frame f = 0 .. F - 1 every track's f-th matrix is applied,
 // the tree is refitted (evplp_group_refit_accel; refitPolicy is evplp_group_set_refit_policy) and the loop runs as a fresh evplp_render_json
@@ -715,6 +718,13 @@ public:
             for (int32_t m : track.meshes) {
                 if (taken[(size_t)m]) throw JsonError(where + ": mesh " + std::to_string(m) + " is in two of the animation.tracks");
                 taken[(size_t)m] = 1;
+            }
+            if (tr.has("morph") || tr.has("weights")) {
+                parse_morph(tr, where, (size_t)F, scene, track);
+                if (!tr.has("matrices") && !tr.has("poses") && !tr.has("skin")) {     // (morphed alone)
+                    tracks.push_back(std::move(track));
+                    continue;
+                }
             }
             if (tr.has("matrices") && tr.has("poses")) throw JsonError(where + ".poses: not beside \"matrices\" (a track has exactly one of the two)");
             if (tr.has("poses")) {
@@ -775,6 +785,9 @@ public:
     }
     void start(evplp_group *g) {
         // (the skins of the "poses" tracks, once: what evplp_set_mesh_skin refuses about the loaded scene -- the vertex count -- is refused here)
+        for (size_t t = 0; on && t < tracks.size(); t++) if (tracks[t].targets > 0)
+            check(g, evplp_group_set_mesh_morph(g, tracks[t].meshes[0], tracks[t].targets, tracks[t].deltas.data(), (int32_t)(tracks[t].deltas.size() / (3 * (size_t)tracks[t].targets))),
+                  ("animation.tracks[" + std::to_string(t) + "].morph").c_str());
         for (size_t t = 0; on && t < tracks.size(); t++) if (tracks[t].bones > 0)
             check(g, evplp_group_set_mesh_skin(g, tracks[t].meshes[0], tracks[t].bones, tracks[t].indices.data(), tracks[t].weights.data(), (int32_t)(tracks[t].indices.size() / 4)),
                   ("animation.tracks[" + std::to_string(t) + "].skin").c_str());
@@ -786,6 +799,8 @@ public:
         if (!on) return;
         frame = f;
         for (const Track &t : tracks) {
+            if (t.targets > 0) check(g, evplp_group_morph_mesh(g, t.meshes[0], &t.morph_weights[(size_t)t.targets * (size_t)f], t.targets), "animation: morph");
+            if (t.matrices.empty()) continue;       // (morphed alone)
             if (t.bones > 0) { check(g, evplp_group_pose_mesh(g, t.meshes[0], &t.matrices[12 * (size_t)t.bones * (size_t)f], t.bones), "animation: pose"); continue; }
             for (int32_t m : t.meshes) check(g, evplp_group_transform_mesh(g, m, &t.matrices[12 * (size_t)f]), "animation: transform");
         }
@@ -809,7 +824,48 @@ public:
 
 private:
     // matrices: [frames][12]; a "poses" track (bones > 0): [frames][bones][12], and the skin of its one mesh, [vertices][4] each
-    struct Track { std::vector<int32_t> meshes; std::vector<float> matrices; int32_t bones = 0; std::vector<int32_t> indices; std::vector<float> weights; };
+    // a track with "morph" (targets > 0): deltas [targets][vertices][3] and morph_weights [frames][targets], with or without matrices
+    struct Track { std::vector<int32_t> meshes; std::vector<float> matrices; int32_t bones = 0; std::vector<int32_t> indices; std::vector<float> weights;
+                   int32_t targets = 0; std::vector<float> deltas, morph_weights; };
+    // {"mesh": i, "morph": {"targets": [[[dx, dy, dz] x vertices] x T]}, "weights": [[T numbers] x F]}: frame f morphs the mesh by its f-th
+    // weight set (evplp_group_morph_mesh: the rest pose + the weighted deltas, nothing composes); the targets are set once
+    // (evplp_group_set_mesh_morph).  Vertex v is the loader's numbering, so only "mesh" can carry targets.
+    static void parse_morph(const Json &tr, const std::string &where, size_t F, const HostScene &scene, Track &track) {
+        const std::string mw = where + ".morph", ww = where + ".weights", tw = mw + ".targets";
+        if (!tr.has("morph")) throw JsonError(mw + ": \"weights\" needs morph targets ({\"targets\"})");
+        if (tr.has("object")) throw JsonError(mw + ": not with \"object\" (one entry of \"scene\" yields several meshes: per-vertex data needs \"mesh\")");
+        if (!tr.has("weights")) throw JsonError(ww + ": \"morph\" needs one weight set per frame");
+        if (!tr.at("morph").is_object() || !tr.at("morph").has("targets") || !tr.at("morph").at("targets").is_array()) throw JsonError(tw + ": expected a list of targets, each a list of one [dx, dy, dz] per vertex");
+        const Json &tg = tr.at("morph").at("targets");
+        const size_t T = tg.size(), nv = scene.meshes[(size_t)track.meshes[0]].verts.size() / 3;
+        if (T < 1 || T > 64) throw JsonError(tw + ": must hold 1 .. 64 targets, not " + std::to_string(T));
+        for (size_t k = 0; k < T; k++) {
+            const std::string kw = tw + "[" + std::to_string(k) + "]";
+            if (!tg.at(k).is_array() || tg.at(k).size() != nv) throw JsonError(kw + ": expected one [dx, dy, dz] per vertex of mesh " + std::to_string(track.meshes[0]) + " (" + std::to_string(nv) + " vertices)");
+            for (size_t v = 0; v < nv; v++) {
+                const Json &d = tg.at(k).at(v);
+                const std::string vw = kw + "[" + std::to_string(v) + "]";
+                if (!d.is_array() || d.size() != 3) throw JsonError(vw + ": expected three numbers");
+                for (size_t r = 0; r < 3; r++) {
+                    const float x = d.at(r).as_float(vw.c_str());
+                    if (!std::isfinite(x)) throw JsonError(vw + ": entry " + std::to_string(r) + " is not a finite fp32 number");
+                    track.deltas.push_back(x);
+                }
+            }
+        }
+        if (!tr.at("weights").is_array() || tr.at("weights").size() != F) throw JsonError(ww + ": expected animation.frames (" + std::to_string(F) + ") weight sets of " + std::to_string(T) + " numbers");
+        for (size_t f = 0; f < F; f++) {
+            const Json &w = tr.at("weights").at(f);
+            const std::string fw = ww + "[" + std::to_string(f) + "]";
+            if (!w.is_array() || w.size() != T) throw JsonError(fw + ": expected " + std::to_string(T) + " numbers (one per target)");
+            for (size_t k = 0; k < T; k++) {
+                const float x = w.at(k).as_float(fw.c_str());
+                if (!std::isfinite(x)) throw JsonError(fw + ": entry " + std::to_string(k) + " is not a finite fp32 number");
+                track.morph_weights.push_back(x);
+            }
+        }
+        track.targets = (int32_t)T;
+    }
     // {"mesh": i, "skin": {"bones": B, "indices": [[b0, b1, b2, b3], ... one per vertex], "weights": [[w0, w1, w2, w3], ...]},
     //  "poses": [[[12 numbers] x B] x F]}: frame f poses the mesh by its f-th palette (evplp_group_pose_mesh: the rest pose skinned, nothing
     // composes); the skin is set once (evplp_group_set_mesh_skin).  Vertex v is the loader's numbering (evplp_mesh_vertices returns it), so only

@@ -139,6 +139,14 @@ typedef struct evplp_config {
      *                                   per bone of their skins + 32 B per mesh, and the last two again in pinned host memory, made by the first
      *                                   refit behind an evplp_pose_mesh and freed with the scene; on the host 32 B per skinned vertex, and 72 B per
      *                                   triangle of the meshes whose corner skin the last posed refit sent; a context that never poses allocates none
+     *   morph targets (after a call)    36 B x T per triangle of the meshes with T targets (per corner and target one float3 delta, target-major per
+     *                                   mesh) + 4 B per target of their weight sets + 32 B per mesh, the last two again in pinned host memory, and,
+     *                                   once a mesh under weights is also moved by a matrix or a pose, 36 B per triangle of the scene (the base
+     *                                   array: a copy of the rest pose in which such a mesh's part is its morphed base), made by the first refit
+     *                                   behind an evplp_morph_mesh and freed with the scene; the rest-pose row above as well (evplp_morph_mesh
+     *                                   counts as a transform there); on the host 12 B x T per vertex with targets, 12 B per vertex under weights,
+     *                                   and 36 B x T per triangle of the meshes whose corner deltas the last morphed refit sent; a context that
+     *                                   never morphs allocates none
  *   PLOC build (during the call)    88 B per triangle on top of the device LBVH's scratch, freed before evplp_build_accel returns: 2 n clusters in ping-pong (28 B
  *                                   each), n nearest neighbours (4 B), n packed flags and their scan (16 B), children and counts of the inner nodes (12 B)
  *   tree cost (after a call)        24 B per 256 nodes + 8 B, and the same in pinned host memory; the refit's plan and staging (the row above) if no
@@ -361,14 +369,56 @@ int evplp_set_mesh_skin(evplp_context *ctx, int32_t mesh, int32_t nbones, const 
 int evplp_pose_mesh(evplp_context *ctx, int32_t mesh, const float *bone_matrices /* [nbones][12] */, int32_t nbones);
 int evplp_skin_points(const float *bone_matrices, int32_t nbones, const int32_t *bone_index, const float *weight,
                       const float *in, float *out, int32_t n);
+/* ---- moving a mesh by morph targets (blend shapes): rest pose + the weighted deltas, blended on the device; 4 B per target go up (DESIGN
+ * section 6b, INTEGRATION B7) ----
+ * A set of T targets gives every vertex T offsets d_k (deltas[T][nverts][3]); a weight set is w[T].  A point p goes to
+ *   out[r] = (((p[r] + w[0] d_0[r]) + w[1] d_1[r]) + ... ) + w[T-1] d_{T-1}[r]
+ * in fp32, every product and every sum rounded on its own, in index order, nothing fused (morph_point in evplp_types.h, the one function the
+ * host and the device call).  All targets are always evaluated -- no shortcut for a zero weight, so -0.0 may become +0.0 and every other bit
+ * is kept -- and the weights are used as given: any finite value, so negative weights and extrapolation beyond 1 are legal.
+ * evplp_set_mesh_morph attaches targets to mesh `mesh` (a host pointer, float[ntargets][nverts][3] in the vertex numbering of
+ * evplp_update_mesh, copied before the call returns).  ntargets is 1 .. 64; ntargets = 0 removes the targets (the array is not looked at).
+ * Targets are constant for the topology: the call moves nothing and marks nothing dirty, and they survive evplp_update_mesh (the deltas
+ * are relative to whatever the rest pose is), evplp_build_accel and a policy's rebuild.  EVPLP_ERR_INVALID, nothing changed, the context
+ * staying usable: no evplp_build_accel yet, mesh out of range, a vertex count other than the mesh's, a null pointer, ntargets outside
+ * 0 .. 64, a delta that is not finite, morph weights in force on that mesh (take them away first).
+ * evplp_morph_mesh puts weights in force: the mesh's BASE becomes morph_point(rest pose), and its positions become that base under whatever
+ * moves the mesh -- nothing, the matrix of evplp_transform_mesh (transform_point of the base) or the palette of evplp_pose_mesh (skin_point
+ * of the base): morphed first, then moved.  The rest pose is never overwritten, so weights do NOT compose and do not drift: each call
+ * replaces the weights before it.  The weights are a state of their own beside matrix and pose: a matrix still replaces a pose and a pose a
+ * matrix, neither touches the weights, and a later evplp_transform_mesh / evplp_pose_mesh acts on the morphed base; evplp_update_mesh
+ * forgets the weights (as it forgets matrix and pose) and keeps the targets.  evplp_morph_mesh(ctx, mesh, NULL, 0) takes the weights away:
+ * the positions are the un-morphed ones again, and the mesh is dirty if weights were in force (not otherwise).  The mesh is dirty exactly as
+ * after evplp_update_mesh (every pass is refused until the refit), and the host copy follows through the same functions, so bounds, areas,
+ * the light's CDF, evplp_scene_metrics, a rebuild and the refit's degenerate-triangle refusal see the positions the device has.
+ * EVPLP_ERR_INVALID, nothing marked: not built, mesh out of range, the mesh has no targets, ntargets is not the targets' count, a null
+ * pointer with a count > 0, a weight that is not finite, a final coordinate that is not finite (the base, or the base under the matrix or
+ * the pose in force, checked on the host copy).  Weights that collapse triangles are legal: they fall under the degenerate rule above.
+ * On the device the deltas are expanded per triangle corner, because the attributes and the rest pose are per triangle: 12 B per corner and
+ * target, per mesh target-major [T][3 x triangles], the meshes with targets one behind the other; a mesh's part is made by its first morphed
+ * refit (and again after a rebuild or a change of the set of meshes with targets).  A refit uploads 4 B x T per morphed mesh and a table of
+ * (first triangle, count, weights, deltas, T, destination) through pinned memory, and ONE launch, in front of the transform and the skin
+ * launch, writes every mesh whose base must be written: straight into the attributes where no matrix and no pose is in force, else into the
+ * base array, which the two launches then read in place of the rest pose.  A mesh whose weights did not change since its base was written
+ * (only its matrix or its pose did) is not morphed again.
+ * evplp_morph_points applies the same function to n points (host only, no GPU; deltas: [ntargets][n][3]; in and out: float3[n], may be the
+ * same array): the base evplp_morph_mesh will use, bit for bit.  It has the refusals above that apply to its arguments (ntargets 1 .. 64,
+ * n >= 0, null pointers, a point, a delta, a weight or a result that is not finite), and a refused call writes nothing to out.
+ * evplp_mesh_vertices(ctx, mesh, 2, ...) returns the morphed base of a mesh with targets (its rest pose while no weights are in force); a
+ * mesh without targets has no morphed base, and which = 2 stays EVPLP_ERR_INVALID for it. */
+#define EVPLP_MAX_MORPH_TARGETS 64
+int evplp_set_mesh_morph(evplp_context *ctx, int32_t mesh, int32_t ntargets, const float *deltas /* [ntargets][nverts][3] */, int32_t nverts);
+int evplp_morph_mesh(evplp_context *ctx, int32_t mesh, const float *weights /* [ntargets] */, int32_t ntargets);
+int evplp_morph_points(const float *in, const float *deltas, const float *weights, int32_t ntargets, int32_t n, float *out);
 /* The meshes as the host copy holds them, in the numbering evplp_update_mesh and evplp_set_mesh_skin expect -- what a caller of
  * evplp_load_scene_json needs to build a skin (the OBJ reader de-duplicates (v, vt) pairs per material group).  evplp_mesh_count: the number
  * of meshes (negative: an error code).  evplp_mesh_info: each pointer may be null.  evplp_mesh_vertices: float3[nverts] into out_xyz, which
- * holds capacity_verts vertices; which = 0 the current positions, 1 the rest pose (the same until a matrix or a pose moves the mesh).
- * EVPLP_ERR_INVALID: mesh out of range, another `which`, a null destination, too small a capacity. */
+ * holds capacity_verts vertices; which = 0 the current positions, 1 the rest pose (the same until a matrix or a pose moves the mesh), 2 the
+ * base a matrix or a pose acts on (the rest pose morphed by the weights in force; the rest pose without weights; only for a mesh with morph targets).
+ * EVPLP_ERR_INVALID: mesh out of range, another `which`, which = 2 for a mesh without morph targets, a null destination, too small a capacity. */
 int evplp_mesh_count(evplp_context *ctx);
 int evplp_mesh_info(evplp_context *ctx, int32_t mesh, int32_t *nverts, int32_t *ntris, int32_t *material);
-int evplp_mesh_vertices(evplp_context *ctx, int32_t mesh, int32_t which /* 0 current, 1 rest pose */, float *out_xyz, int32_t capacity_verts);
+int evplp_mesh_vertices(evplp_context *ctx, int32_t mesh, int32_t which /* 0 current, 1 rest pose, 2 morphed base */, float *out_xyz, int32_t capacity_verts);
 /* refits since evplp_create, heights of the current tree's plan (0 before its first refit), HIP-event time of the last refit (0 while
  * evplp_profile_passes is off; waits for that refit).  Each pointer may be null. */
 int evplp_refit_info(evplp_context *ctx, int32_t *refits, int32_t *levels, float *last_refit_ms);
@@ -1000,6 +1050,10 @@ int evplp_group_transform_mesh(evplp_group *g, int32_t mesh, const float m[12]);
  * before the call returns */
 int evplp_group_set_mesh_skin(evplp_group *g, int32_t mesh, int32_t nbones, const int32_t *bone_index, const float *weight, int32_t nverts);
 int evplp_group_pose_mesh(evplp_group *g, int32_t mesh, const float *bone_matrices, int32_t nbones);
+/* evplp_set_mesh_morph / evplp_morph_mesh on every rank (both partitions), refused on the caller's thread likewise; the arrays are copied
+ * before the call returns */
+int evplp_group_set_mesh_morph(evplp_group *g, int32_t mesh, int32_t ntargets, const float *deltas, int32_t nverts);
+int evplp_group_morph_mesh(evplp_group *g, int32_t mesh, const float *weights, int32_t ntargets);
 /* evplp_accel_quality / evplp_set_refit_policy on every rank (both partitions; the calls wait for the ranks).  Scene and tree are replicated,
  * so every rank computes the same doubles and a policy takes the same decision on each; the group returns rank 0's figures and fails
  * (EVPLP_ERR_INVALID) if any rank's differ.  Refused on the caller's thread, the group staying usable, where the plain context refuses. */
