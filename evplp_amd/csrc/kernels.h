@@ -136,6 +136,20 @@ constexpr int kVplSplit = EVPLP_VPL_SPLIT;
 // 64 partial sums per pixel, 1 GB at 1024^2.  Rounds 1-3, k = 4: 32 partial sums per pixel (512 MB at 1024^2 instead of 2 GB for k = 1) at the same speed (hard scene, cfg2, one GPU:
 // k = 1 113.9 ms, 2 114.3, 4 114.0 on one box); k = 16 was 38 % slower (long items: launch tail)
 constexpr int kDefaultSplitsPerWave = EVPLP_GATHER_K;
+#ifndef EVPLP_PX_LDS
+#define EVPLP_PX_LDS 1            // the pixel's reflectances parked in LDS beside its view direction: seven registers fewer across the walks
+#endif
+constexpr int kGatherPxFloats = 64 * (EVPLP_PX_LDS ? 10 : 3);      // [192] view direction (+ [192] rho_d, [192] rho_s, [64] e) per wavefront
+// Dynamic LDS of a gather wavefront that folds its k split sums (a power of two) in tree order: `px_floats` of pixel data, then one
+// [3][64] block per fold level.  A binary counter over k splits has log2 k + 1 levels; the top one only ever receives the last split's
+// store, which nothing reads back: a kernel that skips that store (gather_vpl_kernel) asks with top_level = false.
+constexpr size_t gather_fold_lds_bytes(int k, int px_floats, bool top_level) {
+    int levels = 1;
+    while ((1 << (levels - 1)) < k) levels++;       // log2 k + 1
+    return (size_t)((top_level ? levels : levels - 1) * 192 + px_floats) * sizeof(float);
+}
+// ... of gather_vpl_kernel: what launch_gather_vpl_items asks for (tests/test_gather_ring_resources.py adds the kernel's static ring to it)
+constexpr size_t gather_vpl_lds_bytes(int k) { return gather_fold_lds_bytes(k, kGatherPxFloats, false); }
 
 struct PathTraceArgs {
     SceneDev sc; StripDev st;

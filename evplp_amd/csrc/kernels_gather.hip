@@ -16,7 +16,8 @@
 // state in SGPRs, node/leaf fetches are scalar loads, stack in the lanes of a VGPR, descent decided by
 // ballots, lanes whose un-normalised cosine product is <= 0 (lighttracing.cu:288) never enter.
 // The VPL record is wave-uniform and is fetched with scalar loads through the scalar cache (LDS
-// staging with a barrier per chunk coupled the waves of a workgroup and measured 5% slower).
+// staging with a barrier per chunk coupled the waves of a workgroup and measured 5% slower).  With entry cuts the VPL gather does not
+// fetch it at all: the record rides behind its cut slot through the wave's own LDS ring (no barrier: one wave per workgroup).
 #include "device_common.hpp"
 #include "kernels.h"
 #include <algorithm>
@@ -201,18 +202,26 @@ EV_DEV bool tile_retired(const GatherArgs &a, const AdaptArgs &ad, const Item &t
 }
 
 #ifndef EVPLP_CUT_RING
-#define EVPLP_CUT_RING 3          // LDS buffers of the cut-slot ring of a gather wave (512 B each): EVPLP_CUT_RING - 1 slots in flight ahead of the walk
+#define EVPLP_CUT_RING 3          // LDS buffers of the cut-slot ring of a gather wave: EVPLP_CUT_RING - 1 slots in flight ahead of the walk
 #endif
-#ifndef EVPLP_PX_LDS
-#define EVPLP_PX_LDS 1            // the pixel's reflectances parked in LDS beside its view direction: seven registers fewer across the walks
+#ifndef EVPLP_VPL_RING
+// gather_vpl_kernel<true>: the VPL's 96-byte record rides behind its cut slot in the same ring buffer (352 B instead of 256 B, moved by lanes
+// 16-21 of the slot's own DMA instruction) and is read from LDS, not fetched with scalar loads.  0 = the record by scalar loads, as without cuts.
+#define EVPLP_VPL_RING 1
 #endif
-constexpr int kGatherPxFloats = 64 * (EVPLP_PX_LDS ? 10 : 3);      // [192] view direction (+ [192] rho_d, [192] rho_s, [64] e) per wavefront
+#ifndef EVPLP_TAIL_PROBE
+// (measured alternative to EVPLP_VPL_RING, off: with the record's scalar head fetch, one-dword scalar loads of the two lines of its tail, so that
+// the tail fetch behind the walk hits the scalar cache -- profiles/vpl_ring_speed.txt)
+#define EVPLP_TAIL_PROBE 0
+#endif
+// (EVPLP_PX_LDS and kGatherPxFloats, the pixel data a gather wavefront parks in LDS: kernels.h, with the size of its dynamic LDS)
 #ifndef EVPLP_GATHER_WAVES
 // waves per SIMD (1-wave workgroups).  cfg2 hard / easy scene -- round 3 (no cuts, 64 registers at either): 7 = 70.6 / 29.3 ms, 8 = 70.9 / 30.9.
 // Round 4, with the entry cuts the walks are half as long and wait relatively more for their node fetches (76 % of the SIMD cycles issue
 // a vector instruction at 7 waves): 8 waves = 53.5 / 20.5 ms against 56.6 / 21.2 -- once the kernel FITS 64 registers (EVPLP_PX_LDS above:
 // with six spilled registers reloaded from scratch per lit VPL 8 waves gave 55.0 / 22.0).  LDS per wavefront: 2.5 KB of pixel data + 768 B
-// per fold level + the 768-byte cut ring = 4864 B at k = 2, inside the 5120 B that 32 wavefronts per CU leave each (k >= 4: 7 waves).
+// per fold level (log2 k of them: the top level is never read back and is not stored) + the ring of 3 x 352 B (cut slot + VPL record) =
+// 4384 B at k = 2, inside the 5120 B that 32 wavefronts per CU leave each (k >= 4: 7 waves).
 #define EVPLP_GATHER_WAVES 8
 #endif
 
@@ -229,10 +238,23 @@ EV_DEV Vpl fetch_vpl(const evplp_record *r) {
 // ... in two parts around the walk (gather_vpl_kernel): position + normal first (all the cosine test and the walk need), the
 // shading fields afterwards.  Held across the walk the 24 dwords cost the walk its SGPRs: eight were spilled to VGPR lanes for
 // every VPL and the node base pointer was re-loaded from the kernel arguments at every node visit.
+// (These scalar fetches serve the walks from the root, the C++ reference walk and the VSL walk kernel.  The VPL gather with entry cuts
+// does not fetch the record at all: it arrives in LDS behind the cut slot -- EVPLP_VPL_RING, gather_vpl_kernel.)
 EV_DEV void fetch_vpl_head(const evplp_record *vpls, uint32_t i, V3 &pos, V3 &n, float &psel) {
     const v8i ra = sload8(vpls, i * (uint32_t)sizeof(evplp_record));
     pos = v3(f_of(ra[0]), f_of(ra[1]), f_of(ra[2])); n = v3(f_of(ra[4]), f_of(ra[5]), f_of(ra[6])); psel = f_of(ra[7]);
 }
+#if EVPLP_TAIL_PROBE
+// the probe (gather_vpl_kernel<true> in front of the walk): the two lines the tail can lie in are asked for with the head and land in the
+// scalar cache; their dwords go to a register nobody reads.  They share the head's wait: scalar loads return in any order, so every lgkmcnt
+// wait behind them -- the walk's first instruction is one -- waits for them anyway.
+EV_DEV void fetch_vpl_head_probe(const evplp_record *vpls, uint32_t i, V3 &pos, V3 &n, float &psel) {
+    v8i ra; int warm;
+    asm volatile("s_load_dwordx8 %0, %2, %3\n\ts_load_dword %1, %2, %3 offset:0x20\n\ts_load_dword %1, %2, %3 offset:0x40\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(ra), "=&s"(warm) : "s"(vpls), "s"(i * (uint32_t)sizeof(evplp_record)));
+    pos = v3(f_of(ra[0]), f_of(ra[1]), f_of(ra[2])); n = v3(f_of(ra[4]), f_of(ra[5]), f_of(ra[6])); psel = f_of(ra[7]);
+}
+#endif
 EV_DEV void fetch_vpl_tail(const evplp_record *vpls, uint32_t i, Vpl &v) {
     const v16i rb = sload16(vpls, i * (uint32_t)sizeof(evplp_record) + 32u);
     v.flux = v3(f_of(rb[0]), f_of(rb[1]), f_of(rb[2])); v.fdir = v3(f_of(rb[4]), f_of(rb[5]), f_of(rb[6]));
@@ -258,7 +280,8 @@ __global__ __launch_bounds__(64, EVPLP_GATHER_WAVES) void gather_vpl_kernel(Gath
 #if EVPLP_GATHER_TIMES
     const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
 #endif
-    // dynamic LDS: [192] the view directions, then one [192] block per level of the k-split fold (log2 k + 1 of them).  Sized by k
+    // dynamic LDS: [192] the view directions, then one [192] block per level of the k-split fold (log2 k of them: the top level, which the
+    // last split would store, is never read back -- see the fold below -- and has no block).  Sized by k
     // because LDS is what limits occupancy next: 7 single-wavefront workgroups per SIMD fit while a workgroup stays within
     // 5120 bytes (the allocation granule of this part is 1280 bytes: 5376 bytes measured 6 % slower, one wave per SIMD fewer)
     extern __shared__ float s_dyn[];
@@ -305,13 +328,27 @@ __global__ __launch_bounds__(64, EVPLP_GATHER_WAVES) void gather_vpl_kernel(Gath
     // The cut slots of the item's VPLs stream through a small LDS ring ahead of the walks (global_load_lds: asynchronous, counted by vmcnt,
     // no register in between).  A walk that fetched its slot itself began with two dependent scalar loads from memory no cache holds
     // (8.6 GB of slots per frame, each read once per tile): 65.6 ms against 70.6 ms without cuts although the node visits had halved.
+    // The VPL's record travels with its slot (kRecRing): lanes 16-21 of the same DMA instruction move its 96 bytes to right behind the slot's
+    // 256, so a ring buffer is 352 bytes and the record of VPL i is in LDS when its slot is -- two walks ahead of its use, and until the buffer
+    // is reused, which is after the step has shaded.  The step then reads it with same-address LDS reads (every lane gets the same bits)
+    // instead of two exposed scalar round trips to L2 per step: the head in front of the cosine test, head and tail again behind the walk.
     constexpr bool kRing = CUT && kWalkAsm;
+    constexpr bool kRecRing = kRing && EVPLP_VPL_RING != 0;
     constexpr int kRingSlots = EVPLP_CUT_RING, kAhead = kRingSlots - 1;
-    __shared__ float4 s_cut[kRing ? kRingSlots : 1][kCutSlotBytes / 16];
+    constexpr int kSlotF4 = kCutSlotBytes / 16, kRingF4 = kSlotF4 + (kRecRing ? kRecF4 : 0);
+    static_assert(kSlotF4 == 16 && kRecF4 == 6 && kRingF4 <= 64, "one DMA instruction moves slot and record: 16 + 6 lanes of 16 bytes");
+    __shared__ float4 s_cut[kRing ? kRingSlots : 1][kRingF4];
     int pj = 0; uint32_t pi = (uint32_t)(t.group * k), qslot = 0u;       // the prefetch position in the item's VPL sequence (split pj, VPL pi)
     auto ring_skip_empty = [&]() { while (pj < k && pi >= nvpl) { pj++; pi = (uint32_t)(t.group * k + pj); } };
+    const uintptr_t ring_lane_base = lane < kSlotF4 ? (uintptr_t)cuts_g + (uintptr_t)lane * 16u : (uintptr_t)vpls + (uintptr_t)(lane - kSlotF4) * 16u;
+    const uint32_t ring_lane_stride = lane < kSlotF4 ? (uint32_t)kCutSlotBytes : (uint32_t)sizeof(evplp_record);
     auto ring_issue = [&](uint32_t slot) {
-        if (lane < kCutSlotBytes / 16) lds_dma16(cuts_g + (size_t)pi * kCutSlotBytes + (size_t)lane * 16u, lds_offset(&s_cut[slot][0]));
+        if constexpr (kRecRing) {
+            // (pi < nvpl here -- ring_skip_empty -- so the record lies inside the array; lanes 22-63 are masked off and their address is not used)
+            // (a lane's source is its own base -- of the slots or of the records -- plus pi times its own stride: one 32 x 32 + 64 multiply-add)
+            const uintptr_t src = ring_lane_base + (uintptr_t)pi * (uintptr_t)ring_lane_stride;
+            if (lane < kRingF4) lds_dma16(reinterpret_cast<const void *>(src), lds_offset(&s_cut[slot][0]));
+        } else if (lane < kSlotF4) lds_dma16(cuts_g + (size_t)pi * kCutSlotBytes + (size_t)lane * 16u, lds_offset(&s_cut[slot][0]));
         pi += (uint32_t)kVplSplit; ring_skip_empty();
     };
     if constexpr (kRing) {
@@ -330,7 +367,12 @@ __global__ __launch_bounds__(64, EVPLP_GATHER_WAVES) void gather_vpl_kernel(Gath
                 cut_lds = &s_cut[qslot][0];
                 qslot = (qslot + 1u) % (uint32_t)kRingSlots;
             }
-            V3 vpos, vn; float vpsel; fetch_vpl_head(vpls, i, vpos, vn, vpsel);
+            V3 vpos, vn; float vpsel;
+            if constexpr (kRecRing) { const float4 h0 = cut_lds[kSlotF4], h1 = cut_lds[kSlotF4 + 1]; vpos = v3(h0); vn = v3(h1); vpsel = h1.w; }
+#if EVPLP_TAIL_PROBE
+            else if constexpr (kRing) fetch_vpl_head_probe(vpls, i, vpos, vn, vpsel);
+#endif
+            else fetch_vpl_head(vpls, i, vpos, vn, vpsel);
             V3 v12 = vpos - px.p1;                                         // :282
             float c1 = fmaxf(dot_exact(px.n1, v12), 0.0f);
             float c2 = fmaxf(-dot_exact(vn, v12), 0.0f);
@@ -382,21 +424,40 @@ __global__ __launch_bounds__(64, EVPLP_GATHER_WAVES) void gather_vpl_kernel(Gath
             }
             const bool lit = active && !occ;
             if (ballot64(lit) == 0ull) continue;
-            // (the record's head is fetched AGAIN for the shading -- it is in the scalar cache -- instead of holding its normal and lobe
-            // probability in four scalar registers across the walk, which has none to spare)
-            Vpl v; fetch_vpl_head(vpls, i, v.pos, v.n, v.psel); fetch_vpl_tail(vpls, i, v);
-            // ... and so are the four frame parameters the shading reads (MIS mode, pdfMc, its square, the clamp): from the kernel-argument
-            // segment, right here -- held in scalar registers from the top of the kernel they are spilled to VGPR lanes and read back
-            // lane by lane in every branch of vpl_shade
-            evplp_frame_params fps; float pdf_mc2;
-            {
-                const void *ka = (const void *)__builtin_amdgcn_kernarg_segment_ptr();
-                typedef int v4i_ __attribute__((ext_vector_type(4)));
-                v4i_ q; int q2;
-                asm volatile("s_load_dwordx4 %0, %2, %3\n\ts_load_dword %1, %2, %4\n\ts_waitcnt lgkmcnt(0)" : "=&s"(q), "=&s"(q2)
-                             : "s"(ka), "s"((uint32_t)(offsetof(GatherArgs, fp) + offsetof(evplp_frame_params, mis_mode))), "s"((uint32_t)offsetof(GatherArgs, pdf_mc2)) : "memory");
-                fps.mis_mode = (uint32_t)q[0]; fps.pdf_mc = f_of(q[1]); fps.clamping_value = f_of(q[2]); pdf_mc2 = f_of(q2);
+            // Behind the walk the record is read AGAIN instead of being held across it (the walk has no registers to spare), together with the
+            // four frame parameters the shading reads (MIS mode, pdfMc, its square, the clamp: from the kernel-argument segment, right here --
+            // held in scalar registers from the top of the kernel they are spilled to VGPR lanes and read back lane by lane in every branch
+            // of vpl_shade).
+            Vpl v; evplp_frame_params fps; float pdf_mc2;
+            typedef int v4i_ __attribute__((ext_vector_type(4)));
+            const void *ka = (const void *)__builtin_amdgcn_kernarg_segment_ptr();
+            constexpr uint32_t kFpOff = (uint32_t)(offsetof(GatherArgs, fp) + offsetof(evplp_frame_params, mis_mode)), kMc2Off = (uint32_t)offsetof(GatherArgs, pdf_mc2);
+            v4i_ q; int q2;
+            if constexpr (kRecRing) {
+                // From the ring buffer: normal + lobe probability, flux, direction, rho_d, rho_s + exponent (the position is not shaded with).
+                // The kernel arguments' two scalar loads are issued with the five LDS reads and all seven are waited for once.  What steers
+                // wave-uniform branches in vpl_shade -- rho_s and the exponent -- goes back to scalar registers so that those branches stay
+                // scalar; the other fields stay vector operands that hold the same bits in every lane.
+                typedef float v3f_ __attribute__((ext_vector_type(3)));
+                typedef float v4f_ __attribute__((ext_vector_type(4)));
+                v4f_ h1, t3; v3f_ t0, t1, t2;
+                asm volatile("s_load_dwordx4 %[q], %[ka], %[o1]\n\ts_load_dword %[q2], %[ka], %[o2]\n\t"
+                             "ds_read_b128 %[h1], %[ad] offset:%[c1]\n\tds_read_b96 %[t0], %[ad] offset:%[c2]\n\tds_read_b96 %[t1], %[ad] offset:%[c3]\n\t"
+                             "ds_read_b96 %[t2], %[ad] offset:%[c4]\n\tds_read_b128 %[t3], %[ad] offset:%[c5]\n\ts_waitcnt lgkmcnt(0)"
+                             : [q] "=&s"(q), [q2] "=&s"(q2), [h1] "=&v"(h1), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3)
+                             : [ka] "s"(ka), [o1] "s"(kFpOff), [o2] "s"(kMc2Off), [ad] "v"(lds_offset(cut_lds)),
+                               [c1] "n"(kCutSlotBytes + 16), [c2] "n"(kCutSlotBytes + 32), [c3] "n"(kCutSlotBytes + 48), [c4] "n"(kCutSlotBytes + 64), [c5] "n"(kCutSlotBytes + 80)
+                             : "memory");
+                auto uni = [](float x) { return f_of(__builtin_amdgcn_readfirstlane(__float_as_int(x))); };
+                v.pos = vpos; v.n = v3(h1.x, h1.y, h1.z); v.psel = h1.w;
+                v.flux = v3(t0.x, t0.y, t0.z); v.fdir = v3(t1.x, t1.y, t1.z); v.rd = v3(t2.x, t2.y, t2.z);
+                v.rs = v3(uni(t3.x), uni(t3.y), uni(t3.z)); v.e = uni(t3.w);
+            } else {
+                // (scalar fetches: the head is in the scalar cache)
+                fetch_vpl_head(vpls, i, v.pos, v.n, v.psel); fetch_vpl_tail(vpls, i, v);
+                asm volatile("s_load_dwordx4 %0, %2, %3\n\ts_load_dword %1, %2, %4\n\ts_waitcnt lgkmcnt(0)" : "=&s"(q), "=&s"(q2) : "s"(ka), "s"(kFpOff), "s"(kMc2Off) : "memory");
             }
+            fps.mis_mode = (uint32_t)q[0]; fps.pdf_mc = f_of(q[1]); fps.clamping_value = f_of(q[2]); pdf_mc2 = f_of(q2);
             if (lit) { result = result + vpl_shade<EVPLP_PX_LDS != 0>(fps, pdf_mc2, px, v, v12, c1c2, EVPLP_WI10_LDS ? s_wi10 + lane : nullptr, px_glossy); shaded++; }
         }
         // fold the split sums in the fixed balanced-tree order: a binary counter whose level j holds the sum of 2^j splits.
@@ -408,8 +469,12 @@ __global__ __launch_bounds__(64, EVPLP_GATHER_WAVES) void gather_vpl_kernel(Gath
                 result = v3(q[0], q[64], q[128]) + result;
                 lev++;
             }
-            float *q = s_lvl + lev * 192 + lane;
-            q[0] = result.x; q[64] = result.y; q[128] = result.z;
+            // (the last split's store would go to the top level, log2 k, which nothing reads: `total` below is the result, and the launcher
+            // sizes the dynamic LDS without that level -- launch_gather_vpl_items)
+            if (jj != k - 1) {
+                float *q = s_lvl + lev * 192 + lane;
+                q[0] = result.x; q[64] = result.y; q[128] = result.z;
+            }
         }
         total = result;     // after the last jj (k - 1 = all ones) this is the sum of all k splits
     }
@@ -1089,14 +1154,12 @@ void launch_gather_reduce_budget(const GatherArgs &a, int stencil_test, const in
     const size_t n = (size_t)a.st.W * a.st.local_rows;
     hipLaunchKernelGGL(gather_reduce_budget_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, stencil_test, tiles, mask, snap, n1);
 }
-static size_t fold_lds_bytes(const GatherArgs &a, int extra_floats) {
-    int levels = 1; while ((1 << (levels - 1)) < a.splits_per_wave) levels++;       // log2 k + 1
-    return (size_t)(levels * 192 + extra_floats) * sizeof(float);
-}
+// (gather_vsl_shade_kernel stores every level of its fold, the top one included)
+static size_t fold_lds_bytes(const GatherArgs &a, int extra_floats) { return gather_fold_lds_bytes(a.splits_per_wave, extra_floats, true); }
 // (a.block_cost set: the calibration variants of the same kernels -- same results, every item also clocks itself; they gather every tile,
 // retired or not: gather_reduce_kernel<true> ignores what they leave for retired pixels.  ad.tiles set otherwise: the ADAPT variants)
 void launch_gather_vpl_items(const GatherArgs &a, hipStream_t s, const AdaptArgs &ad) {
-    const size_t lds = fold_lds_bytes(a, kGatherPxFloats);
+    const size_t lds = gather_vpl_lds_bytes(a.splits_per_wave);     // (no block for the top fold level: the kernel does not store it)
     if (ad.tiles && !a.block_cost) {
         if (a.cuts) hipLaunchKernelGGL((gather_vpl_kernel<true, false, true>), gather_grid(a), dim3(64), lds, s, a, ad);
         else hipLaunchKernelGGL((gather_vpl_kernel<false, false, true>), gather_grid(a), dim3(64), lds, s, a, ad);
