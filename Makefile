@@ -8,7 +8,7 @@ HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-functio
 HOSTFLAGS = -O2 -std=c++17 -fPIC -Wall -Wno-unused-value -ffp-contract=off
 
 HIP_SRCS = $(CSRC)/kernels_trace.hip $(CSRC)/kernels_gather.hip $(CSRC)/kernels_cut.hip $(CSRC)/kernels_splat.hip $(CSRC)/kernels_pt.hip $(CSRC)/kernels_ptbatch.hip $(CSRC)/kernels_ptbatch_primary.hip $(CSRC)/kernels_stats.hip $(CSRC)/kernels_denoise.hip $(CSRC)/kernels_temporal.hip $(CSRC)/bvh_gpu.hip $(CSRC)/selftest.hip
-CPP_SRCS = $(CSRC)/context.cpp $(CSRC)/group.cpp $(CSRC)/bvh_build.cpp $(wildcard $(CSRC)/host/*.cpp)
+CPP_SRCS = $(CSRC)/context.cpp $(CSRC)/scene_motion.cpp $(CSRC)/group.cpp $(CSRC)/bvh_build.cpp $(wildcard $(CSRC)/host/*.cpp)
 # VARIANT selects a separate object directory and library name (developer builds, e.g. `make stats`)
 VARIANT ?=
 BUILD = build$(if $(VARIANT),/$(VARIANT),)

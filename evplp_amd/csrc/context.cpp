@@ -1,13 +1,10 @@
 // C-ABI implementation (include/evplp.h): context, scene upload, pass launchers, statistics.
 // There is deliberately no CPU execution path here: every pass is a HIP kernel launch.
 #include "context.hpp"
-#include "host/morph.hpp"
-#include "host/skin.hpp"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
-#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -24,9 +21,6 @@ void evplp_context::set_error(const char *fmt, ...) {
     vsnprintf(error, sizeof(error), fmt, ap);
     va_end(ap);
 }
-
-#define CTX_CHECK(ctx) do { if (!(ctx)) return EVPLP_ERR_INVALID; if ((ctx)->quiesce && std::this_thread::get_id() != (ctx)->worker_tid) (ctx)->quiesce((ctx)->quiesce_arg); } while (0)
-#define HIP_TRY(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { (ctx)->set_error("%s failed: %s", #expr, hipGetErrorString(e_)); return EVPLP_ERR_HIP; } } while (0)
 
 static size_t buffer_bytes(const evplp_context *c, int which) {
     const size_t px = (size_t)c->st.W * c->st.local_rows;
@@ -205,28 +199,7 @@ static void free_scene_device(evplp_context *c) {
     hipFree((void *)c->sc.nodes); hipFree((void *)c->sc.nodes4); hipFree((void *)c->sc.leaves); hipFree((void *)c->sc.tri_flat); hipFree((void *)c->sc.tri_index); hipFree((void *)c->sc.attrs);
     hipFree((void *)c->sc.materials); hipFree((void *)c->sc.textures); hipFree((void *)c->sc.tex_pool); hipFree((void *)c->sc.light_cdf);
     std::memset(&c->sc, 0, sizeof(c->sc));
-    // the refit's plan and staging belong to the tree (made by the first evplp_refit_accel)
-    hipFree(c->d_refit_order); hipFree(c->d_refit_boxes); hipFree(c->d_refit_stage); if (c->h_refit_stage) hipHostFree(c->h_refit_stage);
-    c->d_refit_order = nullptr; c->d_refit_boxes = c->d_refit_stage = c->h_refit_stage = nullptr;
-    c->refit_levels = 0; c->refit_level_begin.clear(); std::vector<BvhNode>().swap(c->host_nodes);
-    // ... and so does the output of the cost kernel (made by the first evplp_accel_quality)
-    hipFree(c->d_cost); if (c->h_cost) hipHostFree(c->h_cost);
-    c->d_cost = c->h_cost = nullptr; c->refit_reached = c->refit_leaf_refs = 0;
-    // ... and the rest pose and the descriptor tables of evplp_transform_mesh (made by the first transform; the host keeps every rest pose)
-    hipFree(c->d_rest); hipFree(c->d_xform); if (c->h_xform) hipHostFree(c->h_xform);
-    c->d_rest = nullptr; c->d_xform = c->h_xform = nullptr;
-    for (HostMesh &m : c->meshes) m.rest_state = 0;
-    // ... and the corner skins, the palettes and the descriptor tables of evplp_pose_mesh (made by the first posed refit; the host keeps every skin)
-    hipFree(c->d_skin); hipFree(c->d_bones); hipFree(c->d_sdesc); if (c->h_bones) hipHostFree(c->h_bones); if (c->h_sdesc) hipHostFree(c->h_sdesc);
-    c->d_skin = nullptr; c->d_bones = c->h_bones = nullptr; c->d_sdesc = c->h_sdesc = nullptr; c->skin_cap = c->bone_cap = 0; c->skin_stale = true;
-    for (HostMesh &m : c->meshes) m.skin_at = -1;
-    // ... and the corner deltas, the base array, the weight sets and the descriptor tables of evplp_morph_mesh (made by the first morphed refit; the host keeps every target)
-    hipFree(c->d_morph); hipFree(c->d_base); hipFree(c->d_mweights); hipFree(c->d_mdesc); if (c->h_mweights) hipHostFree(c->h_mweights); if (c->h_mdesc) hipHostFree(c->h_mdesc);
-    c->d_morph = c->d_base = c->d_mweights = c->h_mweights = nullptr; c->d_mdesc = c->h_mdesc = nullptr; c->morph_cap = 0; c->weight_cap = 0; c->morph_stale = true;
-    for (HostMesh &m : c->meshes) { m.morph_at = -1; m.base_state = 0; }
-    // ... and the scratch of the rotating sweep (made by the first call that asks for rotations)
-    hipFree(c->d_rotate); hipFree(c->d_rotate_out); if (c->h_rotate_out) hipHostFree(c->h_rotate_out);
-    c->d_rotate = c->d_rotate_out = c->h_rotate_out = nullptr; std::vector<int32_t>().swap(c->refit_height);
+    release_scene_motion(c);        // (scene_motion.cpp: the refit's plan and staging, the cost kernel's output, rest pose, skins, morph targets, the rotating sweep's scratch)
 }
 
 extern "C" void evplp_destroy(evplp_context *c) {
@@ -389,19 +362,20 @@ static void flatten_verts(const evplp_context *c, std::vector<float> &verts, std
 // What a scene carries besides its tree: the area-light CDF, light_area and the light's padded bounds, total_area, bounding_radius, and the
 // builders' box pad.  All of them are folds of per-mesh figures: mesh_figures is the one body for a mesh (evplp_build_accel runs it over every
 // mesh, evplp_refit_accel over the dirty ones), light_figures the one for the light mesh, and scene_fold adds the meshes up in mesh order.
-// evplp_build_accel and evplp_refit_accel both come here, so a refit's figures are a fresh build's.
+// evplp_build_accel and evplp_refit_accel (scene_motion.cpp) both come here, so a refit's figures are a fresh build's.
 static float tri_area(const float *v) {              // Triangle::ComputeArea
     float a[3] = { v[3] - v[0], v[4] - v[1], v[5] - v[2] }, b[3] = { v[6] - v[0], v[7] - v[1], v[8] - v[2] };
     float cx = a[1] * b[2] - a[2] * b[1], cy = a[2] * b[0] - a[0] * b[2], cz = a[0] * b[1] - a[1] * b[0];
     return std::sqrt(cx * cx + cy * cy + cz * cz) / 2.0f;
 }
+namespace evplp {
 // mesh m's triangles, 9 floats each, from `from` (its positions or its rest pose)
-static void flatten_mesh(const HostMesh &m, const std::vector<float> &from, float *o) {
+void flatten_mesh(const HostMesh &m, const std::vector<float> &from, float *o) {
     for (size_t i = 0; i < m.idx.size(); i++, o += 3) std::memcpy(o, &from[3 * (size_t)m.idx[i]], 12);
 }
 // scene metrics (rtcommon.h:759-768, 805-814): the mesh's running float sum of areas and the box of all its vertices; the box of its triangles
 // that the builders keep (tri_has_area).  flat: the mesh's triangles (flatten_mesh); has_area: null, or one byte per triangle of the mesh
-static void mesh_figures(HostMesh &m, const float *flat, char *has_area) {
+void mesh_figures(HostMesh &m, const float *flat, char *has_area) {
     float ms = 0.f;
     for (int k = 0; k < 3; k++) { m.lo[k] = 3.4028235e38f; m.hi[k] = -3.4028235e38f; m.alo[k] = 3.0e38f; m.ahi[k] = -3.0e38f; }
     m.any_area = false;
@@ -419,7 +393,7 @@ static void mesh_figures(HostMesh &m, const float *flat, char *has_area) {
 }
 // area-light CDF, rt/rtcommon.h:501-531 (running float sum, then normalised), light_area, and the unpadded bounds of the light's triangles
 // (flat: the light mesh's triangles)
-static void light_figures(evplp_context *c, const float *flat, std::vector<float> &cdf) {
+void light_figures(evplp_context *c, const float *flat, std::vector<float> &cdf) {
     const size_t n = c->meshes[(size_t)c->light_mesh].idx.size() / 3;
     cdf.resize(n);
     float sum = 0.f;
@@ -433,7 +407,7 @@ static void light_figures(evplp_context *c, const float *flat, std::vector<float
     c->light_area = sum; c->sc.light_area = sum;
 }
 // the meshes' figures in mesh order; returns the builders' box pad for the bounds of the triangles they keep
-static float scene_fold(evplp_context *c) {
+float scene_fold(evplp_context *c) {
     float total = 0.f; float lo[3] = { 3.4028235e38f, 3.4028235e38f, 3.4028235e38f }, hi[3] = { -3.4028235e38f, -3.4028235e38f, -3.4028235e38f };
     float alo[3] = { 3.0e38f, 3.0e38f, 3.0e38f }, ahi[3] = { -3.0e38f, -3.0e38f, -3.0e38f };
     bool any = false;
@@ -450,9 +424,8 @@ static float scene_fold(evplp_context *c) {
     return bvh_pad(alo, ahi, any);
 }
 
-static int measure_cost(evplp_context *c, double out[5]);
 // evplp_build_accel, and the rebuild of a refit policy (policy_builder >= 0: that builder instead of the context's own)
-static int build_accel(evplp_context *c, int policy_builder) {
+int build_accel(evplp_context *c, int policy_builder) {
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     if (c->meshes.empty()) { c->set_error("evplp_build_accel: no meshes"); return EVPLP_ERR_INVALID; }
     if (c->light_mesh < 0) { c->set_error("evplp_build_accel: no area light set"); return EVPLP_ERR_INVALID; }
@@ -563,13 +536,14 @@ static int build_accel(evplp_context *c, int policy_builder) {
     c->sc.light_first = light_first; c->sc.light_count = light_count; c->sc.light_area = sum;
     std::memcpy(c->sc.light_intensity, c->light_scaled, 16); std::memcpy(c->sc.light_unscaled, c->light_unscaled, 16);
     c->accel_built = true; c->primary_cuts_valid = false; c->primary_current = false;
-    c->mesh_dirty.assign(c->meshes.size(), 0); c->scene_dirty = false;
+    c->mesh_dirty.assign(c->meshes.size(), MeshDirty::Clean); c->scene_dirty = false;
     c->built_cost = 0.0; c->built_cost_known = false; c->refits_since_build = 0; c->rotations_since_build = 0;
     if (c->policy_ratio > 0.0) {            // (a policy compares against the cost of the tree as built: one small launch and a wait)
         double q[5];
         if ((rc = measure_cost(c, q))) return rc;
     }
     return EVPLP_OK;
+}
 }
 extern "C" int evplp_build_accel(evplp_context *c) {
     CTX_CHECK(c);
@@ -594,752 +568,6 @@ extern "C" int evplp_accel_info(evplp_context *c, int32_t *nodes, int32_t *leave
 extern "C" int evplp_accel_builder(const evplp_context *c) {
     if (!c || !c->accel_built) return -1;
     return c->accel_builder_used;
-}
-
-// ---------------------------------------------------------------------------------- moving vertices: update, refit
-static_assert(offsetof(BvhNode, c0) == 48 && offsetof(BvhNode, c1) == 52, "host/refit_levels.cpp reads the child references at these offsets");
-
-namespace evplp {
-// evplp_update_mesh's refusals, for the group's caller thread as well (false: the reason is in c's error)
-bool update_mesh_check(evplp_context *c, int32_t mesh, const float *vertices, int32_t nverts) {
-    if (!c->accel_built) { c->set_error("evplp_update_mesh: scene not built (evplp_build_accel)"); return false; }
-    if (mesh < 0 || mesh >= (int32_t)c->meshes.size()) { c->set_error("evplp_update_mesh: mesh %d out of range (%zu meshes)", mesh, c->meshes.size()); return false; }
-    if (!vertices) { c->set_error("evplp_update_mesh: null vertices"); return false; }
-    const size_t have = c->meshes[(size_t)mesh].verts.size() / 3;
-    if (nverts < 0 || (size_t)nverts != have) { c->set_error("evplp_update_mesh: mesh %d has %zu vertices, not %d (the topology stays)", mesh, have, nverts); return false; }
-    for (size_t i = 0; i < 3 * have; i++) if (!std::isfinite(vertices[i])) { c->set_error("evplp_update_mesh: vertex %zu of mesh %d is not finite", i / 3, mesh); return false; }
-    return true;
-}
-// evplp_transform_mesh's refusals, likewise.  The transformed coordinates are checked on the host copy's rest pose, by the function that
-// will move it: a matrix that overflows a coordinate is refused here, not rendered.
-bool transform_mesh_check(evplp_context *c, int32_t mesh, const float *matrix) {
-    if (!c->accel_built) { c->set_error("evplp_transform_mesh: scene not built (evplp_build_accel)"); return false; }
-    if (mesh < 0 || mesh >= (int32_t)c->meshes.size()) { c->set_error("evplp_transform_mesh: mesh %d out of range (%zu meshes)", mesh, c->meshes.size()); return false; }
-    if (!matrix) { c->set_error("evplp_transform_mesh: null matrix"); return false; }
-    for (int i = 0; i < 12; i++) if (!std::isfinite(matrix[i])) { c->set_error("evplp_transform_mesh: matrix entry %d is not finite", i); return false; }
-    const HostMesh &m = c->meshes[(size_t)mesh];
-    const std::vector<float> &rest = mesh_base(m);             // (the morphed base while morph weights are in force)
-    for (size_t v = 0; v < rest.size() / 3; v++) {
-        float o[3]; transform_point(matrix, &rest[3 * v], o);
-        if (!std::isfinite(o[0]) || !std::isfinite(o[1]) || !std::isfinite(o[2])) { c->set_error("evplp_transform_mesh: vertex %zu of mesh %d is not finite under the matrix", v, mesh); return false; }
-    }
-    return true;
-}
-// evplp_set_mesh_skin's and evplp_pose_mesh's refusals, likewise (the arrays' own by host/skin.cpp).  The posed coordinates are checked on the
-// host copy's rest pose, by the function that will move it.
-bool set_mesh_skin_check(evplp_context *c, int32_t mesh, int32_t nbones, const int32_t *bone_index, const float *weight, int32_t nverts) {
-    if (!c->accel_built) { c->set_error("evplp_set_mesh_skin: scene not built (evplp_build_accel)"); return false; }
-    if (mesh < 0 || mesh >= (int32_t)c->meshes.size()) { c->set_error("evplp_set_mesh_skin: mesh %d out of range (%zu meshes)", mesh, c->meshes.size()); return false; }
-    if (nbones == 0) return true;                   // (the skin is removed: the arrays are not looked at)
-    const size_t have = c->meshes[(size_t)mesh].verts.size() / 3;
-    if (nverts < 0 || (size_t)nverts != have) { c->set_error("evplp_set_mesh_skin: mesh %d has %zu vertices, not %d", mesh, have, nverts); return false; }
-    if (!bone_index || !weight) { c->set_error("evplp_set_mesh_skin: null %s", !bone_index ? "bone_index" : "weight"); return false; }
-    char why[256];
-    if (!skin_arrays_ok(nbones, bone_index, weight, nverts, why, sizeof(why))) { c->set_error("evplp_set_mesh_skin: mesh %d: %s", mesh, why); return false; }
-    return true;
-}
-bool pose_mesh_check(evplp_context *c, int32_t mesh, const float *bone_matrices, int32_t nbones, std::vector<float> *posed_out) {
-    if (!c->accel_built) { c->set_error("evplp_pose_mesh: scene not built (evplp_build_accel)"); return false; }
-    if (mesh < 0 || mesh >= (int32_t)c->meshes.size()) { c->set_error("evplp_pose_mesh: mesh %d out of range (%zu meshes)", mesh, c->meshes.size()); return false; }
-    const HostMesh &m = c->meshes[(size_t)mesh];
-    if (m.skin_bones <= 0) { c->set_error("evplp_pose_mesh: mesh %d has no skin (evplp_set_mesh_skin)", mesh); return false; }
-    if (nbones != m.skin_bones) { c->set_error("evplp_pose_mesh: the skin of mesh %d has %d bones, not %d", mesh, m.skin_bones, nbones); return false; }
-    char why[256];
-    if (!skin_palette_ok(bone_matrices, nbones, why, sizeof(why))) { c->set_error("evplp_pose_mesh: mesh %d: %s", mesh, why); return false; }
-    const std::vector<float> &rest = mesh_base(m);             // (the morphed base while morph weights are in force)
-    std::vector<float> posed(rest.size());
-    const int64_t bad = skin_apply(bone_matrices, m.skin_index.data(), m.skin_weight.data(), rest.data(), posed.data(), rest.size() / 3);
-    if (bad >= 0) { c->set_error("evplp_pose_mesh: vertex %lld of mesh %d is not finite under the palette", (long long)bad, mesh); return false; }
-    if (posed_out) posed_out->swap(posed);          // (the context's own call keeps the positions the check has just made)
-    return true;
-}
-// evplp_set_mesh_morph's and evplp_morph_mesh's refusals, likewise (the arrays' own, and every loop over the vertices, by host/morph.cpp).  The
-// final coordinates -- the morphed base under the matrix or the pose in force -- are checked on the host copy, by the functions that move it.
-bool set_mesh_morph_check(evplp_context *c, int32_t mesh, int32_t ntargets, const float *deltas, int32_t nverts) {
-    if (!c->accel_built) { c->set_error("evplp_set_mesh_morph: scene not built (evplp_build_accel)"); return false; }
-    if (mesh < 0 || mesh >= (int32_t)c->meshes.size()) { c->set_error("evplp_set_mesh_morph: mesh %d out of range (%zu meshes)", mesh, c->meshes.size()); return false; }
-    const HostMesh &m = c->meshes[(size_t)mesh];
-    if (!m.morph_w.empty()) { c->set_error("evplp_set_mesh_morph: mesh %d has morph weights in force: take them away first (evplp_morph_mesh(ctx, mesh, NULL, 0))", mesh); return false; }
-    if (ntargets == 0) return true;                 // (the targets are removed: the array is not looked at)
-    const size_t have = m.verts.size() / 3;
-    if (nverts < 0 || (size_t)nverts != have) { c->set_error("evplp_set_mesh_morph: mesh %d has %zu vertices, not %d", mesh, have, nverts); return false; }
-    if (!deltas) { c->set_error("evplp_set_mesh_morph: null deltas"); return false; }
-    char why[256];
-    if (!morph_deltas_ok(ntargets, deltas, nverts, why, sizeof(why))) { c->set_error("evplp_set_mesh_morph: mesh %d: %s", mesh, why); return false; }
-    return true;
-}
-bool morph_mesh_check(evplp_context *c, int32_t mesh, const float *weights, int32_t ntargets, std::vector<float> *base_out, std::vector<float> *moved_out) {
-    if (!c->accel_built) { c->set_error("evplp_morph_mesh: scene not built (evplp_build_accel)"); return false; }
-    if (mesh < 0 || mesh >= (int32_t)c->meshes.size()) { c->set_error("evplp_morph_mesh: mesh %d out of range (%zu meshes)", mesh, c->meshes.size()); return false; }
-    const HostMesh &m = c->meshes[(size_t)mesh];
-    const std::vector<float> &rest = m.rest.empty() ? m.verts : m.rest;
-    const size_t n = rest.size() / 3;
-    std::vector<float> base, moved(rest.size());
-    if (ntargets != 0 || weights) {                 // (NULL, 0 takes the weights away: the positions are the rest pose's again)
-        if (m.morph_targets <= 0) { c->set_error("evplp_morph_mesh: mesh %d has no morph targets (evplp_set_mesh_morph)", mesh); return false; }
-        if (ntargets != m.morph_targets) { c->set_error("evplp_morph_mesh: mesh %d has %d morph targets, not %d", mesh, m.morph_targets, ntargets); return false; }
-        char why[256];
-        if (!morph_weights_ok(weights, ntargets, why, sizeof(why))) { c->set_error("evplp_morph_mesh: mesh %d: %s", mesh, why); return false; }
-        base.resize(rest.size());
-        const int64_t bad = morph_apply(m.morph_delta.data(), weights, ntargets, rest.data(), base.data(), n);
-        if (bad >= 0) { c->set_error("evplp_morph_mesh: vertex %lld of mesh %d is not finite under the weights", (long long)bad, mesh); return false; }
-    } else if (m.morph_w.empty()) {                 // (none in force: nothing moves)
-        if (base_out) base_out->clear(); if (moved_out) moved_out->clear();
-        return true;
-    }
-    const int64_t bad = morph_deform(base.empty() ? rest.data() : base.data(), m.palette.empty() && m.has_matrix ? m.matrix : nullptr, m.palette.empty() ? nullptr : m.palette.data(),
-                                     m.skin_index.data(), m.skin_weight.data(), moved.data(), n);
-    if (bad >= 0) { c->set_error("evplp_morph_mesh: vertex %lld of mesh %d is not finite under the weights and the %s in force", (long long)bad, mesh, m.palette.empty() ? "matrix" : "pose"); return false; }
-    if (base_out) base_out->swap(base);
-    if (moved_out) moved_out->swap(moved);
-    return true;
-}
-// evplp_refit_accel's refusal: a triangle the build dropped (no area) that has one now has no leaf slot to go to
-bool refit_check(evplp_context *c) {
-    if (!c->accel_built) { c->set_error("evplp_refit_accel: scene not built (evplp_build_accel)"); return false; }
-    size_t first = 0;
-    for (size_t mi = 0; mi < c->meshes.size(); first += c->meshes[mi].idx.size() / 3, mi++) {
-        if (!c->scene_dirty || !c->mesh_dirty[mi]) continue;
-        const HostMesh &m = c->meshes[mi];
-        for (size_t t = 0; t < m.idx.size() / 3; t++) {
-            if (!c->tri_dropped[first + t]) continue;
-            float v[9];
-            for (int k = 0; k < 3; k++) std::memcpy(v + 3 * k, &m.verts[3 * (size_t)m.idx[3 * t + k]], 12);
-            if (tri_has_area(v)) {
-                c->set_error("evplp_refit_accel: triangle %zu of mesh %zu had no area when the tree was built and has one now: it has no leaf to go to, call evplp_build_accel", t, mi);
-                return false;
-            }
-        }
-    }
-    return true;
-}
-}
-
-extern "C" int evplp_update_mesh(evplp_context *c, int32_t mesh, const float *vertices, int32_t nverts) {
-    CTX_CHECK(c);
-    if (!evplp::update_mesh_check(c, mesh, vertices, nverts)) return EVPLP_ERR_INVALID;
-    HostMesh &m = c->meshes[(size_t)mesh];
-    std::memcpy(m.verts.data(), vertices, sizeof(float) * 3 * (size_t)nverts);
-    std::vector<float>().swap(m.rest); m.rest_state = 0;        // (a new rest pose: the matrix is forgotten, the device's copy is stale)
-    std::vector<float>().swap(m.palette); m.has_matrix = false; // (... and so is a pose; the skin stays)
-    std::vector<float>().swap(m.morph_w); std::vector<float>().swap(m.base); if (m.base_state == 1) m.base_state = 2;   // (... and so are morph weights; the targets stay)
-    c->mesh_dirty[(size_t)mesh] = 1; c->scene_dirty = true;
-    return EVPLP_OK;
-}
-
-extern "C" int evplp_transform_points(const float *m, const float *in, float *out, int32_t n) {
-    if (!m || n < 0 || (n > 0 && (!in || !out))) return EVPLP_ERR_INVALID;
-    for (int32_t i = 0; i < n; i++) { float o[3]; evplp::transform_point(m, in + 3 * (size_t)i, o); std::memcpy(out + 3 * (size_t)i, o, 12); }
-    return EVPLP_OK;
-}
-
-// the first transform or pose of this scene: the rest-pose array and the two descriptor tables of the transform launch
-static int rest_prepare(evplp_context *c, const char *name) {
-    if (c->d_rest) return EVPLP_OK;
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    hipError_t e = hipMalloc((void **)&c->d_rest, sizeof(float) * 9 * (size_t)std::max(c->scene_tris, 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&c->d_xform, sizeof(TransformDesc) * c->meshes.size());
-    if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_xform, sizeof(TransformDesc) * c->meshes.size(), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        hipFree(c->d_rest); hipFree(c->d_xform); c->d_rest = nullptr; c->d_xform = nullptr;
-        c->set_error("%s: the rest pose on the device: %s", name, hipGetErrorString(e)); return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP;
-    }
-    return EVPLP_OK;
-}
-
-extern "C" int evplp_transform_mesh(evplp_context *c, int32_t mesh, const float *matrix) {
-    CTX_CHECK(c);
-    if (!evplp::transform_mesh_check(c, mesh, matrix)) return EVPLP_ERR_INVALID;
-    HostMesh &m = c->meshes[(size_t)mesh];
-    { const int rc = rest_prepare(c, "evplp_transform_mesh"); if (rc) return rc; }
-    // the device's copy of this mesh's rest pose is made by the refit: from the attributes while they still hold it (a clean mesh that has
-    // no matrix), from the host's rest pose otherwise
-    if (m.rest_state == 0) m.rest_state = (!c->mesh_dirty[(size_t)mesh] && m.rest.empty()) ? 1 : 2;
-    if (m.rest.empty()) m.rest = m.verts;
-    const std::vector<float> &from = evplp::mesh_base(m);       // (morphed first, then moved: the base while morph weights are in force)
-    for (size_t v = 0; v < from.size() / 3; v++) evplp::transform_point(matrix, &from[3 * v], &m.verts[3 * v]);
-    std::memcpy(m.matrix, matrix, sizeof(m.matrix)); m.has_matrix = true;
-    std::vector<float>().swap(m.palette);                       // (a matrix replaces a pose)
-    c->mesh_dirty[(size_t)mesh] = 2; c->scene_dirty = true;
-    return EVPLP_OK;
-}
-
-// ---- moving a mesh by bones: the skin (constant for the topology), the pose (a palette of matrices over the rest pose), and the queries a
-// caller needs to build a skin for a scene the library loaded
-extern "C" int evplp_set_mesh_skin(evplp_context *c, int32_t mesh, int32_t nbones, const int32_t *bone_index, const float *weight, int32_t nverts) {
-    CTX_CHECK(c);
-    if (!evplp::set_mesh_skin_check(c, mesh, nbones, bone_index, weight, nverts)) return EVPLP_ERR_INVALID;
-    HostMesh &m = c->meshes[(size_t)mesh];
-    // A pose that no refit has taken to the device yet stays what it is on the host copy: the mesh goes up by upload instead (its rest pose is kept)
-    // -- and the upload overwrites the attributes, so a rest pose that was still to be taken from them (rest_state 1) comes from the host's instead
-    if (c->mesh_dirty[(size_t)mesh] == 3) { c->mesh_dirty[(size_t)mesh] = 1; if (m.rest_state == 1) m.rest_state = 2; }
-    std::vector<float>().swap(m.palette);
-    m.skin_bones = nbones; m.skin_at = -1; c->skin_stale = true;
-    if (nbones == 0) { std::vector<int32_t>().swap(m.skin_index); std::vector<float>().swap(m.skin_weight); return EVPLP_OK; }
-    m.skin_index.assign(bone_index, bone_index + 4 * (size_t)nverts);
-    m.skin_weight.assign(weight, weight + 4 * (size_t)nverts);
-    return EVPLP_OK;
-}
-
-namespace evplp {
-// evplp_pose_mesh behind its check: posed = the mesh's posed positions as pose_mesh_check made them (float3 per vertex).  The group checks once,
-// on the caller's thread against rank 0's copy, and hands the same positions to every rank: the ranks' scenes are the same.
-int pose_mesh_apply(evplp_context *c, int32_t mesh, const float *bone_matrices, int32_t nbones, const float *posed) {
-    HostMesh &m = c->meshes[(size_t)mesh];
-    { const int rc = rest_prepare(c, "evplp_pose_mesh"); if (rc) return rc; }
-    // (the device's copy of the rest pose: as for a matrix)
-    if (m.rest_state == 0) m.rest_state = (!c->mesh_dirty[(size_t)mesh] && m.rest.empty()) ? 1 : 2;
-    if (m.rest.empty()) m.rest = m.verts;
-    std::memcpy(m.verts.data(), posed, sizeof(float) * m.verts.size());    // (skin_apply of the rest pose, by the check)
-    m.palette.assign(bone_matrices, bone_matrices + 12 * (size_t)nbones); m.has_matrix = false;   // (a pose replaces a matrix)
-    c->mesh_dirty[(size_t)mesh] = 3; c->scene_dirty = true;
-    return EVPLP_OK;
-}
-}
-
-extern "C" int evplp_pose_mesh(evplp_context *c, int32_t mesh, const float *bone_matrices, int32_t nbones) {
-    CTX_CHECK(c);
-    std::vector<float> posed;
-    if (!evplp::pose_mesh_check(c, mesh, bone_matrices, nbones, &posed)) return EVPLP_ERR_INVALID;
-    return evplp::pose_mesh_apply(c, mesh, bone_matrices, nbones, posed.data());
-}
-
-// ---- moving a mesh by morph targets: the targets (constant for the topology) and the weights, a state of their own beside matrix and pose:
-// the weights make the mesh's base from its rest pose, and the matrix or the pose in force acts on that base (morphed first, then moved)
-extern "C" int evplp_set_mesh_morph(evplp_context *c, int32_t mesh, int32_t ntargets, const float *deltas, int32_t nverts) {
-    CTX_CHECK(c);
-    if (!evplp::set_mesh_morph_check(c, mesh, ntargets, deltas, nverts)) return EVPLP_ERR_INVALID;
-    HostMesh &m = c->meshes[(size_t)mesh];
-    m.morph_targets = ntargets; m.morph_at = -1; c->morph_stale = true;
-    if (ntargets == 0) std::vector<float>().swap(m.morph_delta);
-    else m.morph_delta.assign(deltas, deltas + 3 * (size_t)nverts * (size_t)ntargets);
-    return EVPLP_OK;
-}
-
-namespace evplp {
-// evplp_morph_mesh behind its check: base / moved = the mesh's morphed base and its positions as morph_mesh_check made them (float3 per vertex;
-// ntargets = 0: moved alone, the positions without weights).  The group checks once, on the caller's thread against rank 0's copy, and hands
-// the same positions to every rank.
-int morph_mesh_apply(evplp_context *c, int32_t mesh, const float *weights, int32_t ntargets, const float *base, const float *moved) {
-    HostMesh &m = c->meshes[(size_t)mesh];
-    const int kind = !m.palette.empty() ? 3 : m.has_matrix ? 2 : 4;
-    if (ntargets == 0 && m.morph_w.empty()) return EVPLP_OK;     // (none were in force: nothing moves, nothing is dirty)
-    { const int rc = rest_prepare(c, "evplp_morph_mesh"); if (rc) return rc; }
-    // (the device's copy of the rest pose: as for a matrix)
-    if (m.rest_state == 0) m.rest_state = (!c->mesh_dirty[(size_t)mesh] && m.rest.empty()) ? 1 : 2;
-    if (m.rest.empty()) m.rest = m.verts;
-    if (ntargets == 0) {
-        std::vector<float>().swap(m.morph_w); std::vector<float>().swap(m.base);
-        if (m.base_state == 1) m.base_state = 2;
-        std::memcpy(m.verts.data(), moved, sizeof(float) * m.verts.size());
-        // (a mesh that nothing moves any more is at its rest pose: that goes up by upload, like new vertices, and the device's rest pose stays)
-        c->mesh_dirty[(size_t)mesh] = kind == 4 ? 1 : (char)kind; c->scene_dirty = true;
-        return EVPLP_OK;
-    }
-    m.morph_w.assign(weights, weights + ntargets);
-    m.base.assign(base, base + m.verts.size());
-    if (m.base_state == 1) m.base_state = 2;        // (the device's base, if it holds one, is that of other weights)
-    std::memcpy(m.verts.data(), moved, sizeof(float) * m.verts.size());
-    c->mesh_dirty[(size_t)mesh] = (char)kind; c->scene_dirty = true;
-    return EVPLP_OK;
-}
-}
-
-extern "C" int evplp_morph_mesh(evplp_context *c, int32_t mesh, const float *weights, int32_t ntargets) {
-    CTX_CHECK(c);
-    std::vector<float> base, moved;
-    if (!evplp::morph_mesh_check(c, mesh, weights, ntargets, &base, &moved)) return EVPLP_ERR_INVALID;
-    return evplp::morph_mesh_apply(c, mesh, weights, ntargets, base.data(), moved.data());
-}
-
-extern "C" int evplp_mesh_count(evplp_context *c) {
-    CTX_CHECK(c);
-    return (int)c->meshes.size();
-}
-extern "C" int evplp_mesh_info(evplp_context *c, int32_t mesh, int32_t *nverts, int32_t *ntris, int32_t *material) {
-    CTX_CHECK(c);
-    if (mesh < 0 || mesh >= (int32_t)c->meshes.size()) { c->set_error("evplp_mesh_info: mesh %d out of range (%zu meshes)", mesh, c->meshes.size()); return EVPLP_ERR_INVALID; }
-    const HostMesh &m = c->meshes[(size_t)mesh];
-    if (nverts) *nverts = (int32_t)(m.verts.size() / 3);
-    if (ntris) *ntris = (int32_t)(m.idx.size() / 3);
-    if (material) *material = m.material;
-    return EVPLP_OK;
-}
-extern "C" int evplp_mesh_vertices(evplp_context *c, int32_t mesh, int32_t which, float *out_xyz, int32_t capacity_verts) {
-    CTX_CHECK(c);
-    if (mesh < 0 || mesh >= (int32_t)c->meshes.size()) { c->set_error("evplp_mesh_vertices: mesh %d out of range (%zu meshes)", mesh, c->meshes.size()); return EVPLP_ERR_INVALID; }
-    if (which < 0 || which > 2) { c->set_error("evplp_mesh_vertices: which must be 0 (current), 1 (rest pose) or 2 (morphed base), not %d", which); return EVPLP_ERR_INVALID; }
-    const HostMesh &m = c->meshes[(size_t)mesh];
-    // (a mesh without morph targets has no morphed base: for it `which` is what it was before there were targets, 0 or 1)
-    if (which == 2 && m.morph_targets <= 0) { c->set_error("evplp_mesh_vertices: which = 2 (morphed base): mesh %d has no morph targets (evplp_set_mesh_morph); which must be 0 (current) or 1 (rest pose)", mesh); return EVPLP_ERR_INVALID; }
-    const std::vector<float> &src = which == 2 ? evplp::mesh_base(m) : (which == 1 && !m.rest.empty()) ? m.rest : m.verts;
-    if (!out_xyz || capacity_verts < 0 || (size_t)capacity_verts < src.size() / 3) { c->set_error("evplp_mesh_vertices: mesh %d has %zu vertices: a null destination or too small a capacity (%d)", mesh, src.size() / 3, capacity_verts); return EVPLP_ERR_INVALID; }
-    std::memcpy(out_xyz, src.data(), sizeof(float) * src.size());
-    return EVPLP_OK;
-}
-
-// the level plan, the scratch and the staging arrays of a tree: made by its first refit
-static int refit_prepare(evplp_context *c) {
-    if (c->refit_levels > 0) return EVPLP_OK;
-    const int32_t nn = c->accel_nodes;
-    if (c->host_nodes.empty()) {            // (a host builder's tree: its child references come back once; the device builder's were kept)
-        c->host_nodes.resize((size_t)nn);
-        HIP_TRY(c, hipMemcpyAsync(c->host_nodes.data(), c->sc.nodes, sizeof(BvhNode) * (size_t)nn, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    std::vector<int32_t> height((size_t)nn), order((size_t)nn);
-    c->refit_level_begin.assign((size_t)kMaxDepth + 1, 0);
-    const int levels = evplp_refit_levels(c->host_nodes.data(), nn, height.data(), order.data(), c->refit_level_begin.data(), kMaxDepth);
-    if (levels >= 1) {                      // (what evplp_accel_quality reports beside its sums: the reached nodes and their leaf references)
-        c->refit_reached = c->refit_level_begin[(size_t)levels]; c->refit_leaf_refs = 0;
-        for (int32_t k = 0; k < c->refit_reached; k++) {
-            const BvhNode &f = c->host_nodes[(size_t)order[(size_t)k]];
-            c->refit_leaf_refs += (f.c0 < 0 && f.c0 != kNoChild) + (f.c1 < 0 && f.c1 != kNoChild);
-        }
-    }
-    std::vector<BvhNode>().swap(c->host_nodes);
-    c->refit_height.swap(height);           // (the plan's level per node: what a rotating sweep uploads, should one ever be asked for)
-    if (levels < 1) { c->set_error("evplp_refit_accel: the node array is not a tree of at most %d levels", kMaxDepth); return EVPLP_ERR_INVALID; }
-    const size_t stage = 9 * (size_t)c->scene_tris + (size_t)c->sc.light_count;
-    hipError_t e = hipMalloc((void **)&c->d_refit_order, sizeof(int32_t) * (size_t)nn);
-    if (e == hipSuccess) e = hipMalloc((void **)&c->d_refit_boxes, sizeof(float) * 6 * (size_t)nn);
-    if (e == hipSuccess) e = hipMalloc((void **)&c->d_refit_stage, sizeof(float) * stage);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_refit_stage, sizeof(float) * stage, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMemcpy(c->d_refit_order, order.data(), sizeof(int32_t) * (size_t)nn, hipMemcpyHostToDevice);
-    if (e == hipSuccess && !c->ev_refit_staged) e = hipEventCreateWithFlags(&c->ev_refit_staged, hipEventDisableTiming);
-    for (int i = 0; i < 5 && e == hipSuccess; i++) if (!c->ev_refit[i]) e = hipEventCreate(&c->ev_refit[i]);
-    if (e != hipSuccess) { c->set_error("evplp_refit_accel: plan and staging: %s", hipGetErrorString(e)); return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP; }
-    c->refit_levels = levels;
-    return EVPLP_OK;
-}
-
-// ---- tree rotations inside the sweep (evplp_optimize_accel, evplp_set_refit_rotations).  The scratch of the rotating launches, made by the
-// first call that asks for rotations: the plan's level per node goes up once -- a rotation keeps every parent above its children IN THE PLAN,
-// so the plan, its order and these levels hold for every later pass and refit of this tree, though the levels are no tight heights any more.
-static int rotate_prepare(evplp_context *c) {
-    if (c->d_rotate) return EVPLP_OK;
-    const size_t nn = (size_t)c->accel_nodes;
-    hipError_t e = hipMalloc((void **)&c->d_rotate, sizeof(int32_t) * 3 * nn);
-    if (e == hipSuccess) e = hipMalloc((void **)&c->d_rotate_out, sizeof(int32_t) * 16);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_rotate_out, sizeof(int32_t) * 16, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMemcpy(c->d_rotate, c->refit_height.data(), sizeof(int32_t) * nn, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(c->d_rotate + nn, 0, sizeof(int32_t) * 2 * nn);
-    if (e != hipSuccess) {
-        hipFree(c->d_rotate); hipFree(c->d_rotate_out); if (c->h_rotate_out) hipHostFree(c->h_rotate_out);
-        c->d_rotate = c->d_rotate_out = c->h_rotate_out = nullptr;
-        c->set_error("tree rotations: the sweep's scratch: %s", hipGetErrorString(e)); return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP;
-    }
-    return EVPLP_OK;
-}
-// `passes` sweeps, the leaves' parents first and the root last, each launch the rotating one; enqueued, none waits
-static void rotate_enqueue(evplp_context *c, const RefitScene &r, float pad, int32_t passes) {
-    const size_t nn = (size_t)c->accel_nodes;
-    for (int32_t p = 0; p < passes; p++)
-        for (int32_t l = 0; l < c->refit_levels; l++)
-            refit_rotate_level(r, c->d_refit_order + c->refit_level_begin[(size_t)l], c->refit_level_begin[(size_t)l + 1] - c->refit_level_begin[(size_t)l], pad,
-                               c->d_rotate, c->d_rotate + nn, c->d_rotate + 2 * nn, c->d_rotate_out + 2 * p, c->stream);
-}
-// after the wait: the root's { rotations, need } of every pass are in the pinned words
-static void rotate_finish(evplp_context *c, int32_t passes) {
-    c->rotations_last = 0;
-    for (int p = 0; p < 8; p++) { c->rotations_pass[p] = p < passes ? c->h_rotate_out[2 * p] : 0; c->rotations_last += c->rotations_pass[p]; }
-    c->rotations_since_build += c->rotations_last;
-    c->sc.stack4_entries = c->h_rotate_out[2 * (passes - 1) + 1] + 2;   // (kernels.h takes the smaller of this and the generic bound of the depth)
-}
-
-// A refit with posed meshes (behind the wait for the last refit's copies).  begin[mi]: where skinned mesh mi's corner skin lies in d_skin --
-// the skinned meshes one behind the other, in corners.  When the set of skinned meshes has changed (or nothing is there yet) the arrays are
-// made for it: the corner skins, the palette array for all skinned meshes' bones on the device and in pinned memory, the descriptor tables;
-// every mesh's part then goes up again at its next posed refit.  src[mi]: where the part of a posed mesh the device lacks lies in
-// c->skin_upload, expanded here from the per-vertex skin through the mesh's index array.
-static int skin_prepare(evplp_context *c, const std::vector<int32_t> &first, std::vector<int32_t> &begin, std::vector<size_t> &src) {
-    const size_t nm = c->meshes.size();
-    begin.assign(nm, 0); src.assign(nm, 0);
-    int64_t corners = 0, bones = 0;
-    for (size_t mi = 0; mi < nm; mi++) if (c->meshes[mi].skin_bones > 0) { begin[mi] = (int32_t)corners; corners += 3 * (int64_t)(first[mi + 1] - first[mi]); bones += c->meshes[mi].skin_bones; }
-    if (corners > INT32_MAX) { c->set_error("evplp_refit_accel: %lld skinned triangle corners are more than the skin launch indexes", (long long)corners); return EVPLP_ERR_INVALID; }
-    if (c->skin_stale) {
-        for (HostMesh &m : c->meshes) m.skin_at = -1;
-        if (!c->d_sdesc || corners > c->skin_cap || bones > c->bone_cap) {
-            hipFree(c->d_skin); hipFree(c->d_bones); hipFree(c->d_sdesc); if (c->h_bones) hipHostFree(c->h_bones); if (c->h_sdesc) hipHostFree(c->h_sdesc);
-            c->d_skin = nullptr; c->d_bones = c->h_bones = nullptr; c->d_sdesc = c->h_sdesc = nullptr; c->skin_cap = c->bone_cap = 0;
-            hipError_t e = hipMalloc((void **)&c->d_skin, sizeof(CornerSkin) * (size_t)std::max<int64_t>(corners, 1));
-            if (e == hipSuccess) e = hipMalloc((void **)&c->d_bones, sizeof(float) * 12 * (size_t)std::max<int64_t>(bones, 1));
-            if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_bones, sizeof(float) * 12 * (size_t)std::max<int64_t>(bones, 1), hipHostMallocDefault);
-            if (e == hipSuccess) e = hipMalloc((void **)&c->d_sdesc, sizeof(SkinDesc) * nm);
-            if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_sdesc, sizeof(SkinDesc) * nm, hipHostMallocDefault);
-            if (e != hipSuccess) { c->set_error("evplp_refit_accel: the skins on the device: %s", hipGetErrorString(e)); return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP; }
-            c->skin_cap = (int32_t)corners; c->bone_cap = (int32_t)bones;
-        }
-        c->skin_stale = false;
-    }
-    c->skin_upload.clear();
-    for (size_t mi = 0; mi < nm; mi++) if (c->mesh_dirty[mi] == 3 && c->meshes[mi].skin_at < 0) {
-        const HostMesh &m = c->meshes[mi];
-        src[mi] = c->skin_upload.size();
-        for (size_t k = 0; k < m.idx.size(); k++) {
-            const size_t v = (size_t)m.idx[k];
-            CornerSkin s;
-            for (int q = 0; q < 4; q++) { s.b[q] = (uint16_t)m.skin_index[4 * v + q]; s.w[q] = m.skin_weight[4 * v + q]; }
-            c->skin_upload.push_back(s);
-        }
-    }
-    return EVPLP_OK;
-}
-
-// A refit with meshes under morph weights (behind the wait for the last refit's copies), the twin of skin_prepare.  begin[mi]: where mesh mi's
-// corner deltas lie in d_morph -- the meshes with targets one behind the other, in float3, each target-major [T][3 count].  When the set of
-// meshes with targets has changed (or nothing is there yet) the arrays are made for it; every mesh's part then goes up again at its next
-// morphed refit.  src[mi]: where the part of a morphed mesh the device lacks lies in c->morph_upload, expanded here from the per-vertex deltas
-// through the mesh's index array.  need_base: a mesh under weights is also moved by a matrix or a pose -- the base array is made, as a copy of
-// the rest-pose array as the stream finds it here.
-static int morph_prepare(evplp_context *c, const std::vector<int32_t> &first, bool need_base, std::vector<int32_t> &begin, std::vector<size_t> &src) {
-    const size_t nm = c->meshes.size();
-    begin.assign(nm, 0); src.assign(nm, 0);
-    int64_t vectors = 0, weights = 0;
-    for (size_t mi = 0; mi < nm; mi++) if (c->meshes[mi].morph_targets > 0) {
-        begin[mi] = (int32_t)vectors; vectors += 3 * (int64_t)(first[mi + 1] - first[mi]) * c->meshes[mi].morph_targets; weights += c->meshes[mi].morph_targets;
-        if (vectors > INT32_MAX) { c->set_error("evplp_refit_accel: the corner deltas of the morph targets are more than the morph launch indexes"); return EVPLP_ERR_INVALID; }
-    }
-    if (c->morph_stale) {
-        for (HostMesh &m : c->meshes) m.morph_at = -1;
-        if (!c->d_mdesc || vectors > c->morph_cap || weights > c->weight_cap) {
-            hipFree(c->d_morph); hipFree(c->d_mweights); hipFree(c->d_mdesc); if (c->h_mweights) hipHostFree(c->h_mweights); if (c->h_mdesc) hipHostFree(c->h_mdesc);
-            c->d_morph = c->d_mweights = c->h_mweights = nullptr; c->d_mdesc = c->h_mdesc = nullptr; c->morph_cap = 0; c->weight_cap = 0;
-            hipError_t e = hipMalloc((void **)&c->d_morph, sizeof(float) * 3 * (size_t)std::max<int64_t>(vectors, 1));
-            if (e == hipSuccess) e = hipMalloc((void **)&c->d_mweights, sizeof(float) * (size_t)std::max<int64_t>(weights, 1));
-            if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_mweights, sizeof(float) * (size_t)std::max<int64_t>(weights, 1), hipHostMallocDefault);
-            if (e == hipSuccess) e = hipMalloc((void **)&c->d_mdesc, sizeof(MorphDesc) * nm);
-            if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_mdesc, sizeof(MorphDesc) * nm, hipHostMallocDefault);
-            if (e != hipSuccess) { c->set_error("evplp_refit_accel: the morph targets on the device: %s", hipGetErrorString(e)); return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP; }
-            c->morph_cap = vectors; c->weight_cap = (int32_t)weights;
-        }
-        c->morph_stale = false;
-    }
-    if (need_base && !c->d_base) {
-        const size_t bytes = sizeof(float) * 9 * (size_t)std::max(c->scene_tris, 1);
-        hipError_t e = hipMalloc((void **)&c->d_base, bytes);
-        if (e != hipSuccess) { c->d_base = nullptr; c->set_error("evplp_refit_accel: the morphed base on the device: %s", hipGetErrorString(e)); return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP; }
-        HIP_TRY(c, hipMemcpyAsync(c->d_base, c->d_rest, bytes, hipMemcpyDeviceToDevice, c->stream));
-        for (HostMesh &m : c->meshes) m.base_state = 0;
-    }
-    c->morph_upload.clear();
-    for (size_t mi = 0; mi < nm; mi++) if (c->mesh_dirty[mi] >= 2 && !c->meshes[mi].morph_w.empty() && c->meshes[mi].morph_at < 0) {
-        const HostMesh &m = c->meshes[mi];
-        const size_t nv = m.verts.size() / 3;
-        src[mi] = c->morph_upload.size();
-        for (int32_t k = 0; k < m.morph_targets; k++)
-            for (size_t q = 0; q < m.idx.size(); q++) {
-                const float *d = &m.morph_delta[3 * ((size_t)k * nv + (size_t)m.idx[q])];
-                c->morph_upload.insert(c->morph_upload.end(), d, d + 3);
-            }
-    }
-    return EVPLP_OK;
-}
-
-extern "C" int evplp_refit_accel(evplp_context *c) {
-    CTX_CHECK(c);
-    if (!evplp::refit_check(c)) return EVPLP_ERR_INVALID;
-    if (!c->scene_dirty) return EVPLP_OK;
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    // (a photon splat whose verdict is still out is not waited for: a splat reads records and the G-buffer, never the scene)
-    int rc = refit_prepare(c); if (rc) return rc;
-    const int32_t rot = c->rotate_passes;                       // (evplp_set_refit_rotations; 0, the default: the call is what it always was)
-    if (rot > 0 && (rc = rotate_prepare(c))) return rc;
-    std::vector<int32_t> first;
-    { int32_t n = 0; for (const HostMesh &m : c->meshes) { first.push_back(n); n += (int32_t)(m.idx.size() / 3); } first.push_back(n); }
-    // 5. the host's figures, by the code evplp_build_accel uses, for the meshes that moved alone (in front of the launches, so that they
-    // follow each other without a gap)
-    // (flat: the dirty meshes' triangles, flattened once -- for the figures, and for the staging copy of those that are dirty by upload)
-    std::vector<float> cdf, flat; std::vector<size_t> flat_at(c->meshes.size(), 0);
-    { size_t n = 0; for (size_t mi = 0; mi < c->meshes.size(); mi++) if (c->mesh_dirty[mi]) { flat_at[mi] = n; n += 9 * (size_t)(first[mi + 1] - first[mi]); } flat.resize(n); }
-    for (size_t mi = 0; mi < c->meshes.size(); mi++) if (c->mesh_dirty[mi]) {
-        flatten_mesh(c->meshes[mi], c->meshes[mi].verts, flat.data() + flat_at[mi]);
-        mesh_figures(c->meshes[mi], flat.data() + flat_at[mi], nullptr);
-    }
-    if (c->mesh_dirty[(size_t)c->light_mesh]) light_figures(c, flat.data() + flat_at[(size_t)c->light_mesh], cdf);
-    const float pad = scene_fold(c);
-    // Everything below is enqueued on the context's stream, behind every pass it was given -- the light tracing of overlap_light_tracing
-    // included: the call that put it on the second stream made this stream wait for it.
-    const bool timed = c->profile_passes, stages = timed && c->profile_kernels;
-    if (c->refit_count > 0) HIP_TRY(c, hipEventSynchronize(c->ev_refit_staged));     // (the last refit's copies have left the pinned arrays: long ago)
-    std::vector<int32_t> skin_begin; std::vector<size_t> skin_src;
-    if (std::find(c->mesh_dirty.begin(), c->mesh_dirty.end(), (char)3) != c->mesh_dirty.end() && (rc = skin_prepare(c, first, skin_begin, skin_src))) return rc;
-    std::vector<int32_t> morph_begin; std::vector<size_t> morph_src;
-    { bool any = false, need_base = false;
-      for (size_t mi = 0; mi < c->meshes.size(); mi++) if (c->mesh_dirty[mi] >= 2 && !c->meshes[mi].morph_w.empty()) { any = true; need_base = need_base || c->mesh_dirty[mi] != 4; }
-      if (any && (rc = morph_prepare(c, first, need_base, morph_begin, morph_src))) return rc; }
-    // 1. the triangles of the meshes dirty by upload, packed, in one copy; one scatter per run of neighbouring such meshes.  Behind them in the
-    // pinned array, the rest pose of every mesh that was given a matrix and whose rest pose the device does not hold in any form.
-    // (one memcpy per mesh into the pinned array, as ever: what the copy engine then reads was written the way it was before there were matrices)
-    size_t staged = 0;
-    for (size_t mi = 0; mi < c->meshes.size(); mi++) if (c->mesh_dirty[mi] == 1) {
-        const size_t n = 9 * (size_t)(first[mi + 1] - first[mi]);
-        std::memcpy(c->h_refit_stage + staged, flat.data() + flat_at[mi], sizeof(float) * n);
-        staged += n;
-    }
-    const size_t uploaded = staged;
-    for (size_t mi = 0; mi < c->meshes.size(); mi++) if (c->mesh_dirty[mi] >= 2 && c->meshes[mi].rest_state == 2) {
-        const size_t n = 9 * (size_t)(first[mi + 1] - first[mi]);
-        std::vector<float> rest(n);
-        flatten_mesh(c->meshes[mi], c->meshes[mi].rest, rest.data());
-        std::memcpy(c->h_refit_stage + staged, rest.data(), sizeof(float) * n);
-        staged += n;
-    }
-    if (timed) HIP_TRY(c, hipEventRecord(c->ev_refit[0], c->stream));
-    if (uploaded) HIP_TRY(c, hipMemcpyAsync(c->d_refit_stage, c->h_refit_stage, sizeof(float) * uploaded, hipMemcpyHostToDevice, c->stream));
-    staged = 0;
-    for (size_t mi = 0; mi < c->meshes.size();) {
-        if (c->mesh_dirty[mi] != 1) { mi++; continue; }
-        size_t me = mi; while (me < c->meshes.size() && c->mesh_dirty[me] == 1) me++;
-        const int32_t count = first[me] - first[mi];
-        refit_scatter(c->d_refit_stage + staged, first[mi], count, (TriAttr *)c->sc.attrs, c->stream);
-        staged += 9 * (size_t)count; mi = me;
-    }
-    // 1'. the meshes dirty by transform: their rest pose where the device lacks it (once per mesh and rest pose), the table of their matrices
-    // through pinned memory, and ONE launch that writes the attributes of all of them from the rest pose.  Nothing of them is staged or copied.
-    // 1''. the meshes dirty by pose likewise: the same rest pose, each mesh's corner skin where the device lacks it (once per mesh and skin),
-    // the palettes one behind the other and the table of their places through pinned memory, and ONE launch that writes all of them.
-    // 1*. the meshes under morph weights: each mesh's corner deltas where the device lacks them (once per mesh and set of targets), the weight
-    // sets one behind the other and the table through pinned memory, and ONE launch, in front of the two above, that writes the attributes of
-    // the meshes nothing else moves and the base of the others -- which the two launches then read in place of the rest pose: the base array
-    // is a copy of the rest-pose array but for those meshes' parts, kept in step here.  A mesh whose base the device holds is not written again.
-    int32_t nx = 0, moved = 0, ns = 0, posed = 0, nbone = 0, nmo = 0, morphed = 0, nweight = 0;
-    for (size_t mi = 0; mi < c->meshes.size(); mi++) if (c->mesh_dirty[mi] >= 2) {
-        HostMesh &m = c->meshes[mi];
-        const int32_t count = first[mi + 1] - first[mi];
-        if (m.rest_state == 1) refit_rest(c->sc.attrs, first[mi], count, c->d_rest, c->stream);
-        else if (m.rest_state == 2) {
-            if (count > 0) HIP_TRY(c, hipMemcpyAsync(c->d_rest + 9 * (size_t)first[mi], c->h_refit_stage + staged, sizeof(float) * 9 * (size_t)count, hipMemcpyHostToDevice, c->stream));
-            staged += 9 * (size_t)count;
-        }
-        if (m.rest_state != 3 && c->d_base) {
-            if (count > 0) HIP_TRY(c, hipMemcpyAsync(c->d_base + 9 * (size_t)first[mi], c->d_rest + 9 * (size_t)first[mi], sizeof(float) * 9 * (size_t)count, hipMemcpyDeviceToDevice, c->stream));
-            m.base_state = 0;
-        }
-        m.rest_state = 3;
-        if (count <= 0) continue;
-        if (!m.morph_w.empty() && (c->mesh_dirty[mi] == 4 || m.base_state != 1)) {
-            if (m.morph_at < 0) {
-                m.morph_at = morph_begin[mi];
-                HIP_TRY(c, hipMemcpyAsync(c->d_morph + 3 * (size_t)m.morph_at, c->morph_upload.data() + morph_src[mi], sizeof(float) * 9 * (size_t)count * (size_t)m.morph_targets, hipMemcpyHostToDevice, c->stream));
-            }
-            MorphDesc &d = c->h_mdesc[nmo++];
-            d.first = first[mi]; d.count = count; d.begin = morphed; d.weight_at = nweight; d.delta_at = m.morph_at; d.ntargets = m.morph_targets; d.to_base = c->mesh_dirty[mi] != 4; d.pad = 0;
-            std::memcpy(c->h_mweights + nweight, m.morph_w.data(), sizeof(float) * (size_t)m.morph_targets);
-            morphed += count; nweight += m.morph_targets;
-            if (d.to_base) m.base_state = 1;
-        } else if (m.morph_w.empty() && c->d_base && m.base_state != 0) {       // (the weights were taken away: the base is the rest pose again)
-            HIP_TRY(c, hipMemcpyAsync(c->d_base + 9 * (size_t)first[mi], c->d_rest + 9 * (size_t)first[mi], sizeof(float) * 9 * (size_t)count, hipMemcpyDeviceToDevice, c->stream));
-            m.base_state = 0;
-        }
-        if (c->mesh_dirty[mi] == 4) continue;
-        if (c->mesh_dirty[mi] == 3) {
-            if (m.skin_at < 0) {
-                m.skin_at = skin_begin[mi];
-                HIP_TRY(c, hipMemcpyAsync(c->d_skin + m.skin_at, c->skin_upload.data() + skin_src[mi], sizeof(CornerSkin) * 3 * (size_t)count, hipMemcpyHostToDevice, c->stream));
-            }
-            SkinDesc &s = c->h_sdesc[ns++];
-            s.first = first[mi]; s.count = count; s.begin = posed; s.bone_at = nbone; s.nbones = m.skin_bones; s.skin_at = m.skin_at; s.pad[0] = s.pad[1] = 0;
-            std::memcpy(c->h_bones + 12 * (size_t)nbone, m.palette.data(), sizeof(float) * 12 * (size_t)m.skin_bones);
-            posed += count; nbone += m.skin_bones;
-            continue;
-        }
-        TransformDesc &d = c->h_xform[nx++];
-        d.first = first[mi]; d.count = count; d.begin = moved; d.pad = 0; std::memcpy(d.m, m.matrix, sizeof(d.m));
-        moved += count;
-    }
-    if (nmo) {
-        HIP_TRY(c, hipMemcpyAsync(c->d_mdesc, c->h_mdesc, sizeof(MorphDesc) * (size_t)nmo, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(c->d_mweights, c->h_mweights, sizeof(float) * (size_t)nweight, hipMemcpyHostToDevice, c->stream));
-        refit_morph(c->d_mdesc, nmo, morphed, c->d_rest, c->d_mweights, c->weight_cap, c->d_morph, c->morph_cap, c->d_base, (TriAttr *)c->sc.attrs, c->scene_tris, c->stream);
-    }
-    const float *based = c->d_base ? c->d_base : c->d_rest;     // (what a matrix and a pose act on)
-    if (nx) {
-        HIP_TRY(c, hipMemcpyAsync(c->d_xform, c->h_xform, sizeof(TransformDesc) * (size_t)nx, hipMemcpyHostToDevice, c->stream));
-        refit_transform(c->d_xform, nx, moved, based, (TriAttr *)c->sc.attrs, c->scene_tris, c->stream);
-    }
-    if (ns) {
-        HIP_TRY(c, hipMemcpyAsync(c->d_sdesc, c->h_sdesc, sizeof(SkinDesc) * (size_t)ns, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(c->d_bones, c->h_bones, sizeof(float) * 12 * (size_t)nbone, hipMemcpyHostToDevice, c->stream));
-        refit_skin(c->d_sdesc, ns, posed, based, c->d_skin, c->skin_cap, c->d_bones, (TriAttr *)c->sc.attrs, c->scene_tris, c->stream);
-    }
-    if (stages) HIP_TRY(c, hipEventRecord(c->ev_refit[1], c->stream));
-    // 2. leaf operands  3. boxes, one launch per height  4. four-wide nodes
-    RefitScene r; std::memset(&r, 0, sizeof(r));
-    r.nodes = (BvhNode *)c->sc.nodes; r.nnodes = c->accel_nodes; r.leaves = (LeafBlock *)c->sc.leaves; r.tri_flat = (TriFlat *)c->sc.tri_flat; r.tri_index = c->sc.tri_index;
-    r.nslots = 4 * c->accel_leaves; r.attrs = c->sc.attrs; r.ntri = c->scene_tris; r.boxes = c->d_refit_boxes;
-    refit_leaves(r, c->stream);
-    if (stages) HIP_TRY(c, hipEventRecord(c->ev_refit[2], c->stream));
-    if (rot > 0) rotate_enqueue(c, r, pad, rot);             // (the first pass IS the refit's sweep; further passes repeat it)
-    else for (int32_t l = 0; l < c->refit_levels; l++)
-        refit_level(r, c->d_refit_order + c->refit_level_begin[(size_t)l], c->refit_level_begin[(size_t)l + 1] - c->refit_level_begin[(size_t)l], pad, c->stream);
-    if (stages) HIP_TRY(c, hipEventRecord(c->ev_refit[3], c->stream));
-    build_nodes4_into(c->sc.nodes, c->accel_nodes, c->stream, (BvhNode4 *)c->sc.nodes4);
-    if (rot > 0) HIP_TRY(c, hipMemcpyAsync(c->h_rotate_out, c->d_rotate_out, sizeof(int32_t) * 2 * (size_t)rot, hipMemcpyDeviceToHost, c->stream));
-    // 5. ... the CDF goes up only if the light moved
-    if (c->mesh_dirty[(size_t)c->light_mesh]) {
-        float *h = c->h_refit_stage + 9 * (size_t)c->scene_tris;
-        std::memcpy(h, cdf.data(), sizeof(float) * cdf.size());
-        HIP_TRY(c, hipMemcpyAsync((void *)c->sc.light_cdf, h, sizeof(float) * cdf.size(), hipMemcpyHostToDevice, c->stream));
-    }
-    HIP_TRY(c, hipEventRecord(c->ev_refit_staged, c->stream));
-    if (timed) HIP_TRY(c, hipEventRecord(c->ev_refit[4], c->stream));
-    if (c->aux_stream) HIP_TRY(c, hipStreamWaitEvent(c->aux_stream, c->ev_refit_staged, 0));      // (light paths given to the second stream from here on see the new tree)
-    HIP_TRY(c, hipGetLastError());
-    c->accel_pad = pad; c->refit_timed = timed; c->refit_stages_timed = stages; c->refit_count++; c->refits_since_build++;
-    c->primary_cuts_valid = false; c->tile_box_valid = false; c->primary_current = false;
-    std::fill(c->mesh_dirty.begin(), c->mesh_dirty.end(), 0); c->scene_dirty = false;
-    if (c->policy_ratio > 0.0) {
-        // The policy (evplp_set_refit_policy): the cost of the refitted tree against the cost of the tree as built.  One small launch and
-        // one host wait; a rebuild is evplp_build_accel's code (which measures the new built_cost, the policy being on).
-        // With rotations on, the cost is the rotated tree's, and the wait is the one that brings the rotations' counts back.
-        double q[5];
-        if ((rc = measure_cost(c, q))) return rc;
-        if (rot > 0) rotate_finish(c, rot);
-        if (q[0] > c->policy_ratio * c->built_cost) {
-            if ((rc = build_accel(c, c->policy_builder))) return rc;
-            c->policy_rebuilds++; c->last_action = 2;
-        } else c->last_action = rot > 0 ? 3 : 1;
-    } else if (rot > 0) {                   // the refit with rotations is not free of host waits: the root's counts and stack need come back
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        rotate_finish(c, rot);
-        c->last_action = 3;
-    }
-    return EVPLP_OK;
-}
-
-// ---------------------------------------------------------------------------------- the tree's SAH cost, and the refit policy
-// The cost of the tree as it is on the device into out[5], behind everything on the context's stream; waits.  The first measurement
-// since a build is kept as built_cost.
-static int measure_cost(evplp_context *c, double out[5]) {
-    int rc = refit_prepare(c); if (rc) return rc;              // (the plan is the refit's; made here if no refit has made it)
-    const int32_t nchunks = (c->refit_reached + kCostChunk - 1) / kCostChunk;
-    const size_t bytes = sizeof(double) * (1 + 3 * (size_t)nchunks);
-    if (!c->d_cost) {
-        hipError_t e = hipMalloc((void **)&c->d_cost, bytes);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_cost, bytes, hipHostMallocDefault);
-        if (e != hipSuccess) { c->set_error("evplp_accel_quality: the sums' arrays: %s", hipGetErrorString(e)); return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP; }
-    }
-    const bool timed = c->profile_passes;
-    for (int i = 0; i < 2 && timed; i++) if (!c->ev_cost[i]) HIP_TRY(c, hipEventCreate(&c->ev_cost[i]));
-    if (timed) HIP_TRY(c, hipEventRecord(c->ev_cost[0], c->stream));
-    accel_cost(c->sc.nodes, c->accel_nodes, c->d_refit_order, c->refit_reached, c->d_cost, c->stream);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->h_cost, c->d_cost, bytes, hipMemcpyDeviceToHost, c->stream));
-    if (timed) HIP_TRY(c, hipEventRecord(c->ev_cost[1], c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->cost_timed = timed;
-    accel_cost_finish(c->h_cost + 1, nchunks, c->h_cost[0], out);
-    if (!c->built_cost_known) { c->built_cost = out[0]; c->built_cost_known = true; }
-    return EVPLP_OK;
-}
-
-namespace evplp {
-bool accel_quality_check(evplp_context *c, const char *name) {
-    if (!c->accel_built) { c->set_error("%s: scene not built (evplp_build_accel)", name); return false; }
-    if (c->scene_dirty) { c->set_error("%s: vertices were updated (evplp_update_mesh): call evplp_refit_accel or evplp_build_accel first", name); return false; }
-    return true;
-}
-bool refit_policy_check(evplp_context *c, double max_cost_ratio, int32_t rebuild_builder) {
-    if (!(max_cost_ratio >= 0.0) || !std::isfinite(max_cost_ratio)) { c->set_error("evplp_set_refit_policy: max_cost_ratio must be finite and >= 0 (0: off)"); return false; }
-    if (rebuild_builder < -1 || rebuild_builder > EVPLP_BVH_LBVH_GPU) { c->set_error("evplp_set_refit_policy: rebuild_builder %d is neither an evplp_bvh_builder nor -1", rebuild_builder); return false; }
-    if (c->scene_dirty) { c->set_error("evplp_set_refit_policy: vertices were updated (evplp_update_mesh): call evplp_refit_accel or evplp_build_accel first"); return false; }
-    return true;
-}
-}
-
-extern "C" int evplp_accel_quality(evplp_context *c, struct evplp_accel_quality *out) {
-    CTX_CHECK(c);
-    if (!out) { c->set_error("evplp_accel_quality: null destination"); return EVPLP_ERR_INVALID; }
-    if (!evplp::accel_quality_check(c, "evplp_accel_quality")) return EVPLP_ERR_INVALID;
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    double q[5];
-    const int rc = measure_cost(c, q); if (rc) return rc;
-    std::memset(out, 0, sizeof(*out));
-    out->cost = q[0]; out->root_area = q[1]; out->inner_area = q[2]; out->leaf_pair_area = q[3]; out->leaf_tri_area = q[4];
-    out->built_cost = c->built_cost; out->reached_nodes = c->refit_reached; out->leaf_refs = c->refit_leaf_refs;
-    out->refits_since_build = c->refits_since_build; out->policy_rebuilds = c->policy_rebuilds; out->last_action = c->last_action;
-    return EVPLP_OK;
-}
-
-extern "C" int evplp_set_refit_policy(evplp_context *c, double max_cost_ratio, int32_t rebuild_builder) {
-    CTX_CHECK(c);
-    if (!evplp::refit_policy_check(c, max_cost_ratio, rebuild_builder)) return EVPLP_ERR_INVALID;
-    if (max_cost_ratio > 0.0 && c->accel_built && !c->built_cost_known) {
-        HIP_TRY(c, hipSetDevice(c->cfg.device));
-        double q[5];
-        const int rc = measure_cost(c, q); if (rc) return rc;
-    }
-    c->policy_ratio = max_cost_ratio; c->policy_builder = rebuild_builder;
-    return EVPLP_OK;
-}
-
-// ---------------------------------------------------------------------------------- tree rotations
-namespace evplp {
-bool optimize_accel_check(evplp_context *c, const char *name, int32_t passes) {
-    if (!accel_quality_check(c, name)) return false;
-    if (passes < 1 || passes > 8) { c->set_error("%s: passes must be 1 .. 8, not %d", name, passes); return false; }
-    return true;
-}
-bool refit_rotations_check(evplp_context *c, const char *name, int32_t passes) {
-    if (passes < 0 || passes > 8) { c->set_error("%s: passes must be 0 .. 8 (0: off), not %d", name, passes); return false; }
-    return true;
-}
-}
-
-extern "C" int evplp_optimize_accel(evplp_context *c, int32_t passes, int32_t *rotations) {
-    CTX_CHECK(c);
-    if (!evplp::optimize_accel_check(c, "evplp_optimize_accel", passes)) return EVPLP_ERR_INVALID;
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    int rc = refit_prepare(c); if (rc) return rc;
-    if ((rc = rotate_prepare(c))) return rc;
-    // behind everything on the context's stream: `passes` sweeps from the leaves' boxes upward (the triangles have not moved, so the leaf
-    // operands stay), the four-wide nodes again, and the root's counts back in one small copy; one host wait
-    RefitScene r; std::memset(&r, 0, sizeof(r));
-    r.nodes = (BvhNode *)c->sc.nodes; r.nnodes = c->accel_nodes; r.leaves = (LeafBlock *)c->sc.leaves; r.tri_flat = (TriFlat *)c->sc.tri_flat; r.tri_index = c->sc.tri_index;
-    r.nslots = 4 * c->accel_leaves; r.attrs = c->sc.attrs; r.ntri = c->scene_tris; r.boxes = c->d_refit_boxes;
-    rotate_enqueue(c, r, c->accel_pad, passes);
-    build_nodes4_into(c->sc.nodes, c->accel_nodes, c->stream, (BvhNode4 *)c->sc.nodes4);
-    HIP_TRY(c, hipMemcpyAsync(c->h_rotate_out, c->d_rotate_out, sizeof(int32_t) * 2 * (size_t)passes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    rotate_finish(c, passes);
-    c->primary_cuts_valid = false; c->tile_box_valid = false; c->primary_current = false;
-    c->last_action = 3;
-    if (rotations) *rotations = c->rotations_last;
-    return EVPLP_OK;
-}
-
-extern "C" int evplp_set_refit_rotations(evplp_context *c, int32_t passes) {
-    CTX_CHECK(c);
-    if (!evplp::refit_rotations_check(c, "evplp_set_refit_rotations", passes)) return EVPLP_ERR_INVALID;
-    c->rotate_passes = passes;
-    return EVPLP_OK;
-}
-
-extern "C" int evplp_rotation_info(evplp_context *c, int32_t *since_build, int32_t *last_call, int32_t *per_pass, int32_t *refit_passes) {
-    CTX_CHECK(c);
-    if (since_build) *since_build = c->rotations_since_build;
-    if (last_call) *last_call = c->rotations_last;
-    if (per_pass) std::memcpy(per_pass, c->rotations_pass, sizeof(c->rotations_pass));
-    if (refit_passes) *refit_passes = c->rotate_passes;
-    return EVPLP_OK;
-}
-
-extern "C" int evplp_refit_info(evplp_context *c, int32_t *refits, int32_t *levels, float *last_refit_ms) {
-    CTX_CHECK(c);
-    if (refits) *refits = c->refit_count;
-    if (levels) *levels = c->refit_levels;
-    if (last_refit_ms) {
-        *last_refit_ms = 0.f;
-        if (c->refit_count > 0 && c->refit_timed) {
-            HIP_TRY(c, hipSetDevice(c->cfg.device));
-            HIP_TRY(c, hipEventSynchronize(c->ev_refit[4]));
-            HIP_TRY(c, hipEventElapsedTime(last_refit_ms, c->ev_refit[0], c->ev_refit[4]));
-        }
-    }
-    return EVPLP_OK;
 }
 
 extern "C" int evplp_debug_accel(evplp_context *c, int32_t which, void *host_dst, size_t bytes) {

@@ -32,22 +32,45 @@ void refit_level(const RefitScene &r, const int32_t *d_order, int32_t count, flo
 void refit_rotate_level(const RefitScene &r, const int32_t *d_order, int32_t count, float pad, const int32_t *d_level, int32_t *d_taken, int32_t *d_need, int32_t *d_root_out, hipStream_t stream);
 // bvh_gpu.hip: the launch of evplp_accel_quality (enqueued; d_out: 1 + 3 * ceil(count / 256) doubles -- the root's area, then a triple per workgroup)
 void accel_cost(const BvhNode *d_nodes, int32_t nnodes, const int32_t *d_order, int32_t count, double *d_out, hipStream_t stream);
+// How a mesh's vertices changed since the device scene was made, which is how the next evplp_refit_accel takes them to the device
+// (evplp_context::mesh_dirty).  It is a record of the calls, not a function of the mesh's matrix, palette and weights: evplp_set_mesh_skin
+// on a mesh whose pose no refit has consumed makes it Upload while morph weights may still be in force.
+enum class MeshDirty : char {
+    Clean,          // not at all
+    Upload,         // evplp_update_mesh, or a mesh that nothing moves any more: its triangles go up through the staging array
+    Matrix,         // evplp_transform_mesh: the transform launch writes it from the rest pose, or from the base of morph weights in force
+    Pose,           // evplp_pose_mesh: the skin launch, likewise
+    Morph,          // evplp_morph_mesh on a mesh that nothing else moves: the morph launch writes its attributes itself
+};
+inline bool moved_on_device(MeshDirty d) { return d == MeshDirty::Matrix || d == MeshDirty::Pose || d == MeshDirty::Morph; }   // (needs its rest pose there)
+inline bool moves_base(MeshDirty d) { return d == MeshDirty::Matrix || d == MeshDirty::Pose; }      // (a matrix or a pose acts on the base)
+// a mesh's part of the device's rest-pose array (HostMesh::rest_state)
+enum class RestState {
+    Absent,         // not there
+    FromAttrs,      // the next refit makes it from the device's attributes, which still hold it
+    FromHost,       // the next refit makes it from `rest`
+    There,
+};
+// a mesh's part of the device's base array, once there is one (HostMesh::base_state)
+enum class BaseState {
+    Rest,           // the rest pose
+    Weights,        // `base` under the weights in force
+    StaleWeights,   // the base of weights that are no longer in force
+};
 // rest: the rest pose of a mesh that evplp_transform_mesh has moved (verts = transform_point(matrix, rest)); empty: verts is the rest pose.
-// rest_state, the mesh's part of the device's rest-pose array: 0 not there, 1 to be made from the device's attributes, 2 to be made from
-// `rest`, 3 there.  skin_bones > 0: the mesh has a skin (evplp_set_mesh_skin) -- four bone indices and four weights per vertex; palette: the
+// skin_bones > 0: the mesh has a skin (evplp_set_mesh_skin) -- four bone indices and four weights per vertex; palette: the
 // bone matrices of the last evplp_pose_mesh (verts = skin_point(rest) under them) until a matrix or new vertices replace the pose;
 // skin_at: where the mesh's corner skin lies in the device's array (in corners), -1 not there.  area, lo / hi (all vertices), alo / ahi / any_area (triangles with an area): the mesh's share of the scene's figures.
 struct HostMesh {
     std::vector<float> verts, uvs; std::vector<int32_t> idx; int32_t material = 0;
-    std::vector<float> rest; float matrix[12] = {}; int rest_state = 0;
+    std::vector<float> rest; float matrix[12] = {}; RestState rest_state = RestState::Absent;
     float area = 0.f, lo[3] = {}, hi[3] = {}, alo[3] = {}, ahi[3] = {}; bool any_area = false;
     int32_t skin_bones = 0, skin_at = -1; std::vector<int32_t> skin_index; std::vector<float> skin_weight, palette;
     // has_matrix: a matrix of evplp_transform_mesh is in force (palette not empty: a pose is).  morph_targets > 0: the mesh has morph targets
     // (evplp_set_mesh_morph), morph_delta [targets][vertices][3]; morph_w: the weights in force (evplp_morph_mesh), empty: none; base: the
     // morphed rest pose while weights are in force (verts = base under the matrix or the pose in force), empty otherwise.  morph_at: where
-    // the mesh's corner deltas lie in the device's array (in float3), -1 not there.  base_state, the mesh's part of the device's base array
-    // (once there is one): 0 the rest pose, 1 `base` under the weights in force, 2 the base of weights that are no longer in force.
-    bool has_matrix = false; int32_t morph_targets = 0, morph_at = -1; int base_state = 0;
+    // the mesh's corner deltas lie in the device's array (in float3), -1 not there.
+    bool has_matrix = false; int32_t morph_targets = 0, morph_at = -1; BaseState base_state = BaseState::Rest;
     std::vector<float> morph_delta, morph_w, base;
 };
 // what a matrix or a pose acts on: the morphed base while weights are in force, else the rest pose
@@ -65,8 +88,24 @@ void sum_row_errors(const std::vector<RowError> &rows, const std::vector<char> &
 }
 
 struct evplp_context;
+// every entry point of the C ABI that takes a context: a call from another thread than the group's worker waits for the worker first
+#define CTX_CHECK(ctx) do { if (!(ctx)) return EVPLP_ERR_INVALID; if ((ctx)->quiesce && std::this_thread::get_id() != (ctx)->worker_tid) (ctx)->quiesce((ctx)->quiesce_arg); } while (0)
+#define HIP_TRY(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { (ctx)->set_error("%s failed: %s", #expr, hipGetErrorString(e_)); return EVPLP_ERR_HIP; } } while (0)
 namespace evplp {
-// what evplp_update_mesh / evplp_refit_accel refuse (context.cpp), for the group's caller thread as well: false and the reason in c's error
+// what context.cpp and scene_motion.cpp share.  context.cpp: a mesh's triangles flattened, the figures of a mesh, of the light and of the
+// scene (a refit's are a fresh build's), and evplp_build_accel with the rebuild of a refit policy (policy_builder >= 0: that builder).
+// (hidden: between the library's own units, no names of its dynamic symbol table)
+#pragma GCC visibility push(hidden)
+void flatten_mesh(const HostMesh &m, const std::vector<float> &from, float *o);
+void mesh_figures(HostMesh &m, const float *flat, char *has_area);
+void light_figures(evplp_context *c, const float *flat, std::vector<float> &cdf);
+float scene_fold(evplp_context *c);
+int build_accel(evplp_context *c, int policy_builder);
+// scene_motion.cpp: the tree's SAH cost into out[5] (waits), and the release of everything that unit makes for a device scene
+int measure_cost(evplp_context *c, double out[5]);
+void release_scene_motion(evplp_context *c);
+#pragma GCC visibility pop
+// what evplp_update_mesh / evplp_refit_accel refuse (scene_motion.cpp), for the group's caller thread as well: false and the reason in c's error
 bool update_mesh_check(evplp_context *c, int32_t mesh, const float *vertices, int32_t nverts);
 bool transform_mesh_check(evplp_context *c, int32_t mesh, const float *m);
 bool set_mesh_skin_check(evplp_context *c, int32_t mesh, int32_t nbones, const int32_t *bone_index, const float *weight, int32_t nverts);
@@ -164,24 +203,24 @@ struct evplp_context {
     float light_box_lo[3] = {}, light_box_hi[3] = {};     // the light's triangles, unpadded (sc.light_lo / light_hi: padded by the scene's size)
     int32_t accel_nodes = 0, accel_leaves = 0, accel_depth = 0, accel_builder_used = -1; float accel_build_ms = 0.f;
 
-    // evplp_update_mesh / evplp_refit_accel.  mesh_dirty[m]: mesh m's vertices changed since the device scene was made (scene_dirty: any of
-    // them; every pass then refuses).  tri_dropped[t]: original triangle t had no area at the build and so has no leaf slot.  The rest is
+    // Moving vertices (scene_motion.cpp).  mesh_dirty[m]: how mesh m's vertices changed since the device scene was made (scene_dirty: any of
+    // them did; every pass then refuses).  tri_dropped[t]: original triangle t had no area at the build and so has no leaf slot.  The rest is
     // made by the first refit and freed with the scene: the level plan (evplp_refit_levels over host_nodes, the node array of the build),
     // its order on the device, 6 floats per node of scratch, a device and a pinned host staging array for the moved vertices and the light's
     // CDF ([9 * triangles + light triangles] floats; ev_refit_staged: the last refit's copies have left the pinned one).
-    // mesh_dirty: 1 by evplp_update_mesh, 2 by evplp_transform_mesh.  The first transform makes d_rest (the rest pose, 9 floats per triangle of
+    // The first transform makes d_rest (the rest pose, 9 floats per triangle of
     // the scene; a mesh's part is filled at its first transform) and the descriptor table of a refit's one transform launch, pinned and on
     // the device ([meshes] TransformDesc each; ev_refit_staged guards the pinned one); both are freed with the scene.
-    std::vector<char> mesh_dirty, tri_dropped; bool scene_dirty = false;
+    std::vector<evplp::MeshDirty> mesh_dirty; std::vector<char> tri_dropped; bool scene_dirty = false;
     float *d_rest = nullptr; evplp::TransformDesc *d_xform = nullptr, *h_xform = nullptr;
-    // mesh_dirty: 3 by evplp_pose_mesh.  The first refit with a posed mesh (and the first after the set of skinned meshes changed: skin_stale)
+    // The first refit with a posed mesh (and the first after the set of skinned meshes changed: skin_stale)
     // lays the skinned meshes' corner skins out one behind the other in d_skin (skin_cap corners, 24 B each; a mesh's part goes up at its first
     // posed refit, from skin_upload, which the stream may read until ev_refit_staged) and sizes, for the bones of all skinned meshes together
     // (bone_cap matrices), the refit's palette array on the device and in pinned host memory, and the descriptor table of the one skin launch
     // likewise ([meshes] SkinDesc each).  All freed with the scene; a context that never poses allocates none of it.
     evplp::CornerSkin *d_skin = nullptr; int32_t skin_cap = 0, bone_cap = 0; bool skin_stale = true; std::vector<evplp::CornerSkin> skin_upload;
     float *d_bones = nullptr, *h_bones = nullptr; evplp::SkinDesc *d_sdesc = nullptr, *h_sdesc = nullptr;
-    // mesh_dirty: 4 by evplp_morph_mesh on a mesh that nothing else moves (2 and 3 stand for a mesh under weights as well).  The first refit
+    // (MeshDirty::Matrix and Pose stand for a mesh under morph weights as well.)  The first refit
     // with a mesh under weights (and the first after the set of meshes with targets changed: morph_stale) lays those meshes' corner deltas out one
     // behind the other in d_morph (morph_cap float3; a mesh's part goes up at its first morphed refit, from morph_upload, which the stream may
     // read until ev_refit_staged) and sizes the refit's weight array (weight_cap floats) and the descriptor table of the one morph launch

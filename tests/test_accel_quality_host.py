@@ -78,7 +78,7 @@ def test_the_struct_and_the_weights_match_the_sources(evplp, tmp_path):
     assert got == [C.sizeof(Q), Q.built_cost.offset, Q.reached_nodes.offset, Q.policy_rebuilds.offset, Q.last_action.offset]
     types = open(os.path.join(ROOT, "evplp_amd", "csrc", "evplp_types.h")).read()
     assert len(re.findall(r"kCostNodeVisit = 15\.0, kCostPairTest = 40\.0;", types)) == 1
-    for f in ("kernels.h", "bvh_gpu.hip", "context.cpp", os.path.join("host", "accel_cost.cpp")):
+    for f in ("kernels.h", "bvh_gpu.hip", "context.cpp", "scene_motion.cpp", os.path.join("host", "accel_cost.cpp")):
         text = open(os.path.join(ROOT, "evplp_amd", "csrc", f)).read()
         assert not re.search(r"kCost(NodeVisit|PairTest)\s*=", text), f
     assert (evplp.COST_NODE_VISIT, evplp.COST_PAIR_TEST) == (15.0, 40.0)

@@ -45,7 +45,7 @@ def test_the_function_is_stated_once_and_is_what_every_side_calls():
     fn = fn[:fn.index("\n}\n")]
     assert "__host__ __device__ inline void morph_point(const float *p, const float *delta, size_t stride, const float *w, int32_t T, float *out)" in types
     assert "#pragma clang fp contract(off)" in fn and "fma" not in fn and " if " not in fn and "?" not in fn, "uncontracted, unfused, no shortcut for any weight"
-    for f, n in (("bvh_gpu.hip", 1), (os.path.join("host", "morph.cpp"), 1), ("context.cpp", 0), ("group.cpp", 0)):     # context.cpp moves its copy through morph.cpp's loops
+    for f, n in (("bvh_gpu.hip", 1), (os.path.join("host", "morph.cpp"), 1), ("context.cpp", 0), ("scene_motion.cpp", 0), ("group.cpp", 0)):     # scene_motion.cpp moves its copy through morph.cpp's loops
         assert open(os.path.join(csrc, f)).read().count("morph_point(") == n, f
     host = open(os.path.join(csrc, "host", "morph.cpp")).read()
     assert "hip/" not in host and "hipMalloc" not in host, "host/morph.cpp names no HIP header and no HIP call"
@@ -262,6 +262,7 @@ def test_the_kernel_uses_no_scratch_and_is_launched_once_per_refit():
     assert body.count("morph_point(") == 1 and "#pragma clang fp contract(off)" in body and not re.search(r"fmaf?\(|__fm", body)
     assert len(re.findall(r"attrs\[", body)) == 1 and "rest[" not in body and "tri >= ntri" in body and "d.count" in body
     assert src.count("hipLaunchKernelGGL(refit_morph_kernel") == 1
-    refit = function_text(open(os.path.join(ROOT, "evplp_amd", "csrc", "context.cpp")).read(), 'extern "C" int evplp_refit_accel(')
-    assert refit.count("refit_morph(") == 1 and re.search(r"\n    if \(nmo\) \{\n[^\n]*\n[^\n]*\n        refit_morph\(", refit), "the launch sits at the function's own level, behind the loop over the meshes"
+    ctx, motion = (open(os.path.join(ROOT, "evplp_amd", "csrc", f)).read() for f in ("context.cpp", "scene_motion.cpp"))
+    refit = function_text(motion, "static int refit_deform(")          # evplp_refit_accel's stage of the three deformer launches
+    assert (motion + ctx).count("refit_morph(") == 1 and refit.count("refit_morph(") == 1 and re.search(r"\n    if \(nmo\) \{\n[^\n]*\n[^\n]*\n        refit_morph\(", refit), "the launch sits at the function's own level, behind the loop over the meshes"
     assert refit.index("refit_morph(") < refit.index("refit_transform(") < refit.index("refit_skin("), "morphed first, then moved"

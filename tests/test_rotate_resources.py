@@ -53,7 +53,6 @@ def test_it_neither_fences_nor_uses_atomics_and_calls_the_shared_functions():
         assert "atomic" not in body and "__threadfence" not in body and not re.search(r"\bfmaf?\(|__fm", body), f
     # the plain refit is untouched: its kernel is launched from one place, the rotating one from another, and only when asked
     assert src.count("hipLaunchKernelGGL(refit_level_kernel") == 1 and src.count("hipLaunchKernelGGL(" + KERNEL) == 1
-    ctx = open(os.path.join(CSRC, "context.cpp")).read()
-    refit = function_text(ctx, 'extern "C" int evplp_refit_accel(')
+    refit = function_text(open(os.path.join(CSRC, "scene_motion.cpp")).read(), "static int refit_tree(")       # evplp_refit_accel's tree stage
     assert re.search(r"if \(rot > 0\) rotate_enqueue\(", refit) and re.search(r"else for \(int32_t l = 0; l < c->refit_levels; l\+\+\)\n\s+refit_level\(", refit)
     assert "rotate_passes = 0" in open(os.path.join(CSRC, "context.hpp")).read()

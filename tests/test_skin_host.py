@@ -50,7 +50,7 @@ def test_the_function_is_stated_once_and_is_what_every_side_calls():
     fn = fn[:fn.index("\n}\n")]
     assert "__host__ __device__ inline void skin_point(" in types and "#pragma clang fp contract(off)" in fn and "fma" not in fn
     assert fn.count("transform_point(") == 1, "the four influences go through the existing function"
-    for f, n in (("bvh_gpu.hip", 1), (os.path.join("host", "skin.cpp"), 1), ("context.cpp", 0)):      # context.cpp moves its copy through skin.cpp's loop
+    for f, n in (("bvh_gpu.hip", 1), (os.path.join("host", "skin.cpp"), 1), ("context.cpp", 0), ("scene_motion.cpp", 0)):      # scene_motion.cpp moves its copy through skin.cpp's loop
         assert open(os.path.join(csrc, f)).read().count("skin_point(") == n, f
     host = open(os.path.join(csrc, "host", "skin.cpp")).read()
     assert "hip/" not in host and "hipMalloc" not in host, "host/skin.cpp names no HIP header and no HIP call"
@@ -276,5 +276,6 @@ def test_the_kernel_uses_no_scratch_and_is_launched_once_per_refit():
     assert body.count("skin_point(") == 1 and "#pragma clang fp contract(off)" in body and not re.search(r"fmaf?\(|__fm", body)
     assert len(re.findall(r"attrs\[", body)) == 1 and "rest[" not in body and "tri >= ntri" in body
     assert src.count("hipLaunchKernelGGL(refit_skin_kernel") == 1
-    refit = function_text(open(os.path.join(ROOT, "evplp_amd", "csrc", "context.cpp")).read(), 'extern "C" int evplp_refit_accel(')
-    assert refit.count("refit_skin(") == 1 and re.search(r"\n    if \(ns\) \{\n[^\n]*\n[^\n]*\n        refit_skin\(", refit), "the launch sits at the function's own level, behind the loop over the meshes"
+    ctx, motion = (open(os.path.join(ROOT, "evplp_amd", "csrc", f)).read() for f in ("context.cpp", "scene_motion.cpp"))
+    refit = function_text(motion, "static int refit_deform(")          # evplp_refit_accel's stage of the three deformer launches
+    assert (motion + ctx).count("refit_skin(") == 1 and refit.count("refit_skin(") == 1 and re.search(r"\n    if \(ns\) \{\n[^\n]*\n[^\n]*\n        refit_skin\(", refit), "the launch sits at the function's own level, behind the loop over the meshes"

@@ -43,9 +43,9 @@ def test_it_neither_fences_nor_uses_atomics_and_transform_point_is_its_only_arit
     assert len(re.findall(r"attrs\[", body)) == 1 and "rest[" not in body
     # one launch per refit: the host launches it from one place, outside the loop over the meshes
     assert src.count("hipLaunchKernelGGL(refit_transform_kernel") == 1
-    ctx = open(os.path.join(CSRC, "context.cpp")).read()
-    refit = function_text(ctx, 'extern "C" int evplp_refit_accel(')
-    assert refit.count("refit_transform(") == 1
+    ctx, motion = open(os.path.join(CSRC, "context.cpp")).read(), open(os.path.join(CSRC, "scene_motion.cpp")).read()
+    refit = function_text(motion, "static int refit_deform(")          # evplp_refit_accel's stage of the three deformer launches
+    assert (motion + ctx).count("refit_transform(") == 1 and refit.count("refit_transform(") == 1
     assert re.search(r"\n    if \(nx\) \{\n[^\n]*\n        refit_transform\(", refit), "the launch sits at the function's own level, behind the loop over the meshes"
     # the function itself: stated once, uncontracted, without a fused operation
     types = open(os.path.join(CSRC, "evplp_types.h")).read()
@@ -54,4 +54,4 @@ def test_it_neither_fences_nor_uses_atomics_and_transform_point_is_its_only_arit
     fn = fn[:fn.index("\n}\n")]
     assert "#pragma clang fp contract(off)" in fn and "fma" not in fn
     # ... and the host moves its copy through it, nowhere else is a matrix applied
-    assert ctx.count("transform_point(") == 3          # evplp_transform_points, evplp_transform_mesh, its finiteness check
+    assert motion.count("transform_point(") == 3 and ctx.count("transform_point(") == 0       # evplp_transform_points, evplp_transform_mesh, its finiteness check
