@@ -1,6 +1,7 @@
 // C-ABI implementation (include/evplp.h): context, scene upload, pass launchers, statistics.
 // There is deliberately no CPU execution path here: every pass is a HIP kernel launch.
 #include "context.hpp"
+#include "host/gather_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -15,6 +16,7 @@ using namespace evplp;
 static thread_local char g_create_error[512] = "";
 // default bounds of the gathers' two large scratch buffers (evplp_config.cut_scratch_bytes / vsl_mask_bytes = 0; include/evplp.h has the table)
 constexpr size_t kDefaultCutScratchBytes = (size_t)8 << 30, kDefaultVslMaskBytes = (size_t)2 << 30;
+static_assert(kPlanVplSplit == kVplSplit && kPlanDefaultSplitsPerWave == kDefaultSplitsPerWave && kPlanCutSlotBytes == kCutSlotBytes, "host/gather_plan.hpp restates these constants of kernels.h");
 
 void evplp_context::set_error(const char *fmt, ...) {
     va_list ap; va_start(ap, fmt);
@@ -26,6 +28,29 @@ static size_t buffer_bytes(const evplp_context *c, int which) {
     const size_t px = (size_t)c->st.W * c->st.local_rows;
     if (which == EVPLP_BUF_RECORDS) return sizeof(evplp_record) * (size_t)c->cfg.num_light_paths * c->cfg.photons_per_path;
     return px * sizeof(float4);
+}
+
+// A pass's scratch that only grows: nothing to do while it holds `need` bytes; else wait for the context's streams (its kernels may still read
+// the old allocation), free it and allocate `need`.  On failure the scratch is left empty, the sticky HIP error is cleared, and the caller
+// says what that means: a fallback for the gather's cuts, an error in its own words for the rest.
+static hipError_t grow_scratch(evplp_context *c, DeviceScratch &s, size_t need) {
+    if (s.bytes >= need) return hipSuccess;
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess && c->aux_stream) e = hipStreamSynchronize(c->aux_stream);
+    if (e != hipSuccess) return e;
+    hipFree(s.p); s.p = nullptr; s.bytes = 0;
+    if ((e = hipMalloc(&s.p, need)) != hipSuccess) { (void)hipGetLastError(); s.p = nullptr; return e; }
+    s.bytes = need;
+    return hipSuccess;
+}
+// a buffer made by the first call of entry point `name` that needs it and kept (evplp_denoise's and evplp_denoise_temporal's planes)
+static int alloc_once(evplp_context *c, const char *name, void **p, size_t bytes) {
+    if (*p) return EVPLP_OK;
+    const hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16));
+    if (e == hipSuccess) return EVPLP_OK;
+    (void)hipGetLastError(); *p = nullptr;
+    c->set_error("%s: cannot allocate %zu bytes: %s", name, bytes, hipGetErrorString(e));
+    return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP;
 }
 
 static int settle_splat(evplp_context *c);
@@ -86,7 +111,16 @@ extern "C" int evplp_create(const evplp_config *cfg, evplp_context **out) {
     c->env_ploc_radius = ploc_radius; c->env_ploc_iterations = ploc_iterations;
     if (const char *env = std::getenv("EVPLP_CUTS")) c->env_cuts = atoi(env) != 0 ? 1 : 0;
     if (const char *env = std::getenv("EVPLP_ITEM_DEAL")) c->env_item_deal = atoi(env) != 0 ? 1 : 0;
-    if (const char *env = std::getenv("EVPLP_CUT_BYTES")) c->env_cut_bytes = (size_t)strtoull(env, nullptr, 10);      // (tests: forces the band path)
+    // The bounds of the gathers' cut scratch and VSL mask buffer: the test override, else evplp_config, else 8 GB / 2 GB (round 6; until round 5
+    // a quarter and a twentieth of the device's memory -- 72 GB of 288, which let config #5's 68 GB of slots sit in one band, 0.7 % faster than
+    // the eight it takes now, 1 167 against 1 174 ms, and its 8.6 GB of masks in one launch -- and took a quarter of the GPU from whoever else
+    // lives on it: a library embedded in a host application asks for that much only when told to).  Configurations within the bound -- config
+    // #2 / #3: 4.3 GB of cuts -- allocate what they need; larger ones are gathered band by band, group range by group range (host/gather_plan.cpp).
+    size_t env_cut_bytes = 0, env_mask_bytes = 0;
+    if (const char *env = std::getenv("EVPLP_CUT_BYTES")) env_cut_bytes = (size_t)strtoull(env, nullptr, 10);      // (tests: forces the band path)
+    if (const char *env = std::getenv("EVPLP_MASK_BYTES")) env_mask_bytes = (size_t)strtoull(env, nullptr, 10);    // (tests: forces the group-range path)
+    c->cut_cap = env_cut_bytes ? env_cut_bytes : cfg->cut_scratch_bytes ? (size_t)cfg->cut_scratch_bytes : kDefaultCutScratchBytes;
+    c->mask_cap = env_mask_bytes ? env_mask_bytes : cfg->vsl_mask_bytes ? (size_t)cfg->vsl_mask_bytes : kDefaultVslMaskBytes;
     if (const char *env = std::getenv("EVPLP_GATHER_K")) { int v = atoi(env); if (v >= 1 && v <= 32 && (v & (v - 1)) == 0) c->env_gather_k = v; }
     if (const char *env = std::getenv("EVPLP_TILE_BLOCK_LOG2")) c->env_tile_block_log2 = std::max(0, atoi(env));
     if (const char *env = std::getenv("EVPLP_SPLIT_MIN")) c->env_split_min = std::max(0, atoi(env));
@@ -126,7 +160,7 @@ extern "C" int evplp_create(const evplp_config *cfg, evplp_context **out) {
         if ((e = hipMemset(c->buf[b], 0, bytes)) != hipSuccess) return fail("hipMemset", e);
         c->buf_owned[b] = true;
     }
-    const uint32_t nvpl_slots = std::max<uint32_t>(cfg->num_vpl_light_paths * cfg->photons_per_path, 1u);
+    const size_t nvpl_slots = nvpl_slot_count(cfg->num_vpl_light_paths, cfg->photons_per_path);
     if ((e = hipMalloc((void **)&c->d_vpls, sizeof(evplp_record) * nvpl_slots)) != hipSuccess) return fail("hipMalloc(vpls)", e);
     if ((e = hipMalloc((void **)&c->d_vpl_src, sizeof(uint32_t) * nvpl_slots)) != hipSuccess) return fail("hipMalloc(vpl_src)", e);
     if ((e = hipMalloc((void **)&c->d_scalars, 64 * sizeof(uint32_t))) != hipSuccess) return fail("hipMalloc(scalars)", e);
@@ -210,7 +244,8 @@ extern "C" void evplp_destroy(evplp_context *c) {
     if (c->own_stream) hipStreamSynchronize(c->own_stream);
     for (int b = 0; b < EVPLP_BUF_COUNT; b++) if (c->buf_owned[b]) hipFree(c->buf[b]);
     free_scene_device(c);
-    hipFree(c->d_vpls); hipFree(c->d_vpl_src); hipFree(c->d_scalars); hipFree(c->d_counters); hipFree(c->d_rgb); hipFree(c->d_partial); hipFree(c->d_vsl_masks); hipFree(c->d_cuts); hipFree(c->d_primary_cuts); hipFree(c->d_lt_overflow);
+    hipFree(c->d_vpls); hipFree(c->d_vpl_src); hipFree(c->d_scalars); hipFree(c->d_counters); hipFree(c->d_rgb); hipFree(c->d_primary_cuts);
+    for (DeviceScratch *s : { &c->partial, &c->lt_overflow, &c->cuts, &c->vsl_masks, &c->pt_batch, &c->pt_table }) hipFree(s->p);
     hipFree(c->d_tile_cursor); hipFree(c->d_bin_items); hipFree(c->d_bin_items_tmp); hipFree(c->d_seg); hipFree(c->d_seg_off); hipFree(c->d_big_list); hipFree(c->d_big_count);
     hipFree(c->d_compact); hipFree(c->d_tile_box); hipFree(c->d_tile_pairs); hipFree(c->d_summary); hipFree(c->d_heavy_list); hipFree(c->d_tile_flags);
     hipFree(c->d_proxy_slabs); hipFree(c->d_proxy_hm); hipFree(c->d_tile_frags); hipFree(c->d_blocks); hipFree(c->d_block_cost);
@@ -219,7 +254,7 @@ extern "C" void evplp_destroy(evplp_context *c) {
     hipFree(c->d_adapt_tiles); hipFree(c->d_adapt_snap); hipFree(c->d_adapt_mask);
     hipFree(c->d_dn_var); hipFree(c->d_dn_pack); hipFree(c->d_dn_u);
     hipFree(c->d_tp_prev_v); hipFree(c->d_tp_prev); hipFree(c->d_tp_prev_frame); hipFree(c->d_tp_hist); hipFree(c->d_tp_counts);
-    hipFree(c->d_pt_batch); hipFree(c->d_pt_first); hipFree(c->d_pt_table); hipFree(c->d_tile_noise);
+    hipFree(c->d_pt_first); hipFree(c->d_tile_noise);
     for (int i = 0; i < EVPLP_PASS_COUNT; i++) {
         if (c->ev_begin[i]) hipEventDestroy(c->ev_begin[i]);
         if (c->ev_end[i]) hipEventDestroy(c->ev_end[i]);
@@ -698,7 +733,7 @@ static bool jitter_within_cuts(const evplp_context *c, const float jitter[2]) {
 static void primary_cuts_into(evplp_context *c, PrimaryArgs &a) {
     PrimaryCutArgs pc; std::memset(&pc, 0, sizeof(pc));
     pc.nodes = c->sc.nodes; pc.st = c->st; pc.cam = c->cam; pc.tiles_x = c->tiles_x; pc.tiles_y = c->tiles_y;
-    pc.gw_log2 = 1; pc.gh_log2 = (c->st.strip_count == 1 || c->st.strip_rows >= 16) ? 1 : 0;
+    pc.gw_log2 = 1; pc.gh_log2 = tile_rows_are_neighbours(c->st.strip_count, c->st.strip_rows) ? 1 : 0;
     pc.groups_x = (c->tiles_x + (1 << pc.gw_log2) - 1) >> pc.gw_log2; pc.groups_y = (c->tiles_y + (1 << pc.gh_log2) - 1) >> pc.gh_log2;
     if (!c->d_primary_cuts) {
         hipError_t me = hipMalloc((void **)&c->d_primary_cuts, (size_t)pc.groups_x * pc.groups_y * (size_t)kCutSlotBytes);
@@ -770,14 +805,9 @@ extern "C" int evplp_trace_light_paths(evplp_context *c, uint32_t rng_seed, uint
     a.records = (evplp_record *)c->buf[EVPLP_BUF_RECORDS];
     {   // overflow columns of the walk stack (kernels.h): sized for the largest launch so far
         const size_t threads = ((size_t)path_count + 63) / 64 * 64, need = threads * (size_t)lt_overflow_entries(c->sc) * sizeof(int32_t);
-        if (need > c->lt_overflow_bytes) {
-            HIP_TRY(c, hipStreamSynchronize(c->stream)); if (c->aux_stream) HIP_TRY(c, hipStreamSynchronize(c->aux_stream));
-            hipFree(c->d_lt_overflow); c->d_lt_overflow = nullptr; c->lt_overflow_bytes = 0;
-            hipError_t me = hipMalloc((void **)&c->d_lt_overflow, need);
-            if (me != hipSuccess) { c->set_error("evplp_trace_light_paths: stack overflow area: %s", hipGetErrorString(me)); return EVPLP_ERR_OOM; }
-            c->lt_overflow_bytes = need;
-        }
-        a.stack_overflow = c->d_lt_overflow; a.overflow_stride = (uint32_t)threads;
+        const hipError_t me = grow_scratch(c, c->lt_overflow, need);
+        if (me != hipSuccess) { c->set_error("evplp_trace_light_paths: stack overflow area: %s", hipGetErrorString(me)); return EVPLP_ERR_OOM; }
+        a.stack_overflow = (int32_t *)c->lt_overflow.p; a.overflow_stride = (uint32_t)threads;
     }
     if (!c->aux_stream) {
         if ((rc = pass_begin(c, EVPLP_PASS_LIGHT_TRACE))) return rc;
@@ -810,8 +840,8 @@ extern "C" int evplp_trace_light_paths(evplp_context *c, uint32_t rng_seed, uint
     return EVPLP_OK;
 }
 
-static bool small_gather_launch(const evplp_context *c) { return (size_t)c->tiles_x * (size_t)((c->rows_in_image + 7) / 8) <= 8192; }
-static int fill_gather_args(evplp_context *c, const evplp_frame_params *fp, GatherArgs &a, int pass) {
+// the pointers and parameters of a gather launch; how the frame is cut into launches is the plan's (run_gather)
+static void fill_gather_args(evplp_context *c, const evplp_frame_params *fp, GatherArgs &a, int pass) {
     std::memset(&a, 0, sizeof(a));
     a.sc = c->sc; a.st = c->st; a.fp = *fp; a.pdf_mc2 = fp->pdf_mc * fp->pdf_mc;
     a.g_pos = (const float4 *)c->buf[EVPLP_BUF_GBUF_POSITION]; a.g_nrm = (const float4 *)c->buf[EVPLP_BUF_GBUF_NORMAL];
@@ -822,30 +852,6 @@ static int fill_gather_args(evplp_context *c, const evplp_frame_params *fp, Gath
     a.counters = &c->d_counters[pass];
     a.splits_per_wave = 1;
     a.block_cost = c->calibrate ? c->d_block_cost : nullptr;
-    // (small_gather_launch: at most 8 192 OWNED tiles -- half a 1024 x 1024 image, a rank of a two-way partition; the capacity rows a dealt
-    // partition keeps in reserve hold nothing and leave at once)
-    // tiles to XCDs while an XCD's share is >= 1024 tiles (its sum of tile costs then averages out: 1.9 % spread at 1024 x 1024), items over all
-    // XCDs below that (a strip of an n-way partition, small images); EVPLP_ITEM_DEAL=0 / 1 forces either (developer A/B)
-    a.item_deal = c->env_item_deal >= 0 ? c->env_item_deal : (small_gather_launch(c) ? 1 : 0);
-    // tile blocks: as many tile rows as a row strip keeps adjacent, at most 8
-    int sh = 8;
-    if (c->st.strip_count > 1) { sh = 1; while (sh * 2 <= std::min(8, c->st.strip_rows / 8) && (c->st.strip_rows / 8) % (sh * 2) == 0) sh *= 2; }
-    a.block_h_log2 = sh == 8 ? 3 : sh == 4 ? 2 : sh == 2 ? 1 : 0;
-    if (c->env_tile_block_log2 >= 0) a.block_h_log2 = std::min(c->env_tile_block_log2, a.block_h_log2);   // developer knob: 0 = rows of 8 tiles
-    return EVPLP_OK;
-}
-// gather workspace (lazy: path-tracing / photon-only contexts never pay for it): per-item partial sums for `groups` groups
-static int ensure_gather_workspace(evplp_context *c, GatherArgs &a, size_t groups) {
-    const size_t px = (size_t)c->st.W * c->st.local_rows;
-    if (c->partial_groups < groups) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        hipFree(c->d_partial); c->d_partial = nullptr; c->partial_groups = 0;
-        hipError_t e = hipMalloc((void **)&c->d_partial, sizeof(float4) * groups * px);
-        if (e != hipSuccess) { c->set_error("gather: cannot allocate %zu bytes of partial sums: %s", sizeof(float4) * groups * px, hipGetErrorString(e)); return EVPLP_ERR_OOM; }
-        c->partial_groups = groups;
-    }
-    a.partial = c->d_partial;
-    return EVPLP_OK;
 }
 static int check_fp(evplp_context *c, const evplp_frame_params *fp, const char *name) {
     if (!fp) { c->set_error("%s: null frame params", name); return EVPLP_ERR_INVALID; }
@@ -855,7 +861,6 @@ static int check_fp(evplp_context *c, const evplp_frame_params *fp, const char *
     if (fp->mis_mode > 5u) { c->set_error("%s: mis_mode %u out of range", name, fp->mis_mode); return EVPLP_ERR_INVALID; }
     return EVPLP_OK;
 }
-static size_t nvpl_slots_of(const evplp_context *c) { return std::max<size_t>((size_t)c->cfg.num_vpl_light_paths * c->cfg.photons_per_path, 1); }
 static int run_gather(evplp_context *c, const evplp_frame_params *fp, bool vsl) {
     const int pass = vsl ? EVPLP_PASS_GATHER_VSL : EVPLP_PASS_GATHER_VPL;
     const char *name = vsl ? "evplp_gather_vsl" : "evplp_gather_vpl";
@@ -874,112 +879,56 @@ static int run_gather(evplp_context *c, const evplp_frame_params *fp, bool vsl) 
     const bool gbudget = c->adapt_gather_budget;
     const int32_t ntiles_all = c->tiles_x * c->tiles_y, phase = (int32_t)(c->adapt_m % c->adapt_window);
     if (gbudget) ad.tiles = c->d_adapt_mask;
-    // work-item size: k consecutive splits per wavefront (fixed summation tree: the result does not depend on k).  The per-item
-    // statistics need (VPLs per split) * k < 65536.
-    int k = 1;
-    {
-        // (a row strip of an n-way partition is a SMALL launch, and small launches want short items: one rank's gather of an eight-way
-        // partition of config #2 takes 9.3 / 12.1 / 17.5 ms for k = 1 / 2 / 4 where an eighth of the one-GPU kernel is 6.2 ms --
-        // profiles/r05_strip_projection.json: projected 5.2x instead of 4.1x at eight ranks.  The result does not depend on k.)
-        // (round 6: keyed on the size of the launch -- at most 8 192 owned tiles, the threshold of item_deal -- instead of on strip_count > 1; at
-        // eight dealt ranks k = 2 projects x5.1 where k = 1 projects x6.5: an item twice as long is a tail twice as long)
-        const bool small_launch = small_gather_launch(c);
-        k = c->cfg.gather_splits_per_wave > 0 ? c->cfg.gather_splits_per_wave : (small_launch ? 1 : kDefaultSplitsPerWave);
-        if (c->env_gather_k > 0) k = c->env_gather_k;
-        const size_t max_vpls = std::max<size_t>((size_t)c->cfg.num_vpl_light_paths * c->cfg.photons_per_path, 1);
-        while (k > 1 && (max_vpls / kVplSplit + 1) * (size_t)k >= 65536) k >>= 1;
-        if (vsl) while (k > 1 && (max_vpls / kVplSplit + 1) * (size_t)k > 4095) k >>= 1;      // (the estimator kernel's packed per-lane counters)
-        if (vsl && (max_vpls / kVplSplit + 1) > 4095) {      // k = 1 and still more than 4095 VSLs per item: the packed counters would wrap
-            c->set_error("%s: %zu VSL record slots exceed the %d this build can gather in one pass", name, max_vpls, 4094 * kVplSplit); return EVPLP_ERR_INVALID;
-        }
+    // the plan (host/gather_plan.cpp): every count below is its arithmetic, and the result of the gather depends on none of it
+    GatherPlanInput pin{};
+    pin.W = c->st.W; pin.local_rows = c->st.local_rows; pin.rows_in_image = c->rows_in_image; pin.strip_count = c->st.strip_count; pin.strip_rows = c->st.strip_rows;
+    pin.nvpl_slots = nvpl_slot_count(c->cfg.num_vpl_light_paths, c->cfg.photons_per_path); pin.vsl = vsl; pin.splits_per_wave = c->cfg.gather_splits_per_wave;
+    pin.env_gather_k = c->env_gather_k; pin.env_item_deal = c->env_item_deal; pin.env_tile_block_log2 = c->env_tile_block_log2; pin.env_cuts = c->env_cuts;
+    pin.cut_cap = c->cut_cap; pin.mask_cap = c->mask_cap; pin.cuts_available = true;
+    GatherPlan plan = plan_gather(pin);
+    if (plan.refused) {
+        c->set_error("%s: %zu VSL record slots exceed the %d this build can gather in one pass", name, pin.nvpl_slots, 4094 * kVplSplit); return EVPLP_ERR_INVALID;
     }
-    a.splits_per_wave = k;
-    if ((rc = ensure_gather_workspace(c, a, (size_t)(kVplSplit / k)))) return rc;
-    // entry cuts (kernels.h CutArgs): one slot per (tile group, VPL slot).  Groups are 2 x 2 tiles where the strip's tile rows are
-    // neighbours in the image (one GPU, or strips of 16 rows and more), 2 x 1 otherwise.  The scratch is bounded (evplp_config.
-    // cut_scratch_bytes; below): a configuration whose slots need more is gathered band by band -- rows of tile blocks -- cuts first, then the walks.
+    // the workspaces the plan names.  Without memory for the cut scratch the frame is planned again without cuts: one band, walks from the
+    // root, and the masks of that band.
+    const size_t partial_bytes = sizeof(float4) * (size_t)plan.groups * a.partial_stride;
+    hipError_t me = grow_scratch(c, c->partial, partial_bytes);
+    if (me != hipSuccess) { c->set_error("gather: cannot allocate %zu bytes of partial sums: %s", partial_bytes, hipGetErrorString(me)); return EVPLP_ERR_OOM; }
+    if (plan.use_cuts && grow_scratch(c, c->cuts, plan.cut_bytes) != hipSuccess) { pin.cuts_available = false; plan = plan_gather(pin); }
+    if ((me = grow_scratch(c, c->vsl_masks, plan.mask_bytes)) != hipSuccess) { c->set_error("gather_vsl: cannot allocate %zu bytes of lit masks: %s", plan.mask_bytes, hipGetErrorString(me)); return EVPLP_ERR_OOM; }
+    a.splits_per_wave = plan.k; a.item_deal = plan.item_deal; a.block_h_log2 = plan.block_h_log2; a.partial = (float4 *)c->partial.p;
+    a.masks_per_split = plan.masks_per_split; a.vsl_masks = vsl ? (unsigned long long *)c->vsl_masks.p : nullptr;
     CutArgs ca; std::memset(&ca, 0, sizeof(ca));
-    bool use_cuts = c->env_cuts != 0;
-    const int sh = 1 << a.block_h_log2, nby = (c->tiles_y + sh - 1) / sh;       // rows of tile blocks
-    int band_rows = nby;
-    if (use_cuts && nby > 0) {
+    if (plan.use_cuts) {
         ca.nodes = c->sc.nodes; ca.tile_box = c->d_tile_box; ca.tiles_x = c->tiles_x; ca.tiles_y = c->tiles_y;
-        ca.gw_log2 = 1; ca.gh_log2 = (sh >= 2 && (c->st.strip_count == 1 || c->st.strip_rows >= 16)) ? 1 : 0;
-        ca.groups_x = (c->tiles_x + (1 << ca.gw_log2) - 1) >> ca.gw_log2;
-        ca.vpls = c->d_vpls; ca.nvpl = &c->d_scalars[0]; ca.vpl_stride = (uint32_t)nvpl_slots_of(c);
-        const size_t per_block_row = (size_t)(sh >> ca.gh_log2) * ca.groups_x * ca.vpl_stride * (size_t)kCutSlotBytes;
-        // The bound of the scratch: evplp_config.cut_scratch_bytes, or 8 GB (round 6; until round 5 a quarter of the device's memory -- 72 GB of
-        // 288 -- which let config #5's 68 GB of slots sit in one band -- 0.7 % faster than the nine it takes now, 1 167 against 1 174 ms -- and took a quarter of the GPU from whoever else
-        // lives on it: a library embedded in a host application asks for that much only when told to).  Configurations within the bound --
-        // config #2 / #3: 4.3 GB -- allocate what they need; larger ones are gathered band by band.  EVPLP_CUT_BYTES: test override.
-        if (c->cut_cap == 0) {
-            c->cut_cap = c->env_cut_bytes ? c->env_cut_bytes : (size_t)c->cfg.cut_scratch_bytes;
-            if (c->cut_cap == 0) c->cut_cap = kDefaultCutScratchBytes;
-        }
-        band_rows = (int)std::min<size_t>((size_t)nby, c->cut_cap / std::max<size_t>(per_block_row, 1));
-        if (band_rows < 1) { use_cuts = false; band_rows = nby; }            // (the bound does not hold one row of tile blocks: walks from the root)
-        const size_t need = use_cuts ? per_block_row * (size_t)band_rows : 0;
-        if (use_cuts && need > c->cut_bytes) {
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            hipFree(c->d_cuts); c->d_cuts = nullptr; c->cut_bytes = 0;
-            if (hipMalloc((void **)&c->d_cuts, need) == hipSuccess) c->cut_bytes = need;
-            else { (void)hipGetLastError(); use_cuts = false; band_rows = nby; }     // (no memory for the scratch: the walks start at the root)
-        }
-        ca.cuts = c->d_cuts;
+        ca.gw_log2 = plan.gw_log2; ca.gh_log2 = plan.gh_log2; ca.groups_x = plan.groups_x;
+        ca.vpls = c->d_vpls; ca.nvpl = &c->d_scalars[0]; ca.vpl_stride = plan.vpl_stride;
+        ca.cuts = (char *)c->cuts.p;
         ca.adapt_tiles = c->calibrate ? nullptr : ad.tiles;
-    } else use_cuts = false;
+        a.cuts = ca.cuts; a.cut_vpl_stride = ca.vpl_stride; a.cut_gw_log2 = ca.gw_log2; a.cut_gh_log2 = ca.gh_log2; a.cut_groups_x = ca.groups_x;
+    }
     if ((rc = pass_begin(c, pass))) return rc;
     const uint32_t nrec = fp->photons_per_path * fp->num_vpl_light_paths;   // lighttracing.cu:368
     if (gbudget) launch_gather_budget_mask(c->d_adapt_tiles, ntiles_all, phase, c->adapt_window, c->d_adapt_mask, c->stream);
     launch_compact_vpl((const evplp_record *)c->buf[EVPLP_BUF_RECORDS], nrec, c->d_vpls, c->d_vpl_src, &c->d_scalars[0], c->stream);
-    if (use_cuts && !c->tile_box_valid) {      // the G-buffer did not come from evplp_primary (or the caller may have written it): boxes of the tiles as they are now
+    if (plan.use_cuts && !c->tile_box_valid) {      // the G-buffer did not come from evplp_primary (or the caller may have written it): boxes of the tiles as they are now
         launch_tile_boxes(c->st, (const float4 *)c->buf[EVPLP_BUF_GBUF_POSITION], c->d_tile_box, c->tiles_x, c->tiles_y, c->stream);
         c->tile_box_valid = !c->gbuf_pos_exposed;
     }
-    int vsl_groups = 0, vsl_per_launch = 0;
-    if (vsl) {
-        // lit masks between the walk and the estimator kernel: 8 bytes per (tile, VSL slot) of a launch; the groups of a tile are
-        // covered in as many launches as keep the buffer within its cap (below)
-        a.masks_per_split = (int32_t)((nvpl_slots_of(c) + kVplSplit - 1) / kVplSplit);
-        a.band_first = 0; a.band_rows = band_rows < nby ? band_rows : 0;
-        const size_t tiles = (size_t)gather_launch_tiles(a), per_item = (size_t)k * (size_t)a.masks_per_split * sizeof(unsigned long long);
-        vsl_groups = kVplSplit / k;
-        vsl_per_launch = vsl_groups;
-        // the bound of the mask buffer: evplp_config.vsl_mask_bytes, or 2 GB (round 6; until round 5 a twentieth of the device's memory, which
-        // held config #5's 8.6 GB in one launch)
-        if (c->mask_cap == 0) {
-            c->mask_cap = (size_t)c->cfg.vsl_mask_bytes;
-            if (const char *me = std::getenv("EVPLP_MASK_BYTES")) c->mask_cap = (size_t)strtoull(me, nullptr, 10);      // (developer switch)
-            if (c->mask_cap == 0) c->mask_cap = kDefaultVslMaskBytes;
-        }
-        const size_t mask_cap = c->mask_cap;
-        while (vsl_per_launch > 1 && tiles * (size_t)vsl_per_launch * per_item > mask_cap) vsl_per_launch = (vsl_per_launch + 1) / 2;
-        const size_t mask_bytes = tiles * (size_t)vsl_per_launch * per_item;
-        if (c->vsl_mask_bytes < mask_bytes) {
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            hipFree(c->d_vsl_masks); c->d_vsl_masks = nullptr; c->vsl_mask_bytes = 0;
-            hipError_t e = hipMalloc((void **)&c->d_vsl_masks, mask_bytes);
-            if (e != hipSuccess) { c->set_error("gather_vsl: cannot allocate %zu bytes of lit masks: %s", mask_bytes, hipGetErrorString(e)); return EVPLP_ERR_OOM; }
-            c->vsl_mask_bytes = mask_bytes;
-        }
-        a.vsl_masks = (unsigned long long *)c->d_vsl_masks;
-    }
+    // band by band: the cuts of the band's tile groups, then its walks -- the VSL gather's one launch per group range
     // (the events bracket the cuts AND the walks: the cut kernel is part of the gather's work)
     HIP_TRY(c, hipEventRecord(c->ev_dom_begin[pass], c->stream));
-    for (int b0 = 0; b0 < nby; b0 += band_rows) {
-        const int rows = std::min(band_rows, nby - b0);
-        a.band_first = b0; a.band_rows = band_rows < nby ? rows : 0;
-        if (use_cuts) {
-            const int gshift = ca.gh_log2, groups_total_y = (c->tiles_y + (1 << gshift) - 1) >> gshift;
-            ca.group_row_first = (b0 * sh) >> gshift;
-            ca.groups_y = std::min(((b0 + rows) * sh + (1 << gshift) - 1) >> gshift, groups_total_y) - ca.group_row_first;
+    for (int i = 0; i < plan.nbands; i++) {
+        const GatherBand band = gather_band(plan, i);
+        a.band_first = band.first; a.band_rows = band.args_rows;
+        if (plan.use_cuts) {
+            ca.group_row_first = a.cut_group_row_first = band.group_row_first; ca.groups_y = band.groups_y;
             launch_gather_cuts(ca, c->stream);
-            a.cuts = ca.cuts; a.cut_vpl_stride = ca.vpl_stride; a.cut_gw_log2 = ca.gw_log2; a.cut_gh_log2 = ca.gh_log2; a.cut_groups_x = ca.groups_x;
-            a.cut_group_row_first = ca.group_row_first;
         }
         if (vsl) {
-            for (int g0 = 0; g0 < vsl_groups; g0 += vsl_per_launch) {
-                a.group_first = g0; a.group_count = std::min(vsl_per_launch, vsl_groups - g0);
+            for (int j = 0; j < plan.group_launches; j++) {
+                const GatherGroupRange r = gather_group_range(plan, j);
+                a.group_first = r.first; a.group_count = r.count;
                 launch_gather_vsl(a, c->stream, ad);
             }
             a.group_first = 0; a.group_count = 0;
@@ -1076,24 +1025,15 @@ extern "C" int evplp_path_trace_batch(evplp_context *c, const float camera_pos[3
         // the staging buffer: what the call needs, within the bound; it only grows, unless the bound came down below it
         const uint64_t cap_slots = std::min<uint64_t>(c->pt_batch_cap / kPtBatchSlotBytes, 1u << 30);
         const uint64_t slots = std::min<uint64_t>(std::max<uint64_t>(items, 1), cap_slots);
-        if (c->pt_batch_bytes < slots * kPtBatchSlotBytes || c->pt_batch_bytes > cap_slots * kPtBatchSlotBytes) {
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            if (c->d_pt_batch) { hipFree(c->d_pt_batch); c->d_pt_batch = nullptr; c->pt_batch_bytes = 0; }
-            if (hipMalloc((void **)&c->d_pt_batch, slots * kPtBatchSlotBytes) != hipSuccess) {
-                (void)hipGetLastError(); c->d_pt_batch = nullptr;
-                c->set_error("%s: cannot allocate %llu B of staging (bound it with evplp_path_trace_batch_scratch)", name, (unsigned long long)(slots * kPtBatchSlotBytes));
-                return EVPLP_ERR_OOM;
-            }
-            c->pt_batch_bytes = slots * kPtBatchSlotBytes;
+        if (c->pt_batch.bytes > cap_slots * kPtBatchSlotBytes) c->pt_batch.bytes = 0;      // (it counts as holding nothing: the grow below frees it)
+        if (grow_scratch(c, c->pt_batch, slots * kPtBatchSlotBytes) != hipSuccess) {
+            c->set_error("%s: cannot allocate %llu B of staging (bound it with evplp_path_trace_batch_scratch)", name, (unsigned long long)(slots * kPtBatchSlotBytes));
+            return EVPLP_ERR_OOM;
         }
-        const uint64_t have = c->pt_batch_bytes / kPtBatchSlotBytes;
+        const uint64_t have = c->pt_batch.bytes / kPtBatchSlotBytes;
         if (!c->d_pt_first) HIP_TRY(c, hipMalloc((void **)&c->d_pt_first, sizeof(int32_t) * (ntiles + 1)));
-        if (c->pt_table_items < items) {
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            hipFree(c->d_pt_table); c->d_pt_table = nullptr; c->pt_table_items = 0;
-            HIP_TRY(c, hipMalloc((void **)&c->d_pt_table, sizeof(uint32_t) * items));
-            c->pt_table_items = items;
-        }
+        const hipError_t te = grow_scratch(c, c->pt_table, sizeof(uint32_t) * items);
+        if (te != hipSuccess) { c->set_error("%s: cannot allocate %llu B of item table: %s", name, (unsigned long long)(sizeof(uint32_t) * items), hipGetErrorString(te)); return EVPLP_ERR_OOM; }
 
         PrimaryArgs pa; std::memset(&pa, 0, sizeof(pa));
         pa.sc = c->sc; pa.st = c->st; pa.cam = c->cam; pa.g_light = (float4 *)c->buf[EVPLP_BUF_LIGHT];
@@ -1105,9 +1045,9 @@ extern "C" int evplp_path_trace_batch(evplp_context *c, const float camera_pos[3
         ta.counters = &c->d_counters[EVPLP_PASS_PATH_TRACE];
         float4 *out = (float4 *)c->buf[EVPLP_BUF_VPL_ACCUM];
         if ((rc = pass_begin(c, EVPLP_PASS_PATH_TRACE))) return rc;
-        launch_pt_batch_table(c->d_adapt_tiles, (int32_t)ntiles, mode, samples, c->d_pt_first, c->d_pt_table, c->stream);
+        launch_pt_batch_table(c->d_adapt_tiles, (int32_t)ntiles, mode, samples, c->d_pt_first, (uint32_t *)c->pt_table.p, c->stream);
         PtBatchChunk ch; std::memset(&ch, 0, sizeof(ch));
-        ch.table = c->d_pt_table; ch.total = c->d_pt_first + ntiles; ch.staging = (float4 *)c->d_pt_batch; ch.cut_mask = cut_mask;
+        ch.table = (const uint32_t *)c->pt_table.p; ch.total = c->d_pt_first + ntiles; ch.staging = (float4 *)c->pt_batch.p; ch.cut_mask = cut_mask;
         for (uint64_t i0 = 0; i0 < items; i0 += have) {
             ch.item_first = (int32_t)i0; ch.item_count = (int32_t)std::min<uint64_t>(have, items - i0);
             launch_pt_batch_primary(pa, sm, ch, c->stream);
@@ -1475,18 +1415,10 @@ bool denoise_settings(const evplp_denoise_params *p, DenoiseSettings *out, char 
     *out = d;
     return true;
 }
-static int denoise_alloc(evplp_context *c, void **p, size_t bytes) {
-    if (*p) return EVPLP_OK;
-    const hipError_t e = hipMalloc(p, bytes);
-    if (e == hipSuccess) return EVPLP_OK;
-    (void)hipGetLastError(); *p = nullptr;
-    c->set_error("evplp_denoise: cannot allocate %zu bytes: %s", bytes, hipGetErrorString(e));
-    return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP;
-}
 int denoise_keep_variance(evplp_context *c) {
     const size_t px = (size_t)c->st.W * c->st.local_rows;
     HIP_TRY(c, hipSetDevice(c->cfg.device));
-    int rc = denoise_alloc(c, (void **)&c->d_dn_var, sizeof(float) * 3 * std::max<size_t>(px, 1));
+    int rc = alloc_once(c, "evplp_denoise", (void **)&c->d_dn_var, sizeof(float) * 3 * std::max<size_t>(px, 1));
     if (rc) return rc;
     HIP_TRY(c, hipMemcpyAsync(c->d_dn_var, c->d_rgb, sizeof(float) * 3 * px, hipMemcpyDeviceToDevice, c->stream));
     return EVPLP_OK;
@@ -1494,7 +1426,7 @@ int denoise_keep_variance(evplp_context *c) {
 int denoise_prepare(evplp_context *c, const float4 *pos, const float4 *nrm, const float4 *dif, const float4 *phg, const float4 *light) {
     const size_t px = (size_t)c->st.W * c->st.local_rows;
     HIP_TRY(c, hipSetDevice(c->cfg.device));
-    int rc = denoise_alloc(c, (void **)&c->d_dn_pack, sizeof(DenoisePixel) * std::max<size_t>(px, 1));
+    int rc = alloc_once(c, "evplp_denoise", (void **)&c->d_dn_pack, sizeof(DenoisePixel) * std::max<size_t>(px, 1));
     if (rc) return rc;
     launch_denoise_prepare(c->st, c->d_rgb, c->d_dn_var, pos, nrm, dif, phg, light, (float4 *)c->d_dn_pack, c->stream);
     HIP_TRY(c, hipGetLastError());
@@ -1504,7 +1436,7 @@ int denoise_filter(evplp_context *c, const DenoisePixel *frame, int rows, const 
     const size_t px = (size_t)c->st.W * rows;
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     if (c->d_dn_u && c->dn_u_px < px) { hipFree(c->d_dn_u); c->d_dn_u = nullptr; }
-    int rc = denoise_alloc(c, (void **)&c->d_dn_u, sizeof(float4) * 2 * std::max<size_t>(px, 1));
+    int rc = alloc_once(c, "evplp_denoise", (void **)&c->d_dn_u, sizeof(float4) * 2 * std::max<size_t>(px, 1));
     if (rc) return rc;
     c->dn_u_px = std::max(c->dn_u_px, px);
     DenoiseLevelArgs a{};
@@ -1579,14 +1511,6 @@ static void temporal_release(evplp_context *c) {
     c->d_tp_prev_v = nullptr; c->d_tp_prev = c->d_tp_prev_frame = nullptr; c->d_tp_hist = nullptr; c->d_tp_counts = nullptr;
     c->tp_tris = 0; c->tp_hist_px = 0; c->tp_count_slots = 0; c->tp_frames = 0; c->tp_cur = 0; c->tp_on = false;
 }
-static int temporal_alloc(evplp_context *c, void **p, size_t bytes) {
-    if (*p) return EVPLP_OK;
-    const hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16));
-    if (e == hipSuccess) return EVPLP_OK;
-    (void)hipGetLastError(); *p = nullptr;
-    c->set_error("evplp_denoise_temporal: cannot allocate %zu bytes: %s", bytes, hipGetErrorString(e));
-    return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP;
-}
 // the previous pose follows the scene's triangle count: another count forgets the history and makes the array anew
 int temporal_pose_array(evplp_context *c) {
     if (c->d_tp_prev_v && c->tp_tris == c->scene_tris) return EVPLP_OK;
@@ -1594,7 +1518,7 @@ int temporal_pose_array(evplp_context *c) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     hipFree(c->d_tp_prev_v); c->d_tp_prev_v = nullptr; c->tp_frames = 0;
     c->tp_tris = c->scene_tris;
-    return temporal_alloc(c, (void **)&c->d_tp_prev_v, sizeof(float) * 9 * (size_t)std::max(c->scene_tris, 1));
+    return alloc_once(c, "evplp_denoise_temporal", (void **)&c->d_tp_prev_v, sizeof(float) * 9 * (size_t)std::max(c->scene_tris, 1));
 }
 int temporal_enable(evplp_context *c, int32_t on) {
     HIP_TRY(c, hipSetDevice(c->cfg.device));
@@ -1605,7 +1529,7 @@ int temporal_enable(evplp_context *c, int32_t on) {
     }
     if (c->tp_on) return EVPLP_OK;
     int rc = temporal_pose_array(c);
-    if (!rc) rc = temporal_alloc(c, (void **)&c->d_tp_prev, sizeof(TemporalPrev) * (size_t)c->st.W * c->st.local_rows);
+    if (!rc) rc = alloc_once(c, "evplp_denoise_temporal", (void **)&c->d_tp_prev, sizeof(TemporalPrev) * (size_t)c->st.W * c->st.local_rows);
     if (rc) { temporal_release(c); return rc; }
     c->tp_on = true; c->tp_frames = 0;
     return EVPLP_OK;
@@ -1628,10 +1552,10 @@ int temporal_accumulate(evplp_context *c, DenoisePixel *frame, const TemporalPre
     const size_t px = std::max<size_t>((size_t)c->st.W * rows, 1);
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     if (c->d_tp_hist && c->tp_hist_px != px) { HIP_TRY(c, hipStreamSynchronize(c->stream)); hipFree(c->d_tp_hist); c->d_tp_hist = nullptr; c->tp_frames = 0; }
-    int rc = temporal_alloc(c, (void **)&c->d_tp_hist, sizeof(float4) * 6 * px);
+    int rc = alloc_once(c, "evplp_denoise_temporal", (void **)&c->d_tp_hist, sizeof(float4) * 6 * px);
     const int slots = temporal_count_slots(c->st.W, rows);
     if (c->d_tp_counts && c->tp_count_slots < slots) { HIP_TRY(c, hipStreamSynchronize(c->stream)); hipFree(c->d_tp_counts); c->d_tp_counts = nullptr; }
-    if (!rc) rc = temporal_alloc(c, (void **)&c->d_tp_counts, sizeof(uint4) * (size_t)slots);
+    if (!rc) rc = alloc_once(c, "evplp_denoise_temporal", (void **)&c->d_tp_counts, sizeof(uint4) * (size_t)slots);
     if (rc) return rc;
     c->tp_hist_px = px; c->tp_count_slots = slots;
     TemporalArgs a{};

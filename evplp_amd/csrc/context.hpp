@@ -75,6 +75,8 @@ struct HostMesh {
 };
 // what a matrix or a pose acts on: the morphed base while weights are in force, else the rest pose
 inline const std::vector<float> &mesh_base(const HostMesh &m) { return !m.base.empty() ? m.base : m.rest.empty() ? m.verts : m.rest; }
+// device scratch of a pass that only grows (context.cpp grow_scratch); freed by evplp_destroy
+struct DeviceScratch { void *p = nullptr; size_t bytes = 0; };
 struct HostTexture { int32_t w = 0, h = 0; std::vector<float> rgba; };
 struct HostStats { uint64_t rays = 0; };
 // host/proxy_mesh.cpp: the proxy mesh of EVPLP_FOOTPRINT_PROXY as slabs (kernels.h ProxyDev)
@@ -252,13 +254,13 @@ struct evplp_context {
     uint32_t *d_scalars = nullptr;           // [0] usable VPL count, [8] splat overflow
     evplp::PassCounters *d_counters = nullptr;
     float *d_rgb = nullptr;
-    // gather workspace, allocated on the first gather (path-tracing / photon-only contexts never pay for it)
-    float4 *d_partial = nullptr; size_t partial_groups = 0;    // [groups][local_rows * W] per-item partial sums
-    int32_t *d_lt_overflow = nullptr; size_t lt_overflow_bytes = 0;   // light tracing: the walk stack beyond its LDS entries (kernels.h)
+    // gather workspace (DeviceScratch: made by the first pass that needs it, so path-tracing / photon-only contexts never pay for it; it only grows)
+    evplp::DeviceScratch partial;              // [groups][local_rows * W] float4 per-item partial sums
+    evplp::DeviceScratch lt_overflow;          // light tracing: the walk stack beyond its LDS entries (kernels.h)
     char *d_primary_cuts = nullptr; bool primary_cuts_valid = false;   // the eye's entry cuts, one slot per tile group, rebuilt when the camera or the tree changes
-    char *d_cuts = nullptr; size_t cut_bytes = 0, cut_cap = 0;  // gathers: entry cuts of every (tile group, VPL) (kernels.h CutArgs), allocated on the first gather; cut_cap: their bound, fixed at the first gather
-    size_t mask_cap = 0;                                       // bound of d_vsl_masks, fixed at the first VSL gather
-    void *d_vsl_masks = nullptr; size_t vsl_mask_bytes = 0;    // VSL gather: lit masks + per-item ray counts of one launch (kernels.h GatherArgs)
+    evplp::DeviceScratch cuts;                 // gathers: entry cuts of every (tile group, VPL) of a band (kernels.h CutArgs)
+    evplp::DeviceScratch vsl_masks;            // VSL gather: lit masks + per-item ray counts of one launch (kernels.h GatherArgs)
+    size_t cut_cap = 0, mask_cap = 0;          // bounds of cuts and vsl_masks, in bytes: EVPLP_CUT_BYTES / EVPLP_MASK_BYTES, else evplp_config, else the defaults (evplp_create)
 
     // splat workspace
     int32_t tiles_x = 0, tiles_y = 0; uint32_t bin_stride = 0, last_bin_entries = 0, last_bin_max = 0;   // bin_stride: slots per tile bin
@@ -296,12 +298,12 @@ struct evplp_context {
     int npend = 0;
 
     // Test / developer overrides, read ONCE by evplp_create (never in a pass): EVPLP_BVH_BUILDER (every suite under every builder),
-    // EVPLP_BIN_STRIDE (forces the photon-bin overflow path), EVPLP_GATHER_K, EVPLP_TILE_BLOCK_LOG2.  -1 / 0 = not set.
+    // EVPLP_BIN_STRIDE (forces the photon-bin overflow path), EVPLP_GATHER_K, EVPLP_TILE_BLOCK_LOG2.  -1 / 0 = not set.  (EVPLP_CUT_BYTES and
+    // EVPLP_MASK_BYTES -- tests: they force the gather's band and group-range paths -- are resolved there into cut_cap / mask_cap.)
     int32_t env_ploc_radius = 0, env_ploc_iterations = -1;                                         // EVPLP_PLOC_RADIUS, EVPLP_PLOC_ITERATIONS (0 / -1: not set)
     int32_t env_bvh_builder = -1, env_gather_k = 0, env_tile_block_log2 = -1, env_cuts = -1;      // env_cuts: EVPLP_CUTS=0 walks from the root
     int32_t env_item_deal = -1;                // EVPLP_ITEM_DEAL: 0 tiles dealt to XCDs, 1 a tile's items over all XCDs (default: by launch size)
     int32_t env_split_min = 0;                 // EVPLP_SPLIT_MIN: fullest bin from which the splat's tile kernel runs four waves per tile
-    size_t env_cut_bytes = 0;                  // EVPLP_CUT_BYTES: test override of evplp_config.cut_scratch_bytes
 
     // A context that belongs to an evplp_group is driven by that rank's worker thread (group.cpp).  A call from any other thread -- the
     // caller reading statistics or buffers through evplp_group_context -- first waits until the worker has nothing queued for it.
@@ -323,9 +325,9 @@ struct evplp_context {
     int64_t adapt_n = 0; int4 *d_adapt_tiles = nullptr; float4 *d_adapt_snap = nullptr; std::vector<int4> adapt_tiles; int32_t adapt_last = 0;
     bool adapt_pt = false;          // evplp_adaptive_enable_pt: evplp_path_trace owns the retirement (the gathers are refused)
     // evplp_path_trace_batch: the staging slots of one chunk (kernels.h PtBatchChunk; allocated on the first call, bounded by pt_batch_cap --
-    // evplp_path_trace_batch_scratch), first [tiles + 1] and the item table [pt_table_items], which only grows
-    char *d_pt_batch = nullptr; size_t pt_batch_bytes = 0; uint64_t pt_batch_cap = 1ull << 30;
-    int32_t *d_pt_first = nullptr; uint32_t *d_pt_table = nullptr; size_t pt_table_items = 0;
+    // evplp_path_trace_batch_scratch), first [tiles + 1] and the item table (uint32 per item), which only grows
+    evplp::DeviceScratch pt_batch, pt_table; uint64_t pt_batch_cap = 1ull << 30;
+    int32_t *d_pt_first = nullptr;
     // budget mode (evplp_adaptive_enable_pt(ctx, 2)): adapt_pt is set too; the records' host copy follows the device's in every field (a call
     // adds s_t to n_t, a fold closes K_t and B_t: both are functions of the records alone); evplp_adaptive_tile_noise's per-tile doubles [tiles]
     bool adapt_budget = false; double *d_tile_noise = nullptr;

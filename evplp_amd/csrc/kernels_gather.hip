@@ -20,6 +20,7 @@
 // fetch it at all: the record rides behind its cut slot through the wave's own LDS ring (no barrier: one wave per workgroup).
 #include "device_common.hpp"
 #include "kernels.h"
+#include "host/gather_plan.hpp"
 #include <algorithm>
 
 namespace evplp {
@@ -1128,11 +1129,8 @@ __global__ __launch_bounds__(64, EVPLP_VSL_WAVES) void gather_vsl_shade_kernel(G
     if constexpr (COST) item_cost_add(a, item_index<true>(a, blk_out).ty, t_cost, EVPLP_VSL_WAVES);
 }
 
-int gather_launch_tiles(const GatherArgs &a) {                    // tiles of a launch: whole blocks of 8 x (1 << block_h_log2)
-    const int tiles_x = (a.st.W + 7) / 8, tiles_y = (a.st.local_rows + 7) / 8, sh = 1 << a.block_h_log2;
-    const int nby = (tiles_y + sh - 1) / sh, rows = a.band_rows > 0 ? std::min(a.band_rows, nby - a.band_first) : nby;
-    return ((tiles_x + 7) / 8) * std::max(rows, 0) * 8 * sh;
-}
+// tiles of a launch: whole blocks of 8 x (1 << block_h_log2) (host/gather_plan.hpp has the expression: the plan sizes the VSL masks by it)
+int gather_launch_tiles(const GatherArgs &a) { return gather_band_tiles(a.st.W, a.st.local_rows, a.block_h_log2, a.band_first, a.band_rows); }
 static dim3 gather_grid(const GatherArgs &a) {
     const int groups = a.group_count > 0 ? a.group_count : kVplSplit / a.splits_per_wave;
     return dim3((unsigned)(gather_launch_tiles(a) * groups));     // tile = tile_j * 8 + xcd

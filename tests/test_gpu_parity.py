@@ -734,6 +734,42 @@ def test_entry_cuts_do_not_change_a_bit(evplp, monkeypatch):
         assert images[name][1].tobytes() == images["cuts"][1].tobytes(), f"VSL gather: {name} differs from cuts"
 
 
+def test_gather_bands_and_group_ranges_do_not_change_a_bit(evplp, monkeypatch):
+    """How a gather is cut into launches (host/gather_plan.cpp) says where a walk starts and which launch runs it, never what it adds up.  A
+    72 x 136 frame -- 9 x 17 tiles: ragged block columns, a ragged last row of tile blocks, three rows of them -- gathered as one band and one
+    launch, as three bands of eight group ranges each (cut scratch and VSL masks both bounded; tools/host_fuzz/gather_plan_check.cpp pins that
+    these two byte values give at least three bands and four launches per band), and as one band of sixteen group ranges: the same accumulator
+    bytes, shadow rays and unoccluded pairs."""
+    w, h, n = 72, 136, 64
+    tall = scenes.box_room(seed=3, n_boxes=5, tess=2, aspect=w / h)
+    kw = dict(camera_pos=tall.cam_origin, mis_mode=1, pdf_mc=0.35, clamping_value=0.02, photon_radius=0.05, vsl_radius=0.3,
+              vsl_inv_pi_radius2=1.0 / (math.pi * 0.09), num_light_paths=n, num_vpl_light_paths=n, photons_per_path=P, do_accumulate=0, rng_seed=5)
+    cases = (("whole", {}), ("bands x ranges", {"EVPLP_CUT_BYTES": "2000000", "EVPLP_MASK_BYTES": "50000"}), ("ranges", {"EVPLP_MASK_BYTES": "50000"}))
+    out = {}
+    for name, env in cases:
+        for k in ("EVPLP_CUT_BYTES", "EVPLP_MASK_BYTES"):
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)            # (read by evplp_create)
+        with evplp.Context(w, h, n, n, P) as c:
+            tall.upload(c)
+            c.primary((0.003, -0.002)); c.trace_light_paths(5)
+            got = []
+            for gather, pass_id in ((c.gather_vpl, evplp.PASS_GATHER_VPL), (c.gather_vsl, evplp.PASS_GATHER_VSL)):
+                gather(evplp.frame_params(**kw))
+                st = c.pass_stats(pass_id)
+                got.append((c.download(evplp.BUF_VPL_ACCUM)[:h].tobytes(), st["rays"], st["shaded"]))
+            out[name] = got
+    for name in ("EVPLP_CUT_BYTES", "EVPLP_MASK_BYTES"):
+        monkeypatch.delenv(name, raising=False)
+    for which, (img, rays, shaded) in zip(("VPL", "VSL"), out["whole"]):
+        assert rays > 0 and np.frombuffer(img, np.float32).max() > 0, which
+    for name in ("bands x ranges", "ranges"):
+        for which, whole, got in zip(("VPL", "VSL"), out["whole"], out[name]):
+            assert got[1:] == whole[1:], (which, name, got[1:], whole[1:])
+            assert got[0] == whole[0], f"{which} gather: {name} differs from one band, one launch"
+
+
 @pytest.mark.parametrize("seed", [11, 12, 13])
 def test_entry_cuts_with_adversarial_vpl_positions(evplp, monkeypatch, seed):
     """Entry cuts against walks from the root on record sets the light tracer would never produce: VPLs sitting exactly on visible surface
