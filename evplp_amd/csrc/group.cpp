@@ -12,7 +12,7 @@
 //
 // (round 5) ONE WORKER THREAD PER RANK.  Until round 4 the caller's thread issued every rank's launches in turn: at eight ranks that is
 // ~50 enqueue calls per iteration against config #4's 0.15-0.6 ms iteration -- the host, not the GPUs, would have set that
-// configuration's pace.  Now a group call only POSTS a small command record to each rank's single-producer ring (no lock taken by a
+// configuration's pace.  Now a group call only POSTS a small task to each rank's single-producer ring (host/cmd_ring.hpp: no lock taken by a
 // waiting party, no system call while the workers are awake) and returns; every worker is bound to its device, runs its rank's calls in
 // order -- waits for a photon splat's verdict included: nobody else waits with it -- and issues its rank's side of a collective itself
 // (RCCL's one-thread-per-GPU model).  Per-pixel results do not depend on any of this: the same calls reach every context in the same order.
@@ -23,6 +23,7 @@
 //   * a call made directly on a rank's context (evplp_group_context: statistics, buffers) first waits until that rank's worker has
 //     nothing queued (evplp_context::quiesce).
 #include "context.hpp"
+#include "host/cmd_ring.hpp"
 
 #include <rccl/rccl.h>      // types only: the entry points are resolved with dlsym
 
@@ -30,13 +31,11 @@
 #include <atomic>
 #include <chrono>
 #include <cmath>
-#include <condition_variable>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <dlfcn.h>
 #include <memory>
-#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
@@ -48,6 +47,7 @@ int frame_error_rows(evplp_context *c);                                         
 void place_row_errors(const evplp_context *c, const std::vector<RowError> &local, std::vector<RowError> &rows, std::vector<char> &held);   // context.cpp
 }
 
+struct evplp_group;
 namespace {
 struct Rccl {
     void *lib = nullptr;
@@ -65,56 +65,29 @@ struct Rccl {
     }
 };
 
-enum Op { OP_QUIT = 0, OP_CLEAR, OP_SYNC, OP_PRIMARY, OP_TRACE, OP_GATHER, OP_SPLAT, OP_PATH_TRACE, OP_PRESENT, OP_LOAD_SCENE, OP_SET_PROXY, OP_ASSEMBLE, OP_REDUCE, OP_SET_REFERENCE, OP_FRAME_ERROR,
-          OP_NOISE_TRACK, OP_NOISE_FOLD, OP_NOISE_POOL, OP_NOISE_ROWS, OP_NOISE_VARIANCE, OP_ADAPT_ENABLE, OP_ADAPT_RETIRE, OP_DENOISE_PREP, OP_DENOISE_FILTER, OP_PATH_TRACE_BATCH, OP_ADAPT_SET_BUDGETS, OP_ADAPT_TILE_NOISE, OP_UPDATE_MESH, OP_TRANSFORM_MESH, OP_SET_MESH_SKIN, OP_POSE_MESH, OP_SET_MESH_MORPH, OP_MORPH_MESH, OP_REFIT, OP_ACCEL_QUALITY, OP_REFIT_POLICY, OP_OPTIMIZE_ACCEL, OP_REFIT_ROTATIONS,
-          OP_TEMPORAL_ENABLE, OP_TEMPORAL_RESET, OP_TEMPORAL_POSE, OP_TEMPORAL_SNAPSHOT };
-// One posted call, copied into the ring by assignment: plain data (pointers must stay valid until the caller has drained: load_scene, set_proxy,
-// resolve do) but for `batch`, a shared pointer -- so every post and every worker-side copy of a command pays one atomic reference count, null or not.
-struct Cmd {
-    int op = OP_QUIT;
-    evplp_frame_params fp{};
-    float f[4] = {}; int32_t i[4] = {}; uint32_t u[4] = {};
-    const void *p0 = nullptr, *p1 = nullptr; void *out = nullptr;
-    double d = 0.0;
-    // OP_PATH_TRACE_BATCH: the call's jitters and seeds, copied (the call returns before the workers run it; the ring slot keeps the 768 B alive until it is reused)
-    std::shared_ptr<const evplp::PtBatchSamples> batch;
-};
-constexpr int kRing = 64;
-constexpr int kSpinBeforeSleep = 200000;     // ~1-2 ms of polling before an idle worker goes to sleep on its condition variable
-
-// sense-reversing barrier of the workers (spins: the waits are microseconds long, in front of a collective).  wait(flag) returns ONE
-// verdict for all parties of a generation: the last arriver reads `flag` once, in front of flipping the sense, and everybody leaves with
-// what it read -- a rank that fails right behind the barrier cannot make its peers disagree about whether the collective is entered.
-struct SpinBarrier {
-    std::atomic<int> count{ 0 }; std::atomic<int> sense{ 0 }; std::atomic<int> verdict{ 0 }; int n = 1;
-    int wait(const std::atomic<int> *flag = nullptr) {
-        const int s = sense.load(std::memory_order_acquire);
-        if (count.fetch_add(1, std::memory_order_acq_rel) == n - 1) {
-            count.store(0, std::memory_order_relaxed);
-            verdict.store(flag ? flag->load(std::memory_order_acquire) : 0, std::memory_order_relaxed);
-            sense.store(s ^ 1, std::memory_order_release);
-        } else { int spins = 0; while (sense.load(std::memory_order_acquire) == s) { if (++spins > 2000) std::this_thread::yield(); } }
-        // (the verdict of THIS generation: the next one's last arriver cannot overwrite it before every party of this one has arrived there,
-        // i.e. has returned from here)
-        return verdict.load(std::memory_order_relaxed);
-    }
-};
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-} // namespace
 
-struct evplp_group;
+struct Worker;
+// One posted call: what the rank's worker does, with the call's arguments captured by name (plain data; pointers must stay valid until the
+// caller has drained: load_scene, set_proxy, resolve do).  The largest state is a gather's: the frame params and the kind.
+constexpr size_t kTaskBytes = 96;
+using Task = evplp::Task<Worker, kTaskBytes>;
+static_assert(sizeof(Task) <= 176, "a ring slot (120 B) stays within the 176 B of the positional command record it replaced");
+using evplp::SpinBarrier;
 struct Worker {
     evplp_group *g = nullptr; int rank = 0;
+    evplp_context *c = nullptr;                       // the rank's context
     std::thread th;
-    Cmd ring[kRing];
-    alignas(64) std::atomic<uint64_t> head{ 0 };      // consumed
-    alignas(64) std::atomic<uint64_t> tail{ 0 };      // posted
-    std::mutex m; std::condition_variable cv; bool sleeping = false;
+    evplp::Ring<Task> ring;
     std::atomic<int> status{ 0 };                     // first failing call's status (sticky)
     char error[512] = "";
     // host time of this worker (evplp_group_host_stats): inside its rank's enqueue calls / inside exchanges (barriers, copies, collectives)
     double t_calls = 0.0, t_exchange = 0.0; uint64_t n_cmds = 0;
+    bool ok() const { return status.load(std::memory_order_relaxed) == 0; }
+    void fail(int rc, const char *msg);
+    void hip_fail(hipError_t e) { (void)hipGetLastError(); fail(e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP, hipGetErrorString(e)); }
 };
+} // namespace
 
 struct evplp_group {
     int n = 0;
@@ -132,7 +105,7 @@ struct evplp_group {
     int strip_rows = 16, image_blocks = 0, cap_blocks = 0;
     size_t strip_floats_cap = 0;            // d_frame's chunk size (the capacity); strip_floats <= it is what an exchange moves
     // EVPLP_PARTITION_ITERATIONS: every rank renders whole frames; the pass calls go to `selected`; a present with exchange / a resolve sums
-    // the ranks' planes (OP_REDUCE).  sums_fresh (caller's thread): no pass was posted since the last reduction -- the cached sums still hold
+    // the ranks' planes (worker_reduce).  sums_fresh (caller's thread): no pass was posted since the last reduction -- the cached sums still hold
     bool iterations = false; int selected = 0; bool sums_fresh = false;
     bool have_reference = false;            // evplp_group_set_error_reference has given every rank an image (caller's thread)
     bool noise_on = false;                  // evplp_group_noise_track is on on every rank (caller's thread)
@@ -172,18 +145,18 @@ struct evplp_group {
 static thread_local char g_group_create_error[512] = "";
 
 // ------------------------------------------------------------------------------------------------ the workers
-static void worker_fail(Worker *w, int rc, const char *msg) {
+void Worker::fail(int rc, const char *msg) {
     int expected = 0;
-    if (w->status.compare_exchange_strong(expected, rc)) { std::snprintf(w->error, sizeof(w->error), "%s", msg ? msg : ""); w->g->failed.store(1, std::memory_order_release); }
+    if (status.compare_exchange_strong(expected, rc)) { std::snprintf(error, sizeof(error), "%s", msg ? msg : ""); g->failed.store(1, std::memory_order_release); }
 }
 // all-gather of equal chunks, this rank's side: it contributes `count` floats at all_send[rank] and receives n * count floats at `recv`
 static void worker_all_gather(Worker *w, float *recv, size_t count, const std::vector<const float *> &all_send) {
     evplp_group *g = w->g; evplp_context *c = g->ctx[(size_t)w->rank];
     const float *send = all_send[(size_t)w->rank];
     if (g->n == 1 && g->virtual_ranks) {       // one rank: its chunk goes to its place in stream order, the host does not wait
-        if (w->status.load(std::memory_order_relaxed) == 0 && recv != send) {
+        if (w->ok() && recv != send) {
             hipError_t e = hipMemcpyAsync(recv, send, count * sizeof(float), hipMemcpyDeviceToDevice, c->stream);
-            if (e != hipSuccess) worker_fail(w, EVPLP_ERR_HIP, hipGetErrorString(e));
+            if (e != hipSuccess) w->fail(EVPLP_ERR_HIP, hipGetErrorString(e));
         }
         return;
     }
@@ -193,7 +166,7 @@ static void worker_all_gather(Worker *w, float *recv, size_t count, const std::v
     if (g->barrier.wait(&g->failed) != 0) return;
     if (!g->virtual_ranks) {
         ncclResult_t nr = g->rccl.AllGather(send, recv, count, ncclFloat, g->comms[(size_t)w->rank], c->stream);
-        if (nr != ncclSuccess) worker_fail(w, EVPLP_ERR_HIP, g->rccl.GetErrorString(nr));
+        if (nr != ncclSuccess) w->fail(EVPLP_ERR_HIP, g->rccl.GetErrorString(nr));
         return;
     }
     // virtual ranks share a device: every producer finishes, then plain device copies on the receiver's stream; the producers' buffers
@@ -206,42 +179,65 @@ static void worker_all_gather(Worker *w, float *recv, size_t count, const std::v
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     g->barrier.wait();
-    if (e != hipSuccess) worker_fail(w, EVPLP_ERR_HIP, hipGetErrorString(e));
+    if (e != hipSuccess) w->fail(EVPLP_ERR_HIP, hipGetErrorString(e));
+}
+// The collectives a command can end in (its `always` stage: reached by every rank, failed or not).  Every rank's source, this rank's destination:
+// the composited strips (a present, the strips' variance) ...
+static void exchange_strips(Worker &w) {
+    evplp_group *g = w.g;
+    std::vector<const float *> all((size_t)g->n);
+    for (int q = 0; q < g->n; q++) all[(size_t)q] = g->ctx[(size_t)q]->d_rgb;
+    worker_all_gather(&w, g->d_frame[(size_t)w.rank], g->strip_floats, all);
+}
+// ... the split light paths' records, in place: rank q's slice lies at offset q * chunk of its record buffer ...
+static void exchange_records(Worker &w) {
+    evplp_group *g = w.g;
+    std::vector<const float *> all((size_t)g->n);
+    const size_t chunk = (size_t)g->per_rank_paths * w.c->cfg.photons_per_path * (sizeof(evplp_record) / sizeof(float));
+    for (int q = 0; q < g->n; q++) all[(size_t)q] = (const float *)g->ctx[(size_t)q]->buf[EVPLP_BUF_RECORDS] + (size_t)q * chunk;
+    worker_all_gather(&w, (float *)w.c->buf[EVPLP_BUF_RECORDS], chunk, all);
+}
+// ... and the denoiser's packed pixels of the rows an exchange moves, with their previous-pose texels when the call is temporal
+static void exchange_denoise(Worker &w, bool temporal) {
+    evplp_group *g = w.g;
+    std::vector<const float *> all((size_t)g->n);
+    for (int q = 0; q < g->n; q++) all[(size_t)q] = (const float *)g->ctx[(size_t)q]->d_dn_pack;
+    worker_all_gather(&w, g->d_dn_recv[(size_t)w.rank], g->strip_floats / 3 * evplp::kDenoiseFloats, all);
+    if (!temporal) return;
+    for (int q = 0; q < g->n; q++) all[(size_t)q] = (const float *)g->ctx[(size_t)q]->d_tp_prev;
+    worker_all_gather(&w, g->d_tp_recv[(size_t)w.rank], g->strip_floats / 3 * evplp::kTemporalPrevFloats, all);
 }
 
 // EVPLP_PARTITION_ITERATIONS: the three accumulator planes of every rank summed -- VPL and photon in rank order in fp32, light as the first
-// non-zero pixel in rank order -- into this rank's d_sum, then composited from there.  cmd.i[3] = 0: no pass since the last reduction, the
+// non-zero pixel in rank order -- into this rank's d_sum, then composited from there.  exchange = false: no pass since the last reduction, the
 // cached sums are composited again and nothing is exchanged.  The planes are read through the contexts' CURRENT buffer pointers.
 static const int kSumPlanes[3] = { EVPLP_BUF_VPL_ACCUM, EVPLP_BUF_PHOTON_ACCUM, EVPLP_BUF_LIGHT };
-static void worker_reduce(Worker *w, const Cmd &cmd) {
-    evplp_group *g = w->g; const int r = w->rank; evplp_context *c = g->ctx[(size_t)r];
+static void worker_reduce(Worker *w, float vs, float ps, float ls, int32_t mask_emitter, int32_t gamma, bool exchange) {
+    evplp_group *g = w->g; const int r = w->rank; evplp_context *c = w->c;
     const size_t px = g->plane_px;
-    const bool exchange = cmd.i[3] != 0;
-    auto ok = [&] { return w->status.load(std::memory_order_relaxed) == 0; };
-    auto hip_fail = [&](hipError_t e) { (void)hipGetLastError(); worker_fail(w, e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP, hipGetErrorString(e)); };
     const double t0 = now_ms();
-    if (exchange && ok()) {
+    if (exchange && w->ok()) {
         const int rc = evplp::settle(c);                   // (the sums must be exact: every splat has its verdict, a re-run is enqueued)
-        if (rc < 0) worker_fail(w, rc, evplp_last_error(c));
+        if (rc < 0) w->fail(rc, evplp_last_error(c));
         hipError_t e = hipSuccess;
-        if (ok() && !g->d_sum[(size_t)r]) e = hipMalloc((void **)&g->d_sum[(size_t)r], sizeof(float4) * 3 * px);
-        if (e == hipSuccess && ok() && !g->virtual_ranks && !g->d_stage[(size_t)r]) e = hipMalloc((void **)&g->d_stage[(size_t)r], sizeof(float4) * (size_t)g->n * px);
-        if (e != hipSuccess) hip_fail(e);
+        if (w->ok() && !g->d_sum[(size_t)r]) e = hipMalloc((void **)&g->d_sum[(size_t)r], sizeof(float4) * 3 * px);
+        if (e == hipSuccess && w->ok() && !g->virtual_ranks && !g->d_stage[(size_t)r]) e = hipMalloc((void **)&g->d_stage[(size_t)r], sizeof(float4) * (size_t)g->n * px);
+        if (e != hipSuccess) w->hip_fail(e);
     }
-    if (!exchange && ok() && !g->d_sum[(size_t)r]) worker_fail(w, EVPLP_ERR_INVALID, "evplp_group_resolve: no reduction to composite");
+    if (!exchange && w->ok() && !g->d_sum[(size_t)r]) w->fail(EVPLP_ERR_INVALID, "evplp_group_resolve: no reduction to composite");
     const double t1 = now_ms();
     if (exchange) {            // (reached by every rank, failed or not: the barrier decides for all)
         float4 *sum = g->d_sum[(size_t)r];
         evplp::ShardPlanes src; std::memset(&src, 0, sizeof(src));
         if (g->n == 1 && g->virtual_ranks) {               // one rank: its planes, copied in stream order
-            if (ok()) for (int k = 0; k < 3; k++) {
+            if (w->ok()) for (int k = 0; k < 3; k++) {
                 src.p[0] = (const float4 *)c->buf[kSumPlanes[k]];
                 evplp::launch_reduce_shards(src, 1, k == 2, px, sum + (size_t)k * px, g->num_cus[(size_t)r], c->stream);
             }
         } else if (g->virtual_ranks) {
             // every rank's planes are final when its stream is idle; nobody writes them again before every reader has finished (second barrier)
-            hipError_t e = ok() ? hipStreamSynchronize(c->stream) : hipSuccess;
-            if (e != hipSuccess) hip_fail(e);
+            hipError_t e = w->ok() ? hipStreamSynchronize(c->stream) : hipSuccess;
+            if (e != hipSuccess) w->hip_fail(e);
             if (g->barrier.wait(&g->failed) == 0) {
                 for (int k = 0; k < 3; k++) {
                     for (int q = 0; q < g->n; q++) src.p[q] = (const float4 *)g->ctx[(size_t)q]->buf[kSumPlanes[k]];
@@ -250,7 +246,7 @@ static void worker_reduce(Worker *w, const Cmd &cmd) {
                 e = hipGetLastError();
                 if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
                 g->barrier.wait();
-                if (e != hipSuccess) hip_fail(e);
+                if (e != hipSuccess) w->hip_fail(e);
             }
         } else if (g->barrier.wait(&g->failed) == 0) {
             // distinct devices: one plane at a time all-gathered into the staging buffer, then reduced from there (stream order; no
@@ -259,20 +255,20 @@ static void worker_reduce(Worker *w, const Cmd &cmd) {
             for (int q = 0; q < g->n; q++) src.p[q] = stage + (size_t)q * px;
             for (int k = 0; k < 3; k++) {
                 ncclResult_t nr = g->rccl.AllGather(c->buf[kSumPlanes[k]], stage, px * 4, ncclFloat, g->comms[(size_t)r], c->stream);
-                if (nr != ncclSuccess) worker_fail(w, EVPLP_ERR_HIP, g->rccl.GetErrorString(nr));
+                if (nr != ncclSuccess) w->fail(EVPLP_ERR_HIP, g->rccl.GetErrorString(nr));
                 evplp::launch_reduce_shards(src, g->n, k == 2, px, sum + (size_t)k * px, g->num_cus[(size_t)r], c->stream);
             }
             hipError_t e = hipGetLastError();
-            if (e != hipSuccess) hip_fail(e);
+            if (e != hipSuccess) w->hip_fail(e);
         }
         w->t_exchange += now_ms() - t1;
     }
     const double t2 = now_ms();
-    if (ok()) {
+    if (w->ok()) {
         const float4 *sum = g->d_sum[(size_t)r];
-        evplp::launch_resolve(c->st, sum, sum + px, sum + 2 * px, cmd.f[0], cmd.f[1], cmd.f[2], cmd.i[0], cmd.i[1], c->d_rgb, c->stream);
+        evplp::launch_resolve(c->st, sum, sum + px, sum + 2 * px, vs, ps, ls, mask_emitter, gamma, c->d_rgb, c->stream);
         hipError_t e = hipGetLastError();
-        if (e != hipSuccess) hip_fail(e);
+        if (e != hipSuccess) w->hip_fail(e);
     }
     w->t_calls += (t1 - t0) + (now_ms() - t2); w->n_cmds++;
 }
@@ -281,15 +277,13 @@ static void worker_reduce(Worker *w, const Cmd &cmd) {
 // (noise_pool_kernel, once per rank), K and B summed -- the way worker_reduce moves the accumulators: virtual ranks are read where they are,
 // distinct devices all-gather their NoisePlanes into a staging buffer first.
 static void worker_noise_pool(Worker *w) {
-    evplp_group *g = w->g; const int r = w->rank; evplp_context *c = g->ctx[(size_t)r];
-    auto ok = [&] { return w->status.load(std::memory_order_relaxed) == 0; };
-    auto hip_fail = [&](hipError_t e) { (void)hipGetLastError(); worker_fail(w, e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP, hipGetErrorString(e)); };
+    evplp_group *g = w->g; const int r = w->rank; evplp_context *c = w->c;
     const double t0 = now_ms();
     const size_t px = g->plane_px, stride = c->noise_stride, bytes = evplp::noise_bytes(c);
     hipError_t e = hipSuccess;
-    if (ok() && r == 0 && !g->d_noise_pool) e = hipMalloc((void **)&g->d_noise_pool, sizeof(double) * 6 * stride);
-    if (e == hipSuccess && ok() && !g->virtual_ranks && !g->d_noise_stage[(size_t)r]) e = hipMalloc((void **)&g->d_noise_stage[(size_t)r], bytes * (size_t)g->n);
-    if (e != hipSuccess) hip_fail(e);
+    if (w->ok() && r == 0 && !g->d_noise_pool) e = hipMalloc((void **)&g->d_noise_pool, sizeof(double) * 6 * stride);
+    if (e == hipSuccess && w->ok() && !g->virtual_ranks && !g->d_noise_stage[(size_t)r]) e = hipMalloc((void **)&g->d_noise_stage[(size_t)r], bytes * (size_t)g->n);
+    if (e != hipSuccess) w->hip_fail(e);
     // rank 0, behind every rank's last command: K, B and the n launches, src(q) = rank q's moments
     auto pool = [&](auto src) {
         double k = 0.0, b = 0.0;
@@ -299,18 +293,18 @@ static void worker_noise_pool(Worker *w) {
         }
         g->pool_k = k; g->pool_b = b;
         hipError_t le = hipGetLastError();
-        if (le != hipSuccess) hip_fail(le);
+        if (le != hipSuccess) w->hip_fail(le);
     };
-    if (g->n == 1 && g->virtual_ranks) { if (ok()) pool([&](int) { return evplp::noise_moments_of(c); }); }
+    if (g->n == 1 && g->virtual_ranks) { if (w->ok()) pool([&](int) { return evplp::noise_moments_of(c); }); }
     else if (g->virtual_ranks) {
         // every rank's planes are final when its stream is idle; nobody folds again before rank 0 has read them (second barrier)
-        e = ok() ? hipStreamSynchronize(c->stream) : hipSuccess;
-        if (e != hipSuccess) hip_fail(e);
+        e = w->ok() ? hipStreamSynchronize(c->stream) : hipSuccess;
+        if (e != hipSuccess) w->hip_fail(e);
         if (g->barrier.wait(&g->failed) == 0) {
             if (r == 0) {
                 pool([&](int q) { return evplp::noise_moments_of(g->ctx[(size_t)q]); });
                 e = hipStreamSynchronize(c->stream);
-                if (e != hipSuccess) hip_fail(e);
+                if (e != hipSuccess) w->hip_fail(e);
             }
             g->barrier.wait();
         }
@@ -318,7 +312,7 @@ static void worker_noise_pool(Worker *w) {
         // distinct devices: the whole NoisePlanes allocation of every rank, all-gathered (stream order), then rank 0 pools from the stage
         char *stage = g->d_noise_stage[(size_t)r];
         ncclResult_t nr = g->rccl.AllGather(c->d_noise, stage, bytes / sizeof(float), ncclFloat, g->comms[(size_t)r], c->stream);
-        if (nr != ncclSuccess) worker_fail(w, EVPLP_ERR_HIP, g->rccl.GetErrorString(nr));
+        if (nr != ncclSuccess) w->fail(EVPLP_ERR_HIP, g->rccl.GetErrorString(nr));
         else if (r == 0) pool([&](int q) {
             const double *sq = (const double *)(stage + (size_t)q * bytes);
             const float4 *prev = (const float4 *)(sq + 3 * stride);
@@ -331,9 +325,6 @@ static void worker_noise_pool(Worker *w) {
 static evplp::NoiseMoments noise_pooled(const evplp_group *g, const evplp_context *c0) {
     return evplp::NoiseMoments{ g->d_noise_pool, g->d_noise_pool + 3 * c0->noise_stride, nullptr, nullptr, c0->noise_stride };
 }
-// evplp_group_denoise.  Strips (every rank, then the all-gather in worker_run): this rank's variance, composite and packed pixels.
-// Iterations (rank 0, behind the pooled variance and the reduction): the packed pixels of the reduced composite and light plane with the
-// guides of rank cmd.i[2], copied to rank 0's device first when that is another GPU.
 // this context's previous-pose texels (zeros on a first call), stream order
 static int worker_temporal_pose(evplp_context *c) {
     if (c->tp_frames > 0) return evplp::temporal_prev_pose(c);
@@ -341,39 +332,47 @@ static int worker_temporal_pose(evplp_context *c) {
     if (e != hipSuccess) { c->set_error("evplp_group_denoise_temporal: %s", hipGetErrorString(e)); return EVPLP_ERR_HIP; }
     return EVPLP_OK;
 }
-static int worker_denoise_prep(Worker *w, const Cmd &cmd) {
-    evplp_group *g = w->g; const int r = w->rank; evplp_context *c = g->ctx[(size_t)r];
+// evplp_group_denoise.  Strips (every rank, then exchange_denoise): this rank's variance, composite and packed pixels.
+// Iterations (rank 0, behind the pooled variance and the reduction): the packed pixels of the reduced composite and light plane with the
+// guides of rank guides_rank, copied to rank 0's device first when that is another GPU.
+static int worker_denoise_prep(Worker *w, float scale, float ls, int32_t mask_emitter, bool temporal, int guides_rank) {
+    evplp_group *g = w->g; evplp_context *c = w->c;
     const float4 *gb[4]; const float4 *light;
     int rc;
     if (!g->iterations) {
-        if ((rc = evplp::noise_variance_to_device(c, evplp::noise_moments_of(c), (double)c->noise_k, (double)c->noise_b, cmd.f[0])) < 0) return rc;
+        if ((rc = evplp::noise_variance_to_device(c, evplp::noise_moments_of(c), (double)c->noise_k, (double)c->noise_b, scale)) < 0) return rc;
         if ((rc = evplp::denoise_keep_variance(c)) < 0) return rc;
-        if ((rc = evplp::resolve_to_device(c, cmd.f[0], cmd.f[0], cmd.f[1], cmd.i[0], 0, true, false)) < 0) return rc;
+        if ((rc = evplp::resolve_to_device(c, scale, scale, ls, mask_emitter, 0, true, false)) < 0) return rc;
         for (int k = 0; k < 4; k++) gb[k] = (const float4 *)c->buf[EVPLP_BUF_GBUF_POSITION + k];
         light = (const float4 *)c->buf[EVPLP_BUF_LIGHT];
     } else {
-        const evplp_context *src = g->ctx[(size_t)cmd.i[2]];
+        const evplp_context *src = g->ctx[(size_t)guides_rank];
         const size_t px = g->plane_px;
         for (int k = 0; k < 4; k++) gb[k] = (const float4 *)src->buf[EVPLP_BUF_GBUF_POSITION + k];
-        if (src != c && g->device[(size_t)cmd.i[2]] != g->device[0]) {
+        if (src != c && g->device[(size_t)guides_rank] != g->device[0]) {
             hipError_t e = hipSuccess;
             if (!g->d_dn_guides) e = hipMalloc((void **)&g->d_dn_guides, sizeof(float4) * 4 * px);
             for (int k = 0; k < 4 && e == hipSuccess; k++)
-                e = hipMemcpyPeerAsync(g->d_dn_guides + (size_t)k * px, g->device[0], gb[k], g->device[(size_t)cmd.i[2]], sizeof(float4) * px, c->stream);
-            if (e != hipSuccess) { (void)hipGetLastError(); c->set_error("evplp_group_denoise: guides of rank %d: %s", cmd.i[2], hipGetErrorString(e)); return EVPLP_ERR_HIP; }
+                e = hipMemcpyPeerAsync(g->d_dn_guides + (size_t)k * px, g->device[0], gb[k], g->device[(size_t)guides_rank], sizeof(float4) * px, c->stream);
+            if (e != hipSuccess) { (void)hipGetLastError(); c->set_error("evplp_group_denoise: guides of rank %d: %s", guides_rank, hipGetErrorString(e)); return EVPLP_ERR_HIP; }
             for (int k = 0; k < 4; k++) gb[k] = g->d_dn_guides + (size_t)k * px;
         }
         light = g->d_sum[0] + 2 * px;
     }
     rc = evplp::denoise_prepare(c, gb[0], gb[1], gb[2], gb[3], light);
-    if (rc >= 0 && cmd.i[1] && !g->iterations) rc = worker_temporal_pose(c);      // (evplp_group_denoise_temporal: this rank's rows on the previous pose)
+    if (rc >= 0 && temporal && !g->iterations) rc = worker_temporal_pose(c);      // (evplp_group_denoise_temporal: this rank's rows on the previous pose)
     return rc;
 }
-// rank 0: the frame of packed pixels (strips: assembled from the all-gathered rows), the passes, the frame to the caller (cmd.out)
-static int worker_denoise_filter(Worker *w, const Cmd &cmd) {
-    evplp_group *g = w->g; evplp_context *c = g->ctx[0];
+// rank 0: the strips a rank's worker gathered (`gathered`: n chunks in rank order, `channels` floats per pixel) in image order
+static void assemble_strips(const evplp_group *g, const float *gathered, float *frame, int channels = 3) {
+    const evplp_context *c = g->ctx[0];
+    evplp::launch_assemble_strips(c->st, g->n, g->owner.empty() ? nullptr : g->d_owner, (int)(g->strip_floats / ((size_t)c->st.W * 3)), gathered, frame, c->stream, channels);
+}
+// rank 0: the frame of packed pixels (strips: assembled from the all-gathered rows), the accumulation stage of evplp_group_denoise_temporal
+// (iterations: on the texels of rank texels_rank), the passes, the frame to the caller (out_rgb)
+static int worker_denoise_filter(Worker *w, evplp::DenoiseSettings ds, bool temporal, evplp::TemporalSettings ts, int texels_rank, float *out_rgb) {
+    evplp_group *g = w->g; evplp_context *c = w->c;
     const size_t frame_px = (size_t)c->st.W * c->st.H;
-    evplp::DenoiseSettings ds{ cmd.i[0], cmd.f[0], cmd.f[1], cmd.f[2] };
     const evplp::DenoisePixel *frame = c->d_dn_pack;
     int rows = c->st.local_rows;
     float *out = c->d_rgb;
@@ -382,208 +381,141 @@ static int worker_denoise_filter(Worker *w, const Cmd &cmd) {
         if (!g->d_dn_frame) e = hipMalloc((void **)&g->d_dn_frame, sizeof(evplp::DenoisePixel) * frame_px);
         if (e == hipSuccess && !g->d_assembled) e = hipMalloc((void **)&g->d_assembled, sizeof(float) * 3 * frame_px);
         if (e != hipSuccess) { (void)hipGetLastError(); c->set_error("evplp_group_denoise: %s", hipGetErrorString(e)); return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP; }
-        evplp::launch_assemble_strips(c->st, g->n, g->owner.empty() ? nullptr : g->d_owner, (int)(g->strip_floats / ((size_t)c->st.W * 3)), g->d_dn_recv[0],
-                                      (float *)g->d_dn_frame, c->stream, evplp::kDenoiseFloats);
+        assemble_strips(g, g->d_dn_recv[0], (float *)g->d_dn_frame, evplp::kDenoiseFloats);
         frame = g->d_dn_frame; rows = c->st.H; out = g->d_assembled;
     }
     int rc;
-    if (cmd.i[1]) {            // evplp_group_denoise_temporal: the accumulation stage in front of the passes (i[2] = max_history, f[3] = normal_cos, u[0] = the texels' rank)
+    if (temporal) {            // the accumulation stage in front of the passes
         const evplp::TemporalPrev *prev = c->d_tp_prev;
         if (!g->iterations) {
             if (!c->d_tp_prev_frame) e = hipMalloc((void **)&c->d_tp_prev_frame, sizeof(evplp::TemporalPrev) * frame_px);
             if (e != hipSuccess) { (void)hipGetLastError(); c->d_tp_prev_frame = nullptr; c->set_error("evplp_group_denoise_temporal: %s", hipGetErrorString(e)); return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP; }
-            evplp::launch_assemble_strips(c->st, g->n, g->owner.empty() ? nullptr : g->d_owner, (int)(g->strip_floats / ((size_t)c->st.W * 3)), g->d_tp_recv[0],
-                                          (float *)c->d_tp_prev_frame, c->stream, evplp::kTemporalPrevFloats);
+            assemble_strips(g, g->d_tp_recv[0], (float *)c->d_tp_prev_frame, evplp::kTemporalPrevFloats);
             prev = c->d_tp_prev_frame;
-        } else if (cmd.u[0] != 0) {
-            const evplp_context *src = g->ctx[(size_t)cmd.u[0]];
+        } else if (texels_rank != 0) {
+            const evplp_context *src = g->ctx[(size_t)texels_rank];
             prev = src->d_tp_prev;
-            if (g->device[(size_t)cmd.u[0]] != g->device[0]) {
-                e = hipMemcpyPeerAsync(c->d_tp_prev, g->device[0], src->d_tp_prev, g->device[(size_t)cmd.u[0]], sizeof(evplp::TemporalPrev) * g->plane_px, c->stream);
-                if (e != hipSuccess) { (void)hipGetLastError(); c->set_error("evplp_group_denoise_temporal: texels of rank %u: %s", cmd.u[0], hipGetErrorString(e)); return EVPLP_ERR_HIP; }
+            if (g->device[(size_t)texels_rank] != g->device[0]) {
+                e = hipMemcpyPeerAsync(c->d_tp_prev, g->device[0], src->d_tp_prev, g->device[(size_t)texels_rank], sizeof(evplp::TemporalPrev) * g->plane_px, c->stream);
+                if (e != hipSuccess) { (void)hipGetLastError(); c->set_error("evplp_group_denoise_temporal: texels of rank %u: %s", (unsigned)texels_rank, hipGetErrorString(e)); return EVPLP_ERR_HIP; }
                 prev = c->d_tp_prev;
             }
         }
-        const evplp::TemporalSettings ts{ cmd.i[2], cmd.f[3] };
         if ((rc = evplp::temporal_accumulate(c, const_cast<evplp::DenoisePixel *>(frame), prev, rows, ds, ts, c->bounding_radius)) < 0) return rc;
     }
     rc = evplp::denoise_filter(c, frame, rows, ds, c->bounding_radius, out);
     if (rc < 0) return rc;
-    e = hipMemcpyAsync(cmd.out, out, sizeof(float) * 3 * frame_px, hipMemcpyDeviceToHost, c->stream);     // (rows 0 .. H - 1 in image order)
+    e = hipMemcpyAsync(out_rgb, out, sizeof(float) * 3 * frame_px, hipMemcpyDeviceToHost, c->stream);     // (rows 0 .. H - 1 in image order)
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) { c->set_error("evplp_group_denoise: %s", hipGetErrorString(e)); return EVPLP_ERR_HIP; }
     return EVPLP_OK;
 }
-static void worker_run(Worker *w, const Cmd &cmd) {
-    if (cmd.op == OP_REDUCE) { worker_reduce(w, cmd); return; }
-    if (cmd.op == OP_NOISE_POOL) { worker_noise_pool(w); return; }
-    evplp_group *g = w->g; const int r = w->rank; evplp_context *c = g->ctx[(size_t)r];
-    const bool collective = ((cmd.op == OP_PRESENT || cmd.op == OP_NOISE_VARIANCE || cmd.op == OP_DENOISE_PREP) && cmd.i[3] != 0) || (cmd.op == OP_TRACE && g->split_paths);
-    int rc = EVPLP_OK;
+
+// ------------------------------------------------------------------------------------------------ a posted command
+// `run(w)` is the rank's call: skipped when the rank has failed, its negative return is the rank's failure (with the context's message),
+// its time goes to t_calls.  `always(w)` is the collective the command ends in, stated by the wrapper that posts it: EVERY rank reaches it,
+// failed or not (the barrier inside decides for all), and its time goes to t_exchange -- which nothing else touches.
+template <class Run> static double run_stage(Worker &w, const Run &run) {
     const double t0 = now_ms();
-    if (w->status.load(std::memory_order_relaxed) == 0) {
-        switch (cmd.op) {
-        case OP_CLEAR: rc = evplp_clear_accumulators(c); break;
-        case OP_SYNC: rc = evplp_synchronize(c); break;
-        case OP_PRIMARY: rc = evplp_primary(c, cmd.f, cmd.i[0]); break;
-        case OP_TRACE:
-            if (!g->split_paths) rc = evplp_trace_light_paths(c, cmd.u[0], 0, c->cfg.num_light_paths);
-            else {
-                // in place: rank r's own slice goes to offset r * chunk of its record buffer.  A partial path range never goes to the second
-                // record buffer of overlap_light_tracing (context.cpp only double-buffers whole path sets), so EVPLP_BUF_RECORDS must be the
-                // same buffer before and after the call -- checked, because the exchange below would otherwise gather the wrong buffer.
-                const void *before = c->buf[EVPLP_BUF_RECORDS];
-                rc = evplp_trace_light_paths(c, cmd.u[0], (uint32_t)r * g->per_rank_paths, g->per_rank_paths);
-                if (rc >= 0 && c->buf[EVPLP_BUF_RECORDS] != before) worker_fail(w, EVPLP_ERR_INVALID, "evplp_group_trace_light_paths: a partial path range went into a flipped record buffer");
-            }
-            break;
-        case OP_GATHER: rc = cmd.i[0] == 0 ? evplp_gather_vpl(c, &cmd.fp) : cmd.i[0] == 1 ? evplp_gather_vsl(c, &cmd.fp) : evplp_gather_lvc(c, &cmd.fp); break;
-        case OP_SPLAT: rc = evplp_splat_photons(c, &cmd.fp, cmd.i[0]); break;
-        case OP_PATH_TRACE: rc = evplp_path_trace(c, cmd.f, cmd.u[0], cmd.u[1], cmd.i[0]); break;
-        case OP_PATH_TRACE_BATCH: rc = evplp_path_trace_batch(c, cmd.f, cmd.i[0], &cmd.batch->jitter[0][0], cmd.batch->seed, cmd.u[1]); break;
-        case OP_PRESENT: rc = evplp::resolve_to_device(c, cmd.f[0], cmd.f[1], cmd.f[2], cmd.i[0], cmd.i[1], cmd.i[2] != 0 || !c->aux_stream, cmd.u[0] == 0); break;   // (u[0]: the composite evplp_group_frame_error measures)
-        case OP_LOAD_SCENE: rc = evplp_load_scene_json(c, (const char *)cmd.p0); break;
-        case OP_SET_PROXY: rc = evplp_set_splat_proxy(c, (const float *)cmd.p0, cmd.i[0], (const int32_t *)cmd.p1, cmd.i[1]); break;
-        case OP_UPDATE_MESH: rc = evplp_update_mesh(c, cmd.i[0], (const float *)cmd.p0, cmd.i[1]); break;
-        case OP_TRANSFORM_MESH: rc = evplp_transform_mesh(c, cmd.i[0], (const float *)cmd.p0); break;
-        case OP_SET_MESH_SKIN: rc = evplp_set_mesh_skin(c, cmd.i[0], cmd.i[1], (const int32_t *)cmd.p0, (const float *)cmd.p1, cmd.i[2]); break;
-        case OP_POSE_MESH: rc = evplp::pose_mesh_apply(c, cmd.i[0], (const float *)cmd.p0, cmd.i[1], (const float *)cmd.p1); break;   // (checked, and skinned once, by the caller's thread)
-        case OP_SET_MESH_MORPH: rc = evplp_set_mesh_morph(c, cmd.i[0], cmd.i[1], (const float *)cmd.p0, cmd.i[2]); break;
-        // (checked, and morphed once, by the caller's thread: p1 = the base, then the positions, i[2] floats each)
-        case OP_MORPH_MESH: rc = evplp::morph_mesh_apply(c, cmd.i[0], (const float *)cmd.p0, cmd.i[1], (const float *)cmd.p1, (const float *)cmd.p1 + cmd.i[2]); break;
-        case OP_REFIT: rc = evplp_refit_accel(c); break;
-        case OP_ACCEL_QUALITY: rc = evplp_accel_quality(c, (struct evplp_accel_quality *)cmd.out + w->rank); break;      // (out: one record per rank, the caller's)
-        case OP_REFIT_POLICY: rc = evplp_set_refit_policy(c, cmd.d, cmd.i[0]); break;
-        case OP_OPTIMIZE_ACCEL: rc = evplp_optimize_accel(c, cmd.i[0], (int32_t *)cmd.out + w->rank); break;          // (out: one count per rank, the caller's)
-        case OP_REFIT_ROTATIONS: rc = evplp_set_refit_rotations(c, cmd.i[0]); break;
-        case OP_SET_REFERENCE: rc = evplp_set_error_reference(c, (const float *)cmd.p0, (const uint8_t *)cmd.p1); break;
-        case OP_FRAME_ERROR: rc = evplp::frame_error_rows(c); break;          // (behind this rank's composite, on its stream)
-        case OP_NOISE_TRACK: rc = evplp_noise_track(c, cmd.i[0], (const uint8_t *)cmd.p0); break;
-        case OP_NOISE_FOLD: rc = evplp_noise_fold(c, cmd.i[0]); break;
-        // i[1] = 1: rank 0's moments pooled over the ranks (OP_NOISE_POOL before), with the summed light plane of the reduction
-        case OP_NOISE_ROWS:
-            if (cmd.i[1]) rc = evplp::noise_rows(c, noise_pooled(g, c), g->d_sum[0] + 2 * g->plane_px, g->pool_k, g->pool_b, cmd.f[0], cmd.f[1], cmd.i[0]);
-            else rc = evplp::noise_rows(c, evplp::noise_moments_of(c), (const float4 *)c->buf[EVPLP_BUF_LIGHT], (double)c->noise_k, (double)c->noise_b, cmd.f[0], cmd.f[1], cmd.i[0]);
-            break;
-        case OP_ADAPT_ENABLE: rc = cmd.i[1] ? evplp_adaptive_enable_pt(c, cmd.i[0]) : evplp_adaptive_enable(c, cmd.i[0]); break;
-        // (the count of tiles it retired stays in c->adapt_last)
-        case OP_ADAPT_RETIRE: rc = evplp_adaptive_retire(c, cmd.f[0], cmd.f[1], cmd.i[0], cmd.d, cmd.i[1]); if (rc > 0) rc = EVPLP_OK; break;
-        // (every rank takes its own tiles from / puts them into the caller's whole-image array, which outlives the drain)
-        case OP_ADAPT_SET_BUDGETS: rc = evplp_adaptive_set_budgets(c, (const int32_t *)cmd.p0, cmd.i[0]); break;
-        case OP_ADAPT_TILE_NOISE: rc = evplp::adaptive_tile_noise_into(c, cmd.f[0], cmd.f[1], cmd.i[0], (double *)cmd.out); break;
-        case OP_NOISE_VARIANCE:
-            if (cmd.i[1]) rc = evplp::noise_variance_to_device(c, noise_pooled(g, c), g->pool_k, g->pool_b, cmd.f[0]);
-            else rc = evplp::noise_variance_to_device(c, evplp::noise_moments_of(c), (double)c->noise_k, (double)c->noise_b, cmd.f[0]);
-            if (rc >= 0 && cmd.i[2]) rc = evplp::denoise_keep_variance(c);        // (i[2]: evplp_group_denoise's variance)
-            break;
-        case OP_DENOISE_PREP: rc = worker_denoise_prep(w, cmd); break;
-        case OP_DENOISE_FILTER: rc = worker_denoise_filter(w, cmd); break;
-        case OP_TEMPORAL_ENABLE: rc = evplp::temporal_enable(c, cmd.i[0]); break;
-        case OP_TEMPORAL_RESET: evplp::temporal_forget(c); break;
-        // (iterations: the rank of the last primary; it waits, so that rank 0 -- behind the reduction's barrier -- reads finished texels)
-        case OP_TEMPORAL_POSE: rc = worker_temporal_pose(c); if (rc >= 0) rc = evplp_synchronize(c); break;
-        case OP_TEMPORAL_SNAPSHOT: rc = evplp::temporal_snapshot(c); break;
-        case OP_ASSEMBLE: {
-            // rank 0 puts the strips into image order on the device; one copy lands the frame in the caller's buffer (no host-side assembly:
-            // a run that writes every frame resolves every iteration)
-            hipSetDevice(g->device[0]);
-            const size_t frame_floats = (size_t)c->st.W * c->st.H * 3;
-            hipError_t e = hipSuccess;
-            if (g->iterations) e = hipMemcpyAsync(cmd.out, c->d_rgb, frame_floats * sizeof(float), hipMemcpyDeviceToHost, c->stream);   // (whole-image ranks: rows in image order)
-            else if (!g->d_assembled) e = hipMalloc((void **)&g->d_assembled, sizeof(float) * frame_floats);
-            if (e == hipSuccess && !g->iterations) {
-                evplp::launch_assemble_strips(c->st, g->n, g->owner.empty() ? nullptr : g->d_owner, (int)(g->strip_floats / ((size_t)c->st.W * 3)), g->d_frame[0], g->d_assembled, c->stream);
-                e = hipMemcpyAsync(cmd.out, g->d_assembled, frame_floats * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-            }
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-            if (e != hipSuccess) worker_fail(w, e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP, hipGetErrorString(e));
-            break;
-        }
-        default: break;
-        }
-        if (rc < 0) worker_fail(w, rc, evplp_last_error(c));
-    }
+    if (w.ok()) { const int rc = run(w); if (rc < 0) w.fail(rc, evplp_last_error(w.c)); }
     const double t1 = now_ms();
-    w->t_calls += t1 - t0; w->n_cmds++;
-    if (collective) {          // (reached by every rank, failed or not: the barrier inside decides for all)
-        std::vector<const float *> all((size_t)g->n);
-        if (cmd.op == OP_TRACE) {
-            const size_t chunk = (size_t)g->per_rank_paths * c->cfg.photons_per_path * (sizeof(evplp_record) / sizeof(float));
-            for (int q = 0; q < g->n; q++) all[(size_t)q] = (const float *)g->ctx[(size_t)q]->buf[EVPLP_BUF_RECORDS] + (size_t)q * chunk;
-            worker_all_gather(w, (float *)c->buf[EVPLP_BUF_RECORDS], chunk, all);
-        } else if (cmd.op == OP_DENOISE_PREP) {          // (the packed pixels of the rows an exchange moves)
-            for (int q = 0; q < g->n; q++) all[(size_t)q] = (const float *)g->ctx[(size_t)q]->d_dn_pack;
-            worker_all_gather(w, g->d_dn_recv[(size_t)r], g->strip_floats / 3 * evplp::kDenoiseFloats, all);
-            if (cmd.i[1]) {                               // (... and their previous-pose texels)
-                for (int q = 0; q < g->n; q++) all[(size_t)q] = (const float *)g->ctx[(size_t)q]->d_tp_prev;
-                worker_all_gather(w, g->d_tp_recv[(size_t)r], g->strip_floats / 3 * evplp::kTemporalPrevFloats, all);
-            }
-        } else {
-            for (int q = 0; q < g->n; q++) all[(size_t)q] = g->ctx[(size_t)q]->d_rgb;
-            worker_all_gather(w, g->d_frame[(size_t)r], g->strip_floats, all);
+    w.t_calls += t1 - t0; w.n_cmds++;
+    return t1;
+}
+template <class Run> static Task command(Run run) { return Task([run](Worker &w) { run_stage(w, run); return 0; }); }
+template <class Run, class Always> static Task command(Run run, Always always) {
+    return Task([run, always](Worker &w) { const double t1 = run_stage(w, run); always(w); w.t_exchange += now_ms() - t1; return 0; });
+}
+// The commands that are posted from several places.  A rank's composite (as_pass = false: the one evplp_group_frame_error and
+// evplp_group_noise_estimate measure); with `exchange` the strips are all-gathered behind it, so that every GPU holds the frame:
+// the per-frame exchange of a run that presents every frame; nothing comes to the host.
+static Task present(float vs, float ps, float ls, int32_t mask_emitter, int32_t gamma, bool settle, bool exchange, bool as_pass = true) {
+    auto run = [=](Worker &w) { return evplp::resolve_to_device(w.c, vs, ps, ls, mask_emitter, gamma, settle || !w.c->aux_stream, as_pass); };
+    return exchange ? command(run, exchange_strips) : command(run);
+}
+// the variance into the rank's d_rgb -- of its own moments, or (pooled: rank 0, behind noise_pool) of the ranks' pooled ones; keep: it is
+// evplp_group_denoise's; exchange: all-gathered as a present's composite is
+static Task noise_variance(float scale, bool pooled, bool keep, bool exchange) {
+    auto run = [=](Worker &w) {
+        evplp_context *c = w.c;
+        int rc = pooled ? evplp::noise_variance_to_device(c, noise_pooled(w.g, c), w.g->pool_k, w.g->pool_b, scale)
+                        : evplp::noise_variance_to_device(c, evplp::noise_moments_of(c), (double)c->noise_k, (double)c->noise_b, scale);
+        if (rc >= 0 && keep) rc = evplp::denoise_keep_variance(c);
+        return rc;
+    };
+    return exchange ? command(run, exchange_strips) : command(run);
+}
+static Task noise_pool() { return Task([](Worker &w) { worker_noise_pool(&w); return 0; }); }
+static Task synchronize() { return command([](Worker &w) { return evplp_synchronize(w.c); }); }
+// rank 0 puts the strips into image order on the device; one copy lands the frame in the caller's buffer (no host-side assembly: a run that
+// writes every frame resolves every iteration)
+static Task assemble(float *out_rgb) {
+    return command([out_rgb](Worker &w) {
+        evplp_group *g = w.g; evplp_context *c = w.c;
+        hipSetDevice(g->device[0]);
+        const size_t frame_floats = (size_t)c->st.W * c->st.H * 3;
+        hipError_t e = hipSuccess;
+        if (g->iterations) e = hipMemcpyAsync(out_rgb, c->d_rgb, frame_floats * sizeof(float), hipMemcpyDeviceToHost, c->stream);   // (whole-image ranks: rows in image order)
+        else if (!g->d_assembled) e = hipMalloc((void **)&g->d_assembled, sizeof(float) * frame_floats);
+        if (e == hipSuccess && !g->iterations) {
+            assemble_strips(g, g->d_frame[0], g->d_assembled);
+            e = hipMemcpyAsync(out_rgb, g->d_assembled, frame_floats * sizeof(float), hipMemcpyDeviceToHost, c->stream);
         }
-        w->t_exchange += now_ms() - t1;
-    }
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) w.hip_fail(e);
+        return EVPLP_OK;
+    });
 }
 
 static void worker_main(Worker *w) {
     hipSetDevice(w->g->device[(size_t)w->rank]);
-    for (;;) {
-        const uint64_t h = w->head.load(std::memory_order_relaxed);
-        int spins = 0;
-        while (w->tail.load(std::memory_order_acquire) == h) {
-            if (++spins < kSpinBeforeSleep) { if ((spins & 63) == 0) std::this_thread::yield(); continue; }
-            std::unique_lock<std::mutex> lk(w->m);
-            w->sleeping = true;
-            w->cv.wait(lk, [&] { return w->tail.load(std::memory_order_acquire) != h; });
-            w->sleeping = false;
-            spins = 0;
-        }
-        const Cmd cmd = w->ring[h % kRing];
-        if (cmd.op == OP_QUIT) { w->head.store(h + 1, std::memory_order_release); return; }
-        worker_run(w, cmd);
-        w->head.store(h + 1, std::memory_order_release);
-    }
+    w->ring.consume(*w);
 }
-static void post(Worker *w, const Cmd &cmd) {
-    const uint64_t t = w->tail.load(std::memory_order_relaxed);
-    while (t - w->head.load(std::memory_order_acquire) >= (uint64_t)kRing) std::this_thread::yield();      // (the ring is full: the caller is 64 calls ahead)
-    w->ring[t % kRing] = cmd;
-    w->tail.store(t + 1, std::memory_order_seq_cst);
-    std::lock_guard<std::mutex> lk(w->m);                  // (uncontended while the worker polls; pairs with the worker's check before it sleeps)
-    if (w->sleeping) w->cv.notify_one();
-}
-static void drain_one(Worker *w) { int spins = 0; while (w->head.load(std::memory_order_acquire) != w->tail.load(std::memory_order_acquire)) { if (++spins > 1000) std::this_thread::yield(); } }
-static void drain(evplp_group *g) { for (Worker *w : g->workers) drain_one(w); }
-static void quiesce_hook(void *arg) { drain_one((Worker *)arg); }
+static void post(Worker *w, const Task &task) { w->ring.post(task); }
+static void drain(evplp_group *g) { for (Worker *w : g->workers) w->ring.drain(); }
+static void quiesce_hook(void *arg) { ((Worker *)arg)->ring.drain(); }
 // the sticky error of the group, if any: the lowest failing rank's
 static int group_status(evplp_group *g) {
     for (Worker *w : g->workers) { const int st = w->status.load(std::memory_order_acquire); if (st < 0) { g->set_error("rank %d: %s", w->rank, w->error); return st; } }
     return EVPLP_OK;
 }
-static int post_all(evplp_group *g, const Cmd &cmd) {
+// a failed group takes no new command: the workers finish what they have and the call reports the failure
+static int post_all(evplp_group *g, const Task &task) {
     if (g->failed.load(std::memory_order_acquire)) { drain(g); return group_status(g); }
-    for (Worker *w : g->workers) post(w, cmd);
+    for (Worker *w : g->workers) post(w, task);
+    return EVPLP_OK;
+}
+static int post_one(evplp_group *g, int rank, const Task &task) {
+    if (g->failed.load(std::memory_order_acquire)) { drain(g); return group_status(g); }
+    post(g->workers[(size_t)rank], task);
     return EVPLP_OK;
 }
 // a pass call: every rank (strips), or the selected rank alone (EVPLP_PARTITION_ITERATIONS; the cached sums are stale from here on)
-static int post_pass(evplp_group *g, const Cmd &cmd) {
+static int post_pass(evplp_group *g, const Task &task) {
     // (refused here, on the caller's thread, so that a forgotten refit is not a sticky worker failure; the flag only changes in calls that wait)
     if (g->ctx[0]->scene_dirty) { g->set_error("vertices were updated (evplp_group_update_mesh): call evplp_group_refit_accel, or evplp_build_accel on every rank, first"); return EVPLP_ERR_INVALID; }
-    if (!g->iterations) return post_all(g, cmd);
+    if (!g->iterations) return post_all(g, task);
     g->sums_fresh = false;
-    if (g->failed.load(std::memory_order_acquire)) { drain(g); return group_status(g); }
-    post(g->workers[(size_t)g->selected], cmd);
-    return EVPLP_OK;
+    return post_one(g, g->selected, task);
 }
 // calls whose arguments must outlive them, or whose result the caller needs: post, wait until every worker is idle, report
-static int post_and_wait(evplp_group *g, const Cmd &cmd) {
-    int rc = post_all(g, cmd);
+static int post_and_wait(evplp_group *g, const Task &task) {
+    int rc = post_all(g, task);
     if (rc < 0) return rc;
     drain(g);
     return group_status(g);
 }
+// The mesh, refit and tree calls go to every rank (each holds the whole scene, in both partitions).  What the context refuses without
+// touching a device is refused here first -- once the workers are idle, against rank 0's copy (the ranks' scenes are the same), with the
+// context's own message -- so that a refusal is not a sticky worker failure.
+template <class Check> static int rank0_refuses(evplp_group *g, Check check) {
+    drain(g);
+    if (check(g->ctx[0])) return EVPLP_OK;
+    g->set_error("%s", g->ctx[0]->error);
+    return EVPLP_ERR_INVALID;
+}
 
+struct Vec3 { float v[3]; };
 #define GRP_CHECK(g) do { if (!(g)) return EVPLP_ERR_INVALID; } while (0)
 // What a pass call can refuse without touching a device is refused HERE, on the caller's thread, at once -- as the plain context does -- and
 // leaves the group usable; only failures of the device side are sticky.  (The configuration is the same on every rank and never changes.)
@@ -616,16 +548,15 @@ extern "C" int evplp_group_select_rank(evplp_group *g, int32_t rank) {
 extern "C" int evplp_group_synchronize_rank(evplp_group *g, int32_t rank) {
     GRP_CHECK(g);
     if (rank < 0 || rank >= g->n) { g->set_error("evplp_group_synchronize_rank: rank %d out of range (%d ranks)", rank, g->n); return EVPLP_ERR_INVALID; }
-    if (g->failed.load(std::memory_order_acquire)) { drain(g); return group_status(g); }
-    Cmd c; c.op = OP_SYNC;
-    post(g->workers[(size_t)rank], c);
-    drain_one(g->workers[(size_t)rank]);
+    const int rc = post_one(g, rank, synchronize());
+    if (rc < 0) return rc;
+    g->workers[(size_t)rank]->ring.drain();
     return group_status(g);
 }
 extern "C" int evplp_group_host_stats(evplp_group *g, int32_t rank, double out[3]) {
     GRP_CHECK(g);
     if (rank < 0 || rank >= g->n || !out) { g->set_error("evplp_group_host_stats: bad arguments"); return EVPLP_ERR_INVALID; }
-    drain_one(g->workers[(size_t)rank]);
+    g->workers[(size_t)rank]->ring.drain();
     out[0] = g->workers[(size_t)rank]->t_calls; out[1] = g->workers[(size_t)rank]->t_exchange; out[2] = (double)g->workers[(size_t)rank]->n_cmds;
     return EVPLP_OK;
 }
@@ -639,7 +570,7 @@ extern "C" int evplp_group_profile_passes(evplp_group *g, int32_t on) {
 
 extern "C" void evplp_group_destroy(evplp_group *g) {
     if (!g) return;
-    for (Worker *w : g->workers) if (w->th.joinable()) { Cmd q; q.op = OP_QUIT; post(w, q); }
+    for (Worker *w : g->workers) if (w->th.joinable()) post(w, Task([](Worker &) { return 1; }));      // (non-zero: the worker's loop ends)
     for (Worker *w : g->workers) { if (w->th.joinable()) w->th.join(); delete w; }
     g->workers.clear();
     for (int r = 0; r < (int)g->d_frame.size(); r++) if (g->d_frame[(size_t)r]) { hipSetDevice(g->device[(size_t)r]); hipFree(g->d_frame[(size_t)r]); }
@@ -723,11 +654,10 @@ extern "C" int evplp_group_create(const evplp_config *cfg, const evplp_group_con
                      (gc->split_light_paths > 0 || (gc->split_light_paths == 0 && evplp_group_split_model(cfg->num_light_paths, cfg->photons_per_path, g->n, nullptr) == 1));
     g->per_rank_paths = g->split_paths ? cfg->num_light_paths / (uint32_t)g->n : cfg->num_light_paths;
     g->barrier.n = g->n;
-    for (int r = 0; r < g->n; r++) { Worker *w = new Worker(); w->g = g; w->rank = r; g->workers.push_back(w); }
+    for (int r = 0; r < g->n; r++) { Worker *w = new Worker(); w->g = g; w->rank = r; w->c = g->ctx[(size_t)r]; g->workers.push_back(w); }
     for (Worker *w : g->workers) {
         w->th = std::thread(worker_main, w);
-        evplp_context *c = g->ctx[(size_t)w->rank];
-        c->worker_tid = w->th.get_id(); c->quiesce_arg = w; c->quiesce = quiesce_hook;
+        w->c->worker_tid = w->th.get_id(); w->c->quiesce_arg = w; w->c->quiesce = quiesce_hook;
     }
     *out = g;
     return EVPLP_OK;
@@ -814,16 +744,34 @@ extern "C" int evplp_group_block_owners(evplp_group *g, int32_t *owner_rank, int
     return g->image_blocks;
 }
 
-extern "C" int evplp_group_load_scene_json(evplp_group *g, const char *json_path) { GRP_CHECK(g); g->sums_fresh = false; Cmd c; c.op = OP_LOAD_SCENE; c.p0 = json_path; return post_and_wait(g, c); }
-extern "C" int evplp_group_clear_accumulators(evplp_group *g) { GRP_CHECK(g); g->sums_fresh = false; Cmd c; c.op = OP_CLEAR; return post_all(g, c); }
-extern "C" int evplp_group_synchronize(evplp_group *g) { GRP_CHECK(g); Cmd c; c.op = OP_SYNC; return post_and_wait(g, c); }
+extern "C" int evplp_group_load_scene_json(evplp_group *g, const char *json_path) {
+    GRP_CHECK(g);
+    g->sums_fresh = false;
+    return post_and_wait(g, command([json_path](Worker &w) { return evplp_load_scene_json(w.c, json_path); }));
+}
+extern "C" int evplp_group_clear_accumulators(evplp_group *g) { GRP_CHECK(g); g->sums_fresh = false; return post_all(g, command([](Worker &w) { return evplp_clear_accumulators(w.c); })); }
+extern "C" int evplp_group_synchronize(evplp_group *g) { GRP_CHECK(g); return post_and_wait(g, synchronize()); }
 extern "C" int evplp_group_primary(evplp_group *g, const float jitter[2], int32_t light_flags) {
     GRP_CHECK(g);
-    Cmd c; c.op = OP_PRIMARY; c.f[0] = jitter ? jitter[0] : 0.f; c.f[1] = jitter ? jitter[1] : 0.f; c.i[0] = light_flags;
+    const float jx = jitter ? jitter[0] : 0.f, jy = jitter ? jitter[1] : 0.f;
     if (g->iterations) g->last_primary = g->selected;          // (whose G-buffer evplp_group_denoise reads)
-    return post_pass(g, c);
+    return post_pass(g, command([jx, jy, light_flags](Worker &w) { const float j[2] = { jx, jy }; return evplp_primary(w.c, j, light_flags); }));
 }
-extern "C" int evplp_group_trace_light_paths(evplp_group *g, uint32_t rng_seed) { GRP_CHECK(g); Cmd c; c.op = OP_TRACE; c.u[0] = rng_seed; return post_pass(g, c); }
+extern "C" int evplp_group_trace_light_paths(evplp_group *g, uint32_t rng_seed) {
+    GRP_CHECK(g);
+    if (!g->split_paths) return post_pass(g, command([rng_seed](Worker &w) { return evplp_trace_light_paths(w.c, rng_seed, 0, w.c->cfg.num_light_paths); }));
+    // every rank traces its own path range and the records are all-gathered in place: rank r's slice goes to offset r * chunk of its record
+    // buffer.  A partial path range never goes to the second record buffer of overlap_light_tracing (context.cpp only double-buffers whole path
+    // sets), so EVPLP_BUF_RECORDS must be the same buffer before and after the call -- checked, because the exchange would otherwise gather
+    // the wrong buffer.
+    return post_pass(g, command([rng_seed](Worker &w) {
+        evplp_context *c = w.c; const uint32_t per_rank_paths = w.g->per_rank_paths;
+        const void *before = c->buf[EVPLP_BUF_RECORDS];
+        const int rc = evplp_trace_light_paths(c, rng_seed, (uint32_t)w.rank * per_rank_paths, per_rank_paths);
+        if (rc >= 0 && c->buf[EVPLP_BUF_RECORDS] != before) w.fail(EVPLP_ERR_INVALID, "evplp_group_trace_light_paths: a partial path range went into a flipped record buffer");
+        return rc;
+    }, exchange_records));
+}
 extern "C" int evplp_group_gather(evplp_group *g, const evplp_frame_params *fp, int32_t kind) {
     GRP_CHECK(g);
     if (kind < 0 || kind > 2) { g->set_error("evplp_group_gather: kind must be 0 (VPL), 1 (VSL) or 2 (light-path windows)"); return EVPLP_ERR_INVALID; }
@@ -833,98 +781,79 @@ extern "C" int evplp_group_gather(evplp_group *g, const evplp_frame_params *fp, 
     if (g->adapt_on && (kind == 2 || fp->do_accumulate == 0)) {
         g->set_error("evplp_group_gather: adaptivity is on (evplp_group_adaptive_enable): accumulating VPL and VSL gathers only"); return EVPLP_ERR_INVALID;
     }
-    Cmd c; c.op = OP_GATHER; c.fp = *fp; c.i[0] = kind;
-    return post_pass(g, c);
+    return post_pass(g, command([params = *fp, kind](Worker &w) { return kind == 0 ? evplp_gather_vpl(w.c, &params) : kind == 1 ? evplp_gather_vsl(w.c, &params) : evplp_gather_lvc(w.c, &params); }));
 }
 extern "C" int evplp_group_splat_photons(evplp_group *g, const evplp_frame_params *fp, int32_t clear) {
     GRP_CHECK(g);
     if (!fp) { g->set_error("evplp_group_splat_photons: null frame params"); return EVPLP_ERR_INVALID; }
     { int rc = check_frame_params(g, fp, "evplp_group_splat_photons", true); if (rc < 0) return rc; }
     if (g->adapt_gather_budget) { g->set_error("evplp_group_splat_photons: gather budget mode (evplp_group_adaptive_enable(g, 2)): one set of moments cannot price n_t VPL samples and N photon passes"); return EVPLP_ERR_INVALID; }
-    Cmd c; c.op = OP_SPLAT; c.fp = *fp; c.i[0] = clear;
-    return post_pass(g, c);
+    return post_pass(g, command([params = *fp, clear](Worker &w) { return evplp_splat_photons(w.c, &params, clear); }));
 }
 extern "C" int evplp_group_set_splat_proxy(evplp_group *g, const float *vertices, int32_t nverts, const int32_t *indices, int32_t ntris) {
     GRP_CHECK(g);
-    Cmd c; c.op = OP_SET_PROXY; c.p0 = vertices; c.p1 = indices; c.i[0] = nverts; c.i[1] = ntris;
-    return post_and_wait(g, c);
+    return post_and_wait(g, command([=](Worker &w) { return evplp_set_splat_proxy(w.c, vertices, nverts, indices, ntris); }));
 }
-// Every rank holds the whole scene (both partitions): the update and the refit go to all of them.  What the context refuses without touching
-// a device is refused here first, against rank 0's copy (the ranks' scenes are the same), so that a refusal is not a sticky worker failure.
 extern "C" int evplp_group_update_mesh(evplp_group *g, int32_t mesh, const float *vertices, int32_t nverts) {
     GRP_CHECK(g);
-    drain(g);
-    if (!evplp::update_mesh_check(g->ctx[0], mesh, vertices, nverts)) { g->set_error("%s", g->ctx[0]->error); return EVPLP_ERR_INVALID; }
+    if (int rc = rank0_refuses(g, [&](evplp_context *c0) { return evplp::update_mesh_check(c0, mesh, vertices, nverts); })) return rc;
     g->sums_fresh = false;
-    Cmd c; c.op = OP_UPDATE_MESH; c.p0 = vertices; c.i[0] = mesh; c.i[1] = nverts;
-    return post_and_wait(g, c);
+    return post_and_wait(g, command([=](Worker &w) { return evplp_update_mesh(w.c, mesh, vertices, nverts); }));
 }
 extern "C" int evplp_group_transform_mesh(evplp_group *g, int32_t mesh, const float *m) {
     GRP_CHECK(g);
-    drain(g);
-    if (!evplp::transform_mesh_check(g->ctx[0], mesh, m)) { g->set_error("%s", g->ctx[0]->error); return EVPLP_ERR_INVALID; }
+    if (int rc = rank0_refuses(g, [&](evplp_context *c0) { return evplp::transform_mesh_check(c0, mesh, m); })) return rc;
     g->sums_fresh = false;
-    Cmd c; c.op = OP_TRANSFORM_MESH; c.p0 = m; c.i[0] = mesh;
-    return post_and_wait(g, c);
+    return post_and_wait(g, command([=](Worker &w) { return evplp_transform_mesh(w.c, mesh, m); }));
 }
 // (the skin and the palette are copied by every rank before the call returns: it waits for the workers)
 extern "C" int evplp_group_set_mesh_skin(evplp_group *g, int32_t mesh, int32_t nbones, const int32_t *bone_index, const float *weight, int32_t nverts) {
     GRP_CHECK(g);
-    drain(g);
-    if (!evplp::set_mesh_skin_check(g->ctx[0], mesh, nbones, bone_index, weight, nverts)) { g->set_error("%s", g->ctx[0]->error); return EVPLP_ERR_INVALID; }
-    Cmd c; c.op = OP_SET_MESH_SKIN; c.p0 = bone_index; c.p1 = weight; c.i[0] = mesh; c.i[1] = nbones; c.i[2] = nverts;
-    return post_and_wait(g, c);
+    if (int rc = rank0_refuses(g, [&](evplp_context *c0) { return evplp::set_mesh_skin_check(c0, mesh, nbones, bone_index, weight, nverts); })) return rc;
+    return post_and_wait(g, command([=](Worker &w) { return evplp_set_mesh_skin(w.c, mesh, nbones, bone_index, weight, nverts); }));
 }
 extern "C" int evplp_group_pose_mesh(evplp_group *g, int32_t mesh, const float *bone_matrices, int32_t nbones) {
     GRP_CHECK(g);
-    drain(g);
     std::vector<float> posed;           // (the check skins rank 0's rest pose; every rank takes these positions: the call waits for the workers)
-    if (!evplp::pose_mesh_check(g->ctx[0], mesh, bone_matrices, nbones, &posed)) { g->set_error("%s", g->ctx[0]->error); return EVPLP_ERR_INVALID; }
+    if (int rc = rank0_refuses(g, [&](evplp_context *c0) { return evplp::pose_mesh_check(c0, mesh, bone_matrices, nbones, &posed); })) return rc;
     g->sums_fresh = false;
-    Cmd c; c.op = OP_POSE_MESH; c.p0 = bone_matrices; c.p1 = posed.data(); c.i[0] = mesh; c.i[1] = nbones;
-    const int rc = post_and_wait(g, c);
+    const float *positions = posed.data();
+    const int rc = post_and_wait(g, command([=](Worker &w) { return evplp::pose_mesh_apply(w.c, mesh, bone_matrices, nbones, positions); }));
     drain(g);                           // (whatever the outcome, no worker reads `posed` behind this line)
     return rc;
 }
 // (the targets and the weights are copied by every rank before the call returns: it waits for the workers)
 extern "C" int evplp_group_set_mesh_morph(evplp_group *g, int32_t mesh, int32_t ntargets, const float *deltas, int32_t nverts) {
     GRP_CHECK(g);
-    drain(g);
-    if (!evplp::set_mesh_morph_check(g->ctx[0], mesh, ntargets, deltas, nverts)) { g->set_error("%s", g->ctx[0]->error); return EVPLP_ERR_INVALID; }
-    Cmd c; c.op = OP_SET_MESH_MORPH; c.p0 = deltas; c.i[0] = mesh; c.i[1] = ntargets; c.i[2] = nverts;
-    return post_and_wait(g, c);
+    if (int rc = rank0_refuses(g, [&](evplp_context *c0) { return evplp::set_mesh_morph_check(c0, mesh, ntargets, deltas, nverts); })) return rc;
+    return post_and_wait(g, command([=](Worker &w) { return evplp_set_mesh_morph(w.c, mesh, ntargets, deltas, nverts); }));
 }
 extern "C" int evplp_group_morph_mesh(evplp_group *g, int32_t mesh, const float *weights, int32_t ntargets) {
     GRP_CHECK(g);
-    drain(g);
     std::vector<float> base, moved;     // (the check morphs rank 0's rest pose; every rank takes these positions: the call waits for the workers)
-    if (!evplp::morph_mesh_check(g->ctx[0], mesh, weights, ntargets, &base, &moved)) { g->set_error("%s", g->ctx[0]->error); return EVPLP_ERR_INVALID; }
+    if (int rc = rank0_refuses(g, [&](evplp_context *c0) { return evplp::morph_mesh_check(c0, mesh, weights, ntargets, &base, &moved); })) return rc;
     g->sums_fresh = false;
-    const size_t n = moved.size();
-    base.resize(n); base.insert(base.end(), moved.begin(), moved.end());          // (one array: the base -- unused without weights --, then the positions)
-    Cmd c; c.op = OP_MORPH_MESH; c.p0 = weights; c.p1 = base.data(); c.i[0] = mesh; c.i[1] = ntargets; c.i[2] = (int32_t)n;
-    const int rc = post_and_wait(g, c);
+    base.resize(moved.size());          // (unused without weights)
+    const float *base_positions = base.data(), *positions = moved.data();
+    const int rc = post_and_wait(g, command([=](Worker &w) { return evplp::morph_mesh_apply(w.c, mesh, weights, ntargets, base_positions, positions); }));
     drain(g);                           // (whatever the outcome, no worker reads the positions behind this line)
     return rc;
 }
 extern "C" int evplp_group_refit_accel(evplp_group *g) {
     GRP_CHECK(g);
-    drain(g);
-    if (!evplp::refit_check(g->ctx[0])) { g->set_error("%s", g->ctx[0]->error); return EVPLP_ERR_INVALID; }
+    if (int rc = rank0_refuses(g, [&](evplp_context *c0) { return evplp::refit_check(c0); })) return rc;
     g->sums_fresh = false;
-    Cmd c; c.op = OP_REFIT;
-    return post_and_wait(g, c);
+    return post_and_wait(g, command([](Worker &w) { return evplp_refit_accel(w.c); }));
 }
 // The scene and the tree are replicated, so every rank measures the same doubles (and a policy decides the same on each): rank 0's are the
 // group's, and a rank that differs is an error.
 extern "C" int evplp_group_accel_quality(evplp_group *g, struct evplp_accel_quality *out) {
     GRP_CHECK(g);
     if (!out) { g->set_error("evplp_group_accel_quality: null destination"); return EVPLP_ERR_INVALID; }
-    drain(g);
-    if (!evplp::accel_quality_check(g->ctx[0], "evplp_group_accel_quality")) { g->set_error("%s", g->ctx[0]->error); return EVPLP_ERR_INVALID; }
-    std::vector<struct evplp_accel_quality> q((size_t)g->n);
-    Cmd c; c.op = OP_ACCEL_QUALITY; c.out = q.data();
-    const int rc = post_and_wait(g, c);
+    if (int rc = rank0_refuses(g, [&](evplp_context *c0) { return evplp::accel_quality_check(c0, "evplp_group_accel_quality"); })) return rc;
+    std::vector<struct evplp_accel_quality> q((size_t)g->n);            // (one record per rank)
+    struct evplp_accel_quality *per_rank = q.data();
+    const int rc = post_and_wait(g, command([per_rank](Worker &w) { return evplp_accel_quality(w.c, per_rank + w.rank); }));
     if (rc < 0) return rc;
     for (int r = 1; r < g->n; r++)
         if (std::memcmp(&q[(size_t)r], &q[0], 6 * sizeof(double)) != 0 || q[(size_t)r].last_action != q[0].last_action || q[(size_t)r].policy_rebuilds != q[0].policy_rebuilds) {
@@ -937,19 +866,16 @@ extern "C" int evplp_group_accel_quality(evplp_group *g, struct evplp_accel_qual
 }
 extern "C" int evplp_group_set_refit_policy(evplp_group *g, double max_cost_ratio, int32_t rebuild_builder) {
     GRP_CHECK(g);
-    drain(g);
-    if (!evplp::refit_policy_check(g->ctx[0], max_cost_ratio, rebuild_builder)) { g->set_error("%s", g->ctx[0]->error); return EVPLP_ERR_INVALID; }
-    Cmd c; c.op = OP_REFIT_POLICY; c.d = max_cost_ratio; c.i[0] = rebuild_builder;
-    return post_and_wait(g, c);
+    if (int rc = rank0_refuses(g, [&](evplp_context *c0) { return evplp::refit_policy_check(c0, max_cost_ratio, rebuild_builder); })) return rc;
+    return post_and_wait(g, command([=](Worker &w) { return evplp_set_refit_policy(w.c, max_cost_ratio, rebuild_builder); }));
 }
 // Tree rotations: every rank runs the same sweeps over its copy of the tree and must take the same rotations; rank 0's count is the group's.
 extern "C" int evplp_group_optimize_accel(evplp_group *g, int32_t passes, int32_t *rotations) {
     GRP_CHECK(g);
-    drain(g);
-    if (!evplp::optimize_accel_check(g->ctx[0], "evplp_group_optimize_accel", passes)) { g->set_error("%s", g->ctx[0]->error); return EVPLP_ERR_INVALID; }
-    std::vector<int32_t> n((size_t)g->n, 0);
-    Cmd c; c.op = OP_OPTIMIZE_ACCEL; c.i[0] = passes; c.out = n.data();
-    const int rc = post_and_wait(g, c);
+    if (int rc = rank0_refuses(g, [&](evplp_context *c0) { return evplp::optimize_accel_check(c0, "evplp_group_optimize_accel", passes); })) return rc;
+    std::vector<int32_t> n((size_t)g->n, 0);                            // (one count per rank)
+    int32_t *per_rank = n.data();
+    const int rc = post_and_wait(g, command([=](Worker &w) { return evplp_optimize_accel(w.c, passes, per_rank + w.rank); }));
     if (rc < 0) return rc;
     for (int r = 1; r < g->n; r++)
         if (n[(size_t)r] != n[0]) {
@@ -961,10 +887,8 @@ extern "C" int evplp_group_optimize_accel(evplp_group *g, int32_t passes, int32_
 }
 extern "C" int evplp_group_set_refit_rotations(evplp_group *g, int32_t passes) {
     GRP_CHECK(g);
-    drain(g);
-    if (!evplp::refit_rotations_check(g->ctx[0], "evplp_group_set_refit_rotations", passes)) { g->set_error("%s", g->ctx[0]->error); return EVPLP_ERR_INVALID; }
-    Cmd c; c.op = OP_REFIT_ROTATIONS; c.i[0] = passes;
-    return post_and_wait(g, c);
+    if (int rc = rank0_refuses(g, [&](evplp_context *c0) { return evplp::refit_rotations_check(c0, "evplp_group_set_refit_rotations", passes); })) return rc;
+    return post_and_wait(g, command([passes](Worker &w) { return evplp_set_refit_rotations(w.c, passes); }));
 }
 extern "C" int evplp_group_path_trace(evplp_group *g, const float camera_pos[3], uint32_t rng_seed, uint32_t max_bounces, int32_t do_accumulate) {
     GRP_CHECK(g);
@@ -972,8 +896,8 @@ extern "C" int evplp_group_path_trace(evplp_group *g, const float camera_pos[3],
     if (g->adapt_on && !g->adapt_pt) { g->set_error("evplp_group_path_trace: adaptivity is on (evplp_group_adaptive_enable): VPL and VSL gathers only"); return EVPLP_ERR_INVALID; }
     if (g->adapt_budget) { g->set_error("evplp_group_path_trace: budget mode (evplp_group_adaptive_enable_pt(g, 2)): evplp_group_path_trace_batch only"); return EVPLP_ERR_INVALID; }
     if (g->adapt_pt && !do_accumulate) { g->set_error("evplp_group_path_trace: adaptivity is on (evplp_group_adaptive_enable_pt): a sample must accumulate"); return EVPLP_ERR_INVALID; }
-    Cmd c; c.op = OP_PATH_TRACE; c.f[0] = camera_pos[0]; c.f[1] = camera_pos[1]; c.f[2] = camera_pos[2]; c.u[0] = rng_seed; c.u[1] = max_bounces; c.i[0] = do_accumulate;
-    return post_pass(g, c);
+    const Vec3 camera{ { camera_pos[0], camera_pos[1], camera_pos[2] } };
+    return post_pass(g, command([=](Worker &w) { return evplp_path_trace(w.c, camera.v, rng_seed, max_bounces, do_accumulate); }));
 }
 
 // Refused here, on the caller's thread, as the context refuses them (the workers' failures are sticky): the sample count, null arrays, a
@@ -995,9 +919,10 @@ extern "C" int evplp_group_path_trace_batch(evplp_group *g, const float camera_p
         sm->jitter[s][0] = jitters[2 * s]; sm->jitter[s][1] = jitters[2 * s + 1]; sm->seed[s] = rng_seeds[s];
         if (!std::isfinite(sm->jitter[s][0]) || !std::isfinite(sm->jitter[s][1])) { g->set_error("%s: jitter %d is not finite", name, s); return EVPLP_ERR_INVALID; }
     }
-    Cmd c; c.op = OP_PATH_TRACE_BATCH; c.f[0] = camera_pos[0]; c.f[1] = camera_pos[1]; c.f[2] = camera_pos[2]; c.i[0] = samples; c.u[1] = max_bounces; c.batch = sm;
     if (g->iterations) g->last_primary = g->selected;          // (the call ends with a primary pass: whose G-buffer evplp_group_denoise reads)
-    return post_pass(g, c);
+    // (the call returns before the workers run it: every posted copy of the task shares the 768 B of jitters and seeds and keeps them alive)
+    const Vec3 camera{ { camera_pos[0], camera_pos[1], camera_pos[2] } };
+    return post_pass(g, command([=](Worker &w) { return evplp_path_trace_batch(w.c, camera.v, samples, &sm->jitter[0][0], sm->seed, max_bounces); }));
 }
 extern "C" int evplp_group_path_trace_batch_scratch(evplp_group *g, uint64_t bytes) {
     GRP_CHECK(g);
@@ -1008,25 +933,18 @@ extern "C" int evplp_group_path_trace_batch_scratch(evplp_group *g, uint64_t byt
     return EVPLP_OK;
 }
 
-// Composite every strip on its GPU and all-gather the strips: every GPU then holds the frame, strip by strip.  This is
-// the per-frame exchange of a run that presents every frame; nothing comes to the host.
-static Cmd present_cmd(float vs, float ps, float ls, int32_t mask_emitter, int32_t gamma, bool settle, bool exchange) {
-    Cmd c; c.op = OP_PRESENT; c.f[0] = vs; c.f[1] = ps; c.f[2] = ls; c.i[0] = mask_emitter; c.i[1] = gamma; c.i[2] = settle ? 1 : 0; c.i[3] = exchange ? 1 : 0;
-    return c;
-}
 // EVPLP_PARTITION_ITERATIONS: every rank sums the ranks' planes and composites the sums -- or, with no pass since the last reduction, the
-// cached sums again (nothing is exchanged)
+// cached sums again (nothing is exchanged).  worker_reduce keeps its own accounts: its exchange lies between two stretches of its calls.
 static int post_reduce(evplp_group *g, float vs, float ps, float ls, int32_t mask_emitter, int32_t gamma) {
-    Cmd c = present_cmd(vs, ps, ls, mask_emitter, gamma, true, !g->sums_fresh);
-    c.op = OP_REDUCE;
-    const int rc = post_all(g, c);
+    const bool exchange = !g->sums_fresh;
+    const int rc = post_all(g, Task([=](Worker &w) { worker_reduce(&w, vs, ps, ls, mask_emitter, gamma, exchange); return 0; }));
     if (rc >= 0) g->sums_fresh = true;
     return rc;
 }
 extern "C" int evplp_group_present(evplp_group *g, float vs, float ps, float ls, int32_t mask_emitter, int32_t gamma) {
     GRP_CHECK(g);
     if (g->iterations) return post_reduce(g, vs, ps, ls, mask_emitter, gamma);
-    return post_all(g, present_cmd(vs, ps, ls, mask_emitter, gamma, false, true));       // (the per-iteration composite: no wait for the splat's verdict)
+    return post_all(g, present(vs, ps, ls, mask_emitter, gamma, false, true));       // (the per-iteration composite: no wait for the splat's verdict)
 }
 // exchange = 0: every rank composites its strip where it is and nobody waits for anybody -- no host barrier, no collective: the iteration of
 // a loop whose frame is looked at only now and then (a sub-millisecond iteration pays for the exchange otherwise: DESIGN section 5)
@@ -1034,21 +952,18 @@ extern "C" int evplp_group_present_ex(evplp_group *g, float vs, float ps, float 
     GRP_CHECK(g);
     if (g->iterations) {        // exchange = 0: the selected rank composites its own accumulators
         if (exchange != 0) return post_reduce(g, vs, ps, ls, mask_emitter, gamma);
-        if (g->failed.load(std::memory_order_acquire)) { drain(g); return group_status(g); }
-        post(g->workers[(size_t)g->selected], present_cmd(vs, ps, ls, mask_emitter, gamma, false, false));
-        return EVPLP_OK;
+        return post_one(g, g->selected, present(vs, ps, ls, mask_emitter, gamma, false, false));
     }
-    return post_all(g, present_cmd(vs, ps, ls, mask_emitter, gamma, false, exchange != 0));
+    return post_all(g, present(vs, ps, ls, mask_emitter, gamma, false, exchange != 0));
 }
 
 // evplp_group_present (settled), then the frame in image order on rank 0's device and one copy to the caller.
 extern "C" int evplp_group_resolve(evplp_group *g, float vs, float ps, float ls, int32_t mask_emitter, int32_t gamma, float *out_rgb) {
     GRP_CHECK(g);
     if (!out_rgb) { g->set_error("evplp_group_resolve: null output"); return EVPLP_ERR_INVALID; }
-    int rc = g->iterations ? post_reduce(g, vs, ps, ls, mask_emitter, gamma) : post_all(g, present_cmd(vs, ps, ls, mask_emitter, gamma, true, true));
+    int rc = g->iterations ? post_reduce(g, vs, ps, ls, mask_emitter, gamma) : post_all(g, present(vs, ps, ls, mask_emitter, gamma, true, true));
     if (rc < 0) return rc;
-    Cmd c; c.op = OP_ASSEMBLE; c.out = out_rgb;      // (rank 0's stream: behind its side of the exchange)
-    post(g->workers[0], c);
+    post(g->workers[0], assemble(out_rgb));          // (rank 0's stream: behind its side of the exchange)
     drain(g);
     return group_status(g);
 }
@@ -1059,8 +974,7 @@ extern "C" int evplp_group_resolve(evplp_group *g, float vs, float ps, float ls,
 extern "C" int evplp_group_set_error_reference(evplp_group *g, const float *rgb, const uint8_t *mask) {
     GRP_CHECK(g);
     if (!rgb && mask) { g->set_error("evplp_group_set_error_reference: a mask without a reference image"); return EVPLP_ERR_INVALID; }
-    Cmd c; c.op = OP_SET_REFERENCE; c.p0 = rgb; c.p1 = mask;
-    const int rc = post_and_wait(g, c);             // (the caller's images are read before the call returns)
+    const int rc = post_and_wait(g, command([rgb, mask](Worker &w) { return evplp_set_error_reference(w.c, rgb, mask); }));     // (the caller's images are read before the call returns)
     g->have_reference = rc >= 0 && rgb != nullptr;
     return rc;
 }
@@ -1068,16 +982,14 @@ extern "C" int evplp_group_frame_error(evplp_group *g, float vs, float ps, float
     GRP_CHECK(g);
     if (!out) { g->set_error("evplp_group_frame_error: null output"); return EVPLP_ERR_INVALID; }
     if (!g->have_reference) { g->set_error("evplp_group_frame_error: no reference image (evplp_group_set_error_reference)"); return EVPLP_ERR_INVALID; }
-    Cmd c; c.op = OP_FRAME_ERROR;
+    const Task error_rows = command([](Worker &w) { return evplp::frame_error_rows(w.c); });          // (behind the rank's composite, on its stream)
     int rc;
     if (g->iterations) {
         rc = post_reduce(g, vs, ps, ls, mask_emitter, gamma);
-        if (rc >= 0) post(g->workers[0], c);
+        if (rc >= 0) post(g->workers[0], error_rows);
     } else {
-        Cmd p = present_cmd(vs, ps, ls, mask_emitter, gamma, true, false);      // (every rank's own rows: nothing is exchanged; not a pass)
-        p.u[0] = 1;
-        rc = post_all(g, p);
-        if (rc >= 0) rc = post_all(g, c);
+        rc = post_all(g, present(vs, ps, ls, mask_emitter, gamma, true, false, false));      // (every rank's own rows: nothing is exchanged; not a pass)
+        if (rc >= 0) rc = post_all(g, error_rows);
     }
     if (rc < 0) return rc;
     drain(g);
@@ -1100,8 +1012,7 @@ extern "C" int evplp_group_noise_track(evplp_group *g, int32_t on, const uint8_t
         for (evplp_context *x : g->ctx)
             if (x->adapt_n > 0) { g->set_error("evplp_group_noise_track: adaptivity is on and %lld gather(s) accumulated", (long long)x->adapt_n); return EVPLP_ERR_INVALID; }
     }
-    Cmd c; c.op = OP_NOISE_TRACK; c.i[0] = on; c.p0 = mask;
-    const int rc = post_and_wait(g, c);             // (the caller's mask is read before the call returns)
+    const int rc = post_and_wait(g, command([on, mask](Worker &w) { return evplp_noise_track(w.c, on, mask); }));     // (the caller's mask is read before the call returns)
     g->noise_on = rc >= 0 && on != 0;
     return rc;
 }
@@ -1109,11 +1020,8 @@ extern "C" int evplp_group_noise_fold(evplp_group *g, int32_t iterations) {
     GRP_CHECK(g);
     if (!g->noise_on) { g->set_error("evplp_group_noise_fold: tracking is off (evplp_group_noise_track)"); return EVPLP_ERR_INVALID; }
     if (iterations < 1) { g->set_error("evplp_group_noise_fold: a batch holds >= 1 iterations, not %d", iterations); return EVPLP_ERR_INVALID; }
-    Cmd c; c.op = OP_NOISE_FOLD; c.i[0] = iterations;
-    if (!g->iterations) return post_all(g, c);
-    if (g->failed.load(std::memory_order_acquire)) { drain(g); return group_status(g); }
-    post(g->workers[(size_t)g->selected], c);
-    return EVPLP_OK;
+    const Task fold = command([iterations](Worker &w) { return evplp_noise_fold(w.c, iterations); });
+    return g->iterations ? post_one(g, g->selected, fold) : post_all(g, fold);
 }
 // tracking on and B >= 2 (the ranks' folds summed under the iteration partition); drains the workers to read their counts
 static int noise_group_ready(evplp_group *g, const char *name) {
@@ -1131,17 +1039,19 @@ extern "C" int evplp_group_noise_estimate(evplp_group *g, float scale, float ls,
     if (!out) { g->set_error("evplp_group_noise_estimate: null output"); return EVPLP_ERR_INVALID; }
     int rc = noise_group_ready(g, "evplp_group_noise_estimate");
     if (rc < 0) return rc;
-    Cmd rows; rows.op = OP_NOISE_ROWS; rows.f[0] = scale; rows.f[1] = ls; rows.i[0] = mask_emitter; rows.i[1] = g->iterations ? 1 : 0;
     if (g->iterations) {
+        // rank 0's moments pooled over the ranks (noise_pool before), with the summed light plane of the reduction
         rc = post_reduce(g, scale, scale, ls, mask_emitter, 0);
-        Cmd pool; pool.op = OP_NOISE_POOL;
-        if (rc >= 0) rc = post_all(g, pool);
-        if (rc >= 0) post(g->workers[0], rows);
+        if (rc >= 0) rc = post_all(g, noise_pool());
+        if (rc >= 0) post(g->workers[0], command([=](Worker &w) {
+            return evplp::noise_rows(w.c, noise_pooled(w.g, w.c), w.g->d_sum[0] + 2 * w.g->plane_px, w.g->pool_k, w.g->pool_b, scale, ls, mask_emitter);
+        }));
     } else {
-        Cmd p = present_cmd(scale, scale, ls, mask_emitter, 0, true, false);      // (every rank's own rows: nothing is exchanged; not a pass)
-        p.u[0] = 1;
-        rc = post_all(g, p);
-        if (rc >= 0) rc = post_all(g, rows);
+        rc = post_all(g, present(scale, scale, ls, mask_emitter, 0, true, false, false));      // (every rank's own rows: nothing is exchanged; not a pass)
+        if (rc >= 0) rc = post_all(g, command([=](Worker &w) {
+            evplp_context *c = w.c;
+            return evplp::noise_rows(c, evplp::noise_moments_of(c), (const float4 *)c->buf[EVPLP_BUF_LIGHT], (double)c->noise_k, (double)c->noise_b, scale, ls, mask_emitter);
+        }));
     }
     if (rc < 0) return rc;
     drain(g);
@@ -1157,20 +1067,13 @@ extern "C" int evplp_group_noise_variance(evplp_group *g, float scale, float *ou
     if (!out_rgb) { g->set_error("evplp_group_noise_variance: null output"); return EVPLP_ERR_INVALID; }
     int rc = noise_group_ready(g, "evplp_group_noise_variance");
     if (rc < 0) return rc;
-    // every rank's variance into its d_rgb, all-gathered as a present's composite (strips), or rank 0's pooled one; then OP_ASSEMBLE
-    Cmd v; v.op = OP_NOISE_VARIANCE; v.f[0] = scale;
+    // every rank's variance into its d_rgb, all-gathered as a present's composite (strips), or rank 0's pooled one; then the assembly
     if (g->iterations) {
-        Cmd pool; pool.op = OP_NOISE_POOL;
-        rc = post_all(g, pool);
-        v.i[1] = 1;
-        if (rc >= 0) post(g->workers[0], v);
-    } else {
-        v.i[3] = 1;
-        rc = post_all(g, v);
-    }
+        rc = post_all(g, noise_pool());
+        if (rc >= 0) post(g->workers[0], noise_variance(scale, true, false, false));
+    } else rc = post_all(g, noise_variance(scale, false, false, true));
     if (rc < 0) return rc;
-    Cmd a; a.op = OP_ASSEMBLE; a.out = out_rgb;
-    post(g->workers[0], a);
+    post(g->workers[0], assemble(out_rgb));
     drain(g);
     return group_status(g);
 }
@@ -1209,25 +1112,19 @@ static int group_denoise(evplp_group *g, const char *name, float scale, float ls
             if (e != hipSuccess) { (void)hipGetLastError(); g->set_error("%s: rank %d: %s", name, r, hipGetErrorString(e)); return e == hipErrorOutOfMemory ? EVPLP_ERR_OOM : EVPLP_ERR_HIP; }
         }
     }
-    Cmd prep; prep.op = OP_DENOISE_PREP; prep.f[0] = scale; prep.f[1] = ls; prep.i[0] = mask_emitter; prep.i[1] = temporal ? 1 : 0;
+    const int guides_rank = g->iterations ? g->last_primary : 0;          // (iterations: whose G-buffer, and whose previous-pose texels, rank 0 reads)
+    auto prep = [=](Worker &w) { return worker_denoise_prep(&w, scale, ls, mask_emitter, temporal, guides_rank); };
     if (g->iterations) {
-        if (temporal) { Cmd pose; pose.op = OP_TEMPORAL_POSE; post(g->workers[(size_t)g->last_primary], pose); }
-        Cmd pool; pool.op = OP_NOISE_POOL;
-        rc = post_all(g, pool);
-        Cmd v; v.op = OP_NOISE_VARIANCE; v.f[0] = scale; v.i[1] = 1; v.i[2] = 1;
-        if (rc >= 0) post(g->workers[0], v);
+        // (the rank of the last primary; it waits, so that rank 0 -- behind the reduction's barrier -- reads finished texels)
+        if (temporal) post(g->workers[(size_t)g->last_primary], command([](Worker &w) { const int rp = worker_temporal_pose(w.c); return rp < 0 ? rp : evplp_synchronize(w.c); }));
+        rc = post_all(g, noise_pool());
+        if (rc >= 0) post(g->workers[0], noise_variance(scale, true, true, false));
         if (rc >= 0) rc = post_reduce(g, scale, scale, ls, mask_emitter, 0);
-        prep.i[2] = g->last_primary;
-        if (rc >= 0) post(g->workers[0], prep);
-    } else {
-        prep.i[3] = 1;
-        rc = post_all(g, prep);
-    }
+        if (rc >= 0) post(g->workers[0], command(prep));
+    } else rc = post_all(g, command(prep, [temporal](Worker &w) { exchange_denoise(w, temporal); }));
     if (rc < 0) return rc;
-    Cmd f; f.op = OP_DENOISE_FILTER; f.i[0] = ds.levels; f.f[0] = ds.sigma_l; f.f[1] = ds.sigma_n; f.f[2] = ds.sigma_x; f.out = out_rgb;
-    f.i[1] = temporal ? 1 : 0; f.i[2] = ts.max_history; f.f[3] = ts.normal_cos; f.u[0] = g->iterations ? (uint32_t)g->last_primary : 0u;
-    post(g->workers[0], f);
-    if (temporal) { Cmd snap; snap.op = OP_TEMPORAL_SNAPSHOT; rc = post_all(g, snap); if (rc < 0) return rc; }
+    post(g->workers[0], command([=](Worker &w) { return worker_denoise_filter(&w, ds, temporal, ts, guides_rank, out_rgb); }));
+    if (temporal) { rc = post_all(g, command([](Worker &w) { return evplp::temporal_snapshot(w.c); })); if (rc < 0) return rc; }
     drain(g);
     rc = group_status(g);
     if (rc >= 0 && temporal && info) { rc = evplp::temporal_info(g->ctx[0], info); if (rc < 0) g->set_error("%s", g->ctx[0]->error); }
@@ -1242,16 +1139,14 @@ extern "C" int evplp_group_denoise(evplp_group *g, float scale, float ls, int32_
 extern "C" int evplp_group_temporal_enable(evplp_group *g, int32_t on) {
     GRP_CHECK(g);
     drain(g);
-    Cmd c; c.op = OP_TEMPORAL_ENABLE; c.i[0] = on;
-    const int rc = post_and_wait(g, c);
+    const int rc = post_and_wait(g, command([on](Worker &w) { return evplp::temporal_enable(w.c, on); }));
     g->temporal_on = rc >= 0 && on != 0;
     return rc;
 }
 extern "C" int evplp_group_temporal_reset(evplp_group *g) {
     GRP_CHECK(g);
     if (!g->temporal_on) { g->set_error("evplp_group_temporal_reset: temporal accumulation is off (evplp_group_temporal_enable)"); return EVPLP_ERR_INVALID; }
-    Cmd c; c.op = OP_TEMPORAL_RESET;
-    return post_and_wait(g, c);
+    return post_and_wait(g, command([](Worker &w) { evplp::temporal_forget(w.c); return EVPLP_OK; }));
 }
 extern "C" int evplp_group_denoise_temporal(evplp_group *g, float scale, float ls, int32_t mask_emitter, const evplp_denoise_params *p,
                                             const evplp_temporal_params *t, float *out_rgb, evplp_temporal_info *info) {
@@ -1300,8 +1195,7 @@ static int group_adaptive_enable(evplp_group *g, int32_t on, bool pt, const char
     if (on == 2 && !pt)
         for (evplp_context *c : g->ctx)
             if (c->splat_n > 0) { g->set_error("%s: %lld photon splat(s) since the last clear: gather budget mode has no place for them", name, (long long)c->splat_n); return EVPLP_ERR_INVALID; }
-    Cmd c; c.op = OP_ADAPT_ENABLE; c.i[0] = on; c.i[1] = pt ? 1 : 0;
-    rc = post_and_wait(g, c);
+    rc = post_and_wait(g, command([on, pt](Worker &w) { return pt ? evplp_adaptive_enable_pt(w.c, on) : evplp_adaptive_enable(w.c, on); }));
     g->adapt_on = rc >= 0 && on != 0;
     g->adapt_pt = g->adapt_on && pt;
     g->adapt_budget = g->adapt_on && on == 2;
@@ -1318,8 +1212,9 @@ extern "C" int evplp_group_adaptive_retire(evplp_group *g, float scale, float ls
     if (g->adapt_budget) { g->set_error("evplp_group_adaptive_retire: budget mode (evplp_group_adaptive_enable(g, 2) / evplp_group_adaptive_enable_pt(g, 2)): set the tile's budget to 0 instead"); return EVPLP_ERR_INVALID; }
     if (!(tau >= 0.0)) { g->set_error("evplp_group_adaptive_retire: tile_rel_mse must be >= 0, not %g", tau); return EVPLP_ERR_INVALID; }
     if (min_batches < 2) { g->set_error("evplp_group_adaptive_retire: min_batches must be >= 2, not %d", min_batches); return EVPLP_ERR_INVALID; }
-    Cmd c; c.op = OP_ADAPT_RETIRE; c.f[0] = scale; c.f[1] = ls; c.i[0] = mask_emitter; c.i[1] = min_batches; c.d = tau;
-    if ((rc = post_and_wait(g, c)) < 0) return rc;
+    // (the count of tiles a rank retired stays in its context's adapt_last)
+    rc = post_and_wait(g, command([=](Worker &w) { const int retired = evplp_adaptive_retire(w.c, scale, ls, mask_emitter, tau, min_batches); return retired < 0 ? retired : EVPLP_OK; }));
+    if (rc < 0) return rc;
     int32_t n = 0;
     for (evplp_context *x : g->ctx) n += x->adapt_last;
     return n;
@@ -1356,8 +1251,8 @@ extern "C" int evplp_group_adaptive_set_budgets(evplp_group *g, const int32_t *s
         if (c->noise_b < 2) { g->set_error("%s: %lld fold(s): budgets need >= 2 (evplp_group_noise_fold)", name, (long long)c->noise_b); return EVPLP_ERR_INVALID; }
         if (c->noise_k != c->adapt_n) { g->set_error("%s: %lld of %lld samples are folded: fold first (evplp_group_noise_fold)", name, (long long)c->noise_k, (long long)c->adapt_n); return EVPLP_ERR_INVALID; }
     }
-    Cmd c; c.op = OP_ADAPT_SET_BUDGETS; c.p0 = samples_per_image_tile; c.i[0] = count;
-    return post_and_wait(g, c);                     // (the caller's array is read before the call returns)
+    // (every rank takes its own tiles from the caller's whole-image array, which is read before the call returns)
+    return post_and_wait(g, command([=](Worker &w) { return evplp_adaptive_set_budgets(w.c, samples_per_image_tile, count); }));
 }
 // (host state of the contexts only: set on the caller's thread once the workers are idle, as evplp_group_path_trace_batch_scratch does)
 extern "C" int evplp_group_adaptive_budget_window(evplp_group *g, int32_t window) {
@@ -1392,7 +1287,7 @@ extern "C" int evplp_group_adaptive_tile_noise(evplp_group *g, float scale, floa
     int rc = noise_group_ready(g, name);
     if (rc < 0) return rc;
     std::fill(rel_per_image_tile, rel_per_image_tile + n, 0.0);
-    Cmd c; c.op = OP_ADAPT_TILE_NOISE; c.f[0] = scale; c.f[1] = ls; c.i[0] = mask_emitter; c.out = rel_per_image_tile;
-    if ((rc = post_and_wait(g, c)) < 0) return rc;
+    // (every rank puts its own tiles into the caller's whole-image array, which outlives the drain)
+    if ((rc = post_and_wait(g, command([=](Worker &w) { return evplp::adaptive_tile_noise_into(w.c, scale, ls, mask_emitter, rel_per_image_tile); }))) < 0) return rc;
     return (int)n;
 }

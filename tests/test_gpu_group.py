@@ -292,3 +292,69 @@ def test_the_other_gathers_and_the_path_tracer_on_virtual_ranks(evplp, tmp_path,
             images[n] = g.resolve(1.0, 0.0, 1.0)
     assert images[1].max() > 0 and np.isfinite(images[1]).all()
     assert images[1].tobytes() == images[3].tobytes()
+
+
+def test_a_splat_proxy_given_to_the_group_reaches_every_rank(evplp, tmp_path):
+    """evplp_group_set_splat_proxy on two strip ranks: the photon image under the proxy footprint, with an octahedron (every rank must hold
+    the caller's mesh, which the call has read when it returns) and then with the generated icosphere again, equals the single context's."""
+    jp = evplp.synth_scene(str(tmp_path), "room", 3000, 9, W, H, style="hard")
+    sd, _ = scenes.load_obj_scene(jp)
+    NL = 64
+    octa_v = np.array([[1, 0, 0], [-1, 0, 0], [0, 1, 0], [0, -1, 0], [0, 0, 1], [0, 0, -1]], np.float32)
+    octa_t = np.array([[0, 2, 4], [2, 1, 4], [1, 3, 4], [3, 0, 4], [2, 0, 5], [1, 2, 5], [3, 1, 5], [0, 3, 5]], np.int32)
+
+    def photon_images(runner, bsr):
+        fp = evplp.frame_params(camera_pos=sd.cam_origin, mis_mode="one", photon_radius=0.05 * bsr, num_light_paths=NL, num_vpl_light_paths=0, photons_per_path=P,
+                                splat_footprint="proxy")
+        out = []
+        for mesh in ((octa_v.copy(), octa_t.copy()), ()):
+            runner.set_splat_proxy(*mesh)
+            for a in mesh:
+                a[:] = 0                    # (the call has copied the mesh)
+            runner.clear_accumulators()
+            runner.primary((0.0, 0.0)); runner.trace_light_paths(3); runner.splat_photons(fp, clear=True)
+            out.append(runner.resolve(0.0, 1.0, 0.0)[:H])
+        return out
+
+    with evplp.Context(W, H, NL, 0, P, deterministic=True) as c:
+        c.load_scene_json(jp)
+        ref = photon_images(c, c.scene_metrics()[0])
+    with evplp.Group(W, H, NL, 0, P, 2, devices=[0, 0], deterministic=True) as g:
+        g.load_scene_json(jp)
+        img = photon_images(g, g.rank(0).scene_metrics()[0])
+    assert ref[0].max() > 0 and ref[0].tobytes() != ref[1].tobytes(), "the two proxies cover different pixels"
+    for k in range(2):
+        assert img[k].tobytes() == ref[k].tobytes(), ("octahedron", "icosphere")[k]
+
+
+def test_a_temporal_reset_on_the_group_forgets_the_history_as_the_single_context_does(evplp, tmp_path):
+    """evplp_group_temporal_reset on two strip ranks: three path-traced frames through evplp_group_denoise_temporal with a reset in front of
+    the third, which is then a first frame again; images and the stage's counts equal the single context's."""
+    jp = evplp.synth_scene(str(tmp_path), "room", 3000, 9, W, H, style="hard")
+    sd, _ = scenes.load_obj_scene(jp)
+
+    def frames(runner):
+        runner.noise_track(True); runner.temporal_enable(True)
+        out = []
+        for f in range(3):
+            if f == 2:
+                runner.temporal_reset()
+            runner.clear_accumulators()
+            for i in range(2):
+                runner.primary((0.001 * i, -0.002 * i))
+                runner.path_trace(sd.cam_origin, 10 * f + i, 3, accumulate=True)
+                runner.noise_fold(1)
+            img, info = runner.denoise_temporal(0.5)
+            out.append((img[:H], info))
+        return out
+
+    with evplp.Context(W, H, 1, 1, 1, deterministic=True) as c:
+        c.load_scene_json(jp)
+        ref = frames(c)
+    with evplp.Group(W, H, 1, 1, 1, 2, devices=[0, 0], deterministic=True) as g:
+        g.load_scene_json(jp)
+        got = frames(g)
+    assert [info["frames_since_reset"] for _, info in ref] == [1, 2, 1] and ref[1][1]["reprojected"] > 0 and ref[2][1]["reprojected"] == 0
+    for f in range(3):
+        assert got[f][1] == ref[f][1], f
+        assert np.isfinite(ref[f][0]).all() and got[f][0].tobytes() == ref[f][0].tobytes(), f
