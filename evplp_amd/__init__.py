@@ -43,6 +43,13 @@ RECORD_DTYPE = np.dtype([
     ("rho_s", np.float32, 3), ("phong_exp", np.float32),
 ])
 assert RECORD_DTYPE.itemsize == 96
+# ray queries (evplp_ray: origin, tmin, direction, tmax as 8 floats; evplp_hit)
+HIT_DTYPE = np.dtype([("t", np.float32), ("beta", np.float32), ("gamma", np.float32), ("triangle", np.int32)])
+assert HIT_DTYPE.itemsize == 16
+QUERY_CHUNK_RAYS, QUERY_ORDER = 262144, 1
+# trace_closest / trace_occluded's default for `order`: off.  On the furnished stand-in scene the ordering pass did not pay for its keys
+# and its sort on shuffled camera rays by more than the spread of the unordered runs (profiles/ray_query_times.txt)
+QUERY_ORDER_DEFAULT = False
 
 
 class Config(C.Structure):
@@ -178,6 +185,13 @@ _SIGNATURES = {
     "evplp_group_refit_accel": (C.c_int, [_P]),
     "evplp_accel_cost": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double)]),
     "evplp_accel_quality": (C.c_int, [_P, C.POINTER(AccelQuality)]),
+    "evplp_trace_closest": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "evplp_trace_occluded": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
+    "evplp_trace_closest_device": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "evplp_trace_occluded_device": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
+    "evplp_triangle_info": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "evplp_group_trace_closest": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "evplp_group_trace_occluded": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
     "evplp_ploc_tree": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.POINTER(C.c_int32)]),
     "evplp_set_refit_policy": (C.c_int, [_P, C.c_double, C.c_int32]),
     "evplp_group_accel_quality": (C.c_int, [_P, C.POINTER(AccelQuality)]),
@@ -340,6 +354,24 @@ def _ptr(a: Optional[np.ndarray]):
 
 def _f32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _host_rays(rays) -> np.ndarray:
+    """a batch of evplp_ray as a contiguous float32 array [n, 8]: origin, tmin, direction, tmax"""
+    r = np.ascontiguousarray(rays, dtype=np.float32)
+    if r.ndim != 2 or r.shape[1] != 8:
+        raise ValueError(f"rays must be [n, 8] float32 (origin, tmin, direction, tmax), not {r.shape}")
+    return r
+
+
+def _device_rays(rays):
+    """a torch tensor on the device as a batch of evplp_ray (contiguous float32 [n, 8]), or None for anything else"""
+    if not (getattr(rays, "is_cuda", False) and hasattr(rays, "data_ptr")):
+        return None
+    import torch
+    if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
+        raise ValueError(f"rays must be a float32 tensor [n, 8] (origin, tmin, direction, tmax), not {rays.dtype} {tuple(rays.shape)}")
+    return rays.contiguous()
 
 
 def _error_reference(rgb, mask, W: int, H: int):
@@ -610,6 +642,47 @@ class Context:
     def refit_accel(self):
         """evplp_refit_accel: the tree, the triangle operands and the scene's figures follow the updated vertices, on the device; the topology stays"""
         self._check(self._lib.evplp_refit_accel(self._h))
+
+    def trace_closest(self, rays, filter: int = 0, order: bool = QUERY_ORDER_DEFAULT):
+        """evplp_trace_closest: the closest hit of every ray of a float32 array [n, 8] (origin, tmin, direction, tmax) as a HIT_DTYPE array
+        (triangle -1: a miss, -2: an invalid ray); filter 0 all, 1 without the light mesh, 2 the light mesh only; order: the ordering pass.
+        A torch tensor on the device goes through evplp_trace_closest_device instead: enqueued on the context's stream, not waited for
+        (synchronize() before another stream reads it), and the result is an int32 tensor [n, 4] on the same device holding the hits' bytes
+        (t, beta, gamma as float bits: .view(torch.float32))."""
+        flags = QUERY_ORDER if order else 0
+        d = _device_rays(rays)
+        if d is not None:
+            import torch
+            hits = torch.empty((d.shape[0], 4), dtype=torch.int32, device=d.device)
+            self._check(self._lib.evplp_trace_closest_device(self._h, C.c_void_p(d.data_ptr()), int(d.shape[0]), int(filter), flags, C.c_void_p(hits.data_ptr())))
+            self._query_inputs = d          # (the launch reads it after this call returns)
+            return hits
+        r = _host_rays(rays)
+        hits = np.zeros(r.shape[0], HIT_DTYPE)
+        self._check(self._lib.evplp_trace_closest(self._h, _ptr(r), r.shape[0], int(filter), flags, _ptr(hits)))
+        return hits
+
+    def trace_occluded(self, rays, order: bool = QUERY_ORDER_DEFAULT):
+        """evplp_trace_occluded: uint8 per ray of a float32 array [n, 8] -- 1 a triangle lies in (tmin, tmax), 0 none does, 2 an invalid ray.
+        A torch tensor on the device goes through evplp_trace_occluded_device (see trace_closest) and gives a uint8 tensor."""
+        flags = QUERY_ORDER if order else 0
+        d = _device_rays(rays)
+        if d is not None:
+            import torch
+            out = torch.empty((d.shape[0],), dtype=torch.uint8, device=d.device)
+            self._check(self._lib.evplp_trace_occluded_device(self._h, C.c_void_p(d.data_ptr()), int(d.shape[0]), flags, C.c_void_p(out.data_ptr())))
+            self._query_inputs = d
+            return out
+        r = _host_rays(rays)
+        out = np.zeros(r.shape[0], np.uint8)
+        self._check(self._lib.evplp_trace_occluded(self._h, _ptr(r), r.shape[0], flags, _ptr(out)))
+        return out
+
+    def triangle_info(self, triangle: int):
+        """evplp_triangle_info: (mesh, index within the mesh) of a hit's scene triangle"""
+        m, i = C.c_int32(), C.c_int32()
+        self._check(self._lib.evplp_triangle_info(self._h, int(triangle), C.byref(m), C.byref(i)))
+        return m.value, i.value
 
     def accel_quality(self) -> dict:
         """evplp_accel_quality: the SAH cost of the tree as it is on the device (cost, root_area, inner_area, leaf_pair_area, leaf_tri_area),
@@ -1220,6 +1293,20 @@ class Group:
 
     def set_refit_policy(self, max_cost_ratio: float, rebuild_builder: int = -1):
         self._check(self._lib.evplp_group_set_refit_policy(self._h, float(max_cost_ratio), int(rebuild_builder)))
+
+    def trace_closest(self, rays, filter: int = 0, order: bool = QUERY_ORDER_DEFAULT):
+        """evplp_group_trace_closest: Context.trace_closest of a numpy batch, the rays dealt over the ranks by index; the same bytes"""
+        r = _host_rays(rays)
+        hits = np.zeros(r.shape[0], HIT_DTYPE)
+        self._check(self._lib.evplp_group_trace_closest(self._h, _ptr(r), r.shape[0], int(filter), QUERY_ORDER if order else 0, _ptr(hits)))
+        return hits
+
+    def trace_occluded(self, rays, order: bool = QUERY_ORDER_DEFAULT):
+        """evplp_group_trace_occluded: Context.trace_occluded of a numpy batch, the rays dealt over the ranks by index; the same bytes"""
+        r = _host_rays(rays)
+        out = np.zeros(r.shape[0], np.uint8)
+        self._check(self._lib.evplp_group_trace_occluded(self._h, _ptr(r), r.shape[0], QUERY_ORDER if order else 0, _ptr(out)))
+        return out
 
     def optimize_accel(self, passes: int = 1) -> int:
         """evplp_group_optimize_accel: on every rank; rank 0's rotation count, an error if any rank's differs"""

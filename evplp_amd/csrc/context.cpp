@@ -43,6 +43,7 @@ static hipError_t grow_scratch(evplp_context *c, DeviceScratch &s, size_t need) 
     s.bytes = need;
     return hipSuccess;
 }
+namespace evplp { hipError_t grow_scratch_of(evplp_context *ctx, DeviceScratch &s, size_t need) { return grow_scratch(ctx, s, need); } }   // (for ray_query.cpp)
 // a buffer made by the first call of entry point `name` that needs it and kept (evplp_denoise's and evplp_denoise_temporal's planes)
 static int alloc_once(evplp_context *c, const char *name, void **p, size_t bytes) {
     if (*p) return EVPLP_OK;
@@ -244,6 +245,7 @@ extern "C" void evplp_destroy(evplp_context *c) {
     if (c->own_stream) hipStreamSynchronize(c->own_stream);
     for (int b = 0; b < EVPLP_BUF_COUNT; b++) if (c->buf_owned[b]) hipFree(c->buf[b]);
     free_scene_device(c);
+    release_ray_query(c);
     hipFree(c->d_vpls); hipFree(c->d_vpl_src); hipFree(c->d_scalars); hipFree(c->d_counters); hipFree(c->d_rgb); hipFree(c->d_primary_cuts);
     for (DeviceScratch *s : { &c->partial, &c->lt_overflow, &c->cuts, &c->vsl_masks, &c->pt_batch, &c->pt_table }) hipFree(s->p);
     hipFree(c->d_tile_cursor); hipFree(c->d_bin_items); hipFree(c->d_bin_items_tmp); hipFree(c->d_seg); hipFree(c->d_seg_off); hipFree(c->d_big_list); hipFree(c->d_big_count);

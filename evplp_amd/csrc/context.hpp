@@ -2,6 +2,7 @@
 #pragma once
 #include "evplp_types.h"
 #include "kernels.h"
+#include "ray_query.hpp"
 
 #include <string>
 #include <thread>
@@ -106,7 +107,12 @@ int build_accel(evplp_context *c, int policy_builder);
 // scene_motion.cpp: the tree's SAH cost into out[5] (waits), and the release of everything that unit makes for a device scene
 int measure_cost(evplp_context *c, double out[5]);
 void release_scene_motion(evplp_context *c);
+// context.cpp's grow_scratch for the library's other units; ray_query.cpp: the release of what the queries made (evplp_destroy)
+hipError_t grow_scratch_of(evplp_context *ctx, DeviceScratch &s, size_t need);
+void release_ray_query(evplp_context *c);
 #pragma GCC visibility pop
+// what evplp_trace_closest / evplp_trace_occluded refuse (ray_query.cpp; name: the entry point), for the group's caller thread as well
+bool ray_query_check(evplp_context *c, const char *name, const void *rays, int32_t n, int32_t filter, int32_t flags, const void *out);
 // what evplp_update_mesh / evplp_refit_accel refuse (scene_motion.cpp), for the group's caller thread as well: false and the reason in c's error
 bool update_mesh_check(evplp_context *c, int32_t mesh, const float *vertices, int32_t nverts);
 bool transform_mesh_check(evplp_context *c, int32_t mesh, const float *m);
@@ -351,6 +357,10 @@ struct evplp_context {
     bool tp_on = false; float *d_tp_prev_v = nullptr; int32_t tp_tris = 0; evplp::TemporalPrev *d_tp_prev = nullptr, *d_tp_prev_frame = nullptr;
     evplp::CamBasis tp_prev_cam{}; float4 *d_tp_hist = nullptr; size_t tp_hist_px = 0; int tp_cur = 0; int32_t tp_frames = 0;
     uint4 *d_tp_counts = nullptr; int tp_count_slots = 0;           // (one slot per workgroup of the stage's last launch)
+    // evplp_trace_closest / evplp_trace_occluded (ray_query.cpp), all for ONE launch of kQueryChunk rays.  The host forms' staging: rays
+    // then results, 48 B per ray, on the device and in pinned host memory (made by the first host-form call).  The ordering pass's keys and
+    // indices, unsorted and sorted, 16 B per ray, then the radix sort's workspace (made by the first call with EVPLP_QUERY_ORDER).
+    evplp::DeviceScratch query_stage, query_sort; char *h_query_stage = nullptr; size_t query_sort_temp = 0;
 
     char error[512] = "";
     void set_error(const char *fmt, ...);

@@ -890,6 +890,27 @@ extern "C" int evplp_group_set_refit_rotations(evplp_group *g, int32_t passes) {
     if (int rc = rank0_refuses(g, [&](evplp_context *c0) { return evplp::refit_rotations_check(c0, "evplp_group_set_refit_rotations", passes); })) return rc;
     return post_and_wait(g, command([passes](Worker &w) { return evplp_set_refit_rotations(w.c, passes); }));
 }
+// Ray queries.  Scene and tree are replicated (both partitions), so a batch is dealt by index: rank r of N traces rays [r n / N, (r + 1) n / N)
+// into the caller's arrays, which stay valid because the call waits for the ranks.  A ray's result does not depend on the rays beside it, so
+// the output is one context's byte for byte.  What the context refuses is refused on the caller's thread against rank 0's copy.
+static Task trace_share(bool closest, const void *rays, int32_t n, int32_t filter, int32_t flags, void *out) {
+    return command([=](Worker &w) {
+        const int64_t ranks = w.g->n, begin = (int64_t)w.rank * n / ranks, end = ((int64_t)w.rank + 1) * n / ranks;
+        const evplp_ray *r = (const evplp_ray *)rays + begin;
+        return closest ? evplp_trace_closest(w.c, r, (int32_t)(end - begin), filter, flags, (evplp_hit *)out + begin)
+                       : evplp_trace_occluded(w.c, r, (int32_t)(end - begin), flags, (uint8_t *)out + begin);
+    });
+}
+extern "C" int evplp_group_trace_closest(evplp_group *group, const evplp_ray *rays, int32_t n, int32_t filter, int32_t flags, evplp_hit *hits) {
+    GRP_CHECK(group);
+    if (int rc = rank0_refuses(group, [&](evplp_context *c0) { return evplp::ray_query_check(c0, "evplp_group_trace_closest", rays, n, filter, flags, hits); })) return rc;
+    return n == 0 ? group_status(group) : post_and_wait(group, trace_share(true, rays, n, filter, flags, hits));
+}
+extern "C" int evplp_group_trace_occluded(evplp_group *group, const evplp_ray *rays, int32_t n, int32_t flags, uint8_t *out) {
+    GRP_CHECK(group);
+    if (int rc = rank0_refuses(group, [&](evplp_context *c0) { return evplp::ray_query_check(c0, "evplp_group_trace_occluded", rays, n, 0, flags, out); })) return rc;
+    return n == 0 ? group_status(group) : post_and_wait(group, trace_share(false, rays, n, 0, flags, out));
+}
 extern "C" int evplp_group_path_trace(evplp_group *g, const float camera_pos[3], uint32_t rng_seed, uint32_t max_bounces, int32_t do_accumulate) {
     GRP_CHECK(g);
     if (!camera_pos) { g->set_error("evplp_group_path_trace: null camera position"); return EVPLP_ERR_INVALID; }

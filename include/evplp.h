@@ -528,6 +528,44 @@ int evplp_rotate_tree(const void *nodes64, int32_t nnodes, const int32_t *tri_in
  * triangles, or EVPLP_ERR_INVALID for a null pointer, ntri < 0, a radius or search_iterations out of range. */
 int evplp_ploc_tree(const float *verts9, int32_t ntri, int32_t radius, int32_t search_iterations, int32_t *order, int32_t *children, int32_t *iterations);
 
+/* ---- ray queries: a caller's own rays against the scene's tree (INTEGRATION B8) ----
+ * Replaces the second acceleration structure a host application would otherwise build over geometry the device already holds: picking,
+ * dropping a probe onto a surface, a line of sight between two points of the moved scene, visibility baked for the caller's own points.
+ * The rays walk the tree of evplp_build_accel as evplp_refit_accel last left it, with the per-lane walks light tracing uses.
+ *   evplp_trace_closest: hits[i] is the closest hit of rays[i].  A triangle is hit iff the triangle test accepts it with tmin < t < tmax;
+ *     the smallest t wins and among equal t the lowest triangle index, whatever the builder.  t, beta, gamma are the test's own values for
+ *     that triangle (the hit point is (1 - beta - gamma) p0 + beta p1 + gamma p2); the direction is not normalised, so t is in units of
+ *     it.  filter: 0 all triangles, 1 without the light mesh, 2 the light mesh only.  A miss: triangle = -1, t = tmax, beta = gamma = 0.
+ *     triangle counts the scene's triangles in mesh order (the index of the attributes on the device); evplp_triangle_info turns it into
+ *     the mesh and the triangle within that mesh, on the host.  A triangle without area is in no tree and is never reported.
+ *   evplp_trace_occluded: out[i] = 1 iff any triangle is accepted in (tmin, tmax), else 0.
+ *   An invalid ray -- an origin, a direction, a tmin or a tmax that is not finite, a direction of three zeros, tmin > tmax -- is never
+ *     walked: triangle = -2 with t = beta = gamma = 0, or out[i] = 2.  The kernel decides it, for the host and the device forms alike.
+ *   flags: EVPLP_QUERY_ORDER traces the rays of a launch in the order of a 32-bit key (the origin's Morton code in the scene's box, the
+ *     direction's octant in the low bits; one key kernel and one radix sort per launch) and writes every result to its ray's own slot:
+ *     the results do not depend on it.  What it gains and costs is in DESIGN section 6c.
+ *   The host forms copy the rays through pinned memory, launch, copy the results back and wait.  The _device forms take device pointers
+ *     (n evplp_ray; n evplp_hit or n bytes), enqueue on the context's stream and do not wait: evplp_synchronize, or work on that stream,
+ *     comes behind them.  Both run a batch as launches of at most EVPLP_QUERY_CHUNK_RAYS rays, so what a context allocates does not depend
+ *     on n: the first host-form call 48 B per ray of a chunk in pinned host memory and the same on the device (12 MB each), the first
+ *     call with EVPLP_QUERY_ORDER 16 B per ray of a chunk plus the sort's workspace (about 5 MB); all grow-only scratch of the context,
+ *     freed by evplp_destroy.  A walk's stack is LDS, sized from the tree (evplp_accel_stack_entries): no scratch memory, any depth the
+ *     builders accept.
+ *   EVPLP_ERR_INVALID, the context staying usable and nothing written: before evplp_build_accel; while vertices are dirty (as every pass:
+ *     evplp_refit_accel or evplp_build_accel first); n < 0; a null pointer with n > 0; a filter outside 0 .. 2; unknown flag bits.
+ *     n = 0 returns EVPLP_OK and touches nothing.
+ *   evplp_triangle_info (host only): the mesh of scene triangle `triangle` and its index within that mesh; each pointer may be null.
+ *     EVPLP_ERR_INVALID before evplp_build_accel and for a triangle outside the scene. */
+#define EVPLP_QUERY_CHUNK_RAYS 262144
+#define EVPLP_QUERY_ORDER 1
+typedef struct evplp_ray { float origin[3]; float tmin; float direction[3]; float tmax; } evplp_ray;      /* 32 B */
+typedef struct evplp_hit { float t, beta, gamma; int32_t triangle; } evplp_hit;                           /* 16 B */
+int evplp_trace_closest(evplp_context *ctx, const evplp_ray *rays, int32_t n, int32_t filter, int32_t flags, evplp_hit *hits);
+int evplp_trace_occluded(evplp_context *ctx, const evplp_ray *rays, int32_t n, int32_t flags, uint8_t *out);
+int evplp_trace_closest_device(evplp_context *ctx, const void *d_rays, int32_t n, int32_t filter, int32_t flags, void *d_hits);
+int evplp_trace_occluded_device(evplp_context *ctx, const void *d_rays, int32_t n, int32_t flags, void *d_out);
+int evplp_triangle_info(evplp_context *ctx, int32_t triangle, int32_t *mesh, int32_t *index_in_mesh);
+
 /* ---- the per-iteration passes of RtComPhoton::run() (rtcomphoton.h:936-1068) ---- */
 /* [deferredShading] + [lightRender]: runDeferredProgram (:710-754) + runLightProgram (:839-855);
  * jitter = (2u-1)/res NDC translation (:949).  light_flags (evplp_light_flags) restate :985-995:
@@ -1063,6 +1101,11 @@ int evplp_group_set_refit_policy(evplp_group *g, double max_cost_ratio, int32_t 
  * whose count differs is EVPLP_ERR_INVALID, as a differing tree cost is for evplp_group_accel_quality */
 int evplp_group_optimize_accel(evplp_group *g, int32_t passes, int32_t *rotations);
 int evplp_group_set_refit_rotations(evplp_group *g, int32_t passes);
+/* evplp_trace_closest / evplp_trace_occluded over the ranks (both partitions: scene and tree are replicated).  Rank r of N traces rays
+ * [r n / N, (r + 1) n / N) into the caller's arrays, so the output is one context's byte for byte; the calls wait for the ranks.  Refused
+ * on the caller's thread, the group staying usable, where the plain context refuses. */
+int evplp_group_trace_closest(evplp_group *g, const evplp_ray *rays, int32_t n, int32_t filter, int32_t flags, evplp_hit *hits);
+int evplp_group_trace_occluded(evplp_group *g, const evplp_ray *rays, int32_t n, int32_t flags, uint8_t *out);
 int evplp_group_path_trace(evplp_group *g, const float camera_pos[3], uint32_t rng_seed, uint32_t max_bounces, int32_t do_accumulate);
 /* evplp_path_trace_batch, routed like evplp_group_path_trace: a strips group runs it on every rank for its own rows (the result equals one
  * context's bit for bit; evplp_set_blocks / evplp_group_rebalance behave as for evplp_group_path_trace), an iterations group on the selected
