@@ -341,13 +341,23 @@ EV_DEV bool slab_hit(const float *lo, const float *hi, V3 inv, V3 noi, float tmi
     float tf = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)), fminf(fmaxf(t0z, t1z), tmax));
     return tn <= tf;
 }
+// FAR: the ray queries' form, for origins up to 1e4 S from a scene of size S (bvh_pad's S).  The pad of the boxes (2e-6 S) is budgeted
+// for origins inside the scene; what it still covers from any origin is the rounding of o * inv on an axis k with |o_k| <= 30 S
+// (2^-24 |o_k| <= 1.8e-6 S in position).  Every other error of a plane distance t = fma(plane, inv, noi) is relative to t itself: the fma's
+// own rounding (2^-24 |t|), the reciprocal's one ulp, which scales both terms alike (2^-23 |t|), and on an axis with |o_k| > 30 S the
+// rounding of noi, 2^-24 |o_k inv_k| <= 2^-24 (30 / 29) |t| for a plane the ray reaches, because |plane| <= S there.  That is at most
+// 4.04 * 2^-24 |t| for each of tn and tf, and they matter where tn is about tf: the exit distance is given a slack of 9 * 2^-24 of itself,
+// as the oracle's slab does.  The slack also lets a box in that starts that far behind the best hit; the triangle test decides as before.
+constexpr float kFarSlack = 0x1.2p-21f;      // 9 * 2^-24
+template <bool FAR = false>
 EV_DEV float slab_near(const float *lo, const float *hi, V3 inv, V3 noi, float tmin, float tmax, bool &hit) {
     float t0x = __builtin_fmaf(lo[0], inv.x, noi.x), t1x = __builtin_fmaf(hi[0], inv.x, noi.x);
     float t0y = __builtin_fmaf(lo[1], inv.y, noi.y), t1y = __builtin_fmaf(hi[1], inv.y, noi.y);
     float t0z = __builtin_fmaf(lo[2], inv.z, noi.z), t1z = __builtin_fmaf(hi[2], inv.z, noi.z);
     float tn = fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)), fmaxf(fminf(t0z, t1z), tmin));
     float tf = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)), fminf(fmaxf(t0z, t1z), tmax));
-    hit = tn <= tf;
+    if constexpr (FAR) hit = tn <= __builtin_fmaf(fabsf(tf), kFarSlack, tf);
+    else hit = tn <= tf;
     return tn;
 }
 EV_DEV float safe_rcp(float d) {
@@ -1104,11 +1114,12 @@ EV_DEV int32_t closest_wave(const SceneDev &sc, V3 o, V3 d, float tmin, float tm
 // filter: 0 all, 1 skip light mesh, 2 light mesh only.  Returns original triangle index or -1.
 // Four-wide variants (BvhNode4, evplp_types.h): the same boxes, the same leaves, half the dependent node fetches per ray.  A ray of
 // an incoherent wave spends its time waiting for the next node (300 k light paths are 4.6 waves per SIMD, nothing to switch to).
+template <bool FAR = false>
 EV_DEV void node4_slabs(const BvhNode4 &n, V3 inv, V3 noi, float tmin, float tmax, float tn[4], bool h[4]) {
 #pragma unroll
     for (int q = 0; q < 4; q++) {
         const float lo[3] = { n.lo[0][q], n.lo[1][q], n.lo[2][q] }, hi[3] = { n.hi[0][q], n.hi[1][q], n.hi[2][q] };
-        tn[q] = slab_near(lo, hi, inv, noi, tmin, tmax, h[q]);
+        tn[q] = slab_near<FAR>(lo, hi, inv, noi, tmin, tmax, h[q]);
     }
 }
 // Stack of the four-wide walk: the first LDS_ENTRIES entries in LDS ([entry][lane]), the rest -- reached only by rays that defer more
@@ -1119,7 +1130,8 @@ EV_DEV void node4_slabs(const BvhNode4 &n, V3 inv, V3 noi, float tmin, float tma
 // SPEC ("speculative while-while", Aila & Laine 2009): a lane that reaches a leaf while other lanes of the wave still descend keeps the
 // leaf for later and goes on with its walk; the wave then tests up to two leaves per lane in one go.  Fewer, fuller trips through both
 // loops; a postponed leaf shrinks the ray later than it could have, so a few more nodes are visited.  Same hits (order-independent).
-template <int STACK_STRIDE, int LDS_ENTRIES = 0, int SPEC = 0, bool PAIRS = false>      // SPEC: leaves a lane may postpone (0, 1 or 2); PAIRS: two triangles per trip
+// FAR: the slab tests with the relative slack for origins far outside the scene (slab_near); light tracing's rays start on surfaces and do without
+template <int STACK_STRIDE, int LDS_ENTRIES = 0, int SPEC = 0, bool PAIRS = false, bool FAR = false>      // SPEC: leaves a lane may postpone (0, 1 or 2); PAIRS: two triangles per trip
 EV_DEV int32_t closest_lane4(const SceneDev &sc, V3 o, V3 d, float tmin, float tmax, int filter,
                              float &t_out, float &beta_out, float &gamma_out, int32_t *stack /* stack[k*STACK_STRIDE] */,
                              int32_t *ovf = nullptr, uint32_t ovf_stride = 0) {
@@ -1179,7 +1191,7 @@ EV_DEV int32_t closest_lane4(const SceneDev &sc, V3 o, V3 d, float tmin, float t
         while (cur >= 0) {
             const BvhNode4 &n = sc.nodes4[cur];
             float tn[4]; bool h[4];
-            node4_slabs(n, inv, noi, tmin, bt, tn, h);
+            node4_slabs<FAR>(n, inv, noi, tmin, bt, tn, h);
             int32_t c[4] = { n.child[0], n.child[1], n.child[2], n.child[3] };
 #pragma unroll
             for (int q = 0; q < 4; q++) if (!h[q] || c[q] == kNoChild) { tn[q] = 3.0e38f; c[q] = kNoChild; }
@@ -1210,7 +1222,7 @@ EV_DEV int32_t closest_lane4(const SceneDev &sc, V3 o, V3 d, float tmin, float t
     if (best >= 0) { t_out = bt; beta_out = bb; gamma_out = bg; }
     return best;
 }
-template <int STACK_STRIDE, int SPEC = 0>
+template <int STACK_STRIDE, int SPEC = 0, bool FAR = false>
 EV_DEV bool occluded_lane4(const SceneDev &sc, V3 o, V3 d, float tmin, float tmax, int32_t *stack) {
     V3 inv = v3(safe_rcp(d.x), safe_rcp(d.y), safe_rcp(d.z));
     V3 noi = v3(-(o.x * inv.x), -(o.y * inv.y), -(o.z * inv.z));
@@ -1230,7 +1242,7 @@ EV_DEV bool occluded_lane4(const SceneDev &sc, V3 o, V3 d, float tmin, float tma
         while (cur >= 0) {
             const BvhNode4 &n = sc.nodes4[cur];
             float tn[4]; bool h[4];
-            node4_slabs(n, inv, noi, tmin, tmax, tn, h);
+            node4_slabs<FAR>(n, inv, noi, tmin, tmax, tn, h);
             int32_t next = kNoChild;
 #pragma unroll
             for (int q = 0; q < 4; q++) {

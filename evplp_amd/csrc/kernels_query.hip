@@ -1,6 +1,6 @@
 // Ray queries: a caller's own rays against the scene's tree (evplp_trace_closest / evplp_trace_occluded, ray_query.cpp).
-//   ray_closest_kernel   <- the closest-hit program as a free-standing batch: closest_lane4, unchanged
-//   ray_occluded_kernel  <- the any-hit program likewise: occluded_lane4, unchanged
+//   ray_closest_kernel   <- the closest-hit program as a free-standing batch: closest_lane4 with the far-origin slack (FAR)
+//   ray_occluded_kernel  <- the any-hit program likewise: occluded_lane4 with FAR
 //   ray_key_kernel       <- the ordering pass's keys (EVPLP_QUERY_ORDER)
 // One ray per lane; nothing is known about the rays of a wave, so both walks are the per-lane four-wide ones with the full [entry][lane]
 // LDS stack of the tree that was built (kernels.h lane_stack_bytes4).  The unit is built without floating-point contraction, as
@@ -28,11 +28,14 @@ EV_DEV QueryRay load_ray(const evplp_ray *rays, uint32_t r) {
     return q;
 }
 EV_DEV bool is_finite(float x) { return fabsf(x) <= 3.4028235e38f; }      // (false for a NaN)
-// what evplp.h calls an invalid ray: such a ray is never walked
+// what evplp.h calls an invalid ray: such a ray is never walked.  The direction's largest component must lie in [2^-64, 2^64] (which a
+// direction of three zeros does not): the walks' reciprocal replaces a component below 1e-30 by 1e-30, and only above 2^-64 is that a turn of the
+// direction by less than 1e-30 / 2^-64 = 1.9e-11, which the boxes' pad absorbs; at 2^-100 it would be every component
 EV_DEV bool ray_valid(const QueryRay &q) {
     const bool finite = is_finite(q.o.x) && is_finite(q.o.y) && is_finite(q.o.z) && is_finite(q.d.x) && is_finite(q.d.y) && is_finite(q.d.z) && is_finite(q.tmin) && is_finite(q.tmax);
-    const bool zero = q.d.x == 0.0f && q.d.y == 0.0f && q.d.z == 0.0f;
-    return finite && !zero && !(q.tmin > q.tmax);
+    const float largest = fmaxf(fmaxf(fabsf(q.d.x), fabsf(q.d.y)), fabsf(q.d.z));
+    const bool in_range = largest >= 0x1p-64f && largest <= 0x1p64f;
+    return finite && in_range && !(q.tmin > q.tmax);
 }
 
 __global__ __launch_bounds__(64, EVPLP_QUERY_WAVES) void ray_closest_kernel(QueryArgs a) {
@@ -45,7 +48,7 @@ __global__ __launch_bounds__(64, EVPLP_QUERY_WAVES) void ray_closest_kernel(Quer
     float4 *out = reinterpret_cast<float4 *>(a.hits + r);
     if (!ray_valid(q)) { *out = make_float4(0.f, 0.f, 0.f, __int_as_float(-2)); return; }
     float t = q.tmax, b = 0.f, g = 0.f;
-    const int32_t tri = closest_lane4<64, 0, EVPLP_QUERY_SPEC, true>(a.sc, q.o, q.d, q.tmin, q.tmax, a.filter, t, b, g, lds_stack + lane);
+    const int32_t tri = closest_lane4<64, 0, EVPLP_QUERY_SPEC, true, true>(a.sc, q.o, q.d, q.tmin, q.tmax, a.filter, t, b, g, lds_stack + lane);
     *out = make_float4(t, b, g, __int_as_float(tri));        // (a miss: tmax, 0, 0, -1 -- the walk leaves t, b, g alone)
 }
 
@@ -57,7 +60,7 @@ __global__ __launch_bounds__(64, EVPLP_QUERY_WAVES) void ray_occluded_kernel(Que
     const uint32_t r = a.order ? a.order[i] : i;
     const QueryRay q = load_ray(a.rays, r);
     if (!ray_valid(q)) { a.occluded[r] = 2; return; }
-    a.occluded[r] = occluded_lane4<64, EVPLP_QUERY_SPEC>(a.sc, q.o, q.d, q.tmin, q.tmax, lds_stack + lane) ? 1 : 0;
+    a.occluded[r] = occluded_lane4<64, EVPLP_QUERY_SPEC, true>(a.sc, q.o, q.d, q.tmin, q.tmax, lds_stack + lane) ? 1 : 0;
 }
 
 // 27-bit Morton code of the origin in the scene's box (9 bits per axis), the direction's octant below it.  An origin outside the box, or

@@ -532,15 +532,22 @@ int evplp_ploc_tree(const float *verts9, int32_t ntri, int32_t radius, int32_t s
  * Replaces the second acceleration structure a host application would otherwise build over geometry the device already holds: picking,
  * dropping a probe onto a surface, a line of sight between two points of the moved scene, visibility baked for the caller's own points.
  * The rays walk the tree of evplp_build_accel as evplp_refit_accel last left it, with the per-lane walks light tracing uses.
- *   evplp_trace_closest: hits[i] is the closest hit of rays[i].  A triangle is hit iff the triangle test accepts it with tmin < t < tmax;
- *     the smallest t wins and among equal t the lowest triangle index, whatever the builder.  t, beta, gamma are the test's own values for
+ *   evplp_trace_closest: hits[i] is the closest hit of rays[i]: of the triangles the triangle test accepts with tmin < t < tmax the one
+ *     with the smallest t, among equal t the lowest triangle index, whatever the builder.  What is guaranteed, with S = the larger of the
+ *     scene's diagonal and its largest coordinate magnitude: a decidable ray -- one that misses every triangle, or that as an exact line
+ *     crosses the bounding box of the triangle this rule names -- gets exactly the triangle test's answer; any reported hit is one the
+ *     test accepts, with the test's own values; and this holds for origins within 1e4 S of the scene.  (A ray that grazes a triangle's
+ *     edge so closely that only the test's rounding accepts it, outside that triangle's box, may report the next hit instead: DESIGN
+ *     section 2.  Further out than 1e4 S the walk may miss triangles the test would accept.)  t, beta, gamma are the test's own values for
  *     that triangle (the hit point is (1 - beta - gamma) p0 + beta p1 + gamma p2); the direction is not normalised, so t is in units of
  *     it.  filter: 0 all triangles, 1 without the light mesh, 2 the light mesh only.  A miss: triangle = -1, t = tmax, beta = gamma = 0.
  *     triangle counts the scene's triangles in mesh order (the index of the attributes on the device); evplp_triangle_info turns it into
  *     the mesh and the triangle within that mesh, on the host.  A triangle without area is in no tree and is never reported.
  *   evplp_trace_occluded: out[i] = 1 iff any triangle is accepted in (tmin, tmax), else 0.
- *   An invalid ray -- an origin, a direction, a tmin or a tmax that is not finite, a direction of three zeros, tmin > tmax -- is never
- *     walked: triangle = -2 with t = beta = gamma = 0, or out[i] = 2.  The kernel decides it, for the host and the device forms alike.
+ *   An invalid ray -- an origin, a direction, a tmin or a tmax that is not finite, a direction whose largest component in magnitude lies
+ *     outside [2^-64, 2^64] (a direction of three zeros among them), tmin > tmax -- is never walked: triangle = -2 with t = beta = gamma = 0,
+ *     or out[i] = 2.  The kernel decides it, for the host and the device forms alike.  (Inside that range the length of the direction is
+ *     free; beyond it the walk's reciprocals would bend the direction.)
  *   flags: EVPLP_QUERY_ORDER traces the rays of a launch in the order of a 32-bit key (the origin's Morton code in the scene's box, the
  *     direction's octant in the low bits; one key kernel and one radix sort per launch) and writes every result to its ray's own slot:
  *     the results do not depend on it.  What it gains and costs is in DESIGN section 6c.

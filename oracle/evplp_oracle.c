@@ -427,6 +427,38 @@ int evo_closest(const evo_scene *s, const float o_[3], const float d_[3], float 
     if (best >= 0) { *t_out = bt; *beta_out = bb; *gamma_out = bg; }
     return best;
 }
+/* evo_closest without the tree: every triangle in index order, so a tie in t keeps the lowest index by construction */
+int evo_closest_brute(const evo_scene *s, const float o_[3], const float d_[3], float tmin, float tmax,
+                      int filter, float *t_out, float *beta_out, float *gamma_out) {
+    v3 o = ld3(o_), d = ld3(d_);
+    int32_t best = -1; float bt = tmax, bb = 0, bg = 0;
+    for (int32_t tri = 0; tri < s->ntri; tri++) {
+        if (!tri_filter_ok(s, tri, filter)) continue;
+        const float *v = s->verts + 9 * (size_t)tri; float t, b, g;
+        if (!tri_valid(v)) continue;
+        if (tri_test(ld3(v), ld3(v + 3), ld3(v + 6), o, d, tmin, 3.0e38f, &t, &b, &g, NULL) && t < bt) { bt = t; bb = b; bg = g; best = tri; }
+    }
+    if (best >= 0) { *t_out = bt; *beta_out = bb; *gamma_out = bg; }
+    return best;
+}
+/* a batch of rays (8 floats each: origin, tmin, direction, tmax) as the product's evplp_hit records; a miss is (tmax, 0, 0, -1) */
+void evo_closest_brute_batch(const evo_scene *s, const float *rays, int32_t n, int filter, float *hits4) {
+#pragma omp parallel for schedule(dynamic, 64) num_threads(evo_get_threads())
+    for (int32_t i = 0; i < n; i++) {
+        const float *r = rays + 8 * (size_t)i;
+        float t = r[7], b = 0.f, g = 0.f;
+        int32_t tri = evo_closest_brute(s, r, r + 4, r[3], r[7], filter, &t, &b, &g);
+        float *h = hits4 + 4 * (size_t)i;
+        h[0] = tri >= 0 ? t : r[7]; h[1] = tri >= 0 ? b : 0.f; h[2] = tri >= 0 ? g : 0.f; memcpy(h + 3, &tri, 4);
+    }
+}
+void evo_occluded_brute_batch(const evo_scene *s, const float *rays, int32_t n, uint8_t *out) {
+#pragma omp parallel for schedule(dynamic, 64) num_threads(evo_get_threads())
+    for (int32_t i = 0; i < n; i++) {
+        const float *r = rays + 8 * (size_t)i;
+        out[i] = (uint8_t)evo_occluded_brute(s, r, r + 4, r[3], r[7]);
+    }
+}
 
 /* ---------------------------------------------------------------- textures */
 /* tex2D on an RT_FILTER_LINEAR / RT_WRAP_REPEAT / normalised-coordinate sampler
@@ -592,9 +624,9 @@ static inline v3 cam_dir(const cam_basis *b, float ndcx, float ndcy) {
 /* deferred.geom:15-29 / deferred.frag:16-22 restated as one primary ray per pixel centre
  * (SURVEY A.3, A.8): the scene is seen through the jittered matrix, the light mesh through
  * the un-jittered one (rtcomphoton.h:720-727); depth LEQUAL, light mesh drawn last. */
-void evo_primary(const evo_scene *s, const evo_camera *cam, int32_t W, int32_t H, const float jitter[2],
-                 int32_t row_begin, int32_t row_end,
-                 float *g_pos, float *g_nrm, float *g_dif, float *g_phg, float *g_light, int32_t light_unoccluded) {
+static void primary_rows(const evo_scene *s, const evo_camera *cam, int32_t W, int32_t H, const float jitter[2],
+                         int32_t row_begin, int32_t row_end,
+                         float *g_pos, float *g_nrm, float *g_dif, float *g_phg, float *g_light, int32_t light_unoccluded, int brute) {
     cam_basis cb = cam_make(cam);
 #pragma omp parallel for schedule(dynamic, 4) num_threads(evo_get_threads())
     for (int32_t y = row_begin; y < row_end; y++) {
@@ -607,9 +639,9 @@ void evo_primary(const evo_scene *s, const evo_camera *cam, int32_t W, int32_t H
             float o[3]; st3(o, cb.eye);
             float dd[3], t, b, g, tl, bl, gl;
             st3(dd, dj);
-            int32_t tri = evo_closest(s, o, dd, 0.1f, 100.0f, 1, &t, &b, &g);
+            int32_t tri = (brute ? evo_closest_brute : evo_closest)(s, o, dd, 0.1f, 100.0f, 1, &t, &b, &g);
             st3(dd, d0);
-            int32_t ltri = evo_closest(s, o, dd, 0.1f, 100.0f, 2, &tl, &bl, &gl);
+            int32_t ltri = (brute ? evo_closest_brute : evo_closest)(s, o, dd, 0.1f, 100.0f, 2, &tl, &bl, &gl);
             float pos[4] = { 0, 0, 0, 1 }, nrm[4] = { 0, 0, 0, 0 }, dif[4] = { 0, 0, 0, 0 }, phg[4] = { 0, 0, 0, 0 }, lig[4] = { 0, 0, 0, 0 };
             int use_light = ltri >= 0 && (tri < 0 || tl <= t);
             if (use_light) { tri = ltri; b = bl; g = gl; }
@@ -632,6 +664,17 @@ void evo_primary(const evo_scene *s, const evo_camera *cam, int32_t W, int32_t H
             if (g_light) memcpy(g_light + p, lig, 16);
         }
     }
+}
+void evo_primary(const evo_scene *s, const evo_camera *cam, int32_t W, int32_t H, const float jitter[2],
+                 int32_t row_begin, int32_t row_end,
+                 float *g_pos, float *g_nrm, float *g_dif, float *g_phg, float *g_light, int32_t light_unoccluded) {
+    primary_rows(s, cam, W, H, jitter, row_begin, row_end, g_pos, g_nrm, g_dif, g_phg, g_light, light_unoccluded, 0);
+}
+/* ... with both closest hits of a pixel from evo_closest_brute: no tree, no box test */
+void evo_primary_brute(const evo_scene *s, const evo_camera *cam, int32_t W, int32_t H, const float jitter[2],
+                       int32_t row_begin, int32_t row_end,
+                       float *g_pos, float *g_nrm, float *g_dif, float *g_phg, float *g_light, int32_t light_unoccluded) {
+    primary_rows(s, cam, W, H, jitter, row_begin, row_end, g_pos, g_nrm, g_dif, g_phg, g_light, light_unoccluded, 1);
 }
 
 /* ---------------------------------------------------------- light tracing */

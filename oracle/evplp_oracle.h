@@ -108,6 +108,13 @@ int evo_occluded_brute(const evo_scene *s, const float o[3], const float d[3], f
 /* filter: 0 = all triangles, 1 = skip light mesh, 2 = light mesh only. returns tri index or -1 */
 int evo_closest(const evo_scene *s, const float o[3], const float d[3], float tmin, float tmax,
                 int filter, float *t, float *beta, float *gamma);
+/* the same answer without the tree: tri_test over every triangle that has area, far bound 3.0e38 as evo_closest calls it; the smallest
+ * t < tmax wins, among equal t the lowest index.  The reference for rays no box test has seen (tests/ray_hostile.py) */
+int evo_closest_brute(const evo_scene *s, const float o[3], const float d[3], float tmin, float tmax,
+                      int filter, float *t, float *beta, float *gamma);
+/* batches of rays, 8 floats each (origin, tmin, direction, tmax).  hits4: (t, beta, gamma, triangle as int32) per ray, a miss = (tmax, 0, 0, -1) */
+void evo_closest_brute_batch(const evo_scene *s, const float *rays, int32_t n, int filter, float *hits4);
+void evo_occluded_brute_batch(const evo_scene *s, const float *rays, int32_t n, uint8_t *out);
 
 /* ---- RNG (build-defined; see header comment) ---- */
 typedef struct evo_rng { uint64_t state, inc; uint32_t s0, s1; int32_t vsl_draw; uint32_t reserved; } evo_rng;
@@ -140,6 +147,10 @@ void evo_primary(const evo_scene *s, const evo_camera *cam, int32_t W, int32_t H
                  const float jitter[2], int32_t row_begin, int32_t row_end,
                  float *g_pos, float *g_nrm, float *g_dif, float *g_phg, float *g_light,
                  int32_t light_unoccluded /* 1: the emitter image is not depth-tested (cleareveryframe, rtcomphoton.h:989-994) */);
+/* evo_primary with evo_closest_brute for both closest hits of a pixel */
+void evo_primary_brute(const evo_scene *s, const evo_camera *cam, int32_t W, int32_t H,
+                       const float jitter[2], int32_t row_begin, int32_t row_end,
+                       float *g_pos, float *g_nrm, float *g_dif, float *g_phg, float *g_light, int32_t light_unoccluded);
 
 /* lighttracing.cu:192-250 + 113-182 */
 void evo_trace_light_paths(const evo_scene *s, uint32_t rng_seed, uint32_t path_begin, uint32_t path_count,

@@ -68,6 +68,10 @@ def load():
     l.evo_occluded_brute.argtypes = [_P, _P, _P, C.c_float, C.c_float]
     l.evo_closest.restype = C.c_int
     l.evo_closest.argtypes = [_P, _P, _P, C.c_float, C.c_float, C.c_int, _P, _P, _P]
+    l.evo_closest_brute.restype = C.c_int
+    l.evo_closest_brute.argtypes = l.evo_closest.argtypes
+    l.evo_closest_brute_batch.argtypes = [_P, _P, C.c_int32, C.c_int, _P]
+    l.evo_occluded_brute_batch.argtypes = [_P, _P, C.c_int32, _P]
     l.evo_rng_init.argtypes = [_P, C.c_uint32, C.c_uint32, C.c_uint32]
     l.evo_vsl_rng_init.argtypes = [_P, C.c_uint32, C.c_uint32, C.c_uint32]
     l.evo_vsl_rng_step.argtypes = [_P]
@@ -91,6 +95,7 @@ def load():
     l.evo_phong_pdf_w.restype = C.c_float
     l.evo_phong_pdf_w.argtypes = [_P, _P, _P, _P, C.c_float]
     l.evo_primary.argtypes = [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int32]
+    l.evo_primary_brute.argtypes = l.evo_primary.argtypes
     l.evo_trace_light_paths.argtypes = [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P]
     l.evo_vpl_splat_pair.argtypes = [_P, _P, _P, _P, _P, _P, C.c_float, _P, C.c_int, _P]
     l.evo_vsl_splat_pair.argtypes = [_P, _P, _P, _P, _P, _P, C.c_float, _P, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, _P]
@@ -162,13 +167,28 @@ class Scene:
         c.fovy = sd.fovy; c.aspect = sd.aspect
         return c
 
-    def primary(self, W, H, jitter=(0.0, 0.0), rows=None, light_unoccluded=False):
+    def primary(self, W, H, jitter=(0.0, 0.0), rows=None, light_unoccluded=False, brute=False):
+        """brute=True: both closest hits of a pixel from evo_closest_brute (no tree)"""
         planes = [np.zeros((H, W, 4), dtype=np.float32) for _ in range(5)]
         j = f3(jitter)
         cam = self.camera()
         r0, r1 = rows if rows else (0, H)
-        self.lib.evo_primary(self.h, C.byref(cam), W, H, ptr(j), r0, r1, *[ptr(p) for p in planes], int(light_unoccluded))
+        fn = self.lib.evo_primary_brute if brute else self.lib.evo_primary
+        fn(self.h, C.byref(cam), W, H, ptr(j), r0, r1, *[ptr(p) for p in planes], int(light_unoccluded))
         return planes
+
+    def closest_brute(self, rays, filt=0):
+        """evo_closest_brute of every ray (n, 8) as the product's hit records: (t, beta, gamma, triangle), a miss = (tmax, 0, 0, -1)"""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        out = np.zeros(rays.shape[0], [("t", np.float32), ("beta", np.float32), ("gamma", np.float32), ("triangle", np.int32)])
+        self.lib.evo_closest_brute_batch(self.h, ptr(rays), rays.shape[0], int(filt), ptr(out))
+        return out
+
+    def occluded_brute(self, rays):
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        out = np.zeros(rays.shape[0], np.uint8)
+        self.lib.evo_occluded_brute_batch(self.h, ptr(rays), rays.shape[0], ptr(out))
+        return out
 
     def trace_light_paths(self, seed, npaths, P, begin=0, count=None, records=None):
         if records is None:

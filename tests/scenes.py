@@ -217,6 +217,123 @@ def morton_chain_full(clusters=58, per=5, aspect=1.0):
     return s
 
 
+def _rand_unit(rng, n):
+    v = rng.normal(size=(n, 3))
+    return v / np.linalg.norm(v, axis=1, keepdims=True)
+
+
+def oblique_soup(seed=1, aspect=1.0):
+    """Random oblique triangles in [0, 10]^3 (sizes log-uniform 1e-3 .. 3, random orientation, three meshes of 180) and a mesh of planted
+    ones, in this order (s.planted names their scene triangle indices):
+      slivers       12 triangles of aspect 1e4 (long edge 1 .. 4, height 1e-4 of it)
+      tiny          8 triangles whose edges are one or two ulps of their coordinates: area barely above zero in fp32
+      no_area       8 triangles without area (a repeated corner, or three corners on a line with an exactly zero cross product): they are in
+                    no tree and no query may report them
+      ties          two pairs of triangles with identical corners, (a, b) and (c, d) with a < b, c < d and other triangles in between
+      coplanar      two overlapping triangles in the plane x + y + z = 15 (small integer corners: exactly coplanar)
+      fan           8 triangles around the shared corner s.fan_hub
+    The light is a quad under the top of the cube, facing down; the camera looks at the cube's centre from outside."""
+    rng = np.random.RandomState(seed)
+    s = SceneData()
+    s.aspect = aspect
+    mats = [s.add_material(0.2 + 0.6 * rng.rand(3)) for _ in range(4)]
+    for m in range(3):
+        n = 180
+        c = rng.uniform(0.5, 9.5, size=(n, 3))
+        size = np.exp(rng.uniform(np.log(1e-3), np.log(3.0), n))
+        u, w = _rand_unit(rng, n), _rand_unit(rng, n)
+        tri = np.stack([c - size[:, None] * (u + w) / 3.0, c + size[:, None] * (2.0 * u - w) / 3.0, c + size[:, None] * (2.0 * w - u) / 3.0], axis=1)
+        s.add_mesh(np.clip(tri, 0.0, 10.0).reshape(-1, 3), np.arange(3 * n).reshape(-1, 3), mats[m])
+    tris, names = [], {}
+
+    def plant(name, t):
+        names.setdefault(name, []).extend(range(len(tris), len(tris) + len(t)))
+        tris.extend(t)
+    sl = []
+    for _ in range(12):
+        p = rng.uniform(2.0, 8.0, 3); u, w = _rand_unit(rng, 1)[0], _rand_unit(rng, 1)[0]
+        w = w - u * (u @ w); w /= np.linalg.norm(w)
+        L = rng.uniform(1.0, 4.0)
+        sl.append([p - 0.5 * L * u, p + 0.5 * L * u, p + rng.uniform(-0.4, 0.4) * L * u + 1e-4 * L * w])
+    plant("slivers", np.clip(np.array(sl), 0.0, 10.0))
+    tiny = []
+    for k in range(8):
+        p = rng.uniform(1.0, 9.0, 3).astype(np.float32)
+        a, b = p.copy(), p.copy()
+        up = np.float32(np.inf)
+        a[k % 3] = np.nextafter(np.nextafter(p[k % 3], up), up) if k & 1 else np.nextafter(p[k % 3], up)
+        b[(k + 1) % 3] = np.nextafter(p[(k + 1) % 3], up)
+        tiny.append([p, a, b])
+    plant("tiny", np.array(tiny, np.float64))
+    flat = []
+    for k in range(4):
+        p, q = rng.uniform(1.0, 9.0, 3), rng.uniform(1.0, 9.0, 3)
+        flat.append([p, q, q] if k & 1 else [p, p, q])
+    for k in range(4):
+        p = np.round(rng.uniform(1.0, 5.0, 3) * 4.0) / 4.0; e = np.array([1.0, 0.5, 0.25])[[k % 3, (k + 1) % 3, (k + 2) % 3]]
+        flat.append([p, p + e, p + 3.0 * e])                      # (quarters: the edges and their cross product are exact, and zero)
+    plant("no_area", np.array(flat))
+    ta = np.array([[2.0, 2.5, 3.0], [4.5, 2.0, 6.0], [2.5, 5.0, 4.0]]); tb = np.array([[7.0, 6.5, 2.0], [5.5, 8.5, 4.5], [8.0, 8.0, 5.5]])
+    plant("ties", [ta, tb])
+    plant("coplanar", [np.array([[5.0, 5.0, 5.0], [8.0, 4.0, 3.0], [3.0, 8.0, 4.0]]), np.array([[6.0, 5.0, 4.0], [4.0, 7.0, 4.0], [7.0, 3.0, 5.0]])])
+    hub = np.array([3.0, 6.5, 7.0]); ax = np.array([1.0, 2.0, 3.0]) / math.sqrt(14.0)
+    e1 = np.cross(ax, [1.0, 0.0, 0.0]); e1 /= np.linalg.norm(e1); e2 = np.cross(ax, e1)
+    rim = [hub + 0.4 * ax + 1.2 * (math.cos(a) * e1 + math.sin(a) * e2) for a in np.arange(8) * (math.pi / 4.0)]
+    rim = np.array(rim, np.float32).astype(np.float64)
+    plant("fan", [np.array([hub, rim[k], rim[(k + 1) % 8]]) for k in range(8)])
+    plant("ties", [ta, tb])                                        # the second copy of each pair, behind everything planted since
+    first = sum(len(m["idx"]) for m in s.meshes)
+    s.add_mesh(np.array(tris).reshape(-1, 3), np.arange(3 * len(tris)).reshape(-1, 3), mats[3])
+    s.planted = {k: [first + i for i in v] for k, v in names.items()}
+    t = s.planted["ties"]
+    s.planted["ties"] = [(t[0], t[2]), (t[1], t[3])]
+    s.fan_hub = hub.astype(np.float32)
+    lm = s.add_material((0, 0, 0))
+    s.light_mesh = s.add_quad([4.0, 4.0, 9.9], [0, 2.0, 0], [2.0, 0, 0], lm)
+    s.cam_origin = [22.0, -9.0, 12.0]; s.cam_lookat = [5.0, 5.0, 5.0]; s.cam_up = [0.0, 0.0, 1.0]
+    s.fovy = math.radians(40.0)
+    s.triangle_soup()
+    return s
+
+
+def flat_scene(seed=1, aspect=1.0):
+    """Every triangle but the light's in the plane z = 0: an 8 x 8 tessellated quad over [0, 10] x [0, 8] and 200 random in-plane triangles
+    over it, so no leaf box has any thickness.  The light quad sits above."""
+    rng = np.random.RandomState(seed)
+    s = SceneData()
+    s.aspect = aspect
+    s.add_quad([0.0, 0.0, 0.0], [10.0, 0, 0], [0, 8.0, 0], s.add_material((0.6, 0.6, 0.6)), 8, 8)
+    n = 200
+    c = np.concatenate([rng.uniform([0.5, 0.5], [9.5, 7.5], size=(n, 2)), np.zeros((n, 1))], axis=1)
+    size = np.exp(rng.uniform(np.log(1e-2), np.log(3.0), n))
+    ang = rng.uniform(0.0, 2.0 * math.pi, (n, 2))
+    u = np.stack([np.cos(ang[:, 0]), np.sin(ang[:, 0]), np.zeros(n)], axis=1); w = np.stack([np.cos(ang[:, 1]), np.sin(ang[:, 1]), np.zeros(n)], axis=1)
+    tri = np.stack([c - size[:, None] * (u + w) / 3.0, c + size[:, None] * (2.0 * u - w) / 3.0, c + size[:, None] * (2.0 * w - u) / 3.0], axis=1)
+    s.add_mesh(tri.reshape(-1, 3), np.arange(3 * n).reshape(-1, 3), s.add_material((0.4, 0.5, 0.3)))
+    lm = s.add_material((0, 0, 0))
+    s.light_mesh = s.add_quad([4.0, 3.0, 3.0], [0, 2.0, 0], [2.0, 0, 0], lm)
+    s.cam_origin = [5.0, -6.0, 6.0]; s.cam_lookat = [5.0, 4.0, 0.0]; s.cam_up = [0.0, 0.0, 1.0]
+    s.fovy = math.radians(50.0)
+    s.triangle_soup()
+    return s
+
+
+def moved(sd, scale=1.0, offset=(0.0, 0.0, 0.0)):
+    """A copy of the scene with every vertex scaled about the origin and then translated, rounded to fp32 after the move; the camera
+    goes with it.  Attributes a generator added (planted, fan_hub) are kept, the hub moved likewise."""
+    import copy
+    s = copy.deepcopy(sd)
+    off = np.asarray(offset, np.float64)
+    f = lambda p: (np.asarray(p, np.float64) * scale + off).astype(np.float32)       # noqa: E731
+    for m in s.meshes:
+        m["verts"] = np.ascontiguousarray(f(m["verts"]))
+    s.cam_origin = [float(x) for x in f(s.cam_origin)]; s.cam_lookat = [float(x) for x in f(s.cam_lookat)]
+    if hasattr(s, "fan_hub"):
+        s.fan_hub = f(s.fan_hub)
+    s.triangle_soup()
+    return s
+
+
 def load_obj_scene(json_path, decode=None):
     """Independent Python reading of a scene JSON + OBJ/MTL (same semantics as csrc/host/scene_io.cpp).
     decode(path) -> uint8 (h, w, 3) top-down pixels for map_Kd / map_Ks / map_Ns (RtTexture(filepath, 1.0),
