@@ -47,6 +47,10 @@ assert RECORD_DTYPE.itemsize == 96
 HIT_DTYPE = np.dtype([("t", np.float32), ("beta", np.float32), ("gamma", np.float32), ("triangle", np.int32)])
 assert HIT_DTYPE.itemsize == 16
 QUERY_CHUNK_RAYS, QUERY_ORDER = 262144, 1
+# probe gather (evplp_probe_sh: nine SH coefficients x rgb, then the number of lit pairs, -1 for an invalid probe)
+PROBE_SH_DTYPE = np.dtype([("c", np.float32, (9, 3)), ("lit", np.float32)])
+assert PROBE_SH_DTYPE.itemsize == 112
+PROBE_CHUNK, PROBE_SLICE_SLOTS = 16384, 256
 # trace_closest / trace_occluded's default for `order`: off.  On the furnished stand-in scene the ordering pass did not pay for its keys
 # and its sort on shuffled camera rays by more than the spread of the unordered runs (profiles/ray_query_times.txt)
 QUERY_ORDER_DEFAULT = False
@@ -190,6 +194,11 @@ _SIGNATURES = {
     "evplp_trace_closest_device": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     "evplp_trace_occluded_device": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
     "evplp_triangle_info": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "evplp_gather_probes": (C.c_int, [_P, _P, _P, C.c_int32, _P]),
+    "evplp_gather_probes_device": (C.c_int, [_P, _P, _P, C.c_int32, _P]),
+    "evplp_probe_pair": (None, [_P, _P, C.c_float, _P]),
+    "evplp_sh_basis": (None, [_P, _P]),
+    "evplp_sh_irradiance": (None, [_P, _P, _P]),
     "evplp_group_trace_closest": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     "evplp_group_trace_occluded": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
     "evplp_ploc_tree": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.POINTER(C.c_int32)]),
@@ -346,6 +355,37 @@ def lib() -> C.CDLL:
             raise ImportError("libevplp_hip.so ABI version mismatch")
         _lib = l
     return _lib
+
+
+class ProbeParams(C.Structure):
+    """evplp_probe_params"""
+    _fields_ = [("num_vpl_light_paths", C.c_uint32), ("photons_per_path", C.c_uint32), ("min_distance", C.c_float), ("flags", C.c_uint32)]
+
+
+def probe_pair(record, x, min_distance: float) -> np.ndarray:
+    """evplp_probe_pair (host only): the term of one RECORD_DTYPE record at point x with visibility 1, float32 [9, 3], not divided"""
+    r = np.ascontiguousarray(np.asarray(record, dtype=RECORD_DTYPE).reshape(1))
+    p = _f32(x).reshape(3)
+    out = np.zeros((9, 3), np.float32)
+    lib().evplp_probe_pair(_ptr(r), _ptr(p), float(min_distance), _ptr(out))
+    return out
+
+
+def sh_basis(direction) -> np.ndarray:
+    """evplp_sh_basis (host only): Y_0 .. Y_8 of a direction (not normalised), float32 [9]"""
+    d = _f32(direction).reshape(3)
+    y = np.zeros(9, np.float32)
+    lib().evplp_sh_basis(_ptr(d), _ptr(y))
+    return y
+
+
+def sh_irradiance(sh, normal) -> np.ndarray:
+    """evplp_sh_irradiance (host only): the irradiance (rgb, float32 [3]) of one PROBE_SH_DTYPE element on a surface of unit normal"""
+    s = np.ascontiguousarray(np.asarray(sh, dtype=PROBE_SH_DTYPE).reshape(1))
+    n = _f32(normal).reshape(3)
+    rgb = np.zeros(3, np.float32)
+    lib().evplp_sh_irradiance(_ptr(s), _ptr(n), _ptr(rgb))
+    return rgb
 
 
 def _ptr(a: Optional[np.ndarray]):
@@ -676,6 +716,29 @@ class Context:
         r = _host_rays(rays)
         out = np.zeros(r.shape[0], np.uint8)
         self._check(self._lib.evplp_trace_occluded(self._h, _ptr(r), r.shape[0], flags, _ptr(out)))
+        return out
+
+    def gather_probes(self, positions, num_vpl_light_paths: int, photons_per_path: int, min_distance: float, flags: int = 0):
+        """evplp_gather_probes: the indirect light of the record slots [0, num_vpl_light_paths * photons_per_path) at every point of a
+        float32 array [n, 3], as a PROBE_SH_DTYPE array (c[i][rgb] the order-2 SH coefficients of the incident radiance, lit the number of
+        lit pairs, -1 for a point with a coordinate that is not finite).  A torch tensor on the device goes through
+        evplp_gather_probes_device instead: enqueued on the context's stream, not waited for, and the result is a float32 tensor [n, 28]
+        on the same device holding the probes' bytes (27 coefficients, then lit)."""
+        prm = ProbeParams(int(num_vpl_light_paths), int(photons_per_path), float(min_distance), int(flags))
+        if getattr(positions, "is_cuda", False) and hasattr(positions, "data_ptr"):
+            import torch
+            if positions.dtype != torch.float32 or positions.dim() != 2 or positions.shape[1] != 3:
+                raise ValueError(f"positions must be a float32 tensor [n, 3], not {positions.dtype} {tuple(positions.shape)}")
+            d = positions.contiguous()
+            out = torch.empty((d.shape[0], 28), dtype=torch.float32, device=d.device)
+            self._check(self._lib.evplp_gather_probes_device(self._h, C.byref(prm), C.c_void_p(d.data_ptr()), int(d.shape[0]), C.c_void_p(out.data_ptr())))
+            self._query_inputs = d          # (the launch reads it after this call returns)
+            return out
+        x = np.ascontiguousarray(positions, dtype=np.float32)
+        if x.ndim != 2 or x.shape[1] != 3:
+            raise ValueError(f"positions must be [n, 3] float32, not {x.shape}")
+        out = np.zeros(x.shape[0], PROBE_SH_DTYPE)
+        self._check(self._lib.evplp_gather_probes(self._h, C.byref(prm), _ptr(x), x.shape[0], _ptr(out)))
         return out
 
     def triangle_info(self, triangle: int):

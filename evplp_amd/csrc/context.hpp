@@ -110,6 +110,7 @@ void release_scene_motion(evplp_context *c);
 // context.cpp's grow_scratch for the library's other units; ray_query.cpp: the release of what the queries made (evplp_destroy)
 hipError_t grow_scratch_of(evplp_context *ctx, DeviceScratch &s, size_t need);
 void release_ray_query(evplp_context *c);
+void release_probe_gather(evplp_context *c);         // probe_gather.cpp: likewise
 #pragma GCC visibility pop
 // what evplp_trace_closest / evplp_trace_occluded refuse (ray_query.cpp; name: the entry point), for the group's caller thread as well
 bool ray_query_check(evplp_context *c, const char *name, const void *rays, int32_t n, int32_t filter, int32_t flags, const void *out);
@@ -361,6 +362,10 @@ struct evplp_context {
     // then results, 48 B per ray, on the device and in pinned host memory (made by the first host-form call).  The ordering pass's keys and
     // indices, unsorted and sorted, 16 B per ray, then the radix sort's workspace (made by the first call with EVPLP_QUERY_ORDER).
     evplp::DeviceScratch query_stage, query_sort; char *h_query_stage = nullptr; size_t query_sort_temp = 0;
+    // evplp_gather_probes (probe_gather.cpp), all for ONE launch of kProbeChunk probes.  The slices' partial sums, 112 B per probe of a chunk
+    // and slice of the record slots (made by the first call, grown by a call with more slots).  The host form's staging: positions then
+    // results, 124 B per probe, on the device and in pinned host memory (made by the first host-form call).
+    evplp::DeviceScratch probe_partial, probe_stage; char *h_probe_stage = nullptr;
 
     char error[512] = "";
     void set_error(const char *fmt, ...);

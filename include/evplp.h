@@ -573,6 +573,49 @@ int evplp_trace_closest_device(evplp_context *ctx, const void *d_rays, int32_t n
 int evplp_trace_occluded_device(evplp_context *ctx, const void *d_rays, int32_t n, int32_t flags, void *d_out);
 int evplp_triangle_info(evplp_context *ctx, int32_t triangle, int32_t *mesh, int32_t *index_in_mesh);
 
+/* ---- probe gather: the VPL solution's indirect light at the caller's own points (INTEGRATION B9) ----
+ * What lights something the G-buffer does not hold -- a character in front of a wall, particles, a lightmap texel, a point of a volume:
+ * the incident indirect radiance of the records in EVPLP_BUF_RECORDS at n free-standing points, as nine real spherical-harmonic
+ * coefficients (order 2) per colour channel.  A probe has no normal and no BRDF; the caller applies both (evplp_sh_irradiance).
+ *   Slots read: record slot k < num_vpl_light_paths * photons_per_path, in slot order, counts iff its flags have EVPLP_USABLE_VPL.  The
+ *     arithmetic is the light-subpath gather's (evplp_gather_lvc) with the receiver taken away:
+ *       v12 = pos_k - x;  c2 = max(-((n_k.x v12.x + n_k.y v12.y) + n_k.z v12.z), 0), every operation rounded on its own;  c2 <= 0: no ray, no term.
+ *       Shadow ray: origin pos_k, direction -v12, tmin 0.0001f, tmax 1.0f - 0.0001f -- walked as evplp_trace_occluded walks it, so the
+ *       visibility of a pair is what evplp_trace_occluded answers for that ray.
+ *       A lit pair: dist2 = v12 . v12, w = v12 rsq(dist2), cos2 = c2 rsq(dist2),
+ *         brdf2 = rho_d_k / pi + rho_s_k PhongEvalF(-w, flux_dir_k, n_k, e_k)    (0 for rho_s = 0; the power is exp2(e log2 d) on the hardware)
+ *         E = flux_k brdf2 cos2 / max(dist2, min_distance^2),   c[i] += E Y_i(w)
+ *     with Y_i the real SH basis of index l (l + 1) + m on w = (x, y, z): Y0 = 0.28209479, Y1 = 0.48860251 y, Y2 = 0.48860251 z,
+ *     Y3 = 0.48860251 x, Y4 = 1.09254843 x y, Y5 = 1.09254843 y z, Y6 = 0.31539157 (3 z^2 - 1), Y7 = 1.09254843 x z, Y8 = 0.54627422 (x^2 - y^2).
+ *     min_distance bounds the 1 / d^2 of a record next to the probe (a probe has no surface that would bound it).
+ *   Result: lit = the number of lit pairs, c = the sum / (float)num_vpl_light_paths.
+ *   Fixed association: the slots are cut into slices of EVPLP_PROBE_SLICE_SLOTS consecutive SLOTS (not usable records); a slice is summed in
+ *     slot order in fp32, the slices' sums are added in slice order, then the division.  A probe's 112 bytes therefore depend on its
+ *     position, the records and the tree alone: not on n, on its index in the batch, on the chunking, or on the host or device form.
+ *   An invalid probe -- a coordinate that is not finite -- is never walked: c = 0, lit = -1.  The kernel decides it.
+ *   The host form copies one chunk of EVPLP_PROBE_CHUNK probes at a time through pinned memory and waits; the _device form takes device
+ *     pointers (n x 3 floats; n evplp_probe_sh, 16-byte aligned), enqueues on the context's stream and does not wait.  Scratch, grow-only and
+ *     freed by evplp_destroy: EVPLP_PROBE_CHUNK * ceil(slots / EVPLP_PROBE_SLICE_SLOTS) * 112 bytes of partial sums (it depends on the slot
+ *     count, never on n), and for the host form 124 B per probe of a chunk on the device and pinned.
+ *   EVPLP_ERR_INVALID, the context staying usable and nothing written: before evplp_build_accel; while vertices are dirty; n < 0; a null
+ *     pointer with n > 0; null params; min_distance not finite or <= 0; flags != 0; num_vpl_light_paths or photons_per_path 0; more slots
+ *     than the context's record buffer holds (num_light_paths * photons_per_path of evplp_config); a _device destination that is not
+ *     16-byte aligned.  n = 0 returns EVPLP_OK and touches nothing.
+ *   Host only, no GPU: evplp_probe_pair is the term of one (record, point) pair with visibility 1 in fp32 with libm's powf, E Y_i as
+ *     out27[3 i + channel], not divided (all zeros for c2 <= 0; the flags are not looked at); evplp_sh_basis is Y_0 .. Y_8 of a direction
+ *     (taken as given: not normalised); evplp_sh_irradiance is the irradiance on a surface of unit `normal` -- the clamped-cosine
+ *     convolution (Ramamoorthi and Hanrahan 2001): band l weighted pi, 2 pi / 3, pi / 4, the basis evaluated at the normal.  rho_d / pi
+ *     times it is the diffuse radiance leaving that surface. */
+#define EVPLP_PROBE_CHUNK 16384          /* probes per launch */
+#define EVPLP_PROBE_SLICE_SLOTS 256      /* record slots summed by one wave, in slot order */
+typedef struct evplp_probe_params { uint32_t num_vpl_light_paths, photons_per_path; float min_distance; uint32_t flags; } evplp_probe_params;
+typedef struct evplp_probe_sh { float c[9][3]; float lit; } evplp_probe_sh;              /* 112 B */
+int evplp_gather_probes(evplp_context *ctx, const evplp_probe_params *params, const float *positions /* n x 3 */, int32_t n, evplp_probe_sh *out);
+int evplp_gather_probes_device(evplp_context *ctx, const evplp_probe_params *params, const void *d_positions, int32_t n, void *d_out);
+void evplp_probe_pair(const evplp_record *r, const float x[3], float min_distance, float out27[27]);
+void evplp_sh_basis(const float dir[3], float y[9]);
+void evplp_sh_irradiance(const evplp_probe_sh *sh, const float normal[3], float rgb[3]);
+
 /* ---- the per-iteration passes of RtComPhoton::run() (rtcomphoton.h:936-1068) ---- */
 /* [deferredShading] + [lightRender]: runDeferredProgram (:710-754) + runLightProgram (:839-855);
  * jitter = (2u-1)/res NDC translation (:949).  light_flags (evplp_light_flags) restate :985-995:
