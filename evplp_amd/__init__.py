@@ -51,6 +51,13 @@ QUERY_CHUNK_RAYS, QUERY_ORDER = 262144, 1
 PROBE_SH_DTYPE = np.dtype([("c", np.float32, (9, 3)), ("lit", np.float32)])
 assert PROBE_SH_DTYPE.itemsize == 112
 PROBE_CHUNK, PROBE_SLICE_SLOTS = 16384, 256
+# surface gather (evplp_surface_point: the four float4 of a G-buffer pixel; evplp_surface_light: the VPL sum and the lit pairs, the photon
+# estimate and the pairs inside the radius; lit = photons = -1 for a point or an eye that is not finite)
+SURFACE_POINT_DTYPE = np.dtype([("pos", np.float32, 3), ("valid", np.float32), ("normal", np.float32, 3), ("pad0", np.float32),
+                                ("rho_d", np.float32, 3), ("pad1", np.float32), ("rho_s", np.float32, 3), ("phong_exp", np.float32)])
+SURFACE_LIGHT_DTYPE = np.dtype([("vpl", np.float32, 3), ("lit", np.float32), ("pm", np.float32, 3), ("photons", np.float32)])
+assert SURFACE_POINT_DTYPE.itemsize == 64 and SURFACE_LIGHT_DTYPE.itemsize == 32
+SURFACE_VPL, SURFACE_PHOTONS, SURFACE_CHUNK = 1, 2, 16384
 # trace_closest / trace_occluded's default for `order`: off.  On the furnished stand-in scene the ordering pass did not pay for its keys
 # and its sort on shuffled camera rays by more than the spread of the unordered runs (profiles/ray_query_times.txt)
 QUERY_ORDER_DEFAULT = False
@@ -199,6 +206,11 @@ _SIGNATURES = {
     "evplp_probe_pair": (None, [_P, _P, C.c_float, _P]),
     "evplp_sh_basis": (None, [_P, _P]),
     "evplp_sh_irradiance": (None, [_P, _P, _P]),
+    "evplp_gather_surface": (C.c_int, [_P, _P, C.c_uint32, _P, _P, C.c_int32, _P]),
+    "evplp_gather_surface_device": (C.c_int, [_P, _P, C.c_uint32, _P, _P, C.c_int32, _P]),
+    "evplp_photon_grid_plan": (C.c_int, [C.c_float, _P, _P, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
+    "evplp_photon_grid_cell": (C.c_uint32, [_P, _P, C.c_float, C.c_uint32, _P]),
+    "evplp_photon_grid_range": (C.c_int, [_P, C.c_float, _P, _P, C.c_float, _P, _P]),
     "evplp_group_trace_closest": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     "evplp_group_trace_occluded": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
     "evplp_ploc_tree": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.POINTER(C.c_int32)]),
@@ -386,6 +398,32 @@ def sh_irradiance(sh, normal) -> np.ndarray:
     rgb = np.zeros(3, np.float32)
     lib().evplp_sh_irradiance(_ptr(s), _ptr(n), _ptr(rgb))
     return rgb
+
+
+def photon_grid_plan(radius: float, box_lo, box_hi, usable_photons: int):
+    """evplp_photon_grid_plan (host only): (edge, bits) of the surface gather's photon grid, or None where the call refuses"""
+    lo, hi = _f32(box_lo).reshape(3), _f32(box_hi).reshape(3)
+    edge, bits = C.c_float(), C.c_uint32()
+    if lib().evplp_photon_grid_plan(float(radius), _ptr(lo), _ptr(hi), int(usable_photons), C.byref(edge), C.byref(bits)) != OK:
+        return None
+    return edge.value, bits.value
+
+
+def photon_grid_cell(p, box_lo, edge: float, bits: int):
+    """evplp_photon_grid_cell (host only): (cell int32 [3], bucket) of a position"""
+    x, lo = _f32(p).reshape(3), _f32(box_lo).reshape(3)
+    cell = np.zeros(3, np.int32)
+    bucket = lib().evplp_photon_grid_cell(_ptr(x), _ptr(lo), float(edge), int(bits), _ptr(cell))
+    return cell, int(bucket)
+
+
+def photon_grid_range(x, radius: float, box_lo, box_hi, edge: float):
+    """evplp_photon_grid_range (host only): (walked, cell_lo int32 [3], cell_hi int32 [3]) of a point; walked False: farther than the
+    reach from the box on some axis, no cell is visited"""
+    p, lo, hi = _f32(x).reshape(3), _f32(box_lo).reshape(3), _f32(box_hi).reshape(3)
+    c0, c1 = np.zeros(3, np.int32), np.zeros(3, np.int32)
+    walked = lib().evplp_photon_grid_range(_ptr(p), float(radius), _ptr(lo), _ptr(hi), float(edge), _ptr(c0), _ptr(c1))
+    return bool(walked), c0, c1
 
 
 def _ptr(a: Optional[np.ndarray]):
@@ -739,6 +777,36 @@ class Context:
             raise ValueError(f"positions must be [n, 3] float32, not {x.shape}")
         out = np.zeros(x.shape[0], PROBE_SH_DTYPE)
         self._check(self._lib.evplp_gather_probes(self._h, C.byref(prm), _ptr(x), x.shape[0], _ptr(out)))
+        return out
+
+    def gather_surface(self, points, fp: FrameParams, eyes=None, what: int = SURFACE_VPL | SURFACE_PHOTONS):
+        """evplp_gather_surface: the VPL sum and the photon estimate at the surface points of a SURFACE_POINT_DTYPE array, as a
+        SURFACE_LIGHT_DTYPE array; eyes: float32 [n, 3], or None for fp.camera_pos at every point.  A float32 torch tensor [n, 16] on the
+        device (eyes, if any, a tensor [n, 3] there too) goes through evplp_gather_surface_device instead: enqueued on the context's
+        stream, not waited for, and the result is a float32 tensor [n, 8] on the same device holding the results' bytes."""
+        if getattr(points, "is_cuda", False) and hasattr(points, "data_ptr"):
+            import torch
+            if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 16:
+                raise ValueError(f"points must be a float32 tensor [n, 16], not {points.dtype} {tuple(points.shape)}")
+            d = points.contiguous()
+            e = None
+            if eyes is not None:
+                if not getattr(eyes, "is_cuda", False) or eyes.dtype != torch.float32 or tuple(eyes.shape) != (d.shape[0], 3):
+                    raise ValueError("eyes must be a float32 tensor [n, 3] on the points' device")
+                e = eyes.contiguous()
+            out = torch.empty((d.shape[0], 8), dtype=torch.float32, device=d.device)
+            self._check(self._lib.evplp_gather_surface_device(self._h, C.byref(fp), int(what), C.c_void_p(d.data_ptr()),
+                                                              C.c_void_p(e.data_ptr()) if e is not None else None, int(d.shape[0]), C.c_void_p(out.data_ptr())))
+            self._query_inputs = (d, e)     # (the launches read them after this call returns)
+            return out
+        x = np.ascontiguousarray(points, dtype=SURFACE_POINT_DTYPE).reshape(-1)
+        e = None
+        if eyes is not None:
+            e = np.ascontiguousarray(eyes, dtype=np.float32)
+            if e.shape != (x.shape[0], 3):
+                raise ValueError(f"eyes must be [n, 3] float32, not {e.shape}")
+        out = np.zeros(x.shape[0], SURFACE_LIGHT_DTYPE)
+        self._check(self._lib.evplp_gather_surface(self._h, C.byref(fp), int(what), _ptr(x), _ptr(e), x.shape[0], _ptr(out)))
         return out
 
     def triangle_info(self, triangle: int):

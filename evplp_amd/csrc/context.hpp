@@ -111,6 +111,7 @@ void release_scene_motion(evplp_context *c);
 hipError_t grow_scratch_of(evplp_context *ctx, DeviceScratch &s, size_t need);
 void release_ray_query(evplp_context *c);
 void release_probe_gather(evplp_context *c);         // probe_gather.cpp: likewise
+void release_surface_gather(evplp_context *c);       // surface_gather.cpp: likewise
 #pragma GCC visibility pop
 // what evplp_trace_closest / evplp_trace_occluded refuse (ray_query.cpp; name: the entry point), for the group's caller thread as well
 bool ray_query_check(evplp_context *c, const char *name, const void *rays, int32_t n, int32_t filter, int32_t flags, const void *out);
@@ -366,6 +367,9 @@ struct evplp_context {
     // and slice of the record slots (made by the first call, grown by a call with more slots).  The host form's staging: positions then
     // results, 124 B per probe, on the device and in pinned host memory (made by the first host-form call).
     evplp::DeviceScratch probe_partial, probe_stage; char *h_probe_stage = nullptr;
+    // evplp_gather_surface (surface_gather.cpp): the slices' partial sums and the photon half of ONE launch of kSurfaceChunk points; the photon grid of
+    // one call (keys, slots, bucket starts, compact records, the sort's workspace: sized by the record slots); the host form's staging, 108 B per point.
+    evplp::DeviceScratch surface_partial, surface_grid, surface_stage; char *h_surface_stage = nullptr;
 
     char error[512] = "";
     void set_error(const char *fmt, ...);

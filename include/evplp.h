@@ -160,6 +160,10 @@ typedef struct evplp_config {
      *   temporal accumulation (if on)   36 B per triangle + 32 B per pixel of the context's planes (evplp_temporal_enable), and on the context that
      *                                   filters 96 B per pixel of its frame after its first evplp_denoise_temporal; a group's rank under strips:
      *                                   + n x 32 B per pixel of the exchanged rows, and rank 0 + 32 B per image pixel (evplp_group_denoise_temporal)
+     *   surface gather (after a call)   256 KB of partial sums per slice of 256 VPL slots, and with EVPLP_SURFACE_PHOTONS 96 B per photon
+     *                                   slot + 4 B per bucket (at most the slots rounded up to a power of two) + the radix sort's workspace: the grid
+     *                                   of one call, 200 MB at 2 M slots; the host form 108 B per point of a chunk of 16 384 on the device and pinned
+     *                                   (evplp_gather_surface); none of it depends on the number of points
      * A caller that has the device to itself sets cut_scratch_bytes = 72 GB, vsl_mask_bytes = 14 GB for config #5 (one band, one launch). */
     uint64_t cut_scratch_bytes;
     uint64_t vsl_mask_bytes;
@@ -615,6 +619,70 @@ int evplp_gather_probes_device(evplp_context *ctx, const evplp_probe_params *par
 void evplp_probe_pair(const evplp_record *r, const float x[3], float min_distance, float out27[27]);
 void evplp_sh_basis(const float dir[3], float y[9]);
 void evplp_sh_irradiance(const evplp_probe_sh *sh, const float normal[3], float rgb[3]);
+
+/* ---- surface gather: the renderer's two estimates at the caller's own surface points (INTEGRATION B10) ----
+ * A lightmap texel, a texture-space shading sample, the hit of a reflection ray (evplp_trace_closest + evplp_triangle_info), the G-buffer of
+ * a second camera: a point with a normal and a BRDF that is no pixel of the context's frame.  It gets what a pixel gets -- the clamped VPL
+ * sum with its glossy receiver and all six mis_modes, and the photon density estimate that pays the clamped energy back.
+ *   A point is the four float4 of a G-buffer pixel; valid == 0 is the stencil (g_pos.w): eight zeros.  eyes: one eye per point (n x 3), or
+ *     NULL: fp->camera_pos for all.  Of fp are read: mis_mode, pdf_mc, clamping_value, photon_radius, num_light_paths, num_vpl_light_paths,
+ *     photons_per_path, and camera_pos when eyes is NULL.  Nothing else.
+ *   EVPLP_SURFACE_VPL: vpl = splatColor's sum (evplp_gather_lvc's pair: the cosine test with every operation rounded on its own, the
+ *     shadow ray [0.0001f, 1.0f - 0.0001f] from the record walked as evplp_trace_occluded walks it, vplSplat in the six modes) over the
+ *     slots k < num_vpl_light_paths * photons_per_path with EVPLP_USABLE_VPL, divided by (float)num_vpl_light_paths; lit = the pairs that
+ *     pass the cosine test and are unoccluded.  Fixed association, the probe gather's: slices of EVPLP_PROBE_SLICE_SLOTS consecutive slots
+ *     summed in slot order, the slices in index order, then the division -- a function of the slot count alone.
+ *   EVPLP_SURFACE_PHOTONS: pm = the sum of the fragment shader's value (1 / num_light_paths inside) over the slots
+ *     k < num_light_paths * photons_per_path, k != 0, with EVPLP_USABLE_PHOTON and |X - P_k|^2 <= r^2 -- dv = P_k - X, (dv.x dv.x + dv.y dv.y)
+ *     + dv.z dv.z > r r means outside, every operation rounded to fp32 on its own; the predecessor of photon k is slot k - 1, as in
+ *     evplp_splat_photons; photons = the number of such pairs, those whose fragment is discarded included.
+ *     The pairs come from a hashed uniform grid over the photon positions, built on the device once per call: origin = the low corner of
+ *     the scene's box (the meshes as evplp_refit_accel last left them), 2^bits buckets (bits from the slot count, or the environment's
+ *     EVPLP_SURFACE_GRID_BITS, 1 .. 24: the results do not depend on it), a stable radix sort of (bucket, slot).  A point visits the cells
+ *     of its range in ascending (z, y, x) and takes, in each cell's bucket, exactly the photons whose own cell is the visited one, in
+ *     ascending slot: collisions cost time and can neither drop nor repeat a pair.  A point's 16 photon bytes are a function of the
+ *     point, its eye, the records, the radius and the scene's box -- not of n, its index, the chunking, the form or bits.
+ *     The pad.  The test is fp32: a photon passes it at a true distance up to r (1 + 2^-22) per axis (2^-59 for radii whose squares
+ *     underflow).  reach = max(r (1 + 2^-20), 2^-59) exceeds that, and since a photon's coordinate P is an fp32 number and rounding is
+ *     monotone, fl(X - reach) <= P <= fl(X + reach).  cell(p) = floor(clamp(fl(fl(p - lo) / edge), -8, 2^17)) is monotone in p, so the
+ *     photon's cell lies between the cells of those two ends whatever (x +- r - lo) / edge rounds to: the same function on both sides.
+ *     edge = max(2 reach (1 + 2^-4), 2^-16 M), M bounding every magnitude involved, keeps the two ends less than one cell apart after
+ *     their four roundings: at most 2 cells per axis (3 are promised).  A point farther than reach from the box on some axis is answered
+ *     with zeros without touching the table: photons are surface points and lie inside the box.
+ *   A point or an eye with a coordinate that is not finite is never walked: zeros with lit = photons = -1.  A half not asked for: zeros.
+ *   Forms as the probe gather's: the host form copies one chunk of EVPLP_SURFACE_CHUNK points at a time through pinned memory and waits;
+ *     the _device form takes device pointers (n evplp_surface_point and n evplp_surface_light, both 16-byte aligned; n x 3 floats or
+ *     NULL), enqueues on the context's stream and does not wait.
+ *   Scratch, grow-only, freed by evplp_destroy, a function of the slot counts and never of n:
+ *       partial sums     EVPLP_SURFACE_CHUNK * ceil(vpl slots / EVPLP_PROBE_SLICE_SLOTS) * 16 B
+ *       grid             photon slots * (80 B compact record + 16 B keys and slots, before and behind the sort) + (2^bits + 2) * 4 B + the
+ *                        sort's workspace
+ *       host form        108 B per point of a chunk (point, eye, result), on the device and pinned
+ *   EVPLP_ERR_INVALID, the context staying usable and nothing written: what evplp_gather_probes refuses (before evplp_build_accel, dirty
+ *     vertices, n < 0, a null pointer with n > 0, null fp, a count of 0 or more slots than the record buffer holds, for each half asked
+ *     for); what == 0 or unknown bits; mis_mode > 5; with PHOTONS a radius that is not positive and finite; a walk stack above 64 KB; a
+ *     _device pointer that is not 16-byte aligned.  n = 0 returns EVPLP_OK and touches nothing.
+ *   Host only, no GPU, the functions the kernels call: evplp_photon_grid_plan gives the edge and bits for a radius, a box and a photon
+ *     count (EVPLP_ERR_INVALID for a radius or a box that is not finite, radius <= 0, lo > hi); evplp_photon_grid_cell the cell of a
+ *     position and, returned, its bucket; evplp_photon_grid_range the cells [cell_lo, cell_hi] a point visits, 0 when it is farther than
+ *     the reach from the box and visits none, else 1. */
+#define EVPLP_SURFACE_VPL      1u
+#define EVPLP_SURFACE_PHOTONS  2u
+#define EVPLP_SURFACE_CHUNK    16384      /* points per launch */
+typedef struct evplp_surface_point {      /* 64 B: the four float4 of a G-buffer pixel */
+    float pos[3];   float valid;          /* valid == 0: stencilled out, as g_pos.w */
+    float normal[3]; float pad0;
+    float rho_d[3]; float pad1;
+    float rho_s[3]; float phong_exp;
+} evplp_surface_point;
+typedef struct evplp_surface_light { float vpl[3]; float lit; float pm[3]; float photons; } evplp_surface_light;   /* 32 B */
+int evplp_gather_surface(evplp_context *ctx, const evplp_frame_params *fp, uint32_t what, const evplp_surface_point *points,
+                         const float *eyes /* n x 3, or NULL: fp->camera_pos for all */, int32_t n, evplp_surface_light *out);
+int evplp_gather_surface_device(evplp_context *ctx, const evplp_frame_params *fp, uint32_t what, const void *d_points, const void *d_eyes,
+                                int32_t n, void *d_out);
+int evplp_photon_grid_plan(float radius, const float box_lo[3], const float box_hi[3], uint32_t usable_photons, float *edge, uint32_t *bits);
+uint32_t evplp_photon_grid_cell(const float p[3], const float box_lo[3], float edge, uint32_t bits, int32_t cell[3]);
+int evplp_photon_grid_range(const float x[3], float radius, const float box_lo[3], const float box_hi[3], float edge, int32_t cell_lo[3], int32_t cell_hi[3]);
 
 /* ---- the per-iteration passes of RtComPhoton::run() (rtcomphoton.h:936-1068) ---- */
 /* [deferredShading] + [lightRender]: runDeferredProgram (:710-754) + runLightProgram (:839-855);
