@@ -58,6 +58,11 @@ SURFACE_POINT_DTYPE = np.dtype([("pos", np.float32, 3), ("valid", np.float32), (
 SURFACE_LIGHT_DTYPE = np.dtype([("vpl", np.float32, 3), ("lit", np.float32), ("pm", np.float32, 3), ("photons", np.float32)])
 assert SURFACE_POINT_DTYPE.itemsize == 64 and SURFACE_LIGHT_DTYPE.itemsize == 32
 SURFACE_VPL, SURFACE_PHOTONS, SURFACE_CHUNK = 1, 2, 16384
+# lightmap baking (evplp_lightmap_texel: the resolved VPL sum, the coverage -- count / S^2, -d for a texel the gutter's pass d filled --, the
+# photon estimate and the mean pair count)
+LIGHTMAP_TEXEL_DTYPE = np.dtype([("vpl", np.float32, 3), ("coverage", np.float32), ("pm", np.float32, 3), ("photons", np.float32)])
+assert LIGHTMAP_TEXEL_DTYPE.itemsize == 32
+POINTS_WHITE, POINTS_FACE_EYES, LIGHTMAP_CHUNK = 1, 2, 262144
 # trace_closest / trace_occluded's default for `order`: off.  On the furnished stand-in scene the ordering pass did not pay for its keys
 # and its sort on shuffled camera rays by more than the spread of the unordered runs (profiles/ray_query_times.txt)
 QUERY_ORDER_DEFAULT = False
@@ -208,6 +213,13 @@ _SIGNATURES = {
     "evplp_sh_irradiance": (None, [_P, _P, _P]),
     "evplp_gather_surface": (C.c_int, [_P, _P, C.c_uint32, _P, _P, C.c_int32, _P]),
     "evplp_gather_surface_device": (C.c_int, [_P, _P, C.c_uint32, _P, _P, C.c_int32, _P]),
+    "evplp_surface_points": (C.c_int, [_P, _P, C.c_int32, C.c_uint32, _P, _P]),
+    "evplp_surface_points_device": (C.c_int, [_P, _P, C.c_int32, C.c_uint32, _P, _P]),
+    "evplp_lightmap_samples": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "evplp_lightmap_samples_device": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "evplp_lightmap_cover": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "evplp_bake_lightmap": (C.c_int, [_P, _P, C.c_uint32, _P, _P, _P]),
+    "evplp_bake_lightmap_device": (C.c_int, [_P, _P, C.c_uint32, _P, _P, _P]),
     "evplp_photon_grid_plan": (C.c_int, [C.c_float, _P, _P, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "evplp_photon_grid_cell": (C.c_uint32, [_P, _P, C.c_float, C.c_uint32, _P]),
     "evplp_photon_grid_range": (C.c_int, [_P, C.c_float, _P, _P, C.c_float, _P, _P]),
@@ -398,6 +410,36 @@ def sh_irradiance(sh, normal) -> np.ndarray:
     rgb = np.zeros(3, np.float32)
     lib().evplp_sh_irradiance(_ptr(s), _ptr(n), _ptr(rgb))
     return rgb
+
+
+class LightmapParams(C.Structure):
+    """evplp_lightmap_params"""
+    _fields_ = [("mesh", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("samples", C.c_int32), ("gutter", C.c_int32), ("flags", C.c_uint32)]
+
+
+def lightmap_cover(uv6, width: int, height: int, samples: int, x: int, y: int, i: int, j: int):
+    """evplp_lightmap_cover (host only): (beta, gamma) where sample (i, j) of texel (x, y) is covered by the triangle uv6 (u0 v0 u1 v1 u2 v2), else None"""
+    uv = _f32(uv6).reshape(6)
+    b, g = C.c_float(), C.c_float()
+    if not lib().evplp_lightmap_cover(_ptr(uv), int(width), int(height), int(samples), int(x), int(y), int(i), int(j), C.byref(b), C.byref(g)):
+        return None
+    return b.value, g.value
+
+
+def _is_device(t) -> bool:
+    return getattr(t, "is_cuda", False) and hasattr(t, "data_ptr")
+
+
+def _device_uvs(uvs, device):
+    """uvs for a _device form: None, or a contiguous float32 tensor [k, 6] on `device`"""
+    if uvs is None:
+        return None
+    import torch
+    if not _is_device(uvs):
+        uvs = torch.as_tensor(np.ascontiguousarray(uvs, dtype=np.float32).reshape(-1, 6), device=device)
+    if uvs.dtype != torch.float32 or uvs.dim() != 2 or uvs.shape[1] != 6:
+        raise ValueError(f"uvs must be a float32 tensor [triangles, 6], not {uvs.dtype} {tuple(uvs.shape)}")
+    return uvs.contiguous()
 
 
 def photon_grid_plan(radius: float, box_lo, box_hi, usable_photons: int):
@@ -807,6 +849,91 @@ class Context:
                 raise ValueError(f"eyes must be [n, 3] float32, not {e.shape}")
         out = np.zeros(x.shape[0], SURFACE_LIGHT_DTYPE)
         self._check(self._lib.evplp_gather_surface(self._h, C.byref(fp), int(what), _ptr(x), _ptr(e), x.shape[0], _ptr(out)))
+        return out
+
+    def surface_points(self, hits, flags: int = 0, eyes=None):
+        """evplp_surface_points: the G-buffer's four float4 at every hit of a HIT_DTYPE array, as a SURFACE_POINT_DTYPE array (valid = 0 and
+        zeros for a miss, an invalid ray, a triangle outside the scene or without area, a beta or gamma that is not finite); flags:
+        POINTS_WHITE, POINTS_FACE_EYES (then eyes: float32 [n, 3]).  An int32 torch tensor [n, 4] on the device (trace_closest's result;
+        eyes a float32 tensor [n, 3] there too) goes through evplp_surface_points_device instead: enqueued on the context's stream, not
+        waited for, and the result is a float32 tensor [n, 16] on the same device -- what gather_surface takes."""
+        if _is_device(hits):
+            import torch
+            if hits.dtype not in (torch.int32, torch.float32) or hits.dim() != 2 or hits.shape[1] != 4:
+                raise ValueError(f"hits must be an int32 (or float32) tensor [n, 4], not {hits.dtype} {tuple(hits.shape)}")
+            d = hits.contiguous()
+            e = None
+            if eyes is not None:
+                if not _is_device(eyes) or eyes.dtype != torch.float32 or tuple(eyes.shape) != (d.shape[0], 3):
+                    raise ValueError("eyes must be a float32 tensor [n, 3] on the hits' device")
+                e = eyes.contiguous()
+            out = torch.empty((d.shape[0], 16), dtype=torch.float32, device=d.device)
+            self._check(self._lib.evplp_surface_points_device(self._h, C.c_void_p(d.data_ptr()), int(d.shape[0]), int(flags),
+                                                              C.c_void_p(e.data_ptr()) if e is not None else None, C.c_void_p(out.data_ptr())))
+            self._query_inputs = (d, e)     # (the launches read them after this call returns)
+            return out
+        h = np.ascontiguousarray(hits, dtype=HIT_DTYPE).reshape(-1)
+        e = None
+        if eyes is not None:
+            e = np.ascontiguousarray(eyes, dtype=np.float32)
+            if e.shape != (h.shape[0], 3):
+                raise ValueError(f"eyes must be [n, 3] float32, not {e.shape}")
+        out = np.zeros(h.shape[0], SURFACE_POINT_DTYPE)
+        self._check(self._lib.evplp_surface_points(self._h, _ptr(h), h.shape[0], int(flags), _ptr(e), _ptr(out)))
+        return out
+
+    def surface_points_device(self, hits, flags: int = 0, eyes=None):
+        """surface_points for tensors on the device (evplp_surface_points_device); a tensor is required"""
+        if not _is_device(hits):
+            raise ValueError("hits must be a tensor on the device")
+        return self.surface_points(hits, flags, eyes)
+
+    def lightmap_samples(self, width: int, height: int, samples: int = 1, mesh: int = -1, uvs=None):
+        """evplp_lightmap_samples: for every sample of a width x height atlas the covering triangle of mesh `mesh` (-1: of the scene) as a
+        HIT_DTYPE array [height, width, samples, samples] (row 0 at v = 0; triangle -1: uncovered; t = 0); uvs: float32 [triangles of the
+        selection, 6], or None for the meshes' own texcoords"""
+        u = None if uvs is None else np.ascontiguousarray(uvs, dtype=np.float32).reshape(-1, 6)
+        out = np.zeros((int(height), int(width), int(samples), int(samples)), HIT_DTYPE) if min(int(width), int(height), int(samples)) > 0 else np.zeros((0, 0, 0, 0), HIT_DTYPE)
+        self._check(self._lib.evplp_lightmap_samples(self._h, int(mesh), _ptr(u), int(width), int(height), int(samples), _ptr(out) if out.size else None))
+        return out
+
+    def lightmap_samples_device(self, width: int, height: int, samples: int = 1, mesh: int = -1, uvs=None, device=None):
+        """evplp_lightmap_samples_device: as lightmap_samples, the result an int32 tensor [height * width * samples^2, 4] on the device holding
+        the hits' bytes (surface_points takes it); uvs: None, an array, or a float32 tensor [triangles, 6] on the device.  Waits once per
+        band for the size of the tiles' lists, and for nothing else."""
+        import torch
+        dev = device if device is not None else (uvs.device if _is_device(uvs) else torch.device("cuda", self.cfg.device))
+        u = _device_uvs(uvs, dev)
+        n = max(int(width), 0) * max(int(height), 0) * max(int(samples), 0) ** 2
+        out = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        self._check(self._lib.evplp_lightmap_samples_device(self._h, int(mesh), C.c_void_p(u.data_ptr()) if u is not None else None, int(width), int(height),
+                                                            int(samples), C.c_void_p(out.data_ptr()) if n else None))
+        self._query_inputs = u
+        return out
+
+    def bake_lightmap(self, fp: FrameParams, width: int, height: int, samples: int = 1, mesh: int = -1, gutter: int = 0, flags: int = 0, uvs=None,
+                      what: int = SURFACE_VPL | SURFACE_PHOTONS):
+        """evplp_bake_lightmap: the atlas of mesh `mesh` (-1: of the scene) lit by the records, as a LIGHTMAP_TEXEL_DTYPE array [height, width]
+        (row 0 at v = 0): per texel the mean of the surface gather's two estimates over its covered samples, coverage = their share
+        (-d where the gutter's pass d filled the texel); flags: POINTS_WHITE or 0"""
+        prm = LightmapParams(int(mesh), int(width), int(height), int(samples), int(gutter), int(flags))
+        u = None if uvs is None else np.ascontiguousarray(uvs, dtype=np.float32).reshape(-1, 6)
+        out = np.zeros((max(int(height), 0), max(int(width), 0)), LIGHTMAP_TEXEL_DTYPE)
+        self._check(self._lib.evplp_bake_lightmap(self._h, C.byref(fp), int(what), C.byref(prm), _ptr(u), _ptr(out) if out.size else None))
+        return out
+
+    def bake_lightmap_device(self, fp: FrameParams, width: int, height: int, samples: int = 1, mesh: int = -1, gutter: int = 0, flags: int = 0, uvs=None,
+                             what: int = SURFACE_VPL | SURFACE_PHOTONS, device=None):
+        """evplp_bake_lightmap_device: as bake_lightmap, the result a float32 tensor [height, width, 8] on the device holding the texels' bytes;
+        enqueued on the context's stream behind one wait per band (the tiles' lists), not waited for at the end"""
+        import torch
+        dev = device if device is not None else (uvs.device if _is_device(uvs) else torch.device("cuda", self.cfg.device))
+        u = _device_uvs(uvs, dev)
+        prm = LightmapParams(int(mesh), int(width), int(height), int(samples), int(gutter), int(flags))
+        out = torch.empty((max(int(height), 0), max(int(width), 0), 8), dtype=torch.float32, device=dev)
+        self._check(self._lib.evplp_bake_lightmap_device(self._h, C.byref(fp), int(what), C.byref(prm), C.c_void_p(u.data_ptr()) if u is not None else None,
+                                                         C.c_void_p(out.data_ptr()) if out.numel() else None))
+        self._query_inputs = u
         return out
 
     def triangle_info(self, triangle: int):

@@ -248,6 +248,7 @@ extern "C" void evplp_destroy(evplp_context *c) {
     release_ray_query(c);
     release_probe_gather(c);
     release_surface_gather(c);
+    release_lightmap(c);
     hipFree(c->d_vpls); hipFree(c->d_vpl_src); hipFree(c->d_scalars); hipFree(c->d_counters); hipFree(c->d_rgb); hipFree(c->d_primary_cuts);
     for (DeviceScratch *s : { &c->partial, &c->lt_overflow, &c->cuts, &c->vsl_masks, &c->pt_batch, &c->pt_table }) hipFree(s->p);
     hipFree(c->d_tile_cursor); hipFree(c->d_bin_items); hipFree(c->d_bin_items_tmp); hipFree(c->d_seg); hipFree(c->d_seg_off); hipFree(c->d_big_list); hipFree(c->d_big_count);

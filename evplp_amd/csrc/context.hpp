@@ -112,6 +112,7 @@ hipError_t grow_scratch_of(evplp_context *ctx, DeviceScratch &s, size_t need);
 void release_ray_query(evplp_context *c);
 void release_probe_gather(evplp_context *c);         // probe_gather.cpp: likewise
 void release_surface_gather(evplp_context *c);       // surface_gather.cpp: likewise
+void release_lightmap(evplp_context *c);             // lightmap.cpp: likewise
 #pragma GCC visibility pop
 // what evplp_trace_closest / evplp_trace_occluded refuse (ray_query.cpp; name: the entry point), for the group's caller thread as well
 bool ray_query_check(evplp_context *c, const char *name, const void *rays, int32_t n, int32_t filter, int32_t flags, const void *out);
@@ -370,6 +371,12 @@ struct evplp_context {
     // evplp_gather_surface (surface_gather.cpp): the slices' partial sums and the photon half of ONE launch of kSurfaceChunk points; the photon grid of
     // one call (keys, slots, bucket starts, compact records, the sort's workspace: sized by the record slots); the host form's staging, 108 B per point.
     evplp::DeviceScratch surface_partial, surface_grid, surface_stage; char *h_surface_stage = nullptr;
+    // evplp_surface_points / evplp_lightmap_samples / evplp_bake_lightmap (lightmap.cpp).  The host forms' staging of ONE chunk of kQueryChunk
+    // hits (hit, eye, point: 92 B each; a band's hits fit it), on the device and pinned; the selection's set-up triangles (32 B each, and 24 B
+    // each of uploaded uvs); a band's tile arrays (counts, offsets, cursors, the scan's workspace) and its pinned pair count; the tiles'
+    // triangle lists (4 B per (triangle, tile) pair of the fullest band so far: the one array that follows the scene's overlap); the bake's
+    // hits, points and results of one band (112 B per sample); the bake's atlas buffers (32 B per texel: the host form's, the gutter's second).
+    evplp::DeviceScratch lm_stage, lm_tris, lm_band, lm_pairs, lm_bake, lm_atlas; char *h_lm_stage = nullptr; uint32_t *h_lm_count = nullptr;
 
     char error[512] = "";
     void set_error(const char *fmt, ...);

@@ -684,6 +684,76 @@ int evplp_photon_grid_plan(float radius, const float box_lo[3], const float box_
 uint32_t evplp_photon_grid_cell(const float p[3], const float box_lo[3], float edge, uint32_t bits, int32_t cell[3]);
 int evplp_photon_grid_range(const float x[3], float radius, const float box_lo[3], const float box_hi[3], float edge, int32_t cell_lo[3], int32_t cell_hi[3]);
 
+/* ---- lightmap baking: surface points from hits, the atlas rasteriser, the bake (INTEGRATION B11) ----
+ * The two links between what a caller holds and what evplp_gather_surface wants, and the call that chains them, all on the device.
+ *   evplp_surface_points: a hit (evplp_trace_closest's, the rasteriser's, the caller's own) becomes the four float4 a G-buffer pixel of
+ *     that hit would hold, with evplp_primary's arithmetic, every operation rounded on its own: w0 = 1 - beta - gamma,
+ *     P = (p1 beta + p2 gamma) + p0 w0 per component, N = the flat winding normal normalize(cross(p1 - p0, p2 - p0)) with the oracle's
+ *     roundings, rho_d / rho_s / phong_exp the triangle's material, textured ones sampled bilinearly at the interpolated texcoords.
+ *     valid = 1, pads 0.  hit.t is not read and nothing is walked.  flags: EVPLP_POINTS_WHITE writes rho_d = (1, 1, 1), rho_s = 0,
+ *     phong_exp = 0 instead (the gather's result times pi is then the irradiance); EVPLP_POINTS_FACE_EYES flips the normal where
+ *     (N.x e.x + N.y e.y) + N.z e.z < 0 with e = eye - P, every operation rounded on its own, and needs eyes (n x 3).
+ *     64 zero bytes (valid = 0, which evplp_gather_surface answers with zeros) for: triangle < 0 (a miss -1, an invalid ray -2); a
+ *     triangle at or above the scene's count; a beta or gamma that is not finite; a normal that is not finite (a triangle without area).
+ *     Chunked as the queries are (EVPLP_QUERY_CHUNK_RAYS hits per launch): the host form stages through pinned memory and waits (92 B
+ *     per hit of a chunk, on the device and pinned, made by the first host-form call of this section); the _device form takes device
+ *     pointers (n evplp_hit and n evplp_surface_point, both 16-byte aligned; n x 3 floats or NULL), enqueues and does not wait.
+ *     EVPLP_ERR_INVALID, nothing written: before evplp_build_accel; dirty vertices; n < 0; a null pointer with n > 0; unknown flags;
+ *     EVPLP_POINTS_FACE_EYES without eyes; a _device pointer that is not 16-byte aligned.  n = 0 returns EVPLP_OK and touches nothing.
+ *   evplp_lightmap_samples: for every sample of every texel of a width x height atlas (1 .. 8192 each; samples = 1, 2 or 4 per axis) the
+ *     triangle of the selection that covers it in UV space.  mesh: one mesh, or -1 for every triangle of the scene.  uvs: 6 floats per
+ *     triangle of the selection (u0 v0 u1 v1 u2 v2), or NULL for the selection's own texcoords.  out[((y width + x) S + j) S + i]:
+ *     triangle = the scene triangle (evplp_trace_closest's numbering) or -1 where nothing covers the sample, t = 0, beta / gamma below.
+ *     Row y = 0 lies at v = 0.  Coverage is integer arithmetic, hence watertight and the same on every device and on the host:
+ *       X = rint(fl(fl(u * (float)width) * 256.0f)), Y with the height: nearest even, 8 sub-texel bits; a triangle with a uv that is not
+ *         finite or a snapped magnitude above 2^22 is skipped.  Sample (x, y, i, j) lies at px = 256 x + (2 i + 1) 128 / S, py likewise.
+ *         No wrap: what lies outside [0, 1]^2 is clipped by the atlas.
+ *       A2 = (X1 - X0)(Y2 - Y0) - (Y1 - Y0)(X2 - X0) in int64.  0: skipped.  < 0: a mirrored chart, rasterised as (v0, v2, v1), beta and
+ *         gamma swapped back.  The edge a -> b has E = (bx - ax)(py - ay) - (by - ay)(px - ax).  Inside iff for all three edges E > 0, or
+ *         E == 0 and the edge owns: d = b - a, d.y > 0 || (d.y == 0 && d.x < 0).  Of the two directions of a shared edge exactly one owns.
+ *       beta = (float)((double)E_ca / (double)A2), gamma = (float)((double)E_ab / (double)A2).  Among several covering triangles the
+ *         lowest scene index wins.
+ *     The atlas is worked on in bands of whole texel rows holding at most EVPLP_LIGHTMAP_CHUNK samples (the environment's
+ *     EVPLP_LIGHTMAP_BAND lowers it: the results do not depend on it), so no allocation depends on width x height: the selection's
+ *     set-up triangles (32 B each, 24 B more where uvs come from the host), a band's tile arrays (12 B per 8 x 8-texel tile and the
+ *     scan's workspace), and the tiles' triangle lists, 4 B per (triangle, tile) pair of a band.  That last array alone follows the
+ *     scene -- the overlap of its charts, not the atlas -- and its size is known only on the device: per band one 4-byte read-back sizes
+ *     it, and BOTH forms wait there.  The _device form (d_uvs or NULL, d_out 16-byte aligned) enqueues the rest and does not wait again.
+ *     EVPLP_ERR_INVALID, nothing written: before evplp_build_accel; dirty vertices; an unknown mesh; width, height or samples out of
+ *     range; a null destination; a _device destination that is not 16-byte aligned.
+ *   evplp_lightmap_cover (host only, no GPU): 1 iff sample (i, j) of texel (x, y) is covered by the one triangle uv6, with its beta and
+ *     gamma -- the header the kernels include, compiled for the host.  0 for arguments out of range.
+ *   evplp_bake_lightmap: per band, the rasteriser's samples become surface points (flags: EVPLP_POINTS_WHITE or 0), the points go through
+ *     evplp_gather_surface_device with eyes NULL (fp->camera_pos is every sample's eye; fp and what as there), and a texel takes the fp32
+ *     sums of vpl, pm and photons over its samples with valid = 1 in ascending (j, i), each divided by their count; coverage = count / S^2.
+ *     A texel with no such sample is 32 zero bytes.  Then `gutter` (0 .. 8) passes over the whole atlas, each reading the state before
+ *     it: in pass d = 1 .. gutter a texel still at coverage 0 with at least one of its eight neighbours at coverage != 0 takes the mean of
+ *     those neighbours -- the fp32 sum in the order (-1,-1) (0,-1) (1,-1) (-1,0) (1,0) (-1,1) (0,1) (1,1), divided by their number -- and
+ *     coverage = -d.  No wrap at the borders.  out: width * height texels, row y = 0 at v = 0.
+ *     A covered texel's 32 bytes are a function of its samples' points, the records, the radius and the tree: not of the band size, the
+ *     form, or the rest of the atlas.  The photon grid of the surface gather is built once per band.
+ *     Scratch beyond the rasteriser's, grow-only: 112 B per sample of a band (hit, point, result); 32 B per texel of the atlas for the
+ *     host form, and as much again when gutter > 0 (either form).  The host form waits and copies the atlas out; the _device form
+ *     (d_out: width * height evplp_lightmap_texel, 16-byte aligned) waits only for the bands' pair counts.
+ *     EVPLP_ERR_INVALID, nothing written and the context usable: everything evplp_gather_surface refuses; null params; an unknown
+ *     mesh; width, height, samples or gutter out of range; unknown flags; a null or (_device) misaligned destination.
+ *   All scratch of this section is grow-only and freed by evplp_destroy. */
+#define EVPLP_POINTS_WHITE      1u  /* rho_d = (1,1,1), rho_s = 0, phong_exp = 0: lighting without the albedo (x pi = irradiance) */
+#define EVPLP_POINTS_FACE_EYES  2u  /* flip the normal where dot_exact(n, eye - P) < 0; needs eyes */
+#define EVPLP_LIGHTMAP_CHUNK    262144      /* samples per band */
+typedef struct evplp_lightmap_params { int32_t mesh, width, height, samples, gutter /* 0..8 */; uint32_t flags /* EVPLP_POINTS_WHITE */; } evplp_lightmap_params;
+typedef struct evplp_lightmap_texel { float vpl[3]; float coverage; float pm[3]; float photons; } evplp_lightmap_texel;   /* 32 B */
+int evplp_surface_points(evplp_context *ctx, const evplp_hit *hits, int32_t n, uint32_t flags, const float *eyes /* n x 3 or NULL */, evplp_surface_point *out);
+int evplp_surface_points_device(evplp_context *ctx, const void *d_hits, int32_t n, uint32_t flags, const void *d_eyes, void *d_out);
+int evplp_lightmap_samples(evplp_context *ctx, int32_t mesh /* or -1: every triangle of the scene */, const float *uvs /* 6 floats per triangle of the
+    selection, or NULL: the mesh's own texcoords */, int32_t width, int32_t height, int32_t samples /* 1, 2, 4 per axis */,
+    evplp_hit *out /* width*height*samples^2, index ((y*width + x)*S + j)*S + i */);
+int evplp_lightmap_samples_device(evplp_context *ctx, int32_t mesh, const void *d_uvs, int32_t width, int32_t height, int32_t samples, void *d_out);
+int evplp_lightmap_cover(const float uv6[6], int32_t width, int32_t height, int32_t samples, int32_t x, int32_t y, int32_t i, int32_t j, float *beta, float *gamma);
+int evplp_bake_lightmap(evplp_context *ctx, const evplp_frame_params *fp, uint32_t what /* EVPLP_SURFACE_VPL | _PHOTONS */, const evplp_lightmap_params *params,
+                        const float *uvs, evplp_lightmap_texel *out /* width*height, row y = 0 at v = 0 */);
+int evplp_bake_lightmap_device(evplp_context *ctx, const evplp_frame_params *fp, uint32_t what, const evplp_lightmap_params *params, const void *d_uvs, void *d_out);
+
 /* ---- the per-iteration passes of RtComPhoton::run() (rtcomphoton.h:936-1068) ---- */
 /* [deferredShading] + [lightRender]: runDeferredProgram (:710-754) + runLightProgram (:839-855);
  * jitter = (2u-1)/res NDC translation (:949).  light_flags (evplp_light_flags) restate :985-995:
