@@ -295,7 +295,9 @@ def test_path_trace(ctx, oscene, evplp, inputs):
     discrete choices (lobe, Russian roulette, visibility, the reference's 1e-5 self-intersection epsilon)
     on values that differ in the last ulps between CPU and GPU libm, so a few pixels per thousand take another
     path (measured: ~1.5 per thousand per pass); every other pixel agrees to fp32 round-off, and the image
-    energy agrees."""
+    energy agrees.
+    The per-pixel statement -- every decided pixel against a float64 restatement of path_trace_pixel, with no allowance for
+    pixels that took another path -- lives in test_gpu_feeder_domain.py; this test keeps the oracle comparison on the box room."""
     gbuf, _ = inputs
     upload_inputs(ctx, evplp, gbuf, np.zeros(NPATHS * P, dtype=evplp.RECORD_DTYPE))
     cam = oscene.sd.cam_origin
