@@ -288,6 +288,7 @@ _SIGNATURES = {
     "evplp_profile_passes": (C.c_int, [_P, C.c_int32]),
     "evplp_group_profile_passes": (C.c_int, [_P, C.c_int32]),
     "evplp_debug_counters": (C.c_int, [_P, C.c_int32, _P, C.c_int32]),
+    "evplp_debug_splat_bins": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32]),
     "evplp_accel_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     "evplp_accel_builder": (C.c_int, [_P]),
     "evplp_accel_stack_entries": (C.c_int, [_P]),
@@ -1270,6 +1271,15 @@ class Context:
         out = np.zeros(256, dtype=np.uint64)
         n = self._check(self._lib.evplp_debug_counters(self._h, which, _ptr(out), out.size))
         return out[:n]
+
+    def debug_splat_bins(self):
+        """evplp_debug_splat_bins (tests): (big_count uint32 [bin groups of 256 records], tile_cursor uint32 [local tile rows, tile columns])
+        of the last photon splat, settled: the photons of every group that went through the large-rectangle list, and the entries every
+        tile's bin wanted."""
+        big = np.zeros((self.num_records + 255) // 256, dtype=np.uint32)
+        cur = np.zeros((self.local_rows // 8, (self.W + 7) // 8), dtype=np.uint32)
+        self._check(self._lib.evplp_debug_splat_bins(self._h, _ptr(big), big.size, _ptr(cur), cur.size))
+        return big, cur
 
     # -- strips
     def global_rows(self) -> np.ndarray:

@@ -2033,6 +2033,23 @@ extern "C" int evplp_debug_counters(evplp_context *c, int32_t pass, uint64_t *ou
     return n;
 }
 
+// what the binning of the last photon splat left behind (tests: which path the photons took, what every tile's bin wanted)
+extern "C" int evplp_debug_splat_bins(evplp_context *c, uint32_t *big_count, int32_t n_groups, uint32_t *tile_cursor, int32_t n_tiles) {
+    CTX_CHECK(c);
+    { int rc_ = settle_splat(c); if (rc_) return rc_; }
+    const int32_t groups = std::max(c->num_bin_groups, 0), tiles = c->tiles_x * c->tiles_y;
+    if ((big_count && n_groups != groups) || (tile_cursor && n_tiles != tiles)) {
+        c->set_error("evplp_debug_splat_bins: the context has %d bin groups and %d tiles, not %d and %d", groups, tiles, n_groups, n_tiles);
+        return EVPLP_ERR_INVALID;
+    }
+    if (!c->pass_ran[EVPLP_PASS_SPLAT]) { c->set_error("evplp_debug_splat_bins: no photon splat has run"); return EVPLP_ERR_INVALID; }
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (big_count && groups > 0) HIP_TRY(c, hipMemcpy(big_count, c->d_big_count, sizeof(uint32_t) * (size_t)groups, hipMemcpyDeviceToHost));
+    if (tile_cursor && tiles > 0) HIP_TRY(c, hipMemcpy(tile_cursor, c->d_tile_cursor, sizeof(uint32_t) * (size_t)tiles, hipMemcpyDeviceToHost));
+    return EVPLP_OK;
+}
+
 extern "C" int evplp_pass_stats_get(evplp_context *c, int32_t pass, evplp_pass_stats *out) {
     CTX_CHECK(c);
     { int rc_ = settle_splat(c); if (rc_) return rc_; }

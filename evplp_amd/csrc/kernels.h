@@ -219,7 +219,8 @@ constexpr int kSummaryHeavy = kSummaryFinal + 8;     // tiles on the heavy list 
 //   splat_scatter : workgroup (slice, bucket): thread t takes the run of bucket entries of bin-workgroup slice * 256 + t, the
 //                   workgroup ranks them per tile in LDS and reserves the tiles' bin slots with ONE atomic per (workgroup,
 //                   tile): a tile cursor sees one add per slice.
-//   splat_big     : photons whose rectangle is larger than 2x2 tiles (huge radii) place their entries one atomic each.
+//   splat_big     : photons whose rectangle is larger than 3x3 tiles (huge radii), and those whose entries did not fit into their group's
+//                   segment any more, place their entries one atomic each.
 #ifndef EVPLP_BIN_CHUNKS
 #define EVPLP_BIN_CHUNKS 1
 #endif
@@ -227,7 +228,8 @@ constexpr int kSummaryHeavy = kSummaryFinal + 8;     // tiles on the heavy list 
 // 1 chunk 155 / 105, 2 chunks 186 / 134, 4 chunks 182 / 128: short workgroups, four per CU, hide latency best.
 constexpr int kBinChunks = EVPLP_BIN_CHUNKS;
 constexpr int kBinGroup = 256 * kBinChunks;   // records per workgroup
-constexpr int kSegCap = 4 * kBinGroup;        // entries of a workgroup's segment (a photon of the LDS path has at most 2x2)
+constexpr int kSegCap = 4 * kBinGroup;        // entries of a workgroup's segment: four per record on AVERAGE.  A photon of the LDS path has a rectangle of up to
+                                              // 3x3 tiles (nine entries before the depth cull, 1-2 after it); one that no longer fits goes to big_list
 #ifndef EVPLP_SCATTER_G
 #define EVPLP_SCATTER_G 2
 #endif
@@ -249,7 +251,7 @@ struct SplatArgs {
     uint32_t bin_stride;
     uint32_t *seg;            // [num_bin_groups][kSegCap] entries: record - group base (10 bits) | tile within the bucket (<= 9 bits) << 10, sorted by bucket
     uint16_t *seg_off;        // [num_bin_groups][num_buckets + 1] first entry of every bucket in the group's segment
-    uint32_t *big_list;       // [num_bin_groups][kBinGroup] records whose rectangle is larger than 2x2 tiles
+    uint32_t *big_list;       // [num_bin_groups][kBinGroup] records whose rectangle is larger than 3x3 tiles, and those that overflowed the group's segment
     uint32_t *big_count;      // [num_bin_groups]
     int32_t num_bin_groups, bucket_w_log2, bucket_h_log2, buckets_x, num_buckets;
     uint32_t *bin_items_tmp;  // [ntiles][bin_stride] (deterministic mode: unsorted fill target)

@@ -1158,6 +1158,13 @@ int evplp_profile_passes(evplp_context *ctx, int32_t on);
 /* Raw device-side counters of the last run of `pass` (rays, node visits, pairs, aux, then the traversal histogram that
  * only -DEVPLP_TRAVERSAL_STATS=1 diagnostic builds fill).  Returns the number of 64-bit words written. */
 int evplp_debug_counters(evplp_context *ctx, int32_t pass, uint64_t *out, int32_t capacity);
+/* For tests: what the binning of the last photon splat left on the device.  Settles the pending splat as evplp_pass_stats_get does (an
+ * overflowed pass has run again: the arrays describe the pass whose result is in the accumulator), waits for the stream, then copies
+ * big_count (one word per bin group of 256 records: the photons of the group that went through the large-rectangle list, segment
+ * overflow included) and tile_cursor (one word per 8x8-pixel tile of this context's rows, row-major over local tile rows: the entries
+ * the tile's bin wanted).  n_groups / n_tiles must be the context's counts exactly ((records + 255) / 256, ((res_x + 7) / 8) x
+ * (local rows / 8)); either array may be null (its count is then ignored).  Launches nothing. */
+int evplp_debug_splat_bins(evplp_context *ctx, uint32_t *big_count, int32_t n_groups, uint32_t *tile_cursor, int32_t n_tiles);
 /* For tests: the acceleration structure as it is on the device, copied to the host.  which = 0 nodes (64 B each), 1 leaf blocks (192 B),
  * 2 the flat triangle operands (48 B per slot, 4 slots per block), 3 the slots' original triangle indices (int32, -1 = empty), 4 the
  * four-wide nodes (128 B), 5 one float: the box pad of the last build or refit (the host builders' formula), 6 four floats: the last refit's
