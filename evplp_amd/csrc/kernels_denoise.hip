@@ -5,7 +5,7 @@
 //   denoise_finish_kernel   remodulates the filtered pixels and copies the others from the composite
 // The packed pixel (DenoisePixel, kernels.h) carries everything the passes read, so that the strips of a group can be exchanged and assembled
 // as plain floats.  Every sum is taken in a fixed order, without atomics: a call is bit-reproducible.  The file is compiled without
-// floating-point contraction, so that the restatement in tests/test_gpu_denoise.py can follow the operation order.
+// floating-point contraction, so that the restatement in tests/denoise_hostile.py can follow the operation order.
 // No LDS staging: a pass reads 48 B per tap (u, position, normal) of a frame of 80 B per pixel (74 MB at 1280 x 720), which stays in the
 // Infinity Cache across the passes, and neighbouring lanes read neighbouring pixels; the passes are measured (tools/denoise_gain.py).
 #include "kernels.h"
@@ -15,10 +15,12 @@ namespace evplp {
 namespace {
 constexpr float kLumR = 0.2126f, kLumG = 0.7152f, kLumB = 0.0722f;
 __device__ inline float luminance(float r, float g, float b) { return (kLumR * r + kLumG * g) + kLumB * b; }
+__device__ inline bool is_finite(float x) { return fabsf(x) <= 3.4028235e38f; }       // false for Inf and for NaN
 }
 
 // rgb: the composite (scale, scale, light_scale, mask_emitter, no gamma), var: the noise tracker's variance at `scale`, both 3 floats per
-// plane pixel; the guides and the light plane of the same pixels.  Filtered: an image row, a surface (position.w != 0) and no emitter.
+// plane pixel; the guides and the light plane of the same pixels.  Filtered: an image row, a surface (position.w != 0), no emitter, and a
+// finite (u, s).
 __global__ __launch_bounds__(256) void denoise_prepare_kernel(StripDev st, const float *rgb, const float *var, const float4 *pos, const float4 *nrm,
                                                               const float4 *dif, const float4 *phg, const float4 *light, float4 *out) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -26,13 +28,19 @@ __global__ __launch_bounds__(256) void denoise_prepare_kernel(StripDev st, const
     if (i >= n) return;
     const int y = st.global_row((int)(i / (size_t)st.W));
     const float4 p = pos[i], nn = nrm[i], d = dif[i], ph = phg[i], li = light[i];
-    const bool filtered = y < st.H && p.w != 0.0f && li.x == 0.0f && li.y == 0.0f && li.z == 0.0f;
+    bool filtered = y < st.H && p.w != 0.0f && li.x == 0.0f && li.y == 0.0f && li.z == 0.0f;
     const float c[3] = { rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2] };
     const float a[3] = { fmaxf(d.x + ph.x, 1e-3f), fmaxf(d.y + ph.y, 1e-3f), fmaxf(d.z + ph.z, 1e-3f) };
     float4 u = make_float4(c[0], c[1], c[2], 0.0f);
     if (filtered) {
-        u.x = c[0] / a[0]; u.y = c[1] / a[1]; u.z = c[2] / a[2];
-        u.w = ((kLumR * kLumR) * var[3 * i] / (a[0] * a[0]) + (kLumG * kLumG) * var[3 * i + 1] / (a[1] * a[1])) + (kLumB * kLumB) * var[3 * i + 2] / (a[2] * a[2]);
+        float4 v;
+        v.x = c[0] / a[0]; v.y = c[1] / a[1]; v.z = c[2] / a[2];
+        v.w = ((kLumR * kLumR) * var[3 * i] / (a[0] * a[0]) + (kLumG * kLumG) * var[3 * i + 1] / (a[1] * a[1])) + (kLumB * kLumB) * var[3 * i + 2] / (a[2] * a[2]);
+        // a demodulated colour or an s that is not finite (an overflowed sample, c / a beyond fp32, a variance beyond fp32): not filtered.
+        // As a tap it would be weight 0 times Inf, a NaN in every pixel that reaches it, at every pass; position.w = 0 keeps it out of
+        // the passes, of the temporal accumulation and of the history alike.
+        filtered = is_finite(v.x) && is_finite(v.y) && is_finite(v.z) && is_finite(v.w);
+        if (filtered) u = v;
     }
     DenoisePixel o;
     o.u = u;

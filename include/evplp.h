@@ -897,6 +897,8 @@ int evplp_noise_variance(evplp_context *ctx, float scale, float *out_rgb);
  * adaptivity on, the retired tiles' frozen-rescaled variance).  It adds bias: evplp_noise_estimate does not describe the denoised image.
  * A pixel is filtered when its G-buffer position has w != 0, its light plane is zero in all three channels and it lies in the image; every
  * other pixel is the composite evplp_resolve(scale, scale, light_scale, mask_emitter, 0) gives, bit for bit, and is never a neighbour.
+ * A pixel whose u or s below, as fp32 computes them, is not finite (an overflowed or NaN sample, c / a or a variance beyond fp32) is not
+ * filtered either: it is that composite, is never a neighbour, and enters no history of evplp_denoise_temporal.
  * With c = the composite, v = its variance, a = max(diffuse + phong, 1e-3) per channel: u = c / a, s = sum_ch y_ch^2 v_ch / a_ch^2 with
  * y = (0.2126, 0.7152, 0.0722) (luminance l(u) = y . u).  Pass i = 0 .. levels - 1 at step h = 2^i: 5 x 5 taps at h (dx, dy), dy outer,
  * k = b(dx) b(dy) with b = [1, 4, 6, 4, 1] / 16, g_p = the 3 x 3 [1/4, 1/2, 1/4]^2 blur of s over filtered pixels (normalised), and

@@ -60,8 +60,11 @@ def pack(rgb, var, pos, nrm, dif, phg, light, image_rows):
     filt[image_rows:] = False
     a = np.maximum(dif[..., :3] + phg[..., :3], F(1e-3))
     yy = Y * Y
-    s = ((yy[0] * var[..., 0]) / (a[..., 0] * a[..., 0]) + (yy[1] * var[..., 1]) / (a[..., 1] * a[..., 1])) + (yy[2] * var[..., 2]) / (a[..., 2] * a[..., 2])
-    u = np.where(filt[..., None], rgb / a, rgb)
+    with np.errstate(over="ignore", invalid="ignore"):
+        s = ((yy[0] * var[..., 0]) / (a[..., 0] * a[..., 0]) + (yy[1] * var[..., 1]) / (a[..., 1] * a[..., 1])) + (yy[2] * var[..., 2]) / (a[..., 2] * a[..., 2])
+        uf = rgb / a
+    filt &= np.isfinite(uf).all(-1) & np.isfinite(s)              # a pixel whose demodulated colour or s is not finite is not filtered
+    u = np.where(filt[..., None], uf, rgb)
     return np.concatenate([u, np.where(filt, s, F(0))[..., None]], -1).astype(F), filt, a
 
 
