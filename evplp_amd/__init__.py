@@ -58,6 +58,12 @@ SURFACE_POINT_DTYPE = np.dtype([("pos", np.float32, 3), ("valid", np.float32), (
 SURFACE_LIGHT_DTYPE = np.dtype([("vpl", np.float32, 3), ("lit", np.float32), ("pm", np.float32, 3), ("photons", np.float32)])
 assert SURFACE_POINT_DTYPE.itemsize == 64 and SURFACE_LIGHT_DTYPE.itemsize == 32
 SURFACE_VPL, SURFACE_PHOTONS, SURFACE_CHUNK = 1, 2, 16384
+# progressive surface gather (evplp_surface_state: a point's unnormalised photon flux, squared radius, running VPL sums and counts; 48 zero
+# bytes are a fresh state)
+SURFACE_STATE_DTYPE = np.dtype([("tau", np.float32, 3), ("radius2", np.float32), ("vpl", np.float32, 3), ("n", np.float32),
+                                ("lit_sum", np.float32), ("vpl_calls", np.uint32), ("pm_calls", np.uint32), ("flags", np.uint32)])
+assert SURFACE_STATE_DTYPE.itemsize == 48
+STATE_INVALID = 1
 # lightmap baking (evplp_lightmap_texel: the resolved VPL sum, the coverage -- count / S^2, -d for a texel the gutter's pass d filled --, the
 # photon estimate and the mean pair count)
 LIGHTMAP_TEXEL_DTYPE = np.dtype([("vpl", np.float32, 3), ("coverage", np.float32), ("pm", np.float32, 3), ("photons", np.float32)])
@@ -220,6 +226,15 @@ _SIGNATURES = {
     "evplp_lightmap_cover": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "evplp_bake_lightmap": (C.c_int, [_P, _P, C.c_uint32, _P, _P, _P]),
     "evplp_bake_lightmap_device": (C.c_int, [_P, _P, C.c_uint32, _P, _P, _P]),
+    "evplp_gather_surface_progressive": (C.c_int, [_P, _P, C.c_uint32, C.c_float, _P, _P, C.c_int32, _P]),
+    "evplp_gather_surface_progressive_device": (C.c_int, [_P, _P, C.c_uint32, C.c_float, _P, _P, C.c_int32, _P]),
+    "evplp_surface_resolve": (C.c_int, [_P, _P, C.c_int32, _P]),
+    "evplp_surface_resolve_device": (C.c_int, [_P, _P, C.c_int32, _P]),
+    "evplp_bake_lightmap_progressive_device": (C.c_int, [_P, _P, C.c_uint32, C.c_float, _P, _P, _P]),
+    "evplp_bake_lightmap_resolve": (C.c_int, [_P, _P, _P, _P]),
+    "evplp_bake_lightmap_resolve_device": (C.c_int, [_P, _P, _P, _P]),
+    "evplp_surface_state_update": (C.c_int, [_P, C.c_uint32, _P, C.c_float, C.c_float]),
+    "evplp_surface_state_resolve": (C.c_int, [_P, _P]),
     "evplp_photon_grid_plan": (C.c_int, [C.c_float, _P, _P, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "evplp_photon_grid_cell": (C.c_uint32, [_P, _P, C.c_float, C.c_uint32, _P]),
     "evplp_photon_grid_range": (C.c_int, [_P, C.c_float, _P, _P, C.c_float, _P, _P]),
@@ -467,6 +482,25 @@ def photon_grid_range(x, radius: float, box_lo, box_hi, edge: float):
     c0, c1 = np.zeros(3, np.int32), np.zeros(3, np.int32)
     walked = lib().evplp_photon_grid_range(_ptr(p), float(radius), _ptr(lo), _ptr(hi), float(edge), _ptr(c0), _ptr(c1))
     return bool(walked), c0, c1
+
+
+def surface_state_update(state, m: int, phi, alpha: float, r0sq: float) -> np.ndarray:
+    """evplp_surface_state_update (host only): one SURFACE_STATE_DTYPE element after one photon half that found m photons of summed value
+    phi (float32 [3]) -- flagged and otherwise unchanged where its radius2 is out of range for r0sq -- as a new one-element array"""
+    s = np.array(np.asarray(state, dtype=SURFACE_STATE_DTYPE).reshape(1), copy=True)
+    p = _f32(phi).reshape(3)
+    if lib().evplp_surface_state_update(_ptr(s), int(m), _ptr(p), float(alpha), float(r0sq)) != OK:
+        raise ValueError("evplp_surface_state_update refused its arguments")
+    return s
+
+
+def surface_state_resolve(state) -> np.ndarray:
+    """evplp_surface_state_resolve (host only): one SURFACE_STATE_DTYPE element as a one-element SURFACE_LIGHT_DTYPE array"""
+    s = np.ascontiguousarray(np.asarray(state, dtype=SURFACE_STATE_DTYPE).reshape(1))
+    out = np.zeros(1, SURFACE_LIGHT_DTYPE)
+    if lib().evplp_surface_state_resolve(_ptr(s), _ptr(out)) != OK:
+        raise ValueError("evplp_surface_state_resolve refused its arguments")
+    return out
 
 
 def _ptr(a: Optional[np.ndarray]):
@@ -935,6 +969,89 @@ class Context:
         self._check(self._lib.evplp_bake_lightmap_device(self._h, C.byref(fp), int(what), C.byref(prm), C.c_void_p(u.data_ptr()) if u is not None else None,
                                                          C.c_void_p(out.data_ptr()) if out.numel() else None))
         self._query_inputs = u
+        return out
+
+    def gather_surface_progressive(self, points, fp: FrameParams, states, alpha: float = 2.0 / 3.0, eyes=None, what: int = SURFACE_VPL | SURFACE_PHOTONS):
+        """evplp_gather_surface_progressive: one iteration of the records into the points' states (mis_mode 0, 4, 5).  points, eyes as
+        gather_surface takes them; states: a SURFACE_STATE_DTYPE array (np.zeros is fresh), returned as a new array -- or, with points a
+        float32 tensor [n, 16] on the device, a float32 tensor [n, 12] there holding the states' bytes (torch.zeros is fresh), updated IN
+        PLACE through evplp_gather_surface_progressive_device: enqueued on the context's stream, not waited for, and returned."""
+        if _is_device(points):
+            import torch
+            if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 16:
+                raise ValueError(f"points must be a float32 tensor [n, 16], not {points.dtype} {tuple(points.shape)}")
+            d = points.contiguous()
+            if not _is_device(states) or states.dtype != torch.float32 or tuple(states.shape) != (d.shape[0], 12) or not states.is_contiguous():
+                raise ValueError("states must be a contiguous float32 tensor [n, 12] on the points' device")
+            e = None
+            if eyes is not None:
+                if not _is_device(eyes) or eyes.dtype != torch.float32 or tuple(eyes.shape) != (d.shape[0], 3):
+                    raise ValueError("eyes must be a float32 tensor [n, 3] on the points' device")
+                e = eyes.contiguous()
+            self._check(self._lib.evplp_gather_surface_progressive_device(self._h, C.byref(fp), int(what), float(alpha), C.c_void_p(d.data_ptr()),
+                                                                          C.c_void_p(e.data_ptr()) if e is not None else None, int(d.shape[0]),
+                                                                          C.c_void_p(states.data_ptr()) if d.shape[0] else None))
+            self._query_inputs = (d, e, states)     # (the launches read them after this call returns)
+            return states
+        x = np.ascontiguousarray(points, dtype=SURFACE_POINT_DTYPE).reshape(-1)
+        e = None
+        if eyes is not None:
+            e = np.ascontiguousarray(eyes, dtype=np.float32)
+            if e.shape != (x.shape[0], 3):
+                raise ValueError(f"eyes must be [n, 3] float32, not {e.shape}")
+        s = np.array(np.asarray(states, dtype=SURFACE_STATE_DTYPE).reshape(-1), copy=True)
+        if s.shape[0] != x.shape[0]:
+            raise ValueError(f"{s.shape[0]} states for {x.shape[0]} points")
+        self._check(self._lib.evplp_gather_surface_progressive(self._h, C.byref(fp), int(what), float(alpha), _ptr(x), _ptr(e), x.shape[0], _ptr(s)))
+        return s
+
+    def surface_resolve(self, states):
+        """evplp_surface_resolve: a SURFACE_STATE_DTYPE array as a SURFACE_LIGHT_DTYPE array; a float32 tensor [n, 12] on the device goes
+        through evplp_surface_resolve_device (enqueued, not waited for) and gives a float32 tensor [n, 8] there"""
+        if _is_device(states):
+            import torch
+            if states.dtype != torch.float32 or states.dim() != 2 or states.shape[1] != 12:
+                raise ValueError(f"states must be a float32 tensor [n, 12], not {states.dtype} {tuple(states.shape)}")
+            d = states.contiguous()
+            out = torch.empty((d.shape[0], 8), dtype=torch.float32, device=d.device)
+            self._check(self._lib.evplp_surface_resolve_device(self._h, C.c_void_p(d.data_ptr()), int(d.shape[0]), C.c_void_p(out.data_ptr())))
+            self._query_inputs = d
+            return out
+        s = np.ascontiguousarray(states, dtype=SURFACE_STATE_DTYPE).reshape(-1)
+        out = np.zeros(s.shape[0], SURFACE_LIGHT_DTYPE)
+        self._check(self._lib.evplp_surface_resolve(self._h, _ptr(s), s.shape[0], _ptr(out)))
+        return out
+
+    def bake_lightmap_progressive_device(self, fp: FrameParams, states, width: int, height: int, samples: int = 1, alpha: float = 2.0 / 3.0, mesh: int = -1,
+                                         flags: int = 0, uvs=None, what: int = SURFACE_VPL | SURFACE_PHOTONS):
+        """evplp_bake_lightmap_progressive_device: one iteration of the records into the atlas' states, a contiguous float32 tensor
+        [height * width * samples^2, 12] on the device (torch.zeros is fresh), updated in place and returned; waits once per band"""
+        import torch
+        n = max(int(width), 0) * max(int(height), 0) * max(int(samples), 0) ** 2
+        if not _is_device(states) or states.dtype != torch.float32 or tuple(states.shape) != (n, 12) or not states.is_contiguous():
+            raise ValueError(f"states must be a contiguous float32 tensor [{n}, 12] on the device")
+        u = _device_uvs(uvs, states.device)
+        prm = LightmapParams(int(mesh), int(width), int(height), int(samples), 0, int(flags))
+        self._check(self._lib.evplp_bake_lightmap_progressive_device(self._h, C.byref(fp), int(what), float(alpha), C.byref(prm),
+                                                                     C.c_void_p(u.data_ptr()) if u is not None else None, C.c_void_p(states.data_ptr()) if n else None))
+        self._query_inputs = (u, states)
+        return states
+
+    def bake_lightmap_resolve(self, states, width: int, height: int, samples: int = 1, gutter: int = 0):
+        """evplp_bake_lightmap_resolve: the atlas of the states (on the device) as a LIGHTMAP_TEXEL_DTYPE array [height, width]; waits"""
+        prm = LightmapParams(-1, int(width), int(height), int(samples), int(gutter), 0)
+        out = np.zeros((max(int(height), 0), max(int(width), 0)), LIGHTMAP_TEXEL_DTYPE)
+        self._check(self._lib.evplp_bake_lightmap_resolve(self._h, C.byref(prm), C.c_void_p(states.data_ptr()), _ptr(out) if out.size else None))
+        return out
+
+    def bake_lightmap_resolve_device(self, states, width: int, height: int, samples: int = 1, gutter: int = 0):
+        """evplp_bake_lightmap_resolve_device: as bake_lightmap_resolve, the result a float32 tensor [height, width, 8] on the states' device;
+        enqueued, not waited for"""
+        import torch
+        prm = LightmapParams(-1, int(width), int(height), int(samples), int(gutter), 0)
+        out = torch.empty((max(int(height), 0), max(int(width), 0), 8), dtype=torch.float32, device=states.device)
+        self._check(self._lib.evplp_bake_lightmap_resolve_device(self._h, C.byref(prm), C.c_void_p(states.data_ptr()), C.c_void_p(out.data_ptr()) if out.numel() else None))
+        self._query_inputs = states
         return out
 
     def triangle_info(self, triangle: int):

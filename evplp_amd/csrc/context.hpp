@@ -371,6 +371,9 @@ struct evplp_context {
     // evplp_gather_surface (surface_gather.cpp): the slices' partial sums and the photon half of ONE launch of kSurfaceChunk points; the photon grid of
     // one call (keys, slots, bucket starts, compact records, the sort's workspace: sized by the record slots); the host form's staging, 108 B per point.
     evplp::DeviceScratch surface_partial, surface_grid, surface_stage; char *h_surface_stage = nullptr;
+    // evplp_gather_surface_progressive / evplp_surface_resolve (surface_gather.cpp): the reduced VPL half of ONE launch of kSurfaceChunk points
+    // (32 B per point), and the host forms' staging, 156 B per point (point, eye, state: the resolve's states and results fit it).
+    evplp::DeviceScratch surface_prog_lights, surface_prog_stage; char *h_surface_prog_stage = nullptr;
     // evplp_surface_points / evplp_lightmap_samples / evplp_bake_lightmap (lightmap.cpp).  The host forms' staging of ONE chunk of kQueryChunk
     // hits (hit, eye, point: 92 B each; a band's hits fit it), on the device and pinned; the selection's set-up triangles (32 B each, and 24 B
     // each of uploaded uvs); a band's tile arrays (counts, offsets, cursors, the scan's workspace) and its pinned pair count; the tiles'

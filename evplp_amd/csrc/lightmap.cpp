@@ -4,6 +4,8 @@
 // results do not depend on it): per band the tiles' triangle counts, their exclusive sum, ONE read-back of the total to size the lists --
 // both forms wait there -- then the fill and the raster.  The bake chains, per band, raster -> points -> evplp_gather_surface_device ->
 // resolve, and ends with the gutter passes over the whole atlas.  The kernels are in kernels_lightmap.hip, the integers in lightmap_raster.h.
+// The progressive bake chains raster -> points -> evplp_gather_surface_progressive_device per band into the caller's states; its resolve
+// reads the states alone (kernels_surface_prog.hip) and ends with the same gutter passes.
 #include "context.hpp"
 #include "lightmap.hpp"
 #include "surface_gather.hpp"
@@ -229,6 +231,76 @@ int bake(evplp_context *c, const char *name, bool device, const evplp_frame_para
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return EVPLP_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------- the progressive bake
+// one iteration over the atlas: per band raster -> points -> evplp_gather_surface_progressive_device on the band's slice of the states
+int bake_progressive(evplp_context *c, const char *name, const evplp_frame_params *fp, uint32_t what, float alpha, const evplp_lightmap_params *p, const float *uvs, void *states) {
+    if (!p) { c->set_error("%s: null params", name); return EVPLP_ERR_INVALID; }
+    int32_t first, count;
+    if (!atlas_check(c, name, p->mesh, p->width, p->height, p->samples, &first, &count)) return EVPLP_ERR_INVALID;
+    // (params->gutter belongs to the resolve: not looked at here)
+    if (p->flags & ~EVPLP_POINTS_WHITE) { c->set_error("%s: unknown flag bits 0x%x", name, (unsigned)(p->flags & ~EVPLP_POINTS_WHITE)); return EVPLP_ERR_INVALID; }
+    if (!states) { c->set_error("%s: null states", name); return EVPLP_ERR_INVALID; }
+    if ((((uintptr_t)states) & 15u) != 0) { c->set_error("%s: the states are not 16-byte aligned", name); return EVPLP_ERR_INVALID; }
+    // what the progressive gather refuses, before anything is written: its own checks on an empty batch, and the walk's stack
+    int rc = evplp_gather_surface_progressive_device(c, fp, what, alpha, nullptr, nullptr, 0, nullptr);
+    if (rc) return rc;
+    if (surface_stack_bytes(c->sc) > kMaxStackBytes) { c->set_error("%s: the walk's stack of this tree (%zu bytes per wave) exceeds a workgroup's LDS", name, surface_stack_bytes(c->sc)); return EVPLP_ERR_INVALID; }
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    const int32_t W = p->width, H = p->height, s2 = p->samples * p->samples;
+    Raster r;
+    if ((rc = raster_prepare(c, name, true, first, count, uvs, W, H, p->samples, &r))) return rc;
+    const size_t band_samples = (size_t)W * s2 * (size_t)r.band;
+    const size_t hits_b = align256(sizeof(evplp_hit) * band_samples), points_b = align256(sizeof(evplp_surface_point) * band_samples);
+    const hipError_t e = grow_scratch_of(c, c->lm_bake, hits_b + points_b);
+    if (e != hipSuccess) { c->set_error("%s: cannot allocate a band's %zu samples (%zu bytes): %s", name, band_samples, hits_b + points_b, hipGetErrorString(e)); return oom_or_hip(e); }
+    char *d_hits = (char *)c->lm_bake.p, *d_points = d_hits + hits_b;
+    for (int32_t y0 = 0; y0 < H; y0 += r.band) {
+        const int32_t rows = std::min(r.band, H - y0);
+        const int32_t n = (int32_t)((size_t)W * s2 * (size_t)rows);
+        if ((rc = raster_band(c, name, &r, y0, rows, (evplp_hit *)d_hits))) return rc;
+        launch_lightmap_points(points_args(c, d_hits, nullptr, d_points, n, p->flags), c->stream);
+        HIP_TRY(c, hipGetLastError());
+        evplp_surface_state *band = (evplp_surface_state *)states + (size_t)W * s2 * (size_t)y0;
+        if ((rc = evplp_gather_surface_progressive_device(c, fp, what, alpha, d_points, nullptr, n, band))) return rc;
+    }
+    return EVPLP_OK;
+}
+
+// the states of an atlas -> its texels, then the gutter passes of the bake.  No raster: a state says itself whether its sample was covered.
+int bake_resolve(evplp_context *c, const char *name, bool device, const evplp_lightmap_params *p, const void *states, void *out) {
+    if (!p) { c->set_error("%s: null params", name); return EVPLP_ERR_INVALID; }
+    if (p->width < 1 || p->width > LM_MAX_SIZE || p->height < 1 || p->height > LM_MAX_SIZE) { c->set_error("%s: an atlas of %d x %d is not within 1 .. %d", name, p->width, p->height, LM_MAX_SIZE); return EVPLP_ERR_INVALID; }
+    if (p->samples != 1 && p->samples != 2 && p->samples != 4) { c->set_error("%s: %d samples per axis is not 1, 2 or 4", name, p->samples); return EVPLP_ERR_INVALID; }
+    if (p->gutter < 0 || p->gutter > 8) { c->set_error("%s: a gutter of %d is not 0 .. 8", name, p->gutter); return EVPLP_ERR_INVALID; }
+    if (!states || !out) { c->set_error("%s: null states or destination", name); return EVPLP_ERR_INVALID; }
+    if ((((uintptr_t)states) & 15u) != 0 || (device && (((uintptr_t)out) & 15u) != 0)) { c->set_error("%s: the states or the destination are not 16-byte aligned", name); return EVPLP_ERR_INVALID; }
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    const int32_t W = p->width, H = p->height;
+    const size_t texels = (size_t)W * (size_t)H, atlas = align256(sizeof(evplp_lightmap_texel) * texels);
+    const int own = (device ? 0 : 1) + (p->gutter > 0 ? 1 : 0);
+    const hipError_t e = grow_scratch_of(c, c->lm_atlas, atlas * (size_t)own);
+    if (e != hipSuccess) { c->set_error("%s: cannot allocate %d atlas buffers of %d x %d texels: %s", name, own, W, H, hipGetErrorString(e)); return oom_or_hip(e); }
+    evplp_lightmap_texel *cur = device ? (evplp_lightmap_texel *)out : (evplp_lightmap_texel *)c->lm_atlas.p;
+    evplp_lightmap_texel *other = p->gutter > 0 ? (evplp_lightmap_texel *)((char *)c->lm_atlas.p + (device ? 0 : atlas)) : nullptr;
+    // (a launch takes at most 2^31 - 1 texels: the largest atlas has 2^26)
+    LightmapProgResolveArgs ra; ra.states = (const float4 *)states; ra.out = cur; ra.texels = (int32_t)texels; ra.s2 = p->samples * p->samples;
+    launch_lightmap_prog_resolve(ra, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    for (int32_t d = 1; d <= p->gutter; d++) {
+        GutterArgs g; g.from = cur; g.to = other; g.width = W; g.height = H; g.pass = d;
+        launch_lightmap_gutter(g, c->stream);
+        HIP_TRY(c, hipGetLastError());
+        std::swap(cur, other);
+    }
+    if (device) {
+        if (cur != out) HIP_TRY(c, hipMemcpyAsync(out, cur, sizeof(evplp_lightmap_texel) * texels, hipMemcpyDeviceToDevice, c->stream));
+        return EVPLP_OK;
+    }
+    HIP_TRY(c, hipMemcpyAsync(out, cur, sizeof(evplp_lightmap_texel) * texels, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return EVPLP_OK;
+}
 }
 
 namespace evplp {
@@ -263,4 +335,16 @@ extern "C" int evplp_bake_lightmap(evplp_context *c, const evplp_frame_params *f
 extern "C" int evplp_bake_lightmap_device(evplp_context *c, const evplp_frame_params *fp, uint32_t what, const evplp_lightmap_params *p, const void *d_uvs, void *d_out) {
     CTX_CHECK(c);
     return bake(c, "evplp_bake_lightmap_device", true, fp, what, p, (const float *)d_uvs, d_out);
+}
+extern "C" int evplp_bake_lightmap_progressive_device(evplp_context *c, const evplp_frame_params *fp, uint32_t what, float alpha, const evplp_lightmap_params *p, const void *d_uvs, void *d_states) {
+    CTX_CHECK(c);
+    return bake_progressive(c, "evplp_bake_lightmap_progressive_device", fp, what, alpha, p, (const float *)d_uvs, d_states);
+}
+extern "C" int evplp_bake_lightmap_resolve(evplp_context *c, const evplp_lightmap_params *p, const void *d_states, evplp_lightmap_texel *out) {
+    CTX_CHECK(c);
+    return bake_resolve(c, "evplp_bake_lightmap_resolve", false, p, d_states, out);
+}
+extern "C" int evplp_bake_lightmap_resolve_device(evplp_context *c, const evplp_lightmap_params *p, const void *d_states, void *d_out) {
+    CTX_CHECK(c);
+    return bake_resolve(c, "evplp_bake_lightmap_resolve_device", true, p, d_states, d_out);
 }

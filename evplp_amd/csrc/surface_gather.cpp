@@ -2,6 +2,9 @@
 // of at most kSurfaceChunk points (surface_gather.hpp), so the partial sums and the host form's staging have one size whatever n is; the
 // photon grid is built once per call, before the first chunk, for the call's radius and the records as they are.  The kernels are in
 // kernels_surface.hip, the grid's arithmetic in photon_grid.h.
+// The progressive gather (include/evplp.h "progressive surface gather": evplp_gather_surface_progressive, evplp_surface_resolve and their
+// device forms) lives here too, behind the same checks, chunks and grid build: its own kernels are in kernels_surface_prog.hip, a state's
+// rule in surface_state.h.
 #include "context.hpp"
 #include "photon_grid.h"
 #include "surface_gather.hpp"
@@ -57,7 +60,7 @@ void scene_box(const evplp_context *c, float lo[3], float hi[3]) {
 
 // the grid of this call: plan, arrays, build.  The bucket count comes from the SLOT count -- an upper bound of the usable photons the host
 // knows without reading anything back, so the device form never waits; the results do not depend on it.
-int build_grid(evplp_context *c, const char *name, const evplp_frame_params *fp, SurfaceGrid *out) {
+int build_grid(evplp_context *c, const char *name, const evplp_frame_params *fp, SurfaceGrid *out, SurfaceGridBuild *build = nullptr) {
     SurfaceGridBuild b; std::memset(&b, 0, sizeof(b));
     const uint32_t slots = fp->num_light_paths * fp->photons_per_path;           // (checked against the record buffer: it fits 32 bits)
     scene_box(c, b.g.lo, b.g.hi);
@@ -80,6 +83,7 @@ int build_grid(evplp_context *c, const char *name, const evplp_frame_params *fp,
     b.g.start = b.start; b.g.compact = b.compact;
     HIP_TRY(c, launch_surface_grid(b, c->stream));
     *out = b.g;
+    if (build) *build = b;                  // (the progressive gather rewrites the compact records' flux behind the build)
     return EVPLP_OK;
 }
 
@@ -145,14 +149,143 @@ int gather(evplp_context *c, const char *name, bool device, const evplp_frame_pa
     if (c->aux_stream) HIP_TRY(c, hipEventRecord(c->ev_records_read, c->stream));
     return EVPLP_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------- the progressive gather
+// the host forms' staging: the points, the eyes behind them, the states behind those (the resolve puts its states there and its results first)
+constexpr size_t kProgStageStates = sizeof(evplp_surface_state) * (size_t)kSurfaceChunk;
+constexpr size_t kProgStageBytes = kStagePoints + kStageEyes + kProgStageStates;
+constexpr size_t kProgLightsBytes = sizeof(evplp_surface_light) * (size_t)kSurfaceChunk;
+static_assert(sizeof(evplp_surface_light) <= sizeof(evplp_surface_point), "the resolve's results fit the points' part of the staging");
+
+int prog_stage(evplp_context *c, const char *name) {
+    hipError_t e = grow_scratch_of(c, c->surface_prog_stage, kProgStageBytes);
+    if (e == hipSuccess && !c->h_surface_prog_stage) {
+        e = hipHostMalloc((void **)&c->h_surface_prog_stage, kProgStageBytes, hipHostMallocDefault);
+        if (e != hipSuccess) { (void)hipGetLastError(); c->h_surface_prog_stage = nullptr; }
+    }
+    if (e != hipSuccess) { c->set_error("%s: cannot allocate the staging of %d points (%zu bytes): %s", name, kSurfaceChunk, kProgStageBytes, hipGetErrorString(e)); return oom_or_hip(e); }
+    return EVPLP_OK;
+}
+
+// One iteration.  Per chunk: today's VPL kernel into the partial sums, today's reduce into 32 B per point, the fold into the states; the
+// query walks behind the fold -- chunk by chunk in the host form, once over the whole batch in the device form -- so both halves decide
+// "flagged" from the state as it came in.
+int gather_progressive(evplp_context *c, const char *name, bool device, const evplp_frame_params *fp, uint32_t what, float alpha, const void *points, const float *eyes, int32_t n, void *states) {
+    // (the states first, by their name: surface_check would call them "the destination")
+    if (n > 0 && !states) { c->set_error("%s: null states", name); return EVPLP_ERR_INVALID; }
+    if (device && n > 0 && (((uintptr_t)states) & 15u) != 0) { c->set_error("%s: the states are not 16-byte aligned", name); return EVPLP_ERR_INVALID; }
+    if (!surface_check(c, name, device, fp, what, points, eyes, n, states)) return EVPLP_ERR_INVALID;
+    if (fp->mis_mode >= 1u && fp->mis_mode <= 3u) {
+        c->set_error("%s: mis_mode %u weighs by pdf_mc = n_vpl / n_light / (pi r^2), which a radius per point makes a per-point quantity in both halves: only modes 0, 4 and 5", name, (unsigned)fp->mis_mode);
+        return EVPLP_ERR_INVALID;
+    }
+    if (!std::isfinite(alpha) || !(alpha > 0.0f) || alpha > 1.0f) { c->set_error("%s: alpha %g is not within (0, 1]", name, (double)alpha); return EVPLP_ERR_INVALID; }
+    if (n == 0) return EVPLP_OK;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    const size_t lds = surface_stack_bytes(c->sc);
+    if (lds > kMaxStackBytes) { c->set_error("%s: the walk's stack of this tree (%zu bytes per wave) exceeds a workgroup's LDS", name, lds); return EVPLP_ERR_INVALID; }
+    const bool vpl = (what & EVPLP_SURFACE_VPL) != 0u, photons = (what & EVPLP_SURFACE_PHOTONS) != 0u;
+    const uint32_t slots = vpl ? fp->num_vpl_light_paths * fp->photons_per_path : 0u;
+    const uint32_t slices = surface_slices(slots);
+    if (vpl) {
+        hipError_t e = grow_scratch_of(c, c->surface_partial, surface_partial_bytes(slices));
+        if (e == hipSuccess) e = grow_scratch_of(c, c->surface_prog_lights, kProgLightsBytes);
+        if (e != hipSuccess) { c->set_error("%s: cannot allocate the partial sums of %u slices (%zu bytes): %s", name, slices, surface_partial_bytes(slices) + kProgLightsBytes, hipGetErrorString(e)); return oom_or_hip(e); }
+    }
+    int rc;
+    if (!device && (rc = prog_stage(c, name))) return rc;
+    SurfaceProgArgs q; std::memset(&q, 0, sizeof(q));
+    q.fp = *fp; q.what = what; q.alpha = alpha; q.r0sq = fp->photon_radius * fp->photon_radius;
+    q.lights = (const float4 *)c->surface_prog_lights.p;
+    if (photons) {
+        SurfaceGridBuild b;
+        if ((rc = build_grid(c, name, fp, &q.grid, &b))) return rc;
+        launch_surface_prog_compact(b, c->stream);
+        HIP_TRY(c, hipGetLastError());
+    }
+    for (int64_t at = 0; at < n; at += kSurfaceChunk) {
+        const int32_t m = (int32_t)std::min<int64_t>(kSurfaceChunk, n - at);
+        q.n = m;
+        char *h = c->h_surface_prog_stage, *d = (char *)c->surface_prog_stage.p;
+        if (device) {
+            q.points = (const float4 *)points + 4 * (size_t)at; q.eyes = eyes ? eyes + 3 * (size_t)at : nullptr; q.states = (float4 *)states + 3 * (size_t)at;
+        } else {
+            std::memcpy(h, (const evplp_surface_point *)points + at, sizeof(evplp_surface_point) * (size_t)m);
+            if (eyes) std::memcpy(h + kStagePoints, eyes + 3 * (size_t)at, 3 * sizeof(float) * (size_t)m);
+            std::memcpy(h + kStagePoints + kStageEyes, (const evplp_surface_state *)states + at, sizeof(evplp_surface_state) * (size_t)m);
+            HIP_TRY(c, hipMemcpyAsync(d, h, sizeof(evplp_surface_point) * (size_t)m, hipMemcpyHostToDevice, c->stream));
+            if (eyes) HIP_TRY(c, hipMemcpyAsync(d + kStagePoints, h + kStagePoints, 3 * sizeof(float) * (size_t)m, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(d + kStagePoints + kStageEyes, h + kStagePoints + kStageEyes, sizeof(evplp_surface_state) * (size_t)m, hipMemcpyHostToDevice, c->stream));
+            q.points = (const float4 *)d; q.eyes = eyes ? (const float *)(d + kStagePoints) : nullptr; q.states = (float4 *)(d + kStagePoints + kStageEyes);
+        }
+        if (vpl) {
+            SurfaceArgs a; std::memset(&a, 0, sizeof(a));
+            a.sc = c->sc; a.fp = *fp; a.records = (const evplp_record *)c->buf[EVPLP_BUF_RECORDS]; a.n = m; a.what = EVPLP_SURFACE_VPL; a.slots = slots; a.slices = slices;
+            a.pdf_mc2 = fp->pdf_mc * fp->pdf_mc; a.paths = (float)fp->num_vpl_light_paths;
+            a.partial = (float *)c->surface_partial.p;
+            a.points = q.points; a.eyes = q.eyes; a.out = (evplp_surface_light *)c->surface_prog_lights.p;
+            launch_surface_vpl(a, c->stream);
+            launch_surface_reduce(a, c->stream);
+            launch_surface_prog_fold(q, c->stream);
+        }
+        if (photons && !device) launch_surface_prog_photons(q, c->stream);
+        HIP_TRY(c, hipGetLastError());
+        if (!device) {
+            HIP_TRY(c, hipMemcpyAsync(h + kStagePoints + kStageEyes, q.states, sizeof(evplp_surface_state) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            std::memcpy((evplp_surface_state *)states + at, h + kStagePoints + kStageEyes, sizeof(evplp_surface_state) * (size_t)m);
+        }
+    }
+    if (photons && device) {
+        q.n = n; q.points = (const float4 *)points; q.eyes = eyes; q.states = (float4 *)states;
+        launch_surface_prog_photons(q, c->stream);
+        HIP_TRY(c, hipGetLastError());
+    }
+    if (c->aux_stream) HIP_TRY(c, hipEventRecord(c->ev_records_read, c->stream));
+    return EVPLP_OK;
+}
+
+int resolve_states(evplp_context *c, const char *name, bool device, const void *states, int32_t n, void *out) {
+    if (n < 0) { c->set_error("%s: n = %d", name, n); return EVPLP_ERR_INVALID; }
+    if (n > 0 && (!states || !out)) { c->set_error("%s: null states or destination", name); return EVPLP_ERR_INVALID; }
+    if (device && n > 0 && ((((uintptr_t)out) | ((uintptr_t)states)) & 15u) != 0) { c->set_error("%s: the states or the destination are not 16-byte aligned", name); return EVPLP_ERR_INVALID; }
+    if (n == 0) return EVPLP_OK;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    SurfaceResolveArgs a;
+    if (device) {
+        a.states = (const float4 *)states; a.out = (float4 *)out; a.n = n;
+        launch_surface_prog_resolve(a, c->stream);
+        HIP_TRY(c, hipGetLastError());
+        return EVPLP_OK;
+    }
+    int rc;
+    if ((rc = prog_stage(c, name))) return rc;
+    char *h = c->h_surface_prog_stage, *d = (char *)c->surface_prog_stage.p;
+    for (int64_t at = 0; at < n; at += kSurfaceChunk) {
+        const int32_t m = (int32_t)std::min<int64_t>(kSurfaceChunk, n - at);
+        const size_t off = kStagePoints + kStageEyes;
+        std::memcpy(h + off, (const evplp_surface_state *)states + at, sizeof(evplp_surface_state) * (size_t)m);
+        HIP_TRY(c, hipMemcpyAsync(d + off, h + off, sizeof(evplp_surface_state) * (size_t)m, hipMemcpyHostToDevice, c->stream));
+        a.states = (const float4 *)(d + off); a.out = (float4 *)d; a.n = m;
+        launch_surface_prog_resolve(a, c->stream);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(h, d, sizeof(evplp_surface_light) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        std::memcpy((evplp_surface_light *)out + at, h, sizeof(evplp_surface_light) * (size_t)m);
+    }
+    return EVPLP_OK;
+}
 }
 
 namespace evplp {
 void release_surface_gather(evplp_context *c) {
     hipFree(c->surface_partial.p); hipFree(c->surface_grid.p); hipFree(c->surface_stage.p);
+    hipFree(c->surface_prog_lights.p); hipFree(c->surface_prog_stage.p);
     c->surface_partial = DeviceScratch(); c->surface_grid = DeviceScratch(); c->surface_stage = DeviceScratch();
+    c->surface_prog_lights = DeviceScratch(); c->surface_prog_stage = DeviceScratch();
     if (c->h_surface_stage) hipHostFree(c->h_surface_stage);
-    c->h_surface_stage = nullptr;
+    if (c->h_surface_prog_stage) hipHostFree(c->h_surface_prog_stage);
+    c->h_surface_stage = nullptr; c->h_surface_prog_stage = nullptr;
 }
 }
 
@@ -163,4 +296,20 @@ extern "C" int evplp_gather_surface(evplp_context *c, const evplp_frame_params *
 extern "C" int evplp_gather_surface_device(evplp_context *c, const evplp_frame_params *fp, uint32_t what, const void *d_points, const void *d_eyes, int32_t n, void *d_out) {
     CTX_CHECK(c);
     return gather(c, "evplp_gather_surface_device", true, fp, what, d_points, (const float *)d_eyes, n, d_out);
+}
+extern "C" int evplp_gather_surface_progressive(evplp_context *c, const evplp_frame_params *fp, uint32_t what, float alpha, const evplp_surface_point *points, const float *eyes, int32_t n, evplp_surface_state *states) {
+    CTX_CHECK(c);
+    return gather_progressive(c, "evplp_gather_surface_progressive", false, fp, what, alpha, points, eyes, n, states);
+}
+extern "C" int evplp_gather_surface_progressive_device(evplp_context *c, const evplp_frame_params *fp, uint32_t what, float alpha, const void *d_points, const void *d_eyes, int32_t n, void *d_states) {
+    CTX_CHECK(c);
+    return gather_progressive(c, "evplp_gather_surface_progressive_device", true, fp, what, alpha, d_points, (const float *)d_eyes, n, d_states);
+}
+extern "C" int evplp_surface_resolve(evplp_context *c, const evplp_surface_state *states, int32_t n, evplp_surface_light *out) {
+    CTX_CHECK(c);
+    return resolve_states(c, "evplp_surface_resolve", false, states, n, out);
+}
+extern "C" int evplp_surface_resolve_device(evplp_context *c, const void *d_states, int32_t n, void *d_out) {
+    CTX_CHECK(c);
+    return resolve_states(c, "evplp_surface_resolve_device", true, d_states, n, d_out);
 }

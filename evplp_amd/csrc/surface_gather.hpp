@@ -54,4 +54,28 @@ void launch_surface_vpl(const SurfaceArgs &a, hipStream_t s);      // one wave p
 void launch_surface_photons(const SurfaceArgs &a, hipStream_t s);  // lane = point -> the second half of out
 void launch_surface_reduce(const SurfaceArgs &a, hipStream_t s);   // partial -> the first half of out
 
+// The progressive gather (evplp_gather_surface_progressive; kernels_surface_prog.hip).  The VPL half and the grid build are the kernels
+// above; the new unit rewrites the compact records' flux without InvPi / r^2, walks with the lane's own radius into the lane's state,
+// folds the reduced VPL half in, and resolves.
+static_assert(sizeof(evplp_surface_state) == 48, "a state is three float4");
+struct SurfaceProgArgs {
+    evplp_frame_params fp;        // mis_mode (0, 4, 5), clamping_value, photon_radius, num_light_paths; camera_pos where eyes is null
+    const float4 *points;         // [n][4]
+    const float *eyes;            // [n][3] or null
+    const float4 *lights;         // [n][2]: the reduce's evplp_surface_light of this launch (the fold reads the first 16 bytes)
+    float4 *states;               // [n][3]: evplp_surface_state, in and out
+    int32_t n;                    // <= kSurfaceChunk for the fold; the query and the resolve take any number
+    uint32_t what;
+    float alpha, r0sq;            // r0sq = fl(photon_radius * photon_radius)
+    SurfaceGrid grid;
+};
+struct SurfaceResolveArgs { const float4 *states; float4 *out; int32_t n; };     // [n][3] -> [n][2]
+// states of an atlas -> its texels (evplp_bake_lightmap_resolve): lane = texel over its s2 samples' states
+struct LightmapProgResolveArgs { const float4 *states; evplp_lightmap_texel *out; int32_t texels, s2; };
+void launch_surface_prog_compact(const SurfaceGridBuild &b, hipStream_t s);      // behind launch_surface_grid: wflux = flux / num_light_paths
+void launch_surface_prog_fold(const SurfaceProgArgs &a, hipStream_t s);
+void launch_surface_prog_photons(const SurfaceProgArgs &a, hipStream_t s);
+void launch_surface_prog_resolve(const SurfaceResolveArgs &a, hipStream_t s);
+void launch_lightmap_prog_resolve(const LightmapProgResolveArgs &a, hipStream_t s);
+
 }

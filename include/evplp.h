@@ -163,7 +163,8 @@ typedef struct evplp_config {
      *   surface gather (after a call)   256 KB of partial sums per slice of 256 VPL slots, and with EVPLP_SURFACE_PHOTONS 96 B per photon
      *                                   slot + 4 B per bucket (at most the slots rounded up to a power of two) + the radix sort's workspace: the grid
      *                                   of one call, 200 MB at 2 M slots; the host form 108 B per point of a chunk of 16 384 on the device and pinned
-     *                                   (evplp_gather_surface); none of it depends on the number of points
+     *                                   (evplp_gather_surface); none of it depends on the number of points.  The progressive calls: the same,
+     *                                   + 512 KB (the reduced VPL half of a chunk) and their host forms 156 B per point of a chunk, device and pinned
      * A caller that has the device to itself sets cut_scratch_bytes = 72 GB, vsl_mask_bytes = 14 GB for config #5 (one band, one launch). */
     uint64_t cut_scratch_bytes;
     uint64_t vsl_mask_bytes;
@@ -753,6 +754,67 @@ int evplp_lightmap_cover(const float uv6[6], int32_t width, int32_t height, int3
 int evplp_bake_lightmap(evplp_context *ctx, const evplp_frame_params *fp, uint32_t what /* EVPLP_SURFACE_VPL | _PHOTONS */, const evplp_lightmap_params *params,
                         const float *uvs, evplp_lightmap_texel *out /* width*height, row y = 0 at v = 0 */);
 int evplp_bake_lightmap_device(evplp_context *ctx, const evplp_frame_params *fp, uint32_t what, const evplp_lightmap_params *params, const void *d_uvs, void *d_out);
+
+/* ---- progressive surface gather: per-point photon statistics with per-point radii (INTEGRATION B12) ----
+ * evplp_gather_surface answers one record buffer at one radius.  These calls fold one record buffer after another into a state the caller
+ * keeps per point -- stochastic progressive photon mapping (Hachisuka and Jensen 2009): every point has its own squared radius, its own
+ * photon count and its own unnormalised flux, and the radius shrinks where photons arrive.
+ *   A state is 48 B; 48 zero bytes are a fresh state, the caller clears the array, there is no init call.
+ *   Only mis_mode 0, 4 and 5.  pdf_mc = n_vpl / n_light / (pi r^2) would be a per-point quantity and enter both halves per pair in modes
+ *     1 - 3; in modes 0, 4 and 5 nothing reads it, the VPL half does not depend on the radius and the photon-side weight is 1.
+ *   One call, per point, with alpha in (0, 1] and r0sq = fl(fp->photon_radius * fp->photon_radius); every operation rounded to fp32 on
+ *   its own, divisions IEEE's:
+ *     valid == 0 (the stencil): the state is not touched at all.
+ *     A point or eye that is not finite: flags |= EVPLP_STATE_INVALID, nothing else is touched, nothing is walked.  The same for a state
+ *       with pm_calls > 0 whose radius2 is not finite, <= 0 or > r0sq, in a call that asks for photons: fp->photon_radius is the call's
+ *       bound -- the grid is planned for it, and radii only shrink.
+ *     EVPLP_SURFACE_VPL: vpl += v, lit_sum += lit with v, lit exactly the 16 bytes evplp_gather_surface writes for the point; vpl_calls++.
+ *     EVPLP_SURFACE_PHOTONS: radius2 = r0sq first if pm_calls == 0.  The cells of the point's range in ascending (z, y, x), in a bucket in
+ *       ascending slot, the photons whose own cell is the visited one (evplp_gather_surface's order); outside iff, with dv = P_k - X,
+ *       (dv.x dv.x + dv.y dv.y) + dv.z dv.z > radius2.  M = the number inside (discarded fragments included, as `photons` counts them),
+ *       Phi = the fp32 sum in visiting order of the fragment's value in modes 0 / 4 / 5 with the photon-side factor
+ *       flux * rcp((float)num_light_paths): InvPi * uInvPhotonRadius2 is taken out.  If M > 0:
+ *           Nn = n + alpha (float)M;  ratio = Nn / (n + (float)M);  radius2 = radius2 ratio;  tau = (tau + Phi) ratio;  n = Nn
+ *       else tau, radius2 and n keep their bytes.  pm_calls++.
+ *       The range is evplp_photon_grid_range's on the grid planned for fp->photon_radius, with a per-point bound of sqrt(radius2) that
+ *       never exceeds fp->photon_radius and is made without a square root (surface_state.h states why the proof of the pad holds).
+ *   A point's state after a call is a function of its state before, the point and its eye, the records, fp->photon_radius, alpha, the
+ *     scene's box and the tree -- not of n, its index, the chunking, the form or EVPLP_SURFACE_GRID_BITS.
+ *   Resolve, to an evplp_surface_light: vpl = vpl / (float)vpl_calls, lit = lit_sum / (float)vpl_calls,
+ *     pm = (tau * InvPi) / (radius2 * (float)pm_calls), photons = n.  A half with 0 calls: zeros.  EVPLP_STATE_INVALID: zeros with
+ *     lit = photons = -1.  A fresh state: 32 zero bytes.
+ *   Forms, chunking and scratch as evplp_gather_surface: the host forms stage EVPLP_SURFACE_CHUNK points at a time (48 B more per point,
+ *     each way) and wait; the _device forms take device pointers (states 16-byte aligned as the points are), enqueue and do not wait.
+ *     evplp_surface_resolve (host) goes through the device kernel, staged.  Beyond evplp_gather_surface's scratch: 32 B per point of a chunk.
+ *   EVPLP_ERR_INVALID, nothing written, the context usable: everything evplp_gather_surface refuses; mis_mode 1 - 3; an alpha that is
+ *     not finite or outside (0, 1]; null states with n > 0; a _device state pointer that is not 16-byte aligned.  n = 0: EVPLP_OK.
+ *   The bake.  evplp_bake_lightmap_progressive_device is one iteration over the atlas: per band raster -> points -> the progressive gather
+ *     on that band's slice of d_states (width * height * samples^2 states, the samples' order; eyes NULL).  The raster is repeated per
+ *     call, so the call keeps no per-atlas memory; an uncovered sample's point has valid = 0 and its state stays fresh.  params->flags is
+ *     read by this call only; gutter by the resolve only.  evplp_bake_lightmap_resolve needs no raster: a sample counts when
+ *     vpl_calls + pm_calls > 0 and EVPLP_STATE_INVALID is clear; a texel takes the fp32 sums of its samples' resolved vpl, pm and photons
+ *     in ascending (j, i) divided by their count, coverage = count / S^2; then `gutter` passes with evplp_bake_lightmap's rule.  The
+ *     states stay on the device in both forms of the resolve (201 MB at 1024^2, S = 2); the host form copies the atlas out and waits.
+ *   Host only, no GPU, the functions the kernels call: evplp_surface_state_update applies one photon half (M photons, their summed value
+ *     phi) to one state, the out-of-range decision included; evplp_surface_state_resolve resolves one. */
+#define EVPLP_STATE_INVALID 1u
+typedef struct evplp_surface_state {       /* 48 B, 16-byte aligned on the device */
+    float tau[3];  float radius2;          /* unnormalised photon flux; the point's squared radius */
+    float vpl[3];  float n;                /* running fp32 sum of the VPL half; N, the photons kept so far */
+    float lit_sum; uint32_t vpl_calls, pm_calls, flags;   /* EVPLP_STATE_INVALID */
+} evplp_surface_state;
+int evplp_gather_surface_progressive(evplp_context *ctx, const evplp_frame_params *fp, uint32_t what, float alpha, const evplp_surface_point *points,
+                                     const float *eyes /* n x 3 or NULL */, int32_t n, evplp_surface_state *states /* in and out */);
+int evplp_gather_surface_progressive_device(evplp_context *ctx, const evplp_frame_params *fp, uint32_t what, float alpha, const void *d_points,
+                                            const void *d_eyes, int32_t n, void *d_states);
+int evplp_surface_resolve(evplp_context *ctx, const evplp_surface_state *states, int32_t n, evplp_surface_light *out);
+int evplp_surface_resolve_device(evplp_context *ctx, const void *d_states, int32_t n, void *d_out);
+int evplp_bake_lightmap_progressive_device(evplp_context *ctx, const evplp_frame_params *fp, uint32_t what, float alpha, const evplp_lightmap_params *params,
+                                           const void *d_uvs, void *d_states /* width*height*samples^2 states */);
+int evplp_bake_lightmap_resolve(evplp_context *ctx, const evplp_lightmap_params *params, const void *d_states, evplp_lightmap_texel *out /* host */);
+int evplp_bake_lightmap_resolve_device(evplp_context *ctx, const evplp_lightmap_params *params, const void *d_states, void *d_out);
+int evplp_surface_state_update(evplp_surface_state *state, uint32_t m, const float phi[3], float alpha, float r0sq);
+int evplp_surface_state_resolve(const evplp_surface_state *state, evplp_surface_light *out);
 
 /* ---- the per-iteration passes of RtComPhoton::run() (rtcomphoton.h:936-1068) ---- */
 /* [deferredShading] + [lightRender]: runDeferredProgram (:710-754) + runLightProgram (:839-855);
