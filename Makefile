@@ -7,7 +7,7 @@ OUT = evplp_amd/lib
 HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-variable -Wno-unused-value -munsafe-fp-atomics -fno-slp-vectorize $(EXTRA_HIPFLAGS)
 HOSTFLAGS = -O2 -std=c++17 -fPIC -Wall -Wno-unused-value -ffp-contract=off
 
-HIP_SRCS = $(CSRC)/kernels_trace.hip $(CSRC)/kernels_gather.hip $(CSRC)/kernels_cut.hip $(CSRC)/kernels_splat.hip $(CSRC)/kernels_pt.hip $(CSRC)/kernels_ptbatch.hip $(CSRC)/kernels_ptbatch_primary.hip $(CSRC)/kernels_stats.hip $(CSRC)/kernels_denoise.hip $(CSRC)/kernels_temporal.hip $(CSRC)/kernels_query.hip $(CSRC)/kernels_probe.hip $(CSRC)/kernels_surface.hip $(CSRC)/kernels_surface_prog.hip $(CSRC)/kernels_lightmap.hip $(CSRC)/bvh_gpu.hip $(CSRC)/selftest.hip
+HIP_SRCS = $(CSRC)/kernels_trace.hip $(CSRC)/kernels_gather.hip $(CSRC)/kernels_cut.hip $(CSRC)/kernels_splat.hip $(CSRC)/kernels_pt.hip $(CSRC)/kernels_ptbatch.hip $(CSRC)/kernels_ptbatch_primary.hip $(CSRC)/kernels_stats.hip $(CSRC)/kernels_denoise.hip $(CSRC)/kernels_temporal.hip $(CSRC)/kernels_query.hip $(CSRC)/kernels_probe.hip $(CSRC)/kernels_surface.hip $(CSRC)/kernels_surface_prog.hip $(CSRC)/kernels_surface_knn.hip $(CSRC)/kernels_lightmap.hip $(CSRC)/bvh_gpu.hip $(CSRC)/selftest.hip
 CPP_SRCS = $(CSRC)/context.cpp $(CSRC)/scene_motion.cpp $(CSRC)/ray_query.cpp $(CSRC)/probe_gather.cpp $(CSRC)/surface_gather.cpp $(CSRC)/lightmap.cpp $(CSRC)/group.cpp $(CSRC)/bvh_build.cpp $(wildcard $(CSRC)/host/*.cpp)
 # VARIANT selects a separate object directory and library name (developer builds, e.g. `make stats`)
 VARIANT ?=
@@ -53,6 +53,8 @@ $(BUILD)/kernels_probe.o: HIPFLAGS += -ffp-contract=off
 $(BUILD)/kernels_surface.o: HIPFLAGS += -ffp-contract=off
 # (progressive surface gather: the same radius test, and a point's state follows surface_state.h's rule bit for bit, as the host twin does)
 $(BUILD)/kernels_surface_prog.o: HIPFLAGS += -ffp-contract=off
+# (k-nearest start radii: d2 is the same radius test's in the select and in the first photon half, and the seeded state is surface_state.h's bit for bit)
+$(BUILD)/kernels_surface_knn.o: HIPFLAGS += -ffp-contract=off
 # (lightmap baking: a hit's surface point is the G-buffer's arithmetic, bit for bit; the rasteriser is integers)
 $(BUILD)/kernels_lightmap.o: HIPFLAGS += -ffp-contract=off
 $(BUILD)/%.o: $(CSRC)/%.hip $(HDRS)

@@ -235,6 +235,11 @@ _SIGNATURES = {
     "evplp_bake_lightmap_resolve_device": (C.c_int, [_P, _P, _P, _P]),
     "evplp_surface_state_update": (C.c_int, [_P, C.c_uint32, _P, C.c_float, C.c_float]),
     "evplp_surface_state_resolve": (C.c_int, [_P, _P]),
+    "evplp_gather_surface_knn": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P]),
+    "evplp_gather_surface_knn_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P]),
+    "evplp_bake_lightmap_knn_device": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "evplp_knn_radius2": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
+    "evplp_surface_state_seed": (C.c_int, [_P, C.c_float, C.c_uint32, _P, C.c_float, C.c_float]),
     "evplp_photon_grid_plan": (C.c_int, [C.c_float, _P, _P, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "evplp_photon_grid_cell": (C.c_uint32, [_P, _P, C.c_float, C.c_uint32, _P]),
     "evplp_photon_grid_range": (C.c_int, [_P, C.c_float, _P, _P, C.c_float, _P, _P]),
@@ -433,6 +438,11 @@ class LightmapParams(C.Structure):
     _fields_ = [("mesh", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("samples", C.c_int32), ("gutter", C.c_int32), ("flags", C.c_uint32)]
 
 
+class KnnParams(C.Structure):
+    """evplp_knn_params"""
+    _fields_ = [("k", C.c_uint32), ("r_min", C.c_float), ("alpha", C.c_float), ("flags", C.c_uint32)]
+
+
 def lightmap_cover(uv6, width: int, height: int, samples: int, x: int, y: int, i: int, j: int):
     """evplp_lightmap_cover (host only): (beta, gamma) where sample (i, j) of texel (x, y) is covered by the triangle uv6 (u0 v0 u1 v1 u2 v2), else None"""
     uv = _f32(uv6).reshape(6)
@@ -501,6 +511,26 @@ def surface_state_resolve(state) -> np.ndarray:
     if lib().evplp_surface_state_resolve(_ptr(s), _ptr(out)) != OK:
         raise ValueError("evplp_surface_state_resolve refused its arguments")
     return out
+
+
+def knn_radius2(d2, k: int, rminsq: float, r0sq: float):
+    """evplp_knn_radius2 (host only): (radius2, m) -- the k-th smallest of the float32 values d2 that pass !(d2 > r0sq), clamped into
+    [rminsq, r0sq] (r0sq where there are fewer than k), as a numpy float32 scalar, and the number of them that pass !(d2 > radius2)"""
+    a = _f32(d2).reshape(-1)
+    r, m = C.c_float(), C.c_uint32()
+    if lib().evplp_knn_radius2(_ptr(a) if a.size else None, a.size, int(k), float(rminsq), float(r0sq), C.byref(r), C.byref(m)) != OK:
+        raise ValueError("evplp_knn_radius2 refused its arguments")
+    return np.float32(r.value), int(m.value)
+
+
+def surface_state_seed(state, radius2: float, m: int, phi, alpha: float, r0sq: float) -> np.ndarray:
+    """evplp_surface_state_seed (host only): one SURFACE_STATE_DTYPE element with pm_calls == 0 after a first photon half at radius2 that
+    found m photons of summed value phi (float32 [3]), as a new one-element array; ValueError for a state that is not fresh in that sense"""
+    s = np.array(np.asarray(state, dtype=SURFACE_STATE_DTYPE).reshape(1), copy=True)
+    p = _f32(phi).reshape(3)
+    if lib().evplp_surface_state_seed(_ptr(s), float(radius2), int(m), _ptr(p), float(alpha), float(r0sq)) != OK:
+        raise ValueError("evplp_surface_state_seed refused its arguments")
+    return s
 
 
 def _ptr(a: Optional[np.ndarray]):
@@ -1004,6 +1034,57 @@ class Context:
             raise ValueError(f"{s.shape[0]} states for {x.shape[0]} points")
         self._check(self._lib.evplp_gather_surface_progressive(self._h, C.byref(fp), int(what), float(alpha), _ptr(x), _ptr(e), x.shape[0], _ptr(s)))
         return s
+
+    def gather_surface_knn(self, points, fp: FrameParams, states, k: int, r_min: float, alpha: float = 2.0 / 3.0, eyes=None, flags: int = 0):
+        """evplp_gather_surface_knn: the first photon half of the states with pm_calls == 0, each at the distance of its point's k-th nearest
+        photon within fp.photon_radius (not below r_min).  points, eyes, states and what is returned as gather_surface_progressive: numpy
+        arrays give a new array; a float32 tensor [n, 16] on the device with a float32 tensor [n, 12] of states there goes through
+        evplp_gather_surface_knn_device, in place, enqueued and not waited for."""
+        prm = KnnParams(int(k), float(r_min), float(alpha), int(flags))
+        if _is_device(points):
+            import torch
+            if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 16:
+                raise ValueError(f"points must be a float32 tensor [n, 16], not {points.dtype} {tuple(points.shape)}")
+            d = points.contiguous()
+            if not _is_device(states) or states.dtype != torch.float32 or tuple(states.shape) != (d.shape[0], 12) or not states.is_contiguous():
+                raise ValueError("states must be a contiguous float32 tensor [n, 12] on the points' device")
+            e = None
+            if eyes is not None:
+                if not _is_device(eyes) or eyes.dtype != torch.float32 or tuple(eyes.shape) != (d.shape[0], 3):
+                    raise ValueError("eyes must be a float32 tensor [n, 3] on the points' device")
+                e = eyes.contiguous()
+            self._check(self._lib.evplp_gather_surface_knn_device(self._h, C.byref(fp), C.byref(prm), C.c_void_p(d.data_ptr()),
+                                                                  C.c_void_p(e.data_ptr()) if e is not None else None, int(d.shape[0]),
+                                                                  C.c_void_p(states.data_ptr()) if d.shape[0] else None))
+            self._query_inputs = (d, e, states)     # (the launches read them after this call returns)
+            return states
+        x = np.ascontiguousarray(points, dtype=SURFACE_POINT_DTYPE).reshape(-1)
+        e = None
+        if eyes is not None:
+            e = np.ascontiguousarray(eyes, dtype=np.float32)
+            if e.shape != (x.shape[0], 3):
+                raise ValueError(f"eyes must be [n, 3] float32, not {e.shape}")
+        s = np.array(np.asarray(states, dtype=SURFACE_STATE_DTYPE).reshape(-1), copy=True)
+        if s.shape[0] != x.shape[0]:
+            raise ValueError(f"{s.shape[0]} states for {x.shape[0]} points")
+        self._check(self._lib.evplp_gather_surface_knn(self._h, C.byref(fp), C.byref(prm), _ptr(x), _ptr(e), x.shape[0], _ptr(s)))
+        return s
+
+    def bake_lightmap_knn(self, fp: FrameParams, states, width: int, height: int, samples: int = 1, k: int = 8, r_min: float = 0.0, alpha: float = 2.0 / 3.0,
+                          mesh: int = -1, flags: int = 0, uvs=None):
+        """evplp_bake_lightmap_knn_device: gather_surface_knn over the atlas' samples into their states, a contiguous float32 tensor
+        [height * width * samples^2, 12] on the device (torch.zeros is fresh), updated in place and returned; waits once per band"""
+        import torch
+        n = max(int(width), 0) * max(int(height), 0) * max(int(samples), 0) ** 2
+        if not _is_device(states) or states.dtype != torch.float32 or tuple(states.shape) != (n, 12) or not states.is_contiguous():
+            raise ValueError(f"states must be a contiguous float32 tensor [{n}, 12] on the device")
+        u = _device_uvs(uvs, states.device)
+        prm = LightmapParams(int(mesh), int(width), int(height), int(samples), 0, int(flags))
+        knn = KnnParams(int(k), float(r_min), float(alpha), 0)
+        self._check(self._lib.evplp_bake_lightmap_knn_device(self._h, C.byref(fp), C.byref(knn), C.byref(prm),
+                                                             C.c_void_p(u.data_ptr()) if u is not None else None, C.c_void_p(states.data_ptr()) if n else None))
+        self._query_inputs = (u, states)
+        return states
 
     def surface_resolve(self, states):
         """evplp_surface_resolve: a SURFACE_STATE_DTYPE array as a SURFACE_LIGHT_DTYPE array; a float32 tensor [n, 12] on the device goes

@@ -374,6 +374,8 @@ struct evplp_context {
     // evplp_gather_surface_progressive / evplp_surface_resolve (surface_gather.cpp): the reduced VPL half of ONE launch of kSurfaceChunk points
     // (32 B per point), and the host forms' staging, 156 B per point (point, eye, state: the resolve's states and results fit it).
     evplp::DeviceScratch surface_prog_lights, surface_prog_stage; char *h_surface_prog_stage = nullptr;
+    // evplp_gather_surface_knn (surface_gather.cpp): the selected squared radius of every point of a device-form batch or of a host-form chunk, 4 B each.
+    evplp::DeviceScratch surface_knn_rk2;
     // evplp_surface_points / evplp_lightmap_samples / evplp_bake_lightmap (lightmap.cpp).  The host forms' staging of ONE chunk of kQueryChunk
     // hits (hit, eye, point: 92 B each; a band's hits fit it), on the device and pinned; the selection's set-up triangles (32 B each, and 24 B
     // each of uploaded uvs); a band's tile arrays (counts, offsets, cursors, the scan's workspace) and its pinned pair count; the tiles'

@@ -5,7 +5,8 @@
 // both forms wait there -- then the fill and the raster.  The bake chains, per band, raster -> points -> evplp_gather_surface_device ->
 // resolve, and ends with the gutter passes over the whole atlas.  The kernels are in kernels_lightmap.hip, the integers in lightmap_raster.h.
 // The progressive bake chains raster -> points -> evplp_gather_surface_progressive_device per band into the caller's states; its resolve
-// reads the states alone (kernels_surface_prog.hip) and ends with the same gutter passes.
+// reads the states alone (kernels_surface_prog.hip) and ends with the same gutter passes.  evplp_bake_lightmap_knn_device is the same
+// chain with evplp_gather_surface_knn_device in the gather's place.
 #include "context.hpp"
 #include "lightmap.hpp"
 #include "surface_gather.hpp"
@@ -234,7 +235,11 @@ int bake(evplp_context *c, const char *name, bool device, const evplp_frame_para
 
 // ---------------------------------------------------------------------------------------------------------------- the progressive bake
 // one iteration over the atlas: per band raster -> points -> evplp_gather_surface_progressive_device on the band's slice of the states
-int bake_progressive(evplp_context *c, const char *name, const evplp_frame_params *fp, uint32_t what, float alpha, const evplp_lightmap_params *p, const float *uvs, void *states) {
+// knn: the band's first photon half is evplp_gather_surface_knn_device's (what and alpha are then not read) instead of the progressive gather
+int bake_progressive(evplp_context *c, const char *name, const evplp_frame_params *fp, uint32_t what, float alpha, const evplp_lightmap_params *p, const float *uvs, void *states, const evplp_knn_params *knn = nullptr) {
+    const auto band_gather = [&](const void *d_points, int32_t n, void *band) {
+        return knn ? evplp_gather_surface_knn_device(c, fp, knn, d_points, nullptr, n, band) : evplp_gather_surface_progressive_device(c, fp, what, alpha, d_points, nullptr, n, band);
+    };
     if (!p) { c->set_error("%s: null params", name); return EVPLP_ERR_INVALID; }
     int32_t first, count;
     if (!atlas_check(c, name, p->mesh, p->width, p->height, p->samples, &first, &count)) return EVPLP_ERR_INVALID;
@@ -243,7 +248,7 @@ int bake_progressive(evplp_context *c, const char *name, const evplp_frame_param
     if (!states) { c->set_error("%s: null states", name); return EVPLP_ERR_INVALID; }
     if ((((uintptr_t)states) & 15u) != 0) { c->set_error("%s: the states are not 16-byte aligned", name); return EVPLP_ERR_INVALID; }
     // what the progressive gather refuses, before anything is written: its own checks on an empty batch, and the walk's stack
-    int rc = evplp_gather_surface_progressive_device(c, fp, what, alpha, nullptr, nullptr, 0, nullptr);
+    int rc = band_gather(nullptr, 0, nullptr);
     if (rc) return rc;
     if (surface_stack_bytes(c->sc) > kMaxStackBytes) { c->set_error("%s: the walk's stack of this tree (%zu bytes per wave) exceeds a workgroup's LDS", name, surface_stack_bytes(c->sc)); return EVPLP_ERR_INVALID; }
     HIP_TRY(c, hipSetDevice(c->cfg.device));
@@ -262,7 +267,7 @@ int bake_progressive(evplp_context *c, const char *name, const evplp_frame_param
         launch_lightmap_points(points_args(c, d_hits, nullptr, d_points, n, p->flags), c->stream);
         HIP_TRY(c, hipGetLastError());
         evplp_surface_state *band = (evplp_surface_state *)states + (size_t)W * s2 * (size_t)y0;
-        if ((rc = evplp_gather_surface_progressive_device(c, fp, what, alpha, d_points, nullptr, n, band))) return rc;
+        if ((rc = band_gather(d_points, n, band))) return rc;
     }
     return EVPLP_OK;
 }
@@ -339,6 +344,11 @@ extern "C" int evplp_bake_lightmap_device(evplp_context *c, const evplp_frame_pa
 extern "C" int evplp_bake_lightmap_progressive_device(evplp_context *c, const evplp_frame_params *fp, uint32_t what, float alpha, const evplp_lightmap_params *p, const void *d_uvs, void *d_states) {
     CTX_CHECK(c);
     return bake_progressive(c, "evplp_bake_lightmap_progressive_device", fp, what, alpha, p, (const float *)d_uvs, d_states);
+}
+extern "C" int evplp_bake_lightmap_knn_device(evplp_context *c, const evplp_frame_params *fp, const evplp_knn_params *params, const evplp_lightmap_params *p, const void *d_uvs, void *d_states) {
+    CTX_CHECK(c);
+    if (!params) { c->set_error("evplp_bake_lightmap_knn_device: null k-nearest params"); return EVPLP_ERR_INVALID; }
+    return bake_progressive(c, "evplp_bake_lightmap_knn_device", fp, EVPLP_SURFACE_PHOTONS, params->alpha, p, (const float *)d_uvs, d_states, params);
 }
 extern "C" int evplp_bake_lightmap_resolve(evplp_context *c, const evplp_lightmap_params *p, const void *d_states, evplp_lightmap_texel *out) {
     CTX_CHECK(c);

@@ -4,7 +4,8 @@
 // kernels_surface.hip, the grid's arithmetic in photon_grid.h.
 // The progressive gather (include/evplp.h "progressive surface gather": evplp_gather_surface_progressive, evplp_surface_resolve and their
 // device forms) lives here too, behind the same checks, chunks and grid build: its own kernels are in kernels_surface_prog.hip, a state's
-// rule in surface_state.h.
+// rule in surface_state.h.  evplp_gather_surface_knn ("k-nearest-photon start radii") is a first photon half behind the same checks and
+// the same grid: its select and its seeding walk are in kernels_surface_knn.hip, the select's arithmetic in knn_select.h.
 #include "context.hpp"
 #include "photon_grid.h"
 #include "surface_gather.hpp"
@@ -170,16 +171,22 @@ int prog_stage(evplp_context *c, const char *name) {
 // One iteration.  Per chunk: today's VPL kernel into the partial sums, today's reduce into 32 B per point, the fold into the states; the
 // query walks behind the fold -- chunk by chunk in the host form, once over the whole batch in the device form -- so both halves decide
 // "flagged" from the state as it came in.
-int gather_progressive(evplp_context *c, const char *name, bool device, const evplp_frame_params *fp, uint32_t what, float alpha, const void *points, const float *eyes, int32_t n, void *states) {
+// what the progressive calls refuse on top of surface_check, in evplp.h's order (the k-nearest call refuses the same)
+bool prog_check(evplp_context *c, const char *name, bool device, const evplp_frame_params *fp, uint32_t what, float alpha, const void *points, const float *eyes, int32_t n, const void *states) {
     // (the states first, by their name: surface_check would call them "the destination")
-    if (n > 0 && !states) { c->set_error("%s: null states", name); return EVPLP_ERR_INVALID; }
-    if (device && n > 0 && (((uintptr_t)states) & 15u) != 0) { c->set_error("%s: the states are not 16-byte aligned", name); return EVPLP_ERR_INVALID; }
-    if (!surface_check(c, name, device, fp, what, points, eyes, n, states)) return EVPLP_ERR_INVALID;
+    if (n > 0 && !states) { c->set_error("%s: null states", name); return false; }
+    if (device && n > 0 && (((uintptr_t)states) & 15u) != 0) { c->set_error("%s: the states are not 16-byte aligned", name); return false; }
+    if (!surface_check(c, name, device, fp, what, points, eyes, n, states)) return false;
     if (fp->mis_mode >= 1u && fp->mis_mode <= 3u) {
         c->set_error("%s: mis_mode %u weighs by pdf_mc = n_vpl / n_light / (pi r^2), which a radius per point makes a per-point quantity in both halves: only modes 0, 4 and 5", name, (unsigned)fp->mis_mode);
-        return EVPLP_ERR_INVALID;
+        return false;
     }
-    if (!std::isfinite(alpha) || !(alpha > 0.0f) || alpha > 1.0f) { c->set_error("%s: alpha %g is not within (0, 1]", name, (double)alpha); return EVPLP_ERR_INVALID; }
+    if (!std::isfinite(alpha) || !(alpha > 0.0f) || alpha > 1.0f) { c->set_error("%s: alpha %g is not within (0, 1]", name, (double)alpha); return false; }
+    return true;
+}
+
+int gather_progressive(evplp_context *c, const char *name, bool device, const evplp_frame_params *fp, uint32_t what, float alpha, const void *points, const float *eyes, int32_t n, void *states) {
+    if (!prog_check(c, name, device, fp, what, alpha, points, eyes, n, states)) return EVPLP_ERR_INVALID;
     if (n == 0) return EVPLP_OK;
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     const size_t lds = surface_stack_bytes(c->sc);
@@ -245,6 +252,67 @@ int gather_progressive(evplp_context *c, const char *name, bool device, const ev
     return EVPLP_OK;
 }
 
+// --------------------------------------------------------------------------------------------------- k-nearest-photon start radii
+bool knn_check(evplp_context *c, const char *name, const evplp_frame_params *fp, const evplp_knn_params *p) {
+    if (p->k == 0u) { c->set_error("%s: k is 0", name); return false; }
+    const float rminsq = p->r_min * p->r_min;
+    if (!std::isfinite(p->r_min) || !(p->r_min > 0.0f) || p->r_min > fp->photon_radius || !(rminsq >= 0x1p-100f)) {
+        c->set_error("%s: r_min %g is not a positive finite number up to photon_radius %g whose square is at least 2^-100", name, (double)p->r_min, (double)fp->photon_radius);
+        return false;
+    }
+    if (p->flags != 0u) { c->set_error("%s: unknown flag bits 0x%x", name, (unsigned)p->flags); return false; }
+    return true;
+}
+
+// The first photon half at the k-th nearest photon's distance: the progressive gather's grid and compact records, then the select and
+// the seeding walk -- over the whole batch in the device form, chunk by chunk through the progressive gather's staging in the host form.
+int gather_knn(evplp_context *c, const char *name, bool device, const evplp_frame_params *fp, const evplp_knn_params *p, const void *points, const float *eyes, int32_t n, void *states) {
+    if (!p) { c->set_error("%s: null params", name); return EVPLP_ERR_INVALID; }
+    if (!prog_check(c, name, device, fp, EVPLP_SURFACE_PHOTONS, p->alpha, points, eyes, n, states)) return EVPLP_ERR_INVALID;
+    if (!knn_check(c, name, fp, p)) return EVPLP_ERR_INVALID;
+    if (n == 0) return EVPLP_OK;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    const size_t lds = surface_stack_bytes(c->sc);      // (nothing here walks the tree; refused all the same, so that this call refuses what the progressive one does)
+    if (lds > kMaxStackBytes) { c->set_error("%s: the walk's stack of this tree (%zu bytes per wave) exceeds a workgroup's LDS", name, lds); return EVPLP_ERR_INVALID; }
+    int rc;
+    if (!device && (rc = prog_stage(c, name))) return rc;
+    const size_t radii = sizeof(float) * (size_t)(device ? n : std::min(n, kSurfaceChunk));
+    const hipError_t e = grow_scratch_of(c, c->surface_knn_rk2, radii);
+    if (e != hipSuccess) { c->set_error("%s: cannot allocate the selected radii (%zu bytes): %s", name, radii, hipGetErrorString(e)); return oom_or_hip(e); }
+    SurfaceKnnArgs q; std::memset(&q, 0, sizeof(q));
+    q.p.fp = *fp; q.p.what = EVPLP_SURFACE_PHOTONS; q.p.alpha = p->alpha; q.p.r0sq = fp->photon_radius * fp->photon_radius;
+    q.rk2 = (float *)c->surface_knn_rk2.p; q.k = p->k; q.rminsq = p->r_min * p->r_min;
+    SurfaceGridBuild b;
+    if ((rc = build_grid(c, name, fp, &q.p.grid, &b))) return rc;
+    launch_surface_prog_compact(b, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    if (device) {
+        q.p.n = n; q.p.points = (const float4 *)points; q.p.eyes = eyes; q.p.states = (float4 *)states;
+        launch_surface_knn_select(q, c->stream);
+        launch_surface_knn_photons(q, c->stream);
+        HIP_TRY(c, hipGetLastError());
+    } else for (int64_t at = 0; at < n; at += kSurfaceChunk) {
+        const int32_t m = (int32_t)std::min<int64_t>(kSurfaceChunk, n - at);
+        char *h = c->h_surface_prog_stage, *d = (char *)c->surface_prog_stage.p;
+        const size_t off = kStagePoints + kStageEyes;
+        std::memcpy(h, (const evplp_surface_point *)points + at, sizeof(evplp_surface_point) * (size_t)m);
+        if (eyes) std::memcpy(h + kStagePoints, eyes + 3 * (size_t)at, 3 * sizeof(float) * (size_t)m);
+        std::memcpy(h + off, (const evplp_surface_state *)states + at, sizeof(evplp_surface_state) * (size_t)m);
+        HIP_TRY(c, hipMemcpyAsync(d, h, sizeof(evplp_surface_point) * (size_t)m, hipMemcpyHostToDevice, c->stream));
+        if (eyes) HIP_TRY(c, hipMemcpyAsync(d + kStagePoints, h + kStagePoints, 3 * sizeof(float) * (size_t)m, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d + off, h + off, sizeof(evplp_surface_state) * (size_t)m, hipMemcpyHostToDevice, c->stream));
+        q.p.n = m; q.p.points = (const float4 *)d; q.p.eyes = eyes ? (const float *)(d + kStagePoints) : nullptr; q.p.states = (float4 *)(d + off);
+        launch_surface_knn_select(q, c->stream);
+        launch_surface_knn_photons(q, c->stream);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(h + off, q.p.states, sizeof(evplp_surface_state) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        std::memcpy((evplp_surface_state *)states + at, h + off, sizeof(evplp_surface_state) * (size_t)m);
+    }
+    if (c->aux_stream) HIP_TRY(c, hipEventRecord(c->ev_records_read, c->stream));
+    return EVPLP_OK;
+}
+
 int resolve_states(evplp_context *c, const char *name, bool device, const void *states, int32_t n, void *out) {
     if (n < 0) { c->set_error("%s: n = %d", name, n); return EVPLP_ERR_INVALID; }
     if (n > 0 && (!states || !out)) { c->set_error("%s: null states or destination", name); return EVPLP_ERR_INVALID; }
@@ -280,9 +348,9 @@ int resolve_states(evplp_context *c, const char *name, bool device, const void *
 namespace evplp {
 void release_surface_gather(evplp_context *c) {
     hipFree(c->surface_partial.p); hipFree(c->surface_grid.p); hipFree(c->surface_stage.p);
-    hipFree(c->surface_prog_lights.p); hipFree(c->surface_prog_stage.p);
+    hipFree(c->surface_prog_lights.p); hipFree(c->surface_prog_stage.p); hipFree(c->surface_knn_rk2.p);
     c->surface_partial = DeviceScratch(); c->surface_grid = DeviceScratch(); c->surface_stage = DeviceScratch();
-    c->surface_prog_lights = DeviceScratch(); c->surface_prog_stage = DeviceScratch();
+    c->surface_prog_lights = DeviceScratch(); c->surface_prog_stage = DeviceScratch(); c->surface_knn_rk2 = DeviceScratch();
     if (c->h_surface_stage) hipHostFree(c->h_surface_stage);
     if (c->h_surface_prog_stage) hipHostFree(c->h_surface_prog_stage);
     c->h_surface_stage = nullptr; c->h_surface_prog_stage = nullptr;
@@ -304,6 +372,14 @@ extern "C" int evplp_gather_surface_progressive(evplp_context *c, const evplp_fr
 extern "C" int evplp_gather_surface_progressive_device(evplp_context *c, const evplp_frame_params *fp, uint32_t what, float alpha, const void *d_points, const void *d_eyes, int32_t n, void *d_states) {
     CTX_CHECK(c);
     return gather_progressive(c, "evplp_gather_surface_progressive_device", true, fp, what, alpha, d_points, (const float *)d_eyes, n, d_states);
+}
+extern "C" int evplp_gather_surface_knn(evplp_context *c, const evplp_frame_params *fp, const evplp_knn_params *params, const evplp_surface_point *points, const float *eyes, int32_t n, evplp_surface_state *states) {
+    CTX_CHECK(c);
+    return gather_knn(c, "evplp_gather_surface_knn", false, fp, params, points, eyes, n, states);
+}
+extern "C" int evplp_gather_surface_knn_device(evplp_context *c, const evplp_frame_params *fp, const evplp_knn_params *params, const void *d_points, const void *d_eyes, int32_t n, void *d_states) {
+    CTX_CHECK(c);
+    return gather_knn(c, "evplp_gather_surface_knn_device", true, fp, params, d_points, (const float *)d_eyes, n, d_states);
 }
 extern "C" int evplp_surface_resolve(evplp_context *c, const evplp_surface_state *states, int32_t n, evplp_surface_light *out) {
     CTX_CHECK(c);

@@ -78,4 +78,15 @@ void launch_surface_prog_photons(const SurfaceProgArgs &a, hipStream_t s);
 void launch_surface_prog_resolve(const SurfaceResolveArgs &a, hipStream_t s);
 void launch_lightmap_prog_resolve(const LightmapProgResolveArgs &a, hipStream_t s);
 
+// The k-nearest-photon start radius (evplp_gather_surface_knn; kernels_surface_knn.hip).  The grid and the compact records are the
+// progressive gather's; the select leaves a squared radius per point of the launch, the photon kernel seeds the fresh states with it.
+struct SurfaceKnnArgs {
+    SurfaceProgArgs p;            // fp, points, eyes, states, n (any number), alpha, r0sq, grid; lights and what are not read
+    float *rk2;                   // [n]: written by the select and read by the photon kernel, for the lanes both decide to be this call's
+    uint32_t k;                   // >= 1
+    float rminsq;                 // fl(r_min * r_min), within [2^-100, r0sq]
+};
+void launch_surface_knn_select(const SurfaceKnnArgs &a, hipStream_t s);          // lane = point -> rk2
+void launch_surface_knn_photons(const SurfaceKnnArgs &a, hipStream_t s);         // lane = point: the first photon half at rk2 -> states
+
 }

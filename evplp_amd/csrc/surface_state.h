@@ -77,6 +77,22 @@ SS_FN void ss_update(evplp_surface_state *st, uint32_t M, const float phi[3], fl
     st->pm_calls++;
 }
 
+/* the first photon half of a state with pm_calls == 0 at a radius2 chosen for the point (evplp_gather_surface_knn: the k-th nearest
+ * photon's d2, clamped into [rminsq, r0sq]) instead of r0sq: M photons inside it, phi their summed value.  ss_update's M > 0 branch. */
+SS_FN void ss_seed(evplp_surface_state *st, float radius2, uint32_t M, const float phi[3], float alpha) {
+    SS_NO_CONTRACT
+    st->radius2 = radius2;
+    if (M > 0u) {
+        const float m = (float)M;
+        const float nn = st->n + alpha * m;
+        const float ratio = nn / (st->n + m);
+        st->radius2 = st->radius2 * ratio;
+        for (int k = 0; k < 3; k++) st->tau[k] = (st->tau[k] + phi[k]) * ratio;
+        st->n = nn;
+    }
+    st->pm_calls = 1u;
+}
+
 SS_FN void ss_resolve(const evplp_surface_state *st, evplp_surface_light *out) {
     SS_NO_CONTRACT
     for (int k = 0; k < 3; k++) { out->vpl[k] = 0.0f; out->pm[k] = 0.0f; }

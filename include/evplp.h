@@ -164,7 +164,8 @@ typedef struct evplp_config {
      *                                   slot + 4 B per bucket (at most the slots rounded up to a power of two) + the radix sort's workspace: the grid
      *                                   of one call, 200 MB at 2 M slots; the host form 108 B per point of a chunk of 16 384 on the device and pinned
      *                                   (evplp_gather_surface); none of it depends on the number of points.  The progressive calls: the same,
-     *                                   + 512 KB (the reduced VPL half of a chunk) and their host forms 156 B per point of a chunk, device and pinned
+     *                                   + 512 KB (the reduced VPL half of a chunk) and their host forms 156 B per point of a chunk, device and pinned;
+     *                                   evplp_gather_surface_knn: the grid, that staging, and 4 B per point of the batch (_device) or of a chunk
      * A caller that has the device to itself sets cut_scratch_bytes = 72 GB, vsl_mask_bytes = 14 GB for config #5 (one band, one launch). */
     uint64_t cut_scratch_bytes;
     uint64_t vsl_mask_bytes;
@@ -815,6 +816,55 @@ int evplp_bake_lightmap_resolve(evplp_context *ctx, const evplp_lightmap_params 
 int evplp_bake_lightmap_resolve_device(evplp_context *ctx, const evplp_lightmap_params *params, const void *d_states, void *d_out);
 int evplp_surface_state_update(evplp_surface_state *state, uint32_t m, const float phi[3], float alpha, float r0sq);
 int evplp_surface_state_resolve(const evplp_surface_state *state, evplp_surface_light *out);
+
+/* ---- k-nearest-photon start radii for progressive states (INTEGRATION B13) ----
+ * The progressive calls start every point at one radius, fp->photon_radius.  evplp_gather_surface_knn is a first photon half that starts
+ * each point at the distance of its k-th nearest photon instead, found on the device by an exact select on the photon grid.
+ *   For one point X, with r0 = fp->photon_radius, r0sq = fl(r0 r0), rminsq = fl(r_min r_min), and the d2 of a photon at P the value of
+ *   the progressive test: dv = P - X, d2 = (dv.x dv.x + dv.y dv.y) + dv.z dv.z, every operation rounded to fp32 on its own:
+ *     Candidates: the photons evplp_gather_surface's photon half counts at radius r0 -- the usable slots (slot != 0,
+ *       slot < num_light_paths * photons_per_path, the photon flag set) with !(d2 > r0sq).  C is their number.  No candidate's d2 is a
+ *       NaN (knn_select.h: a photon with a NaN coordinate lies on a cell no walked point's range holds), none is negative.
+ *     kth: the k-th smallest d2 among the candidates, with multiplicity, where C >= k; otherwise r0sq.  (Non-negative floats order as
+ *       their bit patterns do: the select works on uint32 and is exact.)
+ *     rk2 = min(max(kth, rminsq), r0sq).
+ *     The first photon half.  M = the number of candidates with !(d2 > rk2): ties with the k-th are inside, so M >= k may hold.
+ *       Phi = their summed fragment value exactly as the progressive photon half forms it (flux * rcp((float)num_light_paths),
+ *       mis_mode 0 / 4 / 5, the same visiting order, discarded fragments counted in M).  Then
+ *           radius2 = rk2;  if M > 0: Nn = n + alpha (float)M; ratio = Nn / (n + (float)M); radius2 = radius2 ratio;
+ *                                     tau = (tau + Phi) ratio; n = Nn;                       pm_calls = 1
+ *   Which states.  Only a state with pm_calls == 0 and EVPLP_STATE_INVALID clear, on a valid point with a finite position and eye.
+ *     A state with pm_calls > 0 or EVPLP_STATE_INVALID set: not a byte is touched.  valid == 0 (the stencil): not touched.  A point or
+ *     eye that is not finite: flags |= EVPLP_STATE_INVALID and nothing else, as the progressive calls do.  vpl, lit_sum and vpl_calls
+ *     are never touched: the call has no VPL half, evplp_gather_surface_progressive with EVPLP_SURFACE_VPL is that.
+ *   What follows.  After the call such a state is an ordinary progressive state with radius2 in (0, r0sq]: every later progressive call
+ *     with a bound >= this r0, the resolves and the bake accept it unchanged.  Fresh states, this call and evplp_surface_resolve are the
+ *     classic k-nearest density estimate pm = Phi InvPi / rk2 (at alpha = 1).  A point with C < k gets exactly the bytes
+ *     evplp_gather_surface_progressive(EVPLP_SURFACE_PHOTONS) would have written.  A point's 48 bytes do not depend on n, its index,
+ *     the chunking, the form or EVPLP_SURFACE_GRID_BITS.
+ *   params: k >= 1; r_min the smallest start radius, finite, > 0, <= fp->photon_radius, with fl(r_min r_min) >= 2^-100 (the range of a
+ *     smaller radius2 is the call's anyway); alpha as the progressive calls take it; flags 0.
+ *   Forms, chunking and staging are evplp_gather_surface_progressive's.  Scratch beyond it, grow-only and freed by evplp_destroy: 4 B per
+ *     point of the batch (_device) or of a chunk (host) for the selected radii.
+ *   evplp_bake_lightmap_knn_device is evplp_bake_lightmap_progressive_device with this call in the place of the progressive gather: per
+ *     band raster -> points -> the k-nearest call on the band's slice of d_states.  An uncovered sample's state stays fresh.
+ *   EVPLP_ERR_INVALID, nothing written, the context usable: everything evplp_gather_surface_progressive refuses for
+ *     what = EVPLP_SURFACE_PHOTONS (mis_mode 1 - 3 and alpha included; the bake: everything the progressive bake refuses); null params;
+ *     k == 0; an r_min that is not finite, <= 0, > fp->photon_radius or whose square is below 2^-100; nonzero flags.  n = 0: EVPLP_OK.
+ *   Host only, no GPU, the functions the kernels call: evplp_knn_radius2 selects over an array of d2 values -- *radius2 = rk2 and *m = M
+ *     of the definitions above, with the elements that pass !(d2 > r0sq) as the candidates; EVPLP_ERR_INVALID for a null pointer,
+ *     k == 0, an rminsq that is not within (0, r0sq] or not finite, or an element that is a NaN or has its sign bit set.
+ *     evplp_surface_state_seed applies "the first photon half" above to one state; EVPLP_ERR_INVALID and nothing written for a null
+ *     pointer, a state with pm_calls > 0 or EVPLP_STATE_INVALID set, or a radius2 that is not within (0, r0sq]. */
+typedef struct evplp_knn_params { uint32_t k; float r_min; float alpha; uint32_t flags /* 0 */; } evplp_knn_params;   /* 16 B */
+int evplp_gather_surface_knn(evplp_context *ctx, const evplp_frame_params *fp, const evplp_knn_params *params, const evplp_surface_point *points,
+                             const float *eyes /* n x 3 or NULL */, int32_t n, evplp_surface_state *states /* in and out */);
+int evplp_gather_surface_knn_device(evplp_context *ctx, const evplp_frame_params *fp, const evplp_knn_params *params, const void *d_points,
+                                    const void *d_eyes, int32_t n, void *d_states);
+int evplp_bake_lightmap_knn_device(evplp_context *ctx, const evplp_frame_params *fp, const evplp_knn_params *params, const evplp_lightmap_params *lightmap,
+                                   const void *d_uvs, void *d_states /* width*height*samples^2 states */);
+int evplp_knn_radius2(const float *d2, uint32_t count, uint32_t k, float rminsq, float r0sq, float *radius2, uint32_t *m);
+int evplp_surface_state_seed(evplp_surface_state *state, float radius2, uint32_t m, const float phi[3], float alpha, float r0sq);
 
 /* ---- the per-iteration passes of RtComPhoton::run() (rtcomphoton.h:936-1068) ---- */
 /* [deferredShading] + [lightRender]: runDeferredProgram (:710-754) + runLightProgram (:839-855);
