@@ -25,6 +25,7 @@ extern "C" void evplp_probe_pair(const evplp_record *r, const float x[3], float 
     const float c2 = std::fmax(-dot3(r->normal, v12), 0.0f);
     if (!(c2 > 0.0f)) return;
     const float dist2 = dot3(v12, v12);
+    if (!(dist2 >= 1.17549435e-38f && dist2 <= 3.4028235e38f)) return;         // not a normal finite number: no ray, no term (the kernel's test, on the same bits)
     const float inv_dist = 1.0f / std::sqrt(dist2);
     const float w[3] = { v12[0] * inv_dist, v12[1] * inv_dist, v12[2] * inv_dist };
     const float cos2 = c2 * inv_dist;

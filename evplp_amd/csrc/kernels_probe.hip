@@ -24,6 +24,7 @@ namespace evplp {
 namespace {
 EV_DEV bool probe_finite(float x) { return fabsf(x) <= 3.4028235e38f; }      // (false for a NaN)
 EV_DEV bool probe_valid(V3 x) { return probe_finite(x.x) && probe_finite(x.y) && probe_finite(x.z); }
+EV_DEV bool probe_walked(float dist2) { return dist2 >= 1.17549435e-38f && dist2 <= 3.4028235e38f; }      // 2^-126 <= dist2 <= FLT_MAX (false for a NaN)
 
 // the VPL side of a record through a wave-uniform base and byte offset: s_load_dwordx8 (position, flags, normal) and s_load_dwordx16
 // (the shading fields) issued together and waited for once, spelled out as device_common.hpp's sload8 / sload16 are -- left to the
@@ -72,6 +73,10 @@ __global__ __launch_bounds__(64, EVPLP_PROBE_WAVES) void probe_gather_kernel(Pro
         const V3 v12 = v.pos - x;
         const float c2 = fmaxf(-dot_exact(v.n, v12), 0.0f);
         if (c2 <= 0.0f) continue;
+        // a pair whose dist2 is not a normal finite number casts no ray, adds no term and is not counted (include/evplp.h): every ray walked
+        // is then one evplp_trace_occluded accepts, and rsq, w, cos2 and the rcp below stay finite.  dist2 is formed again after the walk
+        // (the same bits: the unit is uncontracted), so nothing more is live across it
+        if (!probe_walked(dot(v12, v12))) continue;
         if (occluded_lane4<64, EVPLP_QUERY_SPEC, true>(a.sc, v.pos, -v12, 0.0001f, 1.0f - 0.0001f, lds_stack + lane)) continue;
         const float dist2 = dot(v12, v12);
         const float inv_dist = __builtin_amdgcn_rsqf(dist2);

@@ -588,7 +588,12 @@ int evplp_triangle_info(evplp_context *ctx, int32_t triangle, int32_t *mesh, int
  *       v12 = pos_k - x;  c2 = max(-((n_k.x v12.x + n_k.y v12.y) + n_k.z v12.z), 0), every operation rounded on its own;  c2 <= 0: no ray, no term.
  *       Shadow ray: origin pos_k, direction -v12, tmin 0.0001f, tmax 1.0f - 0.0001f -- walked as evplp_trace_occluded walks it, so the
  *       visibility of a pair is what evplp_trace_occluded answers for that ray.
- *       A lit pair: dist2 = v12 . v12, w = v12 rsq(dist2), cos2 = c2 rsq(dist2),
+ *       A pair whose dist2 = (v12.x v12.x + v12.y v12.y) + v12.z v12.z, each operation rounded to fp32 on its own, is not a normal finite
+ *       number (!(dist2 >= 2^-126 && dist2 <= FLT_MAX)) casts no ray, adds no term and is not counted in lit: a probe within about
+ *       1e-19 of a record, or 2^64 and more away from it.  A normal dist2 puts the largest |v12 component| at 2^-63 / sqrt(3) or above, a
+ *       finite one below 2^64, so every ray walked is one evplp_trace_occluded accepts; and rsq(dist2), w, cos2 and 1 / max(dist2,
+ *       min_distance^2) are finite: the position of a probe with finite coordinates never makes a byte of its answer non-finite.
+ *       A lit pair: dist2 as above, w = v12 rsq(dist2), cos2 = c2 rsq(dist2),
  *         brdf2 = rho_d_k / pi + rho_s_k PhongEvalF(-w, flux_dir_k, n_k, e_k)    (0 for rho_s = 0; the power is exp2(e log2 d) on the hardware)
  *         E = flux_k brdf2 cos2 / max(dist2, min_distance^2),   c[i] += E Y_i(w)
  *     with Y_i the real SH basis of index l (l + 1) + m on w = (x, y, z): Y0 = 0.28209479, Y1 = 0.48860251 y, Y2 = 0.48860251 z,
@@ -608,7 +613,8 @@ int evplp_triangle_info(evplp_context *ctx, int32_t triangle, int32_t *mesh, int
  *     than the context's record buffer holds (num_light_paths * photons_per_path of evplp_config); a _device destination that is not
  *     16-byte aligned.  n = 0 returns EVPLP_OK and touches nothing.
  *   Host only, no GPU: evplp_probe_pair is the term of one (record, point) pair with visibility 1 in fp32 with libm's powf, E Y_i as
- *     out27[3 i + channel], not divided (all zeros for c2 <= 0; the flags are not looked at); evplp_sh_basis is Y_0 .. Y_8 of a direction
+ *     out27[3 i + channel], not divided (all zeros for c2 <= 0 and for a pair the dist2 test above skips, decided on the kernel's bits; the
+ *     flags are not looked at); evplp_sh_basis is Y_0 .. Y_8 of a direction
  *     (taken as given: not normalised); evplp_sh_irradiance is the irradiance on a surface of unit `normal` -- the clamped-cosine
  *     convolution (Ramamoorthi and Hanrahan 2001): band l weighted pi, 2 pi / 3, pi / 4, the basis evaluated at the normal.  rho_d / pi
  *     times it is the diffuse radiance leaving that surface. */

@@ -9,6 +9,10 @@ pair_f64 forms kappa, lam and decided the way shading_domain.vpl_pair_f64 does, 
   lam     e |log2 d| of the lobe power the kernel takes as exp2(e log2 d)
   decided False where the cosine test or the lobe cut lies within shading_domain.COS_MARGIN
 The kernel's max(dist2, min_distance^2) is continuous: it needs no margin.
+
+A pair whose float32 dist2 is not a normal finite number casts no ray and adds no term (include/evplp.h): walked_f32 decides it on the
+kernel's own bits, as facing_f32 decides the cosine test, and pair_f64 takes that decision over -- the rule is stated on those bits, so
+there is no float64 version of it and nothing undecided about it.
 """
 import math
 
@@ -74,15 +78,28 @@ def facing_f32(record, x):
     return (-d) > 0, v12
 
 
+def walked_f32(record, x):
+    """the kernel's test of dist2 = (v.x v.x + v.y v.y) + v.z v.z, every float32 operation rounded on its own (subnormals kept): True where
+    it is a normal finite number, 2^-126 <= dist2 <= FLT_MAX.  Only such a pair casts a shadow ray and adds a term."""
+    F = np.float32
+    x = np.asarray(x, F).reshape(-1, 3)
+    v12 = (np.asarray(record["pos"], F)[None, :] - x).astype(F)
+    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+        p = (v12 * v12).astype(F)
+        d2 = ((p[:, 0] + p[:, 1]).astype(F) + p[:, 2]).astype(F)
+    return (d2 >= F(2.0 ** -126)) & (d2 <= np.finfo(F).max)
+
+
 def pair_f64(record, x, min_distance):
-    """one record against points x [n, 3], visibility 1.  Returns term [n, 9, 3] (E Y_i, NOT divided by the path count), kappa [n, 9, 1],
-    lam [n, 9], decided [n], facing [n] (the pair passes the cosine test: it casts a shadow ray)."""
+    """one record against points x [n, 3] (finite), visibility 1.  Returns term [n, 9, 3] (E Y_i, NOT divided by the path count),
+    kappa [n, 9, 1], lam [n, 9], decided [n], facing [n] (the pair passes the cosine test and walked_f32: it casts a shadow ray)."""
     v = sd._rec64(record)
     x = np.asarray(x, np.float32).astype(np.float64).reshape(-1, 3)
     md2 = float(np.float32(min_distance)) ** 2
     v12 = v.pos - x
     c2u = -sd._dot(v12, v.n)
-    facing = c2u > 0.0
+    walked = walked_f32(record, x)
+    facing = (c2u > 0.0) & walked
     dist2 = sd._dot(v12, v12)
     with np.errstate(divide="ignore", invalid="ignore"):
         dist = np.sqrt(dist2)
@@ -110,4 +127,4 @@ def pair_f64(record, x, min_distance):
     kap = (np.where(facing, kappa, 1.0)[:, None] + np.minimum(ycond, 1e30))[:, :, None]
     lam9 = np.repeat(np.where(facing, lam, 0.0)[:, None], 9, axis=1)
     term = np.where(facing[:, None, None], term, 0.0)
-    return term, kap, lam9, decided, facing
+    return term, kap, lam9, decided | ~walked, facing                           # (a skipped pair is exactly 0 whatever its cosines)

@@ -18,7 +18,7 @@ import oracle_api as oa
 import probe_restate as pr
 import scenes
 import shading_domain as sd
-from test_probe_host import K_ORACLE_PROBE
+from probe_domain import MIN_DISTANCE, Reference, check_values, say      # (Reference holds the kernel to K_GPU_PROBE = 2 K_ORACLE_PROBE)
 
 pytestmark = pytest.mark.gpu
 
@@ -27,90 +27,11 @@ W, H = 64, 48                        # the contexts' frame: only the last test r
 NPATHS, P = 160, 4
 SLOTS = NPATHS * P
 N_PROBES = 197
-MIN_DISTANCE = 0.05
-K_GPU_PROBE = 2 * K_ORACLE_PROBE
-TMIN, TMAX = F(0.0001), F(1.0) - F(0.0001)
-
-
-def say(*a):
-    print("[probe]", *a, flush=True)
 
 
 def free_points(rng, n):
     """points inside the room [0, 10] x [0, 8] x [0, 5] (some lie inside a box: a probe may be anywhere)"""
     return (rng.uniform(0.05, 0.95, size=(n, 3)) * np.array([10.0, 8.0, 5.0])).astype(F)
-
-
-def oracle_occluded_tree(osc, rays):
-    out = np.zeros(rays.shape[0], np.uint8)
-    for i, r in enumerate(rays):
-        o, d = np.ascontiguousarray(r[0:3]), np.ascontiguousarray(r[4:7])
-        out[i] = osc.lib.evo_occluded(osc.h, oa.ptr(o), oa.ptr(d), float(r[3]), float(r[7]))
-    return out
-
-
-class Reference:
-    """every (usable slot, probe) pair once: the float32 cosine test, the shadow rays, the oracle's visibility, the float64 terms"""
-
-    def __init__(self, osc, records, probes, min_distance=MIN_DISTANCE, tree=True):
-        self.records, self.probes = records, probes
-        n = probes.shape[0]
-        self.slots = np.nonzero(records["flags"] & 1)[0]
-        K = len(self.slots)
-        self.facing = np.zeros((K, n), bool)
-        self.term = np.zeros((K, n, 9, 3)); self.bar = np.zeros((K, n, 9, 3)); self.decided = np.ones((K, n), bool)
-        rays, where = [], []
-        for j, k in enumerate(self.slots):
-            f32, v12 = pr.facing_f32(records[k], probes)
-            term, kappa, lam, decided, f64 = pr.pair_f64(records[k], probes, min_distance)
-            self.facing[j] = f32
-            self.decided[j] = decided & (f32 == f64)
-            self.term[j] = term
-            self.bar[j] = sd.bar(term, kappa, lam, K_GPU_PROBE, True)
-            idx = np.nonzero(f32)[0]
-            r = np.zeros((len(idx), 8), F)
-            r[:, 0:3] = records["pos"][k]; r[:, 3] = TMIN; r[:, 4:7] = -v12[idx]; r[:, 7] = TMAX
-            rays.append(r); where.append(np.stack([np.full(len(idx), j), idx], -1))
-        self.rays = np.concatenate(rays); self.where = np.concatenate(where)
-        self.set_visibility(osc, tree)
-
-    def set_visibility(self, osc, tree=True):
-        """the oracle scene's answers for the shadow rays (again after the scene has moved)"""
-        brute = osc.occluded_brute(self.rays)
-        self.aside_rays = (oracle_occluded_tree(osc, self.rays) != brute) if tree else np.zeros(len(brute), bool)
-        self.occluded_rays = brute
-        K, n = self.facing.shape
-        self.lit = np.zeros((K, n), bool); self.aside = np.zeros((K, n), bool)
-        self.lit[self.where[:, 0], self.where[:, 1]] = brute == 0
-        self.aside[self.where[:, 0], self.where[:, 1]] = self.aside_rays
-
-    def expect(self, paths, keep=None):
-        """(c [n, 9, 3] float64, bar [n, 9, 3], lit [n], undecided per probe [n]) of the slots < paths * P, of those only keep[slot]"""
-        use = self.slots < paths * P
-        if keep is not None:
-            use &= keep[self.slots]
-        lit = self.lit & use[:, None]
-        m = lit[:, :, None, None]
-        und = lit & ~self.decided
-        mag = np.abs(self.term)
-        total = np.where(m, self.term, 0.0).sum(0)
-        count = lit.sum(0)
-        bar = np.where(m & self.decided[:, :, None, None], self.bar, 0.0).sum(0) + np.where(und[:, :, None, None], mag + self.bar, 0.0).sum(0)
-        bar = bar + count[:, None, None] * 2.0 ** -24 * np.where(m, mag, 0.0).sum(0)
-        return total / paths, bar / paths, count, und.sum(0)
-
-
-def check_values(got, ref, paths, what, keep=None):
-    c, bar, lit, und = ref.expect(paths, keep)
-    skip = (ref.aside & (ref.slots < paths * P)[:, None]).any(0)
-    ok = ~skip
-    assert np.array_equal(got["lit"][ok], lit[ok].astype(F)), (what, np.nonzero(got["lit"] != lit)[0][:8], got["lit"][:8], lit[:8])
-    err = np.abs(got["c"].astype(np.float64) - c)
-    bad = np.argwhere((err > bar) & ok[:, None, None])
-    worst = float((err / np.maximum(bar, 1e-300))[ok].max()) if ok.any() else 0.0
-    say(f"{what}: {int(lit.sum())} lit pairs, worst error / bar = {worst:.3f}, undecided {int(und.sum())} (worst probe {int(und.max()) if len(und) else 0})")
-    assert bad.size == 0, (what, bad[:4].tolist(), got["c"][tuple(bad[0])], c[tuple(bad[0])], bar[tuple(bad[0])])
-    return lit
 
 
 @pytest.fixture(scope="module")
@@ -134,7 +55,7 @@ def probes():
 
 @pytest.fixture(scope="module")
 def ref(oracle, room, records, probes):
-    r = Reference(oa.Scene(room), records, probes)
+    r = Reference(oa.Scene(room), records, probes, per_path=P)
     assert r.aside_rays.sum() <= 0.005 * len(r.rays)
     assert r.aside_rays.sum() == 0, "with these seeds evo_occluded and evo_occluded_brute agree on every shadow ray"
     _, _, lit, und = r.expect(NPATHS)
@@ -341,7 +262,7 @@ def test_lambert_pixels_lit_through_their_probes_agree_with_the_vpl_gather(evplp
         assert min_distance > 1e-4, "no pixel sits on a record"
         sh = c.gather_probes(x, n, p, min_distance)
     assert (phg == 0).all() and len(px) > 0.9 * w * h, "every receiver is Lambertian (the VPLs on the light keep their emission lobe)"
-    r = Reference(oa.Scene(sdl), rec.astype(oa.RECORD_DTYPE), x, min_distance)
+    r = Reference(oa.Scene(sdl), rec.astype(oa.RECORD_DTYPE), x, min_distance, per_path=p)
     clean = ~r.aside.any(0)                     # (a pixel with a pair the oracle's tree and its brute force disagree on is set aside)
     assert r.aside_rays.sum() <= 0.005 * len(r.rays) and clean.sum() > 0.9 * len(px)
     assert np.array_equal(sh["lit"][clean], r.lit.sum(0).astype(F)[clean])

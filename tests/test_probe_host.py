@@ -14,15 +14,10 @@ import subprocess
 import numpy as np
 import probe_restate as pr
 import shading_domain as sd
+from probe_domain import K_ORACLE_PROBE, MIN_DISTANCE, positions_for      # noqa: F401  (test_gpu_probe.py takes K_ORACLE_PROBE from here)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
-MIN_DISTANCE = 0.05
-
-# The smallest K that holds, measured 2026-10-20 with `pytest -s -m "not gpu" tests/test_probe_host.py` (the pair test prints the worst
-# error / (2^-24 kappa |f64|) it meets): 5.46 over 37 records x 367 positions (11 311 facing pairs, none of them undecided), rounded up.
-K_ORACLE_PROBE = 6
-
 
 def test_symbols_are_exported_and_declared_and_the_abi_stays_5(evplp):
     hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "evplp.h")).read(), flags=re.S)
@@ -105,27 +100,6 @@ def test_sh_basis_and_irradiance_match_the_restatement(evplp):
     # a constant environment L: c0 = L / Y0 ... irradiance pi L on any normal
     sh = np.zeros(1, evplp.PROBE_SH_DTYPE); sh["c"][0, 0] = (2.0 / 0.28209479, 1.0 / 0.28209479, 0.0)
     assert np.allclose(evplp.sh_irradiance(sh[0], [0.0, 0.6, 0.8]), [2.0 * np.pi, np.pi, 0.0], rtol=1e-6)
-
-
-def positions_for(rec):
-    """(positions [m, 3] float32, kind per position) for one record"""
-    pos = rec["pos"].astype(np.float64); n = rec["normal"].astype(np.float64)
-    gx, gy = np.meshgrid(np.linspace(-11.0, 11.0, 15), np.linspace(-7.0, 7.0, 12))
-    grid = [np.stack([gx.ravel(), gy.ravel(), np.full(gx.size, z)], -1) for z in (0.0, 0.35)]
-    parts, kinds = [], []
-
-    def add(kind, p):
-        p = np.asarray(p, np.float64).reshape(-1, 3); parts.append(p); kinds.extend([kind] * len(p))
-    add("grid", np.concatenate(grid))
-    add("behind", [pos - 0.7 * n, pos - 3.0 * n + [0.4, -0.2, 0.0]])
-    add("inside_min_distance", [pos + 0.3 * MIN_DISTANCE * n, pos + 0.9 * MIN_DISTANCE * (n + [0.3, 0.1, 0.0]) / np.linalg.norm(n + [0.3, 0.1, 0.0])])
-    add("at_vpl", [pos])
-    r = sd._mirror(rec["flux_dir"].astype(np.float64), n)                      # the lobe's axis: reflect(-fdir, n)
-    r = r / np.linalg.norm(r)
-    add("on_lobe", [pos + 1.5 * r, pos + 0.4 * r])
-    t = np.cross(r, [0.3, 0.5, 0.81]); t /= np.linalg.norm(t)
-    add("lobe_flank", [pos + 1.5 * (r + 0.05 * t), pos + 1.5 * (r + 0.5 * t)])
-    return np.concatenate(parts).astype(F), np.array(kinds, object)
 
 
 def test_probe_pair_obeys_the_bar_on_every_record_and_kind_of_position(evplp):
