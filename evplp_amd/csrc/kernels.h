@@ -332,20 +332,25 @@ struct AdaptTiles { const int4 *tiles; int32_t tiles_x, pad; double n, scale; };
 // noise_var(Q, S, K_t, B_t - 1, (scale N / n_t)^2 K_t)
 // fold, k = 0: c_prev = c_start = c, Q = 0 (tracking starts); k >= 1: a batch of k iterations closes (noise_fold_kernel, kernels_stats.hip)
 void launch_noise_fold(const NoisePlanes &m, const float4 *vpl, const float4 *pm, const StripDev &st, const AdaptTiles &at, int32_t k, hipStream_t s);
+// Non-finite sums (include/evplp.h evplp_noise_track): a pixel is broken when its den or any of its three v = (Q - S^2 / K) / (B - 1) is
+// not finite (an emitter pixel under mask_emitter reads no moments: its den alone).  The rows take a broken pixel's num and rel as NaN --
+// a report says that it is broken; the tile kernels (adaptive_retire, tile_noise) add nothing for it and do not count it -- a decision
+// works around the break; the variance image keeps its bytes (a NaN v reads 0, beyond fp32 reads Inf).
 // rows, per local row: { sum num, sum rel, sum rel over kept pixels, kept pixels } of the variance against the composite rgb (layout as frame_error)
 void launch_noise_rows(const StripDev &st, const NoiseMoments &m, double K, double B, double s2K, const float4 *light, float ls, int mask_emitter,
                        const float *rgb, const uint8_t *keep, RowError *rows, const AdaptTiles &at, hipStream_t s);
 // the variance of every plane pixel, 3 floats each (resolve's layout)
 void launch_noise_variance(const StripDev &st, const NoiseMoments &m, double K, double B, double s2K, float *out_rgb, const AdaptTiles &at, hipStream_t s);
-// evplp_adaptive_retire: every active tile whose mean relative variance over its in-image pixels (noise_rows_kernel's rel, fp64, summed in a
-// fixed tree over the tile's 64 lanes) is <= tau gets the record { n, K, B, 0 } and the snapshot snap = vpl of its pixels
+// evplp_adaptive_retire: every active tile whose mean relative variance over its sound in-image pixels (noise_rows_kernel's rel, fp64, summed
+// in a fixed tree over the tile's 64 lanes) is <= tau gets the record { n, K, B, 0 } and the snapshot snap = vpl of its pixels; a tile
+// without a sound pixel stays active
 void launch_adaptive_retire(const StripDev &st, const NoiseMoments &m, double K, double B, double s2K, const float4 *light, float ls, int mask_emitter,
                             const float *rgb, double tau, int4 *tiles, int32_t tiles_x, int32_t tiles_y, int32_t n, const float4 *vpl, float4 *snap, hipStream_t s);
 
 // evplp_noise_fold in budget mode, one wavefront per tile with k_t = n_t - K_t: k_t == 0 leaves the tile alone; otherwise per pixel and channel
 // D = R - c_prev (fp32), Q += D * D / k_t (fp64, noise_fold_kernel's order), c_prev = R, then lane 0 writes K_t = n_t, B_t += 1
 void launch_noise_fold_budget(const NoisePlanes &m, const StripDev &st, int4 *tiles, const float4 *snap, int32_t ntiles, hipStream_t s);
-// evplp_adaptive_tile_noise: out[tile] = the mean of rel over the tile's in-image pixels as adaptive_retire_kernel forms it (0: no such pixel)
+// evplp_adaptive_tile_noise: out[tile] = the mean of rel over the tile's sound in-image pixels as adaptive_retire_kernel forms it (0: no such pixel)
 void launch_tile_noise(const StripDev &st, const NoiseMoments &m, double K, double B, double s2K, const float4 *light, float ls, int mask_emitter,
                        const float *rgb, const AdaptTiles &at, int32_t ntiles, double *out, hipStream_t s);
 

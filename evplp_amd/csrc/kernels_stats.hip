@@ -17,43 +17,53 @@ __device__ inline void noise_moments(const NoiseMoments &m, size_t i, double q[3
     const float4 a = m.prev[i], b = m.start[i];
     s[0] = (double)__fsub_rn(a.x, b.x); s[1] = (double)__fsub_rn(a.y, b.y); s[2] = (double)__fsub_rn(a.z, b.z);
 }
-// the variance of one channel of the image scale * c: s2K * max(0, (Q - S * S / K) / (B - 1)), s2K = scale^2 * K
-__device__ inline double noise_var(double q, double s, double K, double B1, double s2K) {
-    const double v = __ddiv_rn(__dsub_rn(q, __ddiv_rn(__dmul_rn(s, s), K)), B1);
-    return __dmul_rn(s2K, v > 0.0 ? v : 0.0);
-}
+// v = (Q - S * S / K) / (B - 1) of one channel, before the clamp: not finite when a sum of the pixel is not (Inf - Inf, NaN) or overflowed
+__device__ inline double noise_v(double q, double s, double K, double B1) { return __ddiv_rn(__dsub_rn(q, __ddiv_rn(__dmul_rn(s, s), K)), B1); }
+// the variance of one channel of the image scale * c: s2K * max(0, v), s2K = scale^2 * K.  A NaN v reads 0 (the comparison is false) and
+// +Inf stays: evplp_noise_variance's bytes (include/evplp.h), which the denoiser reads.
+__device__ inline double noise_var_of(double v, double s2K) { return __dmul_rn(s2K, v > 0.0 ? v : 0.0); }
+__device__ inline double noise_var(double q, double s, double K, double B1, double s2K) { return noise_var_of(noise_v(q, s, K, B1), s2K); }
 // the variance of one channel of a RETIRED pixel (tile record r): the tracker's figure at retirement, rescaled to today's composite --
 // noise_var(Q, S, K_t, B_t - 1, s2K_t), s2K_t = ((scale * N) / n_t)^2 * K_t
 __device__ inline double noise_var_retired(double q, double s, const int4 &r, const AdaptTiles &at) {
     const double f = __ddiv_rn(__dmul_rn(at.scale, at.n), (double)r.x);
     return noise_var(q, s, (double)r.y, (double)r.z - 1.0, __dmul_rn(__dmul_rn(f, f), (double)r.y));
 }
-// num of pixel (x, local row l) from its moments (its tile's record: Adapt only): (var_r + var_g) + var_b, fp64
+// num of pixel (x, local row l) from its moments (its tile's record: Adapt only): (var_r + var_g) + var_b, fp64.  sound = every channel's
+// v is finite (the retired form's v for a retired pixel), tested before the clamp and the s2K factor: the clamp would read a NaN v as 0
 template <bool Adapt>
-__device__ inline double noise_num(const double q[3], const double sm[3], double K, double B1, double s2K, const AdaptTiles &at, int l, int x) {
+__device__ inline double noise_num(const double q[3], const double sm[3], double K, double B1, double s2K, const AdaptTiles &at, int l, int x, bool &sound) {
     if constexpr (Adapt) {
         const int4 r = tile_record(at, l, x);
-        if (r.x != 0) return __dadd_rn(__dadd_rn(noise_var_retired(q[0], sm[0], r, at), noise_var_retired(q[1], sm[1], r, at)), noise_var_retired(q[2], sm[2], r, at));
+        if (r.x != 0) {
+            const double f = __ddiv_rn(__dmul_rn(at.scale, at.n), (double)r.x);
+            K = (double)r.y; B1 = (double)r.z - 1.0; s2K = __dmul_rn(__dmul_rn(f, f), (double)r.y);      // (noise_var_retired)
+        }
     }
-    return __dadd_rn(__dadd_rn(noise_var(q[0], sm[0], K, B1, s2K), noise_var(q[1], sm[1], K, B1, s2K)), noise_var(q[2], sm[2], K, B1, s2K));
+    const double v0 = noise_v(q[0], sm[0], K, B1), v1 = noise_v(q[1], sm[1], K, B1), v2 = noise_v(q[2], sm[2], K, B1);
+    sound = isfinite(v0) && isfinite(v1) && isfinite(v2);
+    return __dadd_rn(__dadd_rn(noise_var_of(v0, s2K), noise_var_of(v1, s2K)), noise_var_of(v2, s2K));
 }
-// A tile's rel, summed: lane = pixel (x, local row l).  The lane forms noise_rows_kernel's rel (0 outside the image); the sum over the 64
-// lanes is a fixed tree (shuffle-down by 32, 16, .. 1) and so is the count of in-image pixels; every lane returns lane 0's pair.
+// A tile's rel, summed: lane = pixel (x, local row l).  The lane forms noise_rows_kernel's rel (0 outside the image, and 0 for a broken pixel:
+// a decision works around the break); the sum over the 64 lanes is a fixed tree (shuffle-down by 32, 16, .. 1) and so is the count of sound
+// in-image pixels; every lane returns lane 0's pair.
 template <bool Adapt>
 __device__ __forceinline__ void tile_rel_sum(const StripDev &st, const NoiseMoments &m, double K, double B1, double s2K, const float4 *light, float ls,
                                              int mask_emitter, const float *rgb, const AdaptTiles &at, int x, int l, double &rel, double &cnt) {
     const bool in = x < st.W && l < st.local_rows && st.global_row(l) < st.H;
-    rel = 0.0; cnt = in ? 1.0 : 0.0;
+    rel = 0.0; cnt = 0.0;
     if (in) {
         const size_t i = (size_t)l * st.W + x;
         double num = 0.0;
+        bool sound = true;
         if (!(mask_emitter && 0.0f < __fmul_rn(light[i].x, ls))) {
             double q[3], sm[3];
             noise_moments(m, i, q, sm);
-            num = noise_num<Adapt>(q, sm, K, B1, s2K, at, l, x);
+            num = noise_num<Adapt>(q, sm, K, B1, s2K, at, l, x, sound);
         }
         const double r = rgb[3 * i], g = rgb[3 * i + 1], b = rgb[3 * i + 2];
-        rel = __ddiv_rn(num, __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(r, r), __dmul_rn(g, g)), __dmul_rn(b, b)), 0.001));
+        const double den = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(r, r), __dmul_rn(g, g)), __dmul_rn(b, b)), 0.001);
+        if (sound && isfinite(den)) { rel = __ddiv_rn(num, den); cnt = 1.0; }       // (a broken pixel adds nothing and is not counted)
     }
     for (int off = 32; off > 0; off >>= 1) { rel = __dadd_rn(rel, __shfl_down(rel, off, 64)); cnt = __dadd_rn(cnt, __shfl_down(cnt, off, 64)); }
     rel = __shfl(rel, 0, 64); cnt = __shfl(cnt, 0, 64);
@@ -222,7 +232,8 @@ void launch_noise_pool(const NoiseMoments &src, bool first, double *q, double *s
 
 // evplp_noise_estimate: one workgroup per local row, the reduction of frame_error_kernel (reduce_row).  Per pixel, fp64:
 // var_ch = noise_var(..) (0 on an emitter pixel under mask_emitter: 0 < light.x * ls), num = (var_r + var_g) + var_b,
-// den = ((r * r + g * g) + b * b) + 0.001 of the composite, rel = num / den.
+// den = ((r * r + g * g) + b * b) + 0.001 of the composite, rel = num / den.  A broken pixel (include/evplp.h evplp_noise_track: den or one
+// of its three v not finite) has num = rel = NaN: the figures it enters say that they are broken.
 // Adapt: retired pixels with noise_var_retired (noise_num)
 template <bool Adapt>
 __device__ __forceinline__ void noise_rows_body(StripDev st, NoiseMoments m, double K, double B1, double s2K, const float4 *light,
@@ -235,13 +246,15 @@ __device__ __forceinline__ void noise_rows_body(StripDev st, NoiseMoments m, dou
         for (int x = tid; x < st.W; x += kRowThreads) {
             const size_t i = own + x;
             double num = 0.0;
+            bool sound = true;
             if (!(mask_emitter && 0.0f < __fmul_rn(light[i].x, ls))) {
                 double q[3], sm[3];
                 noise_moments(m, i, q, sm);
-                num = noise_num<Adapt>(q, sm, K, B1, s2K, at, l, x);
+                num = noise_num<Adapt>(q, sm, K, B1, s2K, at, l, x, sound);
             }
             const double r = rgb[3 * i], g = rgb[3 * i + 1], b = rgb[3 * i + 2];
             const double den = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(r, r), __dmul_rn(g, g)), __dmul_rn(b, b)), 0.001);
+            if (!(sound && isfinite(den))) num = __builtin_nan("");                 // (a broken pixel says so: num and rel are NaN)
             const double rel = __ddiv_rn(num, den);
             s[0] += num; s[1] += rel;
             if (!keep || keep[top + x]) { s[2] += rel; s[3] += 1.0; }
@@ -296,7 +309,7 @@ void launch_noise_variance(const StripDev &st, const NoiseMoments &m, double K, 
 
 // evplp_adaptive_retire: one wavefront per tile of the context's planes, lane = pixel (x = 8 tx + lane % 8, local row 8 ty + lane / 8).  An
 // active tile's lanes form noise_rows_kernel's rel (0 outside the image); the sum over the 64 lanes is a fixed tree (shuffle-down by 32, 16,
-// .. 1: lane 0 holds it), so is the count of in-image pixels, and mean = sum / count in fp64.  mean <= tau (and a pixel in the image): the
+// .. 1: lane 0 holds it), so is the count of sound in-image pixels, and mean = sum / count in fp64.  mean <= tau (and a sound pixel): the
 // record becomes { n, K, B, 0 } and every plane pixel of the tile copies its VPL_ACCUM into the snapshot.  A tile retired before is left
 // alone.  The decision is the wavefront's own: no atomics.
 __global__ __launch_bounds__(64) void adaptive_retire_kernel(StripDev st, NoiseMoments m, double K, double B1, double s2K, const float4 *light, float ls,

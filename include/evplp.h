@@ -976,7 +976,11 @@ int evplp_set_error_reference(evplp_context *ctx, const float *rgb_top_down, con
  * the order of floatimage.cpp:64-112 (num = |img - ref|^2, rel = num / (|ref|^2 + 0.001), no contraction, a correctly rounded division); they
  * are summed in fp64, one image row at a time in a fixed order, and the rows in image row order on the host: the figures are a function of the
  * frame alone (one context and a group of any block table give the same doubles), not of a float accumulator as in the host evplp_image_*
- * functions.  No reference: EVPLP_ERR_INVALID. */
+ * functions.  No reference: EVPLP_ERR_INVALID.
+ * Non-finite terms PROPAGATE: nothing is clamped or set aside.  A pixel whose composite or reference is Inf or NaN, whose |img - ref|^2 or
+ * |ref|^2 overflows fp32 (a reference of 1e20: num = Inf, den = Inf, rel = NaN), or whose composite is negative under gamma (powf gives
+ * NaN) makes every figure it enters Inf or NaN exactly as the fp32 expression does; the third figure stays finite when the mask keeps
+ * such pixels out. */
 int evplp_frame_error(evplp_context *ctx, float vpl_scale, float photon_scale, float light_scale,
                       int32_t mask_emitter, int32_t gamma, double out[3]);
 
@@ -994,7 +998,19 @@ int evplp_frame_error(evplp_context *ctx, float vpl_scale, float photon_scale, f
  * middle of a run; a second on = 1 starts again).  mask: optional, in evplp_set_error_reference's format (kept pixels of evplp_noise_estimate's
  * third figure).  on = 0 releases everything.  Device memory: 56 B per pixel of the context's planes (W x local_rows: Q 3 x 8 B, c_prev and
  * c_start 16 B each; 8 B more when that pixel count is odd), 1 B per IMAGE pixel with a mask, 32 B per local row.
- * evplp_clear_accumulators and evplp_set_blocks (so also a group's rebalance) start tracking again from the cleared sums: K = B = 0. */
+ * evplp_clear_accumulators and evplp_set_blocks (so also a group's rebalance) start tracking again from the cleared sums: K = B = 0.
+ * Non-finite sums.  A report says that it is broken; a decision works around the break.  A pixel is BROKEN when its den = |composite|^2 +
+ * 0.001 is not finite, or any of its three v = (Q - S^2 / K) / (B - 1) is not finite -- the retired form's v for a retired pixel; v is
+ * tested before the clamp and before the scale^2 * K factor.  An accumulator that is or ever was +Inf, -Inf or NaN at a fold gives such a
+ * v (Inf - Inf, or Q = Inf).  An emitter pixel that mask_emitter hides reads no moments: only its den can break it.
+ *   - Image figures (evplp_noise_estimate, evplp_group_noise_estimate, the technique loops' "noise" block): a broken pixel's num and rel
+ *     are NaN, so every figure it enters is NaN (the third one only when the mask keeps the pixel).  An overflowed accumulator does not
+ *     read as a converged pixel.
+ *   - Tile figures and decisions (evplp_adaptive_tile_noise, evplp_adaptive_retire, their group forms, so evplp_plan_budgets' input): a
+ *     broken pixel adds nothing and is not counted; the tile's figure is the mean over its SOUND in-image pixels, a tile without one
+ *     reads 0 from evplp_adaptive_tile_noise and is never retired.  Sound pixels are unchanged to the bit.
+ *   - evplp_noise_variance keeps its bytes, which evplp_denoise reads: a NaN v reads 0 (the clamp's comparison is false), a variance
+ *     beyond fp32 reads Inf (an infinite v too -- times a scale of exactly 0 that is NaN). */
 int evplp_noise_track(evplp_context *ctx, int32_t on, const uint8_t *mask_rgb8_top_down);
 /* Closes a batch of `iterations` >= 1 accumulating iterations.  It settles the pending photon splat first, as evplp_resolve does, so it sees
  * every splat of its iterations exactly once (a pass re-run after a bins overflow included); then one element-wise pass, in stream order.
@@ -1119,7 +1135,8 @@ int evplp_project_points(const evplp_camera *cam, int32_t W, int32_t H, const fl
  * evplp_adaptive_retire retires an active tile when the noise tracker has closed B >= min_batches (>= 2) batches and the mean over the tile's
  * in-image pixels of the per-pixel relative variance -- rel = num / den exactly as evplp_noise_estimate forms it, with the same scale,
  * light_scale, mask_emitter and composite; the mean in fp64, summed in a fixed order (a shuffle-down tree over the tile's 64 lanes, lane =
- * (y % 8) * 8 + x % 8, 0 outside the image; divided by the count of in-image pixels) -- is <= tile_rel_mse.  Retirement is one-way until
+ * (y % 8) * 8 + x % 8, 0 outside the image and for a broken pixel -- evplp_noise_track, "non-finite sums"; divided by the count of sound
+ * in-image pixels; a tile without one is not retired) -- is <= tile_rel_mse.  Retirement is one-way until
  * the next clear: the tile records n_t = N and the tracker's K_t = K and B_t = B, and snapshots R = VPL_ACCUM of its pixels.  It settles
  * the pending photon splat first, as a fold does.  Returns the number of tiles this call retired (>= 0).
  * Later accumulating gathers skip a retired tile's items; the reduce writes VPL_ACCUM = (float)((double)R * ((double)(N + 1) / (double)n_t))
@@ -1216,10 +1233,12 @@ int evplp_adaptive_budgets(evplp_context *ctx, int32_t *samples_per_image_tile, 
  *  - A calibration frame (evplp_calibrate_blocks) walks every tile, as under on = 1; the reduce still follows the schedule. */
 int evplp_adaptive_budget_window(evplp_context *ctx, int32_t window);
 /* The per-tile mean of rel exactly as evplp_adaptive_retire forms it (the same lanes, the same shuffle-down tree, divided by the count of
- * in-image pixels), written out instead of compared with a threshold: a tile evplp_adaptive_retire(.., tau, ..) would retire is one whose
- * figure here is <= tau, the same doubles.  All three adaptive modes; in modes 0 and 1 a tile retired earlier reports its frozen figure.
- * Tiles another rank owns and tiles without an in-image pixel: 0.  Returns the number of tiles.  Refused with adaptivity or tracking off, or
- * with fewer than two folds. */
+ * sound in-image pixels), written out instead of compared with a threshold: a tile evplp_adaptive_retire(.., tau, ..) would retire is one
+ * whose figure here is <= tau, the same doubles -- except a tile without a sound pixel, which reads 0 here and is never retired.  All three
+ * adaptive modes; in modes 0 and 1 a tile retired earlier reports its frozen figure.  A broken pixel (evplp_noise_track, "non-finite sums")
+ * adds nothing and is not counted, so the figures are finite and >= 0 for evplp_plan_budgets whatever single pixels hold.
+ * Tiles another rank owns and tiles without a sound in-image pixel: 0.  Returns the number of tiles.  Refused with adaptivity or tracking
+ * off, or with fewer than two folds. */
 int evplp_adaptive_tile_noise(evplp_context *ctx, float scale, float light_scale, int32_t mask_emitter, double *rel_per_image_tile, int32_t capacity);
 /* The planner (host only, no GPU; deterministic: separate processes agree).  rel: evplp_adaptive_tile_noise's figures, n_t:
  * evplp_adaptive_tiles'.  v_t = rel_t * n_t is the tile's per-sample relative variance.  Tiles with n_t <= 0 (not in the image, or

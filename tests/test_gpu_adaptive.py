@@ -13,6 +13,7 @@ import pytest
 
 import scenes
 from test_gpu_convergence import NL, NV, P, H, W, params, room, write_inputs
+from test_gpu_noise import broken_pixels
 
 pytestmark = pytest.mark.gpu
 
@@ -65,31 +66,37 @@ def variance(v, s2K):
     return s2K * np.where(v > 0.0, v, 0.0)
 
 
-def rel_of(var, composite, light, ls=1.0, mask_emitter=False):
+def rel_of(var, composite, light, ls=1.0, mask_emitter=False, v=None):
+    """num and rel per pixel; a broken pixel's are NaN (test_gpu_noise.broken_pixels; v: the moments before the clamp, None = finite)"""
     num = (var[..., 0] + var[..., 1]) + var[..., 2]
+    emitter = np.zeros(num.shape, bool)
     if mask_emitter:
-        num = np.where(np.float32(0.0) < light[..., 0] * np.float32(ls), 0.0, num)
+        emitter = np.float32(0.0) < light[..., 0] * np.float32(ls)
+        num = np.where(emitter, 0.0, num)
     cp = composite.astype(np.float64)
     den = ((cp[..., 0] * cp[..., 0] + cp[..., 1] * cp[..., 1]) + cp[..., 2] * cp[..., 2]) + 0.001
+    num = np.where(broken_pixels(v, den, emitter), np.nan, num)
     return num, num / den
 
 
-def tile_means(rel):
-    """the retire kernel's per-tile mean: lane = (y % 8) * 8 + x % 8, a shuffle-down tree over the 64 lanes, / in-image pixels"""
-    out = np.zeros((TY, TX), np.float64)
-    for ty in range(TY):
-        for tx in range(TX):
+def tile_means(rel, w=W, h=H):
+    """the retire kernel's per-tile mean: lane = (y % 8) * 8 + x % 8, a shuffle-down tree over the 64 lanes, / the tile's sound in-image
+    pixels.  A broken pixel (rel_of: a NaN rel) adds nothing and is not counted; a tile without a sound pixel reads 0."""
+    ty_n, tx_n = (h + 7) // 8, (w + 7) // 8
+    out = np.zeros((ty_n, tx_n), np.float64)
+    for ty in range(ty_n):
+        for tx in range(tx_n):
             lanes = np.zeros(64, np.float64); cnt = np.zeros(64, np.float64)
             for ly in range(8):
                 for lx in range(8):
                     y, x = ty * 8 + ly, tx * 8 + lx
-                    if y < H and x < W:
+                    if y < h and x < w and not np.isnan(rel[y, x]):
                         lanes[ly * 8 + lx] = rel[y, x]; cnt[ly * 8 + lx] = 1.0
             off = 32
             while off:
                 lanes[:off] = lanes[:off] + lanes[off:2 * off]; cnt[:off] = cnt[:off] + cnt[off:2 * off]
                 off //= 2
-            out[ty, tx] = lanes[0] / cnt[0]
+            out[ty, tx] = lanes[0] / cnt[0] if cnt[0] > 0 else 0.0
     return out
 
 
@@ -107,15 +114,17 @@ def tile_mask(retired, w=W, h=H):
     return np.kron(retired, np.ones((8, 8), bool))[:h, :w]
 
 
-def frozen_figures(cs, retire_at, iters, pm, active_var, composite, light):
+def frozen_figures(cs, retire_at, iters, pm, active_var, composite, light, active_v=None):
     """numpy's restatement of tiles retired after `retire_at` of `iters` iterations (cs[j]: the plain run's sums after j iterations, one fold
     per iteration up to the retirement), at the 1 / iters scale, for any frame shape: the frozen variance of every pixel as if its tile had
-    retired, and the three figures of the variance image that is frozen where pm (h, w) says so and active_var elsewhere"""
+    retired, and the three figures of the variance image that is frozen where pm (h, w) says so and active_var elsewhere.  active_v: the
+    active pixels' v before the clamp -- with it a pixel is broken by the retired form's v where pm says so and by active_v elsewhere"""
     s = np.float64(np.float32(1.0 / iters))
     v_t, K_t = moments(cs[:retire_at + 1])
     f = (s * np.float64(iters)) / np.float64(retire_at)
     frozen = variance(v_t, (f * f) * K_t)
-    num, rel = rel_of(np.where(pm[..., None], frozen, active_var), composite, light)
+    v = None if active_v is None else np.where(pm[..., None], v_t, active_v)
+    num, rel = rel_of(np.where(pm[..., None], frozen, active_var), composite, light, v=v)
     return frozen, (num.sum() / num.size, rel.sum() / num.size, rel.sum() / num.size)
 
 

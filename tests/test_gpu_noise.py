@@ -42,8 +42,10 @@ def sums(evplp, c):
     return (c.download(evplp.BUF_VPL_ACCUM)[..., :3] + c.download(evplp.BUF_PHOTON_ACCUM)[..., :3]).astype(np.float32)
 
 
-def numpy_variance(cs, schedule, scale):
-    """cs[j]: the sums after j iterations (cs[0] where tracking started); the variance image of scale * c (fp64) and K, B"""
+def numpy_variance(cs, schedule, scale, with_v=False):
+    """cs[j]: the sums after j iterations (cs[0] where tracking started; only the fold boundaries are read, so a dict will do); the variance
+    image of scale * c (fp64).  A NaN v reads 0 and an infinite one stays, as in the library.  with_v: also v = (Q - S^2 / K) / (B - 1) before
+    the clamp, which numpy_figures wants for the rule on broken pixels."""
     prev = cs[0]; q = np.zeros(prev.shape, np.float64); it = 0
     for k in schedule:
         it += k
@@ -54,16 +56,30 @@ def numpy_variance(cs, schedule, scale):
     s = (prev - cs[0]).astype(np.float32).astype(np.float64)
     v = (q - s * s / K) / (B - 1.0)
     s2K = np.float64(np.float32(scale)) ** 2 * K                 # (the library takes the scale as a float)
-    return s2K * np.where(v > 0.0, v, 0.0)
+    var = s2K * np.where(v > 0.0, v, 0.0)
+    return (var, v) if with_v else var
 
 
-def numpy_figures(var, composite, light, ls, mask_emitter, mask_top_down=None):
-    """var (H, W, 3) fp64 and composite (H, W, 3) fp32 as resolve() returns it (y = 0 at the bottom)"""
+def broken_pixels(v, den, emitter):
+    """include/evplp.h, "non-finite sums": a pixel is broken when its den is not finite or any of its three v is not (v = None: the caller
+    vouches for finite moments); a pixel that mask_emitter hides reads no moments, so only its den can break it"""
+    broken = ~np.isfinite(den)
+    if v is not None:
+        broken = broken | (~np.isfinite(v).all(-1) & ~emitter)
+    return broken
+
+
+def numpy_figures(var, composite, light, ls, mask_emitter, mask_top_down=None, v=None):
+    """var (H, W, 3) fp64 and composite (H, W, 3) fp32 as resolve() returns it (y = 0 at the bottom); v: numpy_variance(.., with_v=True)'s.
+    A broken pixel's num and rel are NaN: an image figure says that it is broken."""
     num = (var[..., 0] + var[..., 1]) + var[..., 2]
+    emitter = np.zeros(num.shape, bool)
     if mask_emitter:
-        num = np.where(np.float32(0.0) < light[..., 0] * np.float32(ls), 0.0, num)
+        emitter = np.float32(0.0) < light[..., 0] * np.float32(ls)
+        num = np.where(emitter, 0.0, num)
     cp = composite.astype(np.float64)
     den = ((cp[..., 0] * cp[..., 0] + cp[..., 1] * cp[..., 1]) + cp[..., 2] * cp[..., 2]) + 0.001
+    num = np.where(broken_pixels(v, den, emitter), np.nan, num)
     rel = num / den
     keep = np.ones(num.shape, bool) if mask_top_down is None else mask_top_down[::-1].any(-1)
     kept = int(keep.sum())
