@@ -1212,7 +1212,9 @@ class Context:
         (mismatches, cases, hits, then the hits of classes 0|1, 2|3, 4|5 packed 32 bits each), 3 the in-place visit of a synthetic
         node of an entry cut against the scalar-operand node visit (differences, cases, entered lanes, then the entered lanes of
         classes 0|1, 2|3, 4|5 packed 32 bits each), 4 the hardware primitives of the VSL estimators against double precision, maxima
-        in units of 1e-12 (absolute: v_sin, v_cos, the Phong samples' cos_t; relative: v_rcp, v_rsq, v_sqrt)"""
+        in units of 1e-12 (absolute: v_sin, v_cos, the Phong samples' cos_t; relative: v_rcp, v_rsq, v_sqrt), 5 the whole hand-written
+        packet walk against the C++ walk for eight patterns of live lanes (mismatches, cases, occluded lanes, then the occluded lanes of
+        classes 0-2, 3-5, 6-7 packed 21 bits each)"""
         out = np.zeros(8, dtype=np.uint64)
         n = self._check(self._lib.evplp_selftest(self._h, which, _ptr(out), 8))
         return out[:n]

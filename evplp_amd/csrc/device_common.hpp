@@ -594,6 +594,26 @@ constexpr int kWalkKernelVgprs = kWalkAsm ? 50 : 0;
         "v_cmp_lt_f32 " M1 ", " T3H ", " T0H "\n\t" \
         EV_VISIT_DECIDE_TEXT(C0, C1, M1, T64, P0, P1)
 
+// EXEC = the live lanes.  Both statements of the walk (EV_SYN_VISIT_ASM_, EV_WALK_LOOP_ASM) open with s_mov_b64 exec, alive, and the leaf
+// step sets EXEC again whenever it has taken lanes out of `alive`: a lane whose ray is occluded, or that never had one, executes none
+// of the walk's vector instructions (it used to carry +inf origin terms through all of them).  Control flow is the same bit for bit:
+// v_cmp_* writes 0 for a lane outside EXEC, which is what the +inf terms made the slab test give, and the pair test's hit masks were
+// and-ed with `alive` already -- so the entered-lane masks, the popcount order, pushes and pops are those of occluded_wave_ref.
+// * v_writelane_b32 / v_readlane_b32 (the stack) ignore EXEC: ISA, VOP3 lane instructions.
+// * v_readfirstlane_b32 reads the first ACTIVE lane: the synthetic node's LDS reads give every active lane the same bits (one address),
+//   and EXEC != 0 in both statements -- occluded_wave returns before them when `alive` is empty, and a walk whose last lane is occluded
+//   ends the cut (syn is moved past every end) without visiting again.
+// * Hazards: a scalar write of EXEC needs no wait state before a VALU instruction, a ds_read or a lane read on this part (the table of
+//   required software states lists only VALU writes of EXEC -- v_cmpx, v_readlane's data hazards -- none of which occur here); the compiler
+//   itself follows s_and_saveexec / s_mov exec with them directly.  profiles/walk_live_lanes_isa.txt has the notes.
+// * Every statement ends with s_mov_b64 exec, -1: the compiler does not know EXEC changed, and what it emits between the statements
+//   (the cut loop, the parking of scalars in VGPR lanes) must see the EXEC it assumed.  -1 and not a saved pair, which would cost two
+//   scalar registers across the walk: the walk kernels are single-wavefront workgroups of 64 threads (launch_bounds(64), launched with
+//   64), and every branch in front of occluded_wave is wave-uniform -- the grid padding and the retired-tile return of the ADAPT
+//   variants are per item, the COST variants add only a clock read, the loops run over scalar counts, `continue` follows a ballot, and
+//   gather_vsl_walk_kernel's `if (ballot64(pre) != 0)` is a ballot too -- so EXEC is all ones wherever a statement starts.  A caller under
+//   a divergent branch would need the saved pair.
+
 // The visit of a SYNTHETIC node of an entry cut, in place (through fourteen v_readfirstlane into scalar registers and then visited
 // like a fetched node it cost twelve lane-to-scalar moves per visit for operands v_pk_fma_f32 reads from vector registers just as
 // well: profiles/syn_visit_isa.txt, syn_visit_speed.txt).  One statement that does its own LDS reads -- `addr` = the byte address of
@@ -614,6 +634,7 @@ constexpr int kWalkKernelVgprs = kWalkAsm ? 50 : 0;
 // (TAIL: text behind the visit -- empty in the walk; evplp_selftest(3) copies the first mask out of vcc there)
 #define EV_SYN_VISIT_ASM_(TAIL)                                                                                                            \
     asm volatile(                                                                                                                            \
+        "s_mov_b64 exec, %[alive]\n\t"                                                                                                \
         "ds_read_b64 v[50:51], %[addr] offset:48\n\t"                                                                                 \
         "ds_read_b128 v[52:55], %[addr]\n\t"                                                                                          \
         "ds_read_b128 v[56:59], %[addr] offset:16\n\t"                                                                                \
@@ -641,9 +662,10 @@ constexpr int kWalkKernelVgprs = kWalkAsm ? 50 : 0;
         "v_cmp_lt_f32 %[m1], v51, v53\n\t"                                                                                                   \
         EV_VISIT_DECIDE_TEXT("%[c0]", "%[c1]", "%[m1]", "%[t64]", "%[p0]", "%[p1]")                                                          \
         TAIL                                                                                                                                 \
+        "s_mov_b64 exec, -1\n"                                                                                                              \
         : [cur] "+s"(cur), [sp] "+s"(sp), [vstack] "+v"(vstack), [m1] "=&s"(m1_), [t64] "=&s"(t64_), [p0] "=&s"(p0_), [p1] "=&s"(p1_),         \
           [c0] "=&s"(c0_), [c1] "=&s"(c1_)                                                                                                   \
-        : [addr] "v"(syn_addr_), [pa] "v"(pa_), [pb] "v"(pb_), [pc] "v"(pc_), [pd] "v"(pd_), [pe] "v"(pe_)                                   \
+        : [addr] "v"(syn_addr_), [pa] "v"(pa_), [pb] "v"(pb_), [pc] "v"(pc_), [pd] "v"(pd_), [pe] "v"(pe_), [alive] "s"(alive)               \
         : "vcc", "scc", "m0", "memory", "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63")
 
 // The walk below one entry (the root, or what a synthetic node let in) as ONE hand-written statement.  What the compiler made of the leaf
@@ -659,8 +681,8 @@ constexpr int kWalkKernelVgprs = kWalkAsm ? 50 : 0;
 //   reciprocal, fill three of the eight wait states of the den -> rcp -> refinement chain (a packed or transcendental result is not
 //   read by the very next instruction: the compiler pads these, the other five stay s_nop).  40 vector instructions and 5 s_nop.
 // * the bookkeeping: hm = any & alive; none -> pop.  Otherwise alive &= ~hm (the lane's answer is read from alive behind the walk: no
-//   second mask); nobody left -> done, and the cut at its end; else the newly occluded lanes get the dead origin terms (under their own
-//   exec mask) and the walk pops.
+//   second mask); nobody left -> done, and the cut at its end; else the newly occluded lanes leave EXEC (EXEC = alive, below) and the
+//   walk pops.
 // * pair B of a three- or four-triangle leaf is neither fetched nor tested when pair A has occluded every live lane (any-hit).
 // Inline-asm operands cannot name the halves of a register tuple and a statement takes at most 30 operands, so the node / leaf tuples and
 // the scalar temporaries are FIXED registers s31 and s[32:65], named in the clobber list (the compiler's loop held 32 scalar registers of tuples
@@ -724,6 +746,7 @@ constexpr int kWalkKernelVgprs = kWalkAsm ? 50 : 0;
         "s_and_b64 " HB ", " HB ", vcc\n\t"
 #define EV_WALK_LOOP_ASM(T0, T1, T2, T3, T4, T5, T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H)                                 \
     asm volatile(                                                                                                                            \
+        "s_mov_b64 exec, %[alive]\n\t"                                                                                                       \
         "s_cmp_lt_i32 %[cur], 0\n\t"                                                                                                         \
         "s_cbranch_scc1 L_leaf%=\n"                                                                                                          \
         "L_node%=:\n\t"                                                                                                                      \
@@ -762,12 +785,7 @@ constexpr int kWalkKernelVgprs = kWalkAsm ? 50 : 0;
         "s_cbranch_scc0 L_lpop%=\n\t"                                                                                                        \
         "s_andn2_b64 %[alive], %[alive], s[64:65]\n\t"                                                                                       \
         "s_cbranch_scc0 L_alldead%=\n\t"                                                                                                        \
-        "v_mov_b32 " T0L ", 0x7f800000\n\t"                                                                                                  \
-        "v_mov_b32 " T0H ", 0x7f800000\n\t"                                                                                                  \
-        "s_and_saveexec_b64 vcc, s[64:65]\n\t"                                                                                                \
-        "v_mov_b64 %[pd], " T0 "\n\t"                                                                                                        \
-        "v_mov_b64 %[pe], " T0 "\n\t"                                                                                                        \
-        "s_mov_b64 exec, vcc\n"                                                                                                              \
+        "s_mov_b64 exec, %[alive]\n"                                                                                                        \
         "L_lpop%=:\n\t"                                                                                                                      \
         "s_cmp_eq_u32 %[sp], 0\n\t"                                                                                                          \
         "s_cbranch_scc1 L_empty%=\n\t"                                                                                                       \
@@ -783,10 +801,10 @@ constexpr int kWalkKernelVgprs = kWalkAsm ? 50 : 0;
         "s_mov_b32 %[syn], -1\n"                                                                                                             \
         "L_empty%=:\n\t"                                                                                                                     \
         "s_brev_b32 %[cur], 1\n"                                                                                                             \
-        "L_done%=:\n"                                                                                                                      \
-        : [cur] "+s"(cur), [sp] "+s"(sp), [vstack] "+v"(vstack), [alive] "+s"(alive), [pd] "+v"(pd_), [pe] "+v"(pe_),     \
-          [syn] "+s"(syn)                                                                                                                    \
-        : [nodes] "s"(node_base), [leaves] "s"(leaf_base), [pa] "v"(pa_), [pb] "v"(pb_), [pc] "v"(pc_),                                      \
+        "L_done%=:\n\t"                                                                                                                   \
+        "s_mov_b64 exec, -1\n"                                                                                                              \
+        : [cur] "+s"(cur), [sp] "+s"(sp), [vstack] "+v"(vstack), [alive] "+s"(alive), [syn] "+s"(syn)                                        \
+        : [nodes] "s"(node_base), [leaves] "s"(leaf_base), [pa] "v"(pa_), [pb] "v"(pb_), [pc] "v"(pc_), [pd] "v"(pd_), [pe] "v"(pe_),        \
           [ra] "v"(ra_), [rb] "v"(rb_), [rc] "v"(rc_), [tmin] "s"(tmin), [tmax] "s"(tmax)                                                    \
         : "vcc", "scc", "m0", "memory", T0L, T0H, T1L, T1H, T2L, T2H, T3L, T3H, T4L, T4H, T5L, T5H,                                          \
           "s32", "s33", "s34", "s35", "s36", "s37", "s38", "s39", "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", \
@@ -823,7 +841,7 @@ template <bool CUT>
 EV_DEV bool occluded_wave(const char *node_base, const char *leaf_base, V3 o, V3 d, float tmin, float tmax, bool alive_lane, const float4 *cut_lds, uint32_t syn0) {
     // All control state is wave-uniform (SGPRs): `alive` is a 64-bit lane mask, `cur` the node reference, `sp` the stack pointer.
     // Per-lane registers hold only the ray: 1/d and -o/d for the slab tests (in the segment's own parameter, see occluded_wave_ref;
-    // a lane without a live ray carries +inf as its origin term and never enters a box), d and o for the triangle pairs.
+    // a lane without a live ray is outside EXEC while a statement runs and never enters a box), d and o for the triangle pairs.
     unsigned long long alive = ballot64(alive_lane);
     if (alive == 0ull) return false;
     // `syn` walks over the slot's synthetic nodes, `syn_end` is their count.  The count is looked at BEFORE the ray is set up: every
@@ -841,15 +859,15 @@ EV_DEV bool occluded_wave(const char *node_base, const char *leaf_base, V3 o, V3
     const V3 inv0 = v3(safe_rcp(d.x), safe_rcp(d.y), safe_rcp(d.z));
     const float ku = 1.0f / (tmax - tmin);
     const V3 inv = inv0 * ku;
-    const float dead = __builtin_inff();
     int sp = 0;
     int vstack = 0;
     int32_t cur = 0;  // root is always an inner node
     // the ray of the node visits: {1/dx, 1/dy} {1/dz, |1/dx|} {|1/dy|, |1/dz|} {-ox/dx, -oy/dy} {-oz/dz, -}
     v2f pa_, pb_, pc_, pd_, pe_;
     pa_.x = inv.x; pa_.y = inv.y; pb_.x = inv.z; pb_.y = fabsf(inv.x); pc_.x = fabsf(inv.y); pc_.y = fabsf(inv.z);
-    pd_.x = alive_lane ? (-(o.x * inv0.x) - tmin) * ku : dead; pd_.y = alive_lane ? (-(o.y * inv0.y) - tmin) * ku : dead;
-    pe_.x = alive_lane ? (-(o.z * inv0.z) - tmin) * ku : dead; pe_.y = pe_.x;
+    // (every lane's own terms: a lane without a live ray is not in EXEC while a statement runs, what it holds is never read)
+    pd_.x = (-(o.x * inv0.x) - tmin) * ku; pd_.y = (-(o.y * inv0.y) - tmin) * ku;
+    pe_.x = (-(o.z * inv0.z) - tmin) * ku; pe_.y = pe_.x;
     // the ray of the pair test: {dx, dy} {dz, ox} {oy, oz}
     v2f ra_, rb_, rc_;
     ra_.x = d.x; ra_.y = d.y; rb_.x = d.z; rb_.y = o.x; rc_.x = o.y; rc_.y = o.z;

@@ -262,8 +262,9 @@ EV_DEV void fetch_vpl_tail(const evplp_record *vpls, uint32_t i, Vpl &v) {
     v.rd = v3(f_of(rb[8]), f_of(rb[9]), f_of(rb[10])); v.rs = v3(f_of(rb[12]), f_of(rb[13]), f_of(rb[14])); v.e = f_of(rb[15]);
 }
 
-#if EVPLP_GATHER_TIMES       // developer build (tools/gather_times.py): start / end clock (100 MHz) of every 16th item's wavefront
-__device__ unsigned long long g_gather_times[2 * 131072];
+#if EVPLP_GATHER_TIMES       // developer build (tools/gather_times.py): start / end clock (100 MHz) of every 16th item's wavefront, then,
+// in the second half of the buffer, the same item's start / end shader clock (s_memtime): their ratio is the clock the chip held
+__device__ unsigned long long g_gather_times[4 * 131072];
 extern "C" int evplp_debug_gather_times(unsigned long long *out, int n) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_gather_times), sizeof(unsigned long long) * (size_t)n); }
 #endif
 // One item = (tile, group of splits_per_wave consecutive splits): lane = pixel.
@@ -279,7 +280,7 @@ __global__ __launch_bounds__(64, EVPLP_GATHER_WAVES) void gather_vpl_kernel(Gath
     unsigned long long t_cost = 0ull;
     if constexpr (COST) t_cost = __builtin_amdgcn_s_memrealtime();
 #if EVPLP_GATHER_TIMES
-    const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
+    const unsigned long long t_start = __builtin_amdgcn_s_memrealtime(), c_start = __builtin_amdgcn_s_memtime();
 #endif
     // dynamic LDS: [192] the view directions, then one [192] block per level of the k-split fold (log2 k of them: the top level, which the
     // last split would store, is never read back -- see the fold below -- and has no block).  Sized by k
@@ -487,7 +488,11 @@ __global__ __launch_bounds__(64, EVPLP_GATHER_WAVES) void gather_vpl_kernel(Gath
     if (lane == 0) atomicMax(&a.counters->hist[16 + (blockIdx.x & 7u)], (unsigned long long)__builtin_amdgcn_s_memrealtime());
 #endif
 #if EVPLP_GATHER_TIMES
-    if (lane == 0 && (blockIdx.x & 15u) == 0u && (blockIdx.x >> 4) < 131072u) { g_gather_times[2 * (blockIdx.x >> 4)] = t_start; g_gather_times[2 * (blockIdx.x >> 4) + 1] = __builtin_amdgcn_s_memrealtime(); }
+    if (lane == 0 && (blockIdx.x & 15u) == 0u && (blockIdx.x >> 4) < 131072u) {
+        const unsigned long long c_end = __builtin_amdgcn_s_memtime();
+        g_gather_times[2 * (blockIdx.x >> 4)] = t_start; g_gather_times[2 * (blockIdx.x >> 4) + 1] = __builtin_amdgcn_s_memrealtime();
+        g_gather_times[2 * 131072 + 2 * (blockIdx.x >> 4)] = c_start; g_gather_times[2 * 131072 + 2 * (blockIdx.x >> 4) + 1] = c_end;
+    }
 #endif
     // per-lane statistics ride in the unused fourth component: shadow rays | unoccluded pairs << 16 (both < 65536 per item)
     int lane_out = lane, blk_out = (int)blockIdx.x;

@@ -240,9 +240,11 @@ __attribute__((amdgpu_num_vgpr(50))) __global__ __launch_bounds__(64) void selft
         EV_WITH(EV_WALK_VISIT_ASM_, "s", "s_mov_b64 %[t64], vcc\n", EV_TMP_52);
         ref_m0 = t64_; ref_m1 = m1_; ref_cur = cur; ref_sp = sp; ref_stack = vstack;
     }
-    // the subject: the node from LDS, in place
+    // the subject: the node from LDS, in place, with the dead lanes of class 2 outside EXEC as the walk runs it (the reference visit above
+    // keeps EXEC full and relies on their +inf origin terms: the same masks either way)
     unsigned long long got_m0, got_m1; int32_t got_cur; int got_sp, got_stack;
     {
+        const unsigned long long alive = ballot64(alive_lane);
         const uint32_t syn_addr_ = lds_offset(&s_node[0]);
         unsigned long long m1_, t64_; int32_t p0_, p1_, c0_, c1_;
         int32_t cur = 0; int sp = sp0, vstack = vstack0;
@@ -258,6 +260,95 @@ __attribute__((amdgpu_num_vgpr(50))) __global__ __launch_bounds__(64) void selft
         atomicAdd(&out[1], 128ull);
         atomicAdd(&out[2], entered);
         atomicAdd(&out[3 + cls / 2u], entered << (32u * (cls & 1u)));
+    }
+}
+
+// which = 5: the whole hand-written walk (device_common.hpp occluded_wave<false>: EV_WALK_LOOP_ASM with EXEC = the live lanes) against the C++
+// walk (occluded_wave_ref<false>, full EXEC and +inf origin terms) on the same packet, one after the other: kWalkTestPackets packets of 64
+// rays with a shared origin through a tree generated here from a fixed seed -- a complete binary tree over kWalkTestLeaves leaves of 1 - 4
+// small triangles, one leaf per cell of an 8 x 8 x 4 grid over [-1, 1]^3 in Morton order, 255 inner nodes.  The lanes that start alive, by
+// class (packet index mod 8):
+//   0 all 64        2 lanes 32-63 (0-31 dead)     4 only lane 63     6 a random quarter
+//   1 all but 0     3 lanes 0-31 (32-63 dead)     5 only lane 0      7 none (both walks return at once)
+// out[0] lanes whose answers differ + lanes missing from EXEC behind the walk (must be 0), out[1] cases (lanes), out[2] occluded lanes (the C++
+// walk's), out[3] / [4] / [5] = those of classes 0 | 1 << 21 | 2 << 42, 3 | 4 << 21 | 5 << 42, 6 | 7 << 21.
+constexpr uint32_t kWalkTestLeaves = 256u, kWalkTestPackets = 4096u;
+EV_DEV uint32_t wt_leaf_count(uint32_t leaf) { return (uint32_t)(splitmix64(0x1eafull * 0x10001ull + leaf) >> 62) + 1u; }
+__global__ __launch_bounds__(256) void selftest_walk_gen_kernel(float *nodes, float *leaves) {
+    __shared__ float s_lo[2u * kWalkTestLeaves - 1u][3], s_hi[2u * kWalkTestLeaves - 1u][3];
+    const uint32_t k = threadIdx.x;                     // leaf k = heap node kWalkTestLeaves - 1 + k
+    {
+        uint32_t cell[3] = { 0u, 0u, 0u };
+        for (uint32_t bit = 0; bit < 8u; bit++) { const uint32_t ax = bit < 6u ? bit % 3u : bit - 6u; cell[ax] |= ((k >> bit) & 1u) << (bit < 6u ? bit / 3u : 2u); }      // (x, y: three bits, z: two)
+        const float ctr[3] = { -1.0f + ((float)cell[0] + 0.5f) * 0.25f, -1.0f + ((float)cell[1] + 0.5f) * 0.25f, -1.0f + ((float)cell[2] + 0.5f) * 0.5f };
+        const uint32_t cnt = wt_leaf_count(k);
+        uint64_t st = 0x7417ull * 0x10001ull + k;
+        float blk[48];
+        for (int q = 0; q < 48; q++) blk[q] = 0.0f;       // an empty slot is all zeros: never a hit
+        float lo[3] = { 3.0e38f, 3.0e38f, 3.0e38f }, hi[3] = { -3.0e38f, -3.0e38f, -3.0e38f };
+        for (uint32_t j = 0; j < cnt; j++) {
+            float v[9];
+            for (int q = 0; q < 3; q++) v[q] = ctr[q] + (pt_uniform(st) - 0.5f) * 0.2f;
+            for (int q = 3; q < 9; q++) v[q] = v[q % 3] + (pt_uniform(st) - 0.5f) * 0.4f;
+            // (evplp_build_accel's precompute_tri: e0 = p1 - p0, e1 = p0 - p2, n = cross(e1, e0))
+            float e0[3], e1[3];
+            for (int q = 0; q < 3; q++) { e0[q] = v[3 + q] - v[q]; e1[q] = v[q] - v[6 + q]; }
+            const float n[3] = { e1[1] * e0[2] - e1[2] * e0[1], e1[2] * e0[0] - e1[0] * e0[2], e1[0] * e0[1] - e1[1] * e0[0] };
+            float *pr = blk + 24u * (j >> 1); const uint32_t h = j & 1u;
+            for (int q = 0; q < 3; q++) { pr[2 * q + h] = v[q]; pr[6 + 2 * q + h] = e0[q]; pr[12 + 2 * q + h] = e1[q]; pr[18 + 2 * q + h] = n[q]; }
+            for (int q = 0; q < 9; q++) { lo[q % 3] = fminf(lo[q % 3], v[q]); hi[q % 3] = fmaxf(hi[q % 3], v[q]); }
+        }
+        for (int q = 0; q < 48; q++) leaves[k * 48u + q] = blk[q];
+        for (int q = 0; q < 3; q++) { s_lo[kWalkTestLeaves - 1u + k][q] = lo[q]; s_hi[kWalkTestLeaves - 1u + k][q] = hi[q]; }
+    }
+    for (uint32_t w = kWalkTestLeaves / 2u; w >= 1u; w >>= 1) {      // the levels bottom-up: w nodes, heap indices w - 1 .. 2 w - 2
+        __syncthreads();
+        if (k < w) {
+            const uint32_t i = w - 1u + k;
+            for (int q = 0; q < 3; q++) { s_lo[i][q] = fminf(s_lo[2u * i + 1u][q], s_lo[2u * i + 2u][q]); s_hi[i][q] = fmaxf(s_hi[2u * i + 1u][q], s_hi[2u * i + 2u][q]); }
+        }
+    }
+    __syncthreads();
+    if (k < kWalkTestLeaves - 1u) {
+        // BvhNode: centres x x y y z z, half-sizes x x y y z z (child 0, child 1 next to each other), the two references, two padding words
+        float *nd = nodes + k * 16u;
+        for (uint32_t e = 0; e < 2u; e++) {
+            const uint32_t ch = 2u * k + 1u + e;
+            for (int q = 0; q < 3; q++) {
+                nd[2 * q + e] = 0.5f * (s_lo[ch][q] + s_hi[ch][q]);
+                nd[6 + 2 * q + e] = 0.5f * (s_hi[ch][q] - s_lo[ch][q]) * 1.00001f + 1.0e-6f;
+            }
+            const int32_t ref = ch < kWalkTestLeaves - 1u ? (int32_t)ch : ~(int32_t)(((ch - (kWalkTestLeaves - 1u)) << 2) | (wt_leaf_count(ch - (kWalkTestLeaves - 1u)) - 1u));
+            nd[12 + e] = __int_as_float(ref);
+        }
+        nd[14] = 0.0f; nd[15] = 0.0f;
+    }
+}
+__attribute__((amdgpu_num_vgpr(50))) __global__ __launch_bounds__(64) void selftest_walk_kernel(const float *nodes, const float *leaves, unsigned long long *out) {
+    const uint32_t packet = blockIdx.x, lane = threadIdx.x & 63u, cls = packet & 7u;
+    const char *node_base = reinterpret_cast<const char *>(nodes), *leaf_base = reinterpret_cast<const char *>(leaves);
+    // the packet: a shared origin in or around the grid, every lane's end point about a common target inside it
+    uint64_t st = 0x9ac7ull * 0x10001ull + packet;
+    const V3 o = v3(3.0f * pt_uniform(st) - 1.5f, 3.0f * pt_uniform(st) - 1.5f, 3.0f * pt_uniform(st) - 1.5f);
+    const V3 q = v3(2.0f * pt_uniform(st) - 1.0f, 2.0f * pt_uniform(st) - 1.0f, 2.0f * pt_uniform(st) - 1.0f);
+    uint64_t sl = 0xa11ull * 0x10001ull + (uint64_t)packet * 64u + lane;
+    const float ux = pt_uniform(sl) - 0.5f, uy = pt_uniform(sl) - 0.5f, uz = pt_uniform(sl) - 0.5f;
+    const V3 d = v3((q.x + 0.8f * ux) - o.x, (q.y + 0.8f * uy) - o.y, (q.z + 0.8f * uz) - o.z);
+    sl = splitmix64(sl);
+    const bool alive_lane = cls == 0u ? true : cls == 1u ? lane != 0u : cls == 2u ? lane >= 32u : cls == 3u ? lane < 32u : cls == 4u ? lane == 63u :
+                            cls == 5u ? lane == 0u : cls == 6u ? (sl >> 62) == 0ull : false;
+    const float tmin = 0.0001f, tmax = 1.0f - 0.0001f;
+    const bool got = occluded_wave<false>(node_base, leaf_base, o, d, tmin, tmax, alive_lane, nullptr, 0u);
+    const unsigned long long exec_after = ballot64(true);               // every statement of the walk hands EXEC back full
+    const bool ref = occluded_wave_ref<false>(node_base, leaf_base, o, d, tmin, tmax, alive_lane, nullptr, nullptr, 0u);
+    const unsigned long long diff = ballot64(got != ref), occ = ballot64(ref);
+    if (lane == 0u) {
+        const unsigned long long bad = (unsigned long long)(__builtin_popcountll(diff) + __builtin_popcountll(~exec_after));
+        const unsigned long long n_occ = (unsigned long long)__builtin_popcountll(occ);
+        if (bad) atomicAdd(&out[0], bad);
+        atomicAdd(&out[1], 64ull);
+        atomicAdd(&out[2], n_occ);
+        atomicAdd(&out[3 + cls / 3u], n_occ << (21u * (cls % 3u)));
     }
 }
 
@@ -329,7 +420,7 @@ extern "C" int evplp_debug_ev_math(evplp_context *c, int32_t which, const float 
 }
 
 extern "C" int evplp_selftest(evplp_context *c, int32_t which, uint64_t *out, int32_t capacity) {
-    if (!c || !out || capacity < 6 || which < 0 || which > 4) { if (c) c->set_error("evplp_selftest: bad arguments"); return EVPLP_ERR_INVALID; }
+    if (!c || !out || capacity < 6 || which < 0 || which > 5) { if (c) c->set_error("evplp_selftest: bad arguments"); return EVPLP_ERR_INVALID; }
     if (hipSetDevice(c->cfg.device) != hipSuccess) return EVPLP_ERR_HIP;
     unsigned long long *d = nullptr;
     if (hipMalloc((void **)&d, 8 * sizeof(unsigned long long)) != hipSuccess) return EVPLP_ERR_OOM;
@@ -347,6 +438,15 @@ extern "C" int evplp_selftest(evplp_context *c, int32_t which, uint64_t *out, in
                 hipLaunchKernelGGL(evplp::selftest_syn_kernel, dim3(evplp::kSynTestNodes), dim3(64), 0, c->stream, recs, d);
                 e = hipStreamSynchronize(c->stream);
                 hipFree(recs);
+            }
+        } else if (which == 5) {
+            float *tree = nullptr;      // 256 node slots of 64 bytes (255 used), then the leaf blocks of 192 bytes
+            e = hipMalloc((void **)&tree, 64u * evplp::kWalkTestLeaves + 192u * evplp::kWalkTestLeaves);
+            if (e == hipSuccess) {
+                hipLaunchKernelGGL(evplp::selftest_walk_gen_kernel, dim3(1), dim3(evplp::kWalkTestLeaves), 0, c->stream, tree, tree + 16u * evplp::kWalkTestLeaves);
+                hipLaunchKernelGGL(evplp::selftest_walk_kernel, dim3(evplp::kWalkTestPackets), dim3(64), 0, c->stream, tree, tree + 16u * evplp::kWalkTestLeaves, d);
+                e = hipStreamSynchronize(c->stream);
+                hipFree(tree);
             }
         } else {
             evplp::PairTestRec *recs = nullptr;

@@ -1341,6 +1341,11 @@ int evplp_accel_stack_entries(const evplp_context *ctx);
  * error of v_sin_f32(u) / v_cos_f32(u) against sin / cos(2 pi u) over all 2^24 uniforms u = (k + 1) 2^-24; [2] the absolute error of
  * cos_t = exp2(log2(u) rcp(e + 1)) against u^(1 / (e + 1)) for e = 0, 0.5, 1, 20, 200, 1000, 10000 over 2^22 uniforms; [3] / [4] / [5] the
  * relative error of v_rcp_f32 / v_rsq_f32 / v_sqrt_f32 over 2^22 arguments in [2^-20, 2^20].
+ * which = 5: the whole hand-written packet walk (EXEC = its live lanes) against the C++ walk on 4096 generated packets of 64 rays with a
+ * common origin through a generated tree (255 nodes, 256 leaves of 1 - 4 triangles), in eight classes of lanes that start alive (all; all
+ * but lane 0; lanes 32-63; lanes 0-31; only lane 63; only lane 0; a random quarter; none): out[0] lanes whose answers differ plus lanes
+ * missing from EXEC behind the walk (must be 0), [1] cases (lanes), [2] occluded lanes, [3] / [4] / [5] those of classes 0 - 2, 3 - 5 and
+ * 6 - 7, 21 bits each, the lowest class in the lowest bits.
  * Returns the number of words written or a negative status. */
 int evplp_selftest(evplp_context *ctx, int32_t which, uint64_t *out, int32_t capacity);
 /* The direction-sampling functions of light tracing (csrc/ev_math.h: evm_sincosf, evm_powf) as the DEVICE computes them, on host arrays of n
